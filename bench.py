@@ -53,7 +53,6 @@ from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent
 sys.path.insert(0, str(ROOT))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")      # before the HIP runtime starts (terra_amd/runtime.py says why): the host_api block's 8 caller threads each own a stream
 
 HBM_PEAK_GBS = 8000.0       # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 VALU_PEAK_GINST = 1024 * 2.4 / 2      # 256 CUs x 4 SIMD-32, a wave64 VALU instruction issues over 2 cycles at 2.4 GHz (MI355X_MICROARCH.md "Execution model")
@@ -89,7 +88,12 @@ def parse_args(argv=None):
     ap.add_argument("--no-check", action="store_true", help="N > 1: skip that extra pass")
     ap.add_argument("--launch-timeout", type=float, default=900.0, help="seconds the self-started N-rank child may run before its process group is killed (a hung rendezvous must not hang the parent; well below the driver's own 1500 s limit, so that the ranks are gone before the driver kills this parent)")
     ap.add_argument("--master-port", type=int, default=0, help="rendezvous port of the self-started ranks (0 = pick a free one)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps: write the framebuffer the last timed step left (rank 0, the gathered frame "
+                    "when N > 1) as DIR/<name>.npy, float32, at most 64 MB (a fixed, seeded sample of pixels for larger frames), to compare two builds output for output")
+    a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -425,6 +429,42 @@ def roofline(key, st, kernel_ms, lds_resident, world, pmc=None):
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# output dump (--dump-outputs)
+# ------------------------------------------------------------------------------------------------------------------
+
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+DUMP_SAMPLE_SEED = 20240917
+
+
+def dump_outputs(out_dir, fb):
+    """What a caller of terra_amd_render_device receives, as float32 .npy files: pixels (the framebuffer's RGB), accumulated (the running
+    sums, TerraRawIntegrationResult::acc) and samples (the per-pixel sample count; exact in float32 below 2^24). A frame whose arrays exceed
+    DUMP_MAX_BYTES is reduced to a fixed, seeded set of pixels (the same for every run of that frame size), listed in pixel_index.npy (float64)."""
+    import numpy as np
+    from terra_amd import api
+    n = fb.width * fb.height
+    pixels = fb.pixels.cpu().numpy().reshape(n, 3)
+    res = fb.results.cpu().numpy().view(api.RESULT_DTYPE).reshape(n)
+    assert int(res["samples"].max(initial=0)) < (1 << 24), "sample counts beyond float32's exact range"
+    arrays = {"pixels": pixels, "accumulated": res["acc"], "samples": res["samples"].astype(np.float32)}
+    per_pixel = sum(a.itemsize * (a.size // n) for a in arrays.values())
+    room = DUMP_MAX_BYTES - 4096                      # .npy headers: 128 bytes per file
+    sampled = n * per_pixel > room
+    if sampled:
+        k = room // (per_pixel + 8)
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=k, replace=False))
+        arrays = {name: a[idx] for name, a in arrays.items()}
+        arrays["pixel_index"] = idx.astype(np.float64)
+    else:
+        arrays = {name: a.reshape((fb.height, fb.width) + a.shape[1:]) for name, a in arrays.items()}
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", np.ascontiguousarray(a, dtype=np.float64 if name == "pixel_index" else np.float32))
+    return {"dir": str(out_dir), "arrays": {name: list(a.shape) for name, a in arrays.items()}, "sampled": sampled}
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # measurement
 # ------------------------------------------------------------------------------------------------------------------
 
@@ -462,8 +502,9 @@ def setup(args):
     return c
 
 
-def measure(c, d, tree, split, steps, warmup, check=False, prewarm_rect=None):
-    """K timed steps of workload d; returns the measurement (rank 0) incl. per-launch work counters"""
+def measure(c, d, tree, split, steps, warmup, check=False, prewarm_rect=None, dump_dir=""):
+    """K timed steps of workload d; returns the measurement (rank 0) incl. per-launch work counters. dump_dir: rank 0 writes the frame the
+    timed steps left there (dump_outputs) before any untimed launch touches it"""
     from terra_amd import runtime, scenes
     torch, dist, lib, dev = c.torch, c.dist, c.lib, c.dev
     world, rank = c.world, c.rank
@@ -558,6 +599,7 @@ def measure(c, d, tree, split, steps, warmup, check=False, prewarm_rect=None):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     kernel_ms = sum(a.elapsed_time(b) for a, b in ev) / steps
+    dumped = dump_outputs(dump_dir, cur["fb"]) if (dump_dir and rank == 0) else None
     # the work counters (rays, nodes, tests, hits: what the roofline's algorithmic bytes are made of) come from ONE EXTRA, untimed launch with the counters
     # enabled (terra_amd_set_work_counters): they are instrumentation, off by default, and the timed launches above ran without them
     runtime.check(lib.set_work_counters(scene, 1), "terra_amd_set_work_counters")
@@ -605,7 +647,7 @@ def measure(c, d, tree, split, steps, warmup, check=False, prewarm_rect=None):
         fence()
         lib.scene_destroy(scene2)
     ti2 = runtime.TraversalInfo(); runtime.check(lib.traversal_info(scene, C.byref(ti2)))      # after the launches: what the last call actually ran
-    out = {"elapsed": elapsed, "kernel_ms": kernel_ms, "check": ok, "phases": phases, "commit_ms": commit_ms, "split": split,
+    out = {"elapsed": elapsed, "kernel_ms": kernel_ms, "check": ok, "phases": phases, "commit_ms": commit_ms, "split": split, "dumped": dumped,
            "per_launch": {k: v // launches for k, v in st.items() if k != "launches"},
            "traversal": {"fast_tree": bool(ti.fast_tree), "leaf_cull": bool(ti.leaf_cull), "note": ti.note.decode(), "last_call": getattr(ti2, "last_call", None)},
            "lds_resident": bool(ti.lds_resident),
@@ -737,7 +779,7 @@ def main():
     if args.bounces >= 0:
         d.bounces = args.bounces
     integ_name = {0: "simple", 1: "direct", 2: "mis"}.get(d.integrator, str(d.integrator))
-    m = measure(c, d, args.tree, args.sample_split, args.steps, args.warmup, check=args.check or (world > 1 and not args.no_check))
+    m = measure(c, d, args.tree, args.sample_split, args.steps, args.warmup, check=args.check or (world > 1 and not args.no_check), dump_dir=args.dump_outputs)
 
     if rank == 0:
         blk = result_block(d, args.workload, args.tree, m["split"], args.steps, args.warmup, world, m, args.spp, integ_name)
@@ -749,6 +791,8 @@ def main():
                 out[k] = blk[k]
         out["commit_ms"] = blk["commit_ms"]          # terra_scene_commit (host tree build + upload) of this workload, not part of `value`
         out["traversal_note"] = m["traversal"]["note"]
+        if m["dumped"]:
+            out["dump_outputs"] = m["dumped"]
         if m["check"] is not None:
             out["sharded_equals_unsharded"] = m["check"]
         if c.dist_on:

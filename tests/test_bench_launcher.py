@@ -143,3 +143,38 @@ def test_roofline_block_is_recomputable_from_the_committed_pmc_summary():
     hk = bench.pmc_key("cornell_1080p_512spp", "auto", "simple", 8, 0)          # the headline launch's record (bench.DEFAULT_SPLIT = 0 resolves to 8 lanes per pixel for that frame on one GPU)
     head = bench.roofline(hk, pmc[hk]["counters_per_launch"], pmc[hk]["kernel_ms"], True, 1)
     assert head["bound"] == "valu" and 0.6 < head["frac"] < 0.8 and head["pmc_file"] == "profiles/" + f.name
+
+
+def test_dump_outputs_writes_the_framebuffer_and_samples_large_frames(monkeypatch, tmp_path):
+    """--dump-outputs: the framebuffer a caller receives, as float32 .npy files; a frame over the byte budget becomes the same seeded pixel sample every time"""
+    import numpy as np
+    import torch
+    import bench
+    from terra_amd import runtime
+    fb = runtime.DeviceFramebuffer(7, 5, device="cpu")
+    fb.pixels.copy_(torch.arange(7 * 5 * 3, dtype=torch.float32) / 8)
+    res = fb.results.view(torch.float32).view(35, 4)
+    res[:, :3] = torch.arange(35 * 3, dtype=torch.float32).view(35, 3) * 0.5
+    fb.results.view(35, 4)[:, 3] = torch.arange(35, dtype=torch.int32) + 1000
+    info = bench.dump_outputs(tmp_path / "full", fb)
+    assert not info["sampled"] and info["arrays"] == {"pixels": [5, 7, 3], "accumulated": [5, 7, 3], "samples": [5, 7]}
+    px, acc, spp = (np.load(tmp_path / "full" / f"{n}.npy") for n in ("pixels", "accumulated", "samples"))
+    assert px.dtype == acc.dtype == spp.dtype == np.float32
+    assert np.array_equal(px.ravel(), np.arange(105, dtype=np.float32) / 8)
+    assert np.array_equal(acc.ravel(), np.arange(105, dtype=np.float32) * 0.5)
+    assert np.array_equal(spp.ravel(), np.arange(35, dtype=np.float32) + 1000)
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4096 + 10 * (28 + 8))
+    a = bench.dump_outputs(tmp_path / "a", fb); bench.dump_outputs(tmp_path / "b", fb)
+    assert a["sampled"] and a["arrays"]["pixel_index"] == [10] and a["arrays"]["pixels"] == [10, 3]
+    idx = np.load(tmp_path / "a" / "pixel_index.npy")
+    assert idx.dtype == np.float64 and np.array_equal(idx, np.load(tmp_path / "b" / "pixel_index.npy")) and np.all(np.diff(idx) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "samples.npy"), idx.astype(np.float32) + 1000)
+    assert np.array_equal(np.load(tmp_path / "a" / "pixels.npy"), px.reshape(35, 3)[idx.astype(int)])
+    assert sum(f.stat().st_size for f in (tmp_path / "a").glob("*.npy")) <= bench.DUMP_MAX_BYTES
+
+
+def test_steps_must_be_positive():
+    import bench
+    assert bench.parse_args(["--steps", "7"]).steps == 7
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
