@@ -76,7 +76,10 @@ bool gather_to_first ( const std::vector<int>& devices, const std::vector<const 
                 hipError_t e = hipMemcpyAsync ( recv_on_first + off, send[k], counts[k] * sizeof ( float ), hipMemcpyDeviceToDevice, streams[k] );
                 hipEvent_t ev = nullptr;
                 if ( e == hipSuccess && k != 0 ) { e = hipEventCreateWithFlags ( &ev, hipEventDisableTiming ); if ( e == hipSuccess ) e = hipEventRecord ( ev, streams[k] ); if ( e == hipSuccess ) e = hipStreamWaitEvent ( streams[0], ev, 0 ); if ( ev ) ( void ) hipEventDestroy ( ev ); }
-                if ( e != hipSuccess ) { err = std::string ( "rehearsal gather: " ) + hipGetErrorString ( e ); return false; }
+                if ( e != hipSuccess ) {          // no stream left waiting on a half-issued copy: the ones given a copy so far are drained first
+                    for ( size_t j = 0; j <= k; ++j ) ( void ) hipStreamSynchronize ( streams[j] );
+                    err = std::string ( "rehearsal gather: " ) + hipGetErrorString ( e ); return false;
+                }
             }
             off += counts[k];
         }

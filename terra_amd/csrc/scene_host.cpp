@@ -69,7 +69,11 @@ extern "C" void terra_amd_clear_first_error ( void ) {
 // ------------------------------------------------------------------------------
 // device selection
 // ------------------------------------------------------------------------------
+// The device a scene committed from now on lives on, and (g_devices, terra_amd_set_devices) the set it is replicated on: empty = that one device. The set's first
+// device is the scene's primary: it holds the staging frame of terra_render() / terra_amd_render_multi() and receives the gather. Both under g_devices_lock.
+static std::mutex g_devices_lock;
 static int g_device = 0;
+static std::vector<int> g_devices;
 extern "C" int terra_amd_device_count ( void ) {
     int n = 0;
     if ( hipGetDeviceCount ( &n ) != hipSuccess ) return 0;
@@ -79,14 +83,11 @@ extern "C" int terra_amd_set_device ( int device ) {
     int n = terra_amd_device_count();
     if ( device < 0 || device >= n ) return fail ( kTerraAmdErrNoDevice, "device %d not available (%d visible)", device, n );
     HIP_TRY ( hipSetDevice ( device ), kTerraAmdErrNoDevice );
+    std::lock_guard<std::mutex> g ( g_devices_lock );
     g_device = device;
     return 0;
 }
-extern "C" int terra_amd_get_device ( void ) { return g_device; }
-// The devices a scene committed from now on is replicated on (terra_amd_set_devices): empty = the one device above. devices[0] is the scene's primary device: it holds
-// the staging frame of terra_render() / terra_amd_render_multi() and receives the gather.
-static std::mutex g_devices_lock;
-static std::vector<int> g_devices;
+extern "C" int terra_amd_get_device ( void ) { std::lock_guard<std::mutex> g ( g_devices_lock ); return g_device; }
 static std::atomic<int> g_replicas_share_device { 0 };       // TEST HOOK (terra_amd_debug_replicas_share_device)
 extern "C" int terra_amd_debug_replicas_share_device ( int on ) { g_replicas_share_device.store ( on ? 1 : 0 ); return 0; }
 extern "C" int terra_amd_set_devices ( const int* devices, int count ) {
@@ -282,26 +283,54 @@ struct HostLight { uint32_t object; float area; TerraFloat3 power; };
 #define TERRA_SCRATCH_MAX_GB 64                     // most scratch one launch may take from the device's pool (launch_render)
 #endif
 #define TERRA_FAST_STACK_MAX 2048                   // stack entries per ray beyond which the fast tree is not used (its spill space: 4 B x entries x 327,680 resident lanes)
+// A stream on one device and a staging frame there (12 B of pixel + 16 B of running sums per pixel), grown to the largest rectangle rendered through it:
+// a calling thread's (ThreadSlot) and a replica's for terra_amd_render_multi
+struct Staging {
+    int device = -1; hipStream_t stream = nullptr; void* d_pixels = nullptr; void* d_results = nullptr; size_t cap_px = 0;
+    int prepare ( int dev, size_t npx ) {          // `dev` current, a stream on it, room for npx pixels
+        int current = -1;
+        if ( hipGetDevice ( &current ) != hipSuccess || current != dev ) HIP_TRY ( hipSetDevice ( dev ), kTerraAmdErrNoDevice );
+        if ( device != dev ) { if ( device >= 0 ) { release(); HIP_TRY ( hipSetDevice ( dev ), kTerraAmdErrNoDevice ); } device = dev; }
+        if ( !stream ) HIP_TRY ( hipStreamCreateWithFlags ( &stream, hipStreamNonBlocking ), kTerraAmdErrNoDevice );
+        if ( cap_px < npx ) {
+            if ( d_pixels ) ( void ) hipFree ( d_pixels );
+            if ( d_results ) ( void ) hipFree ( d_results );
+            d_pixels = d_results = nullptr; cap_px = 0;
+            HIP_TRY ( hipMalloc ( &d_pixels, npx * 12 ), kTerraAmdErrNoDevice );
+            HIP_TRY ( hipMalloc ( &d_results, npx * 16 ), kTerraAmdErrNoDevice );
+            cap_px = npx;
+        }
+        return 0;
+    }
+    void release() {          // (leaves `device` current)
+        if ( device >= 0 && hipSetDevice ( device ) == hipSuccess ) {
+            if ( stream ) { ( void ) hipStreamSynchronize ( stream ); ( void ) hipStreamDestroy ( stream ); }
+            if ( d_pixels ) ( void ) hipFree ( d_pixels );
+            if ( d_results ) ( void ) hipFree ( d_results );
+        }
+        device = -1; stream = nullptr; d_pixels = d_results = nullptr; cap_px = 0;
+    }
+};
 struct Scene {
     TerraSceneOptions opts, new_opts;
     TerraObject* objects = nullptr; size_t objects_pop = 0, objects_cap = 0;
     bool dirty_objects = true, dirty_lights = true, committed = false, device_ok = false;
     uint64_t frame_seed = 0x5EED0001ull;
-    int device = 0;
     // host mirrors
     std::vector<HostNode> nodes; int max_stack = 1;
     std::vector<HostLight> lights; size_t lights_triangles_count = 0;
     std::vector<uint32_t> first_tri;     // per object
-    // device replica (of the primary device, `device`)
-    DevScene dev; void* d_blob = nullptr; size_t d_bytes = 0;
-    unsigned long long* d_counters = nullptr;
-    // ... and of the other devices of the set the scene was committed for (terra_amd_set_devices): byte copies of the blob with the pointers rebased
-    struct Replica { int device = -1; DevScene dev; void* d_blob = nullptr; unsigned long long* d_counters = nullptr; float* d_env_dist = nullptr; };
-    std::vector<Replica> extra;
-    std::vector<int> devices;           // the set, primary first (size 1: single-device scene)
-    std::vector<DevTexture> tdesc_host; size_t o_tdesc = 0, blob_bytes = 0, env_dist_floats = 0;      // what replicate() needs of the upload's layout
-    struct MultiCtx* multi = nullptr;   // streams / staging frames / packed buffers of terra_amd_render_multi, one set per device (made on first use)
-    std::mutex multi_lock;              // a multi-device render owns every device of the set: one at a time per scene
+    // the scene on each device of the set it was committed for (terra_amd_set_devices), primary first: uploaded to replicas[0], byte copies of that blob with
+    // the pointers rebased on the others (replicate_scene). Each has its own counters, environment tables and terra_amd_render_multi state (made on first use;
+    // d_recv, the gather's receive buffer: replica 0 only)
+    struct Replica {
+        int device = -1; DevScene dev {}; void* d_blob = nullptr; unsigned long long* d_counters = nullptr; float* d_env_dist = nullptr;
+        Staging staging; float* d_packed = nullptr; size_t packed_floats = 0; float* d_recv = nullptr; size_t recv_floats = 0;
+    };
+    std::vector<Replica> replicas;
+    size_t d_bytes = 0; std::vector<DevTexture> tdesc_host; size_t o_tdesc = 0, blob_bytes = 0, env_dist_floats = 0;      // the upload's layout, the same in every replica
+    std::mutex multi_lock;              // a multi-device render owns every device of the set: one at a time per scene; guards the replicas' render_multi state and:
+    uint64_t gathers = 0, last_gather_bytes = 0;
     std::atomic<uint64_t> launches { 0 }, stat_pixels { 0 }, stat_samples { 0 };     // terra_render() is called from several threads at once
     int uniform_attr_count = -1;        // attributes_count shared by every material, or -1
     uint32_t bsdf_kinds = 0;            // mask of preset kinds in the committed scene
@@ -323,7 +352,6 @@ struct Scene {
     bool env_lighting = false;          // terra_amd_set_environment_lighting: escaping rays add throughput * environment
     bool work_counters = false;         // terra_amd_set_work_counters: the render kernels count rays / nodes / tests / hits / draws (instrumentation, off by default)
     bool env_sampling = false;          // terra_amd_set_environment_sampling: Direct / Direct+MIS sample a lat-long environment through a TerraDistribution2D (built at commit)
-    float* d_env_dist = nullptr;        // its tables on the device (own allocation)
     int job_order = 1;                  // terra_amd_set_job_order (0 off, 1 on, 2 on for launches of any size): launches that key their streams ahead hand out the pixel blocks no camera ray hits last (launch_render)
     bool sampler_integration = false;   // terra_amd_set_sampler_integration: the pixel's Halton / stratified sampler feeds the first bounce (a launch parameter)
     int fast_max_stack = 1; uint32_t fast_nodes = 0;
@@ -335,6 +363,9 @@ struct Scene {
 };
 
 static Scene* S ( HTerraScene h ) { return ( Scene* ) h; }
+// the primary replica; a scene without a device copy (device_ok false) reads as one with an empty scene on no device
+static const Scene::Replica& primary ( const Scene* s ) { static const Scene::Replica none; return s->replicas.empty() ? none : s->replicas[0]; }
+static std::vector<int> devices_of ( const Scene* s ) { std::vector<int> d; for ( const Scene::Replica& r : s->replicas ) d.push_back ( r.device ); return d; }
 
 // terra_amd_set_commit_timing(1): commit phases on stderr (tools/scale_triangles.py reads them)
 static std::atomic<bool> g_commit_timing { false };
@@ -354,10 +385,9 @@ static void phase ( const char* what, double& t0 ) { if ( !timing_on() ) return;
 
 extern "C" HTerraScene terra_scene_create ( void ) {
     Scene* s = new Scene();
-    memset ( &s->opts, 0, sizeof s->opts ); memset ( &s->new_opts, 0, sizeof s->new_opts ); memset ( &s->dev, 0, sizeof s->dev );
+    memset ( &s->opts, 0, sizeof s->opts ); memset ( &s->new_opts, 0, sizeof s->new_opts );
     s->objects_cap = 64;
     s->objects = ( TerraObject* ) malloc ( sizeof ( TerraObject ) * s->objects_cap );
-    s->device = g_device;
     return s;
 }
 extern "C" TerraObject* terra_scene_add_object ( HTerraScene h, size_t n ) {
@@ -412,7 +442,7 @@ extern "C" int terra_amd_traversal_info ( HTerraScene h, TerraAmdTraversalInfo* 
     memset ( out, 0, sizeof *out );
     if ( !s->committed ) return fail ( kTerraAmdErrNotCommitted, "scene not committed" );
     out->tree_mode = s->tree_mode; out->fast_tree = s->use_fast ? 1 : 0; out->fast_tree_built_on_device = s->fast_on_device ? 1 : 0; out->leaf_cull = ( s->cull_ok && !s->use_fast ) ? 1 : 0;
-    out->lds_resident = ( !s->use_fast && terra_scene_fits_lds ( ( uint32_t ) s->nodes.size(), s->dev.n_tris, s->max_stack, ( uint32_t ) s->objects_pop, ( uint32_t ) s->lights.size() ) ) ? 1 : 0;
+    out->lds_resident = ( !s->use_fast && terra_scene_fits_lds ( ( uint32_t ) s->nodes.size(), primary ( s ).dev.n_tris, s->max_stack, ( uint32_t ) s->objects_pop, ( uint32_t ) s->lights.size() ) ) ? 1 : 0;
     out->max_coordinate = s->coord_max; out->max_coordinate_allowed = TERRA_CULL_MAX_COORD;
     out->last_call = s->last_call.load ( std::memory_order_relaxed ); out->camera_limit = ( s->reach || s->reach_cull ) ? s->reach_limit : TERRA_CULL_MAX_COORD;
     snprintf ( out->note, sizeof out->note, "%s", s->tree_note.c_str() );
@@ -457,41 +487,13 @@ extern "C" int terra_amd_get_sampler_integration ( HTerraScene h ) { return S ( 
 extern "C" void terra_amd_set_frame_seed ( HTerraScene h, uint64_t seed ) { S ( h )->frame_seed = seed; }
 extern "C" uint64_t terra_amd_get_frame_seed ( HTerraScene h ) { return S ( h )->frame_seed; }
 
-// per device of a multi-device scene: its stream, its staging frame (the rectangle of the call, 28 B per pixel), its packed tiles; on the primary device also
-// the receive buffer of the gather (every rank's packed tiles, one after the other)
-struct MultiCtx {
-    struct PerDevice { int device = -1; hipStream_t stream = nullptr; void* d_pixels = nullptr; void* d_results = nullptr; size_t cap_px = 0; float* d_packed = nullptr; size_t packed_floats = 0; };
-    std::vector<PerDevice> dev; float* d_recv = nullptr; size_t recv_floats = 0;
-    uint64_t gathers = 0, last_gather_bytes = 0;
-    void release() {
-        for ( PerDevice& q : dev ) {
-            if ( q.device < 0 || hipSetDevice ( q.device ) != hipSuccess ) continue;
-            if ( q.stream ) { ( void ) hipStreamSynchronize ( q.stream ); ( void ) hipStreamDestroy ( q.stream ); }
-            if ( q.d_pixels ) ( void ) hipFree ( q.d_pixels );
-            if ( q.d_results ) ( void ) hipFree ( q.d_results );
-            if ( q.d_packed ) ( void ) hipFree ( q.d_packed );
-            if ( &q == &dev[0] && d_recv ) ( void ) hipFree ( d_recv );
-        }
-        dev.clear(); d_recv = nullptr; recv_floats = 0;
-    }
-};
 static void release_device ( Scene* s ) {
-    if ( s->multi ) { s->multi->release(); delete s->multi; s->multi = nullptr; }
-    for ( Scene::Replica& r : s->extra ) {
+    for ( Scene::Replica& r : s->replicas ) {
         if ( r.device < 0 || hipSetDevice ( r.device ) != hipSuccess ) continue;
-        if ( r.d_env_dist ) ( void ) hipFree ( r.d_env_dist );
-        if ( r.d_blob ) ( void ) hipFree ( r.d_blob );
-        if ( r.d_counters ) ( void ) hipFree ( r.d_counters );
+        r.staging.release();          // (synchronises its stream first)
+        for ( void* p : { ( void* ) r.d_env_dist, r.d_blob, ( void* ) r.d_counters, ( void* ) r.d_packed, ( void* ) r.d_recv } ) if ( p ) ( void ) hipFree ( p );
     }
-    s->extra.clear();
-    if ( s->d_blob || s->d_counters || s->d_env_dist ) {
-        ( void ) hipSetDevice ( s->device );
-        if ( s->d_env_dist ) ( void ) hipFree ( s->d_env_dist );
-        if ( s->d_blob ) ( void ) hipFree ( s->d_blob );
-        if ( s->d_counters ) ( void ) hipFree ( s->d_counters );
-    }
-    s->d_blob = nullptr; s->d_counters = nullptr; s->d_env_dist = nullptr; s->d_bytes = 0; s->device_ok = false;
-    memset ( &s->dev, 0, sizeof s->dev );
+    s->replicas.clear(); s->d_bytes = 0; s->device_ok = false; s->gathers = 0; s->last_gather_bytes = 0;
 }
 extern "C" void terra_scene_clear ( HTerraScene h ) {
     Scene* s = S ( h );
@@ -530,7 +532,7 @@ static bool is_phong ( const TerraBSDF& b ) { return b.sample == terra_bsdf_phon
 // origin and a vertex: translating and shearing the vertices perturbs them by <= 4 u D per coordinate, the sign of an edge function
 // can be wrong only within ~2 u D of the edge, the slab test's t values carry <= 3 roundings (<= ~6 u D in position), the box itself
 // is rounded by <= u R: together < 16 u D, D <= 2 sqrt(3) R for origins and vertices inside [-R, R]^3, i.e. < 56 u R.
-// The fast tree's boxes are traversed as binary16 planes rounded outward (tree_build_device.hip tb_half_planes_kernel): the new box contains the old one, and
+// The fast tree's boxes are traversed as binary16 planes rounded outward (tree_build.cpp fastbvh::widen): the new box contains the old one, and
 // t = fma ( plane, inv, -(o * inv) ) carries 2 roundings (the product o * inv, worth u |o| in position, and the fma's), fewer than the 3 of the reference form.
 // The check demands 128 u R <= 1e-4 (a factor 2 beyond those estimates): R <= 13.1 scene units, for the vertices (at commit) and for
 // the camera position (per call). Scenes or cameras outside that range run in replica mode. tools/fuzz_vs_oracle.py scales scenes
@@ -702,8 +704,8 @@ extern "C" int terra_amd_scene_supported ( HTerraScene h, char* why, size_t capa
     return st;          // (a query: nothing is recorded in the error channels)
 }
 
-// validates that every material can run on the device and uploads the flattened scene
-static int upload_scene ( Scene* s ) {
+// validates that every material can run on the device and uploads the flattened scene to the set's first device: replicas[0]
+static int upload_scene ( Scene* s, const std::vector<int>& set ) {
     const size_t nobj = s->objects_pop;
     if ( nobj > 256 ) return fail ( kTerraAmdErrUnsupported, "%zu objects: the primitive reference holds 8 bits of object index (include/Terra.h:195-198)", nobj );
     size_t ntri = 0;
@@ -973,14 +975,16 @@ static int upload_scene ( Scene* s ) {
     }
 
     release_device ( s );
-    s->device = g_device;
     if ( terra_amd_device_count() <= 0 ) return fail ( kTerraAmdErrNoDevice, "no HIP device visible: terra_scene_commit built the host tree but cannot upload; terra_render will fail" );
-    HIP_TRY ( hipSetDevice ( s->device ), kTerraAmdErrNoDevice );
-    HIP_TRY ( hipMalloc ( &s->d_blob, total ), kTerraAmdErrNoDevice );
-    HIP_TRY ( hipMemset ( s->d_blob, 0, total ), kTerraAmdErrNoDevice );
-    HIP_TRY ( hipMalloc ( ( void** ) &s->d_counters, kCtrCount * sizeof ( unsigned long long ) ), kTerraAmdErrNoDevice );
-    HIP_TRY ( hipMemset ( s->d_counters, 0, kCtrCount * sizeof ( unsigned long long ) ), kTerraAmdErrNoDevice );
-    char* base = ( char* ) s->d_blob;
+    s->replicas.resize ( 1 );
+    Scene::Replica& r = s->replicas[0]; DevScene& dev = r.dev;
+    r.device = set[0];
+    HIP_TRY ( hipSetDevice ( r.device ), kTerraAmdErrNoDevice );
+    HIP_TRY ( hipMalloc ( &r.d_blob, total ), kTerraAmdErrNoDevice );
+    HIP_TRY ( hipMemset ( r.d_blob, 0, total ), kTerraAmdErrNoDevice );
+    HIP_TRY ( hipMalloc ( ( void** ) &r.d_counters, kCtrCount * sizeof ( unsigned long long ) ), kTerraAmdErrNoDevice );
+    HIP_TRY ( hipMemset ( r.d_counters, 0, kCtrCount * sizeof ( unsigned long long ) ), kTerraAmdErrNoDevice );
+    char* base = ( char* ) r.d_blob;
     HIP_TRY ( hipMemcpy ( base + o_nodes, nodes.data(), nodes.size() * sizeof ( DevNode ), hipMemcpyHostToDevice ), kTerraAmdErrNoDevice );
     HIP_TRY ( hipMemcpy ( base + o_tris, tris.data(), tris.size() * sizeof ( DevTri ), hipMemcpyHostToDevice ), kTerraAmdErrNoDevice );
     HIP_TRY ( hipMemcpy ( base + o_props, props.data(), props.size() * sizeof ( DevProps ), hipMemcpyHostToDevice ), kTerraAmdErrNoDevice );
@@ -1050,18 +1054,18 @@ static int upload_scene ( Scene* s ) {
         tdesc[k].depth = t->depth; tdesc[k].filter = t->filter; tdesc[k].address_mode = t->address_mode;
     }
     if ( !tdesc.empty() ) HIP_TRY ( hipMemcpy ( base + o_td, tdesc.data(), tdesc.size() * sizeof ( DevTexture ), hipMemcpyHostToDevice ), kTerraAmdErrNoDevice );
-    s->dev.textures = tdesc.empty() ? nullptr : ( const DevTexture* ) ( base + o_td );
+    dev.textures = tdesc.empty() ? nullptr : ( const DevTexture* ) ( base + o_td );
     s->d_bytes = total; s->blob_bytes = total; s->o_tdesc = o_td; s->tdesc_host = tdesc; s->env_dist_floats = 0;
-    s->dev.nodes = ( const DevNode* ) ( base + o_nodes ); s->dev.tris = ( const DevTri* ) ( base + o_tris ); s->dev.props = ( const DevProps* ) ( base + o_props );
-    s->dev.mats = ( const DevMaterial* ) ( base + o_mats ); s->dev.lights = ( const DevLight* ) ( base + o_lights ); s->dev.tri_area = ( const float* ) ( base + o_area );
-    s->dev.n_nodes = ( uint32_t ) nodes.size(); s->dev.n_tris = ( uint32_t ) ntri; s->dev.n_objects = ( uint32_t ) nobj; s->dev.n_lights = ( uint32_t ) s->lights.size();
-    s->dev.lights_triangles_count = ( uint32_t ) s->lights_triangles_count; s->dev.max_stack = s->max_stack;
-    s->dev.fast_nodes = ( have_fast && s->fast_on_device ) ? ( const DevNode* ) ( base + o_fn ) : nullptr; s->dev.fast_nodes_h = have_fast ? ( const DevFastNode* ) ( base + o_fh ) : nullptr; s->dev.fast_tris = have_fast ? ( const DevTri* ) ( base + o_ft ) : nullptr;
-    s->dev.n_fast_nodes = s->fast_nodes; s->dev.fast_max_stack = s->fast_max_stack; s->dev.fast_inv_scale = 1.f / fast_scale;
-    s->dev.reach = ( s->reach && have_fast && !reach_tabs.leaf_parent.empty() ) ? 1u : 0u;
-    s->dev.ref_replay = s->dev.reach ? ( const DevReplay* ) ( base + o_rp ) : nullptr; s->dev.fast_leaf_parent = s->dev.reach ? ( const uint32_t* ) ( base + o_lp ) : nullptr; s->dev.fast_leaf_mask = s->dev.reach ? ( const uint32_t* ) ( base + o_lm ) : nullptr;
-    s->dev.env_mode = env_mode; s->dev.env_tex = env_tex; memcpy ( s->dev.env_color, env_color, sizeof env_color );
-    s->dev.sincos24 = sincos_table_of ( s->device );
+    dev.nodes = ( const DevNode* ) ( base + o_nodes ); dev.tris = ( const DevTri* ) ( base + o_tris ); dev.props = ( const DevProps* ) ( base + o_props );
+    dev.mats = ( const DevMaterial* ) ( base + o_mats ); dev.lights = ( const DevLight* ) ( base + o_lights ); dev.tri_area = ( const float* ) ( base + o_area );
+    dev.n_nodes = ( uint32_t ) nodes.size(); dev.n_tris = ( uint32_t ) ntri; dev.n_objects = ( uint32_t ) nobj; dev.n_lights = ( uint32_t ) s->lights.size();
+    dev.lights_triangles_count = ( uint32_t ) s->lights_triangles_count; dev.max_stack = s->max_stack;
+    dev.fast_nodes = ( have_fast && s->fast_on_device ) ? ( const DevNode* ) ( base + o_fn ) : nullptr; dev.fast_nodes_h = have_fast ? ( const DevFastNode* ) ( base + o_fh ) : nullptr; dev.fast_tris = have_fast ? ( const DevTri* ) ( base + o_ft ) : nullptr;
+    dev.n_fast_nodes = s->fast_nodes; dev.fast_max_stack = s->fast_max_stack; dev.fast_inv_scale = 1.f / fast_scale;
+    dev.reach = ( s->reach && have_fast && !reach_tabs.leaf_parent.empty() ) ? 1u : 0u;
+    dev.ref_replay = dev.reach ? ( const DevReplay* ) ( base + o_rp ) : nullptr; dev.fast_leaf_parent = dev.reach ? ( const uint32_t* ) ( base + o_lp ) : nullptr; dev.fast_leaf_mask = dev.reach ? ( const uint32_t* ) ( base + o_lm ) : nullptr;
+    dev.env_mode = env_mode; dev.env_tex = env_tex; memcpy ( dev.env_color, env_color, sizeof env_color );
+    dev.sincos24 = sincos_table_of ( r.device );
     // environment importance sampling (extension, UNPINNED; the oracle's env_table_build restates it): the map as the reference's TerraDistribution2D would hold it
     // (terra_distribution_2d_init, src/Terra.c:812-829: per row a running float sum in index order divided by its total, then the same over the rows' totals)
     if ( s->env_sampling && env_mode == 2 && textures[env_tex]->components >= 3 ) {        // (the table reads three components per texel)
@@ -1086,12 +1090,12 @@ static int upload_scene ( Scene* s ) {
             row_f[y] = row_init ( f + y * nx, nx, cdf + y * nx );
         }
         const float integral = row_init ( row_f, ny, row_cdf );
-        HIP_TRY ( hipMalloc ( ( void** ) &s->d_env_dist, tab.size() * sizeof ( float ) ), kTerraAmdErrNoDevice );
-        HIP_TRY ( hipMemcpy ( s->d_env_dist, tab.data(), tab.size() * sizeof ( float ), hipMemcpyHostToDevice ), kTerraAmdErrNoDevice );
+        HIP_TRY ( hipMalloc ( ( void** ) &r.d_env_dist, tab.size() * sizeof ( float ) ), kTerraAmdErrNoDevice );
+        HIP_TRY ( hipMemcpy ( r.d_env_dist, tab.data(), tab.size() * sizeof ( float ), hipMemcpyHostToDevice ), kTerraAmdErrNoDevice );
         s->d_bytes += tab.size() * sizeof ( float ); s->env_dist_floats = tab.size();
-        s->dev.env_f = s->d_env_dist; s->dev.env_cdf = s->d_env_dist + cells; s->dev.env_row_f = s->d_env_dist + 2 * cells; s->dev.env_row_cdf = s->d_env_dist + 2 * cells + ny;
-        s->dev.env_nx = ( uint32_t ) nx; s->dev.env_ny = ( uint32_t ) ny; s->dev.env_integral = integral;
-        s->dev.env_monotone = ( mono && integral > 0.f && integral <= FLT_MAX ) ? 1u : 0u;      // then every running sum is non-decreasing: bisection finds the scan's bucket
+        dev.env_f = r.d_env_dist; dev.env_cdf = r.d_env_dist + cells; dev.env_row_f = r.d_env_dist + 2 * cells; dev.env_row_cdf = r.d_env_dist + 2 * cells + ny;
+        dev.env_nx = ( uint32_t ) nx; dev.env_ny = ( uint32_t ) ny; dev.env_integral = integral;
+        dev.env_monotone = ( mono && integral > 0.f && integral <= FLT_MAX ) ? 1u : 0u;      // then every running sum is non-decreasing: bisection finds the scan's bucket
     }
     s->device_ok = true;
     return 0;
@@ -1099,47 +1103,47 @@ static int upload_scene ( Scene* s ) {
 
 // The committed scene on the other devices of the set: the primary device's finished blob (trees built, boxes converted, tables filled) copied device to device,
 // every pointer into it moved by the difference of the two base addresses, the texture descriptors -- which hold absolute addresses -- written again.
-static int replicate_scene ( Scene* s ) {
-    const char* base0 = ( const char* ) s->d_blob;
-    for ( size_t k = 1; k < s->devices.size(); ++k ) {
-        Scene::Replica r; r.device = s->devices[k];
+static int replicate_scene ( Scene* s, const std::vector<int>& set ) {
+    for ( size_t k = 1; k < set.size(); ++k ) {
+        Scene::Replica r; r.device = set[k];
         HIP_TRY ( hipSetDevice ( r.device ), kTerraAmdErrNoDevice );
         HIP_TRY ( hipMalloc ( &r.d_blob, s->blob_bytes ), kTerraAmdErrNoDevice );
-        s->extra.push_back ( r );                                   // (owned from here on: release_device frees it whatever fails below)
-        Scene::Replica& q = s->extra.back();
-        HIP_TRY ( hipMemcpyPeer ( q.d_blob, q.device, s->d_blob, s->device, s->blob_bytes ), kTerraAmdErrNoDevice );
+        s->replicas.push_back ( r );                                // (owned from here on: release_device frees it whatever fails below)
+        const Scene::Replica& r0 = s->replicas[0]; Scene::Replica& q = s->replicas.back();
+        const char* base0 = ( const char* ) r0.d_blob;
+        HIP_TRY ( hipMemcpyPeer ( q.d_blob, q.device, r0.d_blob, r0.device, s->blob_bytes ), kTerraAmdErrNoDevice );
         HIP_TRY ( hipMalloc ( ( void** ) &q.d_counters, kCtrCount * sizeof ( unsigned long long ) ), kTerraAmdErrNoDevice );
         HIP_TRY ( hipMemset ( q.d_counters, 0, kCtrCount * sizeof ( unsigned long long ) ), kTerraAmdErrNoDevice );
         char* base = ( char* ) q.d_blob;
         auto move = [&] ( const void* p ) -> const void* { return p ? ( const void* ) ( base + ( ( const char* ) p - base0 ) ) : nullptr; };
-        q.dev = s->dev;
-        q.dev.nodes = ( const DevNode* ) move ( s->dev.nodes ); q.dev.tris = ( const DevTri* ) move ( s->dev.tris ); q.dev.props = ( const DevProps* ) move ( s->dev.props );
-        q.dev.mats = ( const DevMaterial* ) move ( s->dev.mats ); q.dev.lights = ( const DevLight* ) move ( s->dev.lights ); q.dev.tri_area = ( const float* ) move ( s->dev.tri_area );
-        q.dev.textures = ( const DevTexture* ) move ( s->dev.textures ); q.dev.fast_nodes = ( const DevNode* ) move ( s->dev.fast_nodes ); q.dev.fast_nodes_h = ( const DevFastNode* ) move ( s->dev.fast_nodes_h ); q.dev.fast_tris = ( const DevTri* ) move ( s->dev.fast_tris );
-        q.dev.ref_replay = ( const DevReplay* ) move ( s->dev.ref_replay ); q.dev.fast_leaf_parent = ( const uint32_t* ) move ( s->dev.fast_leaf_parent ); q.dev.fast_leaf_mask = ( const uint32_t* ) move ( s->dev.fast_leaf_mask );
+        q.dev = r0.dev;
+        q.dev.nodes = ( const DevNode* ) move ( r0.dev.nodes ); q.dev.tris = ( const DevTri* ) move ( r0.dev.tris ); q.dev.props = ( const DevProps* ) move ( r0.dev.props );
+        q.dev.mats = ( const DevMaterial* ) move ( r0.dev.mats ); q.dev.lights = ( const DevLight* ) move ( r0.dev.lights ); q.dev.tri_area = ( const float* ) move ( r0.dev.tri_area );
+        q.dev.textures = ( const DevTexture* ) move ( r0.dev.textures ); q.dev.fast_nodes = ( const DevNode* ) move ( r0.dev.fast_nodes ); q.dev.fast_nodes_h = ( const DevFastNode* ) move ( r0.dev.fast_nodes_h ); q.dev.fast_tris = ( const DevTri* ) move ( r0.dev.fast_tris );
+        q.dev.ref_replay = ( const DevReplay* ) move ( r0.dev.ref_replay ); q.dev.fast_leaf_parent = ( const uint32_t* ) move ( r0.dev.fast_leaf_parent ); q.dev.fast_leaf_mask = ( const uint32_t* ) move ( r0.dev.fast_leaf_mask );
         if ( !s->tdesc_host.empty() ) {
             std::vector<DevTexture> td = s->tdesc_host;
             for ( DevTexture& t : td ) t.data = move ( t.data );
             HIP_TRY ( hipMemcpy ( base + s->o_tdesc, td.data(), td.size() * sizeof ( DevTexture ), hipMemcpyHostToDevice ), kTerraAmdErrNoDevice );
         }
-        if ( s->d_env_dist && s->env_dist_floats ) {
+        if ( r0.d_env_dist && s->env_dist_floats ) {
             HIP_TRY ( hipMalloc ( ( void** ) &q.d_env_dist, s->env_dist_floats * sizeof ( float ) ), kTerraAmdErrNoDevice );
-            HIP_TRY ( hipMemcpyPeer ( q.d_env_dist, q.device, s->d_env_dist, s->device, s->env_dist_floats * sizeof ( float ) ), kTerraAmdErrNoDevice );
-            auto emove = [&] ( const float* p ) { return p ? q.d_env_dist + ( p - s->d_env_dist ) : nullptr; };
-            q.dev.env_f = emove ( s->dev.env_f ); q.dev.env_cdf = emove ( s->dev.env_cdf ); q.dev.env_row_f = emove ( s->dev.env_row_f ); q.dev.env_row_cdf = emove ( s->dev.env_row_cdf );
+            HIP_TRY ( hipMemcpyPeer ( q.d_env_dist, q.device, r0.d_env_dist, r0.device, s->env_dist_floats * sizeof ( float ) ), kTerraAmdErrNoDevice );
+            auto emove = [&] ( const float* p ) { return p ? q.d_env_dist + ( p - r0.d_env_dist ) : nullptr; };
+            q.dev.env_f = emove ( r0.dev.env_f ); q.dev.env_cdf = emove ( r0.dev.env_cdf ); q.dev.env_row_f = emove ( r0.dev.env_row_f ); q.dev.env_row_cdf = emove ( r0.dev.env_row_cdf );
         }
         q.dev.sincos24 = sincos_table_of ( q.device );
         // self-check, independent of the list above: no 8-byte word of the replica's scene record may still be an address inside the PRIMARY's blob (or its
         // environment tables) -- a pointer member added to DevScene and forgotten here would be exactly that, and on a single box it would even keep working
         {
             uint64_t words[ ( sizeof ( DevScene ) + 7 ) / 8] = { 0 }; memcpy ( words, &q.dev, sizeof ( DevScene ) );
-            const uint64_t b0 = ( uint64_t ) ( uintptr_t ) base0, b1 = b0 + s->blob_bytes, e0 = ( uint64_t ) ( uintptr_t ) s->d_env_dist, e1 = e0 + s->env_dist_floats * sizeof ( float );
+            const uint64_t b0 = ( uint64_t ) ( uintptr_t ) base0, b1 = b0 + s->blob_bytes, e0 = ( uint64_t ) ( uintptr_t ) r0.d_env_dist, e1 = e0 + s->env_dist_floats * sizeof ( float );
             for ( size_t i = 0; i < sizeof ( DevScene ) / 8; ++i )
                 if ( ( words[i] >= b0 && words[i] < b1 ) || ( e0 && words[i] >= e0 && words[i] < e1 ) )
                     return fail ( kTerraAmdErrLaunch, "scene replica for device %d: byte %zu of its scene record still points into the primary device's copy (a pointer that replicate_scene does not rebase)", q.device, i * 8 );
         }
     }
-    HIP_TRY ( hipSetDevice ( s->device ), kTerraAmdErrNoDevice );
+    HIP_TRY ( hipSetDevice ( set[0] ), kTerraAmdErrNoDevice );
     return 0;
 }
 
@@ -1178,13 +1182,11 @@ extern "C" void terra_scene_commit ( HTerraScene h ) {
     // nothing is uploaded for it; terra_amd_set_environment_lighting(scene, 1) turns that line on (upload_scene binds it).
     // options travel as kernel arguments; geometry/material/light changes need a new replica
     std::vector<int> set;
-    { std::lock_guard<std::mutex> g ( g_devices_lock ); set = g_devices; }
-    if ( set.empty() ) set.push_back ( g_device );
-    const bool set_changed = set != s->devices;          // (terra_amd_set_devices / terra_amd_set_device since the last commit: the replicas move)
+    { std::lock_guard<std::mutex> g ( g_devices_lock ); set = g_devices.empty() ? std::vector<int> { g_device } : g_devices; }
+    const bool set_changed = set != devices_of ( s );          // (terra_amd_set_devices / terra_amd_set_device since the last commit: the replicas move)
     if ( rebuild || relight || env_changed || !s->device_ok || set_changed ) {
-        if ( upload_scene ( s ) != 0 ) { s->commit_error = g_last_error; s->device_ok = false; return; }
-        s->devices = set;
-        if ( set.size() > 1 && replicate_scene ( s ) != 0 ) { s->commit_error = g_last_error; release_device ( s ); }
+        if ( upload_scene ( s, set ) != 0 ) { s->commit_error = g_last_error; s->device_ok = false; return; }
+        if ( set.size() > 1 && replicate_scene ( s, set ) != 0 ) { s->commit_error = g_last_error; release_device ( s ); }
     }
 }
 
@@ -1203,41 +1205,51 @@ extern "C" int terra_amd_scene_bvh_nodes ( HTerraScene h, void* out, int capacit
     if ( out && capacity >= n ) memcpy ( out, s->nodes.data(), ( size_t ) n * sizeof ( HostNode ) );
     return n;
 }
+// counters [first, first + n) summed over every replica, each device current around its copy (the primary's last: it stays current)
+static int sum_counters ( Scene* s, size_t first, size_t n, unsigned long long* out ) {
+    unsigned long long c[kCtrCount];
+    std::fill ( out, out + n, 0ull );
+    for ( size_t k = s->replicas.size(); k-- > 0; ) {
+        const Scene::Replica& r = s->replicas[k];
+        HIP_TRY ( hipSetDevice ( r.device ), kTerraAmdErrNoDevice );
+        HIP_TRY ( hipMemcpy ( c, r.d_counters + first, n * sizeof ( unsigned long long ), hipMemcpyDeviceToHost ), kTerraAmdErrNoDevice );
+        for ( size_t i = 0; i < n; ++i ) out[i] += c[i];
+    }
+    return 0;
+}
 extern "C" int terra_amd_get_stats ( HTerraScene h, TerraAmdStats* out ) {
     Scene* s = S ( h );
     memset ( out, 0, sizeof *out );
     if ( !s->device_ok ) return fail ( kTerraAmdErrNotCommitted, "scene has no device replica" );
     unsigned long long c[kCtrCount];
-    HIP_TRY ( hipSetDevice ( s->device ), kTerraAmdErrNoDevice );
-    HIP_TRY ( hipMemcpy ( c, s->d_counters, sizeof c, hipMemcpyDeviceToHost ), kTerraAmdErrNoDevice );
+    if ( int rc = sum_counters ( s, 0, kCtrCount, c ) ) return rc;
     out->rays = c[kCtrRays]; out->nodes = c[kCtrNodes]; out->tri_tests = c[kCtrTriTests]; out->hits = c[kCtrHits];
     out->rand_calls = c[kCtrRandCalls]; out->attr_fetches = c[kCtrAttrFetches]; out->tri_culled = c[kCtrTriCulled];
     // derived exactly on the host (see Counters in trace_device.h)
-    out->box_tests = s->dev.n_tris >= 2 ? ( s->use_fast ? 4 * out->nodes : s->cull_ok ? 2 * out->nodes : 2 * out->nodes - out->tri_tests ) : 0;      // the fast tree's nodes hold four boxes; with the leaf-box cull every child's slab test is used
+    out->box_tests = primary ( s ).dev.n_tris >= 2 ? ( s->use_fast ? 4 * out->nodes : s->cull_ok ? 2 * out->nodes : 2 * out->nodes - out->tri_tests ) : 0;      // the fast tree's nodes hold four boxes; with the leaf-box cull every child's slab test is used
     out->samples = s->stat_samples; out->pixels = s->stat_pixels; out->launches = s->launches;
     return 0;
 }
 extern "C" long long terra_amd_debug_faults ( HTerraScene h ) {
     // out-of-plan stack / leaf-list writes refused by a TERRA_CHECK_BOUNDS build since the last reset (always 0 in the shipped build)
     Scene* s = S ( h );
-    if ( !s->device_ok ) return -1;
     unsigned long long v = 0;
-    if ( hipSetDevice ( s->device ) != hipSuccess || hipMemcpy ( &v, s->d_counters + kCtrFaults, sizeof v, hipMemcpyDeviceToHost ) != hipSuccess ) return -1;
+    if ( !s->device_ok || sum_counters ( s, kCtrFaults, 1, &v ) ) return -1;
     return ( long long ) v;
 }
 extern "C" int terra_amd_debug_counters ( HTerraScene h, unsigned long long* out16 ) {
     // phase occupancy counters of a TERRA_PHASE_STATS build (tools/phase_stats.py); all zero in the shipped build
     Scene* s = S ( h );
     if ( !s->device_ok || !out16 ) return fail ( kTerraAmdErrNotCommitted, "scene has no device replica" );
-    HIP_TRY ( hipSetDevice ( s->device ), kTerraAmdErrNoDevice );
-    HIP_TRY ( hipMemcpy ( out16, s->d_counters + kCtrDbg0, 16 * sizeof ( unsigned long long ), hipMemcpyDeviceToHost ), kTerraAmdErrNoDevice );
-    return 0;
+    return sum_counters ( s, kCtrDbg0, 16, out16 );
 }
 extern "C" int terra_amd_reset_stats ( HTerraScene h ) {
     Scene* s = S ( h );
     if ( !s->device_ok ) return fail ( kTerraAmdErrNotCommitted, "scene has no device replica" );
-    HIP_TRY ( hipSetDevice ( s->device ), kTerraAmdErrNoDevice );
-    HIP_TRY ( hipMemset ( s->d_counters, 0, kCtrCount * sizeof ( unsigned long long ) ), kTerraAmdErrNoDevice );
+    for ( size_t k = s->replicas.size(); k-- > 0; ) {
+        HIP_TRY ( hipSetDevice ( s->replicas[k].device ), kTerraAmdErrNoDevice );
+        HIP_TRY ( hipMemset ( s->replicas[k].d_counters, 0, kCtrCount * sizeof ( unsigned long long ) ), kTerraAmdErrNoDevice );
+    }
     s->launches = 0; s->stat_pixels = 0; s->stat_samples = 0;
     return 0;
 }
@@ -1255,16 +1267,16 @@ static uint32_t effective_spp ( const TerraSceneOptions& o ) {
     return ( uint32_t ) spp;
 }
 
-// replica: which device's copy of the scene the launch reads (nullptr: the primary device's)
-static int fill_params ( Scene* s, const TerraCamera* cam, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t h,
-                         size_t tile, int rank, int world, DevRenderParams& p, const Scene::Replica* replica = nullptr ) {
+// r: the copy of the scene the launch reads (the launch runs on r.device)
+static int fill_params ( Scene* s, const Scene::Replica& r, const TerraCamera* cam, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t h,
+                         size_t tile, int rank, int world, DevRenderParams& p ) {
     if ( !s->committed ) return fail ( kTerraAmdErrNotCommitted, "terra_scene_commit has not run since the scene changed" );
     if ( !s->device_ok ) return fail ( kTerraAmdErrNoDevice, "scene has no device replica: %s", s->commit_error.c_str() );
     if ( !cam || w == 0 || h == 0 || x + w > fb_w || y + h > fb_h ) return fail ( kTerraAmdErrBadArgument, "bad tile rectangle %zu,%zu %zux%zu in %zux%zu", x, y, w, h, fb_w, fb_h );
     if ( tile == 0 || tile % 16 != 0 ) return fail ( kTerraAmdErrBadArgument, "tile_size %zu must be a positive multiple of 16", tile );
     if ( world < 1 || rank < 0 || rank >= world ) return fail ( kTerraAmdErrBadArgument, "bad shard %d/%d", rank, world );
     memset ( &p, 0, sizeof p );
-    p.scene = replica ? replica->dev : s->dev;
+    p.scene = r.dev;
     // camera frame, reference src/Terra.c:1770-1781
     TerraFloat3 z = terra_normf3 ( &cam->direction );
     TerraFloat3 xa = terra_crossf3 ( &cam->up, &z ); xa = terra_normf3 ( &xa );
@@ -1288,11 +1300,11 @@ static int fill_params ( Scene* s, const TerraCamera* cam, size_t fb_w, size_t f
     if ( ( p.integrator == kTerraIntegratorDirect || p.integrator == kTerraIntegratorDirectMis || p.integrator == kTerraIntegratorDebugMisWeights ) && s->lights.empty() )
         return fail ( kTerraAmdErrBadArgument, "integrator %d needs at least one emissive object (the reference asserts, src/Terra.c:1617)", p.integrator );
     p.frame_seed = s->frame_seed;
-    p.counters = replica ? replica->d_counters : s->d_counters;
+    p.counters = r.d_counters;
     terra_plan_lds ( p );
     // automatic mode: the containment argument also needs the ray origins (the camera) inside the verified coordinate range
     const bool cam_ok = ( s->reach || s->reach_cull ) ? ( fabsf ( p.cam_pos[0] ) <= s->reach_limit && fabsf ( p.cam_pos[1] ) <= s->reach_limit && fabsf ( p.cam_pos[2] ) <= s->reach_limit ) : coords_within_margin ( p.cam_pos, 3 );
-    if ( s->use_fast && s->dev.fast_nodes_h && ( s->tree_mode == 1 || cam_ok ) ) terra_plan_fast_tree ( p );
+    if ( s->use_fast && r.dev.fast_nodes_h && ( s->tree_mode == 1 || cam_ok ) ) terra_plan_fast_tree ( p );
     else if ( ( s->use_fast || s->cull_ok ) && !cam_ok && !s->warned_camera.exchange ( true ) )          // (once per scene)
         fprintf ( stderr, "[terra_amd] warning: camera at (%g, %g, %g) lies outside the range (+-%g) for which this scene's traversal shortcut is proven: this call runs the reference "
                   "tree's replica traversal (same image, typically 10-20 x slower on large scenes); terra_amd_traversal_info() reports camera_limit and last_call\n",
@@ -1314,14 +1326,14 @@ static int fill_params ( Scene* s, const TerraCamera* cam, size_t fb_w, size_t f
 #endif
     if ( p.lds_mode != 1 && ! ( TERRA_SINCOS_TABLE_FAST_TREE && p.lds_mode == 2 ) ) p.scene.sincos24 = nullptr;
     // what this call runs (TerraAmdTraversalInfo::last_call): the commit-time decision can be overridden per call by the camera position
-    s->last_call.store ( p.lds_mode == 2 ? ( s->dev.reach ? kTerraAmdCallFastTreeReach : kTerraAmdCallFastTree ) : ( p.leaf_cull ? kTerraAmdCallLeafCull : kTerraAmdCallReplica ), std::memory_order_relaxed );
+    s->last_call.store ( p.lds_mode == 2 ? ( r.dev.reach ? kTerraAmdCallFastTreeReach : kTerraAmdCallFastTree ) : ( p.leaf_cull ? kTerraAmdCallLeafCull : kTerraAmdCallReplica ), std::memory_order_relaxed );
     p.bsdf_kinds = s->bsdf_kinds;
     p.sampler_mode = 0; p.sampler_strata = ( uint32_t ) s->opts.strata;
     if ( s->sampler_integration && s->opts.sampling_method == kTerraSamplingMethodHalton ) p.sampler_mode = 1;
     if ( s->sampler_integration && s->opts.sampling_method == kTerraSamplingMethodStratified && s->opts.strata > 0 ) p.sampler_mode = 2;
     if ( p.sampler_mode ) p.bsdf_kinds |= TERRA_KIND_SAMPLER;
     // environment sampling lives in the same kernel variant; it only acts in the two integrators that sample lights
-    if ( s->dev.env_nx && ( p.integrator == kTerraIntegratorDirect || p.integrator == kTerraIntegratorDirectMis ) ) p.bsdf_kinds |= TERRA_KIND_SAMPLER;
+    if ( r.dev.env_nx && ( p.integrator == kTerraIntegratorDirect || p.integrator == kTerraIntegratorDirectMis ) ) p.bsdf_kinds |= TERRA_KIND_SAMPLER;
     else { p.scene.env_nx = 0; p.scene.env_ny = 0; }
     p.count_level = s->work_counters ? 2 : 0;
     return 0;
@@ -1362,7 +1374,7 @@ static uint32_t auto_sample_split ( uint32_t blocks, uint32_t spp, bool ordered 
     while ( split < 32 && ( uint64_t ) blocks * split < enough && spp / ( split * 2 ) >= 16 ) split *= 2;
     return split;
 }
-static int launch_render ( Scene* s, DevRenderParams& p, hipStream_t stream, ThreadSlot* slot = nullptr, int device = -1 ) {      // device: the (current) device of the launch, -1 = the scene's primary
+static int launch_render ( Scene* s, DevRenderParams& p, int device, hipStream_t stream, ThreadSlot* slot = nullptr ) {      // device: the (current) device of the launch
     uint32_t split = s->sample_split;
     const uint32_t blocks = terra_render_blocks ( p );
     if ( blocks == 0 ) return 0;
@@ -1370,7 +1382,6 @@ static int launch_render ( Scene* s, DevRenderParams& p, hipStream_t stream, Thr
     if ( split == 0 ) split = auto_sample_split ( blocks, p.spp, s->job_order && terra_block_order_bytes ( p, s->job_order == 2 ) != 0 );
     while ( split > 1 && p.spp % split ) split >>= 1;              // chunks must be equal: fall back to the largest power of two dividing spp
     if ( split < 1 ) split = 1;
-    if ( device < 0 ) device = s->device;
     static thread_local uint64_t pool_kept = 0;          // (bit d: done for device d)
     if ( device < 64 && ! ( pool_kept >> device & 1ull ) ) {        // keep freed scratch cached in the device's default pool instead of returning it to the OS at every sync
         hipMemPool_t pool;
@@ -1430,14 +1441,15 @@ static int launch_render ( Scene* s, DevRenderParams& p, hipStream_t stream, Thr
 extern "C" int terra_amd_render_device_sharded ( const TerraCamera* cam, HTerraScene h, void* d_pixels, void* d_results, size_t fb_w, size_t fb_h,
                                                  size_t x, size_t y, size_t w, size_t hgt, size_t tile, int rank, int world, void* d_rand_calls, void* stream ) {
     Scene* s = S ( h );
+    const Scene::Replica& r = primary ( s );
     DevRenderParams p;
-    int rc = fill_params ( s, cam, fb_w, fb_h, x, y, w, hgt, tile, rank, world, p );
+    int rc = fill_params ( s, r, cam, fb_w, fb_h, x, y, w, hgt, tile, rank, world, p );
     if ( rc ) return rc;
     if ( !d_pixels || !d_results ) return fail ( kTerraAmdErrBadArgument, "null framebuffer pointer" );
     p.pixels = ( float* ) d_pixels; p.results = d_results; p.rand_calls = ( uint32_t* ) d_rand_calls;
     if ( d_rand_calls ) p.count_level = 2;
-    HIP_TRY ( hipSetDevice ( s->device ), kTerraAmdErrNoDevice );
-    if ( int lrc = launch_render ( s, p, ( hipStream_t ) stream ) ) return lrc;
+    HIP_TRY ( hipSetDevice ( r.device ), kTerraAmdErrNoDevice );
+    if ( int lrc = launch_render ( s, p, r.device, ( hipStream_t ) stream ) ) return lrc;
     account_launch ( s, p );
     return 0;
 }
@@ -1453,7 +1465,7 @@ extern "C" int terra_amd_time_render_device ( const TerraCamera* cam, HTerraScen
                                               size_t x, size_t y, size_t w, size_t hgt, int launches, void* stream, float* ms_avg ) {
     if ( launches < 1 || !ms_avg ) return fail ( kTerraAmdErrBadArgument, "launches < 1" );
     hipEvent_t e0, e1;
-    HIP_TRY ( hipSetDevice ( S ( h )->device ), kTerraAmdErrNoDevice );
+    if ( S ( h )->device_ok ) HIP_TRY ( hipSetDevice ( primary ( S ( h ) ).device ), kTerraAmdErrNoDevice );      // (otherwise the first render reports why)
     HIP_TRY ( hipEventCreate ( &e0 ), kTerraAmdErrLaunch ); HIP_TRY ( hipEventCreate ( &e1 ), kTerraAmdErrLaunch );
     HIP_TRY ( hipEventRecord ( e0, ( hipStream_t ) stream ), kTerraAmdErrLaunch );
     for ( int i = 0; i < launches; ++i ) {
@@ -1501,18 +1513,13 @@ extern "C" int terra_amd_unpack_tiles ( void* d_pixels, void* d_results, size_t 
 // frame: a client that renders 128-pixel tiles from 8 workers stages 8 x 0.46 MB, not 8 frames). The tile's running sums go up
 // (they key the random streams and are accumulated on), the kernel renders into the staging rectangle, the tile comes back.
 // The slot is released when its thread exits.
-struct ThreadSlot {
-    int device = -1; hipStream_t stream = nullptr; void* d_pixels = nullptr; void* d_results = nullptr; size_t cap_px = 0;
+struct ThreadSlot : Staging {
     void* d_scratch = nullptr; size_t scratch_bytes = 0;      // the launch's job sums + queue word (launch_render): kept per thread so that a tile-sized call does not go through the pool
     void release() {
-        if ( device < 0 ) return;
-        if ( hipSetDevice ( device ) == hipSuccess ) {
-            if ( stream ) { ( void ) hipStreamSynchronize ( stream ); ( void ) hipStreamDestroy ( stream ); }
-            if ( d_pixels ) ( void ) hipFree ( d_pixels );
-            if ( d_results ) ( void ) hipFree ( d_results );
-            if ( d_scratch ) ( void ) hipFree ( d_scratch );
-        }
-        device = -1; stream = nullptr; d_pixels = d_results = d_scratch = nullptr; cap_px = 0; scratch_bytes = 0;
+        const int d = device;
+        Staging::release();          // (its stream drained: the scratch is idle)
+        if ( d_scratch && hipSetDevice ( d ) == hipSuccess ) ( void ) hipFree ( d_scratch );
+        d_scratch = nullptr; scratch_bytes = 0;
     }
     ~ThreadSlot() { release(); }
 };
@@ -1548,23 +1555,8 @@ static void* slot_scratch ( ThreadSlot* slot, size_t bytes ) {
 
 static int slot_prepare ( int device, size_t npx ) {
     ThreadSlot& t = t_slot;
-    int current = -1;
-    if ( hipGetDevice ( &current ) != hipSuccess || current != device ) HIP_TRY ( hipSetDevice ( device ), kTerraAmdErrNoDevice );
-    if ( t.device != device ) {
-        const bool had_other = t.device >= 0;
-        t.release(); t.device = device;
-        if ( had_other ) HIP_TRY ( hipSetDevice ( device ), kTerraAmdErrNoDevice );      // (release() made the slot's old device current)
-        HIP_TRY ( hipStreamCreateWithFlags ( &t.stream, hipStreamNonBlocking ), kTerraAmdErrNoDevice );
-    }
-    if ( t.cap_px < npx ) {
-        if ( t.d_pixels ) ( void ) hipFree ( t.d_pixels );
-        if ( t.d_results ) ( void ) hipFree ( t.d_results );
-        t.d_pixels = t.d_results = nullptr; t.cap_px = 0;
-        HIP_TRY ( hipMalloc ( &t.d_pixels, npx * 12 ), kTerraAmdErrNoDevice );
-        HIP_TRY ( hipMalloc ( &t.d_results, npx * 16 ), kTerraAmdErrNoDevice );
-        t.cap_px = npx;
-    }
-    return 0;
+    if ( t.device >= 0 && t.device != device ) t.release();          // (its scratch lives on the old device)
+    return t.prepare ( device, npx );
 }
 extern "C" size_t terra_amd_thread_staging_bytes ( void ) { return t_slot.cap_px * 28; }
 
@@ -1576,19 +1568,17 @@ static int render_host ( const TerraCamera* cam, Scene* s, const TerraFramebuffe
     // sharded over them and gathered (render_host_multi); a small one -- the reference client's 128-pixel tiles, called from its worker threads
     // (satellite/src/Renderer.cpp:70-98,316-350) -- goes whole to ONE device, the calling thread's: threads are dealt to the devices round-robin when they first call, so
     // eight workers drive eight GPUs and a thread's stream and staging buffers stay on one device.
-    const Scene::Replica* replica = nullptr;
-    if ( s->devices.size() > 1 && s->device_ok ) {
-        if ( w * h >= ( size_t ) 256 * 256 * s->devices.size() ) return render_host_multi ( cam, s, fb, x, y, w, h, 64 );
+    const Scene::Replica* r = &primary ( s );
+    if ( s->replicas.size() > 1 && s->device_ok ) {
+        if ( w * h >= ( size_t ) 256 * 256 * s->replicas.size() ) return render_host_multi ( cam, s, fb, x, y, w, h, 64 );
         static thread_local int ordinal = -1;
         if ( ordinal < 0 ) ordinal = g_thread_ordinals.fetch_add ( 1, std::memory_order_relaxed );
-        const size_t k = ( size_t ) ordinal % s->devices.size();
-        if ( k > 0 && k - 1 < s->extra.size() ) replica = &s->extra[k - 1];
+        r = &s->replicas[ ( size_t ) ordinal % s->replicas.size()];
     }
-    const int device = replica ? replica->device : s->device;
     DevRenderParams p;
-    int rc = fill_params ( s, cam, fb->width, fb->height, x, y, w, h, 64, 0, 1, p, replica );
+    int rc = fill_params ( s, *r, cam, fb->width, fb->height, x, y, w, h, 64, 0, 1, p );
     if ( rc ) return rc;
-    rc = slot_prepare ( device, w * h );
+    rc = slot_prepare ( r->device, w * h );
     if ( rc ) return rc;
     ThreadSlot& t = t_slot;
     // the staging buffer holds the rectangle only (rows of w pixels); the kernel addresses it through st_x / st_y / st_pitch while
@@ -1599,7 +1589,7 @@ static int render_host ( const TerraCamera* cam, Scene* s, const TerraFramebuffe
     char* hpix = ( char* ) fb->pixels + ( y * fb->width + x ) * 12;
     HIP_TRY ( hipMemcpy2DAsync ( t.d_results, w * 16, hres, rpitch, w * 16, h, hipMemcpyHostToDevice, t.stream ), kTerraAmdErrLaunch );
     p.pixels = ( float* ) t.d_pixels; p.results = t.d_results; p.rand_calls = nullptr;
-    if ( int lrc = launch_render ( s, p, t.stream, &t, device ) ) return lrc;
+    if ( int lrc = launch_render ( s, p, r->device, t.stream, &t ) ) return lrc;
     HIP_TRY ( hipMemcpy2DAsync ( ( void* ) hres, rpitch, t.d_results, w * 16, w * 16, h, hipMemcpyDeviceToHost, t.stream ), kTerraAmdErrLaunch );
     HIP_TRY ( hipMemcpy2DAsync ( hpix, ppitch, t.d_pixels, w * 12, w * 12, h, hipMemcpyDeviceToHost, t.stream ), kTerraAmdErrLaunch );
     HIP_TRY ( hipStreamSynchronize ( t.stream ), kTerraAmdErrLaunch );
@@ -1619,71 +1609,73 @@ static int render_host_multi ( const TerraCamera* cam, Scene* s, const TerraFram
     if ( !s->device_ok ) return fail ( kTerraAmdErrNoDevice, "scene has no device replica: %s", s->commit_error.c_str() );
     if ( tile == 0 || tile % 16 != 0 ) return fail ( kTerraAmdErrBadArgument, "tile_size %zu must be a positive multiple of 16", tile );
     std::lock_guard<std::mutex> lock ( s->multi_lock );
-    const int world = ( int ) s->devices.size();
-    if ( world < 1 || s->extra.size() + 1 != ( size_t ) world ) return fail ( kTerraAmdErrNotCommitted, "the scene's device set changed: commit again" );
-    if ( !s->multi ) { s->multi = new MultiCtx(); s->multi->dev.resize ( ( size_t ) world ); for ( int k = 0; k < world; ++k ) s->multi->dev[ ( size_t ) k].device = s->devices[ ( size_t ) k]; }
-    MultiCtx& m = *s->multi;
+    const int world = ( int ) s->replicas.size();
     const size_t npx = w * h;
     std::vector<size_t> counts ( ( size_t ) world ); size_t total = 0;
     for ( int k = 0; k < world; ++k ) { counts[ ( size_t ) k] = ( size_t ) tiles_of_rank ( w, h, tile, k, world ) * tile * tile * 7; total += counts[ ( size_t ) k]; }
-    for ( int k = 0; k < world; ++k ) {
-        MultiCtx::PerDevice& q = m.dev[ ( size_t ) k];
-        HIP_TRY ( hipSetDevice ( q.device ), kTerraAmdErrNoDevice );
-        if ( !q.stream ) HIP_TRY ( hipStreamCreateWithFlags ( &q.stream, hipStreamNonBlocking ), kTerraAmdErrNoDevice );
-        if ( q.cap_px < npx ) {
-            if ( q.d_pixels ) ( void ) hipFree ( q.d_pixels );
-            if ( q.d_results ) ( void ) hipFree ( q.d_results );
-            q.d_pixels = q.d_results = nullptr; q.cap_px = 0;
-            HIP_TRY ( hipMalloc ( &q.d_pixels, npx * 12 ), kTerraAmdErrNoDevice ); HIP_TRY ( hipMalloc ( &q.d_results, npx * 16 ), kTerraAmdErrNoDevice );
-            q.cap_px = npx;
-        }
-        if ( q.packed_floats < counts[ ( size_t ) k] ) {
-            if ( q.d_packed ) ( void ) hipFree ( q.d_packed );
-            q.d_packed = nullptr; q.packed_floats = 0;
-            HIP_TRY ( hipMalloc ( ( void** ) &q.d_packed, counts[ ( size_t ) k] * sizeof ( float ) ), kTerraAmdErrNoDevice );
-            q.packed_floats = counts[ ( size_t ) k];
-        }
-        if ( k == 0 && m.recv_floats < total ) {
-            if ( m.d_recv ) ( void ) hipFree ( m.d_recv );
-            m.d_recv = nullptr; m.recv_floats = 0;
-            HIP_TRY ( hipMalloc ( ( void** ) &m.d_recv, total * sizeof ( float ) ), kTerraAmdErrNoDevice );
-            m.recv_floats = total;
-        }
-    }
-    const size_t rpitch = fb->width * 16, ppitch = fb->width * 12;
-    const char* hres = ( const char* ) fb->results + ( y * fb->width + x ) * 16;
-    char* hpix = ( char* ) fb->pixels + ( y * fb->width + x ) * 12;
     std::vector<DevRenderParams> params ( ( size_t ) world );
-    for ( int k = 0; k < world; ++k ) {          // every device: sums up, its tiles rendered, its tiles packed -- queued on its own stream, nothing waits here
-        MultiCtx::PerDevice& q = m.dev[ ( size_t ) k];
-        HIP_TRY ( hipSetDevice ( q.device ), kTerraAmdErrNoDevice );
-        DevRenderParams& p = params[ ( size_t ) k];
-        if ( int rc = fill_params ( s, cam, fb->width, fb->height, x, y, w, h, tile, k, world, p, k ? &s->extra[ ( size_t ) k - 1] : nullptr ) ) return rc;
-        p.st_x = ( uint32_t ) x; p.st_y = ( uint32_t ) y; p.st_pitch = ( uint32_t ) w;
-        p.pixels = ( float* ) q.d_pixels; p.results = q.d_results; p.rand_calls = nullptr;
-        HIP_TRY ( hipMemcpy2DAsync ( q.d_results, w * 16, hres, rpitch, w * 16, h, hipMemcpyHostToDevice, q.stream ), kTerraAmdErrLaunch );
-        if ( int rc = launch_render ( s, p, q.stream, nullptr, q.device ) ) return rc;
-        HIP_TRY ( terra_launch_tiles ( true, ( float* ) q.d_pixels, q.d_results, ( uint32_t ) w, 0, 0, ( uint32_t ) w, ( uint32_t ) h, ( uint32_t ) tile, ( uint32_t ) k, ( uint32_t ) world, q.d_packed, q.stream ), kTerraAmdErrLaunch );
+    Scene::Replica& r0 = s->replicas[0];
+    int queued = 0;          // replicas whose streams have been given work
+    int first = [&] () -> int {
+        for ( int k = 0; k < world; ++k ) {
+            Scene::Replica& r = s->replicas[ ( size_t ) k];
+            if ( int rc = r.staging.prepare ( r.device, npx ) ) return rc;
+            if ( r.packed_floats < counts[ ( size_t ) k] ) {
+                if ( r.d_packed ) ( void ) hipFree ( r.d_packed );
+                r.d_packed = nullptr; r.packed_floats = 0;
+                HIP_TRY ( hipMalloc ( ( void** ) &r.d_packed, counts[ ( size_t ) k] * sizeof ( float ) ), kTerraAmdErrNoDevice );
+                r.packed_floats = counts[ ( size_t ) k];
+            }
+            if ( k == 0 && r.recv_floats < total ) {
+                if ( r.d_recv ) ( void ) hipFree ( r.d_recv );
+                r.d_recv = nullptr; r.recv_floats = 0;
+                HIP_TRY ( hipMalloc ( ( void** ) &r.d_recv, total * sizeof ( float ) ), kTerraAmdErrNoDevice );
+                r.recv_floats = total;
+            }
+        }
+        const size_t rpitch = fb->width * 16, ppitch = fb->width * 12;
+        const char* hres = ( const char* ) fb->results + ( y * fb->width + x ) * 16;
+        char* hpix = ( char* ) fb->pixels + ( y * fb->width + x ) * 12;
+        for ( int k = 0; k < world; ++k ) {          // every device: sums up, its tiles rendered, its tiles packed -- queued on its own stream, nothing waits here
+            const Scene::Replica& r = s->replicas[ ( size_t ) k]; const Staging& q = r.staging;
+            HIP_TRY ( hipSetDevice ( r.device ), kTerraAmdErrNoDevice );
+            DevRenderParams& p = params[ ( size_t ) k];
+            if ( int rc = fill_params ( s, r, cam, fb->width, fb->height, x, y, w, h, tile, k, world, p ) ) return rc;
+            p.st_x = ( uint32_t ) x; p.st_y = ( uint32_t ) y; p.st_pitch = ( uint32_t ) w;
+            p.pixels = ( float* ) q.d_pixels; p.results = q.d_results; p.rand_calls = nullptr;
+            queued = k + 1;
+            HIP_TRY ( hipMemcpy2DAsync ( q.d_results, w * 16, hres, rpitch, w * 16, h, hipMemcpyHostToDevice, q.stream ), kTerraAmdErrLaunch );
+            if ( int rc = launch_render ( s, p, r.device, q.stream ) ) return rc;
+            HIP_TRY ( terra_launch_tiles ( true, ( float* ) q.d_pixels, q.d_results, ( uint32_t ) w, 0, 0, ( uint32_t ) w, ( uint32_t ) h, ( uint32_t ) tile, ( uint32_t ) k, ( uint32_t ) world, r.d_packed, q.stream ), kTerraAmdErrLaunch );
+        }
+        {   // the one collective
+            std::vector<const float*> send ( ( size_t ) world ); std::vector<hipStream_t> streams ( ( size_t ) world );
+            for ( int k = 0; k < world; ++k ) { send[ ( size_t ) k] = s->replicas[ ( size_t ) k].d_packed; streams[ ( size_t ) k] = s->replicas[ ( size_t ) k].staging.stream; }
+            std::string err;
+            if ( !multigpu::gather_to_first ( devices_of ( s ), send, counts, r0.d_recv, streams, err ) ) return fail ( kTerraAmdErrLaunch, "%s", err.c_str() );
+            ++s->gathers; s->last_gather_bytes = total * sizeof ( float );
+        }
+        const Staging& q0 = r0.staging;
+        HIP_TRY ( hipSetDevice ( r0.device ), kTerraAmdErrNoDevice );
+        size_t off = 0;
+        for ( int k = 0; k < world; ++k ) {
+            HIP_TRY ( terra_launch_tiles ( false, ( float* ) q0.d_pixels, q0.d_results, ( uint32_t ) w, 0, 0, ( uint32_t ) w, ( uint32_t ) h, ( uint32_t ) tile, ( uint32_t ) k, ( uint32_t ) world, r0.d_recv + off, q0.stream ), kTerraAmdErrLaunch );
+            off += counts[ ( size_t ) k];
+        }
+        HIP_TRY ( hipMemcpy2DAsync ( ( void* ) hres, rpitch, q0.d_results, w * 16, w * 16, h, hipMemcpyDeviceToHost, q0.stream ), kTerraAmdErrLaunch );
+        HIP_TRY ( hipMemcpy2DAsync ( hpix, ppitch, q0.d_pixels, w * 12, w * 12, h, hipMemcpyDeviceToHost, q0.stream ), kTerraAmdErrLaunch );
+        return 0;
+    } ();
+    // the one exit, failed or not: every stream that was given work is drained (the next call reuses its buffers), the primary device is current, the first error returned
+    for ( int k = 0; k < queued; ++k ) {
+        const Staging& q = s->replicas[ ( size_t ) k].staging;
+        hipError_t e = hipSetDevice ( q.device );
+        if ( e == hipSuccess ) e = hipStreamSynchronize ( q.stream );
+        if ( e != hipSuccess && !first ) first = fail ( kTerraAmdErrLaunch, "render_multi: stream of device %d: %s", q.device, hipGetErrorString ( e ) );
     }
-    {   // the one collective
-        std::vector<const float*> send ( ( size_t ) world ); std::vector<hipStream_t> streams ( ( size_t ) world );
-        for ( int k = 0; k < world; ++k ) { send[ ( size_t ) k] = m.dev[ ( size_t ) k].d_packed; streams[ ( size_t ) k] = m.dev[ ( size_t ) k].stream; }
-        std::string err;
-        if ( !multigpu::gather_to_first ( s->devices, send, counts, m.d_recv, streams, err ) ) return fail ( kTerraAmdErrLaunch, "%s", err.c_str() );
-        ++m.gathers; m.last_gather_bytes = total * sizeof ( float );
-    }
-    MultiCtx::PerDevice& q0 = m.dev[0];
-    HIP_TRY ( hipSetDevice ( q0.device ), kTerraAmdErrNoDevice );
-    size_t off = 0;
-    for ( int k = 0; k < world; ++k ) {
-        HIP_TRY ( terra_launch_tiles ( false, ( float* ) q0.d_pixels, q0.d_results, ( uint32_t ) w, 0, 0, ( uint32_t ) w, ( uint32_t ) h, ( uint32_t ) tile, ( uint32_t ) k, ( uint32_t ) world, m.d_recv + off, q0.stream ), kTerraAmdErrLaunch );
-        off += counts[ ( size_t ) k];
-    }
-    HIP_TRY ( hipMemcpy2DAsync ( ( void* ) hres, rpitch, q0.d_results, w * 16, w * 16, h, hipMemcpyDeviceToHost, q0.stream ), kTerraAmdErrLaunch );
-    HIP_TRY ( hipMemcpy2DAsync ( hpix, ppitch, q0.d_pixels, w * 12, w * 12, h, hipMemcpyDeviceToHost, q0.stream ), kTerraAmdErrLaunch );
-    HIP_TRY ( hipStreamSynchronize ( q0.stream ), kTerraAmdErrLaunch );
-    for ( int k = 1; k < world; ++k ) { HIP_TRY ( hipSetDevice ( m.dev[ ( size_t ) k].device ), kTerraAmdErrNoDevice ); HIP_TRY ( hipStreamSynchronize ( m.dev[ ( size_t ) k].stream ), kTerraAmdErrLaunch ); }
-    HIP_TRY ( hipSetDevice ( s->device ), kTerraAmdErrNoDevice );
+    const hipError_t e = hipSetDevice ( r0.device );
+    if ( e != hipSuccess && !first ) first = fail ( kTerraAmdErrNoDevice, "hipSetDevice ( %d ): %s", r0.device, hipGetErrorString ( e ) );
+    if ( first ) return first;
     for ( int k = 0; k < world; ++k ) account_launch ( s, params[ ( size_t ) k] );
     return 0;
 }
@@ -1694,11 +1686,11 @@ extern "C" int terra_amd_multi_info ( HTerraScene h, TerraAmdMultiInfo* out ) {
     Scene* s = S ( h );
     if ( !out ) return fail ( kTerraAmdErrBadArgument, "null output" );
     memset ( out, 0, sizeof *out );
-    out->devices = ( int ) ( s->devices.empty() ? 1 : s->devices.size() );
-    for ( size_t k = 0; k < s->devices.size() && k < 16; ++k ) out->device[k] = s->devices[k];
-    out->replicas = s->device_ok ? ( int ) s->extra.size() + 1 : 0;
+    out->devices = ( int ) ( s->replicas.empty() ? 1 : s->replicas.size() );
+    for ( size_t k = 0; k < s->replicas.size() && k < 16; ++k ) out->device[k] = s->replicas[k].device;
+    out->replicas = s->device_ok ? ( int ) s->replicas.size() : 0;
     std::lock_guard<std::mutex> lock ( s->multi_lock );
-    out->gathers = s->multi ? s->multi->gathers : 0; out->last_gather_bytes = s->multi ? s->multi->last_gather_bytes : 0;
+    out->gathers = s->gathers; out->last_gather_bytes = s->last_gather_bytes;
     out->process_collectives = multigpu::collectives_issued(); out->rehearsed_gathers = multigpu::gathers_rehearsed(); out->rccl_version = multigpu::rccl_version(); out->communicator_ranks = multigpu::communicator_ranks();
     snprintf ( out->rccl_library, sizeof out->rccl_library, "%s", multigpu::rccl_path().c_str() );
     return 0;
@@ -1743,7 +1735,7 @@ int need_device() { return terra_amd_device_count() > 0 ? 0 : fail ( kTerraAmdEr
 int need_scene ( Scene* s ) {
     if ( !s->committed ) return fail ( kTerraAmdErrNotCommitted, "scene not committed" );
     if ( !s->device_ok ) return fail ( kTerraAmdErrNoDevice, "scene has no device replica: %s", s->commit_error.c_str() );
-    ( void ) hipSetDevice ( s->device );
+    ( void ) hipSetDevice ( primary ( s ).device );
     return 0;
 }
 }
@@ -1780,20 +1772,20 @@ extern "C" int terra_amd_unit_bvh_traverse ( HTerraScene hs, int n, const float*
     Scene* s = S ( hs ); int rc = need_scene ( s ); if ( rc ) return rc;
     Unit u; auto a = u.in ( o, 3 * ( size_t ) n ); auto b = u.in ( d, 3 * ( size_t ) n );
     auto f = u.out ( found, n ); auto pr = u.out ( prim, n ); auto pt = u.out ( point3, 3 * ( size_t ) n );
-    return u.finish ( u.ok ? terra_unit_bvh_traverse ( s->dev, n, a, b, f, pr, pt ) : hipSuccess );
+    return u.finish ( u.ok ? terra_unit_bvh_traverse ( primary ( s ).dev, n, a, b, f, pr, pt ) : hipSuccess );
 }
 extern "C" int terra_amd_unit_bvh_traverse_fast ( HTerraScene hs, int n, const float* o, const float* d, int* found, uint32_t* prim, float* point3, uint32_t* nodes_visited ) {
     Scene* s = S ( hs ); int rc = need_scene ( s ); if ( rc ) return rc;
-    if ( !s->dev.fast_nodes_h ) return fail ( kTerraAmdErrBadArgument, "the committed scene has no fast tree (terra_amd_set_tree_mode 1, or 2 on a scene that is not LDS-resident)" );
+    if ( !primary ( s ).dev.fast_nodes_h ) return fail ( kTerraAmdErrBadArgument, "the committed scene has no fast tree (terra_amd_set_tree_mode 1, or 2 on a scene that is not LDS-resident)" );
     Unit u; auto a = u.in ( o, 3 * ( size_t ) n ); auto b = u.in ( d, 3 * ( size_t ) n );
     auto f = u.out ( found, n ); auto pr = u.out ( prim, n ); auto pt = u.out ( point3, 3 * ( size_t ) n ); auto nv = u.out ( nodes_visited, n );
-    return u.finish ( u.ok ? terra_unit_bvh_traverse_fast ( s->dev, n, a, b, f, pr, pt, nv ) : hipSuccess );
+    return u.finish ( u.ok ? terra_unit_bvh_traverse_fast ( primary ( s ).dev, n, a, b, f, pr, pt, nv ) : hipSuccess );
 }
 extern "C" int terra_amd_unit_raycast ( HTerraScene hs, int n, const float* o, const float* d, int* obj, int* tri, float* point3, float* surface47 ) {
     Scene* s = S ( hs ); int rc = need_scene ( s ); if ( rc ) return rc;
     Unit u; auto a = u.in ( o, 3 * ( size_t ) n ); auto b = u.in ( d, 3 * ( size_t ) n );
     auto ob = u.out ( obj, n ); auto tr = u.out ( tri, n ); auto pt = u.out ( point3, 3 * ( size_t ) n ); auto sf = u.out ( surface47, 47 * ( size_t ) n );
-    return u.finish ( u.ok ? terra_unit_raycast ( s->dev, n, a, b, ob, tr, pt, sf ) : hipSuccess );
+    return u.finish ( u.ok ? terra_unit_raycast ( primary ( s ).dev, n, a, b, ob, tr, pt, sf ) : hipSuccess );
 }
 extern "C" int terra_amd_unit_trace ( HTerraScene hs, int n, const float* o, const float* d, const uint64_t* stateB, const uint64_t* incB, float* radiance3, uint32_t* rand_calls ) {
     Scene* s = S ( hs ); int rc = need_scene ( s ); if ( rc ) return rc;
@@ -1801,7 +1793,7 @@ extern "C" int terra_amd_unit_trace ( HTerraScene hs, int n, const float* o, con
         return fail ( kTerraAmdErrBadArgument, "integrator needs a light" );
     Unit u; auto a = u.in ( o, 3 * ( size_t ) n ); auto b = u.in ( d, 3 * ( size_t ) n ); auto sb = u.in ( stateB, n ); auto ib = u.in ( incB, n );
     auto L = u.out ( radiance3, 3 * ( size_t ) n ); auto rcalls = u.out ( rand_calls, n );
-    return u.finish ( u.ok ? terra_unit_trace ( s->dev, ( int ) s->opts.integrator, ( uint32_t ) s->opts.bounces, n, a, b, sb, ib, L, rcalls ) : hipSuccess );
+    return u.finish ( u.ok ? terra_unit_trace ( primary ( s ).dev, ( int ) s->opts.integrator, ( uint32_t ) s->opts.bounces, n, a, b, sb, ib, L, rcalls ) : hipSuccess );
 }
 extern "C" int terra_amd_unit_bsdf ( int kind, int n, float* surfaces47, const float* e3, const float* wo3, float* wi3, float* pdf, float* f3 ) {
     if ( need_device() ) return kTerraAmdErrNoDevice;

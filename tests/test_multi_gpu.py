@@ -153,3 +153,65 @@ def test_rehearsal_of_several_replicas_on_one_device(H, orc_lib, devmath_mode):
     two = (C.c_int * 2)(0, 0)
     assert Lg.set_devices(two, 2) < 0 and "twice" in runtime.last_error()          # the hook is off again
     Lg.clear_error()
+
+
+@pytest.mark.gpu
+def test_work_counters_sum_over_rehearsed_replicas(H):
+    """terra_amd_get_stats, terra_amd_debug_faults and terra_amd_reset_stats cover every replica of a scene: the same frame rendered through
+    terra_amd_render_multi by 2 and 3 replicas (the rehearsal on the one device) is bit-identical to the one-device frame, so the rays, node visits, triangle
+    tests and hits summed over the replicas are the one device's too. Scenes: Cornell Direct (reference tree, LDS-resident) and a soup on the fast tree."""
+    from test_oracle_vs_reference import soup_scene
+    Lg = runtime.load()
+    faults = Lg.fn("terra_amd_debug_faults", C.c_longlong, [C.c_void_p])
+    big = soup_scene(H, 1500, 91, integrator=2); big.width, big.height, big.spp = 136, 100, 2
+    fields = ("rays", "nodes", "tri_tests", "hits")
+    for d in (scenes.cornell_box(128, 96, 4, integrator=1), big):
+        got = {}
+        try:
+            for world in (1, 2, 3):
+                Lg.clear_error()
+                if world == 1:
+                    runtime.check(Lg.set_devices(None, 0))
+                else:
+                    runtime.check(Lg.debug_replicas_share_device(1))
+                    runtime.check(Lg.set_devices((C.c_int * world)(*([0] * world)), world), "terra_amd_set_devices")
+                scene = scenes.build_scene(Lg, d)
+                assert runtime.last_error() == "", runtime.last_error()
+                runtime.check(Lg.set_work_counters(scene, 1))
+                info = runtime.MultiInfo(); runtime.check(Lg.multi_info(scene, C.byref(info)))
+                assert info.replicas == world
+                fb = api.Framebuffer(Lg, d.width, d.height); cam = scenes.camera_of(d)
+                runtime.check(Lg.render_multi(C.byref(cam), scene, C.byref(fb.fb), 0, 0, d.width, d.height, 32), runtime.last_error())
+                st = runtime.Stats(); runtime.check(Lg.get_stats(scene, C.byref(st)))
+                got[world] = ({f: getattr(st, f) for f in fields}, H.bits(fb.results["acc"]).copy())
+                assert faults(scene) == 0, (d.name, world)
+                runtime.check(Lg.reset_stats(scene))
+                st = runtime.Stats(); runtime.check(Lg.get_stats(scene, C.byref(st)))
+                assert all(v == 0 for v in st.as_dict().values()), (d.name, world, st.as_dict())
+                fb.destroy(); Lg.scene_destroy(scene)
+        finally:
+            Lg.set_devices(None, 0); Lg.debug_replicas_share_device(0)
+        assert min(got[1][0].values()) > 0, got[1][0]
+        for world in (2, 3):
+            assert np.array_equal(got[world][1], got[1][1]), (d.name, world)
+            assert got[world][0] == got[1][0], (d.name, world, got[world][0], got[1][0])
+
+
+@pytest.mark.gpu
+def test_primary_replica_follows_the_device_set():
+    """The scene's primary copy is the first replica, on the set's first device: terra_amd_set_device after terra_amd_set_devices does not move it off the set.
+    A box with one GPU cannot show the cross-device mismatch this rules out (set {2, 3}, then device 1: the primary on 1 while the set began with 2, pointers of one
+    device launched on another); the guarantee comes from the data structure -- there is no primary apart from replicas[0] -- and this checks the bookkeeping."""
+    Lg = runtime.load()
+    d = scenes.cornell_box(64, 48, 1, integrator=1)
+    try:
+        runtime.check(Lg.debug_replicas_share_device(1))
+        runtime.check(Lg.set_devices((C.c_int * 2)(0, 0), 2))
+        runtime.check(Lg.set_device(0))
+        scene = scenes.build_scene(Lg, d)
+        assert runtime.last_error() == "", runtime.last_error()
+        info = runtime.MultiInfo(); runtime.check(Lg.multi_info(scene, C.byref(info)))
+        assert info.devices == 2 and info.device[0] == 0 and info.device[1] == 0 and info.replicas == 2
+        Lg.scene_destroy(scene)
+    finally:
+        Lg.set_devices(None, 0); Lg.debug_replicas_share_device(0)

@@ -4,6 +4,9 @@
 hipError_t terra_launch_render ( const DevRenderParams&, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_launch_job_streams ( const DevRenderParams&, hipStream_t ) { return hipErrorNoDevice; }
 size_t terra_job_streams_bytes ( const DevRenderParams& ) { return 0; }
+size_t terra_block_order_bytes ( const DevRenderParams&, bool ) { return 0; }
+uint32_t   terra_job_order_min_blocks ( void ) { return 256; }
+hipError_t terra_launch_block_order ( const DevRenderParams&, uint32_t*, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_fill_sincos24 ( float2*, hipStream_t ) { return hipErrorNoDevice; }
 bool       terra_render_wants_queue ( const DevRenderParams& ) { return false; }
 uint32_t   terra_render_blocks ( const DevRenderParams& ) { return 0; }
