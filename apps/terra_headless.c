@@ -31,6 +31,12 @@
  *       [--integrator simple|direct|mis|normals|depth] [--tonemap none|linear|reinhard|filmic|uncharted2]
  *       [--camera px py pz dx dy dz] [--fov deg] [--exposure e] [--gamma g] [--jitter j]
  *       [--no-flip-z] [--normals apollo|file] [--dump-scene file] [--no-render] [--fast-tree | --replica-tree] [--sample-split n] [--seed n] [--tile n] [--gpus n]
+ *       [--environment map.hdr|map.pfm] [--environment-color r g b] [--env-light] [--env-sampling off|table|mis]
+ *
+ * Environment: the scene's environment attribute is a constant (--environment-color, default 0.4 0.52 1) or a lat-long map (--environment: Radiance .hdr with flat
+ * or new-style run-length-encoded scanlines, orientation -Y H +X W, texel = m 2^(e - 136); or .pfm, either byte order, bottom row first), bound as a 3-component
+ * float texture with terra_attribute_init_cubemap. The reference drops the environment term; libterra_amd.so adds it with --env-light, samples the map with
+ * --env-sampling table (a TerraDistribution2D over the map) and weights that sample against Direct + MIS's BSDF ray with --env-sampling mis.
  */
 #include <ctype.h>
 #include <math.h>
@@ -48,6 +54,9 @@ int         terra_amd_init ( void ) __attribute__ ( ( weak ) );
 int         terra_amd_set_devices ( const int*, int ) __attribute__ ( ( weak ) );
 int         terra_amd_device_count ( void ) __attribute__ ( ( weak ) );
 int         terra_amd_render_multi ( const TerraCamera*, HTerraScene, const TerraFramebuffer*, size_t, size_t, size_t, size_t, size_t ) __attribute__ ( ( weak ) );
+int         terra_amd_set_environment_lighting ( HTerraScene, int ) __attribute__ ( ( weak ) );
+int         terra_amd_set_environment_sampling ( HTerraScene, int ) __attribute__ ( ( weak ) );
+int         terra_amd_set_environment_mis ( HTerraScene, int ) __attribute__ ( ( weak ) );
 
 /* ---- growable arrays ------------------------------------------------------------------------ */
 #define VEC(T) struct { T* d; size_t n, cap; }
@@ -429,6 +438,78 @@ static int write_image ( const char* path, const TerraFramebuffer* fb ) {
     return write_png ( path, fb );      /* png assumed by default, as Visualization.cpp:313-316 */
 }
 
+/* ---- environment maps in ----------------------------------------------------------------------- */
+/* A lat-long map as W x H x 3 floats, row 0 = the top (+y) row, the order the lat-long lookup reads. Returns NULL with `err` set; the caller exits 65. */
+static float* map_fail ( char* err, size_t n, const char* msg, FILE* f, float* px ) { snprintf ( err, n, "%s", msg ); if ( f ) fclose ( f ); free ( px ); return NULL; }
+static int read_line ( FILE* f, char* buf, size_t n ) {            /* one header line without its newline; 0 at end of file */
+    size_t k = 0; int c;
+    while ( ( c = fgetc ( f ) ) != EOF && c != '\n' ) if ( k + 1 < n ) buf[k++] = ( char ) c;
+    buf[k] = 0;
+    return c != EOF || k > 0;
+}
+static float* load_hdr ( const char* path, size_t* W, size_t* H, char* err, size_t en ) {
+    FILE* f = fopen ( path, "rb" ); if ( !f ) return map_fail ( err, en, "cannot open", NULL, NULL );
+    char line[512];
+    if ( !read_line ( f, line, sizeof line ) || strncmp ( line, "#?", 2 ) ) return map_fail ( err, en, "not a Radiance file (no #? signature)", f, NULL );
+    for ( ;; ) {                                                    /* header lines up to the blank one */
+        if ( !read_line ( f, line, sizeof line ) ) return map_fail ( err, en, "truncated header", f, NULL );
+        if ( !line[0] ) break;
+        if ( !strncmp ( line, "FORMAT=", 7 ) && strcmp ( line + 7, "32-bit_rle_rgbe" ) ) return map_fail ( err, en, "unsupported FORMAT (only 32-bit_rle_rgbe)", f, NULL );
+    }
+    long h = 0, w = 0; char tail;
+    if ( !read_line ( f, line, sizeof line ) || sscanf ( line, "-Y %ld +X %ld %c", &h, &w, &tail ) != 2 ) return map_fail ( err, en, "unsupported orientation (only -Y H +X W)", f, NULL );
+    if ( w < 1 || h < 1 || w > 65535 || h > 65535 ) return map_fail ( err, en, "size out of range (1 .. 65535 per dimension)", f, NULL );
+    float* px = malloc ( ( size_t ) w * h * 3 * sizeof ( float ) );
+    unsigned char* row = malloc ( ( size_t ) w * 4 );
+    if ( !px || !row ) { free ( row ); return map_fail ( err, en, "out of memory for the map", f, px ); }
+    for ( long y = 0; y < h; ++y ) {
+        unsigned char q[4];
+        if ( fread ( q, 1, 4, f ) != 4 ) { free ( row ); return map_fail ( err, en, "truncated pixel data", f, px ); }
+        if ( w >= 8 && w <= 0x7fff && q[0] == 2 && q[1] == 2 && ( ( q[2] << 8 ) | q[3] ) == w ) {      /* new-style RLE: the four channels one after the other */
+            for ( int ch = 0; ch < 4; ++ch ) {
+                for ( long x = 0; x < w; ) {
+                    int c = fgetc ( f ), run;
+                    if ( c == EOF || c == 0 ) { free ( row ); return map_fail ( err, en, c == EOF ? "truncated pixel data" : "bad run length", f, px ); }
+                    run = c > 128 ? c - 128 : c;
+                    if ( x + run > w ) { free ( row ); return map_fail ( err, en, "run past the end of a scanline", f, px ); }
+                    if ( c > 128 ) { int v = fgetc ( f ); if ( v == EOF ) { free ( row ); return map_fail ( err, en, "truncated pixel data", f, px ); } for ( int k = 0; k < run; ++k ) row[4 * ( x + k ) + ch] = ( unsigned char ) v; }
+                    else for ( int k = 0; k < run; ++k ) { int v = fgetc ( f ); if ( v == EOF ) { free ( row ); return map_fail ( err, en, "truncated pixel data", f, px ); } row[4 * ( x + k ) + ch] = ( unsigned char ) v; }
+                    x += run;
+                }
+            }
+        } else {                                                    /* flat: q is the first texel */
+            memcpy ( row, q, 4 );
+            if ( w > 1 && fread ( row + 4, 4, ( size_t ) w - 1, f ) != ( size_t ) w - 1 ) { free ( row ); return map_fail ( err, en, "truncated pixel data", f, px ); }
+        }
+        for ( long x = 0; x < w; ++x ) {
+            const unsigned char* t = row + 4 * x; float* o = px + ( ( size_t ) y * w + x ) * 3;
+            for ( int ch = 0; ch < 3; ++ch ) o[ch] = t[3] ? ldexpf ( ( float ) t[ch], ( int ) t[3] - 136 ) : 0.f;
+        }
+    }
+    free ( row ); fclose ( f );
+    *W = ( size_t ) w; *H = ( size_t ) h;
+    return px;
+}
+static float* load_pfm ( const char* path, size_t* W, size_t* H, char* err, size_t en ) {
+    FILE* f = fopen ( path, "rb" ); if ( !f ) return map_fail ( err, en, "cannot open", NULL, NULL );
+    char magic[3] = { 0 }; long w = 0, h = 0; double scale = 0.;
+    if ( fscanf ( f, "%2s %ld %ld %lf", magic, &w, &h, &scale ) != 4 || strcmp ( magic, "PF" ) || scale == 0. ) return map_fail ( err, en, "not a colour PFM (PF W H scale)", f, NULL );
+    if ( fgetc ( f ) == EOF ) return map_fail ( err, en, "truncated header", f, NULL );     /* the single whitespace byte before the data */
+    if ( w < 1 || h < 1 || w > 65535 || h > 65535 ) return map_fail ( err, en, "size out of range (1 .. 65535 per dimension)", f, NULL );
+    const size_t n = ( size_t ) w * h * 3;
+    float* px = malloc ( n * sizeof ( float ) );
+    if ( !px ) return map_fail ( err, en, "out of memory for the map", f, NULL );
+    const uint16_t probe = 1; const int host_le = *( const uint8_t* ) &probe == 1, file_le = scale < 0.;
+    for ( long y = h; y-- > 0; ) {                                  /* bottom row first in the file */
+        float* o = px + ( size_t ) y * w * 3;
+        if ( fread ( o, sizeof ( float ), ( size_t ) w * 3, f ) != ( size_t ) w * 3 ) return map_fail ( err, en, "truncated pixel data", f, px );
+        if ( host_le != file_le ) for ( long k = 0; k < w * 3; ++k ) { uint8_t* b = ( uint8_t* ) &o[k], t0 = b[0], t1 = b[1]; b[0] = b[3]; b[1] = b[2]; b[2] = t1; b[3] = t0; }
+    }
+    fclose ( f );
+    *W = ( size_t ) w; *H = ( size_t ) h;
+    return px;
+}
+
 /* ---- main ------------------------------------------------------------------------------------ */
 static int pick ( const char* v, const char* const* names, int n, int dflt ) { for ( int i = 0; i < n; ++i ) if ( strcmp ( v, names[i] ) == 0 ) return i; return dflt; }
 
@@ -439,6 +520,11 @@ static const char* kHelp =
     "  --dump-scene file --no-render --fast-tree | --replica-tree --sample-split n --seed n --tile n\n"
     "  --gpus N (libterra_amd.so only): the scene is replicated on the first N GPUs and the frame's 64-pixel tiles are dealt to them from this one process, one RCCL\n"
     "           gather at the end (terra_amd_set_devices / terra_amd_render_multi); N = 1 runs the same calls on one GPU. Without it: terra_render() on one GPU.\n"
+    "  --environment FILE: a lat-long environment map, Radiance .hdr (flat or RLE scanlines, -Y H +X W) or .pfm (either byte order); up to 65535 x 65535\n"
+    "  --environment-color R G B: the constant environment when no map is given (default 0.4 0.52 1)\n"
+    "  --env-light (libterra_amd.so only): rays that leave the scene add the environment (terra_amd_set_environment_lighting; the reference drops it)\n"
+    "  --env-sampling off|table|mis (libterra_amd.so only, with a map and --env-light): table = Direct / Direct + MIS sample the map through a TerraDistribution2D\n"
+    "           (terra_amd_set_environment_sampling); mis = that, weighted against Direct + MIS's BSDF ray by the power heuristic (terra_amd_set_environment_mis)\n"
     "OBJ/MTL import (--normals apollo, the default): the policy of the reference client's importer (satellite/include/Apollo.h under the\n"
     "options of satellite/src/Scene.cpp:83-93) RESTATED in this tool and pinned by hand-derived fixtures -- restated, not executed: Apollo.h\n"
     "does not compile with this image's toolchains. Everything after the TerraObject fill (commit, render, export) is the pinned path.\n";
@@ -452,6 +538,7 @@ int main ( int argc, char** argv ) {
     const char* dump_path = NULL; int no_render = 0;
     float fov = 45.f, exposure = 1.f, gamma = 2.2f, jitter = 0.f;
     unsigned long long seed = 0;
+    const char* env_path = NULL; float env_rgb[3] = { 0.4f, 0.52f, 1.f }; int env_light = 0, env_sampling = 0;      /* env_sampling: 0 off, 1 table, 2 mis */
     TerraCamera cam; cam.position = terra_f3_set ( 0.f, 1.f, -3.4f ); cam.direction = terra_f3_set ( 0.f, 0.f, 1.f ); cam.up = terra_f3_set ( 0.f, 1.f, 0.f );
     for ( int i = 3; i < argc; ++i ) {
         const char* a = argv[i];
@@ -477,12 +564,30 @@ int main ( int argc, char** argv ) {
         else if ( !strcmp ( a, "--gpus" ) ) gpus = atoi ( NEXT() );
         else if ( !strcmp ( a, "--integrator" ) ) { static const char* const n[] = { "simple", "direct", "mis", "mono", "depth", "normals", "misweights" }; integrator = pick ( NEXT(), n, 7, integrator ); }
         else if ( !strcmp ( a, "--tonemap" ) ) { static const char* const n[] = { "none", "linear", "reinhard", "filmic", "uncharted2" }; tonemap = pick ( NEXT(), n, 5, tonemap ); }
+        else if ( !strcmp ( a, "--environment" ) ) env_path = NEXT();
+        else if ( !strcmp ( a, "--environment-color" ) && i + 3 < argc ) { for ( int k = 0; k < 3; ++k ) env_rgb[k] = ( float ) atof ( argv[i + 1 + k] ); i += 3; }
+        else if ( !strcmp ( a, "--env-light" ) ) env_light = 1;
+        else if ( !strcmp ( a, "--env-sampling" ) ) { const char* v = NEXT(); static const char* const n[] = { "off", "table", "mis" }; env_sampling = pick ( v, n, 3, -1 ); if ( env_sampling < 0 ) { fprintf ( stderr, "terra_headless: --env-sampling off|table|mis\n" ); return 64; } }
         else if ( !strcmp ( a, "--camera" ) && i + 6 < argc ) {
             cam.position = terra_f3_set ( ( float ) atof ( argv[i + 1] ), ( float ) atof ( argv[i + 2] ), ( float ) atof ( argv[i + 3] ) );
             cam.direction = terra_f3_set ( ( float ) atof ( argv[i + 4] ), ( float ) atof ( argv[i + 5] ), ( float ) atof ( argv[i + 6] ) ); i += 6;
         } else { fprintf ( stderr, "terra_headless: unknown option %s\n", a ); return 64; }
     }
     cam.fov = fov;
+    TerraTexture env_tex; memset ( &env_tex, 0, sizeof env_tex );
+    if ( env_path ) {              /* read before the mesh: a bad map is refused before any work */
+        size_t ew = 0, eh = 0; char err[128] = "";
+        const char* ext = strrchr ( env_path, '.' );
+        float* px = ext && ( !strcmp ( ext, ".pfm" ) || !strcmp ( ext, ".PFM" ) ) ? load_pfm ( env_path, &ew, &eh, err, sizeof err ) : load_hdr ( env_path, &ew, &eh, err, sizeof err );
+        if ( !px ) { fprintf ( stderr, "terra_headless: %s: %s\n", env_path, err ); return 65; }
+        double mean[3] = { 0., 0., 0. };
+        for ( size_t k = 0; k < ew * eh; ++k ) for ( int ch = 0; ch < 3; ++ch ) mean[ch] += px[3 * k + ch];
+        fprintf ( stderr, "environment: %zu x %zu, mean %.6g %.6g %.6g\n", ew, eh, mean[0] / ( double ) ( ew * eh ), mean[1] / ( double ) ( ew * eh ), mean[2] / ( double ) ( ew * eh ) );
+        ( void ) terra_texture_init_hdr ( &env_tex, ew, eh, 3, px );      /* (the reference's returns no value: its result is the pixels it allocated) */
+        free ( px );
+        if ( !env_tex.pixels ) { fprintf ( stderr, "terra_headless: %s: cannot make a texture of it\n", env_path ); return 65; }
+        env_tex.filter = kTerraFilterPoint; env_tex.address_mode = kTerraTextureAddressWrap;
+    }
     Model m; memset ( &m, 0, sizeof m );
     if ( !load_obj ( &m, argv[1] ) ) { fprintf ( stderr, "terra_headless: no faces in %s\n", argv[1] ); return 66; }
     FILE* dump = dump_path ? fopen ( dump_path, "w" ) : NULL;
@@ -491,14 +596,24 @@ int main ( int argc, char** argv ) {
     if ( dump ) fclose ( dump );
     if ( no_render ) { printf ( "%s: %zu objects\n", argv[1], terra_scene_count_objects ( scene ) ); terra_scene_destroy ( scene ); return 0; }
     TerraSceneOptions* o = terra_scene_get_options ( scene );
-    TerraFloat3 env = terra_f3_set ( 0.4f, 0.52f, 1.f );
-    terra_attribute_init_constant ( &o->environment_map, &env );
+    TerraFloat3 env = terra_f3_set ( env_rgb[0], env_rgb[1], env_rgb[2] );
+    if ( env_path ) terra_attribute_init_cubemap ( &o->environment_map, &env_tex );
+    else terra_attribute_init_constant ( &o->environment_map, &env );
     o->tonemapping_operator = ( TerraTonemappingOperator ) tonemap; o->accelerator = kTerraAcceleratorBVH; o->sampling_method = kTerraSamplingMethodRandom;
     o->integrator = ( TerraIntegrator ) integrator; o->subpixel_jitter = jitter; o->samples_per_pixel = spp; o->bounces = bounces; o->strata = 4;
     o->manual_exposure = exposure; o->gamma = gamma;
     if ( fast >= 0 && terra_amd_set_tree_mode ) terra_amd_set_tree_mode ( scene, fast );
     if ( split >= 0 && terra_amd_set_sample_split ) terra_amd_set_sample_split ( scene, split );
     if ( have_seed && terra_amd_set_frame_seed ) terra_amd_set_frame_seed ( scene, seed );
+    if ( env_light || env_sampling ) {
+        if ( !terra_amd_set_environment_lighting || !terra_amd_set_environment_sampling || !terra_amd_set_environment_mis )
+            fprintf ( stderr, "terra_headless: --env-light / --env-sampling need libterra_amd.so (this library drops the environment term); ignored\n" );
+        else {
+            if ( env_light ) terra_amd_set_environment_lighting ( scene, 1 );
+            terra_amd_set_environment_sampling ( scene, env_sampling != 0 );
+            terra_amd_set_environment_mis ( scene, env_sampling == 2 );
+        }
+    }
     if ( gpus > 0 ) {          /* several GPUs from this one process: the first `gpus` devices, the first of them primary */
         int devs[64];
         if ( !terra_amd_set_devices || !terra_amd_render_multi ) { fprintf ( stderr, "terra_headless: --gpus needs libterra_amd.so\n" ); return 64; }
@@ -517,5 +632,6 @@ int main ( int argc, char** argv ) {
     printf ( "%s: %zu triangles, %zu materials -> %s (%zux%zu, %zu spp)\n", argv[1], m.faces.n, m.mtls.n, argv[2], W, H, spp );
     terra_framebuffer_destroy ( &fb );
     terra_scene_destroy ( scene );
+    if ( env_path ) terra_texture_destroy ( &env_tex );
     return 0;
 }

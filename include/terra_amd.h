@@ -238,6 +238,16 @@ int  terra_amd_get_sampler_integration ( HTerraScene scene );
 int  terra_amd_set_environment_sampling ( HTerraScene scene, int on );
 int  terra_amd_get_environment_sampling ( HTerraScene scene );
 
+/* Environment MIS (extension, off by default; no counterpart in the reference or the oracle). With environment sampling active (above), Direct + MIS
+   weights its environment sample and its BSDF-sampled ray against each other by the power heuristic, as it already does for the area lights: the environment
+   sample is weighted p_e^2 / (p_e^2 + p_b^2), and a BSDF ray that leaves the scene now adds environment x BSDF x cosine / p_b weighted p_b^2 / (p_b^2 + p_e^2)
+   (p_e: the density with which the environment sample could have produced its direction, 0 below the shading normal's horizon; glass keeps the whole weight on
+   the BSDF ray). Same draws and the same rays as environment sampling alone; far less noise on glossy lobes. Inert for every other integrator, without
+   environment sampling, and for tables that are not a proper density (a negative texel, a total that is not finite and positive). A launch parameter: takes
+   effect at the next render call, no commit needed. */
+int  terra_amd_set_environment_mis ( HTerraScene scene, int on );
+int  terra_amd_get_environment_mis ( HTerraScene scene );
+
 /* Work counters of the device path, summed over all launches since the last
    reset. They define the algorithmic bytes of the roofline:
    bytes = 64*nodes + 36*tri_tests + hits*(36+60) + 12*attr_fetches + 44*pixels.
@@ -378,6 +388,10 @@ int terra_amd_unit_distribution_1d ( const float* f, size_t n, const float* e, i
 /* terra_distribution_2d_init + _sample (src/Terra.c:812-846) over f[ny][nx] at (e1,e2)[m]: xy2[m][2] = (row coordinate, column
    coordinate) as the reference returns them, pdf[m]; marginal_cdf_out[ny] optional */
 int terra_amd_unit_distribution_2d ( const float* f, size_t nx, size_t ny, const float* e12, int m, float* xy2, float* pdf, float* marginal_cdf_out );
+/* the lookup environment MIS uses: for points xy2[m][2] of the unit square, in the order terra_amd_unit_distribution_2d returns them, pdf[m] = the
+   probability the same distribution assigns to the bucket each point lies in ((row, column) = truncated (v ny, u nx); 0 for an empty row) -- bit for bit
+   the pdf that sampling reports for that bucket */
+int terra_amd_unit_distribution_2d_pdf ( const float* f, size_t nx, size_t ny, const float* xy2, int m, float* pdf );
 
 #ifdef __cplusplus
 }

@@ -158,6 +158,10 @@ struct DevScene {
 #define TERRA_KIND_TEX 32
 // ... and the bit that compiles the sampler integration in (terra_amd_set_sampler_integration: the pixel's Halton / stratified sampler feeds the first bounce)
 #define TERRA_KIND_SAMPLER 64
+// ... and the bit that compiles environment MIS in (terra_amd_set_environment_mis: Direct + MIS weights its environment sample against its BSDF ray). A launch
+// parameter: fill_params sets it in DevRenderParams::bsdf_kinds, next to TERRA_KIND_SAMPLER, only where it acts; it selects a variant of its own, so the sampler
+// variant every other environment-sampling render runs is the code it was without it
+#define TERRA_KIND_ENV_MIS 128
 
 // indices into the device counter array (uint64 each); mirrors TerraAmdStats
 enum { kCtrRays = 0, kCtrNodes, kCtrBoxTests, kCtrTriTests, kCtrHits, kCtrSamples, kCtrRandCalls, kCtrAttrFetches, kCtrPixels, kCtrLaunches, kCtrFaults, kCtrTriCulled,

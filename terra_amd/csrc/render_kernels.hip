@@ -881,7 +881,10 @@ static hipError_t launch_mode ( const DevRenderParams& p, size_t lds, hipStream_
         if ( ( p.bsdf_kinds & ~15u ) == 0 ) return launch_kinds<I, MODE, 15> ( p, lds, stream );
     }
     if ( ( p.bsdf_kinds & TERRA_KIND_SAMPLER ) == 0 ) return launch_kinds<I, MODE, TERRA_KINDS_ALL & ~TERRA_KIND_SAMPLER> ( p, lds, stream );      // (the sampler integration costs the generic
-    return launch_kinds<I, MODE, TERRA_KINDS_ALL> ( p, lds, stream );                                                                            //  kernel 11 % when merely compiled in: its own variant)
+    if constexpr ( I == 2 ) {                                                                                                                    //  kernel 11 % when merely compiled in: its own variant)
+        if ( p.bsdf_kinds & TERRA_KIND_ENV_MIS ) return launch_kinds<I, MODE, TERRA_KINDS_ALL | TERRA_KIND_ENV_MIS> ( p, lds, stream );          // (environment MIS: Direct + MIS only, its own variant)
+    }
+    return launch_kinds<I, MODE, TERRA_KINDS_ALL> ( p, lds, stream );
 }
 template <int MODE>
 static hipError_t launch_integrator ( const DevRenderParams& p, size_t lds, hipStream_t stream ) {

@@ -85,3 +85,11 @@ SD float distribution_sample ( const DevDistribution1D& d, float e, float* pdf, 
     t /= curr - prev;
     return ( ( float ) i + t ) / ( float ) d.n;
 }
+// The probability a 2-D distribution (rows: totals row_f[ny] summing to `integral`; row r: f[r * nx ..] summing to row_f[r]) assigns to bucket (row, col):
+// the *pdf distribution_sample reports for the row times the one it reports for the column inside it -- the same float operations in the same order, so a bucket
+// the sampler picks gets a bit-identical probability. An empty row (which the sampler cannot pick) gets 0.
+SD float distribution_2d_prob ( const float* f, const float* row_f, uint32_t nx, float integral, uint32_t row, uint32_t col ) {
+    const float rf = row_f[row];
+    if ( ! ( rf > 0.f ) ) return 0.f;
+    return ( rf / integral ) * ( f[( size_t ) nx * row + col] / rf );
+}

@@ -352,6 +352,7 @@ struct Scene {
     bool env_lighting = false;          // terra_amd_set_environment_lighting: escaping rays add throughput * environment
     bool work_counters = false;         // terra_amd_set_work_counters: the render kernels count rays / nodes / tests / hits / draws (instrumentation, off by default)
     bool env_sampling = false;          // terra_amd_set_environment_sampling: Direct / Direct+MIS sample a lat-long environment through a TerraDistribution2D (built at commit)
+    bool env_mis = false;               // terra_amd_set_environment_mis: Direct+MIS weights that sample against its BSDF ray (a launch parameter)
     int job_order = 1;                  // terra_amd_set_job_order (0 off, 1 on, 2 on for launches of any size): launches that key their streams ahead hand out the pixel blocks no camera ray hits last (launch_render)
     bool sampler_integration = false;   // terra_amd_set_sampler_integration: the pixel's Halton / stratified sampler feeds the first bounce (a launch parameter)
     int fast_max_stack = 1; uint32_t fast_nodes = 0;
@@ -477,6 +478,12 @@ extern "C" int terra_amd_set_environment_sampling ( HTerraScene h, int on ) {
     return 0;
 }
 extern "C" int terra_amd_get_environment_sampling ( HTerraScene h ) { return S ( h )->env_sampling ? 1 : 0; }
+extern "C" int terra_amd_set_environment_mis ( HTerraScene h, int on ) {
+    Scene* s = S ( h ); if ( !s ) return fail ( kTerraAmdErrBadArgument, "null scene" );
+    s->env_mis = on != 0;
+    return 0;
+}
+extern "C" int terra_amd_get_environment_mis ( HTerraScene h ) { return S ( h )->env_mis ? 1 : 0; }
 extern "C" int terra_amd_set_job_order ( HTerraScene h, int on ) {
     if ( on < 0 || on > 2 ) return fail ( kTerraAmdErrBadArgument, "terra_amd_set_job_order: 0 (off), 1 (on) or 2 (on for launches of any size)" );
     S ( h )->job_order = on; return 0;
@@ -1335,6 +1342,9 @@ static int fill_params ( Scene* s, const Scene::Replica& r, const TerraCamera* c
     // environment sampling lives in the same kernel variant; it only acts in the two integrators that sample lights
     if ( r.dev.env_nx && ( p.integrator == kTerraIntegratorDirect || p.integrator == kTerraIntegratorDirectMis ) ) p.bsdf_kinds |= TERRA_KIND_SAMPLER;
     else { p.scene.env_nx = 0; p.scene.env_ny = 0; }
+    // environment MIS: its own variant (TERRA_KIND_ENV_MIS), in Direct + MIS only and only where the table is a proper density (env_monotone: no negative texel,
+    // a finite positive total -- otherwise the sampler's scan may pick buckets whose probability the lookup cannot restate)
+    if ( s->env_mis && p.scene.env_nx && p.scene.env_monotone && p.integrator == kTerraIntegratorDirectMis ) p.bsdf_kinds |= TERRA_KIND_ENV_MIS;
     p.count_level = s->work_counters ? 2 : 0;
     return 0;
 }
@@ -1863,4 +1873,13 @@ extern "C" int terra_amd_unit_distribution_2d ( const float* f, size_t nx, size_
     auto dc = u.out ( cdf.data(), nx * ny ); auto di = u.out ( integrals.data(), ny + 1 ); auto dmc = u.out ( marginal_cdf_out ? marginal_cdf_out : mcdf_tmp.data(), ny ); auto dm = u.out ( mono.data(), ny + 1 );
     auto dxy = u.out ( xy2, ( size_t ) m * 2 ); auto dp = u.out ( pdf, ( size_t ) m );
     return u.finish ( u.ok ? terra_unit_distribution_2d ( df, ( uint32_t ) nx, ( uint32_t ) ny, dc, di, dmc, dm, de, m, dxy, dp ) : hipSuccess );
+}
+extern "C" int terra_amd_unit_distribution_2d_pdf ( const float* f, size_t nx, size_t ny, const float* xy2, int m, float* pdf ) {
+    if ( need_device() ) return kTerraAmdErrNoDevice;
+    if ( nx == 0 || ny == 0 || nx * ny > 0x7fffffffu || m < 0 ) return fail ( kTerraAmdErrBadArgument, "distribution: empty table" );
+    std::vector<float> cdf ( nx * ny ), integrals ( ny + 1 ), mcdf ( ny ); std::vector<uint32_t> mono ( ny + 1 );
+    Unit u; auto df = u.in ( f, nx * ny ); auto dxy = u.in ( xy2, ( size_t ) m * 2 );
+    auto dc = u.out ( cdf.data(), nx * ny ); auto di = u.out ( integrals.data(), ny + 1 ); auto dmc = u.out ( mcdf.data(), ny ); auto dm = u.out ( mono.data(), ny + 1 );
+    auto dp = u.out ( pdf, ( size_t ) m );
+    return u.finish ( u.ok ? terra_unit_distribution_2d_pdf ( df, ( uint32_t ) nx, ( uint32_t ) ny, dc, di, dmc, dm, dxy, m, dp ) : hipSuccess );
 }

@@ -1199,7 +1199,37 @@ TD bool env_reaches_by_samples ( const DevScene& sc, uint32_t bounce ) {
     if constexpr ( ( KINDS & TERRA_KIND_SAMPLER ) != 0 && ( INTEGRATOR == 1 || INTEGRATOR == 2 ) ) return bounce != 0u && env_sampling_active ( sc );
     return false;
 }
-template <int COUNT, int MODE, int KINDS>
+// environment MIS's lookup by direction: the texel environment_eval reads for `dir` (same mapping, same truncation; clamped into the table, which only a NaN
+// direction can leave) and sin theta of `dir`
+TD void environment_texel ( const DevScene& sc, V3 dir, uint32_t& col, uint32_t& row, float& st ) {
+    const V3 d = normalize ( dir );
+    const float theta = tdm_acosf ( d.y );
+    const float phi = tdm_atan2f ( d.z, d.x ) + TERRA_PI_F;
+    col = ( uint32_t ) ( ( phi / ( 2 * TERRA_PI_F ) ) * ( float ) sc.env_nx );
+    row = ( uint32_t ) ( ( theta / TERRA_PI_F ) * ( float ) sc.env_ny );
+    col = col < sc.env_nx - 1u ? col : sc.env_nx - 1u; row = row < sc.env_ny - 1u ? row : sc.env_ny - 1u;
+    st = tdm_sinf ( theta );
+}
+// ... and the density over the sphere with which environment_light_sample produces a direction in that texel: the texel's probability in the table (bit-identical
+// to the product of the two *pdf distribution_sample reports when it draws the texel) x texels / (2 terra_PI^2 sin theta), as environment_light_sample forms it;
+// 0 where sin theta <= 0 or the texel cannot be drawn
+TD float environment_texel_pdf ( const DevScene& sc, uint32_t col, uint32_t row, float st ) {
+    const float prob = distribution_2d_prob ( sc.env_f, sc.env_row_f, sc.env_nx, sc.env_integral, row, col );
+    if ( ! ( st > 0.f ) || ! ( prob > 0.f ) ) return 0.f;
+    return prob * ( ( float ) sc.env_nx * ( float ) sc.env_ny ) / ( 2 * TERRA_PI_F * TERRA_PI_F * st );
+}
+TD float environment_pdf ( const DevScene& sc, V3 dir ) {
+    uint32_t col, row; float st;
+    environment_texel ( sc, dir, col, row, st );
+    return environment_texel_pdf ( sc, col, row, st );
+}
+// lobes whose bsdf_eval is zero away from the direction their sampler chose (glass): the environment strategy adds nothing there, so under environment MIS the BSDF
+// ray keeps its whole weight and the environment sample is left as it is
+template <int KINDS>
+TD bool bsdf_is_singular ( const Surface& sf ) { return ( KINDS & 8 ) && ( KINDS == 8 || sf.bsdf == kDevBsdfGlass ); }
+// MIS: Direct + MIS in the environment-MIS variant (KINDS & TERRA_KIND_ENV_MIS) -- the term is weighted against the BSDF ray's density, p_e^2 / (p_e^2 + p_b^2), p_b read after the
+// integrator's bsdf_sample (Phong's and glass's scratch slots hold that sample's choice). Same draws and the same shadow ray either way.
+template <int COUNT, int MODE, int KINDS, bool MIS = false>
 TD V3 environment_light_sample ( const Tracer& T, Surface& sf, V3 p, V3 wo, Pcg32& rb, Counters& c ) {
     const DevScene& sc = T.sc;
     const V3 zero = v3 ( 0, 0, 0 );
@@ -1225,6 +1255,11 @@ TD V3 environment_light_sample ( const Tracer& T, Surface& sf, V3 p, V3 wo, Pcg3
     if ( h.hit ) return zero;
     const V3 L = texture_read ( sc.textures[sc.env_tex], col, row );
     const V3 f = bsdf_eval<KINDS> ( sf, wi, wo );
+    if constexpr ( MIS && ( KINDS & TERRA_KIND_ENV_MIS ) != 0 ) if ( !bsdf_is_singular<KINDS> ( sf ) ) {
+        const float b = bsdf_pdf<KINDS> ( sf, wi, wo ), bpdf = b > 0.f ? b : 0.f;     // (Phong's lobe pdf is negative or NaN where the lobe is empty: density 0)
+        const float r = bpdf / pdf, weight = 1.f / ( 1.f + r * r );                 // p_e^2 / (p_e^2 + p_b^2), defined when a density overflows
+        return had ( L, f ) * ( cosine * weight / pdf );
+    }
     return had ( L, f ) * ( cosine / pdf );
 }
 
@@ -1405,8 +1440,21 @@ TD V3 integrate_mis ( const Tracer& T, Surface& sf, V3 p, V3 wo, V3 throughput, 
                 }
             }
         }
+        if constexpr ( ( KINDS & TERRA_KIND_ENV_MIS ) != 0 && !DEBUG_WEIGHTS ) {
+            // environment MIS: the BSDF ray that leaves the scene sees the environment, weighted against the density with which the environment sample could
+            // have produced its direction (0 below the shading normal's horizon and for singular lobes: weight 1)
+            if ( !h.hit && bpdf > 0.f ) {         // (skips p_b = 0 like the area-light branch, and a negative or NaN lobe pdf)
+                uint32_t col, row; float st;
+                environment_texel ( sc, wi, col, row, st );          // (environment_eval's texel: one lookup serves the radiance and the density)
+                const float epdf = ( !bsdf_is_singular<KINDS> ( sf ) && dot ( wi, sf.normal ) > 0 ) ? environment_texel_pdf ( sc, col, row, st ) : 0.f;
+                const float r = epdf / bpdf, weight = 1.f / ( 1.f + r * r );        // p_b^2 / (p_b^2 + p_e^2), defined when a density overflows
+                V3 L = had ( texture_read ( sc.textures[sc.env_tex], col, row ), f );
+                L = L * ( dot ( wi, sf.normal ) * weight / bpdf );
+                Lo = Lo + L;
+            }
+        }
     }
-    if constexpr ( ( KINDS & TERRA_KIND_SAMPLER ) != 0 && !DEBUG_WEIGHTS ) { if ( env_sampling_active ( sc ) ) Lo = Lo + environment_light_sample<COUNT, MODE, KINDS> ( T, sf, p, wo, rb, c ); }
+    if constexpr ( ( KINDS & TERRA_KIND_SAMPLER ) != 0 && !DEBUG_WEIGHTS ) { if ( env_sampling_active ( sc ) ) Lo = Lo + environment_light_sample<COUNT, MODE, KINDS, true> ( T, sf, p, wo, rb, c ); }
     return had ( Lo, throughput );
 }
 

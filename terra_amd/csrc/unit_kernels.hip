@@ -317,6 +317,22 @@ hipError_t terra_unit_distribution_2d ( const float* f, uint32_t nx, uint32_t ny
     if ( m > 0 ) hipLaunchKernelGGL ( k_dist_sample_2d, UNIT_GRID ( m ), 0, 0, f, cdf, nx, ny, integrals, mcdf, monotone, e12, m, xy2, pdf );
     return hipGetLastError();
 }
+// the lookup environment MIS uses (trace_device.h environment_pdf): point (v, u) of the unit square -- the order k_dist_sample_2d reports a sample in -- lies in
+// bucket (row, col) = (v ny, u nx) truncated; its probability is distribution_2d_prob's (points outside [0, 1) clamp to the border buckets)
+__global__ void k_dist_pdf_2d ( const float* f, uint32_t nx, uint32_t ny, const float* integrals, const float* xy2, int m, float* pdf ) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if ( i >= m ) return;
+    const float v = xy2[2 * i], u = xy2[2 * i + 1];
+    uint32_t row = v > 0.f ? ( uint32_t ) ( v * ( float ) ny ) : 0u, col = u > 0.f ? ( uint32_t ) ( u * ( float ) nx ) : 0u;
+    row = row < ny - 1u ? row : ny - 1u; col = col < nx - 1u ? col : nx - 1u;
+    pdf[i] = distribution_2d_prob ( f, integrals, nx, integrals[ny], row, col );
+}
+hipError_t terra_unit_distribution_2d_pdf ( const float* f, uint32_t nx, uint32_t ny, float* cdf, float* integrals, float* mcdf, uint32_t* monotone, const float* xy2, int m, float* pdf ) {
+    hipLaunchKernelGGL ( k_dist_rows, UNIT_GRID ( ny ), 0, 0, f, nx, ny, cdf, integrals, monotone );
+    hipLaunchKernelGGL ( k_dist_marginal, dim3 ( 1 ), dim3 ( 64 ), 0, 0, ny, integrals, mcdf, monotone );
+    if ( m > 0 ) hipLaunchKernelGGL ( k_dist_pdf_2d, UNIT_GRID ( m ), 0, 0, f, nx, ny, integrals, xy2, m, pdf );
+    return hipGetLastError();
+}
 
 // ---- DevScene::sincos24: (cos, sin) of 2 * terra_PI * (k * 2^-24) for every 24-bit k, each entry by tdm_sincosf_pair itself (trace_device.h azimuth_fetch) ----
 __global__ __launch_bounds__ ( 256 ) void terra_sincos24_kernel ( float2* table ) {
