@@ -292,6 +292,10 @@ int terra_amd_scene_info ( HTerraScene scene, TerraAmdSceneInfo* out );
 /* Copies the host BVH (reference node layout, src/TerraBVH.h:13-17, 64 B/node)
    into `out` (capacity in nodes); returns the node count or a negative status. */
 int terra_amd_scene_bvh_nodes ( HTerraScene scene, void* out, int capacity );
+/* Rank of every triangle (soup order: objects in order, their triangles in order) in the
+   reference traversal's leaf visit order with every box hit, as the LDS-resident kernels
+   use it; returns the triangle count (0 for an empty scene) or a negative status. */
+int terra_amd_scene_leaf_ranks ( HTerraScene scene, uint32_t* out, int capacity );
 
 /* terra_render() (include/Terra.h:229, src/Terra.c:512-635) on a framebuffer
    that already lives in HBM: d_pixels = float[3]*fb_width*fb_height,

@@ -65,11 +65,11 @@ TD void wave_flush_counters ( const Counters& c, unsigned long long* g ) {
 #define TERRA_CHECK_SHRINK 0
 #endif
 template <int MODE>
-TD Tracer make_tracer ( const DevScene& sc, float4* lds, uint32_t stack_depth, uint32_t leaf_cap, uint32_t lds_nodes, uint32_t lds_tris, bool cull, bool fused ) {
+TD Tracer make_tracer ( const DevScene& sc, float4* lds, uint32_t stack_depth, uint32_t leaf_cap, uint32_t lds_nodes, uint32_t lds_tris, bool cull, bool fused, bool ranked ) {
     const int tid = threadIdx.x;
     Tracer T;
     T.sc = sc;
-    // [staged nodes][staged triangles][staged properties][stack][leaf list][parked words]  (sizes: terra_lds_bytes)
+    // [staged nodes][staged triangles][staged properties][materials, lights, areas][ranked copies][stack][leaf list][parked words]  (sizes: terra_lds_bytes)
     float4* ln = lds;                                                // byte offset 0: a staged node's address is its stack word
     float4* lt = ln + ( TERRA_LDS_NODE_BYTES / 16 ) * lds_nodes;      // (fast-tree launches stage nothing: lds_nodes == lds_tris == 0)
     float4* lp = lt + 3 * lds_tris;
@@ -77,7 +77,9 @@ TD Tracer make_tracer ( const DevScene& sc, float4* lds, uint32_t stack_depth, u
     uint32_t* lm = reinterpret_cast<uint32_t*> ( lp + 4 * lds_tris );
     const uint32_t m_words = MODE == 1 ? ( ( sc.n_objects * ( uint32_t ) ( sizeof ( DevMaterial ) / 4 ) + 3u ) & ~3u ) : 0u, l_words = MODE == 1 ? sc.n_lights * 4u : 0u, a_words = MODE == 1 ? ( ( sc.n_tris + 3u ) & ~3u ) : 0u;
     uint32_t* ll = lm + m_words; uint32_t* la = ll + l_words;
-    int* words = reinterpret_cast<int*> ( la + a_words );
+    ranked = MODE == 1 && ranked;
+    float4* lr = reinterpret_cast<float4*> ( la + a_words );            // ranked launches: 6 permuted copies of the triangles in rank order (trace_device.h "Ranked launches")
+    int* words = reinterpret_cast<int*> ( lr + ( ranked ? 18u * lds_tris : 0u ) );
     T.stack = words + tid;
     T.leaves = words + stack_depth * TERRA_COL + tid;
     T.leaf_cap = ( int ) leaf_cap;
@@ -95,9 +97,25 @@ TD Tracer make_tracer ( const DevScene& sc, float4* lds, uint32_t stack_depth, u
         #pragma unroll
         for ( int a = 0; a < 3; ++a ) { o[2 * a] = make_float4 ( mn0[a], mx0[a], mn1[a], mx1[a] ); o[2 * a + 1] = make_float4 ( mx0[a], mn0[a], mx1[a], mn1[a] ); }
         uint32_t c0 = __float_as_uint ( q3.x ), c1 = __float_as_uint ( q3.y );
+        // ranked launches: a leaf child's bit in a ray's leaf set = its triangle's reference visit rank (DevTri::pad); none for an inner child or an empty slot
+        const uint32_t b0 = ( ranked && ( c0 & DEV_CHILD_LEAF ) && c0 != DEV_CHILD_EMPTY ) ? 1u << reinterpret_cast<const DevTri*> ( gt ) [c0 & 0x7fffffffu].pad : 0u;
+        const uint32_t b1 = ( ranked && ( c1 & DEV_CHILD_LEAF ) && c1 != DEV_CHILD_EMPTY ) ? 1u << reinterpret_cast<const DevTri*> ( gt ) [c1 & 0x7fffffffu].pad : 0u;
         if ( ! ( c0 & DEV_CHILD_LEAF ) ) c0 *= TERRA_LDS_NODE_BYTES;       // inner child: byte offset of its staged node
         if ( ! ( c1 & DEV_CHILD_LEAF ) ) c1 *= TERRA_LDS_NODE_BYTES;
-        o[6] = make_float4 ( __uint_as_float ( c0 ), __uint_as_float ( c1 ), 0.f, 0.f );
+        o[6] = make_float4 ( __uint_as_float ( c0 ), __uint_as_float ( c1 ), __uint_as_float ( b0 ), __uint_as_float ( b1 ) );
+    }
+    if ( ranked ) {         // copy perm, entry rank: triangle (of that rank) in the axes (kx, ky, kz) of permutation perm = 2 kz + swapped (trace_device.h traverse_ranked)
+        const DevTri* gtri = reinterpret_cast<const DevTri*> ( gt );
+        for ( uint32_t i = tid; i < 6u * lds_tris; i += TERRA_COL ) {
+            const uint32_t perm = i / lds_tris, ti = i - perm * lds_tris;
+            const DevTri& t = gtri[ti];
+            const int kz = ( int ) ( perm >> 1 ), k1 = kz == 2 ? 0 : kz + 1, k2 = k1 == 2 ? 0 : k1 + 1;
+            const int kx = ( perm & 1u ) ? k2 : k1, ky = ( perm & 1u ) ? k1 : k2;
+            float4* e = lr + 3u * ( perm * lds_tris + t.pad );
+            e[0] = make_float4 ( t.a[kx], t.a[ky], t.a[kz], t.b[kx] );
+            e[1] = make_float4 ( t.b[ky], t.b[kz], t.c[kx], t.c[ky] );
+            e[2] = make_float4 ( t.c[kz], __uint_as_float ( ti ), 0.f, 0.f );
+        }
     }
     for ( uint32_t i = tid; i < 3 * lds_tris; i += TERRA_COL ) lt[i] = gt[i];
     for ( uint32_t i = tid; i < 4 * lds_tris; i += TERRA_COL ) lp[i] = gp[i];
@@ -109,6 +127,7 @@ TD Tracer make_tracer ( const DevScene& sc, float4* lds, uint32_t stack_depth, u
     }
     T.l_mats = MODE == 1 ? reinterpret_cast<const DevMaterial*> ( lm ) : sc.mats; T.l_lights = MODE == 1 ? reinterpret_cast<const DevLight*> ( ll ) : sc.lights; T.l_area = MODE == 1 ? reinterpret_cast<const float*> ( la ) : sc.tri_area;
     T.l_nodes = ln; T.l_tris = reinterpret_cast<const float*> ( lt ); T.l_props = lp;
+    T.l_ranked = ranked ? lr : nullptr; T.ranked = ranked;
     T.lds_nodes = lds_nodes; T.lds_tris = lds_tris;
     __syncthreads();
     return T;
@@ -454,7 +473,7 @@ template <int INTEGRATOR, int COUNT, int MODE, int KINDS>
 __global__ __launch_bounds__ ( 256, TERRA_WAVES_FOR ( INTEGRATOR, KINDS, MODE ) ) void terra_render_kernel ( DevRenderParams p ) {
     extern __shared__ float4 lds_f4[];
     const int tid = threadIdx.x;
-    Tracer T0 = make_tracer<MODE> ( p.scene, lds_f4, p.stack_depth, p.leaf_cap, p.lds_nodes, p.lds_tris, p.leaf_cull != 0, p.fused_slab != 0 );
+    Tracer T0 = make_tracer<MODE> ( p.scene, lds_f4, p.stack_depth, p.leaf_cap, p.lds_nodes, p.lds_tris, p.leaf_cull != 0, p.fused_slab != 0, p.leaf_rank != 0 );
     T0.faults = p.counters + kCtrFaults;
     if ( MODE >= 2 && p.stack_spill ) { T0.spill = p.stack_spill + ( size_t ) ( blockIdx.x * 256u + threadIdx.x ) * p.spill_cap; T0.spill_cap = p.spill_cap; }
     const Tracer T = T0;
@@ -750,7 +769,7 @@ static size_t scene_extra_lds_bytes ( uint32_t n_objects, uint32_t n_lights, uin
 }
 size_t terra_lds_bytes ( const DevRenderParams& p ) {
     return ( size_t ) ( p.stack_depth + p.leaf_cap + ( p.lds_mode == 1 ? TERRA_AUX_WORDS_LDS : TERRA_AUX_WORDS ) ) * 1024 + ( size_t ) p.lds_nodes * TERRA_LDS_NODE_BYTES + ( size_t ) p.lds_tris * ( 48 + 64 )
-           + ( p.lds_mode == 1 ? scene_extra_lds_bytes ( p.scene.n_objects, p.scene.n_lights, p.scene.n_tris ) : 0 );
+           + ( p.lds_mode == 1 ? scene_extra_lds_bytes ( p.scene.n_objects, p.scene.n_lights, p.scene.n_tris ) : 0 ) + ( p.lds_mode == 1 && p.leaf_rank ? ( size_t ) p.lds_tris * 6 * 48 : 0 );
 }
 // fast tree (MODE 2 / 3): nothing is staged. A lane holds at most two leaves (in registers: the one it tests, the next one), so there is no leaf list. The stack: its first TERRA_FAST_STACK_LDS entries
 // in LDS (1 KB per entry and block), the rest -- up to the tree's worst case, which a ray almost never reaches -- in HBM, 4 bytes per entry and resident lane
@@ -762,7 +781,7 @@ size_t terra_lds_bytes ( const DevRenderParams& p ) {
 #endif
 void terra_plan_fast_tree ( DevRenderParams& p ) {
     const uint32_t need = ( uint32_t ) ( p.scene.fast_max_stack < 1 ? 1 : p.scene.fast_max_stack );
-    p.lds_mode = 2; p.lds_tris = 0; p.lds_nodes = 0; p.leaf_cap = 0; p.stack_depth = need < ( uint32_t ) TERRA_FAST_STACK_LDS ? need : ( uint32_t ) TERRA_FAST_STACK_LDS;
+    p.lds_mode = 2; p.lds_tris = 0; p.lds_nodes = 0; p.leaf_cap = 0; p.leaf_rank = 0; p.stack_depth = need < ( uint32_t ) TERRA_FAST_STACK_LDS ? need : ( uint32_t ) TERRA_FAST_STACK_LDS;
     p.spill_cap = need - p.stack_depth; p.stack_spill = nullptr;
 }
 // resident lanes a fast-tree launch can have at most (8 blocks of 256 threads per CU): what the spill area is sized for
@@ -807,9 +826,12 @@ bool terra_scene_fits_lds ( uint32_t n_nodes, uint32_t n_tris, int max_stack, ui
 void terra_plan_lds ( DevRenderParams& p ) {
     uint32_t depth = p.scene.max_stack < 1 ? 1u : ( uint32_t ) p.scene.max_stack;
     p.stack_depth = depth;
-    p.leaf_cap = TERRA_LEAF_CAP_MAX;
+    p.leaf_cap = TERRA_LEAF_CAP_MAX; p.leaf_rank = 0;
     if ( const uint32_t cap = resident_leaf_cap ( p.scene.n_nodes, p.scene.n_tris, p.scene.max_stack, p.scene.n_objects, p.scene.n_lights ) ) {
         p.lds_mode = 1; p.lds_nodes = p.scene.n_nodes; p.lds_tris = p.scene.n_tris; p.leaf_cap = cap;
+        // at most TERRA_LEAF_RANK_MAX triangles: the leaf list gives way to the rank set and the permuted copies (trace_device.h "Ranked launches") if they
+        // take no more LDS than the list did -- on the Cornell box 6 x 32 x 48 B = 9 KB in place of the list's 13 KB
+        if ( p.scene.n_tris <= TERRA_LEAF_RANK_MAX && ( size_t ) p.scene.n_tris * 6 * 48 <= ( size_t ) cap * 1024 ) { p.leaf_rank = 1; p.leaf_cap = 0; }
         return;
     }
     p.lds_mode = 0; p.lds_nodes = 0; p.lds_tris = 0;

@@ -610,6 +610,26 @@ static bool verify_fast_tree ( const std::vector<DevNode>& nodes, const std::vec
 }
 
 
+// Rank of every soup triangle in the order the reference traversal meets its leaf when every box is hit: a popped node appends its leaf children, child 0 before
+// child 1, then pushes its inner children, child 0 before child 1 (so child 1's subtree comes first). A ray only prunes subtrees, never reorders them, so the leaves
+// any ray meets are a subsequence of this order: testing them in the order met is testing them by increasing rank. Each leaf names one triangle, each triangle
+// one leaf: the ranks are a permutation of 0 .. triangles - 1 (one entry, 0, for an empty scene).
+static std::vector<uint32_t> leaf_ranks ( const Scene* s ) {
+    size_t ntri = 0;
+    for ( size_t j = 0; j < s->objects_pop; ++j ) ntri += s->objects[j].triangles_count;
+    std::vector<uint32_t> rank ( ntri ? ntri : 1, 0 );
+    if ( s->nodes.empty() ) return rank;
+    uint32_t next = 0; std::vector<int> st; st.push_back ( 0 );
+    while ( !st.empty() ) {
+        const HostNode& h = s->nodes[ ( size_t ) st.back()]; st.pop_back();
+        for ( int c = 0; c < 2; ++c ) {
+            if ( h.type[c] == 1 ) { uint32_t obj = ( uint32_t ) h.index[c] & 0xffu, tri = ( uint32_t ) h.index[c] >> 8; rank[s->first_tri[obj] + tri] = next++; }
+            else if ( h.type[c] == -1 ) st.push_back ( h.index[c] );
+        }
+    }
+    return rank;
+}
+
 // ---- reachability tables (DevScene::ref_replay / fast_leaf_parent / fast_leaf_mask) -------------------------------------------------------------
 // nodes: the reference tree as the DEVICE holds it (breadth-first numbering, test hook applied); soup_of_fast[k] = soup index of fast triangle k.
 // Level L of fast triangle k = the L-th reference node on the way up from the triangle's leaf; its test is the slab test of the box that node's parent
@@ -898,20 +918,12 @@ static int upload_scene ( Scene* s, const std::vector<int>& set ) {
     float fast_scale = 1.f;
     { const float span = s->coord_max + 1e-4f + fast_extra; if ( std::isfinite ( span ) ) while ( span * fast_scale >= 16384.f && fast_scale > 0x1p-100f ) fast_scale *= 0.5f; }
     std::vector<uint32_t> soup_of_fast;                                                             // reach: soup index of every fast triangle (host-built: known here)
+    // rank of every soup triangle in the reference traversal's leaf visit order (all boxes hit). The soup carries the ranks in DevTri::pad: a light-sample ray of the
+    // fast tree tests its triangle before it traverses (trace_device.h fast_expect), and LDS-resident launches of at most TERRA_LEAF_RANK_MAX triangles stage the
+    // triangles in rank order and collect a ray's leaves as a set of ranks (make_tracer, trace_device.h traverse_ranked)
+    std::vector<uint32_t> rank = leaf_ranks ( s );
+    for ( size_t k = 0; k < ntri; ++k ) tris[k].pad = rank[k];
     if ( s->use_fast ) {
-        // rank of every soup triangle in the reference traversal's leaf visit order (all boxes hit)
-        std::vector<uint32_t> rank ( ntri ? ntri : 1, 0 );
-        {
-            uint32_t next = 0; std::vector<int> st; st.push_back ( 0 );
-            while ( !st.empty() ) {
-                const HostNode& h = s->nodes[ ( size_t ) st.back()]; st.pop_back();
-                for ( int c = 0; c < 2; ++c ) {
-                    if ( h.type[c] == 1 ) { uint32_t obj = ( uint32_t ) h.index[c] & 0xffu, tri = ( uint32_t ) h.index[c] >> 8; rank[s->first_tri[obj] + tri] = next++; }
-                    else if ( h.type[c] == -1 ) st.push_back ( h.index[c] );
-                }
-            }
-        }
-        for ( size_t k = 0; k < ntri; ++k ) tris[k].pad = rank[k];      // the soup carries the ranks too: a light-sample ray tests its triangle before it traverses (trace_device.h fast_expect)
         s->fast_on_device = s->tree_builder == 1 && ntri > 64 && terra_amd_device_count() > 0;
         if ( s->fast_on_device ) {
             // built after the upload, from the soup already in HBM; the host only supplies the reference visit ranks
@@ -1210,6 +1222,15 @@ extern "C" int terra_amd_scene_bvh_nodes ( HTerraScene h, void* out, int capacit
     if ( !s->committed ) return fail ( kTerraAmdErrNotCommitted, "scene not committed" );
     int n = ( int ) s->nodes.size();
     if ( out && capacity >= n ) memcpy ( out, s->nodes.data(), ( size_t ) n * sizeof ( HostNode ) );
+    return n;
+}
+extern "C" int terra_amd_scene_leaf_ranks ( HTerraScene h, uint32_t* out, int capacity ) {
+    Scene* s = S ( h );
+    if ( !s->committed ) return fail ( kTerraAmdErrNotCommitted, "scene not committed" );
+    const std::vector<uint32_t> rank = leaf_ranks ( s );
+    size_t ntri = 0; for ( size_t j = 0; j < s->objects_pop; ++j ) ntri += s->objects[j].triangles_count;
+    const int n = ( int ) ntri;
+    if ( out && capacity >= n ) memcpy ( out, rank.data(), ( size_t ) n * sizeof ( uint32_t ) );
     return n;
 }
 // counters [first, first + n) summed over every replica, each device current around its copy (the primary's last: it stays current)

@@ -218,14 +218,20 @@ TD bool moller_trumbore ( V3 o, V3 d, V3 ta, V3 tb, V3 tc, float& t_out, V3& p_o
 //     [x+] min0.x max0.x min1.x max1.x     [x-] max0.x min0.x max1.x min1.x
 //     [y+] ...                             [y-] ...
 //     [z+] ...                             [z-] ...
-//     [children] child0 child1 - -         (an inner child = the BYTE OFFSET of its staged node, a leaf = DEV_CHILD_LEAF | triangle)
+//     [children] child0 child1 bit0 bit1   (an inner child = the BYTE OFFSET of its staged node, a leaf = DEV_CHILD_LEAF | triangle; bit0 / bit1: see below)
 // A ray whose inverse direction is finite and non-zero on every axis reads, per axis, the copy that matches the sign of its
 // direction (SlabSel): the four floats are then (near plane, far plane) of child 0 and of child 1, so the slab test needs no
 // per-axis min/max at all -- v_min/v_max_f32 issue at 0.57 G/s per SIMD on gfx950 against 0.96 for v_sub/v_mul_f32
 // (profiles/r02_measurements/valu_rates.log). Picking the plane by the sign is exactly min(t1, t2) / max(t1, t2): for
 // bmin <= bmax, (b - o) * inv is monotone in b (both roundings are), increasing for inv > 0 and decreasing for inv < 0.
+//
+// Ranked launches (DevRenderParams::leaf_rank: LDS-resident scenes of at most TERRA_LEAF_RANK_MAX triangles, traverse_ranked): bit0 / bit1 of a leaf child =
+// 1 << (its triangle's reference visit rank, DevTri::pad), 0 for an inner child or an empty slot (0 in every other launch). The leaf list is replaced by
+// the triangles staged in rank order once per axis permutation of the watertight test (kz = the dominant axis, kx / ky swapped when d[kz] < 0):
+// 6 copies x lds_tris x 48 B, entry = a[kx] a[ky] a[kz] b[kx] | b[ky] b[kz] c[kx] c[ky] | c[kz] triangle - -.
 // -----------------------------------------------------------------------------
 #define TERRA_LEAF_CAP_MAX 16
+#define TERRA_LEAF_RANK_MAX 32     // triangles a ranked launch can have: a lane's leaf set is one 32-bit word
 #define TERRA_COL 256              // stride of a stack / leaf-list column: the block's thread count
 #define TERRA_LDS_NODE_BYTES 112   // staged node (see above)
 
@@ -237,6 +243,7 @@ struct Tracer {
     const DevMaterial* l_mats;  // materials, lights, per-triangle areas: the block's LDS copies in MODE 1, the arrays in HBM otherwise (make_tracer)
     const DevLight*    l_lights;
     const float*       l_area;
+    const float4* l_ranked;    // ranked launches: the 6 permuted copies of the staged triangles, in rank order (see above); nullptr otherwise
     uint32_t      lds_nodes, lds_tris;
     int*          stack;       // this thread's column
     int*          leaves;
@@ -255,6 +262,8 @@ struct Tracer {
     // cull launches INSIDE the coordinate range may also decide the inner boxes with the fused slab arithmetic (slab_near_far_fused): the containment proof covers
     // every box there. Outside it (Scene::reach_cull) only the rebuilt leaf boxes carry a margin; the inner boxes must be tested exactly as the reference tests them.
     bool fused;
+    // the leaves a ray meets are collected as a set of ranks in one register instead of a list in LDS (traverse_ranked); launch constant
+    bool ranked;
 };
 
 // -----------------------------------------------------------------------------
@@ -383,17 +392,23 @@ TD bool slab_near_far_fused ( float nx, float fx, float ny, float fy, float nz, 
 // one node of the reference traversal (src/TerraBVH.c:262-303): pop, slab-test both child boxes, push the inner children
 // that are hit, append the leaf children to the lane's list (all of them; with Tracer::cull only those whose box is hit).
 // An empty child slot (scenes with < 2 triangles) travels as a leaf and is dropped by leaf_step.
-template <int COUNT, int MODE, bool FAST, bool FUSED = false>
-TD void node_step ( const Tracer& T, const Ray& r, const SlabSel& sel, int*& sp, int*& lp, Counters& c ) {
+// RANKED (MODE 1, ranked launches): the leaf children go into the lane's rank set `leaf_set` (their bits in the staged node) instead of the list; `lp` is not used.
+template <int COUNT, int MODE, bool FAST, bool FUSED = false, bool RANKED = false>
+TD void node_step ( const Tracer& T, const Ray& r, const SlabSel& sel, int*& sp, int*& lp, uint32_t& leaf_set, Counters& c ) {
     PS_WAVE ( c, kPsNodeIter ); PS_LANE ( c, kPsNodeLanes );
     sp -= TERRA_COL;
     const uint32_t w = ( uint32_t ) * sp;
-    uint32_t child0, child1; bool hit0, hit1;
+    uint32_t child0, child1, bit0 = 0u, bit1 = 0u; bool hit0, hit1;
     float te0 = 0.f, te1 = 0.f;          // (FUSED) entry distance of each child box (unused: kept out of registers by the optimiser)
     if ( MODE == 1 ) {
         const char* node = reinterpret_cast<const char*> ( T.l_nodes ) + w;          // w = byte offset of the staged node
-        const uint2 cw = *reinterpret_cast<const uint2*> ( node + 96 );
-        child0 = cw.x; child1 = cw.y;
+        if ( RANKED ) {
+            const uint4 cw = *reinterpret_cast<const uint4*> ( node + 96 );
+            child0 = cw.x; child1 = cw.y; bit0 = cw.z; bit1 = cw.w;
+        } else {
+            const uint2 cw = *reinterpret_cast<const uint2*> ( node + 96 );
+            child0 = cw.x; child1 = cw.y;
+        }
         if ( FAST ) {
             const float4 ax = *reinterpret_cast<const float4*> ( node + sel.x ), ay = *reinterpret_cast<const float4*> ( node + sel.y ), az = *reinterpret_cast<const float4*> ( node + sel.z );
             if ( FUSED ) {
@@ -422,8 +437,13 @@ TD void node_step ( const Tracer& T, const Ray& r, const SlabSel& sel, int*& sp,
     const bool leaf0 = ( child0 & DEV_CHILD_LEAF ) != 0, leaf1 = ( child1 & DEV_CHILD_LEAF ) != 0;
     if ( !leaf0 && hit0 ) { TERRA_PUSH ( T, sp, child0 ); }
     if ( !leaf1 && hit1 ) { TERRA_PUSH ( T, sp, child1 ); }
-    if ( leaf0 && ( hit0 || !T.cull ) ) { TERRA_LEAF ( T, lp, ( child0 & 0x7fffffffu ) ); }
-    if ( leaf1 && ( hit1 || !T.cull ) ) { TERRA_LEAF ( T, lp, ( child1 & 0x7fffffffu ) ); }
+    if ( RANKED ) {          // (bit = 0 for an inner child and for an empty slot: nothing to test, as leaf_step drops the empty slot)
+        leaf_set |= ( hit0 || !T.cull ) ? bit0 : 0u;
+        leaf_set |= ( hit1 || !T.cull ) ? bit1 : 0u;
+    } else {
+        if ( leaf0 && ( hit0 || !T.cull ) ) { TERRA_LEAF ( T, lp, ( child0 & 0x7fffffffu ) ); }
+        if ( leaf1 && ( hit1 || !T.cull ) ) { TERRA_LEAF ( T, lp, ( child1 & 0x7fffffffu ) ); }
+    }
     if ( COUNT == 2 && T.cull ) c.tri_culled += ( uint32_t ) ( leaf0 && !hit0 ) + ( uint32_t ) ( leaf1 && !hit1 );
 }
 
@@ -454,15 +474,47 @@ TD void leaf_step ( const Tracer& T, const int* entry, const RayState& st, V3 o_
     if ( watertight_permuted ( pa, pb, pc, o_perm, st, depth ) && depth < best.depth ) { best.depth = depth; best.tri = ti; if ( ANYHIT && ti != expected ) *stop = true; }
 }
 
+// Ranked launches (MODE 1, Tracer::ranked). The leaves any ray meets are a subsequence of one global order -- the order in which the traversal with every box
+// hit meets them (scene_host.cpp leaf_ranks) --, so "test the listed leaves in the order met" is "test the set ranks from low to high": the same triangles,
+// in the same order, with the same strict "<". The node loop therefore runs to the end in one pass and only sets bits; the leaf loop then walks the set
+// bits and reads each triangle, already permuted into the ray's axes, with three 16-byte loads from the copy for the ray's permutation.
+template <int COUNT, int MODE, bool FAST, bool FUSED = false, bool ANYHIT = false>
+TD void traverse_ranked ( const Tracer& T, const Ray& r, const RayState& st, V3 o_perm, Closest& best, Counters& c, uint32_t expected ) {
+    const SlabSel sel = slab_sel ( r );
+    int* sp = T.stack; int* lp = nullptr;
+    uint32_t leaf_set = 0u;
+    *sp = 0; sp += TERRA_COL;                                          // the root: node 0 = byte offset 0
+    PS_WAVE ( c, kPsDrainIter );
+    while ( sp != T.stack ) node_step<COUNT, MODE, FAST, FUSED, true> ( T, r, sel, sp, lp, leaf_set, c );
+    const uint32_t perm = 2u * ( uint32_t ) st.iz + ( uint32_t ) ( st.ix != ( st.iz == 2 ? 0 : st.iz + 1 ) );      // ray_state_init: ix follows iz unless d[iz] < 0 swapped ix / iy
+    const float4* copy = T.l_ranked + 3u * T.lds_tris * perm;
+    while ( leaf_set != 0u ) {
+        PS_WAVE ( c, kPsLeafIter ); PS_LANE ( c, kPsLeafLanes );
+        const float4* e = copy + 3u * ( uint32_t ) __builtin_ctz ( leaf_set );
+        leaf_set &= leaf_set - 1u;
+        const float4 q0 = e[0], q1 = e[1], q2 = e[2];
+        const float pa[3] = { q0.x, q0.y, q0.z }, pb[3] = { q0.w, q1.x, q1.y }, pc[3] = { q1.z, q1.w, q2.x };
+        if ( COUNT ) ++c.tri_tests;
+        float depth;
+        if ( watertight_permuted ( pa, pb, pc, o_perm, st, depth ) && depth < best.depth ) {
+            const uint32_t ti = __float_as_uint ( q2.y );
+            best.depth = depth; best.tri = ti;
+            if ( ANYHIT && ti != expected ) leaf_set = 0u;             // another triangle comes first: nothing further can change the answer
+        }
+    }
+}
+
 template <int COUNT, int MODE, bool FAST, bool FUSED = false, bool ANYHIT = false>
 TD void traverse_loops ( const Tracer& T, const Ray& r, const RayState& st, V3 o_perm, Closest& best, Counters& c, uint32_t expected = 0xffffffffu ) {
+    if constexpr ( MODE == 1 ) if ( T.ranked ) { traverse_ranked<COUNT, MODE, FAST, FUSED, ANYHIT> ( T, r, st, o_perm, best, c, expected ); return; }
     const SlabSel sel = slab_sel ( r );
     int* sp = T.stack; int* lp = T.leaves;
     int* const lp_full = T.leaves + ( T.leaf_cap - 2 ) * TERRA_COL;       // a node adds at most two leaves
+    uint32_t no_set = 0u;
     *sp = 0; sp += TERRA_COL;                                          // the root: node 0 = byte offset 0
     for ( ;; ) {
         PS_WAVE ( c, kPsDrainIter );
-        while ( sp != T.stack && lp <= lp_full ) node_step<COUNT, MODE, FAST, FUSED> ( T, r, sel, sp, lp, c );
+        while ( sp != T.stack && lp <= lp_full ) node_step<COUNT, MODE, FAST, FUSED> ( T, r, sel, sp, lp, no_set, c );
         if constexpr ( ANYHIT ) {
             bool stop = false;
             for ( const int* e = T.leaves; e != lp && !stop; e += TERRA_COL ) leaf_step<COUNT, MODE, true> ( T, e, st, o_perm, best, c, expected, &stop );
@@ -760,12 +812,13 @@ template <int COUNT, int MODE, bool FAST>
 TD void traverse_resume ( const Tracer& T, const Ray& r, const SlabSel& sel, const RayState& st, V3 o_perm, Closest& best, int*& sp, bool& traversing, int exit_active, Counters& c ) {
     int* const lp_full = T.leaves + ( T.leaf_cap - 2 ) * TERRA_COL;
     int* lp = T.leaves;                                      // every lane's list is empty on entry and on exit
+    uint32_t no_set = 0u;
     for ( ;; ) {
         for ( ;; ) {
             const bool can = traversing && sp != T.stack && lp <= lp_full;
             const int n_can = __popcll ( __ballot ( can ) ), n_nodes = __popcll ( __ballot ( traversing && sp != T.stack ) );
             if ( n_can == 0 || n_nodes <= exit_active ) break;
-            if ( can ) node_step<COUNT, MODE, FAST> ( T, r, sel, sp, lp, c );
+            if ( can ) node_step<COUNT, MODE, FAST> ( T, r, sel, sp, lp, no_set, c );
         }
         for ( const int* e = T.leaves; e != lp; e += TERRA_COL ) leaf_step<COUNT, MODE> ( T, e, st, o_perm, best, c );        // lanes that are not traversing hold an empty list
         lp = T.leaves;

@@ -102,6 +102,7 @@ _EXTRA = {
     "terra_amd_reset_stats": (C.c_int, [C.c_void_p]),
     "terra_amd_scene_info": (C.c_int, [C.c_void_p, C.POINTER(SceneInfo)]),
     "terra_amd_scene_bvh_nodes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "terra_amd_scene_leaf_ranks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "terra_amd_render_device": (C.c_int, [_CAM, C.c_void_p, C.c_void_p, C.c_void_p] + [_SZ] * 6 + [C.c_void_p, C.c_void_p]),
     "terra_amd_render_device_sharded": (C.c_int, [_CAM, C.c_void_p, C.c_void_p, C.c_void_p] + [_SZ] * 7 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "terra_amd_shard_tile_count": (C.c_int, [_SZ, _SZ, _SZ, C.c_int, C.c_int]),
