@@ -283,6 +283,25 @@ struct HostLight { uint32_t object; float area; TerraFloat3 power; };
 #define TERRA_SCRATCH_MAX_GB 64                     // most scratch one launch may take from the device's pool (launch_render)
 #endif
 #define TERRA_FAST_STACK_MAX 2048                   // stack entries per ray beyond which the fast tree is not used (its spill space: 4 B x entries x 327,680 resident lanes)
+// The traversal the commit chose (choose_tree; given up only through fall_back), read by fill_params, terra_amd_traversal_info and terra_amd_get_stats
+struct TreeChoice {
+    bool use_fast = false;              // the fast tree is traversed
+    bool fast_on_device = false;        // ... and was built on the device
+    bool cull_ok = false;               // leaf-box cull allowed for this scene (subject to the per-call camera check)
+    bool reach = false;                 // outside the coordinate range: fast tree + reference reachability check (camera within reach_limit, checked per call)
+    bool reach_cull = false;            // outside the coordinate range, LDS-resident: reference tree, leaf-box cull on leaf boxes inflated to the rounding bound (same camera limit)
+    float reach_limit = 0.f;
+    float coord_max = 0.f;              // largest |coordinate| of any vertex
+    uint32_t fast_nodes = 0; int fast_max_stack = 1;      // the wide fast tree's nodes, and the stack entries a ray can need in it
+    std::string note;                   // why the automatic mode chose what it chose
+    // what the choice implies for the commit's build
+    bool resident = false;              // the reference tree fits the LDS-resident kernels
+    float reach_margin = 0.f, fast_extra = 0.f, fast_scale = 1.f;
+};
+// The blob: one device allocation per copy of the scene, these sections in this order, 256-byte aligned, then one section per texture (layout_blob)
+enum { kSecNodes, kSecTris, kSecProps, kSecMats, kSecLights, kSecArea, kSecFastBin, kSecFastWide, kSecFastTris, kSecReplay, kSecLeafParent, kSecLeafMask, kSecTexDesc, kSecTextures };
+struct Section { size_t offset = 0, bytes = 0; const void* host = nullptr; size_t host_bytes = 0; };      // bytes: its room in the blob; host: what the upload copies there
+struct BlobLayout { std::vector<Section> sec; std::vector<DevTexture> tdesc; size_t total = 0; };        // tdesc: the texture descriptors, less their address
 // A stream on one device and a staging frame there (12 B of pixel + 16 B of running sums per pixel), grown to the largest rectangle rendered through it:
 // a calling thread's (ThreadSlot) and a replica's for terra_amd_render_multi
 struct Staging {
@@ -328,7 +347,7 @@ struct Scene {
         Staging staging; float* d_packed = nullptr; size_t packed_floats = 0; float* d_recv = nullptr; size_t recv_floats = 0;
     };
     std::vector<Replica> replicas;
-    size_t d_bytes = 0; std::vector<DevTexture> tdesc_host; size_t o_tdesc = 0, blob_bytes = 0, env_dist_floats = 0;      // the upload's layout, the same in every replica
+    BlobLayout blob; size_t d_bytes = 0, env_dist_floats = 0;      // the upload's layout, the same in every replica
     std::mutex multi_lock;              // a multi-device render owns every device of the set: one at a time per scene; guards the replicas' render_multi state and:
     uint64_t gathers = 0, last_gather_bytes = 0;
     std::atomic<uint64_t> launches { 0 }, stat_pixels { 0 }, stat_samples { 0 };     // terra_render() is called from several threads at once
@@ -336,18 +355,11 @@ struct Scene {
     uint32_t bsdf_kinds = 0;            // mask of preset kinds in the committed scene
     // traversal policy (terra_amd_set_tree_mode): 0 = replica: the reference's tree, every traversal decision reproduced; 1 = fast tree, unconditionally;
     // 2 = automatic (default): scenes that pass the numeric containment check of verify_containment() run the reference tree with the
-    // leaf-box cull when they are LDS-resident and the fast tree otherwise; scenes that fail it run as mode 0 (the reason is kept in tree_note)
+    // leaf-box cull when they are LDS-resident and the fast tree otherwise; scenes that fail it run as mode 0 (the reason is kept in tree.note)
     int tree_mode = 2;
-    bool use_fast = false;              // what the last upload decided
     int tree_builder = 0;               // terra_amd_set_tree_builder: 0 = host (binned SAH), 1 = device (LBVH, tree_build_device.hip)
-    bool fast_on_device = false;        // the fast tree of the last upload was built on the device
-    bool cull_ok = false;               // leaf-box cull allowed for this scene (subject to the per-call camera check)
-    bool reach = false;                 // outside the coordinate range: fast tree + reference reachability check (camera within reach_limit, checked per call)
-    bool reach_cull = false;            // outside the coordinate range, LDS-resident: reference tree, leaf-box cull on leaf boxes inflated to the rounding bound (same camera limit)
-    float reach_limit = 0.f;
+    TreeChoice tree;                    // what the last commit decided
     std::atomic<int> last_call { 0 };   // TerraAmdTraversalInfo::last_call: the traversal the most recent render call actually ran
-    float coord_max = 0.f;              // largest |coordinate| of any vertex
-    std::string tree_note;              // why the automatic mode chose what it chose
     uint32_t sample_split = 1;          // terra_amd_set_sample_split: chunks a call's samples are cut into (lanes per pixel)
     bool env_lighting = false;          // terra_amd_set_environment_lighting: escaping rays add throughput * environment
     bool work_counters = false;         // terra_amd_set_work_counters: the render kernels count rays / nodes / tests / hits / draws (instrumentation, off by default)
@@ -355,7 +367,6 @@ struct Scene {
     bool env_mis = false;               // terra_amd_set_environment_mis: Direct+MIS weights that sample against its BSDF ray (a launch parameter)
     int job_order = 1;                  // terra_amd_set_job_order (0 off, 1 on, 2 on for launches of any size): launches that key their streams ahead hand out the pixel blocks no camera ray hits last (launch_render)
     bool sampler_integration = false;   // terra_amd_set_sampler_integration: the pixel's Halton / stratified sampler feeds the first bounce (a launch parameter)
-    int fast_max_stack = 1; uint32_t fast_nodes = 0;
     std::string commit_error;
     std::atomic<bool> warned_camera { false };      // the per-call fallback (camera outside camera_limit) has been reported on stderr once
     int test_pad_stack = 0;                         // terra_amd_debug_pad_stack (tests only): extra stack entries every launch plans
@@ -442,11 +453,12 @@ extern "C" int terra_amd_traversal_info ( HTerraScene h, TerraAmdTraversalInfo* 
     if ( !out ) return fail ( kTerraAmdErrBadArgument, "null output" );
     memset ( out, 0, sizeof *out );
     if ( !s->committed ) return fail ( kTerraAmdErrNotCommitted, "scene not committed" );
-    out->tree_mode = s->tree_mode; out->fast_tree = s->use_fast ? 1 : 0; out->fast_tree_built_on_device = s->fast_on_device ? 1 : 0; out->leaf_cull = ( s->cull_ok && !s->use_fast ) ? 1 : 0;
-    out->lds_resident = ( !s->use_fast && terra_scene_fits_lds ( ( uint32_t ) s->nodes.size(), primary ( s ).dev.n_tris, s->max_stack, ( uint32_t ) s->objects_pop, ( uint32_t ) s->lights.size() ) ) ? 1 : 0;
-    out->max_coordinate = s->coord_max; out->max_coordinate_allowed = TERRA_CULL_MAX_COORD;
-    out->last_call = s->last_call.load ( std::memory_order_relaxed ); out->camera_limit = ( s->reach || s->reach_cull ) ? s->reach_limit : TERRA_CULL_MAX_COORD;
-    snprintf ( out->note, sizeof out->note, "%s", s->tree_note.c_str() );
+    const TreeChoice& c = s->tree;
+    out->tree_mode = s->tree_mode; out->fast_tree = c.use_fast ? 1 : 0; out->fast_tree_built_on_device = c.fast_on_device ? 1 : 0; out->leaf_cull = ( c.cull_ok && !c.use_fast ) ? 1 : 0;
+    out->lds_resident = ( !c.use_fast && terra_scene_fits_lds ( ( uint32_t ) s->nodes.size(), primary ( s ).dev.n_tris, s->max_stack, ( uint32_t ) s->objects_pop, ( uint32_t ) s->lights.size() ) ) ? 1 : 0;
+    out->max_coordinate = c.coord_max; out->max_coordinate_allowed = TERRA_CULL_MAX_COORD;
+    out->last_call = s->last_call.load ( std::memory_order_relaxed ); out->camera_limit = ( c.reach || c.reach_cull ) ? c.reach_limit : TERRA_CULL_MAX_COORD;
+    snprintf ( out->note, sizeof out->note, "%s", c.note.c_str() );
     return 0;
 }
 extern "C" int terra_amd_set_sample_split ( HTerraScene h, int split ) {
@@ -568,7 +580,6 @@ static bool verify_reference_leaf_boxes ( const Scene* s, std::string& why ) {
 // every child box of the fast tree contains the boxes of all triangles below it (what its culling relies on)
 static bool verify_fast_tree ( const std::vector<DevNode>& nodes, const std::vector<TerraAABB>& boxes_in_leaf_order, std::string& why ) {
     if ( nodes.empty() ) return true;
-    struct Item { uint32_t node; TerraAABB bound[2]; int stage; };
     // iterative post-order: compute the union of triangle boxes below each child and compare with the stored box
     std::vector<TerraAABB> below ( nodes.size() * 2 );
     std::vector<std::pair<uint32_t, int>> st; st.push_back ( { 0u, 0 } );
@@ -615,15 +626,16 @@ static bool verify_fast_tree ( const std::vector<DevNode>& nodes, const std::vec
 // any ray meets are a subsequence of this order: testing them in the order met is testing them by increasing rank. Each leaf names one triangle, each triangle
 // one leaf: the ranks are a permutation of 0 .. triangles - 1 (one entry, 0, for an empty scene).
 static std::vector<uint32_t> leaf_ranks ( const Scene* s ) {
+    std::vector<size_t> first_tri ( s->objects_pop );
     size_t ntri = 0;
-    for ( size_t j = 0; j < s->objects_pop; ++j ) ntri += s->objects[j].triangles_count;
+    for ( size_t j = 0; j < s->objects_pop; ++j ) { first_tri[j] = ntri; ntri += s->objects[j].triangles_count; }
     std::vector<uint32_t> rank ( ntri ? ntri : 1, 0 );
     if ( s->nodes.empty() ) return rank;
     uint32_t next = 0; std::vector<int> st; st.push_back ( 0 );
     while ( !st.empty() ) {
         const HostNode& h = s->nodes[ ( size_t ) st.back()]; st.pop_back();
         for ( int c = 0; c < 2; ++c ) {
-            if ( h.type[c] == 1 ) { uint32_t obj = ( uint32_t ) h.index[c] & 0xffu, tri = ( uint32_t ) h.index[c] >> 8; rank[s->first_tri[obj] + tri] = next++; }
+            if ( h.type[c] == 1 ) { uint32_t obj = ( uint32_t ) h.index[c] & 0xffu, tri = ( uint32_t ) h.index[c] >> 8; rank[first_tri[obj] + tri] = next++; }
             else if ( h.type[c] == -1 ) st.push_back ( h.index[c] );
         }
     }
@@ -695,129 +707,125 @@ static const float2* sincos_table_of ( int device ) {
     return t;
 }
 
+// ---- commit stages -------------------------------------------------------------------------------------------------------------------------------------------
+// terra_scene_commit runs: check_materials -> flatten -> choose_tree -> the fast tree (host builder) -> [a device?] -> upload (device builder) -> replicate_scene.
+// Everything before the device check is host work, so a box without a device still reports the traversal decision (terra_amd_traversal_info).
+
+static std::string format ( const char* fmt, ... ) {
+    char buf[512];
+    va_list a; va_start ( a, fmt ); vsnprintf ( buf, sizeof buf, fmt, a ); va_end ( a );
+    return buf;
+}
+static bool texture_ok ( const TerraTexture* t ) { return t->pixels && t->width && t->height && ( t->depth == 1 || t->depth == 4 ) && t->components != 0; }
 // Can this scene, as it stands, be rendered by this library? The reference runs ANY host callback (TerraBSDF::sample / pdf / eval, TerraAttribute::eval:
-// src/Terra.c:1071-1075, 1804-1810); the device runs the presets of TerraPresets.h and texture lookups only, and there is no CPU path here. A client that
-// supports custom callbacks asks before it commits and keeps such scenes on the reference renderer. (upload_scene applies the same rules and fails the commit.)
-static int scene_support ( const Scene* s, std::string& why ) {
-    char b[256];
-    if ( s->objects_pop > 256 ) { snprintf ( b, sizeof b, "%zu objects: the primitive reference holds 8 bits of object index (include/Terra.h:195-198)", s->objects_pop ); why = b; return kTerraAmdErrUnsupported; }
-    auto attr_ok = [&] ( const TerraAttribute & at, size_t j, const char* what ) {
-        if ( at.state == nullptr ) return true;
-        if ( at.eval != terra_texture_sample ) { snprintf ( b, sizeof b, "object %zu %s: an attribute callback other than terra_texture_sample (host code cannot run on the device)", j, what ); why = b; return false; }
-        const TerraTexture* t = ( const TerraTexture* ) at.state;
-        if ( !t->pixels || !t->width || !t->height || ( t->depth != 1 && t->depth != 4 ) || t->components == 0 ) { snprintf ( b, sizeof b, "object %zu %s: invalid texture", j, what ); why = b; return false; }
-        return true;
-    };
+// src/Terra.c:1071-1075, 1804-1810); the device runs the presets of TerraPresets.h and texture lookups only, and there is no CPU path here. The commit fails with
+// the status and text returned here; terra_amd_scene_supported asks the same question first, so that a client that supports custom callbacks can keep such
+// scenes on the reference renderer.
+static int check_materials ( const Scene* s, const TerraSceneOptions& opts, std::string& why ) {
+    if ( s->objects_pop > 256 ) { why = format ( "%zu objects: the primitive reference holds 8 bits of object index (include/Terra.h:195-198)", s->objects_pop ); return kTerraAmdErrUnsupported; }
     for ( size_t j = 0; j < s->objects_pop; ++j ) {
         const TerraMaterial& m = s->objects[j].material;
         if ( ! ( is_diffuse ( m.bsdf ) || is_phong ( m.bsdf ) || is_ggx ( m.bsdf ) || is_glass ( m.bsdf ) ) ) {
-            snprintf ( b, sizeof b, "object %zu: its BSDF's sample / pdf / eval are not a terra_bsdf_*_init preset of this library (host callbacks cannot run on the device)", j ); why = b; return kTerraAmdErrUnsupported;
+            why = format ( "object %zu: BSDF function pointers are not a terra_bsdf_*_init preset of this library; host callbacks cannot run on the device", j ); return kTerraAmdErrUnsupported;
         }
-        if ( m.attributes_count > TERRA_MATERIAL_MAX_ATTRIBUTES ) { snprintf ( b, sizeof b, "object %zu: attributes_count %zu > %d", j, m.attributes_count, TERRA_MATERIAL_MAX_ATTRIBUTES ); why = b; return kTerraAmdErrBadArgument; }
-        if ( !attr_ok ( m.emissive, j, "emissive" ) ) return kTerraAmdErrUnsupported;
-        for ( size_t a = 0; a < m.attributes_count; ++a ) { char w[32]; snprintf ( w, sizeof w, "attribute %zu", a ); if ( !attr_ok ( m.attributes[a], j, w ) ) return kTerraAmdErrUnsupported; }
+        if ( m.attributes_count > TERRA_MATERIAL_MAX_ATTRIBUTES ) { why = format ( "object %zu: attributes_count %zu > %d", j, m.attributes_count, TERRA_MATERIAL_MAX_ATTRIBUTES ); return kTerraAmdErrBadArgument; }
+        // an attribute is a constant (state == NULL) or a texture sampled with this library's terra_texture_sample
+        // (reference src/Terra.c:294-298, 1804-1810); anything else is a host callback the device cannot run
+        for ( size_t i = 0; i <= m.attributes_count; ++i ) {          // the emissive attribute, then attributes 0 .. count - 1
+            const TerraAttribute& at = i == 0 ? m.emissive : m.attributes[i - 1];
+            if ( at.state == nullptr ) continue;
+            const std::string what = i == 0 ? "emissive" : format ( "attribute %zu", i - 1 );
+            if ( at.eval != terra_texture_sample ) { why = format ( "object %zu %s: attribute callbacks other than terra_texture_sample cannot run on the device (lat-long lookups of a material attribute read past the texcoord in the reference, src/Terra.c:468-471)", j, what.c_str() ); return kTerraAmdErrUnsupported; }
+            if ( !texture_ok ( ( const TerraTexture* ) at.state ) ) { why = format ( "object %zu %s: invalid texture", j, what.c_str() ); return kTerraAmdErrBadArgument; }
+        }
     }
-    if ( s->env_lighting ) {
-        const TerraAttribute& env = s->new_opts.environment_map;
-        if ( env.state != nullptr && env.eval != terra_texture_sample_latlong ) { why = "environment: with environment lighting on, the attribute must be a constant or terra_attribute_init_cubemap"; return kTerraAmdErrUnsupported; }
+    const TerraAttribute& env = opts.environment_map;
+    if ( s->env_lighting && env.state != nullptr ) {
+        if ( env.eval != terra_texture_sample_latlong ) { why = "environment: with environment lighting on, the attribute must be a constant or terra_attribute_init_cubemap (a lat-long lookup by direction)"; return kTerraAmdErrUnsupported; }
+        if ( !texture_ok ( ( const TerraTexture* ) env.state ) ) { why = "environment: invalid texture"; return kTerraAmdErrBadArgument; }
     }
-    if ( terra_amd_device_count() <= 0 ) { why = "no HIP device visible"; return kTerraAmdErrNoDevice; }
     return 0;
 }
 extern "C" int terra_amd_scene_supported ( HTerraScene h, char* why, size_t capacity ) {
     std::string w;
-    const int st = scene_support ( S ( h ), w );
+    int st = check_materials ( S ( h ), S ( h )->new_opts, w );
+    if ( st == 0 && terra_amd_device_count() <= 0 ) { w = "no HIP device visible"; st = kTerraAmdErrNoDevice; }
     if ( why && capacity ) snprintf ( why, capacity, "%s", w.c_str() );
     return st;          // (a query: nothing is recorded in the error channels)
 }
 
-// validates that every material can run on the device and uploads the flattened scene to the set's first device: replicas[0]
-static int upload_scene ( Scene* s, const std::vector<int>& set ) {
-    const size_t nobj = s->objects_pop;
-    if ( nobj > 256 ) return fail ( kTerraAmdErrUnsupported, "%zu objects: the primitive reference holds 8 bits of object index (include/Terra.h:195-198)", nobj );
+// The scene as the device holds it, made on the host: materials, the soup in object order (DevTri::pad = the triangle's leaf rank), the reference tree numbered
+// breadth first, and the textures and environment the materials bind
+struct Flat {
     size_t ntri = 0;
-    s->first_tri.assign ( nobj, 0 );
-    for ( size_t j = 0; j < nobj; ++j ) { s->first_tri[j] = ( uint32_t ) ntri; ntri += s->objects[j].triangles_count; }
-    if ( ntri >= 0x7fffffffu ) return fail ( kTerraAmdErrUnsupported, "too many triangles" );
+    std::vector<DevMaterial> mats; std::vector<DevTri> tris; std::vector<DevProps> props; std::vector<DevLight> lights; std::vector<float> tri_area;
+    std::vector<DevNode> nodes; std::vector<uint32_t> rank;
     std::vector<const TerraTexture*> textures;
-    std::vector<DevMaterial> mats ( nobj ? nobj : 1 );
-    memset ( mats.data(), 0, mats.size() * sizeof ( DevMaterial ) );
+    int32_t env_mode = 0, env_tex = -1; float env_color[3] = { 0.f, 0.f, 0.f };
+};
+// index of a texture in the scene's list, appended on first use
+static int32_t texture_slot ( std::vector<const TerraTexture*>& textures, const void* state ) {
+    auto it = std::find ( textures.begin(), textures.end(), ( const TerraTexture* ) state );
+    if ( it == textures.end() ) it = textures.insert ( it, ( const TerraTexture* ) state );
+    return ( int32_t ) ( it - textures.begin() );
+}
+// materials as check_materials accepted them, and the environment (extension, off by default): constant colour or a lat-long lookup (reference src/Terra.c:468-477)
+static void flatten_materials ( Scene* s, Flat& f ) {
+    const size_t nobj = s->objects_pop;
+    f.mats.resize ( nobj ? nobj : 1 );
+    memset ( f.mats.data(), 0, f.mats.size() * sizeof ( DevMaterial ) );
+    s->bsdf_kinds = 0;
     for ( size_t j = 0; j < nobj; ++j ) {
         const TerraMaterial& m = s->objects[j].material;
-        DevMaterial& d = mats[j];
-        if ( is_diffuse ( m.bsdf ) ) d.bsdf = kDevBsdfDiffuse;
-        else if ( is_phong ( m.bsdf ) ) d.bsdf = kDevBsdfPhong;
-        else if ( is_ggx ( m.bsdf ) ) d.bsdf = kDevBsdfGGX;
-        else if ( is_glass ( m.bsdf ) ) d.bsdf = kDevBsdfGlass;
-        else return fail ( kTerraAmdErrUnsupported, "object %zu: BSDF function pointers are not a terra_bsdf_*_init preset of this library; host callbacks cannot run on the device", j );
-        if ( m.attributes_count > TERRA_MATERIAL_MAX_ATTRIBUTES ) return fail ( kTerraAmdErrBadArgument, "object %zu: attributes_count %zu > %d", j, m.attributes_count, TERRA_MATERIAL_MAX_ATTRIBUTES );
+        DevMaterial& d = f.mats[j];
+        d.bsdf = is_diffuse ( m.bsdf ) ? kDevBsdfDiffuse : is_phong ( m.bsdf ) ? kDevBsdfPhong : is_ggx ( m.bsdf ) ? kDevBsdfGGX : kDevBsdfGlass;
         for ( int a = 0; a <= TERRA_DEV_MAX_ATTR; ++a ) d.tex[a] = -1;
-        d.any_texture = 0;
-        // an attribute is a constant (state == NULL) or a texture sampled with this library's terra_texture_sample
-        // (reference src/Terra.c:294-298, 1804-1810); anything else is a host callback the device cannot run
-        auto bind = [&] ( const TerraAttribute & at, int slot, const char* what ) -> int {
-            if ( at.state == nullptr ) return 0;
-            if ( at.eval != terra_texture_sample ) return fail ( kTerraAmdErrUnsupported, "object %zu %s: attribute callbacks other than terra_texture_sample cannot run on the device (lat-long lookups of a material attribute read past the texcoord in the reference, src/Terra.c:468-471)", j, what );
-            const TerraTexture* t = ( const TerraTexture* ) at.state;
-            if ( !t->pixels || !t->width || !t->height || ( t->depth != 1 && t->depth != 4 ) || t->components == 0 ) return fail ( kTerraAmdErrBadArgument, "object %zu %s: invalid texture", j, what );
-            size_t k = 0;
-            for ( ; k < textures.size(); ++k ) if ( textures[k] == t ) break;
-            if ( k == textures.size() ) textures.push_back ( t );
-            d.tex[slot] = ( int32_t ) k; d.any_texture = 1;
-            return 0;
-        };
-        if ( int rc = bind ( m.emissive, TERRA_DEV_MAX_ATTR, "emissive" ) ) return rc;
+        if ( m.emissive.state ) { d.tex[TERRA_DEV_MAX_ATTR] = texture_slot ( f.textures, m.emissive.state ); d.any_texture = 1; }
         for ( size_t a = 0; a < m.attributes_count; ++a ) {
-            char what[32]; snprintf ( what, sizeof what, "attribute %zu", a );
-            if ( int rc = bind ( m.attributes[a], ( int ) a, what ) ) return rc;
+            if ( m.attributes[a].state ) { d.tex[a] = texture_slot ( f.textures, m.attributes[a].state ); d.any_texture = 1; }
             d.attributes[a][0] = m.attributes[a].value.x; d.attributes[a][1] = m.attributes[a].value.y; d.attributes[a][2] = m.attributes[a].value.z;
         }
         d.attributes_count = ( uint32_t ) m.attributes_count;
         d.ior = m.ior;
         d.first_tri = s->first_tri[j]; d.tri_count = ( uint32_t ) s->objects[j].triangles_count;
         d.emissive[0] = m.emissive.value.x; d.emissive[1] = m.emissive.value.y; d.emissive[2] = m.emissive.value.z;
+        s->bsdf_kinds |= 1u << d.bsdf;
+        if ( d.any_texture ) s->bsdf_kinds |= TERRA_KIND_TEX;
     }
-    s->uniform_attr_count = nobj ? ( int ) mats[0].attributes_count : -1;
-    for ( size_t j = 1; j < nobj; ++j ) if ( ( int ) mats[j].attributes_count != s->uniform_attr_count ) s->uniform_attr_count = -1;
-    s->bsdf_kinds = 0;
-    for ( size_t j = 0; j < nobj; ++j ) { s->bsdf_kinds |= 1u << mats[j].bsdf; if ( mats[j].any_texture ) s->bsdf_kinds |= TERRA_KIND_TEX; }
-    // environment (extension, off by default): constant colour or a lat-long lookup (reference src/Terra.c:468-477)
-    int32_t env_mode = 0, env_tex = -1; float env_color[3] = { 0.f, 0.f, 0.f };
+    s->uniform_attr_count = nobj ? ( int ) f.mats[0].attributes_count : -1;
+    for ( size_t j = 1; j < nobj; ++j ) if ( ( int ) f.mats[j].attributes_count != s->uniform_attr_count ) s->uniform_attr_count = -1;
     if ( s->env_lighting ) {
         const TerraAttribute& env = s->opts.environment_map;
-        if ( env.state == nullptr ) {
-            env_mode = 1; env_color[0] = env.value.x; env_color[1] = env.value.y; env_color[2] = env.value.z;
-        } else {
-            if ( env.eval != terra_texture_sample_latlong ) return fail ( kTerraAmdErrUnsupported, "environment: with environment lighting on, the attribute must be a constant or terra_attribute_init_cubemap (a lat-long lookup by direction)" );
-            const TerraTexture* t = ( const TerraTexture* ) env.state;
-            if ( !t->pixels || !t->width || !t->height || ( t->depth != 1 && t->depth != 4 ) || t->components == 0 ) return fail ( kTerraAmdErrBadArgument, "environment: invalid texture" );
-            size_t k = 0;
-            for ( ; k < textures.size(); ++k ) if ( textures[k] == t ) break;
-            if ( k == textures.size() ) textures.push_back ( t );
-            env_mode = 2; env_tex = ( int32_t ) k;
-        }
+        if ( env.state == nullptr ) { f.env_mode = 1; f.env_color[0] = env.value.x; f.env_color[1] = env.value.y; f.env_color[2] = env.value.z; }
+        else { f.env_mode = 2; f.env_tex = texture_slot ( f.textures, env.state ); }
         s->bsdf_kinds |= TERRA_KIND_ENV;
     }
-    // flatten
-    std::vector<DevTri> tris ( ntri ? ntri : 1 );
-    std::vector<DevProps> props ( ntri ? ntri : 1 );
-    std::vector<float> tri_area ( ntri ? ntri : 1, 0.f );
+}
+static int flatten ( Scene* s, Flat& f ) {
+    const size_t nobj = s->objects_pop;
+    size_t ntri = 0;
+    s->first_tri.assign ( nobj, 0 );
+    for ( size_t j = 0; j < nobj; ++j ) { s->first_tri[j] = ( uint32_t ) ntri; ntri += s->objects[j].triangles_count; }
+    if ( ntri >= 0x7fffffffu ) return fail ( kTerraAmdErrUnsupported, "too many triangles" );
+    f.ntri = ntri;
+    flatten_materials ( s, f );
+    f.tris.resize ( ntri ? ntri : 1 ); f.props.resize ( ntri ? ntri : 1 ); f.tri_area.assign ( ntri ? ntri : 1, 0.f );
     for ( size_t j = 0; j < nobj; ++j ) for ( size_t i = 0; i < s->objects[j].triangles_count; ++i ) {
         const TerraTriangle& t = s->objects[j].triangles[i]; const TerraTriangleProperties& q = s->objects[j].properties[i];
-        DevTri& d = tris[s->first_tri[j] + i];
+        DevTri& d = f.tris[s->first_tri[j] + i];
         d.a[0] = t.a.x; d.a[1] = t.a.y; d.a[2] = t.a.z; d.object = ( uint32_t ) j;
         d.b[0] = t.b.x; d.b[1] = t.b.y; d.b[2] = t.b.z; d.tri_in_object = ( uint32_t ) i;
         d.c[0] = t.c.x; d.c[1] = t.c.y; d.c[2] = t.c.z; d.pad = 0;
-        DevProps& e = props[s->first_tri[j] + i];
+        DevProps& e = f.props[s->first_tri[j] + i];
         memcpy ( e.na, &q.normal_a, 12 ); memcpy ( e.nb, &q.normal_b, 12 ); memcpy ( e.nc, &q.normal_c, 12 );
         memcpy ( e.ta, &q.texcoord_a, 8 ); memcpy ( e.tb, &q.texcoord_b, 8 ); memcpy ( e.tc, &q.texcoord_c, 8 );
         e.pad = 0.f;
     }
-    std::vector<DevLight> lights ( s->lights.size() ? s->lights.size() : 1 );
+    f.lights.resize ( s->lights.size() ? s->lights.size() : 1 );
     for ( size_t l = 0; l < s->lights.size(); ++l ) {
         const uint32_t o = s->lights[l].object;
-        lights[l].object = o; lights[l].first_tri = s->first_tri[o]; lights[l].tri_count = ( uint32_t ) s->objects[o].triangles_count; lights[l].area = s->lights[l].area;
-        for ( size_t i = 0; i < s->objects[o].triangles_count; ++i ) tri_area[s->first_tri[o] + i] = triangle_area ( s->objects[o].triangles[i] );
+        f.lights[l].object = o; f.lights[l].first_tri = s->first_tri[o]; f.lights[l].tri_count = ( uint32_t ) s->objects[o].triangles_count; f.lights[l].area = s->lights[l].area;
+        for ( size_t i = 0; i < s->objects[o].triangles_count; ++i ) f.tri_area[s->first_tri[o] + i] = triangle_area ( s->objects[o].triangles[i] );
     }
     // Device numbering is breadth first (child 0 before child 1), so the top of the tree is the
     // contiguous prefix the kernel stages in LDS. Traversal order depends on the tree's shape and
@@ -831,9 +839,9 @@ static int upload_scene ( Scene* s, const std::vector<int>& set ) {
             for ( int c = 0; c < 2; ++c ) if ( h.type[c] == -1 ) { bfs_of[ ( size_t ) h.index[c]] = ( uint32_t ) order.size(); order.push_back ( ( uint32_t ) h.index[c] ); }
         }
     }
-    std::vector<DevNode> nodes ( s->nodes.size() );
+    f.nodes.resize ( s->nodes.size() );
     for ( size_t k = 0; k < order.size(); ++k ) {
-        const HostNode& h = s->nodes[order[k]]; DevNode& d = nodes[k];
+        const HostNode& h = s->nodes[order[k]]; DevNode& d = f.nodes[k];
         memcpy ( d.min0, &h.aabb[0].min, 12 ); memcpy ( d.max0, &h.aabb[0].max, 12 );
         memcpy ( d.min1, &h.aabb[1].min, 12 ); memcpy ( d.max1, &h.aabb[1].max, 12 );
         for ( int c = 0; c < 2; ++c ) {
@@ -844,38 +852,32 @@ static int upload_scene ( Scene* s, const std::vector<int>& set ) {
             } else { d.child[c] = DEV_CHILD_EMPTY; d.prim[c] = 0; }
         }
     }
-    // test hook (tests/test_gpu_render.py "reachability"): shrink the DEVICE copy of the reference tree's boxes, so that the reference traversal -- as the device replays
-    // it -- misses triangles the watertight test would hit, the situation the reachability replay exists for and that float rounding alone produces too rarely to test
-    if ( s->test_shrink_reference_boxes > 0.f ) {
-        const float g = s->test_shrink_reference_boxes;
-        for ( DevNode& d : nodes ) for ( int a = 0; a < 3; ++a ) {
-            if ( d.max0[a] - d.min0[a] > 2.f * g ) { d.min0[a] += g; d.max0[a] -= g; }
-            if ( d.max1[a] - d.min1[a] > 2.f * g ) { d.min1[a] += g; d.max1[a] -= g; }
-        }
-    }
-    // optional fast tree: same triangles, own node array and leaf-ordered soup with reference visit ranks
-    std::vector<DevNode> fnodes; std::vector<DevTri> ftris; std::vector<uint32_t> rank_for_device;
-    fastbvh::Wide fwide;                // the fast tree as traversed: 4-wide nodes of binary16 planes
-    ReachTables reach_tabs;
-    s->fast_nodes = 0; s->fast_max_stack = 1; s->fast_on_device = false;
-    // traversal policy (see Scene::tree_mode and the containment check above)
-    s->coord_max = 0.f; s->cull_ok = false; s->tree_note.clear();
-    bool margin_ok = true;
-    for ( size_t j = 0; j < nobj && margin_ok; ++j ) margin_ok = coords_within_margin ( &s->objects[j].triangles[0].a.x, s->objects[j].triangles_count * 9 );
+    // rank of every soup triangle in the reference traversal's leaf visit order (all boxes hit). The soup carries the ranks in DevTri::pad: a light-sample ray of the
+    // fast tree tests its triangle before it traverses (trace_device.h fast_expect), and LDS-resident launches of at most TERRA_LEAF_RANK_MAX triangles stage the
+    // triangles in rank order and collect a ray's leaves as a set of ranks (make_tracer, trace_device.h traverse_ranked)
+    f.rank = leaf_ranks ( s );
+    for ( size_t k = 0; k < ntri; ++k ) f.tris[k].pad = f.rank[k];
+    return 0;
+}
+// The traversal policy of the commit (see Scene::tree_mode and the containment check above) and what it implies for the build
+static TreeChoice choose_tree ( const Scene* s, size_t ntri ) {
+    TreeChoice c;
+    const size_t nobj = s->objects_pop;
     bool coords_finite = true;
-    for ( size_t j = 0; j < nobj; ++j ) for ( size_t i = 0; i < s->objects[j].triangles_count * 9; ++i ) { float v = fabsf ( ( &s->objects[j].triangles[0].a.x ) [i] ); if ( v > s->coord_max ) s->coord_max = v; if ( !std::isfinite ( v ) ) coords_finite = false; }
-    const bool resident = terra_scene_fits_lds ( ( uint32_t ) s->nodes.size(), ( uint32_t ) ntri, s->max_stack, ( uint32_t ) nobj, ( uint32_t ) s->lights.size() );
+    for ( size_t j = 0; j < nobj; ++j ) for ( size_t i = 0; i < s->objects[j].triangles_count * 9; ++i ) { float v = fabsf ( ( &s->objects[j].triangles[0].a.x ) [i] ); if ( v > c.coord_max ) c.coord_max = v; if ( !std::isfinite ( v ) ) coords_finite = false; }
+    const bool margin_ok = coords_finite && c.coord_max <= TERRA_CULL_MAX_COORD;          // (coords_within_margin over every vertex)
+    c.resident = terra_scene_fits_lds ( ( uint32_t ) s->nodes.size(), ( uint32_t ) ntri, s->max_stack, ( uint32_t ) nobj, ( uint32_t ) s->lights.size() );
     const bool hooked = s->test_shrink_reference_boxes > 0.f;      // the containment proof below ran on the unshrunk boxes: no shortcut that rests on it
     bool auto_ok = false;
     if ( s->tree_mode == 2 ) {
         std::string why;
-        if ( ntri < 2 ) s->tree_note = "fewer than 2 triangles: replica traversal";
-        else if ( !margin_ok ) { char b[160]; snprintf ( b, sizeof b, "a vertex coordinate exceeds %.1f (largest %.6g): the 1e-4 box margin is not provably above rounding error, replica traversal", ( double ) TERRA_CULL_MAX_COORD, ( double ) s->coord_max ); s->tree_note = b; }
-        else if ( hooked ) s->tree_note = "TEST HOOK terra_amd_debug_shrink_reference_boxes: replica traversal";
-        else if ( !verify_reference_leaf_boxes ( s, why ) ) s->tree_note = why + ": replica traversal";
+        if ( ntri < 2 ) c.note = "fewer than 2 triangles: replica traversal";
+        else if ( !margin_ok ) c.note = format ( "a vertex coordinate exceeds %.1f (largest %.6g): the 1e-4 box margin is not provably above rounding error, replica traversal", ( double ) TERRA_CULL_MAX_COORD, ( double ) c.coord_max );
+        else if ( hooked ) c.note = "TEST HOOK terra_amd_debug_shrink_reference_boxes: replica traversal";
+        else if ( !verify_reference_leaf_boxes ( s, why ) ) c.note = why + ": replica traversal";
         else auto_ok = true;
-    } else s->tree_note = s->tree_mode == 0 ? "replica traversal requested" : "fast tree requested";
-    s->cull_ok = auto_ok;
+    } else c.note = s->tree_mode == 0 ? "replica traversal requested" : "fast tree requested";
+    c.cull_ok = auto_ok;
     // Outside the range the reference's own slab test can numerically miss a box whose triangle the watertight test would hit, so the containment
     // shortcut is gone -- but not the fast tree: with its boxes inflated to the rounding bound it still finds every triangle the watertight test accepts,
     // and a hit stands only if the reference traversal would have reached it (its inner ancestors' slab tests, replayed exactly: for the closest of all hits first, and only
@@ -883,268 +885,252 @@ static int upload_scene ( Scene* s, const std::vector<int>& set ) {
     // up to TERRA_REACH_CAMERA_FACTOR x the scene's largest coordinate from the origin (the camera, checked per call); margin = 128 u x that limit.
     // LDS-resident scenes out of range keep the reference tree and its exact traversal of the inner nodes; their LEAF boxes -- which the reference never tests -- are rebuilt
     // around the triangle's extent with that same margin, so the leaf-box cull only skips triangle tests that cannot succeed: no replay needed (reach_cull).
-    s->reach = false; s->reach_cull = false; s->reach_limit = 0.f;
-    float reach_margin = 0.f;
-    if ( s->tree_mode == 2 && !auto_ok && !margin_ok && ntri >= 2 && coords_finite && s->coord_max <= TERRA_REACH_MAX_COORD ) {
-        s->reach_limit = TERRA_REACH_CAMERA_FACTOR * s->coord_max;
-        reach_margin = 128.f * 5.9604645e-8f * s->reach_limit;
-        char b[256];
-        if ( resident ) {
-            s->reach_cull = true; s->cull_ok = true;
-            snprintf ( b, sizeof b, "largest coordinate %.6g exceeds %.1f: reference tree with the leaf-box cull on leaf boxes rebuilt with a margin of %.3g (scene is LDS-resident)", ( double ) s->coord_max, ( double ) TERRA_CULL_MAX_COORD, ( double ) reach_margin );
+    if ( s->tree_mode == 2 && !auto_ok && !margin_ok && ntri >= 2 && coords_finite && c.coord_max <= TERRA_REACH_MAX_COORD ) {
+        c.reach_limit = TERRA_REACH_CAMERA_FACTOR * c.coord_max;
+        c.reach_margin = 128.f * 5.9604645e-8f * c.reach_limit;
+        if ( c.resident ) {
+            c.reach_cull = true; c.cull_ok = true;
+            c.note = format ( "largest coordinate %.6g exceeds %.1f: reference tree with the leaf-box cull on leaf boxes rebuilt with a margin of %.3g (scene is LDS-resident)", ( double ) c.coord_max, ( double ) TERRA_CULL_MAX_COORD, ( double ) c.reach_margin );
         } else {
-            s->reach = true;
-            snprintf ( b, sizeof b, "largest coordinate %.6g exceeds %.1f: fast tree with boxes inflated by %.3g, the reference's reachability replayed for the closest hit", ( double ) s->coord_max, ( double ) TERRA_CULL_MAX_COORD, ( double ) reach_margin );
-        }
-        s->tree_note = b;
-    }
-    if ( s->reach_cull ) {
-        // every leaf child's box := its triangle's extent +- the margin (united with the stored box): a ray that hits the triangle passes this box's slab test by the
-        // error bound above, at the scene's scale; inner boxes stay as they are (their tests ARE the reference's traversal)
-        for ( DevNode& d : nodes ) for ( int c = 0; c < 2; ++c ) {
-            if ( d.child[c] == DEV_CHILD_EMPTY || ! ( d.child[c] & DEV_CHILD_LEAF ) ) continue;
-            const DevTri& t = tris[d.child[c] & 0x7fffffffu];
-            float* mn = c ? d.min1 : d.min0; float* mx = c ? d.max1 : d.max0;
-            for ( int a = 0; a < 3; ++a ) {
-                const float lo = std::min ( t.a[a], std::min ( t.b[a], t.c[a] ) ) - reach_margin, hi = std::max ( t.a[a], std::max ( t.b[a], t.c[a] ) ) + reach_margin;
-                mn[a] = std::min ( mn[a], lo ); mx[a] = std::max ( mx[a], hi );
-            }
+            c.reach = true;
+            c.note = format ( "largest coordinate %.6g exceeds %.1f: fast tree with boxes inflated by %.3g, the reference's reachability replayed for the closest hit", ( double ) c.coord_max, ( double ) TERRA_CULL_MAX_COORD, ( double ) c.reach_margin );
         }
     }
-    s->use_fast = s->tree_mode == 1 || ( auto_ok && !resident ) || s->reach;
-    const float fast_extra = ( s->reach && reach_margin > 1e-4f ) ? reach_margin - 1e-4f : 0.f;      // on top of the +-1e-4 of every triangle box
+    c.use_fast = s->tree_mode == 1 || ( auto_ok && !c.resident ) || c.reach;
+    c.fast_on_device = c.use_fast && s->tree_builder == 1 && ntri > 64 && terra_amd_device_count() > 0;
+    if ( auto_ok ) c.note = !c.use_fast ? "containment verified: reference tree with the leaf-box cull (scene is LDS-resident)" :
+                            c.fast_on_device ? "containment verified: fast tree built on the device (LBVH; scene is not LDS-resident)" : "containment verified: fast tree (scene is not LDS-resident)";
+    c.fast_extra = ( c.reach && c.reach_margin > 1e-4f ) ? c.reach_margin - 1e-4f : 0.f;      // on top of the +-1e-4 of every triangle box
     // the fast tree's planes are stored as binary16 times a power of two that brings the largest of them (|coordinate| + box margin) below 2^14: binary16 reaches 65,504,
     // and a power of two changes no bit of a plane or a t value -- the kernel divides the ray's inverse direction by the same factor (DevScene::fast_inv_scale)
-    float fast_scale = 1.f;
-    { const float span = s->coord_max + 1e-4f + fast_extra; if ( std::isfinite ( span ) ) while ( span * fast_scale >= 16384.f && fast_scale > 0x1p-100f ) fast_scale *= 0.5f; }
-    std::vector<uint32_t> soup_of_fast;                                                             // reach: soup index of every fast triangle (host-built: known here)
-    // rank of every soup triangle in the reference traversal's leaf visit order (all boxes hit). The soup carries the ranks in DevTri::pad: a light-sample ray of the
-    // fast tree tests its triangle before it traverses (trace_device.h fast_expect), and LDS-resident launches of at most TERRA_LEAF_RANK_MAX triangles stage the
-    // triangles in rank order and collect a ray's leaves as a set of ranks (make_tracer, trace_device.h traverse_ranked)
-    std::vector<uint32_t> rank = leaf_ranks ( s );
-    for ( size_t k = 0; k < ntri; ++k ) tris[k].pad = rank[k];
-    if ( s->use_fast ) {
-        s->fast_on_device = s->tree_builder == 1 && ntri > 64 && terra_amd_device_count() > 0;
-        if ( s->fast_on_device ) {
-            // built after the upload, from the soup already in HBM; the host only supplies the reference visit ranks
-            rank_for_device.swap ( rank );
-        } else {
-            std::vector<fastbvh::Prim> prims ( ntri );
-            for ( size_t j = 0; j < nobj; ++j ) for ( size_t i = 0; i < s->objects[j].triangles_count; ++i ) {
-                fastbvh::Prim& q = prims[s->first_tri[j] + i];
-                q.box = bvh::empty_box(); bvh::grow_by_triangle ( q.box, s->objects[j].triangles[i] );
-                if ( fast_extra > 0.f ) { const float g = fast_extra; q.box.min.x -= g; q.box.min.y -= g; q.box.min.z -= g; q.box.max.x += g; q.box.max.y += g; q.box.max.z += g; }
-                q.c[0] = 0.5f * ( q.box.min.x + q.box.max.x ); q.c[1] = 0.5f * ( q.box.min.y + q.box.max.y ); q.c[2] = 0.5f * ( q.box.min.z + q.box.max.z );
-                q.soup = ( uint32_t ) ( s->first_tri[j] + i );
-            }
-            double t_phase = now_s();
-            fastbvh::Built built = fastbvh::build ( prims );        // (reorders prims into leaf order)
-            phase ( "fast tree (host)", t_phase );
-            if ( timing_on() ) fprintf ( stderr, "[terra_amd timing]   fast tree: %zu nodes, stack %d entries\n", built.nodes.size(), built.max_stack );
-            std::string why;
-            std::vector<TerraAABB> leaf_boxes ( prims.size() );
-            for ( size_t k = 0; k < prims.size(); ++k ) leaf_boxes[k] = prims[k].box;
-            if ( s->tree_mode == 2 && !verify_fast_tree ( built.nodes, leaf_boxes, why ) ) {       // cannot happen with this builder (plain unions); checked because the culling relies on it
-                s->use_fast = false; s->tree_note = why + ": reference tree";
-                built.nodes.clear(); built.order.clear();
-            }
-            fnodes.swap ( built.nodes );
-            if ( s->use_fast ) {
-                double t_w = now_s();
-                fwide = fastbvh::widen ( fnodes, fast_scale );
-                phase ( "  4-wide binary16 nodes", t_w );
-            }
-            ftris.resize ( ntri ? ntri : 1 );
-            for ( size_t k = 0; k < built.order.size(); ++k ) { ftris[k] = tris[built.order[k]]; ftris[k].pad = rank[built.order[k]]; }
-            if ( s->reach && s->use_fast ) soup_of_fast = built.order;
-            s->fast_nodes = ( uint32_t ) fwide.nodes.size(); s->fast_max_stack = fwide.max_stack;
-        }
+    const float span = c.coord_max + 1e-4f + c.fast_extra;
+    if ( std::isfinite ( span ) ) while ( span * c.fast_scale >= 16384.f && c.fast_scale > 0x1p-100f ) c.fast_scale *= 0.5f;
+    return c;
+}
+// The fast tree given up after choose_tree picked it; `why` becomes the note. The same fields fall back in all three cases -- a host-built tree that fails
+// verify_fast_tree (automatic mode), and a host- or device-built tree whose stack would exceed TERRA_FAST_STACK_MAX -- and the reference tree runs with the
+// leaf-box cull the choice allowed (cull_ok, reach_cull, reach_limit and coord_max stay).
+static void fall_back ( TreeChoice& c, const std::string& why ) {
+    c.use_fast = false; c.fast_on_device = false; c.reach = false; c.fast_nodes = 0; c.fast_max_stack = 1; c.note = why;
+}
+// The fast tree: host-built, `tris` is the soup in its leaf order (the device-built tree's is on the device); `wide` the nodes the kernels traverse; `reach` the
+// reachability tables of an out-of-range scene
+struct FastTree { std::vector<DevTri> tris; fastbvh::Wide wide; ReachTables reach; };
+// a triangle's box in the fast tree: the reference's (grown by 1e-4), grown by `extra` more (reach: up to the rounding bound)
+static TerraAABB fast_leaf_box ( const DevTri& d, float extra ) {
+    TerraTriangle t; memcpy ( &t.a, d.a, 12 ); memcpy ( &t.b, d.b, 12 ); memcpy ( &t.c, d.c, 12 );
+    TerraAABB q = bvh::empty_box(); bvh::grow_by_triangle ( q, t );
+    if ( extra > 0.f ) { q.min.x -= extra; q.min.y -= extra; q.min.z -= extra; q.max.x += extra; q.max.y += extra; q.max.z += extra; }
+    return q;
+}
+// What follows either builder: bin = the binary tree, leaf_tris = the soup in its leaf order. A host-built tree that fails the
+// containment check falls back (it cannot: plain unions; checked in automatic mode because the culling relies on it); a device-built one is an error.
+static int finish_fast_tree ( const Scene* s, TreeChoice& c, const Flat& f, const std::vector<DevNode>& bin, const std::vector<DevTri>& leaf_tris, FastTree& ft, double& t_phase ) {
+    std::vector<TerraAABB> boxes ( leaf_tris.size() );
+    for ( size_t k = 0; k < leaf_tris.size(); ++k ) boxes[k] = fast_leaf_box ( leaf_tris[k], c.fast_extra );
+    std::string why;
+    if ( ( c.fast_on_device || s->tree_mode == 2 ) && !verify_fast_tree ( bin, boxes, why ) ) {
+        if ( c.fast_on_device ) return fail ( kTerraAmdErrLaunch, "device tree build: %s", why.c_str() );
+        fall_back ( c, why + ": reference tree" ); ft = FastTree();
+        return 0;
     }
-    if ( s->tree_mode == 2 && s->reach && !s->use_fast ) { s->reach = false; }
+    if ( c.fast_on_device ) phase ( "  read back + containment check", t_phase );
+    if ( c.reach ) {          // the replay tables need the order the builder put the triangles in
+        std::vector<uint32_t> soup_of_fast ( leaf_tris.size() );
+        for ( size_t k = 0; k < leaf_tris.size(); ++k ) soup_of_fast[k] = s->first_tri[leaf_tris[k].object] + leaf_tris[k].tri_in_object;
+        build_reach_tables ( f.nodes, f.tris, soup_of_fast, c.reach_margin, ft.reach );
+        phase ( "  reachability tables", t_phase );
+        if ( timing_on() ) fprintf ( stderr, "[terra_amd timing]   reachability: %llu ancestor levels, %llu to replay (%.2f per triangle)\n", ( unsigned long long ) ft.reach.levels, ( unsigned long long ) ft.reach.replayed, f.ntri ? ( double ) ft.reach.replayed / ( double ) f.ntri : 0. );
+    }
+    ft.wide = fastbvh::widen ( bin, c.fast_scale );
+    phase ( "  4-wide binary16 nodes", t_phase );
+    c.fast_nodes = ( uint32_t ) ft.wide.nodes.size(); c.fast_max_stack = ft.wide.max_stack;
     // the stack of a fast-tree launch keeps its first entries in LDS and the rest in HBM (terra_plan_fast_tree: 4 bytes per entry and resident lane), so depth is no longer
-    // a reason to give the fast tree up -- short of a degenerate tree whose worst case would ask for gigabytes of spill space
-    auto fast_stack_fits = [] ( int depth ) { return depth <= TERRA_FAST_STACK_MAX; };
-    if ( s->use_fast && !s->fast_on_device && !fast_stack_fits ( s->fast_max_stack ) ) {
-        char b[200]; snprintf ( b, sizeof b, "fast tree needs a traversal stack of %d entries (limit %d): %s", s->fast_max_stack, TERRA_FAST_STACK_MAX, s->cull_ok ? "reference tree with the leaf-box cull (global memory)" : "reference tree, replica traversal" );
-        s->use_fast = false; s->reach = false; s->tree_note = b; fnodes.clear(); fwide.nodes.clear(); ftris.clear(); soup_of_fast.clear(); s->fast_nodes = 0; s->fast_max_stack = 1;
+    // a reason to give the fast tree up -- short of a degenerate tree whose worst case would ask for gigabytes of spill space (a Morton-ordered tree over coincident
+    // geometry can be thousands of levels deep)
+    if ( c.fast_max_stack > TERRA_FAST_STACK_MAX ) {
+        fall_back ( c, format ( "%s needs a traversal stack of %d entries (limit %d): %s", c.fast_on_device ? "device-built fast tree" : "fast tree", c.fast_max_stack, TERRA_FAST_STACK_MAX,
+                                c.cull_ok ? "reference tree with the leaf-box cull (global memory)" : "reference tree, replica traversal" ) );
+        ft.wide = fastbvh::Wide(); ft.tris.clear();          // (reachability tables already built stay: the device builder's blob has room for them)
     }
-    if ( s->tree_mode == 2 && auto_ok ) s->tree_note = s->use_fast ? ( s->fast_on_device ? "containment verified: fast tree built on the device (LBVH; scene is not LDS-resident)" : "containment verified: fast tree (scene is not LDS-resident)" ) : ( resident ? "containment verified: reference tree with the leaf-box cull (scene is LDS-resident)" : s->tree_note );
-    if ( s->reach && !s->fast_on_device ) build_reach_tables ( nodes, tris, soup_of_fast, reach_margin, reach_tabs );
-    // The automatic mode's fallbacks are correct and 10-20 x slower on scenes of this size (hall: 110 against 2,400 Msamples/s): say so where a client looks, once per commit.
-    if ( s->tree_mode == 2 && !s->use_fast && !resident && ntri >= 2 )
-        fprintf ( stderr, "[terra_amd] warning: this scene (%zu triangles) is traversed through the reference tree%s, typically 10-20 x slower than the fast tree -- %s\n", ntri,
-                  s->cull_ok ? " with the leaf-box cull" : " decision by decision", s->tree_note.c_str() );
-    // one blob, 256-byte aligned sections
-    auto align = [] ( size_t v ) { return ( v + 255 ) & ~size_t ( 255 ); };
-    size_t o_nodes = 0, o_tris = align ( o_nodes + nodes.size() * sizeof ( DevNode ) ), o_props = align ( o_tris + tris.size() * sizeof ( DevTri ) );
-    size_t o_mats = align ( o_props + props.size() * sizeof ( DevProps ) ), o_lights = align ( o_mats + mats.size() * sizeof ( DevMaterial ) );
-    size_t o_area = align ( o_lights + lights.size() * sizeof ( DevLight ) ), o_fn = align ( o_area + tri_area.size() * sizeof ( float ) );
-    // o_fn: the device builder's output (a binary tree of at most n - 1 nodes; host-built trees do not need it on the device), o_fh: the wide nodes the kernels traverse
-    const size_t fn_cap = s->fast_on_device ? ntri : 0, fh_cap = s->fast_on_device ? ntri : fwide.nodes.size(), ft_cap = s->fast_on_device ? ntri : ftris.size();
-    size_t o_fh = align ( o_fn + fn_cap * sizeof ( DevNode ) ), o_ft = align ( o_fh + fh_cap * sizeof ( DevFastNode ) ), o_td = align ( o_ft + ft_cap * sizeof ( DevTri ) );
-    const size_t n_replay = s->reach ? ( nodes.size() ? nodes.size() : 1 ) : 0, n_reach_tri = s->reach ? ntri : 0;
-    const size_t o_rp = o_td, o_lp = align ( o_rp + n_replay * sizeof ( DevReplay ) ), o_lm = align ( o_lp + n_reach_tri * 4 ); o_td = align ( o_lm + n_reach_tri * 4 );
-    std::vector<DevTexture> tdesc ( textures.size() );
-    std::vector<size_t> tex_off ( textures.size() );
-    size_t total = align ( o_td + tdesc.size() * sizeof ( DevTexture ) );
-    for ( size_t k = 0; k < textures.size(); ++k ) {
-        const TerraTexture* t = textures[k];
-        tex_off[k] = total;
-        total = align ( total + ( ( size_t ) t->width * t->height * t->components + 2 ) * t->depth );      // +2 elements: the 3-component read of the last texel
+    if ( c.fast_nodes >= ( 1u << 25 ) ) return fail ( kTerraAmdErrUnsupported, "fast tree of %u nodes: the kernels address the 128-byte nodes by a 32-bit byte offset (at most 2^25 nodes)", c.fast_nodes );
+    return 0;
+}
+static int build_fast_tree_host ( const Scene* s, TreeChoice& c, const Flat& f, FastTree& ft ) {
+    std::vector<fastbvh::Prim> prims ( f.ntri );
+    for ( size_t k = 0; k < f.ntri; ++k ) {
+        fastbvh::Prim& q = prims[k];
+        q.box = fast_leaf_box ( f.tris[k], c.fast_extra );
+        q.c[0] = 0.5f * ( q.box.min.x + q.box.max.x ); q.c[1] = 0.5f * ( q.box.min.y + q.box.max.y ); q.c[2] = 0.5f * ( q.box.min.z + q.box.max.z );
+        q.soup = ( uint32_t ) k;
     }
+    double t_phase = now_s();
+    fastbvh::Built built = fastbvh::build ( prims );        // (reorders prims into leaf order)
+    phase ( "fast tree (host)", t_phase );
+    if ( timing_on() ) fprintf ( stderr, "[terra_amd timing]   fast tree: %zu nodes, stack %d entries\n", built.nodes.size(), built.max_stack );
+    ft.tris.resize ( f.ntri ? f.ntri : 1 );
+    for ( size_t k = 0; k < built.order.size(); ++k ) ft.tris[k] = f.tris[built.order[k]];
+    return finish_fast_tree ( s, c, f, built.nodes, ft.tris, ft, t_phase );
+}
 
-    release_device ( s );
-    if ( terra_amd_device_count() <= 0 ) return fail ( kTerraAmdErrNoDevice, "no HIP device visible: terra_scene_commit built the host tree but cannot upload; terra_render will fail" );
+// ---- the blob: every array of the scene in one allocation, 256-byte aligned sections in this order, then one section per texture ----------------------------
+// c: the choice as it stands before the device builder runs (which sections it needs room for)
+static BlobLayout layout_blob ( const Flat& f, const FastTree& ft, const TreeChoice& c ) {
+    BlobLayout L { std::vector<Section> ( kSecTextures + f.textures.size() ), std::vector<DevTexture> ( f.textures.size() ) };
+    auto section_of = [] ( const auto& v, size_t count ) { return Section { 0, count * sizeof ( v[0] ), v.data(), v.size() * sizeof ( v[0] ) }; };
+    const size_t on_dev = c.fast_on_device ? f.ntri : 0;        // the device builder writes its tree into the blob: room for the largest
+    const size_t n_replay = c.reach ? std::max<size_t> ( f.nodes.size(), 1 ) : 0, n_reach = c.reach ? f.ntri : 0;
+    L.sec[kSecNodes] = section_of ( f.nodes, f.nodes.size() ); L.sec[kSecTris] = section_of ( f.tris, f.tris.size() ); L.sec[kSecProps] = section_of ( f.props, f.props.size() );
+    L.sec[kSecMats] = section_of ( f.mats, f.mats.size() ); L.sec[kSecLights] = section_of ( f.lights, f.lights.size() ); L.sec[kSecArea] = section_of ( f.tri_area, f.tri_area.size() );
+    L.sec[kSecFastBin].bytes = on_dev * sizeof ( DevNode );      // the device builder's output: a binary tree of at most n - 1 nodes
+    L.sec[kSecFastWide] = section_of ( ft.wide.nodes, on_dev ? on_dev : ft.wide.nodes.size() );
+    L.sec[kSecFastTris] = section_of ( ft.tris, on_dev ? on_dev : ft.tris.size() );
+    L.sec[kSecReplay] = section_of ( ft.reach.replay, n_replay );
+    L.sec[kSecLeafParent] = section_of ( ft.reach.leaf_parent, n_reach ); L.sec[kSecLeafMask] = section_of ( ft.reach.leaf_mask, n_reach );
+    L.sec[kSecTexDesc].bytes = f.textures.size() * sizeof ( DevTexture );      // (put_texture_descs: they hold absolute addresses)
+    for ( size_t k = 0; k < f.textures.size(); ++k ) {
+        const TerraTexture* t = f.textures[k];
+        const size_t texels = ( size_t ) t->width * t->height * t->components;
+        L.sec[kSecTextures + k] = Section { 0, ( texels + 2 ) * t->depth, t->pixels, texels * t->depth };      // +2 elements: the 3-component read of the last texel
+        DevTexture& d = L.tdesc[k];
+        d.width = t->width; d.height = t->height; d.components = t->components; d.depth = t->depth; d.filter = t->filter; d.address_mode = t->address_mode;
+    }
+    for ( Section& x : L.sec ) { x.offset = L.total; L.total = ( L.total + x.bytes + 255 ) & ~size_t ( 255 ); }
+    return L;
+}
+static int put_section ( char* base, const Section& x ) {
+    const size_t n = std::min ( x.host_bytes, x.bytes );
+    if ( x.host && n ) HIP_TRY ( hipMemcpy ( base + x.offset, x.host, n, hipMemcpyHostToDevice ), kTerraAmdErrNoDevice );
+    return 0;
+}
+// the texture descriptors hold absolute addresses: written into each copy of the blob
+static int put_texture_descs ( const BlobLayout& L, char* base ) {
+    if ( L.tdesc.empty() ) return 0;
+    std::vector<DevTexture> td = L.tdesc;
+    for ( size_t k = 0; k < td.size(); ++k ) td[k].data = base + L.sec[kSecTextures + k].offset;
+    HIP_TRY ( hipMemcpy ( base + L.sec[kSecTexDesc].offset, td.data(), td.size() * sizeof ( DevTexture ), hipMemcpyHostToDevice ), kTerraAmdErrNoDevice );
+    return 0;
+}
+// every pointer of a scene record into the blob at `base`. Which of the optional ones are set follows from the record's own counts: a fast tree (n_fast_nodes),
+// the device builder's binary tree (its section in the layout), the reachability tables (reach)
+static void bind_blob ( DevScene& dev, const BlobLayout& L, char* base ) {
+    auto at = [&] ( int k ) { return ( const void* ) ( base + L.sec[k].offset ); };
+    const bool fast = dev.n_fast_nodes > 0;
+    dev.nodes = ( const DevNode* ) at ( kSecNodes ); dev.tris = ( const DevTri* ) at ( kSecTris ); dev.props = ( const DevProps* ) at ( kSecProps );
+    dev.mats = ( const DevMaterial* ) at ( kSecMats ); dev.lights = ( const DevLight* ) at ( kSecLights ); dev.tri_area = ( const float* ) at ( kSecArea );
+    dev.textures = L.tdesc.empty() ? nullptr : ( const DevTexture* ) at ( kSecTexDesc );
+    dev.fast_nodes = ( fast && L.sec[kSecFastBin].bytes ) ? ( const DevNode* ) at ( kSecFastBin ) : nullptr;
+    dev.fast_nodes_h = fast ? ( const DevFastNode* ) at ( kSecFastWide ) : nullptr; dev.fast_tris = fast ? ( const DevTri* ) at ( kSecFastTris ) : nullptr;
+    dev.ref_replay = dev.reach ? ( const DevReplay* ) at ( kSecReplay ) : nullptr;
+    dev.fast_leaf_parent = dev.reach ? ( const uint32_t* ) at ( kSecLeafParent ) : nullptr; dev.fast_leaf_mask = dev.reach ? ( const uint32_t* ) at ( kSecLeafMask ) : nullptr;
+}
+
+// the device builder: from the soup already in the blob, into the blob; the binary tree and the leaf-ordered soup come back to the host for finish_fast_tree
+static int build_fast_tree_device ( const Scene* s, TreeChoice& c, const Flat& f, const BlobLayout& L, char* base, FastTree& ft ) {
+    const TreeChoice chosen = c;
+    double t_phase = now_s();
+    uint32_t* d_rank = nullptr;
+    HIP_TRY ( hipMalloc ( ( void** ) &d_rank, f.ntri * sizeof ( uint32_t ) ), kTerraAmdErrNoDevice );
+    hipError_t e = hipMemcpy ( d_rank, f.rank.data(), f.ntri * sizeof ( uint32_t ), hipMemcpyHostToDevice );
+    uint32_t built_nodes = 0; int built_stack = 1;
+    if ( e == hipSuccess ) e = terra_build_fast_tree_device ( ( const DevTri* ) ( base + L.sec[kSecTris].offset ), d_rank, ( uint32_t ) f.ntri, c.fast_extra,
+                                                             ( DevNode* ) ( base + L.sec[kSecFastBin].offset ), ( DevTri* ) ( base + L.sec[kSecFastTris].offset ), &built_nodes, &built_stack, nullptr );
+    ( void ) hipFree ( d_rank );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "device tree build: %s", hipGetErrorString ( e ) );
+    phase ( "fast tree (device LBVH)", t_phase );
+    std::vector<DevNode> bin ( built_nodes ); std::vector<DevTri> leaf_tris ( f.ntri );
+    HIP_TRY ( hipMemcpy ( bin.data(), base + L.sec[kSecFastBin].offset, bin.size() * sizeof ( DevNode ), hipMemcpyDeviceToHost ), kTerraAmdErrNoDevice );
+    HIP_TRY ( hipMemcpy ( leaf_tris.data(), base + L.sec[kSecFastTris].offset, leaf_tris.size() * sizeof ( DevTri ), hipMemcpyDeviceToHost ), kTerraAmdErrNoDevice );
+    if ( int rc = finish_fast_tree ( s, c, f, bin, leaf_tris, ft, t_phase ) ) return rc;
+    const BlobLayout now = layout_blob ( f, ft, chosen );          // (the same sections, now with the host data)
+    for ( int k : { kSecFastWide, kSecReplay, kSecLeafParent, kSecLeafMask } ) if ( int rc = put_section ( base, now.sec[k] ) ) return rc;
+    return 0;
+}
+
+// environment importance sampling (extension, UNPINNED; the oracle's env_table_build restates it): the map as the reference's TerraDistribution2D would hold it
+// (terra_distribution_2d_init, src/Terra.c:812-829: per row a running float sum in index order divided by its total, then the same over the rows' totals).
+// table = f (nx x ny), its rows' normalised running sums, the rows' totals, their normalised running sum
+struct EnvTable { std::vector<float> table; size_t nx = 0, ny = 0; float integral = 0.f; bool monotone = false; };
+static EnvTable env_table ( const TerraTexture* tex ) {
+    TerraTexture* t = const_cast<TerraTexture*> ( tex );
+    const size_t nx = t->width, ny = t->height, cells = nx * ny;
+    EnvTable e { std::vector<float> ( 2 * cells + 2 * ny ), nx, ny };
+    float* f = e.table.data(), * cdf = f + cells, * row_f = cdf + cells, * row_cdf = row_f + ny;
+    bool mono = true;
+    auto row_init = [&mono] ( const float* v, size_t n, float* c ) {
+        float integral = 0.f;
+        for ( size_t i = 0; i < n; ++i ) { mono = mono && v[i] >= 0.f; integral += v[i]; c[i] = integral; }
+        for ( size_t i = 0; i < n; ++i ) c[i] /= integral;
+        return integral;
+    };
+    for ( size_t y = 0; y < ny; ++y ) {
+        const float sin_row = sinf ( ( ( float ) y + 0.5f ) / ( float ) ny * terra_PI );
+        for ( size_t x = 0; x < nx; ++x ) {
+            const TerraFloat3 c = terra_texture_read ( t, x, y );
+            float lum = 0.2126f * c.x; lum += 0.7152f * c.y; lum += 0.0722f * c.z;
+            f[y * nx + x] = lum * sin_row;
+        }
+        row_f[y] = row_init ( f + y * nx, nx, cdf + y * nx );
+    }
+    e.integral = row_init ( row_f, ny, row_cdf );
+    e.monotone = mono && e.integral > 0.f && e.integral <= FLT_MAX;      // then every running sum is non-decreasing: bisection finds the scan's bucket
+    return e;
+}
+
+// the scene's first copy, on replicas[0]: the blob, the device builder's tree if the choice asks for one, the scene record, the environment table
+static int upload ( Scene* s, int device, const Flat& f, FastTree& ft ) {
+    TreeChoice& c = s->tree;
+    BlobLayout L = layout_blob ( f, ft, c );
     s->replicas.resize ( 1 );
     Scene::Replica& r = s->replicas[0]; DevScene& dev = r.dev;
-    r.device = set[0];
+    r.device = device;
     HIP_TRY ( hipSetDevice ( r.device ), kTerraAmdErrNoDevice );
-    HIP_TRY ( hipMalloc ( &r.d_blob, total ), kTerraAmdErrNoDevice );
-    HIP_TRY ( hipMemset ( r.d_blob, 0, total ), kTerraAmdErrNoDevice );
+    HIP_TRY ( hipMalloc ( &r.d_blob, L.total ), kTerraAmdErrNoDevice );
+    HIP_TRY ( hipMemset ( r.d_blob, 0, L.total ), kTerraAmdErrNoDevice );
     HIP_TRY ( hipMalloc ( ( void** ) &r.d_counters, kCtrCount * sizeof ( unsigned long long ) ), kTerraAmdErrNoDevice );
     HIP_TRY ( hipMemset ( r.d_counters, 0, kCtrCount * sizeof ( unsigned long long ) ), kTerraAmdErrNoDevice );
     char* base = ( char* ) r.d_blob;
-    HIP_TRY ( hipMemcpy ( base + o_nodes, nodes.data(), nodes.size() * sizeof ( DevNode ), hipMemcpyHostToDevice ), kTerraAmdErrNoDevice );
-    HIP_TRY ( hipMemcpy ( base + o_tris, tris.data(), tris.size() * sizeof ( DevTri ), hipMemcpyHostToDevice ), kTerraAmdErrNoDevice );
-    HIP_TRY ( hipMemcpy ( base + o_props, props.data(), props.size() * sizeof ( DevProps ), hipMemcpyHostToDevice ), kTerraAmdErrNoDevice );
-    HIP_TRY ( hipMemcpy ( base + o_mats, mats.data(), mats.size() * sizeof ( DevMaterial ), hipMemcpyHostToDevice ), kTerraAmdErrNoDevice );
-    HIP_TRY ( hipMemcpy ( base + o_lights, lights.data(), lights.size() * sizeof ( DevLight ), hipMemcpyHostToDevice ), kTerraAmdErrNoDevice );
-    HIP_TRY ( hipMemcpy ( base + o_area, tri_area.data(), tri_area.size() * sizeof ( float ), hipMemcpyHostToDevice ), kTerraAmdErrNoDevice );
-    if ( !fwide.nodes.empty() ) {
-        HIP_TRY ( hipMemcpy ( base + o_fh, fwide.nodes.data(), fwide.nodes.size() * sizeof ( DevFastNode ), hipMemcpyHostToDevice ), kTerraAmdErrNoDevice );
-        HIP_TRY ( hipMemcpy ( base + o_ft, ftris.data(), ftris.size() * sizeof ( DevTri ), hipMemcpyHostToDevice ), kTerraAmdErrNoDevice );
-    }
-    auto upload_reach_tables = [&] () -> int {
-        HIP_TRY ( hipMemcpy ( base + o_rp, reach_tabs.replay.data(), n_replay * sizeof ( DevReplay ), hipMemcpyHostToDevice ), kTerraAmdErrNoDevice );
-        HIP_TRY ( hipMemcpy ( base + o_lp, reach_tabs.leaf_parent.data(), n_reach_tri * 4, hipMemcpyHostToDevice ), kTerraAmdErrNoDevice );
-        HIP_TRY ( hipMemcpy ( base + o_lm, reach_tabs.leaf_mask.data(), n_reach_tri * 4, hipMemcpyHostToDevice ), kTerraAmdErrNoDevice );
-        if ( timing_on() ) fprintf ( stderr, "[terra_amd timing]   reachability: %llu ancestor levels, %llu to replay (%.2f per triangle)\n", ( unsigned long long ) reach_tabs.levels, ( unsigned long long ) reach_tabs.replayed, ntri ? ( double ) reach_tabs.replayed / ( double ) ntri : 0. );
-        return 0;
-    };
-    if ( s->reach && !s->fast_on_device ) { if ( int rc = upload_reach_tables() ) return rc; }
-    bool have_fast = !fwide.nodes.empty();
-    if ( s->fast_on_device ) {
-        double t_phase = now_s();
-        uint32_t* d_rank = nullptr;
-        HIP_TRY ( hipMalloc ( ( void** ) &d_rank, ntri * sizeof ( uint32_t ) ), kTerraAmdErrNoDevice );
-        hipError_t e = hipMemcpy ( d_rank, rank_for_device.data(), ntri * sizeof ( uint32_t ), hipMemcpyHostToDevice );
-        uint32_t built_nodes = 0; int built_stack = 1;
-        if ( e == hipSuccess ) e = terra_build_fast_tree_device ( ( const DevTri* ) ( base + o_tris ), d_rank, ( uint32_t ) ntri, fast_extra, ( DevNode* ) ( base + o_fn ), ( DevTri* ) ( base + o_ft ), &built_nodes, &built_stack, nullptr );
-        ( void ) hipFree ( d_rank );
-        if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "device tree build: %s", hipGetErrorString ( e ) );
-        phase ( "fast tree (device LBVH)", t_phase );
-        // the binary tree comes back to the host: it is checked like a host-built one (automatic mode: the culling relies on containment) and made 4-wide there
-        std::vector<DevNode> rn ( built_nodes );
-        HIP_TRY ( hipMemcpy ( rn.data(), base + o_fn, rn.size() * sizeof ( DevNode ), hipMemcpyDeviceToHost ), kTerraAmdErrNoDevice );
-        {   // (every device-built tree is checked, whatever the tree mode: the read-back is needed for the wide nodes anyway)
-            std::vector<DevTri> rt ( ntri );
-            HIP_TRY ( hipMemcpy ( rt.data(), base + o_ft, rt.size() * sizeof ( DevTri ), hipMemcpyDeviceToHost ), kTerraAmdErrNoDevice );
-            std::vector<TerraAABB> leaf_boxes ( ntri );
-            for ( size_t k = 0; k < ntri; ++k ) {
-                TerraTriangle t; memcpy ( &t.a, rt[k].a, 12 ); memcpy ( &t.b, rt[k].b, 12 ); memcpy ( &t.c, rt[k].c, 12 );
-                leaf_boxes[k] = bvh::empty_box(); bvh::grow_by_triangle ( leaf_boxes[k], t );
-                if ( fast_extra > 0.f ) { const float g = fast_extra; TerraAABB& q = leaf_boxes[k]; q.min.x -= g; q.min.y -= g; q.min.z -= g; q.max.x += g; q.max.y += g; q.max.z += g; }
-            }
-            std::string why;
-            if ( !verify_fast_tree ( rn, leaf_boxes, why ) ) return fail ( kTerraAmdErrLaunch, "device tree build: %s", why.c_str() );
-            phase ( "  read back + containment check", t_phase );
-            if ( s->reach ) {          // the replay tables need the order the device put the triangles in
-                soup_of_fast.resize ( ntri );
-                for ( size_t k = 0; k < ntri; ++k ) soup_of_fast[k] = s->first_tri[rt[k].object] + rt[k].tri_in_object;
-                build_reach_tables ( nodes, tris, soup_of_fast, reach_margin, reach_tabs );
-                if ( int rc = upload_reach_tables() ) return rc;
-                phase ( "  reachability tables", t_phase );
-            }
-        }
-        fwide = fastbvh::widen ( rn, fast_scale );
-        phase ( "  4-wide binary16 nodes", t_phase );
-        s->fast_nodes = ( uint32_t ) fwide.nodes.size(); s->fast_max_stack = fwide.max_stack; have_fast = true;
-        if ( !fast_stack_fits ( fwide.max_stack ) ) {          // (a Morton-ordered tree over coincident geometry can be thousands of levels deep)
-            char b[240]; snprintf ( b, sizeof b, "device-built fast tree needs a traversal stack of %d entries (limit %d): %s", fwide.max_stack, TERRA_FAST_STACK_MAX, s->cull_ok ? "reference tree with the leaf-box cull (global memory)" : "reference tree, replica traversal" );
-            s->use_fast = false; s->reach = false; s->fast_on_device = false; s->tree_note = b; s->fast_nodes = 0; s->fast_max_stack = 1; have_fast = false;
-            if ( s->tree_mode == 2 && auto_ok && resident ) s->tree_note = "containment verified: reference tree with the leaf-box cull (scene is LDS-resident)";
-        } else HIP_TRY ( hipMemcpy ( base + o_fh, fwide.nodes.data(), fwide.nodes.size() * sizeof ( DevFastNode ), hipMemcpyHostToDevice ), kTerraAmdErrNoDevice );
-    }
-    if ( have_fast && s->fast_nodes >= ( 1u << 25 ) ) return fail ( kTerraAmdErrUnsupported, "fast tree of %u nodes: the kernels address the 128-byte nodes by a 32-bit byte offset (at most 2^25 nodes)", s->fast_nodes );
-    for ( size_t k = 0; k < textures.size(); ++k ) {
-        const TerraTexture* t = textures[k];
-        HIP_TRY ( hipMemcpy ( base + tex_off[k], t->pixels, ( size_t ) t->width * t->height * t->components * t->depth, hipMemcpyHostToDevice ), kTerraAmdErrNoDevice );
-        tdesc[k].data = base + tex_off[k]; tdesc[k].width = t->width; tdesc[k].height = t->height; tdesc[k].components = t->components;
-        tdesc[k].depth = t->depth; tdesc[k].filter = t->filter; tdesc[k].address_mode = t->address_mode;
-    }
-    if ( !tdesc.empty() ) HIP_TRY ( hipMemcpy ( base + o_td, tdesc.data(), tdesc.size() * sizeof ( DevTexture ), hipMemcpyHostToDevice ), kTerraAmdErrNoDevice );
-    dev.textures = tdesc.empty() ? nullptr : ( const DevTexture* ) ( base + o_td );
-    s->d_bytes = total; s->blob_bytes = total; s->o_tdesc = o_td; s->tdesc_host = tdesc; s->env_dist_floats = 0;
-    dev.nodes = ( const DevNode* ) ( base + o_nodes ); dev.tris = ( const DevTri* ) ( base + o_tris ); dev.props = ( const DevProps* ) ( base + o_props );
-    dev.mats = ( const DevMaterial* ) ( base + o_mats ); dev.lights = ( const DevLight* ) ( base + o_lights ); dev.tri_area = ( const float* ) ( base + o_area );
-    dev.n_nodes = ( uint32_t ) nodes.size(); dev.n_tris = ( uint32_t ) ntri; dev.n_objects = ( uint32_t ) nobj; dev.n_lights = ( uint32_t ) s->lights.size();
+    for ( const Section& x : L.sec ) if ( int rc = put_section ( base, x ) ) return rc;
+    if ( int rc = put_texture_descs ( L, base ) ) return rc;
+    if ( c.fast_on_device ) { if ( int rc = build_fast_tree_device ( s, c, f, L, base, ft ) ) return rc; }
+    for ( Section& x : L.sec ) { x.host = nullptr; x.host_bytes = 0; }          // (the host data is this commit's)
+    s->blob = std::move ( L ); s->d_bytes = s->blob.total; s->env_dist_floats = 0;
+    dev.n_nodes = ( uint32_t ) f.nodes.size(); dev.n_tris = ( uint32_t ) f.ntri; dev.n_objects = ( uint32_t ) s->objects_pop; dev.n_lights = ( uint32_t ) s->lights.size();
     dev.lights_triangles_count = ( uint32_t ) s->lights_triangles_count; dev.max_stack = s->max_stack;
-    dev.fast_nodes = ( have_fast && s->fast_on_device ) ? ( const DevNode* ) ( base + o_fn ) : nullptr; dev.fast_nodes_h = have_fast ? ( const DevFastNode* ) ( base + o_fh ) : nullptr; dev.fast_tris = have_fast ? ( const DevTri* ) ( base + o_ft ) : nullptr;
-    dev.n_fast_nodes = s->fast_nodes; dev.fast_max_stack = s->fast_max_stack; dev.fast_inv_scale = 1.f / fast_scale;
-    dev.reach = ( s->reach && have_fast && !reach_tabs.leaf_parent.empty() ) ? 1u : 0u;
-    dev.ref_replay = dev.reach ? ( const DevReplay* ) ( base + o_rp ) : nullptr; dev.fast_leaf_parent = dev.reach ? ( const uint32_t* ) ( base + o_lp ) : nullptr; dev.fast_leaf_mask = dev.reach ? ( const uint32_t* ) ( base + o_lm ) : nullptr;
-    dev.env_mode = env_mode; dev.env_tex = env_tex; memcpy ( dev.env_color, env_color, sizeof env_color );
+    dev.n_fast_nodes = c.fast_nodes; dev.fast_max_stack = c.fast_max_stack; dev.fast_inv_scale = 1.f / c.fast_scale;
+    dev.reach = ( c.reach && c.fast_nodes > 0 && !ft.reach.leaf_parent.empty() ) ? 1u : 0u;
+    bind_blob ( dev, s->blob, base );
+    dev.env_mode = f.env_mode; dev.env_tex = f.env_tex; memcpy ( dev.env_color, f.env_color, sizeof f.env_color );
     dev.sincos24 = sincos_table_of ( r.device );
-    // environment importance sampling (extension, UNPINNED; the oracle's env_table_build restates it): the map as the reference's TerraDistribution2D would hold it
-    // (terra_distribution_2d_init, src/Terra.c:812-829: per row a running float sum in index order divided by its total, then the same over the rows' totals)
-    if ( s->env_sampling && env_mode == 2 && textures[env_tex]->components >= 3 ) {        // (the table reads three components per texel)
-        TerraTexture* t = const_cast<TerraTexture*> ( textures[env_tex] );
-        const size_t nx = t->width, ny = t->height, cells = nx * ny;
-        std::vector<float> tab ( 2 * cells + 2 * ny );
-        float* f = tab.data(), * cdf = f + cells, * row_f = cdf + cells, * row_cdf = row_f + ny;
-        bool mono = true;
-        auto row_init = [&mono] ( const float* v, size_t n, float* c ) {
-            float integral = 0.f;
-            for ( size_t i = 0; i < n; ++i ) { mono = mono && v[i] >= 0.f; integral += v[i]; c[i] = integral; }
-            for ( size_t i = 0; i < n; ++i ) c[i] /= integral;
-            return integral;
-        };
-        for ( size_t y = 0; y < ny; ++y ) {
-            const float sin_row = sinf ( ( ( float ) y + 0.5f ) / ( float ) ny * terra_PI );
-            for ( size_t x = 0; x < nx; ++x ) {
-                const TerraFloat3 c = terra_texture_read ( t, x, y );
-                float lum = 0.2126f * c.x; lum += 0.7152f * c.y; lum += 0.0722f * c.z;
-                f[y * nx + x] = lum * sin_row;
-            }
-            row_f[y] = row_init ( f + y * nx, nx, cdf + y * nx );
-        }
-        const float integral = row_init ( row_f, ny, row_cdf );
-        HIP_TRY ( hipMalloc ( ( void** ) &r.d_env_dist, tab.size() * sizeof ( float ) ), kTerraAmdErrNoDevice );
-        HIP_TRY ( hipMemcpy ( r.d_env_dist, tab.data(), tab.size() * sizeof ( float ), hipMemcpyHostToDevice ), kTerraAmdErrNoDevice );
-        s->d_bytes += tab.size() * sizeof ( float ); s->env_dist_floats = tab.size();
-        dev.env_f = r.d_env_dist; dev.env_cdf = r.d_env_dist + cells; dev.env_row_f = r.d_env_dist + 2 * cells; dev.env_row_cdf = r.d_env_dist + 2 * cells + ny;
-        dev.env_nx = ( uint32_t ) nx; dev.env_ny = ( uint32_t ) ny; dev.env_integral = integral;
-        dev.env_monotone = ( mono && integral > 0.f && integral <= FLT_MAX ) ? 1u : 0u;      // then every running sum is non-decreasing: bisection finds the scan's bucket
+    if ( s->env_sampling && f.env_mode == 2 && f.textures[f.env_tex]->components >= 3 ) {        // (the table reads three components per texel)
+        const EnvTable e = env_table ( f.textures[f.env_tex] );
+        const size_t cells = e.nx * e.ny;
+        HIP_TRY ( hipMalloc ( ( void** ) &r.d_env_dist, e.table.size() * sizeof ( float ) ), kTerraAmdErrNoDevice );
+        HIP_TRY ( hipMemcpy ( r.d_env_dist, e.table.data(), e.table.size() * sizeof ( float ), hipMemcpyHostToDevice ), kTerraAmdErrNoDevice );
+        s->d_bytes += e.table.size() * sizeof ( float ); s->env_dist_floats = e.table.size();
+        dev.env_f = r.d_env_dist; dev.env_cdf = r.d_env_dist + cells; dev.env_row_f = r.d_env_dist + 2 * cells; dev.env_row_cdf = r.d_env_dist + 2 * cells + e.ny;
+        dev.env_nx = ( uint32_t ) e.nx; dev.env_ny = ( uint32_t ) e.ny; dev.env_integral = e.integral; dev.env_monotone = e.monotone ? 1u : 0u;
     }
     s->device_ok = true;
     return 0;
 }
 
 // The committed scene on the other devices of the set: the primary device's finished blob (trees built, boxes converted, tables filled) copied device to device,
-// every pointer into it moved by the difference of the two base addresses, the texture descriptors -- which hold absolute addresses -- written again.
+// its record bound to the copy (bind_blob), the texture descriptors written again.
 static int replicate_scene ( Scene* s, const std::vector<int>& set ) {
     for ( size_t k = 1; k < set.size(); ++k ) {
         Scene::Replica r; r.device = set[k];
         HIP_TRY ( hipSetDevice ( r.device ), kTerraAmdErrNoDevice );
-        HIP_TRY ( hipMalloc ( &r.d_blob, s->blob_bytes ), kTerraAmdErrNoDevice );
+        HIP_TRY ( hipMalloc ( &r.d_blob, s->blob.total ), kTerraAmdErrNoDevice );
         s->replicas.push_back ( r );                                // (owned from here on: release_device frees it whatever fails below)
         const Scene::Replica& r0 = s->replicas[0]; Scene::Replica& q = s->replicas.back();
-        const char* base0 = ( const char* ) r0.d_blob;
-        HIP_TRY ( hipMemcpyPeer ( q.d_blob, q.device, r0.d_blob, r0.device, s->blob_bytes ), kTerraAmdErrNoDevice );
+        HIP_TRY ( hipMemcpyPeer ( q.d_blob, q.device, r0.d_blob, r0.device, s->blob.total ), kTerraAmdErrNoDevice );
         HIP_TRY ( hipMalloc ( ( void** ) &q.d_counters, kCtrCount * sizeof ( unsigned long long ) ), kTerraAmdErrNoDevice );
         HIP_TRY ( hipMemset ( q.d_counters, 0, kCtrCount * sizeof ( unsigned long long ) ), kTerraAmdErrNoDevice );
         char* base = ( char* ) q.d_blob;
-        auto move = [&] ( const void* p ) -> const void* { return p ? ( const void* ) ( base + ( ( const char* ) p - base0 ) ) : nullptr; };
         q.dev = r0.dev;
-        q.dev.nodes = ( const DevNode* ) move ( r0.dev.nodes ); q.dev.tris = ( const DevTri* ) move ( r0.dev.tris ); q.dev.props = ( const DevProps* ) move ( r0.dev.props );
-        q.dev.mats = ( const DevMaterial* ) move ( r0.dev.mats ); q.dev.lights = ( const DevLight* ) move ( r0.dev.lights ); q.dev.tri_area = ( const float* ) move ( r0.dev.tri_area );
-        q.dev.textures = ( const DevTexture* ) move ( r0.dev.textures ); q.dev.fast_nodes = ( const DevNode* ) move ( r0.dev.fast_nodes ); q.dev.fast_nodes_h = ( const DevFastNode* ) move ( r0.dev.fast_nodes_h ); q.dev.fast_tris = ( const DevTri* ) move ( r0.dev.fast_tris );
-        q.dev.ref_replay = ( const DevReplay* ) move ( r0.dev.ref_replay ); q.dev.fast_leaf_parent = ( const uint32_t* ) move ( r0.dev.fast_leaf_parent ); q.dev.fast_leaf_mask = ( const uint32_t* ) move ( r0.dev.fast_leaf_mask );
-        if ( !s->tdesc_host.empty() ) {
-            std::vector<DevTexture> td = s->tdesc_host;
-            for ( DevTexture& t : td ) t.data = move ( t.data );
-            HIP_TRY ( hipMemcpy ( base + s->o_tdesc, td.data(), td.size() * sizeof ( DevTexture ), hipMemcpyHostToDevice ), kTerraAmdErrNoDevice );
-        }
+        bind_blob ( q.dev, s->blob, base );
+        if ( int rc = put_texture_descs ( s->blob, base ) ) return rc;
         if ( r0.d_env_dist && s->env_dist_floats ) {
             HIP_TRY ( hipMalloc ( ( void** ) &q.d_env_dist, s->env_dist_floats * sizeof ( float ) ), kTerraAmdErrNoDevice );
             HIP_TRY ( hipMemcpyPeer ( q.d_env_dist, q.device, r0.d_env_dist, r0.device, s->env_dist_floats * sizeof ( float ) ), kTerraAmdErrNoDevice );
@@ -1152,11 +1138,11 @@ static int replicate_scene ( Scene* s, const std::vector<int>& set ) {
             q.dev.env_f = emove ( r0.dev.env_f ); q.dev.env_cdf = emove ( r0.dev.env_cdf ); q.dev.env_row_f = emove ( r0.dev.env_row_f ); q.dev.env_row_cdf = emove ( r0.dev.env_row_cdf );
         }
         q.dev.sincos24 = sincos_table_of ( q.device );
-        // self-check, independent of the list above: no 8-byte word of the replica's scene record may still be an address inside the PRIMARY's blob (or its
-        // environment tables) -- a pointer member added to DevScene and forgotten here would be exactly that, and on a single box it would even keep working
+        // self-check, independent of bind_blob: no 8-byte word of the replica's scene record may still be an address inside the PRIMARY's blob (or its
+        // environment tables) -- a pointer member added to DevScene and set outside bind_blob would be exactly that, and on a single box it would even keep working
         {
             uint64_t words[ ( sizeof ( DevScene ) + 7 ) / 8] = { 0 }; memcpy ( words, &q.dev, sizeof ( DevScene ) );
-            const uint64_t b0 = ( uint64_t ) ( uintptr_t ) base0, b1 = b0 + s->blob_bytes, e0 = ( uint64_t ) ( uintptr_t ) r0.d_env_dist, e1 = e0 + s->env_dist_floats * sizeof ( float );
+            const uint64_t b0 = ( uint64_t ) ( uintptr_t ) r0.d_blob, b1 = b0 + s->blob.total, e0 = ( uint64_t ) ( uintptr_t ) r0.d_env_dist, e1 = e0 + s->env_dist_floats * sizeof ( float );
             for ( size_t i = 0; i < sizeof ( DevScene ) / 8; ++i )
                 if ( ( words[i] >= b0 && words[i] < b1 ) || ( e0 && words[i] >= e0 && words[i] < e1 ) )
                     return fail ( kTerraAmdErrLaunch, "scene replica for device %d: byte %zu of its scene record still points into the primary device's copy (a pointer that replicate_scene does not rebase)", q.device, i * 8 );
@@ -1164,6 +1150,43 @@ static int replicate_scene ( Scene* s, const std::vector<int>& set ) {
     }
     HIP_TRY ( hipSetDevice ( set[0] ), kTerraAmdErrNoDevice );
     return 0;
+}
+
+// the stages up to the scene's first device copy
+static int commit_scene ( Scene* s, int device ) {
+    std::string why;
+    if ( int st = check_materials ( s, s->opts, why ) ) return fail ( ( TerraAmdStatus ) st, "%s", why.c_str() );
+    Flat f;
+    if ( int rc = flatten ( s, f ) ) return rc;
+    // test hook (tests/test_gpu_render.py "reachability"): shrink the DEVICE copy of the reference tree's boxes, so that the reference traversal -- as the device replays
+    // it -- misses triangles the watertight test would hit, the situation the reachability replay exists for and that float rounding alone produces too rarely to test
+    const float g = s->test_shrink_reference_boxes;
+    if ( g > 0.f ) for ( DevNode& d : f.nodes ) for ( int a = 0; a < 3; ++a ) {
+        if ( d.max0[a] - d.min0[a] > 2.f * g ) { d.min0[a] += g; d.max0[a] -= g; }
+        if ( d.max1[a] - d.min1[a] > 2.f * g ) { d.min1[a] += g; d.max1[a] -= g; }
+    }
+    s->tree = choose_tree ( s, f.ntri );
+    TreeChoice& c = s->tree;
+    // out of range and LDS-resident (reach_cull): every leaf child's box := its triangle's extent +- the margin (united with the stored box): a ray that hits the triangle
+    // passes this box's slab test by the error bound above, at the scene's scale; inner boxes stay as they are (their tests ARE the reference's traversal)
+    if ( c.reach_cull ) for ( DevNode& d : f.nodes ) for ( int k = 0; k < 2; ++k ) {
+        if ( d.child[k] == DEV_CHILD_EMPTY || ! ( d.child[k] & DEV_CHILD_LEAF ) ) continue;
+        const DevTri& t = f.tris[d.child[k] & 0x7fffffffu];
+        float* mn = k ? d.min1 : d.min0; float* mx = k ? d.max1 : d.max0;
+        for ( int a = 0; a < 3; ++a ) {
+            const float lo = std::min ( t.a[a], std::min ( t.b[a], t.c[a] ) ) - c.reach_margin, hi = std::max ( t.a[a], std::max ( t.b[a], t.c[a] ) ) + c.reach_margin;
+            mn[a] = std::min ( mn[a], lo ); mx[a] = std::max ( mx[a], hi );
+        }
+    }
+    FastTree ft;
+    if ( c.use_fast && !c.fast_on_device ) { if ( int rc = build_fast_tree_host ( s, c, f, ft ) ) return rc; }
+    // The automatic mode's fallbacks are correct and 10-20 x slower on scenes of this size (hall: 110 against 2,400 Msamples/s): say so where a client looks, once per commit.
+    if ( s->tree_mode == 2 && !c.use_fast && !c.resident && f.ntri >= 2 )
+        fprintf ( stderr, "[terra_amd] warning: this scene (%zu triangles) is traversed through the reference tree%s, typically 10-20 x slower than the fast tree -- %s\n", f.ntri,
+                  c.cull_ok ? " with the leaf-box cull" : " decision by decision", c.note.c_str() );
+    release_device ( s );
+    if ( terra_amd_device_count() <= 0 ) return fail ( kTerraAmdErrNoDevice, "no HIP device visible: terra_scene_commit built the host tree but cannot upload; terra_render will fail" );
+    return upload ( s, device, f, ft );
 }
 
 extern "C" void terra_scene_commit ( HTerraScene h ) {
@@ -1181,7 +1204,7 @@ extern "C" void terra_scene_commit ( HTerraScene h ) {
             const TerraAttribute& em = s->objects[i].material.emissive;
             TerraFloat3 e = em.value;
             if ( em.state != nullptr ) {            // reference src/Terra.c:199-200: evaluated at uv (0.5, 0.5)
-                if ( em.eval != terra_texture_sample ) continue;       // rejected in upload_scene with a message
+                if ( em.eval != terra_texture_sample ) continue;       // rejected by check_materials with a message
                 TerraFloat2 uv = { 0.5f, 0.5f };
                 e = terra_texture_sample ( em.state, &uv, nullptr );
             }
@@ -1198,13 +1221,13 @@ extern "C" void terra_scene_commit ( HTerraScene h ) {
     s->commit_error.clear();
     // The environment attribute only ever scales a throughput that is then discarded (reference src/Terra.c:1053-1058:
     // the "Lo +=" is commented out), so by default neither a constant nor a textured environment reaches the image and
-    // nothing is uploaded for it; terra_amd_set_environment_lighting(scene, 1) turns that line on (upload_scene binds it).
+    // nothing is uploaded for it; terra_amd_set_environment_lighting(scene, 1) turns that line on (flatten_materials binds it).
     // options travel as kernel arguments; geometry/material/light changes need a new replica
     std::vector<int> set;
     { std::lock_guard<std::mutex> g ( g_devices_lock ); set = g_devices.empty() ? std::vector<int> { g_device } : g_devices; }
     const bool set_changed = set != devices_of ( s );          // (terra_amd_set_devices / terra_amd_set_device since the last commit: the replicas move)
     if ( rebuild || relight || env_changed || !s->device_ok || set_changed ) {
-        if ( upload_scene ( s, set ) != 0 ) { s->commit_error = g_last_error; s->device_ok = false; return; }
+        if ( commit_scene ( s, set[0] ) != 0 ) { s->commit_error = g_last_error; s->device_ok = false; return; }
         if ( set.size() > 1 && replicate_scene ( s, set ) != 0 ) { s->commit_error = g_last_error; release_device ( s ); }
     }
 }
@@ -1254,7 +1277,7 @@ extern "C" int terra_amd_get_stats ( HTerraScene h, TerraAmdStats* out ) {
     out->rays = c[kCtrRays]; out->nodes = c[kCtrNodes]; out->tri_tests = c[kCtrTriTests]; out->hits = c[kCtrHits];
     out->rand_calls = c[kCtrRandCalls]; out->attr_fetches = c[kCtrAttrFetches]; out->tri_culled = c[kCtrTriCulled];
     // derived exactly on the host (see Counters in trace_device.h)
-    out->box_tests = primary ( s ).dev.n_tris >= 2 ? ( s->use_fast ? 4 * out->nodes : s->cull_ok ? 2 * out->nodes : 2 * out->nodes - out->tri_tests ) : 0;      // the fast tree's nodes hold four boxes; with the leaf-box cull every child's slab test is used
+    out->box_tests = primary ( s ).dev.n_tris >= 2 ? ( s->tree.use_fast ? 4 * out->nodes : s->tree.cull_ok ? 2 * out->nodes : 2 * out->nodes - out->tri_tests ) : 0;      // the fast tree's nodes hold four boxes; with the leaf-box cull every child's slab test is used
     out->samples = s->stat_samples; out->pixels = s->stat_pixels; out->launches = s->launches;
     return 0;
 }
@@ -1331,12 +1354,13 @@ static int fill_params ( Scene* s, const Scene::Replica& r, const TerraCamera* c
     p.counters = r.d_counters;
     terra_plan_lds ( p );
     // automatic mode: the containment argument also needs the ray origins (the camera) inside the verified coordinate range
-    const bool cam_ok = ( s->reach || s->reach_cull ) ? ( fabsf ( p.cam_pos[0] ) <= s->reach_limit && fabsf ( p.cam_pos[1] ) <= s->reach_limit && fabsf ( p.cam_pos[2] ) <= s->reach_limit ) : coords_within_margin ( p.cam_pos, 3 );
-    if ( s->use_fast && r.dev.fast_nodes_h && ( s->tree_mode == 1 || cam_ok ) ) terra_plan_fast_tree ( p );
-    else if ( ( s->use_fast || s->cull_ok ) && !cam_ok && !s->warned_camera.exchange ( true ) )          // (once per scene)
+    const TreeChoice& c = s->tree;
+    const bool cam_ok = ( c.reach || c.reach_cull ) ? ( fabsf ( p.cam_pos[0] ) <= c.reach_limit && fabsf ( p.cam_pos[1] ) <= c.reach_limit && fabsf ( p.cam_pos[2] ) <= c.reach_limit ) : coords_within_margin ( p.cam_pos, 3 );
+    if ( c.use_fast && r.dev.fast_nodes_h && ( s->tree_mode == 1 || cam_ok ) ) terra_plan_fast_tree ( p );
+    else if ( ( c.use_fast || c.cull_ok ) && !cam_ok && !s->warned_camera.exchange ( true ) )          // (once per scene)
         fprintf ( stderr, "[terra_amd] warning: camera at (%g, %g, %g) lies outside the range (+-%g) for which this scene's traversal shortcut is proven: this call runs the reference "
                   "tree's replica traversal (same image, typically 10-20 x slower on large scenes); terra_amd_traversal_info() reports camera_limit and last_call\n",
-                  ( double ) p.cam_pos[0], ( double ) p.cam_pos[1], ( double ) p.cam_pos[2], ( double ) ( ( s->reach || s->reach_cull ) ? s->reach_limit : TERRA_CULL_MAX_COORD ) );
+                  ( double ) p.cam_pos[0], ( double ) p.cam_pos[1], ( double ) p.cam_pos[2], ( double ) ( ( c.reach || c.reach_cull ) ? c.reach_limit : TERRA_CULL_MAX_COORD ) );
     if ( s->test_fast_stack_lds > 0 && p.lds_mode == 2 ) {      // TEST HOOK: a short LDS column, so that ordinary scenes exercise the HBM part of the stack
         const uint32_t need = p.stack_depth + p.spill_cap;
         p.stack_depth = need < ( uint32_t ) s->test_fast_stack_lds ? need : ( uint32_t ) s->test_fast_stack_lds; p.spill_cap = need - p.stack_depth;
@@ -1345,8 +1369,8 @@ static int fill_params ( Scene* s, const Scene::Replica& r, const TerraCamera* c
         p.stack_depth += ( uint32_t ) s->test_pad_stack;
         while ( p.leaf_cap > 4 && terra_lds_bytes ( p ) > ( size_t ) 64 * 1024 ) --p.leaf_cap;      // (what terra_plan_lds does for a deep tree)
     }
-    p.leaf_cull = ( s->cull_ok && cam_ok && p.lds_mode != 2 ) ? 1u : 0u;
-    p.fused_slab = ( p.leaf_cull && !s->reach_cull ) ? 1u : 0u;      // (out of range only the rebuilt LEAF boxes carry a margin: the inner boxes are tested exactly as the reference tests them)
+    p.leaf_cull = ( c.cull_ok && cam_ok && p.lds_mode != 2 ) ? 1u : 0u;
+    p.fused_slab = ( p.leaf_cull && !c.reach_cull ) ? 1u : 0u;      // (out of range only the rebuilt LEAF boxes carry a margin: the inner boxes are tested exactly as the reference tests them)
     // the azimuth table pays where VALU issue binds (LDS-resident scenes: Cornell Simple 65.8 -> 64.2 ms, Direct 145.2 -> 142.5); the kernels that wait on memory anyway
     // lose by one more dependent load per shaded hit (sphere scene 395 -> 419 ms, hall 282 -> 284; profiles/r03_measurements/ab_sincos_table.log)
 #ifndef TERRA_SINCOS_TABLE_FAST_TREE       // (A/B) the azimuth table for fast-tree launches too

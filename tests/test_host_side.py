@@ -309,4 +309,20 @@ def test_scene_supported_query(H, L):
     assert st == -3 and b"attribute 0" in why.value and b"terra_texture_sample" in why.value
     assert L.scene_supported(scene, None, 0) == -3                           # the reason is optional
     assert runtime.last_error() == "" and runtime.first_error() == (0, "")   # a pure query: nothing recorded
+    # the query answers with the status the commit records (terra_amd_first_error): a texture with no pixels, on a material and as the environment
+    empty = api.TerraTexture()
+    L.attribute_init_texture(C.byref(extra.material.attributes[0]), C.byref(empty))
+    st = L.scene_supported(scene, why, 256)
+    assert st == -4 and b"attribute 0: invalid texture" in why.value
+    L.scene_commit(scene)
+    assert runtime.first_error() == (st, "object 6 attribute 0: invalid texture")
+    L.clear_error(); L.clear_first_error()
+    L.attribute_init_constant(C.byref(extra.material.attributes[0]), C.byref(api.TerraFloat3(0.5, 0.5, 0.5)))
+    assert L.set_environment_lighting(scene, 1) == 0
+    L.attribute_init_cubemap(C.byref(L.scene_get_options(scene).contents.environment_map), C.byref(empty))
+    st = L.scene_supported(scene, why, 256)
+    assert st == -4 and why.value == b"environment: invalid texture"
+    L.scene_commit(scene)
+    assert runtime.first_error() == (st, "environment: invalid texture")
+    L.clear_error(); L.clear_first_error()
     L.scene_destroy(scene)
