@@ -22,22 +22,27 @@ for a launch of its size (terra_amd_auto_sample_split: 8 / 16 / 32 / 32 lanes pe
 successive calls of spp / split samples; --sample-split S fixes it for every N), so the image does not
 depend on N and a 1/8 share of the frame still fills a GPU.
 
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line: value, ms_per_step, config, commit_ms,
+traversal_note and (N > 1) phases. What is marked (--full) below takes launches, processes or CPU time of its own and runs only with
+that option.
+
 Also on the JSON line (rank 0):
-  roofline     -- against the resource that binds the render kernel (DESIGN.md "Roofline"):
+  roofline     -- (--full) against the resource that binds the render kernel (DESIGN.md "Roofline"):
                   bound "valu" for scenes staged in LDS: achieved = VALU wave-instructions per second (SQ_INSTS_VALU of the
                   committed PMC summary profiles/rNN_pmc.json / the kernel time measured live with HIP events), peak = 1024
                   SIMDs x 2.4 GHz / 2 cycles per wave64 instruction; lane_util and the LDS bank-conflict share beside it;
                   bound "l2_fabric" for scenes read from global memory: achieved = bytes the L2 moved on its fabric side
                   (FETCH_SIZE/WRITE_SIZE PMC passes, Infinity Cache hits included) per second, peak = the 8 TB/s HBM figure.
                   algorithmic_* = SURVEY.md 8d's per-unit bytes x the device work counters, kept as its own field.
-  cpu_baseline -- the reference's own CPU renderer (oracle/_ref, prebuilt from its unmodified sources; kind "reference")
+                  mrays_per_s and counters_per_launch come with it, from one extra untimed launch with the work counters on.
+  cpu_baseline -- (--full) the reference's own CPU renderer (oracle/_ref, prebuilt from its unmodified sources; kind "reference")
                   on all usable host cores over a bounded sample of the same workload, with the oracle's rate beside it
                   (port_value); the oracle alone (kind "port") when the prebuilt reference library is absent. N=1 only.
-  host_api     -- (N=1) the same frame through the drop-in boundary, terra_render() on a host framebuffer, PCIe included: one
+  host_api     -- (--full, N=1) the same frame through the drop-in boundary, terra_render() on a host framebuffer, PCIe included: one
                   full-frame call per step, and the reference client's 128-pixel tile loop from 8 threads. Never `value`.
   phases       -- (N>1) per rank: render / pack / gather / unpack milliseconds per step (HIP events on the two streams), the
-                  slowest rank, and sharded_equals_unsharded (one extra low-spp step, checked bit for bit on rank 0)
-  workloads    -- (N=1, default invocation) the other BASELINE.json configurations measured the same way in the same run,
+                  slowest rank, and (--full or --check) sharded_equals_unsharded (one extra low-spp step, checked bit for bit on rank 0)
+  workloads    -- (--full, N=1, headline config) the other BASELINE.json configurations measured the same way in the same run,
                   each with its own value / ms_per_step / roofline / cpu_baseline. The headline stays configs[1].
 """
 from __future__ import annotations
@@ -78,14 +83,16 @@ def parse_args(argv=None):
     ap.add_argument("--spp", type=int, default=0, help="override samples per pixel (the result is then NOT the headline config)")
     ap.add_argument("--bounces", type=int, default=-1, help="override the maximum number of bounces (the result is then NOT the headline config; 0 = camera rays only)")
     ap.add_argument("--job-order", type=int, default=-1, choices=[-1, 0, 1], help="terra_amd_set_job_order: -1 the library's default (on), 0 / 1 to A/B it (the frame does not change)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-host-api", action="store_true", help="skip the `host_api` block (the same frame through terra_render() on a host framebuffer)")
-    ap.add_argument("--no-workloads", action="store_true", help="skip the `workloads` block (the other configurations)")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline figure does not need: roofline and work counters, cpu_baseline, host_api, "
+                    "the other configurations (workloads) and, when N > 1, sharded_equals_unsharded")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the `cpu_baseline` block")
+    ap.add_argument("--no-host-api", action="store_true", help="--full: skip the `host_api` block (the same frame through terra_render() on a host framebuffer)")
+    ap.add_argument("--no-workloads", action="store_true", help="--full: skip the `workloads` block (the other configurations)")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL, the real path) or gloo (rehearsal of N ranks on fewer GPUs: the gather goes through host memory)")
     ap.add_argument("--tree", default="auto", choices=list(TREE_MODES), help="terra_amd_set_tree_mode: auto (2, the library default: leaf-box cull / fast tree when the scene passes the numeric containment check), reference (0: the reference's tree, every traversal decision reproduced), fast (1)")
     ap.add_argument("--sample-split", type=int, default=DEFAULT_SPLIT, help="terra_amd_set_sample_split: lanes per pixel (the frame equals that of this many successive calls of spp/split samples); 0 (default) = the library's automatic choice for the launch each rank makes (terra_amd_auto_sample_split), a number = the same for every N")
-    ap.add_argument("--check", action="store_true", help="after timing: one low-spp sharded+gathered pass into a fresh frame must equal an unsharded pass bit for bit (rank 0); on by default when N > 1")
-    ap.add_argument("--no-check", action="store_true", help="N > 1: skip that extra pass")
+    ap.add_argument("--check", action="store_true", help="after timing: one low-spp sharded+gathered pass into a fresh frame must equal an unsharded pass bit for bit (rank 0); on by default with --full when N > 1")
+    ap.add_argument("--no-check", action="store_true", help="--full, N > 1: skip that extra pass")
     ap.add_argument("--launch-timeout", type=float, default=900.0, help="seconds the self-started N-rank child may run before its process group is killed (a hung rendezvous must not hang the parent; well below the driver's own 1500 s limit, so that the ranks are gone before the driver kills this parent)")
     ap.add_argument("--master-port", type=int, default=0, help="rendezvous port of the self-started ranks (0 = pick a free one)")
     ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps: write the framebuffer the last timed step left (rank 0, the gathered frame "
@@ -502,8 +509,8 @@ def setup(args):
     return c
 
 
-def measure(c, d, tree, split, steps, warmup, check=False, prewarm_rect=None, dump_dir=""):
-    """K timed steps of workload d; returns the measurement (rank 0) incl. per-launch work counters. dump_dir: rank 0 writes the frame the
+def measure(c, d, tree, split, steps, warmup, check=False, counters=True, prewarm_rect=None, dump_dir=""):
+    """K timed steps of workload d; returns the measurement (rank 0), with per-launch work counters when `counters`. dump_dir: rank 0 writes the frame the
     timed steps left there (dump_outputs) before any untimed launch touches it"""
     from terra_amd import runtime, scenes
     torch, dist, lib, dev = c.torch, c.dist, c.lib, c.dev
@@ -602,12 +609,15 @@ def measure(c, d, tree, split, steps, warmup, check=False, prewarm_rect=None, du
     dumped = dump_outputs(dump_dir, cur["fb"]) if (dump_dir and rank == 0) else None
     # the work counters (rays, nodes, tests, hits: what the roofline's algorithmic bytes are made of) come from ONE EXTRA, untimed launch with the counters
     # enabled (terra_amd_set_work_counters): they are instrumentation, off by default, and the timed launches above ran without them
-    runtime.check(lib.set_work_counters(scene, 1), "terra_amd_set_work_counters")
-    runtime.check(lib.reset_stats(scene))
-    step(); fence()
-    st = runtime.Stats(); runtime.check(lib.get_stats(scene, C.byref(st))); st = st.as_dict()
-    runtime.check(lib.set_work_counters(scene, 0), "terra_amd_set_work_counters")
-    launches = max(1, st["launches"])
+    per_launch = None
+    if counters:
+        runtime.check(lib.set_work_counters(scene, 1), "terra_amd_set_work_counters")
+        runtime.check(lib.reset_stats(scene))
+        step(); fence()
+        st = runtime.Stats(); runtime.check(lib.get_stats(scene, C.byref(st))); st = st.as_dict()
+        runtime.check(lib.set_work_counters(scene, 0), "terra_amd_set_work_counters")
+        launches = max(1, st["launches"])
+        per_launch = {k: v // launches for k, v in st.items() if k != "launches"}
 
     # per-rank phase breakdown (N > 1): where a step's time goes on every rank, so that a scaling shortfall can be attributed
     phases = None
@@ -648,7 +658,7 @@ def measure(c, d, tree, split, steps, warmup, check=False, prewarm_rect=None, du
         lib.scene_destroy(scene2)
     ti2 = runtime.TraversalInfo(); runtime.check(lib.traversal_info(scene, C.byref(ti2)))      # after the launches: what the last call actually ran
     out = {"elapsed": elapsed, "kernel_ms": kernel_ms, "check": ok, "phases": phases, "commit_ms": commit_ms, "split": split, "dumped": dumped,
-           "per_launch": {k: v // launches for k, v in st.items() if k != "launches"},
+           "per_launch": per_launch,
            "traversal": {"fast_tree": bool(ti.fast_tree), "leaf_cull": bool(ti.leaf_cull), "note": ti.note.decode(), "last_call": getattr(ti2, "last_call", None)},
            "lds_resident": bool(ti.lds_resident),
            "triangles": info.triangles}
@@ -779,7 +789,8 @@ def main():
     if args.bounces >= 0:
         d.bounces = args.bounces
     integ_name = {0: "simple", 1: "direct", 2: "mis"}.get(d.integrator, str(d.integrator))
-    m = measure(c, d, args.tree, args.sample_split, args.steps, args.warmup, check=args.check or (world > 1 and not args.no_check), dump_dir=args.dump_outputs)
+    m = measure(c, d, args.tree, args.sample_split, args.steps, args.warmup, check=args.check or (args.full and world > 1 and not args.no_check), counters=args.full,
+                dump_dir=args.dump_outputs)
 
     if rank == 0:
         blk = result_block(d, args.workload, args.tree, m["split"], args.steps, args.warmup, world, m, args.spp, integ_name)
@@ -799,16 +810,16 @@ def main():
             out["dist_backend"] = args.dist_backend
         if m.get("phases"):
             out["phases"] = m["phases"]
-        if world == 1 and not c.dist_on and not args.no_host_api:
+        if args.full and world == 1 and not c.dist_on and not args.no_host_api:
             out["host_api"] = host_api(c, d, args.tree, m["split"], max(1, min(args.steps, 3)))
             # SURVEY.md 8(d)'s own definition of the metric -- wall time of terra_render(), kernel + the tile's D2H included -- as a top-level key beside `value`
             # (which is the device-resident rate the bench contract asks for)
             out["value_terra_render"] = out["host_api"]["full_frame_call"]["value"]
             out["host_api"]["multi_device"] = multi_device_block(args.workload)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(d)
         headline = args.workload == "cornell_1080p_512spp" and not (args.spp or args.integrator or args.bounces >= 0) and args.tree == "auto" and args.sample_split == DEFAULT_SPLIT
-        if world == 1 and not c.dist_on and headline and not args.no_workloads:
+        if args.full and world == 1 and not c.dist_on and headline and not args.no_workloads:
             extra = []; cpu_cache = {}
             for name, tree, integ, split, steps, warmup, prewarm, cpu_s in EXTRA_WORKLOADS:
                 dw = workload(name)

@@ -178,3 +178,24 @@ def test_steps_must_be_positive():
     assert bench.parse_args(["--steps", "7"]).steps == 7
     with pytest.raises(SystemExit):
         bench.parse_args(["--steps", "0"])
+
+
+def test_full_is_off_by_default():
+    import bench
+    assert not bench.parse_args([]).full and bench.parse_args(["--full"]).full
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_and_full_adds_the_rest(tmp_path):
+    """a plain run: the timed steps, the dump and the line, nothing measured besides; --full adds the counting launch (roofline, counters_per_launch)"""
+    def run(*extra):
+        r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--spp", "16"] + list(extra),
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        return json.loads(r.stdout.strip().splitlines()[-1])
+    plain = run("--dump-outputs", str(tmp_path / "dump"))
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0 and plain["dump_outputs"]["arrays"]["pixels"] == [1080, 1920, 3]
+    assert not {"roofline", "counters_per_launch", "mrays_per_s", "cpu_baseline", "host_api", "workloads"} & set(plain)
+    full = run("--full", "--no-cpu-baseline", "--no-host-api")
+    assert full["roofline"]["kernel"] == "terra_render_kernel" and full["counters_per_launch"]["rays"] > 0 and full["mrays_per_s"] > 0
+    assert full["config"] == plain["config"]

@@ -2,7 +2,7 @@
 # HBM traffic (PMC FETCH_SIZE / WRITE_SIZE, separate passes) of the config-3 workload, reference tree and fast tree.
 OUT=$GRAFT_REPO_ROOT/gpurun_out/prof_hall; mkdir -p $OUT; cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 for tree in reference fast; do
-  ARGS="bench.py --workload hall_1080p_256spp --tree $tree --steps 1 --warmup 0 --no-cpu-baseline"
+  ARGS="bench.py --full --workload hall_1080p_256spp --tree $tree --steps 1 --warmup 0 --no-cpu-baseline"
   rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/${tree}_fetch -- python3 $ARGS > $OUT/${tree}_fetch.json 2> $OUT/${tree}_fetch.err
   rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/${tree}_write -- python3 $ARGS > $OUT/${tree}_write.json 2> $OUT/${tree}_write.err
 done

@@ -4,8 +4,8 @@ into profiles/ afterwards).
     python3 tools/profile_round.py [--round r03] [--only KEY_SUBSTRING] [--out gpurun_out/r03_prof]
 
 For every configuration below: one `--kernel-trace --stats` run and four separate `--pmc` runs (SQ group 1, SQ group 2,
-FETCH_SIZE, WRITE_SIZE; counters are never combined with tracing) of `python3 bench.py <args> --no-cpu-baseline
---no-workloads --no-host-api`. This script itself never touches the GPU: every run is a child process with the program right after `--`.
+FETCH_SIZE, WRITE_SIZE; counters are never combined with tracing) of `python3 bench.py --full <args> --no-cpu-baseline
+--no-workloads --no-host-api` (--full: the line's roofline and work counters). This script itself never touches the GPU: every run is a child process with the program right after `--`.
 The JSON it writes is what bench.py's `roofline` reads (keyed like bench.pmc_key); the markdown is the human summary.
 HBM bytes = (2 x FETCH_SIZE + WRITE_SIZE) x 1024 (gfx950: FETCH_SIZE tallies 128-B requests at 64 B, MI355X_MICROARCH.md HBM section).
 """
@@ -119,7 +119,7 @@ def main():
         if a.only and a.only not in key:
             continue
         tag = key.replace("|", "_").replace("=", "-")
-        args = ["bench.py", "--workload", wl, "--tree", tree, "--sample-split", str(split), "--no-cpu-baseline", "--no-workloads", "--no-host-api"] + extra
+        args = ["bench.py", "--full", "--workload", wl, "--tree", tree, "--sample-split", str(split), "--no-cpu-baseline", "--no-workloads", "--no-host-api"] + extra
         d = out / tag; d.mkdir(exist_ok=True)
         print("==", key, flush=True)
         if a.reaggregate or (a.no_trace and (d / "bench_line.json").exists()):
