@@ -31,7 +31,7 @@
  *       [--integrator simple|direct|mis|normals|depth] [--tonemap none|linear|reinhard|filmic|uncharted2]
  *       [--camera px py pz dx dy dz] [--fov deg] [--exposure e] [--gamma g] [--jitter j]
  *       [--no-flip-z] [--normals apollo|file] [--dump-scene file] [--no-render] [--fast-tree | --replica-tree] [--sample-split n] [--seed n] [--tile n] [--gpus n]
- *       [--environment map.hdr|map.pfm] [--environment-color r g b] [--env-light] [--env-sampling off|table|mis]
+ *       [--environment map.hdr|map.pfm] [--environment-color r g b] [--env-light] [--env-sampling off|table|mis] [--aov PREFIX] [--denoise K]
  *
  * Environment: the scene's environment attribute is a constant (--environment-color, default 0.4 0.52 1) or a lat-long map (--environment: Radiance .hdr with flat
  * or new-style run-length-encoded scanlines, orientation -Y H +X W, texel = m 2^(e - 136); or .pfm, either byte order, bottom row first), bound as a 3-component
@@ -57,6 +57,10 @@ int         terra_amd_render_multi ( const TerraCamera*, HTerraScene, const Terr
 int         terra_amd_set_environment_lighting ( HTerraScene, int ) __attribute__ ( ( weak ) );
 int         terra_amd_set_environment_sampling ( HTerraScene, int ) __attribute__ ( ( weak ) );
 int         terra_amd_set_environment_mis ( HTerraScene, int ) __attribute__ ( ( weak ) );
+/* first-hit AOV sums (TerraAmdAovResult of terra_amd.h, restated: this file also builds against the reference's headers) and the denoiser */
+typedef struct { float albedo[3]; float coverage; float normal[3]; float depth; int samples; int reserved[3]; } AovSum;
+int         terra_amd_render_aov ( const TerraCamera*, HTerraScene, void*, size_t, size_t, size_t, size_t, size_t, size_t ) __attribute__ ( ( weak ) );
+int         terra_amd_denoise ( HTerraScene, const TerraFramebuffer*, const void*, size_t, size_t, size_t, size_t, int, TerraFloat3*, TerraFloat3* ) __attribute__ ( ( weak ) );
 
 /* ---- growable arrays ------------------------------------------------------------------------ */
 #define VEC(T) struct { T* d; size_t n, cap; }
@@ -377,6 +381,21 @@ static int write_pfm ( const char* path, const TerraFramebuffer* fb ) {
     for ( size_t y = fb->height; y-- > 0; ) fwrite ( &fb->pixels[y * fb->width], sizeof ( TerraFloat3 ), fb->width, f );   /* bottom row first */
     return fclose ( f ) == 0;
 }
+/* the means over hits of one AOV (k: 0 albedo, 1 normal, 2 depth) as a PFM; pixels no sample hit are 0 */
+static int write_aov_pfm ( const char* path, const AovSum* a, size_t W, size_t H, int k ) {
+    TerraFramebuffer img; img.width = W; img.height = H; img.results = NULL;
+    img.pixels = malloc ( W * H * sizeof ( TerraFloat3 ) );
+    if ( !img.pixels ) return 0;
+    for ( size_t i = 0; i < W * H; ++i ) {
+        const float c = a[i].coverage;
+        float v[3] = { 0.f, 0.f, 0.f };
+        if ( c > 0.f ) for ( int ch = 0; ch < 3; ++ch ) v[ch] = ( k == 0 ? a[i].albedo[ch] : k == 1 ? a[i].normal[ch] : a[i].depth ) / c;
+        img.pixels[i] = terra_f3_set ( v[0], v[1], v[2] );
+    }
+    const int ok = write_pfm ( path, &img );
+    free ( img.pixels );
+    return ok;
+}
 static int write_hdr ( const char* path, const TerraFramebuffer* fb ) {       /* Radiance RGBE, flat scanlines */
     FILE* f = fopen ( path, "wb" ); if ( !f ) return 0;
     fprintf ( f, "#?RADIANCE\nFORMAT=32-bit_rle_rgbe\n\n-Y %zu +X %zu\n", fb->height, fb->width );
@@ -525,6 +544,9 @@ static const char* kHelp =
     "  --env-light (libterra_amd.so only): rays that leave the scene add the environment (terra_amd_set_environment_lighting; the reference drops it)\n"
     "  --env-sampling off|table|mis (libterra_amd.so only, with a map and --env-light): table = Direct / Direct + MIS sample the map through a TerraDistribution2D\n"
     "           (terra_amd_set_environment_sampling); mis = that, weighted against Direct + MIS's BSDF ray by the power heuristic (terra_amd_set_environment_mis)\n"
+    "  --aov PREFIX (libterra_amd.so only): also runs the first-hit AOV pass with the same calls as the render (terra_amd_render_aov) and writes the means over hits\n"
+    "           PREFIX.albedo.pfm, PREFIX.normal.pfm, PREFIX.depth.pfm\n"
+    "  --denoise K (libterra_amd.so only): writes the image denoised by K (0 .. 8) a-trous iterations guided by the AOVs (terra_amd_denoise) instead of the plain one\n"
     "OBJ/MTL import (--normals apollo, the default): the policy of the reference client's importer (satellite/include/Apollo.h under the\n"
     "options of satellite/src/Scene.cpp:83-93) RESTATED in this tool and pinned by hand-derived fixtures -- restated, not executed: Apollo.h\n"
     "does not compile with this image's toolchains. Everything after the TerraObject fill (commit, render, export) is the pinned path.\n";
@@ -535,6 +557,7 @@ int main ( int argc, char** argv ) {
     if ( terra_amd_init ) ( void ) terra_amd_init();      /* before anything touches the GPU (libterra_amd.so only) */
     size_t W = 800, H = 600, spp = 8, bounces = 4, tile = 0;     /* defaults of satellite/include/Config.hpp:19-113 */
     int integrator = kTerraIntegratorDirect, tonemap = kTerraTonemappingOperatorLinear, flip = 1, fast = -1, have_seed = 0, split = -1, apollo = 1, gpus = 0;
+    const char* aov_prefix = NULL; int denoise = -1;
     const char* dump_path = NULL; int no_render = 0;
     float fov = 45.f, exposure = 1.f, gamma = 2.2f, jitter = 0.f;
     unsigned long long seed = 0;
@@ -567,6 +590,8 @@ int main ( int argc, char** argv ) {
         else if ( !strcmp ( a, "--environment" ) ) env_path = NEXT();
         else if ( !strcmp ( a, "--environment-color" ) && i + 3 < argc ) { for ( int k = 0; k < 3; ++k ) env_rgb[k] = ( float ) atof ( argv[i + 1 + k] ); i += 3; }
         else if ( !strcmp ( a, "--env-light" ) ) env_light = 1;
+        else if ( !strcmp ( a, "--aov" ) ) aov_prefix = NEXT();
+        else if ( !strcmp ( a, "--denoise" ) ) { denoise = atoi ( NEXT() ); if ( denoise < 0 || denoise > 8 ) { fprintf ( stderr, "terra_headless: --denoise 0 .. 8\n" ); return 64; } }
         else if ( !strcmp ( a, "--env-sampling" ) ) { const char* v = NEXT(); static const char* const n[] = { "off", "table", "mis" }; env_sampling = pick ( v, n, 3, -1 ); if ( env_sampling < 0 ) { fprintf ( stderr, "terra_headless: --env-sampling off|table|mis\n" ); return 64; } }
         else if ( !strcmp ( a, "--camera" ) && i + 6 < argc ) {
             cam.position = terra_f3_set ( ( float ) atof ( argv[i + 1] ), ( float ) atof ( argv[i + 2] ), ( float ) atof ( argv[i + 3] ) );
@@ -621,13 +646,33 @@ int main ( int argc, char** argv ) {
         for ( int k = 0; k < gpus; ++k ) devs[k] = k;
         if ( terra_amd_set_devices ( devs, gpus ) != 0 ) { fprintf ( stderr, "terra_headless: %s\n", terra_amd_last_error ? terra_amd_last_error() : "terra_amd_set_devices failed" ); return 69; }
     }
+    AovSum* aov = NULL;          /* --aov / --denoise: the AOV sums, made by the same calls as the render */
+    if ( aov_prefix || denoise >= 0 ) {
+        if ( !terra_amd_render_aov || !terra_amd_denoise ) { fprintf ( stderr, "terra_headless: --aov / --denoise need libterra_amd.so; ignored, the plain image is written\n" ); aov_prefix = NULL; denoise = -1; }
+        else if ( gpus > 0 ) { fprintf ( stderr, "terra_headless: --aov / --denoise do not mirror --gpus (the sharded render); ignored\n" ); aov_prefix = NULL; denoise = -1; }
+        else if ( !( aov = calloc ( W * H, sizeof ( AovSum ) ) ) ) { fprintf ( stderr, "terra_headless: out of memory\n" ); return 71; }
+    }
     terra_scene_commit ( scene );
     TerraFramebuffer fb;
     if ( !terra_framebuffer_create ( &fb, W, H ) ) { fprintf ( stderr, "terra_headless: bad framebuffer size\n" ); return 65; }
     if ( gpus > 0 ) ( void ) terra_amd_render_multi ( &cam, scene, &fb, 0, 0, W, H, tile );      /* (tile = the shard's tile size here; 0 = 64) */
-    else if ( tile == 0 ) terra_render ( &cam, scene, &fb, 0, 0, W, H );
-    else for ( size_t y = 0; y < H; y += tile ) for ( size_t x = 0; x < W; x += tile ) terra_render ( &cam, scene, &fb, x, y, W - x < tile ? W - x : tile, H - y < tile ? H - y : tile );
+    else if ( tile == 0 ) { terra_render ( &cam, scene, &fb, 0, 0, W, H ); if ( aov ) ( void ) terra_amd_render_aov ( &cam, scene, aov, W, H, 0, 0, W, H ); }
+    else for ( size_t y = 0; y < H; y += tile ) for ( size_t x = 0; x < W; x += tile ) {
+        const size_t tw = W - x < tile ? W - x : tile, th = H - y < tile ? H - y : tile;
+        terra_render ( &cam, scene, &fb, x, y, tw, th );
+        if ( aov ) ( void ) terra_amd_render_aov ( &cam, scene, aov, W, H, x, y, tw, th );
+    }
     if ( terra_amd_last_error && *terra_amd_last_error() ) { fprintf ( stderr, "terra_headless: %s\n", terra_amd_last_error() ); return 70; }
+    if ( aov_prefix ) {
+        static const char* const kind[3] = { "albedo", "normal", "depth" };
+        for ( int k = 0; k < 3; ++k ) {
+            char path[4096];
+            snprintf ( path, sizeof path, "%s.%s.pfm", aov_prefix, kind[k] );
+            if ( !write_aov_pfm ( path, aov, W, H, k ) ) { fprintf ( stderr, "terra_headless: cannot write %s\n", path ); return 73; }
+        }
+    }
+    if ( denoise >= 0 && terra_amd_denoise ( scene, &fb, aov, 0, 0, W, H, denoise, NULL, fb.pixels ) != 0 ) { fprintf ( stderr, "terra_headless: %s\n", terra_amd_last_error ? terra_amd_last_error() : "denoise failed" ); return 70; }
+    free ( aov );
     if ( !write_image ( argv[2], &fb ) ) { fprintf ( stderr, "terra_headless: cannot write %s\n", argv[2] ); return 73; }
     printf ( "%s: %zu triangles, %zu materials -> %s (%zux%zu, %zu spp)\n", argv[1], m.faces.n, m.mtls.n, argv[2], W, H, spp );
     terra_framebuffer_destroy ( &fb );

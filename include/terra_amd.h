@@ -308,6 +308,61 @@ int terra_amd_render_device ( const TerraCamera* camera, HTerraScene scene,
                               size_t x, size_t y, size_t width, size_t height,
                               void* d_rand_calls, void* stream );
 
+/* ---- AOV buffers (first-hit albedo, normal, depth, coverage) -----------------------------------------------------------------------------------
+   Running sums per pixel, like the framebuffer's results: clear the buffer (all zero) together with the framebuffer and make one AOV call per render call, with the
+   same rectangle and the same scene state. Then sample n of a pixel in the AOV buffer traces exactly the camera ray sample n of that pixel traces in terra_render() /
+   terra_amd_render_device(): its streams are keyed (pixel, samples + chunk * chunk_spp) with the AOV buffer's own sample count, it draws r1, r2 from stream A (and the
+   sampler integration's pair where that is on), the call is cut into the render call's sample split, and the traversal is the one the render call takes. Chunk sums
+   are added in chunk order, each summed from zero in sample order: the same bits run after run. Only the camera ray is traced: nothing is shaded, no light is sampled.
+   "Base colour" is the preset's attribute at the first hit, textured where the material is: TERRA_DIFFUSE_ALBEDO, TERRA_PHONG_ALBEDO, TERRA_GGX_F0, TERRA_GLASS_TINT.
+   A call records nothing in terra_amd_get_stats() and does not touch the framebuffer. It fails like a render call (kTerraAmdErrNotCommitted, a bad rectangle, a null
+   buffer, a launch error: terra_amd_last_error()). A scene committed for several devices runs the AOV pass on the primary device (terra_render() calls it shards over
+   the device set are not mirrored). */
+typedef struct {            /* 48 bytes = three 16-byte words */
+    float albedo[3];        /* +0   sum over samples that hit: the preset's base colour at the first hit */
+    float coverage;         /* +12  number of samples whose camera ray hit something */
+    float normal[3];        /* +16  sum over hits: the shading normal (interpolated, normalised, not face-forwarded) */
+    float depth;            /* +28  sum over hits: |hit point - camera position|, world units */
+    int   samples;          /* +32  camera samples taken */
+    int   reserved[3];      /* +36  zero */
+} TerraAmdAovResult;
+TERRA_ABI_ASSERT ( sizeof ( TerraAmdAovResult ) == 48 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdAovResult, coverage ) == 12 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdAovResult, normal ) == 16 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdAovResult, depth ) == 28 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdAovResult, samples ) == 32 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdAovResult, reserved ) == 36 );
+/* d_aov: TerraAmdAovResult per pixel of the frame (row-major, fb_width per row) in HBM; asynchronous on `stream`. Adds the scene's samples_per_pixel camera
+   samples to every pixel of the rectangle. */
+int terra_amd_render_aov_device ( const TerraCamera* camera, HTerraScene scene, void* d_aov, size_t fb_width, size_t fb_height,
+                                  size_t x, size_t y, size_t width, size_t height, void* stream );
+/* The same on a host buffer (frame-indexed): the rectangle is uploaded, the pass runs, the rectangle is downloaded; synchronous. */
+int terra_amd_render_aov ( const TerraCamera* camera, HTerraScene scene, TerraAmdAovResult* aov, size_t fb_width, size_t fb_height,
+                           size_t x, size_t y, size_t width, size_t height );
+
+/* ---- Denoiser: edge-avoiding a-trous wavelet filter (Dammertz et al., HPG 2010) on albedo-demodulated radiance ----------------------------------------------
+   Every buffer is indexed like the frame (y * fb_width + x); only pixels inside the rectangle are read or written. Per pixel p:
+     c_p = acc / samples (the resolve's division); p is VALID if samples > 0 and c_p is finite;
+     coverage > 0: a_p = albedo / coverage, z_p = depth / coverage, n_p = normal / coverage normalised (zero if its length <= 1e-6); coverage == 0: all three zero;
+     u_p = c_p / max(a_p, 0.01) per channel.
+   Iteration i = 0 .. K-1, step s = 2^i:  u'_p = sum W(p,q) u_q / sum W(p,q)  over q = p + s (dx, dy), dx, dy in -2 .. 2, q inside the rectangle and valid;
+     W = h(dx) h(dy) w_c w_n w_z, h = (1/16, 1/4, 3/8, 1/4, 1/16);
+     w_c = exp(-|u_p - u_q|^2 / (sigma_c^2 4^-i (l(u_p)^2 + l(u_q)^2) + 1e-8)), sigma_c = 0.5, l = (0.2126, 0.7152, 0.0722) . u;
+     w_n = 1 if both normals are zero, 0 if exactly one is, else max(0, n_p . n_q)^128 (seven squarings);
+     w_z = exp(-|z_p - z_q| / (sigma_z s max(z_p, z_q) + 1e-6)), sigma_z = 0.05.
+     A pixel with samples > 0 and a non-finite mean gets, in iteration 0, the weighted mean of its valid neighbours with w_c = 1, and is valid from then on if that
+     weight sum is positive.
+   Output: valid pixels radiance = u_K * max(a, 0.01), pixels = the scene's tonemap of radiance * exposure (terra_render's operator and gamma); other pixels 0 and
+   tonemap(0). iterations == 0 is the identity: radiance = c_p, pixels = the framebuffer's pixels bit for bit (pixels without samples: 0, tonemap(0)).
+   iterations must be 0 .. 8 (kTerraAmdErrBadArgument otherwise). d_radiance / d_pixels: float3 per pixel, either may be NULL; d_pixels may be the framebuffer's own
+   d_pixels (the filter reads the results, never the pixels). No atomics: the same inputs give the same bits. The scene gives exposure, operator and gamma (its
+   committed options) and the device (its primary one). */
+int terra_amd_denoise_device ( HTerraScene scene, const void* d_results, const void* d_aov, size_t fb_width, size_t fb_height,
+                               size_t x, size_t y, size_t width, size_t height, int iterations, void* d_radiance, void* d_pixels, void* stream );
+/* The same on host buffers: framebuffer->results and aov are read, radiance / pixels (frame-indexed, either may be NULL) written for the rectangle; synchronous. */
+int terra_amd_denoise ( HTerraScene scene, const TerraFramebuffer* framebuffer, const TerraAmdAovResult* aov, size_t x, size_t y, size_t width, size_t height,
+                        int iterations, TerraFloat3* radiance, TerraFloat3* pixels );
+
 /* Tile-sharded form for one-process-per-GPU rendering (the reference shards
    the same way over CPU threads: satellite/src/Renderer.cpp:316-350): the
    rectangle is cut into tile_size x tile_size tiles numbered row-major and this

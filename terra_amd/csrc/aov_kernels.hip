@@ -1,0 +1,250 @@
+// aov_kernels.hip -- first-hit AOV buffers and the edge-avoiding a-trous denoiser (include/terra_amd.h "AOV buffers", "Denoiser"; DESIGN.md
+// "AOV buffers and the denoiser").
+//
+// AOV pass: one camera ray per sample, nothing shaded. Sample n of a pixel traces exactly the camera ray sample n of the same pixel traces in the render:
+// the same stream keys (pixel, samples already in the AOV pixel + chunk * chunk_spp), the same draws (r1, r2 from stream A, then the sampler integration's
+// pair), the same sample split (scene_host.cpp launch_split) and the traversal the render call would take (fill_params). A 256-thread block holds 256 / split
+// pixels x split chunks; the chunk sums meet in LDS and the chunk-0 lane of each pixel adds them to the buffer in chunk order -- what terra_resolve_kernel does.
+// The grid is capped and strides over the blocks (the fast tree's stack spill is sized for the grid, not the frame).
+//
+// Denoiser: a prepass packs the guides, K step kernels ping-pong the demodulated radiance, a final kernel remodulates and tonemaps. One lane per pixel,
+// 16x16 blocks, every buffer of the filter indexed over the rectangle. No atomics: the same inputs give the same bits.
+#include <hip/hip_runtime.h>
+#include "trace_device.h"
+#include "kernels.h"
+
+struct DevAov { float albedo[3]; float coverage; float normal[3]; float depth; int samples; int reserved[3]; };      // TerraAmdAovResult
+static_assert ( sizeof ( DevAov ) == 48, "DevAov must be 48 bytes" );
+
+// ---- AOV pass ----------------------------------------------------------------------------------------------------------
+#define TERRA_AOV_FOLD_BYTES ( 2 * 256 * 16 )       // the block's chunk sums: two float4 per lane
+#define TERRA_AOV_MAX_BLOCKS_PER_CU 8
+
+template <int MODE>
+__global__ __launch_bounds__ ( 256 ) void terra_aov_kernel ( DevRenderParams p, float4* aov, uint32_t* spill, uint32_t vblocks, uint32_t blocks_x ) {
+    extern __shared__ float4 lds_f4[];
+    const uint32_t tid = threadIdx.x;
+    float4* fold = lds_f4;
+    int* words = reinterpret_cast<int*> ( lds_f4 + 512 );
+    Tracer T;
+    T.sc = p.scene; T.l_nodes = nullptr; T.l_tris = nullptr; T.l_props = nullptr; T.l_ranked = nullptr;
+    T.l_mats = p.scene.mats; T.l_lights = p.scene.lights; T.l_area = p.scene.tri_area;
+    T.lds_nodes = 0; T.lds_tris = 0; T.ranked = false;
+    T.stack = words + tid; T.leaves = words + p.stack_depth * TERRA_COL + tid; T.leaf_cap = ( int ) p.leaf_cap; T.stack_cap = ( int ) p.stack_depth;
+    T.stack_lim = ( uint32_t ) ( uintptr_t ) words + p.stack_depth * 1024u;
+    T.spill = spill ? spill + ( size_t ) ( blockIdx.x * 256u + tid ) * p.spill_cap : nullptr; T.spill_cap = spill ? p.spill_cap : 0u;
+    T.faults = nullptr; T.cull = p.leaf_cull != 0; T.fused = false;
+    const V3 cam_pos = v3 ( p.cam_pos[0], p.cam_pos[1], p.cam_pos[2] );
+    const uint32_t ppb_log2 = 8u - p.split_log2, ppb = 1u << ppb_log2;          // pixels per block
+    const uint32_t chunk = tid >> ppb_log2, k = tid & ( ppb - 1u );
+    for ( uint32_t vb = blockIdx.x; vb < vblocks; vb += gridDim.x ) {
+        // virtual block vb = part (vb mod split) of 16x16 pixel block vb / split of the rectangle; a wave covers an 8x8 packet as in the render (block_pixel)
+        const uint32_t blk = vb >> p.split_log2, r = ( ( vb & ( p.split - 1u ) ) << ppb_log2 ) + k;
+        const uint32_t by = blk / blocks_x, bx = blk - by * blocks_x;
+        const uint32_t wave = r >> 6, lane = r & 63u;
+        const uint32_t lx = bx * 16u + ( wave & 1u ) * 8u + ( lane & 7u ), ly = by * 16u + ( wave >> 1 ) * 8u + ( lane >> 3 );
+        const bool inside = lx < p.w && ly < p.h;
+        const uint32_t px = p.x + lx, py = p.y + ly;
+        const size_t pix = inside ? ( size_t ) ( py - p.st_y ) * p.st_pitch + ( px - p.st_x ) : 0;
+        float4 s0 = make_float4 ( 0.f, 0.f, 0.f, 0.f ), s1 = make_float4 ( 0.f, 0.f, 0.f, 0.f );
+        if ( inside ) {
+            const int prior = __float_as_int ( aov[3 * pix + 2].x );
+            const uint32_t base = ( uint32_t ) prior + chunk * p.chunk_spp;     // (job_next: j.base)
+            PixelStreams rs = trng_pixel_streams ( p.frame_seed, ( uint64_t ) py * p.fb_w + px, ( uint64_t ) ( uint32_t ) prior + ( uint64_t ) chunk * p.chunk_spp );
+            for ( uint32_t s = 0; s < p.chunk_spp; ++s ) {
+                const float r1 = trng_a_float ( rs.a ), r2 = trng_a_float ( rs.a );
+                const V3 rd = camera_sample ( p, px, py, r1, r2 );
+                if ( p.sampler_mode ) ( void ) sampler_pair_draw ( p.sampler_mode, p.sampler_strata, ( uint64_t ) base + s, rs.a );      // (its stratified offsets are stream-A draws)
+                Surface sf;
+                Counters c = counters_zero();
+                const RaycastResult h = scene_raycast<0, MODE, TERRA_KINDS_ALL> ( T, make_ray ( cam_pos, rd ), sf, c );
+                if ( h.hit ) {
+                    const V3 a = sf.bsdf == kDevBsdfPhong ? sf.attr[1] : sf.attr[0];     // TERRA_PHONG_ALBEDO; TERRA_DIFFUSE_ALBEDO, TERRA_GGX_F0, TERRA_GLASS_TINT are slot 0
+                    s0.x = s0.x + a.x; s0.y = s0.y + a.y; s0.z = s0.z + a.z; s0.w = s0.w + 1.f;
+                    s1.x = s1.x + sf.normal.x; s1.y = s1.y + sf.normal.y; s1.z = s1.z + sf.normal.z;
+                    s1.w = s1.w + length ( cam_pos - h.point );                                 // (the DebugDepth integrator's distance, before its / 500)
+                }
+            }
+        }
+        fold[tid] = s0; fold[256 + tid] = s1;
+        __syncthreads();
+        if ( chunk == 0 && inside ) {
+            float4 o0 = aov[3 * pix], o1 = aov[3 * pix + 1], o2 = aov[3 * pix + 2];
+            for ( uint32_t j = 0; j < p.split; ++j ) {
+                const float4 q0 = fold[j * ppb + k], q1 = fold[256 + j * ppb + k];
+                o0.x = o0.x + q0.x; o0.y = o0.y + q0.y; o0.z = o0.z + q0.z; o0.w = o0.w + q0.w;
+                o1.x = o1.x + q1.x; o1.y = o1.y + q1.y; o1.z = o1.z + q1.z; o1.w = o1.w + q1.w;
+            }
+            o2.x = __int_as_float ( __float_as_int ( o2.x ) + ( int ) p.spp );
+            aov[3 * pix] = o0; aov[3 * pix + 1] = o1; aov[3 * pix + 2] = o2;
+        }
+        __syncthreads();
+    }
+}
+
+hipError_t terra_launch_aov ( DevRenderParams p, void* aov, hipStream_t stream ) {
+    const uint32_t blocks_x = ( p.w + 15u ) / 16u, blocks_y = ( p.h + 15u ) / 16u;
+    const uint64_t vblocks = ( uint64_t ) blocks_x * blocks_y * p.split;
+    if ( vblocks == 0 ) return hipSuccess;
+    if ( vblocks >= ( 1ull << 32 ) || p.split > 256u || ( 1u << p.split_log2 ) != p.split ) return hipErrorInvalidValue;
+    int dev = 0, cus = 0; ( void ) hipGetDevice ( &dev );
+    if ( hipDeviceGetAttribute ( &cus, hipDeviceAttributeMultiprocessorCount, dev ) != hipSuccess || cus < 1 ) { ( void ) hipGetLastError(); cus = 256; }
+    const uint32_t grid = ( uint32_t ) ( vblocks < ( uint64_t ) cus * TERRA_AOV_MAX_BLOCKS_PER_CU ? vblocks : ( uint64_t ) cus * TERRA_AOV_MAX_BLOCKS_PER_CU );
+    // the traversal the render call takes (fill_params): the fast tree (MODE 2, or 3 with the reachability replay) or the reference tree read from global memory --
+    // an LDS-resident scene's reference tree with the leaf-box cull answers with the same closest hit whether it is staged or not, so nothing is staged here
+    int mode = 0;
+    if ( p.lds_mode == 2 ) { mode = p.scene.reach ? 3 : 2; }
+    else {
+        p.stack_depth = p.scene.max_stack < 1 ? 1u : ( uint32_t ) p.scene.max_stack;
+        p.leaf_cap = TERRA_LEAF_CAP_MAX; p.spill_cap = 0;
+        while ( p.leaf_cap > 4 && ( size_t ) ( p.stack_depth + p.leaf_cap ) * 1024 + TERRA_AOV_FOLD_BYTES > ( size_t ) 64 * 1024 ) --p.leaf_cap;
+    }
+    const size_t lds = ( size_t ) ( p.stack_depth + ( mode == 0 ? p.leaf_cap : 0u ) ) * 1024 + TERRA_AOV_FOLD_BYTES;
+    if ( lds > terra_lds_block_limit() ) return hipErrorInvalidValue;
+    const void* fn = mode == 0 ? reinterpret_cast<const void*> ( terra_aov_kernel<0> ) : mode == 2 ? reinterpret_cast<const void*> ( terra_aov_kernel<2> ) : reinterpret_cast<const void*> ( terra_aov_kernel<3> );
+    if ( lds > ( size_t ) 64 * 1024 ) { const hipError_t e = hipFuncSetAttribute ( fn, hipFuncAttributeMaxDynamicSharedMemorySize, ( int ) lds ); if ( e != hipSuccess ) return e; }
+    uint32_t* spill = nullptr;
+    const size_t spill_bytes = mode != 0 && p.spill_cap ? ( size_t ) grid * 256 * p.spill_cap * sizeof ( uint32_t ) : 0;
+    if ( spill_bytes ) { const hipError_t e = hipMallocAsync ( ( void** ) &spill, spill_bytes, stream ); if ( e != hipSuccess ) return e; }
+    float4* out = reinterpret_cast<float4*> ( aov );
+    if ( mode == 0 ) hipLaunchKernelGGL ( terra_aov_kernel<0>, dim3 ( grid ), dim3 ( 256 ), lds, stream, p, out, spill, ( uint32_t ) vblocks, blocks_x );
+    else if ( mode == 2 ) hipLaunchKernelGGL ( terra_aov_kernel<2>, dim3 ( grid ), dim3 ( 256 ), lds, stream, p, out, spill, ( uint32_t ) vblocks, blocks_x );
+    else hipLaunchKernelGGL ( terra_aov_kernel<3>, dim3 ( grid ), dim3 ( 256 ), lds, stream, p, out, spill, ( uint32_t ) vblocks, blocks_x );
+    const hipError_t e = hipGetLastError();
+    if ( spill ) ( void ) hipFreeAsync ( spill, stream );
+    return e;
+}
+
+// ---- denoiser -----------------------------------------------------------------------------------------------------------
+// Constants of the filter (include/terra_amd.h, tests/test_denoise.py restates them)
+#define TERRA_DN_SIGMA_C2 0.25f         // sigma_c^2 (sigma_c = 0.5: DESIGN.md "AOV buffers and the denoiser", measured against 1)
+#define TERRA_DN_SIGMA_Z  0.05f
+#define TERRA_DN_ALBEDO_MIN 0.01f
+#define TERRA_DN_NORMAL_MIN 1e-6f
+#define TERRA_DN_EPS_C 1e-8f
+#define TERRA_DN_EPS_Z 1e-6f
+// guide state (g1.w): 0 no samples, 1 valid, 2 samples but a non-finite mean (filled from its neighbours in iteration 0)
+
+TD float dn_max ( float a, float b ) { return a > b ? a : b; }
+TD bool dn_finite ( float v ) { return ( __float_as_uint ( v ) & 0x7f800000u ) != 0x7f800000u; }
+
+__global__ __launch_bounds__ ( 256 ) void terra_denoise_prepass ( const float4* results, const float4* aov, uint32_t fb_w, uint32_t x, uint32_t y, uint32_t w, uint32_t h,
+                                                                  float4* g0, float4* g1, float4* u ) {
+    const uint32_t lx = blockIdx.x * 16u + threadIdx.x, ly = blockIdx.y * 16u + threadIdx.y;
+    if ( lx >= w || ly >= h ) return;
+    const size_t pix = ( size_t ) ( y + ly ) * fb_w + ( x + lx ), i = ( size_t ) ly * w + lx;
+    const float4 res = results[pix];
+    const int samples = __float_as_int ( res.w );
+    const float n = ( float ) samples;
+    const V3 c = v3 ( res.x / n, res.y / n, res.z / n );
+    const bool finite = samples > 0 && dn_finite ( c.x ) && dn_finite ( c.y ) && dn_finite ( c.z );
+    const float4 a0 = aov[3 * pix], a1 = aov[3 * pix + 1];
+    V3 a = v3 ( 0.f, 0.f, 0.f ), nv = v3 ( 0.f, 0.f, 0.f );
+    float z = 0.f;
+    if ( a0.w > 0.f ) {
+        a = v3 ( a0.x / a0.w, a0.y / a0.w, a0.z / a0.w );
+        z = a1.w / a0.w;
+        nv = v3 ( a1.x / a0.w, a1.y / a0.w, a1.z / a0.w );
+        const float len = length ( nv );
+        nv = len > TERRA_DN_NORMAL_MIN ? v3 ( nv.x / len, nv.y / len, nv.z / len ) : v3 ( 0.f, 0.f, 0.f );
+    }
+    g0[i] = make_float4 ( nv.x, nv.y, nv.z, z );
+    g1[i] = make_float4 ( a.x, a.y, a.z, finite ? 1.f : ( samples > 0 ? 2.f : 0.f ) );
+    u[i] = finite ? make_float4 ( c.x / dn_max ( a.x, TERRA_DN_ALBEDO_MIN ), c.y / dn_max ( a.y, TERRA_DN_ALBEDO_MIN ), c.z / dn_max ( a.z, TERRA_DN_ALBEDO_MIN ), 1.f )
+                  : make_float4 ( 0.f, 0.f, 0.f, 0.f );
+}
+
+// iteration `it` (step 2^it): u.w = 1 marks a valid pixel of the input / output
+__global__ __launch_bounds__ ( 256 ) void terra_denoise_step ( const float4* g0, const float4* g1, const float4* uin, float4* uout, uint32_t w, uint32_t h, int it ) {
+    const uint32_t lx = blockIdx.x * 16u + threadIdx.x, ly = blockIdx.y * 16u + threadIdx.y;
+    if ( lx >= w || ly >= h ) return;
+    const size_t i = ( size_t ) ly * w + lx;
+    const float4 up = uin[i];
+    const bool pending = it == 0 && g1[i].w == 2.f;
+    if ( up.w == 0.f && !pending ) { uout[i] = make_float4 ( 0.f, 0.f, 0.f, 0.f ); return; }
+    const float kh[5] = { 1.f / 16.f, 1.f / 4.f, 3.f / 8.f, 1.f / 4.f, 1.f / 16.f };
+    const int step = 1 << it;
+    const float sigma_c2 = TERRA_DN_SIGMA_C2 * ldexpf ( 1.f, -2 * it ), zs = TERRA_DN_SIGMA_Z * ( float ) step;
+    const float4 gp = g0[i];
+    const bool np_zero = gp.x == 0.f && gp.y == 0.f && gp.z == 0.f;
+    const float lp = 0.2126f * up.x + 0.7152f * up.y + 0.0722f * up.z;
+    float sw = 0.f, sx = 0.f, sy = 0.f, sz = 0.f;
+    for ( int dy = -2; dy <= 2; ++dy ) {
+        const int qy = ( int ) ly + step * dy;
+        if ( qy < 0 || qy >= ( int ) h ) continue;
+        for ( int dx = -2; dx <= 2; ++dx ) {
+            const int qx = ( int ) lx + step * dx;
+            if ( qx < 0 || qx >= ( int ) w ) continue;
+            const size_t q = ( size_t ) qy * w + qx;
+            const float4 uq = uin[q];
+            if ( uq.w == 0.f ) continue;
+            const float4 gq = g0[q];
+            float wc = 1.f;
+            if ( !pending ) {
+                const float lq = 0.2126f * uq.x + 0.7152f * uq.y + 0.0722f * uq.z;
+                const float ex = up.x - uq.x, ey = up.y - uq.y, ez = up.z - uq.z;
+                wc = expf ( -( ( ex * ex + ey * ey + ez * ez ) / ( sigma_c2 * ( lp * lp + lq * lq ) + TERRA_DN_EPS_C ) ) );
+            }
+            const bool nq_zero = gq.x == 0.f && gq.y == 0.f && gq.z == 0.f;
+            float wn;
+            if ( np_zero || nq_zero ) wn = ( np_zero && nq_zero ) ? 1.f : 0.f;
+            else {
+                wn = dn_max ( 0.f, gp.x * gq.x + gp.y * gq.y + gp.z * gq.z );
+                #pragma unroll
+                for ( int k = 0; k < 7; ++k ) wn = wn * wn;          // ^128
+            }
+            const float wz = expf ( -( fabsf ( gp.w - gq.w ) / ( zs * dn_max ( gp.w, gq.w ) + TERRA_DN_EPS_Z ) ) );
+            const float W = ( ( ( kh[dx + 2] * kh[dy + 2] ) * wc ) * wn ) * wz;
+            sw = sw + W; sx = sx + W * uq.x; sy = sy + W * uq.y; sz = sz + W * uq.z;
+        }
+    }
+    uout[i] = sw > 0.f ? make_float4 ( sx / sw, sy / sw, sz / sw, 1.f ) : make_float4 ( 0.f, 0.f, 0.f, 0.f );
+}
+
+// remodulate and tonemap (iterations == 0: the framebuffer's own mean, as terra_resolve_kernel computes it)
+__global__ __launch_bounds__ ( 256 ) void terra_denoise_finish ( const float4* results, const float4* g1, const float4* u, uint32_t fb_w, uint32_t x, uint32_t y, uint32_t w, uint32_t h,
+                                                                 int iterations, float exposure, int op, float gamma, float* radiance, float* pixels ) {
+    const uint32_t lx = blockIdx.x * 16u + threadIdx.x, ly = blockIdx.y * 16u + threadIdx.y;
+    if ( lx >= w || ly >= h ) return;
+    const size_t pix = ( size_t ) ( y + ly ) * fb_w + ( x + lx ), i = ( size_t ) ly * w + lx;
+    V3 rad = v3 ( 0.f, 0.f, 0.f );
+    if ( iterations == 0 ) {
+        const float4 res = results[pix];
+        const int samples = __float_as_int ( res.w );
+        const float n = ( float ) samples;
+        if ( samples > 0 ) rad = v3 ( res.x / n, res.y / n, res.z / n );
+    } else {
+        const float4 uq = u[i];
+        if ( uq.w != 0.f ) {
+            const float4 a = g1[i];
+            rad = v3 ( uq.x * dn_max ( a.x, TERRA_DN_ALBEDO_MIN ), uq.y * dn_max ( a.y, TERRA_DN_ALBEDO_MIN ), uq.z * dn_max ( a.z, TERRA_DN_ALBEDO_MIN ) );
+        }
+    }
+    if ( radiance ) { radiance[3 * pix] = rad.x; radiance[3 * pix + 1] = rad.y; radiance[3 * pix + 2] = rad.z; }
+    if ( pixels ) {
+        const V3 color = tonemap ( rad * exposure, op, gamma );
+        pixels[3 * pix] = color.x; pixels[3 * pix + 1] = color.y; pixels[3 * pix + 2] = color.z;
+    }
+}
+
+hipError_t terra_launch_denoise ( const void* results, const void* aov, uint32_t fb_w, uint32_t x, uint32_t y, uint32_t w, uint32_t h, int iterations,
+                                  float exposure, int op, float gamma, float* radiance, float* pixels, hipStream_t stream ) {
+    if ( w == 0 || h == 0 || ( !radiance && !pixels ) ) return hipSuccess;
+    const dim3 grid ( ( w + 15u ) / 16u, ( h + 15u ) / 16u ), block ( 16, 16 );
+    const float4* res = reinterpret_cast<const float4*> ( results );
+    float4* scratch = nullptr;
+    const size_t n = ( size_t ) w * h;
+    if ( iterations > 0 ) { const hipError_t e = hipMallocAsync ( ( void** ) &scratch, 4 * n * sizeof ( float4 ), stream ); if ( e != hipSuccess ) return e; }
+    float4* g0 = scratch; float4* g1 = scratch ? scratch + n : nullptr; float4* ua = scratch ? scratch + 2 * n : nullptr; float4* ub = scratch ? scratch + 3 * n : nullptr;
+    if ( iterations > 0 ) {
+        hipLaunchKernelGGL ( terra_denoise_prepass, grid, block, 0, stream, res, reinterpret_cast<const float4*> ( aov ), fb_w, x, y, w, h, g0, g1, ua );
+        for ( int it = 0; it < iterations; ++it ) {
+            hipLaunchKernelGGL ( terra_denoise_step, grid, block, 0, stream, g0, g1, ua, ub, w, h, it );
+            float4* t = ua; ua = ub; ub = t;
+        }
+    }
+    hipLaunchKernelGGL ( terra_denoise_finish, grid, block, 0, stream, res, g1, ua, fb_w, x, y, w, h, iterations, exposure, op, gamma, radiance, pixels );
+    const hipError_t e = hipGetLastError();
+    if ( scratch ) ( void ) hipFreeAsync ( scratch, stream );
+    return e;
+}

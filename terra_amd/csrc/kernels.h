@@ -26,6 +26,13 @@ void       terra_plan_fast_tree ( DevRenderParams& p );     // the plan of a fas
 hipError_t terra_launch_tiles ( bool pack, float* pixels, void* results, uint32_t fb_w, uint32_t x, uint32_t y, uint32_t w, uint32_t h,
                                 uint32_t tile, uint32_t rank, uint32_t world, float* packed, hipStream_t stream );
 
+// first-hit AOV pass and denoiser (aov_kernels.hip): p as fill_params made it, with the render's sample split set (split, split_log2, chunk_spp); aov = TerraAmdAovResult
+// per pixel, addressed like p.results (st_x / st_y / st_pitch)
+hipError_t terra_launch_aov ( DevRenderParams p, void* aov, hipStream_t stream );
+// results / aov / radiance / pixels indexed like a frame of fb_w pixels per row; only the rectangle is read or written; radiance or pixels may be nullptr
+hipError_t terra_launch_denoise ( const void* results, const void* aov, uint32_t fb_w, uint32_t x, uint32_t y, uint32_t w, uint32_t h, int iterations,
+                                  float exposure, int op, float gamma, float* radiance, float* pixels, hipStream_t stream );
+
 hipError_t terra_fill_sincos24 ( float2* table, hipStream_t stream );    // DevScene::sincos24: 2^24 entries (128 MB), device pointer
 
 // unit-level launchers: all pointers are DEVICE pointers, n items, synchronous semantics left to the caller

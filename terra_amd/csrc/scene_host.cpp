@@ -1429,14 +1429,20 @@ static uint32_t auto_sample_split ( uint32_t blocks, uint32_t spp, bool ordered 
     while ( split < 32 && ( uint64_t ) blocks * split < enough && spp / ( split * 2 ) >= 16 ) split *= 2;
     return split;
 }
-static int launch_render ( Scene* s, DevRenderParams& p, int device, hipStream_t stream, ThreadSlot* slot = nullptr ) {      // device: the (current) device of the launch
+// The sample split of a launch of p with `blocks` pixel blocks per chunk: the scene's setting, or its automatic choice for the launch. The render and the AOV pass
+// (terra_amd_render_aov_device) both take it from here, so that their samples are cut into the same chunks. Sets p.job_blocks = blocks.
+static uint32_t launch_split ( const Scene* s, DevRenderParams& p, uint32_t blocks ) {
     uint32_t split = s->sample_split;
-    const uint32_t blocks = terra_render_blocks ( p );
-    if ( blocks == 0 ) return 0;
     p.job_blocks = blocks;                                            // (what terra_block_order_bytes looks at is the launch's size and layout, not the split)
     if ( split == 0 ) split = auto_sample_split ( blocks, p.spp, s->job_order && terra_block_order_bytes ( p, s->job_order == 2 ) != 0 );
     while ( split > 1 && p.spp % split ) split >>= 1;              // chunks must be equal: fall back to the largest power of two dividing spp
     if ( split < 1 ) split = 1;
+    return split;
+}
+static int launch_render ( Scene* s, DevRenderParams& p, int device, hipStream_t stream, ThreadSlot* slot = nullptr ) {      // device: the (current) device of the launch
+    const uint32_t blocks = terra_render_blocks ( p );
+    if ( blocks == 0 ) return 0;
+    const uint32_t split = launch_split ( s, p, blocks );
     static thread_local uint64_t pool_kept = 0;          // (bit d: done for device d)
     if ( device < 64 && ! ( pool_kept >> device & 1ull ) ) {        // keep freed scratch cached in the device's default pool instead of returning it to the OS at every sync
         hipMemPool_t pool;
@@ -1533,6 +1539,89 @@ extern "C" int terra_amd_time_render_device ( const TerraCamera* cam, HTerraScen
     HIP_TRY ( hipEventElapsedTime ( &ms, e0, e1 ), kTerraAmdErrLaunch );
     ( void ) hipEventDestroy ( e0 ); ( void ) hipEventDestroy ( e1 );
     *ms_avg = ms / ( float ) launches;
+    return 0;
+}
+
+// ---- AOV pass and denoiser (aov_kernels.hip) ----------------------------------------
+static_assert ( sizeof ( TerraAmdAovResult ) == 48, "TerraAmdAovResult must be 48 bytes" );
+// p: the launch fill_params made for the render call this AOV call mirrors; the split is the one that call takes (launch_split), and the samples the AOV buffer
+// already holds key the streams as the framebuffer's do. Runs on the current device (the scene's primary one).
+static int launch_aov ( Scene* s, DevRenderParams& p, void* d_aov, hipStream_t stream ) {
+    const uint32_t blocks = terra_render_blocks ( p );
+    if ( blocks == 0 ) return 0;
+    const uint32_t split = launch_split ( s, p, blocks );
+    p.split = split; p.split_log2 = 0; while ( ( 1u << p.split_log2 ) < split ) ++p.split_log2;
+    p.chunk_spp = p.spp / split; p.job_blocks = blocks * split; p.job_queue = nullptr; p.job_streams = nullptr; p.block_order = nullptr; p.partials = nullptr;
+    p.pixels = nullptr; p.results = nullptr; p.rand_calls = nullptr; p.counters = nullptr; p.count_level = 0;
+    const hipError_t e = terra_launch_aov ( p, d_aov, stream );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "AOV launch: %s", hipGetErrorString ( e ) );
+    return 0;
+}
+extern "C" int terra_amd_render_aov_device ( const TerraCamera* cam, HTerraScene h, void* d_aov, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t hgt, void* stream ) {
+    Scene* s = S ( h );
+    const Scene::Replica& r = primary ( s );
+    DevRenderParams p;
+    if ( int rc = fill_params ( s, r, cam, fb_w, fb_h, x, y, w, hgt, 64, 0, 1, p ) ) return rc;
+    if ( !d_aov ) return fail ( kTerraAmdErrBadArgument, "null AOV buffer" );
+    HIP_TRY ( hipSetDevice ( r.device ), kTerraAmdErrNoDevice );
+    return launch_aov ( s, p, d_aov, ( hipStream_t ) stream );
+}
+extern "C" int terra_amd_render_aov ( const TerraCamera* cam, HTerraScene h, TerraAmdAovResult* aov, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t hgt ) {
+    Scene* s = S ( h );
+    const Scene::Replica& r = primary ( s );
+    DevRenderParams p;
+    if ( int rc = fill_params ( s, r, cam, fb_w, fb_h, x, y, w, hgt, 64, 0, 1, p ) ) return rc;
+    if ( !aov ) return fail ( kTerraAmdErrBadArgument, "null AOV buffer" );
+    HIP_TRY ( hipSetDevice ( r.device ), kTerraAmdErrNoDevice );
+    p.st_x = ( uint32_t ) x; p.st_y = ( uint32_t ) y; p.st_pitch = ( uint32_t ) w;      // the rectangle only, rows of w pixels (as render_host stages it)
+    void* d = nullptr;
+    HIP_TRY ( hipMalloc ( &d, w * hgt * sizeof ( TerraAmdAovResult ) ), kTerraAmdErrNoDevice );
+    const size_t row = w * sizeof ( TerraAmdAovResult ), pitch = fb_w * sizeof ( TerraAmdAovResult );
+    TerraAmdAovResult* host = aov + y * fb_w + x;
+    hipError_t e = hipMemcpy2D ( d, row, host, pitch, row, hgt, hipMemcpyHostToDevice );
+    int rc = e == hipSuccess ? launch_aov ( s, p, d, nullptr ) : fail ( kTerraAmdErrLaunch, "AOV upload: %s", hipGetErrorString ( e ) );
+    if ( !rc ) { e = hipMemcpy2D ( host, pitch, d, row, row, hgt, hipMemcpyDeviceToHost ); if ( e != hipSuccess ) rc = fail ( kTerraAmdErrLaunch, "AOV download: %s", hipGetErrorString ( e ) ); }
+    ( void ) hipFree ( d );
+    return rc;
+}
+static int denoise_check ( Scene* s, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t h, int iterations ) {
+    if ( !s->committed ) return fail ( kTerraAmdErrNotCommitted, "terra_scene_commit has not run since the scene changed" );
+    if ( !s->device_ok ) return fail ( kTerraAmdErrNoDevice, "scene has no device replica: %s", s->commit_error.c_str() );
+    if ( w == 0 || h == 0 || x + w > fb_w || y + h > fb_h ) return fail ( kTerraAmdErrBadArgument, "bad denoise rectangle %zu,%zu %zux%zu in %zux%zu", x, y, w, h, fb_w, fb_h );
+    if ( iterations < 0 || iterations > 8 ) return fail ( kTerraAmdErrBadArgument, "denoise iterations %d: 0 ... 8", iterations );
+    return 0;
+}
+extern "C" int terra_amd_denoise_device ( HTerraScene h, const void* d_results, const void* d_aov, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t hgt, int iterations,
+                                          void* d_radiance, void* d_pixels, void* stream ) {
+    Scene* s = S ( h );
+    if ( int rc = denoise_check ( s, fb_w, fb_h, x, y, w, hgt, iterations ) ) return rc;
+    if ( !d_results || !d_aov ) return fail ( kTerraAmdErrBadArgument, "null framebuffer or AOV buffer" );
+    HIP_TRY ( hipSetDevice ( primary ( s ).device ), kTerraAmdErrNoDevice );
+    const hipError_t e = terra_launch_denoise ( d_results, d_aov, ( uint32_t ) fb_w, ( uint32_t ) x, ( uint32_t ) y, ( uint32_t ) w, ( uint32_t ) hgt, iterations, s->opts.manual_exposure,
+                                                ( int ) s->opts.tonemapping_operator, s->opts.gamma, ( float* ) d_radiance, ( float* ) d_pixels, ( hipStream_t ) stream );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "denoise launch: %s", hipGetErrorString ( e ) );
+    return 0;
+}
+extern "C" int terra_amd_denoise ( HTerraScene h, const TerraFramebuffer* fb, const TerraAmdAovResult* aov, size_t x, size_t y, size_t w, size_t hgt, int iterations,
+                                   TerraFloat3* radiance, TerraFloat3* pixels ) {
+    Scene* s = S ( h );
+    if ( !fb || !fb->results || !aov ) return fail ( kTerraAmdErrBadArgument, "null framebuffer or AOV buffer" );
+    if ( int rc = denoise_check ( s, fb->width, fb->height, x, y, w, hgt, iterations ) ) return rc;
+    if ( !radiance && !pixels ) return 0;
+    HIP_TRY ( hipSetDevice ( primary ( s ).device ), kTerraAmdErrNoDevice );
+    // the rectangle only, as a frame of w x hgt (the filter does not depend on where the rectangle lies)
+    const size_t n = w * hgt;
+    char* d = nullptr;
+    HIP_TRY ( hipMalloc ( ( void** ) &d, n * ( 16 + 48 + 12 + 12 ) ), kTerraAmdErrNoDevice );
+    char* d_res = d; char* d_aov = d + n * 16; float* d_rad = ( float* ) ( d + n * 64 ); float* d_pix = ( float* ) ( d + n * 76 );
+    hipError_t e = hipMemcpy2D ( d_res, w * 16, ( const char* ) fb->results + ( y * fb->width + x ) * 16, fb->width * 16, w * 16, hgt, hipMemcpyHostToDevice );
+    if ( e == hipSuccess ) e = hipMemcpy2D ( d_aov, w * 48, ( const char* ) ( aov + y * fb->width + x ), fb->width * 48, w * 48, hgt, hipMemcpyHostToDevice );
+    if ( e == hipSuccess ) e = terra_launch_denoise ( d_res, d_aov, ( uint32_t ) w, 0, 0, ( uint32_t ) w, ( uint32_t ) hgt, iterations, s->opts.manual_exposure, ( int ) s->opts.tonemapping_operator,
+                                                      s->opts.gamma, radiance ? d_rad : nullptr, pixels ? d_pix : nullptr, nullptr );
+    if ( e == hipSuccess && radiance ) e = hipMemcpy2D ( radiance + y * fb->width + x, fb->width * 12, d_rad, w * 12, w * 12, hgt, hipMemcpyDeviceToHost );
+    if ( e == hipSuccess && pixels ) e = hipMemcpy2D ( pixels + y * fb->width + x, fb->width * 12, d_pix, w * 12, w * 12, hgt, hipMemcpyDeviceToHost );
+    ( void ) hipFree ( d );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "denoise: %s", hipGetErrorString ( e ) );
     return 0;
 }
 

@@ -111,6 +111,10 @@ _EXTRA = {
     "terra_amd_unpack_tiles": (C.c_int, [C.c_void_p, C.c_void_p] + [_SZ] * 7 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "terra_amd_synchronize": (C.c_int, [C.c_void_p]),
     "terra_amd_time_render_device": (C.c_int, [_CAM, C.c_void_p, C.c_void_p, C.c_void_p] + [_SZ] * 6 + [C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
+    "terra_amd_render_aov_device": (C.c_int, [_CAM, C.c_void_p, C.c_void_p] + [_SZ] * 6 + [C.c_void_p]),
+    "terra_amd_render_aov": (C.c_int, [_CAM, C.c_void_p, C.c_void_p] + [_SZ] * 6),
+    "terra_amd_denoise_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [_SZ] * 6 + [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "terra_amd_denoise": (C.c_int, [C.c_void_p, C.POINTER(api.TerraFramebuffer), C.c_void_p] + [_SZ] * 4 + [C.c_int, C.c_void_p, C.c_void_p]),
 }
 
 
@@ -179,6 +183,57 @@ def render_device(lib, cam, scene, fb: DeviceFramebuffer, rect: Optional[Tuple[i
     x, y, w, h = rect if rect else (0, 0, fb.width, fb.height)
     check(lib.render_device(C.byref(cam), scene, fb.pixels.data_ptr(), fb.results.data_ptr(), fb.width, fb.height, x, y, w, h,
                             rand_calls.data_ptr() if rand_calls is not None else None, stream), "terra_amd_render_device")
+
+
+class AovResult(C.Structure):
+    """TerraAmdAovResult (include/terra_amd.h): running sums of the first hits, 48 bytes"""
+    _fields_ = [("albedo", C.c_float * 3), ("coverage", C.c_float), ("normal", C.c_float * 3), ("depth", C.c_float), ("samples", C.c_int), ("reserved", C.c_int * 3)]
+
+
+AOV_DTYPE = np.dtype([("albedo", np.float32, (3,)), ("coverage", np.float32), ("normal", np.float32, (3,)), ("depth", np.float32), ("samples", np.int32), ("reserved", np.int32, (3,))])
+assert AOV_DTYPE.itemsize == C.sizeof(AovResult) == 48
+
+
+class DeviceAov:
+    """A TerraAmdAovResult buffer in HBM (a torch tensor of 12 words per pixel), the companion of a DeviceFramebuffer: clear both together and make
+    one render_aov_device call per render call."""
+
+    def __init__(self, width: int, height: int, device: str = "cuda"):
+        import torch
+        self.width, self.height = width, height
+        self.data = torch.zeros(height * width * 12, dtype=torch.int32, device=device)
+
+    def clear(self):
+        self.data.zero_()
+
+    def host(self) -> np.ndarray:
+        """the raw sums, AOV_DTYPE records (height, width)"""
+        return self.data.cpu().numpy().view(AOV_DTYPE).reshape(self.height, self.width)
+
+    def means_host(self):
+        """(albedo, normal, depth, coverage): the means over the samples that hit (zero where none did); the normal is the mean vector, not renormalised"""
+        a = self.host()
+        cov = a["coverage"]
+        hit = cov > 0
+        div = np.where(hit, cov, np.float32(1))
+        albedo = np.where(hit[..., None], a["albedo"] / div[..., None], np.float32(0)).astype(np.float32)
+        normal = np.where(hit[..., None], a["normal"] / div[..., None], np.float32(0)).astype(np.float32)
+        depth = np.where(hit, a["depth"] / div, np.float32(0)).astype(np.float32)
+        return albedo, normal, depth, cov.copy()
+
+
+def render_aov_device(lib, cam, scene, aov: DeviceAov, rect: Optional[Tuple[int, int, int, int]] = None, stream=None):
+    x, y, w, h = rect if rect else (0, 0, aov.width, aov.height)
+    check(lib.render_aov_device(C.byref(cam), scene, aov.data.data_ptr(), aov.width, aov.height, x, y, w, h, stream), "terra_amd_render_aov_device")
+
+
+def denoise_device(lib, scene, fb: DeviceFramebuffer, aov: DeviceAov, iterations: int, rect: Optional[Tuple[int, int, int, int]] = None,
+                   radiance=None, pixels=None, stream=None):
+    """terra_amd_denoise_device on fb's results and aov's sums; radiance / pixels: float32 tensors of 3 per frame pixel (None: not written;
+    pixels may be fb.pixels)"""
+    x, y, w, h = rect if rect else (0, 0, fb.width, fb.height)
+    check(lib.denoise_device(scene, fb.results.data_ptr(), aov.data.data_ptr(), fb.width, fb.height, x, y, w, h, iterations,
+                             radiance.data_ptr() if radiance is not None else None, pixels.data_ptr() if pixels is not None else None, stream), "terra_amd_denoise_device")
 
 
 def render_device_sharded(lib, cam, scene, fb: DeviceFramebuffer, tile: int, rank: int, world: int, stream=None):
