@@ -451,6 +451,12 @@ int terra_amd_unit_distribution_2d ( const float* f, size_t nx, size_t ny, const
    probability the same distribution assigns to the bucket each point lies in ((row, column) = truncated (v ny, u nx); 0 for an empty row) -- bit for bit
    the pdf that sampling reports for that bucket */
 int terra_amd_unit_distribution_2d_pdf ( const float* f, size_t nx, size_t ny, const float* xy2, int m, float* pdf );
+/* terra_texture_sample (src/Terra.c:410-466) on the device at uv2[n][2], in texel units: out3[n][3]. The texture is uploaded the way terra_scene_commit
+   uploads a scene's textures. Where the reference is undefined (components below 3 at the end of the data, 4 components, mirror addressing at a tile's
+   first column or row, coordinates outside (-1, 2^32)) the result is this library's rule, which terra_texture_sample on the host follows too */
+int terra_amd_unit_texture_sample ( const TerraTexture* texture, int n, const float* uv2, float* out3 );
+/* terra_texture_sample_latlong (src/Terra.c:468-477) on the device, in its math, for directions dir3[n][3] (not normalised): out3[n][3] */
+int terra_amd_unit_texture_latlong ( const TerraTexture* texture, int n, const float* dir3, float* out3 );
 
 #ifdef __cplusplus
 }

@@ -174,6 +174,9 @@ bool orc_texture_init_hdr ( TerraTexture* t, size_t w, size_t h, size_t comps, c
     t->width = ( uint16_t ) w; t->height = ( uint16_t ) h; t->components = ( uint8_t ) comps; t->depth = 4;
     return true;
 }
+/* a coordinate as the lookups use it: itself inside (-1, 2^32), where the reference's (size_t) conversion is defined; u <= -1 and NaN count as 0,
+   u >= 2^32 as the largest float below it */
+static float texture_coord ( float u ) { return u > -1.f ? ( u < 4294967040.f ? u : 4294967040.f ) : 0.f; }
 TerraFloat3 orc_texture_read ( TerraTexture* t, size_t x, size_t y ) {      /* reference src/Terra.c:368-408 */
     size_t W = t->width, H = t->height;
     switch ( t->address_mode ) {
@@ -189,16 +192,18 @@ TerraFloat3 orc_texture_read ( TerraTexture* t, size_t x, size_t y ) {      /* r
             }
             break;
     }
-    if ( t->depth == 1 ) {
-        const uint8_t* p = ( const uint8_t* ) t->pixels + ( y * W + x ) * t->components;
-        return v3_set ( p[0] / 255.f, p[1] / 255.f, p[2] / 255.f );
-    }
-    const float* p = ( const float* ) t->pixels + ( y * W + x ) * t->components;
-    return v3_set ( p[0], p[1], p[2] );
+    /* three consecutive elements from the texel's first, whatever `components` says (as the reference reads them); past the data they are 0, which is
+       what the product's device copy holds there -- the reference reads beyond its allocation */
+    const size_t texel = ( y * W + x ) * t->components, end = W * H * t->components;
+    float e[3] = { 0.f, 0.f, 0.f };
+    for ( size_t k = 0; k < 3 && texel + k < end; ++k )
+        e[k] = t->depth == 1 ? ( ( const uint8_t* ) t->pixels )[texel + k] / 255.f : ( ( const float* ) t->pixels )[texel + k];
+    return v3_set ( e[0], e[1], e[2] );
 }
 TerraFloat3 orc_texture_sample ( void* tex, const void* uvp, const void* xyz ) {   /* reference src/Terra.c:410-466 */
     TerraTexture* t = ( TerraTexture* ) tex; const TerraFloat2* uv = ( const TerraFloat2* ) uvp; ( void ) xyz;
-    size_t ix = ( size_t ) uv->x, iy = ( size_t ) uv->y;
+    const float u = texture_coord ( uv->x ), v = texture_coord ( uv->y );
+    size_t ix = ( size_t ) u, iy = ( size_t ) v;
     v3 s = v3_set ( 0, 0, 0 );
     if ( t->filter == kTerraFilterPoint ) return orc_texture_read ( t, ix, iy );
     if ( t->filter == kTerraFilterBilinear ) {
@@ -206,7 +211,7 @@ TerraFloat3 orc_texture_sample ( void* tex, const void* uvp, const void* xyz ) {
         size_t y3 = iy + 1 < ( size_t ) t->height - 1 ? iy + 1 : ( size_t ) t->height - 1;
         v3 n1 = orc_texture_read ( t, ix, iy ), n2 = orc_texture_read ( t, x2, iy );
         v3 n3 = orc_texture_read ( t, ix, y3 ), n4 = orc_texture_read ( t, x2, y3 );
-        float wu = uv->x - ix, wv = uv->y - iy, wou = 1.f - wu, wov = 1.f - wv;
+        float wu = u - ix, wv = v - iy, wou = 1.f - wu, wov = 1.f - wv;
         s.x = ( n1.x * wou + n2.x * wu ) * wov + ( n3.x * wou + n4.x * wu ) * wv;
         s.y = ( n1.y * wou + n2.y * wu ) * wov + ( n3.y * wou + n4.y * wu ) * wv;
         s.z = ( n1.z * wou + n2.z * wu ) * wov + ( n3.z * wou + n4.z * wu ) * wv;
@@ -218,8 +223,8 @@ TerraFloat3 orc_texture_sample_latlong ( void* tex, const void* dirp, const void
     v3 d = v3_norm ( * ( const v3* ) dirp );
     float theta = orc_math_acosf ( d.y );
     float phi = orc_math_atan2f ( d.z, d.x ) + terra_PI;
-    size_t u = ( size_t ) ( ( phi / ( 2 * terra_PI ) ) * t->width );      /* < width: terra_PI exceeds pi, so phi / (2 terra_PI) < 1 */
-    size_t v = ( size_t ) ( ( theta / ( terra_PI ) ) * t->height );
+    size_t u = ( size_t ) texture_coord ( ( phi / ( 2 * terra_PI ) ) * t->width );      /* < width: terra_PI exceeds pi, so phi / (2 terra_PI) < 1 */
+    size_t v = ( size_t ) texture_coord ( ( theta / ( terra_PI ) ) * t->height );
     return orc_texture_read ( t, u, v );
 }
 void orc_texture_destroy ( TerraTexture* t ) { free ( t->pixels ); t->pixels = NULL; }

@@ -50,6 +50,9 @@ hipError_t terra_unit_bsdf ( int kind, int n, float* surfaces47, const float* e3
 hipError_t terra_unit_camera ( const DevRenderParams& p, int n, const uint32_t* xy2, const float* r2, float* dirs3 );
 hipError_t terra_unit_tonemap ( int op, float gamma, int n, float* colors3 );
 hipError_t terra_unit_math ( int fn, int n, const float* x, const float* y, float* out );
+// texture_sample at uv2[n][2] / environment_eval's lat-long lookup at dir3[n][3] on the texture whose descriptor is at `t` (device memory)
+hipError_t terra_unit_texture_sample ( const DevTexture* t, int n, const float* uv2, float* out3 );
+hipError_t terra_unit_texture_latlong ( const DevTexture* t, int n, const float* dir3, float* out3 );
 // SURVEY.md 8f N4 (sampling_device.h): cdf / integrals / monotone are device scratch the caller provides (sizes in scene_host.cpp)
 hipError_t terra_unit_stratified ( const uint32_t* seeds, int nseeds, int strata, int samples, int n, float* out2 );
 hipError_t terra_unit_halton ( int first, int n, float* out2 );

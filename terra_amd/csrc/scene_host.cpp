@@ -176,6 +176,8 @@ extern "C" bool terra_texture_init_hdr ( TerraTexture* t, size_t w, size_t h, si
     t->width = ( uint16_t ) w; t->height = ( uint16_t ) h; t->components = ( uint8_t ) comps; t->depth = 4;
     return true;
 }
+// the lookups as the device runs them (trace_device.h texture_read / texture_sample; the rules where the reference is undefined: DESIGN.md 2a)
+static float texture_coord ( float u ) { return u > -1.f ? std::min ( u, 4294967040.f ) : 0.f; }
 extern "C" TerraFloat3 terra_texture_read ( TerraTexture* t, size_t x, size_t y ) {
     TerraFloat3 out = { 0.f, 0.f, 0.f };
     if ( !t || !t->pixels || !t->width || !t->height ) return out;
@@ -184,26 +186,25 @@ extern "C" TerraFloat3 terra_texture_read ( TerraTexture* t, size_t x, size_t y 
     else if ( t->address_mode == kTerraTextureAddressWrap ) { x %= W; y %= H; }
     else if ( ( x / W ) % 2 == 0 ) { x %= W; y %= H; }
     else { x = W - ( x % W ); y = H - ( y % H ); x = std::min ( x, W - 1 ); y = std::min ( y, H - 1 ); }
-    const size_t texel = ( y * W + x ) * t->components;
-    if ( t->depth == 1 ) {
-        const uint8_t* p = ( const uint8_t* ) t->pixels + texel;
-        out.x = p[0] / 255.f; out.y = t->components > 1 ? p[1] / 255.f : 0.f; out.z = t->components > 2 ? p[2] / 255.f : 0.f;
-    } else if ( t->depth == 4 ) {
-        const float* p = ( const float* ) t->pixels + texel;
-        out.x = p[0]; out.y = t->components > 1 ? p[1] : 0.f; out.z = t->components > 2 ? p[2] : 0.f;
-    }
+    // three consecutive elements from the texel's first, whatever `components` says; past the data they read as 0 (the device section's padding)
+    const size_t texel = ( y * W + x ) * t->components, end = W * H * t->components;
+    float e[3] = { 0.f, 0.f, 0.f };
+    for ( size_t k = 0; k < 3 && texel + k < end; ++k )
+        e[k] = t->depth == 1 ? ( ( const uint8_t* ) t->pixels )[texel + k] / 255.f : t->depth == 4 ? ( ( const float* ) t->pixels )[texel + k] : 0.f;
+    out.x = e[0]; out.y = e[1]; out.z = e[2];
     return out;
 }
 extern "C" TerraFloat3 terra_texture_sample ( void* tex, const void* uvp, const void* ) {
     TerraTexture* t = ( TerraTexture* ) tex; const TerraFloat2* uv = ( const TerraFloat2* ) uvp;
-    size_t ix = ( size_t ) uv->x, iy = ( size_t ) uv->y;
+    const float u = texture_coord ( uv->x ), v = texture_coord ( uv->y );
+    size_t ix = ( size_t ) u, iy = ( size_t ) v;
     if ( t->filter == kTerraFilterPoint ) return terra_texture_read ( t, ix, iy );
     TerraFloat3 s = { 0.f, 0.f, 0.f };
     if ( t->filter == kTerraFilterBilinear ) {
         size_t x2 = std::min<size_t> ( ix + 1, ( size_t ) t->width - 1 ), y2 = std::min<size_t> ( iy + 1, ( size_t ) t->height - 1 );
         TerraFloat3 n1 = terra_texture_read ( t, ix, iy ), n2 = terra_texture_read ( t, x2, iy );
         TerraFloat3 n3 = terra_texture_read ( t, ix, y2 ), n4 = terra_texture_read ( t, x2, y2 );
-        float wu = uv->x - ix, wv = uv->y - iy, wou = 1.f - wu, wov = 1.f - wv;
+        float wu = u - ix, wv = v - iy, wou = 1.f - wu, wov = 1.f - wv;
         s.x = ( n1.x * wou + n2.x * wu ) * wov + ( n3.x * wou + n4.x * wu ) * wv;
         s.y = ( n1.y * wou + n2.y * wu ) * wov + ( n3.y * wou + n4.y * wu ) * wv;
         s.z = ( n1.z * wou + n2.z * wu ) * wov + ( n3.z * wou + n4.z * wu ) * wv;
@@ -215,8 +216,8 @@ extern "C" TerraFloat3 terra_texture_sample_latlong ( void* tex, const void* dir
     TerraFloat3 d = terra_normf3 ( ( const TerraFloat3* ) dirp );
     float theta = acosf ( d.y );
     float phi = atan2f ( d.z, d.x ) + terra_PI;
-    size_t u = ( size_t ) ( ( phi / ( 2 * terra_PI ) ) * t->width );
-    size_t v = ( size_t ) ( ( theta / ( terra_PI ) ) * t->height );
+    size_t u = ( size_t ) texture_coord ( ( phi / ( 2 * terra_PI ) ) * t->width );
+    size_t v = ( size_t ) texture_coord ( ( theta / ( terra_PI ) ) * t->height );
     return terra_texture_read ( t, u, v );
 }
 extern "C" void terra_texture_destroy ( TerraTexture* t ) { if ( t ) { free ( t->pixels ); t->pixels = nullptr; } }
@@ -973,6 +974,19 @@ static int build_fast_tree_host ( const Scene* s, TreeChoice& c, const Flat& f, 
     return finish_fast_tree ( s, c, f, built.nodes, ft.tris, ft, t_phase );
 }
 
+// the texture part of a blob and its placement: the descriptors' section, one section per texture (its elements and two more, zero: the 3-element read of the
+// last texel of a texture of fewer than three components), the descriptors less their address; then every section of L on its 256-byte boundary
+static void layout_textures ( BlobLayout& L, const std::vector<const TerraTexture*>& textures ) {
+    L.sec[kSecTexDesc].bytes = textures.size() * sizeof ( DevTexture );      // (put_texture_descs: they hold absolute addresses)
+    for ( size_t k = 0; k < textures.size(); ++k ) {
+        const TerraTexture* t = textures[k];
+        const size_t texels = ( size_t ) t->width * t->height * t->components;
+        L.sec[kSecTextures + k] = Section { 0, ( texels + 2 ) * t->depth, t->pixels, texels * t->depth };      // +2 elements: the 3-component read of the last texel
+        DevTexture& d = L.tdesc[k];
+        d.width = t->width; d.height = t->height; d.components = t->components; d.depth = t->depth; d.filter = t->filter; d.address_mode = t->address_mode;
+    }
+    for ( Section& x : L.sec ) { x.offset = L.total; L.total = ( L.total + x.bytes + 255 ) & ~size_t ( 255 ); }
+}
 // ---- the blob: every array of the scene in one allocation, 256-byte aligned sections in this order, then one section per texture ----------------------------
 // c: the choice as it stands before the device builder runs (which sections it needs room for)
 static BlobLayout layout_blob ( const Flat& f, const FastTree& ft, const TreeChoice& c ) {
@@ -987,15 +1001,7 @@ static BlobLayout layout_blob ( const Flat& f, const FastTree& ft, const TreeCho
     L.sec[kSecFastTris] = section_of ( ft.tris, on_dev ? on_dev : ft.tris.size() );
     L.sec[kSecReplay] = section_of ( ft.reach.replay, n_replay );
     L.sec[kSecLeafParent] = section_of ( ft.reach.leaf_parent, n_reach ); L.sec[kSecLeafMask] = section_of ( ft.reach.leaf_mask, n_reach );
-    L.sec[kSecTexDesc].bytes = f.textures.size() * sizeof ( DevTexture );      // (put_texture_descs: they hold absolute addresses)
-    for ( size_t k = 0; k < f.textures.size(); ++k ) {
-        const TerraTexture* t = f.textures[k];
-        const size_t texels = ( size_t ) t->width * t->height * t->components;
-        L.sec[kSecTextures + k] = Section { 0, ( texels + 2 ) * t->depth, t->pixels, texels * t->depth };      // +2 elements: the 3-component read of the last texel
-        DevTexture& d = L.tdesc[k];
-        d.width = t->width; d.height = t->height; d.components = t->components; d.depth = t->depth; d.filter = t->filter; d.address_mode = t->address_mode;
-    }
-    for ( Section& x : L.sec ) { x.offset = L.total; L.total = ( L.total + x.bytes + 255 ) & ~size_t ( 255 ); }
+    layout_textures ( L, f.textures );
     return L;
 }
 static int put_section ( char* base, const Section& x ) {
@@ -1010,6 +1016,14 @@ static int put_texture_descs ( const BlobLayout& L, char* base ) {
     for ( size_t k = 0; k < td.size(); ++k ) td[k].data = base + L.sec[kSecTextures + k].offset;
     HIP_TRY ( hipMemcpy ( base + L.sec[kSecTexDesc].offset, td.data(), td.size() * sizeof ( DevTexture ), hipMemcpyHostToDevice ), kTerraAmdErrNoDevice );
     return 0;
+}
+// a blob on the current device: allocated, zeroed (so what no section covers, the textures' padding included, reads as 0), every section's host data and the
+// texture descriptors copied in. *d_blob is the caller's to free, also when this fails
+static int new_blob ( const BlobLayout& L, void** d_blob ) {
+    HIP_TRY ( hipMalloc ( d_blob, L.total ), kTerraAmdErrNoDevice );
+    HIP_TRY ( hipMemset ( *d_blob, 0, L.total ), kTerraAmdErrNoDevice );
+    for ( const Section& x : L.sec ) if ( int rc = put_section ( ( char* ) *d_blob, x ) ) return rc;
+    return put_texture_descs ( L, ( char* ) *d_blob );
 }
 // every pointer of a scene record into the blob at `base`. Which of the optional ones are set follows from the record's own counts: a fast tree (n_fast_nodes),
 // the device builder's binary tree (its section in the layout), the reachability tables (reach)
@@ -1085,13 +1099,10 @@ static int upload ( Scene* s, int device, const Flat& f, FastTree& ft ) {
     Scene::Replica& r = s->replicas[0]; DevScene& dev = r.dev;
     r.device = device;
     HIP_TRY ( hipSetDevice ( r.device ), kTerraAmdErrNoDevice );
-    HIP_TRY ( hipMalloc ( &r.d_blob, L.total ), kTerraAmdErrNoDevice );
-    HIP_TRY ( hipMemset ( r.d_blob, 0, L.total ), kTerraAmdErrNoDevice );
+    if ( int rc = new_blob ( L, &r.d_blob ) ) return rc;
     HIP_TRY ( hipMalloc ( ( void** ) &r.d_counters, kCtrCount * sizeof ( unsigned long long ) ), kTerraAmdErrNoDevice );
     HIP_TRY ( hipMemset ( r.d_counters, 0, kCtrCount * sizeof ( unsigned long long ) ), kTerraAmdErrNoDevice );
     char* base = ( char* ) r.d_blob;
-    for ( const Section& x : L.sec ) if ( int rc = put_section ( base, x ) ) return rc;
-    if ( int rc = put_texture_descs ( L, base ) ) return rc;
     if ( c.fast_on_device ) { if ( int rc = build_fast_tree_device ( s, c, f, L, base, ft ) ) return rc; }
     for ( Section& x : L.sec ) { x.host = nullptr; x.host_bytes = 0; }          // (the host data is this commit's)
     s->blob = std::move ( L ); s->d_bytes = s->blob.total; s->env_dist_floats = 0;
@@ -2017,3 +2028,22 @@ extern "C" int terra_amd_unit_distribution_2d_pdf ( const float* f, size_t nx, s
     auto dp = u.out ( pdf, ( size_t ) m );
     return u.finish ( u.ok ? terra_unit_distribution_2d_pdf ( df, ( uint32_t ) nx, ( uint32_t ) ny, dc, di, dmc, dm, dxy, m, dp ) : hipSuccess );
 }
+
+// ---- the texture lookups (trace_device.h texture_sample, environment_eval's lat-long lookup) on one texture, which reaches the device the way a scene's
+// textures do: layout_textures (section size with its padding, 256-byte placement, descriptor) and new_blob (zeroed allocation, upload, descriptor's address)
+static int unit_texture ( const TerraTexture* t, int n, const float* in, int in_width, float* out3, hipError_t ( *launch ) ( const DevTexture*, int, const float*, float* ) ) {
+    if ( need_device() ) return kTerraAmdErrNoDevice;
+    if ( !t || !texture_ok ( t ) || n < 0 || ( n && ( !in || !out3 ) ) ) return fail ( kTerraAmdErrBadArgument, "unit texture lookup: invalid texture or null array" );
+    BlobLayout L { std::vector<Section> ( kSecTextures + 1 ), std::vector<DevTexture> ( 1 ) };
+    layout_textures ( L, { t } );
+    void* d_blob = nullptr;
+    int rc = new_blob ( L, &d_blob );
+    if ( !rc ) {
+        Unit u; auto a = u.in ( in, ( size_t ) in_width * n ); auto o = u.out ( out3, 3 * ( size_t ) n );
+        rc = u.finish ( u.ok ? launch ( ( const DevTexture* ) ( ( char* ) d_blob + L.sec[kSecTexDesc].offset ), n, a, o ) : hipSuccess );
+    }
+    ( void ) hipFree ( d_blob );
+    return rc;
+}
+extern "C" int terra_amd_unit_texture_sample ( const TerraTexture* t, int n, const float* uv2, float* out3 ) { return unit_texture ( t, n, uv2, 2, out3, terra_unit_texture_sample ); }
+extern "C" int terra_amd_unit_texture_latlong ( const TerraTexture* t, int n, const float* dir3, float* out3 ) { return unit_texture ( t, n, dir3, 3, out3, terra_unit_texture_latlong ); }

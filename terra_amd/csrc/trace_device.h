@@ -828,10 +828,17 @@ TD void traverse_resume ( const Tracer& T, const Ray& r, const SlabSel& sel, con
 }
 
 // -----------------------------------------------------------------------------
-// textures (reference src/Terra.c:368-466). uv is in TEXEL units, as the reference uses it
-// ((size_t)uv->x); three consecutive components are read whatever `components` says, as the
-// reference does; negative coordinates are undefined there and clamp to 0 here.
+// textures (reference src/Terra.c:368-466; the rules where the reference is undefined: DESIGN.md 2a).
+// uv is in TEXEL units, as the reference uses it ((size_t)uv->x). A texel is `components` elements;
+// three consecutive elements are read from its first whatever `components` says, as the reference
+// does: a 1- or 2-component texel returns its successors' elements too, a 4-component one drops its
+// fourth, and past the last element of the data the section's two padding elements read as 0.
+// A coordinate is used as it is inside (-1, 2^32): truncated towards zero to the texel, the bilinear
+// weight u - texel (negative inside (-1, 0), as in the reference); u <= -1 and NaN count as 0,
+// u >= 2^32 as the largest float below it (texture_coord). Mirror addressing takes the tile's parity
+// from x alone and clamps the column W / row H it reaches at x % W == 0 / y % H == 0 to the last one.
 // -----------------------------------------------------------------------------
+TD float texture_coord ( float u ) { return u > -1.f ? fminf ( u, 4294967040.f ) : 0.f; }
 TD V3 texture_read ( const DevTexture& t, uint32_t x, uint32_t y ) {
     const uint32_t W = t.width, H = t.height;
     if ( t.address_mode == 2 ) { x = x < W - 1 ? x : W - 1; y = y < H - 1 ? y : H - 1; }
@@ -847,7 +854,8 @@ TD V3 texture_read ( const DevTexture& t, uint32_t x, uint32_t y ) {
     return v3 ( p[0], p[1], p[2] );
 }
 TD V3 texture_sample ( const DevTexture& t, float u, float v ) {
-    uint32_t ix = u > 0.f ? ( uint32_t ) u : 0u, iy = v > 0.f ? ( uint32_t ) v : 0u;
+    u = texture_coord ( u ); v = texture_coord ( v );
+    uint32_t ix = ( uint32_t ) u, iy = ( uint32_t ) v;
     if ( t.filter == 0 ) return texture_read ( t, ix, iy );
     if ( t.filter != 1 ) return v3 ( 0, 0, 0 );          // trilinear / anisotropic: unimplemented in the reference too (returns zero)
     uint32_t x2 = ix + 1 < t.width - 1 ? ix + 1 : t.width - 1, y2 = iy + 1 < t.height - 1 ? iy + 1 : t.height - 1;
@@ -867,8 +875,8 @@ TD V3 environment_eval ( const DevScene& sc, V3 dir ) {
     V3 d = normalize ( dir );
     float theta = tdm_acosf ( d.y );
     float phi = tdm_atan2f ( d.z, d.x ) + TERRA_PI_F;
-    uint32_t u = ( uint32_t ) ( ( phi / ( 2 * TERRA_PI_F ) ) * ( float ) t.width );
-    uint32_t v = ( uint32_t ) ( ( theta / TERRA_PI_F ) * ( float ) t.height );
+    uint32_t u = ( uint32_t ) texture_coord ( ( phi / ( 2 * TERRA_PI_F ) ) * ( float ) t.width );      // (a direction without a length gives NaN: texel 0)
+    uint32_t v = ( uint32_t ) texture_coord ( ( theta / TERRA_PI_F ) * ( float ) t.height );
     return texture_read ( t, u, v );
 }
 

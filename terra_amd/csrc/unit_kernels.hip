@@ -143,7 +143,9 @@ __device__ void surface_to_floats ( const DevScene& sc, const Surface& sf, uint3
     q[16] = sf.normal.x; q[17] = sf.normal.y; q[18] = sf.normal.z;
     q[19] = sf.emissive.x; q[20] = sf.emissive.y; q[21] = sf.emissive.z;
     q[22] = sc.mats[object].ior;
-    for ( int a = 0; a < 8; ++a ) for ( int k = 0; k < 3; ++k ) q[23 + 3 * a + k] = sc.mats[object].attributes[a][k];
+    // the attributes as the surface carries them (a textured slot: its sample at the hit's texcoord); slots the surface does not hold: the material's constants.
+    // For a surface as surface_init left it: BSDF sampling overwrites Phong slot 3 and glass slots 2, 3 (scratch), so a record taken after a sample is not this
+    for ( int a = 0; a < 8; ++a ) for ( int k = 0; k < 3; ++k ) q[23 + 3 * a + k] = a < 4 ? pick ( sf.attr[a], k ) : sc.mats[object].attributes[a][k];
 }
 __global__ __launch_bounds__ ( 256 ) void k_raycast ( DevScene sc, int n, const float* o, const float* d, int* obj, int* tri, float* point, float* surface47 ) {
     extern __shared__ int lds_stack[];
@@ -253,6 +255,30 @@ hipError_t terra_unit_math ( int fn, int n, const float* x, const float* y, floa
     return hipGetLastError();
 }
 
+// ---- the texture lookups on one texture of a blob (scene_host.cpp unit_texture): texture_sample in texel units, and environment_eval by direction on a scene
+// record that holds nothing but that texture as its lat-long environment
+__global__ void k_texture_sample ( const DevTexture* t, int n, const float* uv2, float* out3 ) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if ( i >= n ) return;
+    V3 c = texture_sample ( *t, uv2[2 * i], uv2[2 * i + 1] );
+    out3[3 * i] = c.x; out3[3 * i + 1] = c.y; out3[3 * i + 2] = c.z;
+}
+hipError_t terra_unit_texture_sample ( const DevTexture* t, int n, const float* uv2, float* out3 ) {
+    if ( n > 0 ) hipLaunchKernelGGL ( k_texture_sample, UNIT_GRID ( n ), 0, 0, t, n, uv2, out3 );
+    return hipGetLastError();
+}
+__global__ void k_texture_latlong ( DevScene sc, int n, const float* dir3, float* out3 ) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if ( i >= n ) return;
+    V3 c = environment_eval ( sc, v3p ( dir3 + 3 * i ) );
+    out3[3 * i] = c.x; out3[3 * i + 1] = c.y; out3[3 * i + 2] = c.z;
+}
+hipError_t terra_unit_texture_latlong ( const DevTexture* t, int n, const float* dir3, float* out3 ) {
+    DevScene sc {};
+    sc.textures = t; sc.env_mode = 2; sc.env_tex = 0;
+    if ( n > 0 ) hipLaunchKernelGGL ( k_texture_latlong, UNIT_GRID ( n ), 0, 0, sc, n, dir3, out3 );
+    return hipGetLastError();
+}
 
 // ---- SURVEY.md 8f N4, unit level: samplers and distributions (sampling_device.h) ---------------------------------------------
 // one sampler per seed; a stratified sampler's n pairs are inherently sequential (they share one random stream)

@@ -27,6 +27,7 @@ class Material:
     roughness: float = 0.2
     albedo_texture: Optional["TextureDesc"] = None       # replaces the constant albedo (slot 0 diffuse, slot 1 Phong)
     emissive_texture: Optional["TextureDesc"] = None
+    attribute_textures: Optional[dict] = None            # attribute slot -> TextureDesc, bound after the preset's own attributes (any slot below its END)
     albedo: tuple = (0.73, 0.73, 0.73)
     emissive: tuple = (0.0, 0.0, 0.0)
     specular_color: tuple = (0.0, 0.0, 0.0)
@@ -36,7 +37,7 @@ class Material:
 
 @dataclass
 class TextureDesc:
-    """A TerraTexture: data (h, w, c) uint8 or float32, c <= 3; lookups are in TEXEL units (reference src/Terra.c:410-414)."""
+    """A TerraTexture: data (h, w, c) uint8 or float32 (the reference asserts c <= 3; this library and the oracle take any c >= 1); lookups are in TEXEL units (reference src/Terra.c:410-414)."""
     data: np.ndarray
     filter: int = 0            # kTerraFilterPoint / 1 = bilinear
     address_mode: int = 0      # wrap / 1 mirror / 2 clamp
@@ -176,6 +177,62 @@ def cornell_textured(width=256, height=256, spp=4, bounces=8, integrator=api.kTe
     stripes = r.randint(30, 255, size=(4, 6, 3)).astype(np.uint8)
     d.objects[4] = ObjectDesc(box.triangles, box.normals, planar_uv(box.triangles, 0, 1, 9.0), Material(kind="phong", specular_color=(0.4, 0.4, 0.4), specular_intensity=20.0, albedo_texture=TextureDesc(stripes, 1, 1 if mirror else 0)), "phong_tex")
     d.name = "cornell32_textured"
+    for k, v in kw.items():
+        setattr(d, k, v)
+    return d
+
+
+def atlas(width=96, height=64, spp=2, bounces=3, integrator=api.kTerraIntegratorSimple, reference_defined=False, cells=None, filler=0, **kw) -> SceneDesc:
+    """A wall of quads, one per texture configuration (filter x address mode x depth x components 1-4, 48 in all; `cells` takes the first so many of a
+    shuffled list), each its own object with texcoords (texel units) that run from below 0 across more than two tiles, so every quad crosses tile borders.
+    Quads alternate between a diffuse material (the configuration on slot 0) and a Phong one with a texture on every attribute slot (the configuration on
+    slot 0, a texture shared with another object on slot 1, integral exponents on slot 2, a fourth on slot 3); every sixth quad and the ceiling light carry a
+    textured emissive. One texture is the albedo of two quads and the lat-long environment. A floor (of 2 * filler^2 triangles if `filler`) closes the room.
+    reference_defined: only what the reference defines (three components, wrap / clamp, coordinates above -1) and no environment term."""
+    r = np.random.RandomState(17)
+    configs = [(f, a, dp, c) for f in (0, 1) for a in (0, 1, 2) for dp in (1, 4) for c in (1, 2, 3, 4)]
+    if reference_defined:
+        configs = [k for k in configs if k[3] == 3 and k[1] != 1]
+    configs = [configs[i] for i in r.permutation(len(configs))][:cells]
+    def tex(w, h, c, depth, filt, addr, lo=0.05, hi=0.95):
+        data = r.randint(int(lo * 255), int(hi * 255), size=(h, w, c)).astype(np.uint8) if depth == 1 else r.uniform(lo, hi, size=(h, w, c)).astype(np.float32)
+        return TextureDesc(data, filt, addr)
+    shared = tex(6, 4, 3, 4, 1, 0)
+    exponents = TextureDesc(r.randint(1, 40, size=(3, 5, 3)).astype(np.float32), 0, 0)
+    fourth = tex(2, 3, 3, 1, 0, 2)
+    cols = 8 if len(configs) > 8 else 4
+    rows = -(-len(configs) // cols)
+    objs = []
+    for i, (filt, addr, depth, comps) in enumerate(configs):
+        w, h = [(5, 3), (4, 4), (7, 2), (1, 6), (3, 1)][i % 5]
+        t = tex(w, h, comps, depth, filt, addr)
+        cx, cy = i % cols, i // cols
+        x0, x1 = -1 + 2.0 * cx / cols, -1 + 2.0 * (cx + 1) / cols
+        y0, y1 = 2.0 * cy / rows, 2.0 * (cy + 1) / rows
+        tris, nrm = _quad((x0, y0, 1), (x1, y0, 1), (x1, y1, 1), (x0, y1, 1), (0, 0, -1))
+        ulo, vlo = (-0.75, -0.5) if reference_defined else (-1.7 * w, -1.2 * h)
+        corner = {x0: ulo, x1: 2.6 * w, y0: vlo, y1: 2.3 * h}
+        uv = np.zeros((2, 3, 2), np.float32)
+        uv[..., 0] = np.vectorize(corner.get)(tris[..., 0].astype(np.float64)); uv[..., 1] = np.vectorize(corner.get)(tris[..., 1].astype(np.float64))
+        if i % 2 == 0:
+            m = Material(albedo_texture=shared if i in (0, 2) else t)
+        else:
+            m = Material(kind="phong", attribute_textures={api.TERRA_PHONG_SPECULAR_COLOR: t, api.TERRA_PHONG_ALBEDO: shared if i == 1 else tex(3, 3, 3, 1, 1, 0),
+                                                           api.TERRA_PHONG_SPECULAR_INTENSITY: exponents, api.TERRA_PHONG_SAMPLE_PICK: fourth})
+        if i % 6 == 4:
+            m.emissive_texture = tex(2, 2, 3, 4, filt, addr if not reference_defined or addr != 1 else 0, 0.5, 3.0)
+        objs.append(ObjectDesc(tris.astype(np.float32), nrm, uv, m, f"cell{i}_f{filt}a{addr}d{depth}c{comps}"))
+    lt, ln = _quad((-0.5, 1.99, -0.5), (0.5, 1.99, -0.5), (0.5, 1.99, 0.5), (-0.5, 1.99, 0.5), (0, -1, 0))
+    luv = np.zeros((2, 3, 2), np.float32); luv[..., 0] = (lt[..., 0] + 0.5) * 5.0 - 0.5; luv[..., 1] = (lt[..., 2] + 0.5) * 5.0 - 0.5
+    objs.append(ObjectDesc(lt, ln, luv, Material(albedo=(0.78, 0.78, 0.78), emissive_texture=tex(3, 2, 3, 4, 1, 2, 6.0, 15.0)), "light_textured"))
+    n = max(1, filler)
+    parts = [_quad((-1 + 2.0 * a / n, 0, -1 + 2.0 * b / n), (-1 + 2.0 * (a + 1) / n, 0, -1 + 2.0 * b / n), (-1 + 2.0 * (a + 1) / n, 0, -1 + 2.0 * (b + 1) / n),
+                   (-1 + 2.0 * a / n, 0, -1 + 2.0 * (b + 1) / n), (0, 1, 0)) for a in range(n) for b in range(n)]
+    objs.append(ObjectDesc(*_merge(parts), Material(albedo=(0.6, 0.6, 0.55)), "floor"))
+    d = SceneDesc(objects=objs, width=width, height=height, spp=spp, bounces=bounces, integrator=integrator, camera_position=(0.0, 1.0, -2.2),
+                  name="atlas_reference" if reference_defined else "atlas")
+    if not reference_defined:
+        d.environment_texture = shared; d.environment_lighting = True
     for k, v in kw.items():
         setattr(d, k, v)
     return d
@@ -379,19 +436,24 @@ def sponza_hall(width=1920, height=1080, spp=256, bounces=8, integrator=api.kTer
 # --------------------------------------------------------------------------
 
 _keepalive = []      # TerraTexture structs must outlive the scenes that borrow them (reference src/Terra.c:294-304)
+_textures = {}       # (library, TextureDesc, its data) -> (TerraTexture, the two): one TextureDesc bound in several places is ONE texture of that library
 
 
 def texture_attribute(lib: api.TerraLib, td: TextureDesc, latlong: bool = False) -> api.TerraAttribute:
-    data = np.ascontiguousarray(td.data)
-    h, w, c = data.shape
-    tex = api.TerraTexture()
-    if data.dtype == np.uint8:
-        lib.texture_init(C.byref(tex), w, h, c, data.ctypes.data)
-    else:
-        data = data.astype(np.float32)
-        lib.texture_init_hdr(C.byref(tex), w, h, c, data.ctypes.data)
-    tex.filter = td.filter
-    tex.address_mode = td.address_mode
+    key = (id(lib), id(td), id(td.data), td.filter, td.address_mode)
+    if key not in _textures:
+        data = np.ascontiguousarray(td.data)
+        h, w, c = data.shape
+        tex = api.TerraTexture()
+        if data.dtype == np.uint8:
+            lib.texture_init(C.byref(tex), w, h, c, data.ctypes.data)
+        else:
+            data = data.astype(np.float32)
+            lib.texture_init_hdr(C.byref(tex), w, h, c, data.ctypes.data)
+        tex.filter = td.filter
+        tex.address_mode = td.address_mode
+        _textures[key] = (tex, td, td.data)
+    tex = _textures[key][0]
     a = api.TerraAttribute()
     (lib.attribute_init_cubemap if latlong else lib.attribute_init_texture)(C.byref(a), C.byref(tex))
     _keepalive.append((tex, a))
@@ -437,6 +499,9 @@ def fill_object(lib: api.TerraLib, obj: api.TerraObject, od: ObjectDesc) -> None
         lib.bsdf_glass_init(C.byref(mat.bsdf))
     else:
         raise ValueError(f"unknown material kind {m.kind!r}")
+    for slot, td in (m.attribute_textures or {}).items():
+        assert slot < mat.attributes_count
+        mat.attributes[slot] = texture_attribute(lib, td)
 
 
 def apply_options(lib: api.TerraLib, scene, d: SceneDesc) -> None:

@@ -208,6 +208,39 @@ class Unit:
                     surf[i] = np.frombuffer(bytes(s), dtype=np.float32)
         return obj, tri, point, surf
 
+    # -- texture lookups (unit level). data: (h, w, c) uint8 or float32, uv in texel units, dirs not normalised. "amd" runs the device's texture_sample /
+    # environment lookup (terra_amd_unit_texture_*) unless host=True, which calls the library's host functions (terra_texture_sample*, no GPU needed) as
+    # "ref" and "orc" call theirs, sample by sample
+    @staticmethod
+    def texture_of(data, filt=0, addr=0):
+        """(TerraTexture over data's own memory, data): keep both alive while the texture is in use"""
+        assert data.ndim == 3 and data.dtype in (np.uint8, np.float32)
+        data = np.ascontiguousarray(data)
+        t = api.TerraTexture(data.ctypes.data, data.shape[1], data.shape[0], data.shape[2], data.dtype.itemsize, filt, addr)
+        return t, data
+
+    def _texture_lookup(self, name, data, filt, addr, x, host):
+        t, data = self.texture_of(data, filt, addr)
+        x = np.ascontiguousarray(x, np.float32); n = len(x)
+        out = np.zeros((n, 3), np.float32)
+        if self.kind == "amd" and not host:
+            unit = {"texture_sample": "texture_sample", "texture_sample_latlong": "texture_latlong"}[name]
+            rc = self._f(unit, C.c_int, [C.POINTER(api.TerraTexture), C.c_int, C.c_void_p, C.c_void_p])(C.byref(t), n, x.ctypes.data, out.ctypes.data)
+            assert rc == 0, last_error()
+            return out
+        f = getattr(self.L, name)
+        tp = C.addressof(t); base = x.ctypes.data; step = x.strides[0]
+        for i in range(n):
+            r = f(tp, base + i * step, None)
+            out[i] = (r.x, r.y, r.z)
+        return out
+
+    def texture_sample(self, data, filt, addr, uv, host=False):
+        return self._texture_lookup("texture_sample", data, filt, addr, uv, host)
+
+    def texture_latlong(self, data, addr, dirs, host=False):
+        return self._texture_lookup("texture_sample_latlong", data, 0, addr, dirs, host)
+
     # -- SURVEY 8f N4: samplers and distributions (unit level)
     def stratified(self, seeds, strata, samples, n):
         seeds = np.asarray(seeds, np.uint32)

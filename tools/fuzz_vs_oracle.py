@@ -22,6 +22,13 @@ orc.fn("orc_set_math_mode", None, [C.c_int])(1)
 orp = orc.fn("orc_render_pixels", None, [C.POINTER(api.TerraCamera), C.c_void_p, C.POINTER(api.TerraFramebuffer)] + [C.c_size_t] * 4 + [C.c_uint64, C.c_void_p])
 
 
+def random_texture(scale=1.0):
+    """FUZZ_EXT=1: random size, filter, address mode, depth and 1-4 components"""
+    th, tw, c = int(rs.randint(1, 9)), int(rs.randint(1, 12)), int(rs.randint(1, 5))
+    data = (rs.uniform(0, scale, size=(th, tw, c)).astype(np.float32) if rs.randint(2) else rs.randint(0, 256, size=(th, tw, c)).astype(np.uint8))
+    return scenes.TextureDesc(data, filter=int(rs.randint(0, 2)), address_mode=int(rs.randint(0, 3)))
+
+
 def soup(n_tris, n_objects):
     objs = []
     per = max(1, n_tris // n_objects); left = n_tris
@@ -36,7 +43,12 @@ def soup(n_tris, n_objects):
         kind = str(rs.choice(["diffuse", "diffuse", "phong", "ggx", "glass"]))
         m = scenes.Material(kind=kind, albedo=tuple(rs.uniform(0.2, 0.9, 3)), emissive=(4.0, 3.0, 2.0) if k == 0 else (0.0, 0.0, 0.0),
                             specular_color=tuple(rs.uniform(0.1, 0.9, 3)), specular_intensity=float(rs.choice([1.0, 8.0, 30.5])), roughness=float(rs.uniform(0.05, 0.9)), ior=1.5)
-        objs.append(scenes.ObjectDesc(tris, nrm, rs.uniform(0, 1, size=(n, 3, 2)).astype(np.float32), m))
+        uv = rs.uniform(0, 1, size=(n, 3, 2)).astype(np.float32)
+        if EXT and rs.randint(3) == 0:      # FUZZ_EXT=1: some materials with a textured albedo / emissive, texcoords (texel units) across several tiles and below 0
+            if kind in ("diffuse", "phong"): m.albedo_texture = random_texture()
+            if k == 0 and rs.randint(2): m.emissive_texture = random_texture(6.0)
+            uv = rs.uniform(-3, 30, size=(n, 3, 2)).astype(np.float32)
+        objs.append(scenes.ObjectDesc(tris, nrm, uv, m))
     return objs
 
 
@@ -55,7 +67,7 @@ for it in range(n_iter):
     d = scenes.SceneDesc(objects=soup(n, int(rs.randint(1, 5))), width=W, height=H, spp=spp, bounces=int(rs.randint(0, 6)), integrator=integ,
                          camera_position=(0.0, 0.0, -6.0 * SCALE), tonemap=int(rs.randint(0, 5)), environment=(0.2, 0.3, 0.4), environment_lighting=bool(rs.randint(2)),
                          jitter=float(rs.choice([0.0, 0.5])))      # jitter 0 on odd frame sizes gives rays with exactly zero direction components (the exact slab path)
-    if EXT:     # FUZZ_EXT=1: the unpinned extensions too -- a lat-long environment texture, environment importance sampling, the pixel sampler feeding bounce 0
+    if EXT:     # FUZZ_EXT=1: the unpinned extensions too (and textured materials, soup()) -- a lat-long environment texture, environment importance sampling, the pixel sampler feeding bounce 0
         if rs.randint(2):
             th, tw = int(rs.randint(1, 12)), int(rs.randint(1, 20))
             tex = rs.uniform(0, 3, size=(th, tw, 3)).astype(np.float32) if rs.randint(2) else rs.randint(0, 256, size=(th, tw, 3)).astype(np.uint8)
