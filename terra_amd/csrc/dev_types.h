@@ -38,7 +38,7 @@ struct DevNode {
 };
 static_assert ( sizeof ( DevNode ) == 64, "DevNode must be 64 bytes" );
 
-// A fast-tree node as the kernels read it (trace_device.h "MODE 2"), 128 bytes = one cache line, FOUR children: per child and axis the two planes of the child's box
+// A fast-tree node as the kernels read it (traverse_fast.h "MODE 2"), 128 bytes = one cache line, FOUR children: per child and axis the two planes of the child's box
 // as binary16 rounded outward (min down, max up), times DevScene's power-of-two scale, as one 32-bit word -- the four children's words of an axis side by side and
 // every such 16-byte group twice: q[axis][0][child] = min | max << 16 for rays travelling in the axis' positive direction, q[axis][1][child] = max | min << 16 for the
 // others, so that a ray LOADS the group whose low half is its near plane (no per-box swap) --, then the four child words (inner: index of a wide node; leaf:
@@ -139,7 +139,7 @@ struct DevScene {
     const uint32_t*    fast_leaf_mask;
     uint32_t           reach;
     // (cos, sin) of 2 * terra_PI * (k * 2^-24) for k = 0 .. 2^24 - 1: the azimuth the BSDF samplers make of a stream-B variate, tabulated once per device
-    // (128 MB of HBM; trace_device.h azimuth_fetch). nullptr = compute.
+    // (128 MB of HBM; shading_device.h azimuth_fetch). nullptr = compute.
     const float2*      sincos24;
     // environment lighting (terra_amd_set_environment_lighting; off = the reference's behaviour):
     // 0 off, 1 constant env_color, 2 lat-long lookup of textures[env_tex] by ray direction

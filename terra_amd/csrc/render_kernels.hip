@@ -78,7 +78,7 @@ TD Tracer make_tracer ( const DevScene& sc, float4* lds, uint32_t stack_depth, u
     const uint32_t m_words = MODE == 1 ? ( ( sc.n_objects * ( uint32_t ) ( sizeof ( DevMaterial ) / 4 ) + 3u ) & ~3u ) : 0u, l_words = MODE == 1 ? sc.n_lights * 4u : 0u, a_words = MODE == 1 ? ( ( sc.n_tris + 3u ) & ~3u ) : 0u;
     uint32_t* ll = lm + m_words; uint32_t* la = ll + l_words;
     ranked = MODE == 1 && ranked;
-    float4* lr = reinterpret_cast<float4*> ( la + a_words );            // ranked launches: 6 permuted copies of the triangles in rank order (trace_device.h "Ranked launches")
+    float4* lr = reinterpret_cast<float4*> ( la + a_words );            // ranked launches: 6 permuted copies of the triangles in rank order (traverse_ref.h "Ranked launches")
     int* words = reinterpret_cast<int*> ( lr + ( ranked ? 18u * lds_tris : 0u ) );
     T.stack = words + tid;
     T.leaves = words + stack_depth * TERRA_COL + tid;
@@ -90,7 +90,7 @@ TD Tracer make_tracer ( const DevScene& sc, float4* lds, uint32_t stack_depth, u
     const float4* gn = reinterpret_cast<const float4*> ( sc.nodes );
     const float4* gt = reinterpret_cast<const float4*> ( sc.tris );
     const float4* gp = reinterpret_cast<const float4*> ( sc.props );
-    for ( uint32_t i = tid; i < lds_nodes; i += TERRA_COL ) {       // node i -> the axis-major, both-signs layout (trace_device.h "Staged node")
+    for ( uint32_t i = tid; i < lds_nodes; i += TERRA_COL ) {       // node i -> the axis-major, both-signs layout (traverse_ref.h "Staged node")
         const float4 q0 = gn[4 * i], q1 = gn[4 * i + 1], q2 = gn[4 * i + 2], q3 = gn[4 * i + 3];
         const float mn0[3] = { q0.x, q0.y, q0.z }, mx0[3] = { q0.w, q1.x, q1.y }, mn1[3] = { q1.z, q1.w, q2.x }, mx1[3] = { q2.y, q2.z, q2.w };
         float4* o = ln + ( TERRA_LDS_NODE_BYTES / 16 ) * i;
@@ -104,7 +104,7 @@ TD Tracer make_tracer ( const DevScene& sc, float4* lds, uint32_t stack_depth, u
         if ( ! ( c1 & DEV_CHILD_LEAF ) ) c1 *= TERRA_LDS_NODE_BYTES;
         o[6] = make_float4 ( __uint_as_float ( c0 ), __uint_as_float ( c1 ), __uint_as_float ( b0 ), __uint_as_float ( b1 ) );
     }
-    if ( ranked ) {         // copy perm, entry rank: triangle (of that rank) in the axes (kx, ky, kz) of permutation perm = 2 kz + swapped (trace_device.h traverse_ranked)
+    if ( ranked ) {         // copy perm, entry rank: triangle (of that rank) in the axes (kx, ky, kz) of permutation perm = 2 kz + swapped (traverse_ref.h traverse_ranked)
         const DevTri* gtri = reinterpret_cast<const DevTri*> ( gt );
         for ( uint32_t i = tid; i < 6u * lds_tris; i += TERRA_COL ) {
             const uint32_t perm = i / lds_tris, ti = i - perm * lds_tris;
@@ -133,19 +133,21 @@ TD Tracer make_tracer ( const DevScene& sc, float4* lds, uint32_t stack_depth, u
     return T;
 }
 
-// block (in launch order: own tile k, 16x16 block b inside it) and thread -> pixel; a wave covers 8x8 pixels
-TD bool block_pixel ( const DevRenderParams& p, uint32_t blk, uint32_t tid, uint32_t& px, uint32_t& py ) {
-    const uint32_t bpt = p.tile_size >> 4, bpt2 = bpt * bpt;
-    const uint32_t k = blk / bpt2, b = blk - k * bpt2;
-    const uint32_t tiles_x = ( p.w + p.tile_size - 1 ) / p.tile_size;
-    const uint32_t t = p.rank + k * p.world;
-    const uint32_t tx = t % tiles_x, ty = t / tiles_x;
-    const uint32_t bx = b % bpt, by = b / bpt;
+// tile (tx, ty) of the rectangle, 16x16 block (bx, by) inside it and thread -> pixel; a wave covers 8x8 pixels. False: the pixel lies outside the rectangle
+TD bool tile_block_pixel ( const DevRenderParams& p, uint32_t tx, uint32_t ty, uint32_t bx, uint32_t by, uint32_t tid, uint32_t& px, uint32_t& py ) {
     const uint32_t wave = tid >> 6, lane = tid & 63;
     const uint32_t lx = tx * p.tile_size + bx * 16 + ( wave & 1 ) * 8 + ( lane & 7 );
     const uint32_t ly = ty * p.tile_size + by * 16 + ( wave >> 1 ) * 8 + ( lane >> 3 );
     px = p.x + lx; py = p.y + ly;
     return lx < p.w && ly < p.h;
+}
+// block (in launch order: own tile k, 16x16 block b inside it) and thread -> pixel
+TD bool block_pixel ( const DevRenderParams& p, uint32_t blk, uint32_t tid, uint32_t& px, uint32_t& py ) {
+    const uint32_t bpt = p.tile_size >> 4, bpt2 = bpt * bpt;
+    const uint32_t k = blk / bpt2, b = blk - k * bpt2;
+    const uint32_t tiles_x = ( p.w + p.tile_size - 1 ) / p.tile_size;
+    const uint32_t t = p.rank + k * p.world;
+    return tile_block_pixel ( p, t % tiles_x, t / tiles_x, b % bpt, b / bpt, tid, px, py );
 }
 
 #if TERRA_TU_HAS ( 0 )
@@ -253,7 +255,7 @@ __global__ __launch_bounds__ ( 256 ) void terra_resolve_kernel ( DevRenderParams
                                  : TERRA_DECOUPLED ( I, M ) ? TERRA_WAVES_DECOUPLED : ( ( K ) == 1 ? TERRA_WAVES_SIMPLE : TERRA_WAVES_GENERIC ) )
 // ---- pieces shared by the decoupled loops of the kernel below -----------------------------------------
 // Per-lane traversal state that survives leaving the resumable traversal (the stack column and the leaf list are in LDS).
-struct LaneTraversal { RayState st; SlabSel sel; Closest best; uint32_t rank, hand, held; int top; bool traversing, regular, anyhit; };     // anyhit: a light-sample ray that knows its triangle (trace_device.h fast_expect)     // hand: MODE >= 2, what the lane holds between calls (trace_device.h traverse_fast_resume)     // regular: MODE 0 / 1 the ray's slab variant; MODE 2 (which has no use for that) "second, checked pass" of the reachability mode     // top: entries on the lane's stack (its leaf list is always empty between calls)
+struct LaneTraversal { RayState st; SlabSel sel; Closest best; uint32_t rank, hand, held; int top; bool traversing, regular, anyhit; };     // anyhit: a light-sample ray that knows its triangle (traverse_fast.h fast_expect)     // hand: MODE >= 2, what the lane holds between calls (traverse_fast.h traverse_fast_resume)     // regular: MODE 0 / 1 the ray's slab variant; MODE 2 (which has no use for that) "second, checked pass" of the reachability mode     // top: entries on the lane's stack (its leaf list is always empty between calls)
 TD LaneTraversal lane_traversal_idle ( const Tracer& T, const Ray& any_ray ) {
     LaneTraversal t; t.st = ray_state_init ( any_ray ); t.sel = slab_sel ( any_ray ); t.best.depth = FLT_MAX; t.best.tri = 0xffffffffu; t.rank = 0xffffffffu; t.hand = DEV_CHILD_EMPTY; t.held = 0u; t.top = 0; t.anyhit = false; t.traversing = false; t.regular = true;
     return t;
@@ -271,12 +273,12 @@ TD void lane_traversal_start ( const Tracer& T, const Ray& ray, LaneTraversal& t
     t.traversing = true;
     if ( COUNT ) ++c.rays;
 }
-// the ray just started is a light-sample ray towards triangle `expected` (soup index): trace_device.h fast_expect. (A ray that misses its triangle stays an ordinary ray.)
+// the ray just started is a light-sample ray towards triangle `expected` (soup index): traverse_fast.h fast_expect. (A ray that misses its triangle stays an ordinary ray.)
 template <int COUNT, int MODE>
 TD void lane_traversal_expect ( const Tracer& T, const Ray& ray, LaneTraversal& t, uint32_t expected ) {
     if constexpr ( TERRA_SHADOW_ANYHIT && MODE == 2 && COUNT == 0 ) {
         Ray r = ray; r.o = r.o + r.d * 0.001f;
-        const V3 o_perm = v3 ( pick ( r.o, t.st.ix ), pick ( r.o, t.st.iy ), pick ( r.o, t.st.iz ) );
+        const V3 o_perm = permuted ( r.o, t.st );
         ClosestRanked b2; b2.depth = t.best.depth; b2.rank = t.rank; b2.tri = t.best.tri;
         t.anyhit = fast_expect ( T, t.st, o_perm, expected, b2 );
         t.best.depth = b2.depth; t.best.tri = b2.tri; t.rank = b2.rank;
@@ -284,7 +286,7 @@ TD void lane_traversal_expect ( const Tracer& T, const Ray& ray, LaneTraversal& 
     }
 }
 // DevScene::reach (scenes outside the coordinate range of the containment proof, MODE 2): a returned closest hit stands if the reference traversal would have
-// reached it; if not -- very rare -- the same ray goes back in flight with every candidate checked (trace_device.h bvh_traverse_fast). True = the lane is traversing again.
+// reached it; if not -- very rare -- the same ray goes back in flight with every candidate checked (traverse_fast.h bvh_traverse_fast). True = the lane is traversing again.
 template <int MODE>
 TD bool lane_traversal_recheck ( const Tracer& T, const Ray& ray, LaneTraversal& t ) {
     if ( MODE != 3 || !T.sc.reach || !t.regular || t.best.tri == 0xffffffffu ) return false;      // (MODE 2: regular == false marks the checked pass)
@@ -303,7 +305,7 @@ TD bool lane_traversal_run ( const Tracer& T, const Ray& ray, LaneTraversal& t, 
     int quota = MODE >= 2 ? ( n_trav * TERRA_FAST_EXIT_16THS ) >> 4 : n_trav >> TERRA_DECOUPLED_EXIT_SHIFT; if ( quota < 1 ) quota = 1;
     const int exit_active = n_trav - quota;
     Ray r = ray; r.o = r.o + r.d * 0.001f;
-    V3 o_perm = v3 ( pick ( r.o, t.st.ix ), pick ( r.o, t.st.iy ), pick ( r.o, t.st.iz ) );
+    V3 o_perm = permuted ( r.o, t.st );
     int* sp = T.stack + t.top * TERRA_COL;
     if constexpr ( MODE >= 2 ) {
         ClosestRanked b2; b2.depth = t.best.depth; b2.rank = t.rank; b2.tri = t.best.tri;
@@ -381,11 +383,7 @@ TD bool job_pixel_of_block ( const DevRenderParams& p, uint32_t blk, uint32_t ti
     const uint32_t t = p.rank + k * p.world;
     const uint32_t ty = magic_div ( t, p.job_div_tiles_x ), tx = t - ty * p.job_tiles_x;
     const uint32_t by = magic_div ( b, p.job_div_bpt ), bx = b - by * bpt;
-    const uint32_t wave = tid >> 6, lane = tid & 63;
-    const uint32_t lx = tx * p.tile_size + bx * 16 + ( wave & 1 ) * 8 + ( lane & 7 );
-    const uint32_t ly = ty * p.tile_size + by * 16 + ( wave >> 1 ) * 8 + ( lane >> 3 );
-    px = p.x + lx; py = p.y + ly;
-    return lx < p.w && ly < p.h;
+    return tile_block_pixel ( p, tx, ty, bx, by, tid, px, py );
 }
 // aux: the lane's parked words (TERRA_AUX_WORDS rows of 256): [0], [256], [512] the job's radiance sum; [768] the job; [1024] the lane's draw count at the job's
 // start; row 5 holds, per wave, the pool {next job, end} at [1280 + 64 * wave + 0 / 1] relative to thread 0's column
@@ -528,9 +526,9 @@ __global__ __launch_bounds__ ( 256, TERRA_WAVES_FOR ( INTEGRATOR, KINDS, MODE ) 
                         V3 wo = neg ( ray.d );
                         Ray ray_a;
                         pend = mis_prepare<COUNT, KINDS, MODE> ( T, sf, point, wo, throughput, bounce, rs.b, c, ray_a, b_d );
-                        b_o = point + sf.normal * 0.0001f;        // surface_ray ( sf, point, bsdf_dir, 1.f ) without the divisions
+                        b_o = surface_origin ( sf, point );        // surface_ray ( sf, point, bsdf_dir ) without the divisions
                         cont = path_continue<COUNT, KINDS> ( T.sc, sf, wo, throughput, bounce, p.bounces, rs.b, c, cont_d, sp );
-                        cont_o = point + sf.normal * 0.0001f;     // (the divisions of surface_ray are redone when the ray starts)
+                        cont_o = surface_origin ( sf, point );     // (the divisions of surface_ray are redone when the ray starts)
                         ro = ray_a.o; rd = ray_a.d; job = 1; start = true;
                     } else {
                         if ( ( KINDS & TERRA_KIND_ENV ) && T.sc.env_mode ) { throughput = had ( throughput, environment_eval ( T.sc, ray.d ) ); Lo = Lo + throughput; }
@@ -582,7 +580,7 @@ __global__ __launch_bounds__ ( 256, TERRA_WAVES_FOR ( INTEGRATOR, KINDS, MODE ) 
                         Ray shadow_ray;
                         pend = direct_prepare<COUNT, KINDS, MODE> ( T, sf, point, wo, throughput, bounce, rs.b, c, shadow_ray );
                         cont = path_continue<COUNT, KINDS> ( T.sc, sf, wo, throughput, bounce, p.bounces, rs.b, c, cont_d, sp );
-                        cont_o = point + sf.normal * 0.0001f;     // surface_ray ( sf, point, wi, 1.f ) without the divisions: they are taken when the ray starts
+                        cont_o = surface_origin ( sf, point );     // surface_ray ( sf, point, wi ) without the divisions: they are taken when the ray starts
                         ro = shadow_ray.o; rd = shadow_ray.d; shadow = true; start = true;
                     } else {
                         if ( ( KINDS & TERRA_KIND_ENV ) && T.sc.env_mode ) { throughput = had ( throughput, environment_eval ( T.sc, ray.d ) ); Lo = Lo + throughput; }
@@ -626,7 +624,7 @@ __global__ __launch_bounds__ ( 256, TERRA_WAVES_FOR ( INTEGRATOR, KINDS, MODE ) 
                         V3 wo = neg ( ray.d ), wi;
                         Lo = Lo + integrate<INTEGRATOR, COUNT, MODE, KINDS> ( T, ray, sf, point, wo, throughput, bounce, rs.b, c );
                         next = path_continue<KINDS> ( sf, wo, throughput, bounce, p.bounces, pd, wi );
-                        if ( next ) { ro = point + sf.normal * 0.0001f; rd = wi; }       // surface_ray ( sf, point, wi, 1.f ); its reciprocals are taken below
+                        if ( next ) { ro = surface_origin ( sf, point ); rd = wi; }       // surface_ray ( sf, point, wi ); its reciprocals are taken below
                     } else if ( ( KINDS & TERRA_KIND_ENV ) && T.sc.env_mode ) {
                         throughput = had ( throughput, environment_eval ( T.sc, ray.d ) );
                         Lo = Lo + throughput;
@@ -708,7 +706,7 @@ __global__ __launch_bounds__ ( 256, TERRA_WAVES_FOR ( INTEGRATOR, KINDS, MODE ) 
                     const DirectPending pend = direct_prepare<COUNT, KINDS, MODE> ( T, sf, h.point, wo, throughput, bounce, rs.b, c, shadow_ray );
                     pd = path_draw<COUNT> ( T.sc.sincos24, rs.b, c );
                     end = !path_continue<KINDS> ( sf, wo, throughput, bounce, p.bounces, pd, wi );
-                    if ( !end ) { ro = h.point + sf.normal * 0.0001f; rd = wi; }
+                    if ( !end ) { ro = surface_origin ( sf, h.point ); rd = wi; }
                     const uint32_t tri = scene_raycast_triangle<COUNT, MODE> ( T, shadow_ray, c, pend.expected );
                     lo_add ( tri == pend.expected ? pend.vis : pend.hid );
                 } else if constexpr ( TERRA_COUPLED_MIS_SPLIT && INTEGRATOR == 2 && ( KINDS & ( TERRA_KIND_TEX | TERRA_KIND_SAMPLER ) ) == 0 ) {
@@ -716,7 +714,7 @@ __global__ __launch_bounds__ ( 256, TERRA_WAVES_FOR ( INTEGRATOR, KINDS, MODE ) 
                     // name the triangle it hits; B, the BSDF-sampled ray, needs the surface it hits
                     Ray ray_a; V3 b_d;
                     const MisPending pend = mis_prepare<COUNT, KINDS, MODE> ( T, sf, h.point, wo, throughput, bounce, rs.b, c, ray_a, b_d );
-                    const V3 next_o = h.point + sf.normal * 0.0001f;          // surface_ray ( sf, h.point, direction, 1.f ) for B and for the continuation alike
+                    const V3 next_o = surface_origin ( sf, h.point );          // surface_ray ( sf, h.point, direction ) for B and for the continuation alike
                     end = !path_continue<COUNT, KINDS> ( T.sc, sf, wo, throughput, bounce, p.bounces, rs.b, c, wi, sp );
                     if ( !end ) { ro = next_o; rd = wi; }
                     const uint32_t tri_a = scene_raycast_triangle<COUNT, MODE> ( T, ray_a, c, pend.expected );
@@ -729,7 +727,7 @@ __global__ __launch_bounds__ ( 256, TERRA_WAVES_FOR ( INTEGRATOR, KINDS, MODE ) 
                 if ( !pre_draw ) pd = path_draw<COUNT> ( T.sc.sincos24, rs.b, c );
                 if constexpr ( ( KINDS & TERRA_KIND_SAMPLER ) != 0 ) path_apply_sampler ( pd, sp, bounce );
                 end = !path_continue<KINDS> ( sf, wo, throughput, bounce, p.bounces, pd, wi );
-                if ( !end ) { ro = h.point + sf.normal * 0.0001f; rd = wi; }      // surface_ray ( sf, h.point, wi, 1.f ): its make_ray is the one at the top of this block
+                if ( !end ) { ro = surface_origin ( sf, h.point ); rd = wi; }      // surface_ray ( sf, h.point, wi ): its make_ray is the one at the top of this block
                 }
             } else if ( ( KINDS & TERRA_KIND_ENV ) && T.sc.env_mode && !env_reaches_by_samples<INTEGRATOR, KINDS> ( T.sc, bounce ) ) {     // extension: the reference's commented-out "Lo += throughput" (src/Terra.c:1056)
                 throughput = had ( throughput, environment_eval ( T.sc, ray.d ) );
@@ -773,7 +771,7 @@ size_t terra_lds_bytes ( const DevRenderParams& p ) {
 }
 // fast tree (MODE 2 / 3): nothing is staged. A lane holds at most two leaves (in registers: the one it tests, the next one), so there is no leaf list. The stack: its first TERRA_FAST_STACK_LDS entries
 // in LDS (1 KB per entry and block), the rest -- up to the tree's worst case, which a ray almost never reaches -- in HBM, 4 bytes per entry and resident lane
-// (DevRenderParams::stack_spill, part of the launch's scratch: trace_device.h fast_push / fast_pop). Depth no longer decides whether a tree can be launched.
+// (DevRenderParams::stack_spill, part of the launch's scratch: traverse_fast.h fast_push / fast_pop). Depth no longer decides whether a tree can be launched.
 // (Rounds 2-3 staged the first 64 nodes as plain 64-byte nodes read through a flat load: +3.7 % then. Flat loads go through the texture addresser like global ones,
 // and that unit is what binds these kernels: nothing is gained by it now.)
 #ifndef TERRA_FAST_STACK_LDS
@@ -829,7 +827,7 @@ void terra_plan_lds ( DevRenderParams& p ) {
     p.leaf_cap = TERRA_LEAF_CAP_MAX; p.leaf_rank = 0;
     if ( const uint32_t cap = resident_leaf_cap ( p.scene.n_nodes, p.scene.n_tris, p.scene.max_stack, p.scene.n_objects, p.scene.n_lights ) ) {
         p.lds_mode = 1; p.lds_nodes = p.scene.n_nodes; p.lds_tris = p.scene.n_tris; p.leaf_cap = cap;
-        // at most TERRA_LEAF_RANK_MAX triangles: the leaf list gives way to the rank set and the permuted copies (trace_device.h "Ranked launches") if they
+        // at most TERRA_LEAF_RANK_MAX triangles: the leaf list gives way to the rank set and the permuted copies (traverse_ref.h "Ranked launches") if they
         // take no more LDS than the list did -- on the Cornell box 6 x 32 x 48 B = 9 KB in place of the list's 13 KB
         if ( p.scene.n_tris <= TERRA_LEAF_RANK_MAX && ( size_t ) p.scene.n_tris * 6 * 48 <= ( size_t ) cap * 1024 ) { p.leaf_rank = 1; p.leaf_cap = 0; }
         return;
@@ -999,9 +997,9 @@ __global__ __launch_bounds__ ( 256 ) void terra_block_class_kernel ( DevRenderPa
             r.o = r.o + r.d * 0.001f;
             const RayState st = ray_state_init ( r );
             for ( uint32_t t = 0; t < p.scene.n_tris && !hit; ++t ) {
-                const float4 a = tris[3 * t], bb = tris[3 * t + 1], cc = tris[3 * t + 2];
+                V3 ta, tb, tc; tri_vertices ( tris, t, ta, tb, tc );
                 TriHit h;
-                hit = watertight ( r, st, v3 ( a.x, a.y, a.z ), v3 ( bb.x, bb.y, bb.z ), v3 ( cc.x, cc.y, cc.z ), h );
+                hit = watertight ( r, st, ta, tb, tc, h );
             }
         }
     }

@@ -126,7 +126,7 @@ extern "C" void  terra_free ( void* p ) { free ( p ); }
 extern "C" void  terra_log ( const char* str, ... ) { va_list a; va_start ( a, str ); vfprintf ( stdout, str, a ); va_end ( a ); }
 
 // ------------------------------------------------------------------------------
-// preset markers. The device BSDFs live in trace_device.h; these host symbols only
+// preset markers. The device BSDFs live in shading_device.h; these host symbols only
 // identify a preset. Calling them is an error: no CPU shading here.
 // ------------------------------------------------------------------------------
 static TerraFloat3 host_call_refused ( const char* what ) {
@@ -176,7 +176,7 @@ extern "C" bool terra_texture_init_hdr ( TerraTexture* t, size_t w, size_t h, si
     t->width = ( uint16_t ) w; t->height = ( uint16_t ) h; t->components = ( uint8_t ) comps; t->depth = 4;
     return true;
 }
-// the lookups as the device runs them (trace_device.h texture_read / texture_sample; the rules where the reference is undefined: DESIGN.md 2a)
+// the lookups as the device runs them (shading_device.h texture_read / texture_sample; the rules where the reference is undefined: DESIGN.md 2a)
 static float texture_coord ( float u ) { return u > -1.f ? std::min ( u, 4294967040.f ) : 0.f; }
 extern "C" TerraFloat3 terra_texture_read ( TerraTexture* t, size_t x, size_t y ) {
     TerraFloat3 out = { 0.f, 0.f, 0.f };
@@ -651,7 +651,7 @@ static std::vector<uint32_t> leaf_ranks ( const Scene* s ) {
 //   (2) L >= 1 and the box contains the box of level L - 1 component by component: for a regular ray (finite, non-zero inverse direction) fl((b - o) * inv) is
 //       monotone in b, so per axis the outer box's [near, far] contains the inner box's in the very same float arithmetic, hence tmin_outer <= tmin_inner,
 //       tmax_outer >= tmax_inner and "inner passes" implies "outer passes" exactly -- no error bound involved. Level L - 1 itself passes by induction (tested, or
-//       cleared). Irregular rays ignore the mask and replay every level (trace_device.h reference_reaches).
+//       cleared). Irregular rays ignore the mask and replay every level (traverse_fast.h reference_reaches).
 struct ReachTables { std::vector<DevReplay> replay; std::vector<uint32_t> leaf_parent, leaf_mask; uint64_t levels = 0, replayed = 0; };
 static void build_reach_tables ( const std::vector<DevNode>& nodes, const std::vector<DevTri>& tris, const std::vector<uint32_t>& soup_of_fast, float margin, ReachTables& out ) {
     const size_t nn = nodes.size(), nt = soup_of_fast.size();
@@ -854,8 +854,8 @@ static int flatten ( Scene* s, Flat& f ) {
         }
     }
     // rank of every soup triangle in the reference traversal's leaf visit order (all boxes hit). The soup carries the ranks in DevTri::pad: a light-sample ray of the
-    // fast tree tests its triangle before it traverses (trace_device.h fast_expect), and LDS-resident launches of at most TERRA_LEAF_RANK_MAX triangles stage the
-    // triangles in rank order and collect a ray's leaves as a set of ranks (make_tracer, trace_device.h traverse_ranked)
+    // fast tree tests its triangle before it traverses (traverse_fast.h fast_expect), and LDS-resident launches of at most TERRA_LEAF_RANK_MAX triangles stage the
+    // triangles in rank order and collect a ray's leaves as a set of ranks (make_tracer, traverse_ref.h traverse_ranked)
     f.rank = leaf_ranks ( s );
     for ( size_t k = 0; k < ntri; ++k ) f.tris[k].pad = f.rank[k];
     return 0;
@@ -882,7 +882,7 @@ static TreeChoice choose_tree ( const Scene* s, size_t ntri ) {
     // Outside the range the reference's own slab test can numerically miss a box whose triangle the watertight test would hit, so the containment
     // shortcut is gone -- but not the fast tree: with its boxes inflated to the rounding bound it still finds every triangle the watertight test accepts,
     // and a hit stands only if the reference traversal would have reached it (its inner ancestors' slab tests, replayed exactly: for the closest of all hits first, and only
-    // if that one fails -- float rounding makes it very rare -- for every candidate of a second pass; trace_device.h bvh_traverse_fast). Rays may start
+    // if that one fails -- float rounding makes it very rare -- for every candidate of a second pass; traverse_fast.h bvh_traverse_fast). Rays may start
     // up to TERRA_REACH_CAMERA_FACTOR x the scene's largest coordinate from the origin (the camera, checked per call); margin = 128 u x that limit.
     // LDS-resident scenes out of range keep the reference tree and its exact traversal of the inner nodes; their LEAF boxes -- which the reference never tests -- are rebuilt
     // around the triangle's extent with that same margin, so the leaf-box cull only skips triangle tests that cannot succeed: no replay needed (reach_cull).
@@ -1287,7 +1287,7 @@ extern "C" int terra_amd_get_stats ( HTerraScene h, TerraAmdStats* out ) {
     if ( int rc = sum_counters ( s, 0, kCtrCount, c ) ) return rc;
     out->rays = c[kCtrRays]; out->nodes = c[kCtrNodes]; out->tri_tests = c[kCtrTriTests]; out->hits = c[kCtrHits];
     out->rand_calls = c[kCtrRandCalls]; out->attr_fetches = c[kCtrAttrFetches]; out->tri_culled = c[kCtrTriCulled];
-    // derived exactly on the host (see Counters in trace_device.h)
+    // derived exactly on the host (see Counters in traverse_ref.h)
     out->box_tests = primary ( s ).dev.n_tris >= 2 ? ( s->tree.use_fast ? 4 * out->nodes : s->tree.cull_ok ? 2 * out->nodes : 2 * out->nodes - out->tri_tests ) : 0;      // the fast tree's nodes hold four boxes; with the leaf-box cull every child's slab test is used
     out->samples = s->stat_samples; out->pixels = s->stat_pixels; out->launches = s->launches;
     return 0;
@@ -1702,7 +1702,9 @@ static void* slot_scratch ( ThreadSlot* slot, size_t bytes ) {
     if ( slot->scratch_bytes < bytes ) {
         if ( slot->d_scratch ) { ( void ) hipStreamSynchronize ( slot->stream ); ( void ) hipFree ( slot->d_scratch ); slot->d_scratch = nullptr; slot->scratch_bytes = 0; }
         if ( hipMalloc ( &slot->d_scratch, bytes ) != hipSuccess ) { ( void ) hipGetLastError(); slot->d_scratch = nullptr; return nullptr; }      // (the pool then)
-        if ( hipMemset ( slot->d_scratch, 0, 256 ) != hipSuccess ) { ( void ) hipGetLastError(); ( void ) hipFree ( slot->d_scratch ); slot->d_scratch = nullptr; return nullptr; }
+        // (on the slot's own stream, ahead of the launch that reads the word: the stream is non-blocking, so a hipMemset on the null stream is not ordered with it and
+        //  the render kernel could start on whatever the fresh allocation held -- a queue that looks part drained, pixel blocks never rendered)
+        if ( hipMemsetAsync ( slot->d_scratch, 0, 256, slot->stream ) != hipSuccess ) { ( void ) hipGetLastError(); ( void ) hipFree ( slot->d_scratch ); slot->d_scratch = nullptr; return nullptr; }
         slot->scratch_bytes = bytes;
     }
     return slot->d_scratch;
@@ -2029,7 +2031,7 @@ extern "C" int terra_amd_unit_distribution_2d_pdf ( const float* f, size_t nx, s
     return u.finish ( u.ok ? terra_unit_distribution_2d_pdf ( df, ( uint32_t ) nx, ( uint32_t ) ny, dc, di, dmc, dm, dxy, m, dp ) : hipSuccess );
 }
 
-// ---- the texture lookups (trace_device.h texture_sample, environment_eval's lat-long lookup) on one texture, which reaches the device the way a scene's
+// ---- the texture lookups (shading_device.h texture_sample, environment_eval's lat-long lookup) on one texture, which reaches the device the way a scene's
 // textures do: layout_textures (section size with its padding, 256-byte placement, descriptor) and new_blob (zeroed allocation, upload, descriptor's address)
 static int unit_texture ( const TerraTexture* t, int n, const float* in, int in_width, float* out3, hipError_t ( *launch ) ( const DevTexture*, int, const float*, float* ) ) {
     if ( need_device() ) return kTerraAmdErrNoDevice;

@@ -1,0 +1,220 @@
+// trace_geometry.h -- rays against boxes and triangles (trace_device.h lists the layers): the camera sample, the slab tests in their
+// four forms, the watertight test in its two forms and the Moeller-Trumbore test.
+#pragma once
+#include "trace_math.h"
+
+// -----------------------------------------------------------------------------
+// camera
+// -----------------------------------------------------------------------------
+TD V3 camera_sample ( const DevRenderParams& p, uint32_t px, uint32_t py, float r1, float r2 ) {
+    float dx = -p.jitter + 2 * r1 * p.jitter;
+    float dy = -p.jitter + 2 * r2 * p.jitter;
+    float ndc_x = ( ( float ) px + 0.5f + dx ) / ( float ) p.fb_w;
+    float ndc_y = ( ( float ) py + 0.5f + dy ) / ( float ) p.fb_h;
+    float sx = 2 * ndc_x - 1;
+    float sy = 1 - 2 * ndc_y;
+    float fx = sx * p.aspect * p.tan_half_fov;
+    float fy = sy * p.tan_half_fov;
+    V3 d = normalize ( v3 ( fx, fy, 1.f ) );
+    return v3 ( p.cam_rot[0] * d.x + p.cam_rot[1] * d.y + p.cam_rot[2] * d.z,
+                p.cam_rot[3] * d.x + p.cam_rot[4] * d.y + p.cam_rot[5] * d.z,
+                p.cam_rot[6] * d.x + p.cam_rot[7] * d.y + p.cam_rot[8] * d.z );
+}
+
+// -----------------------------------------------------------------------------
+// slab test
+// -----------------------------------------------------------------------------
+TD bool ray_aabb ( const Ray& r, V3 bmin, V3 bmax, float* tmin_out, float* tmax_out ) {
+    float t1 = ( bmin.x - r.o.x ) * r.inv.x;
+    float t2 = ( bmax.x - r.o.x ) * r.inv.x;
+    float tmin = sel_min ( t1, t2 ), tmax = sel_max ( t1, t2 );
+    t1 = ( bmin.y - r.o.y ) * r.inv.y;
+    t2 = ( bmax.y - r.o.y ) * r.inv.y;
+    tmin = sel_max ( tmin, sel_min ( t1, t2 ) ); tmax = sel_min ( tmax, sel_max ( t1, t2 ) );
+    t1 = ( bmin.z - r.o.z ) * r.inv.z;
+    t2 = ( bmax.z - r.o.z ) * r.inv.z;
+    tmin = sel_max ( tmin, sel_min ( t1, t2 ) ); tmax = sel_min ( tmax, sel_max ( t1, t2 ) );
+    bool hit = tmax > sel_max ( tmin, 0.f );
+    if ( tmin_out ) *tmin_out = tmin;
+    if ( tmax_out ) *tmax_out = tmax;
+    return hit;
+}
+
+// -----------------------------------------------------------------------------
+// slab test of one child box. FAST is legal when every component of the ray's
+// inverse direction is finite and non-zero: then no NaN can appear (boxes and
+// origins are finite) and "a<b?a:b" differs from v_min_f32 only in the sign of a
+// zero, which the final comparison cannot see. Otherwise the compare-select form of
+// the reference runs (NaN order matters there).
+// -----------------------------------------------------------------------------
+template <bool FAST>
+TD bool slab ( V3 bmin, V3 bmax, const Ray& r ) {
+    float t1x = ( bmin.x - r.o.x ) * r.inv.x, t2x = ( bmax.x - r.o.x ) * r.inv.x;
+    float t1y = ( bmin.y - r.o.y ) * r.inv.y, t2y = ( bmax.y - r.o.y ) * r.inv.y;
+    float t1z = ( bmin.z - r.o.z ) * r.inv.z, t2z = ( bmax.z - r.o.z ) * r.inv.z;
+    if ( FAST ) {
+        float tmin = __builtin_fmaxf ( __builtin_fmaxf ( __builtin_fminf ( t1x, t2x ), __builtin_fminf ( t1y, t2y ) ), __builtin_fminf ( t1z, t2z ) );
+        float tmax = __builtin_fminf ( __builtin_fminf ( __builtin_fmaxf ( t1x, t2x ), __builtin_fmaxf ( t1y, t2y ) ), __builtin_fmaxf ( t1z, t2z ) );
+        return tmax > __builtin_fmaxf ( tmin, 0.f );
+    }
+    float tmin = sel_min ( t1x, t2x ), tmax = sel_max ( t1x, t2x );
+    tmin = sel_max ( tmin, sel_min ( t1y, t2y ) ); tmax = sel_min ( tmax, sel_max ( t1y, t2y ) );
+    tmin = sel_max ( tmin, sel_min ( t1z, t2z ) ); tmax = sel_min ( tmax, sel_max ( t1z, t2z ) );
+    return tmax > sel_max ( tmin, 0.f );
+}
+
+TD bool ray_is_regular ( const Ray& r ) {
+    // finite and non-zero inverse direction components
+    uint32_t ax = tdm_bits ( r.inv.x ) & 0x7fffffffu, ay = tdm_bits ( r.inv.y ) & 0x7fffffffu, az = tdm_bits ( r.inv.z ) & 0x7fffffffu;
+    return ax - 1u < 0x7f7fffffu && ay - 1u < 0x7f7fffffu && az - 1u < 0x7f7fffffu;
+}
+
+// regular AND every |inverse direction component| below 2^96: origin * inv cannot overflow for any origin the containment check admits
+TD bool ray_is_tame ( const Ray& r ) {
+    uint32_t ax = tdm_bits ( r.inv.x ) & 0x7fffffffu, ay = tdm_bits ( r.inv.y ) & 0x7fffffffu, az = tdm_bits ( r.inv.z ) & 0x7fffffffu;
+    return ax - 1u < 0x6f7fffffu && ay - 1u < 0x6f7fffffu && az - 1u < 0x6f7fffffu;
+}
+// slab test from (near, far) planes per axis: what slab<true> computes, without the per-axis min / max
+TD bool slab_near_far ( float nx, float fx, float ny, float fy, float nz, float fz, const Ray& r ) {
+    float tnx = ( nx - r.o.x ) * r.inv.x, tfx = ( fx - r.o.x ) * r.inv.x;
+    float tny = ( ny - r.o.y ) * r.inv.y, tfy = ( fy - r.o.y ) * r.inv.y;
+    float tnz = ( nz - r.o.z ) * r.inv.z, tfz = ( fz - r.o.z ) * r.inv.z;
+    float tmin = __builtin_fmaxf ( __builtin_fmaxf ( tnx, tny ), tnz );
+    float tmax = __builtin_fminf ( __builtin_fminf ( tfx, tfy ), tfz );
+    return tmax > __builtin_fmaxf ( tmin, 0.f );
+}
+
+// The same test with t = fma ( plane, inv, -(o * inv) ): one instruction per plane instead of two. NOT the reference's arithmetic -- (plane - o) * inv -- so only the
+// launches that need not reproduce the reference's traversal decision by decision may use it: the leaf-box-cull launches (Tracer::cull), whose commit-time proof
+// (scene_host.cpp "numeric containment check") only asks that every box test be CONSERVATIVE within the error budget: a triangle the ray hits must pass the test of
+// every box built around it. Here t carries two roundings -- of o * inv and of the fma -- worth u |o| + u |plane - o| in position, less than the three roundings of
+// the reference form the budget was drawn up for. Which nodes are visited beyond that may differ from the replica's by a few per billion (never the image).
+TD bool slab_near_far_fused ( float nx, float fx, float ny, float fy, float nz, float fz, const Ray& r, V3 oi, float& t_enter ) {
+    float tnx = __builtin_fmaf ( nx, r.inv.x, -oi.x ), tfx = __builtin_fmaf ( fx, r.inv.x, -oi.x );
+    float tny = __builtin_fmaf ( ny, r.inv.y, -oi.y ), tfy = __builtin_fmaf ( fy, r.inv.y, -oi.y );
+    float tnz = __builtin_fmaf ( nz, r.inv.z, -oi.z ), tfz = __builtin_fmaf ( fz, r.inv.z, -oi.z );
+    float tmin = __builtin_fmaxf ( __builtin_fmaxf ( tnx, tny ), tnz );
+    float tmax = __builtin_fminf ( __builtin_fminf ( tfx, tfy ), tfz );
+    t_enter = __builtin_fmaxf ( tmin, 0.f );
+    return tmax > t_enter;
+}
+
+// -----------------------------------------------------------------------------
+// watertight ray/triangle
+// -----------------------------------------------------------------------------
+TD RayState ray_state_init ( const Ray& r ) {
+    float ax = fabsf ( r.d.x ), ay = fabsf ( r.d.y ), az = fabsf ( r.d.z );
+    int iz = ax > ay ? ( ax > az ? 0 : 2 ) : ( ay > az ? 1 : 2 );   // ties -> later axis
+    int ix = iz + 1 == 3 ? 0 : iz + 1;
+    int iy = ix + 1 == 3 ? 0 : ix + 1;
+    if ( pick ( r.d, iz ) < 0.f ) { int t = ix; ix = iy; iy = t; }
+    RayState s;
+    s.scalez = pick ( r.inv, iz );          // 1.f / d[iz] (src/TerraGeometry.c:124): the quotient make_ray already holds, same operands, same rounding
+    s.shearx = pick ( r.d, ix ) * s.scalez;
+    s.sheary = pick ( r.d, iy ) * s.scalez;
+    s.ix = ix; s.iy = iy; s.iz = iz;
+    return s;
+}
+
+// the three vertices of a triangle record (three float4; the w components carry object, triangle in object, pad / rank)
+TD void tri_vertices ( float4 t0, float4 t1, float4 t2, V3& a, V3& b, V3& c ) { a = v3 ( t0.x, t0.y, t0.z ); b = v3 ( t1.x, t1.y, t1.z ); c = v3 ( t2.x, t2.y, t2.z ); }
+TD void tri_vertices ( const float4* tris, uint32_t i, V3& a, V3& b, V3& c ) { tri_vertices ( tris[3 * i], tris[3 * i + 1], tris[3 * i + 2], a, b, c ); }
+
+// A triangle in the ray's permuted axes: a[0..2] = vertex a [ix], [iy], [iz], likewise b and c. Two loaders: from the 12-float record the block
+// staged in LDS (a.xyz object | b.xyz triangle-in-object | c.xyz pad), which reads the components it needs by index, and from the record's three
+// float4 out of global memory, which selects them in registers.
+struct TriPerm { float a[3], b[3], c[3]; };
+TD TriPerm tri_perm_lds ( const float* t, const RayState& s ) {
+    TriPerm p;
+    p.a[0] = t[s.ix]; p.a[1] = t[s.iy]; p.a[2] = t[s.iz];
+    p.b[0] = t[4 + s.ix]; p.b[1] = t[4 + s.iy]; p.b[2] = t[4 + s.iz];
+    p.c[0] = t[8 + s.ix]; p.c[1] = t[8 + s.iy]; p.c[2] = t[8 + s.iz];
+    return p;
+}
+TD TriPerm tri_perm ( float4 t0, float4 t1, float4 t2, const RayState& s ) {
+    const V3 va = v3 ( t0.x, t0.y, t0.z ), vb = v3 ( t1.x, t1.y, t1.z ), vc = v3 ( t2.x, t2.y, t2.z );
+    TriPerm p;
+    p.a[0] = pick ( va, s.ix ); p.a[1] = pick ( va, s.iy ); p.a[2] = pick ( va, s.iz );
+    p.b[0] = pick ( vb, s.ix ); p.b[1] = pick ( vb, s.iy ); p.b[2] = pick ( vb, s.iz );
+    p.c[0] = pick ( vc, s.ix ); p.c[1] = pick ( vc, s.iy ); p.c[2] = pick ( vc, s.iz );
+    return p;
+}
+
+struct TriHit { float u, v, w, depth; V3 point; };
+
+TD bool watertight ( const Ray& r, const RayState& s, V3 ta, V3 tb, V3 tc, TriHit& h ) {
+    V3 A = ta - r.o, B = tb - r.o, C = tc - r.o;
+    float Aiz = pick ( A, s.iz ), Biz = pick ( B, s.iz ), Ciz = pick ( C, s.iz );
+    float Ax = pick ( A, s.ix ) - s.shearx * Aiz, Ay = pick ( A, s.iy ) - s.sheary * Aiz;
+    float Bx = pick ( B, s.ix ) - s.shearx * Biz, By = pick ( B, s.iy ) - s.sheary * Biz;
+    float Cx = pick ( C, s.ix ) - s.shearx * Ciz, Cy = pick ( C, s.iy ) - s.sheary * Ciz;
+    float U = Cx * By - Cy * Bx;
+    float V = Ax * Cy - Ay * Cx;
+    float W = Bx * Ay - By * Ax;
+    if ( U == 0.f || V == 0.f || W == 0.f ) {
+        U = ( float ) ( ( double ) Cx * ( double ) By - ( double ) Cy * ( double ) Bx );
+        V = ( float ) ( ( double ) Ax * ( double ) Cy - ( double ) Ay * ( double ) Cx );
+        W = ( float ) ( ( double ) Bx * ( double ) Ay - ( double ) By * ( double ) Ax );
+    }
+    uint32_t sign = tdm_bits ( U ) & 0x80000000u;
+    if ( ( ( tdm_bits ( V ) ^ tdm_bits ( U ) ) | ( tdm_bits ( W ) ^ tdm_bits ( U ) ) ) & 0x80000000u ) return false;
+    float det = U + V + W;
+    if ( det == 0.f ) return false;
+    float Az = s.scalez * Aiz, Bz = s.scalez * Biz, Cz = s.scalez * Ciz;
+    float depth = U * Az + V * Bz + W * Cz;
+    if ( tdm_float ( tdm_bits ( depth ) ^ sign ) < 0.f ) return false;
+    float inv_det = 1.f / det;
+    h.u = U * inv_det; h.v = V * inv_det; h.w = W * inv_det;
+    h.depth = depth * inv_det;
+    h.point = r.o + r.d * h.depth;
+    return true;
+}
+
+// -----------------------------------------------------------------------------
+// watertight test on components already gathered in the ray's permuted axes
+// (TriPerm); o = origin permuted the same way.
+// Same operations, in the same order, as watertight() above.
+// -----------------------------------------------------------------------------
+TD bool watertight_permuted ( const TriPerm& t, V3 o, const RayState& s, float& depth_out ) {
+    float Aix = t.a[0] - o.x, Aiy = t.a[1] - o.y, Aiz = t.a[2] - o.z;
+    float Bix = t.b[0] - o.x, Biy = t.b[1] - o.y, Biz = t.b[2] - o.z;
+    float Cix = t.c[0] - o.x, Ciy = t.c[1] - o.y, Ciz = t.c[2] - o.z;
+    float Ax = Aix - s.shearx * Aiz, Ay = Aiy - s.sheary * Aiz;
+    float Bx = Bix - s.shearx * Biz, By = Biy - s.sheary * Biz;
+    float Cx = Cix - s.shearx * Ciz, Cy = Ciy - s.sheary * Ciz;
+    float U = Cx * By - Cy * Bx;
+    float V = Ax * Cy - Ay * Cx;
+    float W = Bx * Ay - By * Ax;
+    if ( U == 0.f || V == 0.f || W == 0.f ) {
+        U = ( float ) ( ( double ) Cx * ( double ) By - ( double ) Cy * ( double ) Bx );
+        V = ( float ) ( ( double ) Ax * ( double ) Cy - ( double ) Ay * ( double ) Cx );
+        W = ( float ) ( ( double ) Bx * ( double ) Ay - ( double ) By * ( double ) Ax );
+    }
+    uint32_t sign = tdm_bits ( U ) & 0x80000000u;
+    if ( ( ( tdm_bits ( V ) ^ tdm_bits ( U ) ) | ( tdm_bits ( W ) ^ tdm_bits ( U ) ) ) & 0x80000000u ) return false;
+    float det = U + V + W;
+    if ( det == 0.f ) return false;
+    float Az = s.scalez * Aiz, Bz = s.scalez * Biz, Cz = s.scalez * Ciz;
+    float depth = U * Az + V * Bz + W * Cz;
+    if ( tdm_float ( tdm_bits ( depth ) ^ sign ) < 0.f ) return false;
+    float inv_det = 1.f / det;
+    depth_out = depth * inv_det;
+    return true;
+}
+
+TD bool moller_trumbore ( V3 o, V3 d, V3 ta, V3 tb, V3 tc, float& t_out, V3& p_out ) {
+    V3 e1 = tb - ta, e2 = tc - ta;
+    V3 h = cross ( d, e2 );
+    float a = dot ( e1, h );
+    if ( ( double ) a > -1e-4 && ( double ) a < 1e-4 ) return false;
+    float f = 1 / a;
+    V3 s = o - ta;
+    float u = f * dot ( s, h );
+    if ( u < 0.f || u > 1.f ) return false;
+    V3 q = cross ( s, e1 );
+    float v = f * dot ( d, q );
+    if ( v < 0.f || u + v > 1.f ) return false;
+    float t = f * dot ( e2, q );
+    if ( t > 0.00001f ) { t_out = t; p_out = d * t + o; return true; }
+    return false;
+}

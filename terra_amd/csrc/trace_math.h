@@ -1,0 +1,61 @@
+// trace_math.h -- bottom layer of the device hot path (trace_device.h lists the layers): vectors, the shading basis, rays and the
+// per-ray state of the watertight test.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <float.h>
+#include "dev_types.h"
+#include "dev_math.h"
+#include "rng.h"
+#include "sampling_device.h"
+
+#define TD __device__ __forceinline__
+
+struct V3 { float x, y, z; };
+
+TD V3 v3 ( float x, float y, float z ) { V3 r; r.x = x; r.y = y; r.z = z; return r; }
+TD V3 v3p ( const float* p ) { return v3 ( p[0], p[1], p[2] ); }
+TD V3 operator+ ( V3 a, V3 b ) { return v3 ( a.x + b.x, a.y + b.y, a.z + b.z ); }
+TD V3 operator- ( V3 a, V3 b ) { return v3 ( a.x - b.x, a.y - b.y, a.z - b.z ); }
+TD V3 operator* ( V3 a, float s ) { return v3 ( a.x * s, a.y * s, a.z * s ); }
+TD V3 had ( V3 a, V3 b ) { return v3 ( a.x * b.x, a.y * b.y, a.z * b.z ); }
+TD V3 neg ( V3 a ) { return v3 ( -a.x, -a.y, -a.z ); }
+TD float dot ( V3 a, V3 b ) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+TD V3 cross ( V3 a, V3 b ) { return v3 ( a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x ); }
+TD float length ( V3 a ) { return sqrtf ( a.x * a.x + a.y * a.y + a.z * a.z ); }
+TD V3 normalize ( V3 a ) { float l = length ( a ); return v3 ( a.x / l, a.y / l, a.z / l ); }
+// compare-selects: exactly "a < b ? a : b" / "a > b ? a : b" (NaN-order sensitive)
+TD float sel_min ( float a, float b ) { return a < b ? a : b; }
+TD float sel_max ( float a, float b ) { return a > b ? a : b; }
+TD float pick ( V3 a, int i ) { return i == 0 ? a.x : ( i == 1 ? a.y : a.z ); }
+
+// columns of the shading basis: tangent, normal, bitangent. Stored by rows as the reference does.
+struct Basis { float r0[3], r1[3], r2[3]; };
+TD V3 basis_apply ( const Basis& m, V3 v ) {
+    return v3 ( m.r0[0] * v.x + m.r0[1] * v.y + m.r0[2] * v.z,
+                m.r1[0] * v.x + m.r1[1] * v.y + m.r1[2] * v.z,
+                m.r2[0] * v.x + m.r2[1] * v.y + m.r2[2] * v.z );
+}
+TD Basis make_basis ( V3 n ) {
+    V3 t;
+    if ( fabsf ( n.x ) > fabsf ( n.y ) ) {
+        float k = sqrtf ( n.x * n.x + n.z * n.z );
+        t = v3 ( n.z * k, 0.f * k, -n.x * k );
+    } else {
+        float k = sqrtf ( n.y * n.y + n.z * n.z );
+        t = v3 ( 0.f * k, -n.z * k, n.y * k );
+    }
+    V3 b = cross ( n, t );
+    Basis m;
+    m.r0[0] = t.x; m.r0[1] = n.x; m.r0[2] = b.x;
+    m.r1[0] = t.y; m.r1[1] = n.y; m.r1[2] = b.y;
+    m.r2[0] = t.z; m.r2[1] = n.z; m.r2[2] = b.z;
+    return m;
+}
+
+struct Ray { V3 o, d, inv; };
+TD Ray make_ray ( V3 o, V3 d ) { Ray r; r.o = o; r.d = d; r.inv = v3 ( 1.f / d.x, 1.f / d.y, 1.f / d.z ); return r; }
+
+// what the watertight test keeps per ray (ray_state_init): the dominant axis iz of the direction, the two others in winding order, the shear and the scale
+struct RayState { float shearx, sheary, scalez; int ix, iy, iz; };
+// a point in the ray's permuted axes: (a[ix], a[iy], a[iz])
+TD V3 permuted ( V3 a, const RayState& s ) { return v3 ( pick ( a, s.ix ), pick ( a, s.iy ), pick ( a, s.iz ) ); }

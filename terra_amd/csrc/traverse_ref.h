@@ -1,0 +1,299 @@
+// traverse_ref.h -- the reference-order BVH traversal (trace_device.h lists the layers): work counters, the Tracer, the node and leaf
+// steps, the ranked traversal of small LDS-resident scenes, the resumable form of the decoupled render loops.
+#pragma once
+#include "trace_geometry.h"
+
+// per-lane work counters (registers); flushed with one atomic per wave and counter.
+// Not counted on the device because the host can derive them exactly: slab tests
+// (= 2*nodes - tri_tests: every child of a popped node is either slab-tested or, if a
+// leaf, triangle-tested), camera samples and pixels (tile geometry x spp).
+#ifndef TERRA_PHASE_STATS          // lane-occupancy study builds (tools/phase_stats.py): per-phase wave iterations / active lanes
+#define TERRA_PHASE_STATS 0
+#endif
+struct Counters {
+    uint32_t rays, nodes, tri_tests, hits, rand_calls, attr_fetches;
+    uint32_t tri_culled;     // leaves met whose triangle test was skipped (Tracer::cull); counted at COUNT level 2 only
+#if TERRA_PHASE_STATS
+    uint32_t ps[16];
+#endif
+};
+TD Counters counters_zero() {
+    Counters c; c.rays = c.nodes = c.tri_tests = c.hits = c.rand_calls = c.attr_fetches = c.tri_culled = 0;
+#if TERRA_PHASE_STATS
+    for ( int i = 0; i < 16; ++i ) c.ps[i] = 0;
+#endif
+    return c;
+}
+#if TERRA_PHASE_STATS
+// PS_WAVE: +1 per wave (the first active lane counts); PS_LANE: +1 per active lane
+#define PS_WAVE(c, k) do { if ( ( int ) ( threadIdx.x & 63 ) == __ffsll ( ( long long ) __ballot ( 1 ) ) - 1 ) ++( c ).ps[k]; } while ( 0 )
+#define PS_LANE(c, k) do { ++( c ).ps[k]; } while ( 0 )
+#else
+#define PS_WAVE(c, k) do { } while ( 0 )
+#define PS_LANE(c, k) do { } while ( 0 )
+#endif
+enum { kPsRayIter = 0, kPsNodeIter, kPsLeafIter, kPsShadeIter, kPsCamIter, kPsCamLanes, kPsRayLanes, kPsShadeLanes, kPsNodeLanes, kPsLeafLanes, kPsDrainIter,
+       kPsTop64, kPsTop256, kPsTop1024, kPsTop4096 };      // node visits that fall into the first K nodes of the (breadth-first numbered) array: what an LDS-staged prefix would serve
+
+// -----------------------------------------------------------------------------
+// Tracer: where a thread finds the scene and its traversal scratch.
+//
+// LDS layout of a block (DESIGN.md "LDS"): [staged nodes: lds_nodes x 112 B] [staged triangles: lds_tris x 48 B]
+// [staged vertex properties: lds_tris x 64 B] [node stack: stack_depth x 256 ints] [leaf list: leaf_cap x 256 ints]
+// [per-thread parked words]. Stack and leaf list are indexed [entry][thread] so the 64 lanes of a wave touch
+// 64 consecutive words (conflict free); a lane walks its column with a pointer (one add per push / pop).
+// Nodes and triangles are staged only when the whole scene fits.
+//
+// Staged node (MODE 1), 7 x 16 B, "axis major, both signs":
+//     [x+] min0.x max0.x min1.x max1.x     [x-] max0.x min0.x max1.x min1.x
+//     [y+] ...                             [y-] ...
+//     [z+] ...                             [z-] ...
+//     [children] child0 child1 bit0 bit1   (an inner child = the BYTE OFFSET of its staged node, a leaf = DEV_CHILD_LEAF | triangle; bit0 / bit1: see below)
+// A ray whose inverse direction is finite and non-zero on every axis reads, per axis, the copy that matches the sign of its
+// direction (SlabSel): the four floats are then (near plane, far plane) of child 0 and of child 1, so the slab test needs no
+// per-axis min/max at all -- v_min/v_max_f32 issue at 0.57 G/s per SIMD on gfx950 against 0.96 for v_sub/v_mul_f32
+// (profiles/r02_measurements/valu_rates.log). Picking the plane by the sign is exactly min(t1, t2) / max(t1, t2): for
+// bmin <= bmax, (b - o) * inv is monotone in b (both roundings are), increasing for inv > 0 and decreasing for inv < 0.
+//
+// Ranked launches (DevRenderParams::leaf_rank: LDS-resident scenes of at most TERRA_LEAF_RANK_MAX triangles, traverse_ranked): bit0 / bit1 of a leaf child =
+// 1 << (its triangle's reference visit rank, DevTri::pad), 0 for an inner child or an empty slot (0 in every other launch). The leaf list is replaced by
+// the triangles staged in rank order once per axis permutation of the watertight test (kz = the dominant axis, kx / ky swapped when d[kz] < 0):
+// 6 copies x lds_tris x 48 B, entry = a[kx] a[ky] a[kz] b[kx] | b[ky] b[kz] c[kx] c[ky] | c[kz] triangle - -.
+// -----------------------------------------------------------------------------
+#define TERRA_LEAF_CAP_MAX 16
+#define TERRA_LEAF_RANK_MAX 32     // triangles a ranked launch can have: a lane's leaf set is one 32-bit word
+#define TERRA_COL 256              // stride of a stack / leaf-list column: the block's thread count
+#define TERRA_LDS_NODE_BYTES 112   // staged node (see above)
+
+struct Tracer {
+    DevScene      sc;
+    const float4* l_nodes;     // LDS copies (valid for index < lds_nodes / lds_tris)
+    const float*  l_tris;
+    const float4* l_props;
+    const DevMaterial* l_mats;  // materials, lights, per-triangle areas: the block's LDS copies in MODE 1, the arrays in HBM otherwise (make_tracer)
+    const DevLight*    l_lights;
+    const float*       l_area;
+    const float4* l_ranked;    // ranked launches: the 6 permuted copies of the staged triangles, in rank order (see above); nullptr otherwise
+    uint32_t      lds_nodes, lds_tris;
+    int*          stack;       // this thread's column
+    int*          leaves;
+    int           leaf_cap;    // entries in the leaf list (>= 2)
+    int           stack_cap;   // entries in the stack column (TERRA_CHECK_BOUNDS builds verify every push against it)
+    // fast-tree launches: entries beyond the LDS column live in HBM (DevRenderParams::stack_spill): spill = this lane's spill_cap words, nullptr when the column holds the whole stack
+    uint32_t      stack_lim;   // 32-bit LDS address of the block's stack words + stack entries * 1024: wave-uniform (fast_push / fast_pop)
+    uint32_t*     spill;
+    uint32_t      spill_cap;
+    unsigned long long* faults;
+    // leaf-box cull (DESIGN.md "Leaf-box cull"): a leaf child's triangle is tested only if the ray passes the slab test of
+    // that child's box -- the box the node already carries and the node step already tests. The reference tests the triangle
+    // unconditionally (src/TerraBVH.c:284-300); the closest hit is the same whenever a triangle the ray hits lies inside its
+    // own +-1e-4 box as the slab test sees it, which the host verifies numerically at commit (terra_cull_margin_ok).
+    bool cull;
+    // cull launches INSIDE the coordinate range may also decide the inner boxes with the fused slab arithmetic (slab_near_far_fused): the containment proof covers
+    // every box there. Outside it (Scene::reach_cull) only the rebuilt leaf boxes carry a margin; the inner boxes must be tested exactly as the reference tests them.
+    bool fused;
+    // the leaves a ray meets are collected as a set of ranks in one register instead of a list in LDS (traverse_ranked); launch constant
+    bool ranked;
+};
+
+// -----------------------------------------------------------------------------
+// BVH traversal (reference src/TerraBVH.c:250-310), restructured without changing
+// what is computed:
+//   * the node loop only does slab tests and stack traffic; leaves met on the way are
+//     appended to a per-lane list and tested afterwards in the order they were met.
+//     The reference never lets a hit influence the traversal (no culling against the
+//     closest hit), so testing the leaves later, in the same order, with the same
+//     strict "<" on depth, selects the same triangle;
+//   * when a lane's list is full the lists are drained and the node loop resumes;
+//   * the hit point is formed once, from the winning depth (same expression).
+// MODE 0: nodes/triangles from global memory; 1: everything staged in LDS.
+// -----------------------------------------------------------------------------
+struct Closest { float depth; uint32_t tri; };
+
+// Stack / leaf-list writes. A TERRA_CHECK_BOUNDS build (python -m terra_amd.build --variant chk -DTERRA_CHECK_BOUNDS=1)
+// refuses (drops the entry, so the column is never left) and counts any write beyond the sizes the host planned; the shipped build trusts the plan
+// (max_stack is the exact worst case of the tree, computed at commit).
+#ifndef TERRA_CHECK_BOUNDS
+#define TERRA_CHECK_BOUNDS 0
+#endif
+#define TERRA_PUSH(T, sp, v) do { if ( TERRA_CHECK_BOUNDS && ( sp ) >= ( T ).stack + ( T ).stack_cap * TERRA_COL ) { if ( ( T ).faults ) atomicAdd ( ( T ).faults, 1ull ); } else { *( sp ) = ( int ) ( v ); ( sp ) += TERRA_COL; } } while ( 0 )
+#define TERRA_LEAF(T, lp, v) do { if ( TERRA_CHECK_BOUNDS && ( lp ) >= ( T ).leaves + ( T ).leaf_cap * TERRA_COL ) { if ( ( T ).faults ) atomicAdd ( ( T ).faults, 1ull ); } else { *( lp ) = ( int ) ( v ); ( lp ) += TERRA_COL; } } while ( 0 )
+
+// which copy of each axis a lane reads from a staged node (byte offsets inside the node); regular rays only. oi = origin * inverse direction, for the
+// fused form of the slab test (slab_near_far_fused)
+struct SlabSel { uint32_t x, y, z; V3 oi; };
+TD SlabSel slab_sel ( const Ray& r ) {
+    SlabSel s;
+    s.x = r.inv.x < 0.f ? 16u : 0u; s.y = r.inv.y < 0.f ? 48u : 32u; s.z = r.inv.z < 0.f ? 80u : 64u;
+    s.oi = v3 ( r.o.x * r.inv.x, r.o.y * r.inv.y, r.o.z * r.inv.z );
+    return s;
+}
+
+// one node of the reference traversal (src/TerraBVH.c:262-303): pop, slab-test both child boxes, push the inner children
+// that are hit, append the leaf children to the lane's list (all of them; with Tracer::cull only those whose box is hit).
+// An empty child slot (scenes with < 2 triangles) travels as a leaf and is dropped by leaf_step.
+// RANKED (MODE 1, ranked launches): the leaf children go into the lane's rank set `leaf_set` (their bits in the staged node) instead of the list; `lp` is not used.
+template <int COUNT, int MODE, bool FAST, bool FUSED = false, bool RANKED = false>
+TD void node_step ( const Tracer& T, const Ray& r, const SlabSel& sel, int*& sp, int*& lp, uint32_t& leaf_set, Counters& c ) {
+    PS_WAVE ( c, kPsNodeIter ); PS_LANE ( c, kPsNodeLanes );
+    sp -= TERRA_COL;
+    const uint32_t w = ( uint32_t ) * sp;
+    uint32_t child0, child1, bit0 = 0u, bit1 = 0u; bool hit0, hit1;
+    float te0 = 0.f, te1 = 0.f;          // (FUSED) entry distance of each child box (unused: kept out of registers by the optimiser)
+    if ( MODE == 1 ) {
+        const char* node = reinterpret_cast<const char*> ( T.l_nodes ) + w;          // w = byte offset of the staged node
+        if ( RANKED ) {
+            const uint4 cw = *reinterpret_cast<const uint4*> ( node + 96 );
+            child0 = cw.x; child1 = cw.y; bit0 = cw.z; bit1 = cw.w;
+        } else {
+            const uint2 cw = *reinterpret_cast<const uint2*> ( node + 96 );
+            child0 = cw.x; child1 = cw.y;
+        }
+        if ( FAST ) {
+            const float4 ax = *reinterpret_cast<const float4*> ( node + sel.x ), ay = *reinterpret_cast<const float4*> ( node + sel.y ), az = *reinterpret_cast<const float4*> ( node + sel.z );
+            if ( FUSED ) {
+                hit0 = slab_near_far_fused ( ax.x, ax.y, ay.x, ay.y, az.x, az.y, r, sel.oi, te0 );
+                hit1 = slab_near_far_fused ( ax.z, ax.w, ay.z, ay.w, az.z, az.w, r, sel.oi, te1 );
+            } else {
+                hit0 = slab_near_far ( ax.x, ax.y, ay.x, ay.y, az.x, az.y, r );
+                hit1 = slab_near_far ( ax.z, ax.w, ay.z, ay.w, az.z, az.w, r );
+            }
+        } else {
+            const float4 ax = *reinterpret_cast<const float4*> ( node ), ay = *reinterpret_cast<const float4*> ( node + 32 ), az = *reinterpret_cast<const float4*> ( node + 64 );
+            hit0 = slab<false> ( v3 ( ax.x, ay.x, az.x ), v3 ( ax.y, ay.y, az.y ), r );
+            hit1 = slab<false> ( v3 ( ax.z, ay.z, az.z ), v3 ( ax.w, ay.w, az.w ), r );
+        }
+    } else {
+        const float4* g_nodes = reinterpret_cast<const float4*> ( T.sc.nodes );
+#if TERRA_PHASE_STATS
+        c.ps[kPsTop64] += w < 64u; c.ps[kPsTop256] += w < 256u; c.ps[kPsTop1024] += w < 1024u; c.ps[kPsTop4096] += w < 4096u;
+#endif
+        const float4 q0 = g_nodes[4 * w], q1 = g_nodes[4 * w + 1], q2 = g_nodes[4 * w + 2], q3 = g_nodes[4 * w + 3];
+        child0 = __float_as_uint ( q3.x ); child1 = __float_as_uint ( q3.y );
+        hit0 = slab<FAST> ( v3 ( q0.x, q0.y, q0.z ), v3 ( q0.w, q1.x, q1.y ), r );
+        hit1 = slab<FAST> ( v3 ( q1.z, q1.w, q2.x ), v3 ( q2.y, q2.z, q2.w ), r );
+    }
+    if ( COUNT ) ++c.nodes;
+    const bool leaf0 = ( child0 & DEV_CHILD_LEAF ) != 0, leaf1 = ( child1 & DEV_CHILD_LEAF ) != 0;
+    if ( !leaf0 && hit0 ) { TERRA_PUSH ( T, sp, child0 ); }
+    if ( !leaf1 && hit1 ) { TERRA_PUSH ( T, sp, child1 ); }
+    if ( RANKED ) {          // (bit = 0 for an inner child and for an empty slot: nothing to test, as leaf_step drops the empty slot)
+        leaf_set |= ( hit0 || !T.cull ) ? bit0 : 0u;
+        leaf_set |= ( hit1 || !T.cull ) ? bit1 : 0u;
+    } else {
+        if ( leaf0 && ( hit0 || !T.cull ) ) { TERRA_LEAF ( T, lp, ( child0 & 0x7fffffffu ) ); }
+        if ( leaf1 && ( hit1 || !T.cull ) ) { TERRA_LEAF ( T, lp, ( child1 & 0x7fffffffu ) ); }
+    }
+    if ( COUNT == 2 && T.cull ) c.tri_culled += ( uint32_t ) ( leaf0 && !hit0 ) + ( uint32_t ) ( leaf1 && !hit1 );
+}
+
+// triangle test of one entry of the lane's leaf list, in the order the leaves were met: strict "<" keeps the first of equal depths
+// (expected != none: the ray only asks whether its closest hit is triangle `expected` -- scene_raycast_triangle -- and `stop` is set by the first other triangle that comes first)
+template <int COUNT, int MODE, bool ANYHIT = false>
+TD void leaf_step ( const Tracer& T, const int* entry, const RayState& st, V3 o_perm, Closest& best, Counters& c, uint32_t expected = 0xffffffffu, bool* stop = nullptr ) {
+    const float4* g_tris = reinterpret_cast<const float4*> ( T.sc.tris );
+    PS_WAVE ( c, kPsLeafIter ); PS_LANE ( c, kPsLeafLanes );
+    const uint32_t ti = ( uint32_t ) * entry;
+    if ( ti == ( DEV_CHILD_EMPTY & 0x7fffffffu ) ) return;           // the empty slot of a degenerate tree
+    const TriPerm tp = MODE == 1 ? tri_perm_lds ( T.l_tris + 12 * ti, st ) : tri_perm ( g_tris[3 * ti], g_tris[3 * ti + 1], g_tris[3 * ti + 2], st );
+    if ( COUNT ) ++c.tri_tests;
+    float depth;
+    if ( watertight_permuted ( tp, o_perm, st, depth ) && depth < best.depth ) { best.depth = depth; best.tri = ti; if ( ANYHIT && ti != expected ) *stop = true; }
+}
+
+// Ranked launches (MODE 1, Tracer::ranked). The leaves any ray meets are a subsequence of one global order -- the order in which the traversal with every box
+// hit meets them (scene_host.cpp leaf_ranks) --, so "test the listed leaves in the order met" is "test the set ranks from low to high": the same triangles,
+// in the same order, with the same strict "<". The node loop therefore runs to the end in one pass and only sets bits; the leaf loop then walks the set
+// bits and reads each triangle, already permuted into the ray's axes, with three 16-byte loads from the copy for the ray's permutation.
+template <int COUNT, int MODE, bool FAST, bool FUSED = false, bool ANYHIT = false>
+TD void traverse_ranked ( const Tracer& T, const Ray& r, const RayState& st, V3 o_perm, Closest& best, Counters& c, uint32_t expected ) {
+    const SlabSel sel = slab_sel ( r );
+    int* sp = T.stack; int* lp = nullptr;
+    uint32_t leaf_set = 0u;
+    *sp = 0; sp += TERRA_COL;                                          // the root: node 0 = byte offset 0
+    PS_WAVE ( c, kPsDrainIter );
+    while ( sp != T.stack ) node_step<COUNT, MODE, FAST, FUSED, true> ( T, r, sel, sp, lp, leaf_set, c );
+    const uint32_t perm = 2u * ( uint32_t ) st.iz + ( uint32_t ) ( st.ix != ( st.iz == 2 ? 0 : st.iz + 1 ) );      // ray_state_init: ix follows iz unless d[iz] < 0 swapped ix / iy
+    const float4* copy = T.l_ranked + 3u * T.lds_tris * perm;
+    while ( leaf_set != 0u ) {
+        PS_WAVE ( c, kPsLeafIter ); PS_LANE ( c, kPsLeafLanes );
+        const float4* e = copy + 3u * ( uint32_t ) __builtin_ctz ( leaf_set );
+        leaf_set &= leaf_set - 1u;
+        const float4 q0 = e[0], q1 = e[1], q2 = e[2];
+        const TriPerm tp = { { q0.x, q0.y, q0.z }, { q0.w, q1.x, q1.y }, { q1.z, q1.w, q2.x } };
+        if ( COUNT ) ++c.tri_tests;
+        float depth;
+        if ( watertight_permuted ( tp, o_perm, st, depth ) && depth < best.depth ) {
+            const uint32_t ti = __float_as_uint ( q2.y );
+            best.depth = depth; best.tri = ti;
+            if ( ANYHIT && ti != expected ) leaf_set = 0u;             // another triangle comes first: nothing further can change the answer
+        }
+    }
+}
+
+template <int COUNT, int MODE, bool FAST, bool FUSED = false, bool ANYHIT = false>
+TD void traverse_loops ( const Tracer& T, const Ray& r, const RayState& st, V3 o_perm, Closest& best, Counters& c, uint32_t expected = 0xffffffffu ) {
+    if constexpr ( MODE == 1 ) if ( T.ranked ) { traverse_ranked<COUNT, MODE, FAST, FUSED, ANYHIT> ( T, r, st, o_perm, best, c, expected ); return; }
+    const SlabSel sel = slab_sel ( r );
+    int* sp = T.stack; int* lp = T.leaves;
+    int* const lp_full = T.leaves + ( T.leaf_cap - 2 ) * TERRA_COL;       // a node adds at most two leaves
+    uint32_t no_set = 0u;
+    *sp = 0; sp += TERRA_COL;                                          // the root: node 0 = byte offset 0
+    for ( ;; ) {
+        PS_WAVE ( c, kPsDrainIter );
+        while ( sp != T.stack && lp <= lp_full ) node_step<COUNT, MODE, FAST, FUSED> ( T, r, sel, sp, lp, no_set, c );
+        if constexpr ( ANYHIT ) {
+            bool stop = false;
+            for ( const int* e = T.leaves; e != lp && !stop; e += TERRA_COL ) leaf_step<COUNT, MODE, true> ( T, e, st, o_perm, best, c, expected, &stop );
+            if ( stop ) sp = T.stack;                                  // another triangle comes first: nothing further can change the answer
+        } else
+        for ( const int* e = T.leaves; e != lp; e += TERRA_COL ) leaf_step<COUNT, MODE> ( T, e, st, o_perm, best, c );
+        lp = T.leaves;
+        if ( sp == T.stack ) break;
+    }
+}
+
+#ifndef TERRA_FUSED_SLAB
+#define TERRA_FUSED_SLAB 1
+#endif
+template <int COUNT, int MODE>
+TD Closest bvh_traverse ( const Tracer& T, const Ray& r, const RayState& st, Counters& c ) {
+    Closest best; best.depth = FLT_MAX; best.tri = 0xffffffffu;
+    V3 o_perm = permuted ( r.o, st );
+    // the slab variant is chosen per WAVE: one irregular ray sends its whole wave down the exact path
+    if ( TERRA_FUSED_SLAB && MODE == 1 && T.fused && __all ( ray_is_tame ( r ) ) ) traverse_loops<COUNT, MODE, true, true> ( T, r, st, o_perm, best, c );
+    else if ( __all ( ray_is_regular ( r ) ) ) traverse_loops<COUNT, MODE, true> ( T, r, st, o_perm, best, c );
+    else traverse_loops<COUNT, MODE, false> ( T, r, st, o_perm, best, c );
+    return best;
+}
+
+// -----------------------------------------------------------------------------
+// Resumable traversal for the decoupled render loop (large scenes; render_kernels.hip).
+// The 64 lanes of a wave hold DIFFERENT rays at different stages; a lane's traversal state
+// (stack column and leaf list in LDS; top, nleaf, closest hit in registers) survives leaving
+// and re-entering these functions. They return as soon as the number of lanes that still
+// have nodes to visit has dropped to `exit_active`, so that the finished lanes can be shaded
+// and given their next ray instead of idling until the slowest ray of the wave is done
+// (on the 97k-triangle hall a ray visits 474 nodes on average with a long tail: waiting for
+// the slowest of 64 left 17 % of the lanes busy). What is computed per ray, and in which
+// order, is exactly what traverse_loops computes.
+// `traversing` is cleared for lanes whose traversal completed.
+// -----------------------------------------------------------------------------
+template <int COUNT, int MODE, bool FAST>
+TD void traverse_resume ( const Tracer& T, const Ray& r, const SlabSel& sel, const RayState& st, V3 o_perm, Closest& best, int*& sp, bool& traversing, int exit_active, Counters& c ) {
+    int* const lp_full = T.leaves + ( T.leaf_cap - 2 ) * TERRA_COL;
+    int* lp = T.leaves;                                      // every lane's list is empty on entry and on exit
+    uint32_t no_set = 0u;
+    for ( ;; ) {
+        for ( ;; ) {
+            const bool can = traversing && sp != T.stack && lp <= lp_full;
+            const int n_can = __popcll ( __ballot ( can ) ), n_nodes = __popcll ( __ballot ( traversing && sp != T.stack ) );
+            if ( n_can == 0 || n_nodes <= exit_active ) break;
+            if ( can ) node_step<COUNT, MODE, FAST> ( T, r, sel, sp, lp, no_set, c );
+        }
+        for ( const int* e = T.leaves; e != lp; e += TERRA_COL ) leaf_step<COUNT, MODE> ( T, e, st, o_perm, best, c );        // lanes that are not traversing hold an empty list
+        lp = T.leaves;
+        if ( traversing && sp == T.stack ) traversing = false;
+        if ( __popcll ( __ballot ( traversing ) ) <= exit_active ) break;
+    }
+}

@@ -343,7 +343,7 @@ hipError_t terra_unit_distribution_2d ( const float* f, uint32_t nx, uint32_t ny
     if ( m > 0 ) hipLaunchKernelGGL ( k_dist_sample_2d, UNIT_GRID ( m ), 0, 0, f, cdf, nx, ny, integrals, mcdf, monotone, e12, m, xy2, pdf );
     return hipGetLastError();
 }
-// the lookup environment MIS uses (trace_device.h environment_pdf): point (v, u) of the unit square -- the order k_dist_sample_2d reports a sample in -- lies in
+// the lookup environment MIS uses (integrators_device.h environment_pdf): point (v, u) of the unit square -- the order k_dist_sample_2d reports a sample in -- lies in
 // bucket (row, col) = (v ny, u nx) truncated; its probability is distribution_2d_prob's (points outside [0, 1) clamp to the border buckets)
 __global__ void k_dist_pdf_2d ( const float* f, uint32_t nx, uint32_t ny, const float* integrals, const float* xy2, int m, float* pdf ) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -360,7 +360,7 @@ hipError_t terra_unit_distribution_2d_pdf ( const float* f, uint32_t nx, uint32_
     return hipGetLastError();
 }
 
-// ---- DevScene::sincos24: (cos, sin) of 2 * terra_PI * (k * 2^-24) for every 24-bit k, each entry by tdm_sincosf_pair itself (trace_device.h azimuth_fetch) ----
+// ---- DevScene::sincos24: (cos, sin) of 2 * terra_PI * (k * 2^-24) for every 24-bit k, each entry by tdm_sincosf_pair itself (shading_device.h azimuth_fetch) ----
 __global__ __launch_bounds__ ( 256 ) void terra_sincos24_kernel ( float2* table ) {
     const uint32_t k = blockIdx.x * 256u + threadIdx.x;          // grid = 2^24 / 256 blocks
     float sn, cs;

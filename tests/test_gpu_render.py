@@ -660,7 +660,7 @@ def _light_tie_scene(integ, occluder_first, w=40, h=28, spp=3):
 
 @pytest.mark.parametrize("integ", [1, 2])
 def test_light_sample_rays_that_meet_triangles_at_the_depth_of_their_own(H, L, orc_lib, devmath_mode, integ):
-    """the light-sample rays' shortcut (trace_device.h fast_expect / traverse_loops ANYHIT; kernels without counters) against the oracle where it is easiest to get
+    """the light-sample rays' shortcut (traverse_fast.h fast_expect / traverse_ref.h traverse_loops ANYHIT; kernels without counters) against the oracle where it is easiest to get
     wrong: depth ties with the expected triangle, resolved by the reference's visit order"""
     for occluder_first in (False, True):
         d = _light_tie_scene(integ, occluder_first)

@@ -27,7 +27,7 @@ for tm in (0, 1, 2):
     runtime.render_device(lib, scenes.camera_of(d), s, fb); torch.cuda.synchronize()
     print("positive control (stack shrunk by 19): tree", tm, "faults", f(s)); lib.scene_destroy(s)
 PY
-# the fast tree's stack (LDS column + HBM part, trace_device.h fast_push): its rays reach ~10 of the ~28 planned entries, so the control shrinks the plan by 40 -- every push is then out of plan
+# the fast tree's stack (LDS column + HBM part, traverse_fast.h fast_push): its rays reach ~10 of the ~28 planned entries, so the control shrinks the plan by 40 -- every push is then out of plan
 export TERRA_AMD_LIB=$GRAFT_REPO_ROOT/terra_amd/libterra_amd_chkneg2.so
 python - <<'PY'
 import torch, ctypes as C, sys

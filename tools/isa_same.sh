@@ -1,0 +1,52 @@
+#!/bin/bash
+# Do two source trees compile to the same device code? (dev tool, no GPU needed)
+# Compiles, device-only to assembly, the four TERRA_TU units of render_kernels.hip, unit_kernels.hip and aov_kernels.hip of both trees with
+# exactly the FLAGS of this tree's terra_amd/build.py (plus any extra -D given), strips what is not code -- comment lines, .file/.ident, and the
+# lines naming the per-compilation __hip_cuid_<hash> symbol -- and reports per unit "identical" or the symbols whose bodies differ.
+# usage: tools/isa_same.sh <tree A> <tree B> <scratch dir> [extra -D flags]
+#   e.g. git worktree add /tmp/parent HEAD~1 && tools/isa_same.sh /tmp/parent . /tmp/isa -DTERRA_CHECK_BOUNDS=1
+# A render unit takes a minute or more; at most 16 compile at a time. A unit's assembly is kept in the scratch directory under a key made of the tree's
+# path, the compiler, FLAGS and the extra flags, and compiled again when a file under the tree's terra_amd/csrc or include is newer than it: a second run
+# against the same parent compiles the changed tree alone, and no other tree, flag set or compiler is ever answered from it.
+# Exit status: 0 all identical, 1 some unit differs, 2 a compile failed.
+set -o pipefail
+[ $# -ge 3 ] || { sed -n '2,11p' "$0"; exit 2; }
+HERE=$(cd "$(dirname "$0")/.." && pwd)
+A=$(cd "$1" && pwd) || exit 2; B=$(cd "$2" && pwd) || exit 2; mkdir -p "$3" || exit 2; S=$(cd "$3" && pwd); shift 3
+HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
+FLAGS=$(python3 -c "import runpy, sys; print(' '.join(runpy.run_path(sys.argv[1])['FLAGS']))" "$HERE/terra_amd/build.py") || exit 2
+key() { printf '%s\n' "$1" "$HIPCC" "$($HIPCC --version 2>/dev/null | head -n 1)" "$FLAGS" "$2" | md5sum | cut -c1-16; }
+DA=$S/$(key "$A" "$*"); DB=$S/$(key "$B" "$*")
+UNITS="render_kernels.tu0 render_kernels.tu1 render_kernels.tu2 render_kernels.tu3 unit_kernels aov_kernels"
+JOBS=$(nproc); [ "$JOBS" -gt 16 ] && JOBS=16
+mkdir -p "$DA" "$DB"
+
+for side in a b; do
+    tree=$A; dir=$DA; [ $side = b ] && { tree=$B; dir=$DB; }
+    [ $side = b ] && [ "$DA" = "$DB" ] && continue
+    for u in $UNITS; do
+        s=$dir/$u.s
+        [ -s "$s" ] && [ -z "$(find "$tree/terra_amd/csrc" "$tree/include" -newer "$s" -type f -print -quit)" ] && continue
+        tu=; case $u in *.tu?) tu=-DTERRA_TU=${u##*.tu};; esac
+        printf '%q %s %s %s --cuda-device-only -S %q -o %q 2> %q && mv %q %q\n' "$HIPCC" "$FLAGS" "$tu" "$*" "$tree/terra_amd/csrc/${u%.tu?}.hip" "$s.tmp" "$s.err" "$s.tmp" "$s"
+    done
+done > "$DB/jobs.txt"
+if [ -s "$DB/jobs.txt" ]; then
+    echo "compiling $(wc -l < "$DB/jobs.txt") unit(s), $JOBS at a time ..." >&2
+    xargs -P "$JOBS" -d '\n' -n 1 bash -c < "$DB/jobs.txt" || { echo "a compile failed; see $DA/*.err $DB/*.err" >&2; exit 2; }
+fi
+
+# code lines only, each prefixed with the symbol it belongs to (a function body, or that kernel's .amdhsa_kernel descriptor)
+code_by_symbol() {
+    awk '/^[ \t]*;/ || /^[ \t]*\.(file|ident)[ \t]/ || /__hip_cuid_/ { next }
+         /^[ \t]*\.type[ \t].*,@function/ { sym = $2; sub(/,@function.*/, "", sym) }
+         /^[ \t]*\.amdhsa_kernel[ \t]/    { sym = $2 }
+         { print (sym == "" ? "(outside any function)" : sym) "\t" $0 }
+         /^[ \t]*\.size[ \t]/ || /^[ \t]*\.end_amdhsa_kernel/ { sym = "" }' "$1"
+}
+rc=0
+for u in $UNITS; do
+    d=$(diff <(code_by_symbol "$DA/$u.s") <(code_by_symbol "$DB/$u.s") | sed -n 's/^[<>] \([^\t]*\)\t.*/\1/p' | sort -u)
+    if [ -z "$d" ]; then echo "$u: identical"; else echo "$u: DIFFERS in"; echo "$d" | sed 's/^/    /'; rc=1; fi
+done
+exit $rc
