@@ -32,6 +32,7 @@
  *       [--camera px py pz dx dy dz] [--fov deg] [--exposure e] [--gamma g] [--jitter j]
  *       [--no-flip-z] [--normals apollo|file] [--dump-scene file] [--no-render] [--fast-tree | --replica-tree] [--sample-split n] [--seed n] [--tile n] [--gpus n]
  *       [--environment map.hdr|map.pfm] [--environment-color r g b] [--env-light] [--env-sampling off|table|mis] [--aov PREFIX] [--denoise K]
+ *       [--passes N] [--denoise-variance K] [--adaptive TARGET [--min-passes A] [--max-passes B]] [--variance out.pfm]
  *
  * Environment: the scene's environment attribute is a constant (--environment-color, default 0.4 0.52 1) or a lat-long map (--environment: Radiance .hdr with flat
  * or new-style run-length-encoded scanlines, orientation -Y H +X W, texel = m 2^(e - 136); or .pfm, either byte order, bottom row first), bound as a 3-component
@@ -61,6 +62,13 @@ int         terra_amd_set_environment_mis ( HTerraScene, int ) __attribute__ ( (
 typedef struct { float albedo[3]; float coverage; float normal[3]; float depth; int samples; int reserved[3]; } AovSum;
 int         terra_amd_render_aov ( const TerraCamera*, HTerraScene, void*, size_t, size_t, size_t, size_t, size_t, size_t ) __attribute__ ( ( weak ) );
 int         terra_amd_denoise ( HTerraScene, const TerraFramebuffer*, const void*, size_t, size_t, size_t, size_t, int, TerraFloat3*, TerraFloat3* ) __attribute__ ( ( weak ) );
+/* per-pixel second moments (TerraAmdMoments, TerraAmdAdaptiveOptions / Report of terra_amd.h, restated for the same reason), their denoiser and the adaptive driver */
+typedef struct { float seen_acc[3]; int seen_samples; float mean; float m2; int batches; int weight; } MomentSum;
+typedef struct { size_t tile_size; int min_batches; int max_batches; float target_error; int reserved; } AdaptiveOptions;
+typedef struct { int rounds; int hit_max_batches; int tiles; int tiles_converged; uint64_t tile_calls; uint64_t samples; float max_error; int reserved; } AdaptiveReport;
+int         terra_amd_accumulate_moments ( HTerraScene, const TerraFramebuffer*, void*, size_t, size_t, size_t, size_t ) __attribute__ ( ( weak ) );
+int         terra_amd_denoise_variance ( HTerraScene, const TerraFramebuffer*, const void*, const void*, size_t, size_t, size_t, size_t, int, TerraFloat3*, TerraFloat3* ) __attribute__ ( ( weak ) );
+int         terra_amd_render_adaptive ( const TerraCamera*, HTerraScene, TerraFramebuffer*, void*, void*, size_t, size_t, size_t, size_t, const void*, void* ) __attribute__ ( ( weak ) );
 
 /* ---- growable arrays ------------------------------------------------------------------------ */
 #define VEC(T) struct { T* d; size_t n, cap; }
@@ -396,6 +404,19 @@ static int write_aov_pfm ( const char* path, const AovSum* a, size_t W, size_t H
     free ( img.pixels );
     return ok;
 }
+/* the variance of each pixel's mean luminance (m2 / (weight (batches - 1))) as a grey PFM; pixels with fewer than two batches are 0 */
+static int write_variance_pfm ( const char* path, const MomentSum* m, size_t W, size_t H ) {
+    TerraFramebuffer img; img.width = W; img.height = H; img.results = NULL;
+    img.pixels = malloc ( W * H * sizeof ( TerraFloat3 ) );
+    if ( !img.pixels ) return 0;
+    for ( size_t i = 0; i < W * H; ++i ) {
+        const float v = m[i].batches >= 2 ? m[i].m2 / ( ( float ) m[i].weight * ( float ) ( m[i].batches - 1 ) ) : 0.f;
+        img.pixels[i] = terra_f3_set ( v, v, v );
+    }
+    const int ok = write_pfm ( path, &img );
+    free ( img.pixels );
+    return ok;
+}
 static int write_hdr ( const char* path, const TerraFramebuffer* fb ) {       /* Radiance RGBE, flat scanlines */
     FILE* f = fopen ( path, "wb" ); if ( !f ) return 0;
     fprintf ( f, "#?RADIANCE\nFORMAT=32-bit_rle_rgbe\n\n-Y %zu +X %zu\n", fb->height, fb->width );
@@ -547,6 +568,12 @@ static const char* kHelp =
     "  --aov PREFIX (libterra_amd.so only): also runs the first-hit AOV pass with the same calls as the render (terra_amd_render_aov) and writes the means over hits\n"
     "           PREFIX.albedo.pfm, PREFIX.normal.pfm, PREFIX.depth.pfm\n"
     "  --denoise K (libterra_amd.so only): writes the image denoised by K (0 .. 8) a-trous iterations guided by the AOVs (terra_amd_denoise) instead of the plain one\n"
+    "  --passes N (libterra_amd.so only): N render calls of --spp samples each, the per-pixel second moments folded after each (terra_amd_accumulate_moments)\n"
+    "  --denoise-variance K (libterra_amd.so only): as --denoise, with the colour weight guided by the variance --passes (at least 2) or --adaptive recorded\n"
+    "           (terra_amd_denoise_variance)\n"
+    "  --adaptive TARGET [--min-passes A --max-passes B] (libterra_amd.so only): passes per --tile (0 = 128) tile until its relative error is at most TARGET\n"
+    "           (terra_amd_render_adaptive); the report goes to stderr\n"
+    "  --variance out.pfm (libterra_amd.so only): the variance of each pixel's mean luminance after --passes / --adaptive\n"
     "OBJ/MTL import (--normals apollo, the default): the policy of the reference client's importer (satellite/include/Apollo.h under the\n"
     "options of satellite/src/Scene.cpp:83-93) RESTATED in this tool and pinned by hand-derived fixtures -- restated, not executed: Apollo.h\n"
     "does not compile with this image's toolchains. Everything after the TerraObject fill (commit, render, export) is the pinned path.\n";
@@ -558,6 +585,7 @@ int main ( int argc, char** argv ) {
     size_t W = 800, H = 600, spp = 8, bounces = 4, tile = 0;     /* defaults of satellite/include/Config.hpp:19-113 */
     int integrator = kTerraIntegratorDirect, tonemap = kTerraTonemappingOperatorLinear, flip = 1, fast = -1, have_seed = 0, split = -1, apollo = 1, gpus = 0;
     const char* aov_prefix = NULL; int denoise = -1;
+    int passes = 1, denoise_var = -1, min_passes = 0, max_passes = 0; float adaptive = 0.f; const char* variance_path = NULL;
     const char* dump_path = NULL; int no_render = 0;
     float fov = 45.f, exposure = 1.f, gamma = 2.2f, jitter = 0.f;
     unsigned long long seed = 0;
@@ -592,6 +620,12 @@ int main ( int argc, char** argv ) {
         else if ( !strcmp ( a, "--env-light" ) ) env_light = 1;
         else if ( !strcmp ( a, "--aov" ) ) aov_prefix = NEXT();
         else if ( !strcmp ( a, "--denoise" ) ) { denoise = atoi ( NEXT() ); if ( denoise < 0 || denoise > 8 ) { fprintf ( stderr, "terra_headless: --denoise 0 .. 8\n" ); return 64; } }
+        else if ( !strcmp ( a, "--passes" ) ) { passes = atoi ( NEXT() ); if ( passes < 1 ) { fprintf ( stderr, "terra_headless: --passes 1 ...\n" ); return 64; } }
+        else if ( !strcmp ( a, "--denoise-variance" ) ) { denoise_var = atoi ( NEXT() ); if ( denoise_var < 0 || denoise_var > 8 ) { fprintf ( stderr, "terra_headless: --denoise-variance 0 .. 8\n" ); return 64; } }
+        else if ( !strcmp ( a, "--adaptive" ) ) { adaptive = ( float ) atof ( NEXT() ); if ( !( adaptive > 0.f ) ) { fprintf ( stderr, "terra_headless: --adaptive TARGET > 0\n" ); return 64; } }
+        else if ( !strcmp ( a, "--min-passes" ) ) min_passes = atoi ( NEXT() );
+        else if ( !strcmp ( a, "--max-passes" ) ) max_passes = atoi ( NEXT() );
+        else if ( !strcmp ( a, "--variance" ) ) variance_path = NEXT();
         else if ( !strcmp ( a, "--env-sampling" ) ) { const char* v = NEXT(); static const char* const n[] = { "off", "table", "mis" }; env_sampling = pick ( v, n, 3, -1 ); if ( env_sampling < 0 ) { fprintf ( stderr, "terra_headless: --env-sampling off|table|mis\n" ); return 64; } }
         else if ( !strcmp ( a, "--camera" ) && i + 6 < argc ) {
             cam.position = terra_f3_set ( ( float ) atof ( argv[i + 1] ), ( float ) atof ( argv[i + 2] ), ( float ) atof ( argv[i + 3] ) );
@@ -646,8 +680,14 @@ int main ( int argc, char** argv ) {
         for ( int k = 0; k < gpus; ++k ) devs[k] = k;
         if ( terra_amd_set_devices ( devs, gpus ) != 0 ) { fprintf ( stderr, "terra_headless: %s\n", terra_amd_last_error ? terra_amd_last_error() : "terra_amd_set_devices failed" ); return 69; }
     }
+    MomentSum* mom = NULL;       /* --passes / --denoise-variance / --adaptive / --variance: the second moments of the batch means */
+    if ( passes > 1 || denoise_var >= 0 || adaptive > 0.f || variance_path ) {
+        const char* why = ( !terra_amd_accumulate_moments || !terra_amd_denoise_variance || !terra_amd_render_adaptive || !terra_amd_render_aov ) ? "need libterra_amd.so" : gpus > 0 ? "do not mirror --gpus (the sharded render)" : NULL;
+        if ( why ) { fprintf ( stderr, "terra_headless: --passes / --denoise-variance / --adaptive / --variance %s; ignored, the plain image is written\n", why ); passes = 1; denoise_var = -1; adaptive = 0.f; variance_path = NULL; }
+        else if ( !( mom = calloc ( W * H, sizeof ( MomentSum ) ) ) ) { fprintf ( stderr, "terra_headless: out of memory\n" ); return 71; }
+    }
     AovSum* aov = NULL;          /* --aov / --denoise: the AOV sums, made by the same calls as the render */
-    if ( aov_prefix || denoise >= 0 ) {
+    if ( aov_prefix || denoise >= 0 || denoise_var >= 0 ) {
         if ( !terra_amd_render_aov || !terra_amd_denoise ) { fprintf ( stderr, "terra_headless: --aov / --denoise need libterra_amd.so; ignored, the plain image is written\n" ); aov_prefix = NULL; denoise = -1; }
         else if ( gpus > 0 ) { fprintf ( stderr, "terra_headless: --aov / --denoise do not mirror --gpus (the sharded render); ignored\n" ); aov_prefix = NULL; denoise = -1; }
         else if ( !( aov = calloc ( W * H, sizeof ( AovSum ) ) ) ) { fprintf ( stderr, "terra_headless: out of memory\n" ); return 71; }
@@ -655,7 +695,21 @@ int main ( int argc, char** argv ) {
     terra_scene_commit ( scene );
     TerraFramebuffer fb;
     if ( !terra_framebuffer_create ( &fb, W, H ) ) { fprintf ( stderr, "terra_headless: bad framebuffer size\n" ); return 65; }
-    if ( gpus > 0 ) ( void ) terra_amd_render_multi ( &cam, scene, &fb, 0, 0, W, H, tile );      /* (tile = the shard's tile size here; 0 = 64) */
+    if ( mom && adaptive > 0.f ) {
+        AdaptiveOptions ao = { tile, min_passes, max_passes, adaptive, 0 }; AdaptiveReport ar; memset ( &ar, 0, sizeof ar );
+        if ( terra_amd_render_adaptive ( &cam, scene, &fb, mom, aov, 0, 0, W, H, &ao, &ar ) != 0 ) { fprintf ( stderr, "terra_headless: %s\n", terra_amd_last_error && *terra_amd_last_error() ? terra_amd_last_error() : "terra_amd_render_adaptive failed" ); return 70; }
+        fprintf ( stderr, "adaptive: %d rounds, %llu tile calls, %llu samples, %d of %d tiles at or below %g, largest error left %g%s\n", ar.rounds, ( unsigned long long ) ar.tile_calls,
+                      ( unsigned long long ) ar.samples, ar.tiles_converged, ar.tiles, ( double ) adaptive, ( double ) ar.max_error, ar.hit_max_batches ? " (--max-passes ended it)" : "" );
+    } else if ( mom ) for ( int pass = 0; pass < passes; ++pass ) {
+        const size_t t = tile ? tile : ( W > H ? W : H );
+        for ( size_t y = 0; y < H; y += t ) for ( size_t x = 0; x < W; x += t ) {
+            const size_t tw = W - x < t ? W - x : t, th = H - y < t ? H - y : t;
+            terra_render ( &cam, scene, &fb, x, y, tw, th );
+            if ( aov ) ( void ) terra_amd_render_aov ( &cam, scene, aov, W, H, x, y, tw, th );
+        }
+        ( void ) terra_amd_accumulate_moments ( scene, &fb, mom, 0, 0, W, H );
+    }
+    else if ( gpus > 0 ) ( void ) terra_amd_render_multi ( &cam, scene, &fb, 0, 0, W, H, tile );      /* (tile = the shard's tile size here; 0 = 64) */
     else if ( tile == 0 ) { terra_render ( &cam, scene, &fb, 0, 0, W, H ); if ( aov ) ( void ) terra_amd_render_aov ( &cam, scene, aov, W, H, 0, 0, W, H ); }
     else for ( size_t y = 0; y < H; y += tile ) for ( size_t x = 0; x < W; x += tile ) {
         const size_t tw = W - x < tile ? W - x : tile, th = H - y < tile ? H - y : tile;
@@ -672,7 +726,9 @@ int main ( int argc, char** argv ) {
         }
     }
     if ( denoise >= 0 && terra_amd_denoise ( scene, &fb, aov, 0, 0, W, H, denoise, NULL, fb.pixels ) != 0 ) { fprintf ( stderr, "terra_headless: %s\n", terra_amd_last_error ? terra_amd_last_error() : "denoise failed" ); return 70; }
-    free ( aov );
+    if ( variance_path && !write_variance_pfm ( variance_path, mom, W, H ) ) { fprintf ( stderr, "terra_headless: cannot write %s\n", variance_path ); return 73; }
+    if ( denoise_var >= 0 && terra_amd_denoise_variance ( scene, &fb, aov, mom, 0, 0, W, H, denoise_var, NULL, fb.pixels ) != 0 ) { fprintf ( stderr, "terra_headless: %s\n", terra_amd_last_error ? terra_amd_last_error() : "denoise failed" ); return 70; }
+    free ( aov ); free ( mom );
     if ( !write_image ( argv[2], &fb ) ) { fprintf ( stderr, "terra_headless: cannot write %s\n", argv[2] ); return 73; }
     printf ( "%s: %zu triangles, %zu materials -> %s (%zux%zu, %zu spp)\n", argv[1], m.faces.n, m.mtls.n, argv[2], W, H, spp );
     terra_framebuffer_destroy ( &fb );

@@ -363,6 +363,108 @@ int terra_amd_denoise_device ( HTerraScene scene, const void* d_results, const v
 int terra_amd_denoise ( HTerraScene scene, const TerraFramebuffer* framebuffer, const TerraAmdAovResult* aov, size_t x, size_t y, size_t width, size_t height,
                         int iterations, TerraFloat3* radiance, TerraFloat3* pixels );
 
+/* ---- Moments buffer: per-pixel variance from batch means -----------------------------------------------------------------------------------------------
+   The render keys its streams by (pixel, samples already in the pixel), so B successive render calls on one framebuffer are B independent batches per pixel, and
+   the sum of a batch is the change of results.acc. terra_amd_accumulate_moments* looks at the framebuffer after a render call and folds that change into a running
+   weighted mean and sum of squared deviations of the batch-mean luminance (West 1979). The render kernels are not involved; a client that never calls these pays
+   nothing. Clear the buffer (all zero) together with the framebuffer; one call per render call, over any rectangle that covers what was rendered.
+   Per pixel of the rectangle, with dn = samples - seen_samples, all arithmetic float32 in exactly this order, no fused multiply-add:
+     dn == 0: the entry is not touched (so one call over a whole frame may follow tile-wise rendering);
+     dn <  0: (the framebuffer was cleared) the entry is set to zero first, then dn = samples; if that is 0 the zero entry is stored;
+     b = (acc - seen_acc) / (float) dn per channel, l = 0.2126 b.x + 0.7152 b.y + 0.0722 b.z (summed left to right);
+     l not finite: seen_acc = acc, seen_samples = samples, nothing else;
+     l finite: W = weight + dn; d = l - mean; mean' = mean + (d * (float) dn) / (float) W; m2 = m2 + ((float) dn * d) * (l - mean'); batches + 1; weight = W; seen_* as above.
+   The variance of the pixel's mean luminance is var = m2 / ((float) weight * (float) (batches - 1)) for batches >= 2 and unknown otherwise; with equal batches that is
+   s^2 / n of the batch means. One lane per pixel, no atomics: the same inputs give the same bits. */
+typedef struct {            /* 32 bytes = two 16-byte words */
+    float seen_acc[3];      /* +0   results.acc at the last accumulate */
+    int   seen_samples;     /* +12  results.samples at the last accumulate */
+    float mean;             /* +16  weighted running mean of the batch-mean luminance */
+    float m2;               /* +20  weighted sum of squared deviations */
+    int   batches;          /* +24  batches counted */
+    int   weight;           /* +28  samples those batches hold */
+} TerraAmdMoments;
+TERRA_ABI_ASSERT ( sizeof ( TerraAmdMoments ) == 32 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdMoments, seen_samples ) == 12 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdMoments, mean ) == 16 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdMoments, m2 ) == 20 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdMoments, batches ) == 24 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdMoments, weight ) == 28 );
+/* d_results as terra_amd_render_device() takes it, d_moments: TerraAmdMoments per pixel of the frame (row-major, fb_width per row) in HBM; asynchronous on `stream`.
+   Fails like the denoiser (kTerraAmdErrNotCommitted, a bad rectangle, a null buffer, a launch error); runs on the scene's primary device. */
+int terra_amd_accumulate_moments_device ( HTerraScene scene, const void* d_results, void* d_moments, size_t fb_width, size_t fb_height,
+                                          size_t x, size_t y, size_t width, size_t height, void* stream );
+/* The same on host buffers (frame-indexed): both are uploaded, the rectangle is folded, the moments are downloaded; synchronous. */
+int terra_amd_accumulate_moments ( HTerraScene scene, const TerraFramebuffer* framebuffer, TerraAmdMoments* moments, size_t x, size_t y, size_t width, size_t height );
+
+/* ---- Tile error ------------------------------------------------------------------------------------------------------------------------------------------
+   One float per tile_size x tile_size tile of the rectangle (clipped at its right and bottom edge), tiles numbered row-major in the rectangle as
+   terra_amd_render_device_sharded() numbers them: d_errors holds ceil(width / tile_size) * ceil(height / tile_size) floats. tile_size: 0 means 128, otherwise a
+   multiple of 16. A tile holding any pixel with batches < 2 reports +INFINITY; otherwise, over its N pixels,
+     e = sqrt(sum var_p / N) / (sum mean_p / N + 1e-3):  the RMS standard error of the pixels' mean luminance relative to the tile's mean luminance.
+   One 256-lane block per tile: lane t sums pixels t, t + 256, ... (row-major inside the clipped tile) in that order, a wave folds its 64 lane sums by adding the lane
+   32, 16, 8, 4, 2, 1 above, and the four wave sums are added in wave order. No atomics: the same inputs give the same bits. d_results is not read (the moments hold
+   the mean); it must not be NULL and keeps the call's shape that of its siblings. Runs on the current device; asynchronous on `stream`. */
+int terra_amd_tile_error_device ( const void* d_results, const void* d_moments, size_t fb_width, size_t fb_height,
+                                  size_t x, size_t y, size_t width, size_t height, size_t tile_size, void* d_errors, void* stream );
+/* The same on host buffers (moments frame-indexed, errors as above); synchronous. */
+int terra_amd_tile_error ( const TerraFramebuffer* framebuffer, const TerraAmdMoments* moments, size_t x, size_t y, size_t width, size_t height, size_t tile_size, float* errors );
+
+/* ---- Variance-guided denoiser (the colour weight of SVGF: Schied et al., HPG 2017) --------------------------------------------------------------------------
+   terra_amd_denoise_device() with one change. Validity, demodulation, h, w_n, w_z, the rescue of non-finite pixels, the output and `iterations` are the "Denoiser"
+   section's. Beside u the filter carries v, the variance of l(u_p), where the pixel is valid and its var (Moments buffer) is known:
+     v_p = var_p * (l(u_p) / max(l(c_p), 1e-6))^2   (unknown if that is not finite).
+   In iteration i, for a centre pixel p with known v_p:
+     g_p = sum k min(v_q, 4 v_p) / sum k over the 3 x 3 pixels q around p (distance 1 whatever the step) that lie in the rectangle, are valid and have known v; k = (1/4 centre, 1/8 edge, 1/16 corner) * w_n(p, q) * w_z(p, q), w_z as in iteration 0;
+     w_c(p, q) = exp(-(|l(u_p) - l(u_q)| / (sigma_l sqrt(g_p) + 1e-6))), sigma_l = 8 (SVGF has 4; DESIGN.md section 15 has the values tried);
+     v'_p = sum W^2 v_q / (sum W)^2, both sums over the taps q with known v (unknown if that sum of W is 0).
+   The cap keeps a neighbour's outlier out of g_p (an honest estimate from B batches has a relative spread of sqrt(2 / (B - 1)), 0.53 at B = 8: four times the centre's
+   is beyond five of those), and w_n w_z keep g_p on p's own surface, so that nothing crosses a geometric edge, the tolerance included. So only the centre's variance sets the tolerance: a quiet pixel rejects a firefly neighbour, a firefly accepts its quiet neighbours. A centre pixel with unknown v (and
+   a pixel being rescued) uses the "Denoiser" section's w_c and stays unknown. With every pixel unknown -- a zeroed moments buffer -- the output is
+   terra_amd_denoise_device()'s bit for bit. */
+int terra_amd_denoise_variance_device ( HTerraScene scene, const void* d_results, const void* d_aov, const void* d_moments, size_t fb_width, size_t fb_height,
+                                        size_t x, size_t y, size_t width, size_t height, int iterations, void* d_radiance, void* d_pixels, void* stream );
+int terra_amd_denoise_variance ( HTerraScene scene, const TerraFramebuffer* framebuffer, const TerraAmdAovResult* aov, const TerraAmdMoments* moments,
+                                 size_t x, size_t y, size_t width, size_t height, int iterations, TerraFloat3* radiance, TerraFloat3* pixels );
+
+/* ---- Adaptive tiles -------------------------------------------------------------------------------------------------------------------------------------------
+   Renders the rectangle in batches of the scene's committed samples_per_pixel, tile by tile, until every tile's error (Tile error) is at most target_error.
+   Round r = 0 .. max_batches - 1: the active tiles are all tiles while r < min_batches, afterwards those whose error of the previous round exceeds target_error; no
+   active tile ends the call. Each active tile, in row-major order, gets one terra_amd_render_device() call on its rectangle (and, where d_aov is given, the
+   terra_amd_render_aov_device() call that mirrors it) -- exactly the calls a client could make itself; then one terra_amd_accumulate_moments_device() and one
+   terra_amd_tile_error_device() call over the whole rectangle, and the errors are read back (the only synchronisation). The call is synchronous; the same inputs
+   give the same bits. The buffers are not cleared: clear framebuffer, moments and AOV buffer together before the first call. */
+typedef struct {
+    size_t tile_size;       /* 0: 128; otherwise a multiple of 16 */
+    int    min_batches;     /* 0: 4; at least 2 (an error needs two batches) */
+    int    max_batches;     /* 0: 64; at least min_batches */
+    float  target_error;    /* 0: 0.05; the tile error at which a tile stops */
+    int    reserved;        /* zero */
+} TerraAmdAdaptiveOptions;
+typedef struct {
+    int      rounds;            /* rounds that rendered something */
+    int      hit_max_batches;   /* 1: tiles were still above target_error when max_batches ended the call */
+    int      tiles;             /* tiles of the rectangle */
+    int      tiles_converged;   /* tiles whose last error is <= target_error */
+    uint64_t tile_calls;        /* terra_amd_render_device() calls made */
+    uint64_t samples;           /* samples added: sum over those calls of the tile's pixels x samples_per_pixel */
+    float    max_error;         /* the largest finite tile error left (0 if none is finite) */
+    int      reserved;
+} TerraAmdAdaptiveReport;
+TERRA_ABI_ASSERT ( sizeof ( TerraAmdAdaptiveOptions ) == 24 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdAdaptiveOptions, min_batches ) == 8 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdAdaptiveOptions, target_error ) == 16 );
+TERRA_ABI_ASSERT ( sizeof ( TerraAmdAdaptiveReport ) == 40 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdAdaptiveReport, tile_calls ) == 16 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdAdaptiveReport, max_error ) == 32 );
+/* options may be NULL (all defaults), report may be NULL, d_aov may be NULL. */
+int terra_amd_render_adaptive_device ( const TerraCamera* camera, HTerraScene scene, void* d_pixels, void* d_results, void* d_moments, void* d_aov,
+                                       size_t fb_width, size_t fb_height, size_t x, size_t y, size_t width, size_t height,
+                                       const TerraAmdAdaptiveOptions* options, TerraAmdAdaptiveReport* report, void* stream );
+/* The same on host buffers: the frame is uploaded, rendered and downloaded (pixels, results, moments and, if given, aov: all frame-indexed). */
+int terra_amd_render_adaptive ( const TerraCamera* camera, HTerraScene scene, TerraFramebuffer* framebuffer, TerraAmdMoments* moments, TerraAmdAovResult* aov,
+                                size_t x, size_t y, size_t width, size_t height, const TerraAmdAdaptiveOptions* options, TerraAmdAdaptiveReport* report );
+
 /* Tile-sharded form for one-process-per-GPU rendering (the reference shards
    the same way over CPU threads: satellite/src/Renderer.cpp:316-350): the
    rectangle is cut into tile_size x tile_size tiles numbered row-major and this

@@ -135,6 +135,30 @@ PROPERTIES_DTYPE = np.dtype((np.float32, (15,)))          # na nb nc (9) + ta tb
 RESULT_DTYPE = np.dtype([("acc", np.float32, (3,)), ("samples", np.int32)])
 assert RESULT_DTYPE.itemsize == 16
 
+# TerraAmdMoments (include/terra_amd.h "Moments buffer"): 32 bytes per pixel
+MOMENTS_DTYPE = np.dtype([("seen_acc", np.float32, (3,)), ("seen_samples", np.int32), ("mean", np.float32), ("m2", np.float32), ("batches", np.int32), ("weight", np.int32)])
+assert MOMENTS_DTYPE.itemsize == 32
+
+
+class TerraAmdMoments(Structure):
+    _fields_ = [("seen_acc", c_float * 3), ("seen_samples", c_int), ("mean", c_float), ("m2", c_float), ("batches", c_int), ("weight", c_int)]
+
+
+class TerraAmdAdaptiveOptions(Structure):
+    """0 in a field: its default (tile 128, min_batches 4, max_batches 64, target_error 0.05)"""
+    _fields_ = [("tile_size", c_size_t), ("min_batches", c_int), ("max_batches", c_int), ("target_error", c_float), ("reserved", c_int)]
+
+
+class TerraAmdAdaptiveReport(Structure):
+    _fields_ = [("rounds", c_int), ("hit_max_batches", c_int), ("tiles", c_int), ("tiles_converged", c_int), ("tile_calls", c_uint64), ("samples", c_uint64),
+                ("max_error", c_float), ("reserved", c_int)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
+
+
+assert C.sizeof(TerraAmdMoments) == 32 and C.sizeof(TerraAmdAdaptiveOptions) == 24 and C.sizeof(TerraAmdAdaptiveReport) == 40
+
 # entry points of include/Terra.h + include/TerraPresets.h, name -> (restype, argtypes)
 API_SIGNATURES = {
     "scene_create": (c_void_p, []),

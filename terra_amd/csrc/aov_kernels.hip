@@ -11,6 +11,7 @@
 // 16x16 blocks, every buffer of the filter indexed over the rectangle. No atomics: the same inputs give the same bits.
 #include <hip/hip_runtime.h>
 #include "trace_device.h"
+#include "denoise_device.h"
 #include "kernels.h"
 
 struct DevAov { float albedo[3]; float coverage; float normal[3]; float depth; int samples; int reserved[3]; };      // TerraAmdAovResult
@@ -116,17 +117,7 @@ hipError_t terra_launch_aov ( DevRenderParams p, void* aov, hipStream_t stream )
 }
 
 // ---- denoiser -----------------------------------------------------------------------------------------------------------
-// Constants of the filter (include/terra_amd.h, tests/test_denoise.py restates them)
-#define TERRA_DN_SIGMA_C2 0.25f         // sigma_c^2 (sigma_c = 0.5: DESIGN.md "AOV buffers and the denoiser", measured against 1)
-#define TERRA_DN_SIGMA_Z  0.05f
-#define TERRA_DN_ALBEDO_MIN 0.01f
-#define TERRA_DN_NORMAL_MIN 1e-6f
-#define TERRA_DN_EPS_C 1e-8f
-#define TERRA_DN_EPS_Z 1e-6f
-// guide state (g1.w): 0 no samples, 1 valid, 2 samples but a non-finite mean (filled from its neighbours in iteration 0)
-
-TD float dn_max ( float a, float b ) { return a > b ? a : b; }
-TD bool dn_finite ( float v ) { return ( __float_as_uint ( v ) & 0x7f800000u ) != 0x7f800000u; }
+// (the filter's constants and per-tap weights: denoise_device.h, shared with the variance-guided form in variance_kernels.hip)
 
 __global__ __launch_bounds__ ( 256 ) void terra_denoise_prepass ( const float4* results, const float4* aov, uint32_t fb_w, uint32_t x, uint32_t y, uint32_t w, uint32_t h,
                                                                   float4* g0, float4* g1, float4* u ) {
@@ -162,12 +153,11 @@ __global__ __launch_bounds__ ( 256 ) void terra_denoise_step ( const float4* g0,
     const float4 up = uin[i];
     const bool pending = it == 0 && g1[i].w == 2.f;
     if ( up.w == 0.f && !pending ) { uout[i] = make_float4 ( 0.f, 0.f, 0.f, 0.f ); return; }
-    const float kh[5] = { 1.f / 16.f, 1.f / 4.f, 3.f / 8.f, 1.f / 4.f, 1.f / 16.f };
     const int step = 1 << it;
     const float sigma_c2 = TERRA_DN_SIGMA_C2 * ldexpf ( 1.f, -2 * it ), zs = TERRA_DN_SIGMA_Z * ( float ) step;
     const float4 gp = g0[i];
     const bool np_zero = gp.x == 0.f && gp.y == 0.f && gp.z == 0.f;
-    const float lp = 0.2126f * up.x + 0.7152f * up.y + 0.0722f * up.z;
+    const float lp = dn_lum ( up.x, up.y, up.z );
     float sw = 0.f, sx = 0.f, sy = 0.f, sz = 0.f;
     for ( int dy = -2; dy <= 2; ++dy ) {
         const int qy = ( int ) ly + step * dy;
@@ -179,22 +169,9 @@ __global__ __launch_bounds__ ( 256 ) void terra_denoise_step ( const float4* g0,
             const float4 uq = uin[q];
             if ( uq.w == 0.f ) continue;
             const float4 gq = g0[q];
-            float wc = 1.f;
-            if ( !pending ) {
-                const float lq = 0.2126f * uq.x + 0.7152f * uq.y + 0.0722f * uq.z;
-                const float ex = up.x - uq.x, ey = up.y - uq.y, ez = up.z - uq.z;
-                wc = expf ( -( ( ex * ex + ey * ey + ez * ez ) / ( sigma_c2 * ( lp * lp + lq * lq ) + TERRA_DN_EPS_C ) ) );
-            }
-            const bool nq_zero = gq.x == 0.f && gq.y == 0.f && gq.z == 0.f;
-            float wn;
-            if ( np_zero || nq_zero ) wn = ( np_zero && nq_zero ) ? 1.f : 0.f;
-            else {
-                wn = dn_max ( 0.f, gp.x * gq.x + gp.y * gq.y + gp.z * gq.z );
-                #pragma unroll
-                for ( int k = 0; k < 7; ++k ) wn = wn * wn;          // ^128
-            }
-            const float wz = expf ( -( fabsf ( gp.w - gq.w ) / ( zs * dn_max ( gp.w, gq.w ) + TERRA_DN_EPS_Z ) ) );
-            const float W = ( ( ( kh[dx + 2] * kh[dy + 2] ) * wc ) * wn ) * wz;
+            const float wc = pending ? 1.f : dn_weight_colour ( up, uq, lp, dn_lum ( uq.x, uq.y, uq.z ), sigma_c2 );
+            const float wn = dn_weight_normal ( gp, gq, np_zero ), wz = dn_weight_depth ( gp, gq, zs );
+            const float W = ( ( ( dn_kernel ( dx ) * dn_kernel ( dy ) ) * wc ) * wn ) * wz;
             sw = sw + W; sx = sx + W * uq.x; sy = sy + W * uq.y; sz = sz + W * uq.z;
         }
     }
@@ -247,4 +224,20 @@ hipError_t terra_launch_denoise ( const void* results, const void* aov, uint32_t
     const hipError_t e = hipGetLastError();
     if ( scratch ) ( void ) hipFreeAsync ( scratch, stream );
     return e;
+}
+
+// the filter's first and last kernel on their own, for the variance-guided form (variance_kernels.hip), which runs its own steps between them:
+// g0, g1, u are planes of w * h float4 indexed over the rectangle
+hipError_t terra_launch_denoise_prepass ( const void* results, const void* aov, uint32_t fb_w, uint32_t x, uint32_t y, uint32_t w, uint32_t h, void* g0, void* g1, void* u, hipStream_t stream ) {
+    const dim3 grid ( ( w + 15u ) / 16u, ( h + 15u ) / 16u ), block ( 16, 16 );
+    hipLaunchKernelGGL ( terra_denoise_prepass, grid, block, 0, stream, reinterpret_cast<const float4*> ( results ), reinterpret_cast<const float4*> ( aov ), fb_w, x, y, w, h,
+                         reinterpret_cast<float4*> ( g0 ), reinterpret_cast<float4*> ( g1 ), reinterpret_cast<float4*> ( u ) );
+    return hipGetLastError();
+}
+hipError_t terra_launch_denoise_finish ( const void* results, const void* g1, const void* u, uint32_t fb_w, uint32_t x, uint32_t y, uint32_t w, uint32_t h, int iterations,
+                                         float exposure, int op, float gamma, float* radiance, float* pixels, hipStream_t stream ) {
+    const dim3 grid ( ( w + 15u ) / 16u, ( h + 15u ) / 16u ), block ( 16, 16 );
+    hipLaunchKernelGGL ( terra_denoise_finish, grid, block, 0, stream, reinterpret_cast<const float4*> ( results ), reinterpret_cast<const float4*> ( g1 ), reinterpret_cast<const float4*> ( u ),
+                         fb_w, x, y, w, h, iterations, exposure, op, gamma, radiance, pixels );
+    return hipGetLastError();
 }

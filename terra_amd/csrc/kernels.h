@@ -33,6 +33,18 @@ hipError_t terra_launch_aov ( DevRenderParams p, void* aov, hipStream_t stream )
 hipError_t terra_launch_denoise ( const void* results, const void* aov, uint32_t fb_w, uint32_t x, uint32_t y, uint32_t w, uint32_t h, int iterations,
                                   float exposure, int op, float gamma, float* radiance, float* pixels, hipStream_t stream );
 
+// the a-trous filter's first and last kernel on their own (aov_kernels.hip), for the variance-guided form: g0, g1, u are planes of w * h float4 over the rectangle
+hipError_t terra_launch_denoise_prepass ( const void* results, const void* aov, uint32_t fb_w, uint32_t x, uint32_t y, uint32_t w, uint32_t h, void* g0, void* g1, void* u, hipStream_t stream );
+hipError_t terra_launch_denoise_finish ( const void* results, const void* g1, const void* u, uint32_t fb_w, uint32_t x, uint32_t y, uint32_t w, uint32_t h, int iterations,
+                                         float exposure, int op, float gamma, float* radiance, float* pixels, hipStream_t stream );
+
+// second moments, tile error and the variance-guided denoiser (variance_kernels.hip): results / moments (TerraAmdMoments) / aov / radiance / pixels indexed like a frame
+// of fb_w pixels per row, only the rectangle is read or written; errors: one float per tile x tile tile of the rectangle, row-major
+hipError_t terra_launch_moments_accumulate ( const void* results, void* moments, uint32_t fb_w, uint32_t x, uint32_t y, uint32_t w, uint32_t h, hipStream_t stream );
+hipError_t terra_launch_tile_error ( const void* moments, uint32_t fb_w, uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint32_t tile, float* errors, hipStream_t stream );
+hipError_t terra_launch_denoise_variance ( const void* results, const void* aov, const void* moments, uint32_t fb_w, uint32_t x, uint32_t y, uint32_t w, uint32_t h, int iterations,
+                                           float exposure, int op, float gamma, float* radiance, float* pixels, hipStream_t stream );
+
 hipError_t terra_fill_sincos24 ( float2* table, hipStream_t stream );    // DevScene::sincos24: 2^24 entries (128 MB), device pointer
 
 // unit-level launchers: all pointers are DEVICE pointers, n items, synchronous semantics left to the caller

@@ -1636,6 +1636,178 @@ extern "C" int terra_amd_denoise ( HTerraScene h, const TerraFramebuffer* fb, co
     return 0;
 }
 
+// ---- moments, tile error, variance-guided denoiser, adaptive tiles (variance_kernels.hip) ----------------------------------------
+static_assert ( sizeof ( TerraAmdMoments ) == 32, "TerraAmdMoments must be 32 bytes" );
+static int rect_check ( const char* what, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t h ) {
+    if ( w == 0 || h == 0 || x + w > fb_w || y + h > fb_h || fb_w > 0xffffffffull || fb_h > 0xffffffffull ) return fail ( kTerraAmdErrBadArgument, "bad %s rectangle %zu,%zu %zux%zu in %zux%zu", what, x, y, w, h, fb_w, fb_h );
+    return 0;
+}
+static int tile_size_check ( size_t& tile ) {
+    if ( tile == 0 ) tile = 128;
+    if ( tile % 16 || tile > 32768 ) return fail ( kTerraAmdErrBadArgument, "tile size %zu: 0 (128) or a multiple of 16 up to 32768", tile );
+    return 0;
+}
+// a frame's worth of host buffers on the device for the synchronous host forms: up to four buffers of `stride[k]` bytes per pixel
+struct FrameCopy {
+    char* d[4] = { nullptr, nullptr, nullptr, nullptr };
+    ~FrameCopy() { for ( char* p : d ) if ( p ) ( void ) hipFree ( p ); }
+    hipError_t up ( int k, const void* host, size_t bytes ) {
+        hipError_t e = hipMalloc ( ( void** ) &d[k], bytes );
+        if ( e == hipSuccess ) e = host ? hipMemcpy ( d[k], host, bytes, hipMemcpyHostToDevice ) : hipMemset ( d[k], 0, bytes );
+        return e;
+    }
+    hipError_t down ( int k, void* host, size_t bytes ) const { return hipMemcpy ( host, d[k], bytes, hipMemcpyDeviceToHost ); }
+};
+extern "C" int terra_amd_accumulate_moments_device ( HTerraScene h, const void* d_results, void* d_moments, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t hgt, void* stream ) {
+    Scene* s = S ( h );
+    if ( int rc = denoise_check ( s, fb_w, fb_h, x, y, w, hgt, 0 ) ) return rc;
+    if ( int rc = rect_check ( "moments", fb_w, fb_h, x, y, w, hgt ) ) return rc;
+    if ( !d_results || !d_moments ) return fail ( kTerraAmdErrBadArgument, "null framebuffer or moments buffer" );
+    HIP_TRY ( hipSetDevice ( primary ( s ).device ), kTerraAmdErrNoDevice );
+    const hipError_t e = terra_launch_moments_accumulate ( d_results, d_moments, ( uint32_t ) fb_w, ( uint32_t ) x, ( uint32_t ) y, ( uint32_t ) w, ( uint32_t ) hgt, ( hipStream_t ) stream );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "moments launch: %s", hipGetErrorString ( e ) );
+    return 0;
+}
+extern "C" int terra_amd_accumulate_moments ( HTerraScene h, const TerraFramebuffer* fb, TerraAmdMoments* moments, size_t x, size_t y, size_t w, size_t hgt ) {
+    Scene* s = S ( h );
+    if ( !fb || !fb->results || !moments ) return fail ( kTerraAmdErrBadArgument, "null framebuffer or moments buffer" );
+    if ( int rc = denoise_check ( s, fb->width, fb->height, x, y, w, hgt, 0 ) ) return rc;
+    HIP_TRY ( hipSetDevice ( primary ( s ).device ), kTerraAmdErrNoDevice );
+    const size_t n = fb->width * fb->height;
+    FrameCopy c;
+    hipError_t e = c.up ( 0, fb->results, n * 16 );
+    if ( e == hipSuccess ) e = c.up ( 1, moments, n * 32 );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "moments upload: %s", hipGetErrorString ( e ) );
+    if ( int rc = terra_amd_accumulate_moments_device ( h, c.d[0], c.d[1], fb->width, fb->height, x, y, w, hgt, nullptr ) ) return rc;
+    e = c.down ( 1, moments, n * 32 );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "moments download: %s", hipGetErrorString ( e ) );
+    return 0;
+}
+extern "C" int terra_amd_tile_error_device ( const void* d_results, const void* d_moments, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t hgt, size_t tile, void* d_errors, void* stream ) {
+    if ( int rc = rect_check ( "tile error", fb_w, fb_h, x, y, w, hgt ) ) return rc;
+    if ( int rc = tile_size_check ( tile ) ) return rc;
+    if ( !d_results || !d_moments || !d_errors ) return fail ( kTerraAmdErrBadArgument, "null framebuffer, moments or error buffer" );
+    const hipError_t e = terra_launch_tile_error ( d_moments, ( uint32_t ) fb_w, ( uint32_t ) x, ( uint32_t ) y, ( uint32_t ) w, ( uint32_t ) hgt, ( uint32_t ) tile, ( float* ) d_errors, ( hipStream_t ) stream );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "tile error launch: %s", hipGetErrorString ( e ) );
+    return 0;
+}
+extern "C" int terra_amd_tile_error ( const TerraFramebuffer* fb, const TerraAmdMoments* moments, size_t x, size_t y, size_t w, size_t hgt, size_t tile, float* errors ) {
+    if ( !fb || !fb->results || !moments || !errors ) return fail ( kTerraAmdErrBadArgument, "null framebuffer, moments or error buffer" );
+    if ( int rc = rect_check ( "tile error", fb->width, fb->height, x, y, w, hgt ) ) return rc;
+    if ( int rc = tile_size_check ( tile ) ) return rc;
+    const size_t n = fb->width * fb->height, tiles = ( ( w + tile - 1 ) / tile ) * ( ( hgt + tile - 1 ) / tile );
+    FrameCopy c;
+    hipError_t e = c.up ( 0, moments, n * 32 );
+    if ( e == hipSuccess ) e = c.up ( 1, nullptr, tiles * sizeof ( float ) );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "tile error upload: %s", hipGetErrorString ( e ) );
+    if ( int rc = terra_amd_tile_error_device ( c.d[0], c.d[0], fb->width, fb->height, x, y, w, hgt, tile, c.d[1], nullptr ) ) return rc;      // (the results are not read)
+    e = c.down ( 1, errors, tiles * sizeof ( float ) );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "tile error download: %s", hipGetErrorString ( e ) );
+    return 0;
+}
+extern "C" int terra_amd_denoise_variance_device ( HTerraScene h, const void* d_results, const void* d_aov, const void* d_moments, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t hgt,
+                                                   int iterations, void* d_radiance, void* d_pixels, void* stream ) {
+    Scene* s = S ( h );
+    if ( int rc = denoise_check ( s, fb_w, fb_h, x, y, w, hgt, iterations ) ) return rc;
+    if ( !d_results || !d_aov || !d_moments ) return fail ( kTerraAmdErrBadArgument, "null framebuffer, AOV or moments buffer" );
+    HIP_TRY ( hipSetDevice ( primary ( s ).device ), kTerraAmdErrNoDevice );
+    const hipError_t e = terra_launch_denoise_variance ( d_results, d_aov, d_moments, ( uint32_t ) fb_w, ( uint32_t ) x, ( uint32_t ) y, ( uint32_t ) w, ( uint32_t ) hgt, iterations, s->opts.manual_exposure,
+                                                         ( int ) s->opts.tonemapping_operator, s->opts.gamma, ( float* ) d_radiance, ( float* ) d_pixels, ( hipStream_t ) stream );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "variance denoise launch: %s", hipGetErrorString ( e ) );
+    return 0;
+}
+extern "C" int terra_amd_denoise_variance ( HTerraScene h, const TerraFramebuffer* fb, const TerraAmdAovResult* aov, const TerraAmdMoments* moments, size_t x, size_t y, size_t w, size_t hgt,
+                                            int iterations, TerraFloat3* radiance, TerraFloat3* pixels ) {
+    Scene* s = S ( h );
+    if ( !fb || !fb->results || !aov || !moments ) return fail ( kTerraAmdErrBadArgument, "null framebuffer, AOV or moments buffer" );
+    if ( int rc = denoise_check ( s, fb->width, fb->height, x, y, w, hgt, iterations ) ) return rc;
+    if ( !radiance && !pixels ) return 0;
+    HIP_TRY ( hipSetDevice ( primary ( s ).device ), kTerraAmdErrNoDevice );
+    const size_t n = fb->width * fb->height;
+    FrameCopy c, o;
+    hipError_t e = c.up ( 0, fb->results, n * 16 );
+    if ( e == hipSuccess ) e = c.up ( 1, aov, n * 48 );
+    if ( e == hipSuccess ) e = c.up ( 2, moments, n * 32 );
+    if ( e == hipSuccess ) e = o.up ( 0, radiance, n * 12 );
+    if ( e == hipSuccess ) e = o.up ( 1, pixels, n * 12 );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "variance denoise upload: %s", hipGetErrorString ( e ) );
+    if ( int rc = terra_amd_denoise_variance_device ( h, c.d[0], c.d[1], c.d[2], fb->width, fb->height, x, y, w, hgt, iterations, radiance ? o.d[0] : nullptr, pixels ? o.d[1] : nullptr, nullptr ) ) return rc;
+    if ( radiance ) e = o.down ( 0, radiance, n * 12 );
+    if ( e == hipSuccess && pixels ) e = o.down ( 1, pixels, n * 12 );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "variance denoise download: %s", hipGetErrorString ( e ) );
+    return 0;
+}
+extern "C" int terra_amd_render_adaptive_device ( const TerraCamera* cam, HTerraScene h, void* d_pixels, void* d_results, void* d_moments, void* d_aov, size_t fb_w, size_t fb_h,
+                                                  size_t x, size_t y, size_t w, size_t hgt, const TerraAmdAdaptiveOptions* options, TerraAmdAdaptiveReport* report, void* stream ) {
+    Scene* s = S ( h );
+    if ( int rc = denoise_check ( s, fb_w, fb_h, x, y, w, hgt, 0 ) ) return rc;
+    if ( int rc = rect_check ( "adaptive", fb_w, fb_h, x, y, w, hgt ) ) return rc;
+    if ( !cam || !d_pixels || !d_results || !d_moments ) return fail ( kTerraAmdErrBadArgument, "null camera, framebuffer or moments buffer" );
+    size_t tile = options ? options->tile_size : 0;
+    if ( int rc = tile_size_check ( tile ) ) return rc;
+    const int min_b = options && options->min_batches ? options->min_batches : 4, max_b = options && options->max_batches ? options->max_batches : 64;
+    const float target = options && options->target_error != 0.f ? options->target_error : 0.05f;
+    if ( min_b < 2 || max_b < min_b || ! ( target > 0.f ) ) return fail ( kTerraAmdErrBadArgument, "adaptive options: min_batches %d (>= 2), max_batches %d (>= min_batches), target_error %g (> 0)", min_b, max_b, ( double ) target );
+    HIP_TRY ( hipSetDevice ( primary ( s ).device ), kTerraAmdErrNoDevice );
+    const size_t tiles_x = ( w + tile - 1 ) / tile, tiles_y = ( hgt + tile - 1 ) / tile, tiles = tiles_x * tiles_y;
+    const size_t spp = s->opts.samples_per_pixel;
+    std::vector<float> err ( tiles, INFINITY );
+    float* d_err = nullptr;
+    HIP_TRY ( hipMalloc ( ( void** ) &d_err, tiles * sizeof ( float ) ), kTerraAmdErrNoDevice );
+    TerraAmdAdaptiveReport rep = {};
+    rep.tiles = ( int ) tiles;
+    int rc = 0;
+    for ( int r = 0; r < max_b && !rc; ++r ) {
+        size_t active = 0;
+        for ( size_t t = 0; t < tiles && !rc; ++t ) {
+            if ( r >= min_b && ! ( err[t] > target ) ) continue;
+            const size_t x0 = ( t % tiles_x ) * tile, y0 = ( t / tiles_x ) * tile, tw = std::min ( tile, w - x0 ), th = std::min ( tile, hgt - y0 );
+            rc = terra_amd_render_device ( cam, h, d_pixels, d_results, fb_w, fb_h, x + x0, y + y0, tw, th, nullptr, stream );
+            if ( !rc && d_aov ) rc = terra_amd_render_aov_device ( cam, h, d_aov, fb_w, fb_h, x + x0, y + y0, tw, th, stream );
+            ++active; ++rep.tile_calls; rep.samples += ( uint64_t ) tw * th * spp;
+        }
+        if ( active == 0 || rc ) break;
+        ++rep.rounds;
+        rc = terra_amd_accumulate_moments_device ( h, d_results, d_moments, fb_w, fb_h, x, y, w, hgt, stream );
+        if ( !rc ) rc = terra_amd_tile_error_device ( d_results, d_moments, fb_w, fb_h, x, y, w, hgt, tile, d_err, stream );
+        if ( !rc ) {
+            hipError_t e = hipMemcpyAsync ( err.data(), d_err, tiles * sizeof ( float ), hipMemcpyDeviceToHost, ( hipStream_t ) stream );
+            if ( e == hipSuccess ) e = hipStreamSynchronize ( ( hipStream_t ) stream );
+            if ( e != hipSuccess ) rc = fail ( kTerraAmdErrLaunch, "adaptive error readback: %s", hipGetErrorString ( e ) );
+        }
+    }
+    ( void ) hipFree ( d_err );
+    if ( rc ) return rc;
+    for ( size_t t = 0; t < tiles; ++t ) {
+        if ( err[t] <= target ) ++rep.tiles_converged;
+        if ( std::isfinite ( err[t] ) && err[t] > rep.max_error ) rep.max_error = err[t];
+    }
+    rep.hit_max_batches = rep.tiles_converged < rep.tiles ? 1 : 0;
+    if ( report ) *report = rep;
+    return 0;
+}
+extern "C" int terra_amd_render_adaptive ( const TerraCamera* cam, HTerraScene h, TerraFramebuffer* fb, TerraAmdMoments* moments, TerraAmdAovResult* aov, size_t x, size_t y, size_t w, size_t hgt,
+                                           const TerraAmdAdaptiveOptions* options, TerraAmdAdaptiveReport* report ) {
+    Scene* s = S ( h );
+    if ( !fb || !fb->results || !fb->pixels || !moments ) return fail ( kTerraAmdErrBadArgument, "null framebuffer or moments buffer" );
+    if ( int rc = denoise_check ( s, fb->width, fb->height, x, y, w, hgt, 0 ) ) return rc;
+    HIP_TRY ( hipSetDevice ( primary ( s ).device ), kTerraAmdErrNoDevice );
+    const size_t n = fb->width * fb->height;
+    FrameCopy c;
+    hipError_t e = c.up ( 0, fb->pixels, n * 12 );
+    if ( e == hipSuccess ) e = c.up ( 1, fb->results, n * 16 );
+    if ( e == hipSuccess ) e = c.up ( 2, moments, n * 32 );
+    if ( e == hipSuccess && aov ) e = c.up ( 3, aov, n * 48 );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "adaptive upload: %s", hipGetErrorString ( e ) );
+    if ( int rc = terra_amd_render_adaptive_device ( cam, h, c.d[0], c.d[1], c.d[2], aov ? c.d[3] : nullptr, fb->width, fb->height, x, y, w, hgt, options, report, nullptr ) ) return rc;
+    e = c.down ( 0, fb->pixels, n * 12 );
+    if ( e == hipSuccess ) e = c.down ( 1, fb->results, n * 16 );
+    if ( e == hipSuccess ) e = c.down ( 2, moments, n * 32 );
+    if ( e == hipSuccess && aov ) e = c.down ( 3, aov, n * 48 );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "adaptive download: %s", hipGetErrorString ( e ) );
+    return 0;
+}
+
 // ---- tile pack/unpack ------------------------------------------------------------
 static uint32_t tiles_of_rank ( size_t w, size_t h, size_t tile, int rank, int world ) {
     size_t tiles = ( ( w + tile - 1 ) / tile ) * ( ( h + tile - 1 ) / tile );

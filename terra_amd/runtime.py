@@ -115,6 +115,16 @@ _EXTRA = {
     "terra_amd_render_aov": (C.c_int, [_CAM, C.c_void_p, C.c_void_p] + [_SZ] * 6),
     "terra_amd_denoise_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [_SZ] * 6 + [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "terra_amd_denoise": (C.c_int, [C.c_void_p, C.POINTER(api.TerraFramebuffer), C.c_void_p] + [_SZ] * 4 + [C.c_int, C.c_void_p, C.c_void_p]),
+    "terra_amd_accumulate_moments_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [_SZ] * 6 + [C.c_void_p]),
+    "terra_amd_accumulate_moments": (C.c_int, [C.c_void_p, C.POINTER(api.TerraFramebuffer), C.c_void_p] + [_SZ] * 4),
+    "terra_amd_tile_error_device": (C.c_int, [C.c_void_p, C.c_void_p] + [_SZ] * 7 + [C.c_void_p, C.c_void_p]),
+    "terra_amd_tile_error": (C.c_int, [C.POINTER(api.TerraFramebuffer), C.c_void_p] + [_SZ] * 5 + [C.c_void_p]),
+    "terra_amd_denoise_variance_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [_SZ] * 6 + [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "terra_amd_denoise_variance": (C.c_int, [C.c_void_p, C.POINTER(api.TerraFramebuffer), C.c_void_p, C.c_void_p] + [_SZ] * 4 + [C.c_int, C.c_void_p, C.c_void_p]),
+    "terra_amd_render_adaptive_device": (C.c_int, [_CAM, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [_SZ] * 6 +
+                                         [C.POINTER(api.TerraAmdAdaptiveOptions), C.POINTER(api.TerraAmdAdaptiveReport), C.c_void_p]),
+    "terra_amd_render_adaptive": (C.c_int, [_CAM, C.c_void_p, C.POINTER(api.TerraFramebuffer), C.c_void_p, C.c_void_p] + [_SZ] * 4 +
+                                  [C.POINTER(api.TerraAmdAdaptiveOptions), C.POINTER(api.TerraAmdAdaptiveReport)]),
 }
 
 
@@ -234,6 +244,64 @@ def denoise_device(lib, scene, fb: DeviceFramebuffer, aov: DeviceAov, iterations
     x, y, w, h = rect if rect else (0, 0, fb.width, fb.height)
     check(lib.denoise_device(scene, fb.results.data_ptr(), aov.data.data_ptr(), fb.width, fb.height, x, y, w, h, iterations,
                              radiance.data_ptr() if radiance is not None else None, pixels.data_ptr() if pixels is not None else None, stream), "terra_amd_denoise_device")
+
+
+class DeviceMoments:
+    """A TerraAmdMoments buffer in HBM (8 words per pixel), the companion of a DeviceFramebuffer: clear both together and call
+    accumulate_moments_device after each render call."""
+
+    def __init__(self, width: int, height: int, device: str = "cuda"):
+        import torch
+        self.width, self.height = width, height
+        self.data = torch.zeros(height * width * 8, dtype=torch.int32, device=device)
+
+    def clear(self):
+        self.data.zero_()
+
+    def host(self) -> np.ndarray:
+        """api.MOMENTS_DTYPE records (height, width)"""
+        return self.data.cpu().numpy().view(api.MOMENTS_DTYPE).reshape(self.height, self.width)
+
+    def variance_host(self) -> np.ndarray:
+        """var of each pixel's mean luminance, float32 as the device computes it; -1 where it is unknown (batches < 2)"""
+        m = self.host()
+        known = m["batches"] >= 2
+        den = np.where(known, m["weight"].astype(np.float32) * (m["batches"] - 1).astype(np.float32), np.float32(1))
+        return np.where(known, m["m2"] / den, np.float32(-1)).astype(np.float32)
+
+
+def accumulate_moments_device(lib, scene, fb: DeviceFramebuffer, moments: DeviceMoments, rect: Optional[Tuple[int, int, int, int]] = None, stream=None):
+    x, y, w, h = rect if rect else (0, 0, fb.width, fb.height)
+    check(lib.accumulate_moments_device(scene, fb.results.data_ptr(), moments.data.data_ptr(), fb.width, fb.height, x, y, w, h, stream), "terra_amd_accumulate_moments_device")
+
+
+def tile_error_device(lib, fb: DeviceFramebuffer, moments: DeviceMoments, tile: int = 0, rect: Optional[Tuple[int, int, int, int]] = None, stream=None):
+    """terra_amd_tile_error_device: a float32 tensor of one error per tile of the rectangle, row-major (tile 0: 128)"""
+    import torch
+    x, y, w, h = rect if rect else (0, 0, fb.width, fb.height)
+    t = tile or 128
+    out = torch.zeros(max(1, -(-w // t) * -(-h // t)), dtype=torch.float32, device=fb.results.device)
+    check(lib.tile_error_device(fb.results.data_ptr(), moments.data.data_ptr(), fb.width, fb.height, x, y, w, h, tile, out.data_ptr(), stream), "terra_amd_tile_error_device")
+    return out
+
+
+def denoise_variance_device(lib, scene, fb: DeviceFramebuffer, aov: DeviceAov, moments: DeviceMoments, iterations: int, rect: Optional[Tuple[int, int, int, int]] = None,
+                            radiance=None, pixels=None, stream=None):
+    """terra_amd_denoise_variance_device; arguments as denoise_device"""
+    x, y, w, h = rect if rect else (0, 0, fb.width, fb.height)
+    check(lib.denoise_variance_device(scene, fb.results.data_ptr(), aov.data.data_ptr(), moments.data.data_ptr(), fb.width, fb.height, x, y, w, h, iterations,
+                                      radiance.data_ptr() if radiance is not None else None, pixels.data_ptr() if pixels is not None else None, stream), "terra_amd_denoise_variance_device")
+
+
+def render_adaptive_device(lib, cam, scene, fb: DeviceFramebuffer, moments: DeviceMoments, aov: Optional[DeviceAov] = None, rect: Optional[Tuple[int, int, int, int]] = None,
+                           tile: int = 0, min_batches: int = 0, max_batches: int = 0, target_error: float = 0.0, stream=None) -> dict:
+    """terra_amd_render_adaptive_device (synchronous); returns the report as a dict"""
+    x, y, w, h = rect if rect else (0, 0, fb.width, fb.height)
+    opt = api.TerraAmdAdaptiveOptions(tile, min_batches, max_batches, target_error, 0)
+    rep = api.TerraAmdAdaptiveReport()
+    check(lib.render_adaptive_device(C.byref(cam), scene, fb.pixels.data_ptr(), fb.results.data_ptr(), moments.data.data_ptr(), aov.data.data_ptr() if aov is not None else None,
+                                     fb.width, fb.height, x, y, w, h, C.byref(opt), C.byref(rep), stream), "terra_amd_render_adaptive_device")
+    return rep.as_dict()
 
 
 def render_device_sharded(lib, cam, scene, fb: DeviceFramebuffer, tile: int, rank: int, world: int, stream=None):

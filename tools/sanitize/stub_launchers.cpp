@@ -37,3 +37,12 @@ void terra_plan_fast_tree ( DevRenderParams& p ) { p.lds_mode = 2; p.lds_tris = 
 size_t terra_fast_spill_bytes ( const DevRenderParams& ) { return 0; }
 size_t terra_lds_bytes ( const DevRenderParams& ) { return 0; }
 size_t terra_lds_block_limit ( void ) { return 156 * 1024; }
+hipError_t terra_launch_aov ( DevRenderParams, void*, hipStream_t ) { return hipErrorNoDevice; }
+hipError_t terra_launch_denoise ( const void*, const void*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, int, float, int, float, float*, float*, hipStream_t ) { return hipErrorNoDevice; }
+hipError_t terra_launch_denoise_prepass ( const void*, const void*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, void*, void*, void*, hipStream_t ) { return hipErrorNoDevice; }
+hipError_t terra_launch_denoise_finish ( const void*, const void*, const void*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, int, float, int, float, float*, float*, hipStream_t ) { return hipErrorNoDevice; }
+hipError_t terra_launch_moments_accumulate ( const void*, void*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, hipStream_t ) { return hipErrorNoDevice; }
+hipError_t terra_launch_tile_error ( const void*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, float*, hipStream_t ) { return hipErrorNoDevice; }
+hipError_t terra_launch_denoise_variance ( const void*, const void*, const void*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, int, float, int, float, float*, float*, hipStream_t ) { return hipErrorNoDevice; }
+hipError_t terra_unit_texture_sample ( const DevTexture*, int, const float*, float* ) { return hipErrorNoDevice; }
+hipError_t terra_unit_texture_latlong ( const DevTexture*, int, const float*, float* ) { return hipErrorNoDevice; }
