@@ -33,6 +33,7 @@
  *       [--no-flip-z] [--normals apollo|file] [--dump-scene file] [--no-render] [--fast-tree | --replica-tree] [--sample-split n] [--seed n] [--tile n] [--gpus n]
  *       [--environment map.hdr|map.pfm] [--environment-color r g b] [--env-light] [--env-sampling off|table|mis] [--aov PREFIX] [--denoise K]
  *       [--passes N] [--denoise-variance K] [--adaptive TARGET [--min-passes A] [--max-passes B]] [--variance out.pfm]
+ *       [--frames N] [--camera-to px py pz dx dy dz] [--temporal ALPHA]
  *
  * Environment: the scene's environment attribute is a constant (--environment-color, default 0.4 0.52 1) or a lat-long map (--environment: Radiance .hdr with flat
  * or new-style run-length-encoded scanlines, orientation -Y H +X W, texel = m 2^(e - 136); or .pfm, either byte order, bottom row first), bound as a 3-component
@@ -51,6 +52,7 @@ const char* terra_amd_last_error ( void ) __attribute__ ( ( weak ) );
 int         terra_amd_set_tree_mode ( HTerraScene, int ) __attribute__ ( ( weak ) );
 int         terra_amd_set_sample_split ( HTerraScene, int ) __attribute__ ( ( weak ) );
 void        terra_amd_set_frame_seed ( HTerraScene, uint64_t ) __attribute__ ( ( weak ) );
+uint64_t    terra_amd_get_frame_seed ( HTerraScene ) __attribute__ ( ( weak ) );
 int         terra_amd_init ( void ) __attribute__ ( ( weak ) );
 int         terra_amd_set_devices ( const int*, int ) __attribute__ ( ( weak ) );
 int         terra_amd_device_count ( void ) __attribute__ ( ( weak ) );
@@ -69,6 +71,12 @@ typedef struct { int rounds; int hit_max_batches; int tiles; int tiles_converged
 int         terra_amd_accumulate_moments ( HTerraScene, const TerraFramebuffer*, void*, size_t, size_t, size_t, size_t ) __attribute__ ( ( weak ) );
 int         terra_amd_denoise_variance ( HTerraScene, const TerraFramebuffer*, const void*, const void*, size_t, size_t, size_t, size_t, int, TerraFloat3*, TerraFloat3* ) __attribute__ ( ( weak ) );
 int         terra_amd_render_adaptive ( const TerraCamera*, HTerraScene, TerraFramebuffer*, void*, void*, size_t, size_t, size_t, size_t, const void*, void* ) __attribute__ ( ( weak ) );
+
+/* the per-pixel history of the temporal reprojection (TerraAmdHistory, TerraAmdTemporalOptions of terra_amd.h, restated for the same reason) */
+typedef struct { float radiance[3]; float length; float normal[3]; float depth; float mu1, mu2; float reserved[2]; } HistoryEntry;
+typedef struct { float alpha; float depth_tolerance; float normal_cos; int reserved; } TemporalOptions;
+int         terra_amd_reproject ( HTerraScene, const TerraCamera*, const TerraCamera*, const TerraFramebuffer*, const void*, const void*, void*, void*, void*,
+                                  size_t, size_t, size_t, size_t, const void* ) __attribute__ ( ( weak ) );
 
 /* ---- growable arrays ------------------------------------------------------------------------ */
 #define VEC(T) struct { T* d; size_t n, cap; }
@@ -574,6 +582,13 @@ static const char* kHelp =
     "  --adaptive TARGET [--min-passes A --max-passes B] (libterra_amd.so only): passes per --tile (0 = 128) tile until its relative error is at most TARGET\n"
     "           (terra_amd_render_adaptive); the report goes to stderr\n"
     "  --variance out.pfm (libterra_amd.so only): the variance of each pixel's mean luminance after --passes / --adaptive\n"
+    "  --frames N [--camera-to px py pz dx dy dz]: N frames, frame f under the camera interpolated linearly between --camera and --camera-to (position and direction;\n"
+    "           f / (N - 1) of the way); each frame clears the framebuffer, renders --passes passes and is written to out.0000.ext, out.0001.ext ...\n"
+    "           With libterra_amd.so frame f renders under the frame seed --seed + f * 2^32 (terra_amd_set_frame_seed): seeds closer than the frame has pixels\n"
+    "           would repeat one noise field, moved along the rows\n"
+    "  --temporal ALPHA (libterra_amd.so only, with --frames and --denoise K or --denoise-variance K): each frame also gets its AOV pass and is blended into the\n"
+    "           history of the frames before it, reprojected to where each surface lay under the previous camera (terra_amd_reproject; ALPHA in (0, 1], 0 = 0.2);\n"
+    "           the blended frame is written through that filter (the variance of --denoise-variance is the history's own)\n"
     "OBJ/MTL import (--normals apollo, the default): the policy of the reference client's importer (satellite/include/Apollo.h under the\n"
     "options of satellite/src/Scene.cpp:83-93) RESTATED in this tool and pinned by hand-derived fixtures -- restated, not executed: Apollo.h\n"
     "does not compile with this image's toolchains. Everything after the TerraObject fill (commit, render, export) is the pinned path.\n";
@@ -586,6 +601,7 @@ int main ( int argc, char** argv ) {
     int integrator = kTerraIntegratorDirect, tonemap = kTerraTonemappingOperatorLinear, flip = 1, fast = -1, have_seed = 0, split = -1, apollo = 1, gpus = 0;
     const char* aov_prefix = NULL; int denoise = -1;
     int passes = 1, denoise_var = -1, min_passes = 0, max_passes = 0; float adaptive = 0.f; const char* variance_path = NULL;
+    int frames = 0, have_camera_to = 0; float temporal = -1.f; TerraCamera cam_to; memset ( &cam_to, 0, sizeof cam_to );
     const char* dump_path = NULL; int no_render = 0;
     float fov = 45.f, exposure = 1.f, gamma = 2.2f, jitter = 0.f;
     unsigned long long seed = 0;
@@ -626,6 +642,12 @@ int main ( int argc, char** argv ) {
         else if ( !strcmp ( a, "--min-passes" ) ) min_passes = atoi ( NEXT() );
         else if ( !strcmp ( a, "--max-passes" ) ) max_passes = atoi ( NEXT() );
         else if ( !strcmp ( a, "--variance" ) ) variance_path = NEXT();
+        else if ( !strcmp ( a, "--frames" ) ) { frames = atoi ( NEXT() ); if ( frames < 1 ) { fprintf ( stderr, "terra_headless: --frames 1 ...\n" ); return 64; } }
+        else if ( !strcmp ( a, "--temporal" ) ) { temporal = ( float ) atof ( NEXT() ); if ( !( temporal >= 0.f && temporal <= 1.f ) ) { fprintf ( stderr, "terra_headless: --temporal ALPHA in (0, 1], or 0 for 0.2\n" ); return 64; } }
+        else if ( !strcmp ( a, "--camera-to" ) && i + 6 < argc ) {
+            cam_to.position = terra_f3_set ( ( float ) atof ( argv[i + 1] ), ( float ) atof ( argv[i + 2] ), ( float ) atof ( argv[i + 3] ) );
+            cam_to.direction = terra_f3_set ( ( float ) atof ( argv[i + 4] ), ( float ) atof ( argv[i + 5] ), ( float ) atof ( argv[i + 6] ) ); i += 6; have_camera_to = 1;
+        }
         else if ( !strcmp ( a, "--env-sampling" ) ) { const char* v = NEXT(); static const char* const n[] = { "off", "table", "mis" }; env_sampling = pick ( v, n, 3, -1 ); if ( env_sampling < 0 ) { fprintf ( stderr, "terra_headless: --env-sampling off|table|mis\n" ); return 64; } }
         else if ( !strcmp ( a, "--camera" ) && i + 6 < argc ) {
             cam.position = terra_f3_set ( ( float ) atof ( argv[i + 1] ), ( float ) atof ( argv[i + 2] ), ( float ) atof ( argv[i + 3] ) );
@@ -692,9 +714,75 @@ int main ( int argc, char** argv ) {
         else if ( gpus > 0 ) { fprintf ( stderr, "terra_headless: --aov / --denoise do not mirror --gpus (the sharded render); ignored\n" ); aov_prefix = NULL; denoise = -1; }
         else if ( !( aov = calloc ( W * H, sizeof ( AovSum ) ) ) ) { fprintf ( stderr, "terra_headless: out of memory\n" ); return 71; }
     }
+    if ( ( have_camera_to || temporal >= 0.f ) && frames < 1 ) { fprintf ( stderr, "terra_headless: --camera-to / --temporal go with --frames N; ignored\n" ); temporal = -1.f; }
+    if ( frames >= 1 && ( gpus > 0 || adaptive > 0.f ) ) { fprintf ( stderr, "terra_headless: --frames does not mirror --gpus / --adaptive; ignored, one frame is written\n" ); frames = 0; temporal = -1.f; }
+    if ( frames >= 1 ) {          /* every flag the frames path does not act on is reported, as the other extension flags are */
+        if ( temporal >= 0.f && !terra_amd_reproject ) { fprintf ( stderr, "terra_headless: --temporal needs libterra_amd.so; ignored, the plain frames are written\n" ); temporal = -1.f; }
+        if ( temporal >= 0.f && denoise < 0 && denoise_var < 0 ) {
+            fprintf ( stderr, "terra_headless: --temporal writes the blended frame through --denoise K or --denoise-variance K and neither is given; ignored, the plain frames are written\n" );
+            temporal = -1.f;
+        }
+        if ( temporal < 0.f && ( denoise >= 0 || denoise_var >= 0 ) ) { fprintf ( stderr, "terra_headless: --denoise / --denoise-variance with --frames go with --temporal; ignored, the plain frames are written\n" ); denoise = -1; denoise_var = -1; }
+        if ( aov_prefix || variance_path ) { fprintf ( stderr, "terra_headless: --aov / --variance are not written with --frames; ignored\n" ); aov_prefix = NULL; variance_path = NULL; }
+    }
     terra_scene_commit ( scene );
     TerraFramebuffer fb;
     if ( !terra_framebuffer_create ( &fb, W, H ) ) { fprintf ( stderr, "terra_headless: bad framebuffer size\n" ); return 65; }
+    if ( frames >= 1 ) {            /* a camera move: one image per frame, each blended into the reprojected history of those before it */
+        const int blend = temporal >= 0.f;
+        HistoryEntry* hist[2] = { NULL, NULL }; TerraRawIntegrationResult* chained = NULL; MomentSum* hmom = NULL;
+        if ( blend ) {
+            if ( !aov ) aov = calloc ( W * H, sizeof ( AovSum ) );
+            hist[0] = calloc ( W * H, sizeof ( HistoryEntry ) ); hist[1] = calloc ( W * H, sizeof ( HistoryEntry ) );
+            chained = calloc ( W * H, sizeof ( TerraRawIntegrationResult ) ); hmom = calloc ( W * H, sizeof ( MomentSum ) );
+            if ( !aov || !hist[0] || !hist[1] || !chained || !hmom ) { fprintf ( stderr, "terra_headless: out of memory\n" ); return 71; }
+        }
+        if ( !have_camera_to ) { cam_to.position = cam.position; cam_to.direction = cam.direction; }
+        const char* ext = strrchr ( argv[2], '.' ); if ( !ext || strchr ( ext, '/' ) ) ext = argv[2] + strlen ( argv[2] );
+        TerraCamera prev = cam;
+        /* Each frame draws its own random numbers. The device keys a pixel's stream with (frame seed + pixel index, samples so far), and the clear below sets the
+           last back to 0: under one seed every frame would repeat the first one's noise and the history would average copies, and under seed + f frame f would be
+           frame 0's noise moved by f pixels (seed + f at pixel p is seed at pixel p + f). Two seeds give independent frames only if they lie further apart than
+           the frame has pixels, so frame f renders under seed + f * 2^32 (frame 0 under --seed or the library's default: --frames 1 is the plain run). The
+           reference seeds itself from the clock. */
+        const uint64_t seed0 = have_seed ? ( uint64_t ) seed : terra_amd_get_frame_seed ? terra_amd_get_frame_seed ( scene ) : 0;
+        for ( int f = 0; f < frames; ++f ) {
+            if ( terra_amd_set_frame_seed ) terra_amd_set_frame_seed ( scene, seed0 + ( ( uint64_t ) f << 32 ) );
+            const float t = frames > 1 ? ( float ) f / ( float ) ( frames - 1 ) : 0.f;
+            TerraCamera cf = cam;
+            cf.position = terra_f3_set ( cam.position.x + ( cam_to.position.x - cam.position.x ) * t, cam.position.y + ( cam_to.position.y - cam.position.y ) * t, cam.position.z + ( cam_to.position.z - cam.position.z ) * t );
+            cf.direction = terra_f3_set ( cam.direction.x + ( cam_to.direction.x - cam.direction.x ) * t, cam.direction.y + ( cam_to.direction.y - cam.direction.y ) * t, cam.direction.z + ( cam_to.direction.z - cam.direction.z ) * t );
+            terra_framebuffer_clear ( &fb );
+            if ( aov ) memset ( aov, 0, W * H * sizeof ( AovSum ) );
+            for ( int pass = 0; pass < passes; ++pass ) {
+                const size_t tl = tile ? tile : ( W > H ? W : H );
+                for ( size_t y = 0; y < H; y += tl ) for ( size_t x = 0; x < W; x += tl ) {
+                    const size_t tw = W - x < tl ? W - x : tl, th = H - y < tl ? H - y : tl;
+                    terra_render ( &cf, scene, &fb, x, y, tw, th );
+                    if ( aov ) ( void ) terra_amd_render_aov ( &cf, scene, aov, W, H, x, y, tw, th );
+                }
+            }
+            if ( terra_amd_last_error && *terra_amd_last_error() ) { fprintf ( stderr, "terra_headless: %s\n", terra_amd_last_error() ); return 70; }
+            if ( blend ) {
+                TemporalOptions to = { temporal, 0.f, 0.f, 0 };
+                TerraFramebuffer cfb = fb; cfb.results = chained;
+                int rc = terra_amd_reproject ( scene, &cf, &prev, &fb, aov, f ? hist[( f + 1 ) & 1] : NULL, hist[f & 1], chained, hmom, 0, 0, W, H, &to );
+                if ( !rc ) rc = denoise_var >= 0 ? terra_amd_denoise_variance ( scene, &cfb, aov, hmom, 0, 0, W, H, denoise_var, NULL, fb.pixels )
+                                                 : terra_amd_denoise ( scene, &cfb, aov, 0, 0, W, H, denoise, NULL, fb.pixels );
+                if ( rc ) { fprintf ( stderr, "terra_headless: %s\n", terra_amd_last_error ? terra_amd_last_error() : "reproject failed" ); return 70; }
+            }
+            char path[4096];
+            snprintf ( path, sizeof path, "%.*s.%04d%s", ( int ) ( ext - argv[2] ), argv[2], f, ext );
+            if ( !write_image ( path, &fb ) ) { fprintf ( stderr, "terra_headless: cannot write %s\n", path ); return 73; }
+            prev = cf;
+        }
+        printf ( "%s: %zu triangles, %zu materials -> %d frames %.*s.0000%s ... (%zux%zu, %zu spp)\n", argv[1], m.faces.n, m.mtls.n, frames, ( int ) ( ext - argv[2] ), argv[2], ext, W, H, spp );
+        free ( aov ); free ( mom ); free ( hist[0] ); free ( hist[1] ); free ( chained ); free ( hmom );
+        terra_framebuffer_destroy ( &fb );
+        terra_scene_destroy ( scene );
+        if ( env_path ) terra_texture_destroy ( &env_tex );
+        return 0;
+    }
     if ( mom && adaptive > 0.f ) {
         AdaptiveOptions ao = { tile, min_passes, max_passes, adaptive, 0 }; AdaptiveReport ar; memset ( &ar, 0, sizeof ar );
         if ( terra_amd_render_adaptive ( &cam, scene, &fb, mom, aov, 0, 0, W, H, &ao, &ar ) != 0 ) { fprintf ( stderr, "terra_headless: %s\n", terra_amd_last_error && *terra_amd_last_error() ? terra_amd_last_error() : "terra_amd_render_adaptive failed" ); return 70; }

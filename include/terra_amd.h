@@ -107,7 +107,12 @@ int  terra_amd_scene_supported ( HTerraScene scene, char* why, size_t capacity )
 
 /* Frame seed F of the per-pixel random streams (DESIGN.md "Randomness"):
    replaces the reference's time(NULL)^&exit seed (src/Terra.c:679) and libc
-   rand() (src/Terra.c:115). Default 0x5EED0001. */
+   rand() (src/Terra.c:115). Default 0x5EED0001.
+   A pixel's streams are keyed with (seed + pixel index y * width + x, samples
+   the framebuffer holds): seed S + k at pixel p is seed S at pixel p + k. Two
+   renders have independent noise only if their seeds differ by at least the
+   number of pixels in the frame; a client that clears the framebuffer every
+   frame (temporal reprojection) uses e.g. S + ((uint64_t) frame << 32). */
 void     terra_amd_set_frame_seed ( HTerraScene scene, uint64_t seed );
 uint64_t terra_amd_get_frame_seed ( HTerraScene scene );
 
@@ -464,6 +469,81 @@ int terra_amd_render_adaptive_device ( const TerraCamera* camera, HTerraScene sc
 /* The same on host buffers: the frame is uploaded, rendered and downloaded (pixels, results, moments and, if given, aov: all frame-indexed). */
 int terra_amd_render_adaptive ( const TerraCamera* camera, HTerraScene scene, TerraFramebuffer* framebuffer, TerraAmdMoments* moments, TerraAmdAovResult* aov,
                                 size_t x, size_t y, size_t width, size_t height, const TerraAmdAdaptiveOptions* options, TerraAmdAdaptiveReport* report );
+
+/* ---- Temporal reprojection: a per-pixel history carried across camera moves (the temporal half of SVGF: Schied et al., HPG 2017) -----------------------------
+   A client that renders one frame per camera keeps two history buffers and the previous frame's camera: after the frame's render call and AOV call (framebuffer
+   and AOV buffer cleared before them) it calls terra_amd_reproject* with last frame's history as history_in and the other buffer as history_out, then swaps them.
+   The geometry does not move; only the camera does. Every buffer is indexed like the frame (y * fb_width + x); only pixels of the rectangle are read or written, and
+   a history tap outside the rectangle does not count. All arithmetic is float32 in exactly the order written, no fused multiply-add; sums of three are left to right.
+   Per pixel p = (px, py) of the rectangle:
+   Current sample.  c, VALID, a, z, n and u_c = c / max(a, 0.01) are the "Denoiser" section's; A = max(a, 0.01) per channel; l_c = l(u_c), l as there.
+   Where the surface was (coverage > 0).  D = the render's camera direction through the pixel centre (subpixel_jitter 0): with t = tan((fov * 0.0174533f) / 2) (a double
+     tan rounded to float), aspect = (float) fb_width / (float) fb_height, X = normalize(up x Z), Y = Z x X, Z = normalize(direction) of `camera`:
+       sx = 2 (((float) px + 0.5) / fb_width) - 1, sy = 1 - 2 (((float) py + 0.5) / fb_height), e = normalize((sx * aspect) * t, sy * t, 1), D = X e.x + Y e.y + Z e.z;
+     P = position + D * z;  v = P - prev_position;  d = |v|;  (xc, yc, zc) = (X' . v, Y' . v, Z' . v) with X', Y', Z', t' of prev_camera;
+     fx = (((xc / zc) / (aspect * t') + 1) / 2) * fb_width - 0.5;  fy = ((1 - (yc / zc) / t') / 2) * fb_height - 0.5.
+     There is no history unless zc > 0, -1 <= fx < fb_width and -1 <= fy < fb_height.
+     Snap: with rx = floor(fx + 0.5), ry = floor(fy + 0.5), if |fx - rx| <= 1/64 and |fy - ry| <= 1/64 the only tap is (rx, ry) and, if it is accepted, the history
+     values are that entry's own (no arithmetic). Otherwise x0 = floor(fx), tx = fx - x0, y0 = floor(fy), ty = fy - y0 and the taps are, in this order,
+     (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1) with weights (1 - tx)(1 - ty), tx (1 - ty), (1 - tx) ty, tx ty.
+     A tap q is ACCEPTED if its weight is > 0, it lies in the rectangle, history_in[q].length > 0, |d - depth_q| <= depth_tolerance * max(d, depth_q), and the
+     normals agree: both zero passes, exactly one zero fails, else n_p . normal_q >= normal_cos. Over the accepted taps in order, each sum starting at 0:
+     W = sum w_q; the history is accepted if W >= 1e-3 (so that the division is safe; not a tuning number); u_h = (sum w_q radiance_q) / W per channel, mu1_h, mu2_h
+     likewise; N_h = the smallest length of the accepted taps.
+   Pixels that miss the scene (coverage == 0).  History only if prev_camera equals camera byte for byte: the tap is p itself, accepted if its length > 0 and its
+     depth == 0; the history values are that entry's own.
+   Blend.  With accepted history: alpha_p = max(alpha, 1 / (N_h + 1)) and, for a VALID pixel, u' = u_h + alpha_p (u_c - u_h), mu1' = mu1_h + alpha_p (l_c - mu1_h),
+     mu2' = mu2_h + alpha_p (l_c l_c - mu2_h), length' = min(N_h + 1, floor(1 / alpha)); a pixel that is not VALID carries the history through: u', mu1', mu2',
+     length' = u_h, mu1_h, mu2_h, N_h. Without accepted history: a VALID pixel restarts, u' = u_c, mu1' = l_c, mu2' = l_c l_c, length' = 1; one that is not VALID
+     is written EMPTY (radiance, length, mu1, mu2 all 0). normal and depth of every written entry are n and z of the current frame; reserved is 0.
+   Output for the denoisers (either pointer may be NULL): terra_amd_denoise_device() / terra_amd_denoise_variance_device() run on them as on a framebuffer and a
+     moments buffer, with this frame's AOV buffer. An EMPTY entry: out_results = the input result, out_moments all zero. Otherwise, with n = (float) samples,
+     out_results = { (u' * A) * n per channel, samples } -- the denoiser's own division and demodulation give u' back, a pixel without samples stays one --
+     and out_moments = { seen_acc, seen_samples = out_results; mean = mu1'; m2 = var; batches = 2; weight = 1 }: the form in which the variance-guided filter reads
+     var = ((max(0, mu2' - mu1' mu1') * alpha_p) * (r * r)), r = max(l(u' * A), 1e-6) / l(u') -- the variance of the blended luminance, alpha_p of the per-frame
+     one, in the units that filter expects. Where length' < 2, l(u') is not > 0 or var is not finite, the six moment words after seen_* are zero: unknown, and the
+     filter falls back to its plain colour weight there.
+   d_history_in == NULL: the first frame, no pixel has history. d_history_in == d_history_out is kTerraAmdErrBadArgument (taps read neighbours: the call cannot run
+   in place). Otherwise the call fails like the denoiser (kTerraAmdErrNotCommitted, a bad rectangle, a NULL camera or required buffer), and with
+   kTerraAmdErrBadArgument for alpha outside (0, 1], a negative tolerance or a frame side above 2^24 (pixel coordinates are floats). One lane per pixel, no atomics:
+   the same inputs give the same bits. Runs on the scene's primary device (a multi-device scene's shards are not mirrored). */
+typedef struct {            /* 48 bytes = three 16-byte words */
+    float radiance[3];      /* +0   blended DEMODULATED radiance u (the "Denoiser" section's u = c / max(albedo, 0.01)) */
+    float length;           /* +12  frames blended into this entry; 0 = empty */
+    float normal[3];        /* +16  unit shading normal of the frame that wrote it (zero: none) */
+    float depth;            /* +28  its mean first-hit distance from that frame's camera (0: no hit) */
+    float mu1, mu2;         /* +32  blended first and second moment of the per-frame luminance l(u) */
+    float reserved[2];      /* +40  zero */
+} TerraAmdHistory;
+typedef struct {
+    float alpha;            /* 0: 0.2; otherwise in (0, 1] */
+    float depth_tolerance;  /* 0: 0.05 */
+    float normal_cos;       /* 0: 0.9 */
+    int   reserved;
+} TerraAmdTemporalOptions;
+TERRA_ABI_ASSERT ( sizeof ( TerraAmdHistory ) == 48 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdHistory, length ) == 12 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdHistory, normal ) == 16 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdHistory, depth ) == 28 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdHistory, mu1 ) == 32 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdHistory, mu2 ) == 36 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdHistory, reserved ) == 40 );
+TERRA_ABI_ASSERT ( sizeof ( TerraAmdTemporalOptions ) == 16 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdTemporalOptions, depth_tolerance ) == 4 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdTemporalOptions, normal_cos ) == 8 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdTemporalOptions, reserved ) == 12 );
+/* d_results / d_aov as the denoiser takes them, d_history_in / d_history_out: TerraAmdHistory per pixel of the frame, d_out_results: TerraRawIntegrationResult,
+   d_out_moments: TerraAmdMoments per pixel, all in HBM; options may be NULL (all defaults); asynchronous on `stream`. */
+int terra_amd_reproject_device ( HTerraScene scene, const TerraCamera* camera, const TerraCamera* prev_camera,
+                                 const void* d_results, const void* d_aov, const void* d_history_in, void* d_history_out,
+                                 void* d_out_results, void* d_out_moments,
+                                 size_t fb_width, size_t fb_height, size_t x, size_t y, size_t width, size_t height,
+                                 const TerraAmdTemporalOptions* options, void* stream );
+/* The same on host buffers (all frame-indexed; history_in, out_results and out_moments may be NULL): uploaded, reprojected, the outputs downloaded; synchronous. */
+int terra_amd_reproject ( HTerraScene scene, const TerraCamera* camera, const TerraCamera* prev_camera,
+                          const TerraFramebuffer* framebuffer, const TerraAmdAovResult* aov, const TerraAmdHistory* history_in, TerraAmdHistory* history_out,
+                          TerraRawIntegrationResult* out_results, TerraAmdMoments* out_moments,
+                          size_t x, size_t y, size_t width, size_t height, const TerraAmdTemporalOptions* options );
 
 /* Tile-sharded form for one-process-per-GPU rendering (the reference shards
    the same way over CPU threads: satellite/src/Renderer.cpp:316-350): the

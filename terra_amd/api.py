@@ -159,6 +159,23 @@ class TerraAmdAdaptiveReport(Structure):
 
 assert C.sizeof(TerraAmdMoments) == 32 and C.sizeof(TerraAmdAdaptiveOptions) == 24 and C.sizeof(TerraAmdAdaptiveReport) == 40
 
+# TerraAmdHistory (include/terra_amd.h "Temporal reprojection"): 48 bytes per pixel
+HISTORY_DTYPE = np.dtype([("radiance", np.float32, (3,)), ("length", np.float32), ("normal", np.float32, (3,)), ("depth", np.float32), ("mu1", np.float32), ("mu2", np.float32),
+                          ("reserved", np.float32, (2,))])
+assert HISTORY_DTYPE.itemsize == 48
+
+
+class TerraAmdHistory(Structure):
+    _fields_ = [("radiance", c_float * 3), ("length", c_float), ("normal", c_float * 3), ("depth", c_float), ("mu1", c_float), ("mu2", c_float), ("reserved", c_float * 2)]
+
+
+class TerraAmdTemporalOptions(Structure):
+    """0 in a field: its default (alpha 0.2, depth_tolerance 0.05, normal_cos 0.9)"""
+    _fields_ = [("alpha", c_float), ("depth_tolerance", c_float), ("normal_cos", c_float), ("reserved", c_int)]
+
+
+assert C.sizeof(TerraAmdHistory) == 48 and C.sizeof(TerraAmdTemporalOptions) == 16
+
 # entry points of include/Terra.h + include/TerraPresets.h, name -> (restype, argtypes)
 API_SIGNATURES = {
     "scene_create": (c_void_p, []),

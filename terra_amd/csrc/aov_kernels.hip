@@ -124,25 +124,10 @@ __global__ __launch_bounds__ ( 256 ) void terra_denoise_prepass ( const float4* 
     const uint32_t lx = blockIdx.x * 16u + threadIdx.x, ly = blockIdx.y * 16u + threadIdx.y;
     if ( lx >= w || ly >= h ) return;
     const size_t pix = ( size_t ) ( y + ly ) * fb_w + ( x + lx ), i = ( size_t ) ly * w + lx;
-    const float4 res = results[pix];
-    const int samples = __float_as_int ( res.w );
-    const float n = ( float ) samples;
-    const V3 c = v3 ( res.x / n, res.y / n, res.z / n );
-    const bool finite = samples > 0 && dn_finite ( c.x ) && dn_finite ( c.y ) && dn_finite ( c.z );
-    const float4 a0 = aov[3 * pix], a1 = aov[3 * pix + 1];
-    V3 a = v3 ( 0.f, 0.f, 0.f ), nv = v3 ( 0.f, 0.f, 0.f );
-    float z = 0.f;
-    if ( a0.w > 0.f ) {
-        a = v3 ( a0.x / a0.w, a0.y / a0.w, a0.z / a0.w );
-        z = a1.w / a0.w;
-        nv = v3 ( a1.x / a0.w, a1.y / a0.w, a1.z / a0.w );
-        const float len = length ( nv );
-        nv = len > TERRA_DN_NORMAL_MIN ? v3 ( nv.x / len, nv.y / len, nv.z / len ) : v3 ( 0.f, 0.f, 0.f );
-    }
+    DN_PIXEL_INPUTS ( results, aov, pix )               // res, samples, c, finite, a0, a1, a, nv, z (denoise_device.h: shared with the temporal reprojection)
     g0[i] = make_float4 ( nv.x, nv.y, nv.z, z );
     g1[i] = make_float4 ( a.x, a.y, a.z, finite ? 1.f : ( samples > 0 ? 2.f : 0.f ) );
-    u[i] = finite ? make_float4 ( c.x / dn_max ( a.x, TERRA_DN_ALBEDO_MIN ), c.y / dn_max ( a.y, TERRA_DN_ALBEDO_MIN ), c.z / dn_max ( a.z, TERRA_DN_ALBEDO_MIN ), 1.f )
-                  : make_float4 ( 0.f, 0.f, 0.f, 0.f );
+    u[i] = finite ? dn_valid4 ( dn_demodulate ( c, a ) ) : make_float4 ( 0.f, 0.f, 0.f, 0.f );
 }
 
 // iteration `it` (step 2^it): u.w = 1 marks a valid pixel of the input / output

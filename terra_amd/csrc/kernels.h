@@ -45,6 +45,18 @@ hipError_t terra_launch_tile_error ( const void* moments, uint32_t fb_w, uint32_
 hipError_t terra_launch_denoise_variance ( const void* results, const void* aov, const void* moments, uint32_t fb_w, uint32_t x, uint32_t y, uint32_t w, uint32_t h, int iterations,
                                            float exposure, int op, float gamma, float* radiance, float* pixels, hipStream_t stream );
 
+// temporal reprojection of a per-pixel history (temporal_kernels.hip; include/terra_amd.h "Temporal reprojection"): every buffer indexed like a frame of fb_w pixels
+// per row, only the rectangle is read or written; history_in, out_results, out_moments may be nullptr. cam / prev: the two cameras as fill_camera made them.
+struct DevTemporalParams {
+    float cam_pos[3], cam_rot[9], tan_half_fov, aspect;
+    float prev_pos[3], prev_rot[9], prev_tan_half_fov;
+    uint32_t fb_w, fb_h, x, y, w, h;
+    float alpha, depth_tolerance, normal_cos, max_length;      // max_length = floor(1 / alpha)
+    uint32_t same_camera;                                        // prev_camera equals camera byte for byte
+};
+hipError_t terra_launch_temporal_reproject ( const DevTemporalParams& p, const void* results, const void* aov, const void* history_in, void* history_out,
+                                             void* out_results, void* out_moments, hipStream_t stream );
+
 hipError_t terra_fill_sincos24 ( float2* table, hipStream_t stream );    // DevScene::sincos24: 2^24 entries (128 MB), device pointer
 
 // unit-level launchers: all pointers are DEVICE pointers, n items, synchronous semantics left to the caller

@@ -1329,16 +1329,9 @@ static uint32_t effective_spp ( const TerraSceneOptions& o ) {
     return ( uint32_t ) spp;
 }
 
-// r: the copy of the scene the launch reads (the launch runs on r.device)
-static int fill_params ( Scene* s, const Scene::Replica& r, const TerraCamera* cam, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t h,
-                         size_t tile, int rank, int world, DevRenderParams& p ) {
-    if ( !s->committed ) return fail ( kTerraAmdErrNotCommitted, "terra_scene_commit has not run since the scene changed" );
-    if ( !s->device_ok ) return fail ( kTerraAmdErrNoDevice, "scene has no device replica: %s", s->commit_error.c_str() );
-    if ( !cam || w == 0 || h == 0 || x + w > fb_w || y + h > fb_h ) return fail ( kTerraAmdErrBadArgument, "bad tile rectangle %zu,%zu %zux%zu in %zux%zu", x, y, w, h, fb_w, fb_h );
-    if ( tile == 0 || tile % 16 != 0 ) return fail ( kTerraAmdErrBadArgument, "tile_size %zu must be a positive multiple of 16", tile );
-    if ( world < 1 || rank < 0 || rank >= world ) return fail ( kTerraAmdErrBadArgument, "bad shard %d/%d", rank, world );
-    memset ( &p, 0, sizeof p );
-    p.scene = r.dev;
+// the camera part of a launch: frame (columns of cam_rot: x, y, z axis), position, tan of the half angle, aspect -- for the render (fill_params), the camera unit
+// entry and both cameras of the temporal reprojection
+static void fill_camera ( const TerraCamera* cam, size_t fb_w, size_t fb_h, DevRenderParams& p ) {
     // camera frame, reference src/Terra.c:1770-1781
     TerraFloat3 z = terra_normf3 ( &cam->direction );
     TerraFloat3 xa = terra_crossf3 ( &cam->up, &z ); xa = terra_normf3 ( &xa );
@@ -1349,6 +1342,19 @@ static int fill_params ( Scene* s, const Scene::Replica& r, const TerraCamera* c
     p.cam_pos[0] = cam->position.x; p.cam_pos[1] = cam->position.y; p.cam_pos[2] = cam->position.z;
     p.tan_half_fov = ( float ) tan ( ( double ) ( ( cam->fov * 0.0174533f ) / 2 ) );     // double tan of a float argument, src/Terra.c:1794
     p.aspect = ( float ) fb_w / ( float ) fb_h;
+}
+
+// r: the copy of the scene the launch reads (the launch runs on r.device)
+static int fill_params ( Scene* s, const Scene::Replica& r, const TerraCamera* cam, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t h,
+                         size_t tile, int rank, int world, DevRenderParams& p ) {
+    if ( !s->committed ) return fail ( kTerraAmdErrNotCommitted, "terra_scene_commit has not run since the scene changed" );
+    if ( !s->device_ok ) return fail ( kTerraAmdErrNoDevice, "scene has no device replica: %s", s->commit_error.c_str() );
+    if ( !cam || w == 0 || h == 0 || x + w > fb_w || y + h > fb_h ) return fail ( kTerraAmdErrBadArgument, "bad tile rectangle %zu,%zu %zux%zu in %zux%zu", x, y, w, h, fb_w, fb_h );
+    if ( tile == 0 || tile % 16 != 0 ) return fail ( kTerraAmdErrBadArgument, "tile_size %zu must be a positive multiple of 16", tile );
+    if ( world < 1 || rank < 0 || rank >= world ) return fail ( kTerraAmdErrBadArgument, "bad shard %d/%d", rank, world );
+    memset ( &p, 0, sizeof p );
+    p.scene = r.dev;
+    fill_camera ( cam, fb_w, fb_h, p );
     p.jitter = s->opts.subpixel_jitter; p.exposure = s->opts.manual_exposure; p.gamma = s->opts.gamma;
     p.fb_w = ( uint32_t ) fb_w; p.fb_h = ( uint32_t ) fb_h;
     p.x = ( uint32_t ) x; p.y = ( uint32_t ) y; p.w = ( uint32_t ) w; p.h = ( uint32_t ) h;
@@ -1595,10 +1601,10 @@ extern "C" int terra_amd_render_aov ( const TerraCamera* cam, HTerraScene h, Ter
     ( void ) hipFree ( d );
     return rc;
 }
-static int denoise_check ( Scene* s, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t h, int iterations ) {
+static int denoise_check ( Scene* s, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t h, int iterations, const char* what = "denoise" ) {
     if ( !s->committed ) return fail ( kTerraAmdErrNotCommitted, "terra_scene_commit has not run since the scene changed" );
     if ( !s->device_ok ) return fail ( kTerraAmdErrNoDevice, "scene has no device replica: %s", s->commit_error.c_str() );
-    if ( w == 0 || h == 0 || x + w > fb_w || y + h > fb_h ) return fail ( kTerraAmdErrBadArgument, "bad denoise rectangle %zu,%zu %zux%zu in %zux%zu", x, y, w, h, fb_w, fb_h );
+    if ( w == 0 || h == 0 || x + w > fb_w || y + h > fb_h ) return fail ( kTerraAmdErrBadArgument, "bad %s rectangle %zu,%zu %zux%zu in %zux%zu", what, x, y, w, h, fb_w, fb_h );
     if ( iterations < 0 || iterations > 8 ) return fail ( kTerraAmdErrBadArgument, "denoise iterations %d: 0 ... 8", iterations );
     return 0;
 }
@@ -1735,6 +1741,58 @@ extern "C" int terra_amd_denoise_variance ( HTerraScene h, const TerraFramebuffe
     if ( radiance ) e = o.down ( 0, radiance, n * 12 );
     if ( e == hipSuccess && pixels ) e = o.down ( 1, pixels, n * 12 );
     if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "variance denoise download: %s", hipGetErrorString ( e ) );
+    return 0;
+}
+// ---- temporal reprojection (temporal_kernels.hip) -----------------------------------------------------------------------------------
+static_assert ( sizeof ( TerraAmdHistory ) == 48 && sizeof ( TerraAmdTemporalOptions ) == 16, "TerraAmdHistory / TerraAmdTemporalOptions layout" );
+extern "C" int terra_amd_reproject_device ( HTerraScene h, const TerraCamera* cam, const TerraCamera* prev, const void* d_results, const void* d_aov, const void* d_history_in,
+                                            void* d_history_out, void* d_out_results, void* d_out_moments, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t hgt,
+                                            const TerraAmdTemporalOptions* options, void* stream ) {
+    Scene* s = S ( h );
+    if ( int rc = denoise_check ( s, fb_w, fb_h, x, y, w, hgt, 0, "reproject" ) ) return rc;
+    if ( fb_w > ( 1u << 24 ) || fb_h > ( 1u << 24 ) ) return fail ( kTerraAmdErrBadArgument, "reproject: frame %zux%zu: at most 2^24 pixels a side (pixel coordinates are floats)", fb_w, fb_h );
+    if ( !cam || !prev || !d_results || !d_aov || !d_history_out ) return fail ( kTerraAmdErrBadArgument, "null camera, framebuffer, AOV or history buffer" );
+    if ( d_history_in == d_history_out ) return fail ( kTerraAmdErrBadArgument, "reproject: history_in and history_out are the same buffer (taps read neighbours: the call cannot run in place)" );
+    const float alpha = options && options->alpha != 0.f ? options->alpha : 0.2f;
+    const float depth_tol = options && options->depth_tolerance != 0.f ? options->depth_tolerance : 0.05f;
+    const float normal_cos = options && options->normal_cos != 0.f ? options->normal_cos : 0.9f;
+    if ( ! ( alpha > 0.f && alpha <= 1.f ) ) return fail ( kTerraAmdErrBadArgument, "reproject: alpha %g must lie in (0, 1]", ( double ) alpha );
+    if ( ! ( depth_tol >= 0.f ) || ! ( normal_cos >= 0.f ) ) return fail ( kTerraAmdErrBadArgument, "reproject: negative tolerance (depth %g, normal %g)", ( double ) depth_tol, ( double ) normal_cos );
+    DevRenderParams a, b;
+    fill_camera ( cam, fb_w, fb_h, a ); fill_camera ( prev, fb_w, fb_h, b );
+    DevTemporalParams p;
+    memcpy ( p.cam_pos, a.cam_pos, sizeof p.cam_pos ); memcpy ( p.cam_rot, a.cam_rot, sizeof p.cam_rot ); p.tan_half_fov = a.tan_half_fov; p.aspect = a.aspect;
+    memcpy ( p.prev_pos, b.cam_pos, sizeof p.prev_pos ); memcpy ( p.prev_rot, b.cam_rot, sizeof p.prev_rot ); p.prev_tan_half_fov = b.tan_half_fov;
+    p.fb_w = ( uint32_t ) fb_w; p.fb_h = ( uint32_t ) fb_h; p.x = ( uint32_t ) x; p.y = ( uint32_t ) y; p.w = ( uint32_t ) w; p.h = ( uint32_t ) hgt;
+    p.alpha = alpha; p.depth_tolerance = depth_tol; p.normal_cos = normal_cos; p.max_length = floorf ( 1.f / alpha );
+    p.same_camera = memcmp ( cam, prev, sizeof ( TerraCamera ) ) == 0 ? 1u : 0u;
+    HIP_TRY ( hipSetDevice ( primary ( s ).device ), kTerraAmdErrNoDevice );
+    const hipError_t e = terra_launch_temporal_reproject ( p, d_results, d_aov, d_history_in, d_history_out, d_out_results, d_out_moments, ( hipStream_t ) stream );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "reproject launch: %s", hipGetErrorString ( e ) );
+    return 0;
+}
+extern "C" int terra_amd_reproject ( HTerraScene h, const TerraCamera* cam, const TerraCamera* prev, const TerraFramebuffer* fb, const TerraAmdAovResult* aov, const TerraAmdHistory* history_in,
+                                     TerraAmdHistory* history_out, TerraRawIntegrationResult* out_results, TerraAmdMoments* out_moments, size_t x, size_t y, size_t w, size_t hgt,
+                                     const TerraAmdTemporalOptions* options ) {
+    Scene* s = S ( h );
+    if ( !fb || !fb->results || !aov || !history_out ) return fail ( kTerraAmdErrBadArgument, "null framebuffer, AOV or history buffer" );
+    if ( history_in == history_out ) return fail ( kTerraAmdErrBadArgument, "reproject: history_in and history_out are the same buffer (taps read neighbours: the call cannot run in place)" );
+    if ( int rc = denoise_check ( s, fb->width, fb->height, x, y, w, hgt, 0, "reproject" ) ) return rc;
+    HIP_TRY ( hipSetDevice ( primary ( s ).device ), kTerraAmdErrNoDevice );
+    const size_t n = fb->width * fb->height;
+    FrameCopy c, o;             // (the outputs go up too: what lies outside the rectangle comes back as it was)
+    hipError_t e = c.up ( 0, fb->results, n * 16 );
+    if ( e == hipSuccess ) e = c.up ( 1, aov, n * 48 );
+    if ( e == hipSuccess && history_in ) e = c.up ( 2, history_in, n * 48 );
+    if ( e == hipSuccess ) e = o.up ( 0, history_out, n * 48 );
+    if ( e == hipSuccess && out_results ) e = o.up ( 1, out_results, n * 16 );
+    if ( e == hipSuccess && out_moments ) e = o.up ( 2, out_moments, n * 32 );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "reproject upload: %s", hipGetErrorString ( e ) );
+    if ( int rc = terra_amd_reproject_device ( h, cam, prev, c.d[0], c.d[1], c.d[2], o.d[0], o.d[1], o.d[2], fb->width, fb->height, x, y, w, hgt, options, nullptr ) ) return rc;
+    e = o.down ( 0, history_out, n * 48 );
+    if ( e == hipSuccess && out_results ) e = o.down ( 1, out_results, n * 16 );
+    if ( e == hipSuccess && out_moments ) e = o.down ( 2, out_moments, n * 32 );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "reproject download: %s", hipGetErrorString ( e ) );
     return 0;
 }
 extern "C" int terra_amd_render_adaptive_device ( const TerraCamera* cam, HTerraScene h, void* d_pixels, void* d_results, void* d_moments, void* d_aov, size_t fb_w, size_t fb_h,
@@ -2134,12 +2192,8 @@ extern "C" int terra_amd_unit_bsdf ( int kind, int n, float* surfaces47, const f
 extern "C" int terra_amd_unit_camera ( const TerraCamera* cam, size_t fb_w, size_t fb_h, int n, const uint32_t* xy2, float jitter, const float* r2, float* dirs3 ) {
     if ( need_device() ) return kTerraAmdErrNoDevice;
     DevRenderParams p; memset ( &p, 0, sizeof p );
-    TerraFloat3 z = terra_normf3 ( &cam->direction );
-    TerraFloat3 xa = terra_crossf3 ( &cam->up, &z ); xa = terra_normf3 ( &xa );
-    TerraFloat3 ya = terra_crossf3 ( &z, &xa );
-    p.cam_rot[0] = xa.x; p.cam_rot[1] = ya.x; p.cam_rot[2] = z.x; p.cam_rot[3] = xa.y; p.cam_rot[4] = ya.y; p.cam_rot[5] = z.y; p.cam_rot[6] = xa.z; p.cam_rot[7] = ya.z; p.cam_rot[8] = z.z;
-    p.tan_half_fov = ( float ) tan ( ( double ) ( ( cam->fov * 0.0174533f ) / 2 ) );
-    p.aspect = ( float ) fb_w / ( float ) fb_h; p.jitter = jitter; p.fb_w = ( uint32_t ) fb_w; p.fb_h = ( uint32_t ) fb_h;
+    fill_camera ( cam, fb_w, fb_h, p );
+    p.jitter = jitter; p.fb_w = ( uint32_t ) fb_w; p.fb_h = ( uint32_t ) fb_h;
     Unit u; auto a = u.in ( xy2, 2 * ( size_t ) n ); auto b = u.in ( r2, 2 * ( size_t ) n ); auto o = u.out ( dirs3, 3 * ( size_t ) n );
     return u.finish ( u.ok ? terra_unit_camera ( p, n, a, b, o ) : hipSuccess );
 }

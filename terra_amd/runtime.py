@@ -125,6 +125,8 @@ _EXTRA = {
                                          [C.POINTER(api.TerraAmdAdaptiveOptions), C.POINTER(api.TerraAmdAdaptiveReport), C.c_void_p]),
     "terra_amd_render_adaptive": (C.c_int, [_CAM, C.c_void_p, C.POINTER(api.TerraFramebuffer), C.c_void_p, C.c_void_p] + [_SZ] * 4 +
                                   [C.POINTER(api.TerraAmdAdaptiveOptions), C.POINTER(api.TerraAmdAdaptiveReport)]),
+    "terra_amd_reproject_device": (C.c_int, [C.c_void_p, _CAM, _CAM] + [C.c_void_p] * 6 + [_SZ] * 6 + [C.POINTER(api.TerraAmdTemporalOptions), C.c_void_p]),
+    "terra_amd_reproject": (C.c_int, [C.c_void_p, _CAM, _CAM, C.POINTER(api.TerraFramebuffer)] + [C.c_void_p] * 5 + [_SZ] * 4 + [C.POINTER(api.TerraAmdTemporalOptions)]),
 }
 
 
@@ -302,6 +304,36 @@ def render_adaptive_device(lib, cam, scene, fb: DeviceFramebuffer, moments: Devi
     check(lib.render_adaptive_device(C.byref(cam), scene, fb.pixels.data_ptr(), fb.results.data_ptr(), moments.data.data_ptr(), aov.data.data_ptr() if aov is not None else None,
                                      fb.width, fb.height, x, y, w, h, C.byref(opt), C.byref(rep), stream), "terra_amd_render_adaptive_device")
     return rep.as_dict()
+
+
+class DeviceHistory:
+    """A TerraAmdHistory buffer in HBM (12 words per pixel). A client keeps two and the previous frame's camera: reproject_device reads one and writes the other,
+    then they swap."""
+
+    def __init__(self, width: int, height: int, device: str = "cuda"):
+        import torch
+        self.width, self.height = width, height
+        self.data = torch.zeros(height * width * 12, dtype=torch.float32, device=device)
+
+    def clear(self):
+        self.data.zero_()
+
+    def host(self) -> np.ndarray:
+        """api.HISTORY_DTYPE records (height, width)"""
+        return self.data.cpu().numpy().view(api.HISTORY_DTYPE).reshape(self.height, self.width)
+
+
+def reproject_device(lib, scene, cam, prev_cam, fb: DeviceFramebuffer, aov: DeviceAov, history_in: Optional[DeviceHistory], history_out: DeviceHistory,
+                     out_fb: Optional[DeviceFramebuffer] = None, out_moments: Optional[DeviceMoments] = None, rect: Optional[Tuple[int, int, int, int]] = None,
+                     alpha: float = 0.0, depth_tolerance: float = 0.0, normal_cos: float = 0.0, stream=None):
+    """terra_amd_reproject_device: blends fb / aov (the current frame under cam) into the history read from history_in (None: the first frame) at the place each
+    surface had under prev_cam, and writes history_out; out_fb.results / out_moments receive the blended frame in the form denoise_device /
+    denoise_variance_device read (with this frame's aov). 0 in an option: its default."""
+    x, y, w, h = rect if rect else (0, 0, fb.width, fb.height)
+    opt = api.TerraAmdTemporalOptions(alpha, depth_tolerance, normal_cos, 0)
+    check(lib.reproject_device(scene, C.byref(cam), C.byref(prev_cam), fb.results.data_ptr(), aov.data.data_ptr(), history_in.data.data_ptr() if history_in is not None else None,
+                               history_out.data.data_ptr(), out_fb.results.data_ptr() if out_fb is not None else None, out_moments.data.data_ptr() if out_moments is not None else None,
+                               fb.width, fb.height, x, y, w, h, C.byref(opt), stream), "terra_amd_reproject_device")
 
 
 def render_device_sharded(lib, cam, scene, fb: DeviceFramebuffer, tile: int, rank: int, world: int, stream=None):
