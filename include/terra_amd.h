@@ -545,6 +545,60 @@ int terra_amd_reproject ( HTerraScene scene, const TerraCamera* camera, const Te
                           TerraRawIntegrationResult* out_results, TerraAmdMoments* out_moments,
                           size_t x, size_t y, size_t width, size_t height, const TerraAmdTemporalOptions* options );
 
+/* ---- Ray queries: closest hit and occlusion of a client's own rays on a committed scene ------------------------------------------------------------------------
+   The second door of the library: the trees a commit builds answer batches of rays that are not camera rays -- picking (the triangle under a pixel), visibility
+   between points, ambient-occlusion and light-probe baking, line-of-sight tests. Per ray, independently of every other ray:
+   The ray is traced as given.  This is the reference's terra_bvh_traverse (src/TerraBVH.c:250-310), not terra_scene_raycast: NO 0.001 offset is added to the
+     origin; a client that wants the reference's offset adds it itself. direction need not be normalised; depths are in units of its length.
+   Effective limit.  L = tmax if tmax < FLT_MAX, else FLT_MAX: +inf, FLT_MAX and NaN all mean "no limit". tmax < 0: nothing counts, the ray misses.
+   Which triangles count.  Those the watertight test accepts (its own rule, unchanged) at a depth <= L.
+   Closest hit.  The smallest depth among the triangles that count; equal depths are resolved by the reference traversal's leaf visit order (the first met wins), and
+     only triangles the reference traversal reaches take part. With no limit this is terra_amd_unit_bvh_traverse's answer bit for bit, in every tree mode
+     (terra_amd_set_tree_mode) and in reachability mode. t = that depth as the watertight test reports it; point = origin + direction * t, float32, multiply then
+     add, no fused multiply-add; object / triangle = the object's index in the scene and the triangle's index in that object. A miss: t = FLT_MAX, object = -1,
+     triangle = 0, point = (FLT_MAX, FLT_MAX, FLT_MAX). reserved and reserved2 are written 0.
+   Occlusion.  occluded[i] = 1 exactly when terra_amd_intersect() of the same ray reports a hit, else 0. The search stops at the first triangle that counts (in
+     reachability mode: the first one the reference traversal reaches); which one that is is unspecified and invisible.
+   Traversal.  The one a render call of the scene takes: the fast tree where the commit chose it (with the reachability replay outside the coordinate range),
+     otherwise the reference tree with the leaf-box cull where the commit proved it. That proof covers ray origins within TerraAmdTraversalInfo::camera_limit on
+     every axis, as it covers a render call's camera. The reference tree's cull is decided ray by ray; the host forms give up the fast tree for a batch with an origin
+     further out (the replica traversal answers, slower, same rule); the device forms cannot look at rays in HBM without a synchronise and traverse the fast tree
+     whatever the origins: keep them within camera_limit.
+   Calls.  n == 0 succeeds and launches nothing. n > 2^31 - 1 or a NULL buffer with n > 0 is kTerraAmdErrBadArgument, an uncommitted scene kTerraAmdErrNotCommitted
+     (terra_amd_last_error() has the message); nothing is launched then. A call records nothing in terra_amd_get_stats() and touches neither a framebuffer nor the
+     scene. A scene committed for several devices answers on its primary device. No atomics: the same inputs give the same bits. */
+typedef struct {            /* 32 bytes = two 16-byte words */
+    float origin[3];        /* +0 */
+    float tmax;             /* +12  hits with depth > tmax do not count (see "Effective limit") */
+    float direction[3];     /* +16  need not be normalised; depth is in units of its length */
+    float reserved;         /* +28  ignored (kept for a later near limit) */
+} TerraAmdRay;
+typedef struct {            /* 32 bytes = two 16-byte words */
+    float t;                /* +0   depth of the closest hit as the watertight test reports it; FLT_MAX on a miss */
+    int   object;           /* +4   index of the object in the scene, -1 on a miss */
+    int   triangle;         /* +8   index of the triangle in that object, 0 on a miss */
+    int   reserved;         /* +12  0 */
+    float point[3];         /* +16  origin + direction * t; (FLT_MAX, FLT_MAX, FLT_MAX) on a miss */
+    float reserved2;        /* +28  0 */
+} TerraAmdHit;
+TERRA_ABI_ASSERT ( sizeof ( TerraAmdRay ) == 32 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdRay, tmax ) == 12 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdRay, direction ) == 16 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdRay, reserved ) == 28 );
+TERRA_ABI_ASSERT ( sizeof ( TerraAmdHit ) == 32 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdHit, object ) == 4 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdHit, triangle ) == 8 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdHit, reserved ) == 12 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdHit, point ) == 16 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdHit, reserved2 ) == 28 );
+/* d_rays: n TerraAmdRay, d_hits: n TerraAmdHit, d_occluded: n uint32_t (1 / 0), all in HBM and 16-byte aligned (4-byte for d_occluded); asynchronous on `stream`:
+   any scratch the call needs is allocated and freed in stream order, nothing synchronises. */
+int terra_amd_intersect_device ( HTerraScene scene, const void* d_rays, size_t n, void* d_hits, void* stream );
+int terra_amd_occluded_device  ( HTerraScene scene, const void* d_rays, size_t n, void* d_occluded, void* stream );
+/* The same on host buffers: the rays are uploaded, the query runs, the answers are downloaded; synchronous. */
+int terra_amd_intersect ( HTerraScene scene, const TerraAmdRay* rays, size_t n, TerraAmdHit* hits );
+int terra_amd_occluded  ( HTerraScene scene, const TerraAmdRay* rays, size_t n, uint32_t* occluded );
+
 /* Tile-sharded form for one-process-per-GPU rendering (the reference shards
    the same way over CPU threads: satellite/src/Renderer.cpp:316-350): the
    rectangle is cut into tile_size x tile_size tiles numbered row-major and this

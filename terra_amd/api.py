@@ -176,6 +176,30 @@ class TerraAmdTemporalOptions(Structure):
 
 assert C.sizeof(TerraAmdHistory) == 48 and C.sizeof(TerraAmdTemporalOptions) == 16
 
+# TerraAmdRay / TerraAmdHit (include/terra_amd.h "Ray queries"): 32 bytes each
+RAY_DTYPE = np.dtype([("origin", np.float32, (3,)), ("tmax", np.float32), ("direction", np.float32, (3,)), ("reserved", np.float32)])
+HIT_DTYPE = np.dtype([("t", np.float32), ("object", np.int32), ("triangle", np.int32), ("reserved", np.int32), ("point", np.float32, (3,)), ("reserved2", np.float32)])
+assert RAY_DTYPE.itemsize == 32 and HIT_DTYPE.itemsize == 32
+
+
+class TerraAmdRay(Structure):
+    _fields_ = [("origin", c_float * 3), ("tmax", c_float), ("direction", c_float * 3), ("reserved", c_float)]
+
+
+class TerraAmdHit(Structure):
+    _fields_ = [("t", c_float), ("object", c_int), ("triangle", c_int), ("reserved", c_int), ("point", c_float * 3), ("reserved2", c_float)]
+
+
+assert C.sizeof(TerraAmdRay) == 32 and C.sizeof(TerraAmdHit) == 32
+
+# name -> (restype, argtypes) of the ray-query entry points; terra_amd/runtime.py binds them with the rest of the terra_amd_* surface
+RAY_QUERY_SIGNATURES = {
+    "terra_amd_intersect_device": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "terra_amd_occluded_device": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "terra_amd_intersect": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
+    "terra_amd_occluded": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
+}
+
 # entry points of include/Terra.h + include/TerraPresets.h, name -> (restype, argtypes)
 API_SIGNATURES = {
     "scene_create": (c_void_p, []),

@@ -57,6 +57,16 @@ struct DevTemporalParams {
 hipError_t terra_launch_temporal_reproject ( const DevTemporalParams& p, const void* results, const void* aov, const void* history_in, void* history_out,
                                              void* out_results, void* out_moments, hipStream_t stream );
 
+// batched ray queries (query_kernels.hip; include/terra_amd.h "Ray queries"): rays = n TerraAmdRay, out = n TerraAmdHit (closest hit) or n uint32 (anyhit), all in HBM.
+// fast: traverse the fast tree (stack_depth / spill_cap as terra_plan_fast_tree made them; MODE 3 where scene.reach), otherwise the reference tree from global
+// memory with stack_depth entries (the launcher plans the leaf list), leaf_cull where the commit proved the cull, for origins within +-origin_limit
+struct DevQueryParams {
+    DevScene scene;
+    uint32_t fast, stack_depth, leaf_cap, spill_cap, leaf_cull;
+    float    origin_limit;
+};
+hipError_t terra_launch_query ( DevQueryParams p, const void* rays, size_t n, void* out, bool anyhit, hipStream_t stream );
+
 hipError_t terra_fill_sincos24 ( float2* table, hipStream_t stream );    // DevScene::sincos24: 2^24 entries (128 MB), device pointer
 
 // unit-level launchers: all pointers are DEVICE pointers, n items, synchronous semantics left to the caller

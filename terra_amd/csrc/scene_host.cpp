@@ -1601,6 +1601,78 @@ extern "C" int terra_amd_render_aov ( const TerraCamera* cam, HTerraScene h, Ter
     ( void ) hipFree ( d );
     return rc;
 }
+// ---- ray queries (query_kernels.hip) ---------------------------------------------------
+static_assert ( sizeof ( TerraAmdRay ) == 32 && sizeof ( TerraAmdHit ) == 32, "TerraAmdRay and TerraAmdHit must be 32 bytes" );
+// the one check of the four entry points: the scene can answer, the buffers are there, n fits the kernel's 32-bit ray index
+static int query_check ( Scene* s, const void* rays, size_t n, const void* out, const char* what ) {
+    if ( !s->committed ) return fail ( kTerraAmdErrNotCommitted, "terra_scene_commit has not run since the scene changed" );
+    if ( !s->device_ok ) return fail ( kTerraAmdErrNoDevice, "scene has no device replica: %s", s->commit_error.c_str() );
+    if ( n > ( size_t ) 0x7fffffff ) return fail ( kTerraAmdErrBadArgument, "%s: %zu rays in one call, at most 2^31 - 1", what, n );
+    if ( n > 0 && ( !rays || !out ) ) return fail ( kTerraAmdErrBadArgument, "%s: null ray or result buffer", what );
+    return 0;
+}
+// The traversal a render call of the scene takes (fill_params), without a camera: the fast tree where the commit chose it, otherwise the reference tree with the
+// leaf-box cull where the commit proved it. The render call checks its camera against the range that proof covers; a query's origins are in HBM, so the cull is
+// decided ray by ray on the device (origin_limit), and the fast tree is the caller's to give up (shortcut = false: the host forms, which see the origins).
+static int launch_query ( Scene* s, const void* d_rays, size_t n, void* d_out, bool anyhit, bool shortcut, hipStream_t stream ) {
+    const Scene::Replica& r = primary ( s );
+    const TreeChoice& c = s->tree;
+    DevRenderParams rp;
+    memset ( &rp, 0, sizeof rp );
+    rp.scene = r.dev;
+    DevQueryParams p;
+    memset ( &p, 0, sizeof p );
+    p.scene = r.dev;
+    p.origin_limit = ( c.reach || c.reach_cull ) ? c.reach_limit : TERRA_CULL_MAX_COORD;
+    if ( c.use_fast && r.dev.fast_nodes_h && ( s->tree_mode == 1 || shortcut ) ) {
+        terra_plan_fast_tree ( rp );
+        if ( s->test_fast_stack_lds > 0 ) {          // TEST HOOK (fill_params): a short LDS column
+            const uint32_t need = rp.stack_depth + rp.spill_cap;
+            rp.stack_depth = need < ( uint32_t ) s->test_fast_stack_lds ? need : ( uint32_t ) s->test_fast_stack_lds; rp.spill_cap = need - rp.stack_depth;
+        }
+        p.fast = 1; p.stack_depth = rp.stack_depth; p.spill_cap = rp.spill_cap;
+    } else {
+        p.stack_depth = r.dev.max_stack < 1 ? 1u : ( uint32_t ) r.dev.max_stack;
+        p.leaf_cull = ( c.cull_ok && shortcut ) ? 1u : 0u;
+    }
+    if ( s->test_pad_stack > 0 ) p.stack_depth += ( uint32_t ) s->test_pad_stack;          // TEST HOOK (fill_params): a deeper stack than the tree needs
+    p.scene.sincos24 = nullptr;
+    const hipError_t e = terra_launch_query ( p, d_rays, n, d_out, anyhit, stream );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "ray query launch: %s", hipGetErrorString ( e ) );
+    return 0;
+}
+static int query_device ( HTerraScene h, const void* d_rays, size_t n, void* d_out, bool anyhit, void* stream, const char* what ) {
+    Scene* s = S ( h );
+    if ( int rc = query_check ( s, d_rays, n, d_out, what ) ) return rc;
+    if ( n == 0 ) return 0;
+    HIP_TRY ( hipSetDevice ( primary ( s ).device ), kTerraAmdErrNoDevice );
+    return launch_query ( s, d_rays, n, d_out, anyhit, true, ( hipStream_t ) stream );
+}
+// host buffers: upload, query, download; synchronous. The origins are in reach here: one outside the range the commit's proof covers sends the call down the
+// reference tree's replica traversal, as a camera out there does to a render call.
+static int query_host ( HTerraScene h, const TerraAmdRay* rays, size_t n, void* out, size_t out_stride, bool anyhit, const char* what ) {
+    Scene* s = S ( h );
+    if ( int rc = query_check ( s, rays, n, out, what ) ) return rc;
+    if ( n == 0 ) return 0;
+    HIP_TRY ( hipSetDevice ( primary ( s ).device ), kTerraAmdErrNoDevice );
+    const TreeChoice& c = s->tree;
+    const float limit = ( c.reach || c.reach_cull ) ? c.reach_limit : TERRA_CULL_MAX_COORD;
+    bool shortcut = true;
+    for ( size_t i = 0; i < n && shortcut; ++i ) shortcut = fabsf ( rays[i].origin[0] ) <= limit && fabsf ( rays[i].origin[1] ) <= limit && fabsf ( rays[i].origin[2] ) <= limit;
+    char* d = nullptr;
+    HIP_TRY ( hipMalloc ( ( void** ) &d, n * ( sizeof ( TerraAmdRay ) + out_stride ) ), kTerraAmdErrNoDevice );
+    char* d_out = d + n * sizeof ( TerraAmdRay );
+    hipError_t e = hipMemcpy ( d, rays, n * sizeof ( TerraAmdRay ), hipMemcpyHostToDevice );
+    int rc = e == hipSuccess ? launch_query ( s, d, n, d_out, anyhit, shortcut, nullptr ) : fail ( kTerraAmdErrLaunch, "%s upload: %s", what, hipGetErrorString ( e ) );
+    if ( !rc ) { e = hipMemcpy ( out, d_out, n * out_stride, hipMemcpyDeviceToHost ); if ( e != hipSuccess ) rc = fail ( kTerraAmdErrLaunch, "%s download: %s", what, hipGetErrorString ( e ) ); }
+    ( void ) hipFree ( d );
+    return rc;
+}
+extern "C" int terra_amd_intersect_device ( HTerraScene h, const void* d_rays, size_t n, void* d_hits, void* stream ) { return query_device ( h, d_rays, n, d_hits, false, stream, "terra_amd_intersect_device" ); }
+extern "C" int terra_amd_occluded_device ( HTerraScene h, const void* d_rays, size_t n, void* d_occluded, void* stream ) { return query_device ( h, d_rays, n, d_occluded, true, stream, "terra_amd_occluded_device" ); }
+extern "C" int terra_amd_intersect ( HTerraScene h, const TerraAmdRay* rays, size_t n, TerraAmdHit* hits ) { return query_host ( h, rays, n, hits, sizeof ( TerraAmdHit ), false, "terra_amd_intersect" ); }
+extern "C" int terra_amd_occluded ( HTerraScene h, const TerraAmdRay* rays, size_t n, uint32_t* occluded ) { return query_host ( h, rays, n, occluded, sizeof ( uint32_t ), true, "terra_amd_occluded" ); }
+
 static int denoise_check ( Scene* s, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t h, int iterations, const char* what = "denoise" ) {
     if ( !s->committed ) return fail ( kTerraAmdErrNotCommitted, "terra_scene_commit has not run since the scene changed" );
     if ( !s->device_ok ) return fail ( kTerraAmdErrNoDevice, "scene has no device replica: %s", s->commit_error.c_str() );

@@ -205,9 +205,12 @@ TD void traverse_fast_resume ( const Tracer& T, const Ray& ray, const RayState& 
             float depth;
             if ( watertight_permuted ( tp, o_perm, st, depth ) ) {
                 if ( depth < best.depth || ( depth == best.depth && rank < best.rank ) ) {
-                    if ( !checked || reference_reaches ( T, ti, ray ) ) { best.depth = depth; best.rank = rank; best.tri = ti; }      // (checked: DevScene::reach, second pass)
-                    // a shadow ray that knows the triangle it expects (fast_expect) only asks whether ANY triangle comes first: this one does, the lane is done
-                    if ( anyhit ) { top = T.stack; hand = DEV_CHILD_EMPTY; held = 0u; }
+                    if ( !checked || reference_reaches ( T, ti, ray ) ) {      // (checked: DevScene::reach, second pass)
+                        best.depth = depth; best.rank = rank; best.tri = ti;
+                        // a shadow ray that knows the triangle it expects (fast_expect), or an occlusion query (query_kernels.hip), only asks whether ANY triangle comes
+                        // first: this one does, the lane is done. (With `checked` only a candidate the reference reaches ends the search; no render launch sets both.)
+                        if ( anyhit ) { top = T.stack; hand = DEV_CHILD_EMPTY; held = 0u; }
+                    }
                 }
             }
         }

@@ -127,6 +127,7 @@ _EXTRA = {
                                   [C.POINTER(api.TerraAmdAdaptiveOptions), C.POINTER(api.TerraAmdAdaptiveReport)]),
     "terra_amd_reproject_device": (C.c_int, [C.c_void_p, _CAM, _CAM] + [C.c_void_p] * 6 + [_SZ] * 6 + [C.POINTER(api.TerraAmdTemporalOptions), C.c_void_p]),
     "terra_amd_reproject": (C.c_int, [C.c_void_p, _CAM, _CAM, C.POINTER(api.TerraFramebuffer)] + [C.c_void_p] * 5 + [_SZ] * 4 + [C.POINTER(api.TerraAmdTemporalOptions)]),
+    **api.RAY_QUERY_SIGNATURES,
 }
 
 
@@ -334,6 +335,30 @@ def reproject_device(lib, scene, cam, prev_cam, fb: DeviceFramebuffer, aov: Devi
     check(lib.reproject_device(scene, C.byref(cam), C.byref(prev_cam), fb.results.data_ptr(), aov.data.data_ptr(), history_in.data.data_ptr() if history_in is not None else None,
                                history_out.data.data_ptr(), out_fb.results.data_ptr() if out_fb is not None else None, out_moments.data.data_ptr() if out_moments is not None else None,
                                fb.width, fb.height, x, y, w, h, C.byref(opt), stream), "terra_amd_reproject_device")
+
+
+def _query_rays(rays):
+    import torch
+    if not (isinstance(rays, torch.Tensor) and rays.is_cuda and rays.dtype == torch.float32 and rays.dim() == 2 and rays.shape[1] == 8 and rays.is_contiguous()):
+        raise TerraAmdError("ray queries take a contiguous float32 tensor [n, 8] on the scene's device: origin, tmax, direction, reserved (api.RAY_DTYPE)")
+    return torch, torch.cuda.current_stream(rays.device).cuda_stream or None
+
+
+def intersect(lib, scene, rays):
+    """terra_amd_intersect_device on rays (float32 [n, 8] in HBM: TerraAmdRay records) -> float32 [n, 8], TerraAmdHit records (view the words 1..3 as int32, or
+    .cpu().numpy().view(api.HIT_DTYPE)). Queued on the current torch stream; nothing is copied to the host."""
+    torch, stream = _query_rays(rays)
+    hits = torch.empty((rays.shape[0], 8), dtype=torch.float32, device=rays.device)
+    check(lib.intersect_device(scene, rays.data_ptr(), rays.shape[0], hits.data_ptr(), stream), "terra_amd_intersect_device")
+    return hits
+
+
+def occluded(lib, scene, rays):
+    """terra_amd_occluded_device on rays (as intersect) -> int32 [n], 1 where something lies within the ray's tmax. Queued on the current torch stream."""
+    torch, stream = _query_rays(rays)
+    out = torch.empty(rays.shape[0], dtype=torch.int32, device=rays.device)
+    check(lib.occluded_device(scene, rays.data_ptr(), rays.shape[0], out.data_ptr(), stream), "terra_amd_occluded_device")
+    return out
 
 
 def render_device_sharded(lib, cam, scene, fb: DeviceFramebuffer, tile: int, rank: int, world: int, stream=None):

@@ -45,5 +45,6 @@ hipError_t terra_launch_moments_accumulate ( const void*, void*, uint32_t, uint3
 hipError_t terra_launch_tile_error ( const void*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, float*, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_launch_denoise_variance ( const void*, const void*, const void*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, int, float, int, float, float*, float*, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_launch_temporal_reproject ( const DevTemporalParams&, const void*, const void*, const void*, void*, void*, void*, hipStream_t ) { return hipErrorNoDevice; }
+hipError_t terra_launch_query ( DevQueryParams, const void*, size_t, void*, bool, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_unit_texture_sample ( const DevTexture*, int, const float*, float* ) { return hipErrorNoDevice; }
 hipError_t terra_unit_texture_latlong ( const DevTexture*, int, const float*, float* ) { return hipErrorNoDevice; }
