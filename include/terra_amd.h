@@ -208,6 +208,25 @@ int  terra_amd_auto_sample_split ( size_t width, size_t height, size_t tile, int
 int  terra_amd_set_job_order ( HTerraScene scene, int on );
 int  terra_amd_get_job_order ( HTerraScene scene );
 
+/* Empty skip, on by default. A job-ordered launch (above) also PROVES pixel blocks empty before it starts: in double precision, a block whose footprint -- its pixels
+   clipped to the call's rectangle, widened by the sub-pixel jitter and one guard pixel -- is separated from every triangle of the scene by a plane through the camera
+   position (csrc/empty_proof.h; DESIGN.md 3.6 argues that the float triangle test of the render kernel then says "miss" for every camera ray of the block). Such blocks
+   are never keyed, queued or traced; the resolve kernel gives their pixels what the render would have: `sample split` sums of +0, samples += spp, exposure, tonemap.
+   The framebuffer is the same bit for bit (tests/test_empty_skip.py). The class is used only where a camera miss leaves nothing else behind: no environment lighting, no
+   work counters (they are defined by the walk; a per-pixel draw-count buffer asks for them), the scene and the camera inside the coordinate range of the leaf-box cull
+   (TerraAmdTraversalInfo::camera_limit). Every other launch behaves as with the switch off. A launch parameter: no commit needed.
+   terra_amd_empty_skip_info: out[0] = blocks proved empty, out[1] = all 16x16 pixel blocks of the scene's most recent single-device launch (0 proved when that launch did
+   not use the class). Synchronises the device; for tests and tools: the count lives in a word beside the scene's work counters on that device, so terra_amd_reset_stats
+   between the launch and this call zeroes it, and launches in flight on one scene at the same time (threads, the devices of terra_amd_render_multi) overwrite one
+   another's value -- the figure is exact for one launch at a time, which is how the tests and tools call it.
+   terra_amd_empty_proof: the predicate itself on the host -- 1 when the pixels [x0, x1) x [y0, y1) of a fb_w x fb_h frame are proved empty against n_tris triangles of
+   nine floats; camera as the launch has it (rows of the rotation, position, tan(fov / 2), aspect). Non-finite inputs and a degenerate footprint prove nothing. */
+int  terra_amd_set_empty_skip ( HTerraScene scene, int on );
+int  terra_amd_get_empty_skip ( HTerraScene scene );
+int  terra_amd_empty_skip_info ( HTerraScene scene, uint32_t out[2] );
+int  terra_amd_empty_proof ( const float* cam_rot9, const float* cam_pos3, float tan_half_fov, float aspect, float jitter, uint32_t fb_w, uint32_t fb_h,
+                             uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, const float* tris9, size_t n_tris );
+
 /* Environment lighting, off by default. The reference evaluates scene options' environment_map for a ray
    that leaves the scene, multiplies the throughput by it and then drops the result: the line that would
    add it is commented out (src/Terra.c:1053-1058), so the environment never reaches the image. With

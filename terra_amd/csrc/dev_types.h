@@ -165,7 +165,7 @@ struct DevScene {
 
 // indices into the device counter array (uint64 each); mirrors TerraAmdStats
 enum { kCtrRays = 0, kCtrNodes, kCtrBoxTests, kCtrTriTests, kCtrHits, kCtrSamples, kCtrRandCalls, kCtrAttrFetches, kCtrPixels, kCtrLaunches, kCtrFaults, kCtrTriCulled,
-       kCtrDbg0, kCtrDbgLast = kCtrDbg0 + 15, kCtrCount };   // kCtrFaults: only written by TERRA_CHECK_BOUNDS builds; kCtrDbg*: only by TERRA_PHASE_STATS builds (lane-occupancy study)
+       kCtrDbg0, kCtrDbgLast = kCtrDbg0 + 15, kCtrSkipProved /* not part of TerraAmdStats; stored, not counted: the blocks the last launch proved empty (terra_amd_empty_skip_info; zeroed with the counters by terra_amd_reset_stats) */, kCtrCount };   // kCtrFaults: only written by TERRA_CHECK_BOUNDS builds; kCtrDbg*: only by TERRA_PHASE_STATS builds (lane-occupancy study)
 
 struct DevRenderParams {
     DevScene scene;
@@ -229,4 +229,8 @@ struct DevRenderParams {
     // sampler integration (terra_amd_set_sampler_integration; compiled into the KINDS & TERRA_KIND_SAMPLER variants only): 0 off, 1 Halton, 2 stratified
     // (`sampler_strata` strata per dimension, 16 samples per stratum: the sampler the reference constructs at src/Terra.c:542)
     uint32_t sampler_mode, sampler_strata;
+    // empty skip (render_kernels.hip "proved empty"): the job order ends with the blocks that empty_proof.h proved empty; *job_live = the jobs before them
+    // (live blocks x split x 256, written by terra_block_order_kernel). Those blocks are never keyed, queued or traced: the resolve kernel adds their +0 sums.
+    // nullptr: every block is live. (Last, so that the kernels that never read it keep their argument offsets.)
+    const uint32_t* job_live;
 };

@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 #include "trace_device.h"
 #include "kernels.h"
+#include "empty_proof.h"
 
 // One source, several translation units (terra_amd/build.py compiles this file once per TERRA_TU value, in parallel: a single unit takes 3 minutes):
 //   TERRA_TU 0  everything that is not a render-kernel instance (resolve / tile kernels, LDS planning, the launch dispatch) + the kernels of template MODE 0
@@ -163,8 +164,10 @@ __global__ __launch_bounds__ ( 256 ) void terra_resolve_kernel ( DevRenderParams
     DevResult* results = reinterpret_cast<DevResult*> ( p.results );
     DevResult out = results[pix];
     uint32_t calls = 0;
+    // a block proved empty (DevRenderParams::job_live) has no sums: the render would have stored +0 for each of its chunks, and those are the adds made here
+    const bool proved = p.job_live && ( ( vb << p.split_log2 ) * 256u >= *p.job_live );
     for ( uint32_t j = 0; j < p.split; ++j ) {
-        const float4 q = p.partials[ ( ( size_t ) j * gridDim.x + vb ) * 256 + threadIdx.x];
+        const float4 q = proved ? make_float4 ( 0.f, 0.f, 0.f, 0.f ) : p.partials[ ( ( size_t ) j * gridDim.x + vb ) * 256 + threadIdx.x];
         out.acc[0] = out.acc[0] + q.x; out.acc[1] = out.acc[1] + q.y; out.acc[2] = out.acc[2] + q.z;
         calls += __float_as_uint ( q.w );
     }
@@ -412,7 +415,7 @@ TD void job_init_lane ( const DevRenderParams& p, float* aux ) {
 // TABLE: the job's streams come keyed from DevRenderParams::job_streams (LDS-resident scenes, whose kernels are bound by instruction issue: Cornell 56.7 -> 55.1 ms; the
 // kernels that wait on memory lose a little to the table's 64 bytes of traffic per job -- hall 244.1 -> 245.7 ms -- and key their streams here)
 template <int COUNT, bool TABLE>
-TD void job_next ( const DevRenderParams& p, float* aux, Jobs& j, PixelStreams& rs, const Counters& c ) {
+TD void job_next ( const DevRenderParams& p, float* aux, Jobs& j, PixelStreams& rs, const Counters& c, uint32_t total ) {      // total: where the job space ends (the launch's live jobs)
     uint32_t* auxu = reinterpret_cast<uint32_t*> ( aux );
     const uint32_t fin = auxu[768];
     if ( fin != TERRA_JOB_NONE ) {
@@ -423,7 +426,6 @@ TD void job_next ( const DevRenderParams& p, float* aux, Jobs& j, PixelStreams& 
     PoolWord* pool = job_pool_of_wave ( aux );
     const unsigned long long m = __ballot ( 1 );                 // the lanes here
     const uint32_t lane = threadIdx.x & 63u, n = ( uint32_t ) __popcll ( m ), ahead = ( uint32_t ) __popcll ( m & ( ( 1ull << lane ) - 1ull ) );
-    const uint32_t total = p.job_blocks * 256u;
     uint32_t next = pool_load ( pool ), end = pool_load ( pool + 1 );
     const uint32_t take = n < end - next ? n : end - next;
     uint32_t job = next + ahead;
@@ -479,6 +481,9 @@ __global__ __launch_bounds__ ( 256, TERRA_WAVES_FOR ( INTEGRATOR, KINDS, MODE ) 
     PixelStreams rs = trng_pixel_streams ( 0, 0, 0 );
     Counters c = counters_zero();
     float* acc_lds = reinterpret_cast<float*> ( T.stack - tid ) + ( p.stack_depth + p.leaf_cap ) * TERRA_COL + tid;     // the parked words follow the leaf list
+    // the job space ends where the blocks proved empty begin (DevRenderParams::job_live; only launches that key their streams ahead have such blocks): one uniform load per wave
+    uint32_t job_total = p.job_blocks * 256u;
+    if constexpr ( MODE == 1 ) { if ( p.job_live ) job_total = *p.job_live; }
     job_init_lane ( p, acc_lds );       // (make_tracer's barrier came before; a wave only ever touches its own pool words)
     Jobs jb; jb.px = jb.py = 0; jb.s = p.chunk_spp; jb.exhausted = false; jb.base = 0;
     SamplerPair sp = sampler_pair_none();       // (lives only in the KINDS & TERRA_KIND_SAMPLER variants)
@@ -536,7 +541,7 @@ __global__ __launch_bounds__ ( 256, TERRA_WAVES_FOR ( INTEGRATOR, KINDS, MODE ) 
                     }
                 }
                 if ( !start ) {
-                    if ( jb.s == p.chunk_spp ) { job_next<COUNT, MODE == 1> ( p, acc_lds, jb, rs, c ); if ( jb.exhausted ) done = true; }
+                    if ( jb.s == p.chunk_spp ) { job_next<COUNT, MODE == 1> ( p, acc_lds, jb, rs, c, job_total ); if ( jb.exhausted ) done = true; }
                     if ( jb.s != p.chunk_spp ) {
                         float r1 = trng_a_float ( rs.a ), r2 = trng_a_float ( rs.a );
                         ro = cam_pos; rd = camera_sample ( p, jb.px, jb.py, r1, r2 );
@@ -588,7 +593,7 @@ __global__ __launch_bounds__ ( 256, TERRA_WAVES_FOR ( INTEGRATOR, KINDS, MODE ) 
                     }
                 }
                 if ( !start ) {                                  // the path ended (or none was started yet): the pixel's next sample, or the lane's next job
-                    if ( jb.s == p.chunk_spp ) { job_next<COUNT, MODE == 1> ( p, acc_lds, jb, rs, c ); if ( jb.exhausted ) done = true; }
+                    if ( jb.s == p.chunk_spp ) { job_next<COUNT, MODE == 1> ( p, acc_lds, jb, rs, c, job_total ); if ( jb.exhausted ) done = true; }
                     if ( jb.s != p.chunk_spp ) {
                         float r1 = trng_a_float ( rs.a ), r2 = trng_a_float ( rs.a );
                         ro = cam_pos; rd = camera_sample ( p, jb.px, jb.py, r1, r2 );
@@ -632,7 +637,7 @@ __global__ __launch_bounds__ ( 256, TERRA_WAVES_FOR ( INTEGRATOR, KINDS, MODE ) 
                     if ( !next ) { deposit ( acc_lds, Lo ); have_ray = false; }
                 }
                 if ( !next ) {
-                    if ( jb.s == p.chunk_spp ) { job_next<COUNT, MODE == 1> ( p, acc_lds, jb, rs, c ); if ( jb.exhausted ) done = true; }
+                    if ( jb.s == p.chunk_spp ) { job_next<COUNT, MODE == 1> ( p, acc_lds, jb, rs, c, job_total ); if ( jb.exhausted ) done = true; }
                     if ( jb.s != p.chunk_spp ) {
                         float r1 = trng_a_float ( rs.a ), r2 = trng_a_float ( rs.a );
                         ro = cam_pos; rd = camera_sample ( p, jb.px, jb.py, r1, r2 );
@@ -676,7 +681,7 @@ __global__ __launch_bounds__ ( 256, TERRA_WAVES_FOR ( INTEGRATOR, KINDS, MODE ) 
         const bool any_alive = __any ( alive );
         if ( !alive && ( TERRA_REGEN_MIN <= 1 || !any_alive || __popcll ( __ballot ( !alive ) ) >= TERRA_REGEN_MIN ) ) {
             // (a lane waits at the boundary until TERRA_JOB_FETCH_MIN lanes do, or nobody is tracing: the switch then serves several lanes per execution)
-            if ( jb.s == p.chunk_spp && ( TERRA_JOB_FETCH_MIN <= 1 || !any_alive || __popcll ( __ballot ( jb.s == p.chunk_spp ) ) >= TERRA_JOB_FETCH_MIN ) ) job_next<COUNT, MODE == 1> ( p, acc_lds, jb, rs, c );
+            if ( jb.s == p.chunk_spp && ( TERRA_JOB_FETCH_MIN <= 1 || !any_alive || __popcll ( __ballot ( jb.s == p.chunk_spp ) ) >= TERRA_JOB_FETCH_MIN ) ) job_next<COUNT, MODE == 1> ( p, acc_lds, jb, rs, c, job_total );
             if ( jb.exhausted ) break;
             if ( jb.s != p.chunk_spp ) {
                 PS_WAVE ( c, kPsCamIter ); PS_LANE ( c, kPsCamLanes );
@@ -960,6 +965,7 @@ uint32_t terra_render_blocks ( const DevRenderParams& p ) {
 // numbered like the render kernel's jobs; a job whose pixel lies outside the rectangle has no entry (nobody reads it).
 __global__ __launch_bounds__ ( 256 ) void terra_job_streams_kernel ( DevRenderParams p ) {
     const uint32_t job = blockIdx.x * 256u + threadIdx.x;
+    if ( p.job_live && job >= *p.job_live ) return;          // a block proved empty: nobody takes its jobs
     uint32_t px, py;
     const uint32_t vblock = job >> 8, chunk = vblock & ( p.split - 1 ), v = vblock >> p.split_log2;
     if ( !job_pixel_of_block ( p, p.block_order ? p.block_order[v] : v, job & 255u, px, py ) ) { p.job_streams[2 * ( size_t ) job + 1] = make_uint4 ( 0u, 0u, 0xffffffffu, 0u ); return; }
@@ -977,7 +983,7 @@ __global__ __launch_bounds__ ( 256 ) void terra_job_streams_kernel ( DevRenderPa
 // short work to fill the lanes beside them, and the launch ends on jobs of a few ray iterations. Only the ORDER in which jobs are taken changes: which job a lane runs
 // never mattered (render_kernels.hip "jobs"), a block's sums are stored under its place in the order and the resolve kernel looks them up there (DevRenderParams::block_order).
 #define TERRA_CLASS_LDS_TRIS 256          // triangles the classifier stages in LDS (12 KB); larger scenes are read from global memory
-__global__ __launch_bounds__ ( 256 ) void terra_block_class_kernel ( DevRenderParams p, uint32_t nblocks, uint32_t* cls ) {
+__global__ __launch_bounds__ ( 256 ) void terra_block_class_kernel ( DevRenderParams p, uint32_t nblocks, uint32_t* cls, uint32_t prove ) {
     __shared__ float4 staged[3 * TERRA_CLASS_LDS_TRIS];
     const float4* tris = reinterpret_cast<const float4*> ( p.scene.tris );
     if ( p.scene.n_tris <= TERRA_CLASS_LDS_TRIS ) {          // (every thread of the block takes part, also those beyond the last pixel block)
@@ -1003,24 +1009,48 @@ __global__ __launch_bounds__ ( 256 ) void terra_block_class_kernel ( DevRenderPa
             }
         }
     }
-    const unsigned long long votes = __ballot ( hit );
-    if ( b < nblocks && k == 0 ) cls[b] = ( ( votes >> ( threadIdx.x & 56u ) ) & 0xffull ) ? 0u : 1u;
+    // proved empty (empty_proof.h, in double precision): the block's eight lanes share the triangles; one triangle that is not separated from the block's
+    // footprint, or a footprint that proves nothing, and the block stays a traced one
+    bool refuted = true;
+    if ( prove && b < nblocks ) {
+        uint32_t px, py;
+        if ( job_pixel_of_block ( p, b, 0u, px, py ) ) {                     // thread 0's pixel is the block's first; outside the rectangle: the block has no pixel
+            const uint32_t x1 = px + 16u < p.x + p.w ? px + 16u : p.x + p.w, y1 = py + 16u < p.y + p.h ? py + 16u : p.y + p.h;
+            const TerraEmptyPlanes planes = terra_empty_planes ( p.cam_rot, p.cam_pos, p.tan_half_fov, p.aspect, p.jitter, p.fb_w, p.fb_h, px, py, x1, y1 );
+            refuted = !planes.ok;
+            for ( uint32_t t = k; t < p.scene.n_tris && !refuted; t += 8u ) {
+                V3 ta, tb, tc; tri_vertices ( tris, t, ta, tb, tc );
+                const float fa[3] = { ta.x, ta.y, ta.z }, fb[3] = { tb.x, tb.y, tb.z }, fc[3] = { tc.x, tc.y, tc.z };
+                refuted = !terra_empty_separates ( planes, fa, fb, fc );
+            }
+        }
+    }
+    const unsigned long long votes = __ballot ( hit ), doubts = __ballot ( refuted );
+    const uint32_t group = threadIdx.x & 56u;
+    if ( b < nblocks && k == 0 ) cls[b] = ( ( votes >> group ) & 0xffull ) ? 0u : ( ( doubts >> group ) & 0xffull ) ? 1u : 2u;      // (a probe that hits outvotes a proof: never both, but the trace is the safe side)
 }
-// order[0 .. n): the blocks of class 0 in their own order, then those of class 1; order[n + b]: block b's place. One block of 256 threads.
-__global__ __launch_bounds__ ( 256 ) void terra_block_order_kernel ( uint32_t n, const uint32_t* cls, uint32_t* order ) {
-    __shared__ uint32_t before0[256];
-    __shared__ uint32_t total0;
+// order[0 .. n): the blocks of class 0 (hit) in their own order, then those of class 1 (empty by probe), then those of class 2 (proved empty); order[n + b]: block b's
+// place. *live_jobs (if given) = the jobs of the first two classes, jobs_per_block each; *proved (if given) = the blocks of class 2. One block of 256 threads.
+__global__ __launch_bounds__ ( 256 ) void terra_block_order_kernel ( uint32_t n, const uint32_t* cls, uint32_t* order, uint32_t* live_jobs, uint32_t jobs_per_block, unsigned long long* proved ) {
+    __shared__ uint32_t before0[256], before1[256];
+    __shared__ uint32_t total0, total1;
     const uint32_t t = threadIdx.x, per = ( n + 255u ) / 256u;
     const uint32_t lo = t * per < n ? t * per : n, hi = lo + per < n ? lo + per : n;
-    uint32_t c0 = 0;
-    for ( uint32_t i = lo; i < hi; ++i ) c0 += cls[i] == 0u;
-    before0[t] = c0;
+    uint32_t c0 = 0, c1 = 0;
+    for ( uint32_t i = lo; i < hi; ++i ) { c0 += cls[i] == 0u; c1 += cls[i] == 1u; }
+    before0[t] = c0; before1[t] = c1;
     __syncthreads();
-    if ( t == 0 ) { uint32_t run = 0; for ( uint32_t k = 0; k < 256u; ++k ) { const uint32_t c = before0[k]; before0[k] = run; run += c; } total0 = run; }
+    if ( t == 0 ) {
+        uint32_t run0 = 0, run1 = 0;
+        for ( uint32_t k = 0; k < 256u; ++k ) { const uint32_t a = before0[k], b = before1[k]; before0[k] = run0; before1[k] = run1; run0 += a; run1 += b; }
+        total0 = run0; total1 = run1;
+        if ( live_jobs ) *live_jobs = ( run0 + run1 ) * jobs_per_block;
+        if ( proved ) *proved = n - run0 - run1;
+    }
     __syncthreads();
-    uint32_t at0 = before0[t], at1 = total0 + ( lo - before0[t] );
+    uint32_t at0 = before0[t], at1 = total0 + before1[t], at2 = total0 + total1 + ( lo - before0[t] - before1[t] );
     for ( uint32_t i = lo; i < hi; ++i ) {
-        const uint32_t v = cls[i] == 0u ? at0++ : at1++;
+        const uint32_t v = cls[i] == 0u ? at0++ : cls[i] == 1u ? at1++ : at2++;
         order[v] = i; order[n + i] = v;
     }
 }
@@ -1035,11 +1065,12 @@ size_t terra_block_order_bytes ( const DevRenderParams& p, bool small_too ) {   
     //  and its two extra small kernels would queue behind the other callers' render grids: the reference client's tile loop 66.5 -> 72.6 ms with them)
     return blocks >= ( small_too ? 1u : ( unsigned ) TERRA_JOB_ORDER_MIN_BLOCKS ) ? ( blocks * 3 * sizeof ( uint32_t ) + 255 ) & ~size_t ( 255 ) : 0;
 }
-hipError_t terra_launch_block_order ( const DevRenderParams& p, uint32_t* cls, hipStream_t stream ) {      // p.block_order = cls + blocks
+hipError_t terra_launch_block_order ( const DevRenderParams& p, uint32_t* cls, hipStream_t stream ) {      // p.block_order = cls + blocks; p.job_live set: the launch skips the blocks proved empty
     const uint32_t blocks = terra_render_blocks ( p );
     if ( !p.block_order || !cls || blocks == 0 ) return hipErrorInvalidValue;
-    hipLaunchKernelGGL ( terra_block_class_kernel, dim3 ( ( blocks * 8 + 255 ) / 256 ), dim3 ( 256 ), 0, stream, p, blocks, cls );      // eight lanes per pixel block
-    hipLaunchKernelGGL ( terra_block_order_kernel, dim3 ( 1 ), dim3 ( 256 ), 0, stream, blocks, ( const uint32_t* ) cls, const_cast<uint32_t*> ( p.block_order ) );
+    hipLaunchKernelGGL ( terra_block_class_kernel, dim3 ( ( blocks * 8 + 255 ) / 256 ), dim3 ( 256 ), 0, stream, p, blocks, cls, p.job_live ? 1u : 0u );      // eight lanes per pixel block
+    hipLaunchKernelGGL ( terra_block_order_kernel, dim3 ( 1 ), dim3 ( 256 ), 0, stream, blocks, ( const uint32_t* ) cls, const_cast<uint32_t*> ( p.block_order ),
+                         const_cast<uint32_t*> ( p.job_live ), p.split * 256u, p.job_live && p.counters ? p.counters + kCtrSkipProved : nullptr );
     return hipGetLastError();
 }
 hipError_t terra_launch_job_streams ( const DevRenderParams& p, hipStream_t stream ) {

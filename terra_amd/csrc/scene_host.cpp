@@ -27,6 +27,7 @@
 #include "../../include/TerraPresets.h"
 #include "dev_types.h"
 #include "kernels.h"
+#include "empty_proof.h"
 #include "tree_build.h"
 #include "multi_gpu.h"
 
@@ -367,6 +368,8 @@ struct Scene {
     bool env_sampling = false;          // terra_amd_set_environment_sampling: Direct / Direct+MIS sample a lat-long environment through a TerraDistribution2D (built at commit)
     bool env_mis = false;               // terra_amd_set_environment_mis: Direct+MIS weights that sample against its BSDF ray (a launch parameter)
     int job_order = 1;                  // terra_amd_set_job_order (0 off, 1 on, 2 on for launches of any size): launches that key their streams ahead hand out the pixel blocks no camera ray hits last (launch_render)
+    int empty_skip = 1;                 // terra_amd_set_empty_skip: job-ordered launches neither key nor trace the pixel blocks proved empty before the launch (empty_proof.h, launch_render)
+    std::atomic<uint32_t> skip_last_blocks { 0 }; std::atomic<int> skip_last_device { -1 };      // terra_amd_empty_skip_info: the last launch's pixel blocks; the device whose counter holds its proved ones (-1: that launch proved nothing)
     bool sampler_integration = false;   // terra_amd_set_sampler_integration: the pixel's Halton / stratified sampler feeds the first bounce (a launch parameter)
     std::string commit_error;
     std::atomic<bool> warned_camera { false };      // the per-call fallback (camera outside camera_limit) has been reported on stderr once
@@ -502,6 +505,20 @@ extern "C" int terra_amd_set_job_order ( HTerraScene h, int on ) {
     S ( h )->job_order = on; return 0;
 }
 extern "C" int terra_amd_get_job_order ( HTerraScene h ) { return S ( h )->job_order; }
+extern "C" int terra_amd_set_empty_skip ( HTerraScene h, int on ) {
+    if ( on < 0 || on > 1 ) return fail ( kTerraAmdErrBadArgument, "terra_amd_set_empty_skip: 0 (off) or 1 (on)" );
+    S ( h )->empty_skip = on; return 0;
+}
+extern "C" int terra_amd_get_empty_skip ( HTerraScene h ) { return S ( h )->empty_skip; }
+// the predicate of empty_proof.h on the host (tests, tools): 1 when the block of pixels [x0, x1) x [y0, y1) is proved empty against n_tris triangles of 9 floats each
+extern "C" int terra_amd_empty_proof ( const float* cam_rot9, const float* cam_pos3, float tan_half_fov, float aspect, float jitter, uint32_t fb_w, uint32_t fb_h,
+                                       uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, const float* tris9, size_t n_tris ) {
+    if ( !cam_rot9 || !cam_pos3 || ( n_tris && !tris9 ) ) return 0;
+    const TerraEmptyPlanes planes = terra_empty_planes ( cam_rot9, cam_pos3, tan_half_fov, aspect, jitter, fb_w, fb_h, x0, y0, x1, y1 );
+    if ( !planes.ok ) return 0;
+    for ( size_t t = 0; t < n_tris; ++t ) if ( !terra_empty_separates ( planes, tris9 + 9 * t, tris9 + 9 * t + 3, tris9 + 9 * t + 6 ) ) return 0;
+    return 1;
+}
 extern "C" int terra_amd_set_sampler_integration ( HTerraScene h, int on ) { S ( h )->sampler_integration = on != 0; return 0; }
 extern "C" int terra_amd_get_sampler_integration ( HTerraScene h ) { return S ( h )->sampler_integration ? 1 : 0; }
 extern "C" void terra_amd_set_frame_seed ( HTerraScene h, uint64_t seed ) { S ( h )->frame_seed = seed; }
@@ -1493,6 +1510,11 @@ static int launch_render ( Scene* s, DevRenderParams& p, int device, hipStream_t
     p.stack_spill = spill_bytes ? ( uint32_t* ) ( ( char* ) scratch + header + partial_bytes + stream_bytes ) : nullptr;
     uint32_t* const order_cls = order_bytes ? ( uint32_t* ) ( ( char* ) scratch + header + partial_bytes + stream_bytes + spill_bytes ) : nullptr;
     p.block_order = order_cls ? order_cls + blocks : nullptr;
+    // empty skip (render_kernels.hip "proved empty"): only where a camera miss leaves nothing behind but +0 sums -- no environment term, no work counters (they are
+    // defined by the walk; a per-pixel draw count asks for them too) -- and only inside the coordinate range of the containment proof, which is the fused box test's
+    // precondition and the range DESIGN.md 3.6 argues the float triangle test in. Every integrator of the LDS-resident (coupled) loop deposits +0 for a camera miss.
+    const bool skip = s->empty_skip && order_cls && p.job_queue && p.lds_mode == 1 && p.scene.env_mode == 0 && p.count_level == 0 && !p.rand_calls && p.fused_slab;
+    p.job_live = skip ? ( const uint32_t* ) ( ( const char* ) scratch + 128 ) : nullptr;      // (in the header, on a cache line of its own away from the queue word)
     {   // the job decode divides block numbers by launch constants: as multiplications by ceil(2^32 / d), exact while (largest dividend) * divisor < 2^32
         const uint64_t bpt = p.tile_size / 16, bpt2 = bpt * bpt, tiles_x = ( p.w + p.tile_size - 1 ) / p.tile_size, tiles_y = ( p.h + p.tile_size - 1 ) / p.tile_size;
         auto magic = [] ( uint64_t d ) { return d <= 1 ? 0u : ( uint32_t ) ( ( ( 1ull << 32 ) + d - 1 ) / d ); };
@@ -1513,6 +1535,7 @@ static int launch_render ( Scene* s, DevRenderParams& p, int device, hipStream_t
     if ( pooled ) ( void ) hipFreeAsync ( scratch, stream );
     else if ( e != hipSuccess ) ( void ) hipMemsetAsync ( scratch, 0, header, stream );       // (a launch that failed half way must not leave a used queue word behind)
     if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "render launch: %s", hipGetErrorString ( e ) );
+    s->skip_last_blocks.store ( blocks, std::memory_order_relaxed ); s->skip_last_device.store ( skip ? device : -1, std::memory_order_relaxed );      // (only a launch that was queued whole is reported)
     return 0;
 }
 
@@ -1534,6 +1557,22 @@ extern "C" int terra_amd_render_device_sharded ( const TerraCamera* cam, HTerraS
 extern "C" int terra_amd_render_device ( const TerraCamera* cam, HTerraScene h, void* d_pixels, void* d_results, size_t fb_w, size_t fb_h,
                                          size_t x, size_t y, size_t w, size_t hgt, void* d_rand_calls, void* stream ) {
     return terra_amd_render_device_sharded ( cam, h, d_pixels, d_results, fb_w, fb_h, x, y, w, hgt, 64, 0, 1, d_rand_calls, stream );
+}
+// proved / total pixel blocks of the scene's most recent launch (one device; synchronises that device)
+extern "C" int terra_amd_empty_skip_info ( HTerraScene h, uint32_t out[2] ) {
+    Scene* s = S ( h );
+    if ( !out ) return fail ( kTerraAmdErrBadArgument, "terra_amd_empty_skip_info: null output" );
+    out[0] = 0; out[1] = s->skip_last_blocks.load ( std::memory_order_relaxed );
+    const int device = s->skip_last_device.load ( std::memory_order_relaxed );
+    if ( device < 0 ) return 0;
+    for ( const Scene::Replica& r : s->replicas ) if ( r.device == device && r.d_counters ) {
+        unsigned long long v = 0;
+        HIP_TRY ( hipSetDevice ( device ), kTerraAmdErrNoDevice );
+        HIP_TRY ( hipDeviceSynchronize(), kTerraAmdErrLaunch );
+        HIP_TRY ( hipMemcpy ( &v, r.d_counters + kCtrSkipProved, sizeof v, hipMemcpyDeviceToHost ), kTerraAmdErrLaunch );
+        out[0] = ( uint32_t ) v;
+    }
+    return 0;
 }
 extern "C" int terra_amd_synchronize ( void* stream ) {
     HIP_TRY ( hipStreamSynchronize ( ( hipStream_t ) stream ), kTerraAmdErrLaunch );

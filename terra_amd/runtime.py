@@ -93,6 +93,10 @@ _EXTRA = {
     "terra_amd_get_tree_builder": (C.c_int, [C.c_void_p]),
     "terra_amd_set_job_order": (C.c_int, [C.c_void_p, C.c_int]),
     "terra_amd_get_job_order": (C.c_int, [C.c_void_p]),
+    "terra_amd_set_empty_skip": (C.c_int, [C.c_void_p, C.c_int]),
+    "terra_amd_get_empty_skip": (C.c_int, [C.c_void_p]),
+    "terra_amd_empty_skip_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    "terra_amd_empty_proof": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float] + [C.c_uint32] * 6 + [C.c_void_p, C.c_size_t]),
     "terra_amd_set_sample_split": (C.c_int, [C.c_void_p, C.c_int]),
     "terra_amd_get_sample_split": (C.c_int, [C.c_void_p]),
     "terra_amd_auto_sample_split": (C.c_int, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_size_t, C.c_int]),
@@ -154,6 +158,13 @@ def check(rc: int, what: str = "") -> int:
     if rc < 0:
         raise TerraAmdError(f"{what}: {load().last_error().decode()} (status {rc})")
     return rc
+
+
+def empty_skip_info(lib: api.TerraLib, scene):
+    """(proved, total) 16x16 pixel blocks of the scene's most recent launch (terra_amd_empty_skip_info; synchronises the device)"""
+    out = (C.c_uint32 * 2)()
+    check(lib.empty_skip_info(scene, out), "terra_amd_empty_skip_info")
+    return int(out[0]), int(out[1])
 
 
 def last_error() -> str:
