@@ -21,8 +21,8 @@ SOURCES = [("scene_host.cpp", "scene_host.cpp", []), ("tree_build.cpp", "tree_bu
            ("render_kernels.hip", "render_kernels.tu0.hip", ["-DTERRA_TU=0"]), ("render_kernels.hip", "render_kernels.tu1.hip", ["-DTERRA_TU=1"]),
            ("render_kernels.hip", "render_kernels.tu2.hip", ["-DTERRA_TU=2"]), ("render_kernels.hip", "render_kernels.tu3.hip", ["-DTERRA_TU=3"]),
            ("unit_kernels.hip", "unit_kernels.hip", []), ("tree_build_device.hip", "tree_build_device.hip", []),
-           ("aov_kernels.hip", "aov_kernels.hip", []), ("variance_kernels.hip", "variance_kernels.hip", []),
-           ("temporal_kernels.hip", "temporal_kernels.hip", []), ("query_kernels.hip", "query_kernels.hip", [])]
+           ("aov_kernels.hip", "aov_kernels.hip", []), ("denoise_kernels.hip", "denoise_kernels.hip", []),
+           ("variance_kernels.hip", "variance_kernels.hip", []), ("temporal_kernels.hip", "temporal_kernels.hip", []), ("query_kernels.hip", "query_kernels.hip", [])]
 HEADERS = ["dev_types.h", "dev_math.h", "rng.h", "trace_device.h", "trace_math.h", "trace_geometry.h", "traverse_ref.h", "traverse_fast.h", "shading_device.h",
            "integrators_device.h", "sampling_device.h", "denoise_device.h", "kernels.h", "empty_proof.h", "tree_build.h", "multi_gpu.h"]
 ARCH = os.environ.get("TERRA_AMD_ARCH", "gfx950")

@@ -1,17 +1,13 @@
-// aov_kernels.hip -- first-hit AOV buffers and the edge-avoiding a-trous denoiser (include/terra_amd.h "AOV buffers", "Denoiser"; DESIGN.md
-// "AOV buffers and the denoiser").
+// aov_kernels.hip -- first-hit AOV buffers (include/terra_amd.h "AOV buffers"; DESIGN.md "AOV buffers and the denoiser"). The denoiser that reads them is
+// denoise_kernels.hip.
 //
-// AOV pass: one camera ray per sample, nothing shaded. Sample n of a pixel traces exactly the camera ray sample n of the same pixel traces in the render:
+// One camera ray per sample, nothing shaded. Sample n of a pixel traces exactly the camera ray sample n of the same pixel traces in the render:
 // the same stream keys (pixel, samples already in the AOV pixel + chunk * chunk_spp), the same draws (r1, r2 from stream A, then the sampler integration's
 // pair), the same sample split (scene_host.cpp launch_split) and the traversal the render call would take (fill_params). A 256-thread block holds 256 / split
 // pixels x split chunks; the chunk sums meet in LDS and the chunk-0 lane of each pixel adds them to the buffer in chunk order -- what terra_resolve_kernel does.
 // The grid is capped and strides over the blocks (the fast tree's stack spill is sized for the grid, not the frame).
-//
-// Denoiser: a prepass packs the guides, K step kernels ping-pong the demodulated radiance, a final kernel remodulates and tonemaps. One lane per pixel,
-// 16x16 blocks, every buffer of the filter indexed over the rectangle. No atomics: the same inputs give the same bits.
 #include <hip/hip_runtime.h>
 #include "trace_device.h"
-#include "denoise_device.h"
 #include "kernels.h"
 
 struct DevAov { float albedo[3]; float coverage; float normal[3]; float depth; int samples; int reserved[3]; };      // TerraAmdAovResult
@@ -114,115 +110,4 @@ hipError_t terra_launch_aov ( DevRenderParams p, void* aov, hipStream_t stream )
     const hipError_t e = hipGetLastError();
     if ( spill ) ( void ) hipFreeAsync ( spill, stream );
     return e;
-}
-
-// ---- denoiser -----------------------------------------------------------------------------------------------------------
-// (the filter's constants and per-tap weights: denoise_device.h, shared with the variance-guided form in variance_kernels.hip)
-
-__global__ __launch_bounds__ ( 256 ) void terra_denoise_prepass ( const float4* results, const float4* aov, uint32_t fb_w, uint32_t x, uint32_t y, uint32_t w, uint32_t h,
-                                                                  float4* g0, float4* g1, float4* u ) {
-    const uint32_t lx = blockIdx.x * 16u + threadIdx.x, ly = blockIdx.y * 16u + threadIdx.y;
-    if ( lx >= w || ly >= h ) return;
-    const size_t pix = ( size_t ) ( y + ly ) * fb_w + ( x + lx ), i = ( size_t ) ly * w + lx;
-    DN_PIXEL_INPUTS ( results, aov, pix )               // res, samples, c, finite, a0, a1, a, nv, z (denoise_device.h: shared with the temporal reprojection)
-    g0[i] = make_float4 ( nv.x, nv.y, nv.z, z );
-    g1[i] = make_float4 ( a.x, a.y, a.z, finite ? 1.f : ( samples > 0 ? 2.f : 0.f ) );
-    u[i] = finite ? dn_valid4 ( dn_demodulate ( c, a ) ) : make_float4 ( 0.f, 0.f, 0.f, 0.f );
-}
-
-// iteration `it` (step 2^it): u.w = 1 marks a valid pixel of the input / output
-__global__ __launch_bounds__ ( 256 ) void terra_denoise_step ( const float4* g0, const float4* g1, const float4* uin, float4* uout, uint32_t w, uint32_t h, int it ) {
-    const uint32_t lx = blockIdx.x * 16u + threadIdx.x, ly = blockIdx.y * 16u + threadIdx.y;
-    if ( lx >= w || ly >= h ) return;
-    const size_t i = ( size_t ) ly * w + lx;
-    const float4 up = uin[i];
-    const bool pending = it == 0 && g1[i].w == 2.f;
-    if ( up.w == 0.f && !pending ) { uout[i] = make_float4 ( 0.f, 0.f, 0.f, 0.f ); return; }
-    const int step = 1 << it;
-    const float sigma_c2 = TERRA_DN_SIGMA_C2 * ldexpf ( 1.f, -2 * it ), zs = TERRA_DN_SIGMA_Z * ( float ) step;
-    const float4 gp = g0[i];
-    const bool np_zero = gp.x == 0.f && gp.y == 0.f && gp.z == 0.f;
-    const float lp = dn_lum ( up.x, up.y, up.z );
-    float sw = 0.f, sx = 0.f, sy = 0.f, sz = 0.f;
-    for ( int dy = -2; dy <= 2; ++dy ) {
-        const int qy = ( int ) ly + step * dy;
-        if ( qy < 0 || qy >= ( int ) h ) continue;
-        for ( int dx = -2; dx <= 2; ++dx ) {
-            const int qx = ( int ) lx + step * dx;
-            if ( qx < 0 || qx >= ( int ) w ) continue;
-            const size_t q = ( size_t ) qy * w + qx;
-            const float4 uq = uin[q];
-            if ( uq.w == 0.f ) continue;
-            const float4 gq = g0[q];
-            const float wc = pending ? 1.f : dn_weight_colour ( up, uq, lp, dn_lum ( uq.x, uq.y, uq.z ), sigma_c2 );
-            const float wn = dn_weight_normal ( gp, gq, np_zero ), wz = dn_weight_depth ( gp, gq, zs );
-            const float W = ( ( ( dn_kernel ( dx ) * dn_kernel ( dy ) ) * wc ) * wn ) * wz;
-            sw = sw + W; sx = sx + W * uq.x; sy = sy + W * uq.y; sz = sz + W * uq.z;
-        }
-    }
-    uout[i] = sw > 0.f ? make_float4 ( sx / sw, sy / sw, sz / sw, 1.f ) : make_float4 ( 0.f, 0.f, 0.f, 0.f );
-}
-
-// remodulate and tonemap (iterations == 0: the framebuffer's own mean, as terra_resolve_kernel computes it)
-__global__ __launch_bounds__ ( 256 ) void terra_denoise_finish ( const float4* results, const float4* g1, const float4* u, uint32_t fb_w, uint32_t x, uint32_t y, uint32_t w, uint32_t h,
-                                                                 int iterations, float exposure, int op, float gamma, float* radiance, float* pixels ) {
-    const uint32_t lx = blockIdx.x * 16u + threadIdx.x, ly = blockIdx.y * 16u + threadIdx.y;
-    if ( lx >= w || ly >= h ) return;
-    const size_t pix = ( size_t ) ( y + ly ) * fb_w + ( x + lx ), i = ( size_t ) ly * w + lx;
-    V3 rad = v3 ( 0.f, 0.f, 0.f );
-    if ( iterations == 0 ) {
-        const float4 res = results[pix];
-        const int samples = __float_as_int ( res.w );
-        const float n = ( float ) samples;
-        if ( samples > 0 ) rad = v3 ( res.x / n, res.y / n, res.z / n );
-    } else {
-        const float4 uq = u[i];
-        if ( uq.w != 0.f ) {
-            const float4 a = g1[i];
-            rad = v3 ( uq.x * dn_max ( a.x, TERRA_DN_ALBEDO_MIN ), uq.y * dn_max ( a.y, TERRA_DN_ALBEDO_MIN ), uq.z * dn_max ( a.z, TERRA_DN_ALBEDO_MIN ) );
-        }
-    }
-    if ( radiance ) { radiance[3 * pix] = rad.x; radiance[3 * pix + 1] = rad.y; radiance[3 * pix + 2] = rad.z; }
-    if ( pixels ) {
-        const V3 color = tonemap ( rad * exposure, op, gamma );
-        pixels[3 * pix] = color.x; pixels[3 * pix + 1] = color.y; pixels[3 * pix + 2] = color.z;
-    }
-}
-
-hipError_t terra_launch_denoise ( const void* results, const void* aov, uint32_t fb_w, uint32_t x, uint32_t y, uint32_t w, uint32_t h, int iterations,
-                                  float exposure, int op, float gamma, float* radiance, float* pixels, hipStream_t stream ) {
-    if ( w == 0 || h == 0 || ( !radiance && !pixels ) ) return hipSuccess;
-    const dim3 grid ( ( w + 15u ) / 16u, ( h + 15u ) / 16u ), block ( 16, 16 );
-    const float4* res = reinterpret_cast<const float4*> ( results );
-    float4* scratch = nullptr;
-    const size_t n = ( size_t ) w * h;
-    if ( iterations > 0 ) { const hipError_t e = hipMallocAsync ( ( void** ) &scratch, 4 * n * sizeof ( float4 ), stream ); if ( e != hipSuccess ) return e; }
-    float4* g0 = scratch; float4* g1 = scratch ? scratch + n : nullptr; float4* ua = scratch ? scratch + 2 * n : nullptr; float4* ub = scratch ? scratch + 3 * n : nullptr;
-    if ( iterations > 0 ) {
-        hipLaunchKernelGGL ( terra_denoise_prepass, grid, block, 0, stream, res, reinterpret_cast<const float4*> ( aov ), fb_w, x, y, w, h, g0, g1, ua );
-        for ( int it = 0; it < iterations; ++it ) {
-            hipLaunchKernelGGL ( terra_denoise_step, grid, block, 0, stream, g0, g1, ua, ub, w, h, it );
-            float4* t = ua; ua = ub; ub = t;
-        }
-    }
-    hipLaunchKernelGGL ( terra_denoise_finish, grid, block, 0, stream, res, g1, ua, fb_w, x, y, w, h, iterations, exposure, op, gamma, radiance, pixels );
-    const hipError_t e = hipGetLastError();
-    if ( scratch ) ( void ) hipFreeAsync ( scratch, stream );
-    return e;
-}
-
-// the filter's first and last kernel on their own, for the variance-guided form (variance_kernels.hip), which runs its own steps between them:
-// g0, g1, u are planes of w * h float4 indexed over the rectangle
-hipError_t terra_launch_denoise_prepass ( const void* results, const void* aov, uint32_t fb_w, uint32_t x, uint32_t y, uint32_t w, uint32_t h, void* g0, void* g1, void* u, hipStream_t stream ) {
-    const dim3 grid ( ( w + 15u ) / 16u, ( h + 15u ) / 16u ), block ( 16, 16 );
-    hipLaunchKernelGGL ( terra_denoise_prepass, grid, block, 0, stream, reinterpret_cast<const float4*> ( results ), reinterpret_cast<const float4*> ( aov ), fb_w, x, y, w, h,
-                         reinterpret_cast<float4*> ( g0 ), reinterpret_cast<float4*> ( g1 ), reinterpret_cast<float4*> ( u ) );
-    return hipGetLastError();
-}
-hipError_t terra_launch_denoise_finish ( const void* results, const void* g1, const void* u, uint32_t fb_w, uint32_t x, uint32_t y, uint32_t w, uint32_t h, int iterations,
-                                         float exposure, int op, float gamma, float* radiance, float* pixels, hipStream_t stream ) {
-    const dim3 grid ( ( w + 15u ) / 16u, ( h + 15u ) / 16u ), block ( 16, 16 );
-    hipLaunchKernelGGL ( terra_denoise_finish, grid, block, 0, stream, reinterpret_cast<const float4*> ( results ), reinterpret_cast<const float4*> ( g1 ), reinterpret_cast<const float4*> ( u ),
-                         fb_w, x, y, w, h, iterations, exposure, op, gamma, radiance, pixels );
-    return hipGetLastError();
 }

@@ -1,5 +1,6 @@
-// denoise_device.h -- what the a-trous filter (aov_kernels.hip) and its variance-guided form (variance_kernels.hip) share: the filter's constants and its
-// per-tap weights, each defined once (include/terra_amd.h "Denoiser", "Variance-guided denoiser").
+// denoise_device.h -- what the a-trous filter (denoise_kernels.hip), the moments (variance_kernels.hip) and the temporal reprojection (temporal_kernels.hip)
+// share, each defined once: the filter's constants and per-tap weights, the per-pixel inputs, the lane-to-pixel mapping and the variance of a moments entry
+// (include/terra_amd.h "Denoiser", "Variance-guided denoiser").
 #pragma once
 #include <hip/hip_runtime.h>
 #include "trace_math.h"
@@ -16,29 +17,45 @@
 TD float dn_max ( float a, float b ) { return a > b ? a : b; }
 TD bool dn_finite ( float v ) { return ( __float_as_uint ( v ) & 0x7f800000u ) != 0x7f800000u; }
 TD float dn_lum ( float x, float y, float z ) { return 0.2126f * x + 0.7152f * y + 0.0722f * z; }
-// The "Denoiser" section's per-pixel quantities, declared as locals of the kernel that names them: res (the result word), samples, n = float(samples),
-// c = acc / samples, finite (VALID: samples > 0 and c finite), a0 / a1 (the AOV entry's first two words), a / z / nv (the means over the hits, all zero without one; nv
-// normalised, zero if its length <= 1e-6). A macro and not a function so that the a-trous prepass, which had this text before the temporal reprojection shared it,
-// still compiles to the same instructions (tools/isa_same.sh): through a function, by value or by reference, the compiler schedules the prepass differently.
-// MAINTENANCE HAZARD: the macro injects ten names into the caller's scope (res, samples, n, c, finite, a0, a1, a, nv, z) and `len` into an inner block. A kernel that
-// uses it must declare none of the ten itself, may rely on any of them (temporal_kernels.hip reads n), and a `len` of its own must come after the macro. Adding a
-// name here means checking both users. If the prepass's instructions are ever allowed to change, replace this with a function that returns a struct.
-#define DN_PIXEL_INPUTS( results, aov, pix ) \
-    const float4 res = ( results )[pix]; \
-    const int samples = __float_as_int ( res.w ); \
-    const float n = ( float ) samples; \
-    const V3 c = v3 ( res.x / n, res.y / n, res.z / n ); \
-    const bool finite = samples > 0 && dn_finite ( c.x ) && dn_finite ( c.y ) && dn_finite ( c.z ); \
-    const float4 a0 = ( aov )[3 * ( pix )], a1 = ( aov )[3 * ( pix ) + 1]; \
-    V3 a = v3 ( 0.f, 0.f, 0.f ), nv = v3 ( 0.f, 0.f, 0.f ); \
-    float z = 0.f; \
-    if ( a0.w > 0.f ) { \
-        a = v3 ( a0.x / a0.w, a0.y / a0.w, a0.z / a0.w ); \
-        z = a1.w / a0.w; \
-        nv = v3 ( a1.x / a0.w, a1.y / a0.w, a1.z / a0.w ); \
-        const float len = length ( nv ); \
-        nv = len > TERRA_DN_NORMAL_MIN ? v3 ( nv.x / len, nv.y / len, nv.z / len ) : v3 ( 0.f, 0.f, 0.f ); \
+// The "Denoiser" section's per-pixel quantities of frame pixel `pix`: res (the result word), samples, n = float(samples), c = acc / samples, finite (VALID:
+// samples > 0 and c finite), a0 / a1 (the AOV entry's first two words), a / z / nv (the means over the hits, all zero without one; nv normalised, zero if its
+// length <= 1e-6). Shared by the a-trous prepass (denoise_kernels.hip) and the temporal reprojection (temporal_kernels.hip).
+struct DnPixel { float4 res; int samples; float n; V3 c; bool finite; float4 a0, a1; V3 a, nv; float z; };
+TD DnPixel dn_pixel ( const float4* results, const float4* aov, size_t pix ) {
+    DnPixel p;
+    p.res = results[pix];
+    p.samples = __float_as_int ( p.res.w );
+    p.n = ( float ) p.samples;
+    p.c = v3 ( p.res.x / p.n, p.res.y / p.n, p.res.z / p.n );
+    p.finite = p.samples > 0 && dn_finite ( p.c.x ) && dn_finite ( p.c.y ) && dn_finite ( p.c.z );
+    p.a0 = aov[3 * pix]; p.a1 = aov[3 * pix + 1];
+    p.a = v3 ( 0.f, 0.f, 0.f ); p.nv = v3 ( 0.f, 0.f, 0.f );
+    p.z = 0.f;
+    if ( p.a0.w > 0.f ) {
+        p.a = v3 ( p.a0.x / p.a0.w, p.a0.y / p.a0.w, p.a0.z / p.a0.w );
+        p.z = p.a1.w / p.a0.w;
+        p.nv = v3 ( p.a1.x / p.a0.w, p.a1.y / p.a0.w, p.a1.z / p.a0.w );
+        const float len = length ( p.nv );
+        p.nv = len > TERRA_DN_NORMAL_MIN ? v3 ( p.nv.x / len, p.nv.y / len, p.nv.z / len ) : v3 ( 0.f, 0.f, 0.f );
     }
+    return p;
+}
+// The lane's pixel under 16 x 16 blocks laid over a w x h rectangle at (x, y) of a frame fb_w pixels wide: (lx, ly) in the rectangle, pix its index in the frame,
+// i its index in the rectangle (the filter's planes). !inside: the lane lies beyond the rectangle's edge and has nothing to do (pix and i are then no pixel's).
+// (Returned by value: filled through a reference, the variance-guided step took two more registers and measured 1 % slower.)
+struct DnLane { bool inside; uint32_t lx, ly; size_t pix, i; };
+TD DnLane dn_lane ( uint32_t fb_w, uint32_t x, uint32_t y, uint32_t w, uint32_t h ) {
+    DnLane l;
+    l.lx = blockIdx.x * 16u + threadIdx.x; l.ly = blockIdx.y * 16u + threadIdx.y;
+    l.inside = l.lx < w && l.ly < h;
+    l.pix = ( size_t ) ( y + l.ly ) * fb_w + ( x + l.lx ); l.i = ( size_t ) l.ly * w + l.lx;
+    return l;
+}
+// var of the pixel's mean luminance from the second word of its moments entry (mean, m2, batches, weight); negative: unknown
+TD float var_of ( const float4& m1 ) {
+    const int batches = __float_as_int ( m1.z ), weight = __float_as_int ( m1.w );
+    return batches >= 2 ? m1.y / ( ( float ) weight * ( float ) ( batches - 1 ) ) : -1.f;
+}
 TD V3 dn_demodulate ( V3 c, V3 a ) { return v3 ( c.x / dn_max ( a.x, TERRA_DN_ALBEDO_MIN ), c.y / dn_max ( a.y, TERRA_DN_ALBEDO_MIN ), c.z / dn_max ( a.z, TERRA_DN_ALBEDO_MIN ) ); }      // u = c / max(a, 0.01)
 TD float4 dn_valid4 ( V3 u ) { return make_float4 ( u.x, u.y, u.z, 1.f ); }
 TD float dn_kernel ( int d ) { const float kh[5] = { 1.f / 16.f, 1.f / 4.f, 3.f / 8.f, 1.f / 4.f, 1.f / 16.f }; return kh[d + 2]; }       // h(d), d in -2 .. 2

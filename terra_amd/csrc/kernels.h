@@ -26,24 +26,21 @@ void       terra_plan_fast_tree ( DevRenderParams& p );     // the plan of a fas
 hipError_t terra_launch_tiles ( bool pack, float* pixels, void* results, uint32_t fb_w, uint32_t x, uint32_t y, uint32_t w, uint32_t h,
                                 uint32_t tile, uint32_t rank, uint32_t world, float* packed, hipStream_t stream );
 
-// first-hit AOV pass and denoiser (aov_kernels.hip): p as fill_params made it, with the render's sample split set (split, split_log2, chunk_spp); aov = TerraAmdAovResult
+// first-hit AOV pass (aov_kernels.hip): p as fill_params made it, with the render's sample split set (split, split_log2, chunk_spp); aov = TerraAmdAovResult
 // per pixel, addressed like p.results (st_x / st_y / st_pitch)
 hipError_t terra_launch_aov ( DevRenderParams p, void* aov, hipStream_t stream );
-// results / aov / radiance / pixels indexed like a frame of fb_w pixels per row; only the rectangle is read or written; radiance or pixels may be nullptr
+
+// the a-trous denoiser and its variance-guided form (denoise_kernels.hip): results / aov / moments (TerraAmdMoments) / radiance / pixels indexed like a frame of fb_w
+// pixels per row; only the rectangle is read or written; radiance or pixels may be nullptr
 hipError_t terra_launch_denoise ( const void* results, const void* aov, uint32_t fb_w, uint32_t x, uint32_t y, uint32_t w, uint32_t h, int iterations,
                                   float exposure, int op, float gamma, float* radiance, float* pixels, hipStream_t stream );
-
-// the a-trous filter's first and last kernel on their own (aov_kernels.hip), for the variance-guided form: g0, g1, u are planes of w * h float4 over the rectangle
-hipError_t terra_launch_denoise_prepass ( const void* results, const void* aov, uint32_t fb_w, uint32_t x, uint32_t y, uint32_t w, uint32_t h, void* g0, void* g1, void* u, hipStream_t stream );
-hipError_t terra_launch_denoise_finish ( const void* results, const void* g1, const void* u, uint32_t fb_w, uint32_t x, uint32_t y, uint32_t w, uint32_t h, int iterations,
-                                         float exposure, int op, float gamma, float* radiance, float* pixels, hipStream_t stream );
-
-// second moments, tile error and the variance-guided denoiser (variance_kernels.hip): results / moments (TerraAmdMoments) / aov / radiance / pixels indexed like a frame
-// of fb_w pixels per row, only the rectangle is read or written; errors: one float per tile x tile tile of the rectangle, row-major
-hipError_t terra_launch_moments_accumulate ( const void* results, void* moments, uint32_t fb_w, uint32_t x, uint32_t y, uint32_t w, uint32_t h, hipStream_t stream );
-hipError_t terra_launch_tile_error ( const void* moments, uint32_t fb_w, uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint32_t tile, float* errors, hipStream_t stream );
 hipError_t terra_launch_denoise_variance ( const void* results, const void* aov, const void* moments, uint32_t fb_w, uint32_t x, uint32_t y, uint32_t w, uint32_t h, int iterations,
                                            float exposure, int op, float gamma, float* radiance, float* pixels, hipStream_t stream );
+
+// second moments and tile error (variance_kernels.hip): results / moments indexed like a frame of fb_w pixels per row, only the rectangle is read or written;
+// errors: one float per tile x tile tile of the rectangle, row-major
+hipError_t terra_launch_moments_accumulate ( const void* results, void* moments, uint32_t fb_w, uint32_t x, uint32_t y, uint32_t w, uint32_t h, hipStream_t stream );
+hipError_t terra_launch_tile_error ( const void* moments, uint32_t fb_w, uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint32_t tile, float* errors, hipStream_t stream );
 
 // temporal reprojection of a per-pixel history (temporal_kernels.hip; include/terra_amd.h "Temporal reprojection"): every buffer indexed like a frame of fb_w pixels
 // per row, only the rectangle is read or written; history_in, out_results, out_moments may be nullptr. cam / prev: the two cameras as fill_camera made them.

@@ -1598,7 +1598,46 @@ extern "C" int terra_amd_time_render_device ( const TerraCamera* cam, HTerraScen
     return 0;
 }
 
-// ---- AOV pass and denoiser (aov_kernels.hip) ----------------------------------------
+// ---- host side of the frame passes: one check, one staging helper ------------------------------------------------------------------
+// the scene can answer a call: committed since it last changed, and with a device replica
+static int scene_check ( const Scene* s ) {
+    if ( !s->committed ) return fail ( kTerraAmdErrNotCommitted, "terra_scene_commit has not run since the scene changed" );
+    if ( !s->device_ok ) return fail ( kTerraAmdErrNoDevice, "scene has no device replica: %s", s->commit_error.c_str() );
+    return 0;
+}
+// The one check of the frame passes (denoise, moments, tile error, variance denoise, reproject, adaptive): the scene can answer (nullptr: the pass takes none), the
+// rectangle lies inside a frame whose sides fit the kernels' 32-bit coordinates, 0 ... 8 iterations. `what` names the pass in the message.
+static int frame_check ( const Scene* s, const char* what, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t h, int iterations = 0 ) {
+    if ( s ) if ( int rc = scene_check ( s ) ) return rc;
+    if ( w == 0 || h == 0 || x + w > fb_w || y + h > fb_h || fb_w > 0xffffffffull || fb_h > 0xffffffffull ) return fail ( kTerraAmdErrBadArgument, "bad %s rectangle %zu,%zu %zux%zu in %zux%zu", what, x, y, w, h, fb_w, fb_h );
+    if ( iterations < 0 || iterations > 8 ) return fail ( kTerraAmdErrBadArgument, "%s iterations %d: 0 ... 8", what, iterations );
+    return 0;
+}
+// Host buffers on the device for the synchronous host forms: up to four, freed when the form returns, whichever way it returns. up / down copy `bytes` as they lie
+// (a whole frame, a list of rays); up_rect / down_rect copy the rectangle r of a host frame with `stride` bytes per pixel to and from a frame of its own, r.w pixels
+// per row. A null host pointer uploads zeros.
+struct FrameRect { size_t fb_w, x, y, w, h; };
+struct FrameCopy {
+    char* d[4] = { nullptr, nullptr, nullptr, nullptr };
+    ~FrameCopy() { for ( char* p : d ) if ( p ) ( void ) hipFree ( p ); }
+    hipError_t up ( int k, const void* host, size_t bytes ) {
+        hipError_t e = hipMalloc ( ( void** ) &d[k], bytes );
+        if ( e == hipSuccess ) e = host ? hipMemcpy ( d[k], host, bytes, hipMemcpyHostToDevice ) : hipMemset ( d[k], 0, bytes );
+        return e;
+    }
+    hipError_t down ( int k, void* host, size_t bytes ) const { return hipMemcpy ( host, d[k], bytes, hipMemcpyDeviceToHost ); }
+    hipError_t up_rect ( int k, const void* host, size_t stride, const FrameRect& r ) {
+        if ( !host ) return up ( k, nullptr, r.w * r.h * stride );
+        hipError_t e = hipMalloc ( ( void** ) &d[k], r.w * r.h * stride );
+        if ( e == hipSuccess ) e = hipMemcpy2D ( d[k], r.w * stride, ( const char* ) host + ( r.y * r.fb_w + r.x ) * stride, r.fb_w * stride, r.w * stride, r.h, hipMemcpyHostToDevice );
+        return e;
+    }
+    hipError_t down_rect ( int k, void* host, size_t stride, const FrameRect& r ) const {
+        return hipMemcpy2D ( ( char* ) host + ( r.y * r.fb_w + r.x ) * stride, r.fb_w * stride, d[k], r.w * stride, r.w * stride, r.h, hipMemcpyDeviceToHost );
+    }
+};
+
+// ---- AOV pass (aov_kernels.hip) ----------------------------------------
 static_assert ( sizeof ( TerraAmdAovResult ) == 48, "TerraAmdAovResult must be 48 bytes" );
 // p: the launch fill_params made for the render call this AOV call mirrors; the split is the one that call takes (launch_split), and the samples the AOV buffer
 // already holds key the streams as the framebuffer's do. Runs on the current device (the scene's primary one).
@@ -1613,39 +1652,40 @@ static int launch_aov ( Scene* s, DevRenderParams& p, void* d_aov, hipStream_t s
     if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "AOV launch: %s", hipGetErrorString ( e ) );
     return 0;
 }
-extern "C" int terra_amd_render_aov_device ( const TerraCamera* cam, HTerraScene h, void* d_aov, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t hgt, void* stream ) {
+// the device form with the buffer's addressing spelled out: d_aov holds rows of st_pitch pixels whose first is pixel (st_x, st_y) of the frame
+static int render_aov_device ( const TerraCamera* cam, HTerraScene h, void* d_aov, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t hgt, size_t st_x, size_t st_y, size_t st_pitch, void* stream ) {
     Scene* s = S ( h );
     const Scene::Replica& r = primary ( s );
     DevRenderParams p;
     if ( int rc = fill_params ( s, r, cam, fb_w, fb_h, x, y, w, hgt, 64, 0, 1, p ) ) return rc;
     if ( !d_aov ) return fail ( kTerraAmdErrBadArgument, "null AOV buffer" );
     HIP_TRY ( hipSetDevice ( r.device ), kTerraAmdErrNoDevice );
+    p.st_x = ( uint32_t ) st_x; p.st_y = ( uint32_t ) st_y; p.st_pitch = ( uint32_t ) st_pitch;
     return launch_aov ( s, p, d_aov, ( hipStream_t ) stream );
+}
+extern "C" int terra_amd_render_aov_device ( const TerraCamera* cam, HTerraScene h, void* d_aov, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t hgt, void* stream ) {
+    return render_aov_device ( cam, h, d_aov, fb_w, fb_h, x, y, w, hgt, 0, 0, fb_w, stream );
 }
 extern "C" int terra_amd_render_aov ( const TerraCamera* cam, HTerraScene h, TerraAmdAovResult* aov, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t hgt ) {
     Scene* s = S ( h );
-    const Scene::Replica& r = primary ( s );
-    DevRenderParams p;
-    if ( int rc = fill_params ( s, r, cam, fb_w, fb_h, x, y, w, hgt, 64, 0, 1, p ) ) return rc;
+    DevRenderParams p;          // (for the check alone, before anything is staged: the device form fills its own)
+    if ( int rc = fill_params ( s, primary ( s ), cam, fb_w, fb_h, x, y, w, hgt, 64, 0, 1, p ) ) return rc;
     if ( !aov ) return fail ( kTerraAmdErrBadArgument, "null AOV buffer" );
-    HIP_TRY ( hipSetDevice ( r.device ), kTerraAmdErrNoDevice );
-    p.st_x = ( uint32_t ) x; p.st_y = ( uint32_t ) y; p.st_pitch = ( uint32_t ) w;      // the rectangle only, rows of w pixels (as render_host stages it)
-    void* d = nullptr;
-    HIP_TRY ( hipMalloc ( &d, w * hgt * sizeof ( TerraAmdAovResult ) ), kTerraAmdErrNoDevice );
-    const size_t row = w * sizeof ( TerraAmdAovResult ), pitch = fb_w * sizeof ( TerraAmdAovResult );
-    TerraAmdAovResult* host = aov + y * fb_w + x;
-    hipError_t e = hipMemcpy2D ( d, row, host, pitch, row, hgt, hipMemcpyHostToDevice );
-    int rc = e == hipSuccess ? launch_aov ( s, p, d, nullptr ) : fail ( kTerraAmdErrLaunch, "AOV upload: %s", hipGetErrorString ( e ) );
-    if ( !rc ) { e = hipMemcpy2D ( host, pitch, d, row, row, hgt, hipMemcpyDeviceToHost ); if ( e != hipSuccess ) rc = fail ( kTerraAmdErrLaunch, "AOV download: %s", hipGetErrorString ( e ) ); }
-    ( void ) hipFree ( d );
-    return rc;
+    HIP_TRY ( hipSetDevice ( primary ( s ).device ), kTerraAmdErrNoDevice );
+    const FrameRect rect = { fb_w, x, y, w, hgt };          // the rectangle only, rows of w pixels (as render_host stages it)
+    FrameCopy c;
+    hipError_t e = c.up_rect ( 0, aov, sizeof ( TerraAmdAovResult ), rect );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "AOV upload: %s", hipGetErrorString ( e ) );
+    if ( int rc = render_aov_device ( cam, h, c.d[0], fb_w, fb_h, x, y, w, hgt, x, y, w, nullptr ) ) return rc;
+    e = c.down_rect ( 0, aov, sizeof ( TerraAmdAovResult ), rect );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "AOV download: %s", hipGetErrorString ( e ) );
+    return 0;
 }
 // ---- ray queries (query_kernels.hip) ---------------------------------------------------
 static_assert ( sizeof ( TerraAmdRay ) == 32 && sizeof ( TerraAmdHit ) == 32, "TerraAmdRay and TerraAmdHit must be 32 bytes" );
 // the one check of the four entry points: the scene can answer, the buffers are there, n fits the kernel's 32-bit ray index
 static int query_check ( Scene* s, const void* rays, size_t n, const void* out, const char* what ) {
-    if ( !s->committed ) return fail ( kTerraAmdErrNotCommitted, "terra_scene_commit has not run since the scene changed" );
-    if ( !s->device_ok ) return fail ( kTerraAmdErrNoDevice, "scene has no device replica: %s", s->commit_error.c_str() );
+    if ( int rc = scene_check ( s ) ) return rc;
     if ( n > ( size_t ) 0x7fffffff ) return fail ( kTerraAmdErrBadArgument, "%s: %zu rays in one call, at most 2^31 - 1", what, n );
     if ( n > 0 && ( !rays || !out ) ) return fail ( kTerraAmdErrBadArgument, "%s: null ray or result buffer", what );
     return 0;
@@ -1694,35 +1734,29 @@ static int query_host ( HTerraScene h, const TerraAmdRay* rays, size_t n, void* 
     if ( int rc = query_check ( s, rays, n, out, what ) ) return rc;
     if ( n == 0 ) return 0;
     HIP_TRY ( hipSetDevice ( primary ( s ).device ), kTerraAmdErrNoDevice );
-    const TreeChoice& c = s->tree;
-    const float limit = ( c.reach || c.reach_cull ) ? c.reach_limit : TERRA_CULL_MAX_COORD;
+    const TreeChoice& tc = s->tree;
+    const float limit = ( tc.reach || tc.reach_cull ) ? tc.reach_limit : TERRA_CULL_MAX_COORD;
     bool shortcut = true;
     for ( size_t i = 0; i < n && shortcut; ++i ) shortcut = fabsf ( rays[i].origin[0] ) <= limit && fabsf ( rays[i].origin[1] ) <= limit && fabsf ( rays[i].origin[2] ) <= limit;
-    char* d = nullptr;
-    HIP_TRY ( hipMalloc ( ( void** ) &d, n * ( sizeof ( TerraAmdRay ) + out_stride ) ), kTerraAmdErrNoDevice );
-    char* d_out = d + n * sizeof ( TerraAmdRay );
-    hipError_t e = hipMemcpy ( d, rays, n * sizeof ( TerraAmdRay ), hipMemcpyHostToDevice );
-    int rc = e == hipSuccess ? launch_query ( s, d, n, d_out, anyhit, shortcut, nullptr ) : fail ( kTerraAmdErrLaunch, "%s upload: %s", what, hipGetErrorString ( e ) );
-    if ( !rc ) { e = hipMemcpy ( out, d_out, n * out_stride, hipMemcpyDeviceToHost ); if ( e != hipSuccess ) rc = fail ( kTerraAmdErrLaunch, "%s download: %s", what, hipGetErrorString ( e ) ); }
-    ( void ) hipFree ( d );
-    return rc;
+    FrameCopy c;
+    hipError_t e = c.up ( 0, rays, n * sizeof ( TerraAmdRay ) );
+    if ( e == hipSuccess ) e = c.up ( 1, nullptr, n * out_stride );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "%s upload: %s", what, hipGetErrorString ( e ) );
+    if ( int rc = launch_query ( s, c.d[0], n, c.d[1], anyhit, shortcut, nullptr ) ) return rc;
+    e = c.down ( 1, out, n * out_stride );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "%s download: %s", what, hipGetErrorString ( e ) );
+    return 0;
 }
 extern "C" int terra_amd_intersect_device ( HTerraScene h, const void* d_rays, size_t n, void* d_hits, void* stream ) { return query_device ( h, d_rays, n, d_hits, false, stream, "terra_amd_intersect_device" ); }
 extern "C" int terra_amd_occluded_device ( HTerraScene h, const void* d_rays, size_t n, void* d_occluded, void* stream ) { return query_device ( h, d_rays, n, d_occluded, true, stream, "terra_amd_occluded_device" ); }
 extern "C" int terra_amd_intersect ( HTerraScene h, const TerraAmdRay* rays, size_t n, TerraAmdHit* hits ) { return query_host ( h, rays, n, hits, sizeof ( TerraAmdHit ), false, "terra_amd_intersect" ); }
 extern "C" int terra_amd_occluded ( HTerraScene h, const TerraAmdRay* rays, size_t n, uint32_t* occluded ) { return query_host ( h, rays, n, occluded, sizeof ( uint32_t ), true, "terra_amd_occluded" ); }
 
-static int denoise_check ( Scene* s, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t h, int iterations, const char* what = "denoise" ) {
-    if ( !s->committed ) return fail ( kTerraAmdErrNotCommitted, "terra_scene_commit has not run since the scene changed" );
-    if ( !s->device_ok ) return fail ( kTerraAmdErrNoDevice, "scene has no device replica: %s", s->commit_error.c_str() );
-    if ( w == 0 || h == 0 || x + w > fb_w || y + h > fb_h ) return fail ( kTerraAmdErrBadArgument, "bad %s rectangle %zu,%zu %zux%zu in %zux%zu", what, x, y, w, h, fb_w, fb_h );
-    if ( iterations < 0 || iterations > 8 ) return fail ( kTerraAmdErrBadArgument, "denoise iterations %d: 0 ... 8", iterations );
-    return 0;
-}
+// ---- denoiser (denoise_kernels.hip) ----------------------------------------------------
 extern "C" int terra_amd_denoise_device ( HTerraScene h, const void* d_results, const void* d_aov, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t hgt, int iterations,
                                           void* d_radiance, void* d_pixels, void* stream ) {
     Scene* s = S ( h );
-    if ( int rc = denoise_check ( s, fb_w, fb_h, x, y, w, hgt, iterations ) ) return rc;
+    if ( int rc = frame_check ( s, "denoise", fb_w, fb_h, x, y, w, hgt, iterations ) ) return rc;
     if ( !d_results || !d_aov ) return fail ( kTerraAmdErrBadArgument, "null framebuffer or AOV buffer" );
     HIP_TRY ( hipSetDevice ( primary ( s ).device ), kTerraAmdErrNoDevice );
     const hipError_t e = terra_launch_denoise ( d_results, d_aov, ( uint32_t ) fb_w, ( uint32_t ) x, ( uint32_t ) y, ( uint32_t ) w, ( uint32_t ) hgt, iterations, s->opts.manual_exposure,
@@ -1734,51 +1768,34 @@ extern "C" int terra_amd_denoise ( HTerraScene h, const TerraFramebuffer* fb, co
                                    TerraFloat3* radiance, TerraFloat3* pixels ) {
     Scene* s = S ( h );
     if ( !fb || !fb->results || !aov ) return fail ( kTerraAmdErrBadArgument, "null framebuffer or AOV buffer" );
-    if ( int rc = denoise_check ( s, fb->width, fb->height, x, y, w, hgt, iterations ) ) return rc;
+    if ( int rc = frame_check ( s, "denoise", fb->width, fb->height, x, y, w, hgt, iterations ) ) return rc;
     if ( !radiance && !pixels ) return 0;
     HIP_TRY ( hipSetDevice ( primary ( s ).device ), kTerraAmdErrNoDevice );
     // the rectangle only, as a frame of w x hgt (the filter does not depend on where the rectangle lies)
-    const size_t n = w * hgt;
-    char* d = nullptr;
-    HIP_TRY ( hipMalloc ( ( void** ) &d, n * ( 16 + 48 + 12 + 12 ) ), kTerraAmdErrNoDevice );
-    char* d_res = d; char* d_aov = d + n * 16; float* d_rad = ( float* ) ( d + n * 64 ); float* d_pix = ( float* ) ( d + n * 76 );
-    hipError_t e = hipMemcpy2D ( d_res, w * 16, ( const char* ) fb->results + ( y * fb->width + x ) * 16, fb->width * 16, w * 16, hgt, hipMemcpyHostToDevice );
-    if ( e == hipSuccess ) e = hipMemcpy2D ( d_aov, w * 48, ( const char* ) ( aov + y * fb->width + x ), fb->width * 48, w * 48, hgt, hipMemcpyHostToDevice );
-    if ( e == hipSuccess ) e = terra_launch_denoise ( d_res, d_aov, ( uint32_t ) w, 0, 0, ( uint32_t ) w, ( uint32_t ) hgt, iterations, s->opts.manual_exposure, ( int ) s->opts.tonemapping_operator,
-                                                      s->opts.gamma, radiance ? d_rad : nullptr, pixels ? d_pix : nullptr, nullptr );
-    if ( e == hipSuccess && radiance ) e = hipMemcpy2D ( radiance + y * fb->width + x, fb->width * 12, d_rad, w * 12, w * 12, hgt, hipMemcpyDeviceToHost );
-    if ( e == hipSuccess && pixels ) e = hipMemcpy2D ( pixels + y * fb->width + x, fb->width * 12, d_pix, w * 12, w * 12, hgt, hipMemcpyDeviceToHost );
-    ( void ) hipFree ( d );
-    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "denoise: %s", hipGetErrorString ( e ) );
+    const FrameRect rect = { fb->width, x, y, w, hgt };
+    FrameCopy c, o;
+    hipError_t e = c.up_rect ( 0, fb->results, 16, rect );
+    if ( e == hipSuccess ) e = c.up_rect ( 1, aov, 48, rect );
+    if ( e == hipSuccess && radiance ) e = o.up_rect ( 0, nullptr, 12, rect );
+    if ( e == hipSuccess && pixels ) e = o.up_rect ( 1, nullptr, 12, rect );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "denoise upload: %s", hipGetErrorString ( e ) );
+    if ( int rc = terra_amd_denoise_device ( h, c.d[0], c.d[1], w, hgt, 0, 0, w, hgt, iterations, o.d[0], o.d[1], nullptr ) ) return rc;
+    if ( radiance ) e = o.down_rect ( 0, radiance, 12, rect );
+    if ( e == hipSuccess && pixels ) e = o.down_rect ( 1, pixels, 12, rect );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "denoise download: %s", hipGetErrorString ( e ) );
     return 0;
 }
 
-// ---- moments, tile error, variance-guided denoiser, adaptive tiles (variance_kernels.hip) ----------------------------------------
+// ---- moments, tile error, variance-guided denoiser, adaptive tiles (variance_kernels.hip, denoise_kernels.hip) ----------------------------------------
 static_assert ( sizeof ( TerraAmdMoments ) == 32, "TerraAmdMoments must be 32 bytes" );
-static int rect_check ( const char* what, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t h ) {
-    if ( w == 0 || h == 0 || x + w > fb_w || y + h > fb_h || fb_w > 0xffffffffull || fb_h > 0xffffffffull ) return fail ( kTerraAmdErrBadArgument, "bad %s rectangle %zu,%zu %zux%zu in %zux%zu", what, x, y, w, h, fb_w, fb_h );
-    return 0;
-}
 static int tile_size_check ( size_t& tile ) {
     if ( tile == 0 ) tile = 128;
     if ( tile % 16 || tile > 32768 ) return fail ( kTerraAmdErrBadArgument, "tile size %zu: 0 (128) or a multiple of 16 up to 32768", tile );
     return 0;
 }
-// a frame's worth of host buffers on the device for the synchronous host forms: up to four buffers of `stride[k]` bytes per pixel
-struct FrameCopy {
-    char* d[4] = { nullptr, nullptr, nullptr, nullptr };
-    ~FrameCopy() { for ( char* p : d ) if ( p ) ( void ) hipFree ( p ); }
-    hipError_t up ( int k, const void* host, size_t bytes ) {
-        hipError_t e = hipMalloc ( ( void** ) &d[k], bytes );
-        if ( e == hipSuccess ) e = host ? hipMemcpy ( d[k], host, bytes, hipMemcpyHostToDevice ) : hipMemset ( d[k], 0, bytes );
-        return e;
-    }
-    hipError_t down ( int k, void* host, size_t bytes ) const { return hipMemcpy ( host, d[k], bytes, hipMemcpyDeviceToHost ); }
-};
 extern "C" int terra_amd_accumulate_moments_device ( HTerraScene h, const void* d_results, void* d_moments, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t hgt, void* stream ) {
     Scene* s = S ( h );
-    if ( int rc = denoise_check ( s, fb_w, fb_h, x, y, w, hgt, 0 ) ) return rc;
-    if ( int rc = rect_check ( "moments", fb_w, fb_h, x, y, w, hgt ) ) return rc;
+    if ( int rc = frame_check ( s, "moments", fb_w, fb_h, x, y, w, hgt ) ) return rc;
     if ( !d_results || !d_moments ) return fail ( kTerraAmdErrBadArgument, "null framebuffer or moments buffer" );
     HIP_TRY ( hipSetDevice ( primary ( s ).device ), kTerraAmdErrNoDevice );
     const hipError_t e = terra_launch_moments_accumulate ( d_results, d_moments, ( uint32_t ) fb_w, ( uint32_t ) x, ( uint32_t ) y, ( uint32_t ) w, ( uint32_t ) hgt, ( hipStream_t ) stream );
@@ -1788,7 +1805,7 @@ extern "C" int terra_amd_accumulate_moments_device ( HTerraScene h, const void* 
 extern "C" int terra_amd_accumulate_moments ( HTerraScene h, const TerraFramebuffer* fb, TerraAmdMoments* moments, size_t x, size_t y, size_t w, size_t hgt ) {
     Scene* s = S ( h );
     if ( !fb || !fb->results || !moments ) return fail ( kTerraAmdErrBadArgument, "null framebuffer or moments buffer" );
-    if ( int rc = denoise_check ( s, fb->width, fb->height, x, y, w, hgt, 0 ) ) return rc;
+    if ( int rc = frame_check ( s, "moments", fb->width, fb->height, x, y, w, hgt ) ) return rc;
     HIP_TRY ( hipSetDevice ( primary ( s ).device ), kTerraAmdErrNoDevice );
     const size_t n = fb->width * fb->height;
     FrameCopy c;
@@ -1801,7 +1818,7 @@ extern "C" int terra_amd_accumulate_moments ( HTerraScene h, const TerraFramebuf
     return 0;
 }
 extern "C" int terra_amd_tile_error_device ( const void* d_results, const void* d_moments, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t hgt, size_t tile, void* d_errors, void* stream ) {
-    if ( int rc = rect_check ( "tile error", fb_w, fb_h, x, y, w, hgt ) ) return rc;
+    if ( int rc = frame_check ( nullptr, "tile error", fb_w, fb_h, x, y, w, hgt ) ) return rc;
     if ( int rc = tile_size_check ( tile ) ) return rc;
     if ( !d_results || !d_moments || !d_errors ) return fail ( kTerraAmdErrBadArgument, "null framebuffer, moments or error buffer" );
     const hipError_t e = terra_launch_tile_error ( d_moments, ( uint32_t ) fb_w, ( uint32_t ) x, ( uint32_t ) y, ( uint32_t ) w, ( uint32_t ) hgt, ( uint32_t ) tile, ( float* ) d_errors, ( hipStream_t ) stream );
@@ -1810,7 +1827,7 @@ extern "C" int terra_amd_tile_error_device ( const void* d_results, const void* 
 }
 extern "C" int terra_amd_tile_error ( const TerraFramebuffer* fb, const TerraAmdMoments* moments, size_t x, size_t y, size_t w, size_t hgt, size_t tile, float* errors ) {
     if ( !fb || !fb->results || !moments || !errors ) return fail ( kTerraAmdErrBadArgument, "null framebuffer, moments or error buffer" );
-    if ( int rc = rect_check ( "tile error", fb->width, fb->height, x, y, w, hgt ) ) return rc;
+    if ( int rc = frame_check ( nullptr, "tile error", fb->width, fb->height, x, y, w, hgt ) ) return rc;
     if ( int rc = tile_size_check ( tile ) ) return rc;
     const size_t n = fb->width * fb->height, tiles = ( ( w + tile - 1 ) / tile ) * ( ( hgt + tile - 1 ) / tile );
     FrameCopy c;
@@ -1825,7 +1842,7 @@ extern "C" int terra_amd_tile_error ( const TerraFramebuffer* fb, const TerraAmd
 extern "C" int terra_amd_denoise_variance_device ( HTerraScene h, const void* d_results, const void* d_aov, const void* d_moments, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t hgt,
                                                    int iterations, void* d_radiance, void* d_pixels, void* stream ) {
     Scene* s = S ( h );
-    if ( int rc = denoise_check ( s, fb_w, fb_h, x, y, w, hgt, iterations ) ) return rc;
+    if ( int rc = frame_check ( s, "variance denoise", fb_w, fb_h, x, y, w, hgt, iterations ) ) return rc;
     if ( !d_results || !d_aov || !d_moments ) return fail ( kTerraAmdErrBadArgument, "null framebuffer, AOV or moments buffer" );
     HIP_TRY ( hipSetDevice ( primary ( s ).device ), kTerraAmdErrNoDevice );
     const hipError_t e = terra_launch_denoise_variance ( d_results, d_aov, d_moments, ( uint32_t ) fb_w, ( uint32_t ) x, ( uint32_t ) y, ( uint32_t ) w, ( uint32_t ) hgt, iterations, s->opts.manual_exposure,
@@ -1837,7 +1854,7 @@ extern "C" int terra_amd_denoise_variance ( HTerraScene h, const TerraFramebuffe
                                             int iterations, TerraFloat3* radiance, TerraFloat3* pixels ) {
     Scene* s = S ( h );
     if ( !fb || !fb->results || !aov || !moments ) return fail ( kTerraAmdErrBadArgument, "null framebuffer, AOV or moments buffer" );
-    if ( int rc = denoise_check ( s, fb->width, fb->height, x, y, w, hgt, iterations ) ) return rc;
+    if ( int rc = frame_check ( s, "variance denoise", fb->width, fb->height, x, y, w, hgt, iterations ) ) return rc;
     if ( !radiance && !pixels ) return 0;
     HIP_TRY ( hipSetDevice ( primary ( s ).device ), kTerraAmdErrNoDevice );
     const size_t n = fb->width * fb->height;
@@ -1860,7 +1877,7 @@ extern "C" int terra_amd_reproject_device ( HTerraScene h, const TerraCamera* ca
                                             void* d_history_out, void* d_out_results, void* d_out_moments, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t hgt,
                                             const TerraAmdTemporalOptions* options, void* stream ) {
     Scene* s = S ( h );
-    if ( int rc = denoise_check ( s, fb_w, fb_h, x, y, w, hgt, 0, "reproject" ) ) return rc;
+    if ( int rc = frame_check ( s, "reproject", fb_w, fb_h, x, y, w, hgt ) ) return rc;
     if ( fb_w > ( 1u << 24 ) || fb_h > ( 1u << 24 ) ) return fail ( kTerraAmdErrBadArgument, "reproject: frame %zux%zu: at most 2^24 pixels a side (pixel coordinates are floats)", fb_w, fb_h );
     if ( !cam || !prev || !d_results || !d_aov || !d_history_out ) return fail ( kTerraAmdErrBadArgument, "null camera, framebuffer, AOV or history buffer" );
     if ( d_history_in == d_history_out ) return fail ( kTerraAmdErrBadArgument, "reproject: history_in and history_out are the same buffer (taps read neighbours: the call cannot run in place)" );
@@ -1888,7 +1905,7 @@ extern "C" int terra_amd_reproject ( HTerraScene h, const TerraCamera* cam, cons
     Scene* s = S ( h );
     if ( !fb || !fb->results || !aov || !history_out ) return fail ( kTerraAmdErrBadArgument, "null framebuffer, AOV or history buffer" );
     if ( history_in == history_out ) return fail ( kTerraAmdErrBadArgument, "reproject: history_in and history_out are the same buffer (taps read neighbours: the call cannot run in place)" );
-    if ( int rc = denoise_check ( s, fb->width, fb->height, x, y, w, hgt, 0, "reproject" ) ) return rc;
+    if ( int rc = frame_check ( s, "reproject", fb->width, fb->height, x, y, w, hgt ) ) return rc;
     HIP_TRY ( hipSetDevice ( primary ( s ).device ), kTerraAmdErrNoDevice );
     const size_t n = fb->width * fb->height;
     FrameCopy c, o;             // (the outputs go up too: what lies outside the rectangle comes back as it was)
@@ -1909,8 +1926,7 @@ extern "C" int terra_amd_reproject ( HTerraScene h, const TerraCamera* cam, cons
 extern "C" int terra_amd_render_adaptive_device ( const TerraCamera* cam, HTerraScene h, void* d_pixels, void* d_results, void* d_moments, void* d_aov, size_t fb_w, size_t fb_h,
                                                   size_t x, size_t y, size_t w, size_t hgt, const TerraAmdAdaptiveOptions* options, TerraAmdAdaptiveReport* report, void* stream ) {
     Scene* s = S ( h );
-    if ( int rc = denoise_check ( s, fb_w, fb_h, x, y, w, hgt, 0 ) ) return rc;
-    if ( int rc = rect_check ( "adaptive", fb_w, fb_h, x, y, w, hgt ) ) return rc;
+    if ( int rc = frame_check ( s, "adaptive", fb_w, fb_h, x, y, w, hgt ) ) return rc;
     if ( !cam || !d_pixels || !d_results || !d_moments ) return fail ( kTerraAmdErrBadArgument, "null camera, framebuffer or moments buffer" );
     size_t tile = options ? options->tile_size : 0;
     if ( int rc = tile_size_check ( tile ) ) return rc;
@@ -1959,7 +1975,7 @@ extern "C" int terra_amd_render_adaptive ( const TerraCamera* cam, HTerraScene h
                                            const TerraAmdAdaptiveOptions* options, TerraAmdAdaptiveReport* report ) {
     Scene* s = S ( h );
     if ( !fb || !fb->results || !fb->pixels || !moments ) return fail ( kTerraAmdErrBadArgument, "null framebuffer or moments buffer" );
-    if ( int rc = denoise_check ( s, fb->width, fb->height, x, y, w, hgt, 0 ) ) return rc;
+    if ( int rc = frame_check ( s, "adaptive", fb->width, fb->height, x, y, w, hgt ) ) return rc;
     HIP_TRY ( hipSetDevice ( primary ( s ).device ), kTerraAmdErrNoDevice );
     const size_t n = fb->width * fb->height;
     FrameCopy c;

@@ -53,23 +53,23 @@ __global__ __launch_bounds__ ( 256 ) void terra_temporal_reproject ( DevTemporal
     if ( lx >= p.w || ly >= p.h ) return;
     const uint32_t px = p.x + lx, py = p.y + ly;
     const size_t pix = ( size_t ) py * p.fb_w + px;
-    DN_PIXEL_INPUTS ( results, aov, pix )               // declares res, samples, n, c, finite, a0, a1, a, nv, z (and an inner len): the "Denoiser" section's, from denoise_device.h
-    const V3 A = v3 ( dn_max ( a.x, TERRA_DN_ALBEDO_MIN ), dn_max ( a.y, TERRA_DN_ALBEDO_MIN ), dn_max ( a.z, TERRA_DN_ALBEDO_MIN ) );
-    const V3 uc = finite ? dn_demodulate ( c, a ) : v3 ( 0.f, 0.f, 0.f );
+    const DnPixel in = dn_pixel ( results, aov, pix );          // res, samples, n, c, finite, a0, a1, a, nv, z: the "Denoiser" section's, from denoise_device.h
+    const V3 A = v3 ( dn_max ( in.a.x, TERRA_DN_ALBEDO_MIN ), dn_max ( in.a.y, TERRA_DN_ALBEDO_MIN ), dn_max ( in.a.z, TERRA_DN_ALBEDO_MIN ) );
+    const V3 uc = in.finite ? dn_demodulate ( in.c, in.a ) : v3 ( 0.f, 0.f, 0.f );
     const float lc = dn_lum ( uc.x, uc.y, uc.z );
-    const bool n_zero = nv.x == 0.f && nv.y == 0.f && nv.z == 0.f;
+    const bool n_zero = in.nv.x == 0.f && in.nv.y == 0.f && in.nv.z == 0.f;
 
     // ---- the history at the place this pixel's surface had under the previous camera ------------------------------------------------------------------
     bool have = false;
     V3 uh = v3 ( 0.f, 0.f, 0.f );
     float m1h = 0.f, m2h = 0.f, nh = 0.f;
-    if ( hin && a0.w > 0.f ) {
+    if ( hin && in.a0.w > 0.f ) {
         DevRenderParams rp;                 // the render's own camera function (trace_geometry.h) at the pixel centre: only these fields are read
         rp.jitter = 0.f; rp.fb_w = p.fb_w; rp.fb_h = p.fb_h; rp.aspect = p.aspect; rp.tan_half_fov = p.tan_half_fov;
         #pragma unroll
         for ( int k = 0; k < 9; ++k ) rp.cam_rot[k] = p.cam_rot[k];
         const V3 D = camera_sample ( rp, px, py, 0.f, 0.f );
-        const V3 P = v3 ( p.cam_pos[0] + D.x * z, p.cam_pos[1] + D.y * z, p.cam_pos[2] + D.z * z );
+        const V3 P = v3 ( p.cam_pos[0] + D.x * in.z, p.cam_pos[1] + D.y * in.z, p.cam_pos[2] + D.z * in.z );
         const V3 v = v3 ( P.x - p.prev_pos[0], P.y - p.prev_pos[1], P.z - p.prev_pos[2] );
         const float xc = p.prev_rot[0] * v.x + p.prev_rot[3] * v.y + p.prev_rot[6] * v.z;
         const float yc = p.prev_rot[1] * v.x + p.prev_rot[4] * v.y + p.prev_rot[7] * v.z;
@@ -82,15 +82,15 @@ __global__ __launch_bounds__ ( 256 ) void terra_temporal_reproject ( DevTemporal
                 const float rx = floorf ( fx + 0.5f ), ry = floorf ( fy + 0.5f );
                 if ( fabsf ( fx - rx ) <= TERRA_TMP_SNAP && fabsf ( fy - ry ) <= TERRA_TMP_SNAP ) {
                     float4 h0, h2;
-                    if ( tap_load ( p, hin, ( int ) rx, ( int ) ry, d, nv, n_zero, h0, h2 ) ) { have = true; uh = v3 ( h0.x, h0.y, h0.z ); nh = h0.w; m1h = h2.x; m2h = h2.y; }
+                    if ( tap_load ( p, hin, ( int ) rx, ( int ) ry, d, in.nv, n_zero, h0, h2 ) ) { have = true; uh = v3 ( h0.x, h0.y, h0.z ); nh = h0.w; m1h = h2.x; m2h = h2.y; }
                 } else {
                     const float x0 = floorf ( fx ), y0 = floorf ( fy ), tx = fx - x0, ty = fy - y0;
                     const int ix = ( int ) x0, iy = ( int ) y0;
                     TapSum s; s.w = 0.f; s.x = 0.f; s.y = 0.f; s.z = 0.f; s.m1 = 0.f; s.m2 = 0.f; s.len = INFINITY;
-                    tap_add ( p, hin, ix, iy, ( 1.f - tx ) * ( 1.f - ty ), d, nv, n_zero, s );
-                    tap_add ( p, hin, ix + 1, iy, tx * ( 1.f - ty ), d, nv, n_zero, s );
-                    tap_add ( p, hin, ix, iy + 1, ( 1.f - tx ) * ty, d, nv, n_zero, s );
-                    tap_add ( p, hin, ix + 1, iy + 1, tx * ty, d, nv, n_zero, s );
+                    tap_add ( p, hin, ix, iy, ( 1.f - tx ) * ( 1.f - ty ), d, in.nv, n_zero, s );
+                    tap_add ( p, hin, ix + 1, iy, tx * ( 1.f - ty ), d, in.nv, n_zero, s );
+                    tap_add ( p, hin, ix, iy + 1, ( 1.f - tx ) * ty, d, in.nv, n_zero, s );
+                    tap_add ( p, hin, ix + 1, iy + 1, tx * ty, d, in.nv, n_zero, s );
                     if ( s.w >= TERRA_TMP_MIN_WEIGHT ) { have = true; uh = v3 ( s.x / s.w, s.y / s.w, s.z / s.w ); m1h = s.m1 / s.w; m2h = s.m2 / s.w; nh = s.len; }
                 }
             }
@@ -105,23 +105,23 @@ __global__ __launch_bounds__ ( 256 ) void terra_temporal_reproject ( DevTemporal
     float m1n = 0.f, m2n = 0.f, len = 0.f, ap = 1.f;
     if ( have ) {
         ap = dn_max ( p.alpha, 1.f / ( nh + 1.f ) );
-        if ( finite ) {
+        if ( in.finite ) {
             un = v3 ( uh.x + ap * ( uc.x - uh.x ), uh.y + ap * ( uc.y - uh.y ), uh.z + ap * ( uc.z - uh.z ) );
             m1n = m1h + ap * ( lc - m1h ); m2n = m2h + ap * ( lc * lc - m2h );
             len = nh + 1.f < p.max_length ? nh + 1.f : p.max_length;
         } else { un = uh; m1n = m1h; m2n = m2h; len = nh; }
-    } else if ( finite ) { un = uc; m1n = lc; m2n = lc * lc; len = 1.f; }
+    } else if ( in.finite ) { un = uc; m1n = lc; m2n = lc * lc; len = 1.f; }
     hout[3 * pix] = make_float4 ( un.x, un.y, un.z, len );
-    hout[3 * pix + 1] = make_float4 ( nv.x, nv.y, nv.z, z );
+    hout[3 * pix + 1] = make_float4 ( in.nv.x, in.nv.y, in.nv.z, in.z );
     hout[3 * pix + 2] = make_float4 ( m1n, m2n, 0.f, 0.f );
 
     // ---- the blended frame as a framebuffer and a moments buffer for the denoisers ----------------------------------------------------------------------
     if ( !out_results && !out_moments ) return;
-    float4 o = res;
+    float4 o = in.res;
     float4 m1 = make_float4 ( 0.f, 0.f, __int_as_float ( 0 ), __int_as_float ( 0 ) );
     if ( len > 0.f ) {
         const V3 cn = v3 ( un.x * A.x, un.y * A.y, un.z * A.z );
-        o = make_float4 ( cn.x * n, cn.y * n, cn.z * n, res.w );
+        o = make_float4 ( cn.x * in.n, cn.y * in.n, cn.z * in.n, in.res.w );
         const float lu = dn_lum ( un.x, un.y, un.z );
         if ( len >= 2.f && lu > 0.f ) {
             const float r = dn_max ( dn_lum ( cn.x, cn.y, cn.z ), TERRA_TMP_LUM_MIN ) / lu;

@@ -267,6 +267,24 @@ def test_no_leakage_across_a_normal_edge_and_outside_the_rectangle(L, plain_scen
     close(g0[4:40, 8:48], want)
 
 
+def test_host_form_on_a_rectangle_gives_the_device_form_s_bits_and_writes_nothing_outside(L, plain_scene):
+    """terra_amd_denoise stages the rectangle as a frame of its own. (5, 3, 40, 30) of 64 x 48 is no multiple of the 16 x 16 block, so the edge blocks are partial, and
+    with K = 3 the taps of step 4 cross the rectangle's edge."""
+    from terra_amd import runtime
+    res, aov = synthetic(64, 48, 17)
+    x, y, w, h = rect = (5, 3, 40, 30)
+    rad, pix = device_denoise(L, plain_scene, res, aov, 3, rect=rect)
+    hfb = api.Framebuffer(L, 64, 48)
+    np.copyto(hfb.results, res)
+    hr, hp = np.full((48, 64, 3), -7.0, F), np.full((48, 64, 3), -7.0, F)
+    runtime.check(L.denoise(plain_scene, C.byref(hfb.fb), aov.ctypes.data, x, y, w, h, 3, hr.ctypes.data, hp.ctypes.data), "terra_amd_denoise")
+    inside = np.zeros((48, 64), bool); inside[y:y + h, x:x + w] = True
+    assert np.all(rad[inside] != F(-7.0)) and (rad[inside] > 0).any()
+    assert np.array_equal(hr[inside].view(np.uint32), rad[inside].view(np.uint32)) and np.array_equal(hp[inside].view(np.uint32), pix[inside].view(np.uint32))
+    assert np.all(hr[~inside] == F(-7.0)) and np.all(hp[~inside] == F(-7.0))
+    hfb.destroy()
+
+
 def test_quality_cornell_direct_8spp(L):
     """Cornell 128 x 128, Direct, 8 spp with its AOVs against 4096 spp at another frame seed. Measured, not the issue's first guess (denoised RMSE
     <= 0.5 x noisy): 90 % of the 8-spp frame's squared error sits in 1 % of its pixels -- the emitter's edge, whose guides (albedo 0.78 against the

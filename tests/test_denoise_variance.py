@@ -277,6 +277,33 @@ def test_no_leakage_across_a_normal_edge_and_outside_the_rectangle(L, plain_scen
     close(g0[4:40, 8:48], restate_variance(res[4:40, 8:48], aov[4:40, 8:48], mom[4:40, 8:48], 4))
 
 
+@pytest.mark.parametrize("with_radiance", [True, False], ids=["radiance-and-pixels", "pixels-only"])
+def test_host_form_on_a_rectangle_gives_the_device_form_s_bits_and_writes_nothing_outside(L, plain_scene, with_radiance):
+    """terra_amd_denoise_variance on a rectangle that is no multiple of the 16 x 16 block, K = 3 (the taps of step 4 cross its edge), pixels of known and of unknown
+    variance inside it; radiance may be NULL."""
+    from terra_amd import runtime
+    res, aov = synthetic(64, 48, 18)
+    mom = synthetic_moments(res, 19)
+    x, y, w, h = rect = (5, 3, 40, 30)
+    inside = np.zeros((48, 64), bool); inside[y:y + h, x:x + w] = True
+    known = (mom["batches"] >= 2) & (res["samples"] > 0)
+    assert (known & inside).any() and (~known & inside & (res["samples"] > 0)).any()
+    rad, pix = device_denoise_variance(L, plain_scene, res, aov, mom, 3, rect=rect)
+    assert not np.array_equal(bits(rad[inside]), bits(device_denoise(L, plain_scene, res, aov, 3, rect=rect)[0][inside]))          # (the variance is in play)
+    hfb = api.Framebuffer(L, 64, 48)
+    np.copyto(hfb.results, res)
+    hr, hp = np.full((48, 64, 3), -7.0, F), np.full((48, 64, 3), -7.0, F)
+    runtime.check(L.denoise_variance(plain_scene, C.byref(hfb.fb), aov.ctypes.data, mom.ctypes.data, x, y, w, h, 3, hr.ctypes.data if with_radiance else None, hp.ctypes.data),
+                  "terra_amd_denoise_variance")
+    assert np.all(pix[inside] != F(-7.0))
+    assert np.array_equal(bits(hp[inside]), bits(pix[inside])) and np.all(hp[~inside] == F(-7.0))
+    if with_radiance:
+        assert np.array_equal(bits(hr[inside]), bits(rad[inside])) and np.all(hr[~inside] == F(-7.0))
+    else:
+        assert np.all(hr == F(-7.0))
+    hfb.destroy()
+
+
 def test_a_quiet_pixel_rejects_a_firefly_neighbour(L, plain_scene):
     """constant image, 8 batches of 4 samples all equal -- except one pixel, one of whose batches is 1000 x. After K = 5 the eight neighbours deviate less from the
     constant than terra_amd_denoise_device leaves them on the same inputs."""
