@@ -227,6 +227,18 @@ int  terra_amd_empty_skip_info ( HTerraScene scene, uint32_t out[2] );
 int  terra_amd_empty_proof ( const float* cam_rot9, const float* cam_pos3, float tan_half_fov, float aspect, float jitter, uint32_t fb_w, uint32_t fb_h,
                              uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, const float* tris9, size_t n_tris );
 
+/* Flat leaf-box test, on by default. On a scene of at most 32 triangles held in LDS, the tree walk of a ray only decides which leaf boxes the ray passes. Such a
+   scene's commit also lists its DISTINCT leaf boxes (the two triangles of an axis-aligned quad share one: the Cornell box has 16), and a launch that runs the
+   leaf-box cull with the scene and the camera inside its coordinate range, without work counters, tests every listed box in one loop that is uniform over the wave
+   instead of walking the tree lane by lane. The triangles tested can only gain ones the ray cannot hit (DESIGN.md 3.1 "Flat leaf-box test"): the framebuffer is
+   the same bit for bit (tests/test_leaf_boxes_gpu.py). Every other launch -- counting launches, larger scenes, tree mode `reference`, out of range -- and every wave
+   that holds an axis-parallel ray walks the tree as before. A launch parameter: no commit needed.
+   terra_amd_leaf_box_info: out[0] = 1 when the scene's most recent single-device launch used the flat test, out[1] = the distinct leaf boxes of the committed scene
+   (0: it has no table). */
+int  terra_amd_set_leaf_box_test ( HTerraScene scene, int on );
+int  terra_amd_get_leaf_box_test ( HTerraScene scene );
+int  terra_amd_leaf_box_info ( HTerraScene scene, uint32_t out[2] );
+
 /* Environment lighting, off by default. The reference evaluates scene options' environment_map for a ray
    that leaves the scene, multiplies the throughput by it and then drops the result: the line that would
    add it is commented out (src/Terra.c:1053-1058), so the environment never reaches the image. With
@@ -320,6 +332,10 @@ int terra_amd_scene_bvh_nodes ( HTerraScene scene, void* out, int capacity );
    reference traversal's leaf visit order with every box hit, as the LDS-resident kernels
    use it; returns the triangle count (0 for an empty scene) or a negative status. */
 int terra_amd_scene_leaf_ranks ( HTerraScene scene, uint32_t* out, int capacity );
+/* The distinct leaf boxes of a committed scene of at most 32 triangles, as the flat leaf-box test reads them: seven 32-bit words per entry -- min.xyz, max.xyz
+   (floats) and the mask of the ranks (bit r = the triangle of rank r, above) whose leaf carries that box bit for bit. Entries are ordered by their lowest rank and
+   every rank is in exactly one mask. `out` has room for `capacity` entries; returns the entry count (0: no triangle, or more than 32) or a negative status. Needs no device. */
+int terra_amd_scene_leaf_boxes ( HTerraScene scene, void* out, int capacity );
 
 /* terra_render() (include/Terra.h:229, src/Terra.c:512-635) on a framebuffer
    that already lives in HBM: d_pixels = float[3]*fb_width*fb_height,

@@ -105,6 +105,11 @@ struct DevLight {
     float    area;
 };
 
+// One entry of a scene's leaf-box table (scene_host.cpp leaf_box_table; traverse_ref.h "Flat leaf-box test"): a box that one or more leaf children of the
+// reference tree carry, bit for bit, and the rank bits (1 << DevTri::pad) of those children's triangles
+struct DevLeafBox { float bmin[3], bmax[3]; uint32_t mask; };
+static_assert ( sizeof ( DevLeafBox ) == 28, "DevLeafBox must be 28 bytes" );
+
 struct DevScene {
     const DevNode*     nodes;
     const DevTri*      tris;
@@ -233,4 +238,8 @@ struct DevRenderParams {
     // (live blocks x split x 256, written by terra_block_order_kernel). Those blocks are never keyed, queued or traced: the resolve kernel adds their +0 sums.
     // nullptr: every block is live. (Last, so that the kernels that never read it keep their argument offsets.)
     const uint32_t* job_live;
+    // flat leaf-box test (traverse_ref.h "Flat leaf-box test"; terra_amd_set_leaf_box_test): n_leaf_boxes > 0 = a ranked fused launch without work counters stages the
+    // scene's table of distinct leaf boxes (leaf_boxes: n_leaf_boxes entries in the scene blob) and its tame waves test those boxes instead of walking the tree
+    const DevLeafBox* leaf_boxes;
+    uint32_t n_leaf_boxes;
 };

@@ -20,6 +20,7 @@ hipError_t terra_launch_resolve ( const DevRenderParams& p, hipStream_t stream )
 bool       terra_scene_fits_lds ( uint32_t n_nodes, uint32_t n_tris, int max_stack, uint32_t n_objects, uint32_t n_lights );   // whole scene staged per block (the small-scene kernels)
 void       terra_plan_lds ( DevRenderParams& p );     // fills stack_depth / lds_nodes / lds_tris / lds_mode
 size_t     terra_lds_bytes ( const DevRenderParams& p );   // dynamic LDS per block of the planned launch
+bool       terra_leaf_boxes_fit ( const DevRenderParams& p, uint32_t n );   // may the launch stage a table of n distinct leaf boxes (flat leaf-box test)?
 size_t     terra_lds_block_limit ( void );                // the most a block may ask for (launch_instance opts in above 64 KB)
 size_t     terra_fast_spill_bytes ( const DevRenderParams& p );   // bytes of DevRenderParams::stack_spill a fast-tree launch needs (p.job_blocks set; 0: the stack fits in LDS)
 void       terra_plan_fast_tree ( DevRenderParams& p );     // the plan of a fast-tree (MODE 2 / 3) launch: stack from the tree's depth, nothing staged

@@ -66,7 +66,8 @@ TD void wave_flush_counters ( const Counters& c, unsigned long long* g ) {
 #define TERRA_CHECK_SHRINK 0
 #endif
 template <int MODE>
-TD Tracer make_tracer ( const DevScene& sc, float4* lds, uint32_t stack_depth, uint32_t leaf_cap, uint32_t lds_nodes, uint32_t lds_tris, bool cull, bool fused, bool ranked ) {
+TD Tracer make_tracer ( const DevScene& sc, float4* lds, uint32_t stack_depth, uint32_t leaf_cap, uint32_t lds_nodes, uint32_t lds_tris, bool cull, bool fused, bool ranked,
+                        const DevLeafBox* leaf_boxes, uint32_t n_leaf_boxes ) {
     const int tid = threadIdx.x;
     Tracer T;
     T.sc = sc;
@@ -80,6 +81,9 @@ TD Tracer make_tracer ( const DevScene& sc, float4* lds, uint32_t stack_depth, u
     uint32_t* ll = lm + m_words; uint32_t* la = ll + l_words;
     ranked = MODE == 1 && ranked;
     float4* lr = reinterpret_cast<float4*> ( la + a_words );            // ranked launches: 6 permuted copies of the triangles in rank order (traverse_ref.h "Ranked launches")
+    // flat leaf-box test: the scene's distinct leaf boxes ride in the pad words of the ranked entries and of the staged properties (traverse_ref.h "Flat leaf-box test");
+    // the host admits a table only where it has no more boxes than the launch stages triangles (terra_leaf_boxes_fit)
+    const uint32_t n_boxes = ( ranked && cull && fused && leaf_boxes && n_leaf_boxes <= lds_tris ) ? n_leaf_boxes : 0u;
     int* words = reinterpret_cast<int*> ( lr + ( ranked ? 18u * lds_tris : 0u ) );
     T.stack = words + tid;
     T.leaves = words + stack_depth * TERRA_COL + tid;
@@ -112,14 +116,23 @@ TD Tracer make_tracer ( const DevScene& sc, float4* lds, uint32_t stack_depth, u
             const DevTri& t = gtri[ti];
             const int kz = ( int ) ( perm >> 1 ), k1 = kz == 2 ? 0 : kz + 1, k2 = k1 == 2 ? 0 : k1 + 1;
             const int kx = ( perm & 1u ) ? k2 : k1, ky = ( perm & 1u ) ? k1 : k2;
+            static_assert ( TERRA_RANKED_ENTRY_BYTES == 3 * sizeof ( float4 ) && TERRA_RANKED_PAD_OFFSET == 2 * sizeof ( float4 ) + 8, "e[2].z / e[2].w below are the entry's pad words (leaf_boxes_flat reads them)" );
             float4* e = lr + 3u * ( perm * lds_tris + t.pad );
             e[0] = make_float4 ( t.a[kx], t.a[ky], t.a[kz], t.b[kx] );
             e[1] = make_float4 ( t.b[ky], t.b[kz], t.c[kx], t.c[ky] );
-            e[2] = make_float4 ( t.c[kz], __uint_as_float ( ti ), 0.f, 0.f );
+            // the entry's pad words: slot j = 6 k + 2 a + s of the leaf-box table = box k, axis a, (min, max) for s = 0 / (max, min) for s = 1
+            const uint32_t j = perm * lds_tris + t.pad, k = j / 6u, as = j - 6u * k;
+            float p0 = 0.f, p1 = 0.f;
+            if ( k < n_boxes ) { const float mn = leaf_boxes[k].bmin[as >> 1], mx = leaf_boxes[k].bmax[as >> 1]; p0 = ( as & 1u ) ? mx : mn; p1 = ( as & 1u ) ? mn : mx; }
+            e[2] = make_float4 ( t.c[kz], __uint_as_float ( ti ), p0, p1 );
         }
     }
     for ( uint32_t i = tid; i < 3 * lds_tris; i += TERRA_COL ) lt[i] = gt[i];
-    for ( uint32_t i = tid; i < 4 * lds_tris; i += TERRA_COL ) lp[i] = gp[i];
+    for ( uint32_t i = tid; i < 4 * lds_tris; i += TERRA_COL ) {
+        float4 v = gp[i];
+        if ( ( i & 3u ) == 3u && ( i >> 2 ) < n_boxes ) v.w = __uint_as_float ( leaf_boxes[i >> 2].mask );      // DevProps::pad of triangle k: the rank mask of leaf box k
+        lp[i] = v;
+    }
     if ( MODE == 1 ) {
         const uint32_t* gm = reinterpret_cast<const uint32_t*> ( sc.mats ); const uint32_t* gl = reinterpret_cast<const uint32_t*> ( sc.lights ); const uint32_t* ga = reinterpret_cast<const uint32_t*> ( sc.tri_area );
         for ( uint32_t i = tid; i < sc.n_objects * ( uint32_t ) ( sizeof ( DevMaterial ) / 4 ); i += TERRA_COL ) lm[i] = gm[i];
@@ -129,6 +142,7 @@ TD Tracer make_tracer ( const DevScene& sc, float4* lds, uint32_t stack_depth, u
     T.l_mats = MODE == 1 ? reinterpret_cast<const DevMaterial*> ( lm ) : sc.mats; T.l_lights = MODE == 1 ? reinterpret_cast<const DevLight*> ( ll ) : sc.lights; T.l_area = MODE == 1 ? reinterpret_cast<const float*> ( la ) : sc.tri_area;
     T.l_nodes = ln; T.l_tris = reinterpret_cast<const float*> ( lt ); T.l_props = lp;
     T.l_ranked = ranked ? lr : nullptr; T.ranked = ranked;
+    T.n_boxes = n_boxes;
     T.lds_nodes = lds_nodes; T.lds_tris = lds_tris;
     __syncthreads();
     return T;
@@ -473,7 +487,7 @@ template <int INTEGRATOR, int COUNT, int MODE, int KINDS>
 __global__ __launch_bounds__ ( 256, TERRA_WAVES_FOR ( INTEGRATOR, KINDS, MODE ) ) void terra_render_kernel ( DevRenderParams p ) {
     extern __shared__ float4 lds_f4[];
     const int tid = threadIdx.x;
-    Tracer T0 = make_tracer<MODE> ( p.scene, lds_f4, p.stack_depth, p.leaf_cap, p.lds_nodes, p.lds_tris, p.leaf_cull != 0, p.fused_slab != 0, p.leaf_rank != 0 );
+    Tracer T0 = make_tracer<MODE> ( p.scene, lds_f4, p.stack_depth, p.leaf_cap, p.lds_nodes, p.lds_tris, p.leaf_cull != 0, p.fused_slab != 0, p.leaf_rank != 0, p.leaf_boxes, p.n_leaf_boxes );
     T0.faults = p.counters + kCtrFaults;
     if ( MODE >= 2 && p.stack_spill ) { T0.spill = p.stack_spill + ( size_t ) ( blockIdx.x * 256u + threadIdx.x ) * p.spill_cap; T0.spill_cap = p.spill_cap; }
     const Tracer T = T0;
@@ -772,7 +786,7 @@ static size_t scene_extra_lds_bytes ( uint32_t n_objects, uint32_t n_lights, uin
 }
 size_t terra_lds_bytes ( const DevRenderParams& p ) {
     return ( size_t ) ( p.stack_depth + p.leaf_cap + ( p.lds_mode == 1 ? TERRA_AUX_WORDS_LDS : TERRA_AUX_WORDS ) ) * 1024 + ( size_t ) p.lds_nodes * TERRA_LDS_NODE_BYTES + ( size_t ) p.lds_tris * ( 48 + 64 )
-           + ( p.lds_mode == 1 ? scene_extra_lds_bytes ( p.scene.n_objects, p.scene.n_lights, p.scene.n_tris ) : 0 ) + ( p.lds_mode == 1 && p.leaf_rank ? ( size_t ) p.lds_tris * 6 * 48 : 0 );
+           + ( p.lds_mode == 1 ? scene_extra_lds_bytes ( p.scene.n_objects, p.scene.n_lights, p.scene.n_tris ) : 0 ) + ( p.lds_mode == 1 && p.leaf_rank ? ( size_t ) p.lds_tris * 6 * 48 : 0 );      // (the leaf-box table of a flat launch rides in pad words of these: no bytes of its own)
 }
 // fast tree (MODE 2 / 3): nothing is staged. A lane holds at most two leaves (in registers: the one it tests, the next one), so there is no leaf list. The stack: its first TERRA_FAST_STACK_LDS entries
 // in LDS (1 KB per entry and block), the rest -- up to the tree's worst case, which a ray almost never reaches -- in HBM, 4 bytes per entry and resident lane
@@ -845,6 +859,11 @@ void terra_plan_lds ( DevRenderParams& p ) {
     // a deep tree: keep the block within the 64 KB a launch may ask for without an opt-in while the leaf list keeps at least 4 entries; deeper still, the launch opts in
     // (launch_instance: hipFuncAttributeMaxDynamicSharedMemorySize, one block per CU) up to TERRA_LDS_BLOCK_MAX_KB, beyond which terra_launch_render refuses with a message
     while ( p.leaf_cap > 4 && terra_lds_bytes ( p ) > ( size_t ) 64 * 1024 ) --p.leaf_cap;
+}
+// Flat leaf-box test: can a launch planned as p stage a table of n boxes? Ranked launches with the fused box test only (make_tracer stages under the same
+// condition); the table rides in pad words of what such a launch stages anyway, one set per triangle, so it fits whenever n <= the triangles staged
+bool terra_leaf_boxes_fit ( const DevRenderParams& p, uint32_t n ) {
+    return n != 0 && n <= TERRA_LEAF_RANK_MAX && p.lds_mode == 1 && p.leaf_rank && p.leaf_cull && p.fused_slab && n <= p.lds_tris;
 }
 
 #endif

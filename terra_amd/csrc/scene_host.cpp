@@ -301,7 +301,7 @@ struct TreeChoice {
     float reach_margin = 0.f, fast_extra = 0.f, fast_scale = 1.f;
 };
 // The blob: one device allocation per copy of the scene, these sections in this order, 256-byte aligned, then one section per texture (layout_blob)
-enum { kSecNodes, kSecTris, kSecProps, kSecMats, kSecLights, kSecArea, kSecFastBin, kSecFastWide, kSecFastTris, kSecReplay, kSecLeafParent, kSecLeafMask, kSecTexDesc, kSecTextures };
+enum { kSecNodes, kSecTris, kSecProps, kSecMats, kSecLights, kSecArea, kSecFastBin, kSecFastWide, kSecFastTris, kSecReplay, kSecLeafParent, kSecLeafMask, kSecLeafBoxes, kSecTexDesc, kSecTextures };
 struct Section { size_t offset = 0, bytes = 0; const void* host = nullptr; size_t host_bytes = 0; };      // bytes: its room in the blob; host: what the upload copies there
 struct BlobLayout { std::vector<Section> sec; std::vector<DevTexture> tdesc; size_t total = 0; };        // tdesc: the texture descriptors, less their address
 // A stream on one device and a staging frame there (12 B of pixel + 16 B of running sums per pixel), grown to the largest rectangle rendered through it:
@@ -370,6 +370,9 @@ struct Scene {
     int job_order = 1;                  // terra_amd_set_job_order (0 off, 1 on, 2 on for launches of any size): launches that key their streams ahead hand out the pixel blocks no camera ray hits last (launch_render)
     int empty_skip = 1;                 // terra_amd_set_empty_skip: job-ordered launches neither key nor trace the pixel blocks proved empty before the launch (empty_proof.h, launch_render)
     std::atomic<uint32_t> skip_last_blocks { 0 }; std::atomic<int> skip_last_device { -1 };      // terra_amd_empty_skip_info: the last launch's pixel blocks; the device whose counter holds its proved ones (-1: that launch proved nothing)
+    int leaf_box_test = 1;              // terra_amd_set_leaf_box_test: ranked fused launches without work counters test the scene's distinct leaf boxes in one uniform loop instead of walking the tree (traverse_ref.h "Flat leaf-box test")
+    std::vector<DevLeafBox> leaf_boxes; // the table of the last commit (leaf_box_table; empty: the scene has none), as uploaded in the blob
+    std::atomic<uint32_t> flat_last { 0 };      // terra_amd_leaf_box_info: the boxes the most recent launch staged (0: it walked the tree)
     bool sampler_integration = false;   // terra_amd_set_sampler_integration: the pixel's Halton / stratified sampler feeds the first bounce (a launch parameter)
     std::string commit_error;
     std::atomic<bool> warned_camera { false };      // the per-call fallback (camera outside camera_limit) has been reported on stderr once
@@ -510,6 +513,11 @@ extern "C" int terra_amd_set_empty_skip ( HTerraScene h, int on ) {
     S ( h )->empty_skip = on; return 0;
 }
 extern "C" int terra_amd_get_empty_skip ( HTerraScene h ) { return S ( h )->empty_skip; }
+extern "C" int terra_amd_set_leaf_box_test ( HTerraScene h, int on ) {
+    if ( on < 0 || on > 1 ) return fail ( kTerraAmdErrBadArgument, "terra_amd_set_leaf_box_test: 0 (off) or 1 (on)" );
+    S ( h )->leaf_box_test = on; return 0;
+}
+extern "C" int terra_amd_get_leaf_box_test ( HTerraScene h ) { return S ( h )->leaf_box_test; }
 // the predicate of empty_proof.h on the host (tests, tools): 1 when the block of pixels [x0, x1) x [y0, y1) is proved empty against n_tris triangles of 9 floats each
 extern "C" int terra_amd_empty_proof ( const float* cam_rot9, const float* cam_pos3, float tan_half_fov, float aspect, float jitter, uint32_t fb_w, uint32_t fb_h,
                                        uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, const float* tris9, size_t n_tris ) {
@@ -660,6 +668,26 @@ static std::vector<uint32_t> leaf_ranks ( const Scene* s ) {
     return rank;
 }
 
+// The distinct leaf boxes of a scene of at most TERRA_LEAF_RANK_MAX triangles (traverse_ref.h "Flat leaf-box test"). nodes / tris: the reference tree and the soup as
+// the device stages them (DevTri::pad = the triangle's rank). Every non-empty leaf child contributes its box and its bit 1 << rank; boxes equal bit for bit (the six
+// words compared as integers, so -0 and +0 differ and a NaN equals itself) are one entry whose mask is the OR of their bits. Every rank is in exactly one mask; the
+// entries are ordered by their lowest rank. Empty for a scene without triangles or with more than TERRA_LEAF_RANK_MAX.
+static std::vector<DevLeafBox> leaf_box_table ( const std::vector<DevNode>& nodes, const std::vector<DevTri>& tris, size_t ntri ) {
+    std::vector<DevLeafBox> table;
+    if ( ntri == 0 || ntri > 32 ) return table;
+    for ( const DevNode& d : nodes ) for ( int k = 0; k < 2; ++k ) {
+        if ( d.child[k] == DEV_CHILD_EMPTY || ! ( d.child[k] & DEV_CHILD_LEAF ) ) continue;
+        DevLeafBox b;
+        memcpy ( b.bmin, k ? d.min1 : d.min0, 12 ); memcpy ( b.bmax, k ? d.max1 : d.max0, 12 );
+        b.mask = 1u << ( tris[d.child[k] & 0x7fffffffu].pad & 31u );
+        bool merged = false;
+        for ( DevLeafBox& e : table ) if ( memcmp ( e.bmin, b.bmin, 24 ) == 0 ) { e.mask |= b.mask; merged = true; break; }
+        if ( !merged ) table.push_back ( b );
+    }
+    std::sort ( table.begin(), table.end(), [] ( const DevLeafBox & a, const DevLeafBox & b ) { return ( a.mask & ( 0u - a.mask ) ) < ( b.mask & ( 0u - b.mask ) ); } );
+    return table;
+}
+
 // ---- reachability tables (DevScene::ref_replay / fast_leaf_parent / fast_leaf_mask) -------------------------------------------------------------
 // nodes: the reference tree as the DEVICE holds it (breadth-first numbering, test hook applied); soup_of_fast[k] = soup index of fast triangle k.
 // Level L of fast triangle k = the L-th reference node on the way up from the triangle's leaf; its test is the slab test of the box that node's parent
@@ -778,6 +806,7 @@ struct Flat {
     size_t ntri = 0;
     std::vector<DevMaterial> mats; std::vector<DevTri> tris; std::vector<DevProps> props; std::vector<DevLight> lights; std::vector<float> tri_area;
     std::vector<DevNode> nodes; std::vector<uint32_t> rank;
+    std::vector<DevLeafBox> leaf_boxes;      // (commit_scene: made once the tree's boxes are final)
     std::vector<const TerraTexture*> textures;
     int32_t env_mode = 0, env_tex = -1; float env_color[3] = { 0.f, 0.f, 0.f };
 };
@@ -1018,6 +1047,7 @@ static BlobLayout layout_blob ( const Flat& f, const FastTree& ft, const TreeCho
     L.sec[kSecFastTris] = section_of ( ft.tris, on_dev ? on_dev : ft.tris.size() );
     L.sec[kSecReplay] = section_of ( ft.reach.replay, n_replay );
     L.sec[kSecLeafParent] = section_of ( ft.reach.leaf_parent, n_reach ); L.sec[kSecLeafMask] = section_of ( ft.reach.leaf_mask, n_reach );
+    L.sec[kSecLeafBoxes] = section_of ( f.leaf_boxes, f.leaf_boxes.size() );
     layout_textures ( L, f.textures );
     return L;
 }
@@ -1206,6 +1236,10 @@ static int commit_scene ( Scene* s, int device ) {
             mn[a] = std::min ( mn[a], lo ); mx[a] = std::max ( mx[a], hi );
         }
     }
+    // the distinct leaf boxes of a small scene, from the boxes as they now stand (after the test hook and the rebuilt leaf boxes): what a ranked launch may test
+    // in place of the walk (traverse_ref.h "Flat leaf-box test"). Kept on the host too (terra_amd_scene_leaf_boxes)
+    f.leaf_boxes = leaf_box_table ( f.nodes, f.tris, f.ntri );
+    s->leaf_boxes = f.leaf_boxes;
     FastTree ft;
     if ( c.use_fast && !c.fast_on_device ) { if ( int rc = build_fast_tree_host ( s, c, f, ft ) ) return rc; }
     // The automatic mode's fallbacks are correct and 10-20 x slower on scenes of this size (hall: 110 against 2,400 Msamples/s): say so where a client looks, once per commit.
@@ -1282,6 +1316,14 @@ extern "C" int terra_amd_scene_leaf_ranks ( HTerraScene h, uint32_t* out, int ca
     size_t ntri = 0; for ( size_t j = 0; j < s->objects_pop; ++j ) ntri += s->objects[j].triangles_count;
     const int n = ( int ) ntri;
     if ( out && capacity >= n ) memcpy ( out, rank.data(), ( size_t ) n * sizeof ( uint32_t ) );
+    return n;
+}
+// the scene's distinct leaf boxes as committed: 7 words per entry -- min.xyz, max.xyz, the rank mask. Returns the number of entries (0: the scene has no table)
+extern "C" int terra_amd_scene_leaf_boxes ( HTerraScene h, void* out, int capacity ) {
+    Scene* s = S ( h );
+    if ( !s->committed ) return fail ( kTerraAmdErrNotCommitted, "scene not committed" );
+    const int n = ( int ) s->leaf_boxes.size();
+    if ( out && capacity >= n && n ) memcpy ( out, s->leaf_boxes.data(), ( size_t ) n * sizeof ( DevLeafBox ) );
     return n;
 }
 // counters [first, first + n) summed over every replica, each device current around its copy (the primary's last: it stays current)
@@ -1405,6 +1447,11 @@ static int fill_params ( Scene* s, const Scene::Replica& r, const TerraCamera* c
     }
     p.leaf_cull = ( c.cull_ok && cam_ok && p.lds_mode != 2 ) ? 1u : 0u;
     p.fused_slab = ( p.leaf_cull && !c.reach_cull ) ? 1u : 0u;      // (out of range only the rebuilt LEAF boxes carry a margin: the inner boxes are tested exactly as the reference tests them)
+    // flat leaf-box test: a ranked launch with the fused box test stages the scene's distinct leaf boxes where they fit (launch_render drops them again for a
+    // counting launch: the counters are defined by the walk)
+    if ( s->leaf_box_test && r.d_blob && terra_leaf_boxes_fit ( p, ( uint32_t ) s->leaf_boxes.size() ) ) {
+        p.leaf_boxes = ( const DevLeafBox* ) ( ( const char* ) r.d_blob + s->blob.sec[kSecLeafBoxes].offset ); p.n_leaf_boxes = ( uint32_t ) s->leaf_boxes.size();
+    }
     // the azimuth table pays where VALU issue binds (LDS-resident scenes: Cornell Simple 65.8 -> 64.2 ms, Direct 145.2 -> 142.5); the kernels that wait on memory anyway
     // lose by one more dependent load per shaded hit (sphere scene 395 -> 419 ms, hall 282 -> 284; profiles/r03_measurements/ab_sincos_table.log)
 #ifndef TERRA_SINCOS_TABLE_FAST_TREE       // (A/B) the azimuth table for fast-tree launches too
@@ -1476,6 +1523,7 @@ static uint32_t launch_split ( const Scene* s, DevRenderParams& p, uint32_t bloc
 static int launch_render ( Scene* s, DevRenderParams& p, int device, hipStream_t stream, ThreadSlot* slot = nullptr ) {      // device: the (current) device of the launch
     const uint32_t blocks = terra_render_blocks ( p );
     if ( blocks == 0 ) return 0;
+    if ( p.count_level != 0 || p.rand_calls ) { p.leaf_boxes = nullptr; p.n_leaf_boxes = 0; }      // the work counters keep their meaning: counting launches walk the tree
     const uint32_t split = launch_split ( s, p, blocks );
     static thread_local uint64_t pool_kept = 0;          // (bit d: done for device d)
     if ( device < 64 && ! ( pool_kept >> device & 1ull ) ) {        // keep freed scratch cached in the device's default pool instead of returning it to the OS at every sync
@@ -1535,6 +1583,7 @@ static int launch_render ( Scene* s, DevRenderParams& p, int device, hipStream_t
     if ( pooled ) ( void ) hipFreeAsync ( scratch, stream );
     else if ( e != hipSuccess ) ( void ) hipMemsetAsync ( scratch, 0, header, stream );       // (a launch that failed half way must not leave a used queue word behind)
     if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "render launch: %s", hipGetErrorString ( e ) );
+    s->flat_last.store ( p.n_leaf_boxes, std::memory_order_relaxed );
     s->skip_last_blocks.store ( blocks, std::memory_order_relaxed ); s->skip_last_device.store ( skip ? device : -1, std::memory_order_relaxed );      // (only a launch that was queued whole is reported)
     return 0;
 }
@@ -1572,6 +1621,13 @@ extern "C" int terra_amd_empty_skip_info ( HTerraScene h, uint32_t out[2] ) {
         HIP_TRY ( hipMemcpy ( &v, r.d_counters + kCtrSkipProved, sizeof v, hipMemcpyDeviceToHost ), kTerraAmdErrLaunch );
         out[0] = ( uint32_t ) v;
     }
+    return 0;
+}
+// out[0]: 1 when the scene's most recent launch tested its distinct leaf boxes in place of the tree walk; out[1]: the distinct leaf boxes of the committed scene
+extern "C" int terra_amd_leaf_box_info ( HTerraScene h, uint32_t out[2] ) {
+    Scene* s = S ( h );
+    if ( !out ) return fail ( kTerraAmdErrBadArgument, "terra_amd_leaf_box_info: null output" );
+    out[0] = s->flat_last.load ( std::memory_order_relaxed ) ? 1u : 0u; out[1] = ( uint32_t ) s->leaf_boxes.size();
     return 0;
 }
 extern "C" int terra_amd_synchronize ( void* stream ) {

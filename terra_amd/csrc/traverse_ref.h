@@ -2,6 +2,7 @@
 // steps, the ranked traversal of small LDS-resident scenes, the resumable form of the decoupled render loops.
 #pragma once
 #include "trace_geometry.h"
+#include <stddef.h>
 
 // per-lane work counters (registers); flushed with one atomic per wave and counter.
 // Not counted on the device because the host can derive them exactly: slab tests
@@ -59,7 +60,27 @@ enum { kPsRayIter = 0, kPsNodeIter, kPsLeafIter, kPsShadeIter, kPsCamIter, kPsCa
 // 1 << (its triangle's reference visit rank, DevTri::pad), 0 for an inner child or an empty slot (0 in every other launch). The leaf list is replaced by
 // the triangles staged in rank order once per axis permutation of the watertight test (kz = the dominant axis, kx / ky swapped when d[kz] < 0):
 // 6 copies x lds_tris x 48 B, entry = a[kx] a[ky] a[kz] b[kx] | b[ky] b[kz] c[kx] c[ky] | c[kz] triangle - -.
+//
+// Flat leaf-box test (DevRenderParams::n_leaf_boxes: ranked launches with the fused box test and no work counters; leaf_boxes_flat). The node loop of a ranked
+// launch only computes "which leaf boxes does this ray pass", so the block also stages the scene's DISTINCT leaf boxes (DevLeafBox: the two triangles of an
+// axis-aligned quad share one box bit for bit; the Cornell box has 16 for its 32 triangles) and a tame wave tests every one of them in a wave-uniform loop -- no
+// stack, no child words, no trip count set by the slowest lane. The table takes NO LDS of its own: a 48-byte-per-box table beside the other sections would put the
+// Cornell block (terra_lds_bytes: 31,760 B) at 32,592 B, past the TERRA_LDS_BUDGET that keeps five blocks per CU resident (DESIGN.md 3.1 "Flat leaf-box test" has
+// the arithmetic). It lives in words the ranked layout leaves unused,
+//     the two pad words of the ranked triangle entries (the `- -` above): entry 6 k + 2 a + s (counted through the copies) = box k, axis a:
+//         (min, max) for s = 0, (max, min) for s = 1 -- "both signs", as the staged node: a ray reads (near, far) of an axis with one 8-byte load, picked by
+//         3 x its SlabSel offset (48 x (2 a + s)), box k at the immediate offset 288 k;
+//     the pad word of the staged vertex properties of triangle k (DevProps::pad): the rank mask of box k.
+// A scene has at most as many distinct leaf boxes as triangles, so 6 boxes-worth of entries and one mask word per box are always there.
 // -----------------------------------------------------------------------------
+#define TERRA_RANKED_ENTRY_BYTES 48                                  // a ranked triangle entry: three 16-byte pieces, the last one c[kz] triangle - -
+#define TERRA_RANKED_PAD_OFFSET 40                                   // ... whose two pad words are its last 8 bytes
+#define TERRA_LEAF_BOX_STRIDE ( 6 * TERRA_RANKED_ENTRY_BYTES )       // a leaf box: the pad words of six consecutive entries (3 axes x 2 signs)
+#define TERRA_LEAF_BOX_MASK_OFFSET 60                                // DevProps::pad in the staged properties of triangle k ...
+#define TERRA_LEAF_BOX_MASK_STRIDE 64                                // ... one DevProps per box
+static_assert ( TERRA_RANKED_PAD_OFFSET == TERRA_RANKED_ENTRY_BYTES - 8 && TERRA_LEAF_BOX_STRIDE == 288, "leaf-box slots = the last two words of the 48-byte ranked entries" );
+static_assert ( offsetof ( DevProps, pad ) == TERRA_LEAF_BOX_MASK_OFFSET && sizeof ( DevProps ) == TERRA_LEAF_BOX_MASK_STRIDE, "leaf-box masks = DevProps::pad of the staged properties" );
+#define TERRA_LEAF_BOX_GROUP 4     // boxes per trip of the unrolled loop (offsets as immediates); the up to three boxes left over are tested one per trip
 #define TERRA_LEAF_CAP_MAX 16
 #define TERRA_LEAF_RANK_MAX 32     // triangles a ranked launch can have: a lane's leaf set is one 32-bit word
 #define TERRA_COL 256              // stride of a stack / leaf-list column: the block's thread count
@@ -74,6 +95,7 @@ struct Tracer {
     const DevLight*    l_lights;
     const float*       l_area;
     const float4* l_ranked;    // ranked launches: the 6 permuted copies of the staged triangles, in rank order (see above); nullptr otherwise
+    uint32_t      n_boxes;     // flat leaf-box test: the distinct leaf boxes staged in the pad words of l_ranked / l_props (see above); 0 in every other launch
     uint32_t      lds_nodes, lds_tris;
     int*          stack;       // this thread's column
     int*          leaves;
@@ -205,14 +227,57 @@ TD void leaf_step ( const Tracer& T, const int* entry, const RayState& st, V3 o_
 // hit meets them (scene_host.cpp leaf_ranks) --, so "test the listed leaves in the order met" is "test the set ranks from low to high": the same triangles,
 // in the same order, with the same strict "<". The node loop therefore runs to the end in one pass and only sets bits; the leaf loop then walks the set
 // bits and reads each triangle, already permuted into the ray's axes, with three 16-byte loads from the copy for the ray's permutation.
+// The flat form of a ranked launch's node loop (see "Flat leaf-box test" above): every lane tests every staged box, with the floats and the arithmetic node_step
+// applies to that box on a FUSED walk, and collects the masks of the boxes it passes. The set can only exceed the walk's by leaves whose own box passes while an
+// ancestor's fails; by the containment property the commit verifies (a triangle the ray hits lies inside every box built around it as the box
+// test sees it) such a triangle is not hit, so the closest hit, the tie-breaks and the ANYHIT answers are the walk's.
+// (TERRA_PHASE_STATS builds count one node iteration per box tested.)
+TD void leaf_box_test ( const char* px, const char* py, const char* pz, const char* pm, const Ray& r, const SlabSel& sel, uint32_t& leaf_set, Counters& c ) {
+    PS_WAVE ( c, kPsNodeIter ); PS_LANE ( c, kPsNodeLanes );
+    const float2 ax = *reinterpret_cast<const float2*> ( px ), ay = *reinterpret_cast<const float2*> ( py ), az = *reinterpret_cast<const float2*> ( pz );
+    const uint32_t m = *reinterpret_cast<const uint32_t*> ( pm );          // (read whether or not the box is hit: a select, not a branch around a load)
+    float te;
+    const bool hit = slab_near_far_fused ( ax.x, ax.y, ay.x, ay.y, az.x, az.y, r, sel.oi, te );
+    leaf_set |= hit ? m : 0u;
+}
+TD uint32_t leaf_boxes_flat ( const Tracer& T, const Ray& r, const SlabSel& sel, Counters& c ) {
+    const char* base = reinterpret_cast<const char*> ( T.l_ranked ) + TERRA_RANKED_PAD_OFFSET;
+    constexpr uint32_t kSel = TERRA_RANKED_ENTRY_BYTES / 16;           // SlabSel offsets are 16 x (2 a + s), the slots of a box TERRA_RANKED_ENTRY_BYTES x (2 a + s)
+    const char* px = base + kSel * sel.x; const char* py = base + kSel * sel.y; const char* pz = base + kSel * sel.z;
+    const char* pm = reinterpret_cast<const char*> ( T.l_props ) + TERRA_LEAF_BOX_MASK_OFFSET;
+    uint32_t leaf_set = 0u;
+    // one group at a time, as written. Cross-compiled for gfx950 without these pragmas (profiles/leaf_boxes/kernel_resources.md): left to unroll, the loads of
+    // several groups are hoisted together and the Simple kernel takes 1,728 B of scratch; vectorised two groups wide, the tests become v_pk_fma_f32 fed by moves
+    // (104 B of scratch; build.py on why the build keeps packed arithmetic out). With them: no scratch
+    #pragma clang loop vectorize(disable) interleave(disable) unroll(disable)
+    for ( uint32_t g = T.n_boxes / TERRA_LEAF_BOX_GROUP; g != 0; --g ) {
+        #pragma unroll
+        for ( int k = 0; k < TERRA_LEAF_BOX_GROUP; ++k )
+            leaf_box_test ( px + TERRA_LEAF_BOX_STRIDE * k, py + TERRA_LEAF_BOX_STRIDE * k, pz + TERRA_LEAF_BOX_STRIDE * k, pm + TERRA_LEAF_BOX_MASK_STRIDE * k, r, sel, leaf_set, c );
+        px += TERRA_LEAF_BOX_STRIDE * TERRA_LEAF_BOX_GROUP; py += TERRA_LEAF_BOX_STRIDE * TERRA_LEAF_BOX_GROUP; pz += TERRA_LEAF_BOX_STRIDE * TERRA_LEAF_BOX_GROUP;
+        pm += TERRA_LEAF_BOX_MASK_STRIDE * TERRA_LEAF_BOX_GROUP;
+    }
+    #pragma clang loop vectorize(disable) interleave(disable) unroll(disable)
+    for ( uint32_t k = T.n_boxes % TERRA_LEAF_BOX_GROUP; k != 0; --k ) {
+        leaf_box_test ( px, py, pz, pm, r, sel, leaf_set, c );
+        px += TERRA_LEAF_BOX_STRIDE; py += TERRA_LEAF_BOX_STRIDE; pz += TERRA_LEAF_BOX_STRIDE; pm += TERRA_LEAF_BOX_MASK_STRIDE;
+    }
+    return leaf_set;
+}
+
 template <int COUNT, int MODE, bool FAST, bool FUSED = false, bool ANYHIT = false>
 TD void traverse_ranked ( const Tracer& T, const Ray& r, const RayState& st, V3 o_perm, Closest& best, Counters& c, uint32_t expected ) {
     const SlabSel sel = slab_sel ( r );
-    int* sp = T.stack; int* lp = nullptr;
     uint32_t leaf_set = 0u;
-    *sp = 0; sp += TERRA_COL;                                          // the root: node 0 = byte offset 0
     PS_WAVE ( c, kPsDrainIter );
-    while ( sp != T.stack ) node_step<COUNT, MODE, FAST, FUSED, true> ( T, r, sel, sp, lp, leaf_set, c );
+    bool flat = false;
+    if constexpr ( COUNT == 0 && FUSED ) flat = T.n_boxes != 0u;     // (launch constant; FUSED: the wave's rays are all tame)
+    if ( flat ) leaf_set = leaf_boxes_flat ( T, r, sel, c );
+    else {
+        int* sp = T.stack; int* lp = nullptr;
+        *sp = 0; sp += TERRA_COL;                                      // the root: node 0 = byte offset 0
+        while ( sp != T.stack ) node_step<COUNT, MODE, FAST, FUSED, true> ( T, r, sel, sp, lp, leaf_set, c );
+    }
     const uint32_t perm = 2u * ( uint32_t ) st.iz + ( uint32_t ) ( st.ix != ( st.iz == 2 ? 0 : st.iz + 1 ) );      // ray_state_init: ix follows iz unless d[iz] < 0 swapped ix / iy
     const float4* copy = T.l_ranked + 3u * T.lds_tris * perm;
     while ( leaf_set != 0u ) {

@@ -80,7 +80,7 @@ __device__ __forceinline__ Tracer unit_tracer ( const DevScene& sc, int* lds ) {
     Tracer T; T.sc = sc; T.l_nodes = nullptr; T.l_tris = nullptr; T.l_props = nullptr; T.l_mats = sc.mats; T.l_lights = sc.lights; T.l_area = sc.tri_area; T.lds_nodes = 0; T.lds_tris = 0;
     T.stack = lds + threadIdx.x; T.leaves = lds + ( sc.max_stack < 1 ? 1 : sc.max_stack ) * 256 + threadIdx.x; T.leaf_cap = TERRA_LEAF_CAP_MAX;
     T.stack_lim = 0; T.spill = nullptr; T.spill_cap = 0;
-    T.stack_cap = sc.max_stack < 1 ? 1 : sc.max_stack; T.faults = nullptr; T.cull = false; T.fused = false; T.ranked = false; T.l_ranked = nullptr;      // unit level: the reference's traversal decision by decision       // (unit kernels are not built with TERRA_CHECK_BOUNDS)
+    T.stack_cap = sc.max_stack < 1 ? 1 : sc.max_stack; T.faults = nullptr; T.cull = false; T.fused = false; T.ranked = false; T.l_ranked = nullptr; T.n_boxes = 0;      // unit level: the reference's traversal decision by decision       // (unit kernels are not built with TERRA_CHECK_BOUNDS)
     return T;
 }
 __global__ __launch_bounds__ ( 256 ) void k_bvh_traverse ( DevScene sc, int n, const float* o, const float* d, int* found, uint32_t* prim, float* point ) {
@@ -114,7 +114,7 @@ __global__ __launch_bounds__ ( 256 ) void k_bvh_traverse_fast ( DevScene sc, int
     RayState s = ray_state_init ( r );
     Counters c = counters_zero();
     Tracer T; T.sc = sc; T.l_nodes = nullptr; T.l_tris = nullptr; T.l_props = nullptr; T.l_mats = sc.mats; T.l_lights = sc.lights; T.l_area = sc.tri_area; T.lds_nodes = 0; T.lds_tris = 0;
-    T.stack = lds_stack + threadIdx.x; T.leaves = T.stack; T.leaf_cap = 0; T.stack_cap = ( int ) lds_entries; T.faults = nullptr; T.cull = false; T.fused = false; T.ranked = false; T.l_ranked = nullptr;
+    T.stack = lds_stack + threadIdx.x; T.leaves = T.stack; T.leaf_cap = 0; T.stack_cap = ( int ) lds_entries; T.faults = nullptr; T.cull = false; T.fused = false; T.ranked = false; T.l_ranked = nullptr; T.n_boxes = 0;
     T.stack_lim = ( uint32_t ) ( uintptr_t ) lds_stack + lds_entries * 1024u; T.spill = spill ? spill + ( size_t ) i * spill_cap : nullptr; T.spill_cap = spill_cap;
     ClosestRanked b = bvh_traverse_fast<1> ( T, r, s, c );
     bool f = b.tri != 0xffffffffu;

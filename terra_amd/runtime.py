@@ -96,6 +96,10 @@ _EXTRA = {
     "terra_amd_set_empty_skip": (C.c_int, [C.c_void_p, C.c_int]),
     "terra_amd_get_empty_skip": (C.c_int, [C.c_void_p]),
     "terra_amd_empty_skip_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    "terra_amd_set_leaf_box_test": (C.c_int, [C.c_void_p, C.c_int]),
+    "terra_amd_get_leaf_box_test": (C.c_int, [C.c_void_p]),
+    "terra_amd_leaf_box_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    "terra_amd_scene_leaf_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "terra_amd_empty_proof": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float] + [C.c_uint32] * 6 + [C.c_void_p, C.c_size_t]),
     "terra_amd_set_sample_split": (C.c_int, [C.c_void_p, C.c_int]),
     "terra_amd_get_sample_split": (C.c_int, [C.c_void_p]),
@@ -165,6 +169,25 @@ def empty_skip_info(lib: api.TerraLib, scene):
     out = (C.c_uint32 * 2)()
     check(lib.empty_skip_info(scene, out), "terra_amd_empty_skip_info")
     return int(out[0]), int(out[1])
+
+
+def leaf_box_info(lib: api.TerraLib, scene):
+    """(used, boxes): whether the scene's most recent launch ran the flat leaf-box test, and the distinct leaf boxes of the committed scene (terra_amd_leaf_box_info)"""
+    out = (C.c_uint32 * 2)()
+    check(lib.leaf_box_info(scene, out), "terra_amd_leaf_box_info")
+    return bool(out[0]), int(out[1])
+
+
+LEAF_BOX_DTYPE = np.dtype([("min", np.float32, (3,)), ("max", np.float32, (3,)), ("mask", np.uint32)])
+
+
+def scene_leaf_boxes(lib: api.TerraLib, scene) -> np.ndarray:
+    """the committed scene's distinct leaf boxes (terra_amd_scene_leaf_boxes), LEAF_BOX_DTYPE records; needs no device"""
+    n = check(lib.scene_leaf_boxes(scene, None, 0), "terra_amd_scene_leaf_boxes")
+    out = np.zeros(n, dtype=LEAF_BOX_DTYPE)
+    if n:
+        check(lib.scene_leaf_boxes(scene, out.ctypes.data, n), "terra_amd_scene_leaf_boxes")
+    return out
 
 
 def last_error() -> str:

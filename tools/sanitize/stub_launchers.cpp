@@ -36,6 +36,7 @@ hipError_t terra_build_fast_tree_device ( const DevTri*, const uint32_t*, uint32
 void terra_plan_fast_tree ( DevRenderParams& p ) { p.lds_mode = 2; p.lds_tris = 0; p.leaf_cap = 0; p.stack_depth = 1; p.lds_nodes = 0; p.spill_cap = 0; p.stack_spill = nullptr; }
 size_t terra_fast_spill_bytes ( const DevRenderParams& ) { return 0; }
 size_t terra_lds_bytes ( const DevRenderParams& ) { return 0; }
+bool   terra_leaf_boxes_fit ( const DevRenderParams&, uint32_t ) { return false; }
 size_t terra_lds_block_limit ( void ) { return 156 * 1024; }
 hipError_t terra_launch_aov ( DevRenderParams, void*, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_launch_denoise ( const void*, const void*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, int, float, int, float, float*, float*, hipStream_t ) { return hipErrorNoDevice; }
