@@ -336,6 +336,11 @@ int terra_amd_scene_leaf_ranks ( HTerraScene scene, uint32_t* out, int capacity 
    (floats) and the mask of the ranks (bit r = the triangle of rank r, above) whose leaf carries that box bit for bit. Entries are ordered by their lowest rank and
    every rank is in exactly one mask. `out` has room for `capacity` entries; returns the entry count (0: no triangle, or more than 32) or a negative status. Needs no device. */
 int terra_amd_scene_leaf_boxes ( HTerraScene scene, void* out, int capacity );
+/* Where a launch stages a table of `n` such boxes (n <= 32) in a block's LDS, in bytes: planes[6 k + 2 a + s] = the (near, far) pair of box k on axis a for a ray whose
+   direction there is positive (s = 0) or negative (s = 1), counted from the first ranked triangle entry; masks[k] = box k's mask, counted from the first staged
+   vertex-property record. Either array may be null. Returns the distance from box 0's pair to box n-1's pair of the same axis and sign -- the largest offset the
+   flat loop's reads carry as an immediate -- or a negative status. Needs no scene and no device. */
+int terra_amd_leaf_box_offsets ( uint32_t n, uint32_t* planes, uint32_t* masks );
 
 /* terra_render() (include/Terra.h:229, src/Terra.c:512-635) on a framebuffer
    that already lives in HBM: d_pixels = float[3]*fb_width*fb_height,

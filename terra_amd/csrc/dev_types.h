@@ -16,6 +16,7 @@
 // not the padded ones (DESIGN.md "Roofline").
 #pragma once
 #include <stdint.h>
+#include <stddef.h>
 #include <hip/hip_vector_types.h>     // float4 (DevRenderParams::partials)
 
 #define TERRA_DEV_MAX_ATTR 8
@@ -109,6 +110,22 @@ struct DevLight {
 // reference tree carry, bit for bit, and the rank bits (1 << DevTri::pad) of those children's triangles
 struct DevLeafBox { float bmin[3], bmax[3]; uint32_t mask; };
 static_assert ( sizeof ( DevLeafBox ) == 28, "DevLeafBox must be 28 bytes" );
+// leaf-box table: where a ranked launch stages it in LDS (traverse_ref.h "Flat leaf-box test")
+#define TERRA_RANKED_ENTRY_BYTES 48                                  // a ranked triangle entry: three 16-byte pieces, the last one c[kz] triangle - -
+#define TERRA_RANKED_PAD_OFFSET 40                                   // ... whose two pad words are its last 8 bytes
+#define TERRA_LEAF_BOX_STRIDE ( 6 * TERRA_RANKED_ENTRY_BYTES )       // a leaf box: the pad words of six consecutive entries (3 axes x 2 signs)
+#define TERRA_LEAF_BOX_MASK_OFFSET 60                                // DevProps::pad in the staged properties of triangle k ...
+#define TERRA_LEAF_BOX_MASK_STRIDE 64                                // ... one DevProps per box
+static_assert ( TERRA_RANKED_PAD_OFFSET == TERRA_RANKED_ENTRY_BYTES - 8 && TERRA_LEAF_BOX_STRIDE == 288, "leaf-box slots = the last two words of the 48-byte ranked entries" );
+static_assert ( offsetof ( DevProps, pad ) == TERRA_LEAF_BOX_MASK_OFFSET && sizeof ( DevProps ) == TERRA_LEAF_BOX_MASK_STRIDE, "leaf-box masks = DevProps::pad of the staged properties" );
+// where the table lies, in bytes: the (near, far) pair of box k on axis a for a ray whose direction there is positive (s = 0) or negative (s = 1), from the first
+// ranked entry (Tracer::l_ranked); box k's mask, from the first staged DevProps (Tracer::l_props). leaf_boxes_flat reads through these, make_tracer's stores are tied
+// to them by static_asserts, terra_amd_leaf_box_offsets (scene_host.cpp) reports them.
+constexpr uint32_t terra_leaf_box_plane_offset ( uint32_t k, uint32_t a, uint32_t s ) { return TERRA_LEAF_BOX_STRIDE * k + TERRA_RANKED_ENTRY_BYTES * ( 2u * a + s ) + TERRA_RANKED_PAD_OFFSET; }
+constexpr uint32_t terra_leaf_box_mask_offset ( uint32_t k ) { return TERRA_LEAF_BOX_MASK_STRIDE * k + TERRA_LEAF_BOX_MASK_OFFSET; }
+#define TERRA_LEAF_BOX_REACH 65535u      // a ds_read's immediate offset is 16 bits: every plane pair of a full table is an immediate away from box 0's
+#define TERRA_LEAF_RANK_MAX 32     // triangles a ranked launch can have: a lane's leaf set is one 32-bit word
+static_assert ( terra_leaf_box_plane_offset ( TERRA_LEAF_RANK_MAX - 1, 2, 1 ) + 8u - terra_leaf_box_plane_offset ( 0, 0, 0 ) <= TERRA_LEAF_BOX_REACH, "a full leaf-box table within the reach of one base register" );
 
 struct DevScene {
     const DevNode*     nodes;

@@ -117,6 +117,9 @@ TD Tracer make_tracer ( const DevScene& sc, float4* lds, uint32_t stack_depth, u
             const int kz = ( int ) ( perm >> 1 ), k1 = kz == 2 ? 0 : kz + 1, k2 = k1 == 2 ? 0 : k1 + 1;
             const int kx = ( perm & 1u ) ? k2 : k1, ky = ( perm & 1u ) ? k1 : k2;
             static_assert ( TERRA_RANKED_ENTRY_BYTES == 3 * sizeof ( float4 ) && TERRA_RANKED_PAD_OFFSET == 2 * sizeof ( float4 ) + 8, "e[2].z / e[2].w below are the entry's pad words (leaf_boxes_flat reads them)" );
+            static_assert ( terra_leaf_box_plane_offset ( 0, 0, 0 ) == 2 * sizeof ( float4 ) + 8 && terra_leaf_box_plane_offset ( 0, 0, 1 ) - terra_leaf_box_plane_offset ( 0, 0, 0 ) == 3 * sizeof ( float4 )
+                            && terra_leaf_box_plane_offset ( 0, 1, 0 ) - terra_leaf_box_plane_offset ( 0, 0, 0 ) == 2 * 3 * sizeof ( float4 ) && terra_leaf_box_plane_offset ( 1, 0, 0 ) - terra_leaf_box_plane_offset ( 0, 0, 0 ) == 6 * 3 * sizeof ( float4 ),
+                            "slot j = 6 k + 2 a + s below is where leaf_boxes_flat reads box k, axis a, sign s" );
             float4* e = lr + 3u * ( perm * lds_tris + t.pad );
             e[0] = make_float4 ( t.a[kx], t.a[ky], t.a[kz], t.b[kx] );
             e[1] = make_float4 ( t.b[ky], t.b[kz], t.c[kx], t.c[ky] );
@@ -130,6 +133,7 @@ TD Tracer make_tracer ( const DevScene& sc, float4* lds, uint32_t stack_depth, u
     for ( uint32_t i = tid; i < 3 * lds_tris; i += TERRA_COL ) lt[i] = gt[i];
     for ( uint32_t i = tid; i < 4 * lds_tris; i += TERRA_COL ) {
         float4 v = gp[i];
+        static_assert ( terra_leaf_box_mask_offset ( 0 ) == 3 * sizeof ( float4 ) + 12 && terra_leaf_box_mask_offset ( 1 ) - terra_leaf_box_mask_offset ( 0 ) == 4 * sizeof ( float4 ), "v.w of every fourth piece below is where leaf_boxes_flat reads a mask" );
         if ( ( i & 3u ) == 3u && ( i >> 2 ) < n_boxes ) v.w = __uint_as_float ( leaf_boxes[i >> 2].mask );      // DevProps::pad of triangle k: the rank mask of leaf box k
         lp[i] = v;
     }

@@ -1326,6 +1326,17 @@ extern "C" int terra_amd_scene_leaf_boxes ( HTerraScene h, void* out, int capaci
     if ( out && capacity >= n && n ) memcpy ( out, s->leaf_boxes.data(), ( size_t ) n * sizeof ( DevLeafBox ) );
     return n;
 }
+// where a ranked launch stages a table of n boxes in LDS (dev_types.h "leaf-box table"): planes[6 k + 2 a + s] = the byte offset of box k's (near, far) pair on axis a for
+// direction sign s, from the first ranked entry; masks[k] = the byte offset of box k's mask, from the first staged DevProps. Returns the largest distance a plane
+// read lies from box 0's slot of the same axis and sign (what the flat loop needs as an immediate), or an error for n above TERRA_LEAF_RANK_MAX. Needs no scene.
+extern "C" int terra_amd_leaf_box_offsets ( uint32_t n, uint32_t* planes, uint32_t* masks ) {
+    if ( n > TERRA_LEAF_RANK_MAX ) return fail ( kTerraAmdErrBadArgument, "terra_amd_leaf_box_offsets: a table has at most %u boxes", ( unsigned ) TERRA_LEAF_RANK_MAX );
+    for ( uint32_t k = 0; k < n; ++k ) {
+        for ( uint32_t as = 0; as < 6u && planes; ++as ) planes[6u * k + as] = terra_leaf_box_plane_offset ( k, as >> 1, as & 1u );
+        if ( masks ) masks[k] = terra_leaf_box_mask_offset ( k );
+    }
+    return n ? ( int ) ( terra_leaf_box_plane_offset ( n - 1u, 0, 0 ) - terra_leaf_box_plane_offset ( 0, 0, 0 ) ) : 0;
+}
 // counters [first, first + n) summed over every replica, each device current around its copy (the primary's last: it stays current)
 static int sum_counters ( Scene* s, size_t first, size_t n, unsigned long long* out ) {
     unsigned long long c[kCtrCount];

@@ -68,21 +68,14 @@ enum { kPsRayIter = 0, kPsNodeIter, kPsLeafIter, kPsShadeIter, kPsCamIter, kPsCa
 // Cornell block (terra_lds_bytes: 31,760 B) at 32,592 B, past the TERRA_LDS_BUDGET that keeps five blocks per CU resident (DESIGN.md 3.1 "Flat leaf-box test" has
 // the arithmetic). It lives in words the ranked layout leaves unused,
 //     the two pad words of the ranked triangle entries (the `- -` above): entry 6 k + 2 a + s (counted through the copies) = box k, axis a:
-//         (min, max) for s = 0, (max, min) for s = 1 -- "both signs", as the staged node: a ray reads (near, far) of an axis with one 8-byte load, picked by
-//         3 x its SlabSel offset (48 x (2 a + s)), box k at the immediate offset 288 k;
+//         (min, max) for s = 0, (max, min) for s = 1 -- "both signs", as the staged node: a ray reads (near, far) of an axis with one 8-byte load from the slot
+//         its direction's sign picks (terra_leaf_box_plane_offset ( 0, a, s ) = 48 x (2 a + s) + 40, formed once per traversal), box k at the immediate offset 288 k;
 //     the pad word of the staged vertex properties of triangle k (DevProps::pad): the rank mask of box k.
 // A scene has at most as many distinct leaf boxes as triangles, so 6 boxes-worth of entries and one mask word per box are always there.
 // -----------------------------------------------------------------------------
-#define TERRA_RANKED_ENTRY_BYTES 48                                  // a ranked triangle entry: three 16-byte pieces, the last one c[kz] triangle - -
-#define TERRA_RANKED_PAD_OFFSET 40                                   // ... whose two pad words are its last 8 bytes
-#define TERRA_LEAF_BOX_STRIDE ( 6 * TERRA_RANKED_ENTRY_BYTES )       // a leaf box: the pad words of six consecutive entries (3 axes x 2 signs)
-#define TERRA_LEAF_BOX_MASK_OFFSET 60                                // DevProps::pad in the staged properties of triangle k ...
-#define TERRA_LEAF_BOX_MASK_STRIDE 64                                // ... one DevProps per box
-static_assert ( TERRA_RANKED_PAD_OFFSET == TERRA_RANKED_ENTRY_BYTES - 8 && TERRA_LEAF_BOX_STRIDE == 288, "leaf-box slots = the last two words of the 48-byte ranked entries" );
-static_assert ( offsetof ( DevProps, pad ) == TERRA_LEAF_BOX_MASK_OFFSET && sizeof ( DevProps ) == TERRA_LEAF_BOX_MASK_STRIDE, "leaf-box masks = DevProps::pad of the staged properties" );
-#define TERRA_LEAF_BOX_GROUP 4     // boxes per trip of the unrolled loop (offsets as immediates); the up to three boxes left over are tested one per trip
+// (the table's constants and byte offsets: dev_types.h "leaf-box table", shared with the host)
+#define TERRA_LEAF_BOX_GROUP 8     // boxes per trip of the unrolled loop (offsets as immediates); four left over are one trip more, the up to three boxes after that are tested one per trip
 #define TERRA_LEAF_CAP_MAX 16
-#define TERRA_LEAF_RANK_MAX 32     // triangles a ranked launch can have: a lane's leaf set is one 32-bit word
 #define TERRA_COL 256              // stride of a stack / leaf-list column: the block's thread count
 #define TERRA_LDS_NODE_BYTES 112   // staged node (see above)
 
@@ -232,36 +225,50 @@ TD void leaf_step ( const Tracer& T, const int* entry, const RayState& st, V3 o_
 // ancestor's fails; by the containment property the commit verifies (a triangle the ray hits lies inside every box built around it as the box
 // test sees it) such a triangle is not hit, so the closest hit, the tie-breaks and the ANYHIT answers are the walk's.
 // (TERRA_PHASE_STATS builds count one node iteration per box tested.)
-TD void leaf_box_test ( const char* px, const char* py, const char* pz, const char* pm, const Ray& r, const SlabSel& sel, uint32_t& leaf_set, Counters& c ) {
+// Addresses. A lane's three plane pairs of box k lie at bx / by / bz + TERRA_LEAF_BOX_STRIDE * k, where b<axis> = the 32-bit LDS address of the table's slot
+// (axis, sign of the ray's direction there) in box 0: terra_leaf_box_plane_offset ( 0, a, s ), formed once per traversal in table units (a select between two
+// constants per axis: no SlabSel offset is scaled). The whole table is within reach of a ds_read's 16-bit immediate from there (TERRA_LEAF_BOX_REACH), so a
+// trip's reads are immediates on one moving base per axis. The bases go through an empty asm statement: it hides from the optimiser that they are "start of the
+// dynamic LDS segment + offset", which it otherwise keeps apart to re-add the segment's start (the constant 0) in front of every read. The masks are wave-uniform:
+// their address is scalar arithmetic, one move into the address register per trip.
+// The 32-bit LDS address of a staged word is the low half of its generic pointer (the shared aperture's base has no low bits; the compiler's own cast to
+// address space 3 takes the same half, and Tracer::stack_lim is formed the same way). The asm statements serve speed only: without them the code is as right
+// and a few instructions longer, and nothing fails -- after a compiler upgrade read the trip counts again (python tools/isa_cost.py --loops: 96 / 50 / 16).
+typedef float PlanePair __attribute__ (( ext_vector_type ( 2 ) ));          // (a built-in vector: the host pass, too, can read one through an LDS pointer)
+typedef const __attribute__ (( address_space ( 3 ) )) PlanePair* LdsPlanes;
+TD void leaf_box_test ( uint32_t bx, uint32_t by, uint32_t bz, const char* pm, const Ray& r, const SlabSel& sel, uint32_t& leaf_set, Counters& c ) {
     PS_WAVE ( c, kPsNodeIter ); PS_LANE ( c, kPsNodeLanes );
-    const float2 ax = *reinterpret_cast<const float2*> ( px ), ay = *reinterpret_cast<const float2*> ( py ), az = *reinterpret_cast<const float2*> ( pz );
+    const PlanePair ax = * ( LdsPlanes ) ( uintptr_t ) bx, ay = * ( LdsPlanes ) ( uintptr_t ) by, az = * ( LdsPlanes ) ( uintptr_t ) bz;
     const uint32_t m = *reinterpret_cast<const uint32_t*> ( pm );          // (read whether or not the box is hit: a select, not a branch around a load)
     float te;
     const bool hit = slab_near_far_fused ( ax.x, ax.y, ay.x, ay.y, az.x, az.y, r, sel.oi, te );
     leaf_set |= hit ? m : 0u;
 }
+// N boxes at immediate offsets from the bases, which then move on to the next box
+template <int N>
+TD void leaf_box_group ( uint32_t& bx, uint32_t& by, uint32_t& bz, const char*& pm, const Ray& r, const SlabSel& sel, uint32_t& leaf_set, Counters& c ) {
+    #pragma unroll
+    for ( int k = 0; k < N; ++k )
+        leaf_box_test ( bx + TERRA_LEAF_BOX_STRIDE * k, by + TERRA_LEAF_BOX_STRIDE * k, bz + TERRA_LEAF_BOX_STRIDE * k, pm + TERRA_LEAF_BOX_MASK_STRIDE * k, r, sel, leaf_set, c );
+    bx += TERRA_LEAF_BOX_STRIDE * N; by += TERRA_LEAF_BOX_STRIDE * N; bz += TERRA_LEAF_BOX_STRIDE * N; pm += TERRA_LEAF_BOX_MASK_STRIDE * N;
+}
 TD uint32_t leaf_boxes_flat ( const Tracer& T, const Ray& r, const SlabSel& sel, Counters& c ) {
-    const char* base = reinterpret_cast<const char*> ( T.l_ranked ) + TERRA_RANKED_PAD_OFFSET;
-    constexpr uint32_t kSel = TERRA_RANKED_ENTRY_BYTES / 16;           // SlabSel offsets are 16 x (2 a + s), the slots of a box TERRA_RANKED_ENTRY_BYTES x (2 a + s)
-    const char* px = base + kSel * sel.x; const char* py = base + kSel * sel.y; const char* pz = base + kSel * sel.z;
-    const char* pm = reinterpret_cast<const char*> ( T.l_props ) + TERRA_LEAF_BOX_MASK_OFFSET;
+    const uint32_t table = ( uint32_t ) ( uintptr_t ) T.l_ranked;
+    constexpr uint32_t kNeg = terra_leaf_box_plane_offset ( 0, 0, 1 ) - terra_leaf_box_plane_offset ( 0, 0, 0 );      // from an axis' (near, far) for a positive direction to the one for a negative
+    uint32_t sx = r.inv.x < 0.f ? kNeg : 0u, sy = r.inv.y < 0.f ? kNeg : 0u, sz = r.inv.z < 0.f ? kNeg : 0u;      // (the signs slab_sel goes by)
+    asm ( "" : "+v" ( sx ), "+v" ( sy ), "+v" ( sz ) );          // (kept a select between two inline constants and one add of a wave-uniform base each)
+    uint32_t bx = table + terra_leaf_box_plane_offset ( 0, 0, 0 ) + sx, by = table + terra_leaf_box_plane_offset ( 0, 1, 0 ) + sy, bz = table + terra_leaf_box_plane_offset ( 0, 2, 0 ) + sz;
+    asm ( "" : "+v" ( bx ), "+v" ( by ), "+v" ( bz ) );
+    const char* pm = reinterpret_cast<const char*> ( T.l_props ) + terra_leaf_box_mask_offset ( 0 );
     uint32_t leaf_set = 0u;
     // one group at a time, as written. Cross-compiled for gfx950 without these pragmas (profiles/leaf_boxes/kernel_resources.md): left to unroll, the loads of
     // several groups are hoisted together and the Simple kernel takes 1,728 B of scratch; vectorised two groups wide, the tests become v_pk_fma_f32 fed by moves
     // (104 B of scratch; build.py on why the build keeps packed arithmetic out). With them: no scratch
     #pragma clang loop vectorize(disable) interleave(disable) unroll(disable)
-    for ( uint32_t g = T.n_boxes / TERRA_LEAF_BOX_GROUP; g != 0; --g ) {
-        #pragma unroll
-        for ( int k = 0; k < TERRA_LEAF_BOX_GROUP; ++k )
-            leaf_box_test ( px + TERRA_LEAF_BOX_STRIDE * k, py + TERRA_LEAF_BOX_STRIDE * k, pz + TERRA_LEAF_BOX_STRIDE * k, pm + TERRA_LEAF_BOX_MASK_STRIDE * k, r, sel, leaf_set, c );
-        px += TERRA_LEAF_BOX_STRIDE * TERRA_LEAF_BOX_GROUP; py += TERRA_LEAF_BOX_STRIDE * TERRA_LEAF_BOX_GROUP; pz += TERRA_LEAF_BOX_STRIDE * TERRA_LEAF_BOX_GROUP;
-        pm += TERRA_LEAF_BOX_MASK_STRIDE * TERRA_LEAF_BOX_GROUP;
-    }
+    for ( uint32_t g = T.n_boxes / TERRA_LEAF_BOX_GROUP; g != 0; --g ) leaf_box_group<TERRA_LEAF_BOX_GROUP> ( bx, by, bz, pm, r, sel, leaf_set, c );
+    if ( T.n_boxes & 4u ) leaf_box_group<4> ( bx, by, bz, pm, r, sel, leaf_set, c );
     #pragma clang loop vectorize(disable) interleave(disable) unroll(disable)
-    for ( uint32_t k = T.n_boxes % TERRA_LEAF_BOX_GROUP; k != 0; --k ) {
-        leaf_box_test ( px, py, pz, pm, r, sel, leaf_set, c );
-        px += TERRA_LEAF_BOX_STRIDE; py += TERRA_LEAF_BOX_STRIDE; pz += TERRA_LEAF_BOX_STRIDE; pm += TERRA_LEAF_BOX_MASK_STRIDE;
-    }
+    for ( uint32_t k = T.n_boxes % 4u; k != 0; --k ) leaf_box_group<1> ( bx, by, bz, pm, r, sel, leaf_set, c );
     return leaf_set;
 }
 

@@ -1,8 +1,18 @@
 """Static cost model of one kernel's ISA (dev tool): per basic block, instructions by issue class and an estimate of SIMD
 cycles from the measured per-class issue rates (profiles/r02_measurements/valu_rates.log: cycles per wave64 instruction at
-2.4 GHz with 4 waves per SIMD). Usage: tools/kernel_resources.sh; python tools/isa_cost.py [mangled-name-substring]"""
+2.4 GHz with 4 waves per SIMD). Usage: tools/kernel_resources.sh; python tools/isa_cost.py [mangled-name-substring]
+    python tools/isa_cost.py --loops [file.s]: of the headline kernel <0,0,1,1>, the VALU instructions by opcode of one trip of the flat leaf-box loop
+(the loop over groups of eight, the block for four boxes left over, the loop over the last up to three) and of the ranked leaf loop that follows it, block
+by block (the compiler's "in Loop: Header=" comments say which blocks a loop has); file.s defaults to what tools/kernel_resources.sh left, any assembly of
+the MODE 1 unit will do. The pieces are found by what they contain -- a loop header with several ds_read2_b64 and v_min3_f32, a block between the two loops
+with several v_min3_f32, a loop header with one ds_read_b64 triple and one v_min3_f32, the next loop header with v_ffbl_b32 -- and each is printed with its
+label and its box count, so a compiler that chooses other instructions shows up as "not found" or as a count that is no multiple of the test's 11.5 per box"""
 import re, sys, collections
 S = "/tmp/terra_isa/render_kernels-hip-amdgcn-amd-amdhsa-gfx950.s"
+LOOPS = len(sys.argv) > 1 and sys.argv[1] == "--loops"
+if LOOPS:
+    S = sys.argv[2] if len(sys.argv) > 2 else S
+    del sys.argv[1:]
 name = sys.argv[1] if len(sys.argv) > 1 else "ILi0ELi0ELi1ELi1E"
 FAST = {"v_add_f32", "v_sub_f32", "v_subrev_f32", "v_mul_f32", "v_mov_b32", "v_accvgpr"}
 MED = {"v_and_b32": 3.3, "v_or_b32": 3.3, "v_xor_b32": 3.4, "v_add_u32": 3.5, "v_sub_u32": 3.5, "v_subrev_u32": 3.5, "v_lshrrev_b32": 2.9, "v_fma_f32": 3.9, "v_fmac_f32": 4.1, "v_not_b32": 3.3}
@@ -15,6 +25,57 @@ def cost(op):
     return 4.2, "slow"
 txt = open(S).read().split("\n")
 start = next(i for i, l in enumerate(txt) if re.match(r"^_Z19terra_render_kernel" + name, l))
+
+
+def loops_report():
+    # blocks in layout order: [label, the loop header its comment names (itself for a header), instructions]
+    blocks = []; cur = None
+    for l in txt[start + 1:]:
+        if "s_endpgm" in l: break
+        m = re.match(r"^(\.LBB\d+_\d+):", l) or re.match(r"^; %bb\.(\d+):", l)
+        if m:
+            lab = m.group(1) if m.group(1).startswith(".") else "bb." + m.group(1)
+            cur = [lab, None, []]; blocks.append(cur)
+            h = re.search(r"in Loop: Header=(BB\d+_\d+)", l)
+            if h: cur[1] = ".L" + h.group(1)
+            elif "Loop Header" in l: cur[1] = lab
+            continue
+        if cur is None: continue
+        if cur[1] is None:               # the comment may stand on the lines after the label
+            h = re.search(r"in Loop: Header=(BB\d+_\d+)", l)
+            if h and l.strip().startswith(";"): cur[1] = ".L" + h.group(1)
+            elif "Loop Header" in l and l.strip().startswith(";"): cur[1] = cur[0]
+        t = l.strip()
+        if t and not t.startswith(";") and not t.startswith("."): cur[2].append(t.split()[0])
+    def loop_of(pred, after=0):
+        for i, b in enumerate(blocks):
+            if i >= after and b[1] == b[0] and pred(b[2]): return i
+        raise SystemExit("loop not found")
+    def report(title, i):
+        head = blocks[i][0]; tot = collections.Counter(); print(title + " (header " + head + ")")
+        for b in blocks:
+            if b[1] != head: continue
+            c = collections.Counter(o.replace("_e32", "").replace("_e64", "") for o in b[2] if o.startswith("v_"))
+            tot.update(c)
+            print(f"  {b[0]:11s} valu {sum(c.values()):3d} lds {sum(o.startswith('ds_') for o in b[2]):2d}  " + " ".join(f"{k}x{v}" for k, v in sorted(c.items())))
+        print(f"  all blocks: valu {sum(tot.values())}  " + " ".join(f"{k}x{v}" for k, v in sorted(tot.items())))
+    boxes = lambda ins: sum(o.startswith("v_min3_f32") for o in ins)
+    g = loop_of(lambda ins: ins.count("ds_read2_b64") >= 2 and boxes(ins) >= 2)
+    report(f"flat leaf-box loop, one trip over a group of {boxes(blocks[g][2])}", g)
+    r = loop_of(lambda ins: "ds_read_b64" in ins and boxes(ins) == 1, g + 1)
+    four = [b for b in blocks[g + 1:r] if b[1] != b[0] and boxes(b[2]) >= 2]
+    if len(four) > 1: raise SystemExit("the block for the boxes left over by the groups: more than one candidate")
+    if not four: print("flat leaf-box loop: no block between the two loops tests boxes (a tree with groups of four has none)")
+    for b in four:
+        c = collections.Counter(o.replace("_e32", "").replace("_e64", "") for o in b[2] if o.startswith("v_"))
+        print(f"flat leaf-box loop, the {boxes(b[2])} boxes left over by the groups (block {b[0]}, not a loop)")
+        print(f"  valu {sum(c.values())}  " + " ".join(f"{k}x{v}" for k, v in sorted(c.items())))
+    report("flat leaf-box loop, one trip over a box left over", r)
+    report("ranked leaf loop after it, one trip (every block, as if every branch were taken)", loop_of(lambda ins: any(o.startswith("v_ffbl_b32") for o in ins), r + 1))
+
+
+if LOOPS:
+    loops_report(); sys.exit(0)
 blocks = []; cur = ["entry", []]; blocks.append(cur)
 for l in txt[start + 1:]:
     if "s_endpgm" in l: break
