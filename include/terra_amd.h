@@ -238,6 +238,15 @@ int  terra_amd_empty_proof ( const float* cam_rot9, const float* cam_pos3, float
 int  terra_amd_set_leaf_box_test ( HTerraScene scene, int on );
 int  terra_amd_get_leaf_box_test ( HTerraScene scene );
 int  terra_amd_leaf_box_info ( HTerraScene scene, uint32_t out[2] );
+/* Pair form (default on). A scene of at most 32 triangles in which every triangle is one half of a fan (a, b, c), (a, c, d) inside one distinct leaf box -- the two
+   triangles of a quad, as in the Cornell box -- has the pair form (terra_amd_scene_leaf_pairs). A ranked launch of such a scene without work counters and without a
+   draw-count buffer then tests the two triangles of a pair in one trip of its leaf loop: the shared vertices are transformed once, the diagonal's edge function is
+   computed once, the division runs once. The image is the same bit for bit (tests/test_leaf_pairs_gpu.py). Independent of the flat leaf-box test. Every other launch
+   keeps one triangle per trip. Out of scope: scenes that mix pairs and single triangles, other shared-edge arrangements, quad scenes of 33-64 triangles.
+   terra_amd_leaf_pair_info: out[0] = 1 when the scene's most recent single-device launch used the pair form, out[1] = the pairs of the committed scene */
+int  terra_amd_set_leaf_pairs ( HTerraScene scene, int on );
+int  terra_amd_get_leaf_pairs ( HTerraScene scene );
+int  terra_amd_leaf_pair_info ( HTerraScene scene, uint32_t out[2] );
 
 /* Environment lighting, off by default. The reference evaluates scene options' environment_map for a ray
    that leaves the scene, multiplies the throughput by it and then drops the result: the line that would
@@ -341,6 +350,13 @@ int terra_amd_scene_leaf_boxes ( HTerraScene scene, void* out, int capacity );
    vertex-property record. Either array may be null. Returns the distance from box 0's pair to box n-1's pair of the same axis and sign -- the largest offset the
    flat loop's reads carry as an immediate -- or a negative status. Needs no scene and no device. */
 int terra_amd_leaf_box_offsets ( uint32_t n, uint32_t* planes, uint32_t* masks );
+/* the committed scene's pair form: 4 words per entry -- the soup indices of T1 = (a, b, c) and T2 = (a, c, d), then their reference visit ranks --, entries ordered by
+   their lowest rank; returns the number of entries (0: no pair form). terra_amd_scene_leaf_pair_masks: per distinct leaf box its mask in entry bits. No device needed. */
+int terra_amd_scene_leaf_pairs ( HTerraScene scene, void* out, int capacity );
+int terra_amd_scene_leaf_pair_masks ( HTerraScene scene, uint32_t* out, int capacity );
+/* where a pair launch of n entries stages its LDS section, byte offsets from the section's start: entries[perm * n + e] (64 bytes each), planes[6 k + 2 a + s]
+   (8 bytes each); returns the section's size in bytes. No scene needed. */
+int terra_amd_leaf_pair_offsets ( uint32_t n, uint32_t* entries, uint32_t* planes );
 
 /* terra_render() (include/Terra.h:229, src/Terra.c:512-635) on a framebuffer
    that already lives in HBM: d_pixels = float[3]*fb_width*fb_height,
@@ -686,6 +702,8 @@ int terra_amd_unit_stream_keys ( uint64_t frame_seed, const uint64_t* pix, const
 int terra_amd_unit_ray_aabb ( int n, const float* origins3, const float* dirs3, const float* boxes6, int* hit, float* tmin, float* tmax );
 /* watertight init+query (src/TerraGeometry.c:98-138,159-260): out8 = u,v,w,depth,px,py,pz,0 */
 int terra_amd_unit_watertight ( int n, const float* origins3, const float* dirs3, const float* tris9, int* hit, float* out8 );
+/* the pair test (watertight_pair) on one fan p0 p1 p2 p3 per ray: hit[2 i + t], depth[2 i + t] for T1 = (p0, p1, p2) (t = 0) and T2 = (p0, p2, p3) (t = 1) */
+int terra_amd_unit_watertight_pair ( int n, const float* origins3, const float* dirs3, const float* quads12, int* hit2, float* depth2 );
 /* Moeller-Trumbore (src/Terra.c:880-922): out4 = t,px,py,pz */
 int terra_amd_unit_moller_trumbore ( int n, const float* origins3, const float* dirs3, const float* tris9, int* hit, float* out4 );
 /* terra_bvh_traverse on the committed scene (src/TerraBVH.c:250-310): prim = obj | tri<<8, point3 */

@@ -26,7 +26,7 @@ __global__ __launch_bounds__ ( 256 ) void terra_aov_kernel ( DevRenderParams p, 
     Tracer T;
     T.sc = p.scene; T.l_nodes = nullptr; T.l_tris = nullptr; T.l_props = nullptr; T.l_ranked = nullptr; T.n_boxes = 0;
     T.l_mats = p.scene.mats; T.l_lights = p.scene.lights; T.l_area = p.scene.tri_area;
-    T.lds_nodes = 0; T.lds_tris = 0; T.ranked = false;
+    T.lds_nodes = 0; T.lds_tris = 0; T.ranked = false; T.pairs = false;
     T.stack = words + tid; T.leaves = words + p.stack_depth * TERRA_COL + tid; T.leaf_cap = ( int ) p.leaf_cap; T.stack_cap = ( int ) p.stack_depth;
     T.stack_lim = ( uint32_t ) ( uintptr_t ) words + p.stack_depth * 1024u;
     T.spill = spill ? spill + ( size_t ) ( blockIdx.x * 256u + tid ) * p.spill_cap : nullptr; T.spill_cap = spill ? p.spill_cap : 0u;

@@ -126,6 +126,28 @@ constexpr uint32_t terra_leaf_box_mask_offset ( uint32_t k ) { return TERRA_LEAF
 #define TERRA_LEAF_BOX_REACH 65535u      // a ds_read's immediate offset is 16 bits: every plane pair of a full table is an immediate away from box 0's
 #define TERRA_LEAF_RANK_MAX 32     // triangles a ranked launch can have: a lane's leaf set is one 32-bit word
 static_assert ( terra_leaf_box_plane_offset ( TERRA_LEAF_RANK_MAX - 1, 2, 1 ) + 8u - terra_leaf_box_plane_offset ( 0, 0, 0 ) <= TERRA_LEAF_BOX_REACH, "a full leaf-box table within the reach of one base register" );
+// pair form of a ranked launch (traverse_ref.h "Pair form"; scene_host.cpp leaf_pair_table): every triangle of the scene is one half of a fan (a, b, c), (a, c, d) inside one
+// distinct leaf box. One entry of the commit's table: the two triangles (soup indices, T1 = (a, b, c) first) and their reference visit ranks
+struct DevLeafPair { uint32_t tri[2]; uint32_t rank[2]; };
+static_assert ( sizeof ( DevLeafPair ) == 16, "DevLeafPair must be 16 bytes" );
+// what DevRenderParams::leaf_pairs points at, in 32-bit words, for a scene of n triangles (n / 2 entries): [n / 2 DevLeafPair] [n words: the entry of soup triangle i]
+// [one word per distinct leaf box: its mask in ENTRY bits (bit e = entry e), the image of DevLeafBox::mask]
+constexpr uint32_t terra_leaf_pair_words_entry_of ( uint32_t n_tris ) { return 2u * n_tris; }
+constexpr uint32_t terra_leaf_pair_words_masks ( uint32_t n_tris ) { return 3u * n_tris; }
+// where a pair launch stages its section in LDS, in place of the ranked entries (Tracer::l_ranked): 6 permuted copies x n / 2 entries x 64 B (p0 p1 p2 p3 in (kx, ky, kz), then
+// the two record keys and two spare words), then the leaf-box table in a part of its own -- 48 B per box, axis major, both signs: box k's (near, far) pair on axis a for
+// direction sign s at 48 k + 8 (2 a + s) -- so that a group of eight boxes is still read at immediate offsets (box 7 at 336 B). The masks stay where the single form has them.
+#define TERRA_PAIR_ENTRY_BYTES 64
+#define TERRA_PAIR_BOX_STRIDE 48
+constexpr uint32_t terra_pair_entry_offset ( uint32_t n_pairs, uint32_t perm, uint32_t e ) { return TERRA_PAIR_ENTRY_BYTES * ( perm * n_pairs + e ); }
+constexpr uint32_t terra_pair_boxes_offset ( uint32_t n_pairs ) { return 6u * TERRA_PAIR_ENTRY_BYTES * n_pairs; }
+constexpr uint32_t terra_pair_box_plane_offset ( uint32_t k, uint32_t a, uint32_t s ) { return TERRA_PAIR_BOX_STRIDE * k + 8u * ( 2u * a + s ); }
+constexpr uint32_t terra_pair_section_bytes ( uint32_t n_pairs ) { return terra_pair_boxes_offset ( n_pairs ) + TERRA_PAIR_BOX_STRIDE * n_pairs; }
+static_assert ( terra_pair_box_plane_offset ( 7, 0, 0 ) == 336 && terra_pair_box_plane_offset ( 0, 2, 1 ) + 8u == TERRA_PAIR_BOX_STRIDE, "a box = six 8-byte plane pairs; a group of eight within 384 bytes" );
+static_assert ( terra_pair_section_bytes ( TERRA_LEAF_RANK_MAX / 2 ) <= 6u * TERRA_RANKED_ENTRY_BYTES * TERRA_LEAF_RANK_MAX && terra_pair_section_bytes ( 1 ) <= 6u * TERRA_RANKED_ENTRY_BYTES * 2u, "the pair section never takes more LDS than the ranked entries it replaces" );
+// a record key of the pair loop: (rank + 1) << 5 | soup triangle -- ordered as the ranks are, 0 = no hit, the triangle in its low five bits
+constexpr uint32_t terra_pair_key ( uint32_t rank, uint32_t tri ) { return ( rank + 1u ) << 5 | tri; }
+static_assert ( TERRA_LEAF_RANK_MAX <= 32, "a pair key keeps the triangle in five bits" );
 
 struct DevScene {
     const DevNode*     nodes;
@@ -259,4 +281,9 @@ struct DevRenderParams {
     // scene's table of distinct leaf boxes (leaf_boxes: n_leaf_boxes entries in the scene blob) and its tame waves test those boxes instead of walking the tree
     const DevLeafBox* leaf_boxes;
     uint32_t n_leaf_boxes;
+    // pair form (traverse_ref.h "Pair form"; terra_amd_set_leaf_pairs): non-null = a ranked launch without work counters of a scene in which every triangle is half of a
+    // fan inside one leaf box stages the pairs (dev_types.h "pair form": the table in the scene blob) and its leaf loop tests both triangles of a pair in one trip.
+    // The table's distance in bytes from scene.tris, inside the same blob; 0 = none. (A 32-bit word in what was padding: the structure keeps its size, so the kernels
+    // that never read it keep their argument offsets.)
+    uint32_t leaf_pairs;
 };

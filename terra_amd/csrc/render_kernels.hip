@@ -65,13 +65,17 @@ TD void wave_flush_counters ( const Counters& c, unsigned long long* g ) {
 #ifndef TERRA_CHECK_SHRINK
 #define TERRA_CHECK_SHRINK 0
 #endif
+// DevRenderParams::leaf_pairs as a pointer (nullptr: the launch has no pair form)
+TD const uint32_t* terra_leaf_pair_table ( const DevRenderParams& p ) {
+    return p.leaf_pairs ? reinterpret_cast<const uint32_t*> ( reinterpret_cast<const char*> ( p.scene.tris ) + p.leaf_pairs ) : nullptr;
+}
 template <int MODE>
 TD Tracer make_tracer ( const DevScene& sc, float4* lds, uint32_t stack_depth, uint32_t leaf_cap, uint32_t lds_nodes, uint32_t lds_tris, bool cull, bool fused, bool ranked,
-                        const DevLeafBox* leaf_boxes, uint32_t n_leaf_boxes ) {
+                        const DevLeafBox* leaf_boxes, uint32_t n_leaf_boxes, const uint32_t* leaf_pairs ) {
     const int tid = threadIdx.x;
     Tracer T;
     T.sc = sc;
-    // [staged nodes][staged triangles][staged properties][materials, lights, areas][ranked copies][stack][leaf list][parked words]  (sizes: terra_lds_bytes)
+    // [staged nodes][staged triangles][staged properties][materials, lights, areas][ranked copies, or the pair section: pair copies + leaf-box table][stack][leaf list][parked words]  (sizes: terra_lds_bytes)
     float4* ln = lds;                                                // byte offset 0: a staged node's address is its stack word
     float4* lt = ln + ( TERRA_LDS_NODE_BYTES / 16 ) * lds_nodes;      // (fast-tree launches stage nothing: lds_nodes == lds_tris == 0)
     float4* lp = lt + 3 * lds_tris;
@@ -83,8 +87,11 @@ TD Tracer make_tracer ( const DevScene& sc, float4* lds, uint32_t stack_depth, u
     float4* lr = reinterpret_cast<float4*> ( la + a_words );            // ranked launches: 6 permuted copies of the triangles in rank order (traverse_ref.h "Ranked launches")
     // flat leaf-box test: the scene's distinct leaf boxes ride in the pad words of the ranked entries and of the staged properties (traverse_ref.h "Flat leaf-box test");
     // the host admits a table only where it has no more boxes than the launch stages triangles (terra_leaf_boxes_fit)
-    const uint32_t n_boxes = ( ranked && cull && fused && leaf_boxes && n_leaf_boxes <= lds_tris ) ? n_leaf_boxes : 0u;
-    int* words = reinterpret_cast<int*> ( lr + ( ranked ? 18u * lds_tris : 0u ) );
+    // pair form (traverse_ref.h "Pair form"): the ranked entries give way to the pair section (dev_types.h "pair form"), which has the leaf-box table in a part of its own
+    const bool pairs = ranked && leaf_pairs != nullptr;
+    const uint32_t n_pairs = lds_tris >> 1;
+    const uint32_t n_boxes = ( ranked && cull && fused && leaf_boxes && n_leaf_boxes <= ( pairs ? n_pairs : lds_tris ) ) ? n_leaf_boxes : 0u;
+    int* words = reinterpret_cast<int*> ( lr + ( ranked ? ( pairs ? terra_pair_section_bytes ( n_pairs ) / 16u : 18u * lds_tris ) : 0u ) );
     T.stack = words + tid;
     T.leaves = words + stack_depth * TERRA_COL + tid;
     T.leaf_cap = ( int ) leaf_cap;
@@ -103,13 +110,39 @@ TD Tracer make_tracer ( const DevScene& sc, float4* lds, uint32_t stack_depth, u
         for ( int a = 0; a < 3; ++a ) { o[2 * a] = make_float4 ( mn0[a], mx0[a], mn1[a], mx1[a] ); o[2 * a + 1] = make_float4 ( mx0[a], mn0[a], mx1[a], mn1[a] ); }
         uint32_t c0 = __float_as_uint ( q3.x ), c1 = __float_as_uint ( q3.y );
         // ranked launches: a leaf child's bit in a ray's leaf set = its triangle's reference visit rank (DevTri::pad); none for an inner child or an empty slot
-        const uint32_t b0 = ( ranked && ( c0 & DEV_CHILD_LEAF ) && c0 != DEV_CHILD_EMPTY ) ? 1u << reinterpret_cast<const DevTri*> ( gt ) [c0 & 0x7fffffffu].pad : 0u;
-        const uint32_t b1 = ( ranked && ( c1 & DEV_CHILD_LEAF ) && c1 != DEV_CHILD_EMPTY ) ? 1u << reinterpret_cast<const DevTri*> ( gt ) [c1 & 0x7fffffffu].pad : 0u;
+        // (pair form: the bit of the triangle's ENTRY)
+        const uint32_t l0 = c0 & 0x7fffffffu, l1 = c1 & 0x7fffffffu;
+        const uint32_t b0 = ( ranked && ( c0 & DEV_CHILD_LEAF ) && c0 != DEV_CHILD_EMPTY ) ? 1u << ( pairs ? leaf_pairs[terra_leaf_pair_words_entry_of ( lds_tris ) + l0] : reinterpret_cast<const DevTri*> ( gt ) [l0].pad ) : 0u;
+        const uint32_t b1 = ( ranked && ( c1 & DEV_CHILD_LEAF ) && c1 != DEV_CHILD_EMPTY ) ? 1u << ( pairs ? leaf_pairs[terra_leaf_pair_words_entry_of ( lds_tris ) + l1] : reinterpret_cast<const DevTri*> ( gt ) [l1].pad ) : 0u;
         if ( ! ( c0 & DEV_CHILD_LEAF ) ) c0 *= TERRA_LDS_NODE_BYTES;       // inner child: byte offset of its staged node
         if ( ! ( c1 & DEV_CHILD_LEAF ) ) c1 *= TERRA_LDS_NODE_BYTES;
         o[6] = make_float4 ( __uint_as_float ( c0 ), __uint_as_float ( c1 ), __uint_as_float ( b0 ), __uint_as_float ( b1 ) );
     }
-    if ( ranked ) {         // copy perm, entry rank: triangle (of that rank) in the axes (kx, ky, kz) of permutation perm = 2 kz + swapped (traverse_ref.h traverse_ranked)
+    if ( pairs ) {          // copy perm, entry e: the pair's four vertices in the axes (kx, ky, kz) of permutation perm, and the record keys of its two triangles
+        const DevTri* gtri = reinterpret_cast<const DevTri*> ( gt );
+        const DevLeafPair* gpair = reinterpret_cast<const DevLeafPair*> ( leaf_pairs );
+        for ( uint32_t i = tid; i < 6u * n_pairs; i += TERRA_COL ) {
+            const uint32_t perm = i / n_pairs, en = i - perm * n_pairs;
+            const DevLeafPair pr = gpair[en];
+            const DevTri& t1 = gtri[pr.tri[0]]; const DevTri& t2 = gtri[pr.tri[1]];          // T1 = (p0, p1, p2), T2 = (p0, p2, p3): p3 = T2's c
+            const int kz = ( int ) ( perm >> 1 ), k1 = kz == 2 ? 0 : kz + 1, k2 = k1 == 2 ? 0 : k1 + 1;
+            const int kx = ( perm & 1u ) ? k2 : k1, ky = ( perm & 1u ) ? k1 : k2;
+            static_assert ( TERRA_PAIR_ENTRY_BYTES == 4 * sizeof ( float4 ), "an entry = the four 16-byte pieces below (traverse_pairs reads them)" );
+            float4* e = lr + terra_pair_entry_offset ( n_pairs, perm, en ) / 16u;
+            e[0] = make_float4 ( t1.a[kx], t1.a[ky], t1.a[kz], t1.b[kx] );
+            e[1] = make_float4 ( t1.b[ky], t1.b[kz], t1.c[kx], t1.c[ky] );
+            e[2] = make_float4 ( t1.c[kz], t2.c[kx], t2.c[ky], t2.c[kz] );
+            e[3] = make_float4 ( __uint_as_float ( terra_pair_key ( pr.rank[0], pr.tri[0] ) ), __uint_as_float ( terra_pair_key ( pr.rank[1], pr.tri[1] ) ), 0.f, 0.f );
+        }
+        // the leaf-box table: box k, axis a: (min, max) for sign 0, (max, min) for sign 1 (terra_pair_box_plane_offset)
+        float2* lb = reinterpret_cast<float2*> ( reinterpret_cast<char*> ( lr ) + terra_pair_boxes_offset ( n_pairs ) );
+        static_assert ( terra_pair_box_plane_offset ( 1, 0, 0 ) == 6 * sizeof ( float2 ) && terra_pair_box_plane_offset ( 0, 1, 1 ) == 3 * sizeof ( float2 ), "slot 6 k + 2 a + s below is where leaf_boxes_flat<true> reads box k, axis a, sign s" );
+        for ( uint32_t i = tid; i < 6u * n_boxes; i += TERRA_COL ) {
+            const uint32_t k = i / 6u, as = i - 6u * k;
+            const float mn = leaf_boxes[k].bmin[as >> 1], mx = leaf_boxes[k].bmax[as >> 1];
+            lb[i] = ( as & 1u ) ? make_float2 ( mx, mn ) : make_float2 ( mn, mx );
+        }
+    } else if ( ranked ) {         // copy perm, entry rank: triangle (of that rank) in the axes (kx, ky, kz) of permutation perm = 2 kz + swapped (traverse_ref.h traverse_ranked)
         const DevTri* gtri = reinterpret_cast<const DevTri*> ( gt );
         for ( uint32_t i = tid; i < 6u * lds_tris; i += TERRA_COL ) {
             const uint32_t perm = i / lds_tris, ti = i - perm * lds_tris;
@@ -134,7 +167,7 @@ TD Tracer make_tracer ( const DevScene& sc, float4* lds, uint32_t stack_depth, u
     for ( uint32_t i = tid; i < 4 * lds_tris; i += TERRA_COL ) {
         float4 v = gp[i];
         static_assert ( terra_leaf_box_mask_offset ( 0 ) == 3 * sizeof ( float4 ) + 12 && terra_leaf_box_mask_offset ( 1 ) - terra_leaf_box_mask_offset ( 0 ) == 4 * sizeof ( float4 ), "v.w of every fourth piece below is where leaf_boxes_flat reads a mask" );
-        if ( ( i & 3u ) == 3u && ( i >> 2 ) < n_boxes ) v.w = __uint_as_float ( leaf_boxes[i >> 2].mask );      // DevProps::pad of triangle k: the rank mask of leaf box k
+        if ( ( i & 3u ) == 3u && ( i >> 2 ) < n_boxes ) v.w = __uint_as_float ( pairs ? leaf_pairs[terra_leaf_pair_words_masks ( lds_tris ) + ( i >> 2 )] : leaf_boxes[i >> 2].mask );      // DevProps::pad of triangle k: the rank mask of leaf box k (pair form: its entry mask)
         lp[i] = v;
     }
     if ( MODE == 1 ) {
@@ -145,7 +178,7 @@ TD Tracer make_tracer ( const DevScene& sc, float4* lds, uint32_t stack_depth, u
     }
     T.l_mats = MODE == 1 ? reinterpret_cast<const DevMaterial*> ( lm ) : sc.mats; T.l_lights = MODE == 1 ? reinterpret_cast<const DevLight*> ( ll ) : sc.lights; T.l_area = MODE == 1 ? reinterpret_cast<const float*> ( la ) : sc.tri_area;
     T.l_nodes = ln; T.l_tris = reinterpret_cast<const float*> ( lt ); T.l_props = lp;
-    T.l_ranked = ranked ? lr : nullptr; T.ranked = ranked;
+    T.l_ranked = ranked ? lr : nullptr; T.ranked = ranked; T.pairs = pairs;
     T.n_boxes = n_boxes;
     T.lds_nodes = lds_nodes; T.lds_tris = lds_tris;
     __syncthreads();
@@ -491,7 +524,7 @@ template <int INTEGRATOR, int COUNT, int MODE, int KINDS>
 __global__ __launch_bounds__ ( 256, TERRA_WAVES_FOR ( INTEGRATOR, KINDS, MODE ) ) void terra_render_kernel ( DevRenderParams p ) {
     extern __shared__ float4 lds_f4[];
     const int tid = threadIdx.x;
-    Tracer T0 = make_tracer<MODE> ( p.scene, lds_f4, p.stack_depth, p.leaf_cap, p.lds_nodes, p.lds_tris, p.leaf_cull != 0, p.fused_slab != 0, p.leaf_rank != 0, p.leaf_boxes, p.n_leaf_boxes );
+    Tracer T0 = make_tracer<MODE> ( p.scene, lds_f4, p.stack_depth, p.leaf_cap, p.lds_nodes, p.lds_tris, p.leaf_cull != 0, p.fused_slab != 0, p.leaf_rank != 0, p.leaf_boxes, p.n_leaf_boxes, terra_leaf_pair_table ( p ) );
     T0.faults = p.counters + kCtrFaults;
     if ( MODE >= 2 && p.stack_spill ) { T0.spill = p.stack_spill + ( size_t ) ( blockIdx.x * 256u + threadIdx.x ) * p.spill_cap; T0.spill_cap = p.spill_cap; }
     const Tracer T = T0;
@@ -790,7 +823,7 @@ static size_t scene_extra_lds_bytes ( uint32_t n_objects, uint32_t n_lights, uin
 }
 size_t terra_lds_bytes ( const DevRenderParams& p ) {
     return ( size_t ) ( p.stack_depth + p.leaf_cap + ( p.lds_mode == 1 ? TERRA_AUX_WORDS_LDS : TERRA_AUX_WORDS ) ) * 1024 + ( size_t ) p.lds_nodes * TERRA_LDS_NODE_BYTES + ( size_t ) p.lds_tris * ( 48 + 64 )
-           + ( p.lds_mode == 1 ? scene_extra_lds_bytes ( p.scene.n_objects, p.scene.n_lights, p.scene.n_tris ) : 0 ) + ( p.lds_mode == 1 && p.leaf_rank ? ( size_t ) p.lds_tris * 6 * 48 : 0 );      // (the leaf-box table of a flat launch rides in pad words of these: no bytes of its own)
+           + ( p.lds_mode == 1 ? scene_extra_lds_bytes ( p.scene.n_objects, p.scene.n_lights, p.scene.n_tris ) : 0 ) + ( p.lds_mode == 1 && p.leaf_rank ? ( p.leaf_pairs ? ( size_t ) terra_pair_section_bytes ( p.lds_tris / 2 ) : ( size_t ) p.lds_tris * 6 * 48 ) : 0 );      // (the leaf-box table of a flat launch rides in pad words of the ranked entries: no bytes of its own; the pair form's section includes its table)
 }
 // fast tree (MODE 2 / 3): nothing is staged. A lane holds at most two leaves (in registers: the one it tests, the next one), so there is no leaf list. The stack: its first TERRA_FAST_STACK_LDS entries
 // in LDS (1 KB per entry and block), the rest -- up to the tree's worst case, which a ray almost never reaches -- in HBM, 4 bytes per entry and resident lane

@@ -301,7 +301,7 @@ struct TreeChoice {
     float reach_margin = 0.f, fast_extra = 0.f, fast_scale = 1.f;
 };
 // The blob: one device allocation per copy of the scene, these sections in this order, 256-byte aligned, then one section per texture (layout_blob)
-enum { kSecNodes, kSecTris, kSecProps, kSecMats, kSecLights, kSecArea, kSecFastBin, kSecFastWide, kSecFastTris, kSecReplay, kSecLeafParent, kSecLeafMask, kSecLeafBoxes, kSecTexDesc, kSecTextures };
+enum { kSecNodes, kSecTris, kSecProps, kSecMats, kSecLights, kSecArea, kSecFastBin, kSecFastWide, kSecFastTris, kSecReplay, kSecLeafParent, kSecLeafMask, kSecLeafBoxes, kSecLeafPairs, kSecTexDesc, kSecTextures };
 struct Section { size_t offset = 0, bytes = 0; const void* host = nullptr; size_t host_bytes = 0; };      // bytes: its room in the blob; host: what the upload copies there
 struct BlobLayout { std::vector<Section> sec; std::vector<DevTexture> tdesc; size_t total = 0; };        // tdesc: the texture descriptors, less their address
 // A stream on one device and a staging frame there (12 B of pixel + 16 B of running sums per pixel), grown to the largest rectangle rendered through it:
@@ -373,6 +373,9 @@ struct Scene {
     int leaf_box_test = 1;              // terra_amd_set_leaf_box_test: ranked fused launches without work counters test the scene's distinct leaf boxes in one uniform loop instead of walking the tree (traverse_ref.h "Flat leaf-box test")
     std::vector<DevLeafBox> leaf_boxes; // the table of the last commit (leaf_box_table; empty: the scene has none), as uploaded in the blob
     std::atomic<uint32_t> flat_last { 0 };      // terra_amd_leaf_box_info: the boxes the most recent launch staged (0: it walked the tree)
+    int leaf_pair_form = 1;             // terra_amd_set_leaf_pairs: ranked launches without work counters of a scene that has the pair form test a quad's two triangles in one trip (traverse_ref.h "Pair form")
+    std::vector<uint32_t> leaf_pairs;   // the pair table of the last commit as uploaded in the blob (leaf_pair_table; empty: the scene has no pair form)
+    std::atomic<uint32_t> pairs_last { 0 };     // terra_amd_leaf_pair_info: 1 when the most recent launch used the pair form
     bool sampler_integration = false;   // terra_amd_set_sampler_integration: the pixel's Halton / stratified sampler feeds the first bounce (a launch parameter)
     std::string commit_error;
     std::atomic<bool> warned_camera { false };      // the per-call fallback (camera outside camera_limit) has been reported on stderr once
@@ -518,6 +521,11 @@ extern "C" int terra_amd_set_leaf_box_test ( HTerraScene h, int on ) {
     S ( h )->leaf_box_test = on; return 0;
 }
 extern "C" int terra_amd_get_leaf_box_test ( HTerraScene h ) { return S ( h )->leaf_box_test; }
+extern "C" int terra_amd_set_leaf_pairs ( HTerraScene h, int on ) {
+    if ( on < 0 || on > 1 ) return fail ( kTerraAmdErrBadArgument, "terra_amd_set_leaf_pairs: 0 (off) or 1 (on)" );
+    S ( h )->leaf_pair_form = on; return 0;
+}
+extern "C" int terra_amd_get_leaf_pairs ( HTerraScene h ) { return S ( h )->leaf_pair_form; }
 // the predicate of empty_proof.h on the host (tests, tools): 1 when the block of pixels [x0, x1) x [y0, y1) is proved empty against n_tris triangles of 9 floats each
 extern "C" int terra_amd_empty_proof ( const float* cam_rot9, const float* cam_pos3, float tan_half_fov, float aspect, float jitter, uint32_t fb_w, uint32_t fb_h,
                                        uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, const float* tris9, size_t n_tris ) {
@@ -688,6 +696,60 @@ static std::vector<DevLeafBox> leaf_box_table ( const std::vector<DevNode>& node
     return table;
 }
 
+// The pair form of a scene (traverse_ref.h "Pair form"): every triangle is in exactly one pair (T1, T2) of two triangles that lie in the same distinct leaf box (the same
+// entry of `boxes`) and form a fan, the vertex order taken as it is: T2.a == T1.a and T2.b == T1.c as 32-bit words -- T1 = (a, b, c), T2 = (a, c, d). (A triangle's
+// vertices are never rotated: det = U + V + W depends on their order.) Which of the two has the lower rank does not matter. Inside a box the triangles are matched by
+// a search over its (at most kPairBoxMax) triangles, the lowest unmatched rank first, so an exactly duplicated quad pairs into two fans. Returns the table as the
+// device reads it (dev_types.h "pair form"): the entries ordered by their lowest rank, the entry of every soup triangle, the boxes' masks in entry bits. Empty: the
+// scene has no pair form (an odd or empty scene, more than TERRA_LEAF_RANK_MAX triangles, a triangle without a partner). Mixed scenes, other shared-edge
+// arrangements and quad scenes of 33-64 triangles are out of scope.
+static bool match_fans ( const std::vector<DevTri>& tris, std::vector<uint32_t>& left, std::vector<DevLeafPair>& out ) {
+    if ( left.empty() ) return true;
+    const uint32_t i = left.front();
+    auto fan = [&] ( uint32_t t1, uint32_t t2 ) { return memcmp ( tris[t2].a, tris[t1].a, 12 ) == 0 && memcmp ( tris[t2].b, tris[t1].c, 12 ) == 0; };
+    for ( size_t k = 1; k < left.size(); ++k ) {
+        const uint32_t j = left[k];
+        for ( int flip = 0; flip < 2; ++flip ) {
+            const uint32_t t1 = flip ? j : i, t2 = flip ? i : j;
+            if ( !fan ( t1, t2 ) ) continue;
+            std::vector<uint32_t> rest;
+            for ( size_t m = 1; m < left.size(); ++m ) if ( m != k ) rest.push_back ( left[m] );
+            out.push_back ( DevLeafPair { { t1, t2 }, { tris[t1].pad, tris[t2].pad } } );
+            if ( match_fans ( tris, rest, out ) ) return true;
+            out.pop_back();
+        }
+    }
+    return false;
+}
+static std::vector<uint32_t> leaf_pair_table ( const std::vector<DevLeafBox>& boxes, const std::vector<DevTri>& tris, size_t ntri ) {
+    const size_t kPairBoxMax = 8;          // (bounds the search: 7 x 5 x 3 matchings at most)
+    std::vector<uint32_t> none;
+    if ( ntri == 0 || ntri > TERRA_LEAF_RANK_MAX || ( ntri & 1 ) || boxes.empty() ) return none;
+    std::vector<uint32_t> tri_of_rank ( ntri, 0u );
+    for ( size_t i = 0; i < ntri; ++i ) { if ( tris[i].pad >= ntri ) return none; tri_of_rank[tris[i].pad] = ( uint32_t ) i; }
+    std::vector<DevLeafPair> pairs; std::vector<uint32_t> box_of_pair;
+    for ( size_t b = 0; b < boxes.size(); ++b ) {
+        std::vector<uint32_t> left;          // the box's triangles by increasing rank
+        for ( uint32_t r = 0; r < ntri; ++r ) if ( boxes[b].mask >> r & 1u ) left.push_back ( tri_of_rank[r] );
+        if ( left.empty() || ( left.size() & 1 ) || left.size() > kPairBoxMax ) return none;
+        if ( !match_fans ( tris, left, pairs ) ) return none;
+        box_of_pair.resize ( pairs.size(), ( uint32_t ) b );
+    }
+    if ( pairs.size() * 2 != ntri ) return none;
+    std::vector<uint32_t> order ( pairs.size() );
+    for ( size_t e = 0; e < order.size(); ++e ) order[e] = ( uint32_t ) e;
+    auto low = [&] ( uint32_t e ) { return std::min ( pairs[e].rank[0], pairs[e].rank[1] ); };
+    std::sort ( order.begin(), order.end(), [&] ( uint32_t x, uint32_t y ) { return low ( x ) < low ( y ); } );
+    std::vector<uint32_t> t ( terra_leaf_pair_words_masks ( ( uint32_t ) ntri ) + boxes.size(), 0u );
+    for ( size_t e = 0; e < order.size(); ++e ) {
+        const DevLeafPair& p = pairs[order[e]];
+        memcpy ( &t[4 * e], &p, sizeof p );
+        t[terra_leaf_pair_words_entry_of ( ( uint32_t ) ntri ) + p.tri[0]] = ( uint32_t ) e; t[terra_leaf_pair_words_entry_of ( ( uint32_t ) ntri ) + p.tri[1]] = ( uint32_t ) e;
+        t[terra_leaf_pair_words_masks ( ( uint32_t ) ntri ) + box_of_pair[order[e]]] |= 1u << e;
+    }
+    return t;
+}
+
 // ---- reachability tables (DevScene::ref_replay / fast_leaf_parent / fast_leaf_mask) -------------------------------------------------------------
 // nodes: the reference tree as the DEVICE holds it (breadth-first numbering, test hook applied); soup_of_fast[k] = soup index of fast triangle k.
 // Level L of fast triangle k = the L-th reference node on the way up from the triangle's leaf; its test is the slab test of the box that node's parent
@@ -807,6 +869,7 @@ struct Flat {
     std::vector<DevMaterial> mats; std::vector<DevTri> tris; std::vector<DevProps> props; std::vector<DevLight> lights; std::vector<float> tri_area;
     std::vector<DevNode> nodes; std::vector<uint32_t> rank;
     std::vector<DevLeafBox> leaf_boxes;      // (commit_scene: made once the tree's boxes are final)
+    std::vector<uint32_t> leaf_pairs;        // (leaf_pair_table, from leaf_boxes)
     std::vector<const TerraTexture*> textures;
     int32_t env_mode = 0, env_tex = -1; float env_color[3] = { 0.f, 0.f, 0.f };
 };
@@ -1048,6 +1111,7 @@ static BlobLayout layout_blob ( const Flat& f, const FastTree& ft, const TreeCho
     L.sec[kSecReplay] = section_of ( ft.reach.replay, n_replay );
     L.sec[kSecLeafParent] = section_of ( ft.reach.leaf_parent, n_reach ); L.sec[kSecLeafMask] = section_of ( ft.reach.leaf_mask, n_reach );
     L.sec[kSecLeafBoxes] = section_of ( f.leaf_boxes, f.leaf_boxes.size() );
+    L.sec[kSecLeafPairs] = section_of ( f.leaf_pairs, f.leaf_pairs.size() );
     layout_textures ( L, f.textures );
     return L;
 }
@@ -1240,6 +1304,9 @@ static int commit_scene ( Scene* s, int device ) {
     // in place of the walk (traverse_ref.h "Flat leaf-box test"). Kept on the host too (terra_amd_scene_leaf_boxes)
     f.leaf_boxes = leaf_box_table ( f.nodes, f.tris, f.ntri );
     s->leaf_boxes = f.leaf_boxes;
+    // ... and, where every triangle is half of a fan inside one of those boxes, the pairs a ranked launch tests in one trip each (terra_amd_scene_leaf_pairs)
+    f.leaf_pairs = leaf_pair_table ( f.leaf_boxes, f.tris, f.ntri );
+    s->leaf_pairs = f.leaf_pairs;
     FastTree ft;
     if ( c.use_fast && !c.fast_on_device ) { if ( int rc = build_fast_tree_host ( s, c, f, ft ) ) return rc; }
     // The automatic mode's fallbacks are correct and 10-20 x slower on scenes of this size (hall: 110 against 2,400 Msamples/s): say so where a client looks, once per commit.
@@ -1325,6 +1392,33 @@ extern "C" int terra_amd_scene_leaf_boxes ( HTerraScene h, void* out, int capaci
     const int n = ( int ) s->leaf_boxes.size();
     if ( out && capacity >= n && n ) memcpy ( out, s->leaf_boxes.data(), ( size_t ) n * sizeof ( DevLeafBox ) );
     return n;
+}
+// the scene's pair form as committed (leaf_pair_table): 4 words per entry -- the soup indices of T1 and T2, their ranks --, entries ordered by their lowest rank.
+// Returns the number of entries, 0 when the scene has no pair form; masks (optional, one word per distinct leaf box, as many as terra_amd_scene_leaf_boxes
+// reports): the boxes' masks in entry bits. Needs no device.
+extern "C" int terra_amd_scene_leaf_pairs ( HTerraScene h, void* out, int capacity ) {
+    Scene* s = S ( h );
+    if ( !s->committed ) return fail ( kTerraAmdErrNotCommitted, "scene not committed" );
+    const int n = s->leaf_pairs.empty() ? 0 : ( int ) ( ( s->leaf_pairs.size() - s->leaf_boxes.size() ) / 6 );          // (4 n + 2 n words, then the masks)
+    if ( out && capacity >= n && n ) memcpy ( out, s->leaf_pairs.data(), ( size_t ) n * sizeof ( DevLeafPair ) );
+    return n;
+}
+extern "C" int terra_amd_scene_leaf_pair_masks ( HTerraScene h, uint32_t* out, int capacity ) {
+    Scene* s = S ( h );
+    if ( !s->committed ) return fail ( kTerraAmdErrNotCommitted, "scene not committed" );
+    if ( s->leaf_pairs.empty() ) return 0;
+    const int n = ( int ) s->leaf_boxes.size();
+    if ( out && capacity >= n ) memcpy ( out, s->leaf_pairs.data() + s->leaf_pairs.size() - ( size_t ) n, ( size_t ) n * sizeof ( uint32_t ) );
+    return n;
+}
+// where a pair launch of n entries stages its section in LDS (dev_types.h "pair form"), byte offsets from the section's start (Tracer::l_ranked): entries[perm * n + e] = entry e
+// of permutation perm (64 bytes each), planes[6 k + 2 a + s] = box k's (near, far) pair on axis a for direction sign s (8 bytes each). Returns the section's size in
+// bytes, or an error for n above TERRA_LEAF_RANK_MAX / 2. Needs no scene.
+extern "C" int terra_amd_leaf_pair_offsets ( uint32_t n, uint32_t* entries, uint32_t* planes ) {
+    if ( n > TERRA_LEAF_RANK_MAX / 2 ) return fail ( kTerraAmdErrBadArgument, "terra_amd_leaf_pair_offsets: a pair section has at most %u entries", ( unsigned ) TERRA_LEAF_RANK_MAX / 2 );
+    for ( uint32_t perm = 0; perm < 6u && entries; ++perm ) for ( uint32_t e = 0; e < n; ++e ) entries[perm * n + e] = terra_pair_entry_offset ( n, perm, e );
+    for ( uint32_t k = 0; k < n && planes; ++k ) for ( uint32_t as = 0; as < 6u; ++as ) planes[6u * k + as] = terra_pair_boxes_offset ( n ) + terra_pair_box_plane_offset ( k, as >> 1, as & 1u );
+    return ( int ) terra_pair_section_bytes ( n );
 }
 // where a ranked launch stages a table of n boxes in LDS (dev_types.h "leaf-box table"): planes[6 k + 2 a + s] = the byte offset of box k's (near, far) pair on axis a for
 // direction sign s, from the first ranked entry; masks[k] = the byte offset of box k's mask, from the first staged DevProps. Returns the largest distance a plane
@@ -1463,6 +1557,10 @@ static int fill_params ( Scene* s, const Scene::Replica& r, const TerraCamera* c
     if ( s->leaf_box_test && r.d_blob && terra_leaf_boxes_fit ( p, ( uint32_t ) s->leaf_boxes.size() ) ) {
         p.leaf_boxes = ( const DevLeafBox* ) ( ( const char* ) r.d_blob + s->blob.sec[kSecLeafBoxes].offset ); p.n_leaf_boxes = ( uint32_t ) s->leaf_boxes.size();
     }
+    // pair form: a ranked launch of a scene that has it (launch_render drops it again for a counting launch); independent of the flat test -- without the table the
+    // launch walks the tree and the staged nodes carry entry bits
+    p.leaf_pairs = 0;
+    if ( s->leaf_pair_form && r.d_blob && !s->leaf_pairs.empty() && p.lds_mode == 1 && p.leaf_rank ) p.leaf_pairs = ( uint32_t ) ( s->blob.sec[kSecLeafPairs].offset - s->blob.sec[kSecTris].offset );      // (both in the blob; scenes of at most 32 triangles: a few KB apart)
     // the azimuth table pays where VALU issue binds (LDS-resident scenes: Cornell Simple 65.8 -> 64.2 ms, Direct 145.2 -> 142.5); the kernels that wait on memory anyway
     // lose by one more dependent load per shaded hit (sphere scene 395 -> 419 ms, hall 282 -> 284; profiles/r03_measurements/ab_sincos_table.log)
 #ifndef TERRA_SINCOS_TABLE_FAST_TREE       // (A/B) the azimuth table for fast-tree launches too
@@ -1534,7 +1632,7 @@ static uint32_t launch_split ( const Scene* s, DevRenderParams& p, uint32_t bloc
 static int launch_render ( Scene* s, DevRenderParams& p, int device, hipStream_t stream, ThreadSlot* slot = nullptr ) {      // device: the (current) device of the launch
     const uint32_t blocks = terra_render_blocks ( p );
     if ( blocks == 0 ) return 0;
-    if ( p.count_level != 0 || p.rand_calls ) { p.leaf_boxes = nullptr; p.n_leaf_boxes = 0; }      // the work counters keep their meaning: counting launches walk the tree
+    if ( p.count_level != 0 || p.rand_calls ) { p.leaf_boxes = nullptr; p.n_leaf_boxes = 0; p.leaf_pairs = 0; }      // the work counters keep their meaning: counting launches walk the tree and test one triangle per trip
     const uint32_t split = launch_split ( s, p, blocks );
     static thread_local uint64_t pool_kept = 0;          // (bit d: done for device d)
     if ( device < 64 && ! ( pool_kept >> device & 1ull ) ) {        // keep freed scratch cached in the device's default pool instead of returning it to the OS at every sync
@@ -1594,7 +1692,7 @@ static int launch_render ( Scene* s, DevRenderParams& p, int device, hipStream_t
     if ( pooled ) ( void ) hipFreeAsync ( scratch, stream );
     else if ( e != hipSuccess ) ( void ) hipMemsetAsync ( scratch, 0, header, stream );       // (a launch that failed half way must not leave a used queue word behind)
     if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "render launch: %s", hipGetErrorString ( e ) );
-    s->flat_last.store ( p.n_leaf_boxes, std::memory_order_relaxed );
+    s->flat_last.store ( p.n_leaf_boxes, std::memory_order_relaxed ); s->pairs_last.store ( p.leaf_pairs ? 1u : 0u, std::memory_order_relaxed );
     s->skip_last_blocks.store ( blocks, std::memory_order_relaxed ); s->skip_last_device.store ( skip ? device : -1, std::memory_order_relaxed );      // (only a launch that was queued whole is reported)
     return 0;
 }
@@ -1639,6 +1737,14 @@ extern "C" int terra_amd_leaf_box_info ( HTerraScene h, uint32_t out[2] ) {
     Scene* s = S ( h );
     if ( !out ) return fail ( kTerraAmdErrBadArgument, "terra_amd_leaf_box_info: null output" );
     out[0] = s->flat_last.load ( std::memory_order_relaxed ) ? 1u : 0u; out[1] = ( uint32_t ) s->leaf_boxes.size();
+    return 0;
+}
+// out[0]: 1 when the scene's most recent single-device launch used the pair form; out[1]: the pairs of the committed scene (0: it has no pair form)
+extern "C" int terra_amd_leaf_pair_info ( HTerraScene h, uint32_t out[2] ) {
+    Scene* s = S ( h );
+    if ( !out ) return fail ( kTerraAmdErrBadArgument, "terra_amd_leaf_pair_info: null output" );
+    out[0] = s->pairs_last.load ( std::memory_order_relaxed );
+    out[1] = s->leaf_pairs.empty() ? 0u : ( uint32_t ) ( ( s->leaf_pairs.size() - s->leaf_boxes.size() ) / 6 );
     return 0;
 }
 extern "C" int terra_amd_synchronize ( void* stream ) {
@@ -2342,6 +2448,12 @@ extern "C" int terra_amd_unit_watertight ( int n, const float* o, const float* d
     Unit u; auto a = u.in ( o, 3 * ( size_t ) n ); auto b = u.in ( d, 3 * ( size_t ) n ); auto c = u.in ( tris, 9 * ( size_t ) n );
     auto h = u.out ( hit, n ); auto q = u.out ( out8, 8 * ( size_t ) n );
     return u.finish ( u.ok ? terra_unit_watertight ( n, a, b, c, h, q ) : hipSuccess );
+}
+extern "C" int terra_amd_unit_watertight_pair ( int n, const float* o, const float* d, const float* quads, int* hit, float* depth ) {
+    if ( need_device() ) return kTerraAmdErrNoDevice;
+    Unit u; auto a = u.in ( o, 3 * ( size_t ) n ); auto b = u.in ( d, 3 * ( size_t ) n ); auto c = u.in ( quads, 12 * ( size_t ) n );
+    auto h = u.out ( hit, 2 * ( size_t ) n ); auto q = u.out ( depth, 2 * ( size_t ) n );
+    return u.finish ( u.ok ? terra_unit_watertight_pair ( n, a, b, c, h, q ) : hipSuccess );
 }
 extern "C" int terra_amd_unit_moller_trumbore ( int n, const float* o, const float* d, const float* tris, int* hit, float* out4 ) {
     if ( need_device() ) return kTerraAmdErrNoDevice;

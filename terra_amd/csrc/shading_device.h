@@ -173,9 +173,13 @@ TD uint32_t scene_raycast_triangle ( const Tracer& T, const Ray& in, Counters& c
         float depth;
         if ( !watertight_permuted ( tri_perm_lds ( T.l_tris + 12 * expected, st ), o_perm, st, depth ) ) return 0xffffffffu;
         Closest best; best.depth = __uint_as_float ( __float_as_uint ( depth + 0.f ) + 1u ); best.tri = 0xffffffffu;      // (depth >= 0; + 0.f: -0 -> +0)
+        // pair form (traverse_ref.h traverse_pairs): the trips are not in rank order, so the record is preset to the expected triangle's own (depth, key) exactly and the
+        // first triangle that beats it in that order answers "another one" (key 0)
+        if ( T.pairs ) { best.depth = depth; best.tri = terra_pair_key ( __float_as_uint ( T.l_tris[12 * expected + 11] ), expected ); }
         if ( TERRA_FUSED_SLAB && T.fused && __all ( ray_is_tame ( r ) ) ) traverse_loops<COUNT, MODE, true, true, true> ( T, r, st, o_perm, best, c, expected );
         else if ( __all ( ray_is_regular ( r ) ) ) traverse_loops<COUNT, MODE, true, false, true> ( T, r, st, o_perm, best, c, expected );
         else traverse_loops<COUNT, MODE, false, false, true> ( T, r, st, o_perm, best, c, expected );
+        if ( T.pairs ) return best.tri != 0u ? expected : 0xffffffffu;
         return best.tri;
     }
     uint32_t tri;

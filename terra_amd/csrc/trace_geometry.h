@@ -202,6 +202,79 @@ TD bool watertight_permuted ( const TriPerm& t, V3 o, const RayState& s, float& 
     return true;
 }
 
+// -----------------------------------------------------------------------------
+// watertight test of a PAIR of triangles that share an edge as a fan does: T1 = (p0, p1, p2), T2 = (p0, p2, p3), components already in the ray's permuted axes.
+// Per triangle the same operations, in the same order, as watertight_permuted -- so the same answer and the same depth bit for bit -- with what the two share done once:
+//   * the four vertices are translated and sheared once;
+//   * the diagonal's edge function: V of T1 = p0.x p2.y - p0.y p2.x, W of T2 = p2.x p0.y - p2.y p0.x -- the same two products (a product does not depend on the order of
+//     its factors) subtracted the other way round, and in round-to-nearest b - a = -(a - b) exactly, up to the sign of a zero: W2 = -V1 whenever V1 != 0;
+//   * the part after the sign test (determinant, depth and its sign, the division) runs once, for the triangle the lane's sign test passed: a ray through a quad
+//     passes at most one of the two except on the diagonal or in a folded pair, and only where some lane of the wave passes both does the part run again, for T2.
+// A triangle with an edge function that is +-0 takes the double-precision fallback, each triangle by its own zero test (V1 = +-0 sends both: W2 is +-0 then). That
+// triangle leaves the shared path and is tested afterwards by watertight_permuted itself, from vertices read AGAIN -- so the rare fallback's registers are not live
+// beside the pair's twelve components; the other triangle of the pair stays on the shared path with its float values untouched.
+// load ( again ): the pair's vertices (again: the second read; the loader hides from the optimiser that it is the same address, which would keep the first copy alive).
+// record ( depth, second ) is called for each triangle hit (second: T2), in no particular order.
+// -----------------------------------------------------------------------------
+struct PairPerm { float p0[3], p1[3], p2[3], p3[3]; };
+TD bool pair_finish ( float U, float V, float W, float Aiz, float Biz, float Ciz, const RayState& s, float& depth_out ) {
+    uint32_t sign = tdm_bits ( U ) & 0x80000000u;
+    float det = U + V + W;
+    if ( det == 0.f ) return false;
+    float Az = s.scalez * Aiz, Bz = s.scalez * Biz, Cz = s.scalez * Ciz;
+    float depth = U * Az + V * Bz + W * Cz;
+    if ( tdm_float ( tdm_bits ( depth ) ^ sign ) < 0.f ) return false;
+    float inv_det = 1.f / det;
+    depth_out = depth * inv_det;
+    return true;
+}
+template <class Load, class Record>
+TD void watertight_pair ( Load&& load, V3 o, const RayState& s, Record&& record ) {
+    bool z1, z2;          // T1 / T2 has an edge function that is +-0
+    {
+        const PairPerm t = load ( false );
+        float P0ix = t.p0[0] - o.x, P0iy = t.p0[1] - o.y, P0iz = t.p0[2] - o.z;
+        float P1ix = t.p1[0] - o.x, P1iy = t.p1[1] - o.y, P1iz = t.p1[2] - o.z;
+        float P2ix = t.p2[0] - o.x, P2iy = t.p2[1] - o.y, P2iz = t.p2[2] - o.z;
+        float P3ix = t.p3[0] - o.x, P3iy = t.p3[1] - o.y, P3iz = t.p3[2] - o.z;
+        float P0x = P0ix - s.shearx * P0iz, P0y = P0iy - s.sheary * P0iz;
+        float P1x = P1ix - s.shearx * P1iz, P1y = P1iy - s.sheary * P1iz;
+        float P2x = P2ix - s.shearx * P2iz, P2y = P2iy - s.sheary * P2iz;
+        float P3x = P3ix - s.shearx * P3iz, P3y = P3iy - s.sheary * P3iz;
+        // T1: A = p0, B = p1, C = p2;  T2: A = p0, B = p2, C = p3
+        float U1 = P2x * P1y - P2y * P1x;
+        float V1 = P0x * P2y - P0y * P2x;
+        float W1 = P1x * P0y - P1y * P0x;
+        float U2 = P3x * P2y - P3y * P2x;
+        float V2 = P0x * P3y - P0y * P3x;
+        float W2 = -V1;
+        z1 = U1 == 0.f || V1 == 0.f || W1 == 0.f;
+        z2 = U2 == 0.f || V2 == 0.f || V1 == 0.f;
+        const bool pass1 = !z1 && ! ( ( ( tdm_bits ( V1 ) ^ tdm_bits ( U1 ) ) | ( tdm_bits ( W1 ) ^ tdm_bits ( U1 ) ) ) & 0x80000000u );
+        const bool pass2 = !z2 && ! ( ( ( tdm_bits ( V2 ) ^ tdm_bits ( U2 ) ) | ( tdm_bits ( W2 ) ^ tdm_bits ( U2 ) ) ) & 0x80000000u );
+        if ( pass1 || pass2 ) {          // the triangle that passed (T1 where both did) through the one copy of the rest
+            float depth;
+            if ( pair_finish ( pass1 ? U1 : U2, pass1 ? V1 : V2, pass1 ? W1 : W2, P0iz, pass1 ? P1iz : P2iz, pass1 ? P2iz : P3iz, s, depth ) ) record ( depth, !pass1 );
+        }
+        if ( __any ( pass1 && pass2 ) ) {          // on the diagonal, or a folded pair: T2 of the lanes that had T1 above
+            float depth;
+            if ( pass1 && pass2 && pair_finish ( U2, V2, W2, P0iz, P2iz, P3iz, s, depth ) ) record ( depth, true );
+        }
+    }
+    if ( z1 ) {
+        const PairPerm t = load ( true );
+        const TriPerm tp = { { t.p0[0], t.p0[1], t.p0[2] }, { t.p1[0], t.p1[1], t.p1[2] }, { t.p2[0], t.p2[1], t.p2[2] } };
+        float depth;
+        if ( watertight_permuted ( tp, o, s, depth ) ) record ( depth, false );
+    }
+    if ( z2 ) {
+        const PairPerm t = load ( true );
+        const TriPerm tp = { { t.p0[0], t.p0[1], t.p0[2] }, { t.p2[0], t.p2[1], t.p2[2] }, { t.p3[0], t.p3[1], t.p3[2] } };
+        float depth;
+        if ( watertight_permuted ( tp, o, s, depth ) ) record ( depth, true );
+    }
+}
+
 TD bool moller_trumbore ( V3 o, V3 d, V3 ta, V3 tb, V3 tc, float& t_out, V3& p_out ) {
     V3 e1 = tb - ta, e2 = tc - ta;
     V3 h = cross ( d, e2 );

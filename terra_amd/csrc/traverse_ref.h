@@ -72,6 +72,15 @@ enum { kPsRayIter = 0, kPsNodeIter, kPsLeafIter, kPsShadeIter, kPsCamIter, kPsCa
 //         its direction's sign picks (terra_leaf_box_plane_offset ( 0, a, s ) = 48 x (2 a + s) + 40, formed once per traversal), box k at the immediate offset 288 k;
 //     the pad word of the staged vertex properties of triangle k (DevProps::pad): the rank mask of box k.
 // A scene has at most as many distinct leaf boxes as triangles, so 6 boxes-worth of entries and one mask word per box are always there.
+//
+// Pair form (DevRenderParams::leaf_pairs: ranked launches without work counters of a scene whose every triangle is one half of a fan (a, b, c), (a, c, d) inside one
+// distinct leaf box -- the two triangles of a quad; scene_host.cpp leaf_pair_table; traverse_pairs). A lane that passes a leaf box tests both of its triangles, so the
+// leaf set is a set of ENTRIES (bit e = pair e, in the staged nodes' bit0 / bit1 and in the leaf-box masks alike) and one trip of the leaf loop tests a pair: the
+// four vertices are transformed once, the diagonal's edge function is computed once, and the determinant / depth / division part runs once for the triangle that
+// passed its sign test (watertight_pair). The ranked entries give way to 6 permuted copies x pairs x 64 B,
+//     entry = p0[kx] p0[ky] p0[kz] p1[kx] | p1[ky] p1[kz] p2[kx] p2[ky] | p2[kz] p3[kx] p3[ky] p3[kz] | key of T1, key of T2, - -     (T1 = p0 p1 p2, T2 = p0 p2 p3),
+// followed by the leaf-box table in a part of its own (dev_types.h "pair form": 48 B per box). A pair tested because only its partner's leaf was reached on a walk is
+// harmless for the reason given under "Flat leaf-box test": a triangle whose box the ray misses is not hit.
 // -----------------------------------------------------------------------------
 // (the table's constants and byte offsets: dev_types.h "leaf-box table", shared with the host)
 #define TERRA_LEAF_BOX_GROUP 8     // boxes per trip of the unrolled loop (offsets as immediates); four left over are one trip more, the up to three boxes after that are tested one per trip
@@ -87,8 +96,8 @@ struct Tracer {
     const DevMaterial* l_mats;  // materials, lights, per-triangle areas: the block's LDS copies in MODE 1, the arrays in HBM otherwise (make_tracer)
     const DevLight*    l_lights;
     const float*       l_area;
-    const float4* l_ranked;    // ranked launches: the 6 permuted copies of the staged triangles, in rank order (see above); nullptr otherwise
-    uint32_t      n_boxes;     // flat leaf-box test: the distinct leaf boxes staged in the pad words of l_ranked / l_props (see above); 0 in every other launch
+    const float4* l_ranked;    // ranked launches: the 6 permuted copies of the staged triangles, in rank order -- pair form: the pair section, 6 copies of the entries then the leaf-box table -- (see above); nullptr otherwise
+    uint32_t      n_boxes;     // flat leaf-box test: the distinct leaf boxes staged -- planes in the pad words of l_ranked (pair form: in the pair section's own part), masks in those of l_props (see above); 0 in every other launch
     uint32_t      lds_nodes, lds_tris;
     int*          stack;       // this thread's column
     int*          leaves;
@@ -109,6 +118,8 @@ struct Tracer {
     bool fused;
     // the leaves a ray meets are collected as a set of ranks in one register instead of a list in LDS (traverse_ranked); launch constant
     bool ranked;
+    // ... and the ranked entries are pairs (see "Pair form" above); launch constant, only ever set in launches without work counters
+    bool pairs;
 };
 
 // -----------------------------------------------------------------------------
@@ -244,20 +255,25 @@ TD void leaf_box_test ( uint32_t bx, uint32_t by, uint32_t bz, const char* pm, c
     const bool hit = slab_near_far_fused ( ax.x, ax.y, ay.x, ay.y, az.x, az.y, r, sel.oi, te );
     leaf_set |= hit ? m : 0u;
 }
-// N boxes at immediate offsets from the bases, which then move on to the next box
-template <int N>
+// N boxes at immediate offsets from the bases, which then move on to the next box. STRIDE: from a box's plane pairs to the next one's, in the form in use
+template <int N, uint32_t STRIDE>
 TD void leaf_box_group ( uint32_t& bx, uint32_t& by, uint32_t& bz, const char*& pm, const Ray& r, const SlabSel& sel, uint32_t& leaf_set, Counters& c ) {
     #pragma unroll
     for ( int k = 0; k < N; ++k )
-        leaf_box_test ( bx + TERRA_LEAF_BOX_STRIDE * k, by + TERRA_LEAF_BOX_STRIDE * k, bz + TERRA_LEAF_BOX_STRIDE * k, pm + TERRA_LEAF_BOX_MASK_STRIDE * k, r, sel, leaf_set, c );
-    bx += TERRA_LEAF_BOX_STRIDE * N; by += TERRA_LEAF_BOX_STRIDE * N; bz += TERRA_LEAF_BOX_STRIDE * N; pm += TERRA_LEAF_BOX_MASK_STRIDE * N;
+        leaf_box_test ( bx + STRIDE * k, by + STRIDE * k, bz + STRIDE * k, pm + TERRA_LEAF_BOX_MASK_STRIDE * k, r, sel, leaf_set, c );
+    bx += STRIDE * N; by += STRIDE * N; bz += STRIDE * N; pm += TERRA_LEAF_BOX_MASK_STRIDE * N;
 }
+// PAIRS: the table lies in the pair section's own part (dev_types.h "pair form") and its masks are in entry bits; otherwise in the pad words of the ranked entries
+template <bool PAIRS>
 TD uint32_t leaf_boxes_flat ( const Tracer& T, const Ray& r, const SlabSel& sel, Counters& c ) {
-    const uint32_t table = ( uint32_t ) ( uintptr_t ) T.l_ranked;
-    constexpr uint32_t kNeg = terra_leaf_box_plane_offset ( 0, 0, 1 ) - terra_leaf_box_plane_offset ( 0, 0, 0 );      // from an axis' (near, far) for a positive direction to the one for a negative
+    constexpr uint32_t kStride = PAIRS ? ( uint32_t ) TERRA_PAIR_BOX_STRIDE : ( uint32_t ) TERRA_LEAF_BOX_STRIDE;
+    constexpr uint32_t kX = PAIRS ? terra_pair_box_plane_offset ( 0, 0, 0 ) : terra_leaf_box_plane_offset ( 0, 0, 0 ), kY = PAIRS ? terra_pair_box_plane_offset ( 0, 1, 0 ) : terra_leaf_box_plane_offset ( 0, 1, 0 ),
+                       kZ = PAIRS ? terra_pair_box_plane_offset ( 0, 2, 0 ) : terra_leaf_box_plane_offset ( 0, 2, 0 );
+    const uint32_t table = ( uint32_t ) ( uintptr_t ) T.l_ranked + ( PAIRS ? terra_pair_boxes_offset ( T.lds_tris >> 1 ) : 0u );
+    constexpr uint32_t kNeg = PAIRS ? terra_pair_box_plane_offset ( 0, 0, 1 ) - terra_pair_box_plane_offset ( 0, 0, 0 ) : terra_leaf_box_plane_offset ( 0, 0, 1 ) - terra_leaf_box_plane_offset ( 0, 0, 0 );      // from an axis' (near, far) for a positive direction to the one for a negative
     uint32_t sx = r.inv.x < 0.f ? kNeg : 0u, sy = r.inv.y < 0.f ? kNeg : 0u, sz = r.inv.z < 0.f ? kNeg : 0u;      // (the signs slab_sel goes by)
     asm ( "" : "+v" ( sx ), "+v" ( sy ), "+v" ( sz ) );          // (kept a select between two inline constants and one add of a wave-uniform base each)
-    uint32_t bx = table + terra_leaf_box_plane_offset ( 0, 0, 0 ) + sx, by = table + terra_leaf_box_plane_offset ( 0, 1, 0 ) + sy, bz = table + terra_leaf_box_plane_offset ( 0, 2, 0 ) + sz;
+    uint32_t bx = table + kX + sx, by = table + kY + sy, bz = table + kZ + sz;
     asm ( "" : "+v" ( bx ), "+v" ( by ), "+v" ( bz ) );
     const char* pm = reinterpret_cast<const char*> ( T.l_props ) + terra_leaf_box_mask_offset ( 0 );
     uint32_t leaf_set = 0u;
@@ -265,21 +281,71 @@ TD uint32_t leaf_boxes_flat ( const Tracer& T, const Ray& r, const SlabSel& sel,
     // several groups are hoisted together and the Simple kernel takes 1,728 B of scratch; vectorised two groups wide, the tests become v_pk_fma_f32 fed by moves
     // (104 B of scratch; build.py on why the build keeps packed arithmetic out). With them: no scratch
     #pragma clang loop vectorize(disable) interleave(disable) unroll(disable)
-    for ( uint32_t g = T.n_boxes / TERRA_LEAF_BOX_GROUP; g != 0; --g ) leaf_box_group<TERRA_LEAF_BOX_GROUP> ( bx, by, bz, pm, r, sel, leaf_set, c );
-    if ( T.n_boxes & 4u ) leaf_box_group<4> ( bx, by, bz, pm, r, sel, leaf_set, c );
+    for ( uint32_t g = T.n_boxes / TERRA_LEAF_BOX_GROUP; g != 0; --g ) leaf_box_group<TERRA_LEAF_BOX_GROUP, kStride> ( bx, by, bz, pm, r, sel, leaf_set, c );
+    if ( T.n_boxes & 4u ) leaf_box_group<4, kStride> ( bx, by, bz, pm, r, sel, leaf_set, c );
     #pragma clang loop vectorize(disable) interleave(disable) unroll(disable)
-    for ( uint32_t k = T.n_boxes % 4u; k != 0; --k ) leaf_box_group<1> ( bx, by, bz, pm, r, sel, leaf_set, c );
+    for ( uint32_t k = T.n_boxes % 4u; k != 0; --k ) leaf_box_group<1, kStride> ( bx, by, bz, pm, r, sel, leaf_set, c );
     return leaf_set;
+}
+
+// The pair form of a ranked traversal (see "Pair form" above). The node part is the ranked one -- the flat loop over the pair section's table, or the walk, whose
+// staged nodes carry entry bits --; the leaf loop walks the set entries, one pair per trip.
+// Record rule. Entry order is not rank order across pairs (the Cornell box has pairs of ranks (2, 4) and (3, 12)), so "first met wins a tie" cannot be left to the
+// order of the trips: the record is the lexicographic minimum of (depth, key), key = terra_pair_key ( rank, triangle ), which is what the reference's order with its
+// strict "<" selects -- among equal depths the triangle met first, i.e. of the lowest rank. The record starts as (FLT_MAX, 0): no key is below 0, so a hit at FLT_MAX
+// is refused as the strict "<" refuses it. ANYHIT: the record is preset to the expected triangle's own (depth, key) (scene_raycast_triangle); the first triangle
+// that beats it comes first in the reference's order too, and ends the loop with key 0 ("another one"); the expected triangle itself never beats its own record.
+template <int COUNT, int MODE, bool FAST, bool FUSED, bool ANYHIT>
+TD void traverse_pairs ( const Tracer& T, const Ray& r, const RayState& st, V3 o_perm, Closest& best, Counters& c ) {
+    const SlabSel sel = slab_sel ( r );
+    uint32_t leaf_set = 0u;
+    PS_WAVE ( c, kPsDrainIter );
+    bool flat = false;
+    if constexpr ( FUSED ) flat = T.n_boxes != 0u;
+    if ( flat ) leaf_set = leaf_boxes_flat<true> ( T, r, sel, c );
+    else {
+        int* sp = T.stack; int* lp = nullptr;
+        *sp = 0; sp += TERRA_COL;
+        while ( sp != T.stack ) node_step<COUNT, MODE, FAST, FUSED, true> ( T, r, sel, sp, lp, leaf_set, c );
+    }
+    const uint32_t perm = 2u * ( uint32_t ) st.iz + ( uint32_t ) ( st.ix != ( st.iz == 2 ? 0 : st.iz + 1 ) );
+    const float4* copy = T.l_ranked + ( TERRA_PAIR_ENTRY_BYTES / 16 ) * ( T.lds_tris >> 1 ) * perm;
+    float depth_best = best.depth; uint32_t key_best = ANYHIT ? best.tri : 0u;          // (ANYHIT: the caller's preset key travels in best.tri; the record itself never moves)
+    bool beaten = false;
+    while ( leaf_set != 0u ) {
+        PS_WAVE ( c, kPsLeafIter ); PS_LANE ( c, kPsLeafLanes );
+        const float4* e = copy + ( TERRA_PAIR_ENTRY_BYTES / 16 ) * ( uint32_t ) __builtin_ctz ( leaf_set );
+        leaf_set &= leaf_set - 1u;
+        const uint2 keys = *reinterpret_cast<const uint2*> ( e + 3 );
+        auto load = [&] ( bool again ) {
+            uint32_t a = ( uint32_t ) ( uintptr_t ) e;
+            if ( again ) asm volatile ( "" : "+v" ( a ) );          // (the second read is a read: see watertight_pair)
+            typedef float Piece __attribute__ (( ext_vector_type ( 4 ) ));          // (a built-in vector, as PlanePair)
+            const __attribute__ (( address_space ( 3 ) )) Piece* q = ( const __attribute__ (( address_space ( 3 ) )) Piece* ) ( uintptr_t ) a;
+            const Piece q0 = q[0], q1 = q[1], q2 = q[2];
+            return PairPerm { { q0.x, q0.y, q0.z }, { q0.w, q1.x, q1.y }, { q1.z, q1.w, q2.x }, { q2.y, q2.z, q2.w } };
+        };
+        watertight_pair ( load, o_perm, st, [&] ( float depth, bool second ) {
+            const uint32_t key = second ? keys.y : keys.x;
+            if ( ( depth < depth_best ) | ( ( depth == depth_best ) & ( key < key_best ) ) ) {
+                if ( ANYHIT ) { beaten = true; leaf_set = 0u; }
+                else { depth_best = depth; key_best = key; }
+            }
+        } );
+    }
+    best.depth = depth_best;
+    best.tri = ANYHIT ? ( beaten ? 0u : key_best ) : ( key_best ? ( key_best & 31u ) : 0xffffffffu );
 }
 
 template <int COUNT, int MODE, bool FAST, bool FUSED = false, bool ANYHIT = false>
 TD void traverse_ranked ( const Tracer& T, const Ray& r, const RayState& st, V3 o_perm, Closest& best, Counters& c, uint32_t expected ) {
+    if constexpr ( COUNT == 0 ) if ( T.pairs ) { traverse_pairs<COUNT, MODE, FAST, FUSED, ANYHIT> ( T, r, st, o_perm, best, c ); return; }      // (launch constant)
     const SlabSel sel = slab_sel ( r );
     uint32_t leaf_set = 0u;
     PS_WAVE ( c, kPsDrainIter );
     bool flat = false;
     if constexpr ( COUNT == 0 && FUSED ) flat = T.n_boxes != 0u;     // (launch constant; FUSED: the wave's rays are all tame)
-    if ( flat ) leaf_set = leaf_boxes_flat ( T, r, sel, c );
+    if ( flat ) leaf_set = leaf_boxes_flat<false> ( T, r, sel, c );
     else {
         int* sp = T.stack; int* lp = nullptr;
         *sp = 0; sp += TERRA_COL;                                      // the root: node 0 = byte offset 0

@@ -62,6 +62,29 @@ hipError_t terra_unit_watertight ( int n, const float* o, const float* d, const 
     return hipGetLastError();
 }
 
+// watertight_pair on one fan per ray: quads = p0 p1 p2 p3 (12 floats); hit[2 i], hit[2 i + 1] and depth[2 i], depth[2 i + 1] for T1 = (p0, p1, p2) and T2 = (p0, p2, p3).
+// Must equal k_watertight run on each triangle, bit for bit (tests/test_leaf_pairs_gpu.py)
+__global__ void k_watertight_pair ( int n, const float* o, const float* d, const float* quads, int* hit, float* depth ) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if ( i >= n ) return;
+    Ray r = make_ray ( v3p ( o + 3 * i ), v3p ( d + 3 * i ) );
+    RayState s = ray_state_init ( r );
+    auto load = [&] ( bool again ) {
+        const float* q = quads + 12 * i;
+        if ( again ) asm volatile ( "" : "+v" ( q ) );
+        const V3 p0 = v3p ( q ), p1 = v3p ( q + 3 ), p2 = v3p ( q + 6 ), p3 = v3p ( q + 9 );
+        return PairPerm { { pick ( p0, s.ix ), pick ( p0, s.iy ), pick ( p0, s.iz ) }, { pick ( p1, s.ix ), pick ( p1, s.iy ), pick ( p1, s.iz ) },
+                          { pick ( p2, s.ix ), pick ( p2, s.iy ), pick ( p2, s.iz ) }, { pick ( p3, s.ix ), pick ( p3, s.iy ), pick ( p3, s.iz ) } };
+    };
+    int h0 = 0, h1 = 0; float d0 = 0.f, d1 = 0.f;
+    watertight_pair ( load, permuted ( r.o, s ), s, [&] ( float dep, bool second ) { if ( second ) { h1 = 1; d1 = dep; } else { h0 = 1; d0 = dep; } } );
+    hit[2 * i] = h0; hit[2 * i + 1] = h1; depth[2 * i] = d0; depth[2 * i + 1] = d1;
+}
+hipError_t terra_unit_watertight_pair ( int n, const float* o, const float* d, const float* quads, int* hit, float* depth ) {
+    hipLaunchKernelGGL ( k_watertight_pair, UNIT_GRID ( n ), 0, 0, n, o, d, quads, hit, depth );
+    return hipGetLastError();
+}
+
 __global__ void k_mt ( int n, const float* o, const float* d, const float* tris, int* hit, float* out4 ) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if ( i >= n ) return;
@@ -80,7 +103,7 @@ __device__ __forceinline__ Tracer unit_tracer ( const DevScene& sc, int* lds ) {
     Tracer T; T.sc = sc; T.l_nodes = nullptr; T.l_tris = nullptr; T.l_props = nullptr; T.l_mats = sc.mats; T.l_lights = sc.lights; T.l_area = sc.tri_area; T.lds_nodes = 0; T.lds_tris = 0;
     T.stack = lds + threadIdx.x; T.leaves = lds + ( sc.max_stack < 1 ? 1 : sc.max_stack ) * 256 + threadIdx.x; T.leaf_cap = TERRA_LEAF_CAP_MAX;
     T.stack_lim = 0; T.spill = nullptr; T.spill_cap = 0;
-    T.stack_cap = sc.max_stack < 1 ? 1 : sc.max_stack; T.faults = nullptr; T.cull = false; T.fused = false; T.ranked = false; T.l_ranked = nullptr; T.n_boxes = 0;      // unit level: the reference's traversal decision by decision       // (unit kernels are not built with TERRA_CHECK_BOUNDS)
+    T.stack_cap = sc.max_stack < 1 ? 1 : sc.max_stack; T.faults = nullptr; T.cull = false; T.fused = false; T.ranked = false; T.pairs = false; T.l_ranked = nullptr; T.n_boxes = 0;      // unit level: the reference's traversal decision by decision       // (unit kernels are not built with TERRA_CHECK_BOUNDS)
     return T;
 }
 __global__ __launch_bounds__ ( 256 ) void k_bvh_traverse ( DevScene sc, int n, const float* o, const float* d, int* found, uint32_t* prim, float* point ) {
@@ -114,7 +137,7 @@ __global__ __launch_bounds__ ( 256 ) void k_bvh_traverse_fast ( DevScene sc, int
     RayState s = ray_state_init ( r );
     Counters c = counters_zero();
     Tracer T; T.sc = sc; T.l_nodes = nullptr; T.l_tris = nullptr; T.l_props = nullptr; T.l_mats = sc.mats; T.l_lights = sc.lights; T.l_area = sc.tri_area; T.lds_nodes = 0; T.lds_tris = 0;
-    T.stack = lds_stack + threadIdx.x; T.leaves = T.stack; T.leaf_cap = 0; T.stack_cap = ( int ) lds_entries; T.faults = nullptr; T.cull = false; T.fused = false; T.ranked = false; T.l_ranked = nullptr; T.n_boxes = 0;
+    T.stack = lds_stack + threadIdx.x; T.leaves = T.stack; T.leaf_cap = 0; T.stack_cap = ( int ) lds_entries; T.faults = nullptr; T.cull = false; T.fused = false; T.ranked = false; T.pairs = false; T.l_ranked = nullptr; T.n_boxes = 0;
     T.stack_lim = ( uint32_t ) ( uintptr_t ) lds_stack + lds_entries * 1024u; T.spill = spill ? spill + ( size_t ) i * spill_cap : nullptr; T.spill_cap = spill_cap;
     ClosestRanked b = bvh_traverse_fast<1> ( T, r, s, c );
     bool f = b.tri != 0xffffffffu;

@@ -100,6 +100,12 @@ _EXTRA = {
     "terra_amd_get_leaf_box_test": (C.c_int, [C.c_void_p]),
     "terra_amd_leaf_box_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "terra_amd_scene_leaf_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "terra_amd_set_leaf_pairs": (C.c_int, [C.c_void_p, C.c_int]),
+    "terra_amd_get_leaf_pairs": (C.c_int, [C.c_void_p]),
+    "terra_amd_leaf_pair_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    "terra_amd_scene_leaf_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "terra_amd_scene_leaf_pair_masks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "terra_amd_leaf_pair_offsets": (C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p]),
     "terra_amd_empty_proof": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float] + [C.c_uint32] * 6 + [C.c_void_p, C.c_size_t]),
     "terra_amd_set_sample_split": (C.c_int, [C.c_void_p, C.c_int]),
     "terra_amd_get_sample_split": (C.c_int, [C.c_void_p]),
@@ -188,6 +194,38 @@ def scene_leaf_boxes(lib: api.TerraLib, scene) -> np.ndarray:
     if n:
         check(lib.scene_leaf_boxes(scene, out.ctypes.data, n), "terra_amd_scene_leaf_boxes")
     return out
+
+
+LEAF_PAIR_DTYPE = np.dtype([("tri", np.uint32, (2,)), ("rank", np.uint32, (2,))])
+
+
+def leaf_pair_info(lib: api.TerraLib, scene):
+    """(used, pairs): whether the scene's most recent launch used the pair form, and the pairs of the committed scene, 0 = no pair form (terra_amd_leaf_pair_info)"""
+    out = (C.c_uint32 * 2)()
+    check(lib.leaf_pair_info(scene, out), "terra_amd_leaf_pair_info")
+    return bool(out[0]), int(out[1])
+
+
+def scene_leaf_pairs(lib: api.TerraLib, scene):
+    """(pairs, masks): the committed scene's pair form (terra_amd_scene_leaf_pairs: LEAF_PAIR_DTYPE records, T1 = (a, b, c) first, ordered by lowest rank; none = no
+    pair form) and its distinct leaf boxes' masks in entry bits (terra_amd_scene_leaf_pair_masks); needs no device"""
+    n = check(lib.scene_leaf_pairs(scene, None, 0), "terra_amd_scene_leaf_pairs")
+    pairs = np.zeros(n, dtype=LEAF_PAIR_DTYPE)
+    if n:
+        check(lib.scene_leaf_pairs(scene, pairs.ctypes.data, n), "terra_amd_scene_leaf_pairs")
+    m = check(lib.scene_leaf_pair_masks(scene, None, 0), "terra_amd_scene_leaf_pair_masks")
+    masks = np.zeros(m, dtype=np.uint32)
+    if m:
+        check(lib.scene_leaf_pair_masks(scene, masks.ctypes.data, m), "terra_amd_scene_leaf_pair_masks")
+    return pairs, masks
+
+
+def leaf_pair_offsets(lib: api.TerraLib, n: int):
+    """(entries[6, n], planes[n, 3, 2], section bytes): where a pair launch of n entries stages its LDS section (terra_amd_leaf_pair_offsets)"""
+    entries = np.zeros((6, n), dtype=np.uint32)
+    planes = np.zeros((n, 3, 2), dtype=np.uint32)
+    size = check(lib.leaf_pair_offsets(n, entries.ctypes.data, planes.ctypes.data), "terra_amd_leaf_pair_offsets")
+    return entries, planes, size
 
 
 def last_error() -> str:

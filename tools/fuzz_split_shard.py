@@ -9,6 +9,7 @@ from terra_amd import api, runtime, scenes
 
 n_iter = int(sys.argv[1]) if len(sys.argv) > 1 else 60
 rs = np.random.RandomState(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
+rs_pairs = np.random.RandomState((int(sys.argv[2]) if len(sys.argv) > 2 else 1) ^ 0x9A125)      # terra_amd_set_leaf_pairs, drawn apart from the cases
 lib = runtime.load()
 makers = [scenes.cornell_box, scenes.cornell_phong, scenes.cornell_textured, lambda w, h, s, **k: scenes.cornell_spheres(w, h, s, **k)]
 bad = 0
@@ -21,6 +22,8 @@ for it in range(n_iter):
     d = mk(W, H, spp, integrator=integ); cam = scenes.camera_of(d)
     a = runtime.DeviceFramebuffer(W, H); b = runtime.DeviceFramebuffer(W, H)
     sa = scenes.build_scene(lib, d); runtime.check(lib.set_sample_split(sa, split))
+    if hasattr(lib, "set_leaf_pairs"):      # the pair form of ranked launches: off or on (the default), drawn per case from a stream of its own, so that a seed's cases stay the ones earlier logs name
+        runtime.check(lib.set_leaf_pairs(sa, int(rs_pairs.randint(2))))
     for rank in range(world):
         runtime.check(lib.render_device_sharded(C.byref(cam), sa, a.pixels.data_ptr(), a.results.data_ptr(), W, H, x, y, w, h, tile, rank, world, None, None))
     d2 = mk(W, H, chunk, integrator=integ); sb = scenes.build_scene(lib, d2)

@@ -16,6 +16,7 @@ n_iter = int(sys.argv[1]) if len(sys.argv) > 1 else 40
 SCALE = float(os.environ.get("FUZZ_SCALE", "1"))       # multiplies every coordinate (scene and camera): the 1e-4 box margins do not scale with it
 EXT = os.environ.get("FUZZ_EXT", "0") == "1"
 rs = np.random.RandomState(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
+rs_pairs = np.random.RandomState((int(sys.argv[2]) if len(sys.argv) > 2 else 1) ^ 0x9A125)      # terra_amd_set_leaf_pairs, drawn apart from the cases
 lib = runtime.load()
 orc = api.TerraLib(os.path.join(ROOT, "oracle", "liboracle.so"), "orc_")
 orc.fn("orc_set_math_mode", None, [C.c_int])(1)
@@ -87,6 +88,8 @@ for it in range(n_iter):
         lib.clear_error()
         # (work counters on or off at random: the counting kernels are separate instantiations, and only the ones WITHOUT counters take the light-sample rays' shortcut)
         s = scenes.build_scene(lib, d, tree_mode=tree, counters=bool(rs.randint(2))); runtime.check(lib.set_sample_split(s, split))
+        if hasattr(lib, "set_leaf_pairs"):      # the pair form of ranked launches (scenes of quads): off or on (the default), from a stream of its own, so that a seed's cases stay the ones earlier logs name
+            runtime.check(lib.set_leaf_pairs(s, int(rs_pairs.randint(2))))
         if hasattr(lib, "set_job_order"):      # the order LDS-resident launches hand their pixel blocks out in: off, the default (off at these frame sizes), or on for launches of any size
             runtime.check(lib.set_job_order(s, int(rs.choice([0, 1, 2, 2]))))
         if tree and hasattr(lib, "debug_fast_stack_lds"):      # the fast tree's stack: sometimes only 1-3 entries in LDS, so that the HBM part is exercised (the image must not change)

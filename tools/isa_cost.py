@@ -3,7 +3,8 @@ cycles from the measured per-class issue rates (profiles/r02_measurements/valu_r
 2.4 GHz with 4 waves per SIMD). Usage: tools/kernel_resources.sh; python tools/isa_cost.py [mangled-name-substring]
     python tools/isa_cost.py --loops [file.s]: of the headline kernel <0,0,1,1>, the VALU instructions by opcode of one trip of the flat leaf-box loop
 (the loop over groups of eight, the block for four boxes left over, the loop over the last up to three) and of the ranked leaf loop that follows it, block
-by block (the compiler's "in Loop: Header=" comments say which blocks a loop has); file.s defaults to what tools/kernel_resources.sh left, any assembly of
+by block, then the same for the pair form (its flat loop over the 48-byte table and the leaf loop that tests a pair per trip, recognised by the four vertices
+its header transforms) (the compiler's "in Loop: Header=" comments say which blocks a loop has); file.s defaults to what tools/kernel_resources.sh left, any assembly of
 the MODE 1 unit will do. The pieces are found by what they contain -- a loop header with several ds_read2_b64 and v_min3_f32, a block between the two loops
 with several v_min3_f32, a loop header with one ds_read_b64 triple and one v_min3_f32, the next loop header with v_ffbl_b32 -- and each is printed with its
 label and its box count, so a compiler that chooses other instructions shows up as "not found" or as a count that is no multiple of the test's 11.5 per box"""
@@ -60,19 +61,32 @@ def loops_report():
             print(f"  {b[0]:11s} valu {sum(c.values()):3d} lds {sum(o.startswith('ds_') for o in b[2]):2d}  " + " ".join(f"{k}x{v}" for k, v in sorted(c.items())))
         print(f"  all blocks: valu {sum(tot.values())}  " + " ".join(f"{k}x{v}" for k, v in sorted(tot.items())))
     boxes = lambda ins: sum(o.startswith("v_min3_f32") for o in ins)
-    g = loop_of(lambda ins: ins.count("ds_read2_b64") >= 2 and boxes(ins) >= 2)
-    report(f"flat leaf-box loop, one trip over a group of {boxes(blocks[g][2])}", g)
-    r = loop_of(lambda ins: "ds_read_b64" in ins and boxes(ins) == 1, g + 1)
-    four = [b for b in blocks[g + 1:r] if b[1] != b[0] and boxes(b[2]) >= 2]
-    if len(four) > 1: raise SystemExit("the block for the boxes left over by the groups: more than one candidate")
-    if not four: print("flat leaf-box loop: no block between the two loops tests boxes (a tree with groups of four has none)")
-    for b in four:
-        c = collections.Counter(o.replace("_e32", "").replace("_e64", "") for o in b[2] if o.startswith("v_"))
-        print(f"flat leaf-box loop, the {boxes(b[2])} boxes left over by the groups (block {b[0]}, not a loop)")
-        print(f"  valu {sum(c.values())}  " + " ".join(f"{k}x{v}" for k, v in sorted(c.items())))
-    report("flat leaf-box loop, one trip over a box left over", r)
-    report("ranked leaf loop after it, one trip (every block, as if every branch were taken)", loop_of(lambda ins: any(o.startswith("v_ffbl_b32") for o in ins), r + 1))
-
+    is_leaf = lambda ins: any(o.startswith("v_ffbl_b32") for o in ins)
+    subs = lambda ins: sum(o.startswith("v_sub_f32") or o.startswith("v_subrev_f32") for o in ins)
+    def flat_and_leaf(after, form, leaf_title):
+        g = loop_of(lambda ins: ins.count("ds_read2_b64") >= 2 and boxes(ins) >= 2, after)
+        report(f"{form}flat leaf-box loop, one trip over a group of {boxes(blocks[g][2])}", g)
+        r = loop_of(lambda ins: "ds_read_b64" in ins and boxes(ins) == 1, g + 1)
+        four = [b for b in blocks[g + 1:r] if b[1] != b[0] and boxes(b[2]) >= 2]
+        if len(four) > 1: raise SystemExit("the block for the boxes left over by the groups: more than one candidate")
+        if not four: print("flat leaf-box loop: no block between the two loops tests boxes (a tree with groups of four has none)")
+        for b in four:
+            c = collections.Counter(o.replace("_e32", "").replace("_e64", "") for o in b[2] if o.startswith("v_"))
+            print(f"{form}flat leaf-box loop, the {boxes(b[2])} boxes left over by the groups (block {b[0]}, not a loop)")
+            print(f"  valu {sum(c.values())}  " + " ".join(f"{k}x{v}" for k, v in sorted(c.items())))
+        report(f"{form}flat leaf-box loop, one trip over a box left over", r)
+        f = loop_of(is_leaf, r + 1)
+        report(leaf_title, f)
+        return f
+    # the single form: the first flat loop of the kernel and the ranked leaf loop after it (one triangle per trip: 18 v_sub_f32 in its header)
+    f = flat_and_leaf(0, "", "ranked leaf loop after it, one trip (every block, as if every branch were taken)")
+    # the pair form (traverse_pairs): the flat loop whose leaf loop's header transforms four vertices (25 v_sub_f32: 12 + 8 + the 5 edge functions). Its blocks:
+    # the header = the shared path to the two zero tests; sign tests and selects; determinant / depth / division, once and (behind a wave-level branch) a second
+    # time for T2; the record update; then the two fallback copies of the single test, each with its double-precision block
+    groups = [i for i, b in enumerate(blocks) if b[1] == b[0] and b[2].count("ds_read2_b64") >= 2 and boxes(b[2]) >= 2]
+    pair = [g for g in groups if subs(blocks[loop_of(is_leaf, g + 1)][2]) >= 22]
+    if not pair: print("pair form: no flat loop whose leaf loop transforms four vertices (a tree without the pair form has none)"); return
+    flat_and_leaf(pair[0], "pair form: ", "pair form: leaf loop, one trip over a PAIR (every block, as if every branch were taken; the last blocks are the two fallback copies of the single test)")
 
 if LOOPS:
     loops_report(); sys.exit(0)

@@ -18,6 +18,7 @@ hipError_t terra_unit_pcg ( const uint32_t*, int, int, float* ) { return hipErro
 hipError_t terra_unit_stream_keys ( uint64_t, const uint64_t*, const uint64_t*, int, uint64_t* ) { return hipErrorNoDevice; }
 hipError_t terra_unit_ray_aabb ( int, const float*, const float*, const float*, int*, float*, float* ) { return hipErrorNoDevice; }
 hipError_t terra_unit_watertight ( int, const float*, const float*, const float*, int*, float* ) { return hipErrorNoDevice; }
+hipError_t terra_unit_watertight_pair ( int, const float*, const float*, const float*, int*, float* ) { return hipErrorNoDevice; }
 hipError_t terra_unit_moller_trumbore ( int, const float*, const float*, const float*, int*, float* ) { return hipErrorNoDevice; }
 hipError_t terra_unit_bvh_traverse ( const DevScene&, int, const float*, const float*, int*, uint32_t*, float* ) { return hipErrorNoDevice; }
 hipError_t terra_unit_raycast ( const DevScene&, int, const float*, const float*, int*, int*, float*, float* ) { return hipErrorNoDevice; }
