@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include "trace_device.h"
 #include "kernels.h"
+#include "launch_plan.h"
 
 struct DevAov { float albedo[3]; float coverage; float normal[3]; float depth; int samples; int reserved[3]; };      // TerraAmdAovResult
 static_assert ( sizeof ( DevAov ) == 48, "DevAov must be 48 bytes" );
@@ -23,14 +24,8 @@ __global__ __launch_bounds__ ( 256 ) void terra_aov_kernel ( DevRenderParams p, 
     const uint32_t tid = threadIdx.x;
     float4* fold = lds_f4;
     int* words = reinterpret_cast<int*> ( lds_f4 + 512 );
-    Tracer T;
-    T.sc = p.scene; T.l_nodes = nullptr; T.l_tris = nullptr; T.l_props = nullptr; T.l_ranked = nullptr; T.n_boxes = 0;
-    T.l_mats = p.scene.mats; T.l_lights = p.scene.lights; T.l_area = p.scene.tri_area;
-    T.lds_nodes = 0; T.lds_tris = 0; T.ranked = false; T.pairs = false;
-    T.stack = words + tid; T.leaves = words + p.stack_depth * TERRA_COL + tid; T.leaf_cap = ( int ) p.leaf_cap; T.stack_cap = ( int ) p.stack_depth;
-    T.stack_lim = ( uint32_t ) ( uintptr_t ) words + p.stack_depth * 1024u;
-    T.spill = spill ? spill + ( size_t ) ( blockIdx.x * 256u + tid ) * p.spill_cap : nullptr; T.spill_cap = spill ? p.spill_cap : 0u;
-    T.faults = nullptr; T.cull = p.leaf_cull != 0; T.fused = false;
+    Tracer T = unstaged_tracer ( p.scene, words, p.stack_depth, p.leaf_cap, spill, p.spill_cap );
+    T.cull = p.leaf_cull != 0;
     const V3 cam_pos = v3 ( p.cam_pos[0], p.cam_pos[1], p.cam_pos[2] );
     const uint32_t ppb_log2 = 8u - p.split_log2, ppb = 1u << ppb_log2;          // pixels per block
     const uint32_t chunk = tid >> ppb_log2, k = tid & ( ppb - 1u );
@@ -84,24 +79,20 @@ hipError_t terra_launch_aov ( DevRenderParams p, void* aov, hipStream_t stream )
     const uint64_t vblocks = ( uint64_t ) blocks_x * blocks_y * p.split;
     if ( vblocks == 0 ) return hipSuccess;
     if ( vblocks >= ( 1ull << 32 ) || p.split > 256u || ( 1u << p.split_log2 ) != p.split ) return hipErrorInvalidValue;
-    int dev = 0, cus = 0; ( void ) hipGetDevice ( &dev );
-    if ( hipDeviceGetAttribute ( &cus, hipDeviceAttributeMultiprocessorCount, dev ) != hipSuccess || cus < 1 ) { ( void ) hipGetLastError(); cus = 256; }
-    const uint32_t grid = ( uint32_t ) ( vblocks < ( uint64_t ) cus * TERRA_AOV_MAX_BLOCKS_PER_CU ? vblocks : ( uint64_t ) cus * TERRA_AOV_MAX_BLOCKS_PER_CU );
-    // the traversal the render call takes (fill_params): the fast tree (MODE 2, or 3 with the reachability replay) or the reference tree read from global memory --
+    const uint64_t cap = ( uint64_t ) terra_cu_count() * TERRA_AOV_MAX_BLOCKS_PER_CU;
+    const uint32_t grid = ( uint32_t ) ( vblocks < cap ? vblocks : cap );
+    // the traversal the render call takes (fill_params): the fast tree (MODE 2, or 3 with the reachability replay; its stack as launch_plan.h terra_plan_fast_tree
+    // made it) or the reference tree read from global memory (its leaf list: terra_unstaged_leaf_cap) --
     // an LDS-resident scene's reference tree with the leaf-box cull answers with the same closest hit whether it is staged or not, so nothing is staged here
     int mode = 0;
     if ( p.lds_mode == 2 ) { mode = p.scene.reach ? 3 : 2; }
-    else {
-        p.stack_depth = p.scene.max_stack < 1 ? 1u : ( uint32_t ) p.scene.max_stack;
-        p.leaf_cap = TERRA_LEAF_CAP_MAX; p.spill_cap = 0;
-        while ( p.leaf_cap > 4 && ( size_t ) ( p.stack_depth + p.leaf_cap ) * 1024 + TERRA_AOV_FOLD_BYTES > ( size_t ) 64 * 1024 ) --p.leaf_cap;
-    }
+    else { p.stack_depth = p.scene.max_stack < 1 ? 1u : ( uint32_t ) p.scene.max_stack; p.leaf_cap = terra_unstaged_leaf_cap ( p.stack_depth, TERRA_AOV_FOLD_BYTES ); p.spill_cap = 0; }
     const size_t lds = ( size_t ) ( p.stack_depth + ( mode == 0 ? p.leaf_cap : 0u ) ) * 1024 + TERRA_AOV_FOLD_BYTES;
     if ( lds > terra_lds_block_limit() ) return hipErrorInvalidValue;
     const void* fn = mode == 0 ? reinterpret_cast<const void*> ( terra_aov_kernel<0> ) : mode == 2 ? reinterpret_cast<const void*> ( terra_aov_kernel<2> ) : reinterpret_cast<const void*> ( terra_aov_kernel<3> );
     if ( lds > ( size_t ) 64 * 1024 ) { const hipError_t e = hipFuncSetAttribute ( fn, hipFuncAttributeMaxDynamicSharedMemorySize, ( int ) lds ); if ( e != hipSuccess ) return e; }
     uint32_t* spill = nullptr;
-    const size_t spill_bytes = mode != 0 && p.spill_cap ? ( size_t ) grid * 256 * p.spill_cap * sizeof ( uint32_t ) : 0;
+    const size_t spill_bytes = mode != 0 ? terra_spill_bytes ( grid, p.spill_cap ) : 0;
     if ( spill_bytes ) { const hipError_t e = hipMallocAsync ( ( void** ) &spill, spill_bytes, stream ); if ( e != hipSuccess ) return e; }
     float4* out = reinterpret_cast<float4*> ( aov );
     if ( mode == 0 ) hipLaunchKernelGGL ( terra_aov_kernel<0>, dim3 ( grid ), dim3 ( 256 ), lds, stream, p, out, spill, ( uint32_t ) vblocks, blocks_x );

@@ -148,6 +148,39 @@ static_assert ( terra_pair_section_bytes ( TERRA_LEAF_RANK_MAX / 2 ) <= 6u * TER
 // a record key of the pair loop: (rank + 1) << 5 | soup triangle -- ordered as the ranks are, 0 = no hit, the triangle in its low five bits
 constexpr uint32_t terra_pair_key ( uint32_t rank, uint32_t tri ) { return ( rank + 1u ) << 5 | tri; }
 static_assert ( TERRA_LEAF_RANK_MAX <= 32, "a pair key keeps the triangle in five bits" );
+// launch plan: the constants both the host's plan (launch_plan.h) and the device code read
+#define TERRA_LEAF_CAP_MAX 16
+#define TERRA_COL 256              // stride of a stack / leaf-list column: the block's thread count
+#define TERRA_LDS_NODE_BYTES 112   // staged node (traverse_ref.h "Staged node")
+// per-thread words parked in LDS between uses (indexed [word][thread] like the stack): the radiance sum of the lane's
+// current job (touched once per path), the job's number and the lane's draw count when the job started (read at its end), and a row
+// that holds each wave's pool of claimed jobs (render_kernels.hip "jobs")
+#define TERRA_AUX_WORDS 6        // rows every launch has (acc x 3, job, draw count, wave pools)
+#define TERRA_AUX_WORDS_LDS 9    // ... plus, on LDS-resident scenes (lds_mode 1), the path radiance Lo x 3 (TERRA_LO_IN_LDS)
+#ifndef TERRA_JOB_STREAM_TABLE      // the jobs' random streams keyed by a kernel of their own ahead of the render (DevRenderParams::job_streams): 0 = by the lane that takes the job
+#define TERRA_JOB_STREAM_TABLE 1
+#endif
+#ifndef TERRA_FAST_STACK_LDS     // entries of a fast-tree launch's stack kept in LDS, the rest in HBM (launch_plan.h terra_plan_fast_tree)
+#define TERRA_FAST_STACK_LDS 16
+#endif
+#ifndef TERRA_LDS_CU_KB
+#define TERRA_LDS_CU_KB 158
+#endif
+#ifndef TERRA_LEAF_CAP_MIN       // smallest leaf list worth an extra resident block (with the decoupled loop, hall: 5 blocks x 6 entries
+#define TERRA_LEAF_CAP_MIN 6     // 391 ms vs 4 blocks x 14 entries 400 ms, Direct 473 vs 487 ms; profiles/r01_measurements/ab_lc*.log)
+#endif
+#ifndef TERRA_LDS_BUDGET          // per block, so that FIVE blocks stay resident per CU: a CU does not hand out all of its 160 KB -- 5 x 31,632 B fit, 5 x 32,656 B
+#define TERRA_LDS_BUDGET ( TERRA_LDS_CU_KB * 1024 / 5 )      // do not (measured: 4.57 -> 3.67 waves per SIMD and 65.6 -> 74.4 ms on the Cornell frame, profiles/r03_measurements/lds_cliff.log)
+#endif
+#ifndef TERRA_LEAF_CAP_RESIDENT_MIN
+#define TERRA_LEAF_CAP_RESIDENT_MIN 8
+#endif
+#ifndef TERRA_LDS_BLOCK_MAX_KB      // the most dynamic LDS one block may opt in to (a CU's 160 KB less what the runtime keeps)
+#define TERRA_LDS_BLOCK_MAX_KB 156
+#endif
+#ifndef TERRA_JOB_ORDER_MIN_BLOCKS
+#define TERRA_JOB_ORDER_MIN_BLOCKS 256
+#endif
 
 struct DevScene {
     const DevNode*     nodes;
@@ -257,7 +290,7 @@ struct DevRenderParams {
     void*    results;               // {float acc[3]; int samples} per pixel
     uint32_t* rand_calls;           // optional
     unsigned long long* counters;   // kCtrCount entries
-    // LDS plan of a block (host decides, kernel obeys): stack_depth stack entries per thread,
+    // LDS plan of a block (host decides -- launch_plan.h --, kernel obeys): stack_depth stack entries per thread,
     // lds_nodes nodes (breadth-first prefix) and lds_tris triangles (+ their vertex properties)
     // staged; leaf_cap deferred-leaf entries per thread; lds_mode 0 = nothing staged, 1 = whole scene
     uint32_t stack_depth, leaf_cap, lds_nodes, lds_tris;

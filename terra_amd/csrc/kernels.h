@@ -1,29 +1,17 @@
-// kernels.h -- launchers implemented in the .hip files, called by the host side.
+// kernels.h -- launchers implemented in the .hip files, called by the host side. (How a launch is laid out -- LDS, spill, job scratch, blocks: launch_plan.h.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include "dev_types.h"
 
 hipError_t terra_launch_render ( const DevRenderParams& p, hipStream_t stream );
-hipError_t terra_launch_job_streams ( const DevRenderParams& p, hipStream_t stream );      // before terra_launch_render: DevRenderParams::job_streams
-size_t terra_block_order_bytes ( const DevRenderParams& p, bool small_too );        // scratch of the job order (class + order words per pixel block); 0: the launch keeps the order of the numbering (p.job_blocks, p.lds_mode set); small_too: also below TERRA_JOB_ORDER_MIN_BLOCKS
-uint32_t   terra_job_order_min_blocks ( void );                     // launches of fewer pixel blocks keep the numbering's order (unless terra_amd_set_job_order(scene, 2))
+hipError_t terra_launch_job_streams ( const DevRenderParams& p, hipStream_t stream );      // before terra_launch_render: DevRenderParams::job_streams (none where terra_job_streams_bytes is 0)
 hipError_t terra_launch_block_order ( const DevRenderParams& p, uint32_t* cls, hipStream_t stream );      // before terra_launch_job_streams: fills p.block_order (= cls + blocks)
-size_t terra_job_streams_bytes ( const DevRenderParams& p );        // 0: this launch keys its streams in the render kernel (p.lds_mode, p.job_blocks set)
 // (render_kernels.hip is compiled as several translation units, one per template MODE: 0 reference tree from global memory, 1 LDS-resident, 2 fast tree, 3 fast tree + reachability replay)
 hipError_t terra_launch_render_mode0 ( const DevRenderParams& p, size_t lds, hipStream_t stream );
 hipError_t terra_launch_render_mode1 ( const DevRenderParams& p, size_t lds, hipStream_t stream );
 hipError_t terra_launch_render_mode2 ( const DevRenderParams& p, size_t lds, hipStream_t stream );
 hipError_t terra_launch_render_mode3 ( const DevRenderParams& p, size_t lds, hipStream_t stream );
-bool       terra_render_wants_queue ( const DevRenderParams& p );   // the launch's loop gains from the persistent grid + job queue (render_kernels.hip "jobs")
-uint32_t   terra_render_blocks ( const DevRenderParams& p );   // 256-thread blocks of one chunk (own tiles x blocks per tile)
 hipError_t terra_launch_resolve ( const DevRenderParams& p, hipStream_t stream );   // second kernel of a split render (p.split > 1)
-bool       terra_scene_fits_lds ( uint32_t n_nodes, uint32_t n_tris, int max_stack, uint32_t n_objects, uint32_t n_lights );   // whole scene staged per block (the small-scene kernels)
-void       terra_plan_lds ( DevRenderParams& p );     // fills stack_depth / lds_nodes / lds_tris / lds_mode
-size_t     terra_lds_bytes ( const DevRenderParams& p );   // dynamic LDS per block of the planned launch
-bool       terra_leaf_boxes_fit ( const DevRenderParams& p, uint32_t n );   // may the launch stage a table of n distinct leaf boxes (flat leaf-box test)?
-size_t     terra_lds_block_limit ( void );                // the most a block may ask for (launch_instance opts in above 64 KB)
-size_t     terra_fast_spill_bytes ( const DevRenderParams& p );   // bytes of DevRenderParams::stack_spill a fast-tree launch needs (p.job_blocks set; 0: the stack fits in LDS)
-void       terra_plan_fast_tree ( DevRenderParams& p );     // the plan of a fast-tree (MODE 2 / 3) launch: stack from the tree's depth, nothing staged
 hipError_t terra_launch_tiles ( bool pack, float* pixels, void* results, uint32_t fb_w, uint32_t x, uint32_t y, uint32_t w, uint32_t h,
                                 uint32_t tile, uint32_t rank, uint32_t world, float* packed, hipStream_t stream );
 
@@ -56,7 +44,7 @@ hipError_t terra_launch_temporal_reproject ( const DevTemporalParams& p, const v
                                              void* out_results, void* out_moments, hipStream_t stream );
 
 // batched ray queries (query_kernels.hip; include/terra_amd.h "Ray queries"): rays = n TerraAmdRay, out = n TerraAmdHit (closest hit) or n uint32 (anyhit), all in HBM.
-// fast: traverse the fast tree (stack_depth / spill_cap as terra_plan_fast_tree made them; MODE 3 where scene.reach), otherwise the reference tree from global
+// fast: traverse the fast tree (stack_depth / spill_cap as launch_plan.h terra_plan_fast_tree made them; MODE 3 where scene.reach), otherwise the reference tree from global
 // memory with stack_depth entries (the launcher plans the leaf list), leaf_cull where the commit proved the cull, for origins within +-origin_limit
 struct DevQueryParams {
     DevScene scene;

@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include "trace_device.h"
 #include "kernels.h"
+#include "launch_plan.h"
 
 #define TERRA_QUERY_MAX_BLOCKS_PER_CU 8
 
@@ -21,14 +22,7 @@ template <int MODE, bool ANYHIT>
 __global__ __launch_bounds__ ( 256 ) void terra_query_kernel ( DevQueryParams p, const float4* rays, uint32_t n, void* out, uint32_t* spill ) {
     extern __shared__ int words[];
     const uint32_t tid = threadIdx.x;
-    Tracer T;
-    T.sc = p.scene; T.l_nodes = nullptr; T.l_tris = nullptr; T.l_props = nullptr; T.l_ranked = nullptr; T.n_boxes = 0;
-    T.l_mats = p.scene.mats; T.l_lights = p.scene.lights; T.l_area = p.scene.tri_area;
-    T.lds_nodes = 0; T.lds_tris = 0; T.ranked = false; T.pairs = false;
-    T.stack = words + tid; T.leaves = words + p.stack_depth * TERRA_COL + tid; T.leaf_cap = ( int ) p.leaf_cap; T.stack_cap = ( int ) p.stack_depth;
-    T.stack_lim = ( uint32_t ) ( uintptr_t ) words + p.stack_depth * 1024u;
-    T.spill = spill ? spill + ( size_t ) ( blockIdx.x * 256u + tid ) * p.spill_cap : nullptr; T.spill_cap = spill ? p.spill_cap : 0u;
-    T.faults = nullptr; T.cull = false; T.fused = false;
+    Tracer T = unstaged_tracer ( p.scene, words, p.stack_depth, p.leaf_cap, spill, p.spill_cap );
     // (n <= 2^31 - 1 and the grid has at most 2^19 lanes: neither base + tid nor the stride's add leaves 32 bits)
     for ( uint32_t base = blockIdx.x * 256u; base < n; base += gridDim.x * 256u ) {
         const uint32_t i = base + tid;
@@ -89,23 +83,17 @@ static hipError_t launch_query ( const DevQueryParams& p, const float4* rays, ui
 hipError_t terra_launch_query ( DevQueryParams p, const void* rays, size_t n, void* out, bool anyhit, hipStream_t stream ) {
     if ( n == 0 ) return hipSuccess;
     if ( n > 0x7fffffffull ) return hipErrorInvalidValue;
-    int dev = 0, cus = 0; ( void ) hipGetDevice ( &dev );
-    if ( hipDeviceGetAttribute ( &cus, hipDeviceAttributeMultiprocessorCount, dev ) != hipSuccess || cus < 1 ) { ( void ) hipGetLastError(); cus = 256; }
-    const uint64_t blocks = ( n + 255 ) / 256, cap = ( uint64_t ) cus * TERRA_QUERY_MAX_BLOCKS_PER_CU;
+    const uint64_t blocks = ( n + 255 ) / 256, cap = ( uint64_t ) terra_cu_count() * TERRA_QUERY_MAX_BLOCKS_PER_CU;
     const uint32_t grid = ( uint32_t ) ( blocks < cap ? blocks : cap );
-    // the stack as terra_launch_aov plans it: the fast tree's LDS column + HBM rest came with p (terra_plan_fast_tree); the reference tree's whole stack and a
-    // leaf list of what 64 KB leave (at least 4 entries) live in LDS
+    // the stack as terra_launch_aov plans it: the fast tree's LDS column + HBM rest came with p (launch_plan.h terra_plan_fast_tree); the reference tree's whole
+    // stack and a leaf list of what 64 KB leave (at least 4 entries) live in LDS (terra_unstaged_leaf_cap)
     int mode = 0;
     if ( p.fast ) mode = p.scene.reach ? 3 : 2;
-    else {
-        if ( p.stack_depth < 1 ) p.stack_depth = 1;
-        p.leaf_cap = TERRA_LEAF_CAP_MAX; p.spill_cap = 0;
-        while ( p.leaf_cap > 4 && ( size_t ) ( p.stack_depth + p.leaf_cap ) * 1024 > ( size_t ) 64 * 1024 ) --p.leaf_cap;
-    }
+    else { if ( p.stack_depth < 1 ) p.stack_depth = 1; p.leaf_cap = terra_unstaged_leaf_cap ( p.stack_depth, 0 ); p.spill_cap = 0; }
     const size_t lds = ( size_t ) ( p.stack_depth + ( mode == 0 ? p.leaf_cap : 0u ) ) * 1024;
     if ( lds > terra_lds_block_limit() ) return hipErrorInvalidValue;
     uint32_t* spill = nullptr;
-    const size_t spill_bytes = mode != 0 && p.spill_cap ? ( size_t ) grid * 256 * p.spill_cap * sizeof ( uint32_t ) : 0;      // sized for the grid, not for n
+    const size_t spill_bytes = mode != 0 ? terra_spill_bytes ( grid, p.spill_cap ) : 0;      // sized for the grid, not for n
     if ( spill_bytes ) { const hipError_t e = hipMallocAsync ( ( void** ) &spill, spill_bytes, stream ); if ( e != hipSuccess ) return e; }
     const float4* in = reinterpret_cast<const float4*> ( rays );
     const uint32_t n32 = ( uint32_t ) n;

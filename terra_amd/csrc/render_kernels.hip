@@ -22,15 +22,13 @@
 #include <hip/hip_runtime.h>
 #include "trace_device.h"
 #include "kernels.h"
+#include "launch_plan.h"
 #include "empty_proof.h"
 
 // One source, several translation units (terra_amd/build.py compiles this file once per TERRA_TU value, in parallel: a single unit takes 3 minutes):
-//   TERRA_TU 0  everything that is not a render-kernel instance (resolve / tile kernels, LDS planning, the launch dispatch) + the kernels of template MODE 0
+//   TERRA_TU 0  everything that is not a render-kernel instance (resolve / tile kernels, the launch dispatch; the plan itself: launch_plan.h) + the kernels of template MODE 0
 //   TERRA_TU 1 / 2 / 3  the kernels of template MODE 1 (LDS-resident scenes) / 2 (fast tree) / 3 (fast tree + reachability replay) and their launcher
 //   undefined   all of it in one unit (tools/kernel_resources.sh, tools/isa_cost.py)
-#ifndef TERRA_JOB_STREAM_TABLE      // the jobs' random streams keyed by a kernel of their own ahead of the render (DevRenderParams::job_streams): 0 = by the lane that takes the job
-#define TERRA_JOB_STREAM_TABLE 1
-#endif
 #ifdef TERRA_TU
 #define TERRA_TU_HAS(k) ( TERRA_TU == ( k ) )
 #else
@@ -54,11 +52,7 @@ TD void wave_flush_counters ( const Counters& c, unsigned long long* g ) {
 // Builds the block's Tracer: carves the dynamic LDS, stages the scene prefix the host
 // planned (DevRenderParams.lds_*), and leaves every thread with its own stack / leaf
 // list column. Called by all 256 threads (it contains the block barrier).
-// per-thread words parked in LDS between uses (indexed [word][thread] like the stack): the radiance sum of the lane's
-// current job (touched once per path), the job's number and the lane's draw count when the job started (read at its end), and a row
-// that holds each wave's pool of claimed jobs (render_kernels.hip "jobs")
-#define TERRA_AUX_WORDS 6        // rows every launch has (acc x 3, job, draw count, wave pools)
-#define TERRA_AUX_WORDS_LDS 9    // ... plus, on LDS-resident scenes (lds_mode 1), the path radiance Lo x 3 (TERRA_LO_IN_LDS)
+// (the per-thread words parked in LDS between uses, TERRA_AUX_WORDS / TERRA_AUX_WORDS_LDS: dev_types.h "launch plan")
 #ifndef TERRA_LO_IN_LDS          // the coupled loop of LDS-resident scenes keeps the current path's radiance (three words that change on few hits) in rows 6-8 instead of registers
 #define TERRA_LO_IN_LDS 1
 #endif
@@ -75,7 +69,7 @@ TD Tracer make_tracer ( const DevScene& sc, float4* lds, uint32_t stack_depth, u
     const int tid = threadIdx.x;
     Tracer T;
     T.sc = sc;
-    // [staged nodes][staged triangles][staged properties][materials, lights, areas][ranked copies, or the pair section: pair copies + leaf-box table][stack][leaf list][parked words]  (sizes: terra_lds_bytes)
+    // [staged nodes][staged triangles][staged properties][materials, lights, areas][ranked copies, or the pair section: pair copies + leaf-box table][stack][leaf list][parked words]  (sizes: launch_plan.h terra_lds_bytes)
     float4* ln = lds;                                                // byte offset 0: a staged node's address is its stack word
     float4* lt = ln + ( TERRA_LDS_NODE_BYTES / 16 ) * lds_nodes;      // (fast-tree launches stage nothing: lds_nodes == lds_tris == 0)
     float4* lp = lt + 3 * lds_tris;
@@ -811,116 +805,15 @@ __global__ __launch_bounds__ ( 256, TERRA_WAVES_FOR ( INTEGRATOR, KINDS, MODE ) 
 
 // ---- launch -------------------------------------------------------------------
 
-#if TERRA_TU_HAS ( 0 )
-static uint32_t own_tiles ( uint32_t w, uint32_t h, uint32_t tile, uint32_t rank, uint32_t world ) {
-    uint32_t tiles = ( ( w + tile - 1 ) / tile ) * ( ( h + tile - 1 ) / tile );
-    return tiles > rank ? ( tiles - rank + world - 1 ) / world : 0;
-}
-
-// LDS a MODE-1 block spends on materials, lights and triangle areas (make_tracer): three sections, each a multiple of 16 bytes
-static size_t scene_extra_lds_bytes ( uint32_t n_objects, uint32_t n_lights, uint32_t n_tris ) {
-    return ( ( ( size_t ) n_objects * sizeof ( DevMaterial ) + 15 ) & ~size_t ( 15 ) ) + ( size_t ) n_lights * sizeof ( DevLight ) + ( ( ( size_t ) n_tris * 4 + 15 ) & ~size_t ( 15 ) );
-}
-size_t terra_lds_bytes ( const DevRenderParams& p ) {
-    return ( size_t ) ( p.stack_depth + p.leaf_cap + ( p.lds_mode == 1 ? TERRA_AUX_WORDS_LDS : TERRA_AUX_WORDS ) ) * 1024 + ( size_t ) p.lds_nodes * TERRA_LDS_NODE_BYTES + ( size_t ) p.lds_tris * ( 48 + 64 )
-           + ( p.lds_mode == 1 ? scene_extra_lds_bytes ( p.scene.n_objects, p.scene.n_lights, p.scene.n_tris ) : 0 ) + ( p.lds_mode == 1 && p.leaf_rank ? ( p.leaf_pairs ? ( size_t ) terra_pair_section_bytes ( p.lds_tris / 2 ) : ( size_t ) p.lds_tris * 6 * 48 ) : 0 );      // (the leaf-box table of a flat launch rides in pad words of the ranked entries: no bytes of its own; the pair form's section includes its table)
-}
-// fast tree (MODE 2 / 3): nothing is staged. A lane holds at most two leaves (in registers: the one it tests, the next one), so there is no leaf list. The stack: its first TERRA_FAST_STACK_LDS entries
-// in LDS (1 KB per entry and block), the rest -- up to the tree's worst case, which a ray almost never reaches -- in HBM, 4 bytes per entry and resident lane
-// (DevRenderParams::stack_spill, part of the launch's scratch: traverse_fast.h fast_push / fast_pop). Depth no longer decides whether a tree can be launched.
-// (Rounds 2-3 staged the first 64 nodes as plain 64-byte nodes read through a flat load: +3.7 % then. Flat loads go through the texture addresser like global ones,
-// and that unit is what binds these kernels: nothing is gained by it now.)
-#ifndef TERRA_FAST_STACK_LDS
-#define TERRA_FAST_STACK_LDS 16
-#endif
-void terra_plan_fast_tree ( DevRenderParams& p ) {
-    const uint32_t need = ( uint32_t ) ( p.scene.fast_max_stack < 1 ? 1 : p.scene.fast_max_stack );
-    p.lds_mode = 2; p.lds_tris = 0; p.lds_nodes = 0; p.leaf_cap = 0; p.leaf_rank = 0; p.stack_depth = need < ( uint32_t ) TERRA_FAST_STACK_LDS ? need : ( uint32_t ) TERRA_FAST_STACK_LDS;
-    p.spill_cap = need - p.stack_depth; p.stack_spill = nullptr;
-}
-// resident lanes a fast-tree launch can have at most (8 blocks of 256 threads per CU): what the spill area is sized for
-size_t terra_fast_spill_bytes ( const DevRenderParams& p ) {
-    if ( p.lds_mode != 2 || p.spill_cap == 0 ) return 0;
-    int cus = 0, dev = 0; ( void ) hipGetDevice ( &dev );
-    if ( hipDeviceGetAttribute ( &cus, hipDeviceAttributeMultiprocessorCount, dev ) != hipSuccess || cus < 1 ) { ( void ) hipGetLastError(); cus = 256; }
-    const size_t blocks = ( size_t ) p.job_blocks < ( size_t ) cus * 8 ? ( size_t ) p.job_blocks : ( size_t ) cus * 8;
-    return blocks * 256 * ( size_t ) p.spill_cap * sizeof ( uint32_t );
-}
-
-// LDS plan. Small scenes (whole scene + stack + a leaf list of at least TERRA_LEAF_CAP_RESIDENT_MIN entries <= budget): stage
-// everything; with the Cornell box that is 31.9 KB per block (112-B staged nodes, 14-entry leaf list), so the 5 blocks/CU the
-// Simple kernel's registers allow stay resident. The leaf list takes what the budget leaves, up to 16 entries: a list that
-// fills is drained and the node loop resumes, so its length only decides how often that happens.
-// Large scenes: nothing is staged -- their node fetches are bound by the L1 tag rate of divergent
-// 16-byte loads (each lane its own 64-B node) and by latency, so resident blocks matter most: the
-// leaf list takes what is left of the CU's 160 KB after fitting as many blocks as possible while
-// keeping at least 8 entries (profiles/r01_measurements/ab4.log, ab5.log: 4 blocks x 14 entries 219 ms vs
-// 3 blocks x 16 entries 305 ms vs 4-entry lists 261 ms on the 97k-triangle hall).
-#ifndef TERRA_LDS_CU_KB
-#define TERRA_LDS_CU_KB 158
-#endif
-#ifndef TERRA_LEAF_CAP_MIN       // smallest leaf list worth an extra resident block (with the decoupled loop, hall: 5 blocks x 6 entries
-#define TERRA_LEAF_CAP_MIN 6     // 391 ms vs 4 blocks x 14 entries 400 ms, Direct 473 vs 487 ms; profiles/r01_measurements/ab_lc*.log)
-#endif
-#ifndef TERRA_LDS_BUDGET          // per block, so that FIVE blocks stay resident per CU: a CU does not hand out all of its 160 KB -- 5 x 31,632 B fit, 5 x 32,656 B
-#define TERRA_LDS_BUDGET ( TERRA_LDS_CU_KB * 1024 / 5 )      // do not (measured: 4.57 -> 3.67 waves per SIMD and 65.6 -> 74.4 ms on the Cornell frame, profiles/r03_measurements/lds_cliff.log)
-#endif
-#ifndef TERRA_LEAF_CAP_RESIDENT_MIN
-#define TERRA_LEAF_CAP_RESIDENT_MIN 8
-#endif
-// leaf-list entries an LDS-resident plan can afford (0 = the scene does not fit)
-static uint32_t resident_leaf_cap ( uint32_t n_nodes, uint32_t n_tris, int max_stack, uint32_t n_objects, uint32_t n_lights ) {
-    const uint32_t depth = max_stack < 1 ? 1u : ( uint32_t ) max_stack;
-    const size_t fixed = ( size_t ) ( depth + TERRA_AUX_WORDS_LDS ) * 1024 + ( size_t ) n_nodes * TERRA_LDS_NODE_BYTES + ( size_t ) n_tris * 112 + scene_extra_lds_bytes ( n_objects, n_lights, n_tris );
-    if ( fixed + ( size_t ) TERRA_LEAF_CAP_RESIDENT_MIN * 1024 > ( size_t ) TERRA_LDS_BUDGET ) return 0;
-    const uint32_t cap = ( uint32_t ) ( ( ( size_t ) TERRA_LDS_BUDGET - fixed ) / 1024 );
-    return cap > TERRA_LEAF_CAP_MAX ? TERRA_LEAF_CAP_MAX : cap;
-}
-bool terra_scene_fits_lds ( uint32_t n_nodes, uint32_t n_tris, int max_stack, uint32_t n_objects, uint32_t n_lights ) { return resident_leaf_cap ( n_nodes, n_tris, max_stack, n_objects, n_lights ) != 0; }
-void terra_plan_lds ( DevRenderParams& p ) {
-    uint32_t depth = p.scene.max_stack < 1 ? 1u : ( uint32_t ) p.scene.max_stack;
-    p.stack_depth = depth;
-    p.leaf_cap = TERRA_LEAF_CAP_MAX; p.leaf_rank = 0;
-    if ( const uint32_t cap = resident_leaf_cap ( p.scene.n_nodes, p.scene.n_tris, p.scene.max_stack, p.scene.n_objects, p.scene.n_lights ) ) {
-        p.lds_mode = 1; p.lds_nodes = p.scene.n_nodes; p.lds_tris = p.scene.n_tris; p.leaf_cap = cap;
-        // at most TERRA_LEAF_RANK_MAX triangles: the leaf list gives way to the rank set and the permuted copies (traverse_ref.h "Ranked launches") if they
-        // take no more LDS than the list did -- on the Cornell box 6 x 32 x 48 B = 9 KB in place of the list's 13 KB
-        if ( p.scene.n_tris <= TERRA_LEAF_RANK_MAX && ( size_t ) p.scene.n_tris * 6 * 48 <= ( size_t ) cap * 1024 ) { p.leaf_rank = 1; p.leaf_cap = 0; }
-        return;
-    }
-    p.lds_mode = 0; p.lds_nodes = 0; p.lds_tris = 0;
-    for ( int blocks = 5; blocks >= 1; --blocks ) {
-        int room = TERRA_LDS_CU_KB / blocks - ( int ) depth - TERRA_AUX_WORDS;       // KB per block left for the leaf list (2 KB of slack per CU)
-        if ( room >= TERRA_LEAF_CAP_MIN || blocks == 1 ) { p.leaf_cap = ( uint32_t ) ( room > TERRA_LEAF_CAP_MAX ? TERRA_LEAF_CAP_MAX : ( room < 4 ? 4 : room ) ); break; }
-    }
-    // a deep tree: keep the block within the 64 KB a launch may ask for without an opt-in while the leaf list keeps at least 4 entries; deeper still, the launch opts in
-    // (launch_instance: hipFuncAttributeMaxDynamicSharedMemorySize, one block per CU) up to TERRA_LDS_BLOCK_MAX_KB, beyond which terra_launch_render refuses with a message
-    while ( p.leaf_cap > 4 && terra_lds_bytes ( p ) > ( size_t ) 64 * 1024 ) --p.leaf_cap;
-}
-// Flat leaf-box test: can a launch planned as p stage a table of n boxes? Ranked launches with the fused box test only (make_tracer stages under the same
-// condition); the table rides in pad words of what such a launch stages anyway, one set per triangle, so it fits whenever n <= the triangles staged
-bool terra_leaf_boxes_fit ( const DevRenderParams& p, uint32_t n ) {
-    return n != 0 && n <= TERRA_LEAF_RANK_MAX && p.lds_mode == 1 && p.leaf_rank && p.leaf_cull && p.fused_slab && n <= p.lds_tris;
-}
-
-#endif
-
-#ifndef TERRA_LDS_BLOCK_MAX_KB      // the most dynamic LDS one block may opt in to (a CU's 160 KB less what the runtime keeps)
-#define TERRA_LDS_BLOCK_MAX_KB 156
-#endif
-#if TERRA_TU_HAS ( 0 )
-size_t terra_lds_block_limit ( void ) { return ( size_t ) TERRA_LDS_BLOCK_MAX_KB * 1024; }
-#endif
 // blocks of one kernel instance the GPU holds at once (occupancy x CUs), cached per (kernel, LDS size): the persistent grid
 static uint32_t resident_blocks ( const void* fn, size_t lds ) {
     struct Key { const void* fn; size_t lds; int dev; uint32_t blocks; };
     static thread_local Key cache[8]; static thread_local int used = 0;
     int dev = 0; ( void ) hipGetDevice ( &dev );
     for ( int i = 0; i < used; ++i ) if ( cache[i].fn == fn && cache[i].lds == lds && cache[i].dev == dev ) return cache[i].blocks;
-    int per_cu = 0, cus = 0;
+    int per_cu = 0;
     if ( hipOccupancyMaxActiveBlocksPerMultiprocessor ( &per_cu, fn, 256, lds ) != hipSuccess || per_cu < 1 ) { ( void ) hipGetLastError(); per_cu = 1; }
-    if ( hipDeviceGetAttribute ( &cus, hipDeviceAttributeMultiprocessorCount, dev ) != hipSuccess || cus < 1 ) { ( void ) hipGetLastError(); cus = 256; }
-    const uint32_t blocks = ( uint32_t ) per_cu * ( uint32_t ) cus;
+    const uint32_t blocks = ( uint32_t ) per_cu * terra_cu_count();
     Key& k = cache[used < 8 ? used++ : 7]; k.fn = fn; k.lds = lds; k.dev = dev; k.blocks = blocks;
     return blocks;
 }
@@ -928,7 +821,7 @@ template <int I, int COUNT, int MODE, int KINDS>
 static hipError_t launch_instance ( const DevRenderParams& p, size_t lds, hipStream_t stream ) {
     auto fn = terra_render_kernel<I, COUNT, MODE, KINDS>;
     if ( lds > ( size_t ) 64 * 1024 ) {          // a traversal stack deeper than ~55 entries (deep reference tree, Morton-ordered tree over clustered geometry): opt in, once per kernel and size
-        if ( lds > ( size_t ) TERRA_LDS_BLOCK_MAX_KB * 1024 ) return hipErrorInvalidValue;      // (terra_launch_render checks first and says why)
+        if ( lds > terra_lds_block_limit() ) return hipErrorInvalidValue;      // (scene_host.cpp launch_render checks first and says why)
         static thread_local size_t opted[8] = { 0 }; int dev = 0; ( void ) hipGetDevice ( &dev );
         if ( opted[dev & 7] < lds ) {
             const hipError_t e = hipFuncSetAttribute ( reinterpret_cast<const void*> ( fn ), hipFuncAttributeMaxDynamicSharedMemorySize, ( int ) lds );
@@ -938,7 +831,7 @@ static hipError_t launch_instance ( const DevRenderParams& p, size_t lds, hipStr
     }
     uint32_t grid = p.job_blocks;
     if ( p.job_queue ) { const uint32_t cap = resident_blocks ( reinterpret_cast<const void*> ( fn ), lds ); if ( grid > cap ) grid = cap; }
-    if ( MODE >= 2 && p.spill_cap && ( !p.stack_spill || ( size_t ) grid * 256 * p.spill_cap * sizeof ( uint32_t ) > terra_fast_spill_bytes ( p ) ) ) return hipErrorInvalidValue;      // (the spill area is sized for 8 blocks per CU)
+    if ( MODE >= 2 && p.spill_cap && ( !p.stack_spill || terra_spill_bytes ( grid, p.spill_cap ) > terra_fast_spill_bytes ( p ) ) ) return hipErrorInvalidValue;      // (the spill area is sized for 8 blocks per CU)
     hipLaunchKernelGGL ( fn, dim3 ( grid ), dim3 ( 256 ), lds, stream, p );
     return hipGetLastError();
 }
@@ -996,13 +889,6 @@ hipError_t terra_launch_render_mode3 ( const DevRenderParams& p, size_t lds, hip
 
 #if TERRA_TU_HAS ( 0 )
 // p.job_blocks and p.partials must be set (scene_host.cpp launch_render); p.job_queue (a zeroed word) = persistent grid fed by the queue, nullptr = plain launch
-bool terra_render_wants_queue ( const DevRenderParams& p ) {
-#ifdef TERRA_QUEUE_NEVER         // A/B builds: every loop launched plainly
-    ( void ) p; return false;
-#else
-    ( void ) p; return true;
-#endif
-}
 hipError_t terra_launch_render ( const DevRenderParams& p, hipStream_t stream ) {
     if ( p.job_blocks == 0 ) return hipSuccess;
     if ( !p.partials ) return hipErrorInvalidValue;
@@ -1013,10 +899,6 @@ hipError_t terra_launch_render ( const DevRenderParams& p, hipStream_t stream ) 
     return terra_launch_render_mode0 ( p, lds, stream );
 }
 
-uint32_t terra_render_blocks ( const DevRenderParams& p ) {
-    uint32_t bpt = p.tile_size / 16;
-    return own_tiles ( p.w, p.h, p.tile_size, p.rank, p.world ) * bpt * bpt;
-}
 // First kernel of every render: the random streams of every job of the launch (what job_next would otherwise compute when a lane takes the job). One thread per job,
 // numbered like the render kernel's jobs; a job whose pixel lies outside the rectangle has no entry (nobody reads it).
 __global__ __launch_bounds__ ( 256 ) void terra_job_streams_kernel ( DevRenderParams p ) {
@@ -1110,17 +992,6 @@ __global__ __launch_bounds__ ( 256 ) void terra_block_order_kernel ( uint32_t n,
         order[v] = i; order[n + i] = v;
     }
 }
-#ifndef TERRA_JOB_ORDER_MIN_BLOCKS
-#define TERRA_JOB_ORDER_MIN_BLOCKS 256
-#endif
-uint32_t terra_job_order_min_blocks ( void ) { return TERRA_JOB_ORDER_MIN_BLOCKS; }
-size_t terra_block_order_bytes ( const DevRenderParams& p, bool small_too ) {          // class word + the two halves of the order per pixel block, or 0: this launch keeps the order of the numbering
-    if ( terra_job_streams_bytes ( p ) == 0 || p.scene.n_tris == 0 || p.scene.n_tris > 4096 ) return 0;
-    const size_t blocks = terra_render_blocks ( p );
-    // (not for small launches -- below TERRA_JOB_ORDER_MIN_BLOCKS pixel blocks, a 256 x 256 rectangle: a tile-sized call is one of several in flight, whose work hides its tail,
-    //  and its two extra small kernels would queue behind the other callers' render grids: the reference client's tile loop 66.5 -> 72.6 ms with them)
-    return blocks >= ( small_too ? 1u : ( unsigned ) TERRA_JOB_ORDER_MIN_BLOCKS ) ? ( blocks * 3 * sizeof ( uint32_t ) + 255 ) & ~size_t ( 255 ) : 0;
-}
 hipError_t terra_launch_block_order ( const DevRenderParams& p, uint32_t* cls, hipStream_t stream ) {      // p.block_order = cls + blocks; p.job_live set: the launch skips the blocks proved empty
     const uint32_t blocks = terra_render_blocks ( p );
     if ( !p.block_order || !cls || blocks == 0 ) return hipErrorInvalidValue;
@@ -1135,7 +1006,6 @@ hipError_t terra_launch_job_streams ( const DevRenderParams& p, hipStream_t stre
     hipLaunchKernelGGL ( terra_job_streams_kernel, dim3 ( p.job_blocks ), dim3 ( 256 ), 0, stream, p );
     return hipGetLastError();
 }
-size_t terra_job_streams_bytes ( const DevRenderParams& p ) { return ( TERRA_JOB_STREAM_TABLE && p.lds_mode == 1 ) ? ( size_t ) p.job_blocks * 256 * 32 : 0; }      // (p.job_blocks set)
 hipError_t terra_launch_resolve ( const DevRenderParams& p, hipStream_t stream ) {
     uint32_t blocks = terra_render_blocks ( p );
     if ( blocks == 0 ) return hipSuccess;

@@ -27,6 +27,7 @@
 #include "../../include/TerraPresets.h"
 #include "dev_types.h"
 #include "kernels.h"
+#include "launch_plan.h"
 #include "empty_proof.h"
 #include "tree_build.h"
 #include "multi_gpu.h"
@@ -300,6 +301,8 @@ struct TreeChoice {
     bool resident = false;              // the reference tree fits the LDS-resident kernels
     float reach_margin = 0.f, fast_extra = 0.f, fast_scale = 1.f;
 };
+// the largest |coordinate| of a ray origin (the camera, a query's rays) for which the choice's traversal shortcut -- fast tree, leaf-box cull -- is proven
+static float shortcut_limit ( const TreeChoice& c ) { return ( c.reach || c.reach_cull ) ? c.reach_limit : TERRA_CULL_MAX_COORD; }
 // The blob: one device allocation per copy of the scene, these sections in this order, 256-byte aligned, then one section per texture (layout_blob)
 enum { kSecNodes, kSecTris, kSecProps, kSecMats, kSecLights, kSecArea, kSecFastBin, kSecFastWide, kSecFastTris, kSecReplay, kSecLeafParent, kSecLeafMask, kSecLeafBoxes, kSecLeafPairs, kSecTexDesc, kSecTextures };
 struct Section { size_t offset = 0, bytes = 0; const void* host = nullptr; size_t host_bytes = 0; };      // bytes: its room in the blob; host: what the upload copies there
@@ -467,7 +470,7 @@ extern "C" int terra_amd_traversal_info ( HTerraScene h, TerraAmdTraversalInfo* 
     out->tree_mode = s->tree_mode; out->fast_tree = c.use_fast ? 1 : 0; out->fast_tree_built_on_device = c.fast_on_device ? 1 : 0; out->leaf_cull = ( c.cull_ok && !c.use_fast ) ? 1 : 0;
     out->lds_resident = ( !c.use_fast && terra_scene_fits_lds ( ( uint32_t ) s->nodes.size(), primary ( s ).dev.n_tris, s->max_stack, ( uint32_t ) s->objects_pop, ( uint32_t ) s->lights.size() ) ) ? 1 : 0;
     out->max_coordinate = c.coord_max; out->max_coordinate_allowed = TERRA_CULL_MAX_COORD;
-    out->last_call = s->last_call.load ( std::memory_order_relaxed ); out->camera_limit = ( c.reach || c.reach_cull ) ? c.reach_limit : TERRA_CULL_MAX_COORD;
+    out->last_call = s->last_call.load ( std::memory_order_relaxed ); out->camera_limit = shortcut_limit ( c );
     snprintf ( out->note, sizeof out->note, "%s", c.note.c_str() );
     return 0;
 }
@@ -1508,11 +1511,28 @@ static void fill_camera ( const TerraCamera* cam, size_t fb_w, size_t fb_h, DevR
     p.aspect = ( float ) fb_w / ( float ) fb_h;
 }
 
+// the scene can answer a call: committed since it last changed, and with a device replica
+static int scene_check ( const Scene* s ) {
+    if ( !s->committed ) return fail ( kTerraAmdErrNotCommitted, "terra_scene_commit has not run since the scene changed" );
+    if ( !s->device_ok ) return fail ( kTerraAmdErrNoDevice, "scene has no device replica: %s", s->commit_error.c_str() );
+    return 0;
+}
+// TEST HOOKS on a planned launch (terra_amd_debug_fast_stack_lds, terra_amd_debug_pad_stack): a short LDS column, so that ordinary scenes exercise the HBM part of a
+// fast-tree stack; a deeper stack than the tree needs (the LDS-resident plan is sized to the byte and stays as it is), the leaf list clamped as terra_plan_lds clamps it
+static void apply_stack_hooks ( const Scene* s, DevRenderParams& p ) {
+    if ( s->test_fast_stack_lds > 0 && p.lds_mode == 2 ) {
+        const uint32_t need = p.stack_depth + p.spill_cap;
+        p.stack_depth = need < ( uint32_t ) s->test_fast_stack_lds ? need : ( uint32_t ) s->test_fast_stack_lds; p.spill_cap = need - p.stack_depth;
+    }
+    if ( s->test_pad_stack > 0 && p.lds_mode != 1 ) {
+        p.stack_depth += ( uint32_t ) s->test_pad_stack;
+        p.leaf_cap = terra_clamp_leaf_cap ( p.stack_depth, p.leaf_cap, terra_lds_bytes ( p ) - ( size_t ) ( p.stack_depth + p.leaf_cap ) * 1024 );
+    }
+}
 // r: the copy of the scene the launch reads (the launch runs on r.device)
 static int fill_params ( Scene* s, const Scene::Replica& r, const TerraCamera* cam, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t h,
                          size_t tile, int rank, int world, DevRenderParams& p ) {
-    if ( !s->committed ) return fail ( kTerraAmdErrNotCommitted, "terra_scene_commit has not run since the scene changed" );
-    if ( !s->device_ok ) return fail ( kTerraAmdErrNoDevice, "scene has no device replica: %s", s->commit_error.c_str() );
+    if ( int rc = scene_check ( s ) ) return rc;
     if ( !cam || w == 0 || h == 0 || x + w > fb_w || y + h > fb_h ) return fail ( kTerraAmdErrBadArgument, "bad tile rectangle %zu,%zu %zux%zu in %zux%zu", x, y, w, h, fb_w, fb_h );
     if ( tile == 0 || tile % 16 != 0 ) return fail ( kTerraAmdErrBadArgument, "tile_size %zu must be a positive multiple of 16", tile );
     if ( world < 1 || rank < 0 || rank >= world ) return fail ( kTerraAmdErrBadArgument, "bad shard %d/%d", rank, world );
@@ -1541,15 +1561,8 @@ static int fill_params ( Scene* s, const Scene::Replica& r, const TerraCamera* c
     else if ( ( c.use_fast || c.cull_ok ) && !cam_ok && !s->warned_camera.exchange ( true ) )          // (once per scene)
         fprintf ( stderr, "[terra_amd] warning: camera at (%g, %g, %g) lies outside the range (+-%g) for which this scene's traversal shortcut is proven: this call runs the reference "
                   "tree's replica traversal (same image, typically 10-20 x slower on large scenes); terra_amd_traversal_info() reports camera_limit and last_call\n",
-                  ( double ) p.cam_pos[0], ( double ) p.cam_pos[1], ( double ) p.cam_pos[2], ( double ) ( ( c.reach || c.reach_cull ) ? c.reach_limit : TERRA_CULL_MAX_COORD ) );
-    if ( s->test_fast_stack_lds > 0 && p.lds_mode == 2 ) {      // TEST HOOK: a short LDS column, so that ordinary scenes exercise the HBM part of the stack
-        const uint32_t need = p.stack_depth + p.spill_cap;
-        p.stack_depth = need < ( uint32_t ) s->test_fast_stack_lds ? need : ( uint32_t ) s->test_fast_stack_lds; p.spill_cap = need - p.stack_depth;
-    }
-    if ( s->test_pad_stack > 0 && p.lds_mode != 1 ) {          // TEST HOOK: a deeper stack than the tree needs (the LDS-resident plan is sized to the byte and stays as it is)
-        p.stack_depth += ( uint32_t ) s->test_pad_stack;
-        while ( p.leaf_cap > 4 && terra_lds_bytes ( p ) > ( size_t ) 64 * 1024 ) --p.leaf_cap;      // (what terra_plan_lds does for a deep tree)
-    }
+                  ( double ) p.cam_pos[0], ( double ) p.cam_pos[1], ( double ) p.cam_pos[2], ( double ) shortcut_limit ( c ) );
+    apply_stack_hooks ( s, p );
     p.leaf_cull = ( c.cull_ok && cam_ok && p.lds_mode != 2 ) ? 1u : 0u;
     p.fused_slab = ( p.leaf_cull && !c.reach_cull ) ? 1u : 0u;      // (out of range only the rebuilt LEAF boxes carry a margin: the inner boxes are tested exactly as the reference tests them)
     // flat leaf-box test: a ranked launch with the fused box test stages the scene's distinct leaf boxes where they fit (launch_render drops them again for a
@@ -1640,6 +1653,7 @@ static int launch_render ( Scene* s, DevRenderParams& p, int device, hipStream_t
         if ( hipDeviceGetDefaultMemPool ( &pool, device ) == hipSuccess ) { uint64_t keep = ~0ull; ( void ) hipMemPoolSetAttribute ( pool, hipMemPoolAttrReleaseThreshold, &keep ); }
         pool_kept |= 1ull << device;
     }
+    // the sections of the launch's scratch, one after the other: [queue word][job sums][job streams (LDS-resident scenes)][stack spill (fast tree)][job order]
     const size_t header = 256;                                     // the job queue word (+ padding that keeps the partials 256-byte aligned)
     const size_t partial_bytes = ( size_t ) split * blocks * 256 * sizeof ( float4 );
     p.job_blocks = blocks * split;
@@ -1647,7 +1661,7 @@ static int launch_render ( Scene* s, DevRenderParams& p, int device, hipStream_t
     if ( stream_bytes && ( p.fb_w > 65535u || p.fb_h > 65535u ) ) return fail ( kTerraAmdErrBadArgument, "framebuffer of %u x %u: at most 65,535 pixels per side (the job table packs a pixel into 32 bits)", p.fb_w, p.fb_h );
     const size_t spill_bytes = terra_fast_spill_bytes ( p );                 // fast-tree launches: the part of the lanes' traversal stacks that does not live in LDS
     const size_t order_bytes = s->job_order ? terra_block_order_bytes ( p, s->job_order == 2 ) : 0;           // LDS-resident launches: the order the pixel blocks are handed out in (render_kernels.hip "job order")
-    const size_t scratch_bytes = header + partial_bytes + stream_bytes + spill_bytes + order_bytes;      // [queue word][job sums][job streams (LDS-resident scenes)][stack spill (fast tree)][job order]
+    const size_t scratch_bytes = header + partial_bytes + stream_bytes + spill_bytes + order_bytes;
     // (a thread's slot keeps scratch for tile-sized calls only: a full-frame call's gigabytes come from, and go back to, the device's pool)
     // a launch's scratch is bounded: 48 bytes per (pixel, lane-per-pixel) job on LDS-resident scenes -- a 4K frame at 64 lanes per pixel asks for 25 GB per concurrent stream.
     // Beyond TERRA_SCRATCH_MAX_GB the call is refused with the size in the message (fewer lanes per pixel, or the frame in several calls, give the same framebuffer)
@@ -1661,11 +1675,14 @@ static int launch_render ( Scene* s, DevRenderParams& p, int device, hipStream_t
     // call on the host path, whose small kernels wait behind the other callers' render grids); memory from the pool is fresh each time
     hipError_t e = pooled ? hipMemsetAsync ( scratch, 0, header, stream ) : hipSuccess;
     p.split = split; p.split_log2 = 0; while ( ( 1u << p.split_log2 ) < split ) ++p.split_log2;
-    p.chunk_spp = p.spp / split; p.partials = ( float4* ) ( ( char* ) scratch + header );
-    p.job_blocks = blocks * split; p.job_queue = terra_render_wants_queue ( p ) ? ( uint32_t* ) scratch : nullptr;
-    p.job_streams = stream_bytes ? ( uint4* ) ( ( char* ) scratch + header + partial_bytes ) : nullptr;
-    p.stack_spill = spill_bytes ? ( uint32_t* ) ( ( char* ) scratch + header + partial_bytes + stream_bytes ) : nullptr;
-    uint32_t* const order_cls = order_bytes ? ( uint32_t* ) ( ( char* ) scratch + header + partial_bytes + stream_bytes + spill_bytes ) : nullptr;
+    p.chunk_spp = p.spp / split; p.job_blocks = blocks * split;
+    char* at = ( char* ) scratch;
+    auto section = [&at] ( size_t bytes ) { char* const here = bytes ? at : nullptr; at += bytes; return here; };
+    p.job_queue = ( uint32_t* ) section ( header );
+    p.partials = ( float4* ) section ( partial_bytes );
+    p.job_streams = ( uint4* ) section ( stream_bytes );
+    p.stack_spill = ( uint32_t* ) section ( spill_bytes );
+    uint32_t* const order_cls = ( uint32_t* ) section ( order_bytes );
     p.block_order = order_cls ? order_cls + blocks : nullptr;
     // empty skip (render_kernels.hip "proved empty"): only where a camera miss leaves nothing behind but +0 sums -- no environment term, no work counters (they are
     // defined by the walk; a per-pixel draw count asks for them too) -- and only inside the coordinate range of the containment proof, which is the fused box test's
@@ -1771,13 +1788,7 @@ extern "C" int terra_amd_time_render_device ( const TerraCamera* cam, HTerraScen
     return 0;
 }
 
-// ---- host side of the frame passes: one check, one staging helper ------------------------------------------------------------------
-// the scene can answer a call: committed since it last changed, and with a device replica
-static int scene_check ( const Scene* s ) {
-    if ( !s->committed ) return fail ( kTerraAmdErrNotCommitted, "terra_scene_commit has not run since the scene changed" );
-    if ( !s->device_ok ) return fail ( kTerraAmdErrNoDevice, "scene has no device replica: %s", s->commit_error.c_str() );
-    return 0;
-}
+// ---- host side of the frame passes: one check (on top of scene_check, above fill_params), one staging helper -----------------------------
 // The one check of the frame passes (denoise, moments, tile error, variance denoise, reproject, adaptive): the scene can answer (nullptr: the pass takes none), the
 // rectangle lies inside a frame whose sides fit the kernels' 32-bit coordinates, 0 ... 8 iterations. `what` names the pass in the message.
 static int frame_check ( const Scene* s, const char* what, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t h, int iterations = 0 ) {
@@ -1875,19 +1886,14 @@ static int launch_query ( Scene* s, const void* d_rays, size_t n, void* d_out, b
     DevQueryParams p;
     memset ( &p, 0, sizeof p );
     p.scene = r.dev;
-    p.origin_limit = ( c.reach || c.reach_cull ) ? c.reach_limit : TERRA_CULL_MAX_COORD;
-    if ( c.use_fast && r.dev.fast_nodes_h && ( s->tree_mode == 1 || shortcut ) ) {
-        terra_plan_fast_tree ( rp );
-        if ( s->test_fast_stack_lds > 0 ) {          // TEST HOOK (fill_params): a short LDS column
-            const uint32_t need = rp.stack_depth + rp.spill_cap;
-            rp.stack_depth = need < ( uint32_t ) s->test_fast_stack_lds ? need : ( uint32_t ) s->test_fast_stack_lds; rp.spill_cap = need - rp.stack_depth;
-        }
-        p.fast = 1; p.stack_depth = rp.stack_depth; p.spill_cap = rp.spill_cap;
-    } else {
-        p.stack_depth = r.dev.max_stack < 1 ? 1u : ( uint32_t ) r.dev.max_stack;
+    p.origin_limit = shortcut_limit ( c );
+    if ( c.use_fast && r.dev.fast_nodes_h && ( s->tree_mode == 1 || shortcut ) ) { terra_plan_fast_tree ( rp ); p.fast = 1; }
+    else {          // (lds_mode 0, no leaf list yet: the launcher plans it)
+        rp.stack_depth = r.dev.max_stack < 1 ? 1u : ( uint32_t ) r.dev.max_stack;
         p.leaf_cull = ( c.cull_ok && shortcut ) ? 1u : 0u;
     }
-    if ( s->test_pad_stack > 0 ) p.stack_depth += ( uint32_t ) s->test_pad_stack;          // TEST HOOK (fill_params): a deeper stack than the tree needs
+    apply_stack_hooks ( s, rp );
+    p.stack_depth = rp.stack_depth; p.spill_cap = rp.spill_cap;
     p.scene.sincos24 = nullptr;
     const hipError_t e = terra_launch_query ( p, d_rays, n, d_out, anyhit, stream );
     if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "ray query launch: %s", hipGetErrorString ( e ) );
@@ -1907,8 +1913,7 @@ static int query_host ( HTerraScene h, const TerraAmdRay* rays, size_t n, void* 
     if ( int rc = query_check ( s, rays, n, out, what ) ) return rc;
     if ( n == 0 ) return 0;
     HIP_TRY ( hipSetDevice ( primary ( s ).device ), kTerraAmdErrNoDevice );
-    const TreeChoice& tc = s->tree;
-    const float limit = ( tc.reach || tc.reach_cull ) ? tc.reach_limit : TERRA_CULL_MAX_COORD;
+    const float limit = shortcut_limit ( s->tree );
     bool shortcut = true;
     for ( size_t i = 0; i < n && shortcut; ++i ) shortcut = fabsf ( rays[i].origin[0] ) <= limit && fabsf ( rays[i].origin[1] ) <= limit && fabsf ( rays[i].origin[2] ) <= limit;
     FrameCopy c;
@@ -2292,8 +2297,7 @@ static int render_host ( const TerraCamera* cam, Scene* s, const TerraFramebuffe
 // With ONE device in the set the same calls run: a communicator of one rank, the gather a copy inside the device.
 static int render_host_multi ( const TerraCamera* cam, Scene* s, const TerraFramebuffer* fb, size_t x, size_t y, size_t w, size_t h, size_t tile ) {
     if ( !fb || !fb->pixels || !fb->results ) return fail ( kTerraAmdErrBadArgument, "null framebuffer" );
-    if ( !s->committed ) return fail ( kTerraAmdErrNotCommitted, "terra_scene_commit has not run since the scene changed" );
-    if ( !s->device_ok ) return fail ( kTerraAmdErrNoDevice, "scene has no device replica: %s", s->commit_error.c_str() );
+    if ( int rc = scene_check ( s ) ) return rc;
     if ( tile == 0 || tile % 16 != 0 ) return fail ( kTerraAmdErrBadArgument, "tile_size %zu must be a positive multiple of 16", tile );
     std::lock_guard<std::mutex> lock ( s->multi_lock );
     const int world = ( int ) s->replicas.size();

@@ -65,7 +65,7 @@ enum { kPsRayIter = 0, kPsNodeIter, kPsLeafIter, kPsShadeIter, kPsCamIter, kPsCa
 // launch only computes "which leaf boxes does this ray pass", so the block also stages the scene's DISTINCT leaf boxes (DevLeafBox: the two triangles of an
 // axis-aligned quad share one box bit for bit; the Cornell box has 16 for its 32 triangles) and a tame wave tests every one of them in a wave-uniform loop -- no
 // stack, no child words, no trip count set by the slowest lane. The table takes NO LDS of its own: a 48-byte-per-box table beside the other sections would put the
-// Cornell block (terra_lds_bytes: 31,760 B) at 32,592 B, past the TERRA_LDS_BUDGET that keeps five blocks per CU resident (DESIGN.md 3.1 "Flat leaf-box test" has
+// Cornell block (launch_plan.h terra_lds_bytes: 31,760 B) at 32,592 B, past the TERRA_LDS_BUDGET that keeps five blocks per CU resident (DESIGN.md 3.1 "Flat leaf-box test" has
 // the arithmetic). It lives in words the ranked layout leaves unused,
 //     the two pad words of the ranked triangle entries (the `- -` above): entry 6 k + 2 a + s (counted through the copies) = box k, axis a:
 //         (min, max) for s = 0, (max, min) for s = 1 -- "both signs", as the staged node: a ray reads (near, far) of an axis with one 8-byte load from the slot
@@ -82,11 +82,8 @@ enum { kPsRayIter = 0, kPsNodeIter, kPsLeafIter, kPsShadeIter, kPsCamIter, kPsCa
 // followed by the leaf-box table in a part of its own (dev_types.h "pair form": 48 B per box). A pair tested because only its partner's leaf was reached on a walk is
 // harmless for the reason given under "Flat leaf-box test": a triangle whose box the ray misses is not hit.
 // -----------------------------------------------------------------------------
-// (the table's constants and byte offsets: dev_types.h "leaf-box table", shared with the host)
+// (the table's constants and byte offsets: dev_types.h "leaf-box table", shared with the host; TERRA_LEAF_CAP_MAX, TERRA_COL, TERRA_LDS_NODE_BYTES: dev_types.h "launch plan")
 #define TERRA_LEAF_BOX_GROUP 8     // boxes per trip of the unrolled loop (offsets as immediates); four left over are one trip more, the up to three boxes after that are tested one per trip
-#define TERRA_LEAF_CAP_MAX 16
-#define TERRA_COL 256              // stride of a stack / leaf-list column: the block's thread count
-#define TERRA_LDS_NODE_BYTES 112   // staged node (see above)
 
 struct Tracer {
     DevScene      sc;
@@ -121,6 +118,20 @@ struct Tracer {
     // ... and the ranked entries are pairs (see "Pair form" above); launch constant, only ever set in launches without work counters
     bool pairs;
 };
+// The Tracer of a launch that stages nothing (the AOV, query and unit kernels): the scene read from HBM; words = the block's stack_depth stack entries, then leaf_cap
+// leaf-list entries, each 256 ints; spill = the HBM part of the launch's fast-tree stacks, spill_cap words per lane of the grid, lane blockIdx.x * 256 + threadIdx.x's
+// being its own (nullptr: the column holds the whole stack). No cull: a kernel that has one sets it afterwards, as does one that numbers its lanes otherwise.
+TD Tracer unstaged_tracer ( const DevScene& sc, int* words, uint32_t stack_depth, uint32_t leaf_cap, uint32_t* spill, uint32_t spill_cap ) {
+    Tracer T;
+    T.sc = sc; T.l_nodes = nullptr; T.l_tris = nullptr; T.l_props = nullptr; T.l_ranked = nullptr; T.n_boxes = 0;
+    T.l_mats = sc.mats; T.l_lights = sc.lights; T.l_area = sc.tri_area;
+    T.lds_nodes = 0; T.lds_tris = 0; T.ranked = false; T.pairs = false;
+    T.stack = words + threadIdx.x; T.leaves = words + stack_depth * TERRA_COL + threadIdx.x; T.leaf_cap = ( int ) leaf_cap; T.stack_cap = ( int ) stack_depth;
+    T.stack_lim = ( uint32_t ) ( uintptr_t ) words + stack_depth * 1024u;
+    T.spill = spill ? spill + ( size_t ) ( blockIdx.x * 256u + threadIdx.x ) * spill_cap : nullptr; T.spill_cap = spill ? spill_cap : 0u;
+    T.faults = nullptr; T.cull = false; T.fused = false;
+    return T;
+}
 
 // -----------------------------------------------------------------------------
 // BVH traversal (reference src/TerraBVH.c:250-310), restructured without changing

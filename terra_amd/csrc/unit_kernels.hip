@@ -100,11 +100,7 @@ hipError_t terra_unit_moller_trumbore ( int n, const float* o, const float* d, c
 
 // unit kernels read the scene from global memory (MODE 0); LDS only holds stack + leaf list
 __device__ __forceinline__ Tracer unit_tracer ( const DevScene& sc, int* lds ) {
-    Tracer T; T.sc = sc; T.l_nodes = nullptr; T.l_tris = nullptr; T.l_props = nullptr; T.l_mats = sc.mats; T.l_lights = sc.lights; T.l_area = sc.tri_area; T.lds_nodes = 0; T.lds_tris = 0;
-    T.stack = lds + threadIdx.x; T.leaves = lds + ( sc.max_stack < 1 ? 1 : sc.max_stack ) * 256 + threadIdx.x; T.leaf_cap = TERRA_LEAF_CAP_MAX;
-    T.stack_lim = 0; T.spill = nullptr; T.spill_cap = 0;
-    T.stack_cap = sc.max_stack < 1 ? 1 : sc.max_stack; T.faults = nullptr; T.cull = false; T.fused = false; T.ranked = false; T.pairs = false; T.l_ranked = nullptr; T.n_boxes = 0;      // unit level: the reference's traversal decision by decision       // (unit kernels are not built with TERRA_CHECK_BOUNDS)
-    return T;
+    return unstaged_tracer ( sc, lds, ( uint32_t ) ( sc.max_stack < 1 ? 1 : sc.max_stack ), TERRA_LEAF_CAP_MAX, nullptr, 0 );      // no cull at unit level: the reference's traversal decision by decision       // (unit kernels are not built with TERRA_CHECK_BOUNDS)
 }
 __global__ __launch_bounds__ ( 256 ) void k_bvh_traverse ( DevScene sc, int n, const float* o, const float* d, int* found, uint32_t* prim, float* point ) {
     extern __shared__ int lds_stack[];
@@ -136,9 +132,8 @@ __global__ __launch_bounds__ ( 256 ) void k_bvh_traverse_fast ( DevScene sc, int
     Ray r = make_ray ( v3p ( o + 3 * i ), v3p ( d + 3 * i ) );
     RayState s = ray_state_init ( r );
     Counters c = counters_zero();
-    Tracer T; T.sc = sc; T.l_nodes = nullptr; T.l_tris = nullptr; T.l_props = nullptr; T.l_mats = sc.mats; T.l_lights = sc.lights; T.l_area = sc.tri_area; T.lds_nodes = 0; T.lds_tris = 0;
-    T.stack = lds_stack + threadIdx.x; T.leaves = T.stack; T.leaf_cap = 0; T.stack_cap = ( int ) lds_entries; T.faults = nullptr; T.cull = false; T.fused = false; T.ranked = false; T.pairs = false; T.l_ranked = nullptr; T.n_boxes = 0;
-    T.stack_lim = ( uint32_t ) ( uintptr_t ) lds_stack + lds_entries * 1024u; T.spill = spill ? spill + ( size_t ) i * spill_cap : nullptr; T.spill_cap = spill_cap;
+    Tracer T = unstaged_tracer ( sc, lds_stack, lds_entries, 0, nullptr, 0 );
+    T.spill = spill ? spill + ( size_t ) i * spill_cap : nullptr; T.spill_cap = spill_cap;          // (one lane per ray: the lane's part of the spill area is its ray's)
     ClosestRanked b = bvh_traverse_fast<1> ( T, r, s, c );
     bool f = b.tri != 0xffffffffu;
     found[i] = f ? 1 : 0;

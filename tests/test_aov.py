@@ -116,6 +116,33 @@ def test_alignment_hall_x100_reachability_mode(L):
     check_alignment(*aligned_frames(L, lambda i: scaled(scenes.sponza_hall(64, 36, 2, integrator=i), 100.0)))
 
 
+def test_fast_tree_stack_hooks_leave_the_buffer_unchanged(H, L):
+    """The AOV launcher sizes its LDS and its stack spill from the plan the call hands it (launch_plan.h: terra_clamp_leaf_cap, terra_spill_bytes). On the forced
+    fast tree (tree mode 1: the launcher takes the stack from the call; the reference tree's it plans itself, so the hooks do nothing there) a short LDS column
+    sends nearly every push to the HBM part, and 60 padded entries make the block ask for more than 64 KB, which the launcher opts in to: the same buffer, bit
+    for bit, each time."""
+    import torch
+    from terra_amd import runtime
+    from test_oracle_vs_reference import soup_scene
+    d = soup_scene(H, 1500, 77); d.width, d.height, d.spp = 64, 40, 2
+    s = _scene(L, d, tree_mode=1)
+    cam = scenes.camera_of(d)
+
+    def render():
+        aov = runtime.DeviceAov(d.width, d.height)
+        runtime.render_aov_device(L, cam, s, aov); torch.cuda.synchronize()
+        return aov.host().copy()
+    try:
+        plain = render()
+        assert plain["coverage"].sum() > 0
+        for fast_lds, pad in ((1, 0), (2, 0), (0, 60)):
+            runtime.check(L.debug_fast_stack_lds(s, fast_lds)); runtime.check(L.debug_pad_stack(s, pad))
+            assert np.array_equal(render().view(np.uint8), plain.view(np.uint8)), (fast_lds, pad)
+    finally:
+        L.debug_fast_stack_lds(s, 0); L.debug_pad_stack(s, 0)
+        L.scene_destroy(s)
+
+
 @pytest.mark.parametrize("make", [scenes.cornell_box, scenes.cornell_phong], ids=["diffuse", "phong"])
 def test_exact_first_hits(H, L, make):
     """spp 1, no jitter: every pixel's first hit is the pixel-centre ray's, as the unit camera + raycast give it"""

@@ -795,7 +795,7 @@ def test_decoupled_loop_matches_the_oracle(H, L, orc_lib, devmath_mode, name, in
 
 
 # ---------------------------------------------------------------------------
-# a traversal stack deeper than 64 KB of LDS per block (render_kernels.hip launch_instance opts in; terra_plan_lds clamps the leaf list). The reference's own builder
+# a traversal stack deeper than 64 KB of LDS per block (render_kernels.hip launch_instance opts in; launch_plan.h terra_plan_lds / terra_clamp_leaf_cap clamp the leaf list). The reference's own builder
 # only produces such stacks on inputs of pathological size, so the launches are driven through the test hook terra_amd_debug_pad_stack on an ordinary scene.
 # ---------------------------------------------------------------------------
 

@@ -83,7 +83,7 @@ def test_headless_against_the_reference_says_so_and_writes_the_plain_image(H, re
 
 def test_sanitizer_stand_ins_cover_every_launcher(H, tmp_path):
     """the harness links the host layer against tools/sanitize/stub_launchers.cpp: every launcher kernels.h declares that the host layer calls is defined
-    there, and the host layer plus the stand-ins link with no undefined terra_ symbol"""
+    there, every terra_ function defined there is such a launcher, and the host layer plus the stand-ins link with no undefined terra_ symbol"""
     csrc = H.ROOT / "terra_amd" / "csrc"
     declared = set(re.findall(r"\b(terra_launch_\w+|terra_unit_\w+|terra_build_fast_tree_device|terra_fill_sincos24)\s*\(", (csrc / "kernels.h").read_text()))
     stubs = (H.ROOT / "tools" / "sanitize" / "stub_launchers.cpp").read_text()
@@ -93,6 +93,9 @@ def test_sanitizer_stand_ins_cover_every_launcher(H, tmp_path):
             assert re.search(rf"\b{name}\s*\(", stubs), f"{name} has no stand-in"
     for name in ("terra_launch_moments_accumulate", "terra_launch_tile_error", "terra_launch_denoise_variance"):
         assert name in stubs
+    # ... and the converse: the stand-in file defines launchers only -- how a launch is planned is launch_plan.h, which the CPU build runs as the product does
+    defined = set(re.findall(r"^[\w\s\*]*?\b(terra_\w+)\s*\(", stubs, re.M))
+    assert defined and defined <= declared, f"stand-ins that kernels.h does not declare as launchers: {sorted(defined - declared)}"
     so = tmp_path / "libhost.so"
     r = subprocess.run(["g++", "-std=c++17", "-O0", "-fPIC", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", f"-I{csrc}", "-w", "-shared", "-o", str(so),
                         str(csrc / "scene_host.cpp"), str(csrc / "tree_build.cpp"), str(csrc / "multi_gpu.cpp"), str(H.ROOT / "tools" / "sanitize" / "stub_launchers.cpp")],

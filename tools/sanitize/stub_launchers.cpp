@@ -3,16 +3,9 @@
 #include "kernels.h"
 hipError_t terra_launch_render ( const DevRenderParams&, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_launch_job_streams ( const DevRenderParams&, hipStream_t ) { return hipErrorNoDevice; }
-size_t terra_job_streams_bytes ( const DevRenderParams& ) { return 0; }
-size_t terra_block_order_bytes ( const DevRenderParams&, bool ) { return 0; }
-uint32_t   terra_job_order_min_blocks ( void ) { return 256; }
 hipError_t terra_launch_block_order ( const DevRenderParams&, uint32_t*, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_fill_sincos24 ( float2*, hipStream_t ) { return hipErrorNoDevice; }
-bool       terra_render_wants_queue ( const DevRenderParams& ) { return false; }
-uint32_t   terra_render_blocks ( const DevRenderParams& ) { return 0; }
 hipError_t terra_launch_resolve ( const DevRenderParams&, hipStream_t ) { return hipErrorNoDevice; }
-bool       terra_scene_fits_lds ( uint32_t n_nodes, uint32_t n_tris, int, uint32_t, uint32_t ) { return n_nodes * 64 + n_tris * 112 < 8192; }
-void       terra_plan_lds ( DevRenderParams& ) {}
 hipError_t terra_launch_tiles ( bool, float*, void*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, float*, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_unit_pcg ( const uint32_t*, int, int, float* ) { return hipErrorNoDevice; }
 hipError_t terra_unit_stream_keys ( uint64_t, const uint64_t*, const uint64_t*, int, uint64_t* ) { return hipErrorNoDevice; }
@@ -34,11 +27,6 @@ hipError_t terra_unit_distribution_1d ( const float*, uint32_t, float*, float*, 
 hipError_t terra_unit_distribution_2d ( const float*, uint32_t, uint32_t, float*, float*, float*, uint32_t*, const float*, int, float*, float* ) { return hipErrorNoDevice; }
 hipError_t terra_unit_distribution_2d_pdf ( const float*, uint32_t, uint32_t, float*, float*, float*, uint32_t*, const float*, int, float* ) { return hipErrorNoDevice; }
 hipError_t terra_build_fast_tree_device ( const DevTri*, const uint32_t*, uint32_t, float, DevNode*, DevTri*, uint32_t*, int*, hipStream_t ) { return hipErrorNoDevice; }
-void terra_plan_fast_tree ( DevRenderParams& p ) { p.lds_mode = 2; p.lds_tris = 0; p.leaf_cap = 0; p.stack_depth = 1; p.lds_nodes = 0; p.spill_cap = 0; p.stack_spill = nullptr; }
-size_t terra_fast_spill_bytes ( const DevRenderParams& ) { return 0; }
-size_t terra_lds_bytes ( const DevRenderParams& ) { return 0; }
-bool   terra_leaf_boxes_fit ( const DevRenderParams&, uint32_t ) { return false; }
-size_t terra_lds_block_limit ( void ) { return 156 * 1024; }
 hipError_t terra_launch_aov ( DevRenderParams, void*, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_launch_denoise ( const void*, const void*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, int, float, int, float, float*, float*, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_launch_moments_accumulate ( const void*, void*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, hipStream_t ) { return hipErrorNoDevice; }
