@@ -655,6 +655,47 @@ int terra_amd_occluded_device  ( HTerraScene scene, const void* d_rays, size_t n
 int terra_amd_intersect ( HTerraScene scene, const TerraAmdRay* rays, size_t n, TerraAmdHit* hits );
 int terra_amd_occluded  ( HTerraScene scene, const TerraAmdRay* rays, size_t n, uint32_t* occluded );
 
+/* ---- Ray-sourced rendering: terra_render() along a client's own primary rays ---------------------------------------------------------------------------------
+   The third door: radiance -- the scene's integrator, bounces and options, every switch of this header -- along rays that are not the pinhole camera's. Light
+   probes, lightmap and irradiance baking with full global illumination, panoramic / fisheye / orthographic cameras, thin-lens depth of field (a new ray buffer
+   per batch). The output is a framebuffer, so the AOV pass (its ray-sourced form below), both denoisers, the moments buffer and a client's own adaptive loop
+   work on such frames as they do on camera frames.
+   Ray buffer.  TerraAmdRay records (the struct of the ray queries), one per pixel of the frame, indexed like the frame (y * fb_width + x), 16-byte aligned.
+     Only the rectangle's records are read.
+   Which ray a sample traces.  Every sample of pixel (x, y), in this call, traces that pixel's ray -- exactly as terra_render() traces a camera ray with that
+     origin and direction: terra_trace with the reference's 0.001 origin offset (UNLIKE the ray queries, which add none), the scene's integrator, bounces and
+     options. direction is used as given and must have unit length: the library does not normalise it, so a client that passes the camera's own positions and
+     directions gets the camera call's framebuffer bit for bit. tmax and reserved are IGNORED: a primary ray has no limit, like a camera ray.
+   Streams.  As in a camera call: keyed (frame seed + pixel index, samples already in the pixel + chunk * chunk spp); stream A is advanced by the two camera
+     draws and then by the sampler integration's pair, exactly as a camera sample advances it -- only their use for the direction falls away; stream B is
+     untouched. A client that wants anti-aliasing or lens sampling renders several batches with a new ray buffer each: the running sums and the keying by
+     samples-so-far make the batches independent.
+   Inactive rays.  A ray whose direction is exactly (0, 0, 0), or any of whose six origin and direction components is not finite, is inactive: nothing is traced
+     for it, it draws nothing (its d_rand_calls entry is 0) and its pixel receives samples_per_pixel samples of +0. This is how a bake skips uncovered texels
+     and how a 1-D batch is padded to a frame.
+   Launch.  A render launch in every other respect: the same sample split (terra_amd_set_sample_split; the AUTOMATIC split is the one of a launch without the
+     job order, so it can differ from the camera call's), job queue, resolve, tonemap, statistics (terra_amd_get_stats), d_rand_calls and work counters, flat
+     leaf-box test and pair form. It never has the job order or the empty skip (terra_amd_set_job_order, terra_amd_set_empty_skip): both are made from camera
+     rays. Traversal: the one the commit chose, with the rule of the ray queries -- the host forms look at the active rays' origins and run the replica traversal
+     (TerraAmdTraversalInfo::last_call == kTerraAmdCallReplica) when one lies beyond TerraAmdTraversalInfo::camera_limit on some axis; the device forms cannot
+     look at rays in HBM: keep origins within camera_limit.
+   AOV form.  terra_amd_render_aov_device() with the same substitution: depth sums |hit point - ray origin|, an inactive ray adds samples_per_pixel to
+     `samples` and nothing else; the sample split is the one the ray-sourced render call takes.
+   Calls.  They fail like the camera forms -- kTerraAmdErrNotCommitted, a bad rectangle or a NULL buffer (kTerraAmdErrBadArgument), an integrator that needs a
+     light in a scene without one -- and with kTerraAmdErrBadArgument for a ray buffer that is not 16-byte aligned; nothing is launched then. A scene committed
+     for several devices answers on its primary device. */
+/* d_rays: fb_width * fb_height TerraAmdRay in HBM; the other arguments as terra_amd_render_device(). Asynchronous on `stream`. */
+int terra_amd_render_rays_device ( HTerraScene scene, const void* d_rays, void* d_pixels, void* d_results, size_t fb_width, size_t fb_height,
+                                   size_t x, size_t y, size_t width, size_t height, void* d_rand_calls, void* stream );
+/* The same on a host framebuffer and host rays (frame-indexed): the rectangle's rays and running sums are uploaded, the rectangle comes back; synchronous. */
+int terra_amd_render_rays ( HTerraScene scene, const TerraAmdRay* rays, const TerraFramebuffer* framebuffer, size_t x, size_t y, size_t width, size_t height );
+/* d_aov as terra_amd_render_aov_device() takes it. Asynchronous on `stream`. */
+int terra_amd_render_aov_rays_device ( HTerraScene scene, const void* d_rays, void* d_aov, size_t fb_width, size_t fb_height,
+                                       size_t x, size_t y, size_t width, size_t height, void* stream );
+/* The same on host buffers (frame-indexed); synchronous. */
+int terra_amd_render_aov_rays ( HTerraScene scene, const TerraAmdRay* rays, TerraAmdAovResult* aov, size_t fb_width, size_t fb_height,
+                                size_t x, size_t y, size_t width, size_t height );
+
 /* Tile-sharded form for one-process-per-GPU rendering (the reference shards
    the same way over CPU threads: satellite/src/Renderer.cpp:316-350): the
    rectangle is cut into tile_size x tile_size tiles numbered row-major and this

@@ -200,6 +200,14 @@ RAY_QUERY_SIGNATURES = {
     "terra_amd_occluded": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
+# ... and of ray-sourced rendering (include/terra_amd.h "Ray-sourced rendering")
+RAY_SOURCE_SIGNATURES = {
+    "terra_amd_render_rays_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p] + [c_size_t] * 6 + [c_void_p, c_void_p]),
+    "terra_amd_render_rays": (c_int, [c_void_p, c_void_p, POINTER(TerraFramebuffer)] + [c_size_t] * 4),
+    "terra_amd_render_aov_rays_device": (c_int, [c_void_p, c_void_p, c_void_p] + [c_size_t] * 6 + [c_void_p]),
+    "terra_amd_render_aov_rays": (c_int, [c_void_p, c_void_p, c_void_p] + [c_size_t] * 6),
+}
+
 # entry points of include/Terra.h + include/TerraPresets.h, name -> (restype, argtypes)
 API_SIGNATURES = {
     "scene_create": (c_void_p, []),

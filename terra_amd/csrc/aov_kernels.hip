@@ -6,6 +6,10 @@
 // pair), the same sample split (scene_host.cpp launch_split) and the traversal the render call would take (fill_params). A 256-thread block holds 256 / split
 // pixels x split chunks; the chunk sums meet in LDS and the chunk-0 lane of each pixel adds them to the buffer in chunk order -- what terra_resolve_kernel does.
 // The grid is capped and strides over the blocks (the fast tree's stack spill is sized for the grid, not the frame).
+//
+// Compiled twice (terra_amd/build.py): as it stands, and with TERRA_TU=4 as the RAY-SOURCED unit (TERRA_RAY_SOURCE, dev_types.h; include/terra_amd.h "Ray-sourced
+// rendering"), whose kernel terra_aov_rays_kernel and launcher terra_launch_aov_rays take a ray buffer -- one TerraAmdRay per pixel, addressed like the AOV buffer -- and trace the pixel's
+// ray for every sample: depth sums |hit point - ray origin|, an inactive ray adds its samples and nothing else. The camera unit's code is the same with and without it.
 #include <hip/hip_runtime.h>
 #include "trace_device.h"
 #include "kernels.h"
@@ -18,8 +22,15 @@ static_assert ( sizeof ( DevAov ) == 48, "DevAov must be 48 bytes" );
 #define TERRA_AOV_FOLD_BYTES ( 2 * 256 * 16 )       // the block's chunk sums: two float4 per lane
 #define TERRA_AOV_MAX_BLOCKS_PER_CU 8
 
+#if TERRA_RAY_SOURCE
+#define TERRA_AOV_KERNEL terra_aov_rays_kernel
+#define TERRA_AOV_RAYS_PARAM , const float4* rays
+#else
+#define TERRA_AOV_KERNEL terra_aov_kernel
+#define TERRA_AOV_RAYS_PARAM
+#endif
 template <int MODE>
-__global__ __launch_bounds__ ( 256 ) void terra_aov_kernel ( DevRenderParams p, float4* aov, uint32_t* spill, uint32_t vblocks, uint32_t blocks_x ) {
+__global__ __launch_bounds__ ( 256 ) void TERRA_AOV_KERNEL ( DevRenderParams p, float4* aov, uint32_t* spill, uint32_t vblocks, uint32_t blocks_x TERRA_AOV_RAYS_PARAM ) {
     extern __shared__ float4 lds_f4[];
     const uint32_t tid = threadIdx.x;
     float4* fold = lds_f4;
@@ -39,6 +50,29 @@ __global__ __launch_bounds__ ( 256 ) void terra_aov_kernel ( DevRenderParams p, 
         const uint32_t px = p.x + lx, py = p.y + ly;
         const size_t pix = inside ? ( size_t ) ( py - p.st_y ) * p.st_pitch + ( px - p.st_x ) : 0;
         float4 s0 = make_float4 ( 0.f, 0.f, 0.f, 0.f ), s1 = make_float4 ( 0.f, 0.f, 0.f, 0.f );
+#if TERRA_RAY_SOURCE
+        if ( inside ) {
+            // every sample of the pixel traces the pixel's ray (no draw decides anything here): one traversal, its hit added once per sample, in sample order
+            const float4* rec = rays + 2 * pix;
+            const float4 q0 = rec[0], q1 = rec[1];          // {origin, tmax} {direction, reserved}
+            const V3 ro = v3 ( q0.x, q0.y, q0.z ), rd = v3 ( q1.x, q1.y, q1.z );
+            const bool finite = fabsf ( ro.x ) < INFINITY && fabsf ( ro.y ) < INFINITY && fabsf ( ro.z ) < INFINITY && fabsf ( rd.x ) < INFINITY && fabsf ( rd.y ) < INFINITY && fabsf ( rd.z ) < INFINITY;
+            if ( finite && ! ( rd.x == 0.f && rd.y == 0.f && rd.z == 0.f ) ) {          // (else: an inactive ray)
+                Surface sf;
+                Counters c = counters_zero();
+                const RaycastResult h = scene_raycast<0, MODE, TERRA_KINDS_ALL> ( T, make_ray ( ro, rd ), sf, c );
+                if ( h.hit ) {
+                    const V3 a = sf.bsdf == kDevBsdfPhong ? sf.attr[1] : sf.attr[0];
+                    const float dist = length ( ro - h.point );
+                    for ( uint32_t s = 0; s < p.chunk_spp; ++s ) {
+                        s0.x = s0.x + a.x; s0.y = s0.y + a.y; s0.z = s0.z + a.z; s0.w = s0.w + 1.f;
+                        s1.x = s1.x + sf.normal.x; s1.y = s1.y + sf.normal.y; s1.z = s1.z + sf.normal.z;
+                        s1.w = s1.w + dist;
+                    }
+                }
+            }
+        }
+#else
         if ( inside ) {
             const int prior = __float_as_int ( aov[3 * pix + 2].x );
             const uint32_t base = ( uint32_t ) prior + chunk * p.chunk_spp;     // (job_next: j.base)
@@ -58,6 +92,7 @@ __global__ __launch_bounds__ ( 256 ) void terra_aov_kernel ( DevRenderParams p, 
                 }
             }
         }
+#endif
         fold[tid] = s0; fold[256 + tid] = s1;
         __syncthreads();
         if ( chunk == 0 && inside ) {
@@ -74,7 +109,14 @@ __global__ __launch_bounds__ ( 256 ) void terra_aov_kernel ( DevRenderParams p, 
     }
 }
 
+#if TERRA_RAY_SOURCE
+#define TERRA_AOV_RAYS_ARG , reinterpret_cast<const float4*> ( rays )
+hipError_t terra_launch_aov_rays ( DevRenderParams p, const void* rays, void* aov, hipStream_t stream ) {
+    if ( !rays ) return hipErrorInvalidValue;
+#else
+#define TERRA_AOV_RAYS_ARG
 hipError_t terra_launch_aov ( DevRenderParams p, void* aov, hipStream_t stream ) {
+#endif
     const uint32_t blocks_x = ( p.w + 15u ) / 16u, blocks_y = ( p.h + 15u ) / 16u;
     const uint64_t vblocks = ( uint64_t ) blocks_x * blocks_y * p.split;
     if ( vblocks == 0 ) return hipSuccess;
@@ -89,15 +131,15 @@ hipError_t terra_launch_aov ( DevRenderParams p, void* aov, hipStream_t stream )
     else { p.stack_depth = p.scene.max_stack < 1 ? 1u : ( uint32_t ) p.scene.max_stack; p.leaf_cap = terra_unstaged_leaf_cap ( p.stack_depth, TERRA_AOV_FOLD_BYTES ); p.spill_cap = 0; }
     const size_t lds = ( size_t ) ( p.stack_depth + ( mode == 0 ? p.leaf_cap : 0u ) ) * 1024 + TERRA_AOV_FOLD_BYTES;
     if ( lds > terra_lds_block_limit() ) return hipErrorInvalidValue;
-    const void* fn = mode == 0 ? reinterpret_cast<const void*> ( terra_aov_kernel<0> ) : mode == 2 ? reinterpret_cast<const void*> ( terra_aov_kernel<2> ) : reinterpret_cast<const void*> ( terra_aov_kernel<3> );
+    const void* fn = mode == 0 ? reinterpret_cast<const void*> ( TERRA_AOV_KERNEL<0> ) : mode == 2 ? reinterpret_cast<const void*> ( TERRA_AOV_KERNEL<2> ) : reinterpret_cast<const void*> ( TERRA_AOV_KERNEL<3> );
     if ( lds > ( size_t ) 64 * 1024 ) { const hipError_t e = hipFuncSetAttribute ( fn, hipFuncAttributeMaxDynamicSharedMemorySize, ( int ) lds ); if ( e != hipSuccess ) return e; }
     uint32_t* spill = nullptr;
     const size_t spill_bytes = mode != 0 ? terra_spill_bytes ( grid, p.spill_cap ) : 0;
     if ( spill_bytes ) { const hipError_t e = hipMallocAsync ( ( void** ) &spill, spill_bytes, stream ); if ( e != hipSuccess ) return e; }
     float4* out = reinterpret_cast<float4*> ( aov );
-    if ( mode == 0 ) hipLaunchKernelGGL ( terra_aov_kernel<0>, dim3 ( grid ), dim3 ( 256 ), lds, stream, p, out, spill, ( uint32_t ) vblocks, blocks_x );
-    else if ( mode == 2 ) hipLaunchKernelGGL ( terra_aov_kernel<2>, dim3 ( grid ), dim3 ( 256 ), lds, stream, p, out, spill, ( uint32_t ) vblocks, blocks_x );
-    else hipLaunchKernelGGL ( terra_aov_kernel<3>, dim3 ( grid ), dim3 ( 256 ), lds, stream, p, out, spill, ( uint32_t ) vblocks, blocks_x );
+    if ( mode == 0 ) hipLaunchKernelGGL ( TERRA_AOV_KERNEL<0>, dim3 ( grid ), dim3 ( 256 ), lds, stream, p, out, spill, ( uint32_t ) vblocks, blocks_x TERRA_AOV_RAYS_ARG );
+    else if ( mode == 2 ) hipLaunchKernelGGL ( TERRA_AOV_KERNEL<2>, dim3 ( grid ), dim3 ( 256 ), lds, stream, p, out, spill, ( uint32_t ) vblocks, blocks_x TERRA_AOV_RAYS_ARG );
+    else hipLaunchKernelGGL ( TERRA_AOV_KERNEL<3>, dim3 ( grid ), dim3 ( 256 ), lds, stream, p, out, spill, ( uint32_t ) vblocks, blocks_x TERRA_AOV_RAYS_ARG );
     const hipError_t e = hipGetLastError();
     if ( spill ) ( void ) hipFreeAsync ( spill, stream );
     return e;

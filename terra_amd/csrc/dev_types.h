@@ -320,3 +320,16 @@ struct DevRenderParams {
     // that never read it keep their argument offsets.)
     uint32_t leaf_pairs;
 };
+// ray-sourced launches (include/terra_amd.h "Ray-sourced rendering"): the launch's parameters end with the ray buffer -- one TerraAmdRay (two 16-byte words) per pixel,
+// addressed like `results` (st_x / st_y / st_pitch: the frame for the device forms, the staged rectangle for the host forms). The pointer follows DevRenderParams' last field in a structure of its own, which only
+// the ray-sourced kernel instances take: no field of DevRenderParams moves and the camera kernels keep their kernel-argument segment to the byte.
+struct DevRayRenderParams : DevRenderParams { const float4* rays; };
+// Ray-sourced kernel instances are units of their own: render_kernels.hip and aov_kernels.hip compiled with TERRA_TU >= 4 (terra_amd/build.py), or with
+// -DTERRA_RAY_SOURCE=1 and no TERRA_TU (tools/kernel_resources.sh).
+#ifndef TERRA_RAY_SOURCE
+#if defined ( TERRA_TU ) && TERRA_TU >= 4
+#define TERRA_RAY_SOURCE 1
+#else
+#define TERRA_RAY_SOURCE 0
+#endif
+#endif

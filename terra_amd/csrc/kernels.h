@@ -11,6 +11,14 @@ hipError_t terra_launch_render_mode0 ( const DevRenderParams& p, size_t lds, hip
 hipError_t terra_launch_render_mode1 ( const DevRenderParams& p, size_t lds, hipStream_t stream );
 hipError_t terra_launch_render_mode2 ( const DevRenderParams& p, size_t lds, hipStream_t stream );
 hipError_t terra_launch_render_mode3 ( const DevRenderParams& p, size_t lds, hipStream_t stream );
+// ray-sourced launches (include/terra_amd.h "Ray-sourced rendering"): terra_launch_render with every primary ray read from rays = one TerraAmdRay per pixel, addressed
+// like p.results (st_x / st_y / st_pitch), in place of the camera sample; p without job order and empty skip (block_order, job_live null). The ray-sourced kernel instances
+// are units of their own (render_kernels.hip TERRA_TU 4 - 7)
+hipError_t terra_launch_render_rays ( const DevRenderParams& p, const void* rays, hipStream_t stream );
+hipError_t terra_launch_render_rays_mode0 ( const DevRayRenderParams& p, size_t lds, hipStream_t stream );
+hipError_t terra_launch_render_rays_mode1 ( const DevRayRenderParams& p, size_t lds, hipStream_t stream );
+hipError_t terra_launch_render_rays_mode2 ( const DevRayRenderParams& p, size_t lds, hipStream_t stream );
+hipError_t terra_launch_render_rays_mode3 ( const DevRayRenderParams& p, size_t lds, hipStream_t stream );
 hipError_t terra_launch_resolve ( const DevRenderParams& p, hipStream_t stream );   // second kernel of a split render (p.split > 1)
 hipError_t terra_launch_tiles ( bool pack, float* pixels, void* results, uint32_t fb_w, uint32_t x, uint32_t y, uint32_t w, uint32_t h,
                                 uint32_t tile, uint32_t rank, uint32_t world, float* packed, hipStream_t stream );
@@ -18,6 +26,9 @@ hipError_t terra_launch_tiles ( bool pack, float* pixels, void* results, uint32_
 // first-hit AOV pass (aov_kernels.hip): p as fill_params made it, with the render's sample split set (split, split_log2, chunk_spp); aov = TerraAmdAovResult
 // per pixel, addressed like p.results (st_x / st_y / st_pitch)
 hipError_t terra_launch_aov ( DevRenderParams p, void* aov, hipStream_t stream );
+// ... with the rays of a ray-sourced launch (as terra_launch_render_rays takes them) in place of the camera's: depth sums |hit point - ray origin|, an inactive ray
+// adds its samples and nothing else (aov_kernels.hip compiled as a unit of its own, TERRA_TU 4)
+hipError_t terra_launch_aov_rays ( DevRenderParams p, const void* rays, void* aov, hipStream_t stream );
 
 // the a-trous denoiser and its variance-guided form (denoise_kernels.hip): results / aov / moments (TerraAmdMoments) / radiance / pixels indexed like a frame of fb_w
 // pixels per row; only the rectangle is read or written; radiance or pixels may be nullptr

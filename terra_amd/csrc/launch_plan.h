@@ -117,9 +117,10 @@ inline size_t terra_job_streams_bytes ( const DevRenderParams& p ) { return ( TE
 // launches of fewer pixel blocks keep the numbering's order (unless terra_amd_set_job_order(scene, 2))
 inline uint32_t terra_job_order_min_blocks ( void ) { return TERRA_JOB_ORDER_MIN_BLOCKS; }
 // scratch of the job order: class word + the two halves of the order per pixel block, or 0: this launch keeps the order of the numbering (p.job_blocks, p.lds_mode set);
-// small_too: also below TERRA_JOB_ORDER_MIN_BLOCKS
-inline size_t terra_block_order_bytes ( const DevRenderParams& p, bool small_too ) {
-    if ( terra_job_streams_bytes ( p ) == 0 || p.scene.n_tris == 0 || p.scene.n_tris > 4096 ) return 0;
+// small_too: also below TERRA_JOB_ORDER_MIN_BLOCKS; ray_source: a ray-sourced launch (kernels.h terra_launch_render_rays) never has one -- the order and the empty
+// skip that rides on it are made from camera rays
+inline size_t terra_block_order_bytes ( const DevRenderParams& p, bool small_too, bool ray_source = false ) {
+    if ( ray_source || terra_job_streams_bytes ( p ) == 0 || p.scene.n_tris == 0 || p.scene.n_tris > 4096 ) return 0;
     const size_t blocks = terra_render_blocks ( p );
     // (not for small launches -- below TERRA_JOB_ORDER_MIN_BLOCKS pixel blocks, a 256 x 256 rectangle: a tile-sized call is one of several in flight, whose work hides its tail,
     //  and its two extra small kernels would queue behind the other callers' render grids: the reference client's tile loop 66.5 -> 72.6 ms with them)

@@ -28,11 +28,21 @@
 // One source, several translation units (terra_amd/build.py compiles this file once per TERRA_TU value, in parallel: a single unit takes 3 minutes):
 //   TERRA_TU 0  everything that is not a render-kernel instance (resolve / tile kernels, the launch dispatch; the plan itself: launch_plan.h) + the kernels of template MODE 0
 //   TERRA_TU 1 / 2 / 3  the kernels of template MODE 1 (LDS-resident scenes) / 2 (fast tree) / 3 (fast tree + reachability replay) and their launcher
-//   undefined   all of it in one unit (tools/kernel_resources.sh, tools/isa_cost.py)
+//   TERRA_TU 4 / 5 / 6 / 7  the RAY-SOURCED kernels of template MODE 0 / 1 / 2 / 3 and their launcher, nothing else (TERRA_RAY_SOURCE, dev_types.h: a primary ray
+//               is the pixel's record of DevRayRenderParams::rays instead of a camera sample). Units of their own, so that units 0 - 3 compile as before
+//   undefined   all of it in one unit (tools/kernel_resources.sh, tools/isa_cost.py); with -DTERRA_RAY_SOURCE=1: every ray-sourced kernel in one unit
 #ifdef TERRA_TU
 #define TERRA_TU_HAS(k) ( TERRA_TU == ( k ) )
+#define TERRA_TU_MODE(k) ( TERRA_TU == ( k ) || TERRA_TU == ( k ) + 4 )      // the unit holds the kernels of template MODE k
 #else
-#define TERRA_TU_HAS(k) 1
+#define TERRA_TU_HAS(k) ( !TERRA_RAY_SOURCE )
+#define TERRA_TU_MODE(k) 1
+#endif
+// what a render kernel instance of this unit takes: where its primary rays come from
+#if TERRA_RAY_SOURCE
+typedef DevRayRenderParams RenderKernelParams;
+#else
+typedef DevRenderParams RenderKernelParams;
 #endif
 
 struct DevResult { float acc[3]; int samples; };
@@ -514,8 +524,53 @@ TD void job_next ( const DevRenderParams& p, float* aux, Jobs& j, PixelStreams& 
     j.s = 0; j.base = ( uint32_t ) prior_samples + chunk * p.chunk_spp;
 }
 
+// ---- primary rays ----------------------------------------------------------------------------------------------------
+// The one place a sample's primary ray is made. Camera launches: the pinhole camera's sample. Ray-sourced launches: the pixel's record of the ray buffer, traced exactly
+// as a camera ray with that origin and direction would be (the direction as given: not normalised). r1 and r2 are drawn either way -- stream A advances alike.
+// TERRA_RAY_HOLD 0: the record is fetched again for every sample (two cached 16-byte loads in place of camera_sample's ~40 instructions, and nothing more held across
+// a job than the camera form holds: the pixel); 1: fetched once per job and held in six registers. Figures of both: profiles/ray_source/kernel_resources.md.
+#ifndef TERRA_RAY_HOLD
+#define TERRA_RAY_HOLD 0
+#endif
+struct PrimaryRay { V3 o, d; };
+TD PrimaryRay ray_record ( const RenderKernelParams& p, uint32_t px, uint32_t py ) {
+    PrimaryRay r; r.o = v3 ( 0, 0, 0 ); r.d = v3 ( 0, 0, 1 );
+#if TERRA_RAY_SOURCE
+    const float4* rec = p.rays + 2 * ( ( size_t ) ( py - p.st_y ) * p.st_pitch + ( px - p.st_x ) );          // addressed like p.results
+    const float4 q0 = rec[0], q1 = rec[1];          // {origin, tmax} {direction, reserved}: a primary ray has no limit, tmax and reserved are not looked at
+    r.o = v3 ( q0.x, q0.y, q0.z ); r.d = v3 ( q1.x, q1.y, q1.z );
+#endif
+    return r;
+}
+// an inactive record traces nothing: a direction of exactly (0, 0, 0), or an origin or direction component that is not finite
+TD bool ray_record_inactive ( const PrimaryRay& r ) {
+    const bool finite = fabsf ( r.o.x ) < INFINITY && fabsf ( r.o.y ) < INFINITY && fabsf ( r.o.z ) < INFINITY && fabsf ( r.d.x ) < INFINITY && fabsf ( r.d.y ) < INFINITY && fabsf ( r.d.z ) < INFINITY;      // (false for a NaN too)
+    return !finite || ( r.d.x == 0.f && r.d.y == 0.f && r.d.z == 0.f );
+}
+// (macros inside the kernel, not functions: the camera units then compile the very statements they always had -- tools/isa_same.sh against the parent)
+#if TERRA_RAY_SOURCE
+#define TERRA_PRIMARY_RAY( ro, rd, r1, r2 ) do { const PrimaryRay pr_ = TERRA_RAY_HOLD ? held : ray_record ( p, jb.px, jb.py ); ro = pr_.o; rd = pr_.d; } while ( 0 )
+#define TERRA_JOB_NEXT() job_take<COUNT, MODE == 1> ( p, acc_lds, jb, rs, c, job_total, held )
+#else
+#define TERRA_PRIMARY_RAY( ro, rd, r1, r2 ) ro = cam_pos; rd = camera_sample ( p, jb.px, jb.py, r1, r2 )
+#define TERRA_JOB_NEXT() job_next<COUNT, MODE == 1> ( p, acc_lds, jb, rs, c, job_total )
+#endif
+// job_next for the kernel's loops. Ray-sourced launches look at the new job's ray here, once per job: an inactive one ends the job where it starts -- its sum stays
+// the +0 job_next set, it draws nothing, and the resolve kernel adds that +0 and the call's samples to the pixel like any other job's sum.
+#if TERRA_RAY_SOURCE
+template <int COUNT, bool TABLE>
+TD void job_take ( const RenderKernelParams& p, float* aux, Jobs& j, PixelStreams& rs, const Counters& c, uint32_t total, PrimaryRay& held ) {
+    job_next<COUNT, TABLE> ( p, aux, j, rs, c, total );
+    if ( j.s != p.chunk_spp ) {          // (a job was taken: job_next leaves s at chunk_spp for a pixel outside the rectangle and for a lane that found nothing)
+        const PrimaryRay r = ray_record ( p, j.px, j.py );
+        if ( ray_record_inactive ( r ) ) j.s = p.chunk_spp;
+        if ( TERRA_RAY_HOLD ) held = r;
+    }
+}
+#endif
+
 template <int INTEGRATOR, int COUNT, int MODE, int KINDS>
-__global__ __launch_bounds__ ( 256, TERRA_WAVES_FOR ( INTEGRATOR, KINDS, MODE ) ) void terra_render_kernel ( DevRenderParams p ) {
+__global__ __launch_bounds__ ( 256, TERRA_WAVES_FOR ( INTEGRATOR, KINDS, MODE ) ) void terra_render_kernel ( RenderKernelParams p ) {
     extern __shared__ float4 lds_f4[];
     const int tid = threadIdx.x;
     Tracer T0 = make_tracer<MODE> ( p.scene, lds_f4, p.stack_depth, p.leaf_cap, p.lds_nodes, p.lds_tris, p.leaf_cull != 0, p.fused_slab != 0, p.leaf_rank != 0, p.leaf_boxes, p.n_leaf_boxes, terra_leaf_pair_table ( p ) );
@@ -536,6 +591,9 @@ __global__ __launch_bounds__ ( 256, TERRA_WAVES_FOR ( INTEGRATOR, KINDS, MODE ) 
     Ray ray = make_ray ( v3 ( 0, 0, 0 ), v3 ( 0, 0, 1 ) );
     uint32_t bounce = 0;
     const V3 cam_pos = v3p ( p.cam_pos );
+#if TERRA_RAY_SOURCE
+    PrimaryRay held; held.o = v3 ( 0, 0, 0 ); held.d = v3 ( 0, 0, 1 );      // the job's ray (TERRA_RAY_HOLD only)
+#endif
 
     if constexpr ( TERRA_DECOUPLED_MIS ( INTEGRATOR, MODE, KINDS ) ) {
         // Decoupled loop for Direct + MIS: like the Direct one below with two shadow jobs per shaded hit, in the reference's
@@ -586,10 +644,10 @@ __global__ __launch_bounds__ ( 256, TERRA_WAVES_FOR ( INTEGRATOR, KINDS, MODE ) 
                     }
                 }
                 if ( !start ) {
-                    if ( jb.s == p.chunk_spp ) { job_next<COUNT, MODE == 1> ( p, acc_lds, jb, rs, c, job_total ); if ( jb.exhausted ) done = true; }
+                    if ( jb.s == p.chunk_spp ) { TERRA_JOB_NEXT(); if ( jb.exhausted ) done = true; }
                     if ( jb.s != p.chunk_spp ) {
                         float r1 = trng_a_float ( rs.a ), r2 = trng_a_float ( rs.a );
-                        ro = cam_pos; rd = camera_sample ( p, jb.px, jb.py, r1, r2 );
+                        TERRA_PRIMARY_RAY ( ro, rd, r1, r2 );
                         if constexpr ( ( KINDS & TERRA_KIND_SAMPLER ) != 0 ) sp = sampler_pair_draw ( p.sampler_mode, p.sampler_strata, ( uint64_t ) jb.base + jb.s, rs.a );
                         Lo = v3 ( 0, 0, 0 ); throughput = v3 ( 1, 1, 1 ); bounce = 0; ++jb.s; job = 0; start = true;
                     }
@@ -638,10 +696,10 @@ __global__ __launch_bounds__ ( 256, TERRA_WAVES_FOR ( INTEGRATOR, KINDS, MODE ) 
                     }
                 }
                 if ( !start ) {                                  // the path ended (or none was started yet): the pixel's next sample, or the lane's next job
-                    if ( jb.s == p.chunk_spp ) { job_next<COUNT, MODE == 1> ( p, acc_lds, jb, rs, c, job_total ); if ( jb.exhausted ) done = true; }
+                    if ( jb.s == p.chunk_spp ) { TERRA_JOB_NEXT(); if ( jb.exhausted ) done = true; }
                     if ( jb.s != p.chunk_spp ) {
                         float r1 = trng_a_float ( rs.a ), r2 = trng_a_float ( rs.a );
-                        ro = cam_pos; rd = camera_sample ( p, jb.px, jb.py, r1, r2 );
+                        TERRA_PRIMARY_RAY ( ro, rd, r1, r2 );
                         if constexpr ( ( KINDS & TERRA_KIND_SAMPLER ) != 0 ) sp = sampler_pair_draw ( p.sampler_mode, p.sampler_strata, ( uint64_t ) jb.base + jb.s, rs.a );
                         Lo = v3 ( 0, 0, 0 ); throughput = v3 ( 1, 1, 1 ); bounce = 0; ++jb.s; start = true;
                     }
@@ -682,10 +740,10 @@ __global__ __launch_bounds__ ( 256, TERRA_WAVES_FOR ( INTEGRATOR, KINDS, MODE ) 
                     if ( !next ) { deposit ( acc_lds, Lo ); have_ray = false; }
                 }
                 if ( !next ) {
-                    if ( jb.s == p.chunk_spp ) { job_next<COUNT, MODE == 1> ( p, acc_lds, jb, rs, c, job_total ); if ( jb.exhausted ) done = true; }
+                    if ( jb.s == p.chunk_spp ) { TERRA_JOB_NEXT(); if ( jb.exhausted ) done = true; }
                     if ( jb.s != p.chunk_spp ) {
                         float r1 = trng_a_float ( rs.a ), r2 = trng_a_float ( rs.a );
-                        ro = cam_pos; rd = camera_sample ( p, jb.px, jb.py, r1, r2 );
+                        TERRA_PRIMARY_RAY ( ro, rd, r1, r2 );
                         if constexpr ( ( KINDS & TERRA_KIND_SAMPLER ) != 0 ) sp = sampler_pair_draw ( p.sampler_mode, p.sampler_strata, ( uint64_t ) jb.base + jb.s, rs.a );
                         Lo = v3 ( 0, 0, 0 ); throughput = v3 ( 1, 1, 1 ); bounce = 0; ++jb.s; next = true;
                     }
@@ -726,12 +784,12 @@ __global__ __launch_bounds__ ( 256, TERRA_WAVES_FOR ( INTEGRATOR, KINDS, MODE ) 
         const bool any_alive = __any ( alive );
         if ( !alive && ( TERRA_REGEN_MIN <= 1 || !any_alive || __popcll ( __ballot ( !alive ) ) >= TERRA_REGEN_MIN ) ) {
             // (a lane waits at the boundary until TERRA_JOB_FETCH_MIN lanes do, or nobody is tracing: the switch then serves several lanes per execution)
-            if ( jb.s == p.chunk_spp && ( TERRA_JOB_FETCH_MIN <= 1 || !any_alive || __popcll ( __ballot ( jb.s == p.chunk_spp ) ) >= TERRA_JOB_FETCH_MIN ) ) job_next<COUNT, MODE == 1> ( p, acc_lds, jb, rs, c, job_total );
+            if ( jb.s == p.chunk_spp && ( TERRA_JOB_FETCH_MIN <= 1 || !any_alive || __popcll ( __ballot ( jb.s == p.chunk_spp ) ) >= TERRA_JOB_FETCH_MIN ) ) TERRA_JOB_NEXT();
             if ( jb.exhausted ) break;
             if ( jb.s != p.chunk_spp ) {
                 PS_WAVE ( c, kPsCamIter ); PS_LANE ( c, kPsCamLanes );
                 float r1 = trng_a_float ( rs.a ), r2 = trng_a_float ( rs.a );
-                ro = cam_pos; rd = camera_sample ( p, jb.px, jb.py, r1, r2 );
+                TERRA_PRIMARY_RAY ( ro, rd, r1, r2 );
                 if constexpr ( ( KINDS & TERRA_KIND_SAMPLER ) != 0 ) sp = sampler_pair_draw ( p.sampler_mode, p.sampler_strata, ( uint64_t ) jb.base + jb.s, rs.a );
                 lo_reset(); throughput = v3 ( 1, 1, 1 ); bounce = 0; alive = true; ++jb.s;
             }
@@ -818,7 +876,7 @@ static uint32_t resident_blocks ( const void* fn, size_t lds ) {
     return blocks;
 }
 template <int I, int COUNT, int MODE, int KINDS>
-static hipError_t launch_instance ( const DevRenderParams& p, size_t lds, hipStream_t stream ) {
+static hipError_t launch_instance ( const RenderKernelParams& p, size_t lds, hipStream_t stream ) {
     auto fn = terra_render_kernel<I, COUNT, MODE, KINDS>;
     if ( lds > ( size_t ) 64 * 1024 ) {          // a traversal stack deeper than ~55 entries (deep reference tree, Morton-ordered tree over clustered geometry): opt in, once per kernel and size
         if ( lds > terra_lds_block_limit() ) return hipErrorInvalidValue;      // (scene_host.cpp launch_render checks first and says why)
@@ -836,7 +894,7 @@ static hipError_t launch_instance ( const DevRenderParams& p, size_t lds, hipStr
     return hipGetLastError();
 }
 template <int I, int MODE, int KINDS>
-static hipError_t launch_kinds ( const DevRenderParams& p, size_t lds, hipStream_t stream ) {
+static hipError_t launch_kinds ( const RenderKernelParams& p, size_t lds, hipStream_t stream ) {
     // work counters are instrumentation, off unless asked for (terra_amd_set_work_counters / a per-pixel draw-count buffer): the counting kernels carry
     // 4-7 more live registers per lane and cost the Cornell frame 6 % (59.3 vs 62.9 ms; profiles/r03_measurements/ab_counters.log)
     if ( p.count_level == 0 ) return launch_instance<I, 0, MODE, KINDS> ( p, lds, stream );
@@ -848,7 +906,7 @@ static hipError_t launch_kinds ( const DevRenderParams& p, size_t lds, hipStream
 #define TERRA_KINDS_PRESETS_VARIANT 1
 #endif
 template <int I, int MODE>
-static hipError_t launch_mode ( const DevRenderParams& p, size_t lds, hipStream_t stream ) {
+static hipError_t launch_mode ( const RenderKernelParams& p, size_t lds, hipStream_t stream ) {
     if ( p.bsdf_kinds == 1 ) return launch_kinds<I, MODE, 1> ( p, lds, stream );
     if ( ( p.bsdf_kinds & ~3u ) == 0 ) return launch_kinds<I, MODE, 3> ( p, lds, stream );
     if constexpr ( TERRA_KINDS_PRESETS_VARIANT && I <= 2 && MODE != 0 ) {       // the four presets on constant attributes, no environment term (BASELINE config 4's sphere scene): the usual integrators, off the reference tree
@@ -861,7 +919,7 @@ static hipError_t launch_mode ( const DevRenderParams& p, size_t lds, hipStream_
     return launch_kinds<I, MODE, TERRA_KINDS_ALL> ( p, lds, stream );
 }
 template <int MODE>
-static hipError_t launch_integrator ( const DevRenderParams& p, size_t lds, hipStream_t stream ) {
+static hipError_t launch_integrator ( const RenderKernelParams& p, size_t lds, hipStream_t stream ) {
     switch ( p.integrator ) {
         case 0: return launch_mode<0, MODE> ( p, lds, stream );
         case 1: return launch_mode<1, MODE> ( p, lds, stream );
@@ -873,7 +931,21 @@ static hipError_t launch_integrator ( const DevRenderParams& p, size_t lds, hipS
         default: return hipErrorInvalidValue;
     }
 }
-// one launcher per template MODE, each in its own translation unit (see the top of the file)
+// one launcher per template MODE and ray source, each in its own translation unit (see the top of the file)
+#if TERRA_RAY_SOURCE
+#if TERRA_TU_MODE ( 0 )
+hipError_t terra_launch_render_rays_mode0 ( const DevRayRenderParams& p, size_t lds, hipStream_t stream ) { return launch_integrator<0> ( p, lds, stream ); }
+#endif
+#if TERRA_TU_MODE ( 1 )
+hipError_t terra_launch_render_rays_mode1 ( const DevRayRenderParams& p, size_t lds, hipStream_t stream ) { return launch_integrator<1> ( p, lds, stream ); }
+#endif
+#if TERRA_TU_MODE ( 2 )
+hipError_t terra_launch_render_rays_mode2 ( const DevRayRenderParams& p, size_t lds, hipStream_t stream ) { return launch_integrator<2> ( p, lds, stream ); }
+#endif
+#if TERRA_TU_MODE ( 3 )
+hipError_t terra_launch_render_rays_mode3 ( const DevRayRenderParams& p, size_t lds, hipStream_t stream ) { return launch_integrator<3> ( p, lds, stream ); }
+#endif
+#endif
 #if TERRA_TU_HAS ( 0 )
 hipError_t terra_launch_render_mode0 ( const DevRenderParams& p, size_t lds, hipStream_t stream ) { return launch_integrator<0> ( p, lds, stream ); }
 #endif
@@ -897,6 +969,18 @@ hipError_t terra_launch_render ( const DevRenderParams& p, hipStream_t stream ) 
     if ( p.lds_mode == 1 ) return terra_launch_render_mode1 ( p, lds, stream );
     if ( p.lds_mode == 2 ) return p.scene.reach ? terra_launch_render_mode3 ( p, lds, stream ) : terra_launch_render_mode2 ( p, lds, stream );
     return terra_launch_render_mode0 ( p, lds, stream );
+}
+// the same launch with its primary rays read from `rays` (DevRayRenderParams): the ray-sourced instances of the same kernels. A ray launch has no job order and no
+// empty skip -- both reason about camera rays (scene_host.cpp launch_render)
+hipError_t terra_launch_render_rays ( const DevRenderParams& p, const void* rays, hipStream_t stream ) {
+    if ( p.job_blocks == 0 ) return hipSuccess;
+    if ( !p.partials || !rays || p.block_order || p.job_live ) return hipErrorInvalidValue;
+    DevRayRenderParams rp;
+    static_cast<DevRenderParams&> ( rp ) = p; rp.rays = reinterpret_cast<const float4*> ( rays );
+    size_t lds = terra_lds_bytes ( p );
+    if ( p.lds_mode == 1 ) return terra_launch_render_rays_mode1 ( rp, lds, stream );
+    if ( p.lds_mode == 2 ) return p.scene.reach ? terra_launch_render_rays_mode3 ( rp, lds, stream ) : terra_launch_render_rays_mode2 ( rp, lds, stream );
+    return terra_launch_render_rays_mode0 ( rp, lds, stream );
 }
 
 // First kernel of every render: the random streams of every job of the launch (what job_next would otherwise compute when a lane takes the job). One thread per job,

@@ -1530,15 +1530,17 @@ static void apply_stack_hooks ( const Scene* s, DevRenderParams& p ) {
     }
 }
 // r: the copy of the scene the launch reads (the launch runs on r.device)
+// ray_origins_ok: non-null = a ray-sourced launch (no camera: cam is not looked at and the camera fields stay zero); what it points to stands in for "the camera lies
+// inside the range the commit's traversal shortcut is proven for" -- the host forms look at their rays' origins, the device forms cannot and pass true
 static int fill_params ( Scene* s, const Scene::Replica& r, const TerraCamera* cam, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t h,
-                         size_t tile, int rank, int world, DevRenderParams& p ) {
+                         size_t tile, int rank, int world, DevRenderParams& p, const bool* ray_origins_ok = nullptr ) {
     if ( int rc = scene_check ( s ) ) return rc;
-    if ( !cam || w == 0 || h == 0 || x + w > fb_w || y + h > fb_h ) return fail ( kTerraAmdErrBadArgument, "bad tile rectangle %zu,%zu %zux%zu in %zux%zu", x, y, w, h, fb_w, fb_h );
+    if ( ( !cam && !ray_origins_ok ) || w == 0 || h == 0 || x + w > fb_w || y + h > fb_h ) return fail ( kTerraAmdErrBadArgument, "bad tile rectangle %zu,%zu %zux%zu in %zux%zu", x, y, w, h, fb_w, fb_h );
     if ( tile == 0 || tile % 16 != 0 ) return fail ( kTerraAmdErrBadArgument, "tile_size %zu must be a positive multiple of 16", tile );
     if ( world < 1 || rank < 0 || rank >= world ) return fail ( kTerraAmdErrBadArgument, "bad shard %d/%d", rank, world );
     memset ( &p, 0, sizeof p );
     p.scene = r.dev;
-    fill_camera ( cam, fb_w, fb_h, p );
+    if ( !ray_origins_ok ) fill_camera ( cam, fb_w, fb_h, p );
     p.jitter = s->opts.subpixel_jitter; p.exposure = s->opts.manual_exposure; p.gamma = s->opts.gamma;
     p.fb_w = ( uint32_t ) fb_w; p.fb_h = ( uint32_t ) fb_h;
     p.x = ( uint32_t ) x; p.y = ( uint32_t ) y; p.w = ( uint32_t ) w; p.h = ( uint32_t ) h;
@@ -1556,9 +1558,9 @@ static int fill_params ( Scene* s, const Scene::Replica& r, const TerraCamera* c
     terra_plan_lds ( p );
     // automatic mode: the containment argument also needs the ray origins (the camera) inside the verified coordinate range
     const TreeChoice& c = s->tree;
-    const bool cam_ok = ( c.reach || c.reach_cull ) ? ( fabsf ( p.cam_pos[0] ) <= c.reach_limit && fabsf ( p.cam_pos[1] ) <= c.reach_limit && fabsf ( p.cam_pos[2] ) <= c.reach_limit ) : coords_within_margin ( p.cam_pos, 3 );
+    const bool cam_ok = ray_origins_ok ? *ray_origins_ok : ( c.reach || c.reach_cull ) ? ( fabsf ( p.cam_pos[0] ) <= c.reach_limit && fabsf ( p.cam_pos[1] ) <= c.reach_limit && fabsf ( p.cam_pos[2] ) <= c.reach_limit ) : coords_within_margin ( p.cam_pos, 3 );
     if ( c.use_fast && r.dev.fast_nodes_h && ( s->tree_mode == 1 || cam_ok ) ) terra_plan_fast_tree ( p );
-    else if ( ( c.use_fast || c.cull_ok ) && !cam_ok && !s->warned_camera.exchange ( true ) )          // (once per scene)
+    else if ( ( c.use_fast || c.cull_ok ) && !cam_ok && !ray_origins_ok && !s->warned_camera.exchange ( true ) )          // (once per scene)
         fprintf ( stderr, "[terra_amd] warning: camera at (%g, %g, %g) lies outside the range (+-%g) for which this scene's traversal shortcut is proven: this call runs the reference "
                   "tree's replica traversal (same image, typically 10-20 x slower on large scenes); terra_amd_traversal_info() reports camera_limit and last_call\n",
                   ( double ) p.cam_pos[0], ( double ) p.cam_pos[1], ( double ) p.cam_pos[2], ( double ) shortcut_limit ( c ) );
@@ -1634,19 +1636,22 @@ static uint32_t auto_sample_split ( uint32_t blocks, uint32_t spp, bool ordered 
 }
 // The sample split of a launch of p with `blocks` pixel blocks per chunk: the scene's setting, or its automatic choice for the launch. The render and the AOV pass
 // (terra_amd_render_aov_device) both take it from here, so that their samples are cut into the same chunks. Sets p.job_blocks = blocks.
-static uint32_t launch_split ( const Scene* s, DevRenderParams& p, uint32_t blocks ) {
+// ray_source: a ray-sourced launch (never ordered: launch_plan.h terra_block_order_bytes).
+static uint32_t launch_split ( const Scene* s, DevRenderParams& p, uint32_t blocks, bool ray_source = false ) {
     uint32_t split = s->sample_split;
     p.job_blocks = blocks;                                            // (what terra_block_order_bytes looks at is the launch's size and layout, not the split)
-    if ( split == 0 ) split = auto_sample_split ( blocks, p.spp, s->job_order && terra_block_order_bytes ( p, s->job_order == 2 ) != 0 );
+    if ( split == 0 ) split = auto_sample_split ( blocks, p.spp, s->job_order && terra_block_order_bytes ( p, s->job_order == 2, ray_source ) != 0 );
     while ( split > 1 && p.spp % split ) split >>= 1;              // chunks must be equal: fall back to the largest power of two dividing spp
     if ( split < 1 ) split = 1;
     return split;
 }
-static int launch_render ( Scene* s, DevRenderParams& p, int device, hipStream_t stream, ThreadSlot* slot = nullptr ) {      // device: the (current) device of the launch
+// d_rays: non-null = a ray-sourced launch (include/terra_amd.h "Ray-sourced rendering"): the same plan, scratch, queue and resolve, the primary rays read from d_rays
+// (addressed like p.results); no job order and no empty skip, which are made from camera rays
+static int launch_render ( Scene* s, DevRenderParams& p, int device, hipStream_t stream, ThreadSlot* slot = nullptr, const void* d_rays = nullptr ) {      // device: the (current) device of the launch
     const uint32_t blocks = terra_render_blocks ( p );
     if ( blocks == 0 ) return 0;
     if ( p.count_level != 0 || p.rand_calls ) { p.leaf_boxes = nullptr; p.n_leaf_boxes = 0; p.leaf_pairs = 0; }      // the work counters keep their meaning: counting launches walk the tree and test one triangle per trip
-    const uint32_t split = launch_split ( s, p, blocks );
+    const uint32_t split = launch_split ( s, p, blocks, d_rays != nullptr );
     static thread_local uint64_t pool_kept = 0;          // (bit d: done for device d)
     if ( device < 64 && ! ( pool_kept >> device & 1ull ) ) {        // keep freed scratch cached in the device's default pool instead of returning it to the OS at every sync
         hipMemPool_t pool;
@@ -1660,7 +1665,7 @@ static int launch_render ( Scene* s, DevRenderParams& p, int device, hipStream_t
     const size_t stream_bytes = terra_job_streams_bytes ( p );
     if ( stream_bytes && ( p.fb_w > 65535u || p.fb_h > 65535u ) ) return fail ( kTerraAmdErrBadArgument, "framebuffer of %u x %u: at most 65,535 pixels per side (the job table packs a pixel into 32 bits)", p.fb_w, p.fb_h );
     const size_t spill_bytes = terra_fast_spill_bytes ( p );                 // fast-tree launches: the part of the lanes' traversal stacks that does not live in LDS
-    const size_t order_bytes = s->job_order ? terra_block_order_bytes ( p, s->job_order == 2 ) : 0;           // LDS-resident launches: the order the pixel blocks are handed out in (render_kernels.hip "job order")
+    const size_t order_bytes = s->job_order ? terra_block_order_bytes ( p, s->job_order == 2, d_rays != nullptr ) : 0;           // LDS-resident launches: the order the pixel blocks are handed out in (render_kernels.hip "job order")
     const size_t scratch_bytes = header + partial_bytes + stream_bytes + spill_bytes + order_bytes;
     // (a thread's slot keeps scratch for tile-sized calls only: a full-frame call's gigabytes come from, and go back to, the device's pool)
     // a launch's scratch is bounded: 48 bytes per (pixel, lane-per-pixel) job on LDS-resident scenes -- a 4K frame at 64 lanes per pixel asks for 25 GB per concurrent stream.
@@ -1704,7 +1709,7 @@ static int launch_render ( Scene* s, DevRenderParams& p, int device, hipStream_t
     }
     if ( e == hipSuccess && order_cls ) e = terra_launch_block_order ( p, order_cls, stream );
     if ( e == hipSuccess ) e = terra_launch_job_streams ( p, stream );
-    if ( e == hipSuccess ) e = terra_launch_render ( p, stream );
+    if ( e == hipSuccess ) e = d_rays ? terra_launch_render_rays ( p, d_rays, stream ) : terra_launch_render ( p, stream );
     if ( e == hipSuccess ) e = terra_launch_resolve ( p, stream );
     if ( pooled ) ( void ) hipFreeAsync ( scratch, stream );
     else if ( e != hipSuccess ) ( void ) hipMemsetAsync ( scratch, 0, header, stream );       // (a launch that failed half way must not leave a used queue word behind)
@@ -1732,6 +1737,40 @@ extern "C" int terra_amd_render_device_sharded ( const TerraCamera* cam, HTerraS
 extern "C" int terra_amd_render_device ( const TerraCamera* cam, HTerraScene h, void* d_pixels, void* d_results, size_t fb_w, size_t fb_h,
                                          size_t x, size_t y, size_t w, size_t hgt, void* d_rand_calls, void* stream ) {
     return terra_amd_render_device_sharded ( cam, h, d_pixels, d_results, fb_w, fb_h, x, y, w, hgt, 64, 0, 1, d_rand_calls, stream );
+}
+// ---- ray-sourced rendering: the render call with a client's own primary rays (include/terra_amd.h "Ray-sourced rendering") -----------------------
+// the one check of the four entry points, after fill_params' (scene, rectangle): the ray buffer is there and 16-byte aligned (the kernels read a record as two 16-byte words)
+static int rays_check ( const void* rays, const char* what ) {
+    if ( !rays ) return fail ( kTerraAmdErrBadArgument, "%s: null ray buffer", what );
+    if ( ( uintptr_t ) rays & 15u ) return fail ( kTerraAmdErrBadArgument, "%s: the ray buffer must be 16-byte aligned", what );
+    return 0;
+}
+// host forms: do all ACTIVE rays of the rectangle start inside the range the commit's traversal shortcut is proven for? (an inactive ray is never traced)
+static bool ray_origins_within ( const Scene* s, const TerraAmdRay* rays, size_t fb_w, size_t x, size_t y, size_t w, size_t h ) {
+    const float limit = shortcut_limit ( s->tree );
+    for ( size_t j = y; j < y + h; ++j ) for ( size_t i = x; i < x + w; ++i ) {
+        const TerraAmdRay& q = rays[j * fb_w + i];
+        const bool finite = std::isfinite ( q.origin[0] ) && std::isfinite ( q.origin[1] ) && std::isfinite ( q.origin[2] ) && std::isfinite ( q.direction[0] ) && std::isfinite ( q.direction[1] ) && std::isfinite ( q.direction[2] );
+        if ( !finite || ( q.direction[0] == 0.f && q.direction[1] == 0.f && q.direction[2] == 0.f ) ) continue;
+        if ( ! ( fabsf ( q.origin[0] ) <= limit && fabsf ( q.origin[1] ) <= limit && fabsf ( q.origin[2] ) <= limit ) ) return false;
+    }
+    return true;
+}
+extern "C" int terra_amd_render_rays_device ( HTerraScene h, const void* d_rays, void* d_pixels, void* d_results, size_t fb_w, size_t fb_h,
+                                              size_t x, size_t y, size_t w, size_t hgt, void* d_rand_calls, void* stream ) {
+    Scene* s = S ( h );
+    const Scene::Replica& r = primary ( s );
+    DevRenderParams p;
+    const bool origins_ok = true;          // (the rays are in HBM: the client keeps their origins within camera_limit)
+    if ( int rc = fill_params ( s, r, nullptr, fb_w, fb_h, x, y, w, hgt, 64, 0, 1, p, &origins_ok ) ) return rc;
+    if ( int rc = rays_check ( d_rays, "terra_amd_render_rays_device" ) ) return rc;
+    if ( !d_pixels || !d_results ) return fail ( kTerraAmdErrBadArgument, "null framebuffer pointer" );
+    p.pixels = ( float* ) d_pixels; p.results = d_results; p.rand_calls = ( uint32_t* ) d_rand_calls;
+    if ( d_rand_calls ) p.count_level = 2;
+    HIP_TRY ( hipSetDevice ( r.device ), kTerraAmdErrNoDevice );
+    if ( int lrc = launch_render ( s, p, r.device, ( hipStream_t ) stream, nullptr, d_rays ) ) return lrc;
+    account_launch ( s, p );
+    return 0;
 }
 // proved / total pixel blocks of the scene's most recent launch (one device; synchronises that device)
 extern "C" int terra_amd_empty_skip_info ( HTerraScene h, uint32_t out[2] ) {
@@ -1825,14 +1864,15 @@ struct FrameCopy {
 static_assert ( sizeof ( TerraAmdAovResult ) == 48, "TerraAmdAovResult must be 48 bytes" );
 // p: the launch fill_params made for the render call this AOV call mirrors; the split is the one that call takes (launch_split), and the samples the AOV buffer
 // already holds key the streams as the framebuffer's do. Runs on the current device (the scene's primary one).
-static int launch_aov ( Scene* s, DevRenderParams& p, void* d_aov, hipStream_t stream ) {
+// d_rays: non-null = the ray-sourced form, mirroring a ray-sourced render call (addressed like d_aov).
+static int launch_aov ( Scene* s, DevRenderParams& p, void* d_aov, hipStream_t stream, const void* d_rays = nullptr ) {
     const uint32_t blocks = terra_render_blocks ( p );
     if ( blocks == 0 ) return 0;
-    const uint32_t split = launch_split ( s, p, blocks );
+    const uint32_t split = launch_split ( s, p, blocks, d_rays != nullptr );
     p.split = split; p.split_log2 = 0; while ( ( 1u << p.split_log2 ) < split ) ++p.split_log2;
     p.chunk_spp = p.spp / split; p.job_blocks = blocks * split; p.job_queue = nullptr; p.job_streams = nullptr; p.block_order = nullptr; p.partials = nullptr;
     p.pixels = nullptr; p.results = nullptr; p.rand_calls = nullptr; p.counters = nullptr; p.count_level = 0;
-    const hipError_t e = terra_launch_aov ( p, d_aov, stream );
+    const hipError_t e = d_rays ? terra_launch_aov_rays ( p, d_rays, d_aov, stream ) : terra_launch_aov ( p, d_aov, stream );
     if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "AOV launch: %s", hipGetErrorString ( e ) );
     return 0;
 }
@@ -1861,6 +1901,41 @@ extern "C" int terra_amd_render_aov ( const TerraCamera* cam, HTerraScene h, Ter
     hipError_t e = c.up_rect ( 0, aov, sizeof ( TerraAmdAovResult ), rect );
     if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "AOV upload: %s", hipGetErrorString ( e ) );
     if ( int rc = render_aov_device ( cam, h, c.d[0], fb_w, fb_h, x, y, w, hgt, x, y, w, nullptr ) ) return rc;
+    e = c.down_rect ( 0, aov, sizeof ( TerraAmdAovResult ), rect );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "AOV download: %s", hipGetErrorString ( e ) );
+    return 0;
+}
+// ray-sourced forms: d_rays addressed like d_aov
+static int render_aov_rays_device ( HTerraScene h, const void* d_rays, void* d_aov, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t hgt, size_t st_x, size_t st_y, size_t st_pitch,
+                                    bool origins_ok, void* stream, const char* what ) {
+    Scene* s = S ( h );
+    const Scene::Replica& r = primary ( s );
+    DevRenderParams p;
+    if ( int rc = fill_params ( s, r, nullptr, fb_w, fb_h, x, y, w, hgt, 64, 0, 1, p, &origins_ok ) ) return rc;
+    if ( int rc = rays_check ( d_rays, what ) ) return rc;
+    if ( !d_aov ) return fail ( kTerraAmdErrBadArgument, "null AOV buffer" );
+    HIP_TRY ( hipSetDevice ( r.device ), kTerraAmdErrNoDevice );
+    p.st_x = ( uint32_t ) st_x; p.st_y = ( uint32_t ) st_y; p.st_pitch = ( uint32_t ) st_pitch;
+    return launch_aov ( s, p, d_aov, ( hipStream_t ) stream, d_rays );
+}
+extern "C" int terra_amd_render_aov_rays_device ( HTerraScene h, const void* d_rays, void* d_aov, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t hgt, void* stream ) {
+    return render_aov_rays_device ( h, d_rays, d_aov, fb_w, fb_h, x, y, w, hgt, 0, 0, fb_w, true, stream, "terra_amd_render_aov_rays_device" );
+}
+extern "C" int terra_amd_render_aov_rays ( HTerraScene h, const TerraAmdRay* rays, TerraAmdAovResult* aov, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t hgt ) {
+    Scene* s = S ( h );
+    DevRenderParams p;          // (for the check alone, before anything is staged: the device form fills its own)
+    const bool any = true;
+    if ( int rc = fill_params ( s, primary ( s ), nullptr, fb_w, fb_h, x, y, w, hgt, 64, 0, 1, p, &any ) ) return rc;
+    if ( int rc = rays_check ( rays, "terra_amd_render_aov_rays" ) ) return rc;
+    if ( !aov ) return fail ( kTerraAmdErrBadArgument, "null AOV buffer" );
+    HIP_TRY ( hipSetDevice ( primary ( s ).device ), kTerraAmdErrNoDevice );
+    const bool origins_ok = ray_origins_within ( s, rays, fb_w, x, y, w, hgt );
+    const FrameRect rect = { fb_w, x, y, w, hgt };
+    FrameCopy c;
+    hipError_t e = c.up_rect ( 0, aov, sizeof ( TerraAmdAovResult ), rect );
+    if ( e == hipSuccess ) e = c.up_rect ( 1, rays, sizeof ( TerraAmdRay ), rect );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "AOV upload: %s", hipGetErrorString ( e ) );
+    if ( int rc = render_aov_rays_device ( h, c.d[1], c.d[0], fb_w, fb_h, x, y, w, hgt, x, y, w, origins_ok, nullptr, "terra_amd_render_aov_rays" ) ) return rc;
     e = c.down_rect ( 0, aov, sizeof ( TerraAmdAovResult ), rect );
     if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "AOV download: %s", hipGetErrorString ( e ) );
     return 0;
@@ -2285,6 +2360,45 @@ static int render_host ( const TerraCamera* cam, Scene* s, const TerraFramebuffe
     HIP_TRY ( hipMemcpy2DAsync ( ( void* ) hres, rpitch, t.d_results, w * 16, w * 16, h, hipMemcpyDeviceToHost, t.stream ), kTerraAmdErrLaunch );
     HIP_TRY ( hipMemcpy2DAsync ( hpix, ppitch, t.d_pixels, w * 12, w * 12, h, hipMemcpyDeviceToHost, t.stream ), kTerraAmdErrLaunch );
     HIP_TRY ( hipStreamSynchronize ( t.stream ), kTerraAmdErrLaunch );
+    account_launch ( s, p );
+    return 0;
+}
+
+// terra_amd_render_rays: render_host with the rectangle's rays uploaded beside the running sums (rows of w records, addressed like the staging rectangle). A scene
+// committed for several devices answers on its primary device.
+extern "C" int terra_amd_render_rays ( HTerraScene h, const TerraAmdRay* rays, const TerraFramebuffer* fb, size_t x, size_t y, size_t w, size_t hgt ) {
+    Scene* s = S ( h );
+    if ( !fb || !fb->pixels || !fb->results ) return fail ( kTerraAmdErrBadArgument, "null framebuffer" );
+    const Scene::Replica* r = &primary ( s );
+    DevRenderParams p;
+    bool origins_ok = true;          // (first pass: the checks alone, before the rays are read)
+    if ( int rc = fill_params ( s, *r, nullptr, fb->width, fb->height, x, y, w, hgt, 64, 0, 1, p, &origins_ok ) ) return rc;
+    if ( int rc = rays_check ( rays, "terra_amd_render_rays" ) ) return rc;
+    origins_ok = ray_origins_within ( s, rays, fb->width, x, y, w, hgt );
+    if ( !origins_ok ) if ( int rc = fill_params ( s, *r, nullptr, fb->width, fb->height, x, y, w, hgt, 64, 0, 1, p, &origins_ok ) ) return rc;      // an active origin beyond camera_limit: the replica traversal
+    if ( int rc = slot_prepare ( r->device, w * hgt ) ) return rc;
+    ThreadSlot& t = t_slot;
+    p.st_x = ( uint32_t ) x; p.st_y = ( uint32_t ) y; p.st_pitch = ( uint32_t ) w;
+    const size_t rpitch = fb->width * 16, ppitch = fb->width * 12;
+    const char* hres = ( const char* ) fb->results + ( y * fb->width + x ) * 16;
+    char* hpix = ( char* ) fb->pixels + ( y * fb->width + x ) * 12;
+    FrameCopy c;          // the rays' device copy: freed when the call returns (after the stream has drained, below)
+    void* d_rays = nullptr;
+    {
+        const hipError_t e = hipMalloc ( ( void** ) &c.d[0], w * hgt * sizeof ( TerraAmdRay ) );
+        if ( e != hipSuccess ) { ( void ) hipGetLastError(); return fail ( kTerraAmdErrNoDevice, "ray upload: %s", hipGetErrorString ( e ) ); }
+        d_rays = c.d[0];
+    }
+    HIP_TRY ( hipMemcpy2DAsync ( d_rays, w * sizeof ( TerraAmdRay ), ( const char* ) rays + ( y * fb->width + x ) * sizeof ( TerraAmdRay ), fb->width * sizeof ( TerraAmdRay ), w * sizeof ( TerraAmdRay ), hgt, hipMemcpyHostToDevice, t.stream ), kTerraAmdErrLaunch );
+    HIP_TRY ( hipMemcpy2DAsync ( t.d_results, w * 16, hres, rpitch, w * 16, hgt, hipMemcpyHostToDevice, t.stream ), kTerraAmdErrLaunch );
+    p.pixels = ( float* ) t.d_pixels; p.results = t.d_results; p.rand_calls = nullptr;
+    int lrc = launch_render ( s, p, r->device, t.stream, &t, d_rays );
+    if ( !lrc ) {
+        HIP_TRY ( hipMemcpy2DAsync ( ( void* ) hres, rpitch, t.d_results, w * 16, w * 16, hgt, hipMemcpyDeviceToHost, t.stream ), kTerraAmdErrLaunch );
+        HIP_TRY ( hipMemcpy2DAsync ( hpix, ppitch, t.d_pixels, w * 12, w * 12, hgt, hipMemcpyDeviceToHost, t.stream ), kTerraAmdErrLaunch );
+    }
+    HIP_TRY ( hipStreamSynchronize ( t.stream ), kTerraAmdErrLaunch );          // (also on a failed launch: the upload above still reads the ray copy)
+    if ( lrc ) return lrc;
     account_launch ( s, p );
     return 0;
 }

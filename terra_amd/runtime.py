@@ -142,6 +142,7 @@ _EXTRA = {
     "terra_amd_reproject_device": (C.c_int, [C.c_void_p, _CAM, _CAM] + [C.c_void_p] * 6 + [_SZ] * 6 + [C.POINTER(api.TerraAmdTemporalOptions), C.c_void_p]),
     "terra_amd_reproject": (C.c_int, [C.c_void_p, _CAM, _CAM, C.POINTER(api.TerraFramebuffer)] + [C.c_void_p] * 5 + [_SZ] * 4 + [C.POINTER(api.TerraAmdTemporalOptions)]),
     **api.RAY_QUERY_SIGNATURES,
+    **api.RAY_SOURCE_SIGNATURES,
 }
 
 
@@ -431,6 +432,79 @@ def occluded(lib, scene, rays):
     out = torch.empty(rays.shape[0], dtype=torch.int32, device=rays.device)
     check(lib.occluded_device(scene, rays.data_ptr(), rays.shape[0], out.data_ptr(), stream), "terra_amd_occluded_device")
     return out
+
+
+# ---------------------------------------------------------------------------
+# ray-sourced rendering (include/terra_amd.h "Ray-sourced rendering")
+# ---------------------------------------------------------------------------
+
+def _frame_rays(rays, width: int, height: int):
+    import torch
+    if not (isinstance(rays, torch.Tensor) and rays.is_cuda and rays.dtype == torch.float32 and rays.is_contiguous() and tuple(rays.shape) == (height, width, 8)):
+        raise TerraAmdError(f"ray-sourced calls take a contiguous float32 tensor [{height}, {width}, 8] on the scene's device: one api.RAY_DTYPE record per pixel of the frame")
+    if rays.data_ptr() % 16:
+        raise TerraAmdError("the ray buffer must be 16-byte aligned")
+
+
+def render_rays_device(lib, scene, rays, fb: DeviceFramebuffer, rect: Optional[Tuple[int, int, int, int]] = None, rand_calls=None, stream=None):
+    """terra_amd_render_rays_device: the render call with every pixel's primary ray read from rays (float32 [fb.height, fb.width, 8] in HBM: TerraAmdRay records)"""
+    _frame_rays(rays, fb.width, fb.height)
+    x, y, w, h = rect if rect else (0, 0, fb.width, fb.height)
+    check(lib.render_rays_device(scene, rays.data_ptr(), fb.pixels.data_ptr(), fb.results.data_ptr(), fb.width, fb.height, x, y, w, h,
+                                 rand_calls.data_ptr() if rand_calls is not None else None, stream), "terra_amd_render_rays_device")
+
+
+def render_aov_rays_device(lib, scene, rays, aov: DeviceAov, rect: Optional[Tuple[int, int, int, int]] = None, stream=None):
+    """terra_amd_render_aov_rays_device: the AOV pass of a render_rays_device call (rays as there)"""
+    _frame_rays(rays, aov.width, aov.height)
+    x, y, w, h = rect if rect else (0, 0, aov.width, aov.height)
+    check(lib.render_aov_rays_device(scene, rays.data_ptr(), aov.data.data_ptr(), aov.width, aov.height, x, y, w, h, stream), "terra_amd_render_aov_rays_device")
+
+
+RADIANCE_FRAME_WIDTH = 256
+
+
+def radiance_frame_shape(n: int) -> Tuple[int, int]:
+    """(height, width) of the frame radiance() folds n rays into: rows of RADIANCE_FRAME_WIDTH pixels, the last one padded"""
+    return max(1, -(-n // RADIANCE_FRAME_WIDTH)), RADIANCE_FRAME_WIDTH
+
+
+def fold_rays(rays, xp=np):
+    """n ray records [n, 8] -> a frame [height, 256, 8] (radiance_frame_shape), ray i at pixel (i % 256, i // 256), padded with inactive records (all zero:
+    a zero direction). A pure function of its input: xp is numpy, or torch for a tensor (which stays on its device)."""
+    n = int(rays.shape[0])
+    h, w = radiance_frame_shape(n)
+    if xp is np:
+        frame = np.zeros((h * w, 8), dtype=np.float32)
+    else:
+        frame = xp.zeros((h * w, 8), dtype=xp.float32, device=rays.device)
+    frame[:n] = rays
+    return frame.reshape(h, w, 8)
+
+
+def unfold_pixels(frame, n: int):
+    """the first n pixels of a folded frame [height, 256, k], in the rays' order: [n, k]"""
+    return frame.reshape(-1, frame.shape[-1])[:n]
+
+
+def radiance(lib, scene, rays, batches: int = 1):
+    """Mean radiance along n rays (float32 [n, 8] in HBM: TerraAmdRay records) -> float32 [n, 3]: the rays folded into a frame 256 pixels wide, `batches`
+    render_rays_device calls of the scene's samples_per_pixel each, acc / samples (NaN-free: an inactive ray's mean is 0). Queued on the current torch stream;
+    nothing goes through the host."""
+    torch, stream = _query_rays(rays)
+    if batches < 1:
+        raise TerraAmdError("radiance: batches must be at least 1")
+    n = rays.shape[0]
+    frame = fold_rays(rays, torch)
+    h, w = frame.shape[0], frame.shape[1]
+    with torch.cuda.device(rays.device):
+        fb = DeviceFramebuffer(w, h, device=rays.device)
+        for _ in range(batches):
+            render_rays_device(lib, scene, frame, fb, stream=stream)
+        res = fb.results.view(h, w, 4)
+        acc = res[..., :3].view(torch.float32)
+        samples = res[..., 3:4].to(torch.float32)
+        return unfold_pixels(acc / samples, n).contiguous()
 
 
 def render_device_sharded(lib, cam, scene, fb: DeviceFramebuffer, tile: int, rank: int, world: int, stream=None):
