@@ -6,8 +6,8 @@ leaf loop (csrc/traverse_ref.h "Pair form", csrc/trace_geometry.h watertight_pai
 * the pair form is independent of the flat leaf-box test: with that test off, in tree mode `reference` (no cull: every pair is tested) and out of range (the
   walk with regular slabs) the launch walks the tree and its staged nodes carry entry bits;
 * the tie scene -- a quad duplicated exactly, so that coincident triangles lie in different entries whose ranks interleave, in objects of different colour, one
-  of them emissive -- is held against the oracle under Simple and Direct. (The commit gives the lower-ranked copy of coincident triangles to the earlier entry, so
-  for closest hits this scene does not tell the (depth, rank) record from "first trip wins"; it pins the images and the shadow rays' preset record.)
+  of them emissive -- is held against the oracle under Simple and Direct: it pins the images and the shadow rays' preset record. (The closest hits' (depth, rank)
+  record is held apart from "first trip wins" by tests/test_exact_ties_gpu.py, on different triangles at equal depths; coincident copies cannot do that.)
 * k_watertight_pair equals k_watertight run on each triangle, bit for bit, on about 10^5 rays: random ones, rays aimed exactly at points of the diagonal, at each
   of the four vertices and at the outer edges, axis-parallel ones, a degenerate pair (p3 on the line p0-p2: T2's double-precision fallback) and a folded pair.
 """
