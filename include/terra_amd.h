@@ -767,6 +767,19 @@ int terra_amd_unit_camera ( const TerraCamera* camera, size_t fb_width, size_t f
 int terra_amd_unit_tonemap ( int op, float gamma, int n, float* colors3 );
 /* device math: fn 0 sinf, 1 cosf, 2 powf(x,y), 3 acosf, 4 atan2f(x,y) */
 int terra_amd_unit_math ( int fn, int n, const float* x, const float* y, float* out );
+/* The LDS plan of a committed scene's launches, from host-side counts (no device needed): out6 = { bytes per block of a launch that takes the pair form where the scene
+   has one, of those the per-triangle shading constants (48 per staged triangle; 0 without a pair form), the pair section, the per-block budget that keeps five blocks
+   per CU resident, triangles staged (0: not LDS-resident), 1 if leaves are collected as a rank set } */
+int terra_amd_scene_lds_plan ( HTerraScene scene, uint32_t* out6 );
+/* The exact-quotient helpers of the shading code against the plain float division, element by element, both computed on the device and compared there by bit pattern
+   (two NaNs count as equal): *mismatches = the elements that differ, first_bad[16][9] = the first of them as {inputs[3], helper bits[3], plain bits[3]}.
+   op 0: 1 / a; op 1: a / denominator with `reciprocal` = its correctly rounded reciprocal (2^-60 <= |denominator| <= 2^60); op 2: a / b; op 4: normalize (a, b, c).
+   Explicit form (a != NULL): `count` elements (at most 2^28) read from the arrays, both results also stored in helper_bits / plain_bits (three words per element for op 4).
+   Generated form (a == NULL): elements first .. first + count - 1 of a set made on the device from the counter and `seed` -- ops 0, 1: the 32-bit pattern k itself;
+   op 2: hashed pairs, alternately uniform in bit pattern and inside the helpers' guarded range; op 3: three pairs per element whose exact quotient lies at, or half a
+   unit of the last place from, a float (to within the rounding of the numerator); op 4: hashed vectors. Nothing is stored but the count and the records. */
+int terra_amd_unit_exact_div ( int op, const float* a, const float* b, const float* c, uint64_t first, uint64_t count, float denominator, float reciprocal, uint64_t seed,
+                               uint32_t* helper_bits, uint32_t* plain_bits, uint64_t* mismatches, uint32_t* first_bad );
 /* The plane values of the fast tree's nodes: x[i] rounded to binary16 towards -inf (up = 0) or +inf (up != 0), as bits -- so that a box of such planes
    contains the box it was made from (host arithmetic; no device needed) */
 int terra_amd_unit_half_outward ( const double* x, int n, int up, uint16_t* out );

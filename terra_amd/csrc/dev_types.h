@@ -144,6 +144,18 @@ constexpr uint32_t terra_pair_boxes_offset ( uint32_t n_pairs ) { return 6u * TE
 constexpr uint32_t terra_pair_box_plane_offset ( uint32_t k, uint32_t a, uint32_t s ) { return TERRA_PAIR_BOX_STRIDE * k + 8u * ( 2u * a + s ); }
 constexpr uint32_t terra_pair_section_bytes ( uint32_t n_pairs ) { return terra_pair_boxes_offset ( n_pairs ) + TERRA_PAIR_BOX_STRIDE * n_pairs; }
 static_assert ( terra_pair_box_plane_offset ( 7, 0, 0 ) == 336 && terra_pair_box_plane_offset ( 0, 2, 1 ) + 8u == TERRA_PAIR_BOX_STRIDE, "a box = six 8-byte plane pairs; a group of eight within 384 bytes" );
+// shading constants (TERRA_SHADE_CONSTS; make_tracer fills, surface_init<1> reads): 48 bytes per staged triangle of a PAIR-FORM launch, behind the pair section --
+// e0[3], e1[3], d00, d11, d01, div = d00 d11 - d01 d01, rcp_exact ( div ), and a flag word: 1 where div is inside the range in which the short quotient form is
+// valid (exact_div.h xd_rcp_ok: normal, 2^-60 <= |div| <= 2^60, significand not all ones), 0 for a zero, denormal, non-finite or out-of-range div.
+// Only pair-form launches have it: a pair section is 216 bytes per triangle where the ranked entries the plan budgeted are 288, so section + constants (264) never
+// take more LDS than the plan allowed and resident_leaf_cap stays as it is. Cornell: 29,456 + 32 x 48 = 30,992 B <= TERRA_LDS_BUDGET.
+// TERRA_SHADE_CONSTS 0: nothing is staged and surface_init computes the constants per hit (an A/B build: python -m terra_amd.build --variant noconsts -DTERRA_SHADE_CONSTS=0)
+#ifndef TERRA_SHADE_CONSTS
+#define TERRA_SHADE_CONSTS 1
+#endif
+#define TERRA_SHADE_CONSTS_BYTES 48u
+static_assert ( terra_pair_section_bytes ( TERRA_LEAF_RANK_MAX / 2 ) + TERRA_SHADE_CONSTS_BYTES * TERRA_LEAF_RANK_MAX <= 6u * TERRA_RANKED_ENTRY_BYTES * TERRA_LEAF_RANK_MAX
+                && terra_pair_section_bytes ( 1 ) + TERRA_SHADE_CONSTS_BYTES * 2u <= 6u * TERRA_RANKED_ENTRY_BYTES * 2u, "pair section + shading constants fit where the plan budgeted ranked entries" );
 static_assert ( terra_pair_section_bytes ( TERRA_LEAF_RANK_MAX / 2 ) <= 6u * TERRA_RANKED_ENTRY_BYTES * TERRA_LEAF_RANK_MAX && terra_pair_section_bytes ( 1 ) <= 6u * TERRA_RANKED_ENTRY_BYTES * 2u, "the pair section never takes more LDS than the ranked entries it replaces" );
 // a record key of the pair loop: (rank + 1) << 5 | soup triangle -- ordered as the ranks are, 0 = no hit, the triangle in its low five bits
 constexpr uint32_t terra_pair_key ( uint32_t rank, uint32_t tri ) { return ( rank + 1u ) << 5 | tri; }
@@ -319,6 +331,10 @@ struct DevRenderParams {
     // The table's distance in bytes from scene.tris, inside the same blob; 0 = none. (A 32-bit word in what was padding: the structure keeps its size, so the kernels
     // that never read it keep their argument offsets.)
     uint32_t leaf_pairs;
+    // 1.f / (float) fb_w, 1.f / (float) fb_h, correctly rounded on the host (fill_camera): camera_sample's two divisions by the frame size take them through div_exact_rk
+    // (exact_div.h). No padding was left: the record grows by 8 bytes, at its end, so every other field -- and the argument offsets of the kernels that read no camera --
+    // stays where it was; a ray-sourced launch's ray pointer (DevRayRenderParams) moves 8 bytes up.
+    float    inv_fb_w, inv_fb_h;
 };
 // ray-sourced launches (include/terra_amd.h "Ray-sourced rendering"): the launch's parameters end with the ray buffer -- one TerraAmdRay (two 16-byte words) per pixel,
 // addressed like `results` (st_x / st_y / st_pitch: the frame for the device forms, the staged rectangle for the host forms). The pointer follows DevRenderParams' last field in a structure of its own, which only

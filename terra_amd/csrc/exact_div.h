@@ -1,0 +1,107 @@
+// exact_div.h -- correctly rounded float quotients in fewer instructions than the IEEE expansion of "/" (DESIGN.md 5 "Where the arithmetic legitimately differs",
+// entry 4: the argument). Every helper returns the bits "/" returns, for every input: inside a guarded range it takes a short fma sequence that is proved to round as the
+// division does (Markstein's theorems on a reciprocal refined by fma, and on a quotient corrected by one exact remainder), outside it it IS the plain "/", behind a branch.
+//   rcp_exact ( d )               = 1.f / d
+//   div_exact_r ( x, d, r )       = x / d, r = rcp_exact ( d ) or any correctly rounded 1 / d (a host's 1.f / d)
+//   div_exact_rk ( x, d, r )      = x / d for a denominator the CALLER knows to be normal with 2^-60 <= |d| <= 2^60 (a launch constant, a literal)
+//   div2_exact ( x1, x2, d, .. )  = x1 / d and x2 / d, one reciprocal; div2_exact_rk: two quotients by known denominators behind one branch
+//   rcp3_exact ( .. )             = three reciprocals behind one branch (make_ray)
+//   xd_normalize3 ( x, y, z, l, .. ) = x / l, y / l, z / l for l = the vector's length (>= 0 or NaN, as sqrtf returns it): one reciprocal, three quotients
+// TERRA_EXACT_DIV_FAST 0: every helper is the plain "/" (an A/B build: python -m terra_amd.build --variant plain -DTERRA_EXACT_DIV_FAST=0).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#ifndef TERRA_EXACT_DIV_FAST
+#define TERRA_EXACT_DIV_FAST 1
+#endif
+
+#define XD __device__ __forceinline__
+
+// The guarded range of every operand: normal, 2^-60 <= |v| <= 2^60 (a NaN fails both comparisons). Then a quotient lies in [2^-120, 2^120], a reciprocal in
+// [2^-60, 2^60], and the remainders below -- no smaller than 2^-48 times an operand product -- are normal too: nothing in a short sequence underflows, overflows or
+// meets a denormal, which is all that the theorems (stated for an unbounded exponent range) ask of the format.
+// (The guards are ints joined with "&", not bools with "&&": every comparison is evaluated and ONE branch chooses between the short sequence and the division.)
+XD int xd_in_range ( float v ) { const float a = __builtin_fabsf ( v ); return ( int ) ( a >= 0x1p-60f ) & ( int ) ( a <= 0x1p60f ); }
+// ... and, for a denominator whose reciprocal is refined here, a significand that is not all ones: the one pattern Markstein's reciprocal theorem excludes
+// (1 / (2 - 2^-23) lies 2^-48 above a rounding midpoint, and the last fma can land on the midpoint itself)
+XD int xd_rcp_ok ( float d ) { return xd_in_range ( d ) & ( int ) ( ( __float_as_uint ( d ) & 0x7fffffu ) != 0x7fffffu ); }
+
+// v_rcp_f32 (1 ulp) and two Newton steps in fma: after the first the estimate is within a unit of the last place of 1 / d, where the residual 1 - d y is exact and the
+// second step rounds 1 / d correctly (Markstein 1990, theorem on the reciprocal; significand of d not all ones). Checked on all 2^32 patterns (tests/test_exact_div_gpu.py).
+XD float xd_rcp_short ( float d ) {
+    float y = __builtin_amdgcn_rcpf ( d );
+    float e = __builtin_fmaf ( -d, y, 1.f );
+    y = __builtin_fmaf ( e, y, y );
+    e = __builtin_fmaf ( -d, y, 1.f );
+    return __builtin_fmaf ( e, y, y );
+}
+// r = RN ( 1 / d ): q0 = RN ( x r ) is within a unit of the last place of x / d, so rem = x - d q0 is exact, and RN ( q0 + rem r ) = RN ( x / d ) (Markstein's
+// theorem on the quotient; no significand is excluded).
+XD float xd_div_short ( float x, float d, float r ) {
+    const float q0 = x * r;
+    const float rem = __builtin_fmaf ( -d, q0, x );
+    return __builtin_fmaf ( rem, r, q0 );
+}
+// the same for d > 0 and a numerator that may be +-0. The form above returns +0 for x = -0: its remainder is (+0) + (-0) = +0, and (+0) r + (-0) = +0. Here the
+// remainder is formed negated, d q0 - x, and subtracted: for x = -0 it is (-0) + (+0) = +0 and the last fma adds (-0) r = -0 to q0 = -0: -0; for x = +0 it adds
+// (-0) r = -0 to q0 = +0: +0 -- the quotient's own zero both times. For x != 0 the remainder is the same number, exactly.
+XD float xd_div_short_pos ( float x, float d, float r ) {
+    const float q0 = x * r;
+    const float nrem = __builtin_fmaf ( d, q0, -x );
+    return __builtin_fmaf ( -nrem, r, q0 );
+}
+
+XD float rcp_exact ( float d ) {
+#if TERRA_EXACT_DIV_FAST
+    if ( xd_rcp_ok ( d ) ) return xd_rcp_short ( d );
+#endif
+    return 1.f / d;
+}
+XD float div_exact_r ( float x, float d, float r ) {
+#if TERRA_EXACT_DIV_FAST
+    if ( xd_in_range ( x ) & xd_in_range ( d ) ) return xd_div_short ( x, d, r );
+#endif
+    return x / d;
+}
+XD float div_exact_rk ( float x, float d, float r ) {
+#if TERRA_EXACT_DIV_FAST
+    if ( xd_in_range ( x ) ) return xd_div_short ( x, d, r );
+#endif
+    return x / d;
+}
+// x1 / d, x2 / d for one such denominator, behind one branch
+XD void div2_exact_rk ( float x1, float x2, float d1, float r1, float d2, float r2, float& q1, float& q2 ) {
+#if TERRA_EXACT_DIV_FAST
+    if ( xd_in_range ( x1 ) & xd_in_range ( x2 ) ) { q1 = xd_div_short ( x1, d1, r1 ); q2 = xd_div_short ( x2, d2, r2 ); return; }
+#endif
+    q1 = x1 / d1; q2 = x2 / d2;
+}
+XD void div2_exact ( float x1, float x2, float d, float& q1, float& q2 ) {
+#if TERRA_EXACT_DIV_FAST
+    if ( xd_rcp_ok ( d ) & xd_in_range ( x1 ) & xd_in_range ( x2 ) ) {
+        const float r = xd_rcp_short ( d );
+        q1 = xd_div_short ( x1, d, r ); q2 = xd_div_short ( x2, d, r );
+        return;
+    }
+#endif
+    q1 = x1 / d; q2 = x2 / d;
+}
+XD void rcp3_exact ( float dx, float dy, float dz, float& rx, float& ry, float& rz ) {
+#if TERRA_EXACT_DIV_FAST
+    if ( xd_rcp_ok ( dx ) & xd_rcp_ok ( dy ) & xd_rcp_ok ( dz ) ) { rx = xd_rcp_short ( dx ); ry = xd_rcp_short ( dy ); rz = xd_rcp_short ( dz ); return; }
+#endif
+    rx = 1.f / dx; ry = 1.f / dy; rz = 1.f / dz;
+}
+// a component of a vector of length l in the guarded range: +-0, or no smaller than 2^-60 (it cannot exceed l by more than a rounding, so it needs no upper bound)
+XD int xd_component_ok ( float c ) { return ( int ) ( c == 0.f ) | ( int ) ( __builtin_fabsf ( c ) >= 0x1p-60f ); }
+XD void xd_normalize3 ( float x, float y, float z, float l, float& qx, float& qy, float& qz ) {
+#if TERRA_EXACT_DIV_FAST
+    if ( ( int ) ( l >= 0x1p-60f ) & ( int ) ( l <= 0x1p60f ) & ( int ) ( ( __float_as_uint ( l ) & 0x7fffffu ) != 0x7fffffu ) & xd_component_ok ( x ) & xd_component_ok ( y ) & xd_component_ok ( z ) ) {          // (xd_rcp_ok for l > 0)
+        const float r = xd_rcp_short ( l );
+        qx = xd_div_short_pos ( x, l, r ); qy = xd_div_short_pos ( y, l, r ); qz = xd_div_short_pos ( z, l, r );
+        return;
+    }
+#endif
+    qx = x / l; qy = y / l; qz = z / l;
+}

@@ -370,7 +370,7 @@ template <int KINDS>
 TD bool path_continue ( Surface& sf, V3 wo, V3& throughput, uint32_t& bounce, uint32_t max_bounces, const PathDraws& d, V3& wi ) {
     wi = bsdf_sample<KINDS> ( sf, d.e0, d.e1, d.e2, wo, d.az );
     float pdf = sel_max ( bsdf_pdf<KINDS> ( sf, wi, wo ), ( float ) 1e-4 );
-    V3 f = bsdf_eval<KINDS> ( sf, wi, wo ) * ( 1.f / pdf );
+    V3 f = bsdf_eval<KINDS> ( sf, wi, wo ) * rcp_exact ( pdf );
     throughput = had ( throughput, f );
     throughput = throughput * dot ( sf.normal, wi );
     float pr = sel_max ( throughput.x, sel_max ( throughput.y, throughput.z ) );

@@ -50,6 +50,7 @@ struct DevTemporalParams {
     uint32_t fb_w, fb_h, x, y, w, h;
     float alpha, depth_tolerance, normal_cos, max_length;      // max_length = floor(1 / alpha)
     uint32_t same_camera;                                        // prev_camera equals camera byte for byte
+    float inv_fb_w, inv_fb_h;                                    // 1.f / fb_w, 1.f / fb_h as fill_camera rounds them (camera_sample)
 };
 hipError_t terra_launch_temporal_reproject ( const DevTemporalParams& p, const void* results, const void* aov, const void* history_in, void* history_out,
                                              void* out_results, void* out_moments, hipStream_t stream );
@@ -82,6 +83,9 @@ hipError_t terra_unit_bsdf ( int kind, int n, float* surfaces47, const float* e3
 hipError_t terra_unit_camera ( const DevRenderParams& p, int n, const uint32_t* xy2, const float* r2, float* dirs3 );
 hipError_t terra_unit_tonemap ( int op, float gamma, int n, float* colors3 );
 hipError_t terra_unit_math ( int fn, int n, const float* x, const float* y, float* out );
+// exact_div.h against "/" (unit_kernels.hip "exact_div.h against the plain"): a == nullptr = the generated set; helper_bits / plain_bits only in the explicit form
+hipError_t terra_unit_exact_div ( int op, const float* a, const float* b, const float* c, uint64_t first, uint64_t count, float D, float R, uint64_t seed,
+                                  uint32_t* helper_bits, uint32_t* plain_bits, unsigned long long* mismatches, uint32_t* first_bad );
 // texture_sample at uv2[n][2] / environment_eval's lat-long lookup at dir3[n][3] on the texture whose descriptor is at `t` (device memory)
 hipError_t terra_unit_texture_sample ( const DevTexture* t, int n, const float* uv2, float* out3 );
 hipError_t terra_unit_texture_latlong ( const DevTexture* t, int n, const float* dir3, float* out3 );

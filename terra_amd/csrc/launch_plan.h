@@ -41,9 +41,13 @@ inline uint32_t terra_render_blocks ( const DevRenderParams& p ) {
 inline size_t scene_extra_lds_bytes ( uint32_t n_objects, uint32_t n_lights, uint32_t n_tris ) {
     return ( ( ( size_t ) n_objects * sizeof ( DevMaterial ) + 15 ) & ~size_t ( 15 ) ) + ( size_t ) n_lights * sizeof ( DevLight ) + ( ( ( size_t ) n_tris * 4 + 15 ) & ~size_t ( 15 ) );
 }
+// the shading constants of a pair-form launch (dev_types.h "shading constants")
+inline size_t terra_shade_consts_bytes ( const DevRenderParams& p ) {
+    return ( TERRA_SHADE_CONSTS && p.lds_mode == 1 && p.leaf_rank && p.leaf_pairs ) ? ( size_t ) p.lds_tris * TERRA_SHADE_CONSTS_BYTES : 0;
+}
 // dynamic LDS per block of the planned launch
 inline size_t terra_lds_bytes ( const DevRenderParams& p ) {
-    return ( size_t ) ( p.stack_depth + p.leaf_cap + ( p.lds_mode == 1 ? TERRA_AUX_WORDS_LDS : TERRA_AUX_WORDS ) ) * 1024 + ( size_t ) p.lds_nodes * TERRA_LDS_NODE_BYTES + ( size_t ) p.lds_tris * ( 48 + 64 )
+    return terra_shade_consts_bytes ( p ) + ( size_t ) ( p.stack_depth + p.leaf_cap + ( p.lds_mode == 1 ? TERRA_AUX_WORDS_LDS : TERRA_AUX_WORDS ) ) * 1024 + ( size_t ) p.lds_nodes * TERRA_LDS_NODE_BYTES + ( size_t ) p.lds_tris * ( 48 + 64 )
            + ( p.lds_mode == 1 ? scene_extra_lds_bytes ( p.scene.n_objects, p.scene.n_lights, p.scene.n_tris ) : 0 ) + ( p.lds_mode == 1 && p.leaf_rank ? ( p.leaf_pairs ? ( size_t ) terra_pair_section_bytes ( p.lds_tris / 2 ) : ( size_t ) p.lds_tris * 6 * 48 ) : 0 );      // (the leaf-box table of a flat launch rides in pad words of the ranked entries: no bytes of its own; the pair form's section includes its table)
 }
 // fast tree (MODE 2 / 3): nothing is staged. A lane holds at most two leaves (in registers: the one it tests, the next one), so there is no leaf list. The stack: its first TERRA_FAST_STACK_LDS entries

@@ -95,7 +95,9 @@ TD Tracer make_tracer ( const DevScene& sc, float4* lds, uint32_t stack_depth, u
     const bool pairs = ranked && leaf_pairs != nullptr;
     const uint32_t n_pairs = lds_tris >> 1;
     const uint32_t n_boxes = ( ranked && cull && fused && leaf_boxes && n_leaf_boxes <= ( pairs ? n_pairs : lds_tris ) ) ? n_leaf_boxes : 0u;
-    int* words = reinterpret_cast<int*> ( lr + ( ranked ? ( pairs ? terra_pair_section_bytes ( n_pairs ) / 16u : 18u * lds_tris ) : 0u ) );
+    float4* lc = lr + ( ranked ? ( pairs ? terra_pair_section_bytes ( n_pairs ) / 16u : 18u * lds_tris ) : 0u );      // pair form: the shading constants, three float4 per triangle
+    const bool consts = TERRA_SHADE_CONSTS && pairs;
+    int* words = reinterpret_cast<int*> ( lc + ( consts ? ( TERRA_SHADE_CONSTS_BYTES / 16u ) * lds_tris : 0u ) );
     T.stack = words + tid;
     T.leaves = words + stack_depth * TERRA_COL + tid;
     T.leaf_cap = ( int ) leaf_cap;
@@ -168,6 +170,18 @@ TD Tracer make_tracer ( const DevScene& sc, float4* lds, uint32_t stack_depth, u
         }
     }
     for ( uint32_t i = tid; i < 3 * lds_tris; i += TERRA_COL ) lt[i] = gt[i];
+    if ( consts ) {          // surface_init's per-triangle constants: its own float operations on the same operands, in its order (shading_device.h)
+        static_assert ( TERRA_SHADE_CONSTS_BYTES == 3 * sizeof ( float4 ), "three pieces per triangle below" );
+        for ( uint32_t i = tid; i < lds_tris; i += TERRA_COL ) {
+            V3 ta, tb, tc; tri_vertices ( gt, i, ta, tb, tc );
+            const V3 e0 = tb - ta, e1 = tc - ta;
+            const float d00 = dot ( e0, e0 ), d11 = dot ( e1, e1 ), d01 = dot ( e0, e1 );
+            const float div = d00 * d11 - d01 * d01;
+            lc[3 * i] = make_float4 ( e0.x, e0.y, e0.z, e1.x );
+            lc[3 * i + 1] = make_float4 ( e1.y, e1.z, d00, d11 );
+            lc[3 * i + 2] = make_float4 ( d01, div, rcp_exact ( div ), __uint_as_float ( TERRA_EXACT_DIV_FAST && xd_rcp_ok ( div ) ? 1u : 0u ) );
+        }
+    }
     for ( uint32_t i = tid; i < 4 * lds_tris; i += TERRA_COL ) {
         float4 v = gp[i];
         static_assert ( terra_leaf_box_mask_offset ( 0 ) == 3 * sizeof ( float4 ) + 12 && terra_leaf_box_mask_offset ( 1 ) - terra_leaf_box_mask_offset ( 0 ) == 4 * sizeof ( float4 ), "v.w of every fourth piece below is where leaf_boxes_flat reads a mask" );
@@ -183,6 +197,7 @@ TD Tracer make_tracer ( const DevScene& sc, float4* lds, uint32_t stack_depth, u
     T.l_mats = MODE == 1 ? reinterpret_cast<const DevMaterial*> ( lm ) : sc.mats; T.l_lights = MODE == 1 ? reinterpret_cast<const DevLight*> ( ll ) : sc.lights; T.l_area = MODE == 1 ? reinterpret_cast<const float*> ( la ) : sc.tri_area;
     T.l_nodes = ln; T.l_tris = reinterpret_cast<const float*> ( lt ); T.l_props = lp;
     T.l_ranked = ranked ? lr : nullptr; T.ranked = ranked; T.pairs = pairs;
+    T.l_consts = consts ? lc : nullptr;
     T.n_boxes = n_boxes;
     T.lds_nodes = lds_nodes; T.lds_tris = lds_tris;
     __syncthreads();

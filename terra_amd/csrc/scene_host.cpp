@@ -1414,6 +1414,22 @@ extern "C" int terra_amd_scene_leaf_pair_masks ( HTerraScene h, uint32_t* out, i
     if ( out && capacity >= n ) memcpy ( out, s->leaf_pairs.data() + s->leaf_pairs.size() - ( size_t ) n, ( size_t ) n * sizeof ( uint32_t ) );
     return n;
 }
+// The LDS plan of the scene's launches as launch_plan.h makes it, from the commit's host-side counts (needs no device). out[0] = bytes per block of a launch that
+// takes the pair form where the scene has one (terra_lds_bytes), out[1] = of those, the shading constants (dev_types.h "shading constants"; 0: no pair form, or
+// TERRA_SHADE_CONSTS 0), out[2] = the pair section, out[3] = TERRA_LDS_BUDGET, out[4] = triangles staged (0: the scene is not LDS-resident), out[5] = leaf_rank.
+extern "C" int terra_amd_scene_lds_plan ( HTerraScene h, uint32_t* out6 ) {
+    Scene* s = S ( h );
+    if ( !s->committed ) return fail ( kTerraAmdErrNotCommitted, "scene not committed" );
+    if ( !out6 ) return fail ( kTerraAmdErrBadArgument, "terra_amd_scene_lds_plan: null output" );
+    DevRenderParams p; memset ( &p, 0, sizeof p );
+    size_t ntri = 0; for ( size_t j = 0; j < s->objects_pop; ++j ) ntri += s->objects[j].triangles_count;
+    p.scene.n_nodes = ( uint32_t ) s->nodes.size(); p.scene.n_tris = ( uint32_t ) ntri; p.scene.max_stack = s->max_stack; p.scene.n_objects = ( uint32_t ) s->objects_pop; p.scene.n_lights = ( uint32_t ) s->lights.size();
+    terra_plan_lds ( p );
+    p.leaf_pairs = ( p.lds_mode == 1 && p.leaf_rank && !s->leaf_pairs.empty() ) ? 1u : 0u;          // (any non-zero distance: only "has a pair form" is read)
+    out6[0] = ( uint32_t ) terra_lds_bytes ( p ); out6[1] = ( uint32_t ) terra_shade_consts_bytes ( p ); out6[2] = p.leaf_pairs ? terra_pair_section_bytes ( p.lds_tris / 2 ) : 0u;
+    out6[3] = ( uint32_t ) TERRA_LDS_BUDGET; out6[4] = p.lds_mode == 1 ? p.lds_tris : 0u; out6[5] = p.leaf_rank;
+    return 0;
+}
 // where a pair launch of n entries stages its section in LDS (dev_types.h "pair form"), byte offsets from the section's start (Tracer::l_ranked): entries[perm * n + e] = entry e
 // of permutation perm (64 bytes each), planes[6 k + 2 a + s] = box k's (near, far) pair on axis a for direction sign s (8 bytes each). Returns the section's size in
 // bytes, or an error for n above TERRA_LEAF_RANK_MAX / 2. Needs no scene.
@@ -1509,6 +1525,7 @@ static void fill_camera ( const TerraCamera* cam, size_t fb_w, size_t fb_h, DevR
     p.cam_pos[0] = cam->position.x; p.cam_pos[1] = cam->position.y; p.cam_pos[2] = cam->position.z;
     p.tan_half_fov = ( float ) tan ( ( double ) ( ( cam->fov * 0.0174533f ) / 2 ) );     // double tan of a float argument, src/Terra.c:1794
     p.aspect = ( float ) fb_w / ( float ) fb_h;
+    p.inv_fb_w = 1.f / ( float ) fb_w; p.inv_fb_h = 1.f / ( float ) fb_h;          // correctly rounded (IEEE division): what camera_sample's div_exact_rk takes
 }
 
 // the scene can answer a call: committed since it last changed, and with a device replica
@@ -2142,7 +2159,7 @@ extern "C" int terra_amd_reproject_device ( HTerraScene h, const TerraCamera* ca
     DevRenderParams a, b;
     fill_camera ( cam, fb_w, fb_h, a ); fill_camera ( prev, fb_w, fb_h, b );
     DevTemporalParams p;
-    memcpy ( p.cam_pos, a.cam_pos, sizeof p.cam_pos ); memcpy ( p.cam_rot, a.cam_rot, sizeof p.cam_rot ); p.tan_half_fov = a.tan_half_fov; p.aspect = a.aspect;
+    memcpy ( p.cam_pos, a.cam_pos, sizeof p.cam_pos ); memcpy ( p.cam_rot, a.cam_rot, sizeof p.cam_rot ); p.tan_half_fov = a.tan_half_fov; p.aspect = a.aspect; p.inv_fb_w = a.inv_fb_w; p.inv_fb_h = a.inv_fb_h;
     memcpy ( p.prev_pos, b.cam_pos, sizeof p.prev_pos ); memcpy ( p.prev_rot, b.cam_rot, sizeof p.prev_rot ); p.prev_tan_half_fov = b.tan_half_fov;
     p.fb_w = ( uint32_t ) fb_w; p.fb_h = ( uint32_t ) fb_h; p.x = ( uint32_t ) x; p.y = ( uint32_t ) y; p.w = ( uint32_t ) w; p.h = ( uint32_t ) hgt;
     p.alpha = alpha; p.depth_tolerance = depth_tol; p.normal_cos = normal_cos; p.max_length = floorf ( 1.f / alpha );
@@ -2630,6 +2647,21 @@ extern "C" int terra_amd_unit_math ( int fn, int n, const float* x, const float*
     if ( need_device() ) return kTerraAmdErrNoDevice;
     Unit u; auto a = u.in ( x, n ); auto b = u.in ( y ? y : x, n ); auto o = u.out ( out, n );
     return u.finish ( u.ok ? terra_unit_math ( fn, n, a, b, o ) : hipSuccess );
+}
+extern "C" int terra_amd_unit_exact_div ( int op, const float* a, const float* b, const float* c, uint64_t first, uint64_t count, float denominator, float reciprocal, uint64_t seed,
+                                           uint32_t* helper_bits, uint32_t* plain_bits, uint64_t* mismatches, uint32_t* first_bad ) {
+    if ( need_device() ) return kTerraAmdErrNoDevice;
+    if ( op < 0 || op > 4 || !mismatches || !first_bad ) return fail ( kTerraAmdErrBadArgument, "exact_div unit: op %d, or no place for the mismatch count and records", op );
+    const bool explicit_set = a != nullptr;
+    if ( explicit_set && ( op == 3 || !helper_bits || !plain_bits || ( ( op == 2 || op == 4 ) && !b ) || ( op == 4 && !c ) || count > ( 1ull << 28 ) ) )
+        return fail ( kTerraAmdErrBadArgument, "exact_div unit: the explicit form of op %d needs its input and output arrays (op 3 has none), at most 2^28 elements", op );
+    const size_t n = explicit_set ? ( size_t ) count : 0, per = op == 4 ? 3 : 1;
+    Unit u;
+    const float* da = explicit_set ? u.in ( a, n ) : nullptr; const float* db = explicit_set && ( op == 2 || op == 4 ) ? u.in ( b, n ) : nullptr; const float* dc = explicit_set && op == 4 ? u.in ( c, n ) : nullptr;
+    uint32_t* dh = explicit_set ? u.out ( helper_bits, per * n ) : nullptr; uint32_t* dp = explicit_set ? u.out ( plain_bits, per * n ) : nullptr;
+    *mismatches = 0;
+    unsigned long long* dm = reinterpret_cast<unsigned long long*> ( u.inout ( mismatches, 1 ) ); uint32_t* dr = u.out ( first_bad, 9 * 16 );
+    return u.finish ( u.ok ? terra_unit_exact_div ( op, da, db, dc, first, count, denominator, reciprocal, seed, dh, dp, dm, dr ) : hipSuccess );
 }
 
 // binary16 planes of the fast tree's nodes (tree_build.cpp fastbvh::half_outward): host arithmetic, no device needed

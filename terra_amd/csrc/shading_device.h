@@ -43,6 +43,8 @@ TD V3 texture_sample ( const DevTexture& t, float u, float v ) {
 }
 
 #define TERRA_PI_F 3.1416926535f        // the reference's terra_PI (include/TerraMath.h), not pi
+#define TERRA_INV_PI_F 0x1.45f06p-2f    // 1.f / TERRA_PI_F, correctly rounded (0.3182997703552246), for div_exact_rk
+static_assert ( TERRA_INV_PI_F == 1.f / TERRA_PI_F, "the literal is the compiler's own correctly rounded quotient" );
 // lat-long environment lookup by direction (reference src/Terra.c:468-477): nearest texel, no filtering.
 // terra_PI exceeds pi, so phi / (2 terra_PI) and theta / terra_PI stay below 1 and the texel is in range.
 TD V3 environment_eval ( const DevScene& sc, V3 dir ) {
@@ -85,15 +87,26 @@ TD void surface_init ( const Tracer& T, uint32_t ti, V3 point, Surface& sf, uint
         if ( MODE >= 2 ) pi = T.sc.mats[__float_as_uint ( t0.w )].first_tri + __float_as_uint ( t1.w );
         p0 = props[4 * pi]; p1 = props[4 * pi + 1]; p2 = props[4 * pi + 2]; p3x = props[4 * pi + 3];
     }
-    V3 ta, tb, tc; tri_vertices ( t0, t1, t2, ta, tb, tc );
     uint32_t object = __float_as_uint ( t0.w );
     object_out = object; tri_in_object_out = __float_as_uint ( t1.w );
-    V3 e0 = tb - ta, e1 = tc - ta, p = point - ta;
-    float d00 = dot ( e0, e0 ), d11 = dot ( e1, e1 ), d01 = dot ( e0, e1 );
-    float dp0 = dot ( p, e0 ), dp1 = dot ( p, e1 );
-    float div = d00 * d11 - d01 * d01;
-    float u = ( d11 * dp0 - d01 * dp1 ) / div;
-    float v = ( d00 * dp1 - d01 * dp0 ) / div;
+    float u, v;
+    if ( MODE == 1 && TERRA_SHADE_CONSTS && T.l_consts ) {          // pair-form launches: e0, e1, d00, d11, d01, div as make_tracer formed them once per block, by these very operations
+        const float4 c0 = T.l_consts[3 * ti], c1 = T.l_consts[3 * ti + 1], c2 = T.l_consts[3 * ti + 2];
+        const V3 e0 = v3 ( c0.x, c0.y, c0.z ), e1 = v3 ( c0.w, c1.x, c1.y ), p = point - v3 ( t0.x, t0.y, t0.z );
+        const float d00 = c1.z, d11 = c1.w, d01 = c2.x, div = c2.y;
+        const float dp0 = dot ( p, e0 ), dp1 = dot ( p, e1 );
+        const float nu = d11 * dp0 - d01 * dp1, nv = d00 * dp1 - d01 * dp0;
+        // the flag word stands for xd_rcp_ok ( div ), c2.z for xd_rcp_short ( div ): div2_exact with its denominator's part done ahead
+        if ( ( int ) __float_as_uint ( c2.w ) & xd_in_range ( nu ) & xd_in_range ( nv ) ) { u = xd_div_short ( nu, div, c2.z ); v = xd_div_short ( nv, div, c2.z ); }
+        else { u = nu / div; v = nv / div; }
+    } else {
+        V3 ta, tb, tc; tri_vertices ( t0, t1, t2, ta, tb, tc );
+        V3 e0 = tb - ta, e1 = tc - ta, p = point - ta;
+        float d00 = dot ( e0, e0 ), d11 = dot ( e1, e1 ), d01 = dot ( e0, e1 );
+        float dp0 = dot ( p, e0 ), dp1 = dot ( p, e1 );
+        float div = d00 * d11 - d01 * d01;
+        div2_exact ( d11 * dp0 - d01 * dp1, d00 * dp1 - d01 * dp0, div, u, v );
+    }
     float w = 1 - u - v;
     V3 na = v3 ( p0.x, p0.y, p0.z ), nb = v3 ( p0.w, p1.x, p1.y ), nc = v3 ( p1.z, p1.w, p2.x );
     sf.normal = normalize ( ( nc * v + nb * u ) + na * w );
@@ -237,7 +250,7 @@ TD V3 diffuse_sample ( const Surface& sf, float e1, float e2, const Azimuth& az 
     V3 wi = v3 ( x, sqrtf ( sel_max ( 0.f, 1 - e1 ) ), z );
     return normalize ( basis_apply ( make_basis ( sf.normal ), wi ) );
 }
-TD float diffuse_pdf ( const Surface& sf, V3 wi ) { return sel_max ( 0.f, dot ( sf.normal, wi ) ) / TERRA_PI_F; }
+TD float diffuse_pdf ( const Surface& sf, V3 wi ) { return div_exact_rk ( sel_max ( 0.f, dot ( sf.normal, wi ) ), TERRA_PI_F, TERRA_INV_PI_F ); }
 TD V3 diffuse_eval ( const Surface& sf ) { return sf.attr[0] * ( float ) ( 1. / ( double ) TERRA_PI_F ); }
 
 TD void phong_kd_ks ( const Surface& sf, float& kd, float& ks ) {

@@ -65,7 +65,7 @@ __global__ __launch_bounds__ ( 256 ) void terra_temporal_reproject ( DevTemporal
     float m1h = 0.f, m2h = 0.f, nh = 0.f;
     if ( hin && in.a0.w > 0.f ) {
         DevRenderParams rp;                 // the render's own camera function (trace_geometry.h) at the pixel centre: only these fields are read
-        rp.jitter = 0.f; rp.fb_w = p.fb_w; rp.fb_h = p.fb_h; rp.aspect = p.aspect; rp.tan_half_fov = p.tan_half_fov;
+        rp.jitter = 0.f; rp.fb_w = p.fb_w; rp.fb_h = p.fb_h; rp.inv_fb_w = p.inv_fb_w; rp.inv_fb_h = p.inv_fb_h; rp.aspect = p.aspect; rp.tan_half_fov = p.tan_half_fov;
         #pragma unroll
         for ( int k = 0; k < 9; ++k ) rp.cam_rot[k] = p.cam_rot[k];
         const V3 D = camera_sample ( rp, px, py, 0.f, 0.f );

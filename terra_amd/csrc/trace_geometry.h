@@ -9,8 +9,9 @@
 TD V3 camera_sample ( const DevRenderParams& p, uint32_t px, uint32_t py, float r1, float r2 ) {
     float dx = -p.jitter + 2 * r1 * p.jitter;
     float dy = -p.jitter + 2 * r2 * p.jitter;
-    float ndc_x = ( ( float ) px + 0.5f + dx ) / ( float ) p.fb_w;
-    float ndc_y = ( ( float ) py + 0.5f + dy ) / ( float ) p.fb_h;
+    // x / fb_w, y / fb_h bit for bit: the reciprocals of the frame size are launch constants, rounded on the host (fill_camera), and 1 <= fb_w, fb_h <= 2^32 is inside
+    // the range div_exact_rk asks of its caller
+    float ndc_x, ndc_y; div2_exact_rk ( ( float ) px + 0.5f + dx, ( float ) py + 0.5f + dy, ( float ) p.fb_w, p.inv_fb_w, ( float ) p.fb_h, p.inv_fb_h, ndc_x, ndc_y );
     float sx = 2 * ndc_x - 1;
     float sy = 1 - 2 * ndc_y;
     float fx = sx * p.aspect * p.tan_half_fov;

@@ -7,6 +7,7 @@
 #include "dev_math.h"
 #include "rng.h"
 #include "sampling_device.h"
+#include "exact_div.h"
 
 #define TD __device__ __forceinline__
 
@@ -22,7 +23,9 @@ TD V3 neg ( V3 a ) { return v3 ( -a.x, -a.y, -a.z ); }
 TD float dot ( V3 a, V3 b ) { return a.x * b.x + a.y * b.y + a.z * b.z; }
 TD V3 cross ( V3 a, V3 b ) { return v3 ( a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x ); }
 TD float length ( V3 a ) { return sqrtf ( a.x * a.x + a.y * a.y + a.z * a.z ); }
-TD V3 normalize ( V3 a ) { float l = length ( a ); return v3 ( a.x / l, a.y / l, a.z / l ); }
+// a / |a|: the three quotients share one refined reciprocal of the length (exact_div.h); normalize_plain is the same function written with "/" (the unit entry compares them)
+TD V3 normalize_plain ( V3 a ) { float l = length ( a ); return v3 ( a.x / l, a.y / l, a.z / l ); }
+TD V3 normalize ( V3 a ) { float l = length ( a ); V3 r; xd_normalize3 ( a.x, a.y, a.z, l, r.x, r.y, r.z ); return r; }
 // compare-selects: exactly "a < b ? a : b" / "a > b ? a : b" (NaN-order sensitive)
 TD float sel_min ( float a, float b ) { return a < b ? a : b; }
 TD float sel_max ( float a, float b ) { return a > b ? a : b; }
@@ -53,7 +56,7 @@ TD Basis make_basis ( V3 n ) {
 }
 
 struct Ray { V3 o, d, inv; };
-TD Ray make_ray ( V3 o, V3 d ) { Ray r; r.o = o; r.d = d; r.inv = v3 ( 1.f / d.x, 1.f / d.y, 1.f / d.z ); return r; }
+TD Ray make_ray ( V3 o, V3 d ) { Ray r; r.o = o; r.d = d; rcp3_exact ( d.x, d.y, d.z, r.inv.x, r.inv.y, r.inv.z ); return r; }      // 1.f / d, bit for bit -- 1 / -0 = -inf included: a zero takes the plain division
 
 // what the watertight test keeps per ray (ray_state_init): the dominant axis iz of the direction, the two others in winding order, the shear and the scale
 struct RayState { float shearx, sheary, scalez; int ix, iy, iz; };

@@ -94,6 +94,7 @@ struct Tracer {
     const DevLight*    l_lights;
     const float*       l_area;
     const float4* l_ranked;    // ranked launches: the 6 permuted copies of the staged triangles, in rank order -- pair form: the pair section, 6 copies of the entries then the leaf-box table -- (see above); nullptr otherwise
+    const float4* l_consts = nullptr;      // pair-form launches with TERRA_SHADE_CONSTS: three float4 per staged triangle (dev_types.h "shading constants"); nullptr in every other launch and in every Tracer filled by hand
     uint32_t      n_boxes;     // flat leaf-box test: the distinct leaf boxes staged -- planes in the pad words of l_ranked (pair form: in the pair section's own part), masks in those of l_props (see above); 0 in every other launch
     uint32_t      lds_nodes, lds_tris;
     int*          stack;       // this thread's column

@@ -273,6 +273,85 @@ hipError_t terra_unit_math ( int fn, int n, const float* x, const float* y, floa
     return hipGetLastError();
 }
 
+// ---- exact_div.h against the plain "/" (tests/test_exact_div_gpu.py). Per element both are computed and their bits compared ON THE DEVICE (NaN = NaN): *mismatches counts
+// the elements that differ and first_bad keeps the first 16 of them as {inputs[3], helper bits[3], plain bits[3]}. Two forms: explicit -- elements read from a / b / c,
+// both results also stored, so the caller can compare them itself -- and generated (a == nullptr) -- element k of the set made from the counter, for the sets that are too
+// large to store: every bit pattern (ops 0, 1), hashed pairs (2), pairs built around rounding midpoints and representable quotients (3), hashed vectors (4).
+//   op 0  rcp_exact ( d )                                   generated: d = the pattern k
+//   op 1  div_exact_rk ( x, D, R ), D / R launch constants   generated: x = the pattern k
+//   op 2  div_exact_r ( x, d, rcp_exact ( d ) )              generated: even k: two patterns uniform in bits; odd k: both inside the guarded range
+//   op 3  the same on generated pairs only: d and a target quotient q hashed from k, x = RN ( d (q + s ulp(q) / 2) ), s = -1, 0, +1 by k, and x's two float neighbours
+//   op 4  normalize ( x, y, z ) against normalize_plain       generated: three components hashed from k (every fourth vector uniform in bits)
+struct XdSink { unsigned long long* mismatches; uint32_t* first_bad; };
+TD uint64_t xd_hash ( uint64_t x ) { x += 0x9e3779b97f4a7c15ull; x = ( x ^ ( x >> 30 ) ) * 0xbf58476d1ce4e5b9ull; x = ( x ^ ( x >> 27 ) ) * 0x94d049bb133111ebull; return x ^ ( x >> 31 ); }
+// a float of random sign and significand with its exponent field in [lo, lo + span)
+TD float xd_float_in ( uint32_t h, uint32_t lo, uint32_t span ) { return __uint_as_float ( ( h & 0x807fffffu ) | ( ( lo + ( ( h >> 23 ) & 0xffu ) % span ) << 23 ) ); }
+TD bool xd_same ( float h, float p ) { return __float_as_uint ( h ) == __float_as_uint ( p ) || ( h != h && p != p ); }
+TD void xd_check ( const XdSink& s, V3 in, V3 h, V3 p ) {
+    if ( xd_same ( h.x, p.x ) && xd_same ( h.y, p.y ) && xd_same ( h.z, p.z ) ) return;
+    const unsigned long long slot = atomicAdd ( s.mismatches, 1ull );
+    if ( slot < 16ull ) {
+        uint32_t* r = s.first_bad + 9 * slot;
+        r[0] = __float_as_uint ( in.x ); r[1] = __float_as_uint ( in.y ); r[2] = __float_as_uint ( in.z );
+        r[3] = __float_as_uint ( h.x ); r[4] = __float_as_uint ( h.y ); r[5] = __float_as_uint ( h.z );
+        r[6] = __float_as_uint ( p.x ); r[7] = __float_as_uint ( p.y ); r[8] = __float_as_uint ( p.z );
+    }
+}
+TD void xd_pair ( const XdSink& s, float x, float d ) { xd_check ( s, v3 ( x, d, 0.f ), v3 ( div_exact_r ( x, d, rcp_exact ( d ) ), 0.f, 0.f ), v3 ( x / d, 0.f, 0.f ) ); }
+template <int OP>
+__global__ __launch_bounds__ ( 256 ) void k_exact_div ( const float* a, const float* b, const float* c, unsigned long long first, unsigned long long count, float D, float R, unsigned long long seed,
+                                                        uint32_t* helper_bits, uint32_t* plain_bits, XdSink s ) {
+    const unsigned long long stride = ( unsigned long long ) gridDim.x * blockDim.x;
+    for ( unsigned long long i = ( unsigned long long ) blockIdx.x * blockDim.x + threadIdx.x; i < count; i += stride ) {
+        const unsigned long long k = first + i;
+        const uint64_t h0 = xd_hash ( seed ^ ( k * 0xd1342543de82ef95ull ) ), h1 = xd_hash ( h0 );
+        if ( OP == 3 ) {
+            const float d = xd_float_in ( ( uint32_t ) h0, 107u, 40u ), q = xd_float_in ( ( uint32_t ) ( h0 >> 32 ), 107u, 40u );
+            const double half_ulp = ( double ) __uint_as_float ( ( __float_as_uint ( q ) & 0x7f800000u ) - ( 24u << 23 ) );          // 2^(e - 24): half a unit of q's last place
+            const double target = ( double ) q + ( double ) ( ( int ) ( k % 3ull ) - 1 ) * half_ulp;
+            const float x = ( float ) ( ( double ) d * target );          // (24 x 25 bits: the product is exact, the conversion rounds to nearest)
+            xd_pair ( s, x, d );
+            xd_pair ( s, __uint_as_float ( __float_as_uint ( x ) + 1u ), d );
+            xd_pair ( s, __uint_as_float ( __float_as_uint ( x ) - 1u ), d );
+            continue;
+        }
+        V3 in = v3 ( 0.f, 0.f, 0.f ), hv = in, pv = in;
+        if ( a ) { in.x = a[i]; if ( OP == 2 || OP == 4 ) in.y = b[i]; if ( OP == 4 ) in.z = c[i]; }
+        else if ( OP == 0 || OP == 1 ) in.x = __uint_as_float ( ( uint32_t ) k );
+        else if ( OP == 2 ) {
+            if ( k & 1ull ) { in.x = xd_float_in ( ( uint32_t ) h0, 67u, 121u ); in.y = xd_float_in ( ( uint32_t ) ( h0 >> 32 ), 67u, 121u ); }
+            else { in.x = __uint_as_float ( ( uint32_t ) h0 ); in.y = __uint_as_float ( ( uint32_t ) ( h0 >> 32 ) ); }
+        } else {
+            if ( ( k & 3ull ) == 3ull ) in = v3 ( __uint_as_float ( ( uint32_t ) h0 ), __uint_as_float ( ( uint32_t ) ( h0 >> 32 ) ), __uint_as_float ( ( uint32_t ) h1 ) );
+            else { const uint32_t lo = 87u + ( uint32_t ) ( h1 >> 40 ) % 60u; in = v3 ( xd_float_in ( ( uint32_t ) h0, lo, 24u ), xd_float_in ( ( uint32_t ) ( h0 >> 32 ), lo, 24u ), xd_float_in ( ( uint32_t ) h1, lo, 24u ) ); }
+        }
+        if ( OP == 0 ) { hv.x = rcp_exact ( in.x ); pv.x = 1.f / in.x; }
+        else if ( OP == 1 ) { hv.x = div_exact_rk ( in.x, D, R ); pv.x = in.x / D; }
+        else if ( OP == 2 ) { hv.x = div_exact_r ( in.x, in.y, rcp_exact ( in.y ) ); pv.x = in.x / in.y; }
+        else { hv = normalize ( in ); pv = normalize_plain ( in ); }
+        xd_check ( s, in, hv, pv );
+        if ( a ) {
+            if ( OP == 4 ) { helper_bits[3 * i] = __float_as_uint ( hv.x ); helper_bits[3 * i + 1] = __float_as_uint ( hv.y ); helper_bits[3 * i + 2] = __float_as_uint ( hv.z );
+                             plain_bits[3 * i] = __float_as_uint ( pv.x ); plain_bits[3 * i + 1] = __float_as_uint ( pv.y ); plain_bits[3 * i + 2] = __float_as_uint ( pv.z ); }
+            else { helper_bits[i] = __float_as_uint ( hv.x ); plain_bits[i] = __float_as_uint ( pv.x ); }
+        }
+    }
+}
+hipError_t terra_unit_exact_div ( int op, const float* a, const float* b, const float* c, uint64_t first, uint64_t count, float D, float R, uint64_t seed,
+                                  uint32_t* helper_bits, uint32_t* plain_bits, unsigned long long* mismatches, uint32_t* first_bad ) {
+    if ( count == 0 ) return hipSuccess;
+    const uint64_t blocks = ( count + 255u ) / 256u;
+    const dim3 grid ( ( unsigned ) ( blocks < 4096u ? blocks : 4096u ) ), block ( 256 );          // (grid-stride: a set of 2^32 elements is 4096 trips of a lane)
+    const XdSink s = { mismatches, first_bad };
+#define XD_CASE(OP) case OP: hipLaunchKernelGGL ( k_exact_div<OP>, grid, block, 0, 0, a, b, c, ( unsigned long long ) first, ( unsigned long long ) count, D, R, ( unsigned long long ) seed, helper_bits, plain_bits, s ); break;
+    switch ( op ) {
+        XD_CASE ( 0 ) XD_CASE ( 1 ) XD_CASE ( 2 ) XD_CASE ( 3 ) XD_CASE ( 4 )
+        default: return hipErrorInvalidValue;
+    }
+#undef XD_CASE
+    return hipGetLastError();
+}
+
 // ---- the texture lookups on one texture of a blob (scene_host.cpp unit_texture): texture_sample in texel units, and environment_eval by direction on a scene
 // record that holds nothing but that texture as its lat-long environment
 __global__ void k_texture_sample ( const DevTexture* t, int n, const float* uv2, float* out3 ) {
