@@ -144,15 +144,12 @@ constexpr uint32_t terra_pair_boxes_offset ( uint32_t n_pairs ) { return 6u * TE
 constexpr uint32_t terra_pair_box_plane_offset ( uint32_t k, uint32_t a, uint32_t s ) { return TERRA_PAIR_BOX_STRIDE * k + 8u * ( 2u * a + s ); }
 constexpr uint32_t terra_pair_section_bytes ( uint32_t n_pairs ) { return terra_pair_boxes_offset ( n_pairs ) + TERRA_PAIR_BOX_STRIDE * n_pairs; }
 static_assert ( terra_pair_box_plane_offset ( 7, 0, 0 ) == 336 && terra_pair_box_plane_offset ( 0, 2, 1 ) + 8u == TERRA_PAIR_BOX_STRIDE, "a box = six 8-byte plane pairs; a group of eight within 384 bytes" );
-// shading constants (TERRA_SHADE_CONSTS; make_tracer fills, surface_init<1> reads): 48 bytes per staged triangle of a PAIR-FORM launch, behind the pair section --
+// shading constants (make_tracer fills, surface_init<1> reads): 48 bytes per staged triangle of a PAIR-FORM launch, behind the pair section --
 // e0[3], e1[3], d00, d11, d01, div = d00 d11 - d01 d01, rcp_exact ( div ), and a flag word: 1 where div is inside the range in which the short quotient form is
 // valid (exact_div.h xd_rcp_ok: normal, 2^-60 <= |div| <= 2^60, significand not all ones), 0 for a zero, denormal, non-finite or out-of-range div.
 // Only pair-form launches have it: a pair section is 216 bytes per triangle where the ranked entries the plan budgeted are 288, so section + constants (264) never
 // take more LDS than the plan allowed and resident_leaf_cap stays as it is. Cornell: 29,456 + 32 x 48 = 30,992 B <= TERRA_LDS_BUDGET.
-// TERRA_SHADE_CONSTS 0: nothing is staged and surface_init computes the constants per hit (an A/B build: python -m terra_amd.build --variant noconsts -DTERRA_SHADE_CONSTS=0)
-#ifndef TERRA_SHADE_CONSTS
-#define TERRA_SHADE_CONSTS 1
-#endif
+// Every launch without the pair form stages nothing and surface_init computes the constants per hit. The A/B of both: profiles/exact_div/ab.md.
 #define TERRA_SHADE_CONSTS_BYTES 48u
 static_assert ( terra_pair_section_bytes ( TERRA_LEAF_RANK_MAX / 2 ) + TERRA_SHADE_CONSTS_BYTES * TERRA_LEAF_RANK_MAX <= 6u * TERRA_RANKED_ENTRY_BYTES * TERRA_LEAF_RANK_MAX
                 && terra_pair_section_bytes ( 1 ) + TERRA_SHADE_CONSTS_BYTES * 2u <= 6u * TERRA_RANKED_ENTRY_BYTES * 2u, "pair section + shading constants fit where the plan budgeted ranked entries" );
@@ -168,10 +165,7 @@ static_assert ( TERRA_LEAF_RANK_MAX <= 32, "a pair key keeps the triangle in fiv
 // current job (touched once per path), the job's number and the lane's draw count when the job started (read at its end), and a row
 // that holds each wave's pool of claimed jobs (render_kernels.hip "jobs")
 #define TERRA_AUX_WORDS 6        // rows every launch has (acc x 3, job, draw count, wave pools)
-#define TERRA_AUX_WORDS_LDS 9    // ... plus, on LDS-resident scenes (lds_mode 1), the path radiance Lo x 3 (TERRA_LO_IN_LDS)
-#ifndef TERRA_JOB_STREAM_TABLE      // the jobs' random streams keyed by a kernel of their own ahead of the render (DevRenderParams::job_streams): 0 = by the lane that takes the job
-#define TERRA_JOB_STREAM_TABLE 1
-#endif
+#define TERRA_AUX_WORDS_LDS 9    // ... plus, on LDS-resident scenes (lds_mode 1), the path radiance Lo x 3 (render_kernels.hip LO_LDS)
 #ifndef TERRA_FAST_STACK_LDS     // entries of a fast-tree launch's stack kept in LDS, the rest in HBM (launch_plan.h terra_plan_fast_tree)
 #define TERRA_FAST_STACK_LDS 16
 #endif

@@ -7,14 +7,10 @@
 //   div2_exact ( x1, x2, d, .. )  = x1 / d and x2 / d, one reciprocal; div2_exact_rk: two quotients by known denominators behind one branch
 //   rcp3_exact ( .. )             = three reciprocals behind one branch (make_ray)
 //   xd_normalize3 ( x, y, z, l, .. ) = x / l, y / l, z / l for l = the vector's length (>= 0 or NaN, as sqrtf returns it): one reciprocal, three quotients
-// TERRA_EXACT_DIV_FAST 0: every helper is the plain "/" (an A/B build: python -m terra_amd.build --variant plain -DTERRA_EXACT_DIV_FAST=0).
+// The A/B against the plain "/" in every helper: profiles/exact_div/ab.md.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-
-#ifndef TERRA_EXACT_DIV_FAST
-#define TERRA_EXACT_DIV_FAST 1
-#endif
 
 #define XD __device__ __forceinline__
 
@@ -53,55 +49,41 @@ XD float xd_div_short_pos ( float x, float d, float r ) {
 }
 
 XD float rcp_exact ( float d ) {
-#if TERRA_EXACT_DIV_FAST
     if ( xd_rcp_ok ( d ) ) return xd_rcp_short ( d );
-#endif
     return 1.f / d;
 }
 XD float div_exact_r ( float x, float d, float r ) {
-#if TERRA_EXACT_DIV_FAST
     if ( xd_in_range ( x ) & xd_in_range ( d ) ) return xd_div_short ( x, d, r );
-#endif
     return x / d;
 }
 XD float div_exact_rk ( float x, float d, float r ) {
-#if TERRA_EXACT_DIV_FAST
     if ( xd_in_range ( x ) ) return xd_div_short ( x, d, r );
-#endif
     return x / d;
 }
 // x1 / d, x2 / d for one such denominator, behind one branch
 XD void div2_exact_rk ( float x1, float x2, float d1, float r1, float d2, float r2, float& q1, float& q2 ) {
-#if TERRA_EXACT_DIV_FAST
     if ( xd_in_range ( x1 ) & xd_in_range ( x2 ) ) { q1 = xd_div_short ( x1, d1, r1 ); q2 = xd_div_short ( x2, d2, r2 ); return; }
-#endif
     q1 = x1 / d1; q2 = x2 / d2;
 }
 XD void div2_exact ( float x1, float x2, float d, float& q1, float& q2 ) {
-#if TERRA_EXACT_DIV_FAST
     if ( xd_rcp_ok ( d ) & xd_in_range ( x1 ) & xd_in_range ( x2 ) ) {
         const float r = xd_rcp_short ( d );
         q1 = xd_div_short ( x1, d, r ); q2 = xd_div_short ( x2, d, r );
         return;
     }
-#endif
     q1 = x1 / d; q2 = x2 / d;
 }
 XD void rcp3_exact ( float dx, float dy, float dz, float& rx, float& ry, float& rz ) {
-#if TERRA_EXACT_DIV_FAST
     if ( xd_rcp_ok ( dx ) & xd_rcp_ok ( dy ) & xd_rcp_ok ( dz ) ) { rx = xd_rcp_short ( dx ); ry = xd_rcp_short ( dy ); rz = xd_rcp_short ( dz ); return; }
-#endif
     rx = 1.f / dx; ry = 1.f / dy; rz = 1.f / dz;
 }
 // a component of a vector of length l in the guarded range: +-0, or no smaller than 2^-60 (it cannot exceed l by more than a rounding, so it needs no upper bound)
 XD int xd_component_ok ( float c ) { return ( int ) ( c == 0.f ) | ( int ) ( __builtin_fabsf ( c ) >= 0x1p-60f ); }
 XD void xd_normalize3 ( float x, float y, float z, float l, float& qx, float& qy, float& qz ) {
-#if TERRA_EXACT_DIV_FAST
     if ( ( int ) ( l >= 0x1p-60f ) & ( int ) ( l <= 0x1p60f ) & ( int ) ( ( __float_as_uint ( l ) & 0x7fffffu ) != 0x7fffffu ) & xd_component_ok ( x ) & xd_component_ok ( y ) & xd_component_ok ( z ) ) {          // (xd_rcp_ok for l > 0)
         const float r = xd_rcp_short ( l );
         qx = xd_div_short_pos ( x, l, r ); qy = xd_div_short_pos ( y, l, r ); qz = xd_div_short_pos ( z, l, r );
         return;
     }
-#endif
     qx = x / l; qy = y / l; qz = z / l;
 }

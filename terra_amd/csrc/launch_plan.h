@@ -43,7 +43,7 @@ inline size_t scene_extra_lds_bytes ( uint32_t n_objects, uint32_t n_lights, uin
 }
 // the shading constants of a pair-form launch (dev_types.h "shading constants")
 inline size_t terra_shade_consts_bytes ( const DevRenderParams& p ) {
-    return ( TERRA_SHADE_CONSTS && p.lds_mode == 1 && p.leaf_rank && p.leaf_pairs ) ? ( size_t ) p.lds_tris * TERRA_SHADE_CONSTS_BYTES : 0;
+    return ( p.lds_mode == 1 && p.leaf_rank && p.leaf_pairs ) ? ( size_t ) p.lds_tris * TERRA_SHADE_CONSTS_BYTES : 0;
 }
 // dynamic LDS per block of the planned launch
 inline size_t terra_lds_bytes ( const DevRenderParams& p ) {
@@ -117,7 +117,7 @@ inline bool terra_leaf_boxes_fit ( const DevRenderParams& p, uint32_t n ) {
 
 // ---- job streams and job order (render_kernels.hip "jobs", "job order") -------------------------------------------------------
 // scratch of the job streams; 0: this launch keys its streams in the render kernel (p.lds_mode, p.job_blocks set)
-inline size_t terra_job_streams_bytes ( const DevRenderParams& p ) { return ( TERRA_JOB_STREAM_TABLE && p.lds_mode == 1 ) ? ( size_t ) p.job_blocks * 256 * 32 : 0; }
+inline size_t terra_job_streams_bytes ( const DevRenderParams& p ) { return p.lds_mode == 1 ? ( size_t ) p.job_blocks * 256 * 32 : 0; }
 // launches of fewer pixel blocks keep the numbering's order (unless terra_amd_set_job_order(scene, 2))
 inline uint32_t terra_job_order_min_blocks ( void ) { return TERRA_JOB_ORDER_MIN_BLOCKS; }
 // scratch of the job order: class word + the two halves of the order per pixel block, or 0: this launch keeps the order of the numbering (p.job_blocks, p.lds_mode set);

@@ -63,9 +63,6 @@ TD void wave_flush_counters ( const Counters& c, unsigned long long* g ) {
 // planned (DevRenderParams.lds_*), and leaves every thread with its own stack / leaf
 // list column. Called by all 256 threads (it contains the block barrier).
 // (the per-thread words parked in LDS between uses, TERRA_AUX_WORDS / TERRA_AUX_WORDS_LDS: dev_types.h "launch plan")
-#ifndef TERRA_LO_IN_LDS          // the coupled loop of LDS-resident scenes keeps the current path's radiance (three words that change on few hits) in rows 6-8 instead of registers
-#define TERRA_LO_IN_LDS 1
-#endif
 #ifndef TERRA_CHECK_SHRINK
 #define TERRA_CHECK_SHRINK 0
 #endif
@@ -96,7 +93,7 @@ TD Tracer make_tracer ( const DevScene& sc, float4* lds, uint32_t stack_depth, u
     const uint32_t n_pairs = lds_tris >> 1;
     const uint32_t n_boxes = ( ranked && cull && fused && leaf_boxes && n_leaf_boxes <= ( pairs ? n_pairs : lds_tris ) ) ? n_leaf_boxes : 0u;
     float4* lc = lr + ( ranked ? ( pairs ? terra_pair_section_bytes ( n_pairs ) / 16u : 18u * lds_tris ) : 0u );      // pair form: the shading constants, three float4 per triangle
-    const bool consts = TERRA_SHADE_CONSTS && pairs;
+    const bool consts = pairs;
     int* words = reinterpret_cast<int*> ( lc + ( consts ? ( TERRA_SHADE_CONSTS_BYTES / 16u ) * lds_tris : 0u ) );
     T.stack = words + tid;
     T.leaves = words + stack_depth * TERRA_COL + tid;
@@ -179,7 +176,7 @@ TD Tracer make_tracer ( const DevScene& sc, float4* lds, uint32_t stack_depth, u
             const float div = d00 * d11 - d01 * d01;
             lc[3 * i] = make_float4 ( e0.x, e0.y, e0.z, e1.x );
             lc[3 * i + 1] = make_float4 ( e1.y, e1.z, d00, d11 );
-            lc[3 * i + 2] = make_float4 ( d01, div, rcp_exact ( div ), __uint_as_float ( TERRA_EXACT_DIV_FAST && xd_rcp_ok ( div ) ? 1u : 0u ) );
+            lc[3 * i + 2] = make_float4 ( d01, div, rcp_exact ( div ), __uint_as_float ( xd_rcp_ok ( div ) ? 1u : 0u ) );
         }
     }
     for ( uint32_t i = tid; i < 4 * lds_tris; i += TERRA_COL ) {
@@ -252,80 +249,41 @@ __global__ __launch_bounds__ ( 256 ) void terra_resolve_kernel ( DevRenderParams
 
 #endif
 
-// Occupancy target per integrator (second __launch_bounds__ argument = waves per SIMD = 256-thread
-// blocks per CU). Measured on MI355X (profiles/): the Simple/debug kernels run fastest at 5 even
-// with a small spill; Direct/MIS carry a second surface and more live state.
-#ifndef TERRA_WAVES_SIMPLE
-#define TERRA_WAVES_SIMPLE 5
-#endif
-#ifndef TERRA_WAVES_LIGHT
-#define TERRA_WAVES_LIGHT 4
-#endif
-#ifndef TERRA_WAVES_MIS          // Direct + MIS on LDS-resident diffuse scenes, split at its two rays (TERRA_COUPLED_MIS_SPLIT): 5 -> 158.1 ms with 116 B of scratch, 4 -> 165.4 with none
-#define TERRA_WAVES_MIS 5        // (Cornell 512 spp; profiles/r04_measurements/ab_light_split.log; unsplit, round 3: 5 -> 191.9, 4 -> 178.9)
-#endif
-#ifndef TERRA_WAVES_DIRECT_PHONG // ... also the diffuse + Phong variant (A/B)
-#define TERRA_WAVES_DIRECT_PHONG 0
-#endif
-#ifndef TERRA_WAVES_DIRECT       // Direct on LDS-resident scenes, without work counters: 5 -> 117.7 ms, 4 -> 120.4 (Direct + MIS: 5 -> 191.9, 4 -> 178.9; profiles/r03_measurements/ab_waves_light.log)
-#define TERRA_WAVES_DIRECT 5
-#endif
-#ifndef TERRA_WAVES_GENERIC      // Simple/debug kernels compiled for every preset, textures and the environment term (KINDS != diffuse-only)
-#define TERRA_WAVES_GENERIC TERRA_WAVES_SIMPLE
-#endif
+#define TERRA_IS_LIGHT(I) ( ( I ) == 1 || ( I ) == 2 || ( I ) == 6 )
 // Decoupled traversal (see the kernel): scenes that are not LDS-resident, integrators whose shading casts no rays of its own
-#ifndef TERRA_DECOUPLED_ENABLE
-#define TERRA_DECOUPLED_ENABLE 1
-#endif
+// (LDS-resident scenes, MODE 1, keep the coupled loop: decoupled they measure 20 % slower -- shading outweighs traversal there; CHANGELOG.md round 1 / 2)
+constexpr bool terra_decoupled ( int I, int M ) { return M != 1 && ( I == 0 || I == 3 || I == 4 || I == 5 ); }
+// ... and Direct, whose one shadow ray per hit becomes a traversal job of its own (scenes without textured attributes); also on the fast tree (MODE 2): hall, 32 spp, 112.0 -> 108.2 ms
+constexpr bool terra_decoupled_direct ( int I, int M, int K ) { return M != 1 && I == 1 && ( K & TERRA_KIND_TEX ) == 0; }
+// ... and Direct + MIS, on the reference tree only: on the fast tree it is faster coupled (hall, 32 spp: 168.6 ms against 187.7 decoupled, profiles/r02_measurements/ab_fast_light.log; round 4, with the
+// light-sample rays' shortcut in both: 100.5 against 117.5, sphere scene 128 spp 157.8 against 162.4, profiles/r04_measurements/ab_fast_tree_knobs.log)
+constexpr bool terra_decoupled_mis ( int I, int M, int K ) { return M == 0 && I == 2 && ( K & TERRA_KIND_TEX ) == 0; }
 #ifndef TERRA_DECOUPLED_EXIT_SHIFT      // leave the traversal when n >> shift of the n lanes that entered it have finished
 #define TERRA_DECOUPLED_EXIT_SHIFT 4
-#endif
-#ifndef TERRA_DECOUPLED_FAST     // ... and the fast-tree kernels (MODE 2)
-#define TERRA_DECOUPLED_FAST 1
 #endif
 #ifndef TERRA_FAST_EXIT_16THS    // MODE 2 leaves the traversal when this many 16ths of the lanes that entered it have finished (a ray is cheap there, so shading wants fuller waves)
 #define TERRA_FAST_EXIT_16THS 12
 #endif
-// (LDS-resident scenes, MODE 1, keep the coupled loop: decoupled they measure 20 % slower -- shading outweighs traversal there; CHANGELOG.md round 1 / 2)
-#define TERRA_DECOUPLED(I, M) ( TERRA_DECOUPLED_ENABLE && ( ( M ) == 0 || ( TERRA_DECOUPLED_FAST && ( M ) >= 2 ) ) && ( ( I ) == 0 || ( I ) == 3 || ( I ) == 4 || ( I ) == 5 ) )
-// ... and Direct, whose one shadow ray per hit becomes a traversal job of its own (scenes without textured attributes)
-#ifndef TERRA_DECOUPLED_DIRECT_ENABLE
-#define TERRA_DECOUPLED_DIRECT_ENABLE 1
-#endif
-#ifndef TERRA_DECOUPLED_FAST_DIRECT  // ... also on the fast tree (MODE 2): hall, 32 spp, 112.0 -> 108.2 ms
-#define TERRA_DECOUPLED_FAST_DIRECT 1
-#endif
-#ifndef TERRA_DECOUPLED_FAST_MIS     // Direct + MIS on the fast tree is faster coupled (hall, 32 spp: 168.6 ms against 187.7 decoupled, profiles/r02_measurements/ab_fast_light.log; round 4, with the
-                                     // light-sample rays' shortcut in both: 100.5 against 117.5, sphere scene 128 spp 157.8 against 162.4, profiles/r04_measurements/ab_fast_tree_knobs.log)
-#define TERRA_DECOUPLED_FAST_MIS 0
-#endif
-#define TERRA_DECOUPLED_DIRECT(I, M, K) ( TERRA_DECOUPLED_DIRECT_ENABLE && ( ( M ) == 0 || ( TERRA_DECOUPLED_FAST_DIRECT && ( M ) >= 2 ) ) && ( I ) == 1 && ( ( K ) & TERRA_KIND_TEX ) == 0 )
-#ifndef TERRA_DECOUPLED_MIS_ENABLE
-#define TERRA_DECOUPLED_MIS_ENABLE 1
-#endif
-#define TERRA_DECOUPLED_MIS(I, M, K) ( TERRA_DECOUPLED_MIS_ENABLE && ( ( M ) == 0 || ( TERRA_DECOUPLED_FAST_MIS && ( M ) >= 2 ) ) && ( I ) == 2 && ( ( K ) & TERRA_KIND_TEX ) == 0 )
-#ifndef TERRA_WAVES_DECOUPLED
-#define TERRA_WAVES_DECOUPLED TERRA_WAVES_SIMPLE
-#endif
-#ifndef TERRA_WAVES_FAST_TREE      // fast-tree (MODE 2) kernels are latency bound: more resident waves pay for the extra scratch
-#define TERRA_WAVES_FAST_TREE 5     // (round 1, coupled loop: 4 -> 81.2 ms, 5 -> 71.0, 6 -> 67.2; with the decoupled loop, hall 64 spp: 5 -> 82.0 ms, 6 -> 83.6, 7 -> 89.0)
-#endif
-#ifndef TERRA_WAVES_FAST_TREE_LIGHT  // (round 2, hall, 16 spp, Direct / MIS: 4 -> 85.0 / 135.3 ms, 5 -> 79.3 / 122.2 ms, 6 -> 74.7 / 114.5 ms; ab_fl*.log. Round 3, with the job queue and
-#define TERRA_WAVES_FAST_TREE_LIGHT 5 // without work counters, hall 64 spp: 5 -> 140.3 / 246.6 ms, 6 -> 163.5 / 267.5 ms; profiles/r03_measurements/ab_waves_light.log)
-#endif
-#ifndef TERRA_WAVES_GLOBAL_LIGHT     // reference tree read from global memory (MODE 0), Direct/MIS (sphere scene, Direct: 4 -> 864 ms, 5 -> 815 ms, 6 -> 841 ms; ab_gl*.log)
-#define TERRA_WAVES_GLOBAL_LIGHT 5
-#endif
-#ifndef TERRA_WAVES_FAST_TREE_GENERIC        // ... but the generic-kinds kernels (Phong/GGX/glass/textures compiled in) already spill at 5:
-#define TERRA_WAVES_FAST_TREE_GENERIC 5      // sphere scene, Simple, 64 spp: 5 -> 63.5 ms, 6 -> 70.1 ms, 7 -> 71.5 ms, 8 -> 81 ms (ab_ww2.log, ab_f78.log)
-#endif
-#ifndef TERRA_WAVES_FAST_TREE_GENERIC_LIGHT
-#define TERRA_WAVES_FAST_TREE_GENERIC_LIGHT 4
-#endif
-#define TERRA_IS_LIGHT(I) ( ( I ) == 1 || ( I ) == 2 || ( I ) == 6 )
-#define TERRA_WAVES_FOR(I, K, M) ( ( M ) >= 2 ? ( ( K ) == 1 ? ( TERRA_IS_LIGHT ( I ) ? TERRA_WAVES_FAST_TREE_LIGHT : TERRA_WAVES_FAST_TREE ) : ( TERRA_IS_LIGHT ( I ) ? TERRA_WAVES_FAST_TREE_GENERIC_LIGHT : TERRA_WAVES_FAST_TREE_GENERIC ) ) \
-                                 : TERRA_IS_LIGHT ( I ) ? ( ( M ) == 0 ? TERRA_WAVES_GLOBAL_LIGHT : ( ( I ) == 1 && ( ( K ) == 1 || ( TERRA_WAVES_DIRECT_PHONG && ( K ) == 3 ) ) ) ? TERRA_WAVES_DIRECT : ( ( I ) == 2 && ( K ) == 1 ) ? TERRA_WAVES_MIS : TERRA_WAVES_LIGHT ) \
-                                 : TERRA_DECOUPLED ( I, M ) ? TERRA_WAVES_DECOUPLED : ( ( K ) == 1 ? TERRA_WAVES_SIMPLE : TERRA_WAVES_GENERIC ) )
+// Occupancy of a kernel instance (second __launch_bounds__ argument = waves per SIMD = 256-thread blocks per CU): the only place it is decided. Measured on MI355X
+// (profiles/): the Simple/debug kernels run fastest at 5 even with a small spill; Direct/MIS carry a second surface and more live state.
+constexpr int terra_waves ( int I, int K, int M ) {
+    // fast-tree (MODE >= 2) kernels are latency bound: more resident waves pay for the extra scratch (round 1, coupled loop: 4 -> 81.2 ms, 5 -> 71.0, 6 -> 67.2; with the
+    // decoupled loop, hall 64 spp: 5 -> 82.0 ms, 6 -> 83.6, 7 -> 89.0; Direct / MIS, round 2, hall, 16 spp: 4 -> 85.0 / 135.3 ms, 5 -> 79.3 / 122.2 ms, 6 -> 74.7 / 114.5 ms,
+    // ab_fl*.log; round 3, with the job queue and without work counters, hall 64 spp: 5 -> 140.3 / 246.6 ms, 6 -> 163.5 / 267.5 ms; profiles/r03_measurements/ab_waves_light.log)
+    // -- but the generic-kinds kernels (Phong/GGX/glass/textures compiled in) already spill at 5 (sphere scene, Simple, 64 spp: 5 -> 63.5 ms, 6 -> 70.1 ms, 7 -> 71.5 ms,
+    // 8 -> 81 ms; ab_ww2.log, ab_f78.log), and their Direct / MIS forms run at 4
+    if ( M >= 2 ) return TERRA_IS_LIGHT ( I ) && K != 1 ? 4 : 5;
+    // LDS-resident scenes (MODE 1), Direct / MIS: 5 on diffuse-only scenes (Direct, without work counters: 5 -> 117.7 ms, 4 -> 120.4; profiles/r03_measurements/ab_waves_light.log.
+    // Direct + MIS, split at its two rays: 5 -> 158.1 ms with 116 B of scratch, 4 -> 165.4 with none; Cornell 512 spp, profiles/r04_measurements/ab_light_split.log;
+    // unsplit, round 3: 5 -> 191.9, 4 -> 178.9); 4 with any other kind compiled in, and for integrator 6
+    if ( M == 1 && TERRA_IS_LIGHT ( I ) ) return ( I == 1 || I == 2 ) && K == 1 ? 5 : 4;
+    // everything else: the Simple/debug kernels on every tree and kind set, and Direct / MIS on the reference tree read from global memory (MODE 0; sphere scene, Direct:
+    // 4 -> 864 ms, 5 -> 815 ms, 6 -> 841 ms; ab_gl*.log)
+    return 5;
+}
+// the instances DESIGN.md 3.1 names, <INTEGRATOR, COUNT, MODE, KINDS>
+static_assert ( terra_waves ( 0, 1, 1 ) == 5 && terra_waves ( 1, 1, 1 ) == 5 && terra_waves ( 2, 1, 1 ) == 5 && terra_waves ( 6, 1, 1 ) == 4 && terra_waves ( 1, 3, 1 ) == 4, "LDS-resident scenes" );
+static_assert ( terra_waves ( 1, 1, 0 ) == 5 && terra_waves ( 1, 63, 0 ) == 5 && terra_waves ( 1, 1, 2 ) == 5 && terra_waves ( 1, 63, 2 ) == 4 && terra_waves ( 0, 63, 2 ) == 5, "reference tree from global memory, fast tree" );
 // ---- pieces shared by the decoupled loops of the kernel below -----------------------------------------
 // Per-lane traversal state that survives leaving the resumable traversal (the stack column and the leaf list are in LDS).
 struct LaneTraversal { RayState st; SlabSel sel; Closest best; uint32_t rank, hand, held; int top; bool traversing, regular, anyhit; };     // anyhit: a light-sample ray that knows its triangle (traverse_fast.h fast_expect)     // hand: MODE >= 2, what the lane holds between calls (traverse_fast.h traverse_fast_resume)     // regular: MODE 0 / 1 the ray's slab variant; MODE 2 (which has no use for that) "second, checked pass" of the reachability mode     // top: entries on the lane's stack (its leaf list is always empty between calls)
@@ -349,7 +307,7 @@ TD void lane_traversal_start ( const Tracer& T, const Ray& ray, LaneTraversal& t
 // the ray just started is a light-sample ray towards triangle `expected` (soup index): traverse_fast.h fast_expect. (A ray that misses its triangle stays an ordinary ray.)
 template <int COUNT, int MODE>
 TD void lane_traversal_expect ( const Tracer& T, const Ray& ray, LaneTraversal& t, uint32_t expected ) {
-    if constexpr ( TERRA_SHADOW_ANYHIT && MODE == 2 && COUNT == 0 ) {
+    if constexpr ( MODE == 2 && COUNT == 0 ) {
         Ray r = ray; r.o = r.o + r.d * 0.001f;
         const V3 o_perm = permuted ( r.o, t.st );
         ClosestRanked b2; b2.depth = t.best.depth; b2.rank = t.rank; b2.tri = t.best.tri;
@@ -382,7 +340,7 @@ TD bool lane_traversal_run ( const Tracer& T, const Ray& ray, LaneTraversal& t, 
     int* sp = T.stack + t.top * TERRA_COL;
     if constexpr ( MODE >= 2 ) {
         ClosestRanked b2; b2.depth = t.best.depth; b2.rank = t.rank; b2.tri = t.best.tri;
-        traverse_fast_resume<COUNT> ( T, r, t.st, o_perm, b2, sp, t.hand, t.held, exit_active, c, MODE == 3 && T.sc.reach && !t.regular, TERRA_SHADOW_ANYHIT && MODE == 2 && COUNT == 0 && t.anyhit );      // (a ray with a zero direction component starts in the checked pass: harmless)
+        traverse_fast_resume<COUNT> ( T, r, t.st, o_perm, b2, sp, t.hand, t.held, exit_active, c, MODE == 3 && T.sc.reach && !t.regular, MODE == 2 && COUNT == 0 && t.anyhit );      // (a ray with a zero direction component starts in the checked pass: harmless)
         t.traversing = fast_traversing ( T, t.hand, t.held, sp );
         t.best.depth = b2.depth; t.best.tri = b2.tri; t.rank = b2.rank;
     } else {
@@ -516,7 +474,7 @@ TD void job_next ( const DevRenderParams& p, float* aux, Jobs& j, PixelStreams& 
     if ( !got ) { j.exhausted = true; return; }                  // the queue is monotone: a batch that does not cover the askers means nothing is left, ever
     uint32_t chunk;
     int prior_samples;
-    if constexpr ( TERRA_JOB_STREAM_TABLE && TABLE ) {
+    if constexpr ( TABLE ) {
         const uint4 e1 = p.job_streams[2 * ( size_t ) job + 1];       // keyed by terra_job_streams_kernel (below): the job's pixel comes with it, the decode's divisions are not repeated here
         const uint4 e0 = p.job_streams[2 * ( size_t ) job];
         // both halves of the entry are asked for BEFORE the first is looked at: the compiler otherwise fetches e1.z, waits, branches, and only then fetches the rest -- two
@@ -585,7 +543,7 @@ TD void job_take ( const RenderKernelParams& p, float* aux, Jobs& j, PixelStream
 #endif
 
 template <int INTEGRATOR, int COUNT, int MODE, int KINDS>
-__global__ __launch_bounds__ ( 256, TERRA_WAVES_FOR ( INTEGRATOR, KINDS, MODE ) ) void terra_render_kernel ( RenderKernelParams p ) {
+__global__ __launch_bounds__ ( 256, terra_waves ( INTEGRATOR, KINDS, MODE ) ) void terra_render_kernel ( RenderKernelParams p ) {
     extern __shared__ float4 lds_f4[];
     const int tid = threadIdx.x;
     Tracer T0 = make_tracer<MODE> ( p.scene, lds_f4, p.stack_depth, p.leaf_cap, p.lds_nodes, p.lds_tris, p.leaf_cull != 0, p.fused_slab != 0, p.leaf_rank != 0, p.leaf_boxes, p.n_leaf_boxes, terra_leaf_pair_table ( p ) );
@@ -610,7 +568,7 @@ __global__ __launch_bounds__ ( 256, TERRA_WAVES_FOR ( INTEGRATOR, KINDS, MODE ) 
     PrimaryRay held; held.o = v3 ( 0, 0, 0 ); held.d = v3 ( 0, 0, 1 );      // the job's ray (TERRA_RAY_HOLD only)
 #endif
 
-    if constexpr ( TERRA_DECOUPLED_MIS ( INTEGRATOR, MODE, KINDS ) ) {
+    if constexpr ( terra_decoupled_mis ( INTEGRATOR, MODE, KINDS ) ) {
         // Decoupled loop for Direct + MIS: like the Direct one below with two shadow jobs per shaded hit, in the reference's
         // order -- A: the ray to the light sample, B: the BSDF-sampled ray (mis_prepare / mis_finish_b).
         LaneTraversal lt = lane_traversal_idle ( T, ray );
@@ -671,7 +629,7 @@ __global__ __launch_bounds__ ( 256, TERRA_WAVES_FOR ( INTEGRATOR, KINDS, MODE ) 
             }
             if ( !lane_traversal_run<COUNT, MODE> ( T, ray, lt, c ) && __all ( done ) ) break;      // nobody traversing and no job left
         }
-    } else if constexpr ( TERRA_DECOUPLED_DIRECT ( INTEGRATOR, MODE, KINDS ) ) {
+    } else if constexpr ( terra_decoupled_direct ( INTEGRATOR, MODE, KINDS ) ) {
         // Decoupled loop for the Direct integrator. A lane's ray in flight is either a path segment (MAIN) or the shadow
         // ray of the hit it just shaded (SHADOW). Shading a MAIN hit draws the light sample, prepares both outcomes of the
         // shadow test (direct_prepare), samples the BSDF and plays Russian roulette -- all stream draws in the reference's
@@ -686,7 +644,7 @@ __global__ __launch_bounds__ ( 256, TERRA_WAVES_FOR ( INTEGRATOR, KINDS, MODE ) 
                 bool start = false;
                 V3 ro = v3 ( 0, 0, 0 ), rd = v3 ( 0, 0, 1 );
                 if ( have_ray && shadow ) {                      // the shadow ray came back
-                    const uint32_t tri_s = ( TERRA_SHADOW_ANYHIT && MODE == 2 && COUNT == 0 && lt.best.tri == TERRA_TRI_EXPECTED ) ? pend.expected : hit_soup_index<MODE> ( T, lt.best.tri );
+                    const uint32_t tri_s = ( MODE == 2 && COUNT == 0 && lt.best.tri == TERRA_TRI_EXPECTED ) ? pend.expected : hit_soup_index<MODE> ( T, lt.best.tri );
                     if ( tri_s != 0xffffffffu ) {                   // (its hit counts as a surface init, as in the coupled form)
                         if ( COUNT ) ++c.hits;
                         if ( COUNT == 2 ) { const float4 t0 = reinterpret_cast<const float4*> ( T.sc.tris ) [3 * tri_s]; c.attr_fetches += T.sc.mats[__float_as_uint ( t0.w )].attributes_count + 1; }
@@ -726,7 +684,7 @@ __global__ __launch_bounds__ ( 256, TERRA_WAVES_FOR ( INTEGRATOR, KINDS, MODE ) 
             }
             if ( !lane_traversal_run<COUNT, MODE> ( T, ray, lt, c ) && __all ( done ) ) break;      // nobody traversing and no job left
         }
-    } else if constexpr ( TERRA_DECOUPLED ( INTEGRATOR, MODE ) ) {
+    } else if constexpr ( terra_decoupled ( INTEGRATOR, MODE ) ) {
         // Decoupled loop (scenes read from global memory, integrators without nested raycasts): a lane is either
         // traversing its current ray or waiting to be shaded. The resumable traversal returns as soon as 1/16 of
         // the lanes that entered it have finished; those are shaded and handed their next ray (continuation or the
@@ -773,12 +731,9 @@ __global__ __launch_bounds__ ( 256, TERRA_WAVES_FOR ( INTEGRATOR, KINDS, MODE ) 
     bool alive = false;
     V3 ro = v3 ( 0, 0, 0 ), rd = v3 ( 0, 0, 1 );                     // origin / direction of the lane's next ray; the reciprocals are taken in ONE place for camera and continuation rays
     // The path's radiance Lo: a term is added on the few hits that emit (or, Direct / MIS, are lit) and the sum is needed when the path ends -- in between it only
-    // occupies three registers of a kernel that has none to spare. LDS-resident scenes park it next to the job's sum. Adding a term of +-0 would leave every
-    // component as it is (Lo is never -0: it starts at +0 and x + (-x) = +0), so skipping such terms is exact.
-#ifndef TERRA_LO_IN_LDS_LIGHT     // ... also for Direct / MIS, whose Lo changes on most hits (A/B)
-#define TERRA_LO_IN_LDS_LIGHT 1
-#endif
-    constexpr bool LO_LDS = TERRA_LO_IN_LDS && MODE == 1 && ( TERRA_LO_IN_LDS_LIGHT || !TERRA_IS_LIGHT ( INTEGRATOR ) );
+    // occupies three registers of a kernel that has none to spare. LDS-resident scenes park it next to the job's sum, in rows 6-8 (also for Direct / MIS, whose Lo
+    // changes on most hits). Adding a term of +-0 would leave every component as it is (Lo is never -0: it starts at +0 and x + (-x) = +0), so skipping such terms is exact.
+    constexpr bool LO_LDS = MODE == 1;
     float* lo_lds = acc_lds + 6 * 256;
     auto lo_reset = [&] () { if ( LO_LDS ) { lo_lds[0] = 0.f; lo_lds[256] = 0.f; lo_lds[512] = 0.f; } else Lo = v3 ( 0, 0, 0 ); };
     auto lo_add = [&] ( V3 t ) {
@@ -786,12 +741,6 @@ __global__ __launch_bounds__ ( 256, TERRA_WAVES_FOR ( INTEGRATOR, KINDS, MODE ) 
         else Lo = Lo + t;
     };
     auto lo_deposit = [&] () { if ( LO_LDS ) deposit ( acc_lds, v3 ( lo_lds[0], lo_lds[256], lo_lds[512] ) ); else deposit ( acc_lds, Lo ); };
-#ifndef TERRA_COUPLED_DIRECT_SPLIT     // the coupled loop's Direct integrator split at its shadow ray (below); 0: integrate_direct as one piece (A/B)
-#define TERRA_COUPLED_DIRECT_SPLIT 1
-#endif
-#ifndef TERRA_COUPLED_MIS_SPLIT        // ... and Direct + MIS at its two rays
-#define TERRA_COUPLED_MIS_SPLIT 1
-#endif
 #ifndef TERRA_REGEN_MIN           // (A/B) lanes whose path ended wait until this many of the wave's lanes have, then start their next camera rays TOGETHER (same bounce depth afterwards)
 #define TERRA_REGEN_MIN 1
 #endif
@@ -823,7 +772,7 @@ __global__ __launch_bounds__ ( 256, TERRA_WAVES_FOR ( INTEGRATOR, KINDS, MODE ) 
                 // Direct on scenes whose emissive attributes are constants: the integrator is split at its shadow ray. Everything that does not depend on the ray's outcome --
                 // the light sample, both possible values of the integrator, then the continuation's draws, in the reference's order (src/Terra.c:1068-1079 after :1349-1426) --
                 // comes BEFORE the shadow traversal, so that the traversal runs with a pending pair and a continuation ray in registers instead of the whole shaded surface
-                constexpr bool SPLIT_DIRECT = TERRA_COUPLED_DIRECT_SPLIT && INTEGRATOR == 1 && ( KINDS & ( TERRA_KIND_TEX | TERRA_KIND_SAMPLER ) ) == 0;
+                constexpr bool SPLIT_DIRECT = INTEGRATOR == 1 && ( KINDS & ( TERRA_KIND_TEX | TERRA_KIND_SAMPLER ) ) == 0;
                 if constexpr ( SPLIT_DIRECT ) {
                     Ray shadow_ray;
                     const DirectPending pend = direct_prepare<COUNT, KINDS, MODE> ( T, sf, h.point, wo, throughput, bounce, rs.b, c, shadow_ray );
@@ -832,7 +781,7 @@ __global__ __launch_bounds__ ( 256, TERRA_WAVES_FOR ( INTEGRATOR, KINDS, MODE ) 
                     if ( !end ) { ro = surface_origin ( sf, h.point ); rd = wi; }
                     const uint32_t tri = scene_raycast_triangle<COUNT, MODE> ( T, shadow_ray, c, pend.expected );
                     lo_add ( tri == pend.expected ? pend.vis : pend.hid );
-                } else if constexpr ( TERRA_COUPLED_MIS_SPLIT && INTEGRATOR == 2 && ( KINDS & ( TERRA_KIND_TEX | TERRA_KIND_SAMPLER ) ) == 0 ) {
+                } else if constexpr ( INTEGRATOR == 2 && ( KINDS & ( TERRA_KIND_TEX | TERRA_KIND_SAMPLER ) ) == 0 ) {
                     // Direct + MIS split the same way at its two rays (mis_prepare / mis_finish_b, src/Terra.c:1428-1587): A, the ray to the light sample, only has to
                     // name the triangle it hits; B, the BSDF-sampled ray, needs the surface it hits
                     Ray ray_a; V3 b_d;
@@ -917,14 +866,11 @@ static hipError_t launch_kinds ( const RenderKernelParams& p, size_t lds, hipStr
 }
 // kinds present in the scene -> the leanest compiled variant that covers them: diffuse only (1), diffuse + Phong (3: what
 // OBJ/MTL scenes map to, satellite/src/Scene.cpp:193-230), everything (GGX, glass, textures, environment term), or everything + the sampler integration
-#ifndef TERRA_KINDS_PRESETS_VARIANT
-#define TERRA_KINDS_PRESETS_VARIANT 1
-#endif
 template <int I, int MODE>
 static hipError_t launch_mode ( const RenderKernelParams& p, size_t lds, hipStream_t stream ) {
     if ( p.bsdf_kinds == 1 ) return launch_kinds<I, MODE, 1> ( p, lds, stream );
     if ( ( p.bsdf_kinds & ~3u ) == 0 ) return launch_kinds<I, MODE, 3> ( p, lds, stream );
-    if constexpr ( TERRA_KINDS_PRESETS_VARIANT && I <= 2 && MODE != 0 ) {       // the four presets on constant attributes, no environment term (BASELINE config 4's sphere scene): the usual integrators, off the reference tree
+    if constexpr ( I <= 2 && MODE != 0 ) {       // the four presets on constant attributes, no environment term (BASELINE config 4's sphere scene): the usual integrators, off the reference tree
         if ( ( p.bsdf_kinds & ~15u ) == 0 ) return launch_kinds<I, MODE, 15> ( p, lds, stream );
     }
     if ( ( p.bsdf_kinds & TERRA_KIND_SAMPLER ) == 0 ) return launch_kinds<I, MODE, TERRA_KINDS_ALL & ~TERRA_KIND_SAMPLER> ( p, lds, stream );      // (the sampler integration costs the generic

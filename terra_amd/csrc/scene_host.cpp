@@ -802,7 +802,7 @@ static void build_reach_tables ( const std::vector<DevNode>& nodes, const std::v
 }
 
 // DevScene::sincos24, one table per device for the life of the process (128 MB of its 288 GB; filled by tdm_sincosf_pair itself, ~1 ms). nullptr when it cannot
-// be had (or TERRA_AMD_NO_SINCOS_TABLE is set: A/B runs) -- the kernels then compute.
+// be had (or terra_amd_set_azimuth_table turned it off) -- the kernels then compute.
 static std::atomic<bool> g_azimuth_table { true };
 extern "C" void terra_amd_set_azimuth_table ( int on ) { g_azimuth_table.store ( on != 0, std::memory_order_relaxed ); }      // (takes effect at the next commit)
 static const float2* sincos_table_of ( int device ) {
@@ -1415,8 +1415,8 @@ extern "C" int terra_amd_scene_leaf_pair_masks ( HTerraScene h, uint32_t* out, i
     return n;
 }
 // The LDS plan of the scene's launches as launch_plan.h makes it, from the commit's host-side counts (needs no device). out[0] = bytes per block of a launch that
-// takes the pair form where the scene has one (terra_lds_bytes), out[1] = of those, the shading constants (dev_types.h "shading constants"; 0: no pair form, or
-// TERRA_SHADE_CONSTS 0), out[2] = the pair section, out[3] = TERRA_LDS_BUDGET, out[4] = triangles staged (0: the scene is not LDS-resident), out[5] = leaf_rank.
+// takes the pair form where the scene has one (terra_lds_bytes), out[1] = of those, the shading constants (dev_types.h "shading constants"; 0: no pair form),
+// out[2] = the pair section, out[3] = TERRA_LDS_BUDGET, out[4] = triangles staged (0: the scene is not LDS-resident), out[5] = leaf_rank.
 extern "C" int terra_amd_scene_lds_plan ( HTerraScene h, uint32_t* out6 ) {
     Scene* s = S ( h );
     if ( !s->committed ) return fail ( kTerraAmdErrNotCommitted, "scene not committed" );
@@ -1594,11 +1594,9 @@ static int fill_params ( Scene* s, const Scene::Replica& r, const TerraCamera* c
     p.leaf_pairs = 0;
     if ( s->leaf_pair_form && r.d_blob && !s->leaf_pairs.empty() && p.lds_mode == 1 && p.leaf_rank ) p.leaf_pairs = ( uint32_t ) ( s->blob.sec[kSecLeafPairs].offset - s->blob.sec[kSecTris].offset );      // (both in the blob; scenes of at most 32 triangles: a few KB apart)
     // the azimuth table pays where VALU issue binds (LDS-resident scenes: Cornell Simple 65.8 -> 64.2 ms, Direct 145.2 -> 142.5); the kernels that wait on memory anyway
-    // lose by one more dependent load per shaded hit (sphere scene 395 -> 419 ms, hall 282 -> 284; profiles/r03_measurements/ab_sincos_table.log)
-#ifndef TERRA_SINCOS_TABLE_FAST_TREE       // (A/B) the azimuth table for fast-tree launches too
-#define TERRA_SINCOS_TABLE_FAST_TREE 0
-#endif
-    if ( p.lds_mode != 1 && ! ( TERRA_SINCOS_TABLE_FAST_TREE && p.lds_mode == 2 ) ) p.scene.sincos24 = nullptr;
+    // lose by one more dependent load per shaded hit (sphere scene 395 -> 419 ms, hall 282 -> 284; profiles/r03_measurements/ab_sincos_table.log;
+    // fast-tree launches alone: hall 218.9 -> 219.6 ms, sphere scene 318.6 -> 321.1, profiles/r04_measurements/ab_fast_node_formats.log)
+    if ( p.lds_mode != 1 ) p.scene.sincos24 = nullptr;
     // what this call runs (TerraAmdTraversalInfo::last_call): the commit-time decision can be overridden per call by the camera position
     s->last_call.store ( p.lds_mode == 2 ? ( r.dev.reach ? kTerraAmdCallFastTreeReach : kTerraAmdCallFastTree ) : ( p.leaf_cull ? kTerraAmdCallLeafCull : kTerraAmdCallReplica ), std::memory_order_relaxed );
     p.bsdf_kinds = s->bsdf_kinds;

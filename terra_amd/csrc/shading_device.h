@@ -90,7 +90,7 @@ TD void surface_init ( const Tracer& T, uint32_t ti, V3 point, Surface& sf, uint
     uint32_t object = __float_as_uint ( t0.w );
     object_out = object; tri_in_object_out = __float_as_uint ( t1.w );
     float u, v;
-    if ( MODE == 1 && TERRA_SHADE_CONSTS && T.l_consts ) {          // pair-form launches: e0, e1, d00, d11, d01, div as make_tracer formed them once per block, by these very operations
+    if ( MODE == 1 && T.l_consts ) {          // pair-form launches: e0, e1, d00, d11, d01, div as make_tracer formed them once per block, by these very operations
         const float4 c0 = T.l_consts[3 * ti], c1 = T.l_consts[3 * ti + 1], c2 = T.l_consts[3 * ti + 2];
         const V3 e0 = v3 ( c0.x, c0.y, c0.z ), e1 = v3 ( c0.w, c1.x, c1.y ), p = point - v3 ( t0.x, t0.y, t0.z );
         const float d00 = c1.z, d11 = c1.w, d01 = c2.x, div = c2.y;
@@ -169,7 +169,7 @@ TD uint32_t scene_raycast_triangle ( const Tracer& T, const Ray& in, Counters& c
     r.o = r.o + r.d * 0.001f;
     RayState st = ray_state_init ( r );
     if ( COUNT ) ++c.rays;
-    if constexpr ( TERRA_SHADOW_ANYHIT && MODE == 2 && COUNT == 0 ) {
+    if constexpr ( MODE == 2 && COUNT == 0 ) {
         const V3 o_perm = permuted ( r.o, st );
         ClosestRanked best;
         if ( !fast_expect ( T, st, o_perm, expected, best ) ) return 0xffffffffu;          // (not the expected triangle; without counters nothing else is asked)
@@ -181,7 +181,7 @@ TD uint32_t scene_raycast_triangle ( const Tracer& T, const Ray& in, Counters& c
     // BEYOND the expected triangle's depth, a triangle as near as the expected one wins exactly when the reference meets it earlier; the expected triangle itself, when
     // its leaf is reached, takes the record as it would; and the traversal ends at the first OTHER triangle that takes it (traverse_loops ANYHIT): up to there it has
     // made the reference's decisions one by one, after that none can change the answer. A ray that misses its triangle is not traced at all.
-    if constexpr ( TERRA_SHADOW_ANYHIT && MODE == 1 && COUNT == 0 ) {
+    if constexpr ( MODE == 1 && COUNT == 0 ) {
         const V3 o_perm = permuted ( r.o, st );
         float depth;
         if ( !watertight_permuted ( tri_perm_lds ( T.l_tris + 12 * expected, st ), o_perm, st, depth ) ) return 0xffffffffu;
@@ -189,7 +189,7 @@ TD uint32_t scene_raycast_triangle ( const Tracer& T, const Ray& in, Counters& c
         // pair form (traverse_ref.h traverse_pairs): the trips are not in rank order, so the record is preset to the expected triangle's own (depth, key) exactly and the
         // first triangle that beats it in that order answers "another one" (key 0)
         if ( T.pairs ) { best.depth = depth; best.tri = terra_pair_key ( __float_as_uint ( T.l_tris[12 * expected + 11] ), expected ); }
-        if ( TERRA_FUSED_SLAB && T.fused && __all ( ray_is_tame ( r ) ) ) traverse_loops<COUNT, MODE, true, true, true> ( T, r, st, o_perm, best, c, expected );
+        if ( T.fused && __all ( ray_is_tame ( r ) ) ) traverse_loops<COUNT, MODE, true, true, true> ( T, r, st, o_perm, best, c, expected );
         else if ( __all ( ray_is_regular ( r ) ) ) traverse_loops<COUNT, MODE, true, false, true> ( T, r, st, o_perm, best, c, expected );
         else traverse_loops<COUNT, MODE, false, false, true> ( T, r, st, o_perm, best, c, expected );
         if ( T.pairs ) return best.tri != 0u ? expected : 0xffffffffu;

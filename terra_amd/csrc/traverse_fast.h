@@ -104,9 +104,6 @@ TD bool reference_reaches ( const Tracer& T, uint32_t ti, const Ray& ray ) {
 #ifndef TERRA_FAST_LEAF_16THS
 #define TERRA_FAST_LEAF_16THS 12
 #endif
-#ifndef TERRA_FAST_SORT            // 1: the entered children of a node are visited nearest first (sorting network); 0: nearest first, the rest in slot order (A/B)
-#define TERRA_FAST_SORT 1
-#endif
 // (the test "is this entry in the LDS column" compares the entry's 32-bit LDS address with ONE wave-uniform limit: entry e of thread t sits at column base + e * 1024 + t * 4,
 //  and t * 4 < 1024, so address < base + cap * 1024 exactly when e < cap; the HBM index is computed on the cold side only)
 // (Entries that carry their box's entry distance, so that one the closest hit has overtaken is dropped when it comes off the stack, were measured: 8 % fewer node
@@ -175,11 +172,9 @@ TD void traverse_fast_resume ( const Tracer& T, const Ray& ray, const RayState& 
                     // nearest first: the entry distances (>= 0, so their bit patterns order like the floats) sorted with their child words; a box not entered sorts last
                     uint32_t k0 = hit0 ? __float_as_uint ( te0 ) : 0xffffffffu, k1 = hit1 ? __float_as_uint ( te1 ) : 0xffffffffu, k2 = hit2 ? __float_as_uint ( te2 ) : 0xffffffffu, k3 = hit3 ? __float_as_uint ( te3 ) : 0xffffffffu;
                     uint32_t c0 = ch.x, c1 = ch.y, c2 = ch.z, c3 = ch.w;
-#if TERRA_FAST_SORT
+                    // (a full sorting network: finding only the nearest and pushing the others in slot order measured hall 218.9 -> 220.7 ms, sphere scene 318.6 -> 314.9;
+                    //  profiles/r04_measurements/ab_fast_node_formats.log)
                     order_pair ( k0, c0, k1, c1 ); order_pair ( k2, c2, k3, c3 ); order_pair ( k0, c0, k2, c2 ); order_pair ( k1, c1, k3, c3 ); order_pair ( k1, c1, k2, c2 );
-#else               // (A/B) only the nearest is found; the others go on the stack in slot order
-                    order_pair ( k0, c0, k1, c1 ); order_pair ( k0, c0, k2, c2 ); order_pair ( k0, c0, k3, c3 );
-#endif
                     // the farthest goes in first, so the nearer ones come off first. (Branch-free pushes -- every child word stored at the top, the top moved only for the
                     // entered ones -- measured no faster on the hall and 2 % slower on the sphere scene: profiles/r04_measurements/ab_fast_tree_knobs.log)
                     if ( k3 != 0xffffffffu ) fast_push ( T, top, c3 );
@@ -225,9 +220,6 @@ TD void traverse_fast_resume ( const Tracer& T, const Ray& ray, const RayState& 
 // TERRA_TRI_EXPECTED if none does. Scenes inside the coordinate range only (MODE 2: what the reference reaches needs no replay), kernels without work counters only
 // (the attribute-fetch counter is defined by the CLOSEST hit's material). DevTri::pad of the soup holds the rank when the scene has a fast tree.
 #define TERRA_TRI_EXPECTED 0xfffffffeu
-#ifndef TERRA_SHADOW_ANYHIT
-#define TERRA_SHADOW_ANYHIT 1
-#endif
 TD bool fast_expect ( const Tracer& T, const RayState& st, V3 o_perm, uint32_t expected_soup, ClosestRanked& best ) {
     const float4* tris = reinterpret_cast<const float4*> ( T.sc.tris );
     const float4 a = tris[3 * expected_soup], b = tris[3 * expected_soup + 1], cc = tris[3 * expected_soup + 2];

@@ -94,7 +94,7 @@ struct Tracer {
     const DevLight*    l_lights;
     const float*       l_area;
     const float4* l_ranked;    // ranked launches: the 6 permuted copies of the staged triangles, in rank order -- pair form: the pair section, 6 copies of the entries then the leaf-box table -- (see above); nullptr otherwise
-    const float4* l_consts = nullptr;      // pair-form launches with TERRA_SHADE_CONSTS: three float4 per staged triangle (dev_types.h "shading constants"); nullptr in every other launch and in every Tracer filled by hand
+    const float4* l_consts = nullptr;      // pair-form launches: three float4 per staged triangle (dev_types.h "shading constants"); nullptr in every other launch and in every Tracer filled by hand
     uint32_t      n_boxes;     // flat leaf-box test: the distinct leaf boxes staged -- planes in the pad words of l_ranked (pair form: in the pair section's own part), masks in those of l_props (see above); 0 in every other launch
     uint32_t      lds_nodes, lds_tris;
     int*          stack;       // this thread's column
@@ -403,15 +403,12 @@ TD void traverse_loops ( const Tracer& T, const Ray& r, const RayState& st, V3 o
     }
 }
 
-#ifndef TERRA_FUSED_SLAB
-#define TERRA_FUSED_SLAB 1
-#endif
 template <int COUNT, int MODE>
 TD Closest bvh_traverse ( const Tracer& T, const Ray& r, const RayState& st, Counters& c ) {
     Closest best; best.depth = FLT_MAX; best.tri = 0xffffffffu;
     V3 o_perm = permuted ( r.o, st );
     // the slab variant is chosen per WAVE: one irregular ray sends its whole wave down the exact path
-    if ( TERRA_FUSED_SLAB && MODE == 1 && T.fused && __all ( ray_is_tame ( r ) ) ) traverse_loops<COUNT, MODE, true, true> ( T, r, st, o_perm, best, c );
+    if ( MODE == 1 && T.fused && __all ( ray_is_tame ( r ) ) ) traverse_loops<COUNT, MODE, true, true> ( T, r, st, o_perm, best, c );
     else if ( __all ( ray_is_regular ( r ) ) ) traverse_loops<COUNT, MODE, true> ( T, r, st, o_perm, best, c );
     else traverse_loops<COUNT, MODE, false> ( T, r, st, o_perm, best, c );
     return best;
