@@ -34,6 +34,7 @@
  *       [--environment map.hdr|map.pfm] [--environment-color r g b] [--env-light] [--env-sampling off|table|mis] [--aov PREFIX] [--denoise K]
  *       [--passes N] [--denoise-variance K] [--adaptive TARGET [--min-passes A] [--max-passes B]] [--variance out.pfm]
  *       [--frames N] [--camera-to px py pz dx dy dz] [--temporal ALPHA]
+ *       [--camera-model pinhole|thinlens|ortho|equirect|fisheye] [--aperture R] [--focus D] [--ortho-height H] [--fisheye-fov DEG]
  *
  * Environment: the scene's environment attribute is a constant (--environment-color, default 0.4 0.52 1) or a lat-long map (--environment: Radiance .hdr with flat
  * or new-style run-length-encoded scanlines, orientation -Y H +X W, texel = m 2^(e - 136); or .pfm, either byte order, bottom row first), bound as a 3-component
@@ -77,6 +78,21 @@ typedef struct { float radiance[3]; float length; float normal[3]; float depth; 
 typedef struct { float alpha; float depth_tolerance; float normal_cos; int reserved; } TemporalOptions;
 int         terra_amd_reproject ( HTerraScene, const TerraCamera*, const TerraCamera*, const TerraFramebuffer*, const void*, const void*, void*, void*, void*,
                                   size_t, size_t, size_t, size_t, const void* ) __attribute__ ( ( weak ) );
+
+/* camera models (TerraAmdLens and the lens calls of terra_amd.h "Lens rendering", restated for the same reason) */
+typedef struct { int model; float lens_radius, focus_distance, ortho_height, fisheye_fov; int reserved[3]; } Lens;
+int         terra_amd_render_lens ( const TerraCamera*, const void*, HTerraScene, const TerraFramebuffer*, size_t, size_t, size_t, size_t ) __attribute__ ( ( weak ) );
+int         terra_amd_render_aov_lens ( const TerraCamera*, const void*, HTerraScene, void*, size_t, size_t, size_t, size_t, size_t, size_t ) __attribute__ ( ( weak ) );
+/* --camera-model: non-NULL = every render call and its AOV call go through the lens door */
+static const Lens* g_lens = NULL;
+static void render_rect ( const TerraCamera* cam, HTerraScene scene, const TerraFramebuffer* fb, size_t x, size_t y, size_t w, size_t h ) {
+    if ( g_lens ) ( void ) terra_amd_render_lens ( cam, g_lens, scene, fb, x, y, w, h );
+    else terra_render ( cam, scene, fb, x, y, w, h );
+}
+static void render_aov_rect ( const TerraCamera* cam, HTerraScene scene, void* aov, size_t W, size_t H, size_t x, size_t y, size_t w, size_t h ) {
+    if ( g_lens ) ( void ) terra_amd_render_aov_lens ( cam, g_lens, scene, aov, W, H, x, y, w, h );
+    else ( void ) terra_amd_render_aov ( cam, scene, aov, W, H, x, y, w, h );
+}
 
 /* ---- growable arrays ------------------------------------------------------------------------ */
 #define VEC(T) struct { T* d; size_t n, cap; }
@@ -589,6 +605,11 @@ static const char* kHelp =
     "  --temporal ALPHA (libterra_amd.so only, with --frames and --denoise K or --denoise-variance K): each frame also gets its AOV pass and is blended into the\n"
     "           history of the frames before it, reprojected to where each surface lay under the previous camera (terra_amd_reproject; ALPHA in (0, 1], 0 = 0.2);\n"
     "           the blended frame is written through that filter (the variance of --denoise-variance is the history's own)\n"
+    "  --camera-model pinhole|thinlens|ortho|equirect|fisheye (libterra_amd.so only; pinhole is the default): the render and AOV calls go through the lens door\n"
+    "           (terra_amd_render_lens, terra_amd_render_aov_lens) with --aperture R (thinlens: the lens radius, 0 = pinhole) and --focus D (the distance of the plane\n"
+    "           in focus), --ortho-height H (ortho: the world height of the film window), --fisheye-fov DEG (fisheye: the angle across the frame's height, up to 360).\n"
+    "           Works with --passes, --aov, --denoise, --denoise-variance, --variance and --frames; not with --adaptive / --gpus (ignored), and --temporal is refused:\n"
+    "           reprojection is defined for the pinhole only\n"
     "OBJ/MTL import (--normals apollo, the default): the policy of the reference client's importer (satellite/include/Apollo.h under the\n"
     "options of satellite/src/Scene.cpp:83-93) RESTATED in this tool and pinned by hand-derived fixtures -- restated, not executed: Apollo.h\n"
     "does not compile with this image's toolchains. Everything after the TerraObject fill (commit, render, export) is the pinned path.\n";
@@ -603,6 +624,7 @@ int main ( int argc, char** argv ) {
     int passes = 1, denoise_var = -1, min_passes = 0, max_passes = 0; float adaptive = 0.f; const char* variance_path = NULL;
     int frames = 0, have_camera_to = 0; float temporal = -1.f; TerraCamera cam_to; memset ( &cam_to, 0, sizeof cam_to );
     const char* dump_path = NULL; int no_render = 0;
+    int camera_model = 0; float aperture = 0.f, focus = 1.f, ortho_height = 2.f, fisheye_fov = 180.f;      /* camera_model: 0 pinhole, 1 thinlens, 2 ortho, 3 equirect, 4 fisheye */
     float fov = 45.f, exposure = 1.f, gamma = 2.2f, jitter = 0.f;
     unsigned long long seed = 0;
     const char* env_path = NULL; float env_rgb[3] = { 0.4f, 0.52f, 1.f }; int env_light = 0, env_sampling = 0;      /* env_sampling: 0 off, 1 table, 2 mis */
@@ -644,6 +666,11 @@ int main ( int argc, char** argv ) {
         else if ( !strcmp ( a, "--variance" ) ) variance_path = NEXT();
         else if ( !strcmp ( a, "--frames" ) ) { frames = atoi ( NEXT() ); if ( frames < 1 ) { fprintf ( stderr, "terra_headless: --frames 1 ...\n" ); return 64; } }
         else if ( !strcmp ( a, "--temporal" ) ) { temporal = ( float ) atof ( NEXT() ); if ( !( temporal >= 0.f && temporal <= 1.f ) ) { fprintf ( stderr, "terra_headless: --temporal ALPHA in (0, 1], or 0 for 0.2\n" ); return 64; } }
+        else if ( !strcmp ( a, "--camera-model" ) ) { static const char* const n[] = { "pinhole", "thinlens", "ortho", "equirect", "fisheye" }; camera_model = pick ( NEXT(), n, 5, -1 ); if ( camera_model < 0 ) { fprintf ( stderr, "terra_headless: --camera-model pinhole|thinlens|ortho|equirect|fisheye\n" ); return 64; } }
+        else if ( !strcmp ( a, "--aperture" ) ) aperture = ( float ) atof ( NEXT() );
+        else if ( !strcmp ( a, "--focus" ) ) focus = ( float ) atof ( NEXT() );
+        else if ( !strcmp ( a, "--ortho-height" ) ) ortho_height = ( float ) atof ( NEXT() );
+        else if ( !strcmp ( a, "--fisheye-fov" ) ) fisheye_fov = ( float ) atof ( NEXT() );
         else if ( !strcmp ( a, "--camera-to" ) && i + 6 < argc ) {
             cam_to.position = terra_f3_set ( ( float ) atof ( argv[i + 1] ), ( float ) atof ( argv[i + 2] ), ( float ) atof ( argv[i + 3] ) );
             cam_to.direction = terra_f3_set ( ( float ) atof ( argv[i + 4] ), ( float ) atof ( argv[i + 5] ), ( float ) atof ( argv[i + 6] ) ); i += 6; have_camera_to = 1;
@@ -702,6 +729,19 @@ int main ( int argc, char** argv ) {
         for ( int k = 0; k < gpus; ++k ) devs[k] = k;
         if ( terra_amd_set_devices ( devs, gpus ) != 0 ) { fprintf ( stderr, "terra_headless: %s\n", terra_amd_last_error ? terra_amd_last_error() : "terra_amd_set_devices failed" ); return 69; }
     }
+    Lens lens; memset ( &lens, 0, sizeof lens );          /* --camera-model: the lens door's camera model */
+    if ( camera_model > 0 ) {
+        if ( temporal >= 0.f ) { fprintf ( stderr, "terra_headless: --temporal with --camera-model other than pinhole: reprojection is defined for the pinhole camera only\n" ); return 64; }
+        if ( !terra_amd_render_lens || !terra_amd_render_aov_lens ) fprintf ( stderr, "terra_headless: --camera-model needs libterra_amd.so; ignored, the pinhole image is written\n" );
+        else {
+            lens.model = camera_model - 1;
+            if ( camera_model == 1 ) { lens.lens_radius = aperture; lens.focus_distance = focus; }
+            if ( camera_model == 2 ) lens.ortho_height = ortho_height;
+            if ( camera_model == 4 ) lens.fisheye_fov = fisheye_fov;
+            g_lens = &lens;
+            if ( gpus > 0 || adaptive > 0.f ) { fprintf ( stderr, "terra_headless: --camera-model does not mirror --gpus / --adaptive; those are ignored\n" ); gpus = 0; adaptive = 0.f; }
+        }
+    }
     MomentSum* mom = NULL;       /* --passes / --denoise-variance / --adaptive / --variance: the second moments of the batch means */
     if ( passes > 1 || denoise_var >= 0 || adaptive > 0.f || variance_path ) {
         const char* why = ( !terra_amd_accumulate_moments || !terra_amd_denoise_variance || !terra_amd_render_adaptive || !terra_amd_render_aov ) ? "need libterra_amd.so" : gpus > 0 ? "do not mirror --gpus (the sharded render)" : NULL;
@@ -758,8 +798,8 @@ int main ( int argc, char** argv ) {
                 const size_t tl = tile ? tile : ( W > H ? W : H );
                 for ( size_t y = 0; y < H; y += tl ) for ( size_t x = 0; x < W; x += tl ) {
                     const size_t tw = W - x < tl ? W - x : tl, th = H - y < tl ? H - y : tl;
-                    terra_render ( &cf, scene, &fb, x, y, tw, th );
-                    if ( aov ) ( void ) terra_amd_render_aov ( &cf, scene, aov, W, H, x, y, tw, th );
+                    render_rect ( &cf, scene, &fb, x, y, tw, th );
+                    if ( aov ) render_aov_rect ( &cf, scene, aov, W, H, x, y, tw, th );
                 }
             }
             if ( terra_amd_last_error && *terra_amd_last_error() ) { fprintf ( stderr, "terra_headless: %s\n", terra_amd_last_error() ); return 70; }
@@ -792,17 +832,17 @@ int main ( int argc, char** argv ) {
         const size_t t = tile ? tile : ( W > H ? W : H );
         for ( size_t y = 0; y < H; y += t ) for ( size_t x = 0; x < W; x += t ) {
             const size_t tw = W - x < t ? W - x : t, th = H - y < t ? H - y : t;
-            terra_render ( &cam, scene, &fb, x, y, tw, th );
-            if ( aov ) ( void ) terra_amd_render_aov ( &cam, scene, aov, W, H, x, y, tw, th );
+            render_rect ( &cam, scene, &fb, x, y, tw, th );
+            if ( aov ) render_aov_rect ( &cam, scene, aov, W, H, x, y, tw, th );
         }
         ( void ) terra_amd_accumulate_moments ( scene, &fb, mom, 0, 0, W, H );
     }
     else if ( gpus > 0 ) ( void ) terra_amd_render_multi ( &cam, scene, &fb, 0, 0, W, H, tile );      /* (tile = the shard's tile size here; 0 = 64) */
-    else if ( tile == 0 ) { terra_render ( &cam, scene, &fb, 0, 0, W, H ); if ( aov ) ( void ) terra_amd_render_aov ( &cam, scene, aov, W, H, 0, 0, W, H ); }
+    else if ( tile == 0 ) { render_rect ( &cam, scene, &fb, 0, 0, W, H ); if ( aov ) render_aov_rect ( &cam, scene, aov, W, H, 0, 0, W, H ); }
     else for ( size_t y = 0; y < H; y += tile ) for ( size_t x = 0; x < W; x += tile ) {
         const size_t tw = W - x < tile ? W - x : tile, th = H - y < tile ? H - y : tile;
-        terra_render ( &cam, scene, &fb, x, y, tw, th );
-        if ( aov ) ( void ) terra_amd_render_aov ( &cam, scene, aov, W, H, x, y, tw, th );
+        render_rect ( &cam, scene, &fb, x, y, tw, th );
+        if ( aov ) render_aov_rect ( &cam, scene, aov, W, H, x, y, tw, th );
     }
     if ( terra_amd_last_error && *terra_amd_last_error() ) { fprintf ( stderr, "terra_headless: %s\n", terra_amd_last_error() ); return 70; }
     if ( aov_prefix ) {

@@ -696,6 +696,69 @@ int terra_amd_render_aov_rays_device ( HTerraScene scene, const void* d_rays, vo
 int terra_amd_render_aov_rays ( HTerraScene scene, const TerraAmdRay* rays, TerraAmdAovResult* aov, size_t fb_width, size_t fb_height,
                                 size_t x, size_t y, size_t width, size_t height );
 
+/* ---- Lens rendering: terra_render() through a camera model -- thin-lens depth of field, orthographic, equirectangular, fisheye --------------------------------
+   The fourth door: a render launch whose primary ray is generated per SAMPLE, in the kernel, from the camera, a TerraAmdLens and the pixel's stream A -- so an
+   anti-aliased panorama or a depth-of-field frame is one call, like a camera frame, instead of one ray buffer and one launch per batch through the ray door. The
+   reference has no such camera: this is the library's own definition (like GGX, glass and environment sampling), off unless called; terra_render() is untouched.
+   The ray of a sample.  All arithmetic is binary32 in exactly the order written, no fused multiply-add. (sx, sy) is the sample's film position and (fx, fy) its
+     perspective slope exactly as the camera call makes them from the pixel, the jitter and the draws r1, r2 (sx = 2 ndc_x - 1, sy = 1 - 2 ndc_y, fx = sx * aspect *
+     tan_half_fov, fy = sy * tan_half_fov); normalize is the camera call's; R(v) is its rotation of a camera-space vector v into the world, cam_rot its matrix (row-major:
+     columns are the camera's x, y, z axes); sinf / cosf are the device's (terra_amd_unit_math fn 0 / 1); PI = 0x40490FDB, PI/2 = 0x3FC90FDB, PI/4 = 0x3F490FDB.
+     model 0, perspective.  d = normalize(fx, fy, 1).
+       lens_radius == 0: origin = position, direction = R(d) -- the camera call's sample bit for bit, and NO extra draw.
+       lens_radius > 0:  l1, l2 are drawn from stream A after r1, r2 and after whatever the sampler integration draws. Concentric map to the unit disk: a = 2 l1 - 1,
+         b = 2 l2 - 1; if a == 0 && b == 0 then (u, v) = (0, 0); else if |a| > |b| then r = a, phi = PI/4 * (b / a), else r = b, phi = PI/2 - PI/4 * (a / b);
+         u = r cosf(phi), v = r sinf(phi). Lx = lens_radius * u, Ly = lens_radius * v. t = focus_distance / d.z, F = (d.x t, d.y t, d.z t).
+         direction = R(normalize(F.x - Lx, F.y - Ly, F.z)); origin = position + (cam_rot[0] Lx + cam_rot[1] Ly, cam_rot[3] Lx + cam_rot[4] Ly, cam_rot[6] Lx + cam_rot[7] Ly).
+     model 1, orthographic.  origin = position + the same expression with Lx = (sx * aspect) * (ortho_height * 0.5f), Ly = sy * (ortho_height * 0.5f);
+       direction = R((0, 0, 1)).
+     model 2, equirectangular.  phi = sx * PI, theta = sy * PI/2; direction = R((cosf(theta) sinf(phi), sinf(theta), cosf(theta) cosf(phi))); origin = position.
+       The camera's fov is not used.
+     model 3, fisheye (equidistant).  ux = sx * aspect, uy = sy, rr = sqrtf(ux ux + uy uy), theta = rr * h with h = (fisheye_fov * 0.0174533f) / 2 rounded on the
+       host as the camera's own angle is. rr == 0: direction = R((0, 0, 1)); otherwise R(((sinf(theta) * ux) / rr, (sinf(theta) * uy) / rr, cosf(theta))).
+       origin = position. There is no image-circle mask: pixels beyond rr = 1 continue the mapping; a client masks them if it wants to.
+   Everything else is a render launch.  terra_trace with the 0.001 origin offset; the scene's integrator, bounces and switches; streams keyed as in a camera
+     call; stream B untouched by the lens; the sample split (the AUTOMATIC split is that of a launch without the job order, as in the ray door), job queue, resolve,
+     tonemap, statistics, d_rand_calls, work counters, flat leaf-box test and pair form unchanged. A lens launch never has the job order or the empty skip: both are
+     built from pinhole rays.
+   Traversal.  The commit's. Host and device forms both know the lens, so both decide the camera_limit rule on the host: every axis of |position| + e must be within
+     TerraAmdTraversalInfo::camera_limit, with e = lens_radius (model 0), (ortho_height / 2) * sqrt(aspect^2 + 1) (model 1), 0 otherwise; if not, the call runs the
+     replica traversal and last_call says so. A scene committed for several devices answers on its primary device.
+   AOV form.  terra_amd_render_aov_device() with the same substitution and the same draws: depth sums |hit point - ray origin|; the sample split is the one the lens
+     render call takes.
+   Calls.  They fail like the camera forms -- kTerraAmdErrNotCommitted first, before anything else is looked at and without touching a device -- and with
+     kTerraAmdErrBadArgument, nothing launched, for a NULL camera or lens, a model outside 0..3, a non-finite or negative field, lens_radius > 0 with
+     focus_distance <= 0, lens_radius != 0 for models 1 - 3, ortho_height <= 0 for model 1, fisheye_fov outside (0, 360] for model 3, non-zero reserved. */
+typedef struct {
+    int   model;            /* 0 perspective (pinhole / thin lens), 1 orthographic, 2 equirectangular, 3 fisheye (equidistant) */
+    float lens_radius;      /* model 0: aperture radius, world units; 0 = pinhole. Must be 0 for the other models */
+    float focus_distance;   /* model 0, lens_radius > 0: distance along the camera axis of the plane in focus; > 0 */
+    float ortho_height;     /* model 1: world height of the film window; > 0 (width = height * aspect) */
+    float fisheye_fov;      /* model 3: full angle in degrees across the frame's height; in (0, 360] */
+    int   reserved[3];      /* zero */
+} TerraAmdLens;
+TERRA_ABI_ASSERT ( sizeof ( TerraAmdLens ) == 32 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdLens, lens_radius ) == 4 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdLens, focus_distance ) == 8 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdLens, ortho_height ) == 12 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdLens, fisheye_fov ) == 16 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdLens, reserved ) == 20 );
+/* The other arguments as terra_amd_render_device(). Asynchronous on `stream`. */
+int terra_amd_render_lens_device ( const TerraCamera* camera, const TerraAmdLens* lens, HTerraScene scene, void* d_pixels, void* d_results, size_t fb_width, size_t fb_height,
+                                   size_t x, size_t y, size_t width, size_t height, void* d_rand_calls, void* stream );
+/* The same on a host framebuffer, as terra_render() takes it: the rectangle's running sums are uploaded, the rectangle comes back; synchronous. */
+int terra_amd_render_lens ( const TerraCamera* camera, const TerraAmdLens* lens, HTerraScene scene, const TerraFramebuffer* framebuffer, size_t x, size_t y, size_t width, size_t height );
+/* d_aov as terra_amd_render_aov_device() takes it. Asynchronous on `stream`. */
+int terra_amd_render_aov_lens_device ( const TerraCamera* camera, const TerraAmdLens* lens, HTerraScene scene, void* d_aov, size_t fb_width, size_t fb_height,
+                                       size_t x, size_t y, size_t width, size_t height, void* stream );
+/* The same on a host buffer (frame-indexed); synchronous. */
+int terra_amd_render_aov_lens ( const TerraCamera* camera, const TerraAmdLens* lens, HTerraScene scene, TerraAmdAovResult* aov, size_t fb_width, size_t fb_height,
+                                size_t x, size_t y, size_t width, size_t height );
+/* The device's ray generator on arrays (needs no scene): input i is pixel xy2[i] = (x, y) of an fb_width x fb_height frame with subpixel jitter `jitter` and the
+   draws r4[i] = (r1, r2, l1, l2); out_rays[i] receives the sample's ray with tmax = FLT_MAX and reserved = 0 -- a record the ray door takes as it is. */
+int terra_amd_unit_lens_rays ( const TerraCamera* camera, const TerraAmdLens* lens, size_t fb_width, size_t fb_height, int n, const uint32_t* xy2, float jitter,
+                               const float* r4, TerraAmdRay* out_rays );
+
 /* Tile-sharded form for one-process-per-GPU rendering (the reference shards
    the same way over CPU threads: satellite/src/Renderer.cpp:316-350): the
    rectangle is cut into tile_size x tile_size tiles numbered row-major and this

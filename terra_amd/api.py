@@ -208,6 +208,24 @@ RAY_SOURCE_SIGNATURES = {
     "terra_amd_render_aov_rays": (c_int, [c_void_p, c_void_p, c_void_p] + [c_size_t] * 6),
 }
 
+
+
+class Lens(Structure):
+    """TerraAmdLens (include/terra_amd.h "Lens rendering"): model 0 perspective (pinhole / thin lens), 1 orthographic, 2 equirectangular, 3 fisheye; 32 bytes"""
+    _fields_ = [("model", c_int), ("lens_radius", c_float), ("focus_distance", c_float), ("ortho_height", c_float), ("fisheye_fov", c_float), ("reserved", c_int * 3)]
+
+
+assert C.sizeof(Lens) == 32
+
+# ... and of lens rendering (include/terra_amd.h "Lens rendering")
+LENS_SIGNATURES = {
+    "terra_amd_render_lens_device": (c_int, [POINTER(TerraCamera), POINTER(Lens), c_void_p, c_void_p, c_void_p] + [c_size_t] * 6 + [c_void_p, c_void_p]),
+    "terra_amd_render_lens": (c_int, [POINTER(TerraCamera), POINTER(Lens), c_void_p, POINTER(TerraFramebuffer)] + [c_size_t] * 4),
+    "terra_amd_render_aov_lens_device": (c_int, [POINTER(TerraCamera), POINTER(Lens), c_void_p, c_void_p] + [c_size_t] * 6 + [c_void_p]),
+    "terra_amd_render_aov_lens": (c_int, [POINTER(TerraCamera), POINTER(Lens), c_void_p, c_void_p] + [c_size_t] * 6),
+    "terra_amd_unit_lens_rays": (c_int, [POINTER(TerraCamera), POINTER(Lens), c_size_t, c_size_t, c_int, c_void_p, c_float, c_void_p, c_void_p]),
+}
+
 # entry points of include/Terra.h + include/TerraPresets.h, name -> (restype, argtypes)
 API_SIGNATURES = {
     "scene_create": (c_void_p, []),

@@ -10,6 +10,9 @@
 // Compiled twice (terra_amd/build.py): as it stands, and with TERRA_TU=4 as the RAY-SOURCED unit (TERRA_RAY_SOURCE, dev_types.h; include/terra_amd.h "Ray-sourced
 // rendering"), whose kernel terra_aov_rays_kernel and launcher terra_launch_aov_rays take a ray buffer -- one TerraAmdRay per pixel, addressed like the AOV buffer -- and trace the pixel's
 // ray for every sample: depth sums |hit point - ray origin|, an inactive ray adds its samples and nothing else. The camera unit's code is the same with and without it.
+// With TERRA_TU=8 it is the LENS unit (TERRA_RAY_SOURCE 2; include/terra_amd.h "Lens rendering"): terra_aov_lens_kernel and terra_launch_aov_lens trace, per sample, the
+// ray lens_sample (trace_geometry.h) makes from the camera model, drawing stream A as the lens render kernels do; the unit also holds the generator's unit entry
+// (terra_unit_lens_rays), so that no other unit's code changes.
 #include <hip/hip_runtime.h>
 #include "trace_device.h"
 #include "kernels.h"
@@ -22,7 +25,10 @@ static_assert ( sizeof ( DevAov ) == 48, "DevAov must be 48 bytes" );
 #define TERRA_AOV_FOLD_BYTES ( 2 * 256 * 16 )       // the block's chunk sums: two float4 per lane
 #define TERRA_AOV_MAX_BLOCKS_PER_CU 8
 
-#if TERRA_RAY_SOURCE
+#if TERRA_RAY_SOURCE == 2
+#define TERRA_AOV_KERNEL terra_aov_lens_kernel
+#define TERRA_AOV_RAYS_PARAM , const DevLens lens
+#elif TERRA_RAY_SOURCE == 1
 #define TERRA_AOV_KERNEL terra_aov_rays_kernel
 #define TERRA_AOV_RAYS_PARAM , const float4* rays
 #else
@@ -50,7 +56,31 @@ __global__ __launch_bounds__ ( 256 ) void TERRA_AOV_KERNEL ( DevRenderParams p, 
         const uint32_t px = p.x + lx, py = p.y + ly;
         const size_t pix = inside ? ( size_t ) ( py - p.st_y ) * p.st_pitch + ( px - p.st_x ) : 0;
         float4 s0 = make_float4 ( 0.f, 0.f, 0.f, 0.f ), s1 = make_float4 ( 0.f, 0.f, 0.f, 0.f );
-#if TERRA_RAY_SOURCE
+#if TERRA_RAY_SOURCE == 2
+        if ( inside ) {
+            // the camera form below with the lens launch's ray: r1, r2, the sampler integration's pair, then the lens pair where the launch draws one
+            const int prior = __float_as_int ( aov[3 * pix + 2].x );
+            const uint32_t base = ( uint32_t ) prior + chunk * p.chunk_spp;
+            PixelStreams rs = trng_pixel_streams ( p.frame_seed, ( uint64_t ) py * p.fb_w + px, ( uint64_t ) ( uint32_t ) prior + ( uint64_t ) chunk * p.chunk_spp );
+            for ( uint32_t s = 0; s < p.chunk_spp; ++s ) {
+                const float r1 = trng_a_float ( rs.a ), r2 = trng_a_float ( rs.a );
+                if ( p.sampler_mode ) ( void ) sampler_pair_draw ( p.sampler_mode, p.sampler_strata, ( uint64_t ) base + s, rs.a );
+                float l1 = 0.f, l2 = 0.f;
+                if ( lens_draws ( lens ) ) { l1 = trng_a_float ( rs.a ); l2 = trng_a_float ( rs.a ); }
+                V3 ro, rd;
+                lens_sample ( p, lens, px, py, r1, r2, l1, l2, ro, rd );
+                Surface sf;
+                Counters c = counters_zero();
+                const RaycastResult h = scene_raycast<0, MODE, TERRA_KINDS_ALL> ( T, make_ray ( ro, rd ), sf, c );
+                if ( h.hit ) {
+                    const V3 a = sf.bsdf == kDevBsdfPhong ? sf.attr[1] : sf.attr[0];
+                    s0.x = s0.x + a.x; s0.y = s0.y + a.y; s0.z = s0.z + a.z; s0.w = s0.w + 1.f;
+                    s1.x = s1.x + sf.normal.x; s1.y = s1.y + sf.normal.y; s1.z = s1.z + sf.normal.z;
+                    s1.w = s1.w + length ( ro - h.point );
+                }
+            }
+        }
+#elif TERRA_RAY_SOURCE == 1
         if ( inside ) {
             // every sample of the pixel traces the pixel's ray (no draw decides anything here): one traversal, its hit added once per sample, in sample order
             const float4* rec = rays + 2 * pix;
@@ -109,7 +139,26 @@ __global__ __launch_bounds__ ( 256 ) void TERRA_AOV_KERNEL ( DevRenderParams p, 
     }
 }
 
-#if TERRA_RAY_SOURCE
+#if TERRA_RAY_SOURCE == 2
+// the generator on arrays (terra_amd_unit_lens_rays): one thread per input
+__global__ void k_lens_rays ( DevRenderParams p, DevLens lens, int n, const uint32_t* xy2, const float* r4, float* rays8 ) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if ( i >= n ) return;
+    V3 ro, rd;
+    lens_sample ( p, lens, xy2[2 * i], xy2[2 * i + 1], r4[4 * i], r4[4 * i + 1], r4[4 * i + 2], r4[4 * i + 3], ro, rd );
+    float* q = rays8 + 8 * ( size_t ) i;
+    q[0] = ro.x; q[1] = ro.y; q[2] = ro.z; q[3] = FLT_MAX;
+    q[4] = rd.x; q[5] = rd.y; q[6] = rd.z; q[7] = 0.f;          // (reserved: the all-zero word)
+}
+hipError_t terra_unit_lens_rays ( const DevRenderParams& p, const DevLens& lens, int n, const uint32_t* xy2, const float* r4, float* rays8 ) {
+    if ( n <= 0 ) return hipSuccess;
+    hipLaunchKernelGGL ( k_lens_rays, dim3 ( ( n + 255 ) / 256 ), dim3 ( 256 ), 0, 0, p, lens, n, xy2, r4, rays8 );
+    return hipGetLastError();
+}
+#define TERRA_AOV_RAYS_ARG , lens
+hipError_t terra_launch_aov_lens ( DevRenderParams p, const DevLens& lens, void* aov, hipStream_t stream ) {
+    if ( lens.model < 0 || lens.model > 3 ) return hipErrorInvalidValue;
+#elif TERRA_RAY_SOURCE == 1
 #define TERRA_AOV_RAYS_ARG , reinterpret_cast<const float4*> ( rays )
 hipError_t terra_launch_aov_rays ( DevRenderParams p, const void* rays, void* aov, hipStream_t stream ) {
     if ( !rays ) return hipErrorInvalidValue;

@@ -334,10 +334,24 @@ struct DevRenderParams {
 // addressed like `results` (st_x / st_y / st_pitch: the frame for the device forms, the staged rectangle for the host forms). The pointer follows DevRenderParams' last field in a structure of its own, which only
 // the ray-sourced kernel instances take: no field of DevRenderParams moves and the camera kernels keep their kernel-argument segment to the byte.
 struct DevRayRenderParams : DevRenderParams { const float4* rays; };
-// Ray-sourced kernel instances are units of their own: render_kernels.hip and aov_kernels.hip compiled with TERRA_TU >= 4 (terra_amd/build.py), or with
-// -DTERRA_RAY_SOURCE=1 and no TERRA_TU (tools/kernel_resources.sh).
+// lens launches (include/terra_amd.h "Lens rendering"): the camera model and its constants as fill_lens rounds them on the host; the launch's camera fields
+// (cam_pos, cam_rot, aspect, tan_half_fov, jitter, inv_fb_*) are filled as for a camera launch. The generator: lens_sample, trace_geometry.h.
+struct DevLens {
+    int32_t model;              // 0 perspective (pinhole / thin lens), 1 orthographic, 2 equirectangular, 3 fisheye
+    float   lens_radius;        // model 0: aperture radius; 0 = pinhole (no lens pair is drawn)
+    float   focus_distance;     // model 0, lens_radius > 0
+    float   ortho_half;         // model 1: ortho_height * 0.5f
+    float   fisheye_half;       // model 3: (fisheye_fov * 0.0174533f) / 2
+};
+// ... and their parameters: DevRenderParams followed by the lens, a structure only the lens kernel instances take (as DevRayRenderParams and for its reason)
+struct DevLensRenderParams : DevRenderParams { DevLens lens; };
+// Where a launch's primary rays come from, TERRA_RAY_SOURCE: 0 the pinhole camera's sample, 1 the ray buffer (ray-sourced), 2 a camera model's sample (lens).
+// Ray-sourced and lens kernel instances are units of their own: render_kernels.hip compiled with TERRA_TU 4 - 7 / 8 - 11 and aov_kernels.hip with TERRA_TU 4 / 8
+// (terra_amd/build.py), or with -DTERRA_RAY_SOURCE=1 / 2 and no TERRA_TU (tools/kernel_resources.sh).
 #ifndef TERRA_RAY_SOURCE
-#if defined ( TERRA_TU ) && TERRA_TU >= 4
+#if defined ( TERRA_TU ) && TERRA_TU >= 8
+#define TERRA_RAY_SOURCE 2
+#elif defined ( TERRA_TU ) && TERRA_TU >= 4
 #define TERRA_RAY_SOURCE 1
 #else
 #define TERRA_RAY_SOURCE 0

@@ -19,6 +19,13 @@ hipError_t terra_launch_render_rays_mode0 ( const DevRayRenderParams& p, size_t 
 hipError_t terra_launch_render_rays_mode1 ( const DevRayRenderParams& p, size_t lds, hipStream_t stream );
 hipError_t terra_launch_render_rays_mode2 ( const DevRayRenderParams& p, size_t lds, hipStream_t stream );
 hipError_t terra_launch_render_rays_mode3 ( const DevRayRenderParams& p, size_t lds, hipStream_t stream );
+// lens launches (include/terra_amd.h "Lens rendering"): terra_launch_render with every primary ray made by lens_sample (trace_geometry.h) from the launch's camera
+// fields and `lens`; p without job order and empty skip, as for a ray-sourced launch. The lens kernel instances are units of their own (render_kernels.hip TERRA_TU 8 - 11)
+hipError_t terra_launch_render_lens ( const DevRenderParams& p, const DevLens& lens, hipStream_t stream );
+hipError_t terra_launch_render_lens_mode0 ( const DevLensRenderParams& p, size_t lds, hipStream_t stream );
+hipError_t terra_launch_render_lens_mode1 ( const DevLensRenderParams& p, size_t lds, hipStream_t stream );
+hipError_t terra_launch_render_lens_mode2 ( const DevLensRenderParams& p, size_t lds, hipStream_t stream );
+hipError_t terra_launch_render_lens_mode3 ( const DevLensRenderParams& p, size_t lds, hipStream_t stream );
 hipError_t terra_launch_resolve ( const DevRenderParams& p, hipStream_t stream );   // second kernel of a split render (p.split > 1)
 hipError_t terra_launch_tiles ( bool pack, float* pixels, void* results, uint32_t fb_w, uint32_t x, uint32_t y, uint32_t w, uint32_t h,
                                 uint32_t tile, uint32_t rank, uint32_t world, float* packed, hipStream_t stream );
@@ -29,6 +36,9 @@ hipError_t terra_launch_aov ( DevRenderParams p, void* aov, hipStream_t stream )
 // ... with the rays of a ray-sourced launch (as terra_launch_render_rays takes them) in place of the camera's: depth sums |hit point - ray origin|, an inactive ray
 // adds its samples and nothing else (aov_kernels.hip compiled as a unit of its own, TERRA_TU 4)
 hipError_t terra_launch_aov_rays ( DevRenderParams p, const void* rays, void* aov, hipStream_t stream );
+// ... with the samples of a lens launch (as terra_launch_render_lens makes them, the lens pair drawn where that draws it): depth sums |hit point - ray origin|
+// (aov_kernels.hip compiled as a unit of its own, TERRA_TU 8)
+hipError_t terra_launch_aov_lens ( DevRenderParams p, const DevLens& lens, void* aov, hipStream_t stream );
 
 // the a-trous denoiser and its variance-guided form (denoise_kernels.hip): results / aov / moments (TerraAmdMoments) / radiance / pixels indexed like a frame of fb_w
 // pixels per row; only the rectangle is read or written; radiance or pixels may be nullptr
@@ -81,6 +91,8 @@ hipError_t terra_unit_trace ( const DevScene& sc, int integrator, uint32_t bounc
                               const uint64_t* stateB, const uint64_t* incB, float* radiance, uint32_t* rand_calls );
 hipError_t terra_unit_bsdf ( int kind, int n, float* surfaces47, const float* e3, const float* wo3, float* wi3, float* pdf, float* f3 );
 hipError_t terra_unit_camera ( const DevRenderParams& p, int n, const uint32_t* xy2, const float* r2, float* dirs3 );
+// lens_sample on arrays: r4[n][4] = (r1, r2, l1, l2); rays8[n][8] = TerraAmdRay records (tmax FLT_MAX, reserved 0). p: the camera fields, jitter and frame size
+hipError_t terra_unit_lens_rays ( const DevRenderParams& p, const DevLens& lens, int n, const uint32_t* xy2, const float* r4, float* rays8 );
 hipError_t terra_unit_tonemap ( int op, float gamma, int n, float* colors3 );
 hipError_t terra_unit_math ( int fn, int n, const float* x, const float* y, float* out );
 // exact_div.h against "/" (unit_kernels.hip "exact_div.h against the plain"): a == nullptr = the generated set; helper_bits / plain_bits only in the explicit form

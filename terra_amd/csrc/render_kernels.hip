@@ -30,16 +30,20 @@
 //   TERRA_TU 1 / 2 / 3  the kernels of template MODE 1 (LDS-resident scenes) / 2 (fast tree) / 3 (fast tree + reachability replay) and their launcher
 //   TERRA_TU 4 / 5 / 6 / 7  the RAY-SOURCED kernels of template MODE 0 / 1 / 2 / 3 and their launcher, nothing else (TERRA_RAY_SOURCE, dev_types.h: a primary ray
 //               is the pixel's record of DevRayRenderParams::rays instead of a camera sample). Units of their own, so that units 0 - 3 compile as before
-//   undefined   all of it in one unit (tools/kernel_resources.sh, tools/isa_cost.py); with -DTERRA_RAY_SOURCE=1: every ray-sourced kernel in one unit
+//   TERRA_TU 8 / 9 / 10 / 11  the LENS kernels of template MODE 0 / 1 / 2 / 3 and their launcher, nothing else (TERRA_RAY_SOURCE 2: a primary ray is the sample of
+//               DevLensRenderParams::lens, a camera model -- lens_sample, trace_geometry.h)
+//   undefined   all of it in one unit (tools/kernel_resources.sh, tools/isa_cost.py); with -DTERRA_RAY_SOURCE=1 / 2: every ray-sourced / lens kernel in one unit
 #ifdef TERRA_TU
 #define TERRA_TU_HAS(k) ( TERRA_TU == ( k ) )
-#define TERRA_TU_MODE(k) ( TERRA_TU == ( k ) || TERRA_TU == ( k ) + 4 )      // the unit holds the kernels of template MODE k
+#define TERRA_TU_MODE(k) ( TERRA_TU == ( k ) || TERRA_TU == ( k ) + 4 || TERRA_TU == ( k ) + 8 )      // the unit holds the kernels of template MODE k
 #else
 #define TERRA_TU_HAS(k) ( !TERRA_RAY_SOURCE )
 #define TERRA_TU_MODE(k) 1
 #endif
 // what a render kernel instance of this unit takes: where its primary rays come from
-#if TERRA_RAY_SOURCE
+#if TERRA_RAY_SOURCE == 2
+typedef DevLensRenderParams RenderKernelParams;
+#elif TERRA_RAY_SOURCE == 1
 typedef DevRayRenderParams RenderKernelParams;
 #else
 typedef DevRenderParams RenderKernelParams;
@@ -508,7 +512,7 @@ TD void job_next ( const DevRenderParams& p, float* aux, Jobs& j, PixelStreams& 
 struct PrimaryRay { V3 o, d; };
 TD PrimaryRay ray_record ( const RenderKernelParams& p, uint32_t px, uint32_t py ) {
     PrimaryRay r; r.o = v3 ( 0, 0, 0 ); r.d = v3 ( 0, 0, 1 );
-#if TERRA_RAY_SOURCE
+#if TERRA_RAY_SOURCE == 1
     const float4* rec = p.rays + 2 * ( ( size_t ) ( py - p.st_y ) * p.st_pitch + ( px - p.st_x ) );          // addressed like p.results
     const float4 q0 = rec[0], q1 = rec[1];          // {origin, tmax} {direction, reserved}: a primary ray has no limit, tmax and reserved are not looked at
     r.o = v3 ( q0.x, q0.y, q0.z ); r.d = v3 ( q1.x, q1.y, q1.z );
@@ -520,17 +524,25 @@ TD bool ray_record_inactive ( const PrimaryRay& r ) {
     const bool finite = fabsf ( r.o.x ) < INFINITY && fabsf ( r.o.y ) < INFINITY && fabsf ( r.o.z ) < INFINITY && fabsf ( r.d.x ) < INFINITY && fabsf ( r.d.y ) < INFINITY && fabsf ( r.d.z ) < INFINITY;      // (false for a NaN too)
     return !finite || ( r.d.x == 0.f && r.d.y == 0.f && r.d.z == 0.f );
 }
+// Lens launches: the sample of the launch's camera model (lens_sample), made AFTER the sampler integration's draws -- TERRA_LENS_RAY, which follows them in every loop and
+// is empty in the other units -- because a thin lens draws its pair from stream A there; the other models and the pinhole draw nothing (lens_draws is a launch constant).
 // (macros inside the kernel, not functions: the camera units then compile the very statements they always had -- tools/isa_same.sh against the parent)
-#if TERRA_RAY_SOURCE
+#if TERRA_RAY_SOURCE == 2
+#define TERRA_PRIMARY_RAY( ro, rd, r1, r2 )
+#define TERRA_LENS_RAY( ro, rd, r1, r2 ) do { float l1_ = 0.f, l2_ = 0.f; if ( lens_draws ( p.lens ) ) { l1_ = trng_a_float ( rs.a ); l2_ = trng_a_float ( rs.a ); } lens_sample ( p, p.lens, jb.px, jb.py, r1, r2, l1_, l2_, ro, rd ); } while ( 0 )
+#define TERRA_JOB_NEXT() job_next<COUNT, MODE == 1> ( p, acc_lds, jb, rs, c, job_total )
+#elif TERRA_RAY_SOURCE == 1
 #define TERRA_PRIMARY_RAY( ro, rd, r1, r2 ) do { const PrimaryRay pr_ = TERRA_RAY_HOLD ? held : ray_record ( p, jb.px, jb.py ); ro = pr_.o; rd = pr_.d; } while ( 0 )
+#define TERRA_LENS_RAY( ro, rd, r1, r2 )
 #define TERRA_JOB_NEXT() job_take<COUNT, MODE == 1> ( p, acc_lds, jb, rs, c, job_total, held )
 #else
+#define TERRA_LENS_RAY( ro, rd, r1, r2 )
 #define TERRA_PRIMARY_RAY( ro, rd, r1, r2 ) ro = cam_pos; rd = camera_sample ( p, jb.px, jb.py, r1, r2 )
 #define TERRA_JOB_NEXT() job_next<COUNT, MODE == 1> ( p, acc_lds, jb, rs, c, job_total )
 #endif
 // job_next for the kernel's loops. Ray-sourced launches look at the new job's ray here, once per job: an inactive one ends the job where it starts -- its sum stays
 // the +0 job_next set, it draws nothing, and the resolve kernel adds that +0 and the call's samples to the pixel like any other job's sum.
-#if TERRA_RAY_SOURCE
+#if TERRA_RAY_SOURCE == 1
 template <int COUNT, bool TABLE>
 TD void job_take ( const RenderKernelParams& p, float* aux, Jobs& j, PixelStreams& rs, const Counters& c, uint32_t total, PrimaryRay& held ) {
     job_next<COUNT, TABLE> ( p, aux, j, rs, c, total );
@@ -564,7 +576,7 @@ __global__ __launch_bounds__ ( 256, terra_waves ( INTEGRATOR, KINDS, MODE ) ) vo
     Ray ray = make_ray ( v3 ( 0, 0, 0 ), v3 ( 0, 0, 1 ) );
     uint32_t bounce = 0;
     const V3 cam_pos = v3p ( p.cam_pos );
-#if TERRA_RAY_SOURCE
+#if TERRA_RAY_SOURCE == 1
     PrimaryRay held; held.o = v3 ( 0, 0, 0 ); held.d = v3 ( 0, 0, 1 );      // the job's ray (TERRA_RAY_HOLD only)
 #endif
 
@@ -622,6 +634,7 @@ __global__ __launch_bounds__ ( 256, terra_waves ( INTEGRATOR, KINDS, MODE ) ) vo
                         float r1 = trng_a_float ( rs.a ), r2 = trng_a_float ( rs.a );
                         TERRA_PRIMARY_RAY ( ro, rd, r1, r2 );
                         if constexpr ( ( KINDS & TERRA_KIND_SAMPLER ) != 0 ) sp = sampler_pair_draw ( p.sampler_mode, p.sampler_strata, ( uint64_t ) jb.base + jb.s, rs.a );
+                        TERRA_LENS_RAY ( ro, rd, r1, r2 );
                         Lo = v3 ( 0, 0, 0 ); throughput = v3 ( 1, 1, 1 ); bounce = 0; ++jb.s; job = 0; start = true;
                     }
                 }
@@ -674,6 +687,7 @@ __global__ __launch_bounds__ ( 256, terra_waves ( INTEGRATOR, KINDS, MODE ) ) vo
                         float r1 = trng_a_float ( rs.a ), r2 = trng_a_float ( rs.a );
                         TERRA_PRIMARY_RAY ( ro, rd, r1, r2 );
                         if constexpr ( ( KINDS & TERRA_KIND_SAMPLER ) != 0 ) sp = sampler_pair_draw ( p.sampler_mode, p.sampler_strata, ( uint64_t ) jb.base + jb.s, rs.a );
+                        TERRA_LENS_RAY ( ro, rd, r1, r2 );
                         Lo = v3 ( 0, 0, 0 ); throughput = v3 ( 1, 1, 1 ); bounce = 0; ++jb.s; start = true;
                     }
                 }
@@ -718,6 +732,7 @@ __global__ __launch_bounds__ ( 256, terra_waves ( INTEGRATOR, KINDS, MODE ) ) vo
                         float r1 = trng_a_float ( rs.a ), r2 = trng_a_float ( rs.a );
                         TERRA_PRIMARY_RAY ( ro, rd, r1, r2 );
                         if constexpr ( ( KINDS & TERRA_KIND_SAMPLER ) != 0 ) sp = sampler_pair_draw ( p.sampler_mode, p.sampler_strata, ( uint64_t ) jb.base + jb.s, rs.a );
+                        TERRA_LENS_RAY ( ro, rd, r1, r2 );
                         Lo = v3 ( 0, 0, 0 ); throughput = v3 ( 1, 1, 1 ); bounce = 0; ++jb.s; next = true;
                     }
                 }
@@ -755,6 +770,7 @@ __global__ __launch_bounds__ ( 256, terra_waves ( INTEGRATOR, KINDS, MODE ) ) vo
                 float r1 = trng_a_float ( rs.a ), r2 = trng_a_float ( rs.a );
                 TERRA_PRIMARY_RAY ( ro, rd, r1, r2 );
                 if constexpr ( ( KINDS & TERRA_KIND_SAMPLER ) != 0 ) sp = sampler_pair_draw ( p.sampler_mode, p.sampler_strata, ( uint64_t ) jb.base + jb.s, rs.a );
+                TERRA_LENS_RAY ( ro, rd, r1, r2 );
                 lo_reset(); throughput = v3 ( 1, 1, 1 ); bounce = 0; alive = true; ++jb.s;
             }
         }
@@ -893,7 +909,21 @@ static hipError_t launch_integrator ( const RenderKernelParams& p, size_t lds, h
     }
 }
 // one launcher per template MODE and ray source, each in its own translation unit (see the top of the file)
-#if TERRA_RAY_SOURCE
+#if TERRA_RAY_SOURCE == 2
+#if TERRA_TU_MODE ( 0 )
+hipError_t terra_launch_render_lens_mode0 ( const DevLensRenderParams& p, size_t lds, hipStream_t stream ) { return launch_integrator<0> ( p, lds, stream ); }
+#endif
+#if TERRA_TU_MODE ( 1 )
+hipError_t terra_launch_render_lens_mode1 ( const DevLensRenderParams& p, size_t lds, hipStream_t stream ) { return launch_integrator<1> ( p, lds, stream ); }
+#endif
+#if TERRA_TU_MODE ( 2 )
+hipError_t terra_launch_render_lens_mode2 ( const DevLensRenderParams& p, size_t lds, hipStream_t stream ) { return launch_integrator<2> ( p, lds, stream ); }
+#endif
+#if TERRA_TU_MODE ( 3 )
+hipError_t terra_launch_render_lens_mode3 ( const DevLensRenderParams& p, size_t lds, hipStream_t stream ) { return launch_integrator<3> ( p, lds, stream ); }
+#endif
+#endif
+#if TERRA_RAY_SOURCE == 1
 #if TERRA_TU_MODE ( 0 )
 hipError_t terra_launch_render_rays_mode0 ( const DevRayRenderParams& p, size_t lds, hipStream_t stream ) { return launch_integrator<0> ( p, lds, stream ); }
 #endif
@@ -942,6 +972,18 @@ hipError_t terra_launch_render_rays ( const DevRenderParams& p, const void* rays
     if ( p.lds_mode == 1 ) return terra_launch_render_rays_mode1 ( rp, lds, stream );
     if ( p.lds_mode == 2 ) return p.scene.reach ? terra_launch_render_rays_mode3 ( rp, lds, stream ) : terra_launch_render_rays_mode2 ( rp, lds, stream );
     return terra_launch_render_rays_mode0 ( rp, lds, stream );
+}
+// ... and with its primary rays made from `lens` (DevLensRenderParams): the lens instances of the same kernels, under the same rule -- the job order and the empty
+// skip reason about pinhole rays
+hipError_t terra_launch_render_lens ( const DevRenderParams& p, const DevLens& lens, hipStream_t stream ) {
+    if ( p.job_blocks == 0 ) return hipSuccess;
+    if ( !p.partials || p.block_order || p.job_live || lens.model < 0 || lens.model > 3 ) return hipErrorInvalidValue;
+    DevLensRenderParams lp;
+    static_cast<DevRenderParams&> ( lp ) = p; lp.lens = lens;
+    size_t lds = terra_lds_bytes ( p );
+    if ( p.lds_mode == 1 ) return terra_launch_render_lens_mode1 ( lp, lds, stream );
+    if ( p.lds_mode == 2 ) return p.scene.reach ? terra_launch_render_lens_mode3 ( lp, lds, stream ) : terra_launch_render_lens_mode2 ( lp, lds, stream );
+    return terra_launch_render_lens_mode0 ( lp, lds, stream );
 }
 
 // First kernel of every render: the random streams of every job of the launch (what job_next would otherwise compute when a lane takes the job). One thread per job,

@@ -1548,7 +1548,8 @@ static void apply_stack_hooks ( const Scene* s, DevRenderParams& p ) {
 }
 // r: the copy of the scene the launch reads (the launch runs on r.device)
 // ray_origins_ok: non-null = a ray-sourced launch (no camera: cam is not looked at and the camera fields stay zero); what it points to stands in for "the camera lies
-// inside the range the commit's traversal shortcut is proven for" -- the host forms look at their rays' origins, the device forms cannot and pass true
+// inside the range the commit's traversal shortcut is proven for" -- the host forms look at their rays' origins, the device forms cannot and pass true.
+// A lens launch (fill_lens_params) passes both: its camera fills the camera fields, and the range decision is the lens rule's (|position| + the model's extent)
 static int fill_params ( Scene* s, const Scene::Replica& r, const TerraCamera* cam, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t h,
                          size_t tile, int rank, int world, DevRenderParams& p, const bool* ray_origins_ok = nullptr ) {
     if ( int rc = scene_check ( s ) ) return rc;
@@ -1557,7 +1558,7 @@ static int fill_params ( Scene* s, const Scene::Replica& r, const TerraCamera* c
     if ( world < 1 || rank < 0 || rank >= world ) return fail ( kTerraAmdErrBadArgument, "bad shard %d/%d", rank, world );
     memset ( &p, 0, sizeof p );
     p.scene = r.dev;
-    if ( !ray_origins_ok ) fill_camera ( cam, fb_w, fb_h, p );
+    if ( cam ) fill_camera ( cam, fb_w, fb_h, p );
     p.jitter = s->opts.subpixel_jitter; p.exposure = s->opts.manual_exposure; p.gamma = s->opts.gamma;
     p.fb_w = ( uint32_t ) fb_w; p.fb_h = ( uint32_t ) fb_h;
     p.x = ( uint32_t ) x; p.y = ( uint32_t ) y; p.w = ( uint32_t ) w; p.h = ( uint32_t ) h;
@@ -1662,11 +1663,13 @@ static uint32_t launch_split ( const Scene* s, DevRenderParams& p, uint32_t bloc
 }
 // d_rays: non-null = a ray-sourced launch (include/terra_amd.h "Ray-sourced rendering"): the same plan, scratch, queue and resolve, the primary rays read from d_rays
 // (addressed like p.results); no job order and no empty skip, which are made from camera rays
-static int launch_render ( Scene* s, DevRenderParams& p, int device, hipStream_t stream, ThreadSlot* slot = nullptr, const void* d_rays = nullptr ) {      // device: the (current) device of the launch
+// lens: non-null = a lens launch (include/terra_amd.h "Lens rendering"): likewise, the primary rays made from the camera fields of p and *lens
+static int launch_render ( Scene* s, DevRenderParams& p, int device, hipStream_t stream, ThreadSlot* slot = nullptr, const void* d_rays = nullptr, const DevLens* lens = nullptr ) {      // device: the (current) device of the launch
     const uint32_t blocks = terra_render_blocks ( p );
     if ( blocks == 0 ) return 0;
     if ( p.count_level != 0 || p.rand_calls ) { p.leaf_boxes = nullptr; p.n_leaf_boxes = 0; p.leaf_pairs = 0; }      // the work counters keep their meaning: counting launches walk the tree and test one triangle per trip
-    const uint32_t split = launch_split ( s, p, blocks, d_rays != nullptr );
+    const bool ray_source = d_rays != nullptr || lens != nullptr;
+    const uint32_t split = launch_split ( s, p, blocks, ray_source );
     static thread_local uint64_t pool_kept = 0;          // (bit d: done for device d)
     if ( device < 64 && ! ( pool_kept >> device & 1ull ) ) {        // keep freed scratch cached in the device's default pool instead of returning it to the OS at every sync
         hipMemPool_t pool;
@@ -1680,7 +1683,7 @@ static int launch_render ( Scene* s, DevRenderParams& p, int device, hipStream_t
     const size_t stream_bytes = terra_job_streams_bytes ( p );
     if ( stream_bytes && ( p.fb_w > 65535u || p.fb_h > 65535u ) ) return fail ( kTerraAmdErrBadArgument, "framebuffer of %u x %u: at most 65,535 pixels per side (the job table packs a pixel into 32 bits)", p.fb_w, p.fb_h );
     const size_t spill_bytes = terra_fast_spill_bytes ( p );                 // fast-tree launches: the part of the lanes' traversal stacks that does not live in LDS
-    const size_t order_bytes = s->job_order ? terra_block_order_bytes ( p, s->job_order == 2, d_rays != nullptr ) : 0;           // LDS-resident launches: the order the pixel blocks are handed out in (render_kernels.hip "job order")
+    const size_t order_bytes = s->job_order ? terra_block_order_bytes ( p, s->job_order == 2, ray_source ) : 0;           // LDS-resident launches: the order the pixel blocks are handed out in (render_kernels.hip "job order")
     const size_t scratch_bytes = header + partial_bytes + stream_bytes + spill_bytes + order_bytes;
     // (a thread's slot keeps scratch for tile-sized calls only: a full-frame call's gigabytes come from, and go back to, the device's pool)
     // a launch's scratch is bounded: 48 bytes per (pixel, lane-per-pixel) job on LDS-resident scenes -- a 4K frame at 64 lanes per pixel asks for 25 GB per concurrent stream.
@@ -1724,7 +1727,7 @@ static int launch_render ( Scene* s, DevRenderParams& p, int device, hipStream_t
     }
     if ( e == hipSuccess && order_cls ) e = terra_launch_block_order ( p, order_cls, stream );
     if ( e == hipSuccess ) e = terra_launch_job_streams ( p, stream );
-    if ( e == hipSuccess ) e = d_rays ? terra_launch_render_rays ( p, d_rays, stream ) : terra_launch_render ( p, stream );
+    if ( e == hipSuccess ) e = lens ? terra_launch_render_lens ( p, *lens, stream ) : d_rays ? terra_launch_render_rays ( p, d_rays, stream ) : terra_launch_render ( p, stream );
     if ( e == hipSuccess ) e = terra_launch_resolve ( p, stream );
     if ( pooled ) ( void ) hipFreeAsync ( scratch, stream );
     else if ( e != hipSuccess ) ( void ) hipMemsetAsync ( scratch, 0, header, stream );       // (a launch that failed half way must not leave a used queue word behind)
@@ -1879,15 +1882,15 @@ struct FrameCopy {
 static_assert ( sizeof ( TerraAmdAovResult ) == 48, "TerraAmdAovResult must be 48 bytes" );
 // p: the launch fill_params made for the render call this AOV call mirrors; the split is the one that call takes (launch_split), and the samples the AOV buffer
 // already holds key the streams as the framebuffer's do. Runs on the current device (the scene's primary one).
-// d_rays: non-null = the ray-sourced form, mirroring a ray-sourced render call (addressed like d_aov).
-static int launch_aov ( Scene* s, DevRenderParams& p, void* d_aov, hipStream_t stream, const void* d_rays = nullptr ) {
+// d_rays: non-null = the ray-sourced form, mirroring a ray-sourced render call (addressed like d_aov); lens: non-null = the lens form, mirroring a lens render call.
+static int launch_aov ( Scene* s, DevRenderParams& p, void* d_aov, hipStream_t stream, const void* d_rays = nullptr, const DevLens* lens = nullptr ) {
     const uint32_t blocks = terra_render_blocks ( p );
     if ( blocks == 0 ) return 0;
-    const uint32_t split = launch_split ( s, p, blocks, d_rays != nullptr );
+    const uint32_t split = launch_split ( s, p, blocks, d_rays != nullptr || lens != nullptr );
     p.split = split; p.split_log2 = 0; while ( ( 1u << p.split_log2 ) < split ) ++p.split_log2;
     p.chunk_spp = p.spp / split; p.job_blocks = blocks * split; p.job_queue = nullptr; p.job_streams = nullptr; p.block_order = nullptr; p.partials = nullptr;
     p.pixels = nullptr; p.results = nullptr; p.rand_calls = nullptr; p.counters = nullptr; p.count_level = 0;
-    const hipError_t e = d_rays ? terra_launch_aov_rays ( p, d_rays, d_aov, stream ) : terra_launch_aov ( p, d_aov, stream );
+    const hipError_t e = lens ? terra_launch_aov_lens ( p, *lens, d_aov, stream ) : d_rays ? terra_launch_aov_rays ( p, d_rays, d_aov, stream ) : terra_launch_aov ( p, d_aov, stream );
     if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "AOV launch: %s", hipGetErrorString ( e ) );
     return 0;
 }
@@ -2418,6 +2421,107 @@ extern "C" int terra_amd_render_rays ( HTerraScene h, const TerraAmdRay* rays, c
     return 0;
 }
 
+// ---- lens rendering: the render call through a camera model (include/terra_amd.h "Lens rendering") -----------------------------------------------
+static_assert ( sizeof ( TerraAmdLens ) == 32, "TerraAmdLens must be 32 bytes" );
+// the one argument check of the five entry points; fills the launch constants as the kernels take them (DevLens)
+static int fill_lens ( const TerraCamera* cam, const TerraAmdLens* lens, const char* what, DevLens& L ) {
+    if ( !cam || !lens ) return fail ( kTerraAmdErrBadArgument, "%s: null camera or lens", what );
+    if ( lens->model < 0 || lens->model > 3 ) return fail ( kTerraAmdErrBadArgument, "%s: camera model %d: 0 perspective, 1 orthographic, 2 equirectangular, 3 fisheye", what, lens->model );
+    const float f[4] = { lens->lens_radius, lens->focus_distance, lens->ortho_height, lens->fisheye_fov };
+    for ( float v : f ) if ( !std::isfinite ( v ) || v < 0.f ) return fail ( kTerraAmdErrBadArgument, "%s: a lens field is negative or not finite", what );
+    if ( lens->reserved[0] || lens->reserved[1] || lens->reserved[2] ) return fail ( kTerraAmdErrBadArgument, "%s: TerraAmdLens::reserved must be zero", what );
+    if ( lens->model != 0 && lens->lens_radius != 0.f ) return fail ( kTerraAmdErrBadArgument, "%s: lens_radius %g with camera model %d: only the perspective model has a lens", what, ( double ) lens->lens_radius, lens->model );
+    if ( lens->lens_radius > 0.f && ! ( lens->focus_distance > 0.f ) ) return fail ( kTerraAmdErrBadArgument, "%s: a lens of radius %g needs a focus_distance > 0", what, ( double ) lens->lens_radius );
+    if ( lens->model == 1 && ! ( lens->ortho_height > 0.f ) ) return fail ( kTerraAmdErrBadArgument, "%s: the orthographic model needs an ortho_height > 0", what );
+    if ( lens->model == 3 && ! ( lens->fisheye_fov > 0.f && lens->fisheye_fov <= 360.f ) ) return fail ( kTerraAmdErrBadArgument, "%s: fisheye_fov %g: in (0, 360]", what, ( double ) lens->fisheye_fov );
+    L.model = lens->model; L.lens_radius = lens->lens_radius; L.focus_distance = lens->focus_distance;
+    L.ortho_half = lens->ortho_height * 0.5f;
+    L.fisheye_half = ( lens->fisheye_fov * 0.0174533f ) / 2;          // (rounded as fill_camera rounds the camera's angle)
+    return 0;
+}
+// fill_params of a lens launch: "not committed" first, then the arguments, then the launch -- with the camera_limit rule decided here for host and device forms alike:
+// every axis of |position| + e within the limit, e = the furthest a ray origin lies from the position (the lens radius; the film window's half diagonal)
+static int fill_lens_params ( Scene* s, const Scene::Replica& r, const TerraCamera* cam, const TerraAmdLens* lens, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t h,
+                              const char* what, DevRenderParams& p, DevLens& L ) {
+    if ( !s->committed ) return scene_check ( s );
+    if ( int rc = fill_lens ( cam, lens, what, L ) ) return rc;          // (before fill_params asks for the device replica: a bad lens is refused on a host without a GPU too)
+    double e = 0.0;
+    if ( L.model == 0 ) e = L.lens_radius;
+    else if ( L.model == 1 && fb_h ) { const double aspect = ( double ) ( ( float ) fb_w / ( float ) fb_h ); e = ( ( double ) lens->ortho_height / 2 ) * sqrt ( aspect * aspect + 1.0 ); }
+    const double limit = shortcut_limit ( s->tree );
+    const bool origins_ok = fabs ( ( double ) cam->position.x ) + e <= limit && fabs ( ( double ) cam->position.y ) + e <= limit && fabs ( ( double ) cam->position.z ) + e <= limit;
+    return fill_params ( s, r, cam, fb_w, fb_h, x, y, w, h, 64, 0, 1, p, &origins_ok );
+}
+extern "C" int terra_amd_render_lens_device ( const TerraCamera* cam, const TerraAmdLens* lens, HTerraScene h, void* d_pixels, void* d_results, size_t fb_w, size_t fb_h,
+                                              size_t x, size_t y, size_t w, size_t hgt, void* d_rand_calls, void* stream ) {
+    Scene* s = S ( h );
+    const Scene::Replica& r = primary ( s );
+    DevRenderParams p; DevLens L;
+    if ( int rc = fill_lens_params ( s, r, cam, lens, fb_w, fb_h, x, y, w, hgt, "terra_amd_render_lens_device", p, L ) ) return rc;
+    if ( !d_pixels || !d_results ) return fail ( kTerraAmdErrBadArgument, "null framebuffer pointer" );
+    p.pixels = ( float* ) d_pixels; p.results = d_results; p.rand_calls = ( uint32_t* ) d_rand_calls;
+    if ( d_rand_calls ) p.count_level = 2;
+    HIP_TRY ( hipSetDevice ( r.device ), kTerraAmdErrNoDevice );
+    if ( int lrc = launch_render ( s, p, r.device, ( hipStream_t ) stream, nullptr, nullptr, &L ) ) return lrc;
+    account_launch ( s, p );
+    return 0;
+}
+// the host form: render_host's staging of the rectangle, on the primary device
+extern "C" int terra_amd_render_lens ( const TerraCamera* cam, const TerraAmdLens* lens, HTerraScene h, const TerraFramebuffer* fb, size_t x, size_t y, size_t w, size_t hgt ) {
+    Scene* s = S ( h );
+    if ( !s->committed ) return scene_check ( s );
+    if ( !fb || !fb->pixels || !fb->results ) return fail ( kTerraAmdErrBadArgument, "null framebuffer" );
+    const Scene::Replica* r = &primary ( s );
+    DevRenderParams p; DevLens L;
+    if ( int rc = fill_lens_params ( s, *r, cam, lens, fb->width, fb->height, x, y, w, hgt, "terra_amd_render_lens", p, L ) ) return rc;
+    if ( int rc = slot_prepare ( r->device, w * hgt ) ) return rc;
+    ThreadSlot& t = t_slot;
+    p.st_x = ( uint32_t ) x; p.st_y = ( uint32_t ) y; p.st_pitch = ( uint32_t ) w;
+    const size_t rpitch = fb->width * 16, ppitch = fb->width * 12;
+    const char* hres = ( const char* ) fb->results + ( y * fb->width + x ) * 16;
+    char* hpix = ( char* ) fb->pixels + ( y * fb->width + x ) * 12;
+    HIP_TRY ( hipMemcpy2DAsync ( t.d_results, w * 16, hres, rpitch, w * 16, hgt, hipMemcpyHostToDevice, t.stream ), kTerraAmdErrLaunch );
+    p.pixels = ( float* ) t.d_pixels; p.results = t.d_results; p.rand_calls = nullptr;
+    if ( int lrc = launch_render ( s, p, r->device, t.stream, &t, nullptr, &L ) ) return lrc;
+    HIP_TRY ( hipMemcpy2DAsync ( ( void* ) hres, rpitch, t.d_results, w * 16, w * 16, hgt, hipMemcpyDeviceToHost, t.stream ), kTerraAmdErrLaunch );
+    HIP_TRY ( hipMemcpy2DAsync ( hpix, ppitch, t.d_pixels, w * 12, w * 12, hgt, hipMemcpyDeviceToHost, t.stream ), kTerraAmdErrLaunch );
+    HIP_TRY ( hipStreamSynchronize ( t.stream ), kTerraAmdErrLaunch );
+    account_launch ( s, p );
+    return 0;
+}
+// AOV forms: d_aov holds rows of st_pitch pixels whose first is pixel (st_x, st_y) of the frame
+static int render_aov_lens_device ( const TerraCamera* cam, const TerraAmdLens* lens, HTerraScene h, void* d_aov, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t hgt,
+                                    size_t st_x, size_t st_y, size_t st_pitch, void* stream, const char* what ) {
+    Scene* s = S ( h );
+    const Scene::Replica& r = primary ( s );
+    DevRenderParams p; DevLens L;
+    if ( int rc = fill_lens_params ( s, r, cam, lens, fb_w, fb_h, x, y, w, hgt, what, p, L ) ) return rc;
+    if ( !d_aov ) return fail ( kTerraAmdErrBadArgument, "null AOV buffer" );
+    HIP_TRY ( hipSetDevice ( r.device ), kTerraAmdErrNoDevice );
+    p.st_x = ( uint32_t ) st_x; p.st_y = ( uint32_t ) st_y; p.st_pitch = ( uint32_t ) st_pitch;
+    return launch_aov ( s, p, d_aov, ( hipStream_t ) stream, nullptr, &L );
+}
+extern "C" int terra_amd_render_aov_lens_device ( const TerraCamera* cam, const TerraAmdLens* lens, HTerraScene h, void* d_aov, size_t fb_w, size_t fb_h,
+                                                  size_t x, size_t y, size_t w, size_t hgt, void* stream ) {
+    return render_aov_lens_device ( cam, lens, h, d_aov, fb_w, fb_h, x, y, w, hgt, 0, 0, fb_w, stream, "terra_amd_render_aov_lens_device" );
+}
+extern "C" int terra_amd_render_aov_lens ( const TerraCamera* cam, const TerraAmdLens* lens, HTerraScene h, TerraAmdAovResult* aov, size_t fb_w, size_t fb_h,
+                                           size_t x, size_t y, size_t w, size_t hgt ) {
+    Scene* s = S ( h );
+    DevRenderParams p; DevLens L;          // (for the checks alone, before anything is staged: the device form fills its own)
+    if ( int rc = fill_lens_params ( s, primary ( s ), cam, lens, fb_w, fb_h, x, y, w, hgt, "terra_amd_render_aov_lens", p, L ) ) return rc;
+    if ( !aov ) return fail ( kTerraAmdErrBadArgument, "null AOV buffer" );
+    HIP_TRY ( hipSetDevice ( primary ( s ).device ), kTerraAmdErrNoDevice );
+    const FrameRect rect = { fb_w, x, y, w, hgt };
+    FrameCopy c;
+    hipError_t e = c.up_rect ( 0, aov, sizeof ( TerraAmdAovResult ), rect );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "AOV upload: %s", hipGetErrorString ( e ) );
+    if ( int rc = render_aov_lens_device ( cam, lens, h, c.d[0], fb_w, fb_h, x, y, w, hgt, x, y, w, nullptr, "terra_amd_render_aov_lens" ) ) return rc;
+    e = c.down_rect ( 0, aov, sizeof ( TerraAmdAovResult ), rect );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "AOV download: %s", hipGetErrorString ( e ) );
+    return 0;
+}
+
 // terra_render() over the scene's device set from one process: device k renders the tiles t with t % N == k of the rectangle (terra_amd_shard_owner; the same kernels
 // with DevRenderParams::rank / world set) into its own staging frame, packs them, and ONE gather -- RCCL over xGMI, issued from here (multi_gpu.cpp) -- brings every
 // rank's packed tiles to the primary device, which unpacks them into its staging frame and copies the rectangle to the host once. The reference's client shards tiles over
@@ -2635,6 +2739,17 @@ extern "C" int terra_amd_unit_camera ( const TerraCamera* cam, size_t fb_w, size
     p.jitter = jitter; p.fb_w = ( uint32_t ) fb_w; p.fb_h = ( uint32_t ) fb_h;
     Unit u; auto a = u.in ( xy2, 2 * ( size_t ) n ); auto b = u.in ( r2, 2 * ( size_t ) n ); auto o = u.out ( dirs3, 3 * ( size_t ) n );
     return u.finish ( u.ok ? terra_unit_camera ( p, n, a, b, o ) : hipSuccess );
+}
+extern "C" int terra_amd_unit_lens_rays ( const TerraCamera* cam, const TerraAmdLens* lens, size_t fb_w, size_t fb_h, int n, const uint32_t* xy2, float jitter, const float* r4, TerraAmdRay* out_rays ) {
+    DevLens L;
+    if ( int rc = fill_lens ( cam, lens, "terra_amd_unit_lens_rays", L ) ) return rc;
+    if ( n < 0 || fb_w == 0 || fb_h == 0 || ( n && ( !xy2 || !r4 || !out_rays ) ) ) return fail ( kTerraAmdErrBadArgument, "terra_amd_unit_lens_rays: null array or empty frame" );
+    if ( need_device() ) return kTerraAmdErrNoDevice;
+    DevRenderParams p; memset ( &p, 0, sizeof p );
+    fill_camera ( cam, fb_w, fb_h, p );
+    p.jitter = jitter; p.fb_w = ( uint32_t ) fb_w; p.fb_h = ( uint32_t ) fb_h;
+    Unit u; auto a = u.in ( xy2, 2 * ( size_t ) n ); auto b = u.in ( r4, 4 * ( size_t ) n ); auto o = u.out ( reinterpret_cast<float*> ( out_rays ), 8 * ( size_t ) n );
+    return u.finish ( u.ok ? terra_unit_lens_rays ( p, L, n, a, b, o ) : hipSuccess );
 }
 extern "C" int terra_amd_unit_tonemap ( int op, float gamma, int n, float* colors3 ) {
     if ( need_device() ) return kTerraAmdErrNoDevice;

@@ -6,20 +6,73 @@
 // -----------------------------------------------------------------------------
 // camera
 // -----------------------------------------------------------------------------
-TD V3 camera_sample ( const DevRenderParams& p, uint32_t px, uint32_t py, float r1, float r2 ) {
+// the sample's film position in [-1, 1]^2 (sx to the right, sy up)
+TD void camera_film ( const DevRenderParams& p, uint32_t px, uint32_t py, float r1, float r2, float& sx, float& sy ) {
     float dx = -p.jitter + 2 * r1 * p.jitter;
     float dy = -p.jitter + 2 * r2 * p.jitter;
     // x / fb_w, y / fb_h bit for bit: the reciprocals of the frame size are launch constants, rounded on the host (fill_camera), and 1 <= fb_w, fb_h <= 2^32 is inside
     // the range div_exact_rk asks of its caller
     float ndc_x, ndc_y; div2_exact_rk ( ( float ) px + 0.5f + dx, ( float ) py + 0.5f + dy, ( float ) p.fb_w, p.inv_fb_w, ( float ) p.fb_h, p.inv_fb_h, ndc_x, ndc_y );
-    float sx = 2 * ndc_x - 1;
-    float sy = 1 - 2 * ndc_y;
-    float fx = sx * p.aspect * p.tan_half_fov;
-    float fy = sy * p.tan_half_fov;
-    V3 d = normalize ( v3 ( fx, fy, 1.f ) );
+    sx = 2 * ndc_x - 1;
+    sy = 1 - 2 * ndc_y;
+}
+// world direction of a camera-space vector
+TD V3 camera_rotate ( const DevRenderParams& p, V3 d ) {
     return v3 ( p.cam_rot[0] * d.x + p.cam_rot[1] * d.y + p.cam_rot[2] * d.z,
                 p.cam_rot[3] * d.x + p.cam_rot[4] * d.y + p.cam_rot[5] * d.z,
                 p.cam_rot[6] * d.x + p.cam_rot[7] * d.y + p.cam_rot[8] * d.z );
+}
+TD V3 camera_sample ( const DevRenderParams& p, uint32_t px, uint32_t py, float r1, float r2 ) {
+    float sx, sy; camera_film ( p, px, py, r1, r2, sx, sy );
+    float fx = sx * p.aspect * p.tan_half_fov;
+    float fy = sy * p.tan_half_fov;
+    V3 d = normalize ( v3 ( fx, fy, 1.f ) );
+    return camera_rotate ( p, d );
+}
+
+// The ray of a lens launch's sample (include/terra_amd.h "Lens rendering" is the definition): the one generator of the render kernels' lens instances,
+// the lens AOV kernel and the unit entry. (l1, l2): the lens pair, looked at only where lens_draws -- the caller draws it from stream A then, after the sampler
+// integration's pair, and passes anything otherwise. L is a launch constant: every branch on it is wave-uniform.
+TD bool lens_draws ( const DevLens& L ) { return L.model == 0 && L.lens_radius > 0.f; }
+TD void lens_sample ( const DevRenderParams& p, const DevLens& L, uint32_t px, uint32_t py, float r1, float r2, float l1, float l2, V3& ro, V3& rd ) {
+    const float kPi = tdm_float ( 0x40490FDBu ), kPi2 = tdm_float ( 0x3FC90FDBu ), kPi4 = tdm_float ( 0x3F490FDBu );
+    float sx, sy; camera_film ( p, px, py, r1, r2, sx, sy );
+    const V3 pos = v3 ( p.cam_pos[0], p.cam_pos[1], p.cam_pos[2] );
+    float Lx = 0.f, Ly = 0.f;          // the origin's offset in the lens / film plane (models 0 with a lens, 1)
+    bool shifted = false;
+    if ( L.model == 0 ) {
+        const float fx = sx * p.aspect * p.tan_half_fov;
+        const float fy = sy * p.tan_half_fov;
+        const V3 d = normalize ( v3 ( fx, fy, 1.f ) );
+        if ( L.lens_radius > 0.f ) {
+            // concentric map of the pair to the unit disk
+            const float a = 2 * l1 - 1, b = 2 * l2 - 1;
+            float u = 0.f, v = 0.f;
+            if ( ! ( a == 0.f && b == 0.f ) ) {
+                float r, phi;
+                if ( fabsf ( a ) > fabsf ( b ) ) { r = a; phi = kPi4 * ( b / a ); }
+                else { r = b; phi = kPi2 - kPi4 * ( a / b ); }
+                float sp, cp; tdm_sincosf_pair ( phi, sp, cp );          // (each bit-identical to tdm_sinf / tdm_cosf: dev_math.h)
+                u = r * cp; v = r * sp;
+            }
+            Lx = L.lens_radius * u; Ly = L.lens_radius * v; shifted = true;
+            const float t = L.focus_distance / d.z;
+            const V3 F = v3 ( d.x * t, d.y * t, d.z * t );          // where the pinhole ray meets the plane in focus
+            rd = camera_rotate ( p, normalize ( v3 ( F.x - Lx, F.y - Ly, F.z ) ) );
+        } else rd = camera_rotate ( p, d );
+    } else if ( L.model == 1 ) {
+        Lx = ( sx * p.aspect ) * L.ortho_half; Ly = sy * L.ortho_half; shifted = true;
+        rd = camera_rotate ( p, v3 ( 0.f, 0.f, 1.f ) );
+    } else if ( L.model == 2 ) {
+        const float phi = sx * kPi, theta = sy * kPi2;
+        float st, ct, sp, cp; tdm_sincosf_pair ( theta, st, ct ); tdm_sincosf_pair ( phi, sp, cp );
+        rd = camera_rotate ( p, v3 ( ct * sp, st, ct * cp ) );
+    } else {
+        const float ux = sx * p.aspect, uy = sy, rr = sqrtf ( ux * ux + uy * uy ), theta = rr * L.fisheye_half;
+        if ( rr == 0.f ) rd = camera_rotate ( p, v3 ( 0.f, 0.f, 1.f ) );
+        else { float st, ct; tdm_sincosf_pair ( theta, st, ct ); rd = camera_rotate ( p, v3 ( ( st * ux ) / rr, ( st * uy ) / rr, ct ) ); }
+    }
+    ro = shifted ? v3 ( pos.x + ( p.cam_rot[0] * Lx + p.cam_rot[1] * Ly ), pos.y + ( p.cam_rot[3] * Lx + p.cam_rot[4] * Ly ), pos.z + ( p.cam_rot[6] * Lx + p.cam_rot[7] * Ly ) ) : pos;
 }
 
 // -----------------------------------------------------------------------------

@@ -143,6 +143,7 @@ _EXTRA = {
     "terra_amd_reproject": (C.c_int, [C.c_void_p, _CAM, _CAM, C.POINTER(api.TerraFramebuffer)] + [C.c_void_p] * 5 + [_SZ] * 4 + [C.POINTER(api.TerraAmdTemporalOptions)]),
     **api.RAY_QUERY_SIGNATURES,
     **api.RAY_SOURCE_SIGNATURES,
+    **api.LENS_SIGNATURES,
 }
 
 
@@ -459,6 +460,35 @@ def render_aov_rays_device(lib, scene, rays, aov: DeviceAov, rect: Optional[Tupl
     _frame_rays(rays, aov.width, aov.height)
     x, y, w, h = rect if rect else (0, 0, aov.width, aov.height)
     check(lib.render_aov_rays_device(scene, rays.data_ptr(), aov.data.data_ptr(), aov.width, aov.height, x, y, w, h, stream), "terra_amd_render_aov_rays_device")
+
+
+# ---------------------------------------------------------------------------
+# lens rendering (include/terra_amd.h "Lens rendering")
+# ---------------------------------------------------------------------------
+
+def render_lens_device(lib, cam, lens: api.Lens, scene, fb: DeviceFramebuffer, rect: Optional[Tuple[int, int, int, int]] = None, rand_calls=None, stream=None):
+    """terra_amd_render_lens_device: the render call with every sample's primary ray made from the camera model `lens`"""
+    x, y, w, h = rect if rect else (0, 0, fb.width, fb.height)
+    check(lib.render_lens_device(C.byref(cam), C.byref(lens), scene, fb.pixels.data_ptr(), fb.results.data_ptr(), fb.width, fb.height, x, y, w, h,
+                                 rand_calls.data_ptr() if rand_calls is not None else None, stream), "terra_amd_render_lens_device")
+
+
+def render_aov_lens_device(lib, cam, lens: api.Lens, scene, aov: DeviceAov, rect: Optional[Tuple[int, int, int, int]] = None, stream=None):
+    """terra_amd_render_aov_lens_device: the AOV pass of a render_lens_device call"""
+    x, y, w, h = rect if rect else (0, 0, aov.width, aov.height)
+    check(lib.render_aov_lens_device(C.byref(cam), C.byref(lens), scene, aov.data.data_ptr(), aov.width, aov.height, x, y, w, h, stream), "terra_amd_render_aov_lens_device")
+
+
+def lens_rays(lib, cam, lens: api.Lens, width: int, height: int, xy, jitter: float, r4) -> np.ndarray:
+    """terra_amd_unit_lens_rays: the device's ray generator on arrays. xy [n, 2] pixels of a width x height frame, r4 [n, 4] = (r1, r2, l1, l2);
+    returns n api.RAY_DTYPE records (tmax FLT_MAX, reserved 0), which the ray door takes as they are"""
+    xy = np.ascontiguousarray(xy, dtype=np.uint32).reshape(-1, 2)
+    r4 = np.ascontiguousarray(r4, dtype=np.float32).reshape(-1, 4)
+    if len(xy) != len(r4):
+        raise TerraAmdError("lens_rays: one (r1, r2, l1, l2) per pixel")
+    out = np.zeros(len(xy), dtype=api.RAY_DTYPE)
+    check(lib.unit_lens_rays(C.byref(cam), C.byref(lens), width, height, len(xy), xy.ctypes.data, jitter, r4.ctypes.data, out.ctypes.data), "terra_amd_unit_lens_rays")
+    return out
 
 
 RADIANCE_FRAME_WIDTH = 256

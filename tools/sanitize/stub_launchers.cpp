@@ -3,6 +3,7 @@
 #include "kernels.h"
 hipError_t terra_launch_render ( const DevRenderParams&, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_launch_render_rays ( const DevRenderParams&, const void*, hipStream_t ) { return hipErrorNoDevice; }
+hipError_t terra_launch_render_lens ( const DevRenderParams&, const DevLens&, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_launch_job_streams ( const DevRenderParams&, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_launch_block_order ( const DevRenderParams&, uint32_t*, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_fill_sincos24 ( float2*, hipStream_t ) { return hipErrorNoDevice; }
@@ -31,6 +32,8 @@ hipError_t terra_unit_distribution_2d_pdf ( const float*, uint32_t, uint32_t, fl
 hipError_t terra_build_fast_tree_device ( const DevTri*, const uint32_t*, uint32_t, float, DevNode*, DevTri*, uint32_t*, int*, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_launch_aov ( DevRenderParams, void*, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_launch_aov_rays ( DevRenderParams, const void*, void*, hipStream_t ) { return hipErrorNoDevice; }
+hipError_t terra_launch_aov_lens ( DevRenderParams, const DevLens&, void*, hipStream_t ) { return hipErrorNoDevice; }
+hipError_t terra_unit_lens_rays ( const DevRenderParams&, const DevLens&, int, const uint32_t*, const float*, float* ) { return hipErrorNoDevice; }
 hipError_t terra_launch_denoise ( const void*, const void*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, int, float, int, float, float*, float*, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_launch_moments_accumulate ( const void*, void*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_launch_tile_error ( const void*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, float*, hipStream_t ) { return hipErrorNoDevice; }
