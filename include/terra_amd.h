@@ -843,6 +843,17 @@ int terra_amd_scene_lds_plan ( HTerraScene scene, uint32_t* out6 );
    unit of the last place from, a float (to within the rounding of the numerator); op 4: hashed vectors. Nothing is stored but the count and the records. */
 int terra_amd_unit_exact_div ( int op, const float* a, const float* b, const float* c, uint64_t first, uint64_t count, float denominator, float reciprocal, uint64_t seed,
                                uint32_t* helper_bits, uint32_t* plain_bits, uint64_t* mismatches, uint32_t* first_bad );
+/* The short square root of the shading code, the one-path tangent frame and the short roulette rescale against their plain forms, in the manner of
+   terra_amd_unit_exact_div: *mismatches = the elements that differ, first_bad[16][21] = the first of them as {inputs[3], helper bits[9], plain bits[9]} (unused words 0).
+   op 0: sqrt (a) against sqrtf; op 1: a root with a deliberately wrong core against sqrtf (the comparison's positive control: it must report mismatches);
+   op 2: the tangent frame of the normal (a, b, c), nine words per element (rows of tangent | normal | bitangent); op 3: the roulette rescale
+   (float) (1.0 / ((double) a + 1e-4)); op 4: normalize (a, b, c), three words per element.
+   Explicit form (a != NULL): `count` elements (at most 2^26) read from the arrays, both results also stored in helper_bits / plain_bits (1, 9 or 3 words per element).
+   Generated form (a == NULL): elements first .. first + count - 1 of a set made on the device from the counter and `seed` -- ops 0, 1, 3: the 32-bit pattern k itself;
+   op 2: hashed unit normals, scaled by 1, 2^40 or 2^-40, every fourth uniform in bit pattern; op 4: hashed vectors, among them ones whose squared length lies near
+   2^-96 and 2^96. Nothing is stored but the count and the records. */
+int terra_amd_unit_exact_sqrt ( int op, const float* a, const float* b, const float* c, uint64_t first, uint64_t count, uint64_t seed,
+                                uint32_t* helper_bits, uint32_t* plain_bits, uint64_t* mismatches, uint32_t* first_bad );
 /* The plane values of the fast tree's nodes: x[i] rounded to binary16 towards -inf (up = 0) or +inf (up != 0), as bits -- so that a box of such planes
    contains the box it was made from (host arithmetic; no device needed) */
 int terra_amd_unit_half_outward ( const double* x, int n, int up, uint16_t* out );

@@ -226,6 +226,12 @@ LENS_SIGNATURES = {
     "terra_amd_unit_lens_rays": (c_int, [POINTER(TerraCamera), POINTER(Lens), c_size_t, c_size_t, c_int, c_void_p, c_float, c_void_p, c_void_p]),
 }
 
+# ... and of the unit entry that holds the short square root, the one-path tangent frame and the roulette rescale to their plain forms (include/terra_amd.h):
+# (op, a, b, c, first, count, seed, helper_bits, plain_bits, mismatches, first_bad[16][21])
+EXACT_SQRT_SIGNATURES = {
+    "terra_amd_unit_exact_sqrt": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p]),
+}
+
 # entry points of include/Terra.h + include/TerraPresets.h, name -> (restype, argtypes)
 API_SIGNATURES = {
     "scene_create": (c_void_p, []),

@@ -30,7 +30,7 @@ SOURCES = [("scene_host.cpp", "scene_host.cpp", []), ("tree_build.cpp", "tree_bu
            ("aov_kernels.hip", "aov_kernels.hip", []), ("aov_kernels.hip", "aov_kernels.tu4.hip", ["-DTERRA_TU=4"]),
            ("aov_kernels.hip", "aov_kernels.tu8.hip", ["-DTERRA_TU=8"]),("denoise_kernels.hip", "denoise_kernels.hip", []),
            ("variance_kernels.hip", "variance_kernels.hip", []), ("temporal_kernels.hip", "temporal_kernels.hip", []), ("query_kernels.hip", "query_kernels.hip", [])]
-HEADERS = ["dev_types.h", "dev_math.h", "rng.h", "trace_device.h", "trace_math.h", "exact_div.h", "trace_geometry.h", "traverse_ref.h", "traverse_fast.h", "shading_device.h",
+HEADERS = ["dev_types.h", "dev_math.h", "rng.h", "trace_device.h", "trace_math.h", "exact_div.h", "exact_sqrt.h", "trace_geometry.h", "traverse_ref.h", "traverse_fast.h", "shading_device.h",
            "integrators_device.h", "sampling_device.h", "denoise_device.h", "kernels.h", "launch_plan.h", "empty_proof.h", "tree_build.h", "multi_gpu.h"]
 ARCH = os.environ.get("TERRA_AMD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -7,7 +7,8 @@
 //   div2_exact ( x1, x2, d, .. )  = x1 / d and x2 / d, one reciprocal; div2_exact_rk: two quotients by known denominators behind one branch
 //   rcp3_exact ( .. )             = three reciprocals behind one branch (make_ray)
 //   xd_normalize3 ( x, y, z, l, .. ) = x / l, y / l, z / l for l = the vector's length (>= 0 or NaN, as sqrtf returns it): one reciprocal, three quotients
-// The A/B against the plain "/" in every helper: profiles/exact_div/ab.md.
+//   roulette_scale ( pr )         = ( float ) ( 1.0 / ( ( double ) pr + 1e-4 ) ): the double division's own reciprocal and fma steps, without its scaling and fix-up
+// The A/B against the plain "/" in every helper: profiles/exact_div/ab.md (roulette_scale: profiles/short_sqrt/ab.md).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -86,4 +87,21 @@ XD void xd_normalize3 ( float x, float y, float z, float l, float& qx, float& qy
         return;
     }
     qx = x / l; qy = y / l; qz = z / l;
+}
+
+// The Russian-roulette rescale (integrators_device.h path_continue): ( float ) ( 1.0 / ( ( double ) pr + 1e-4 ) ), bit for bit. The IEEE expansion of the double
+// division is v_div_scale (twice), v_rcp_f64, two Newton steps, q = n y, the remainder n - d q, v_div_fmas, v_div_fixup: 13 instructions. For 0 <= pr <= 2^60 the
+// denominator lies in [1e-4, 2^60 + 1e-4]: both v_div_scale pass their operand through, the numerator 1.0 makes q = y exactly, v_div_fmas applies no scale and
+// v_div_fixup meets no special operand -- what is left is the reciprocal, two Newton steps and the last correction e = 1 - d y, y + e y (Markstein's step), the same
+// operations on the same operands: 7 instructions. Any other pr (negative, huge, NaN) takes the plain expression. All 2^32 patterns: tests/test_exact_sqrt_gpu.py.
+XD float roulette_scale ( float pr ) {
+    const double d = ( double ) pr + 1e-4;
+    if ( ( int ) ( pr >= 0.f ) & ( int ) ( pr <= 0x1p60f ) ) {
+        double y = __builtin_amdgcn_rcp ( d );
+        double e = __builtin_fma ( -d, y, 1.0 ); y = __builtin_fma ( y, e, y );
+        e = __builtin_fma ( -d, y, 1.0 ); y = __builtin_fma ( y, e, y );
+        e = __builtin_fma ( -d, y, 1.0 ); y = __builtin_fma ( e, y, y );
+        return ( float ) y;
+    }
+    return ( float ) ( 1.0 / d );
 }

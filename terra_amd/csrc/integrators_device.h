@@ -31,7 +31,13 @@ TD LightSample draw_light_sample ( const DevScene& sc, Pcg32& rb, Counters& c, c
     const float4* props = ( MODE == 1 && T ) ? T->l_props : reinterpret_cast<const float4*> ( sc.props );
     V3 ta, tb, tc; tri_vertices ( tris, ls.tri, ta, tb, tc );
     float4 p0 = props[4 * ls.tri + 0], p1 = props[4 * ls.tri + 1], p2 = props[4 * ls.tri + 2];
+    // (the ray-sourced and lens units keep the plain root here: with the short one their LDS-resident Direct instances take 12 / 4 B more scratch than before,
+    // profiles/short_sqrt/kernel_resources.md)
+#if TERRA_RAY_SOURCE
     float s = sqrtf ( e1 );
+#else
+    float s = sqrt_exact ( e1 );
+#endif
     float a = 1 - s, b = e2 * s, cw = 1 - a - b;
     ls.pos = ( ta * a + tb * b ) + tc * cw;
     V3 n = ( v3 ( p0.x, p0.y, p0.z ) * a + v3 ( p0.w, p1.x, p1.y ) * b ) + v3 ( p1.z, p1.w, p2.x ) * cw;
@@ -375,7 +381,7 @@ TD bool path_continue ( Surface& sf, V3 wo, V3& throughput, uint32_t& bounce, ui
     throughput = throughput * dot ( sf.normal, wi );
     float pr = sel_max ( throughput.x, sel_max ( throughput.y, throughput.z ) );
     if ( d.e3 > pr ) return false;
-    throughput = throughput * ( float ) ( 1.0 / ( ( double ) pr + 1e-4 ) );
+        throughput = throughput * roulette_scale ( pr );          // ( float ) ( 1.0 / ( ( double ) pr + 1e-4 ) ), bit for bit (exact_div.h)
     ++bounce;
     return bounce <= max_bounces;
 }

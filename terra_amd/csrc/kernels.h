@@ -98,6 +98,9 @@ hipError_t terra_unit_math ( int fn, int n, const float* x, const float* y, floa
 // exact_div.h against "/" (unit_kernels.hip "exact_div.h against the plain"): a == nullptr = the generated set; helper_bits / plain_bits only in the explicit form
 hipError_t terra_unit_exact_div ( int op, const float* a, const float* b, const float* c, uint64_t first, uint64_t count, float D, float R, uint64_t seed,
                                   uint32_t* helper_bits, uint32_t* plain_bits, unsigned long long* mismatches, uint32_t* first_bad );
+// exact_sqrt.h, make_basis and roulette_scale against their plain forms (unit_kernels.hip "exact_sqrt.h, the one-path"): the same two forms; first_bad[16][21]
+hipError_t terra_unit_exact_sqrt ( int op, const float* a, const float* b, const float* c, uint64_t first, uint64_t count, uint64_t seed,
+                                   uint32_t* helper_bits, uint32_t* plain_bits, unsigned long long* mismatches, uint32_t* first_bad );
 // texture_sample at uv2[n][2] / environment_eval's lat-long lookup at dir3[n][3] on the texture whose descriptor is at `t` (device memory)
 hipError_t terra_unit_texture_sample ( const DevTexture* t, int n, const float* uv2, float* out3 );
 hipError_t terra_unit_texture_latlong ( const DevTexture* t, int n, const float* dir3, float* out3 );

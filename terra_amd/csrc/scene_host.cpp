@@ -2776,6 +2776,21 @@ extern "C" int terra_amd_unit_exact_div ( int op, const float* a, const float* b
     unsigned long long* dm = reinterpret_cast<unsigned long long*> ( u.inout ( mismatches, 1 ) ); uint32_t* dr = u.out ( first_bad, 9 * 16 );
     return u.finish ( u.ok ? terra_unit_exact_div ( op, da, db, dc, first, count, denominator, reciprocal, seed, dh, dp, dm, dr ) : hipSuccess );
 }
+extern "C" int terra_amd_unit_exact_sqrt ( int op, const float* a, const float* b, const float* c, uint64_t first, uint64_t count, uint64_t seed,
+                                            uint32_t* helper_bits, uint32_t* plain_bits, uint64_t* mismatches, uint32_t* first_bad ) {
+    if ( need_device() ) return kTerraAmdErrNoDevice;
+    if ( op < 0 || op > 4 || !mismatches || !first_bad ) return fail ( kTerraAmdErrBadArgument, "exact_sqrt unit: op %d, or no place for the mismatch count and records", op );
+    const bool explicit_set = a != nullptr, three = op == 2 || op == 4;
+    if ( explicit_set && ( !helper_bits || !plain_bits || ( three && ( !b || !c ) ) || count > ( 1ull << 26 ) ) )
+        return fail ( kTerraAmdErrBadArgument, "exact_sqrt unit: the explicit form of op %d needs its input and output arrays, at most 2^26 elements", op );
+    const size_t n = explicit_set ? ( size_t ) count : 0, per = op == 2 ? 9 : ( op == 4 ? 3 : 1 );
+    Unit u;
+    const float* da = explicit_set ? u.in ( a, n ) : nullptr; const float* db = explicit_set && three ? u.in ( b, n ) : nullptr; const float* dc = explicit_set && three ? u.in ( c, n ) : nullptr;
+    uint32_t* dh = explicit_set ? u.out ( helper_bits, per * n ) : nullptr; uint32_t* dp = explicit_set ? u.out ( plain_bits, per * n ) : nullptr;
+    *mismatches = 0;
+    unsigned long long* dm = reinterpret_cast<unsigned long long*> ( u.inout ( mismatches, 1 ) ); uint32_t* dr = u.out ( first_bad, 21 * 16 );
+    return u.finish ( u.ok ? terra_unit_exact_sqrt ( op, da, db, dc, first, count, seed, dh, dp, dm, dr ) : hipSuccess );
+}
 
 // binary16 planes of the fast tree's nodes (tree_build.cpp fastbvh::half_outward): host arithmetic, no device needed
 extern "C" int terra_amd_unit_half_outward ( const double* x, int n, int up, uint16_t* out ) {

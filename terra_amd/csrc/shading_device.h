@@ -242,12 +242,12 @@ TD void azimuth_sincos ( const Azimuth& az, float e, float& sn, float& cs ) {
 }
 
 TD V3 diffuse_sample ( const Surface& sf, float e1, float e2, const Azimuth& az ) {
-    float r = sqrtf ( e1 );
+    float r = sqrt_exact ( e1 );
     float sn, cs;
     azimuth_sincos ( az, e2, sn, cs );
     float x = r * cs;
     float z = r * sn;
-    V3 wi = v3 ( x, sqrtf ( sel_max ( 0.f, 1 - e1 ) ), z );
+    V3 wi = v3 ( x, sqrt_exact ( sel_max ( 0.f, 1 - e1 ) ), z );
     return normalize ( basis_apply ( make_basis ( sf.normal ), wi ) );
 }
 TD float diffuse_pdf ( const Surface& sf, V3 wi ) { return div_exact_rk ( sel_max ( 0.f, dot ( sf.normal, wi ) ), TERRA_PI_F, TERRA_INV_PI_F ); }
@@ -305,13 +305,13 @@ TD float ggx_G1 ( V3 v, V3 n, V3 h, float alpha2 ) {
     if ( VoH / VoN <= 0.f ) return 0.f;
     float VoN2 = VoN * VoN;
     float tan2 = ( 1.f - VoN2 ) / VoN2;        // Smith G1 w.r.t. the normal (Walter 2007 eq. 34), see oracle note
-    return 2.f / ( sqrtf ( 1 + alpha2 * tan2 ) + 1 );
+    return 2.f / ( sqrt_exact ( 1 + alpha2 * tan2 ) + 1 );
 }
 TD V3 ggx_sample ( const Surface& sf, float e1, float e2, V3 wo, const Azimuth& az ) {
     float alpha = sf.attr[1].x;
     float t2 = alpha * alpha * e1 / ( 1.f - e1 );
-    float cos_t = 1.f / sqrtf ( 1.f + t2 );
-    float sin_t = sqrtf ( sel_max ( 0.f, 1.f - cos_t * cos_t ) );
+    float cos_t = 1.f / sqrt_exact ( 1.f + t2 );
+    float sin_t = sqrt_exact ( sel_max ( 0.f, 1.f - cos_t * cos_t ) );
     float sn, cs;
     azimuth_sincos ( az, e2, sn, cs );
     V3 h = v3 ( sin_t * cs, cos_t, sin_t * sn );
@@ -350,7 +350,7 @@ TD V3 glass_sample ( Surface& sf, float e3, V3 wo ) {
     V3 dir; float prob;
     if ( cos_t2 < 0.f ) { dir = refl; prob = 1.f; }
     else {
-        float cos_t = sqrtf ( cos_t2 );
+        float cos_t = sqrt_exact ( cos_t2 );
         float t = 1.f - ( n1 <= n2 ? cos_i : cos_t );
         float R0 = ( n1 - n2 ) / ( n1 + n2 ); R0 *= R0;
         float R = R0 + ( 1 - R0 ) * ( t * t * t * t * t );

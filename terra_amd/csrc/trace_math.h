@@ -8,6 +8,7 @@
 #include "rng.h"
 #include "sampling_device.h"
 #include "exact_div.h"
+#include "exact_sqrt.h"
 
 #define TD __device__ __forceinline__
 
@@ -22,10 +23,12 @@ TD V3 had ( V3 a, V3 b ) { return v3 ( a.x * b.x, a.y * b.y, a.z * b.z ); }
 TD V3 neg ( V3 a ) { return v3 ( -a.x, -a.y, -a.z ); }
 TD float dot ( V3 a, V3 b ) { return a.x * b.x + a.y * b.y + a.z * b.z; }
 TD V3 cross ( V3 a, V3 b ) { return v3 ( a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x ); }
-TD float length ( V3 a ) { return sqrtf ( a.x * a.x + a.y * a.y + a.z * a.z ); }
-// a / |a|: the three quotients share one refined reciprocal of the length (exact_div.h); normalize_plain is the same function written with "/" (the unit entry compares them)
-TD V3 normalize_plain ( V3 a ) { float l = length ( a ); return v3 ( a.x / l, a.y / l, a.z / l ); }
-TD V3 normalize ( V3 a ) { float l = length ( a ); V3 r; xd_normalize3 ( a.x, a.y, a.z, l, r.x, r.y, r.z ); return r; }
+TD float length2 ( V3 a ) { return a.x * a.x + a.y * a.y + a.z * a.z; }
+TD float length ( V3 a ) { return sqrtf ( length2 ( a ) ); }          // (the plain root: its callers are the denoise, temporal and AOV kernels and one-off sites)
+// a / |a|: the short root of the squared length (exact_sqrt.h), then three quotients that share one refined reciprocal of the length (exact_div.h), each behind its
+// own guard; normalize_plain is the same function written with sqrtf and "/" (the unit entries compare them)
+TD V3 normalize_plain ( V3 a ) { float l = sqrtf ( length2 ( a ) ); return v3 ( a.x / l, a.y / l, a.z / l ); }
+TD V3 normalize ( V3 a ) { float l = sqrt_exact ( length2 ( a ) ); V3 r; xd_normalize3 ( a.x, a.y, a.z, l, r.x, r.y, r.z ); return r; }
 // compare-selects: exactly "a < b ? a : b" / "a > b ? a : b" (NaN-order sensitive)
 TD float sel_min ( float a, float b ) { return a < b ? a : b; }
 TD float sel_max ( float a, float b ) { return a > b ? a : b; }
@@ -38,7 +41,16 @@ TD V3 basis_apply ( const Basis& m, V3 v ) {
                 m.r1[0] * v.x + m.r1[1] * v.y + m.r1[2] * v.z,
                 m.r2[0] * v.x + m.r2[1] * v.y + m.r2[2] * v.z );
 }
-TD Basis make_basis ( V3 n ) {
+TD Basis basis_of ( V3 t, V3 n ) {
+    V3 b = cross ( n, t );
+    Basis m;
+    m.r0[0] = t.x; m.r0[1] = n.x; m.r0[2] = b.x;
+    m.r1[0] = t.y; m.r1[1] = n.y; m.r1[2] = b.y;
+    m.r2[0] = t.z; m.r2[1] = n.z; m.r2[2] = b.z;
+    return m;
+}
+// the tangent as the reference writes it: two arms, a root and three products in each (the unit entry compares make_basis with it)
+TD Basis make_basis_plain ( V3 n ) {
     V3 t;
     if ( fabsf ( n.x ) > fabsf ( n.y ) ) {
         float k = sqrtf ( n.x * n.x + n.z * n.z );
@@ -47,12 +59,16 @@ TD Basis make_basis ( V3 n ) {
         float k = sqrtf ( n.y * n.y + n.z * n.z );
         t = v3 ( 0.f * k, -n.z * k, n.y * k );
     }
-    V3 b = cross ( n, t );
-    Basis m;
-    m.r0[0] = t.x; m.r0[1] = n.x; m.r0[2] = b.x;
-    m.r1[0] = t.y; m.r1[1] = n.y; m.r1[2] = b.y;
-    m.r2[0] = t.z; m.r2[1] = n.z; m.r2[2] = b.z;
-    return m;
+    return basis_of ( t, n );
+}
+// ... and as the kernels run it: the arms are one computation on different operands, so the operands are selected and one path runs -- a wave whose lanes disagree
+// on the comparison no longer executes both arms. Same sum order, same three products, the negations on the operands as above; the products by 0.f stay (k may be
+// NaN or inf)
+TD Basis make_basis ( V3 n ) {
+    const bool c = fabsf ( n.x ) > fabsf ( n.y );
+    const float a = c ? n.x : n.y;
+    const float k = sqrt_exact ( a * a + n.z * n.z );
+    return basis_of ( v3 ( ( c ? n.z : 0.f ) * k, ( c ? 0.f : -n.z ) * k, ( c ? -n.x : n.y ) * k ), n );
 }
 
 struct Ray { V3 o, d, inv; };

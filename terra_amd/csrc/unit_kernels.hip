@@ -352,6 +352,80 @@ hipError_t terra_unit_exact_div ( int op, const float* a, const float* b, const 
     return hipGetLastError();
 }
 
+// ---- exact_sqrt.h, the one-path make_basis and roulette_scale against their plain forms (tests/test_exact_sqrt_gpu.py), in the manner of k_exact_div: both computed per
+// element, bits compared on the device (NaN = NaN), *mismatches and the first 16 offenders as {inputs[3], helper bits[9], plain bits[9]} (unused words 0). Explicit form:
+// elements read from a / b / c, both results also stored, `per` words per element; generated form (a == nullptr): element k of a set made from the counter.
+//   op 0  sqrt_exact ( x ) against sqrtf ( x )                       per 1   generated: x = the pattern k
+//   op 1  a deliberately wrong core (the upper candidate dropped) against sqrtf: the comparison's positive control          generated: x = the pattern k
+//   op 2  make_basis ( n ) against make_basis_plain ( n )            per 9   generated: n a hashed unit vector, scaled by 1, 2^40 or 2^-40 by k; every fourth uniform in bits
+//   op 3  roulette_scale ( pr ) against the plain expression         per 1   generated: pr = the pattern k
+//   op 4  normalize ( x, y, z ) against normalize_plain              per 3   generated: k_exact_div's vectors; every eighth with components of magnitude 2^-49 .. 2^-47 or
+//                                                                            2^47 .. 2^49, so that the squared length falls on either side of the root's guard 2^-96 (and of 2^96)
+struct XsSink { unsigned long long* mismatches; uint32_t* first_bad; };
+TD float xs_sqrt_wrong ( float x ) {
+    if ( !xs_in_range ( x ) ) return sqrtf ( x );
+    const float s = __builtin_amdgcn_sqrtf ( x );
+    const float down = __uint_as_float ( __float_as_uint ( s ) - 1u );
+    return __builtin_fmaf ( -down, s, x ) <= 0.f ? down : s;
+}
+TD void basis_words ( const Basis& m, float* w ) { for ( int j = 0; j < 3; ++j ) { w[j] = m.r0[j]; w[3 + j] = m.r1[j]; w[6 + j] = m.r2[j]; } }
+template <int OP>
+__global__ __launch_bounds__ ( 256 ) void k_exact_sqrt ( const float* a, const float* b, const float* c, unsigned long long first, unsigned long long count, unsigned long long seed,
+                                                         uint32_t* helper_bits, uint32_t* plain_bits, XsSink s ) {
+    constexpr int PER = OP == 2 ? 9 : ( OP == 4 ? 3 : 1 );
+    const unsigned long long stride = ( unsigned long long ) gridDim.x * blockDim.x;
+    for ( unsigned long long i = ( unsigned long long ) blockIdx.x * blockDim.x + threadIdx.x; i < count; i += stride ) {
+        const unsigned long long k = first + i;
+        const uint64_t h0 = xd_hash ( seed ^ ( k * 0xd1342543de82ef95ull ) ), h1 = xd_hash ( h0 );
+        V3 in = v3 ( 0.f, 0.f, 0.f );
+        if ( a ) { in.x = a[i]; if ( OP == 2 || OP == 4 ) { in.y = b[i]; in.z = c[i]; } }
+        else if ( OP == 0 || OP == 1 || OP == 3 ) in.x = __uint_as_float ( ( uint32_t ) k );
+        else if ( ( k & 3ull ) == 3ull ) in = v3 ( __uint_as_float ( ( uint32_t ) h0 ), __uint_as_float ( ( uint32_t ) ( h0 >> 32 ) ), __uint_as_float ( ( uint32_t ) h1 ) );
+        else if ( OP == 2 ) {
+            in = normalize_plain ( v3 ( xd_float_in ( ( uint32_t ) h0, 115u, 13u ), xd_float_in ( ( uint32_t ) ( h0 >> 32 ), 115u, 13u ), xd_float_in ( ( uint32_t ) h1, 115u, 13u ) ) );
+            const uint32_t pick3 = ( uint32_t ) ( h1 >> 40 ) % 3u;
+            in = in * ( pick3 == 0u ? 1.f : ( pick3 == 1u ? 0x1p40f : 0x1p-40f ) );
+        } else if ( ( k & 7ull ) == 5ull ) {
+            const uint32_t lo = ( h1 >> 40 ) & 1u ? 78u : 174u;
+            in = v3 ( xd_float_in ( ( uint32_t ) h0, lo, 3u ), xd_float_in ( ( uint32_t ) ( h0 >> 32 ), lo, 3u ), xd_float_in ( ( uint32_t ) h1, lo, 3u ) );
+        } else {
+            const uint32_t lo = 87u + ( uint32_t ) ( h1 >> 40 ) % 60u;
+            in = v3 ( xd_float_in ( ( uint32_t ) h0, lo, 24u ), xd_float_in ( ( uint32_t ) ( h0 >> 32 ), lo, 24u ), xd_float_in ( ( uint32_t ) h1, lo, 24u ) );
+        }
+        float hw[9] = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f }, pw[9] = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f };
+        if ( OP == 0 ) { hw[0] = sqrt_exact ( in.x ); pw[0] = sqrtf ( in.x ); }
+        else if ( OP == 1 ) { hw[0] = xs_sqrt_wrong ( in.x ); pw[0] = sqrtf ( in.x ); }
+        else if ( OP == 2 ) { basis_words ( make_basis ( in ), hw ); basis_words ( make_basis_plain ( in ), pw ); }
+        else if ( OP == 3 ) { hw[0] = roulette_scale ( in.x ); pw[0] = ( float ) ( 1.0 / ( ( double ) in.x + 1e-4 ) ); }
+        else { const V3 hv = normalize ( in ), pv = normalize_plain ( in ); hw[0] = hv.x; hw[1] = hv.y; hw[2] = hv.z; pw[0] = pv.x; pw[1] = pv.y; pw[2] = pv.z; }
+        bool same = true;
+        for ( int j = 0; j < PER; ++j ) same = same && xd_same ( hw[j], pw[j] );
+        if ( !same ) {
+            const unsigned long long slot = atomicAdd ( s.mismatches, 1ull );
+            if ( slot < 16ull ) {
+                uint32_t* r = s.first_bad + 21 * slot;
+                r[0] = __float_as_uint ( in.x ); r[1] = __float_as_uint ( in.y ); r[2] = __float_as_uint ( in.z );
+                for ( int j = 0; j < 9; ++j ) { r[3 + j] = __float_as_uint ( hw[j] ); r[12 + j] = __float_as_uint ( pw[j] ); }
+            }
+        }
+        if ( a ) for ( int j = 0; j < PER; ++j ) { helper_bits[PER * i + j] = __float_as_uint ( hw[j] ); plain_bits[PER * i + j] = __float_as_uint ( pw[j] ); }
+    }
+}
+hipError_t terra_unit_exact_sqrt ( int op, const float* a, const float* b, const float* c, uint64_t first, uint64_t count, uint64_t seed,
+                                   uint32_t* helper_bits, uint32_t* plain_bits, unsigned long long* mismatches, uint32_t* first_bad ) {
+    if ( count == 0 ) return hipSuccess;
+    const uint64_t blocks = ( count + 255u ) / 256u;
+    const dim3 grid ( ( unsigned ) ( blocks < 4096u ? blocks : 4096u ) ), block ( 256 );
+    const XsSink s = { mismatches, first_bad };
+#define XS_CASE(OP) case OP: hipLaunchKernelGGL ( k_exact_sqrt<OP>, grid, block, 0, 0, a, b, c, ( unsigned long long ) first, ( unsigned long long ) count, ( unsigned long long ) seed, helper_bits, plain_bits, s ); break;
+    switch ( op ) {
+        XS_CASE ( 0 ) XS_CASE ( 1 ) XS_CASE ( 2 ) XS_CASE ( 3 ) XS_CASE ( 4 )
+        default: return hipErrorInvalidValue;
+    }
+#undef XS_CASE
+    return hipGetLastError();
+}
+
 // ---- the texture lookups on one texture of a blob (scene_host.cpp unit_texture): texture_sample in texel units, and environment_eval by direction on a scene
 // record that holds nothing but that texture as its lat-long environment
 __global__ void k_texture_sample ( const DevTexture* t, int n, const float* uv2, float* out3 ) {

@@ -144,6 +144,7 @@ _EXTRA = {
     **api.RAY_QUERY_SIGNATURES,
     **api.RAY_SOURCE_SIGNATURES,
     **api.LENS_SIGNATURES,
+    **api.EXACT_SQRT_SIGNATURES,
 }
 
 

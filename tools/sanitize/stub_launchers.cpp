@@ -23,6 +23,7 @@ hipError_t terra_unit_camera ( const DevRenderParams&, int, const uint32_t*, con
 hipError_t terra_unit_tonemap ( int, float, int, float* ) { return hipErrorNoDevice; }
 hipError_t terra_unit_math ( int, int, const float*, const float*, float* ) { return hipErrorNoDevice; }
 hipError_t terra_unit_exact_div ( int, const float*, const float*, const float*, uint64_t, uint64_t, float, float, uint64_t, uint32_t*, uint32_t*, unsigned long long*, uint32_t* ) { return hipErrorNoDevice; }
+hipError_t terra_unit_exact_sqrt ( int, const float*, const float*, const float*, uint64_t, uint64_t, uint64_t, uint32_t*, uint32_t*, unsigned long long*, uint32_t* ) { return hipErrorNoDevice; }
 hipError_t terra_unit_bvh_traverse_fast ( const DevScene&, int, const float*, const float*, int*, uint32_t*, float*, uint32_t* ) { return hipErrorNoDevice; }
 hipError_t terra_unit_stratified ( const uint32_t*, int, int, int, int, float* ) { return hipErrorNoDevice; }
 hipError_t terra_unit_halton ( int, int, float* ) { return hipErrorNoDevice; }
