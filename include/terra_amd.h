@@ -759,6 +759,75 @@ int terra_amd_render_aov_lens ( const TerraCamera* camera, const TerraAmdLens* l
 int terra_amd_unit_lens_rays ( const TerraCamera* camera, const TerraAmdLens* lens, size_t fb_width, size_t fb_height, int n, const uint32_t* xy2, float jitter,
                                const float* r4, TerraAmdRay* out_rays );
 
+/* ---- Point rendering: irradiance and probe samples -- directions drawn in the kernel about a client's points ------------------------------------------------
+   The fifth door: a render launch whose primary ray is generated per SAMPLE, in the kernel, from the pixel's TerraAmdPoint -- a position and a normal, one record per
+   pixel of the frame, frame-indexed like a TerraAmdRay buffer -- and the pixel's stream A. A bake does not want one fixed ray per pixel: it wants, per surface point,
+   many directions over the hemisphere about that point's normal, and through the ray door that is one ray buffer and one launch per batch of samples. The output is an
+   ordinary framebuffer: with distribution 0, PI * acc / samples is the IRRADIANCE at the point (what a lightmap texel or a baked vertex colour stores); with
+   distribution 1, acc / samples is a probe's mean radiance over the sphere. The denoisers, the moments buffer, a client's adaptive loop and samples-keyed accumulation
+   over several calls work on such a frame as on an image. The reference has no such call: this is the library's own definition, off unless called.
+   Inactive point.  One of the six components of position and normal is not finite, or q = nx*nx + ny*ny + nz*nz is 0 or not finite. It behaves exactly like the ray
+     door's inactive ray, in both distributions: nothing is traced, nothing is drawn (d_rand_calls 0), the pixel receives samples_per_pixel samples of +0.
+   Draw order on stream A, per sample.  r1, r2 -- drawn and unused, as in the ray door --; the sampler integration's pair, where that draws; then g1, g2, always.
+     Stream B is untouched by the generator.
+   The ray of a sample.  All arithmetic is binary32 in exactly the order written, no fused multiply-add; normalize is the camera call's; sinf / cosf are the device's
+     (terra_amd_unit_math fn 0 / 1); PI/2 = 0x3FC90FDB, PI/4 = 0x3F490FDB, 2 PI = 0x40C90FDB.
+     n = normalize(normal). The frame is the branch-free orthonormal basis of Duff et al. 2017 (NOT the shading basis, whose tangent is the reference's unnormalised one):
+       s = copysignf(1, n.z), a = -1 / (s + n.z), b = (n.x * n.y) * a,
+       t = (1 + (s * (n.x * n.x)) * a, s * b, (-s) * n.x), bt = (b, s + (n.y * n.y) * a, -n.y).
+     distribution 0, cosine-weighted hemisphere.  (u, v) = the concentric map of (g1, g2) to the unit disk, exactly as "Lens rendering" states it for (l1, l2);
+       w = sqrtf(max(0, (1 - u*u) - v*v)); d = ((u t.x + v bt.x) + w n.x, (u t.y + v bt.y) + w n.y, (u t.z + v bt.z) + w n.z).
+     distribution 1, uniform sphere.  z = 1 - 2 g1, r = sqrtf(max(0, 1 - z*z)), phi = (2 PI) g2, x = r cosf(phi), y = r sinf(phi);
+       d = ((x t.x + y bt.x) + z n.x, (x t.y + y bt.y) + z n.y, (x t.z + y bt.z) + z n.z).
+     direction = normalize(d); origin = position. terra_trace's own 0.001 offset along the direction applies as for every primary ray: it is what keeps a point ON a
+     surface from hitting that surface.
+   Everything else is a render launch, as the lens door states it: the scene's integrator, bounces and switches; the sample split (the AUTOMATIC split is that of a
+     launch without the job order), job queue, resolve, tonemap, statistics, d_rand_calls, work counters, flat leaf-box test and pair form unchanged. A point launch
+     never has the job order or the empty skip.
+   Traversal.  The ray door's rule: the host forms look at the ACTIVE points' positions and run the replica traversal when one lies beyond
+     TerraAmdTraversalInfo::camera_limit on some axis; the device forms cannot look and take the commit's choice -- the client keeps the positions within camera_limit.
+     A scene committed for several devices answers on its primary device.
+   AOV form.  terra_amd_render_aov_device() with the same substitution and the same draws: depth sums |hit point - position|; an inactive point adds its samples and
+     nothing else. With distribution 0, 1 - coverage / samples is the cosine-weighted sky visibility of the point: AMBIENT OCCLUSION.
+   Calls.  They fail like the lens forms -- kTerraAmdErrNotCommitted first, before anything else is looked at and without touching a device -- then with
+     kTerraAmdErrBadArgument, nothing launched and nothing written, for a NULL sampling struct, a distribution outside 0..1, non-zero reserved, a NULL point buffer or one
+     that is not 16-byte aligned, a bad rectangle; then like a render call (an integrator that needs a light and finds none). */
+typedef struct {            /* 32 bytes, 16-byte aligned in a buffer, frame-indexed like TerraAmdRay */
+    float position[3];      /* +0  */
+    float reserved;         /* +12 ignored */
+    float normal[3];        /* +16 need not be normalised */
+    float reserved2;        /* +28 ignored */
+} TerraAmdPoint;
+typedef struct {            /* 16 bytes */
+    int distribution;       /* 0 cosine-weighted hemisphere about the normal, 1 uniform sphere */
+    int reserved[3];        /* zero */
+} TerraAmdPointSampling;
+TERRA_ABI_ASSERT ( sizeof ( TerraAmdPoint ) == 32 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdPoint, reserved ) == 12 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdPoint, normal ) == 16 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdPoint, reserved2 ) == 28 );
+TERRA_ABI_ASSERT ( sizeof ( TerraAmdPointSampling ) == 16 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdPointSampling, reserved ) == 4 );
+/* d_points: device memory, one TerraAmdPoint per pixel of the frame (fb_width * fb_height records; only the rectangle's are read). The other arguments as
+   terra_amd_render_rays_device(). Asynchronous on `stream`. */
+int terra_amd_render_points_device ( HTerraScene scene, const TerraAmdPointSampling* sampling, const void* d_points, void* d_pixels, void* d_results, size_t fb_width, size_t fb_height,
+                                     size_t x, size_t y, size_t width, size_t height, void* d_rand_calls, void* stream );
+/* The same on host memory, as terra_amd_render_rays() takes it: points frame-indexed, 16-byte aligned; synchronous. */
+int terra_amd_render_points ( HTerraScene scene, const TerraAmdPointSampling* sampling, const TerraAmdPoint* points, const TerraFramebuffer* framebuffer, size_t x, size_t y, size_t width, size_t height );
+/* d_aov as terra_amd_render_aov_device() takes it. Asynchronous on `stream`. */
+int terra_amd_render_aov_points_device ( HTerraScene scene, const TerraAmdPointSampling* sampling, const void* d_points, void* d_aov, size_t fb_width, size_t fb_height,
+                                         size_t x, size_t y, size_t width, size_t height, void* stream );
+/* The same on host buffers (frame-indexed); synchronous. */
+int terra_amd_render_aov_points ( HTerraScene scene, const TerraAmdPointSampling* sampling, const TerraAmdPoint* points, TerraAmdAovResult* aov, size_t fb_width, size_t fb_height,
+                                  size_t x, size_t y, size_t width, size_t height );
+/* The device's generator on arrays (needs no scene): out_rays[i] receives the ray of points[i] for the pair g2[2 i], g2[2 i + 1] = (g1, g2), with tmax = FLT_MAX and
+   reserved = 0 -- a record the ray door takes as it is. An inactive point gives an all-zero origin and direction, which the ray door treats as inactive too. */
+int terra_amd_unit_point_rays ( const TerraAmdPointSampling* sampling, int n, const TerraAmdPoint* points, const float* g2, TerraAmdRay* out_rays );
+/* The committed scene's vertices as points, on the host (no device is touched): record 3 * T + k is vertex k of the scene's T-th triangle (objects in order,
+   triangles in order within each) -- its position and its TerraTriangleProperties normal as stored. Returns the number of records (3 * triangles) whatever the
+   capacity, or a negative status, and writes the first min(capacity, records) records. Baking vertex colours is this helper plus one render call. */
+int terra_amd_scene_vertex_points ( HTerraScene scene, TerraAmdPoint* out, int capacity );
+
 /* Tile-sharded form for one-process-per-GPU rendering (the reference shards
    the same way over CPU threads: satellite/src/Renderer.cpp:316-350): the
    rectangle is cut into tile_size x tile_size tiles numbered row-major and this

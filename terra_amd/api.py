@@ -232,6 +232,33 @@ EXACT_SQRT_SIGNATURES = {
     "terra_amd_unit_exact_sqrt": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
+
+
+class Point(Structure):
+    """TerraAmdPoint (include/terra_amd.h "Point rendering"): a position and a normal (need not be normalised), one per pixel of a frame; 32 bytes"""
+    _fields_ = [("position", c_float * 3), ("reserved", c_float), ("normal", c_float * 3), ("reserved2", c_float)]
+
+
+class PointSampling(Structure):
+    """TerraAmdPointSampling: distribution 0 cosine-weighted hemisphere about the normal, 1 uniform sphere; 16 bytes"""
+    _fields_ = [("distribution", c_int), ("reserved", c_int * 3)]
+
+
+ABI_SIZES.update({Point: 32, PointSampling: 16})
+assert C.sizeof(Point) == 32 and C.sizeof(PointSampling) == 16
+POINT_DTYPE = np.dtype([("position", np.float32, 3), ("reserved", np.float32), ("normal", np.float32, 3), ("reserved2", np.float32)])
+assert POINT_DTYPE.itemsize == 32
+
+# ... and of point rendering (include/terra_amd.h "Point rendering")
+POINT_SIGNATURES = {
+    "terra_amd_render_points_device": (c_int, [c_void_p, POINTER(PointSampling), c_void_p, c_void_p, c_void_p] + [c_size_t] * 6 + [c_void_p, c_void_p]),
+    "terra_amd_render_points": (c_int, [c_void_p, POINTER(PointSampling), c_void_p, POINTER(TerraFramebuffer)] + [c_size_t] * 4),
+    "terra_amd_render_aov_points_device": (c_int, [c_void_p, POINTER(PointSampling), c_void_p, c_void_p] + [c_size_t] * 6 + [c_void_p]),
+    "terra_amd_render_aov_points": (c_int, [c_void_p, POINTER(PointSampling), c_void_p, c_void_p] + [c_size_t] * 6),
+    "terra_amd_unit_point_rays": (c_int, [POINTER(PointSampling), c_int, c_void_p, c_void_p, c_void_p]),
+    "terra_amd_scene_vertex_points": (c_int, [c_void_p, c_void_p, c_int]),
+}
+
 # entry points of include/Terra.h + include/TerraPresets.h, name -> (restype, argtypes)
 API_SIGNATURES = {
     "scene_create": (c_void_p, []),

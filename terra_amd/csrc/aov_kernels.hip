@@ -13,6 +13,9 @@
 // With TERRA_TU=8 it is the LENS unit (TERRA_RAY_SOURCE 2; include/terra_amd.h "Lens rendering"): terra_aov_lens_kernel and terra_launch_aov_lens trace, per sample, the
 // ray lens_sample (trace_geometry.h) makes from the camera model, drawing stream A as the lens render kernels do; the unit also holds the generator's unit entry
 // (terra_unit_lens_rays), so that no other unit's code changes.
+// With TERRA_TU=12 it is the POINT unit (TERRA_RAY_SOURCE 3; include/terra_amd.h "Point rendering"): terra_aov_points_kernel and terra_launch_aov_points trace, per
+// sample, the ray point_sample (trace_geometry.h) draws about the pixel's point, drawing stream A as the point render kernels do; the unit also holds the generator's
+// unit entry (terra_unit_point_rays).
 #include <hip/hip_runtime.h>
 #include "trace_device.h"
 #include "kernels.h"
@@ -25,7 +28,10 @@ static_assert ( sizeof ( DevAov ) == 48, "DevAov must be 48 bytes" );
 #define TERRA_AOV_FOLD_BYTES ( 2 * 256 * 16 )       // the block's chunk sums: two float4 per lane
 #define TERRA_AOV_MAX_BLOCKS_PER_CU 8
 
-#if TERRA_RAY_SOURCE == 2
+#if TERRA_RAY_SOURCE == 3
+#define TERRA_AOV_KERNEL terra_aov_points_kernel
+#define TERRA_AOV_RAYS_PARAM , const float4* points, const DevPointSampling sampling
+#elif TERRA_RAY_SOURCE == 2
 #define TERRA_AOV_KERNEL terra_aov_lens_kernel
 #define TERRA_AOV_RAYS_PARAM , const DevLens lens
 #elif TERRA_RAY_SOURCE == 1
@@ -56,7 +62,35 @@ __global__ __launch_bounds__ ( 256 ) void TERRA_AOV_KERNEL ( DevRenderParams p, 
         const uint32_t px = p.x + lx, py = p.y + ly;
         const size_t pix = inside ? ( size_t ) ( py - p.st_y ) * p.st_pitch + ( px - p.st_x ) : 0;
         float4 s0 = make_float4 ( 0.f, 0.f, 0.f, 0.f ), s1 = make_float4 ( 0.f, 0.f, 0.f, 0.f );
-#if TERRA_RAY_SOURCE == 2
+#if TERRA_RAY_SOURCE == 3
+        if ( inside ) {
+            // the camera form below with the point launch's ray: r1, r2 (unused), the sampler integration's pair, then g1, g2; an inactive point adds its samples and nothing else
+            const float4* rec = points + 2 * pix;
+            const float4 q0 = rec[0], q1 = rec[1];          // {position, reserved} {normal, reserved2}
+            const V3 pos = v3 ( q0.x, q0.y, q0.z ), nrm = v3 ( q1.x, q1.y, q1.z );
+            if ( !point_inactive ( pos, nrm ) ) {
+                const int prior = __float_as_int ( aov[3 * pix + 2].x );
+                const uint32_t base = ( uint32_t ) prior + chunk * p.chunk_spp;
+                PixelStreams rs = trng_pixel_streams ( p.frame_seed, ( uint64_t ) py * p.fb_w + px, ( uint64_t ) ( uint32_t ) prior + ( uint64_t ) chunk * p.chunk_spp );
+                for ( uint32_t s = 0; s < p.chunk_spp; ++s ) {
+                    ( void ) trng_a_float ( rs.a ); ( void ) trng_a_float ( rs.a );
+                    if ( p.sampler_mode ) ( void ) sampler_pair_draw ( p.sampler_mode, p.sampler_strata, ( uint64_t ) base + s, rs.a );
+                    const float g1 = trng_a_float ( rs.a ), g2 = trng_a_float ( rs.a );
+                    V3 ro, rd;
+                    point_sample ( sampling, pos, nrm, g1, g2, ro, rd );
+                    Surface sf;
+                    Counters c = counters_zero();
+                    const RaycastResult h = scene_raycast<0, MODE, TERRA_KINDS_ALL> ( T, make_ray ( ro, rd ), sf, c );
+                    if ( h.hit ) {
+                        const V3 a = sf.bsdf == kDevBsdfPhong ? sf.attr[1] : sf.attr[0];
+                        s0.x = s0.x + a.x; s0.y = s0.y + a.y; s0.z = s0.z + a.z; s0.w = s0.w + 1.f;
+                        s1.x = s1.x + sf.normal.x; s1.y = s1.y + sf.normal.y; s1.z = s1.z + sf.normal.z;
+                        s1.w = s1.w + length ( ro - h.point );
+                    }
+                }
+            }
+        }
+#elif TERRA_RAY_SOURCE == 2
         if ( inside ) {
             // the camera form below with the lens launch's ray: r1, r2, the sampler integration's pair, then the lens pair where the launch draws one
             const int prior = __float_as_int ( aov[3 * pix + 2].x );
@@ -139,7 +173,28 @@ __global__ __launch_bounds__ ( 256 ) void TERRA_AOV_KERNEL ( DevRenderParams p, 
     }
 }
 
-#if TERRA_RAY_SOURCE == 2
+#if TERRA_RAY_SOURCE == 3
+// the generator on arrays (terra_amd_unit_point_rays): one thread per input; an inactive point gives the all-zero origin and direction
+__global__ void k_point_rays ( DevPointSampling sampling, int n, const float4* points, const float* g2, float* rays8 ) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if ( i >= n ) return;
+    const float4 q0 = points[2 * ( size_t ) i], q1 = points[2 * ( size_t ) i + 1];
+    const V3 pos = v3 ( q0.x, q0.y, q0.z ), nrm = v3 ( q1.x, q1.y, q1.z );
+    V3 ro = v3 ( 0.f, 0.f, 0.f ), rd = v3 ( 0.f, 0.f, 0.f );
+    if ( !point_inactive ( pos, nrm ) ) point_sample ( sampling, pos, nrm, g2[2 * ( size_t ) i], g2[2 * ( size_t ) i + 1], ro, rd );
+    float* q = rays8 + 8 * ( size_t ) i;
+    q[0] = ro.x; q[1] = ro.y; q[2] = ro.z; q[3] = FLT_MAX;
+    q[4] = rd.x; q[5] = rd.y; q[6] = rd.z; q[7] = 0.f;          // (reserved: the all-zero word)
+}
+hipError_t terra_unit_point_rays ( const DevPointSampling& sampling, int n, const float* points8, const float* g2, float* rays8 ) {
+    if ( n <= 0 ) return hipSuccess;
+    hipLaunchKernelGGL ( k_point_rays, dim3 ( ( n + 255 ) / 256 ), dim3 ( 256 ), 0, 0, sampling, n, reinterpret_cast<const float4*> ( points8 ), g2, rays8 );
+    return hipGetLastError();
+}
+#define TERRA_AOV_RAYS_ARG , reinterpret_cast<const float4*> ( points ), sampling
+hipError_t terra_launch_aov_points ( DevRenderParams p, const void* points, const DevPointSampling& sampling, void* aov, hipStream_t stream ) {
+    if ( !points || sampling.distribution < 0 || sampling.distribution > 1 ) return hipErrorInvalidValue;
+#elif TERRA_RAY_SOURCE == 2
 // the generator on arrays (terra_amd_unit_lens_rays): one thread per input
 __global__ void k_lens_rays ( DevRenderParams p, DevLens lens, int n, const uint32_t* xy2, const float* r4, float* rays8 ) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;

@@ -345,11 +345,21 @@ struct DevLens {
 };
 // ... and their parameters: DevRenderParams followed by the lens, a structure only the lens kernel instances take (as DevRayRenderParams and for its reason)
 struct DevLensRenderParams : DevRenderParams { DevLens lens; };
-// Where a launch's primary rays come from, TERRA_RAY_SOURCE: 0 the pinhole camera's sample, 1 the ray buffer (ray-sourced), 2 a camera model's sample (lens).
-// Ray-sourced and lens kernel instances are units of their own: render_kernels.hip compiled with TERRA_TU 4 - 7 / 8 - 11 and aov_kernels.hip with TERRA_TU 4 / 8
-// (terra_amd/build.py), or with -DTERRA_RAY_SOURCE=1 / 2 and no TERRA_TU (tools/kernel_resources.sh).
+// point launches (include/terra_amd.h "Point rendering"): one TerraAmdPoint (two 16-byte words: {position, -} {normal, -}) per pixel, addressed like `results` as a
+// ray-sourced launch's rays are, and the distribution every sample's direction is drawn from about the point's normal. The generator: point_sample, trace_geometry.h.
+struct DevPointSampling {
+    int32_t distribution;       // 0 cosine-weighted hemisphere about the normal, 1 uniform sphere
+};
+// ... and their parameters, a structure only the point kernel instances take (as DevRayRenderParams and for its reason)
+struct DevPointRenderParams : DevRenderParams { const float4* points; DevPointSampling sampling; };
+// Where a launch's primary rays come from, TERRA_RAY_SOURCE: 0 the pinhole camera's sample, 1 the ray buffer (ray-sourced), 2 a camera model's sample (lens),
+// 3 a direction drawn about the pixel's point (points).
+// Ray-sourced, lens and point kernel instances are units of their own: render_kernels.hip compiled with TERRA_TU 4 - 7 / 8 - 11 / 12 - 15 and aov_kernels.hip with
+// TERRA_TU 4 / 8 / 12 (terra_amd/build.py), or with -DTERRA_RAY_SOURCE=1 / 2 / 3 and no TERRA_TU (tools/kernel_resources.sh).
 #ifndef TERRA_RAY_SOURCE
-#if defined ( TERRA_TU ) && TERRA_TU >= 8
+#if defined ( TERRA_TU ) && TERRA_TU >= 12
+#define TERRA_RAY_SOURCE 3
+#elif defined ( TERRA_TU ) && TERRA_TU >= 8
 #define TERRA_RAY_SOURCE 2
 #elif defined ( TERRA_TU ) && TERRA_TU >= 4
 #define TERRA_RAY_SOURCE 1

@@ -26,6 +26,14 @@ hipError_t terra_launch_render_lens_mode0 ( const DevLensRenderParams& p, size_t
 hipError_t terra_launch_render_lens_mode1 ( const DevLensRenderParams& p, size_t lds, hipStream_t stream );
 hipError_t terra_launch_render_lens_mode2 ( const DevLensRenderParams& p, size_t lds, hipStream_t stream );
 hipError_t terra_launch_render_lens_mode3 ( const DevLensRenderParams& p, size_t lds, hipStream_t stream );
+// point launches (include/terra_amd.h "Point rendering"): terra_launch_render with every primary ray drawn by point_sample (trace_geometry.h) about the pixel's record
+// of `points` (one TerraAmdPoint per pixel, addressed like p.results); p without job order and empty skip, as for a ray-sourced launch. The point kernel instances
+// are units of their own (render_kernels.hip TERRA_TU 12 - 15)
+hipError_t terra_launch_render_points ( const DevRenderParams& p, const void* points, const DevPointSampling& sampling, hipStream_t stream );
+hipError_t terra_launch_render_points_mode0 ( const DevPointRenderParams& p, size_t lds, hipStream_t stream );
+hipError_t terra_launch_render_points_mode1 ( const DevPointRenderParams& p, size_t lds, hipStream_t stream );
+hipError_t terra_launch_render_points_mode2 ( const DevPointRenderParams& p, size_t lds, hipStream_t stream );
+hipError_t terra_launch_render_points_mode3 ( const DevPointRenderParams& p, size_t lds, hipStream_t stream );
 hipError_t terra_launch_resolve ( const DevRenderParams& p, hipStream_t stream );   // second kernel of a split render (p.split > 1)
 hipError_t terra_launch_tiles ( bool pack, float* pixels, void* results, uint32_t fb_w, uint32_t x, uint32_t y, uint32_t w, uint32_t h,
                                 uint32_t tile, uint32_t rank, uint32_t world, float* packed, hipStream_t stream );
@@ -39,6 +47,9 @@ hipError_t terra_launch_aov_rays ( DevRenderParams p, const void* rays, void* ao
 // ... with the samples of a lens launch (as terra_launch_render_lens makes them, the lens pair drawn where that draws it): depth sums |hit point - ray origin|
 // (aov_kernels.hip compiled as a unit of its own, TERRA_TU 8)
 hipError_t terra_launch_aov_lens ( DevRenderParams p, const DevLens& lens, void* aov, hipStream_t stream );
+// ... with the samples of a point launch (as terra_launch_render_points makes them): depth sums |hit point - position|, an inactive point adds its samples and
+// nothing else (aov_kernels.hip compiled as a unit of its own, TERRA_TU 12)
+hipError_t terra_launch_aov_points ( DevRenderParams p, const void* points, const DevPointSampling& sampling, void* aov, hipStream_t stream );
 
 // the a-trous denoiser and its variance-guided form (denoise_kernels.hip): results / aov / moments (TerraAmdMoments) / radiance / pixels indexed like a frame of fb_w
 // pixels per row; only the rectangle is read or written; radiance or pixels may be nullptr
@@ -93,6 +104,9 @@ hipError_t terra_unit_bsdf ( int kind, int n, float* surfaces47, const float* e3
 hipError_t terra_unit_camera ( const DevRenderParams& p, int n, const uint32_t* xy2, const float* r2, float* dirs3 );
 // lens_sample on arrays: r4[n][4] = (r1, r2, l1, l2); rays8[n][8] = TerraAmdRay records (tmax FLT_MAX, reserved 0). p: the camera fields, jitter and frame size
 hipError_t terra_unit_lens_rays ( const DevRenderParams& p, const DevLens& lens, int n, const uint32_t* xy2, const float* r4, float* rays8 );
+// point_sample on arrays: points8[n][8] = TerraAmdPoint records (device memory, 16-byte aligned), g2[n][2] = (g1, g2); rays8[n][8] = TerraAmdRay records (tmax
+// FLT_MAX, reserved 0; all-zero origin and direction for an inactive point)
+hipError_t terra_unit_point_rays ( const DevPointSampling& sampling, int n, const float* points8, const float* g2, float* rays8 );
 hipError_t terra_unit_tonemap ( int op, float gamma, int n, float* colors3 );
 hipError_t terra_unit_math ( int fn, int n, const float* x, const float* y, float* out );
 // exact_div.h against "/" (unit_kernels.hip "exact_div.h against the plain"): a == nullptr = the generated set; helper_bits / plain_bits only in the explicit form

@@ -32,16 +32,20 @@
 //               is the pixel's record of DevRayRenderParams::rays instead of a camera sample). Units of their own, so that units 0 - 3 compile as before
 //   TERRA_TU 8 / 9 / 10 / 11  the LENS kernels of template MODE 0 / 1 / 2 / 3 and their launcher, nothing else (TERRA_RAY_SOURCE 2: a primary ray is the sample of
 //               DevLensRenderParams::lens, a camera model -- lens_sample, trace_geometry.h)
-//   undefined   all of it in one unit (tools/kernel_resources.sh, tools/isa_cost.py); with -DTERRA_RAY_SOURCE=1 / 2: every ray-sourced / lens kernel in one unit
+//   TERRA_TU 12 / 13 / 14 / 15  the POINT kernels of template MODE 0 / 1 / 2 / 3 and their launcher, nothing else (TERRA_RAY_SOURCE 3: a primary ray is a direction
+//               drawn about the pixel's record of DevPointRenderParams::points -- point_sample, trace_geometry.h)
+//   undefined   all of it in one unit (tools/kernel_resources.sh, tools/isa_cost.py); with -DTERRA_RAY_SOURCE=1 / 2 / 3: every ray-sourced / lens / point kernel in one unit
 #ifdef TERRA_TU
 #define TERRA_TU_HAS(k) ( TERRA_TU == ( k ) )
-#define TERRA_TU_MODE(k) ( TERRA_TU == ( k ) || TERRA_TU == ( k ) + 4 || TERRA_TU == ( k ) + 8 )      // the unit holds the kernels of template MODE k
+#define TERRA_TU_MODE(k) ( TERRA_TU == ( k ) || TERRA_TU == ( k ) + 4 || TERRA_TU == ( k ) + 8 || TERRA_TU == ( k ) + 12 )      // the unit holds the kernels of template MODE k
 #else
 #define TERRA_TU_HAS(k) ( !TERRA_RAY_SOURCE )
 #define TERRA_TU_MODE(k) 1
 #endif
 // what a render kernel instance of this unit takes: where its primary rays come from
-#if TERRA_RAY_SOURCE == 2
+#if TERRA_RAY_SOURCE == 3
+typedef DevPointRenderParams RenderKernelParams;
+#elif TERRA_RAY_SOURCE == 2
 typedef DevLensRenderParams RenderKernelParams;
 #elif TERRA_RAY_SOURCE == 1
 typedef DevRayRenderParams RenderKernelParams;
@@ -516,6 +520,10 @@ TD PrimaryRay ray_record ( const RenderKernelParams& p, uint32_t px, uint32_t py
     const float4* rec = p.rays + 2 * ( ( size_t ) ( py - p.st_y ) * p.st_pitch + ( px - p.st_x ) );          // addressed like p.results
     const float4 q0 = rec[0], q1 = rec[1];          // {origin, tmax} {direction, reserved}: a primary ray has no limit, tmax and reserved are not looked at
     r.o = v3 ( q0.x, q0.y, q0.z ); r.d = v3 ( q1.x, q1.y, q1.z );
+#elif TERRA_RAY_SOURCE == 3
+    const float4* rec = p.points + 2 * ( ( size_t ) ( py - p.st_y ) * p.st_pitch + ( px - p.st_x ) );        // addressed like p.results
+    const float4 q0 = rec[0], q1 = rec[1];          // {position, reserved} {normal, reserved2}: o = the position, d = the normal as stored
+    r.o = v3 ( q0.x, q0.y, q0.z ); r.d = v3 ( q1.x, q1.y, q1.z );
 #endif
     return r;
 }
@@ -526,8 +534,18 @@ TD bool ray_record_inactive ( const PrimaryRay& r ) {
 }
 // Lens launches: the sample of the launch's camera model (lens_sample), made AFTER the sampler integration's draws -- TERRA_LENS_RAY, which follows them in every loop and
 // is empty in the other units -- because a thin lens draws its pair from stream A there; the other models and the pinhole draw nothing (lens_draws is a launch constant).
+// Point launches: a direction drawn about the pixel's point (point_sample) from the pair g1, g2, which every sample draws from stream A where the lens pair is drawn.
+// TERRA_POINT_HOLD 0: the point's record is fetched again for every sample, as the ray door's ray is; 1: fetched once per job and held in six registers -- the
+// normalised normal and the frame are made per sample either way. Figures of both: profiles/points/kernel_resources.md.
+#ifndef TERRA_POINT_HOLD
+#define TERRA_POINT_HOLD 0
+#endif
 // (macros inside the kernel, not functions: the camera units then compile the very statements they always had -- tools/isa_same.sh against the parent)
-#if TERRA_RAY_SOURCE == 2
+#if TERRA_RAY_SOURCE == 3
+#define TERRA_PRIMARY_RAY( ro, rd, r1, r2 )
+#define TERRA_LENS_RAY( ro, rd, r1, r2 ) do { const PrimaryRay pt_ = TERRA_POINT_HOLD ? held : ray_record ( p, jb.px, jb.py ); const float g1_ = trng_a_float ( rs.a ), g2_ = trng_a_float ( rs.a ); point_sample ( p.sampling, pt_.o, pt_.d, g1_, g2_, ro, rd ); } while ( 0 )
+#define TERRA_JOB_NEXT() job_take<COUNT, MODE == 1> ( p, acc_lds, jb, rs, c, job_total, held )
+#elif TERRA_RAY_SOURCE == 2
 #define TERRA_PRIMARY_RAY( ro, rd, r1, r2 )
 #define TERRA_LENS_RAY( ro, rd, r1, r2 ) do { float l1_ = 0.f, l2_ = 0.f; if ( lens_draws ( p.lens ) ) { l1_ = trng_a_float ( rs.a ); l2_ = trng_a_float ( rs.a ); } lens_sample ( p, p.lens, jb.px, jb.py, r1, r2, l1_, l2_, ro, rd ); } while ( 0 )
 #define TERRA_JOB_NEXT() job_next<COUNT, MODE == 1> ( p, acc_lds, jb, rs, c, job_total )
@@ -541,15 +559,21 @@ TD bool ray_record_inactive ( const PrimaryRay& r ) {
 #define TERRA_JOB_NEXT() job_next<COUNT, MODE == 1> ( p, acc_lds, jb, rs, c, job_total )
 #endif
 // job_next for the kernel's loops. Ray-sourced launches look at the new job's ray here, once per job: an inactive one ends the job where it starts -- its sum stays
-// the +0 job_next set, it draws nothing, and the resolve kernel adds that +0 and the call's samples to the pixel like any other job's sum.
-#if TERRA_RAY_SOURCE == 1
+// the +0 job_next set, it draws nothing, and the resolve kernel adds that +0 and the call's samples to the pixel like any other job's sum. Point launches look at
+// the new job's point in the same place, to the same end.
+#if TERRA_RAY_SOURCE == 1 || TERRA_RAY_SOURCE == 3
 template <int COUNT, bool TABLE>
 TD void job_take ( const RenderKernelParams& p, float* aux, Jobs& j, PixelStreams& rs, const Counters& c, uint32_t total, PrimaryRay& held ) {
     job_next<COUNT, TABLE> ( p, aux, j, rs, c, total );
     if ( j.s != p.chunk_spp ) {          // (a job was taken: job_next leaves s at chunk_spp for a pixel outside the rectangle and for a lane that found nothing)
         const PrimaryRay r = ray_record ( p, j.px, j.py );
+#if TERRA_RAY_SOURCE == 3
+        if ( point_inactive ( r.o, r.d ) ) j.s = p.chunk_spp;
+        if ( TERRA_POINT_HOLD ) held = r;
+#else
         if ( ray_record_inactive ( r ) ) j.s = p.chunk_spp;
         if ( TERRA_RAY_HOLD ) held = r;
+#endif
     }
 }
 #endif
@@ -576,8 +600,8 @@ __global__ __launch_bounds__ ( 256, terra_waves ( INTEGRATOR, KINDS, MODE ) ) vo
     Ray ray = make_ray ( v3 ( 0, 0, 0 ), v3 ( 0, 0, 1 ) );
     uint32_t bounce = 0;
     const V3 cam_pos = v3p ( p.cam_pos );
-#if TERRA_RAY_SOURCE == 1
-    PrimaryRay held; held.o = v3 ( 0, 0, 0 ); held.d = v3 ( 0, 0, 1 );      // the job's ray (TERRA_RAY_HOLD only)
+#if TERRA_RAY_SOURCE == 1 || TERRA_RAY_SOURCE == 3
+    PrimaryRay held; held.o = v3 ( 0, 0, 0 ); held.d = v3 ( 0, 0, 1 );      // the job's ray or point (TERRA_RAY_HOLD / TERRA_POINT_HOLD only)
 #endif
 
     if constexpr ( terra_decoupled_mis ( INTEGRATOR, MODE, KINDS ) ) {
@@ -909,6 +933,20 @@ static hipError_t launch_integrator ( const RenderKernelParams& p, size_t lds, h
     }
 }
 // one launcher per template MODE and ray source, each in its own translation unit (see the top of the file)
+#if TERRA_RAY_SOURCE == 3
+#if TERRA_TU_MODE ( 0 )
+hipError_t terra_launch_render_points_mode0 ( const DevPointRenderParams& p, size_t lds, hipStream_t stream ) { return launch_integrator<0> ( p, lds, stream ); }
+#endif
+#if TERRA_TU_MODE ( 1 )
+hipError_t terra_launch_render_points_mode1 ( const DevPointRenderParams& p, size_t lds, hipStream_t stream ) { return launch_integrator<1> ( p, lds, stream ); }
+#endif
+#if TERRA_TU_MODE ( 2 )
+hipError_t terra_launch_render_points_mode2 ( const DevPointRenderParams& p, size_t lds, hipStream_t stream ) { return launch_integrator<2> ( p, lds, stream ); }
+#endif
+#if TERRA_TU_MODE ( 3 )
+hipError_t terra_launch_render_points_mode3 ( const DevPointRenderParams& p, size_t lds, hipStream_t stream ) { return launch_integrator<3> ( p, lds, stream ); }
+#endif
+#endif
 #if TERRA_RAY_SOURCE == 2
 #if TERRA_TU_MODE ( 0 )
 hipError_t terra_launch_render_lens_mode0 ( const DevLensRenderParams& p, size_t lds, hipStream_t stream ) { return launch_integrator<0> ( p, lds, stream ); }
@@ -984,6 +1022,17 @@ hipError_t terra_launch_render_lens ( const DevRenderParams& p, const DevLens& l
     if ( p.lds_mode == 1 ) return terra_launch_render_lens_mode1 ( lp, lds, stream );
     if ( p.lds_mode == 2 ) return p.scene.reach ? terra_launch_render_lens_mode3 ( lp, lds, stream ) : terra_launch_render_lens_mode2 ( lp, lds, stream );
     return terra_launch_render_lens_mode0 ( lp, lds, stream );
+}
+// ... and with its primary rays drawn about `points` (DevPointRenderParams): the point instances of the same kernels, under the same rule
+hipError_t terra_launch_render_points ( const DevRenderParams& p, const void* points, const DevPointSampling& sampling, hipStream_t stream ) {
+    if ( p.job_blocks == 0 ) return hipSuccess;
+    if ( !points || !p.partials || p.block_order || p.job_live || sampling.distribution < 0 || sampling.distribution > 1 ) return hipErrorInvalidValue;
+    DevPointRenderParams pp;
+    static_cast<DevRenderParams&> ( pp ) = p; pp.points = reinterpret_cast<const float4*> ( points ); pp.sampling = sampling;
+    size_t lds = terra_lds_bytes ( p );
+    if ( p.lds_mode == 1 ) return terra_launch_render_points_mode1 ( pp, lds, stream );
+    if ( p.lds_mode == 2 ) return p.scene.reach ? terra_launch_render_points_mode3 ( pp, lds, stream ) : terra_launch_render_points_mode2 ( pp, lds, stream );
+    return terra_launch_render_points_mode0 ( pp, lds, stream );
 }
 
 // First kernel of every render: the random streams of every job of the launch (what job_next would otherwise compute when a lane takes the job). One thread per job,

@@ -1664,11 +1664,13 @@ static uint32_t launch_split ( const Scene* s, DevRenderParams& p, uint32_t bloc
 // d_rays: non-null = a ray-sourced launch (include/terra_amd.h "Ray-sourced rendering"): the same plan, scratch, queue and resolve, the primary rays read from d_rays
 // (addressed like p.results); no job order and no empty skip, which are made from camera rays
 // lens: non-null = a lens launch (include/terra_amd.h "Lens rendering"): likewise, the primary rays made from the camera fields of p and *lens
-static int launch_render ( Scene* s, DevRenderParams& p, int device, hipStream_t stream, ThreadSlot* slot = nullptr, const void* d_rays = nullptr, const DevLens* lens = nullptr ) {      // device: the (current) device of the launch
+// points: non-null = a point launch (include/terra_amd.h "Point rendering"): likewise, the primary rays drawn about the records of d_points (addressed like p.results)
+static int launch_render ( Scene* s, DevRenderParams& p, int device, hipStream_t stream, ThreadSlot* slot = nullptr, const void* d_rays = nullptr, const DevLens* lens = nullptr,
+                           const void* d_points = nullptr, const DevPointSampling* points = nullptr ) {      // device: the (current) device of the launch
     const uint32_t blocks = terra_render_blocks ( p );
     if ( blocks == 0 ) return 0;
     if ( p.count_level != 0 || p.rand_calls ) { p.leaf_boxes = nullptr; p.n_leaf_boxes = 0; p.leaf_pairs = 0; }      // the work counters keep their meaning: counting launches walk the tree and test one triangle per trip
-    const bool ray_source = d_rays != nullptr || lens != nullptr;
+    const bool ray_source = d_rays != nullptr || lens != nullptr || points != nullptr;
     const uint32_t split = launch_split ( s, p, blocks, ray_source );
     static thread_local uint64_t pool_kept = 0;          // (bit d: done for device d)
     if ( device < 64 && ! ( pool_kept >> device & 1ull ) ) {        // keep freed scratch cached in the device's default pool instead of returning it to the OS at every sync
@@ -1727,7 +1729,7 @@ static int launch_render ( Scene* s, DevRenderParams& p, int device, hipStream_t
     }
     if ( e == hipSuccess && order_cls ) e = terra_launch_block_order ( p, order_cls, stream );
     if ( e == hipSuccess ) e = terra_launch_job_streams ( p, stream );
-    if ( e == hipSuccess ) e = lens ? terra_launch_render_lens ( p, *lens, stream ) : d_rays ? terra_launch_render_rays ( p, d_rays, stream ) : terra_launch_render ( p, stream );
+    if ( e == hipSuccess ) e = points ? terra_launch_render_points ( p, d_points, *points, stream ) : lens ? terra_launch_render_lens ( p, *lens, stream ) : d_rays ? terra_launch_render_rays ( p, d_rays, stream ) : terra_launch_render ( p, stream );
     if ( e == hipSuccess ) e = terra_launch_resolve ( p, stream );
     if ( pooled ) ( void ) hipFreeAsync ( scratch, stream );
     else if ( e != hipSuccess ) ( void ) hipMemsetAsync ( scratch, 0, header, stream );       // (a launch that failed half way must not leave a used queue word behind)
@@ -1883,14 +1885,16 @@ static_assert ( sizeof ( TerraAmdAovResult ) == 48, "TerraAmdAovResult must be 4
 // p: the launch fill_params made for the render call this AOV call mirrors; the split is the one that call takes (launch_split), and the samples the AOV buffer
 // already holds key the streams as the framebuffer's do. Runs on the current device (the scene's primary one).
 // d_rays: non-null = the ray-sourced form, mirroring a ray-sourced render call (addressed like d_aov); lens: non-null = the lens form, mirroring a lens render call.
-static int launch_aov ( Scene* s, DevRenderParams& p, void* d_aov, hipStream_t stream, const void* d_rays = nullptr, const DevLens* lens = nullptr ) {
+// points: non-null = the point form, mirroring a point render call (d_points addressed like d_aov).
+static int launch_aov ( Scene* s, DevRenderParams& p, void* d_aov, hipStream_t stream, const void* d_rays = nullptr, const DevLens* lens = nullptr,
+                        const void* d_points = nullptr, const DevPointSampling* points = nullptr ) {
     const uint32_t blocks = terra_render_blocks ( p );
     if ( blocks == 0 ) return 0;
-    const uint32_t split = launch_split ( s, p, blocks, d_rays != nullptr || lens != nullptr );
+    const uint32_t split = launch_split ( s, p, blocks, d_rays != nullptr || lens != nullptr || points != nullptr );
     p.split = split; p.split_log2 = 0; while ( ( 1u << p.split_log2 ) < split ) ++p.split_log2;
     p.chunk_spp = p.spp / split; p.job_blocks = blocks * split; p.job_queue = nullptr; p.job_streams = nullptr; p.block_order = nullptr; p.partials = nullptr;
     p.pixels = nullptr; p.results = nullptr; p.rand_calls = nullptr; p.counters = nullptr; p.count_level = 0;
-    const hipError_t e = lens ? terra_launch_aov_lens ( p, *lens, d_aov, stream ) : d_rays ? terra_launch_aov_rays ( p, d_rays, d_aov, stream ) : terra_launch_aov ( p, d_aov, stream );
+    const hipError_t e = points ? terra_launch_aov_points ( p, d_points, *points, d_aov, stream ) : lens ? terra_launch_aov_lens ( p, *lens, d_aov, stream ) : d_rays ? terra_launch_aov_rays ( p, d_rays, d_aov, stream ) : terra_launch_aov ( p, d_aov, stream );
     if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "AOV launch: %s", hipGetErrorString ( e ) );
     return 0;
 }
@@ -2522,6 +2526,153 @@ extern "C" int terra_amd_render_aov_lens ( const TerraCamera* cam, const TerraAm
     return 0;
 }
 
+// ---- point rendering: the render call with directions drawn about a client's points (include/terra_amd.h "Point rendering") ----------------------------------
+static_assert ( sizeof ( TerraAmdPoint ) == 32 && sizeof ( TerraAmdPointSampling ) == 16, "TerraAmdPoint must be 32 bytes, TerraAmdPointSampling 16" );
+// the one check of the sampling struct, for the five entry points that take one; fills the launch constants as the kernels take them (DevPointSampling)
+static int fill_point_sampling ( const TerraAmdPointSampling* ps, const char* what, DevPointSampling& S ) {
+    if ( !ps ) return fail ( kTerraAmdErrBadArgument, "%s: null sampling", what );
+    if ( ps->distribution < 0 || ps->distribution > 1 ) return fail ( kTerraAmdErrBadArgument, "%s: distribution %d: 0 cosine-weighted hemisphere, 1 uniform sphere", what, ps->distribution );
+    if ( ps->reserved[0] || ps->reserved[1] || ps->reserved[2] ) return fail ( kTerraAmdErrBadArgument, "%s: TerraAmdPointSampling::reserved must be zero", what );
+    S.distribution = ps->distribution;
+    return 0;
+}
+// the header's inactive point, on the host
+static bool point_is_inactive ( const TerraAmdPoint& q ) {
+    const bool finite = std::isfinite ( q.position[0] ) && std::isfinite ( q.position[1] ) && std::isfinite ( q.position[2] ) && std::isfinite ( q.normal[0] ) && std::isfinite ( q.normal[1] ) && std::isfinite ( q.normal[2] );
+    const float qq = q.normal[0] * q.normal[0] + q.normal[1] * q.normal[1] + q.normal[2] * q.normal[2];
+    return !finite || ! ( qq > 0.f && std::isfinite ( qq ) );
+}
+// host forms: do all ACTIVE points of the rectangle lie inside the range the commit's traversal shortcut is proven for? (an inactive point is never traced)
+static bool point_positions_within ( const Scene* s, const TerraAmdPoint* points, size_t fb_w, size_t x, size_t y, size_t w, size_t h ) {
+    const float limit = shortcut_limit ( s->tree );
+    for ( size_t j = y; j < y + h; ++j ) for ( size_t i = x; i < x + w; ++i ) {
+        const TerraAmdPoint& q = points[j * fb_w + i];
+        if ( point_is_inactive ( q ) ) continue;
+        if ( ! ( fabsf ( q.position[0] ) <= limit && fabsf ( q.position[1] ) <= limit && fabsf ( q.position[2] ) <= limit ) ) return false;
+    }
+    return true;
+}
+// fill_params of a point launch: "not committed" first, then the arguments -- all of them, the rectangle included, before the call asks for the scene's device
+// replica: a bad argument is refused on a host without a GPU too --, then the launch. origins_ok: as fill_params' ray_origins_ok
+static int fill_point_params ( Scene* s, const Scene::Replica& r, const TerraAmdPointSampling* ps, const void* points, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t h,
+                               bool origins_ok, const char* what, DevRenderParams& p, DevPointSampling& S ) {
+    if ( !s->committed ) return scene_check ( s );
+    if ( int rc = fill_point_sampling ( ps, what, S ) ) return rc;
+    if ( !points ) return fail ( kTerraAmdErrBadArgument, "%s: null point buffer", what );
+    if ( ( uintptr_t ) points & 15u ) return fail ( kTerraAmdErrBadArgument, "%s: the point buffer must be 16-byte aligned", what );
+    if ( w == 0 || h == 0 || x + w > fb_w || y + h > fb_h ) return fail ( kTerraAmdErrBadArgument, "%s: bad rectangle %zu,%zu %zux%zu in %zux%zu", what, x, y, w, h, fb_w, fb_h );
+    return fill_params ( s, r, nullptr, fb_w, fb_h, x, y, w, h, 64, 0, 1, p, &origins_ok );
+}
+extern "C" int terra_amd_render_points_device ( HTerraScene h, const TerraAmdPointSampling* ps, const void* d_points, void* d_pixels, void* d_results, size_t fb_w, size_t fb_h,
+                                                size_t x, size_t y, size_t w, size_t hgt, void* d_rand_calls, void* stream ) {
+    Scene* s = S ( h );
+    const Scene::Replica& r = primary ( s );
+    DevRenderParams p; DevPointSampling D;
+    // (the points are in HBM: the client keeps their positions within camera_limit)
+    if ( int rc = fill_point_params ( s, r, ps, d_points, fb_w, fb_h, x, y, w, hgt, true, "terra_amd_render_points_device", p, D ) ) return rc;
+    if ( !d_pixels || !d_results ) return fail ( kTerraAmdErrBadArgument, "null framebuffer pointer" );
+    p.pixels = ( float* ) d_pixels; p.results = d_results; p.rand_calls = ( uint32_t* ) d_rand_calls;
+    if ( d_rand_calls ) p.count_level = 2;
+    HIP_TRY ( hipSetDevice ( r.device ), kTerraAmdErrNoDevice );
+    if ( int lrc = launch_render ( s, p, r.device, ( hipStream_t ) stream, nullptr, nullptr, nullptr, d_points, &D ) ) return lrc;
+    account_launch ( s, p );
+    return 0;
+}
+// the host form: terra_amd_render_rays' staging, with the rectangle's points uploaded beside the running sums (rows of w records, addressed like the staging rectangle)
+extern "C" int terra_amd_render_points ( HTerraScene h, const TerraAmdPointSampling* ps, const TerraAmdPoint* points, const TerraFramebuffer* fb, size_t x, size_t y, size_t w, size_t hgt ) {
+    Scene* s = S ( h );
+    if ( !s->committed ) return scene_check ( s );
+    if ( !fb || !fb->pixels || !fb->results ) return fail ( kTerraAmdErrBadArgument, "null framebuffer" );
+    const Scene::Replica* r = &primary ( s );
+    DevRenderParams p; DevPointSampling D;
+    // (first pass: the checks alone, before the points are read)
+    if ( int rc = fill_point_params ( s, *r, ps, points, fb->width, fb->height, x, y, w, hgt, true, "terra_amd_render_points", p, D ) ) return rc;
+    if ( !point_positions_within ( s, points, fb->width, x, y, w, hgt ) )          // an active point beyond camera_limit: the replica traversal
+        if ( int rc = fill_point_params ( s, *r, ps, points, fb->width, fb->height, x, y, w, hgt, false, "terra_amd_render_points", p, D ) ) return rc;
+    if ( int rc = slot_prepare ( r->device, w * hgt ) ) return rc;
+    ThreadSlot& t = t_slot;
+    p.st_x = ( uint32_t ) x; p.st_y = ( uint32_t ) y; p.st_pitch = ( uint32_t ) w;
+    const size_t rpitch = fb->width * 16, ppitch = fb->width * 12;
+    const char* hres = ( const char* ) fb->results + ( y * fb->width + x ) * 16;
+    char* hpix = ( char* ) fb->pixels + ( y * fb->width + x ) * 12;
+    FrameCopy c;          // the points' device copy: freed when the call returns (after the stream has drained, below)
+    void* d_points = nullptr;
+    {
+        const hipError_t e = hipMalloc ( ( void** ) &c.d[0], w * hgt * sizeof ( TerraAmdPoint ) );
+        if ( e != hipSuccess ) { ( void ) hipGetLastError(); return fail ( kTerraAmdErrNoDevice, "point upload: %s", hipGetErrorString ( e ) ); }
+        d_points = c.d[0];
+    }
+    HIP_TRY ( hipMemcpy2DAsync ( d_points, w * sizeof ( TerraAmdPoint ), ( const char* ) points + ( y * fb->width + x ) * sizeof ( TerraAmdPoint ), fb->width * sizeof ( TerraAmdPoint ), w * sizeof ( TerraAmdPoint ), hgt, hipMemcpyHostToDevice, t.stream ), kTerraAmdErrLaunch );
+    HIP_TRY ( hipMemcpy2DAsync ( t.d_results, w * 16, hres, rpitch, w * 16, hgt, hipMemcpyHostToDevice, t.stream ), kTerraAmdErrLaunch );
+    p.pixels = ( float* ) t.d_pixels; p.results = t.d_results; p.rand_calls = nullptr;
+    int lrc = launch_render ( s, p, r->device, t.stream, &t, nullptr, nullptr, d_points, &D );
+    if ( !lrc ) {
+        HIP_TRY ( hipMemcpy2DAsync ( ( void* ) hres, rpitch, t.d_results, w * 16, w * 16, hgt, hipMemcpyDeviceToHost, t.stream ), kTerraAmdErrLaunch );
+        HIP_TRY ( hipMemcpy2DAsync ( hpix, ppitch, t.d_pixels, w * 12, w * 12, hgt, hipMemcpyDeviceToHost, t.stream ), kTerraAmdErrLaunch );
+    }
+    HIP_TRY ( hipStreamSynchronize ( t.stream ), kTerraAmdErrLaunch );          // (also on a failed launch: the upload above still reads the point copy)
+    if ( lrc ) return lrc;
+    account_launch ( s, p );
+    return 0;
+}
+// AOV forms: d_aov and d_points hold rows of st_pitch pixels whose first is pixel (st_x, st_y) of the frame
+static int render_aov_points_device ( HTerraScene h, const TerraAmdPointSampling* ps, const void* d_points, void* d_aov, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t hgt,
+                                      size_t st_x, size_t st_y, size_t st_pitch, bool origins_ok, void* stream, const char* what ) {
+    Scene* s = S ( h );
+    const Scene::Replica& r = primary ( s );
+    DevRenderParams p; DevPointSampling D;
+    if ( int rc = fill_point_params ( s, r, ps, d_points, fb_w, fb_h, x, y, w, hgt, origins_ok, what, p, D ) ) return rc;
+    if ( !d_aov ) return fail ( kTerraAmdErrBadArgument, "null AOV buffer" );
+    HIP_TRY ( hipSetDevice ( r.device ), kTerraAmdErrNoDevice );
+    p.st_x = ( uint32_t ) st_x; p.st_y = ( uint32_t ) st_y; p.st_pitch = ( uint32_t ) st_pitch;
+    return launch_aov ( s, p, d_aov, ( hipStream_t ) stream, nullptr, nullptr, d_points, &D );
+}
+extern "C" int terra_amd_render_aov_points_device ( HTerraScene h, const TerraAmdPointSampling* ps, const void* d_points, void* d_aov, size_t fb_w, size_t fb_h,
+                                                    size_t x, size_t y, size_t w, size_t hgt, void* stream ) {
+    return render_aov_points_device ( h, ps, d_points, d_aov, fb_w, fb_h, x, y, w, hgt, 0, 0, fb_w, true, stream, "terra_amd_render_aov_points_device" );
+}
+extern "C" int terra_amd_render_aov_points ( HTerraScene h, const TerraAmdPointSampling* ps, const TerraAmdPoint* points, TerraAmdAovResult* aov, size_t fb_w, size_t fb_h,
+                                             size_t x, size_t y, size_t w, size_t hgt ) {
+    Scene* s = S ( h );
+    DevRenderParams p; DevPointSampling D;          // (for the checks alone, before anything is staged: the device form fills its own)
+    if ( int rc = fill_point_params ( s, primary ( s ), ps, points, fb_w, fb_h, x, y, w, hgt, true, "terra_amd_render_aov_points", p, D ) ) return rc;
+    if ( !aov ) return fail ( kTerraAmdErrBadArgument, "null AOV buffer" );
+    HIP_TRY ( hipSetDevice ( primary ( s ).device ), kTerraAmdErrNoDevice );
+    const bool origins_ok = point_positions_within ( s, points, fb_w, x, y, w, hgt );
+    const FrameRect rect = { fb_w, x, y, w, hgt };
+    FrameCopy c;
+    hipError_t e = c.up_rect ( 0, aov, sizeof ( TerraAmdAovResult ), rect );
+    if ( e == hipSuccess ) e = c.up_rect ( 1, points, sizeof ( TerraAmdPoint ), rect );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "AOV upload: %s", hipGetErrorString ( e ) );
+    if ( int rc = render_aov_points_device ( h, ps, c.d[1], c.d[0], fb_w, fb_h, x, y, w, hgt, x, y, w, origins_ok, nullptr, "terra_amd_render_aov_points" ) ) return rc;
+    e = c.down_rect ( 0, aov, sizeof ( TerraAmdAovResult ), rect );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "AOV download: %s", hipGetErrorString ( e ) );
+    return 0;
+}
+// the scene's vertices as points: record 3 T + k = vertex k of the T-th triangle (objects in order, their triangles in order) with its TerraTriangleProperties
+// normal as stored. Host only. Returns the number of records whatever the capacity; writes the first min(capacity, records) of them
+extern "C" int terra_amd_scene_vertex_points ( HTerraScene h, TerraAmdPoint* out, int capacity ) {
+    Scene* s = S ( h );
+    if ( !s->committed ) return fail ( kTerraAmdErrNotCommitted, "scene not committed" );
+    size_t ntri = 0; for ( size_t j = 0; j < s->objects_pop; ++j ) ntri += s->objects[j].triangles_count;
+    if ( 3 * ntri > ( size_t ) 0x7fffffff ) return fail ( kTerraAmdErrBadArgument, "terra_amd_scene_vertex_points: %zu triangles: the record count does not fit an int", ntri );
+    size_t at = 0;
+    const size_t cap = ( out && capacity > 0 ) ? ( size_t ) capacity : 0;
+    for ( size_t j = 0; j < s->objects_pop && at < cap; ++j ) {
+        const TerraObject& o = s->objects[j];
+        for ( size_t t = 0; t < o.triangles_count && at < cap; ++t ) {
+            const TerraFloat3* v[3] = { &o.triangles[t].a, &o.triangles[t].b, &o.triangles[t].c };
+            const TerraFloat3* n[3] = { &o.properties[t].normal_a, &o.properties[t].normal_b, &o.properties[t].normal_c };
+            for ( int k = 0; k < 3 && at < cap; ++k, ++at ) {
+                TerraAmdPoint& q = out[at];
+                q.position[0] = v[k]->x; q.position[1] = v[k]->y; q.position[2] = v[k]->z; q.reserved = 0.f;
+                q.normal[0] = n[k]->x; q.normal[1] = n[k]->y; q.normal[2] = n[k]->z; q.reserved2 = 0.f;
+            }
+        }
+    }
+    return ( int ) ( 3 * ntri );
+}
+
 // terra_render() over the scene's device set from one process: device k renders the tiles t with t % N == k of the rectangle (terra_amd_shard_owner; the same kernels
 // with DevRenderParams::rank / world set) into its own staging frame, packs them, and ONE gather -- RCCL over xGMI, issued from here (multi_gpu.cpp) -- brings every
 // rank's packed tiles to the primary device, which unpacks them into its staging frame and copies the rectangle to the host once. The reference's client shards tiles over
@@ -2750,6 +2901,14 @@ extern "C" int terra_amd_unit_lens_rays ( const TerraCamera* cam, const TerraAmd
     p.jitter = jitter; p.fb_w = ( uint32_t ) fb_w; p.fb_h = ( uint32_t ) fb_h;
     Unit u; auto a = u.in ( xy2, 2 * ( size_t ) n ); auto b = u.in ( r4, 4 * ( size_t ) n ); auto o = u.out ( reinterpret_cast<float*> ( out_rays ), 8 * ( size_t ) n );
     return u.finish ( u.ok ? terra_unit_lens_rays ( p, L, n, a, b, o ) : hipSuccess );
+}
+extern "C" int terra_amd_unit_point_rays ( const TerraAmdPointSampling* ps, int n, const TerraAmdPoint* points, const float* g2, TerraAmdRay* out_rays ) {
+    DevPointSampling D;
+    if ( int rc = fill_point_sampling ( ps, "terra_amd_unit_point_rays", D ) ) return rc;
+    if ( n < 0 || ( n && ( !points || !g2 || !out_rays ) ) ) return fail ( kTerraAmdErrBadArgument, "terra_amd_unit_point_rays: null array or negative count" );
+    if ( need_device() ) return kTerraAmdErrNoDevice;
+    Unit u; auto a = u.in ( reinterpret_cast<const float*> ( points ), 8 * ( size_t ) n ); auto b = u.in ( g2, 2 * ( size_t ) n ); auto o = u.out ( reinterpret_cast<float*> ( out_rays ), 8 * ( size_t ) n );
+    return u.finish ( u.ok ? terra_unit_point_rays ( D, n, a, b, o ) : hipSuccess );
 }
 extern "C" int terra_amd_unit_tonemap ( int op, float gamma, int n, float* colors3 ) {
     if ( need_device() ) return kTerraAmdErrNoDevice;

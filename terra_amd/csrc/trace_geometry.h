@@ -30,12 +30,27 @@ TD V3 camera_sample ( const DevRenderParams& p, uint32_t px, uint32_t py, float 
     return camera_rotate ( p, d );
 }
 
+// concentric map of a pair of draws to the unit disk (include/terra_amd.h "Lens rendering" spells it out): the thin lens's aperture sample and the point door's
+// cosine-weighted direction both take it
+TD void concentric_disk ( float l1, float l2, float& u, float& v ) {
+    const float kPi2 = tdm_float ( 0x3FC90FDBu ), kPi4 = tdm_float ( 0x3F490FDBu );
+    const float a = 2 * l1 - 1, b = 2 * l2 - 1;
+    u = 0.f; v = 0.f;
+    if ( ! ( a == 0.f && b == 0.f ) ) {
+        float r, phi;
+        if ( fabsf ( a ) > fabsf ( b ) ) { r = a; phi = kPi4 * ( b / a ); }
+        else { r = b; phi = kPi2 - kPi4 * ( a / b ); }
+        float sp, cp; tdm_sincosf_pair ( phi, sp, cp );          // (each bit-identical to tdm_sinf / tdm_cosf: dev_math.h)
+        u = r * cp; v = r * sp;
+    }
+}
+
 // The ray of a lens launch's sample (include/terra_amd.h "Lens rendering" is the definition): the one generator of the render kernels' lens instances,
 // the lens AOV kernel and the unit entry. (l1, l2): the lens pair, looked at only where lens_draws -- the caller draws it from stream A then, after the sampler
 // integration's pair, and passes anything otherwise. L is a launch constant: every branch on it is wave-uniform.
 TD bool lens_draws ( const DevLens& L ) { return L.model == 0 && L.lens_radius > 0.f; }
 TD void lens_sample ( const DevRenderParams& p, const DevLens& L, uint32_t px, uint32_t py, float r1, float r2, float l1, float l2, V3& ro, V3& rd ) {
-    const float kPi = tdm_float ( 0x40490FDBu ), kPi2 = tdm_float ( 0x3FC90FDBu ), kPi4 = tdm_float ( 0x3F490FDBu );
+    const float kPi = tdm_float ( 0x40490FDBu ), kPi2 = tdm_float ( 0x3FC90FDBu );
     float sx, sy; camera_film ( p, px, py, r1, r2, sx, sy );
     const V3 pos = v3 ( p.cam_pos[0], p.cam_pos[1], p.cam_pos[2] );
     float Lx = 0.f, Ly = 0.f;          // the origin's offset in the lens / film plane (models 0 with a lens, 1)
@@ -45,16 +60,7 @@ TD void lens_sample ( const DevRenderParams& p, const DevLens& L, uint32_t px, u
         const float fy = sy * p.tan_half_fov;
         const V3 d = normalize ( v3 ( fx, fy, 1.f ) );
         if ( L.lens_radius > 0.f ) {
-            // concentric map of the pair to the unit disk
-            const float a = 2 * l1 - 1, b = 2 * l2 - 1;
-            float u = 0.f, v = 0.f;
-            if ( ! ( a == 0.f && b == 0.f ) ) {
-                float r, phi;
-                if ( fabsf ( a ) > fabsf ( b ) ) { r = a; phi = kPi4 * ( b / a ); }
-                else { r = b; phi = kPi2 - kPi4 * ( a / b ); }
-                float sp, cp; tdm_sincosf_pair ( phi, sp, cp );          // (each bit-identical to tdm_sinf / tdm_cosf: dev_math.h)
-                u = r * cp; v = r * sp;
-            }
+            float u, v; concentric_disk ( l1, l2, u, v );
             Lx = L.lens_radius * u; Ly = L.lens_radius * v; shifted = true;
             const float t = L.focus_distance / d.z;
             const V3 F = v3 ( d.x * t, d.y * t, d.z * t );          // where the pinhole ray meets the plane in focus
@@ -73,6 +79,38 @@ TD void lens_sample ( const DevRenderParams& p, const DevLens& L, uint32_t px, u
         else { float st, ct; tdm_sincosf_pair ( theta, st, ct ); rd = camera_rotate ( p, v3 ( ( st * ux ) / rr, ( st * uy ) / rr, ct ) ); }
     }
     ro = shifted ? v3 ( pos.x + ( p.cam_rot[0] * Lx + p.cam_rot[1] * Ly ), pos.y + ( p.cam_rot[3] * Lx + p.cam_rot[4] * Ly ), pos.z + ( p.cam_rot[6] * Lx + p.cam_rot[7] * Ly ) ) : pos;
+}
+
+// The ray of a point launch's sample (include/terra_amd.h "Point rendering" is the definition): the one generator of the render kernels' point instances,
+// the point AOV kernel and the unit entry. pos / nrm: the pixel's TerraAmdPoint as stored (the normal not normalised); (g1, g2): the pair the caller draws from
+// stream A after the sampler integration's. S is a launch constant: the branch on it is wave-uniform.
+// an inactive point traces nothing: a component that is not finite, or a normal whose squared length is 0 (exactly, or by underflow) or not finite
+TD bool point_inactive ( V3 pos, V3 nrm ) {
+    const bool finite = fabsf ( pos.x ) < INFINITY && fabsf ( pos.y ) < INFINITY && fabsf ( pos.z ) < INFINITY && fabsf ( nrm.x ) < INFINITY && fabsf ( nrm.y ) < INFINITY && fabsf ( nrm.z ) < INFINITY;      // (false for a NaN too)
+    const float q = nrm.x * nrm.x + nrm.y * nrm.y + nrm.z * nrm.z;
+    return !finite || ! ( q > 0.f && q < INFINITY );
+}
+TD void point_sample ( const DevPointSampling& S, V3 pos, V3 nrm, float g1, float g2, V3& ro, V3& rd ) {
+    const V3 n = normalize ( nrm );
+    // the branch-free orthonormal basis of Duff et al. 2017 (make_basis keeps the reference's unnormalised tangent, which would skew the distribution)
+    const float s = copysignf ( 1.f, n.z );
+    const float a = -1.f / ( s + n.z );
+    const float b = ( n.x * n.y ) * a;
+    const V3 t = v3 ( 1.f + ( s * ( n.x * n.x ) ) * a, s * b, ( -s ) * n.x );
+    const V3 bt = v3 ( b, s + ( n.y * n.y ) * a, -n.y );
+    float x, y, z;
+    if ( S.distribution == 0 ) {
+        concentric_disk ( g1, g2, x, y );
+        z = sqrtf ( fmaxf ( 0.f, ( 1.f - x * x ) - y * y ) );
+    } else {
+        z = 1.f - 2 * g1;
+        const float r = sqrtf ( fmaxf ( 0.f, 1.f - z * z ) );
+        const float phi = tdm_float ( 0x40C90FDBu ) * g2;          // 2 PI
+        float sp, cp; tdm_sincosf_pair ( phi, sp, cp );
+        x = r * cp; y = r * sp;
+    }
+    rd = normalize ( v3 ( ( x * t.x + y * bt.x ) + z * n.x, ( x * t.y + y * bt.y ) + z * n.y, ( x * t.z + y * bt.z ) + z * n.z ) );
+    ro = pos;
 }
 
 // -----------------------------------------------------------------------------

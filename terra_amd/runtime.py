@@ -144,6 +144,7 @@ _EXTRA = {
     **api.RAY_QUERY_SIGNATURES,
     **api.RAY_SOURCE_SIGNATURES,
     **api.LENS_SIGNATURES,
+    **api.POINT_SIGNATURES,
     **api.EXACT_SQRT_SIGNATURES,
 }
 
@@ -536,6 +537,105 @@ def radiance(lib, scene, rays, batches: int = 1):
         acc = res[..., :3].view(torch.float32)
         samples = res[..., 3:4].to(torch.float32)
         return unfold_pixels(acc / samples, n).contiguous()
+
+
+# ---------------------------------------------------------------------------
+# point rendering (include/terra_amd.h "Point rendering")
+# ---------------------------------------------------------------------------
+
+def point_sampling(distribution: int = 0) -> api.PointSampling:
+    """api.PointSampling with `distribution` (0 cosine-weighted hemisphere about the normal, 1 uniform sphere)"""
+    ps = api.PointSampling()
+    ps.distribution = distribution
+    return ps
+
+
+def _frame_points(points, width: int, height: int):
+    import torch
+    if not (isinstance(points, torch.Tensor) and points.is_cuda and points.dtype == torch.float32 and points.is_contiguous() and tuple(points.shape) == (height, width, 8)):
+        raise TerraAmdError(f"point calls take a contiguous float32 tensor [{height}, {width}, 8] on the scene's device: one api.POINT_DTYPE record per pixel of the frame")
+    if points.data_ptr() % 16:
+        raise TerraAmdError("the point buffer must be 16-byte aligned")
+
+
+def render_points_device(lib, scene, sampling: api.PointSampling, points, fb: DeviceFramebuffer, rect: Optional[Tuple[int, int, int, int]] = None, rand_calls=None, stream=None):
+    """terra_amd_render_points_device: the render call with every sample's primary ray drawn about the pixel's point (float32 [fb.height, fb.width, 8] in HBM:
+    TerraAmdPoint records)"""
+    _frame_points(points, fb.width, fb.height)
+    x, y, w, h = rect if rect else (0, 0, fb.width, fb.height)
+    check(lib.render_points_device(scene, C.byref(sampling), points.data_ptr(), fb.pixels.data_ptr(), fb.results.data_ptr(), fb.width, fb.height, x, y, w, h,
+                                   rand_calls.data_ptr() if rand_calls is not None else None, stream), "terra_amd_render_points_device")
+
+
+def render_aov_points_device(lib, scene, sampling: api.PointSampling, points, aov: DeviceAov, rect: Optional[Tuple[int, int, int, int]] = None, stream=None):
+    """terra_amd_render_aov_points_device: the AOV pass of a render_points_device call (points as there); with distribution 0, 1 - coverage / samples is ambient occlusion"""
+    _frame_points(points, aov.width, aov.height)
+    x, y, w, h = rect if rect else (0, 0, aov.width, aov.height)
+    check(lib.render_aov_points_device(scene, C.byref(sampling), points.data_ptr(), aov.data.data_ptr(), aov.width, aov.height, x, y, w, h, stream), "terra_amd_render_aov_points_device")
+
+
+def point_rays(lib, sampling: api.PointSampling, points, g2) -> np.ndarray:
+    """terra_amd_unit_point_rays: the device's generator on arrays. points: n api.POINT_DTYPE records (or float32 [n, 8]), g2 [n, 2] = (g1, g2); returns n
+    api.RAY_DTYPE records (tmax FLT_MAX, reserved 0; all zero for an inactive point), which the ray door takes as they are"""
+    pts = np.ascontiguousarray(points)
+    pts = np.ascontiguousarray(pts.view(np.float32) if pts.dtype == api.POINT_DTYPE else pts.astype(np.float32, copy=False)).reshape(-1, 8)
+    g2 = np.ascontiguousarray(g2, dtype=np.float32).reshape(-1, 2)
+    if len(pts) != len(g2):
+        raise TerraAmdError("point_rays: one (g1, g2) per point")
+    out = np.zeros(len(pts), dtype=api.RAY_DTYPE)
+    check(lib.unit_point_rays(C.byref(sampling), len(pts), pts.ctypes.data, g2.ctypes.data, out.ctypes.data), "terra_amd_unit_point_rays")
+    return out
+
+
+def scene_vertex_points(lib, scene) -> np.ndarray:
+    """terra_amd_scene_vertex_points: the committed scene's vertices as api.POINT_DTYPE records, record 3 T + k = vertex k of triangle T with its stored normal"""
+    n = check(lib.scene_vertex_points(scene, None, 0), "terra_amd_scene_vertex_points")
+    out = np.zeros(n, dtype=api.POINT_DTYPE)
+    if n:
+        check(lib.scene_vertex_points(scene, out.ctypes.data, n), "terra_amd_scene_vertex_points")
+    return out
+
+
+def fold_points(positions, normals, xp=np):
+    """n points ([n, 3] positions, [n, 3] normals) -> a frame [height, 256, 8] of TerraAmdPoint records (radiance_frame_shape), point i at pixel (i % 256, i // 256),
+    padded with inactive points (all zero: a zero normal). xp is numpy, or torch for tensors (which stay on their device)."""
+    n = int(positions.shape[0])
+    h, w = radiance_frame_shape(n)
+    if xp is np:
+        frame = np.zeros((h * w, 8), dtype=np.float32)
+    else:
+        frame = xp.zeros((h * w, 8), dtype=xp.float32, device=positions.device)
+    frame[:n, 0:3] = positions
+    frame[:n, 4:7] = normals
+    return frame.reshape(h, w, 8)
+
+
+def irradiance(lib, scene, positions, normals, spp_batches: int = 1, distribution: int = 0):
+    """Irradiance at n points (float32 [n, 3] positions and normals in HBM) -> float32 [n, 3]: the points folded into a frame 256 pixels wide, `spp_batches`
+    render_points_device calls of the scene's samples_per_pixel each, PI * acc / samples (an inactive point's is 0). With distribution 1 the same factor is applied to
+    the probe's mean radiance over the sphere. Queued on the current torch stream; nothing goes through the host."""
+    import math
+    import torch
+    for t in (positions, normals):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] == 3):
+            raise TerraAmdError("irradiance takes float32 tensors [n, 3] on the scene's device: the points' positions and normals")
+    if positions.shape[0] != normals.shape[0] or positions.device != normals.device:
+        raise TerraAmdError("irradiance: one normal per position, on the same device")
+    stream = torch.cuda.current_stream(positions.device).cuda_stream or None
+    if spp_batches < 1:
+        raise TerraAmdError("irradiance: spp_batches must be at least 1")
+    n = positions.shape[0]
+    frame = fold_points(positions, normals, torch)
+    h, w = frame.shape[0], frame.shape[1]
+    ps = point_sampling(distribution)
+    with torch.cuda.device(positions.device):
+        fb = DeviceFramebuffer(w, h, device=positions.device)
+        for _ in range(spp_batches):
+            render_points_device(lib, scene, ps, frame, fb, stream=stream)
+        res = fb.results.view(h, w, 4)
+        acc = res[..., :3].view(torch.float32)
+        samples = res[..., 3:4].to(torch.float32)
+        return unfold_pixels(acc / samples * math.pi, n).contiguous()
 
 
 def render_device_sharded(lib, cam, scene, fb: DeviceFramebuffer, tile: int, rank: int, world: int, stream=None):

@@ -4,6 +4,7 @@
 hipError_t terra_launch_render ( const DevRenderParams&, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_launch_render_rays ( const DevRenderParams&, const void*, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_launch_render_lens ( const DevRenderParams&, const DevLens&, hipStream_t ) { return hipErrorNoDevice; }
+hipError_t terra_launch_render_points ( const DevRenderParams&, const void*, const DevPointSampling&, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_launch_job_streams ( const DevRenderParams&, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_launch_block_order ( const DevRenderParams&, uint32_t*, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_fill_sincos24 ( float2*, hipStream_t ) { return hipErrorNoDevice; }
@@ -35,6 +36,8 @@ hipError_t terra_launch_aov ( DevRenderParams, void*, hipStream_t ) { return hip
 hipError_t terra_launch_aov_rays ( DevRenderParams, const void*, void*, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_launch_aov_lens ( DevRenderParams, const DevLens&, void*, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_unit_lens_rays ( const DevRenderParams&, const DevLens&, int, const uint32_t*, const float*, float* ) { return hipErrorNoDevice; }
+hipError_t terra_launch_aov_points ( DevRenderParams, const void*, const DevPointSampling&, void*, hipStream_t ) { return hipErrorNoDevice; }
+hipError_t terra_unit_point_rays ( const DevPointSampling&, int, const float*, const float*, float* ) { return hipErrorNoDevice; }
 hipError_t terra_launch_denoise ( const void*, const void*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, int, float, int, float, float*, float*, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_launch_moments_accumulate ( const void*, void*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_launch_tile_error ( const void*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, float*, hipStream_t ) { return hipErrorNoDevice; }
