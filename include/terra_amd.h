@@ -247,6 +247,14 @@ int  terra_amd_leaf_box_info ( HTerraScene scene, uint32_t out[2] );
 int  terra_amd_set_leaf_pairs ( HTerraScene scene, int on );
 int  terra_amd_get_leaf_pairs ( HTerraScene scene );
 int  terra_amd_leaf_pair_info ( HTerraScene scene, uint32_t out[2] );
+/* Nearest first (default on). A pair-form launch that also runs the flat leaf-box test keeps, per ray, the two smallest entry distances among the boxes the ray
+   passes. Its leaf loop then tests the pair of the nearest box first and drops every pair whose box the ray enters strictly beyond the closest hit found: a triangle
+   lies beyond the entry distance of its own box, so such a pair can neither be closer nor win a tie (DESIGN.md 3.1 "Nearest first"). Shadow rays skip the loop when
+   their expected hit lies in front of every box passed. The image is the same bit for bit (tests/test_leaf_nearest_gpu.py). Used only where no two pairs share a
+   leaf box (an exactly duplicated quad switches it off for its scene); every other launch -- the walk, the single form, counting launches -- is as with the switch
+   off. A launch parameter: no commit needed. */
+int  terra_amd_set_leaf_nearest_first ( HTerraScene scene, int on );
+int  terra_amd_get_leaf_nearest_first ( HTerraScene scene );
 
 /* Environment lighting, off by default. The reference evaluates scene options' environment_map for a ray
    that leaves the scene, multiplies the throughput by it and then drops the result: the line that would

@@ -154,6 +154,7 @@ static_assert ( terra_pair_box_plane_offset ( 7, 0, 0 ) == 336 && terra_pair_box
 static_assert ( terra_pair_section_bytes ( TERRA_LEAF_RANK_MAX / 2 ) + TERRA_SHADE_CONSTS_BYTES * TERRA_LEAF_RANK_MAX <= 6u * TERRA_RANKED_ENTRY_BYTES * TERRA_LEAF_RANK_MAX
                 && terra_pair_section_bytes ( 1 ) + TERRA_SHADE_CONSTS_BYTES * 2u <= 6u * TERRA_RANKED_ENTRY_BYTES * 2u, "pair section + shading constants fit where the plan budgeted ranked entries" );
 static_assert ( terra_pair_section_bytes ( TERRA_LEAF_RANK_MAX / 2 ) <= 6u * TERRA_RANKED_ENTRY_BYTES * TERRA_LEAF_RANK_MAX && terra_pair_section_bytes ( 1 ) <= 6u * TERRA_RANKED_ENTRY_BYTES * 2u, "the pair section never takes more LDS than the ranked entries it replaces" );
+#define TERRA_LEAF_PAIRS_NEAREST 1u          // DevRenderParams::leaf_pairs, lowest bit: nearest first (the distance itself is a multiple of 4)
 // a record key of the pair loop: (rank + 1) << 5 | soup triangle -- ordered as the ranks are, 0 = no hit, the triangle in its low five bits
 constexpr uint32_t terra_pair_key ( uint32_t rank, uint32_t tri ) { return ( rank + 1u ) << 5 | tri; }
 static_assert ( TERRA_LEAF_RANK_MAX <= 32, "a pair key keeps the triangle in five bits" );
@@ -324,6 +325,9 @@ struct DevRenderParams {
     // fan inside one leaf box stages the pairs (dev_types.h "pair form": the table in the scene blob) and its leaf loop tests both triangles of a pair in one trip.
     // The table's distance in bytes from scene.tris, inside the same blob; 0 = none. (A 32-bit word in what was padding: the structure keeps its size, so the kernels
     // that never read it keep their argument offsets.)
+    // Nearest first (traverse_ref.h "Nearest first"; terra_amd_set_leaf_nearest_first): the table is 4-byte aligned in the blob, so the distance's lowest bit is free:
+    // TERRA_LEAF_PAIRS_NEAREST set = the launch's flat lanes test their nearest box's entry first and drop the entries beyond the record. The host sets it only beside a
+    // table of distinct leaf boxes in which box k holds exactly entry k.
     uint32_t leaf_pairs;
     // 1.f / (float) fb_w, 1.f / (float) fb_h, correctly rounded on the host (fill_camera): camera_sample's two divisions by the frame size take them through div_exact_rk
     // (exact_div.h). No padding was left: the record grows by 8 bytes, at its end, so every other field -- and the argument offsets of the kernels that read no camera --

@@ -76,7 +76,7 @@ TD void wave_flush_counters ( const Counters& c, unsigned long long* g ) {
 #endif
 // DevRenderParams::leaf_pairs as a pointer (nullptr: the launch has no pair form)
 TD const uint32_t* terra_leaf_pair_table ( const DevRenderParams& p ) {
-    return p.leaf_pairs ? reinterpret_cast<const uint32_t*> ( reinterpret_cast<const char*> ( p.scene.tris ) + p.leaf_pairs ) : nullptr;
+    return p.leaf_pairs ? reinterpret_cast<const uint32_t*> ( reinterpret_cast<const char*> ( p.scene.tris ) + ( p.leaf_pairs & ~TERRA_LEAF_PAIRS_NEAREST ) ) : nullptr;
 }
 template <int MODE>
 TD Tracer make_tracer ( const DevScene& sc, float4* lds, uint32_t stack_depth, uint32_t leaf_cap, uint32_t lds_nodes, uint32_t lds_tris, bool cull, bool fused, bool ranked,
@@ -583,6 +583,8 @@ __global__ __launch_bounds__ ( 256, terra_waves ( INTEGRATOR, KINDS, MODE ) ) vo
     extern __shared__ float4 lds_f4[];
     const int tid = threadIdx.x;
     Tracer T0 = make_tracer<MODE> ( p.scene, lds_f4, p.stack_depth, p.leaf_cap, p.lds_nodes, p.lds_tris, p.leaf_cull != 0, p.fused_slab != 0, p.leaf_rank != 0, p.leaf_boxes, p.n_leaf_boxes, terra_leaf_pair_table ( p ) );
+    // nearest first (traverse_ref.h "Nearest first"): set here, for the instances that can take the pair form alone -- as a parameter of make_tracer it moved two registers of every other instance
+    if constexpr ( MODE == 1 && COUNT == 0 ) T0.nearest = T0.pairs && T0.n_boxes != 0u && ( p.leaf_pairs & TERRA_LEAF_PAIRS_NEAREST ) != 0u;
     T0.faults = p.counters + kCtrFaults;
     if ( MODE >= 2 && p.stack_spill ) { T0.spill = p.stack_spill + ( size_t ) ( blockIdx.x * 256u + threadIdx.x ) * p.spill_cap; T0.spill_cap = p.spill_cap; }
     const Tracer T = T0;

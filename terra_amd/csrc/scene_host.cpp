@@ -379,6 +379,8 @@ struct Scene {
     int leaf_pair_form = 1;             // terra_amd_set_leaf_pairs: ranked launches without work counters of a scene that has the pair form test a quad's two triangles in one trip (traverse_ref.h "Pair form")
     std::vector<uint32_t> leaf_pairs;   // the pair table of the last commit as uploaded in the blob (leaf_pair_table; empty: the scene has no pair form)
     std::atomic<uint32_t> pairs_last { 0 };     // terra_amd_leaf_pair_info: 1 when the most recent launch used the pair form
+    int leaf_nearest_first = 1;         // terra_amd_set_leaf_nearest_first: flat pair-form launches test a lane's nearest box first and drop the entries beyond the record (traverse_ref.h "Nearest first")
+    bool pair_per_box = false;          // the pair table of the last commit has box k hold exactly entry k (leaf_pairs_one_per_box): what nearest first numbers its keys by
     bool sampler_integration = false;   // terra_amd_set_sampler_integration: the pixel's Halton / stratified sampler feeds the first bounce (a launch parameter)
     std::string commit_error;
     std::atomic<bool> warned_camera { false };      // the per-call fallback (camera outside camera_limit) has been reported on stderr once
@@ -529,6 +531,11 @@ extern "C" int terra_amd_set_leaf_pairs ( HTerraScene h, int on ) {
     S ( h )->leaf_pair_form = on; return 0;
 }
 extern "C" int terra_amd_get_leaf_pairs ( HTerraScene h ) { return S ( h )->leaf_pair_form; }
+extern "C" int terra_amd_set_leaf_nearest_first ( HTerraScene h, int on ) {
+    if ( on < 0 || on > 1 ) return fail ( kTerraAmdErrBadArgument, "terra_amd_set_leaf_nearest_first: 0 (off) or 1 (on)" );
+    S ( h )->leaf_nearest_first = on; return 0;
+}
+extern "C" int terra_amd_get_leaf_nearest_first ( HTerraScene h ) { return S ( h )->leaf_nearest_first; }
 // the predicate of empty_proof.h on the host (tests, tools): 1 when the block of pixels [x0, x1) x [y0, y1) is proved empty against n_tris triangles of 9 floats each
 extern "C" int terra_amd_empty_proof ( const float* cam_rot9, const float* cam_pos3, float tan_half_fov, float aspect, float jitter, uint32_t fb_w, uint32_t fb_h,
                                        uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, const float* tris9, size_t n_tris ) {
@@ -751,6 +758,13 @@ static std::vector<uint32_t> leaf_pair_table ( const std::vector<DevLeafBox>& bo
         t[terra_leaf_pair_words_masks ( ( uint32_t ) ntri ) + box_of_pair[order[e]]] |= 1u << e;
     }
     return t;
+}
+// Does box k of the table hold exactly entry k? (Boxes are ordered by their lowest rank, entries by theirs: true whenever no two pairs share a box -- the Cornell
+// box; false for an exactly duplicated quad.) The flat loop of a nearest-first launch numbers a box's key by the box (traverse_ref.h "Nearest first").
+static bool leaf_pairs_one_per_box ( const std::vector<uint32_t>& table, size_t n_boxes, size_t ntri ) {
+    if ( table.empty() || n_boxes * 2 != ntri ) return false;
+    for ( size_t k = 0; k < n_boxes; ++k ) if ( table[terra_leaf_pair_words_masks ( ( uint32_t ) ntri ) + k] != 1u << k ) return false;
+    return true;
 }
 
 // ---- reachability tables (DevScene::ref_replay / fast_leaf_parent / fast_leaf_mask) -------------------------------------------------------------
@@ -1310,6 +1324,7 @@ static int commit_scene ( Scene* s, int device ) {
     // ... and, where every triangle is half of a fan inside one of those boxes, the pairs a ranked launch tests in one trip each (terra_amd_scene_leaf_pairs)
     f.leaf_pairs = leaf_pair_table ( f.leaf_boxes, f.tris, f.ntri );
     s->leaf_pairs = f.leaf_pairs;
+    s->pair_per_box = leaf_pairs_one_per_box ( f.leaf_pairs, f.leaf_boxes.size(), f.ntri );
     FastTree ft;
     if ( c.use_fast && !c.fast_on_device ) { if ( int rc = build_fast_tree_host ( s, c, f, ft ) ) return rc; }
     // The automatic mode's fallbacks are correct and 10-20 x slower on scenes of this size (hall: 110 against 2,400 Msamples/s): say so where a client looks, once per commit.
@@ -1594,6 +1609,8 @@ static int fill_params ( Scene* s, const Scene::Replica& r, const TerraCamera* c
     // launch walks the tree and the staged nodes carry entry bits
     p.leaf_pairs = 0;
     if ( s->leaf_pair_form && r.d_blob && !s->leaf_pairs.empty() && p.lds_mode == 1 && p.leaf_rank ) p.leaf_pairs = ( uint32_t ) ( s->blob.sec[kSecLeafPairs].offset - s->blob.sec[kSecTris].offset );      // (both in the blob; scenes of at most 32 triangles: a few KB apart)
+    // nearest first: a pair launch that also runs the flat test, of a table in which box k holds entry k; the switch rides in the distance's lowest bit (sections are 16-byte aligned)
+    if ( p.leaf_pairs && ! ( p.leaf_pairs & 3u ) && p.n_leaf_boxes && s->leaf_nearest_first && s->pair_per_box ) p.leaf_pairs |= TERRA_LEAF_PAIRS_NEAREST;
     // the azimuth table pays where VALU issue binds (LDS-resident scenes: Cornell Simple 65.8 -> 64.2 ms, Direct 145.2 -> 142.5); the kernels that wait on memory anyway
     // lose by one more dependent load per shaded hit (sphere scene 395 -> 419 ms, hall 282 -> 284; profiles/r03_measurements/ab_sincos_table.log;
     // fast-tree launches alone: hall 218.9 -> 219.6 ms, sphere scene 318.6 -> 321.1, profiles/r04_measurements/ab_fast_node_formats.log)

@@ -118,6 +118,9 @@ struct Tracer {
     bool ranked;
     // ... and the ranked entries are pairs (see "Pair form" above); launch constant, only ever set in launches without work counters
     bool pairs;
+    // ... and a lane of a flat pair-form launch tests the entry of its nearest box first and drops the entries beyond the record (traverse_pairs "Nearest first";
+    // terra_amd_set_leaf_nearest_first); launch constant, only ever set where box k holds exactly entry k
+    bool nearest = false;
 };
 // The Tracer of a launch that stages nothing (the AOV, query and unit kernels): the scene read from HBM; words = the block's stack_depth stack entries, then leaf_cap
 // leaf-list entries, each 256 ints; spill = the HBM part of the launch's fast-tree stacks, spill_cap words per lane of the grid, lane blockIdx.x * 256 + threadIdx.x's
@@ -255,29 +258,47 @@ TD void leaf_step ( const Tracer& T, const int* entry, const RayState& st, V3 o_
 // dynamic LDS segment + offset", which it otherwise keeps apart to re-add the segment's start (the constant 0) in front of every read. The masks are wave-uniform:
 // their address is scalar arithmetic, one move into the address register per trip.
 // The 32-bit LDS address of a staged word is the low half of its generic pointer (the shared aperture's base has no low bits; the compiler's own cast to
-// address space 3 takes the same half, and Tracer::stack_lim is formed the same way). The asm statements serve speed only: without them the code is as right
-// and a few instructions longer, and nothing fails -- after a compiler upgrade read the trip counts again (python tools/isa_cost.py --loops: 96 / 50 / 16).
+// address space 3 takes the same half, and Tracer::stack_lim is formed the same way). The empty asm statements serve speed only: without them the code is as right
+// and a few instructions longer, and nothing fails -- after a compiler upgrade read the trip counts again (python tools/isa_cost.py --loops: 96 / 50 / 16; the pair
+// form with its four key instructions per box: 128 / 66 / 21). The one asm statement that is not empty, leaf_box_test's v_bfi_b32, computes: it IS (te & ~31) | entry.
 typedef float PlanePair __attribute__ (( ext_vector_type ( 2 ) ));          // (a built-in vector: the host pass, too, can read one through an LDS pointer)
 typedef const __attribute__ (( address_space ( 3 ) )) PlanePair* LdsPlanes;
-TD void leaf_box_test ( uint32_t bx, uint32_t by, uint32_t bz, const char* pm, const Ray& r, const SlabSel& sel, uint32_t& leaf_set, Counters& c ) {
+// Nearest first (PAIRS only; "Nearest first" below): lo / hi = the smallest and second-smallest key among the boxes the lane passes, key = the bits of the box's entry
+// distance with the low five replaced by the box's number `entry` (wave-uniform: the scalar operand of one v_bfi_b32; below 32), TERRA_NO_BOX for a box it misses.
+// Compared as SIGNED words: an entry distance is >= +0 or is -0, and -0 then sorts first and fails the cut as a float bound -- the safe side both times.
+#define TERRA_NO_BOX 0x7fffffff
+struct NearestBoxes { int32_t lo, hi; };
+template <bool PAIRS>
+TD void leaf_box_test ( uint32_t bx, uint32_t by, uint32_t bz, const char* pm, const Ray& r, const SlabSel& sel, uint32_t& leaf_set, Counters& c, uint32_t entry, NearestBoxes& nb ) {
     PS_WAVE ( c, kPsNodeIter ); PS_LANE ( c, kPsNodeLanes );
     const PlanePair ax = * ( LdsPlanes ) ( uintptr_t ) bx, ay = * ( LdsPlanes ) ( uintptr_t ) by, az = * ( LdsPlanes ) ( uintptr_t ) bz;
     const uint32_t m = *reinterpret_cast<const uint32_t*> ( pm );          // (read whether or not the box is hit: a select, not a branch around a load)
     float te;
     const bool hit = slab_near_far_fused ( ax.x, ax.y, ay.x, ay.y, az.x, az.y, r, sel.oi, te );
     leaf_set |= hit ? m : 0u;
+    if constexpr ( PAIRS ) {
+        // (te & ~31) | entry as one instruction: a bit-field insert under the inline constant 31 with the entry as its one scalar operand. Written out, the compiler
+        // takes a v_and_b32 with the literal ~31 and a v_or3_b32 -- or, asked for the insert in C, holds ~31 in a scalar and moves every entry to a vector register.
+        uint32_t bits;
+        asm ( "v_bfi_b32 %0, 31, %1, %2" : "=v" ( bits ) : "s" ( entry ), "v" ( te ) );
+        const int32_t key = hit ? ( int32_t ) bits : TERRA_NO_BOX;
+        const int32_t lo = nb.lo, hi = nb.hi;
+        nb.lo = key < lo ? key : lo;
+        nb.hi = __builtin_elementwise_max ( __builtin_elementwise_min ( lo, hi ), __builtin_elementwise_min ( __builtin_elementwise_max ( lo, hi ), key ) );      // (v_med3_i32: with lo <= hi the median is the second smallest of the three)
+    }
 }
 // N boxes at immediate offsets from the bases, which then move on to the next box. STRIDE: from a box's plane pairs to the next one's, in the form in use
-template <int N, uint32_t STRIDE>
-TD void leaf_box_group ( uint32_t& bx, uint32_t& by, uint32_t& bz, const char*& pm, const Ray& r, const SlabSel& sel, uint32_t& leaf_set, Counters& c ) {
+template <int N, uint32_t STRIDE, bool PAIRS>
+TD void leaf_box_group ( uint32_t& bx, uint32_t& by, uint32_t& bz, const char*& pm, const Ray& r, const SlabSel& sel, uint32_t& leaf_set, Counters& c, uint32_t& entry, NearestBoxes& nb ) {
     #pragma unroll
     for ( int k = 0; k < N; ++k )
-        leaf_box_test ( bx + STRIDE * k, by + STRIDE * k, bz + STRIDE * k, pm + TERRA_LEAF_BOX_MASK_STRIDE * k, r, sel, leaf_set, c );
+        leaf_box_test<PAIRS> ( bx + STRIDE * k, by + STRIDE * k, bz + STRIDE * k, pm + TERRA_LEAF_BOX_MASK_STRIDE * k, r, sel, leaf_set, c, entry + ( uint32_t ) k, nb );
     bx += STRIDE * N; by += STRIDE * N; bz += STRIDE * N; pm += TERRA_LEAF_BOX_MASK_STRIDE * N;
+    if constexpr ( PAIRS ) entry += ( uint32_t ) N;
 }
 // PAIRS: the table lies in the pair section's own part (dev_types.h "pair form") and its masks are in entry bits; otherwise in the pad words of the ranked entries
 template <bool PAIRS>
-TD uint32_t leaf_boxes_flat ( const Tracer& T, const Ray& r, const SlabSel& sel, Counters& c ) {
+TD uint32_t leaf_boxes_flat ( const Tracer& T, const Ray& r, const SlabSel& sel, Counters& c, NearestBoxes& nb ) {
     constexpr uint32_t kStride = PAIRS ? ( uint32_t ) TERRA_PAIR_BOX_STRIDE : ( uint32_t ) TERRA_LEAF_BOX_STRIDE;
     constexpr uint32_t kX = PAIRS ? terra_pair_box_plane_offset ( 0, 0, 0 ) : terra_leaf_box_plane_offset ( 0, 0, 0 ), kY = PAIRS ? terra_pair_box_plane_offset ( 0, 1, 0 ) : terra_leaf_box_plane_offset ( 0, 1, 0 ),
                        kZ = PAIRS ? terra_pair_box_plane_offset ( 0, 2, 0 ) : terra_leaf_box_plane_offset ( 0, 2, 0 );
@@ -288,15 +309,16 @@ TD uint32_t leaf_boxes_flat ( const Tracer& T, const Ray& r, const SlabSel& sel,
     uint32_t bx = table + kX + sx, by = table + kY + sy, bz = table + kZ + sz;
     asm ( "" : "+v" ( bx ), "+v" ( by ), "+v" ( bz ) );
     const char* pm = reinterpret_cast<const char*> ( T.l_props ) + terra_leaf_box_mask_offset ( 0 );
-    uint32_t leaf_set = 0u;
+    uint32_t leaf_set = 0u, entry = 0u;
+    if constexpr ( PAIRS ) nb.lo = nb.hi = TERRA_NO_BOX;
     // one group at a time, as written. Cross-compiled for gfx950 without these pragmas (profiles/leaf_boxes/kernel_resources.md): left to unroll, the loads of
     // several groups are hoisted together and the Simple kernel takes 1,728 B of scratch; vectorised two groups wide, the tests become v_pk_fma_f32 fed by moves
     // (104 B of scratch; build.py on why the build keeps packed arithmetic out). With them: no scratch
     #pragma clang loop vectorize(disable) interleave(disable) unroll(disable)
-    for ( uint32_t g = T.n_boxes / TERRA_LEAF_BOX_GROUP; g != 0; --g ) leaf_box_group<TERRA_LEAF_BOX_GROUP, kStride> ( bx, by, bz, pm, r, sel, leaf_set, c );
-    if ( T.n_boxes & 4u ) leaf_box_group<4, kStride> ( bx, by, bz, pm, r, sel, leaf_set, c );
+    for ( uint32_t g = T.n_boxes / TERRA_LEAF_BOX_GROUP; g != 0; --g ) leaf_box_group<TERRA_LEAF_BOX_GROUP, kStride, PAIRS> ( bx, by, bz, pm, r, sel, leaf_set, c, entry, nb );
+    if ( T.n_boxes & 4u ) leaf_box_group<4, kStride, PAIRS> ( bx, by, bz, pm, r, sel, leaf_set, c, entry, nb );
     #pragma clang loop vectorize(disable) interleave(disable) unroll(disable)
-    for ( uint32_t k = T.n_boxes % 4u; k != 0; --k ) leaf_box_group<1, kStride> ( bx, by, bz, pm, r, sel, leaf_set, c );
+    for ( uint32_t k = T.n_boxes % 4u; k != 0; --k ) leaf_box_group<1, kStride, PAIRS> ( bx, by, bz, pm, r, sel, leaf_set, c, entry, nb );
     return leaf_set;
 }
 
@@ -307,6 +329,23 @@ TD uint32_t leaf_boxes_flat ( const Tracer& T, const Ray& r, const SlabSel& sel,
 // strict "<" selects -- among equal depths the triangle met first, i.e. of the lowest rank. The record starts as (FLT_MAX, 0): no key is below 0, so a hit at FLT_MAX
 // is refused as the strict "<" refuses it. ANYHIT: the record is preset to the expected triangle's own (depth, key) (scene_raycast_triangle); the first triangle
 // that beats it comes first in the reference's order too, and ends the loop with key 0 ("another one"); the expected triangle itself never beats its own record.
+// Nearest first (Tracer::nearest; flat launches of a table in which box k holds exactly entry k). The reference never culls against the closest hit, so a lane's set
+// is every quad on the ray's line and the wave's trip count is its longest such line, although only the nearest quad can win. The flat loop therefore keeps the two
+// smallest entry distances of the boxes a lane passes (leaf_box_test), and the leaf loop
+//   * tests the entry of the nearest box first (lo & 31), then the lowest entry left, as before;
+//   * after every trip drops the whole set once depth_best < cut, cut = the second-smallest key with its index bits cleared: an entry distance rounded DOWN.
+// Why no bit can move. The record rule does not depend on the order of the trips, so only the dropped entries matter. Every entry j still in the set after the first
+// trip has t_enter_j >= cut (cut is a lower bound of the second smallest, and the smallest has been tested). A triangle of entry j that the ray hits lies inside its
+// own extent, i.e. at least 1e-4 inside its box (the extent grown by 1e-4) on every axis, so the ray's true entry parameter into the box is below the true depth by at
+// least 1e-4 / |d|. The computed t_enter carries the two roundings of the fused slab form, the computed depth the watertight test's error; both are inside the
+// < 56 u R / |d| the commit's containment check budgets (scene_host.cpp "numeric containment check": admitted only where 128 u R <= 1e-4, and the flat form runs only
+// there, on tame rays). Hence computed t_enter_j < computed depth_j, and with depth_best < cut <= t_enter_j < depth_j the triangle is strictly beyond the record: it
+// wins neither by depth nor, among equal depths, by key. Nothing is assumed of |d| -- ray-sourced launches do not normalise --: t_enter and depth are parameters along
+// the same d and scale alike, as do their error bounds. tests/test_leaf_nearest.py holds the inequality on the host with the device's operations.
+// Where the cut fails -- the first trip misses its pair and the record stays FLT_MAX, a tie keeps cut from lying strictly beyond the record, cut is -0 or the NaN of
+// "no second box" -- every entry left is tested in bit order as before: exact whatever the first trip did.
+// ANYHIT: a preset record strictly below the smallest entry distance cannot be beaten and the loop is skipped; otherwise the nearest entry goes first, the first
+// triangle that beats the record ends the loop as before, and the cut applies with the preset record.
 template <int COUNT, int MODE, bool FAST, bool FUSED, bool ANYHIT>
 TD void traverse_pairs ( const Tracer& T, const Ray& r, const RayState& st, V3 o_perm, Closest& best, Counters& c ) {
     const SlabSel sel = slab_sel ( r );
@@ -314,7 +353,9 @@ TD void traverse_pairs ( const Tracer& T, const Ray& r, const RayState& st, V3 o
     PS_WAVE ( c, kPsDrainIter );
     bool flat = false;
     if constexpr ( FUSED ) flat = T.n_boxes != 0u;
-    if ( flat ) leaf_set = leaf_boxes_flat<true> ( T, r, sel, c );
+    NearestBoxes nb; nb.lo = nb.hi = TERRA_NO_BOX;
+    bool nearest = false;
+    if ( flat ) { leaf_set = leaf_boxes_flat<true> ( T, r, sel, c, nb ); nearest = T.nearest; }          // (launch constant)
     else {
         int* sp = T.stack; int* lp = nullptr;
         *sp = 0; sp += TERRA_COL;
@@ -324,10 +365,16 @@ TD void traverse_pairs ( const Tracer& T, const Ray& r, const RayState& st, V3 o
     const float4* copy = T.l_ranked + ( TERRA_PAIR_ENTRY_BYTES / 16 ) * ( T.lds_tris >> 1 ) * perm;
     float depth_best = best.depth; uint32_t key_best = ANYHIT ? best.tri : 0u;          // (ANYHIT: the caller's preset key travels in best.tri; the record itself never moves)
     bool beaten = false;
+    // Nearest first: the first trip tests the entry of the nearest box the lane passes, every later one the lowest entry left; after each trip the set is dropped
+    // once the record lies strictly below `cut`, the second-smallest entry distance rounded down -- a lower bound of the entry distance of every entry still in the
+    // set, and an entry's triangles lie beyond their box's entry distance. Without it (the walk, the switch off) cut is a NaN: no record is below it.
+    const float cut = __uint_as_float ( ( uint32_t ) ( nearest ? nb.hi : TERRA_NO_BOX ) & ~31u );
+    if ( ANYHIT && nearest && depth_best < __uint_as_float ( ( uint32_t ) nb.lo & ~31u ) ) leaf_set = 0u;          // the preset record lies in front of every box passed
+    uint32_t next = nearest ? ( uint32_t ) nb.lo & 31u : ( uint32_t ) __builtin_ctz ( leaf_set | 0x80000000u );          // (an empty set: never used)
     while ( leaf_set != 0u ) {
         PS_WAVE ( c, kPsLeafIter ); PS_LANE ( c, kPsLeafLanes );
-        const float4* e = copy + ( TERRA_PAIR_ENTRY_BYTES / 16 ) * ( uint32_t ) __builtin_ctz ( leaf_set );
-        leaf_set &= leaf_set - 1u;
+        const float4* e = copy + ( TERRA_PAIR_ENTRY_BYTES / 16 ) * next;
+        leaf_set &= ~ ( 1u << next );
         const uint2 keys = *reinterpret_cast<const uint2*> ( e + 3 );
         auto load = [&] ( bool again ) {
             uint32_t a = ( uint32_t ) ( uintptr_t ) e;
@@ -344,6 +391,8 @@ TD void traverse_pairs ( const Tracer& T, const Ray& r, const RayState& st, V3 o
                 else { depth_best = depth; key_best = key; }
             }
         } );
+        if ( depth_best < cut ) leaf_set = 0u;
+        next = ( uint32_t ) __builtin_ctz ( leaf_set | 0x80000000u );
     }
     best.depth = depth_best;
     best.tri = ANYHIT ? ( beaten ? 0u : key_best ) : ( key_best ? ( key_best & 31u ) : 0xffffffffu );
@@ -357,7 +406,8 @@ TD void traverse_ranked ( const Tracer& T, const Ray& r, const RayState& st, V3 
     PS_WAVE ( c, kPsDrainIter );
     bool flat = false;
     if constexpr ( COUNT == 0 && FUSED ) flat = T.n_boxes != 0u;     // (launch constant; FUSED: the wave's rays are all tame)
-    if ( flat ) leaf_set = leaf_boxes_flat<false> ( T, r, sel, c );
+    NearestBoxes no_nb;          // (single form: never written)
+    if ( flat ) leaf_set = leaf_boxes_flat<false> ( T, r, sel, c, no_nb );
     else {
         int* sp = T.stack; int* lp = nullptr;
         *sp = 0; sp += TERRA_COL;                                      // the root: node 0 = byte offset 0

@@ -103,6 +103,8 @@ _EXTRA = {
     "terra_amd_set_leaf_pairs": (C.c_int, [C.c_void_p, C.c_int]),
     "terra_amd_get_leaf_pairs": (C.c_int, [C.c_void_p]),
     "terra_amd_leaf_pair_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    "terra_amd_set_leaf_nearest_first": (C.c_int, [C.c_void_p, C.c_int]),
+    "terra_amd_get_leaf_nearest_first": (C.c_int, [C.c_void_p]),
     "terra_amd_scene_leaf_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "terra_amd_scene_leaf_pair_masks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "terra_amd_leaf_pair_offsets": (C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p]),

@@ -63,7 +63,7 @@ def loops_report():
     boxes = lambda ins: sum(o.startswith("v_min3_f32") for o in ins)
     is_leaf = lambda ins: any(o.startswith("v_ffbl_b32") for o in ins)
     subs = lambda ins: sum(o.startswith("v_sub_f32") or o.startswith("v_subrev_f32") for o in ins)
-    def flat_and_leaf(after, form, leaf_title):
+    def flat_and_leaf(after, form, leaf_title, is_leaf=is_leaf):
         g = loop_of(lambda ins: ins.count("ds_read2_b64") >= 2 and boxes(ins) >= 2, after)
         report(f"{form}flat leaf-box loop, one trip over a group of {boxes(blocks[g][2])}", g)
         r = loop_of(lambda ins: "ds_read_b64" in ins and boxes(ins) == 1, g + 1)
@@ -83,10 +83,16 @@ def loops_report():
     # the pair form (traverse_pairs): the flat loop whose leaf loop's header transforms four vertices (25 v_sub_f32: 12 + 8 + the 5 edge functions). Its blocks:
     # the header = the shared path to the two zero tests; sign tests and selects; determinant / depth / division, once and (behind a wave-level branch) a second
     # time for T2; the record update; then the two fallback copies of the single test, each with its double-precision block
+    # (nearest first: that loop takes its first entry from the flat loop's smallest key, so its v_ffbl_b32 stands in the latch, not in the header: the header is
+    # recognised by the four vertices alone -- 128 / 66 / 20 per trip with the four key instructions per box)
     groups = [i for i, b in enumerate(blocks) if b[1] == b[0] and b[2].count("ds_read2_b64") >= 2 and boxes(b[2]) >= 2]
-    pair = [g for g in groups if subs(blocks[loop_of(is_leaf, g + 1)][2]) >= 22]
+    is_pair_leaf = lambda ins: subs(ins) >= 22
+    def next_leaf(g):
+        try: return loop_of(lambda ins: is_leaf(ins) or is_pair_leaf(ins), g + 1)
+        except SystemExit: return None
+    pair = [g for g in groups if next_leaf(g) is not None and is_pair_leaf(blocks[next_leaf(g)][2])]
     if not pair: print("pair form: no flat loop whose leaf loop transforms four vertices (a tree without the pair form has none)"); return
-    flat_and_leaf(pair[0], "pair form: ", "pair form: leaf loop, one trip over a PAIR (every block, as if every branch were taken; the last blocks are the two fallback copies of the single test)")
+    flat_and_leaf(pair[0], "pair form: ", "pair form: leaf loop, one trip over a PAIR (every block, as if every branch were taken; the last blocks are the two fallback copies of the single test)", is_pair_leaf)
 
 if LOOPS:
     loops_report(); sys.exit(0)
