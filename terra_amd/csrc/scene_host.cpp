@@ -1678,16 +1678,25 @@ static uint32_t launch_split ( const Scene* s, DevRenderParams& p, uint32_t bloc
     if ( split < 1 ) split = 1;
     return split;
 }
-// d_rays: non-null = a ray-sourced launch (include/terra_amd.h "Ray-sourced rendering"): the same plan, scratch, queue and resolve, the primary rays read from d_rays
-// (addressed like p.results); no job order and no empty skip, which are made from camera rays
-// lens: non-null = a lens launch (include/terra_amd.h "Lens rendering"): likewise, the primary rays made from the camera fields of p and *lens
-// points: non-null = a point launch (include/terra_amd.h "Point rendering"): likewise, the primary rays drawn about the records of d_points (addressed like p.results)
-static int launch_render ( Scene* s, DevRenderParams& p, int device, hipStream_t stream, ThreadSlot* slot = nullptr, const void* d_rays = nullptr, const DevLens* lens = nullptr,
-                           const void* d_points = nullptr, const DevPointSampling* points = nullptr ) {      // device: the (current) device of the launch
+// ---- the doors (DESIGN.md "The doors on the host") -------------------------------------------------------------------------------------------
+// Where a launch's primary rays come from, numbered as the kernel units' TERRA_RAY_SOURCE: the pinhole camera of DevRenderParams; a client's rays (include/terra_amd.h
+// "Ray-sourced rendering"); a camera model ("Lens rendering": the rays made from the camera fields of p and `lens`); a client's points ("Point rendering": the rays
+// drawn about the records as `points` says). Every door takes the same plan, scratch, queue and resolve; all but the camera go without the job order and the empty
+// skip, which are made from camera rays (launch_plan.h terra_block_order_bytes)
+struct RaySource {
+    enum Kind { kCamera = 0, kRays = 1, kLens = 2, kPoints = 3 };
+    Kind kind;
+    const void* d_records;                      // kRays, kPoints: the device records, addressed like p.results (and like the AOV buffer)
+    DevLens lens = {};                          // kLens (fill_lens)
+    DevPointSampling points = {};               // kPoints (fill_point_sampling)
+    RaySource ( Kind k = kCamera, const void* d = nullptr ) : kind ( k ), d_records ( d ) {}
+    bool camera() const { return kind == kCamera; }
+};
+static int launch_render ( Scene* s, DevRenderParams& p, int device, hipStream_t stream, const RaySource& src, ThreadSlot* slot = nullptr ) {      // device: the (current) device of the launch
     const uint32_t blocks = terra_render_blocks ( p );
     if ( blocks == 0 ) return 0;
     if ( p.count_level != 0 || p.rand_calls ) { p.leaf_boxes = nullptr; p.n_leaf_boxes = 0; p.leaf_pairs = 0; }      // the work counters keep their meaning: counting launches walk the tree and test one triangle per trip
-    const bool ray_source = d_rays != nullptr || lens != nullptr || points != nullptr;
+    const bool ray_source = !src.camera();
     const uint32_t split = launch_split ( s, p, blocks, ray_source );
     static thread_local uint64_t pool_kept = 0;          // (bit d: done for device d)
     if ( device < 64 && ! ( pool_kept >> device & 1ull ) ) {        // keep freed scratch cached in the device's default pool instead of returning it to the OS at every sync
@@ -1746,7 +1755,12 @@ static int launch_render ( Scene* s, DevRenderParams& p, int device, hipStream_t
     }
     if ( e == hipSuccess && order_cls ) e = terra_launch_block_order ( p, order_cls, stream );
     if ( e == hipSuccess ) e = terra_launch_job_streams ( p, stream );
-    if ( e == hipSuccess ) e = points ? terra_launch_render_points ( p, d_points, *points, stream ) : lens ? terra_launch_render_lens ( p, *lens, stream ) : d_rays ? terra_launch_render_rays ( p, d_rays, stream ) : terra_launch_render ( p, stream );
+    if ( e == hipSuccess ) switch ( src.kind ) {
+        case RaySource::kCamera: e = terra_launch_render ( p, stream ); break;
+        case RaySource::kRays:   e = terra_launch_render_rays ( p, src.d_records, stream ); break;
+        case RaySource::kLens:   e = terra_launch_render_lens ( p, src.lens, stream ); break;
+        case RaySource::kPoints: e = terra_launch_render_points ( p, src.d_records, src.points, stream ); break;
+    }
     if ( e == hipSuccess ) e = terra_launch_resolve ( p, stream );
     if ( pooled ) ( void ) hipFreeAsync ( scratch, stream );
     else if ( e != hipSuccess ) ( void ) hipMemsetAsync ( scratch, 0, header, stream );       // (a launch that failed half way must not leave a used queue word behind)
@@ -1756,20 +1770,23 @@ static int launch_render ( Scene* s, DevRenderParams& p, int device, hipStream_t
     return 0;
 }
 
+// The tail of the four device render forms, after the door's own preparation (p, src): the caller's framebuffer in HBM, addressed like the frame
+static int render_device_tail ( Scene* s, const Scene::Replica& r, DevRenderParams& p, const RaySource& src, void* d_pixels, void* d_results, void* d_rand_calls, void* stream ) {
+    if ( !d_pixels || !d_results ) return fail ( kTerraAmdErrBadArgument, "null framebuffer pointer" );
+    p.pixels = ( float* ) d_pixels; p.results = d_results; p.rand_calls = ( uint32_t* ) d_rand_calls;
+    if ( d_rand_calls ) p.count_level = 2;
+    HIP_TRY ( hipSetDevice ( r.device ), kTerraAmdErrNoDevice );
+    if ( int lrc = launch_render ( s, p, r.device, ( hipStream_t ) stream, src ) ) return lrc;
+    account_launch ( s, p );
+    return 0;
+}
 extern "C" int terra_amd_render_device_sharded ( const TerraCamera* cam, HTerraScene h, void* d_pixels, void* d_results, size_t fb_w, size_t fb_h,
                                                  size_t x, size_t y, size_t w, size_t hgt, size_t tile, int rank, int world, void* d_rand_calls, void* stream ) {
     Scene* s = S ( h );
     const Scene::Replica& r = primary ( s );
     DevRenderParams p;
-    int rc = fill_params ( s, r, cam, fb_w, fb_h, x, y, w, hgt, tile, rank, world, p );
-    if ( rc ) return rc;
-    if ( !d_pixels || !d_results ) return fail ( kTerraAmdErrBadArgument, "null framebuffer pointer" );
-    p.pixels = ( float* ) d_pixels; p.results = d_results; p.rand_calls = ( uint32_t* ) d_rand_calls;
-    if ( d_rand_calls ) p.count_level = 2;
-    HIP_TRY ( hipSetDevice ( r.device ), kTerraAmdErrNoDevice );
-    if ( int lrc = launch_render ( s, p, r.device, ( hipStream_t ) stream ) ) return lrc;
-    account_launch ( s, p );
-    return 0;
+    if ( int rc = fill_params ( s, r, cam, fb_w, fb_h, x, y, w, hgt, tile, rank, world, p ) ) return rc;
+    return render_device_tail ( s, r, p, RaySource(), d_pixels, d_results, d_rand_calls, stream );
 }
 extern "C" int terra_amd_render_device ( const TerraCamera* cam, HTerraScene h, void* d_pixels, void* d_results, size_t fb_w, size_t fb_h,
                                          size_t x, size_t y, size_t w, size_t hgt, void* d_rand_calls, void* stream ) {
@@ -1782,32 +1799,34 @@ static int rays_check ( const void* rays, const char* what ) {
     if ( ( uintptr_t ) rays & 15u ) return fail ( kTerraAmdErrBadArgument, "%s: the ray buffer must be 16-byte aligned", what );
     return 0;
 }
-// host forms: do all ACTIVE rays of the rectangle start inside the range the commit's traversal shortcut is proven for? (an inactive ray is never traced)
-static bool ray_origins_within ( const Scene* s, const TerraAmdRay* rays, size_t fb_w, size_t x, size_t y, size_t w, size_t h ) {
+// the origin of an active ray (the header's rule), nullptr of an inactive one
+static const float* ray_origin ( const TerraAmdRay& q ) {
+    const bool finite = std::isfinite ( q.origin[0] ) && std::isfinite ( q.origin[1] ) && std::isfinite ( q.origin[2] ) && std::isfinite ( q.direction[0] ) && std::isfinite ( q.direction[1] ) && std::isfinite ( q.direction[2] );
+    return ( !finite || ( q.direction[0] == 0.f && q.direction[1] == 0.f && q.direction[2] == 0.f ) ) ? nullptr : q.origin;
+}
+// host forms of the ray and point doors: do all ACTIVE records of the rectangle start inside the range the commit's traversal shortcut is proven for? (an inactive
+// record is never traced) origin: the record type's ray_origin / point_origin
+template <class Record> static bool origins_within ( const Scene* s, const Record* records, const float* ( *origin ) ( const Record& ), size_t fb_w, size_t x, size_t y, size_t w, size_t h ) {
     const float limit = shortcut_limit ( s->tree );
     for ( size_t j = y; j < y + h; ++j ) for ( size_t i = x; i < x + w; ++i ) {
-        const TerraAmdRay& q = rays[j * fb_w + i];
-        const bool finite = std::isfinite ( q.origin[0] ) && std::isfinite ( q.origin[1] ) && std::isfinite ( q.origin[2] ) && std::isfinite ( q.direction[0] ) && std::isfinite ( q.direction[1] ) && std::isfinite ( q.direction[2] );
-        if ( !finite || ( q.direction[0] == 0.f && q.direction[1] == 0.f && q.direction[2] == 0.f ) ) continue;
-        if ( ! ( fabsf ( q.origin[0] ) <= limit && fabsf ( q.origin[1] ) <= limit && fabsf ( q.origin[2] ) <= limit ) ) return false;
+        const float* o = origin ( records[j * fb_w + i] );
+        if ( o && ! ( fabsf ( o[0] ) <= limit && fabsf ( o[1] ) <= limit && fabsf ( o[2] ) <= limit ) ) return false;
     }
     return true;
+}
+// fill_params of a ray launch, then the ray buffer. origins_ok: as fill_params' ray_origins_ok (the device forms pass true: the rays are in HBM, the client keeps their
+// origins within camera_limit)
+static int fill_ray_params ( Scene* s, const Scene::Replica& r, const void* rays, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t h, bool origins_ok, const char* what, DevRenderParams& p ) {
+    if ( int rc = fill_params ( s, r, nullptr, fb_w, fb_h, x, y, w, h, 64, 0, 1, p, &origins_ok ) ) return rc;
+    return rays_check ( rays, what );
 }
 extern "C" int terra_amd_render_rays_device ( HTerraScene h, const void* d_rays, void* d_pixels, void* d_results, size_t fb_w, size_t fb_h,
                                               size_t x, size_t y, size_t w, size_t hgt, void* d_rand_calls, void* stream ) {
     Scene* s = S ( h );
     const Scene::Replica& r = primary ( s );
     DevRenderParams p;
-    const bool origins_ok = true;          // (the rays are in HBM: the client keeps their origins within camera_limit)
-    if ( int rc = fill_params ( s, r, nullptr, fb_w, fb_h, x, y, w, hgt, 64, 0, 1, p, &origins_ok ) ) return rc;
-    if ( int rc = rays_check ( d_rays, "terra_amd_render_rays_device" ) ) return rc;
-    if ( !d_pixels || !d_results ) return fail ( kTerraAmdErrBadArgument, "null framebuffer pointer" );
-    p.pixels = ( float* ) d_pixels; p.results = d_results; p.rand_calls = ( uint32_t* ) d_rand_calls;
-    if ( d_rand_calls ) p.count_level = 2;
-    HIP_TRY ( hipSetDevice ( r.device ), kTerraAmdErrNoDevice );
-    if ( int lrc = launch_render ( s, p, r.device, ( hipStream_t ) stream, nullptr, d_rays ) ) return lrc;
-    account_launch ( s, p );
-    return 0;
+    if ( int rc = fill_ray_params ( s, r, d_rays, fb_w, fb_h, x, y, w, hgt, true, "terra_amd_render_rays_device", p ) ) return rc;
+    return render_device_tail ( s, r, p, RaySource ( RaySource::kRays, d_rays ), d_pixels, d_results, d_rand_calls, stream );
 }
 // proved / total pixel blocks of the scene's most recent launch (one device; synchronises that device)
 extern "C" int terra_amd_empty_skip_info ( HTerraScene h, uint32_t out[2] ) {
@@ -1901,83 +1920,74 @@ struct FrameCopy {
 static_assert ( sizeof ( TerraAmdAovResult ) == 48, "TerraAmdAovResult must be 48 bytes" );
 // p: the launch fill_params made for the render call this AOV call mirrors; the split is the one that call takes (launch_split), and the samples the AOV buffer
 // already holds key the streams as the framebuffer's do. Runs on the current device (the scene's primary one).
-// d_rays: non-null = the ray-sourced form, mirroring a ray-sourced render call (addressed like d_aov); lens: non-null = the lens form, mirroring a lens render call.
-// points: non-null = the point form, mirroring a point render call (d_points addressed like d_aov).
-static int launch_aov ( Scene* s, DevRenderParams& p, void* d_aov, hipStream_t stream, const void* d_rays = nullptr, const DevLens* lens = nullptr,
-                        const void* d_points = nullptr, const DevPointSampling* points = nullptr ) {
+// src: the door of that render call (its records addressed like d_aov).
+static int launch_aov ( Scene* s, DevRenderParams& p, void* d_aov, hipStream_t stream, const RaySource& src ) {
     const uint32_t blocks = terra_render_blocks ( p );
     if ( blocks == 0 ) return 0;
-    const uint32_t split = launch_split ( s, p, blocks, d_rays != nullptr || lens != nullptr || points != nullptr );
+    const uint32_t split = launch_split ( s, p, blocks, !src.camera() );
     p.split = split; p.split_log2 = 0; while ( ( 1u << p.split_log2 ) < split ) ++p.split_log2;
     p.chunk_spp = p.spp / split; p.job_blocks = blocks * split; p.job_queue = nullptr; p.job_streams = nullptr; p.block_order = nullptr; p.partials = nullptr;
     p.pixels = nullptr; p.results = nullptr; p.rand_calls = nullptr; p.counters = nullptr; p.count_level = 0;
-    const hipError_t e = points ? terra_launch_aov_points ( p, d_points, *points, d_aov, stream ) : lens ? terra_launch_aov_lens ( p, *lens, d_aov, stream ) : d_rays ? terra_launch_aov_rays ( p, d_rays, d_aov, stream ) : terra_launch_aov ( p, d_aov, stream );
+    hipError_t e = hipSuccess;
+    switch ( src.kind ) {
+        case RaySource::kCamera: e = terra_launch_aov ( p, d_aov, stream ); break;
+        case RaySource::kRays:   e = terra_launch_aov_rays ( p, src.d_records, d_aov, stream ); break;
+        case RaySource::kLens:   e = terra_launch_aov_lens ( p, src.lens, d_aov, stream ); break;
+        case RaySource::kPoints: e = terra_launch_aov_points ( p, src.d_records, src.points, d_aov, stream ); break;
+    }
     if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "AOV launch: %s", hipGetErrorString ( e ) );
     return 0;
 }
-// the device form with the buffer's addressing spelled out: d_aov holds rows of st_pitch pixels whose first is pixel (st_x, st_y) of the frame
-static int render_aov_device ( const TerraCamera* cam, HTerraScene h, void* d_aov, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t hgt, size_t st_x, size_t st_y, size_t st_pitch, void* stream ) {
-    Scene* s = S ( h );
-    const Scene::Replica& r = primary ( s );
-    DevRenderParams p;
-    if ( int rc = fill_params ( s, r, cam, fb_w, fb_h, x, y, w, hgt, 64, 0, 1, p ) ) return rc;
-    if ( !d_aov ) return fail ( kTerraAmdErrBadArgument, "null AOV buffer" );
-    HIP_TRY ( hipSetDevice ( r.device ), kTerraAmdErrNoDevice );
+static int aov_check ( const void* aov ) { return aov ? 0 : fail ( kTerraAmdErrBadArgument, "null AOV buffer" ); }
+// The tail of the four AOV device forms, after the door's own preparation (p, src), with the buffer's addressing spelled out: d_aov (and the door's records) hold
+// rows of st_pitch pixels whose first is pixel (st_x, st_y) of the frame
+static int aov_device_tail ( Scene* s, DevRenderParams& p, const RaySource& src, void* d_aov, size_t st_x, size_t st_y, size_t st_pitch, void* stream ) {
+    if ( int rc = aov_check ( d_aov ) ) return rc;
+    HIP_TRY ( hipSetDevice ( primary ( s ).device ), kTerraAmdErrNoDevice );
     p.st_x = ( uint32_t ) st_x; p.st_y = ( uint32_t ) st_y; p.st_pitch = ( uint32_t ) st_pitch;
-    return launch_aov ( s, p, d_aov, ( hipStream_t ) stream );
+    return launch_aov ( s, p, d_aov, ( hipStream_t ) stream, src );
+}
+// The tail of the four AOV host forms: the rectangle only goes up and comes back, rows of q.w pixels (as render_staged_tail stages it); records: the host records of
+// the ray and point doors, whose rectangle goes up beside it
+static int aov_staged_tail ( Scene* s, DevRenderParams& p, RaySource src, TerraAmdAovResult* aov, const FrameRect& q, const void* records = nullptr, size_t record_size = 0 ) {
+    if ( int rc = aov_check ( aov ) ) return rc;
+    HIP_TRY ( hipSetDevice ( primary ( s ).device ), kTerraAmdErrNoDevice );
+    FrameCopy c;
+    hipError_t e = c.up_rect ( 0, aov, sizeof ( TerraAmdAovResult ), q );
+    if ( e == hipSuccess && records ) { e = c.up_rect ( 1, records, record_size, q ); src.d_records = c.d[1]; }
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "AOV upload: %s", hipGetErrorString ( e ) );
+    if ( int rc = aov_device_tail ( s, p, src, c.d[0], q.x, q.y, q.w, nullptr ) ) return rc;
+    e = c.down_rect ( 0, aov, sizeof ( TerraAmdAovResult ), q );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "AOV download: %s", hipGetErrorString ( e ) );
+    return 0;
 }
 extern "C" int terra_amd_render_aov_device ( const TerraCamera* cam, HTerraScene h, void* d_aov, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t hgt, void* stream ) {
-    return render_aov_device ( cam, h, d_aov, fb_w, fb_h, x, y, w, hgt, 0, 0, fb_w, stream );
+    Scene* s = S ( h );
+    DevRenderParams p;
+    if ( int rc = fill_params ( s, primary ( s ), cam, fb_w, fb_h, x, y, w, hgt, 64, 0, 1, p ) ) return rc;
+    return aov_device_tail ( s, p, RaySource(), d_aov, 0, 0, fb_w, stream );
 }
 extern "C" int terra_amd_render_aov ( const TerraCamera* cam, HTerraScene h, TerraAmdAovResult* aov, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t hgt ) {
     Scene* s = S ( h );
-    DevRenderParams p;          // (for the check alone, before anything is staged: the device form fills its own)
+    DevRenderParams p;
     if ( int rc = fill_params ( s, primary ( s ), cam, fb_w, fb_h, x, y, w, hgt, 64, 0, 1, p ) ) return rc;
-    if ( !aov ) return fail ( kTerraAmdErrBadArgument, "null AOV buffer" );
-    HIP_TRY ( hipSetDevice ( primary ( s ).device ), kTerraAmdErrNoDevice );
-    const FrameRect rect = { fb_w, x, y, w, hgt };          // the rectangle only, rows of w pixels (as render_host stages it)
-    FrameCopy c;
-    hipError_t e = c.up_rect ( 0, aov, sizeof ( TerraAmdAovResult ), rect );
-    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "AOV upload: %s", hipGetErrorString ( e ) );
-    if ( int rc = render_aov_device ( cam, h, c.d[0], fb_w, fb_h, x, y, w, hgt, x, y, w, nullptr ) ) return rc;
-    e = c.down_rect ( 0, aov, sizeof ( TerraAmdAovResult ), rect );
-    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "AOV download: %s", hipGetErrorString ( e ) );
-    return 0;
+    return aov_staged_tail ( s, p, RaySource(), aov, { fb_w, x, y, w, hgt } );
 }
 // ray-sourced forms: d_rays addressed like d_aov
-static int render_aov_rays_device ( HTerraScene h, const void* d_rays, void* d_aov, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t hgt, size_t st_x, size_t st_y, size_t st_pitch,
-                                    bool origins_ok, void* stream, const char* what ) {
-    Scene* s = S ( h );
-    const Scene::Replica& r = primary ( s );
-    DevRenderParams p;
-    if ( int rc = fill_params ( s, r, nullptr, fb_w, fb_h, x, y, w, hgt, 64, 0, 1, p, &origins_ok ) ) return rc;
-    if ( int rc = rays_check ( d_rays, what ) ) return rc;
-    if ( !d_aov ) return fail ( kTerraAmdErrBadArgument, "null AOV buffer" );
-    HIP_TRY ( hipSetDevice ( r.device ), kTerraAmdErrNoDevice );
-    p.st_x = ( uint32_t ) st_x; p.st_y = ( uint32_t ) st_y; p.st_pitch = ( uint32_t ) st_pitch;
-    return launch_aov ( s, p, d_aov, ( hipStream_t ) stream, d_rays );
-}
 extern "C" int terra_amd_render_aov_rays_device ( HTerraScene h, const void* d_rays, void* d_aov, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t hgt, void* stream ) {
-    return render_aov_rays_device ( h, d_rays, d_aov, fb_w, fb_h, x, y, w, hgt, 0, 0, fb_w, true, stream, "terra_amd_render_aov_rays_device" );
+    Scene* s = S ( h );
+    DevRenderParams p;
+    if ( int rc = fill_ray_params ( s, primary ( s ), d_rays, fb_w, fb_h, x, y, w, hgt, true, "terra_amd_render_aov_rays_device", p ) ) return rc;
+    return aov_device_tail ( s, p, RaySource ( RaySource::kRays, d_rays ), d_aov, 0, 0, fb_w, stream );
 }
 extern "C" int terra_amd_render_aov_rays ( HTerraScene h, const TerraAmdRay* rays, TerraAmdAovResult* aov, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t hgt ) {
     Scene* s = S ( h );
-    DevRenderParams p;          // (for the check alone, before anything is staged: the device form fills its own)
-    const bool any = true;
-    if ( int rc = fill_params ( s, primary ( s ), nullptr, fb_w, fb_h, x, y, w, hgt, 64, 0, 1, p, &any ) ) return rc;
-    if ( int rc = rays_check ( rays, "terra_amd_render_aov_rays" ) ) return rc;
-    if ( !aov ) return fail ( kTerraAmdErrBadArgument, "null AOV buffer" );
-    HIP_TRY ( hipSetDevice ( primary ( s ).device ), kTerraAmdErrNoDevice );
-    const bool origins_ok = ray_origins_within ( s, rays, fb_w, x, y, w, hgt );
-    const FrameRect rect = { fb_w, x, y, w, hgt };
-    FrameCopy c;
-    hipError_t e = c.up_rect ( 0, aov, sizeof ( TerraAmdAovResult ), rect );
-    if ( e == hipSuccess ) e = c.up_rect ( 1, rays, sizeof ( TerraAmdRay ), rect );
-    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "AOV upload: %s", hipGetErrorString ( e ) );
-    if ( int rc = render_aov_rays_device ( h, c.d[1], c.d[0], fb_w, fb_h, x, y, w, hgt, x, y, w, origins_ok, nullptr, "terra_amd_render_aov_rays" ) ) return rc;
-    e = c.down_rect ( 0, aov, sizeof ( TerraAmdAovResult ), rect );
-    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "AOV download: %s", hipGetErrorString ( e ) );
-    return 0;
+    DevRenderParams p;
+    if ( int rc = fill_ray_params ( s, primary ( s ), rays, fb_w, fb_h, x, y, w, hgt, true, "terra_amd_render_aov_rays", p ) ) return rc;          // (first pass: the checks alone, before the rays are read)
+    if ( int rc = aov_check ( aov ) ) return rc;          // (before the second pass: a refused call leaves last_call as the first pass set it)
+    if ( !origins_within ( s, rays, ray_origin, fb_w, x, y, w, hgt ) )          // an active origin beyond camera_limit: the replica traversal
+        if ( int rc = fill_ray_params ( s, primary ( s ), rays, fb_w, fb_h, x, y, w, hgt, false, "terra_amd_render_aov_rays", p ) ) return rc;
+    return aov_staged_tail ( s, p, RaySource ( RaySource::kRays ), aov, { fb_w, x, y, w, hgt }, rays, sizeof ( TerraAmdRay ) );
 }
 // ---- ray queries (query_kernels.hip) ---------------------------------------------------
 static_assert ( sizeof ( TerraAmdRay ) == 32 && sizeof ( TerraAmdHit ) == 32, "TerraAmdRay and TerraAmdHit must be 32 bytes" );
@@ -2366,10 +2376,42 @@ static int slot_prepare ( int device, size_t npx ) {
 }
 extern "C" size_t terra_amd_thread_staging_bytes ( void ) { return t_slot.cap_px * 28; }
 
+static int framebuffer_check ( const TerraFramebuffer* fb ) { return ( fb && fb->pixels && fb->results ) ? 0 : fail ( kTerraAmdErrBadArgument, "null framebuffer" ); }
+// The tail of the four host render forms, after the door's own preparation (p, src), on replica r and the calling thread's slot. The staging buffers hold the
+// rectangle q only (rows of q.w pixels); the kernel addresses them through st_x / st_y / st_pitch while the camera and the random streams keep using the frame's
+// geometry. records: the host records of the ray and point doors (record_size bytes each, one per pixel of the frame), whose rectangle goes up beside the running
+// sums, rows of q.w records, into a copy that lives as long as the call
+static int render_staged_tail ( Scene* s, const Scene::Replica& r, DevRenderParams& p, RaySource src, const TerraFramebuffer* fb, const FrameRect& q, const void* records = nullptr, size_t record_size = 0 ) {
+    if ( int rc = slot_prepare ( r.device, q.w * q.h ) ) return rc;
+    ThreadSlot& t = t_slot;
+    p.st_x = ( uint32_t ) q.x; p.st_y = ( uint32_t ) q.y; p.st_pitch = ( uint32_t ) q.w;
+    const size_t first = q.y * q.fb_w + q.x, rpitch = q.fb_w * 16, ppitch = q.fb_w * 12;
+    char* const hres = ( char* ) fb->results + first * 16;
+    char* const hpix = ( char* ) fb->pixels + first * 12;
+    FrameCopy c;          // the records' device copy: freed when the call returns (after the stream has drained, below)
+    if ( records ) {
+        const hipError_t e = hipMalloc ( ( void** ) &c.d[0], q.w * q.h * record_size );
+        if ( e != hipSuccess ) { ( void ) hipGetLastError(); return fail ( kTerraAmdErrNoDevice, "%s upload: %s", src.kind == RaySource::kPoints ? "point" : "ray", hipGetErrorString ( e ) ); }
+        src.d_records = c.d[0];
+        HIP_TRY ( hipMemcpy2DAsync ( c.d[0], q.w * record_size, ( const char* ) records + first * record_size, q.fb_w * record_size, q.w * record_size, q.h, hipMemcpyHostToDevice, t.stream ), kTerraAmdErrLaunch );
+    }
+    HIP_TRY ( hipMemcpy2DAsync ( t.d_results, q.w * 16, hres, rpitch, q.w * 16, q.h, hipMemcpyHostToDevice, t.stream ), kTerraAmdErrLaunch );
+    p.pixels = ( float* ) t.d_pixels; p.results = t.d_results; p.rand_calls = nullptr;
+    const int lrc = launch_render ( s, p, r.device, t.stream, src, &t );
+    if ( !lrc ) {
+        HIP_TRY ( hipMemcpy2DAsync ( hres, rpitch, t.d_results, q.w * 16, q.w * 16, q.h, hipMemcpyDeviceToHost, t.stream ), kTerraAmdErrLaunch );
+        HIP_TRY ( hipMemcpy2DAsync ( hpix, ppitch, t.d_pixels, q.w * 12, q.w * 12, q.h, hipMemcpyDeviceToHost, t.stream ), kTerraAmdErrLaunch );
+    }
+    HIP_TRY ( hipStreamSynchronize ( t.stream ), kTerraAmdErrLaunch );          // (also on a failed launch: the uploads above still read the host frame and the records' copy)
+    if ( lrc ) return lrc;
+    account_launch ( s, p );
+    return 0;
+}
+
 static int render_host_multi ( const TerraCamera* cam, Scene* s, const TerraFramebuffer* fb, size_t x, size_t y, size_t w, size_t h, size_t tile );
 static std::atomic<int> g_thread_ordinals { 0 };
 static int render_host ( const TerraCamera* cam, Scene* s, const TerraFramebuffer* fb, size_t x, size_t y, size_t w, size_t h ) {
-    if ( !fb || !fb->pixels || !fb->results ) return fail ( kTerraAmdErrBadArgument, "null framebuffer" );
+    if ( int rc = framebuffer_check ( fb ) ) return rc;
     // A scene committed for several devices (terra_amd_set_devices). A call that covers enough of a frame to give every device a fair share of 64-pixel tiles is
     // sharded over them and gathered (render_host_multi); a small one -- the reference client's 128-pixel tiles, called from its worker threads
     // (satellite/src/Renderer.cpp:70-98,316-350) -- goes whole to ONE device, the calling thread's: threads are dealt to the devices round-robin when they first call, so
@@ -2382,64 +2424,20 @@ static int render_host ( const TerraCamera* cam, Scene* s, const TerraFramebuffe
         r = &s->replicas[ ( size_t ) ordinal % s->replicas.size()];
     }
     DevRenderParams p;
-    int rc = fill_params ( s, *r, cam, fb->width, fb->height, x, y, w, h, 64, 0, 1, p );
-    if ( rc ) return rc;
-    rc = slot_prepare ( r->device, w * h );
-    if ( rc ) return rc;
-    ThreadSlot& t = t_slot;
-    // the staging buffer holds the rectangle only (rows of w pixels); the kernel addresses it through st_x / st_y / st_pitch while
-    // the camera and the random streams keep using the frame's geometry
-    p.st_x = ( uint32_t ) x; p.st_y = ( uint32_t ) y; p.st_pitch = ( uint32_t ) w;
-    const size_t rpitch = fb->width * 16, ppitch = fb->width * 12;
-    const char* hres = ( const char* ) fb->results + ( y * fb->width + x ) * 16;
-    char* hpix = ( char* ) fb->pixels + ( y * fb->width + x ) * 12;
-    HIP_TRY ( hipMemcpy2DAsync ( t.d_results, w * 16, hres, rpitch, w * 16, h, hipMemcpyHostToDevice, t.stream ), kTerraAmdErrLaunch );
-    p.pixels = ( float* ) t.d_pixels; p.results = t.d_results; p.rand_calls = nullptr;
-    if ( int lrc = launch_render ( s, p, r->device, t.stream, &t ) ) return lrc;
-    HIP_TRY ( hipMemcpy2DAsync ( ( void* ) hres, rpitch, t.d_results, w * 16, w * 16, h, hipMemcpyDeviceToHost, t.stream ), kTerraAmdErrLaunch );
-    HIP_TRY ( hipMemcpy2DAsync ( hpix, ppitch, t.d_pixels, w * 12, w * 12, h, hipMemcpyDeviceToHost, t.stream ), kTerraAmdErrLaunch );
-    HIP_TRY ( hipStreamSynchronize ( t.stream ), kTerraAmdErrLaunch );
-    account_launch ( s, p );
-    return 0;
+    if ( int rc = fill_params ( s, *r, cam, fb->width, fb->height, x, y, w, h, 64, 0, 1, p ) ) return rc;
+    return render_staged_tail ( s, *r, p, RaySource(), fb, { fb->width, x, y, w, h } );
 }
 
-// terra_amd_render_rays: render_host with the rectangle's rays uploaded beside the running sums (rows of w records, addressed like the staging rectangle). A scene
-// committed for several devices answers on its primary device.
+// terra_amd_render_rays: the rectangle's rays go up beside the running sums. A scene committed for several devices answers on its primary device.
 extern "C" int terra_amd_render_rays ( HTerraScene h, const TerraAmdRay* rays, const TerraFramebuffer* fb, size_t x, size_t y, size_t w, size_t hgt ) {
     Scene* s = S ( h );
-    if ( !fb || !fb->pixels || !fb->results ) return fail ( kTerraAmdErrBadArgument, "null framebuffer" );
-    const Scene::Replica* r = &primary ( s );
+    if ( int rc = framebuffer_check ( fb ) ) return rc;
+    const Scene::Replica& r = primary ( s );
     DevRenderParams p;
-    bool origins_ok = true;          // (first pass: the checks alone, before the rays are read)
-    if ( int rc = fill_params ( s, *r, nullptr, fb->width, fb->height, x, y, w, hgt, 64, 0, 1, p, &origins_ok ) ) return rc;
-    if ( int rc = rays_check ( rays, "terra_amd_render_rays" ) ) return rc;
-    origins_ok = ray_origins_within ( s, rays, fb->width, x, y, w, hgt );
-    if ( !origins_ok ) if ( int rc = fill_params ( s, *r, nullptr, fb->width, fb->height, x, y, w, hgt, 64, 0, 1, p, &origins_ok ) ) return rc;      // an active origin beyond camera_limit: the replica traversal
-    if ( int rc = slot_prepare ( r->device, w * hgt ) ) return rc;
-    ThreadSlot& t = t_slot;
-    p.st_x = ( uint32_t ) x; p.st_y = ( uint32_t ) y; p.st_pitch = ( uint32_t ) w;
-    const size_t rpitch = fb->width * 16, ppitch = fb->width * 12;
-    const char* hres = ( const char* ) fb->results + ( y * fb->width + x ) * 16;
-    char* hpix = ( char* ) fb->pixels + ( y * fb->width + x ) * 12;
-    FrameCopy c;          // the rays' device copy: freed when the call returns (after the stream has drained, below)
-    void* d_rays = nullptr;
-    {
-        const hipError_t e = hipMalloc ( ( void** ) &c.d[0], w * hgt * sizeof ( TerraAmdRay ) );
-        if ( e != hipSuccess ) { ( void ) hipGetLastError(); return fail ( kTerraAmdErrNoDevice, "ray upload: %s", hipGetErrorString ( e ) ); }
-        d_rays = c.d[0];
-    }
-    HIP_TRY ( hipMemcpy2DAsync ( d_rays, w * sizeof ( TerraAmdRay ), ( const char* ) rays + ( y * fb->width + x ) * sizeof ( TerraAmdRay ), fb->width * sizeof ( TerraAmdRay ), w * sizeof ( TerraAmdRay ), hgt, hipMemcpyHostToDevice, t.stream ), kTerraAmdErrLaunch );
-    HIP_TRY ( hipMemcpy2DAsync ( t.d_results, w * 16, hres, rpitch, w * 16, hgt, hipMemcpyHostToDevice, t.stream ), kTerraAmdErrLaunch );
-    p.pixels = ( float* ) t.d_pixels; p.results = t.d_results; p.rand_calls = nullptr;
-    int lrc = launch_render ( s, p, r->device, t.stream, &t, d_rays );
-    if ( !lrc ) {
-        HIP_TRY ( hipMemcpy2DAsync ( ( void* ) hres, rpitch, t.d_results, w * 16, w * 16, hgt, hipMemcpyDeviceToHost, t.stream ), kTerraAmdErrLaunch );
-        HIP_TRY ( hipMemcpy2DAsync ( hpix, ppitch, t.d_pixels, w * 12, w * 12, hgt, hipMemcpyDeviceToHost, t.stream ), kTerraAmdErrLaunch );
-    }
-    HIP_TRY ( hipStreamSynchronize ( t.stream ), kTerraAmdErrLaunch );          // (also on a failed launch: the upload above still reads the ray copy)
-    if ( lrc ) return lrc;
-    account_launch ( s, p );
-    return 0;
+    if ( int rc = fill_ray_params ( s, r, rays, fb->width, fb->height, x, y, w, hgt, true, "terra_amd_render_rays", p ) ) return rc;          // (first pass: the checks alone, before the rays are read)
+    if ( !origins_within ( s, rays, ray_origin, fb->width, x, y, w, hgt ) )          // an active origin beyond camera_limit: the replica traversal
+        if ( int rc = fill_ray_params ( s, r, rays, fb->width, fb->height, x, y, w, hgt, false, "terra_amd_render_rays", p ) ) return rc;
+    return render_staged_tail ( s, r, p, RaySource ( RaySource::kRays ), fb, { fb->width, x, y, w, hgt }, rays, sizeof ( TerraAmdRay ) );
 }
 
 // ---- lens rendering: the render call through a camera model (include/terra_amd.h "Lens rendering") -----------------------------------------------
@@ -2477,70 +2475,33 @@ extern "C" int terra_amd_render_lens_device ( const TerraCamera* cam, const Terr
                                               size_t x, size_t y, size_t w, size_t hgt, void* d_rand_calls, void* stream ) {
     Scene* s = S ( h );
     const Scene::Replica& r = primary ( s );
-    DevRenderParams p; DevLens L;
-    if ( int rc = fill_lens_params ( s, r, cam, lens, fb_w, fb_h, x, y, w, hgt, "terra_amd_render_lens_device", p, L ) ) return rc;
-    if ( !d_pixels || !d_results ) return fail ( kTerraAmdErrBadArgument, "null framebuffer pointer" );
-    p.pixels = ( float* ) d_pixels; p.results = d_results; p.rand_calls = ( uint32_t* ) d_rand_calls;
-    if ( d_rand_calls ) p.count_level = 2;
-    HIP_TRY ( hipSetDevice ( r.device ), kTerraAmdErrNoDevice );
-    if ( int lrc = launch_render ( s, p, r.device, ( hipStream_t ) stream, nullptr, nullptr, &L ) ) return lrc;
-    account_launch ( s, p );
-    return 0;
+    DevRenderParams p; RaySource src ( RaySource::kLens );
+    if ( int rc = fill_lens_params ( s, r, cam, lens, fb_w, fb_h, x, y, w, hgt, "terra_amd_render_lens_device", p, src.lens ) ) return rc;
+    return render_device_tail ( s, r, p, src, d_pixels, d_results, d_rand_calls, stream );
 }
-// the host form: render_host's staging of the rectangle, on the primary device
+// the host form: on the primary device
 extern "C" int terra_amd_render_lens ( const TerraCamera* cam, const TerraAmdLens* lens, HTerraScene h, const TerraFramebuffer* fb, size_t x, size_t y, size_t w, size_t hgt ) {
     Scene* s = S ( h );
     if ( !s->committed ) return scene_check ( s );
-    if ( !fb || !fb->pixels || !fb->results ) return fail ( kTerraAmdErrBadArgument, "null framebuffer" );
-    const Scene::Replica* r = &primary ( s );
-    DevRenderParams p; DevLens L;
-    if ( int rc = fill_lens_params ( s, *r, cam, lens, fb->width, fb->height, x, y, w, hgt, "terra_amd_render_lens", p, L ) ) return rc;
-    if ( int rc = slot_prepare ( r->device, w * hgt ) ) return rc;
-    ThreadSlot& t = t_slot;
-    p.st_x = ( uint32_t ) x; p.st_y = ( uint32_t ) y; p.st_pitch = ( uint32_t ) w;
-    const size_t rpitch = fb->width * 16, ppitch = fb->width * 12;
-    const char* hres = ( const char* ) fb->results + ( y * fb->width + x ) * 16;
-    char* hpix = ( char* ) fb->pixels + ( y * fb->width + x ) * 12;
-    HIP_TRY ( hipMemcpy2DAsync ( t.d_results, w * 16, hres, rpitch, w * 16, hgt, hipMemcpyHostToDevice, t.stream ), kTerraAmdErrLaunch );
-    p.pixels = ( float* ) t.d_pixels; p.results = t.d_results; p.rand_calls = nullptr;
-    if ( int lrc = launch_render ( s, p, r->device, t.stream, &t, nullptr, &L ) ) return lrc;
-    HIP_TRY ( hipMemcpy2DAsync ( ( void* ) hres, rpitch, t.d_results, w * 16, w * 16, hgt, hipMemcpyDeviceToHost, t.stream ), kTerraAmdErrLaunch );
-    HIP_TRY ( hipMemcpy2DAsync ( hpix, ppitch, t.d_pixels, w * 12, w * 12, hgt, hipMemcpyDeviceToHost, t.stream ), kTerraAmdErrLaunch );
-    HIP_TRY ( hipStreamSynchronize ( t.stream ), kTerraAmdErrLaunch );
-    account_launch ( s, p );
-    return 0;
-}
-// AOV forms: d_aov holds rows of st_pitch pixels whose first is pixel (st_x, st_y) of the frame
-static int render_aov_lens_device ( const TerraCamera* cam, const TerraAmdLens* lens, HTerraScene h, void* d_aov, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t hgt,
-                                    size_t st_x, size_t st_y, size_t st_pitch, void* stream, const char* what ) {
-    Scene* s = S ( h );
+    if ( int rc = framebuffer_check ( fb ) ) return rc;
     const Scene::Replica& r = primary ( s );
-    DevRenderParams p; DevLens L;
-    if ( int rc = fill_lens_params ( s, r, cam, lens, fb_w, fb_h, x, y, w, hgt, what, p, L ) ) return rc;
-    if ( !d_aov ) return fail ( kTerraAmdErrBadArgument, "null AOV buffer" );
-    HIP_TRY ( hipSetDevice ( r.device ), kTerraAmdErrNoDevice );
-    p.st_x = ( uint32_t ) st_x; p.st_y = ( uint32_t ) st_y; p.st_pitch = ( uint32_t ) st_pitch;
-    return launch_aov ( s, p, d_aov, ( hipStream_t ) stream, nullptr, &L );
+    DevRenderParams p; RaySource src ( RaySource::kLens );
+    if ( int rc = fill_lens_params ( s, r, cam, lens, fb->width, fb->height, x, y, w, hgt, "terra_amd_render_lens", p, src.lens ) ) return rc;
+    return render_staged_tail ( s, r, p, src, fb, { fb->width, x, y, w, hgt } );
 }
 extern "C" int terra_amd_render_aov_lens_device ( const TerraCamera* cam, const TerraAmdLens* lens, HTerraScene h, void* d_aov, size_t fb_w, size_t fb_h,
                                                   size_t x, size_t y, size_t w, size_t hgt, void* stream ) {
-    return render_aov_lens_device ( cam, lens, h, d_aov, fb_w, fb_h, x, y, w, hgt, 0, 0, fb_w, stream, "terra_amd_render_aov_lens_device" );
+    Scene* s = S ( h );
+    DevRenderParams p; RaySource src ( RaySource::kLens );
+    if ( int rc = fill_lens_params ( s, primary ( s ), cam, lens, fb_w, fb_h, x, y, w, hgt, "terra_amd_render_aov_lens_device", p, src.lens ) ) return rc;
+    return aov_device_tail ( s, p, src, d_aov, 0, 0, fb_w, stream );
 }
 extern "C" int terra_amd_render_aov_lens ( const TerraCamera* cam, const TerraAmdLens* lens, HTerraScene h, TerraAmdAovResult* aov, size_t fb_w, size_t fb_h,
                                            size_t x, size_t y, size_t w, size_t hgt ) {
     Scene* s = S ( h );
-    DevRenderParams p; DevLens L;          // (for the checks alone, before anything is staged: the device form fills its own)
-    if ( int rc = fill_lens_params ( s, primary ( s ), cam, lens, fb_w, fb_h, x, y, w, hgt, "terra_amd_render_aov_lens", p, L ) ) return rc;
-    if ( !aov ) return fail ( kTerraAmdErrBadArgument, "null AOV buffer" );
-    HIP_TRY ( hipSetDevice ( primary ( s ).device ), kTerraAmdErrNoDevice );
-    const FrameRect rect = { fb_w, x, y, w, hgt };
-    FrameCopy c;
-    hipError_t e = c.up_rect ( 0, aov, sizeof ( TerraAmdAovResult ), rect );
-    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "AOV upload: %s", hipGetErrorString ( e ) );
-    if ( int rc = render_aov_lens_device ( cam, lens, h, c.d[0], fb_w, fb_h, x, y, w, hgt, x, y, w, nullptr, "terra_amd_render_aov_lens" ) ) return rc;
-    e = c.down_rect ( 0, aov, sizeof ( TerraAmdAovResult ), rect );
-    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "AOV download: %s", hipGetErrorString ( e ) );
-    return 0;
+    DevRenderParams p; RaySource src ( RaySource::kLens );
+    if ( int rc = fill_lens_params ( s, primary ( s ), cam, lens, fb_w, fb_h, x, y, w, hgt, "terra_amd_render_aov_lens", p, src.lens ) ) return rc;
+    return aov_staged_tail ( s, p, src, aov, { fb_w, x, y, w, hgt } );
 }
 
 // ---- point rendering: the render call with directions drawn about a client's points (include/terra_amd.h "Point rendering") ----------------------------------
@@ -2553,21 +2514,11 @@ static int fill_point_sampling ( const TerraAmdPointSampling* ps, const char* wh
     S.distribution = ps->distribution;
     return 0;
 }
-// the header's inactive point, on the host
-static bool point_is_inactive ( const TerraAmdPoint& q ) {
+// the position of an active point (the header's rule, on the host), nullptr of an inactive one (origins_within)
+static const float* point_origin ( const TerraAmdPoint& q ) {
     const bool finite = std::isfinite ( q.position[0] ) && std::isfinite ( q.position[1] ) && std::isfinite ( q.position[2] ) && std::isfinite ( q.normal[0] ) && std::isfinite ( q.normal[1] ) && std::isfinite ( q.normal[2] );
     const float qq = q.normal[0] * q.normal[0] + q.normal[1] * q.normal[1] + q.normal[2] * q.normal[2];
-    return !finite || ! ( qq > 0.f && std::isfinite ( qq ) );
-}
-// host forms: do all ACTIVE points of the rectangle lie inside the range the commit's traversal shortcut is proven for? (an inactive point is never traced)
-static bool point_positions_within ( const Scene* s, const TerraAmdPoint* points, size_t fb_w, size_t x, size_t y, size_t w, size_t h ) {
-    const float limit = shortcut_limit ( s->tree );
-    for ( size_t j = y; j < y + h; ++j ) for ( size_t i = x; i < x + w; ++i ) {
-        const TerraAmdPoint& q = points[j * fb_w + i];
-        if ( point_is_inactive ( q ) ) continue;
-        if ( ! ( fabsf ( q.position[0] ) <= limit && fabsf ( q.position[1] ) <= limit && fabsf ( q.position[2] ) <= limit ) ) return false;
-    }
-    return true;
+    return ( !finite || ! ( qq > 0.f && std::isfinite ( qq ) ) ) ? nullptr : q.position;
 }
 // fill_params of a point launch: "not committed" first, then the arguments -- all of them, the rectangle included, before the call asks for the scene's device
 // replica: a bad argument is refused on a host without a GPU too --, then the launch. origins_ok: as fill_params' ray_origins_ok
@@ -2584,87 +2535,41 @@ extern "C" int terra_amd_render_points_device ( HTerraScene h, const TerraAmdPoi
                                                 size_t x, size_t y, size_t w, size_t hgt, void* d_rand_calls, void* stream ) {
     Scene* s = S ( h );
     const Scene::Replica& r = primary ( s );
-    DevRenderParams p; DevPointSampling D;
+    DevRenderParams p; RaySource src ( RaySource::kPoints, d_points );
     // (the points are in HBM: the client keeps their positions within camera_limit)
-    if ( int rc = fill_point_params ( s, r, ps, d_points, fb_w, fb_h, x, y, w, hgt, true, "terra_amd_render_points_device", p, D ) ) return rc;
-    if ( !d_pixels || !d_results ) return fail ( kTerraAmdErrBadArgument, "null framebuffer pointer" );
-    p.pixels = ( float* ) d_pixels; p.results = d_results; p.rand_calls = ( uint32_t* ) d_rand_calls;
-    if ( d_rand_calls ) p.count_level = 2;
-    HIP_TRY ( hipSetDevice ( r.device ), kTerraAmdErrNoDevice );
-    if ( int lrc = launch_render ( s, p, r.device, ( hipStream_t ) stream, nullptr, nullptr, nullptr, d_points, &D ) ) return lrc;
-    account_launch ( s, p );
-    return 0;
+    if ( int rc = fill_point_params ( s, r, ps, d_points, fb_w, fb_h, x, y, w, hgt, true, "terra_amd_render_points_device", p, src.points ) ) return rc;
+    return render_device_tail ( s, r, p, src, d_pixels, d_results, d_rand_calls, stream );
 }
-// the host form: terra_amd_render_rays' staging, with the rectangle's points uploaded beside the running sums (rows of w records, addressed like the staging rectangle)
+// the host form: the rectangle's points go up beside the running sums, on the primary device
 extern "C" int terra_amd_render_points ( HTerraScene h, const TerraAmdPointSampling* ps, const TerraAmdPoint* points, const TerraFramebuffer* fb, size_t x, size_t y, size_t w, size_t hgt ) {
     Scene* s = S ( h );
     if ( !s->committed ) return scene_check ( s );
-    if ( !fb || !fb->pixels || !fb->results ) return fail ( kTerraAmdErrBadArgument, "null framebuffer" );
-    const Scene::Replica* r = &primary ( s );
-    DevRenderParams p; DevPointSampling D;
-    // (first pass: the checks alone, before the points are read)
-    if ( int rc = fill_point_params ( s, *r, ps, points, fb->width, fb->height, x, y, w, hgt, true, "terra_amd_render_points", p, D ) ) return rc;
-    if ( !point_positions_within ( s, points, fb->width, x, y, w, hgt ) )          // an active point beyond camera_limit: the replica traversal
-        if ( int rc = fill_point_params ( s, *r, ps, points, fb->width, fb->height, x, y, w, hgt, false, "terra_amd_render_points", p, D ) ) return rc;
-    if ( int rc = slot_prepare ( r->device, w * hgt ) ) return rc;
-    ThreadSlot& t = t_slot;
-    p.st_x = ( uint32_t ) x; p.st_y = ( uint32_t ) y; p.st_pitch = ( uint32_t ) w;
-    const size_t rpitch = fb->width * 16, ppitch = fb->width * 12;
-    const char* hres = ( const char* ) fb->results + ( y * fb->width + x ) * 16;
-    char* hpix = ( char* ) fb->pixels + ( y * fb->width + x ) * 12;
-    FrameCopy c;          // the points' device copy: freed when the call returns (after the stream has drained, below)
-    void* d_points = nullptr;
-    {
-        const hipError_t e = hipMalloc ( ( void** ) &c.d[0], w * hgt * sizeof ( TerraAmdPoint ) );
-        if ( e != hipSuccess ) { ( void ) hipGetLastError(); return fail ( kTerraAmdErrNoDevice, "point upload: %s", hipGetErrorString ( e ) ); }
-        d_points = c.d[0];
-    }
-    HIP_TRY ( hipMemcpy2DAsync ( d_points, w * sizeof ( TerraAmdPoint ), ( const char* ) points + ( y * fb->width + x ) * sizeof ( TerraAmdPoint ), fb->width * sizeof ( TerraAmdPoint ), w * sizeof ( TerraAmdPoint ), hgt, hipMemcpyHostToDevice, t.stream ), kTerraAmdErrLaunch );
-    HIP_TRY ( hipMemcpy2DAsync ( t.d_results, w * 16, hres, rpitch, w * 16, hgt, hipMemcpyHostToDevice, t.stream ), kTerraAmdErrLaunch );
-    p.pixels = ( float* ) t.d_pixels; p.results = t.d_results; p.rand_calls = nullptr;
-    int lrc = launch_render ( s, p, r->device, t.stream, &t, nullptr, nullptr, d_points, &D );
-    if ( !lrc ) {
-        HIP_TRY ( hipMemcpy2DAsync ( ( void* ) hres, rpitch, t.d_results, w * 16, w * 16, hgt, hipMemcpyDeviceToHost, t.stream ), kTerraAmdErrLaunch );
-        HIP_TRY ( hipMemcpy2DAsync ( hpix, ppitch, t.d_pixels, w * 12, w * 12, hgt, hipMemcpyDeviceToHost, t.stream ), kTerraAmdErrLaunch );
-    }
-    HIP_TRY ( hipStreamSynchronize ( t.stream ), kTerraAmdErrLaunch );          // (also on a failed launch: the upload above still reads the point copy)
-    if ( lrc ) return lrc;
-    account_launch ( s, p );
-    return 0;
-}
-// AOV forms: d_aov and d_points hold rows of st_pitch pixels whose first is pixel (st_x, st_y) of the frame
-static int render_aov_points_device ( HTerraScene h, const TerraAmdPointSampling* ps, const void* d_points, void* d_aov, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t hgt,
-                                      size_t st_x, size_t st_y, size_t st_pitch, bool origins_ok, void* stream, const char* what ) {
-    Scene* s = S ( h );
+    if ( int rc = framebuffer_check ( fb ) ) return rc;
     const Scene::Replica& r = primary ( s );
-    DevRenderParams p; DevPointSampling D;
-    if ( int rc = fill_point_params ( s, r, ps, d_points, fb_w, fb_h, x, y, w, hgt, origins_ok, what, p, D ) ) return rc;
-    if ( !d_aov ) return fail ( kTerraAmdErrBadArgument, "null AOV buffer" );
-    HIP_TRY ( hipSetDevice ( r.device ), kTerraAmdErrNoDevice );
-    p.st_x = ( uint32_t ) st_x; p.st_y = ( uint32_t ) st_y; p.st_pitch = ( uint32_t ) st_pitch;
-    return launch_aov ( s, p, d_aov, ( hipStream_t ) stream, nullptr, nullptr, d_points, &D );
+    DevRenderParams p; RaySource src ( RaySource::kPoints );
+    // (first pass: the checks alone, before the points are read)
+    if ( int rc = fill_point_params ( s, r, ps, points, fb->width, fb->height, x, y, w, hgt, true, "terra_amd_render_points", p, src.points ) ) return rc;
+    if ( !origins_within ( s, points, point_origin, fb->width, x, y, w, hgt ) )          // an active point beyond camera_limit: the replica traversal
+        if ( int rc = fill_point_params ( s, r, ps, points, fb->width, fb->height, x, y, w, hgt, false, "terra_amd_render_points", p, src.points ) ) return rc;
+    return render_staged_tail ( s, r, p, src, fb, { fb->width, x, y, w, hgt }, points, sizeof ( TerraAmdPoint ) );
 }
+// AOV forms: d_points addressed like d_aov
 extern "C" int terra_amd_render_aov_points_device ( HTerraScene h, const TerraAmdPointSampling* ps, const void* d_points, void* d_aov, size_t fb_w, size_t fb_h,
                                                     size_t x, size_t y, size_t w, size_t hgt, void* stream ) {
-    return render_aov_points_device ( h, ps, d_points, d_aov, fb_w, fb_h, x, y, w, hgt, 0, 0, fb_w, true, stream, "terra_amd_render_aov_points_device" );
+    Scene* s = S ( h );
+    DevRenderParams p; RaySource src ( RaySource::kPoints, d_points );
+    if ( int rc = fill_point_params ( s, primary ( s ), ps, d_points, fb_w, fb_h, x, y, w, hgt, true, "terra_amd_render_aov_points_device", p, src.points ) ) return rc;
+    return aov_device_tail ( s, p, src, d_aov, 0, 0, fb_w, stream );
 }
 extern "C" int terra_amd_render_aov_points ( HTerraScene h, const TerraAmdPointSampling* ps, const TerraAmdPoint* points, TerraAmdAovResult* aov, size_t fb_w, size_t fb_h,
                                              size_t x, size_t y, size_t w, size_t hgt ) {
     Scene* s = S ( h );
-    DevRenderParams p; DevPointSampling D;          // (for the checks alone, before anything is staged: the device form fills its own)
-    if ( int rc = fill_point_params ( s, primary ( s ), ps, points, fb_w, fb_h, x, y, w, hgt, true, "terra_amd_render_aov_points", p, D ) ) return rc;
-    if ( !aov ) return fail ( kTerraAmdErrBadArgument, "null AOV buffer" );
-    HIP_TRY ( hipSetDevice ( primary ( s ).device ), kTerraAmdErrNoDevice );
-    const bool origins_ok = point_positions_within ( s, points, fb_w, x, y, w, hgt );
-    const FrameRect rect = { fb_w, x, y, w, hgt };
-    FrameCopy c;
-    hipError_t e = c.up_rect ( 0, aov, sizeof ( TerraAmdAovResult ), rect );
-    if ( e == hipSuccess ) e = c.up_rect ( 1, points, sizeof ( TerraAmdPoint ), rect );
-    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "AOV upload: %s", hipGetErrorString ( e ) );
-    if ( int rc = render_aov_points_device ( h, ps, c.d[1], c.d[0], fb_w, fb_h, x, y, w, hgt, x, y, w, origins_ok, nullptr, "terra_amd_render_aov_points" ) ) return rc;
-    e = c.down_rect ( 0, aov, sizeof ( TerraAmdAovResult ), rect );
-    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "AOV download: %s", hipGetErrorString ( e ) );
-    return 0;
+    DevRenderParams p; RaySource src ( RaySource::kPoints );
+    if ( int rc = fill_point_params ( s, primary ( s ), ps, points, fb_w, fb_h, x, y, w, hgt, true, "terra_amd_render_aov_points", p, src.points ) ) return rc;          // (first pass, as above)
+    if ( int rc = aov_check ( aov ) ) return rc;          // (before the second pass: a refused call leaves last_call as the first pass set it)
+    if ( !origins_within ( s, points, point_origin, fb_w, x, y, w, hgt ) )
+        if ( int rc = fill_point_params ( s, primary ( s ), ps, points, fb_w, fb_h, x, y, w, hgt, false, "terra_amd_render_aov_points", p, src.points ) ) return rc;
+    return aov_staged_tail ( s, p, src, aov, { fb_w, x, y, w, hgt }, points, sizeof ( TerraAmdPoint ) );
 }
 // the scene's vertices as points: record 3 T + k = vertex k of the T-th triangle (objects in order, their triangles in order) with its TerraTriangleProperties
 // normal as stored. Host only. Returns the number of records whatever the capacity; writes the first min(capacity, records) of them
@@ -2737,7 +2642,7 @@ static int render_host_multi ( const TerraCamera* cam, Scene* s, const TerraFram
             p.pixels = ( float* ) q.d_pixels; p.results = q.d_results; p.rand_calls = nullptr;
             queued = k + 1;
             HIP_TRY ( hipMemcpy2DAsync ( q.d_results, w * 16, hres, rpitch, w * 16, h, hipMemcpyHostToDevice, q.stream ), kTerraAmdErrLaunch );
-            if ( int rc = launch_render ( s, p, r.device, q.stream ) ) return rc;
+            if ( int rc = launch_render ( s, p, r.device, q.stream, RaySource() ) ) return rc;
             HIP_TRY ( terra_launch_tiles ( true, ( float* ) q.d_pixels, q.d_results, ( uint32_t ) w, 0, 0, ( uint32_t ) w, ( uint32_t ) h, ( uint32_t ) tile, ( uint32_t ) k, ( uint32_t ) world, r.d_packed, q.stream ), kTerraAmdErrLaunch );
         }
         {   // the one collective
