@@ -35,6 +35,7 @@
  *       [--passes N] [--denoise-variance K] [--adaptive TARGET [--min-passes A] [--max-passes B]] [--variance out.pfm]
  *       [--frames N] [--camera-to px py pz dx dy dz] [--temporal ALPHA]
  *       [--camera-model pinhole|thinlens|ortho|equirect|fisheye] [--aperture R] [--focus D] [--ortho-height H] [--fisheye-fov DEG]
+ *       [--bake-lightmap [--atlas WxH] [--bake-margin M] [--bake-dilate N]]
  *
  * Environment: the scene's environment attribute is a constant (--environment-color, default 0.4 0.52 1) or a lat-long map (--environment: Radiance .hdr with flat
  * or new-style run-length-encoded scanlines, orientation -Y H +X W, texel = m 2^(e - 136); or .pfm, either byte order, bottom row first), bound as a 3-component
@@ -83,6 +84,15 @@ int         terra_amd_reproject ( HTerraScene, const TerraCamera*, const TerraCa
 typedef struct { int model; float lens_radius, focus_distance, ortho_height, fisheye_fov; int reserved[3]; } Lens;
 int         terra_amd_render_lens ( const TerraCamera*, const void*, HTerraScene, const TerraFramebuffer*, size_t, size_t, size_t, size_t ) __attribute__ ( ( weak ) );
 int         terra_amd_render_aov_lens ( const TerraCamera*, const void*, HTerraScene, void*, size_t, size_t, size_t, size_t, size_t, size_t ) __attribute__ ( ( weak ) );
+/* lightmap baking (TerraAmdPoint, TerraAmdPointSampling, TerraAmdAtlas, TerraAmdAtlasTexel and the calls of terra_amd.h "Point rendering" / "Lightmap baking",
+   restated for the same reason) */
+typedef struct { float position[3]; float reserved; float normal[3]; float reserved2; } BakePoint;
+typedef struct { int distribution; int reserved[3]; } BakeSampling;
+typedef struct { int width, height; float uv_scale[2]; float uv_offset[2]; float margin; int reserved[5]; } BakeAtlas;
+typedef struct { int triangle; float wb, wc; float distance2; } BakeTexel;
+int         terra_amd_atlas_points ( HTerraScene, const void*, const float*, void*, void* ) __attribute__ ( ( weak ) );
+int         terra_amd_render_points ( HTerraScene, const void*, const void*, const TerraFramebuffer*, size_t, size_t, size_t, size_t ) __attribute__ ( ( weak ) );
+int         terra_amd_dilate ( float*, int, int*, int, int, int ) __attribute__ ( ( weak ) );
 /* --camera-model: non-NULL = every render call and its AOV call go through the lens door */
 static const Lens* g_lens = NULL;
 static void render_rect ( const TerraCamera* cam, HTerraScene scene, const TerraFramebuffer* fb, size_t x, size_t y, size_t w, size_t h ) {
@@ -610,6 +620,11 @@ static const char* kHelp =
     "           in focus), --ortho-height H (ortho: the world height of the film window), --fisheye-fov DEG (fisheye: the angle across the frame's height, up to 360).\n"
     "           Works with --passes, --aov, --denoise, --denoise-variance, --variance and --frames; not with --adaptive / --gpus (ignored), and --temporal is refused:\n"
     "           reprojection is defined for the pinhole only\n"
+    "  --bake-lightmap [--atlas WxH] [--bake-margin M] [--bake-dilate N] (libterra_amd.so only): writes, in place of the camera's image, the irradiance map of the\n"
+    "           scene over a W x H texel atlas (default 256x256) as float RGB (.pfm / .hdr): the OBJ's vt times (W, H) are the atlas coordinates, row 0 is v = 0.\n"
+    "           terra_amd_atlas_points lays a surface point under every texel whose centre a triangle covers or comes within M texels of (0 .. 4, default 0.5),\n"
+    "           terra_amd_render_points gathers --spp cosine-weighted samples per --passes pass at each (PI * sum / samples), terra_amd_dilate grows the lit texels\n"
+    "           N passes (0 .. 64, default 2) into the gutters. The camera flags, --aov, --denoise*, --adaptive, --frames and --gpus are ignored.\n"
     "OBJ/MTL import (--normals apollo, the default): the policy of the reference client's importer (satellite/include/Apollo.h under the\n"
     "options of satellite/src/Scene.cpp:83-93) RESTATED in this tool and pinned by hand-derived fixtures -- restated, not executed: Apollo.h\n"
     "does not compile with this image's toolchains. Everything after the TerraObject fill (commit, render, export) is the pinned path.\n";
@@ -625,6 +640,7 @@ int main ( int argc, char** argv ) {
     int frames = 0, have_camera_to = 0; float temporal = -1.f; TerraCamera cam_to; memset ( &cam_to, 0, sizeof cam_to );
     const char* dump_path = NULL; int no_render = 0;
     int camera_model = 0; float aperture = 0.f, focus = 1.f, ortho_height = 2.f, fisheye_fov = 180.f;      /* camera_model: 0 pinhole, 1 thinlens, 2 ortho, 3 equirect, 4 fisheye */
+    int bake = 0, atlas_w = 256, atlas_h = 256, bake_dilate = 2; float bake_margin = 0.5f;      /* --bake-lightmap */
     float fov = 45.f, exposure = 1.f, gamma = 2.2f, jitter = 0.f;
     unsigned long long seed = 0;
     const char* env_path = NULL; float env_rgb[3] = { 0.4f, 0.52f, 1.f }; int env_light = 0, env_sampling = 0;      /* env_sampling: 0 off, 1 table, 2 mis */
@@ -671,6 +687,10 @@ int main ( int argc, char** argv ) {
         else if ( !strcmp ( a, "--focus" ) ) focus = ( float ) atof ( NEXT() );
         else if ( !strcmp ( a, "--ortho-height" ) ) ortho_height = ( float ) atof ( NEXT() );
         else if ( !strcmp ( a, "--fisheye-fov" ) ) fisheye_fov = ( float ) atof ( NEXT() );
+        else if ( !strcmp ( a, "--bake-lightmap" ) ) bake = 1;
+        else if ( !strcmp ( a, "--atlas" ) ) { if ( sscanf ( NEXT(), "%dx%d", &atlas_w, &atlas_h ) != 2 || atlas_w < 1 || atlas_w > 16384 || atlas_h < 1 || atlas_h > 16384 ) { fprintf ( stderr, "terra_headless: --atlas WxH, each 1 .. 16384\n" ); return 64; } }
+        else if ( !strcmp ( a, "--bake-margin" ) ) { bake_margin = ( float ) atof ( NEXT() ); if ( !( bake_margin >= 0.f && bake_margin <= 4.f ) ) { fprintf ( stderr, "terra_headless: --bake-margin 0 .. 4\n" ); return 64; } }
+        else if ( !strcmp ( a, "--bake-dilate" ) ) { bake_dilate = atoi ( NEXT() ); if ( bake_dilate < 0 || bake_dilate > 64 ) { fprintf ( stderr, "terra_headless: --bake-dilate 0 .. 64\n" ); return 64; } }
         else if ( !strcmp ( a, "--camera-to" ) && i + 6 < argc ) {
             cam_to.position = terra_f3_set ( ( float ) atof ( argv[i + 1] ), ( float ) atof ( argv[i + 2] ), ( float ) atof ( argv[i + 3] ) );
             cam_to.direction = terra_f3_set ( ( float ) atof ( argv[i + 4] ), ( float ) atof ( argv[i + 5] ), ( float ) atof ( argv[i + 6] ) ); i += 6; have_camera_to = 1;
@@ -728,6 +748,35 @@ int main ( int argc, char** argv ) {
         if ( gpus > 64 || ( terra_amd_device_count && gpus > terra_amd_device_count() ) ) { fprintf ( stderr, "terra_headless: --gpus %d but %d visible\n", gpus, terra_amd_device_count ? terra_amd_device_count() : 0 ); return 69; }
         for ( int k = 0; k < gpus; ++k ) devs[k] = k;
         if ( terra_amd_set_devices ( devs, gpus ) != 0 ) { fprintf ( stderr, "terra_headless: %s\n", terra_amd_last_error ? terra_amd_last_error() : "terra_amd_set_devices failed" ); return 69; }
+    }
+    if ( bake && ( !terra_amd_atlas_points || !terra_amd_render_points || !terra_amd_dilate ) ) { fprintf ( stderr, "terra_headless: --bake-lightmap needs libterra_amd.so; ignored, the camera's image is written\n" ); bake = 0; }
+    if ( bake ) {          /* the atlas is the frame: points under the texels, irradiance at the points, the lit texels grown into the gutters */
+        const size_t aw = ( size_t ) atlas_w, ah = ( size_t ) atlas_h, n = aw * ah;
+        terra_scene_commit ( scene );
+        BakeAtlas atlas; memset ( &atlas, 0, sizeof atlas );
+        atlas.width = atlas_w; atlas.height = atlas_h; atlas.uv_scale[0] = ( float ) atlas_w; atlas.uv_scale[1] = ( float ) atlas_h; atlas.margin = bake_margin;
+        BakeSampling cosine; memset ( &cosine, 0, sizeof cosine );
+        BakePoint* points = aligned_alloc ( 16, n * sizeof ( BakePoint ) ); BakeTexel* texels = malloc ( n * sizeof ( BakeTexel ) ); int* valid = malloc ( n * sizeof ( int ) );
+        TerraFramebuffer lm;
+        if ( !points || !texels || !valid || !terra_framebuffer_create ( &lm, aw, ah ) ) { fprintf ( stderr, "terra_headless: out of memory\n" ); return 71; }
+        int rc = terra_amd_atlas_points ( scene, &atlas, NULL, points, texels );
+        for ( int pass = 0; pass < passes && !rc; ++pass ) rc = terra_amd_render_points ( scene, &cosine, points, &lm, 0, 0, aw, ah );
+        size_t covered = 0;
+        for ( size_t i = 0; i < n && !rc; ++i ) {
+            const TerraRawIntegrationResult* r = &lm.results[i];
+            const float s = ( float ) r->samples;
+            lm.pixels[i] = terra_f3_set ( 3.14159274f * r->acc.x / s, 3.14159274f * r->acc.y / s, 3.14159274f * r->acc.z / s );
+            valid[i] = texels[i].triangle >= 0; covered += ( size_t ) valid[i];
+        }
+        if ( !rc ) rc = terra_amd_dilate ( &lm.pixels[0].x, 3, valid, atlas_w, atlas_h, bake_dilate );
+        if ( rc ) { fprintf ( stderr, "terra_headless: %s\n", terra_amd_last_error && *terra_amd_last_error() ? terra_amd_last_error() : "the bake failed" ); return 70; }
+        if ( !write_image ( argv[2], &lm ) ) { fprintf ( stderr, "terra_headless: cannot write %s\n", argv[2] ); return 73; }
+        printf ( "%s: %zu triangles, %zu materials -> lightmap %s (%zux%zu texels, %zu covered, %zu spp x %d)\n", argv[1], m.faces.n, m.mtls.n, argv[2], aw, ah, covered, spp, passes );
+        free ( points ); free ( texels ); free ( valid );
+        terra_framebuffer_destroy ( &lm );
+        terra_scene_destroy ( scene );
+        if ( env_path ) terra_texture_destroy ( &env_tex );
+        return 0;
     }
     Lens lens; memset ( &lens, 0, sizeof lens );          /* --camera-model: the lens door's camera model */
     if ( camera_model > 0 ) {

@@ -836,6 +836,70 @@ int terra_amd_unit_point_rays ( const TerraAmdPointSampling* sampling, int n, co
    capacity, or a negative status, and writes the first min(capacity, records) records. Baking vertex colours is this helper plus one render call. */
 int terra_amd_scene_vertex_points ( HTerraScene scene, TerraAmdPoint* out, int capacity );
 
+/* ---- Lightmap baking: a UV-atlas rasteriser that makes the point door's points, and gutter dilation ----------------------------------------------------------
+   A lightmap bake is: for every texel of an atlas, the world position and normal of the surface point laid out there (terra_amd_atlas_points*); the irradiance at
+   those points (terra_amd_render_points*, distribution 0: PI * acc / samples); the lit texels grown into the gutters between charts so that bilinear lookups do not
+   bleed black (terra_amd_dilate*). The frame IS the atlas: texel (x, y) is pixel (x, y), row 0 is v = 0. The reference has no such calls: this is the library's own
+   definition, off unless called. UV unwrapping is the client's: it brings the atlas, as the scene's texcoords (which are in texels, Terra.h) or as an array of its own.
+   Rule of coverage.  All arithmetic is binary64 in exactly the order written, no fused multiply-add, IEEE division; (double) of a binary32 is exact.
+     Texel (x, y) has the centre P = (x + 0.5, y + 0.5). A vertex's atlas coordinate is (double) u * (double) uv_scale[k] + (double) uv_offset[k] on axis k.
+     For a triangle A, B, C (atlas coordinates): area2 = (Bx-Ax)*(Cy-Ay) - (By-Ay)*(Cx-Ax). A triangle covers nothing if one of its six atlas coordinates is not
+     finite, or if area2 is 0 or not finite. Edge values:
+       ea = (Cx-Bx)*(Py-By) - (Cy-By)*(Px-Bx),  eb = (Ax-Cx)*(Py-Cy) - (Ay-Cy)*(Px-Cx),  ec = (Bx-Ax)*(Py-Ay) - (By-Ay)*(Px-Ax);
+     where area2 < 0 the three are negated for the test (and only for the test).
+     Inside: all three >= 0. Then d2 = 0, wb = eb / area2, wc = ec / area2 (the values as computed, not negated).
+     Outside, and only when margin > 0: for the edges (U, V) = (A, B), (B, C), (C, A) in that order,
+       t = ((Px-Ux)*(Vx-Ux) + (Py-Uy)*(Vy-Uy)) / ((Vx-Ux)*(Vx-Ux) + (Vy-Uy)*(Vy-Uy)); t < 0 becomes 0, t > 1 becomes 1 (two comparisons: a NaN stays);
+       Q = (Ux + t*(Vx-Ux), Uy + t*(Vy-Uy)); d2 = (Px-Qx)*(Px-Qx) + (Py-Qy)*(Py-Qy).
+       The edge taken is A B unless B C's d2 is strictly smaller, and that one unless C A's is strictly smaller again. Its weights: A B (wb, wc) = (t, 0); B C
+       (1 - t, t); C A (0, 1 - t). The triangle is a candidate of the texel when d2 <= (double) margin * (double) margin.
+     Winner of a texel: the candidate with the least (distance2, triangle) in lexicographic order, distance2 = (float) d2 -- so a centre on an edge that two triangles
+       share goes to the lower index, and the image does not depend on the order in which triangles are processed.
+     Point: wa = (1.0 - wb) - wc with wb, wc in binary64 as above; every component of position and normal is (float) ((wa * (double) a + wb * (double) b) +
+       wc * (double) c) of the three vertices' values. The normal is the interpolated TerraTriangleProperties normal as stored, not normalised. reserved, reserved2 = 0.
+       The texel record holds the triangle, (float) wb, (float) wc and distance2.
+     An uncovered texel gets the all-zero point -- inactive at the point door: it costs nothing there -- and the record { -1, 0, 0, 0 }.
+   Triangles are numbered as terra_amd_scene_vertex_points numbers them: objects in order, their triangles in order.
+   Dilation.  data: width * height * channels packed floats (channels 1 .. 4); valid: one int per texel, non-zero = valid; passes 0 .. 64. In each pass, with validity
+     read as it stood at the start of the pass: every invalid texel visits its in-frame 8 neighbours in the order (dy, dx) = (-1,-1), (-1,0), (-1,1), (0,-1), (0,1),
+     (1,-1), (1,0), (1,1); per channel its new value is the binary32 sum of the valid neighbours' values, added in that order starting from the first valid one,
+     divided by (float) count; it becomes valid (1) if count > 0 and is left as it is otherwise. Valid texels never change. passes = 0 writes nothing.
+   Calls.  The atlas calls fail with kTerraAmdErrNotCommitted first, before anything else is looked at and without touching a device; then every call fails with
+     kTerraAmdErrBadArgument, before it asks for a device and with nothing written, for: a NULL atlas, a size outside 1 .. 16384, a uv_scale, uv_offset or margin that is
+     not finite, a margin outside [0, 4], non-zero reserved, a NULL point buffer or one that is not 16-byte aligned; for dilate: NULL data or valid, channels outside
+     1 .. 4, a width or height that is not positive, passes outside 0 .. 64. A scene committed for several devices answers on its primary device; the dilate calls
+     run on the calling thread's current device. */
+typedef struct {              /* 48 bytes */
+    int   width, height;      /* +0  atlas size in texels, each 1 .. 16384 */
+    float uv_scale[2];        /* +8  atlas coordinate = uv * uv_scale + uv_offset, per axis */
+    float uv_offset[2];       /* +16 */
+    float margin;             /* +24 0 .. 4 texels; finite */
+    int   reserved[5];        /* +28 zero */
+} TerraAmdAtlas;
+typedef struct {              /* 16 bytes, frame-indexed */
+    int   triangle;           /* +0  scene triangle index as terra_amd_scene_vertex_points numbers triangles; -1: uncovered */
+    float wb, wc;             /* +4  weights of vertices b and c of the point taken (wa = 1 - wb - wc) */
+    float distance2;          /* +12 squared distance in texels from the texel centre to the triangle in the atlas; 0 inside */
+} TerraAmdAtlasTexel;
+TERRA_ABI_ASSERT ( sizeof ( TerraAmdAtlas ) == 48 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdAtlas, uv_scale ) == 8 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdAtlas, uv_offset ) == 16 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdAtlas, margin ) == 24 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdAtlas, reserved ) == 28 );
+TERRA_ABI_ASSERT ( sizeof ( TerraAmdAtlasTexel ) == 16 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdAtlasTexel, wb ) == 4 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdAtlasTexel, distance2 ) == 12 );
+/* d_uvs: device memory, six floats per scene triangle (ua va ub vb uc vc) in scene triangle order, or NULL = the scene's own texcoord_a / b / c. d_points: device
+   memory, width * height TerraAmdPoint records, 16-byte aligned -- what terra_amd_render_points_device() takes as it is. d_texels: width * height TerraAmdAtlasTexel
+   records, or NULL. Every texel of both is written. Asynchronous on `stream`. */
+int terra_amd_atlas_points_device ( HTerraScene scene, const TerraAmdAtlas* atlas, const void* d_uvs, void* d_points, void* d_texels, void* stream );
+/* The same on host memory; synchronous. */
+int terra_amd_atlas_points ( HTerraScene scene, const TerraAmdAtlas* atlas, const float* uvs, TerraAmdPoint* points, TerraAmdAtlasTexel* texels );
+/* d_data, d_valid: device memory, dilated in place. Asynchronous on `stream`. */
+int terra_amd_dilate_device ( void* d_data, int channels, void* d_valid, int width, int height, int passes, void* stream );
+/* The same on host memory; synchronous. */
+int terra_amd_dilate ( float* data, int channels, int* valid, int width, int height, int passes );
+
 /* Tile-sharded form for one-process-per-GPU rendering (the reference shards
    the same way over CPU threads: satellite/src/Renderer.cpp:316-350): the
    rectangle is cut into tile_size x tile_size tiles numbered row-major and this

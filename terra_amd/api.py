@@ -259,6 +259,30 @@ POINT_SIGNATURES = {
     "terra_amd_scene_vertex_points": (c_int, [c_void_p, c_void_p, c_int]),
 }
 
+
+class Atlas(Structure):
+    """TerraAmdAtlas (include/terra_amd.h "Lightmap baking"): the atlas size in texels, uv -> atlas coordinate (uv * uv_scale + uv_offset), the margin in texels; 48 bytes"""
+    _fields_ = [("width", c_int), ("height", c_int), ("uv_scale", c_float * 2), ("uv_offset", c_float * 2), ("margin", c_float), ("reserved", c_int * 5)]
+
+
+class AtlasTexel(Structure):
+    """TerraAmdAtlasTexel: the triangle a texel took (-1: uncovered), the weights of its vertices b and c, the squared distance in texels (0 inside); 16 bytes"""
+    _fields_ = [("triangle", c_int), ("wb", c_float), ("wc", c_float), ("distance2", c_float)]
+
+
+ABI_SIZES.update({Atlas: 48, AtlasTexel: 16})
+assert C.sizeof(Atlas) == 48 and C.sizeof(AtlasTexel) == 16
+ATLAS_TEXEL_DTYPE = np.dtype([("triangle", np.int32), ("wb", np.float32), ("wc", np.float32), ("distance2", np.float32)])
+assert ATLAS_TEXEL_DTYPE.itemsize == 16
+
+# ... and of lightmap baking (include/terra_amd.h "Lightmap baking")
+BAKE_SIGNATURES = {
+    "terra_amd_atlas_points_device": (c_int, [c_void_p, POINTER(Atlas), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "terra_amd_atlas_points": (c_int, [c_void_p, POINTER(Atlas), c_void_p, c_void_p, c_void_p]),
+    "terra_amd_dilate_device": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "terra_amd_dilate": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int]),
+}
+
 # entry points of include/Terra.h + include/TerraPresets.h, name -> (restype, argtypes)
 API_SIGNATURES = {
     "scene_create": (c_void_p, []),

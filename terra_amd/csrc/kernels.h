@@ -86,6 +86,16 @@ struct DevQueryParams {
 };
 hipError_t terra_launch_query ( DevQueryParams p, const void* rays, size_t n, void* out, bool anyhit, hipStream_t stream );
 
+// lightmap baking (bake_kernels.hip; include/terra_amd.h "Lightmap baking"): all pointers are device pointers; the launchers take their scratch (the coverage
+// keys; the dilation's second copy) from the stream's pool and give it back on the stream
+struct DevAtlas {
+    uint32_t width, height;
+    float    uv_scale[2], uv_offset[2], margin;
+};
+// points: width * height TerraAmdPoint, texels: width * height TerraAmdAtlasTexel or nullptr; uvs: 6 floats per triangle or nullptr = sc.props' texcoords
+hipError_t terra_launch_atlas_points ( const DevScene& sc, const DevAtlas& atlas, const float* uvs, void* points, void* texels, hipStream_t stream );
+hipError_t terra_launch_dilate ( float* data, int channels, int* valid, uint32_t width, uint32_t height, int passes, hipStream_t stream );
+
 hipError_t terra_fill_sincos24 ( float2* table, hipStream_t stream );    // DevScene::sincos24: 2^24 entries (128 MB), device pointer
 
 // unit-level launchers: all pointers are DEVICE pointers, n items, synchronous semantics left to the caller

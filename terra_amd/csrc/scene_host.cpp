@@ -2595,6 +2595,83 @@ extern "C" int terra_amd_scene_vertex_points ( HTerraScene h, TerraAmdPoint* out
     return ( int ) ( 3 * ntri );
 }
 
+// ---- lightmap baking: the UV-atlas rasteriser and gutter dilation (bake_kernels.hip; include/terra_amd.h "Lightmap baking") ----------------------------------
+static_assert ( sizeof ( TerraAmdAtlas ) == 48 && sizeof ( TerraAmdAtlasTexel ) == 16, "TerraAmdAtlas must be 48 bytes, TerraAmdAtlasTexel 16" );
+// the one check of the two atlas calls: "not committed" first, then every argument, before the call asks for the scene's device replica
+static int fill_atlas ( const Scene* s, const TerraAmdAtlas* a, const void* points, const char* what, DevAtlas& A ) {
+    if ( !s->committed ) return scene_check ( s );
+    if ( !a ) return fail ( kTerraAmdErrBadArgument, "%s: null atlas", what );
+    if ( a->width < 1 || a->width > 16384 || a->height < 1 || a->height > 16384 ) return fail ( kTerraAmdErrBadArgument, "%s: atlas %d x %d: each side 1 .. 16384", what, a->width, a->height );
+    if ( !std::isfinite ( a->uv_scale[0] ) || !std::isfinite ( a->uv_scale[1] ) || !std::isfinite ( a->uv_offset[0] ) || !std::isfinite ( a->uv_offset[1] ) )
+        return fail ( kTerraAmdErrBadArgument, "%s: uv_scale and uv_offset must be finite", what );
+    if ( !std::isfinite ( a->margin ) || a->margin < 0.f || a->margin > 4.f ) return fail ( kTerraAmdErrBadArgument, "%s: margin %g: 0 .. 4 texels", what, ( double ) a->margin );
+    for ( int r : a->reserved ) if ( r ) return fail ( kTerraAmdErrBadArgument, "%s: TerraAmdAtlas::reserved must be zero", what );
+    if ( !points ) return fail ( kTerraAmdErrBadArgument, "%s: null point buffer", what );
+    if ( ( uintptr_t ) points & 15u ) return fail ( kTerraAmdErrBadArgument, "%s: the point buffer must be 16-byte aligned", what );
+    A.width = ( uint32_t ) a->width; A.height = ( uint32_t ) a->height; A.margin = a->margin;
+    A.uv_scale[0] = a->uv_scale[0]; A.uv_scale[1] = a->uv_scale[1]; A.uv_offset[0] = a->uv_offset[0]; A.uv_offset[1] = a->uv_offset[1];
+    return scene_check ( s );
+}
+static int launch_atlas ( Scene* s, const DevAtlas& A, const void* d_uvs, void* d_points, void* d_texels, hipStream_t stream ) {
+    HIP_TRY ( hipSetDevice ( primary ( s ).device ), kTerraAmdErrNoDevice );
+    const hipError_t e = terra_launch_atlas_points ( primary ( s ).dev, A, ( const float* ) d_uvs, d_points, d_texels, stream );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "atlas launch: %s", hipGetErrorString ( e ) );
+    return 0;
+}
+extern "C" int terra_amd_atlas_points_device ( HTerraScene h, const TerraAmdAtlas* atlas, const void* d_uvs, void* d_points, void* d_texels, void* stream ) {
+    Scene* s = S ( h );
+    DevAtlas A;
+    if ( int rc = fill_atlas ( s, atlas, d_points, "terra_amd_atlas_points_device", A ) ) return rc;
+    return launch_atlas ( s, A, d_uvs, d_points, d_texels, ( hipStream_t ) stream );
+}
+// the host form: the client's uvs go up, every texel's point and record come back
+extern "C" int terra_amd_atlas_points ( HTerraScene h, const TerraAmdAtlas* atlas, const float* uvs, TerraAmdPoint* points, TerraAmdAtlasTexel* texels ) {
+    Scene* s = S ( h );
+    DevAtlas A;
+    if ( int rc = fill_atlas ( s, atlas, points, "terra_amd_atlas_points", A ) ) return rc;
+    HIP_TRY ( hipSetDevice ( primary ( s ).device ), kTerraAmdErrNoDevice );
+    const size_t n = ( size_t ) A.width * A.height;
+    FrameCopy c;
+    hipError_t e = c.up ( 0, nullptr, n * sizeof ( TerraAmdPoint ) );
+    if ( e == hipSuccess && texels ) e = c.up ( 1, nullptr, n * sizeof ( TerraAmdAtlasTexel ) );
+    if ( e == hipSuccess && uvs && primary ( s ).dev.n_tris ) e = c.up ( 2, uvs, ( size_t ) primary ( s ).dev.n_tris * 6 * sizeof ( float ) );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "atlas upload: %s", hipGetErrorString ( e ) );
+    if ( int rc = launch_atlas ( s, A, c.d[2], c.d[0], c.d[1], nullptr ) ) return rc;
+    e = c.down ( 0, points, n * sizeof ( TerraAmdPoint ) );
+    if ( e == hipSuccess && texels ) e = c.down ( 1, texels, n * sizeof ( TerraAmdAtlasTexel ) );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "atlas download: %s", hipGetErrorString ( e ) );
+    return 0;
+}
+static int dilate_check ( const void* data, int channels, const void* valid, int width, int height, int passes, const char* what ) {
+    if ( !data || !valid ) return fail ( kTerraAmdErrBadArgument, "%s: null data or valid buffer", what );
+    if ( channels < 1 || channels > 4 ) return fail ( kTerraAmdErrBadArgument, "%s: channels %d: 1 .. 4", what, channels );
+    if ( width < 1 || height < 1 ) return fail ( kTerraAmdErrBadArgument, "%s: frame %d x %d", what, width, height );
+    if ( passes < 0 || passes > 64 ) return fail ( kTerraAmdErrBadArgument, "%s: passes %d: 0 .. 64", what, passes );
+    return 0;
+}
+extern "C" int terra_amd_dilate_device ( void* d_data, int channels, void* d_valid, int width, int height, int passes, void* stream ) {
+    if ( int rc = dilate_check ( d_data, channels, d_valid, width, height, passes, "terra_amd_dilate_device" ) ) return rc;
+    if ( passes == 0 ) return 0;
+    const hipError_t e = terra_launch_dilate ( ( float* ) d_data, channels, ( int* ) d_valid, ( uint32_t ) width, ( uint32_t ) height, passes, ( hipStream_t ) stream );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "dilate launch: %s", hipGetErrorString ( e ) );
+    return 0;
+}
+extern "C" int terra_amd_dilate ( float* data, int channels, int* valid, int width, int height, int passes ) {
+    if ( int rc = dilate_check ( data, channels, valid, width, height, passes, "terra_amd_dilate" ) ) return rc;
+    if ( passes == 0 ) return 0;
+    if ( terra_amd_device_count() <= 0 ) return fail ( kTerraAmdErrNoDevice, "no HIP device visible" );
+    const size_t n = ( size_t ) width * ( size_t ) height;
+    FrameCopy c;
+    hipError_t e = c.up ( 0, data, n * ( size_t ) channels * sizeof ( float ) );
+    if ( e == hipSuccess ) e = c.up ( 1, valid, n * sizeof ( int ) );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "dilate upload: %s", hipGetErrorString ( e ) );
+    if ( int rc = terra_amd_dilate_device ( c.d[0], channels, c.d[1], width, height, passes, nullptr ) ) return rc;
+    e = c.down ( 0, data, n * ( size_t ) channels * sizeof ( float ) );
+    if ( e == hipSuccess ) e = c.down ( 1, valid, n * sizeof ( int ) );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "dilate download: %s", hipGetErrorString ( e ) );
+    return 0;
+}
+
 // terra_render() over the scene's device set from one process: device k renders the tiles t with t % N == k of the rectangle (terra_amd_shard_owner; the same kernels
 // with DevRenderParams::rank / world set) into its own staging frame, packs them, and ONE gather -- RCCL over xGMI, issued from here (multi_gpu.cpp) -- brings every
 // rank's packed tiles to the primary device, which unpacks them into its staging frame and copies the rectangle to the host once. The reference's client shards tiles over

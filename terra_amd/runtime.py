@@ -147,6 +147,7 @@ _EXTRA = {
     **api.RAY_SOURCE_SIGNATURES,
     **api.LENS_SIGNATURES,
     **api.POINT_SIGNATURES,
+    **api.BAKE_SIGNATURES,
     **api.EXACT_SQRT_SIGNATURES,
 }
 
@@ -638,6 +639,73 @@ def irradiance(lib, scene, positions, normals, spp_batches: int = 1, distributio
         acc = res[..., :3].view(torch.float32)
         samples = res[..., 3:4].to(torch.float32)
         return unfold_pixels(acc / samples * math.pi, n).contiguous()
+
+
+# ---------------------------------------------------------------------------
+# lightmap baking (include/terra_amd.h "Lightmap baking")
+# ---------------------------------------------------------------------------
+
+def atlas_of(width: int, height: int, uv_scale=None, uv_offset=None, margin: float = 0.5) -> api.Atlas:
+    """api.Atlas of width x height texels; uv_scale / uv_offset (pairs) default to (1, 1) / (0, 0): uvs already in texels"""
+    a = api.Atlas()
+    a.width, a.height, a.margin = width, height, margin
+    a.uv_scale[:] = (1.0, 1.0) if uv_scale is None else tuple(uv_scale)
+    a.uv_offset[:] = (0.0, 0.0) if uv_offset is None else tuple(uv_offset)
+    return a
+
+
+def _current_stream():
+    import torch
+    return torch.cuda.current_stream().cuda_stream or None
+
+
+def atlas_points(lib, scene, atlas: api.Atlas, uvs=None):
+    """terra_amd_atlas_points_device on the current torch stream: (points, texels) in HBM -- points float32 [height, width, 8], the api.POINT_DTYPE records
+    render_points_device takes as they are; texels int32 [height, width, 4], api.ATLAS_TEXEL_DTYPE records (triangle, then the bits of wb, wc, distance2).
+    uvs: float32 [triangles, 6] (ua va ub vb uc vc) in HBM, or None = the scene's own texcoords."""
+    import torch
+    if uvs is not None and not (isinstance(uvs, torch.Tensor) and uvs.is_cuda and uvs.dtype == torch.float32 and uvs.is_contiguous() and uvs.dim() == 2 and uvs.shape[1] == 6):
+        raise TerraAmdError("atlas_points takes uvs as a contiguous float32 tensor [triangles, 6] on the scene's device")
+    points = torch.empty((atlas.height, atlas.width, 8), dtype=torch.float32, device="cuda")
+    texels = torch.empty((atlas.height, atlas.width, 4), dtype=torch.int32, device="cuda")
+    check(lib.atlas_points_device(scene, C.byref(atlas), uvs.data_ptr() if uvs is not None else None, points.data_ptr(), texels.data_ptr(), _current_stream()),
+          "terra_amd_atlas_points_device")
+    return points, texels
+
+
+def dilate(data, valid, passes: int):
+    """terra_amd_dilate_device in place on the current torch stream: data float32 [height, width, channels] (or [height, width]), valid int32 [height, width], in HBM"""
+    import torch
+    if not (isinstance(data, torch.Tensor) and data.is_cuda and data.dtype == torch.float32 and data.is_contiguous() and data.dim() in (2, 3)):
+        raise TerraAmdError("dilate takes data as a contiguous float32 tensor [height, width, channels] in HBM")
+    h, w = int(data.shape[0]), int(data.shape[1])
+    if not (isinstance(valid, torch.Tensor) and valid.is_cuda and valid.dtype == torch.int32 and valid.is_contiguous() and tuple(valid.shape) == (h, w)):
+        raise TerraAmdError(f"dilate takes valid as a contiguous int32 tensor [{h}, {w}] in HBM")
+    check(load().dilate_device(data.data_ptr(), int(data.shape[2]) if data.dim() == 3 else 1, valid.data_ptr(), w, h, passes, _current_stream()), "terra_amd_dilate_device")
+
+
+_dilate = dilate          # (bake_lightmap's `dilate` argument is the pass count)
+
+
+def bake_lightmap(lib, scene, width: int, height: int, uvs=None, uv_scale=None, margin: float = 0.5, dilate: int = 2, batches: int = 1):
+    """A lightmap of the committed scene -> (irradiance float32 [height, width, 3], texels as atlas_points returns them), in HBM: atlas_points ->
+    `batches` render_points_device calls (distribution 0) of the scene's samples_per_pixel each -> PI * acc / samples -> `dilate` passes of dilation with
+    triangle >= 0 as the validity (an uncovered texel that no pass reaches stays 0). Everything is queued on the current torch stream."""
+    import math
+    import torch
+    if batches < 1:
+        raise TerraAmdError("bake_lightmap: batches must be at least 1")
+    points, texels = atlas_points(lib, scene, atlas_of(width, height, uv_scale=uv_scale, margin=margin), uvs)
+    fb = DeviceFramebuffer(width, height)
+    ps = point_sampling(0)
+    stream = _current_stream()
+    for _ in range(batches):
+        render_points_device(lib, scene, ps, points, fb, stream=stream)
+    res = fb.results.view(height, width, 4)
+    irradiance = (math.pi * res[..., :3].view(torch.float32) / res[..., 3:4].to(torch.float32)).contiguous()
+    valid = (texels[..., 0] >= 0).to(torch.int32).contiguous()
+    _dilate(irradiance, valid, dilate)
+    return irradiance, texels
 
 
 def render_device_sharded(lib, cam, scene, fb: DeviceFramebuffer, tile: int, rank: int, world: int, stream=None):

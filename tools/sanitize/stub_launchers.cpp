@@ -46,3 +46,5 @@ hipError_t terra_launch_temporal_reproject ( const DevTemporalParams&, const voi
 hipError_t terra_launch_query ( DevQueryParams, const void*, size_t, void*, bool, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_unit_texture_sample ( const DevTexture*, int, const float*, float* ) { return hipErrorNoDevice; }
 hipError_t terra_unit_texture_latlong ( const DevTexture*, int, const float*, float* ) { return hipErrorNoDevice; }
+hipError_t terra_launch_atlas_points ( const DevScene&, const DevAtlas&, const float*, void*, void*, hipStream_t ) { return hipErrorNoDevice; }
+hipError_t terra_launch_dilate ( float*, int, int*, uint32_t, uint32_t, int, hipStream_t ) { return hipErrorNoDevice; }
