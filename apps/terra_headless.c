@@ -36,6 +36,7 @@
  *       [--frames N] [--camera-to px py pz dx dy dz] [--temporal ALPHA]
  *       [--camera-model pinhole|thinlens|ortho|equirect|fisheye] [--aperture R] [--focus D] [--ortho-height H] [--fisheye-fov DEG]
  *       [--bake-lightmap [--atlas WxH] [--bake-margin M] [--bake-dilate N]]
+ *       [--bake-probes NXxNYxNZ [--probe-cells N]]
  *
  * Environment: the scene's environment attribute is a constant (--environment-color, default 0.4 0.52 1) or a lat-long map (--environment: Radiance .hdr with flat
  * or new-style run-length-encoded scanlines, orientation -Y H +X W, texel = m 2^(e - 136); or .pfm, either byte order, bottom row first), bound as a 3-component
@@ -93,6 +94,15 @@ typedef struct { int triangle; float wb, wc; float distance2; } BakeTexel;
 int         terra_amd_atlas_points ( HTerraScene, const void*, const float*, void*, void* ) __attribute__ ( ( weak ) );
 int         terra_amd_render_points ( HTerraScene, const void*, const void*, const TerraFramebuffer*, size_t, size_t, size_t, size_t ) __attribute__ ( ( weak ) );
 int         terra_amd_dilate ( float*, int, int*, int, int, int ) __attribute__ ( ( weak ) );
+/* probe harmonics (TerraAmdRay, TerraAmdProbeSH, TerraAmdProbeGrid and the calls of terra_amd.h "Ray-sourced rendering" / "Probe harmonics", restated for the same reason) */
+typedef struct { float origin[3]; float tmax; float direction[3]; float reserved; } ProbeRay;
+typedef struct { float c[9][3]; int cells; } ProbeSH;
+typedef struct { float origin[3]; int nx; float spacing[3]; int ny; int nz; int reserved[3]; } ProbeGrid;
+int         terra_amd_scene_vertex_points ( HTerraScene, void*, int ) __attribute__ ( ( weak ) );
+int         terra_amd_probe_grid_points ( const void*, void*, int ) __attribute__ ( ( weak ) );
+int         terra_amd_probe_rays ( const void*, size_t, int, const float*, void* ) __attribute__ ( ( weak ) );
+int         terra_amd_render_rays ( HTerraScene, const void*, const TerraFramebuffer*, size_t, size_t, size_t, size_t ) __attribute__ ( ( weak ) );
+int         terra_amd_sh_project ( const TerraFramebuffer*, const void*, size_t, int, int, void* ) __attribute__ ( ( weak ) );
 /* --camera-model: non-NULL = every render call and its AOV call go through the lens door */
 static const Lens* g_lens = NULL;
 static void render_rect ( const TerraCamera* cam, HTerraScene scene, const TerraFramebuffer* fb, size_t x, size_t y, size_t w, size_t h ) {
@@ -625,6 +635,11 @@ static const char* kHelp =
     "           terra_amd_atlas_points lays a surface point under every texel whose centre a triangle covers or comes within M texels of (0 .. 4, default 0.5),\n"
     "           terra_amd_render_points gathers --spp cosine-weighted samples per --passes pass at each (PI * sum / samples), terra_amd_dilate grows the lit texels\n"
     "           N passes (0 .. 64, default 2) into the gutters. The camera flags, --aov, --denoise*, --adaptive, --frames and --gpus are ignored.\n"
+    "  --bake-probes NXxNYxNZ [--probe-cells N] (libterra_amd.so only): writes, in place of the camera's image, the order-2 spherical harmonics of the radiance\n"
+    "           arriving at a grid of NX x NY x NZ light probes, cell-centred over the scene's bounding box (probe (ix, iy, iz) at lo + (i + 0.5) * (hi - lo) / count,\n"
+    "           index (iz * NY + iy) * NX + ix), as a float RGB image (.pfm / .hdr) 9 wide and NX * NY * NZ high: pixel (k, p) is coefficient k of probe p.\n"
+    "           terra_amd_probe_rays lays N x N (1 .. 64, default 16) equal-area directions about every probe, terra_amd_render_rays gathers --spp samples per\n"
+    "           --passes pass along each into one frame, terra_amd_sh_project reduces it. The camera flags, --aov, --denoise*, --adaptive, --frames and --gpus are ignored.\n"
     "OBJ/MTL import (--normals apollo, the default): the policy of the reference client's importer (satellite/include/Apollo.h under the\n"
     "options of satellite/src/Scene.cpp:83-93) RESTATED in this tool and pinned by hand-derived fixtures -- restated, not executed: Apollo.h\n"
     "does not compile with this image's toolchains. Everything after the TerraObject fill (commit, render, export) is the pinned path.\n";
@@ -641,6 +656,7 @@ int main ( int argc, char** argv ) {
     const char* dump_path = NULL; int no_render = 0;
     int camera_model = 0; float aperture = 0.f, focus = 1.f, ortho_height = 2.f, fisheye_fov = 180.f;      /* camera_model: 0 pinhole, 1 thinlens, 2 ortho, 3 equirect, 4 fisheye */
     int bake = 0, atlas_w = 256, atlas_h = 256, bake_dilate = 2; float bake_margin = 0.5f;      /* --bake-lightmap */
+    int probes_on = 0, probe_n[3] = { 1, 1, 1 }, probe_cells = 16;      /* --bake-probes */
     float fov = 45.f, exposure = 1.f, gamma = 2.2f, jitter = 0.f;
     unsigned long long seed = 0;
     const char* env_path = NULL; float env_rgb[3] = { 0.4f, 0.52f, 1.f }; int env_light = 0, env_sampling = 0;      /* env_sampling: 0 off, 1 table, 2 mis */
@@ -691,6 +707,11 @@ int main ( int argc, char** argv ) {
         else if ( !strcmp ( a, "--atlas" ) ) { if ( sscanf ( NEXT(), "%dx%d", &atlas_w, &atlas_h ) != 2 || atlas_w < 1 || atlas_w > 16384 || atlas_h < 1 || atlas_h > 16384 ) { fprintf ( stderr, "terra_headless: --atlas WxH, each 1 .. 16384\n" ); return 64; } }
         else if ( !strcmp ( a, "--bake-margin" ) ) { bake_margin = ( float ) atof ( NEXT() ); if ( !( bake_margin >= 0.f && bake_margin <= 4.f ) ) { fprintf ( stderr, "terra_headless: --bake-margin 0 .. 4\n" ); return 64; } }
         else if ( !strcmp ( a, "--bake-dilate" ) ) { bake_dilate = atoi ( NEXT() ); if ( bake_dilate < 0 || bake_dilate > 64 ) { fprintf ( stderr, "terra_headless: --bake-dilate 0 .. 64\n" ); return 64; } }
+        else if ( !strcmp ( a, "--bake-probes" ) ) {
+            probes_on = 1;
+            if ( sscanf ( NEXT(), "%dx%dx%d", &probe_n[0], &probe_n[1], &probe_n[2] ) != 3 || probe_n[0] < 1 || probe_n[1] < 1 || probe_n[2] < 1 || ( double ) probe_n[0] * probe_n[1] * probe_n[2] > 1048576. ) { fprintf ( stderr, "terra_headless: --bake-probes NXxNYxNZ, each at least 1, at most 1048576 probes\n" ); return 64; }
+        }
+        else if ( !strcmp ( a, "--probe-cells" ) ) { probe_cells = atoi ( NEXT() ); if ( probe_cells < 1 || probe_cells > 64 ) { fprintf ( stderr, "terra_headless: --probe-cells 1 .. 64\n" ); return 64; } }
         else if ( !strcmp ( a, "--camera-to" ) && i + 6 < argc ) {
             cam_to.position = terra_f3_set ( ( float ) atof ( argv[i + 1] ), ( float ) atof ( argv[i + 2] ), ( float ) atof ( argv[i + 3] ) );
             cam_to.direction = terra_f3_set ( ( float ) atof ( argv[i + 4] ), ( float ) atof ( argv[i + 5] ), ( float ) atof ( argv[i + 6] ) ); i += 6; have_camera_to = 1;
@@ -774,6 +795,41 @@ int main ( int argc, char** argv ) {
         printf ( "%s: %zu triangles, %zu materials -> lightmap %s (%zux%zu texels, %zu covered, %zu spp x %d)\n", argv[1], m.faces.n, m.mtls.n, argv[2], aw, ah, covered, spp, passes );
         free ( points ); free ( texels ); free ( valid );
         terra_framebuffer_destroy ( &lm );
+        terra_scene_destroy ( scene );
+        if ( env_path ) terra_texture_destroy ( &env_tex );
+        return 0;
+    }
+    if ( probes_on && ( !terra_amd_scene_vertex_points || !terra_amd_probe_grid_points || !terra_amd_probe_rays || !terra_amd_render_rays || !terra_amd_sh_project ) ) {
+        fprintf ( stderr, "terra_headless: --bake-probes needs libterra_amd.so; ignored, the camera's image is written\n" ); probes_on = 0;
+    }
+    if ( probes_on ) {          /* the probe frame: cell c of probe p at pixel (c, p); one projection of everything the passes gathered */
+        const size_t P = ( size_t ) probe_n[0] * ( size_t ) probe_n[1] * ( size_t ) probe_n[2], K = ( size_t ) probe_cells * ( size_t ) probe_cells;
+        terra_scene_commit ( scene );
+        const int nv = terra_amd_scene_vertex_points ( scene, NULL, 0 );
+        BakePoint* verts = nv > 0 ? aligned_alloc ( 16, ( size_t ) nv * sizeof ( BakePoint ) ) : NULL;
+        BakePoint* probes = aligned_alloc ( 16, P * sizeof ( BakePoint ) ); ProbeRay* rays = aligned_alloc ( 16, P * K * sizeof ( ProbeRay ) ); ProbeSH* sh = aligned_alloc ( 16, P * sizeof ( ProbeSH ) );
+        TerraFramebuffer frame, image;
+        if ( !verts || !probes || !rays || !sh || !terra_framebuffer_create ( &frame, K, P ) || !terra_framebuffer_create ( &image, 9, P ) ) { fprintf ( stderr, "terra_headless: out of memory\n" ); return 71; }
+        int rc = terra_amd_scene_vertex_points ( scene, verts, nv ) < 0;
+        ProbeGrid grid; memset ( &grid, 0, sizeof grid );
+        grid.nx = probe_n[0]; grid.ny = probe_n[1]; grid.nz = probe_n[2];
+        for ( int a = 0; a < 3; ++a ) {          /* cell-centred over the bounding box; an axis the scene has no extent on gets the spacing 1 */
+            float lo = verts[0].position[a], hi = lo;
+            for ( int k = 1; k < nv; ++k ) { const float v = verts[k].position[a]; if ( v < lo ) lo = v; if ( v > hi ) hi = v; }
+            float sp = ( hi - lo ) / ( float ) probe_n[a];
+            if ( !( sp > 0.f ) ) sp = 1.f;
+            grid.spacing[a] = sp; grid.origin[a] = lo + 0.5f * sp;
+        }
+        if ( !rc ) rc = terra_amd_probe_grid_points ( &grid, probes, ( int ) P ) < 0;
+        if ( !rc ) rc = terra_amd_probe_rays ( probes, P, probe_cells, NULL, rays );
+        for ( int pass = 0; pass < passes && !rc; ++pass ) rc = terra_amd_render_rays ( scene, rays, &frame, 0, 0, K, P );
+        if ( !rc ) rc = terra_amd_sh_project ( &frame, rays, P, probe_cells, 0, sh );
+        if ( rc ) { fprintf ( stderr, "terra_headless: %s\n", terra_amd_last_error && *terra_amd_last_error() ? terra_amd_last_error() : "the probe bake failed" ); return 70; }
+        for ( size_t p = 0; p < P; ++p ) for ( int k = 0; k < 9; ++k ) image.pixels[9 * p + ( size_t ) k] = terra_f3_set ( sh[p].c[k][0], sh[p].c[k][1], sh[p].c[k][2] );
+        if ( !write_image ( argv[2], &image ) ) { fprintf ( stderr, "terra_headless: cannot write %s\n", argv[2] ); return 73; }
+        printf ( "%s: %zu triangles, %zu materials -> probes %s (%dx%dx%d probes, %d x %d cells, %zu spp x %d)\n", argv[1], m.faces.n, m.mtls.n, argv[2], probe_n[0], probe_n[1], probe_n[2], probe_cells, probe_cells, spp, passes );
+        free ( verts ); free ( probes ); free ( rays ); free ( sh );
+        terra_framebuffer_destroy ( &frame ); terra_framebuffer_destroy ( &image );
         terra_scene_destroy ( scene );
         if ( env_path ) terra_texture_destroy ( &env_tex );
         return 0;

@@ -900,6 +900,86 @@ int terra_amd_dilate_device ( void* d_data, int channels, void* d_valid, int wid
 /* The same on host memory; synchronous. */
 int terra_amd_dilate ( float* data, int channels, int* valid, int width, int height, int passes );
 
+/* ---- Probe harmonics: stratified probe rays, projection onto order-2 spherical harmonics, irradiance from them ------------------------------------------------
+   An irradiance volume is: per probe, a stratified set of directions over the sphere (terra_amd_probe_rays*); radiance along them through the ray door
+   (terra_amd_render_rays*); the frame reduced to nine real SH coefficients per channel (terra_amd_sh_project*); and, at shading time, the cosine-lobe evaluation
+   of those coefficients for a normal, from one probe or blended trilinearly in a grid of probes (terra_amd_sh_irradiance*). The reference has no such calls: this
+   is the library's own definition, off unless called. None of the calls takes a scene; all run on the calling thread's current device.
+   Probe frame.  P probes, each a TerraAmdPoint: position = where the probe is, normal = the pole of its direction set; a probe is inactive exactly when the point
+     door says so ("Point rendering"). cells = n, 1 .. 64, gives K = n * n direction cells per probe. The probe frame is an ordinary framebuffer K wide and P high:
+     pixel (c, p) is cell c of probe p; cell c has i = c % n, j = c / n. K * P <= 2^31 - 1. P = 0 succeeds and launches nothing.
+   Rule of the rays.  binary32, IEEE division. jitter: NULL, or 2 * K floats (ju, jv) per cell, shared by all probes; NULL = (0.5, 0.5), the cell's centre.
+       g1 = ((float) i + ju) / (float) n,  g2 = ((float) j + jv) / (float) n,
+     each then clamped by two comparisons: !(g >= 0) becomes 0 (so a NaN becomes 0), g > 1 - 2^-24 becomes 1 - 2^-24.
+     The ray is exactly the record terra_amd_unit_point_rays() gives for that probe with distribution 1 and the pair (g1, g2): tmax = FLT_MAX, reserved = 0.
+     An inactive probe's K records are all-zero (inactive at the ray door). The map is equal-area: every cell subtends 4 PI / K.
+   Rule of the projection.  binary64 throughout, in exactly the order written, no fused multiply-add, IEEE division; (double) of a binary32 is exact.
+     Cell c of probe p contributes unless its samples <= 0 or its ray is inactive by the ray door's rule (a direction of exactly (0, 0, 0), or an origin or
+     direction component that is not finite). A cell that does not contribute adds +0.
+     L_ch = (double) acc[ch] / (double) samples. The direction (x, y, z) is the stored binary32 direction widened, used as given and not normalised.
+       Y0 = 0.28209479177387814
+       Y1 = 0.4886025119029199 * y            Y2 = 0.4886025119029199 * z            Y3 = 0.4886025119029199 * x
+       Y4 = 1.0925484305920792 * (x * y)      Y5 = 1.0925484305920792 * (y * z)      Y6 = 0.31539156525252005 * ((3.0 * (z * z)) - 1.0)
+       Y7 = 1.0925484305920792 * (x * z)      Y8 = 0.5462742152960396 * ((x * x) - (y * y))
+     The term of a cell is L_ch * Y_k. Lane l of 64 adds its cells c = l, l + 64, l + 128, ... in ascending order onto +0.0; the 64 partials are then combined
+     in six steps s = 32, 16, 8, 4, 2, 1, in each partial[l] = partial[l] + partial[l + s] for l < s.
+     new = partial[0] * (12.566370614359172 / (double) K). batch == 0: c[k][ch] = (float) new. batch > 0:
+       c[k][ch] = (float) ((((double) c_old * (double) batch) + new) / (double) (batch + 1))
+     -- the running mean of batches rendered with different jitter, without a second buffer. cells = the cells that contributed in this call.
+     Any directions of uniform density over the sphere are allowed, not only terra_amd_probe_rays' own. No atomics: the same inputs give the same bits.
+   Rule of the irradiance.  binary64, as above. A query is a TerraAmdPoint; the output is four floats per query, (E_r, E_g, E_b, 0).
+     q = (nx*nx + ny*ny) + nz*nz of the widened normal. A normal component that is not finite, or q that is 0 or not finite: the output is (0, 0, 0, 0).
+     Otherwise N = normal / sqrt(q), the correctly rounded binary64 square root, IEEE division.
+     Index mode (grid == NULL; index required): the coefficients of probe index[i], widened; an index outside [0, probes) gives (0, 0, 0, 0).
+     Grid mode (grid != NULL; index ignored; probes == nx * ny * nz): per axis a, f = ((double) position_a - (double) origin_a) / (double) spacing_a; a NaN f
+       gives (0, 0, 0, 0); f < 0 becomes 0, f > count_a - 1 becomes count_a - 1 (two comparisons); i = (int) floor(f), reduced to max(count_a - 2, 0) if it
+       exceeds that; t = f - (double) i; the upper neighbour is min(i + 1, count_a - 1). Probe (ix, iy, iz) has the index (iz * ny + iy) * nx + ix. The eight
+       corners are visited in the order (dz, dy, dx) = 000, 001, 010, 011, 100, 101, 110, 111, each with the weight (wz * wy) * wx, w = 1 - t for the lower
+       corner and t for the upper; per coefficient the sum is weight * (double) c, added in that order starting from the first corner's term.
+     E_ch = sum over k ascending, starting from the k = 0 term, of ((A_k * c_k) * Y_k(N)); A_0 = 3.141592653589793, A_1..3 = 2.0943951023931953,
+       A_4..8 = 0.7853981633974483. The output is (float) E_ch.
+   Calls.  Every refusal is kTerraAmdErrBadArgument, decided before a device is asked for and with nothing written: a NULL required buffer; a device or host
+     record buffer (probes, rays, results, sh, queries, the device form's output) that is not 16-byte aligned; cells outside 1 .. 64; K * P above 2^31 - 1; batch < 0; more than
+     2^31 - 1 queries; for a grid: a count below 1, a product of the counts that differs from `probes`, a spacing that is not finite or is 0, an origin that is
+     not finite, non-zero reserved; for terra_amd_sh_project(): a framebuffer that is not K wide and P high. */
+typedef struct {              /* 112 bytes = seven 16-byte words, 16-byte aligned in a buffer */
+    float c[9][3];            /* +0   c[k][channel], k as Y_k above */
+    int   cells;              /* +108 cells that contributed to the last projection */
+} TerraAmdProbeSH;
+typedef struct {              /* 48 bytes */
+    float origin[3];          /* +0  position of probe (0, 0, 0); finite */
+    int   nx;                 /* +12 probes along x, >= 1 */
+    float spacing[3];         /* +16 distance between neighbours per axis; finite, not 0 */
+    int   ny, nz;             /* +28 */
+    int   reserved[3];        /* +36 zero */
+} TerraAmdProbeGrid;
+TERRA_ABI_ASSERT ( sizeof ( TerraAmdProbeSH ) == 112 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdProbeSH, cells ) == 108 );
+TERRA_ABI_ASSERT ( sizeof ( TerraAmdProbeGrid ) == 48 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdProbeGrid, nx ) == 12 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdProbeGrid, spacing ) == 16 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdProbeGrid, ny ) == 28 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdProbeGrid, nz ) == 32 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdProbeGrid, reserved ) == 36 );
+/* d_probes: `probes` TerraAmdPoint; d_jitter: 2 * cells * cells floats or NULL; d_rays: probes * cells * cells TerraAmdRay -- what terra_amd_render_rays_device()
+   takes as a frame cells * cells wide and `probes` high. Asynchronous on `stream`. */
+int terra_amd_probe_rays_device ( const void* d_probes, size_t probes, int cells, const void* d_jitter, void* d_rays, void* stream );
+/* The same on host memory; synchronous. */
+int terra_amd_probe_rays ( const TerraAmdPoint* probes, size_t probes_n, int cells, const float* jitter, TerraAmdRay* rays );
+/* d_results: the probe frame's running sums {float acc[3]; int samples}, nothing else of the frame is read; d_rays: the rays it was rendered along;
+   d_sh: `probes` TerraAmdProbeSH, read as well where batch > 0. Asynchronous on `stream`. */
+int terra_amd_sh_project_device ( const void* d_results, const void* d_rays, size_t probes, int cells, int batch, void* d_sh, void* stream );
+/* The same on a host framebuffer (cells * cells wide, `probes` high) and host records; synchronous. */
+int terra_amd_sh_project ( const TerraFramebuffer* framebuffer, const TerraAmdRay* rays, size_t probes, int cells, int batch, TerraAmdProbeSH* sh );
+/* d_sh: `probes` TerraAmdProbeSH; grid: host memory, or NULL = index mode; d_points: n TerraAmdPoint; d_index: n ints (index mode); d_out: n * 4 floats.
+   Asynchronous on `stream`. */
+int terra_amd_sh_irradiance_device ( const void* d_sh, size_t probes, const TerraAmdProbeGrid* grid, const void* d_points, const void* d_index, size_t n, void* d_out, void* stream );
+/* The same on host memory; synchronous. */
+int terra_amd_sh_irradiance ( const TerraAmdProbeSH* sh, size_t probes, const TerraAmdProbeGrid* grid, const TerraAmdPoint* points, const int* index, size_t n, float* out4 );
+/* The grid's probes as points, on the host (no device is touched), in index order: position on axis a is (float) ((double) origin_a + (double) i_a *
+   (double) spacing_a), the normal (0, 0, 1). Returns nx * ny * nz whatever the capacity, or a negative status, and writes the first min(capacity, probes) records. */
+int terra_amd_probe_grid_points ( const TerraAmdProbeGrid* grid, TerraAmdPoint* out, int capacity );
+
 /* Tile-sharded form for one-process-per-GPU rendering (the reference shards
    the same way over CPU threads: satellite/src/Renderer.cpp:316-350): the
    rectangle is cut into tile_size x tile_size tiles numbered row-major and this

@@ -283,6 +283,33 @@ BAKE_SIGNATURES = {
     "terra_amd_dilate": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int]),
 }
 
+
+class ProbeSH(Structure):
+    """TerraAmdProbeSH (include/terra_amd.h "Probe harmonics"): nine real SH coefficients per channel, c[k][channel], and the cells that contributed; 112 bytes"""
+    _fields_ = [("c", (c_float * 3) * 9), ("cells", c_int)]
+
+
+class ProbeGrid(Structure):
+    """TerraAmdProbeGrid: nx * ny * nz probes, probe (ix, iy, iz) at origin + i * spacing with the index (iz * ny + iy) * nx + ix; 48 bytes"""
+    _fields_ = [("origin", c_float * 3), ("nx", c_int), ("spacing", c_float * 3), ("ny", c_int), ("nz", c_int), ("reserved", c_int * 3)]
+
+
+ABI_SIZES.update({ProbeSH: 112, ProbeGrid: 48})
+assert C.sizeof(ProbeSH) == 112 and C.sizeof(ProbeGrid) == 48
+PROBE_SH_DTYPE = np.dtype([("c", np.float32, (9, 3)), ("cells", np.int32)])
+assert PROBE_SH_DTYPE.itemsize == 112
+
+# ... and of probe harmonics (include/terra_amd.h "Probe harmonics")
+PROBE_SIGNATURES = {
+    "terra_amd_probe_rays_device": (c_int, [c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_void_p]),
+    "terra_amd_probe_rays": (c_int, [c_void_p, c_size_t, c_int, c_void_p, c_void_p]),
+    "terra_amd_sh_project_device": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p, c_void_p]),
+    "terra_amd_sh_project": (c_int, [POINTER(TerraFramebuffer), c_void_p, c_size_t, c_int, c_int, c_void_p]),
+    "terra_amd_sh_irradiance_device": (c_int, [c_void_p, c_size_t, POINTER(ProbeGrid), c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "terra_amd_sh_irradiance": (c_int, [c_void_p, c_size_t, POINTER(ProbeGrid), c_void_p, c_void_p, c_size_t, c_void_p]),
+    "terra_amd_probe_grid_points": (c_int, [POINTER(ProbeGrid), c_void_p, c_int]),
+}
+
 # entry points of include/Terra.h + include/TerraPresets.h, name -> (restype, argtypes)
 API_SIGNATURES = {
     "scene_create": (c_void_p, []),

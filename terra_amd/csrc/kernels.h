@@ -96,6 +96,20 @@ struct DevAtlas {
 hipError_t terra_launch_atlas_points ( const DevScene& sc, const DevAtlas& atlas, const float* uvs, void* points, void* texels, hipStream_t stream );
 hipError_t terra_launch_dilate ( float* data, int channels, int* valid, uint32_t width, uint32_t height, int passes, hipStream_t stream );
 
+// probe harmonics (probe_kernels.hip; include/terra_amd.h "Probe harmonics"): all pointers are device pointers, records 16-byte aligned; no scratch, no scene.
+// count probes of cells * cells direction cells each (count * cells * cells <= 2^31 - 1)
+struct DevProbeGrid {
+    int32_t on;                 // 0: index mode (the rest is not looked at)
+    int32_t count[3];           // probes along x, y, z
+    float   origin[3], spacing[3];
+};
+// probes: count TerraAmdPoint; jitter: 2 * cells * cells floats or nullptr = cell centres; rays: count * cells * cells TerraAmdRay
+hipError_t terra_launch_probe_rays ( const void* probes, uint32_t count, uint32_t cells, const float* jitter, void* rays, hipStream_t stream );
+// results: the frame's running sums {float acc[3]; int samples}, rays as above; sh: count TerraAmdProbeSH, read as well where batch > 0
+hipError_t terra_launch_sh_project ( const void* results, const void* rays, uint32_t count, uint32_t cells, int batch, void* sh, hipStream_t stream );
+// sh: probes TerraAmdProbeSH; points: n TerraAmdPoint; index: n ints (index mode only); out: n float4
+hipError_t terra_launch_sh_irradiance ( const void* sh, uint32_t probes, const DevProbeGrid& grid, const void* points, const int* index, uint32_t n, void* out, hipStream_t stream );
+
 hipError_t terra_fill_sincos24 ( float2* table, hipStream_t stream );    // DevScene::sincos24: 2^24 entries (128 MB), device pointer
 
 // unit-level launchers: all pointers are DEVICE pointers, n items, synchronous semantics left to the caller

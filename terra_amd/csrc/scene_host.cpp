@@ -2672,6 +2672,148 @@ extern "C" int terra_amd_dilate ( float* data, int channels, int* valid, int wid
     return 0;
 }
 
+// ---- probe harmonics: probe rays, SH projection, irradiance (probe_kernels.hip; include/terra_amd.h "Probe harmonics") --------------------------------------
+static_assert ( sizeof ( TerraAmdProbeSH ) == 112 && sizeof ( TerraAmdProbeGrid ) == 48, "TerraAmdProbeSH must be 112 bytes, TerraAmdProbeGrid 48" );
+// a required record buffer: there, and 16-byte aligned
+static int probe_buffer ( const void* p, const char* name, const char* what ) {
+    if ( !p ) return fail ( kTerraAmdErrBadArgument, "%s: null %s buffer", what, name );
+    if ( ( uintptr_t ) p & 15u ) return fail ( kTerraAmdErrBadArgument, "%s: the %s buffer must be 16-byte aligned", what, name );
+    return 0;
+}
+// the frame of a probe set: cells 1 .. 64, cells * cells * probes <= 2^31 - 1
+static int probe_frame_check ( size_t probes, int cells, const char* what ) {
+    if ( cells < 1 || cells > 64 ) return fail ( kTerraAmdErrBadArgument, "%s: cells %d: 1 .. 64", what, cells );
+    if ( probes > ( size_t ) 0x7fffffff / ( ( size_t ) cells * ( size_t ) cells ) ) return fail ( kTerraAmdErrBadArgument, "%s: %zu probes of %d x %d cells: more than 2^31 - 1 rays", what, probes, cells, cells );
+    return 0;
+}
+// the one check of each call pair, made before the call asks for a device
+static int probe_rays_check ( const void* probes, size_t n, int cells, const void* rays, const char* what ) {
+    if ( int rc = probe_frame_check ( n, cells, what ) ) return rc;
+    if ( int rc = probe_buffer ( probes, "probe", what ) ) return rc;
+    return probe_buffer ( rays, "ray", what );
+}
+static int sh_project_check ( const void* results, const void* rays, size_t probes, int cells, int batch, const void* sh, const char* what ) {
+    if ( int rc = probe_frame_check ( probes, cells, what ) ) return rc;
+    if ( batch < 0 ) return fail ( kTerraAmdErrBadArgument, "%s: batch %d", what, batch );
+    if ( int rc = probe_buffer ( results, "result", what ) ) return rc;
+    if ( int rc = probe_buffer ( rays, "ray", what ) ) return rc;
+    return probe_buffer ( sh, "coefficient", what );
+}
+static int probe_grid_check ( const TerraAmdProbeGrid* g, const char* what, size_t& count ) {
+    if ( g->nx < 1 || g->ny < 1 || g->nz < 1 ) return fail ( kTerraAmdErrBadArgument, "%s: grid %d x %d x %d: every count at least 1", what, g->nx, g->ny, g->nz );
+    const unsigned long long n = ( unsigned long long ) g->nx * ( unsigned long long ) g->ny;          // (< 2^62)
+    if ( n > 0x7fffffffull || n * ( unsigned long long ) g->nz > 0x7fffffffull ) return fail ( kTerraAmdErrBadArgument, "%s: grid %d x %d x %d: more than 2^31 - 1 probes", what, g->nx, g->ny, g->nz );
+    for ( int a = 0; a < 3; ++a ) {
+        if ( !std::isfinite ( g->spacing[a] ) || g->spacing[a] == 0.f ) return fail ( kTerraAmdErrBadArgument, "%s: grid spacing must be finite and not 0", what );
+        if ( !std::isfinite ( g->origin[a] ) ) return fail ( kTerraAmdErrBadArgument, "%s: grid origin must be finite", what );
+    }
+    for ( int r : g->reserved ) if ( r ) return fail ( kTerraAmdErrBadArgument, "%s: TerraAmdProbeGrid::reserved must be zero", what );
+    count = ( size_t ) ( n * ( unsigned long long ) g->nz );
+    return 0;
+}
+// out_aligned: the device form's output is stored in 16-byte words; the host form's is staged
+static int sh_irradiance_check ( const void* sh, size_t probes, const TerraAmdProbeGrid* grid, const void* points, const void* index, size_t n, const void* out, bool out_aligned, const char* what, DevProbeGrid& G ) {
+    G = DevProbeGrid{};
+    if ( probes > ( size_t ) 0x7fffffff || n > ( size_t ) 0x7fffffff ) return fail ( kTerraAmdErrBadArgument, "%s: %zu probes, %zu queries: at most 2^31 - 1 each", what, probes, n );
+    if ( grid ) {
+        size_t count = 0;
+        if ( int rc = probe_grid_check ( grid, what, count ) ) return rc;
+        if ( count != probes ) return fail ( kTerraAmdErrBadArgument, "%s: a grid of %zu probes with %zu coefficient records", what, count, probes );
+        G.on = 1; G.count[0] = grid->nx; G.count[1] = grid->ny; G.count[2] = grid->nz;
+        for ( int a = 0; a < 3; ++a ) { G.origin[a] = grid->origin[a]; G.spacing[a] = grid->spacing[a]; }
+    } else if ( !index ) return fail ( kTerraAmdErrBadArgument, "%s: null index buffer without a grid", what );
+    if ( int rc = probe_buffer ( sh, "coefficient", what ) ) return rc;
+    if ( int rc = probe_buffer ( points, "query", what ) ) return rc;
+    if ( !out ) return fail ( kTerraAmdErrBadArgument, "%s: null output buffer", what );
+    if ( out_aligned && ( ( uintptr_t ) out & 15u ) ) return fail ( kTerraAmdErrBadArgument, "%s: the output buffer must be 16-byte aligned", what );
+    return 0;
+}
+extern "C" int terra_amd_probe_rays_device ( const void* d_probes, size_t probes, int cells, const void* d_jitter, void* d_rays, void* stream ) {
+    if ( int rc = probe_rays_check ( d_probes, probes, cells, d_rays, "terra_amd_probe_rays_device" ) ) return rc;
+    if ( probes == 0 ) return 0;
+    const hipError_t e = terra_launch_probe_rays ( d_probes, ( uint32_t ) probes, ( uint32_t ) cells, ( const float* ) d_jitter, d_rays, ( hipStream_t ) stream );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "probe rays launch: %s", hipGetErrorString ( e ) );
+    return 0;
+}
+extern "C" int terra_amd_probe_rays ( const TerraAmdPoint* probes, size_t probes_n, int cells, const float* jitter, TerraAmdRay* rays ) {
+    if ( int rc = probe_rays_check ( probes, probes_n, cells, rays, "terra_amd_probe_rays" ) ) return rc;
+    if ( probes_n == 0 ) return 0;
+    if ( terra_amd_device_count() <= 0 ) return fail ( kTerraAmdErrNoDevice, "no HIP device visible" );
+    const size_t K = ( size_t ) cells * ( size_t ) cells, ray_bytes = probes_n * K * sizeof ( TerraAmdRay );
+    FrameCopy c;
+    hipError_t e = c.up ( 0, probes, probes_n * sizeof ( TerraAmdPoint ) );
+    if ( e == hipSuccess ) e = c.up ( 1, nullptr, ray_bytes );
+    if ( e == hipSuccess && jitter ) e = c.up ( 2, jitter, 2 * K * sizeof ( float ) );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "probe rays upload: %s", hipGetErrorString ( e ) );
+    if ( int rc = terra_amd_probe_rays_device ( c.d[0], probes_n, cells, c.d[2], c.d[1], nullptr ) ) return rc;
+    e = c.down ( 1, rays, ray_bytes );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "probe rays download: %s", hipGetErrorString ( e ) );
+    return 0;
+}
+extern "C" int terra_amd_sh_project_device ( const void* d_results, const void* d_rays, size_t probes, int cells, int batch, void* d_sh, void* stream ) {
+    if ( int rc = sh_project_check ( d_results, d_rays, probes, cells, batch, d_sh, "terra_amd_sh_project_device" ) ) return rc;
+    if ( probes == 0 ) return 0;
+    const hipError_t e = terra_launch_sh_project ( d_results, d_rays, ( uint32_t ) probes, ( uint32_t ) cells, batch, d_sh, ( hipStream_t ) stream );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "SH projection launch: %s", hipGetErrorString ( e ) );
+    return 0;
+}
+extern "C" int terra_amd_sh_project ( const TerraFramebuffer* fb, const TerraAmdRay* rays, size_t probes, int cells, int batch, TerraAmdProbeSH* sh ) {
+    const char* what = "terra_amd_sh_project";
+    if ( !fb ) return fail ( kTerraAmdErrBadArgument, "%s: null framebuffer", what );
+    if ( int rc = sh_project_check ( fb->results, rays, probes, cells, batch, sh, what ) ) return rc;
+    const size_t K = ( size_t ) cells * ( size_t ) cells;
+    if ( fb->width != K || fb->height != probes ) return fail ( kTerraAmdErrBadArgument, "%s: a framebuffer of %zu x %zu for %zu probes of %zu cells", what, fb->width, fb->height, probes, K );
+    if ( probes == 0 ) return 0;
+    if ( terra_amd_device_count() <= 0 ) return fail ( kTerraAmdErrNoDevice, "no HIP device visible" );
+    FrameCopy c;
+    hipError_t e = c.up ( 0, fb->results, probes * K * sizeof ( TerraRawIntegrationResult ) );
+    if ( e == hipSuccess ) e = c.up ( 1, rays, probes * K * sizeof ( TerraAmdRay ) );
+    if ( e == hipSuccess ) e = c.up ( 2, sh, probes * sizeof ( TerraAmdProbeSH ) );          // (batch > 0 reads the records)
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "SH projection upload: %s", hipGetErrorString ( e ) );
+    if ( int rc = terra_amd_sh_project_device ( c.d[0], c.d[1], probes, cells, batch, c.d[2], nullptr ) ) return rc;
+    e = c.down ( 2, sh, probes * sizeof ( TerraAmdProbeSH ) );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "SH projection download: %s", hipGetErrorString ( e ) );
+    return 0;
+}
+extern "C" int terra_amd_sh_irradiance_device ( const void* d_sh, size_t probes, const TerraAmdProbeGrid* grid, const void* d_points, const void* d_index, size_t n, void* d_out, void* stream ) {
+    DevProbeGrid G;
+    if ( int rc = sh_irradiance_check ( d_sh, probes, grid, d_points, d_index, n, d_out, true, "terra_amd_sh_irradiance_device", G ) ) return rc;
+    if ( n == 0 ) return 0;
+    const hipError_t e = terra_launch_sh_irradiance ( d_sh, ( uint32_t ) probes, G, d_points, ( const int* ) d_index, ( uint32_t ) n, d_out, ( hipStream_t ) stream );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "SH irradiance launch: %s", hipGetErrorString ( e ) );
+    return 0;
+}
+extern "C" int terra_amd_sh_irradiance ( const TerraAmdProbeSH* sh, size_t probes, const TerraAmdProbeGrid* grid, const TerraAmdPoint* points, const int* index, size_t n, float* out4 ) {
+    DevProbeGrid G;
+    if ( int rc = sh_irradiance_check ( sh, probes, grid, points, index, n, out4, false, "terra_amd_sh_irradiance", G ) ) return rc;
+    if ( n == 0 ) return 0;
+    if ( terra_amd_device_count() <= 0 ) return fail ( kTerraAmdErrNoDevice, "no HIP device visible" );
+    FrameCopy c;
+    hipError_t e = probes ? c.up ( 0, sh, probes * sizeof ( TerraAmdProbeSH ) ) : c.up ( 0, nullptr, 16 );          // (no probes: every index is outside the range)
+    if ( e == hipSuccess ) e = c.up ( 1, points, n * sizeof ( TerraAmdPoint ) );
+    if ( e == hipSuccess && !grid ) e = c.up ( 2, index, n * sizeof ( int ) );
+    if ( e == hipSuccess ) e = c.up ( 3, nullptr, n * 4 * sizeof ( float ) );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "SH irradiance upload: %s", hipGetErrorString ( e ) );
+    if ( int rc = terra_amd_sh_irradiance_device ( c.d[0], probes, grid, c.d[1], c.d[2], n, c.d[3], nullptr ) ) return rc;
+    e = c.down ( 3, out4, n * 4 * sizeof ( float ) );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "SH irradiance download: %s", hipGetErrorString ( e ) );
+    return 0;
+}
+// the grid's probes as points, in index order. Host only. Returns the number of probes whatever the capacity; writes the first min(capacity, probes) of them
+extern "C" int terra_amd_probe_grid_points ( const TerraAmdProbeGrid* grid, TerraAmdPoint* out, int capacity ) {
+    if ( !grid ) return fail ( kTerraAmdErrBadArgument, "terra_amd_probe_grid_points: null grid" );
+    size_t count = 0;
+    if ( int rc = probe_grid_check ( grid, "terra_amd_probe_grid_points", count ) ) return rc;
+    const size_t cap = ( out && capacity > 0 ) ? std::min ( ( size_t ) capacity, count ) : 0;
+    for ( size_t at = 0; at < cap; ++at ) {
+        const size_t i[3] = { at % ( size_t ) grid->nx, at / ( size_t ) grid->nx % ( size_t ) grid->ny, at / ( ( size_t ) grid->nx * ( size_t ) grid->ny ) };
+        TerraAmdPoint& q = out[at];
+        for ( int a = 0; a < 3; ++a ) q.position[a] = ( float ) ( ( double ) grid->origin[a] + ( double ) i[a] * ( double ) grid->spacing[a] );
+        q.reserved = 0.f; q.normal[0] = 0.f; q.normal[1] = 0.f; q.normal[2] = 1.f; q.reserved2 = 0.f;
+    }
+    return ( int ) count;
+}
+
 // terra_render() over the scene's device set from one process: device k renders the tiles t with t % N == k of the rectangle (terra_amd_shard_owner; the same kernels
 // with DevRenderParams::rank / world set) into its own staging frame, packs them, and ONE gather -- RCCL over xGMI, issued from here (multi_gpu.cpp) -- brings every
 // rank's packed tiles to the primary device, which unpacks them into its staging frame and copies the rectangle to the host once. The reference's client shards tiles over

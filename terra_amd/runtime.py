@@ -148,6 +148,7 @@ _EXTRA = {
     **api.LENS_SIGNATURES,
     **api.POINT_SIGNATURES,
     **api.BAKE_SIGNATURES,
+    **api.PROBE_SIGNATURES,
     **api.EXACT_SQRT_SIGNATURES,
 }
 
@@ -706,6 +707,121 @@ def bake_lightmap(lib, scene, width: int, height: int, uvs=None, uv_scale=None, 
     valid = (texels[..., 0] >= 0).to(torch.int32).contiguous()
     _dilate(irradiance, valid, dilate)
     return irradiance, texels
+
+
+# ---------------------------------------------------------------------------
+# probe harmonics (include/terra_amd.h "Probe harmonics")
+# ---------------------------------------------------------------------------
+
+def _records(t, words: int, what: str):
+    import torch
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype in (torch.float32, torch.int32) and t.is_contiguous() and t.numel() % words == 0):
+        raise TerraAmdError(f"{what}: a contiguous float32 or int32 tensor of {words} words per record in HBM")
+    if t.data_ptr() % 16:
+        raise TerraAmdError(f"{what}: the buffer must be 16-byte aligned")
+    return t.numel() // words
+
+
+def probe_grid(lib, origin, spacing, counts):
+    """(api.ProbeGrid, points): the grid of counts = (nx, ny, nz) probes, probe (ix, iy, iz) at origin + i * spacing, and its probes as api.POINT_DTYPE records in
+    index order with the normal (0, 0, 1) (terra_amd_probe_grid_points; needs no device)"""
+    g = api.ProbeGrid()
+    g.origin[:] = tuple(origin)
+    g.spacing[:] = tuple(spacing)
+    g.nx, g.ny, g.nz = (int(c) for c in counts)
+    n = check(lib.probe_grid_points(C.byref(g), None, 0), "terra_amd_probe_grid_points")
+    points = np.zeros(n, dtype=api.POINT_DTYPE)
+    check(lib.probe_grid_points(C.byref(g), points.ctypes.data, n), "terra_amd_probe_grid_points")
+    return g, points
+
+
+def probe_grid_over(lib, lo, hi, counts):
+    """probe_grid cell-centred over the box lo .. hi, as terra_headless --bake-probes lays it: per axis spacing = (hi - lo) / count in binary32 (1 where the box
+    has no extent), origin = lo + 0.5 * spacing"""
+    f = np.float32
+    spacing = [(f(h) - f(l)) / f(c) for l, h, c in zip(lo, hi, counts)]
+    spacing = [s if s > 0 else f(1) for s in spacing]
+    return probe_grid(lib, [f(l) + f(0.5) * s for l, s in zip(lo, spacing)], spacing, counts)
+
+
+def probe_rays(lib, probes, cells: int, jitter=None):
+    """terra_amd_probe_rays_device on the current torch stream: probes float32 [P, 8] in HBM (api.POINT_DTYPE records), jitter None (cell centres) or float32
+    [cells * cells, 2] in HBM -> rays float32 [P, cells * cells, 8], the frame render_rays_device takes as it is (cell c of probe p at pixel (c, p))"""
+    import torch
+    n = _records(probes, 8, "probe_rays probes")
+    if jitter is not None and not (isinstance(jitter, torch.Tensor) and jitter.is_cuda and jitter.dtype == torch.float32 and jitter.is_contiguous() and jitter.numel() == 2 * cells * cells):
+        raise TerraAmdError("probe_rays takes jitter as a contiguous float32 tensor [cells * cells, 2] in HBM")
+    rays = torch.empty((n, cells * cells, 8), dtype=torch.float32, device=probes.device)
+    check(lib.probe_rays_device(probes.data_ptr(), n, cells, jitter.data_ptr() if jitter is not None else None, rays.data_ptr(), _current_stream()), "terra_amd_probe_rays_device")
+    return rays
+
+
+def sh_project(lib, results, rays, cells: int, batch: int = 0, sh=None):
+    """terra_amd_sh_project_device on the current torch stream: results = the probe frame's running sums (a DeviceFramebuffer, or its results tensor), rays as
+    probe_rays returns them -> sh float32 [P, 28] in HBM: api.PROBE_SH_DTYPE records (27 coefficients c[k][channel], then the bits of cells; probe_sh_host gives
+    the records). batch > 0 averages into `sh`, the tensor an earlier call returned."""
+    import torch
+    results = results.results if isinstance(results, DeviceFramebuffer) else results
+    n = _records(rays, 8, "sh_project rays")
+    if _records(results, 4, "sh_project results") != n or n % (cells * cells):
+        raise TerraAmdError("sh_project: one result and one ray per cell of every probe")
+    probes = n // (cells * cells)
+    if sh is None:
+        if batch:
+            raise TerraAmdError("sh_project: batch > 0 averages into the records of the earlier batches: pass sh")
+        sh = torch.zeros((probes, 28), dtype=torch.float32, device=rays.device)
+    elif _records(sh, 28, "sh_project sh") != probes:
+        raise TerraAmdError("sh_project: one coefficient record per probe")
+    check(lib.sh_project_device(results.data_ptr(), rays.data_ptr(), probes, cells, batch, sh.data_ptr(), _current_stream()), "terra_amd_sh_project_device")
+    return sh
+
+
+def probe_sh_host(sh) -> np.ndarray:
+    """the coefficient records of a tensor [P, 28] as [P] api.PROBE_SH_DTYPE records on the host"""
+    return sh.cpu().numpy().view(api.PROBE_SH_DTYPE).reshape(-1)
+
+
+def sh_irradiance(lib, sh, points, grid: Optional[api.ProbeGrid] = None, index=None):
+    """terra_amd_sh_irradiance_device on the current torch stream: sh [P, 28] as sh_project returns it, points float32 [n, 8] in HBM (api.POINT_DTYPE records: the
+    normal is the lobe's axis, the position is looked at in grid mode), and either grid (trilinear blend of the grid's probes) or index (int32 [n] in HBM: one
+    probe per query) -> float32 [n, 4]: (E_r, E_g, E_b, 0)"""
+    import torch
+    probes = _records(sh, 28, "sh_irradiance sh")
+    n = _records(points, 8, "sh_irradiance points")
+    if grid is None and not (isinstance(index, torch.Tensor) and index.is_cuda and index.dtype == torch.int32 and index.is_contiguous() and index.numel() == n):
+        raise TerraAmdError("sh_irradiance without a grid takes index as a contiguous int32 tensor [n] in HBM")
+    out = torch.empty((n, 4), dtype=torch.float32, device=points.device)
+    check(lib.sh_irradiance_device(sh.data_ptr(), probes, C.byref(grid) if grid is not None else None, points.data_ptr(),
+                                   index.data_ptr() if grid is None else None, n, out.data_ptr(), _current_stream()), "terra_amd_sh_irradiance_device")
+    return out
+
+
+def bake_probes(lib, scene, probes, cells: int = 16, batches: int = 1, jitter=None):
+    """Order-2 SH of the radiance arriving at P probes (float32 [P, 8] in HBM: api.POINT_DTYPE records) -> sh float32 [P, 28] in HBM (probe_sh_host gives the [P]
+    api.PROBE_SH_DTYPE records): probe_rays -> render_rays_device -> sh_project, all on the current torch stream. jitter None: the cell-centre rays, `batches`
+    render calls of the scene's samples_per_pixel each into one frame, one projection. jitter = an int seed: every batch draws a fresh jitter array
+    (torch.rand of [cells * cells, 2] from a device generator with that seed), renders a fresh frame along its rays and is averaged in by sh_project's batch."""
+    import torch
+    if batches < 1:
+        raise TerraAmdError("bake_probes: batches must be at least 1")
+    n = _records(probes, 8, "bake_probes probes")
+    stream = _current_stream()
+    fb = DeviceFramebuffer(cells * cells, n, device=probes.device)
+    if jitter is None:
+        rays = probe_rays(lib, probes, cells)
+        for _ in range(batches):
+            render_rays_device(lib, scene, rays, fb, stream=stream)
+        return sh_project(lib, fb, rays, cells)
+    gen = torch.Generator(device=probes.device)
+    gen.manual_seed(int(jitter))
+    sh = None
+    for b in range(batches):
+        if b:
+            fb = DeviceFramebuffer(cells * cells, n, device=probes.device)
+        rays = probe_rays(lib, probes, cells, torch.rand((cells * cells, 2), generator=gen, dtype=torch.float32, device=probes.device))
+        render_rays_device(lib, scene, rays, fb, stream=stream)
+        sh = sh_project(lib, fb, rays, cells, batch=b, sh=sh)
+    return sh
 
 
 def render_device_sharded(lib, cam, scene, fb: DeviceFramebuffer, tile: int, rank: int, world: int, stream=None):

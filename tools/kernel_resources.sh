@@ -4,7 +4,7 @@
 #        tools/kernel_resources.sh -DTERRA_RAY_SOURCE=1 [-DTERRA_RAY_HOLD=1]   the ray-sourced instances (the ray re-fetched per sample / held across a job)
 #        tools/kernel_resources.sh -DTERRA_RAY_SOURCE=2                        the lens instances (include/terra_amd.h "Lens rendering")
 #        tools/kernel_resources.sh -DTERRA_RAY_SOURCE=3 [-DTERRA_POINT_HOLD=1] the point instances (include/terra_amd.h "Point rendering": the point re-fetched per sample / held across a job)
-#        tools/kernel_resources.sh --unit bake_kernels                          every kernel of another unit (terra_amd/csrc/<unit>.hip), demangled
+#        tools/kernel_resources.sh --unit bake_kernels                          every kernel of another unit (terra_amd/csrc/<unit>.hip: bake_kernels, probe_kernels, ...), demangled
 set -e
 D=/tmp/terra_isa; rm -rf $D; mkdir -p $D; cd $D
 if [ "$1" = "--unit" ]; then

@@ -48,3 +48,6 @@ hipError_t terra_unit_texture_sample ( const DevTexture*, int, const float*, flo
 hipError_t terra_unit_texture_latlong ( const DevTexture*, int, const float*, float* ) { return hipErrorNoDevice; }
 hipError_t terra_launch_atlas_points ( const DevScene&, const DevAtlas&, const float*, void*, void*, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_launch_dilate ( float*, int, int*, uint32_t, uint32_t, int, hipStream_t ) { return hipErrorNoDevice; }
+hipError_t terra_launch_probe_rays ( const void*, uint32_t, uint32_t, const float*, void*, hipStream_t ) { return hipErrorNoDevice; }
+hipError_t terra_launch_sh_project ( const void*, const void*, uint32_t, uint32_t, int, void*, hipStream_t ) { return hipErrorNoDevice; }
+hipError_t terra_launch_sh_irradiance ( const void*, uint32_t, const DevProbeGrid&, const void*, const int*, uint32_t, void*, hipStream_t ) { return hipErrorNoDevice; }
