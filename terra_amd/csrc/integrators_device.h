@@ -8,6 +8,8 @@
 // -----------------------------------------------------------------------------
 // COUNT levels: 0 none (the default launch); 2 = rays, nodes, triangle tests, hits, stream-B draws, attribute fetches per lane
 TD float randf ( Pcg32& b, Counters& c, int count ) { if ( count == 2 ) ++c.rand_calls; return trng_b_float ( b ); }
+// the same draw as its 24 bits: randf = trng_b_from_bits ( randf_bits )
+TD uint32_t randf_bits ( Pcg32& b, Counters& c, int count ) { if ( count == 2 ) ++c.rand_calls; return trng_b_bits ( b ); }
 
 TD float triangle_area ( V3 a, V3 b, V3 cc ) { return length ( cross ( b - a, cc - a ) ) / 2; }
 
@@ -364,12 +366,24 @@ TD V3 integrate ( const Tracer& T, const Ray& ray, Surface& sf, V3 p, V3 wo, V3 
 // The four variates are consecutive draws of stream B whatever the surface is, so they can be drawn -- and the azimuth table entry requested -- BEFORE the
 // surface is set up (path_draw), which hides the load behind terra_surface_init's work; integrators that draw from the stream themselves (Direct, MIS) call
 // path_draw after their own draws, as the reference's order demands.
-template <int COUNT>
+// INDEX (the launches of ray_start_masks_for): the table is fetched by the variate's 24 bits
+template <int COUNT, bool INDEX>
 TD PathDraws path_draw ( const float2* sincos24, Pcg32& rb, Counters& c ) {
     PathDraws d;
-    d.e0 = randf ( rb, c, COUNT ); d.e1 = randf ( rb, c, COUNT ); d.e2 = randf ( rb, c, COUNT );
-    d.az = azimuth_fetch ( sincos24, d.e1 );
-    d.e3 = randf ( rb, c, COUNT );
+    if constexpr ( INDEX ) {
+        // e1 = k * 2^-24 exactly (k < 2^24 is a float, and so is the product): the float form of azimuth_fetch would multiply it back to k, find it in range and
+        // whole, and read entry k -- the integer is still here, so the fetch takes it
+        d.e0 = randf ( rb, c, COUNT );
+        const uint32_t k1 = randf_bits ( rb, c, COUNT );
+        d.e1 = trng_b_from_bits ( k1 );
+        d.e2 = randf ( rb, c, COUNT );
+        d.az = azimuth_fetch_index ( sincos24, k1 );
+        d.e3 = randf ( rb, c, COUNT );
+    } else {
+        d.e0 = randf ( rb, c, COUNT ); d.e1 = randf ( rb, c, COUNT ); d.e2 = randf ( rb, c, COUNT );
+        d.az = azimuth_fetch ( sincos24, d.e1 );
+        d.e3 = randf ( rb, c, COUNT );
+    }
     return d;
 }
 template <int KINDS>

@@ -801,12 +801,14 @@ __global__ __launch_bounds__ ( 256, terra_waves ( INTEGRATOR, KINDS, MODE ) ) vo
             }
         }
         if ( alive ) {
+            bool guarded = false;          // (make_ray's guard, for the kernels that make one range test per ray: trace_geometry.h)
+            if constexpr ( ray_start_masks_for ( COUNT, MODE, KINDS ) ) ray = make_ray_guarded ( ro, rd, guarded ); else
             ray = make_ray ( ro, rd );
             Surface sf;
             PS_WAVE ( c, kPsRayIter ); PS_LANE ( c, kPsRayLanes );
             constexpr bool pre_draw = !TERRA_IS_LIGHT ( INTEGRATOR );      // integrators that draw nothing themselves: the continuation variates come before the surface set-up
             PathDraws pd;
-            RaycastResult h = scene_raycast<COUNT, MODE, KINDS> ( T, ray, sf, c, pre_draw ? &pd : nullptr, pre_draw ? &rs.b : nullptr );
+            RaycastResult h = scene_raycast<COUNT, MODE, KINDS> ( T, ray, sf, c, pre_draw ? &pd : nullptr, pre_draw ? &rs.b : nullptr, guarded );
             bool end = !h.hit;
             if ( h.hit ) {
                 PS_WAVE ( c, kPsShadeIter ); PS_LANE ( c, kPsShadeLanes );
@@ -818,10 +820,10 @@ __global__ __launch_bounds__ ( 256, terra_waves ( INTEGRATOR, KINDS, MODE ) ) vo
                 if constexpr ( SPLIT_DIRECT ) {
                     Ray shadow_ray;
                     const DirectPending pend = direct_prepare<COUNT, KINDS, MODE> ( T, sf, h.point, wo, throughput, bounce, rs.b, c, shadow_ray );
-                    pd = path_draw<COUNT> ( T.sc.sincos24, rs.b, c );
+                    pd = path_draw<COUNT, ray_start_masks_for ( COUNT, MODE, KINDS )> ( T.sc.sincos24, rs.b, c );
                     end = !path_continue<KINDS> ( sf, wo, throughput, bounce, p.bounces, pd, wi );
                     if ( !end ) { ro = surface_origin ( sf, h.point ); rd = wi; }
-                    const uint32_t tri = scene_raycast_triangle<COUNT, MODE> ( T, shadow_ray, c, pend.expected );
+                    const uint32_t tri = scene_raycast_triangle<COUNT, MODE, ray_start_masks_for ( COUNT, MODE, KINDS )> ( T, shadow_ray, c, pend.expected );
                     lo_add ( tri == pend.expected ? pend.vis : pend.hid );
                 } else if constexpr ( INTEGRATOR == 2 && ( KINDS & ( TERRA_KIND_TEX | TERRA_KIND_SAMPLER ) ) == 0 ) {
                     // Direct + MIS split the same way at its two rays (mis_prepare / mis_finish_b, src/Terra.c:1428-1587): A, the ray to the light sample, only has to
@@ -831,14 +833,14 @@ __global__ __launch_bounds__ ( 256, terra_waves ( INTEGRATOR, KINDS, MODE ) ) vo
                     const V3 next_o = surface_origin ( sf, h.point );          // surface_ray ( sf, h.point, direction ) for B and for the continuation alike
                     end = !path_continue<COUNT, KINDS> ( T.sc, sf, wo, throughput, bounce, p.bounces, rs.b, c, wi, sp );
                     if ( !end ) { ro = next_o; rd = wi; }
-                    const uint32_t tri_a = scene_raycast_triangle<COUNT, MODE> ( T, ray_a, c, pend.expected );
+                    const uint32_t tri_a = scene_raycast_triangle<COUNT, MODE, ray_start_masks_for ( COUNT, MODE, KINDS )> ( T, ray_a, c, pend.expected );
                     const V3 lo_a = tri_a == pend.expected ? pend.a_vis : pend.a_hid;
                     Surface lsf;
                     const RaycastResult hb = scene_raycast<COUNT, MODE, KINDS> ( T, make_ray ( next_o, b_d ), lsf, c );
                     lo_add ( mis_finish_b<MODE> ( T, pend, lo_a, hb.hit, hb.object, hb.tri, hb.point, lsf, b_d ) );
                 } else {
                 lo_add ( integrate<INTEGRATOR, COUNT, MODE, KINDS> ( T, ray, sf, h.point, wo, throughput, bounce, rs.b, c ) );
-                if ( !pre_draw ) pd = path_draw<COUNT> ( T.sc.sincos24, rs.b, c );
+                if ( !pre_draw ) pd = path_draw<COUNT, ray_start_masks_for ( COUNT, MODE, KINDS )> ( T.sc.sincos24, rs.b, c );
                 if constexpr ( ( KINDS & TERRA_KIND_SAMPLER ) != 0 ) path_apply_sampler ( pd, sp, bounce );
                 end = !path_continue<KINDS> ( sf, wo, throughput, bounce, p.bounces, pd, wi );
                 if ( !end ) { ro = surface_origin ( sf, h.point ); rd = wi; }      // surface_ray ( sf, h.point, wi ): its make_ray is the one at the top of this block

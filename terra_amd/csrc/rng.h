@@ -62,3 +62,6 @@ TRNG_FN PixelStreams trng_pixel_streams ( uint64_t frame_seed, uint64_t pix, uin
 TRNG_FN float trng_a_float ( Pcg32& a ) { return ( float ) trng_next ( a ) * 0x1p-32f; }
 // the value "(float)rand() / RAND_MAX" takes: 24 random bits * 2^-24, in [0,1)
 TRNG_FN float trng_b_float ( Pcg32& b ) { return ( float ) ( trng_next ( b ) >> 8 ) * 0x1p-24f; }
+// the same draw as its 24 bits, and the variate of 24 bits: trng_b_float ( b ) = trng_b_from_bits ( trng_b_bits ( b ) )
+TRNG_FN uint32_t trng_b_bits ( Pcg32& b ) { return trng_next ( b ) >> 8; }
+TRNG_FN float trng_b_from_bits ( uint32_t k ) { return ( float ) k * 0x1p-24f; }

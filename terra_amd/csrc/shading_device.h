@@ -133,24 +133,29 @@ struct RaycastResult { bool hit; uint32_t object, tri_in_object, tri; V3 point; 
 
 struct Azimuth { float sn, cs; bool have; };
 struct PathDraws { float e0, e1, e2, e3; Azimuth az; };
-template <int COUNT> TD PathDraws path_draw ( const float2* sincos24, Pcg32& rb, Counters& c );
+template <int COUNT, bool INDEX = false> TD PathDraws path_draw ( const float2* sincos24, Pcg32& rb, Counters& c );
 
+// guarded (the kernels of ray_start_masks_for): what make_ray_guarded found for this lane's ray
 // pre / rb (optional): a hit draws the path's four continuation variates (path_draw) BEFORE the surface is set up, so that the azimuth table load they issue
 // is in flight during terra_surface_init's arithmetic -- only for integrators that draw nothing of their own between the hit and the BSDF sample
 template <int COUNT, int MODE, int KINDS>
-TD RaycastResult scene_raycast ( const Tracer& T, const Ray& in, Surface& sf, Counters& c, PathDraws* pre = nullptr, Pcg32* rb = nullptr ) {
+TD RaycastResult scene_raycast ( const Tracer& T, const Ray& in, Surface& sf, Counters& c, PathDraws* pre = nullptr, Pcg32* rb = nullptr, bool guarded = false ) {
     Ray r = in;
     r.o = r.o + r.d * 0.001f;
-    RayState st = ray_state_init ( r );
+    constexpr bool MASKS = ray_start_masks_for ( COUNT, MODE, KINDS );          // (trace_geometry.h: the ray start by lane predicates, one range test, the azimuth by its integer)
     if ( COUNT ) ++c.rays;
     Closest best;
+    if constexpr ( MASKS ) { V3 o_perm; const RayStateMasks st = ray_start_masks ( r, o_perm ); best = bvh_traverse_from<COUNT, MODE> ( T, r, st, o_perm, c, __all ( guarded ) != 0 ); }
+    else {
+    RayState st = ray_state_init ( r );
     if ( MODE >= 2 ) { ClosestRanked b2 = bvh_traverse_fast<COUNT, MODE == 3> ( T, r, st, c ); best.depth = b2.depth; best.tri = b2.tri; }
     else best = bvh_traverse<COUNT, MODE> ( T, r, st, c );
+    }
     RaycastResult res; res.hit = best.tri != 0xffffffffu; res.tri = best.tri; res.object = 0; res.tri_in_object = 0;
     res.point = res.hit ? r.o + r.d * best.depth : v3 ( FLT_MAX, FLT_MAX, FLT_MAX );
     if ( res.hit ) {
         uint32_t nattr;
-        if ( pre ) *pre = path_draw<COUNT> ( T.sc.sincos24, *rb, c );
+        if ( pre ) *pre = path_draw<COUNT, MASKS> ( T.sc.sincos24, *rb, c );
         surface_init<MODE, KINDS> ( T, best.tri, res.point, sf, res.object, res.tri_in_object, nattr );
         if ( MODE >= 2 ) res.tri = T.sc.mats[res.object].first_tri + res.tri_in_object;      // back to the soup index (lights, areas)
         if ( COUNT ) ++c.hits;
@@ -163,11 +168,13 @@ TD RaycastResult scene_raycast ( const Tracer& T, const Ray& in, Surface& sf, Co
 // emissive attributes are constants): same traversal, same counts -- a hit is a surface initialisation in the reference -- without setting the surface up.
 // Returns the triangle's index in the soup (the index the light tables use), 0xffffffff for a miss.
 // `expected` (soup index): the only answer the caller distinguishes from the others; kernels without counters then take the shortcut of fast_expect on MODE 2
-template <int COUNT, int MODE>
+// MASKS: ray_start_masks_for of the calling kernel (only its MODE 1, COUNT 0 block looks at it)
+template <int COUNT, int MODE, bool MASKS = false>
 TD uint32_t scene_raycast_triangle ( const Tracer& T, const Ray& in, Counters& c, uint32_t expected ) {
     Ray r = in;
     r.o = r.o + r.d * 0.001f;
-    RayState st = ray_state_init ( r );
+    V3 o_masks = v3 ( 0, 0, 0 );
+    const auto st = [&] { if constexpr ( MASKS ) return ray_start_masks ( r, o_masks ); else return ray_state_init ( r ); } ();
     if ( COUNT ) ++c.rays;
     if constexpr ( MODE == 2 && COUNT == 0 ) {
         const V3 o_perm = permuted ( r.o, st );
@@ -182,7 +189,7 @@ TD uint32_t scene_raycast_triangle ( const Tracer& T, const Ray& in, Counters& c
     // its leaf is reached, takes the record as it would; and the traversal ends at the first OTHER triangle that takes it (traverse_loops ANYHIT): up to there it has
     // made the reference's decisions one by one, after that none can change the answer. A ray that misses its triangle is not traced at all.
     if constexpr ( MODE == 1 && COUNT == 0 ) {
-        const V3 o_perm = permuted ( r.o, st );
+        const V3 o_perm = MASKS ? o_masks : permuted ( r.o, st );
         float depth;
         if ( !watertight_permuted ( tri_perm_lds ( T.l_tris + 12 * expected, st ), o_perm, st, depth ) ) return 0xffffffffu;
         Closest best; best.depth = __uint_as_float ( __float_as_uint ( depth + 0.f ) + 1u ); best.tri = 0xffffffffu;      // (depth >= 0; + 0.f: -0 -> +0)
@@ -234,6 +241,12 @@ TD Azimuth azimuth_fetch ( const float2* tab, float e ) {
         const uint32_t k = ( uint32_t ) x;
         if ( ( float ) k == x ) { const float2 v = tab[k]; a.cs = v.x; a.sn = v.y; a.have = true; }
     }
+    return a;
+}
+// the same for a variate whose 24 bits the caller still holds (path_draw): e = k * 2^-24 passes every test above and lands on entry k
+TD Azimuth azimuth_fetch_index ( const float2* tab, uint32_t k ) {
+    Azimuth a = azimuth_none();
+    if ( tab ) { const float2 v = tab[k]; a.cs = v.x; a.sn = v.y; a.have = true; }
     return a;
 }
 TD void azimuth_sincos ( const Azimuth& az, float e, float& sn, float& cs ) {

@@ -166,6 +166,12 @@ TD bool ray_is_tame ( const Ray& r ) {
     uint32_t ax = tdm_bits ( r.inv.x ) & 0x7fffffffu, ay = tdm_bits ( r.inv.y ) & 0x7fffffffu, az = tdm_bits ( r.inv.z ) & 0x7fffffffu;
     return ax - 1u < 0x6f7fffffu && ay - 1u < 0x6f7fffffu && az - 1u < 0x6f7fffffu;
 }
+// One range test per ray (the kernels of ray_start_masks_for, their camera and continuation rays). make_ray_guarded's guard has already looked at the three numbers
+// these two functions look at the reciprocals of: a direction component that passed xd_rcp_ok is normal with 2^-60 <= |d| <= 2^60, so RN ( 1 / d ) lies in
+// [2^-60, 2^60] -- bits 0x21800000 .. 0x5d800000 without the sign, inside both 1 .. 0x7f7fffff (regular) and 1 .. 0x6f7fffff (tame). A wave whose lanes all passed
+// the guard is therefore all tame and all regular, and the traversal entry (traverse_ref.h bvh_traverse_from) asks that first: "all_guarded || __all ( tame )" has
+// the value of "__all ( tame )" for every input, and the second operand -- the three ands, the three decrements, the max and the vote -- runs only in a wave that
+// holds a lane the guard turned away (a zero, a denormal, a huge, tiny or non-finite component, a significand of all ones), where it decides as it always did.
 // slab test from (near, far) planes per axis: what slab<true> computes, without the per-axis min / max
 TD bool slab_near_far ( float nx, float fx, float ny, float fy, float nz, float fz, const Ray& r ) {
     float tnx = ( nx - r.o.x ) * r.inv.x, tfx = ( fx - r.o.x ) * r.inv.x;
@@ -207,6 +213,48 @@ TD RayState ray_state_init ( const Ray& r ) {
     s.ix = ix; s.iy = iy; s.iz = iz;
     return s;
 }
+
+// The same ray state, and the origin in the ray's axes, for the launches of ray_start_masks_for below: the axes as three lane predicates instead of three numbers --
+// z0 / z1 = "iz is 0 / 1" (neither: 2), from the three comparisons above with ties to the later axis and a NaN losing every comparison it is in; flip = "d[iz] < 0"
+// (false for -0 and a NaN). ix = iz + 1 and iy = iz + 2 (mod 3) change places when flip holds, so a pick is selects on masks that are already there: two for the
+// component at iz, two each for those at iz + 1 and iz + 2, two more to put that pair in order -- 18 for d, inv and the origin. (Picking by the numbers, the
+// compiler builds them with selects, additions and compares and compares them with 0 and 1 again at every pick: about 44 instructions.) The predicates do not
+// leave this function. What the traversal needs later is a NUMBER -- perm for the ranked copy, the word offsets of tri_perm_lds -- and it is made here, in one
+// vector register the empty asm pins: left alone the compiler makes perm where it is used, behind the box loop, and carries three masks there, which this
+// kernel pays for with launch constants parked in vector lanes (profiles/ray_start/kernel_resources.md). ix, iy, iz come from perm by two 12-bit tables
+// (ix = 1 2 2 0 0 1, iy = 2 1 0 2 1 0 for perm = 0 .. 5); only the launches without ranked copies read them.
+// tests/test_ray_start.py restates both forms and holds them equal on every direction of {+-0, +-denormal, +-1, +-nextafter(1), +-2, +-inf, NaN}^3.
+TD RayStateMasks ray_start_masks ( const Ray& r, V3& o_perm ) {
+    const float ax = fabsf ( r.d.x ), ay = fabsf ( r.d.y ), az = fabsf ( r.d.z );
+    const bool xy = ax > ay, xz = ax > az, yz = ay > az;
+    const bool z0 = xy & xz, z1 = !xy & yz;
+    const auto at_z = [&] ( V3 a ) { return z0 ? a.x : ( z1 ? a.y : a.z ); };
+    const bool flip = at_z ( r.d ) < 0.f;
+    const auto at_xy = [&] ( V3 a, float& px, float& py ) {
+        const float u = z0 ? a.y : ( z1 ? a.z : a.x ), v = z0 ? a.z : ( z1 ? a.x : a.y );
+        px = flip ? v : u; py = flip ? u : v;
+    };
+    RayStateMasks s;
+    s.perm = ( z0 ? 0u : ( z1 ? 2u : 4u ) ) + ( flip ? 1u : 0u );
+    asm volatile ( "" : "+v" ( s.perm ) );
+    s.ix = ( int ) ( ( 0x429u >> ( 2u * s.perm ) ) & 3u ); s.iy = ( int ) ( ( 0x186u >> ( 2u * s.perm ) ) & 3u ); s.iz = ( int ) ( s.perm >> 1 );
+    s.scalez = at_z ( r.inv );              // 1.f / d[iz], as ray_state_init takes it
+    float dix, diy; at_xy ( r.d, dix, diy );
+    s.shearx = dix * s.scalez;
+    s.sheary = diy * s.scalez;
+    at_xy ( r.o, o_perm.x, o_perm.y ); o_perm.z = at_z ( r.o );
+    return s;
+}
+// Which launches start their rays that way, make one range test per ray (make_ray_guarded) and fetch the azimuth by its integer (shading_device.h
+// azimuth_fetch_index): the LDS-resident kernels of the plain presets without work counters, camera rays made in the kernel -- the headline's and Direct's kernels.
+// Every other instance keeps the integer form and compiles to the code it had: with the three changes some of them took a few bytes more scratch
+// (work-counter instances, MODE 0 light integrators, MODE 3), and the hall (MODE 2, a ray's state kept across the calls of a resumable loop) lost 1 %.
+#if TERRA_RAY_SOURCE
+#define TERRA_RAY_START_CAMERA 0
+#else
+#define TERRA_RAY_START_CAMERA 1
+#endif
+TD constexpr bool ray_start_masks_for ( int COUNT, int MODE, int KINDS ) { return TERRA_RAY_START_CAMERA && MODE == 1 && COUNT == 0 && KINDS == 1; }
 
 // the three vertices of a triangle record (three float4; the w components carry object, triangle in object, pad / rank)
 TD void tri_vertices ( float4 t0, float4 t1, float4 t2, V3& a, V3& b, V3& c ) { a = v3 ( t0.x, t0.y, t0.z ); b = v3 ( t1.x, t1.y, t1.z ); c = v3 ( t2.x, t2.y, t2.z ); }

@@ -73,8 +73,24 @@ TD Basis make_basis ( V3 n ) {
 
 struct Ray { V3 o, d, inv; };
 TD Ray make_ray ( V3 o, V3 d ) { Ray r; r.o = o; r.d = d; rcp3_exact ( d.x, d.y, d.z, r.inv.x, r.inv.y, r.inv.z ); return r; }      // 1.f / d, bit for bit -- 1 / -0 = -inf included: a zero takes the plain division
+// make_ray that also says what its guard found (the kernels of trace_geometry.h ray_start_masks_for): guarded = every component of d passed xd_rcp_ok, so inv came
+// from the short sequence. Such a component is normal with 2^-60 <= |d| <= 2^60, and its correctly rounded reciprocal lies in [2^-60, 2^60] too (rounding is
+// monotonic and both bounds are floats): finite, non-zero and far below 2^96 -- the ray is regular and tame (trace_geometry.h ray_is_regular, ray_is_tame)
+// without looking at inv again. tests/test_ray_start.py holds the implication on the bits. Same quotients as make_ray, bit for bit.
+TD Ray make_ray_guarded ( V3 o, V3 d, bool& guarded ) {
+    Ray r; r.o = o; r.d = d;
+    guarded = ( xd_rcp_ok ( d.x ) & xd_rcp_ok ( d.y ) & xd_rcp_ok ( d.z ) ) != 0;
+    if ( guarded ) { r.inv.x = xd_rcp_short ( d.x ); r.inv.y = xd_rcp_short ( d.y ); r.inv.z = xd_rcp_short ( d.z ); }
+    else { r.inv.x = 1.f / d.x; r.inv.y = 1.f / d.y; r.inv.z = 1.f / d.z; }
+    return r;
+}
 
 // what the watertight test keeps per ray (ray_state_init): the dominant axis iz of the direction, the two others in winding order, the shear and the scale
 struct RayState { float shearx, sheary, scalez; int ix, iy, iz; };
 // a point in the ray's permuted axes: (a[ix], a[iy], a[iz])
 TD V3 permuted ( V3 a, const RayState& s ) { return v3 ( pick ( a, s.ix ), pick ( a, s.iy ), pick ( a, s.iz ) ); }
+// which of the six pre-permuted copies of the ranked triangles the ray reads (scene_host.cpp): 2 iz + "ix does not follow iz" (d[iz] < 0 swapped ix / iy)
+TD uint32_t ray_perm ( const RayState& s ) { return 2u * ( uint32_t ) s.iz + ( uint32_t ) ( s.ix != ( s.iz == 2 ? 0 : s.iz + 1 ) ); }
+// the ray state of trace_geometry.h ray_start_masks: that number is made at the ray's start and kept
+struct RayStateMasks : RayState { uint32_t perm; };
+TD uint32_t ray_perm ( const RayStateMasks& s ) { return s.perm; }

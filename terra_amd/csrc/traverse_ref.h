@@ -346,8 +346,8 @@ TD uint32_t leaf_boxes_flat ( const Tracer& T, const Ray& r, const SlabSel& sel,
 // "no second box" -- every entry left is tested in bit order as before: exact whatever the first trip did.
 // ANYHIT: a preset record strictly below the smallest entry distance cannot be beaten and the loop is skipped; otherwise the nearest entry goes first, the first
 // triangle that beats the record ends the loop as before, and the cut applies with the preset record.
-template <int COUNT, int MODE, bool FAST, bool FUSED, bool ANYHIT>
-TD void traverse_pairs ( const Tracer& T, const Ray& r, const RayState& st, V3 o_perm, Closest& best, Counters& c ) {
+template <int COUNT, int MODE, bool FAST, bool FUSED, bool ANYHIT, class RS = RayState>
+TD void traverse_pairs ( const Tracer& T, const Ray& r, const RS& st, V3 o_perm, Closest& best, Counters& c ) {
     const SlabSel sel = slab_sel ( r );
     uint32_t leaf_set = 0u;
     PS_WAVE ( c, kPsDrainIter );
@@ -361,7 +361,7 @@ TD void traverse_pairs ( const Tracer& T, const Ray& r, const RayState& st, V3 o
         *sp = 0; sp += TERRA_COL;
         while ( sp != T.stack ) node_step<COUNT, MODE, FAST, FUSED, true> ( T, r, sel, sp, lp, leaf_set, c );
     }
-    const uint32_t perm = 2u * ( uint32_t ) st.iz + ( uint32_t ) ( st.ix != ( st.iz == 2 ? 0 : st.iz + 1 ) );
+    const uint32_t perm = ray_perm ( st );
     const float4* copy = T.l_ranked + ( TERRA_PAIR_ENTRY_BYTES / 16 ) * ( T.lds_tris >> 1 ) * perm;
     float depth_best = best.depth; uint32_t key_best = ANYHIT ? best.tri : 0u;          // (ANYHIT: the caller's preset key travels in best.tri; the record itself never moves)
     bool beaten = false;
@@ -398,8 +398,8 @@ TD void traverse_pairs ( const Tracer& T, const Ray& r, const RayState& st, V3 o
     best.tri = ANYHIT ? ( beaten ? 0u : key_best ) : ( key_best ? ( key_best & 31u ) : 0xffffffffu );
 }
 
-template <int COUNT, int MODE, bool FAST, bool FUSED = false, bool ANYHIT = false>
-TD void traverse_ranked ( const Tracer& T, const Ray& r, const RayState& st, V3 o_perm, Closest& best, Counters& c, uint32_t expected ) {
+template <int COUNT, int MODE, bool FAST, bool FUSED = false, bool ANYHIT = false, class RS = RayState>
+TD void traverse_ranked ( const Tracer& T, const Ray& r, const RS& st, V3 o_perm, Closest& best, Counters& c, uint32_t expected ) {
     if constexpr ( COUNT == 0 ) if ( T.pairs ) { traverse_pairs<COUNT, MODE, FAST, FUSED, ANYHIT> ( T, r, st, o_perm, best, c ); return; }      // (launch constant)
     const SlabSel sel = slab_sel ( r );
     uint32_t leaf_set = 0u;
@@ -413,7 +413,7 @@ TD void traverse_ranked ( const Tracer& T, const Ray& r, const RayState& st, V3 
         *sp = 0; sp += TERRA_COL;                                      // the root: node 0 = byte offset 0
         while ( sp != T.stack ) node_step<COUNT, MODE, FAST, FUSED, true> ( T, r, sel, sp, lp, leaf_set, c );
     }
-    const uint32_t perm = 2u * ( uint32_t ) st.iz + ( uint32_t ) ( st.ix != ( st.iz == 2 ? 0 : st.iz + 1 ) );      // ray_state_init: ix follows iz unless d[iz] < 0 swapped ix / iy
+    const uint32_t perm = ray_perm ( st );
     const float4* copy = T.l_ranked + 3u * T.lds_tris * perm;
     while ( leaf_set != 0u ) {
         PS_WAVE ( c, kPsLeafIter ); PS_LANE ( c, kPsLeafLanes );
@@ -431,8 +431,8 @@ TD void traverse_ranked ( const Tracer& T, const Ray& r, const RayState& st, V3 
     }
 }
 
-template <int COUNT, int MODE, bool FAST, bool FUSED = false, bool ANYHIT = false>
-TD void traverse_loops ( const Tracer& T, const Ray& r, const RayState& st, V3 o_perm, Closest& best, Counters& c, uint32_t expected = 0xffffffffu ) {
+template <int COUNT, int MODE, bool FAST, bool FUSED = false, bool ANYHIT = false, class RS = RayState>
+TD void traverse_loops ( const Tracer& T, const Ray& r, const RS& st, V3 o_perm, Closest& best, Counters& c, uint32_t expected = 0xffffffffu ) {
     if constexpr ( MODE == 1 ) if ( T.ranked ) { traverse_ranked<COUNT, MODE, FAST, FUSED, ANYHIT> ( T, r, st, o_perm, best, c, expected ); return; }
     const SlabSel sel = slab_sel ( r );
     int* sp = T.stack; int* lp = T.leaves;
@@ -453,6 +453,19 @@ TD void traverse_loops ( const Tracer& T, const Ray& r, const RayState& st, V3 o
     }
 }
 
+// the same from a ray start that brings the origin in the ray's axes along (trace_geometry.h ray_start_masks) and what make_ray_guarded found in the wave:
+// all_guarded answers both votes (trace_geometry.h "One range test per ray"). (bvh_traverse above keeps its own text: written as a call of this one with
+// all_guarded = false it compiles to the same instructions in another order, and every kernel but seven is held to the code it had.)
+template <int COUNT, int MODE, class RS>
+TD Closest bvh_traverse_from ( const Tracer& T, const Ray& r, const RS& st, V3 o_perm, Counters& c, bool all_guarded ) {
+    Closest best; best.depth = FLT_MAX; best.tri = 0xffffffffu;
+    // the slab variant is chosen per WAVE: one irregular ray sends its whole wave down the exact path
+    const bool guarded = all_guarded;
+    if ( MODE == 1 && T.fused && ( guarded || __all ( ray_is_tame ( r ) ) ) ) traverse_loops<COUNT, MODE, true, true> ( T, r, st, o_perm, best, c );
+    else if ( guarded || __all ( ray_is_regular ( r ) ) ) traverse_loops<COUNT, MODE, true> ( T, r, st, o_perm, best, c );
+    else traverse_loops<COUNT, MODE, false> ( T, r, st, o_perm, best, c );
+    return best;
+}
 template <int COUNT, int MODE>
 TD Closest bvh_traverse ( const Tracer& T, const Ray& r, const RayState& st, Counters& c ) {
     Closest best; best.depth = FLT_MAX; best.tri = 0xffffffffu;

@@ -67,8 +67,11 @@ hipError_t terra_unit_watertight ( int n, const float* o, const float* d, const 
 __global__ void k_watertight_pair ( int n, const float* o, const float* d, const float* quads, int* hit, float* depth ) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if ( i >= n ) return;
-    Ray r = make_ray ( v3p ( o + 3 * i ), v3p ( d + 3 * i ) );
-    RayState s = ray_state_init ( r );
+    // the ray start of the LDS-resident kernels (trace_geometry.h ray_start_masks): axes by lane predicates, ix / iy / iz from perm's tables, the origin picked with them
+    bool guarded;
+    Ray r = make_ray_guarded ( v3p ( o + 3 * i ), v3p ( d + 3 * i ), guarded );
+    V3 o_perm;
+    const RayStateMasks s = ray_start_masks ( r, o_perm );
     auto load = [&] ( bool again ) {
         const float* q = quads + 12 * i;
         if ( again ) asm volatile ( "" : "+v" ( q ) );
@@ -77,7 +80,7 @@ __global__ void k_watertight_pair ( int n, const float* o, const float* d, const
                           { pick ( p2, s.ix ), pick ( p2, s.iy ), pick ( p2, s.iz ) }, { pick ( p3, s.ix ), pick ( p3, s.iy ), pick ( p3, s.iz ) } };
     };
     int h0 = 0, h1 = 0; float d0 = 0.f, d1 = 0.f;
-    watertight_pair ( load, permuted ( r.o, s ), s, [&] ( float dep, bool second ) { if ( second ) { h1 = 1; d1 = dep; } else { h0 = 1; d0 = dep; } } );
+    watertight_pair ( load, o_perm, s, [&] ( float dep, bool second ) { if ( second ) { h1 = 1; d1 = dep; } else { h0 = 1; d0 = dep; } } );
     hit[2 * i] = h0; hit[2 * i + 1] = h1; depth[2 * i] = d0; depth[2 * i + 1] = d1;
 }
 hipError_t terra_unit_watertight_pair ( int n, const float* o, const float* d, const float* quads, int* hit, float* depth ) {
