@@ -32,7 +32,7 @@
  *       [--camera px py pz dx dy dz] [--fov deg] [--exposure e] [--gamma g] [--jitter j]
  *       [--no-flip-z] [--normals apollo|file] [--dump-scene file] [--no-render] [--fast-tree | --replica-tree] [--sample-split n] [--seed n] [--tile n] [--gpus n]
  *       [--environment map.hdr|map.pfm] [--environment-color r g b] [--env-light] [--env-sampling off|table|mis] [--aov PREFIX] [--denoise K]
- *       [--passes N] [--denoise-variance K] [--adaptive TARGET [--min-passes A] [--max-passes B]] [--variance out.pfm]
+ *       [--passes N] [--denoise-variance K] [--adaptive TARGET [--min-passes A] [--max-passes B] [--adaptive-masked]] [--variance out.pfm]
  *       [--frames N] [--camera-to px py pz dx dy dz] [--temporal ALPHA]
  *       [--camera-model pinhole|thinlens|ortho|equirect|fisheye] [--aperture R] [--focus D] [--ortho-height H] [--fisheye-fov DEG]
  *       [--bake-lightmap [--atlas WxH] [--bake-margin M] [--bake-dilate N]]
@@ -74,6 +74,7 @@ typedef struct { int rounds; int hit_max_batches; int tiles; int tiles_converged
 int         terra_amd_accumulate_moments ( HTerraScene, const TerraFramebuffer*, void*, size_t, size_t, size_t, size_t ) __attribute__ ( ( weak ) );
 int         terra_amd_denoise_variance ( HTerraScene, const TerraFramebuffer*, const void*, const void*, size_t, size_t, size_t, size_t, int, TerraFloat3*, TerraFloat3* ) __attribute__ ( ( weak ) );
 int         terra_amd_render_adaptive ( const TerraCamera*, HTerraScene, TerraFramebuffer*, void*, void*, size_t, size_t, size_t, size_t, const void*, void* ) __attribute__ ( ( weak ) );
+int         terra_amd_render_adaptive_masked ( const TerraCamera*, HTerraScene, TerraFramebuffer*, void*, void*, size_t, size_t, size_t, size_t, const void*, void* ) __attribute__ ( ( weak ) );
 
 /* the per-pixel history of the temporal reprojection (TerraAmdHistory, TerraAmdTemporalOptions of terra_amd.h, restated for the same reason) */
 typedef struct { float radiance[3]; float length; float normal[3]; float depth; float mu1, mu2; float reserved[2]; } HistoryEntry;
@@ -617,6 +618,8 @@ static const char* kHelp =
     "           (terra_amd_denoise_variance)\n"
     "  --adaptive TARGET [--min-passes A --max-passes B] (libterra_amd.so only): passes per --tile (0 = 128) tile until its relative error is at most TARGET\n"
     "           (terra_amd_render_adaptive); the report goes to stderr\n"
+    "  --adaptive-masked (with --adaptive, libterra_amd.so only): each round is one masked launch over the active tiles' pixel blocks instead of one call per\n"
+    "           tile (terra_amd_render_adaptive_masked); the same rounds and report\n"
     "  --variance out.pfm (libterra_amd.so only): the variance of each pixel's mean luminance after --passes / --adaptive\n"
     "  --frames N [--camera-to px py pz dx dy dz]: N frames, frame f under the camera interpolated linearly between --camera and --camera-to (position and direction;\n"
     "           f / (N - 1) of the way); each frame clears the framebuffer, renders --passes passes and is written to out.0000.ext, out.0001.ext ...\n"
@@ -651,7 +654,7 @@ int main ( int argc, char** argv ) {
     size_t W = 800, H = 600, spp = 8, bounces = 4, tile = 0;     /* defaults of satellite/include/Config.hpp:19-113 */
     int integrator = kTerraIntegratorDirect, tonemap = kTerraTonemappingOperatorLinear, flip = 1, fast = -1, have_seed = 0, split = -1, apollo = 1, gpus = 0;
     const char* aov_prefix = NULL; int denoise = -1;
-    int passes = 1, denoise_var = -1, min_passes = 0, max_passes = 0; float adaptive = 0.f; const char* variance_path = NULL;
+    int passes = 1, denoise_var = -1, min_passes = 0, max_passes = 0, adaptive_masked = 0; float adaptive = 0.f; const char* variance_path = NULL;
     int frames = 0, have_camera_to = 0; float temporal = -1.f; TerraCamera cam_to; memset ( &cam_to, 0, sizeof cam_to );
     const char* dump_path = NULL; int no_render = 0;
     int camera_model = 0; float aperture = 0.f, focus = 1.f, ortho_height = 2.f, fisheye_fov = 180.f;      /* camera_model: 0 pinhole, 1 thinlens, 2 ortho, 3 equirect, 4 fisheye */
@@ -692,6 +695,7 @@ int main ( int argc, char** argv ) {
         else if ( !strcmp ( a, "--denoise" ) ) { denoise = atoi ( NEXT() ); if ( denoise < 0 || denoise > 8 ) { fprintf ( stderr, "terra_headless: --denoise 0 .. 8\n" ); return 64; } }
         else if ( !strcmp ( a, "--passes" ) ) { passes = atoi ( NEXT() ); if ( passes < 1 ) { fprintf ( stderr, "terra_headless: --passes 1 ...\n" ); return 64; } }
         else if ( !strcmp ( a, "--denoise-variance" ) ) { denoise_var = atoi ( NEXT() ); if ( denoise_var < 0 || denoise_var > 8 ) { fprintf ( stderr, "terra_headless: --denoise-variance 0 .. 8\n" ); return 64; } }
+        else if ( !strcmp ( a, "--adaptive-masked" ) ) adaptive_masked = 1;
         else if ( !strcmp ( a, "--adaptive" ) ) { adaptive = ( float ) atof ( NEXT() ); if ( !( adaptive > 0.f ) ) { fprintf ( stderr, "terra_headless: --adaptive TARGET > 0\n" ); return 64; } }
         else if ( !strcmp ( a, "--min-passes" ) ) min_passes = atoi ( NEXT() );
         else if ( !strcmp ( a, "--max-passes" ) ) max_passes = atoi ( NEXT() );
@@ -723,6 +727,7 @@ int main ( int argc, char** argv ) {
         } else { fprintf ( stderr, "terra_headless: unknown option %s\n", a ); return 64; }
     }
     cam.fov = fov;
+    if ( adaptive_masked && !( adaptive > 0.f ) ) { fprintf ( stderr, "terra_headless: --adaptive-masked is valid only with --adaptive TARGET\n" ); return 64; }
     TerraTexture env_tex; memset ( &env_tex, 0, sizeof env_tex );
     if ( env_path ) {              /* read before the mesh: a bad map is refused before any work */
         size_t ew = 0, eh = 0; char err[128] = "";
@@ -847,6 +852,7 @@ int main ( int argc, char** argv ) {
             if ( gpus > 0 || adaptive > 0.f ) { fprintf ( stderr, "terra_headless: --camera-model does not mirror --gpus / --adaptive; those are ignored\n" ); gpus = 0; adaptive = 0.f; }
         }
     }
+    if ( adaptive_masked && !terra_amd_render_adaptive_masked ) { fprintf ( stderr, "terra_headless: --adaptive-masked needs libterra_amd.so; ignored\n" ); adaptive_masked = 0; }
     MomentSum* mom = NULL;       /* --passes / --denoise-variance / --adaptive / --variance: the second moments of the batch means */
     if ( passes > 1 || denoise_var >= 0 || adaptive > 0.f || variance_path ) {
         const char* why = ( !terra_amd_accumulate_moments || !terra_amd_denoise_variance || !terra_amd_render_adaptive || !terra_amd_render_aov ) ? "need libterra_amd.so" : gpus > 0 ? "do not mirror --gpus (the sharded render)" : NULL;
@@ -930,8 +936,8 @@ int main ( int argc, char** argv ) {
     }
     if ( mom && adaptive > 0.f ) {
         AdaptiveOptions ao = { tile, min_passes, max_passes, adaptive, 0 }; AdaptiveReport ar; memset ( &ar, 0, sizeof ar );
-        if ( terra_amd_render_adaptive ( &cam, scene, &fb, mom, aov, 0, 0, W, H, &ao, &ar ) != 0 ) { fprintf ( stderr, "terra_headless: %s\n", terra_amd_last_error && *terra_amd_last_error() ? terra_amd_last_error() : "terra_amd_render_adaptive failed" ); return 70; }
-        fprintf ( stderr, "adaptive: %d rounds, %llu tile calls, %llu samples, %d of %d tiles at or below %g, largest error left %g%s\n", ar.rounds, ( unsigned long long ) ar.tile_calls,
+        if ( ( adaptive_masked ? terra_amd_render_adaptive_masked : terra_amd_render_adaptive ) ( &cam, scene, &fb, mom, aov, 0, 0, W, H, &ao, &ar ) != 0 ) { fprintf ( stderr, "terra_headless: %s\n", terra_amd_last_error && *terra_amd_last_error() ? terra_amd_last_error() : "terra_amd_render_adaptive failed" ); return 70; }
+        fprintf ( stderr, "adaptive%s: %d rounds, %llu tile calls, %llu samples, %d of %d tiles at or below %g, largest error left %g%s\n", adaptive_masked ? " (masked launches)" : "", ar.rounds, ( unsigned long long ) ar.tile_calls,
                       ( unsigned long long ) ar.samples, ar.tiles_converged, ar.tiles, ( double ) adaptive, ( double ) ar.max_error, ar.hit_max_batches ? " (--max-passes ended it)" : "" );
     } else if ( mom ) for ( int pass = 0; pass < passes; ++pass ) {
         const size_t t = tile ? tile : ( W > H ? W : H );

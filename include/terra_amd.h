@@ -534,6 +534,52 @@ int terra_amd_render_adaptive_device ( const TerraCamera* camera, HTerraScene sc
 int terra_amd_render_adaptive ( const TerraCamera* camera, HTerraScene scene, TerraFramebuffer* framebuffer, TerraAmdMoments* moments, TerraAmdAovResult* aov,
                                 size_t x, size_t y, size_t width, size_t height, const TerraAmdAdaptiveOptions* options, TerraAmdAdaptiveReport* report );
 
+/* ---- Masked rendering: one launch over the active 16 x 16 pixel blocks of a rectangle ---------------------------------------------------------------------------
+   terra_amd_render_device() / terra_amd_render_aov_device() with a mask that says which 16 x 16 blocks of the rectangle are rendered. Spending samples unevenly --
+   adaptive tiles, re-rendering what changed -- then costs one launch per round instead of one per tile.
+   The mask.  d_mask holds ceil(width / 16) * ceil(height / 16) uint32_t words, row-major, 4-byte aligned. Word (bx, by) stands for the pixels
+   [x + 16 bx, x + 16 bx + 16) x [y + 16 by, y + 16 by + 16), clipped to the rectangle. Non-zero means active. The words are indexed by position in the rectangle.
+   The contract.
+     * With the same prior buffers, every pixel of an active block holds the bits that terra_amd_render_device() (respectively terra_amd_render_aov_device()) over
+       the same rectangle leaves. This covers pixels, results, the draw count and AOV.
+     * Every other byte of those buffers is untouched. Samples are not incremented and no +0 is added.
+     * The sample split is the scene's explicit one. With terra_amd_set_sample_split(scene, 0) it is what the unmasked launch of that rectangle would choose. The
+       host does not read the mask.
+     * It follows, and is tested, that with an explicit split the call equals hand-issued terra_amd_render_device() calls on the active blocks' rectangles.
+     * Job order, empty skip, leaf boxes and pairs apply to the active blocks exactly as in an unmasked launch.
+   The calls run on the scene's primary device with rank 0 of 1, like terra_amd_render_device(). They refuse what that call refuses, and a NULL mask or one that is
+   not 4-byte aligned with kTerraAmdErrBadArgument. Sharded and multi-device masked launches, and masked forms of the ray, lens and point calls, do not exist.
+   LDS-resident scenes only.  A masked launch rides on the job table of the launches that key their streams ahead (TerraAmdTraversalInfo::lds_resident = 1 and a
+   tree mode other than 1). For every other scene -- the fast tree, the reference tree read from global memory -- all masked calls, the AOV form and the adaptive
+   driver below included, return kTerraAmdErrUnsupported with a message and touch nothing: teaching those kernels to skip blocks made their unmasked frames
+   0.4 - 0.5 % slower. terra_amd_render_adaptive_device() serves such scenes.
+   Stats.  terra_amd_get_stats() counts one launch per call; its host-side `pixels` and `samples` count the WHOLE rectangle, active or not (the host does not read
+   the mask). The adaptive driver below reports the true numbers. An inactive block traces nothing: the work counters see the active blocks only.
+   Asynchronous on `stream`. */
+int terra_amd_render_masked_device ( const TerraCamera* camera, HTerraScene scene, void* d_pixels, void* d_results,
+                                     size_t fb_width, size_t fb_height, size_t x, size_t y, size_t width, size_t height,
+                                     const void* d_mask, void* d_rand_calls, void* stream );
+/* The same on a host framebuffer and a host mask: the frame is uploaded, rendered and downloaded; synchronous. */
+int terra_amd_render_masked ( const TerraCamera* camera, HTerraScene scene, const TerraFramebuffer* framebuffer,
+                              size_t x, size_t y, size_t width, size_t height, const uint32_t* mask );
+/* The AOV call that mirrors it: d_aov as terra_amd_render_aov_device() takes it; an inactive block's records, `samples` included, are untouched. */
+int terra_amd_render_aov_masked_device ( const TerraCamera* camera, HTerraScene scene, void* d_aov,
+                                         size_t fb_width, size_t fb_height, size_t x, size_t y, size_t width, size_t height,
+                                         const void* d_mask, void* stream );
+/* The mask of the adaptive rule from tile errors: d_errors as terra_amd_tile_error_device() leaves them for a rectangle of width x height and tile_size (0: 128).
+   Block (bx, by) belongs to tile (16 bx / tile_size, 16 by / tile_size) and is active (its word 1, else 0) iff all != 0 or the tile's error > target_error --
+   the adaptive driver's comparison: +INFINITY is active, NaN and equality are not. Runs on the current device; asynchronous on `stream`. */
+int terra_amd_error_mask_device ( const void* d_errors, size_t width, size_t height, size_t tile_size, float target_error, int all, void* d_mask, void* stream );
+/* terra_amd_render_adaptive_device() / terra_amd_render_adaptive() on masked launches: the same rounds, options and report; in each round the per-tile calls are one
+   terra_amd_error_mask_device(), one terra_amd_render_masked_device() and, where d_aov is given, one terra_amd_render_aov_masked_device() over the rectangle. Moments,
+   tile error and the read-back are the same. tile_calls and samples count the active tiles and their samples. With an explicit sample split the buffers and the
+   report equal the tile driver's bit for bit; with the automatic split (0) the masked launch takes the split of the whole rectangle, the tile calls that of a tile. */
+int terra_amd_render_adaptive_masked_device ( const TerraCamera* camera, HTerraScene scene, void* d_pixels, void* d_results, void* d_moments, void* d_aov,
+                                              size_t fb_width, size_t fb_height, size_t x, size_t y, size_t width, size_t height,
+                                              const TerraAmdAdaptiveOptions* options, TerraAmdAdaptiveReport* report, void* stream );
+int terra_amd_render_adaptive_masked ( const TerraCamera* camera, HTerraScene scene, TerraFramebuffer* framebuffer, TerraAmdMoments* moments, TerraAmdAovResult* aov,
+                                       size_t x, size_t y, size_t width, size_t height, const TerraAmdAdaptiveOptions* options, TerraAmdAdaptiveReport* report );
+
 /* ---- Temporal reprojection: a per-pixel history carried across camera moves (the temporal half of SVGF: Schied et al., HPG 2017) -----------------------------
    A client that renders one frame per camera keeps two history buffers and the previous frame's camera: after the frame's render call and AOV call (framebuffer
    and AOV buffer cleared before them) it calls terra_amd_reproject* with last frame's history as history_in and the other buffer as history_out, then swaps them.

@@ -208,6 +208,19 @@ RAY_SOURCE_SIGNATURES = {
     "terra_amd_render_aov_rays": (c_int, [c_void_p, c_void_p, c_void_p] + [c_size_t] * 6),
 }
 
+# ... and of masked rendering (include/terra_amd.h "Masked rendering"): the masked camera call, its host and AOV forms, the mask from tile errors, and the adaptive
+# driver on masked launches
+MASKED_SIGNATURES = {
+    "terra_amd_render_masked_device": (c_int, [POINTER(TerraCamera), c_void_p, c_void_p, c_void_p] + [c_size_t] * 6 + [c_void_p, c_void_p, c_void_p]),
+    "terra_amd_render_masked": (c_int, [POINTER(TerraCamera), c_void_p, POINTER(TerraFramebuffer)] + [c_size_t] * 4 + [c_void_p]),
+    "terra_amd_render_aov_masked_device": (c_int, [POINTER(TerraCamera), c_void_p, c_void_p] + [c_size_t] * 6 + [c_void_p, c_void_p]),
+    "terra_amd_error_mask_device": (c_int, [c_void_p, c_size_t, c_size_t, c_size_t, c_float, c_int, c_void_p, c_void_p]),
+    "terra_amd_render_adaptive_masked_device": (c_int, [POINTER(TerraCamera), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p] + [c_size_t] * 6 +
+                                                [POINTER(TerraAmdAdaptiveOptions), POINTER(TerraAmdAdaptiveReport), c_void_p]),
+    "terra_amd_render_adaptive_masked": (c_int, [POINTER(TerraCamera), c_void_p, POINTER(TerraFramebuffer), c_void_p, c_void_p] + [c_size_t] * 4 +
+                                         [POINTER(TerraAmdAdaptiveOptions), POINTER(TerraAmdAdaptiveReport)]),
+}
+
 
 
 class Lens(Structure):

@@ -39,7 +39,7 @@ static_assert ( sizeof ( DevAov ) == 48, "DevAov must be 48 bytes" );
 #define TERRA_AOV_RAYS_PARAM , const float4* rays
 #else
 #define TERRA_AOV_KERNEL terra_aov_kernel
-#define TERRA_AOV_RAYS_PARAM
+#define TERRA_AOV_RAYS_PARAM , const uint32_t* mask      // masked launches (include/terra_amd.h "Masked rendering"): one word per 16x16 block of the rectangle, row-major as the blocks here are; nullptr: none
 #endif
 template <int MODE>
 __global__ __launch_bounds__ ( 256 ) void TERRA_AOV_KERNEL ( DevRenderParams p, float4* aov, uint32_t* spill, uint32_t vblocks, uint32_t blocks_x TERRA_AOV_RAYS_PARAM ) {
@@ -55,6 +55,9 @@ __global__ __launch_bounds__ ( 256 ) void TERRA_AOV_KERNEL ( DevRenderParams p, 
     for ( uint32_t vb = blockIdx.x; vb < vblocks; vb += gridDim.x ) {
         // virtual block vb = part (vb mod split) of 16x16 pixel block vb / split of the rectangle; a wave covers an 8x8 packet as in the render (block_pixel)
         const uint32_t blk = vb >> p.split_log2, r = ( ( vb & ( p.split - 1u ) ) << ppb_log2 ) + k;
+#if TERRA_RAY_SOURCE == 0
+        if ( mask && mask[blk] == 0u ) continue;          // an inactive block is left alone (uniform over the thread block: nobody waits at the barriers below)
+#endif
         const uint32_t by = blk / blocks_x, bx = blk - by * blocks_x;
         const uint32_t wave = r >> 6, lane = r & 63u;
         const uint32_t lx = bx * 16u + ( wave & 1u ) * 8u + ( lane & 7u ), ly = by * 16u + ( wave >> 1 ) * 8u + ( lane >> 3 );
@@ -218,8 +221,8 @@ hipError_t terra_launch_aov_lens ( DevRenderParams p, const DevLens& lens, void*
 hipError_t terra_launch_aov_rays ( DevRenderParams p, const void* rays, void* aov, hipStream_t stream ) {
     if ( !rays ) return hipErrorInvalidValue;
 #else
-#define TERRA_AOV_RAYS_ARG
-hipError_t terra_launch_aov ( DevRenderParams p, void* aov, hipStream_t stream ) {
+#define TERRA_AOV_RAYS_ARG , mask
+hipError_t terra_launch_aov ( DevRenderParams p, void* aov, hipStream_t stream, const uint32_t* mask ) {
 #endif
     const uint32_t blocks_x = ( p.w + 15u ) / 16u, blocks_y = ( p.h + 15u ) / 16u;
     const uint64_t vblocks = ( uint64_t ) blocks_x * blocks_y * p.split;

@@ -334,6 +334,15 @@ struct DevRenderParams {
     // stays where it was; a ray-sourced launch's ray pointer (DevRayRenderParams) moves 8 bytes up.
     float    inv_fb_w, inv_fb_h;
 };
+// masked launches (include/terra_amd.h "Masked rendering"; render_kernels.hip "masked launches"): which 16x16 pixel blocks of the rectangle a launch renders. A property
+// of the launch, beside its ray source, not a field of DevRenderParams: the small kernels around the render grid take its two pointers as arguments of their own, the
+// render kernels that key their streams ahead read DevRenderParams::job_live and the job table as they stand, and so no kernel-argument offset of any kernel moves
+// and no render kernel changes (the kernels that key their streams in place cannot be launched masked: scene_host.cpp masked_plan_check).
+//   words: ceil(w / 16) * ceil(h / 16) words, row-major in the rectangle (not in the launch's tile-major block numbering), non-zero = active;
+//   live_blocks: a word of the launch's scratch header (its own cache line, as job_live's): the blocks the order placed before the masked ones, written by
+//   terra_block_order_kernel, read by terra_resolve_kernel -- a block at or beyond it is left alone.
+struct DevLaunchMask { const uint32_t* words; uint32_t* live_blocks; };
+#define TERRA_CLASS_MASKED 3u      // the block class of an inactive block: the last one (0 hit, 1 empty by probe, 2 proved empty)
 // ray-sourced launches (include/terra_amd.h "Ray-sourced rendering"): the launch's parameters end with the ray buffer -- one TerraAmdRay (two 16-byte words) per pixel,
 // addressed like `results` (st_x / st_y / st_pitch: the frame for the device forms, the staged rectangle for the host forms). The pointer follows DevRenderParams' last field in a structure of its own, which only
 // the ray-sourced kernel instances take: no field of DevRenderParams moves and the camera kernels keep their kernel-argument segment to the byte.

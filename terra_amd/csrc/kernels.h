@@ -5,7 +5,9 @@
 
 hipError_t terra_launch_render ( const DevRenderParams& p, hipStream_t stream );
 hipError_t terra_launch_job_streams ( const DevRenderParams& p, hipStream_t stream );      // before terra_launch_render: DevRenderParams::job_streams (none where terra_job_streams_bytes is 0)
-hipError_t terra_launch_block_order ( const DevRenderParams& p, uint32_t* cls, hipStream_t stream );      // before terra_launch_job_streams: fills p.block_order (= cls + blocks)
+// before terra_launch_job_streams: fills p.block_order (= cls + blocks). mask (nullptr: none): a masked launch -- the blocks whose word is zero go last, *mask->live_blocks = the
+// blocks before them, p.job_live is set and written whatever `prove`; classify = false: the active blocks are not probed (class 0 all); prove: empty skip (p.job_live set)
+hipError_t terra_launch_block_order ( const DevRenderParams& p, uint32_t* cls, hipStream_t stream, const DevLaunchMask* mask, bool classify, bool prove );
 // (render_kernels.hip is compiled as several translation units, one per template MODE: 0 reference tree from global memory, 1 LDS-resident, 2 fast tree, 3 fast tree + reachability replay)
 hipError_t terra_launch_render_mode0 ( const DevRenderParams& p, size_t lds, hipStream_t stream );
 hipError_t terra_launch_render_mode1 ( const DevRenderParams& p, size_t lds, hipStream_t stream );
@@ -34,13 +36,14 @@ hipError_t terra_launch_render_points_mode0 ( const DevPointRenderParams& p, siz
 hipError_t terra_launch_render_points_mode1 ( const DevPointRenderParams& p, size_t lds, hipStream_t stream );
 hipError_t terra_launch_render_points_mode2 ( const DevPointRenderParams& p, size_t lds, hipStream_t stream );
 hipError_t terra_launch_render_points_mode3 ( const DevPointRenderParams& p, size_t lds, hipStream_t stream );
-hipError_t terra_launch_resolve ( const DevRenderParams& p, hipStream_t stream );   // second kernel of a split render (p.split > 1)
+hipError_t terra_launch_resolve ( const DevRenderParams& p, hipStream_t stream, const uint32_t* live_blocks );   // second kernel of every render; live_blocks: DevLaunchMask::live_blocks of a masked launch, or nullptr
 hipError_t terra_launch_tiles ( bool pack, float* pixels, void* results, uint32_t fb_w, uint32_t x, uint32_t y, uint32_t w, uint32_t h,
                                 uint32_t tile, uint32_t rank, uint32_t world, float* packed, hipStream_t stream );
 
 // first-hit AOV pass (aov_kernels.hip): p as fill_params made it, with the render's sample split set (split, split_log2, chunk_spp); aov = TerraAmdAovResult
 // per pixel, addressed like p.results (st_x / st_y / st_pitch)
-hipError_t terra_launch_aov ( DevRenderParams p, void* aov, hipStream_t stream );
+// mask: DevLaunchMask::words of a masked launch (a block whose word is zero is left alone), or nullptr
+hipError_t terra_launch_aov ( DevRenderParams p, void* aov, hipStream_t stream, const uint32_t* mask );
 // ... with the rays of a ray-sourced launch (as terra_launch_render_rays takes them) in place of the camera's: depth sums |hit point - ray origin|, an inactive ray
 // adds its samples and nothing else (aov_kernels.hip compiled as a unit of its own, TERRA_TU 4)
 hipError_t terra_launch_aov_rays ( DevRenderParams p, const void* rays, void* aov, hipStream_t stream );
@@ -62,6 +65,8 @@ hipError_t terra_launch_denoise_variance ( const void* results, const void* aov,
 // errors: one float per tile x tile tile of the rectangle, row-major
 hipError_t terra_launch_moments_accumulate ( const void* results, void* moments, uint32_t fb_w, uint32_t x, uint32_t y, uint32_t w, uint32_t h, hipStream_t stream );
 hipError_t terra_launch_tile_error ( const void* moments, uint32_t fb_w, uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint32_t tile, float* errors, hipStream_t stream );
+// the mask of a masked launch over a w x h rectangle from such errors (include/terra_amd.h "Masked rendering"): mask word (bx, by) = all || errors[tile of the block] > target
+hipError_t terra_launch_error_mask ( const float* errors, uint32_t w, uint32_t h, uint32_t tile, float target, int all, uint32_t* mask, hipStream_t stream );
 
 // temporal reprojection of a per-pixel history (temporal_kernels.hip; include/terra_amd.h "Temporal reprojection"): every buffer indexed like a frame of fb_w pixels
 // per row, only the rectangle is read or written; history_in, out_results, out_moments may be nullptr. cam / prev: the two cameras as fill_camera made them.

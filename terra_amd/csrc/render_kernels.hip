@@ -230,11 +230,13 @@ TD bool block_pixel ( const DevRenderParams& p, uint32_t blk, uint32_t tid, uint
 // Second kernel of every render: pixel += chunk sums, in chunk order (float adds in the order `split` successive calls
 // would make them; split == 1: the one sum of the call, reference src/Terra.c:570-572), then exposure / tonemap / store
 // (src/Terra.c:574-630). gridDim.x = the job space's 16x16 pixel blocks.
-__global__ __launch_bounds__ ( 256 ) void terra_resolve_kernel ( DevRenderParams p ) {
+// live_blocks (masked launches, DevLaunchMask::live_blocks; else nullptr): a block the order placed at or beyond *live_blocks is inactive -- neither read nor written here.
+__global__ __launch_bounds__ ( 256 ) void terra_resolve_kernel ( DevRenderParams p, const uint32_t* live_blocks ) {
     if ( p.job_queue && blockIdx.x == 0 && threadIdx.x == 0 ) *p.job_queue = 0u;       // the render kernel is done with its queue: leave the word ready for the next launch on this scratch (scene_host.cpp launch_render)
+    const uint32_t vb = p.block_order ? p.block_order[gridDim.x + blockIdx.x] : blockIdx.x;      // where the job order put this pixel block: its sums are stored under that number
+    if ( live_blocks && vb >= *live_blocks ) return;
     uint32_t px, py;
     if ( !block_pixel ( p, blockIdx.x, threadIdx.x, px, py ) ) return;
-    const uint32_t vb = p.block_order ? p.block_order[gridDim.x + blockIdx.x] : blockIdx.x;      // where the job order put this pixel block: its sums are stored under that number
     const size_t pix = ( size_t ) ( py - p.st_y ) * p.st_pitch + ( px - p.st_x );
     DevResult* results = reinterpret_cast<DevResult*> ( p.results );
     DevResult out = results[pix];
@@ -1061,10 +1063,18 @@ __global__ __launch_bounds__ ( 256 ) void terra_job_streams_kernel ( DevRenderPa
 // short work to fill the lanes beside them, and the launch ends on jobs of a few ray iterations. Only the ORDER in which jobs are taken changes: which job a lane runs
 // never mattered (render_kernels.hip "jobs"), a block's sums are stored under its place in the order and the resolve kernel looks them up there (DevRenderParams::block_order).
 #define TERRA_CLASS_LDS_TRIS 256          // triangles the classifier stages in LDS (12 KB); larger scenes are read from global memory
-__global__ __launch_bounds__ ( 256 ) void terra_block_class_kernel ( DevRenderParams p, uint32_t nblocks, uint32_t* cls, uint32_t prove ) {
+// Masked launches (include/terra_amd.h "Masked rendering"; dev_types.h DevLaunchMask): `mask` non-null = the caller says which blocks are rendered at all. A block's
+// word is found by where its first pixel lies in the rectangle -- the words are row-major there, the launch's blocks tile-major --; a block whose word is zero, or that
+// has no pixel, gets TERRA_CLASS_MASKED, the last class, whatever its rays would hit. probe == 0 (a launch the classifier would not have run for: small launches,
+// scenes of more than 4096 triangles): no probe rays, an active block is class 0.
+// Only the kernels that key their streams ahead (MODE 1) can be launched masked: they alone end their job space at *job_live and take a job's pixel from the table
+// that terra_job_streams_kernel filled through block_order. The kernels that key their streams in place would have to read both themselves; with every one of their
+// instances at its SGPR limit that cost 4 - 9 more spilled SGPRs each and 0.4 - 0.5 % of the hall frames (profiles/masked/ab.md), so they are left as they are and
+// the host refuses a masked launch of them (scene_host.cpp launch_render).
+__global__ __launch_bounds__ ( 256 ) void terra_block_class_kernel ( DevRenderParams p, uint32_t nblocks, uint32_t* cls, uint32_t prove, const uint32_t* mask, uint32_t probe ) {
     __shared__ float4 staged[3 * TERRA_CLASS_LDS_TRIS];
     const float4* tris = reinterpret_cast<const float4*> ( p.scene.tris );
-    if ( p.scene.n_tris <= TERRA_CLASS_LDS_TRIS ) {          // (every thread of the block takes part, also those beyond the last pixel block)
+    if ( ( probe || prove ) && p.scene.n_tris <= TERRA_CLASS_LDS_TRIS ) {          // (every thread of the block takes part, also those beyond the last pixel block)
         for ( uint32_t i = threadIdx.x; i < 3 * p.scene.n_tris; i += 256u ) staged[i] = tris[i];
         __syncthreads();
         tris = staged;
@@ -1072,7 +1082,7 @@ __global__ __launch_bounds__ ( 256 ) void terra_block_class_kernel ( DevRenderPa
     // eight lanes per pixel block, five of them with a probe each (centre and corners): the block's class is the vote of its lanes
     const uint32_t id = blockIdx.x * 256u + threadIdx.x, b = id >> 3, k = id & 7u;
     bool hit = false;
-    if ( b < nblocks && k < 5u ) {
+    if ( probe && b < nblocks && k < 5u ) {
         const uint32_t lx = k == 0 ? 8u : ( ( k - 1 ) & 1u ) * 15u, ly = k == 0 ? 8u : ( ( k - 1 ) >> 1 ) * 15u;
         const uint32_t tid = ( ( ( lx >> 3 ) | ( ( ly >> 3 ) << 1 ) ) << 6 ) | ( lx & 7u ) | ( ( ly & 7u ) << 3 );      // (block_pixel's thread -> pixel map, inverted)
         uint32_t px, py;
@@ -1105,39 +1115,52 @@ __global__ __launch_bounds__ ( 256 ) void terra_block_class_kernel ( DevRenderPa
     }
     const unsigned long long votes = __ballot ( hit ), doubts = __ballot ( refuted );
     const uint32_t group = threadIdx.x & 56u;
-    if ( b < nblocks && k == 0 ) cls[b] = ( ( votes >> group ) & 0xffull ) ? 0u : ( ( doubts >> group ) & 0xffull ) ? 1u : 2u;      // (a probe that hits outvotes a proof: never both, but the trace is the safe side)
+    if ( b < nblocks && k == 0 ) {
+        uint32_t c = ( ( votes >> group ) & 0xffull ) ? 0u : ( ( doubts >> group ) & 0xffull ) ? 1u : 2u;      // (a probe that hits outvotes a proof: never both, but the trace is the safe side)
+        if ( mask ) {
+            if ( !probe && c == 1u ) c = 0u;
+            uint32_t px, py;
+            const bool has_pixel = job_pixel_of_block ( p, b, 0u, px, py );      // thread 0's pixel is the block's first
+            if ( !has_pixel || mask[ ( size_t ) ( ( py - p.y ) >> 4 ) * ( ( p.w + 15u ) >> 4 ) + ( ( px - p.x ) >> 4 )] == 0u ) c = TERRA_CLASS_MASKED;
+        }
+        cls[b] = c;
+    }
 }
 // order[0 .. n): the blocks of class 0 (hit) in their own order, then those of class 1 (empty by probe), then those of class 2 (proved empty); order[n + b]: block b's
-// place. *live_jobs (if given) = the jobs of the first two classes, jobs_per_block each; *proved (if given) = the blocks of class 2. One block of 256 threads.
-__global__ __launch_bounds__ ( 256 ) void terra_block_order_kernel ( uint32_t n, const uint32_t* cls, uint32_t* order, uint32_t* live_jobs, uint32_t jobs_per_block, unsigned long long* proved ) {
-    __shared__ uint32_t before0[256], before1[256];
-    __shared__ uint32_t total0, total1;
+// place; last those of TERRA_CLASS_MASKED (masked launches). *live_jobs (if given) = the jobs of the first two classes, jobs_per_block each; *proved (if given) = the
+// blocks of class 2; *live_blocks (if given) = the blocks of the first three classes: the ones placed before the masked ones. One block of 256 threads.
+__global__ __launch_bounds__ ( 256 ) void terra_block_order_kernel ( uint32_t n, const uint32_t* cls, uint32_t* order, uint32_t* live_jobs, uint32_t jobs_per_block, unsigned long long* proved, uint32_t* live_blocks ) {
+    __shared__ uint32_t before0[256], before1[256], before2[256];
+    __shared__ uint32_t total0, total1, total2;
     const uint32_t t = threadIdx.x, per = ( n + 255u ) / 256u;
     const uint32_t lo = t * per < n ? t * per : n, hi = lo + per < n ? lo + per : n;
-    uint32_t c0 = 0, c1 = 0;
-    for ( uint32_t i = lo; i < hi; ++i ) { c0 += cls[i] == 0u; c1 += cls[i] == 1u; }
-    before0[t] = c0; before1[t] = c1;
+    uint32_t c0 = 0, c1 = 0, c2 = 0;
+    for ( uint32_t i = lo; i < hi; ++i ) { c0 += cls[i] == 0u; c1 += cls[i] == 1u; c2 += cls[i] == 2u; }
+    before0[t] = c0; before1[t] = c1; before2[t] = c2;
     __syncthreads();
     if ( t == 0 ) {
-        uint32_t run0 = 0, run1 = 0;
-        for ( uint32_t k = 0; k < 256u; ++k ) { const uint32_t a = before0[k], b = before1[k]; before0[k] = run0; before1[k] = run1; run0 += a; run1 += b; }
-        total0 = run0; total1 = run1;
+        uint32_t run0 = 0, run1 = 0, run2 = 0;
+        for ( uint32_t k = 0; k < 256u; ++k ) { const uint32_t a = before0[k], b = before1[k], c = before2[k]; before0[k] = run0; before1[k] = run1; before2[k] = run2; run0 += a; run1 += b; run2 += c; }
+        total0 = run0; total1 = run1; total2 = run2;
         if ( live_jobs ) *live_jobs = ( run0 + run1 ) * jobs_per_block;
-        if ( proved ) *proved = n - run0 - run1;
+        if ( proved ) *proved = run2;
+        if ( live_blocks ) *live_blocks = run0 + run1 + run2;
     }
     __syncthreads();
-    uint32_t at0 = before0[t], at1 = total0 + before1[t], at2 = total0 + total1 + ( lo - before0[t] - before1[t] );
+    uint32_t at0 = before0[t], at1 = total0 + before1[t], at2 = total0 + total1 + before2[t], at3 = total0 + total1 + total2 + ( lo - before0[t] - before1[t] - before2[t] );
     for ( uint32_t i = lo; i < hi; ++i ) {
-        const uint32_t v = cls[i] == 0u ? at0++ : cls[i] == 1u ? at1++ : at2++;
+        const uint32_t v = cls[i] == 0u ? at0++ : cls[i] == 1u ? at1++ : cls[i] == 2u ? at2++ : at3++;
         order[v] = i; order[n + i] = v;
     }
 }
-hipError_t terra_launch_block_order ( const DevRenderParams& p, uint32_t* cls, hipStream_t stream ) {      // p.block_order = cls + blocks; p.job_live set: the launch skips the blocks proved empty
+// p.block_order = cls + blocks; prove (p.job_live set): the launch skips the blocks proved empty. mask: a masked launch (p.job_live set whatever prove says: the job
+// space ends before the masked blocks at the latest); classify: probe the active blocks (false: class 0 all)
+hipError_t terra_launch_block_order ( const DevRenderParams& p, uint32_t* cls, hipStream_t stream, const DevLaunchMask* mask, bool classify, bool prove ) {
     const uint32_t blocks = terra_render_blocks ( p );
-    if ( !p.block_order || !cls || blocks == 0 ) return hipErrorInvalidValue;
-    hipLaunchKernelGGL ( terra_block_class_kernel, dim3 ( ( blocks * 8 + 255 ) / 256 ), dim3 ( 256 ), 0, stream, p, blocks, cls, p.job_live ? 1u : 0u );      // eight lanes per pixel block
+    if ( !p.block_order || !cls || blocks == 0 || ( ( prove || mask ) && !p.job_live ) || ( mask && ( !mask->words || !mask->live_blocks ) ) || ( !mask && !classify ) ) return hipErrorInvalidValue;
+    hipLaunchKernelGGL ( terra_block_class_kernel, dim3 ( ( blocks * 8 + 255 ) / 256 ), dim3 ( 256 ), 0, stream, p, blocks, cls, prove ? 1u : 0u, mask ? mask->words : nullptr, classify ? 1u : 0u );      // eight lanes per pixel block
     hipLaunchKernelGGL ( terra_block_order_kernel, dim3 ( 1 ), dim3 ( 256 ), 0, stream, blocks, ( const uint32_t* ) cls, const_cast<uint32_t*> ( p.block_order ),
-                         const_cast<uint32_t*> ( p.job_live ), p.split * 256u, p.job_live && p.counters ? p.counters + kCtrSkipProved : nullptr );
+                         const_cast<uint32_t*> ( p.job_live ), p.split * 256u, prove && p.counters ? p.counters + kCtrSkipProved : nullptr, mask ? mask->live_blocks : nullptr );
     return hipGetLastError();
 }
 hipError_t terra_launch_job_streams ( const DevRenderParams& p, hipStream_t stream ) {
@@ -1146,10 +1169,11 @@ hipError_t terra_launch_job_streams ( const DevRenderParams& p, hipStream_t stre
     hipLaunchKernelGGL ( terra_job_streams_kernel, dim3 ( p.job_blocks ), dim3 ( 256 ), 0, stream, p );
     return hipGetLastError();
 }
-hipError_t terra_launch_resolve ( const DevRenderParams& p, hipStream_t stream ) {
+hipError_t terra_launch_resolve ( const DevRenderParams& p, hipStream_t stream, const uint32_t* live_blocks ) {
     uint32_t blocks = terra_render_blocks ( p );
     if ( blocks == 0 ) return hipSuccess;
-    hipLaunchKernelGGL ( terra_resolve_kernel, dim3 ( blocks ), dim3 ( 256 ), 0, stream, p );
+    if ( live_blocks && !p.block_order ) return hipErrorInvalidValue;
+    hipLaunchKernelGGL ( terra_resolve_kernel, dim3 ( blocks ), dim3 ( 256 ), 0, stream, p, live_blocks );
     return hipGetLastError();
 }
 

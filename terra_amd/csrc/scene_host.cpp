@@ -1692,7 +1692,18 @@ struct RaySource {
     RaySource ( Kind k = kCamera, const void* d = nullptr ) : kind ( k ), d_records ( d ) {}
     bool camera() const { return kind == kCamera; }
 };
-static int launch_render ( Scene* s, DevRenderParams& p, int device, hipStream_t stream, const RaySource& src, ThreadSlot* slot = nullptr ) {      // device: the (current) device of the launch
+// d_mask (include/terra_amd.h "Masked rendering"; nullptr: none): the launch renders only the 16x16 blocks of the rectangle whose word is non-zero. A property of the
+// launch, like src: any door may pass one (today the camera door's masked entry points do). A masked launch always has an order section -- the masked blocks are its
+// last class, and the job space and the resolve end before them (DevLaunchMask) -- whatever terra_block_order_bytes says; the sample split, the classifier's probes and
+// the empty skip are those of the unmasked launch of the same rectangle: the host never reads the mask.
+// Only launches that key their streams ahead (LDS-resident scenes, lds_mode 1) can be masked: the kernels that key their streams in place do not look their blocks up
+// in the order (render_kernels.hip "Masked launches" has the measurement that decided it). The masked entry points refuse every other plan, AOV form included.
+static int masked_plan_check ( const void* d_mask, const DevRenderParams& p ) {
+    if ( d_mask && p.lds_mode != 1 )
+        return fail ( kTerraAmdErrUnsupported, "masked rendering needs an LDS-resident launch (TerraAmdTraversalInfo::lds_resident, terra_amd_set_tree_mode other than 1): this scene's kernels key their streams in place and cannot skip pixel blocks" );
+    return 0;
+}
+static int launch_render ( Scene* s, DevRenderParams& p, int device, hipStream_t stream, const RaySource& src, ThreadSlot* slot = nullptr, const uint32_t* d_mask = nullptr ) {      // device: the (current) device of the launch
     const uint32_t blocks = terra_render_blocks ( p );
     if ( blocks == 0 ) return 0;
     if ( p.count_level != 0 || p.rand_calls ) { p.leaf_boxes = nullptr; p.n_leaf_boxes = 0; p.leaf_pairs = 0; }      // the work counters keep their meaning: counting launches walk the tree and test one triangle per trip
@@ -1705,13 +1716,16 @@ static int launch_render ( Scene* s, DevRenderParams& p, int device, hipStream_t
         pool_kept |= 1ull << device;
     }
     // the sections of the launch's scratch, one after the other: [queue word][job sums][job streams (LDS-resident scenes)][stack spill (fast tree)][job order]
-    const size_t header = 256;                                     // the job queue word (+ padding that keeps the partials 256-byte aligned)
+    const size_t header = d_mask ? 512 : 256;                      // the job queue word (+ padding that keeps the partials 256-byte aligned); a masked launch's second device word has a line of its own
     const size_t partial_bytes = ( size_t ) split * blocks * 256 * sizeof ( float4 );
     p.job_blocks = blocks * split;
     const size_t stream_bytes = terra_job_streams_bytes ( p );
     if ( stream_bytes && ( p.fb_w > 65535u || p.fb_h > 65535u ) ) return fail ( kTerraAmdErrBadArgument, "framebuffer of %u x %u: at most 65,535 pixels per side (the job table packs a pixel into 32 bits)", p.fb_w, p.fb_h );
     const size_t spill_bytes = terra_fast_spill_bytes ( p );                 // fast-tree launches: the part of the lanes' traversal stacks that does not live in LDS
-    const size_t order_bytes = s->job_order ? terra_block_order_bytes ( p, s->job_order == 2, ray_source ) : 0;           // LDS-resident launches: the order the pixel blocks are handed out in (render_kernels.hip "job order")
+    const size_t order_own = s->job_order ? terra_block_order_bytes ( p, s->job_order == 2, ray_source ) : 0;           // LDS-resident launches: the order the pixel blocks are handed out in (render_kernels.hip "job order")
+    if ( d_mask && ray_source ) return fail ( kTerraAmdErrUnsupported, "masked launches: camera launches only" );      // (the job order's classes are made from camera rays)
+    if ( int rc = masked_plan_check ( d_mask, p ) ) return rc;
+    const size_t order_bytes = d_mask ? ( ( size_t ) blocks * 3 * sizeof ( uint32_t ) + 255 ) & ~size_t ( 255 ) : order_own;
     const size_t scratch_bytes = header + partial_bytes + stream_bytes + spill_bytes + order_bytes;
     // (a thread's slot keeps scratch for tile-sized calls only: a full-frame call's gigabytes come from, and go back to, the device's pool)
     // a launch's scratch is bounded: 48 bytes per (pixel, lane-per-pixel) job on LDS-resident scenes -- a 4K frame at 64 lanes per pixel asks for 25 GB per concurrent stream.
@@ -1738,8 +1752,9 @@ static int launch_render ( Scene* s, DevRenderParams& p, int device, hipStream_t
     // empty skip (render_kernels.hip "proved empty"): only where a camera miss leaves nothing behind but +0 sums -- no environment term, no work counters (they are
     // defined by the walk; a per-pixel draw count asks for them too) -- and only inside the coordinate range of the containment proof, which is the fused box test's
     // precondition and the range DESIGN.md 3.6 argues the float triangle test in. Every integrator of the LDS-resident (coupled) loop deposits +0 for a camera miss.
-    const bool skip = s->empty_skip && order_cls && p.job_queue && p.lds_mode == 1 && p.scene.env_mode == 0 && p.count_level == 0 && !p.rand_calls && p.fused_slab;
-    p.job_live = skip ? ( const uint32_t* ) ( ( const char* ) scratch + 128 ) : nullptr;      // (in the header, on a cache line of its own away from the queue word)
+    const bool skip = s->empty_skip && order_own && order_cls && p.job_queue && p.lds_mode == 1 && p.scene.env_mode == 0 && p.count_level == 0 && !p.rand_calls && p.fused_slab;
+    p.job_live = ( skip || d_mask ) ? ( const uint32_t* ) ( ( const char* ) scratch + 128 ) : nullptr;      // (in the header, on a cache line of its own away from the queue word)
+    const DevLaunchMask mask = { d_mask, d_mask ? ( uint32_t* ) ( ( char* ) scratch + 256 ) : nullptr };         // (... and the blocks before the masked ones on the line after)
     {   // the job decode divides block numbers by launch constants: as multiplications by ceil(2^32 / d), exact while (largest dividend) * divisor < 2^32
         const uint64_t bpt = p.tile_size / 16, bpt2 = bpt * bpt, tiles_x = ( p.w + p.tile_size - 1 ) / p.tile_size, tiles_y = ( p.h + p.tile_size - 1 ) / p.tile_size;
         auto magic = [] ( uint64_t d ) { return d <= 1 ? 0u : ( uint32_t ) ( ( ( 1ull << 32 ) + d - 1 ) / d ); };
@@ -1753,7 +1768,7 @@ static int launch_render ( Scene* s, DevRenderParams& p, int device, hipStream_t
         if ( pooled ) ( void ) hipFreeAsync ( scratch, stream );
         return fail ( kTerraAmdErrUnsupported, "the traversal stack of this scene's tree (%u entries) needs %zu KB of LDS per block, more than the %zu KB a block can have", p.stack_depth, terra_lds_bytes ( p ) / 1024, terra_lds_block_limit() / 1024 );
     }
-    if ( e == hipSuccess && order_cls ) e = terra_launch_block_order ( p, order_cls, stream );
+    if ( e == hipSuccess && order_cls ) e = terra_launch_block_order ( p, order_cls, stream, d_mask ? &mask : nullptr, order_own != 0, skip );
     if ( e == hipSuccess ) e = terra_launch_job_streams ( p, stream );
     if ( e == hipSuccess ) switch ( src.kind ) {
         case RaySource::kCamera: e = terra_launch_render ( p, stream ); break;
@@ -1761,7 +1776,7 @@ static int launch_render ( Scene* s, DevRenderParams& p, int device, hipStream_t
         case RaySource::kLens:   e = terra_launch_render_lens ( p, src.lens, stream ); break;
         case RaySource::kPoints: e = terra_launch_render_points ( p, src.d_records, src.points, stream ); break;
     }
-    if ( e == hipSuccess ) e = terra_launch_resolve ( p, stream );
+    if ( e == hipSuccess ) e = terra_launch_resolve ( p, stream, mask.live_blocks );
     if ( pooled ) ( void ) hipFreeAsync ( scratch, stream );
     else if ( e != hipSuccess ) ( void ) hipMemsetAsync ( scratch, 0, header, stream );       // (a launch that failed half way must not leave a used queue word behind)
     if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "render launch: %s", hipGetErrorString ( e ) );
@@ -1771,12 +1786,12 @@ static int launch_render ( Scene* s, DevRenderParams& p, int device, hipStream_t
 }
 
 // The tail of the four device render forms, after the door's own preparation (p, src): the caller's framebuffer in HBM, addressed like the frame
-static int render_device_tail ( Scene* s, const Scene::Replica& r, DevRenderParams& p, const RaySource& src, void* d_pixels, void* d_results, void* d_rand_calls, void* stream ) {
+static int render_device_tail ( Scene* s, const Scene::Replica& r, DevRenderParams& p, const RaySource& src, void* d_pixels, void* d_results, void* d_rand_calls, void* stream, const uint32_t* d_mask = nullptr ) {
     if ( !d_pixels || !d_results ) return fail ( kTerraAmdErrBadArgument, "null framebuffer pointer" );
     p.pixels = ( float* ) d_pixels; p.results = d_results; p.rand_calls = ( uint32_t* ) d_rand_calls;
     if ( d_rand_calls ) p.count_level = 2;
     HIP_TRY ( hipSetDevice ( r.device ), kTerraAmdErrNoDevice );
-    if ( int lrc = launch_render ( s, p, r.device, ( hipStream_t ) stream, src ) ) return lrc;
+    if ( int lrc = launch_render ( s, p, r.device, ( hipStream_t ) stream, src, nullptr, d_mask ) ) return lrc;
     account_launch ( s, p );
     return 0;
 }
@@ -1921,7 +1936,7 @@ static_assert ( sizeof ( TerraAmdAovResult ) == 48, "TerraAmdAovResult must be 4
 // p: the launch fill_params made for the render call this AOV call mirrors; the split is the one that call takes (launch_split), and the samples the AOV buffer
 // already holds key the streams as the framebuffer's do. Runs on the current device (the scene's primary one).
 // src: the door of that render call (its records addressed like d_aov).
-static int launch_aov ( Scene* s, DevRenderParams& p, void* d_aov, hipStream_t stream, const RaySource& src ) {
+static int launch_aov ( Scene* s, DevRenderParams& p, void* d_aov, hipStream_t stream, const RaySource& src, const uint32_t* d_mask = nullptr ) {
     const uint32_t blocks = terra_render_blocks ( p );
     if ( blocks == 0 ) return 0;
     const uint32_t split = launch_split ( s, p, blocks, !src.camera() );
@@ -1930,7 +1945,7 @@ static int launch_aov ( Scene* s, DevRenderParams& p, void* d_aov, hipStream_t s
     p.pixels = nullptr; p.results = nullptr; p.rand_calls = nullptr; p.counters = nullptr; p.count_level = 0;
     hipError_t e = hipSuccess;
     switch ( src.kind ) {
-        case RaySource::kCamera: e = terra_launch_aov ( p, d_aov, stream ); break;
+        case RaySource::kCamera: e = terra_launch_aov ( p, d_aov, stream, d_mask ); break;
         case RaySource::kRays:   e = terra_launch_aov_rays ( p, src.d_records, d_aov, stream ); break;
         case RaySource::kLens:   e = terra_launch_aov_lens ( p, src.lens, d_aov, stream ); break;
         case RaySource::kPoints: e = terra_launch_aov_points ( p, src.d_records, src.points, d_aov, stream ); break;
@@ -1941,11 +1956,11 @@ static int launch_aov ( Scene* s, DevRenderParams& p, void* d_aov, hipStream_t s
 static int aov_check ( const void* aov ) { return aov ? 0 : fail ( kTerraAmdErrBadArgument, "null AOV buffer" ); }
 // The tail of the four AOV device forms, after the door's own preparation (p, src), with the buffer's addressing spelled out: d_aov (and the door's records) hold
 // rows of st_pitch pixels whose first is pixel (st_x, st_y) of the frame
-static int aov_device_tail ( Scene* s, DevRenderParams& p, const RaySource& src, void* d_aov, size_t st_x, size_t st_y, size_t st_pitch, void* stream ) {
+static int aov_device_tail ( Scene* s, DevRenderParams& p, const RaySource& src, void* d_aov, size_t st_x, size_t st_y, size_t st_pitch, void* stream, const uint32_t* d_mask = nullptr ) {
     if ( int rc = aov_check ( d_aov ) ) return rc;
     HIP_TRY ( hipSetDevice ( primary ( s ).device ), kTerraAmdErrNoDevice );
     p.st_x = ( uint32_t ) st_x; p.st_y = ( uint32_t ) st_y; p.st_pitch = ( uint32_t ) st_pitch;
-    return launch_aov ( s, p, d_aov, ( hipStream_t ) stream, src );
+    return launch_aov ( s, p, d_aov, ( hipStream_t ) stream, src, d_mask );
 }
 // The tail of the four AOV host forms: the rectangle only goes up and comes back, rows of q.w pixels (as render_staged_tail stages it); records: the host records of
 // the ray and point doors, whose rectangle goes up beside it
@@ -2287,6 +2302,138 @@ extern "C" int terra_amd_render_adaptive ( const TerraCamera* cam, HTerraScene h
     if ( e == hipSuccess && aov ) e = c.up ( 3, aov, n * 48 );
     if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "adaptive upload: %s", hipGetErrorString ( e ) );
     if ( int rc = terra_amd_render_adaptive_device ( cam, h, c.d[0], c.d[1], c.d[2], aov ? c.d[3] : nullptr, fb->width, fb->height, x, y, w, hgt, options, report, nullptr ) ) return rc;
+    e = c.down ( 0, fb->pixels, n * 12 );
+    if ( e == hipSuccess ) e = c.down ( 1, fb->results, n * 16 );
+    if ( e == hipSuccess ) e = c.down ( 2, moments, n * 32 );
+    if ( e == hipSuccess && aov ) e = c.down ( 3, aov, n * 48 );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "adaptive download: %s", hipGetErrorString ( e ) );
+    return 0;
+}
+
+// ---- masked rendering: one launch over the active 16x16 blocks of a rectangle (include/terra_amd.h "Masked rendering") -----------------------------
+// the one check of the masked entry points, after fill_params' (scene, camera, rectangle): the mask is there and 4-byte aligned (the kernels read it as 32-bit words)
+static int mask_check ( const void* mask, const char* what ) {
+    if ( !mask ) return fail ( kTerraAmdErrBadArgument, "%s: null mask", what );
+    if ( ( uintptr_t ) mask & 3u ) return fail ( kTerraAmdErrBadArgument, "%s: the mask must be 4-byte aligned", what );
+    return 0;
+}
+extern "C" int terra_amd_render_masked_device ( const TerraCamera* cam, HTerraScene h, void* d_pixels, void* d_results, size_t fb_w, size_t fb_h,
+                                                size_t x, size_t y, size_t w, size_t hgt, const void* d_mask, void* d_rand_calls, void* stream ) {
+    Scene* s = S ( h );
+    const Scene::Replica& r = primary ( s );
+    DevRenderParams p;
+    if ( int rc = fill_params ( s, r, cam, fb_w, fb_h, x, y, w, hgt, 64, 0, 1, p ) ) return rc;
+    if ( int rc = mask_check ( d_mask, "terra_amd_render_masked_device" ) ) return rc;
+    return render_device_tail ( s, r, p, RaySource(), d_pixels, d_results, d_rand_calls, stream, ( const uint32_t* ) d_mask );
+}
+extern "C" int terra_amd_render_aov_masked_device ( const TerraCamera* cam, HTerraScene h, void* d_aov, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t hgt,
+                                                    const void* d_mask, void* stream ) {
+    Scene* s = S ( h );
+    DevRenderParams p;
+    if ( int rc = fill_params ( s, primary ( s ), cam, fb_w, fb_h, x, y, w, hgt, 64, 0, 1, p ) ) return rc;
+    if ( int rc = mask_check ( d_mask, "terra_amd_render_aov_masked_device" ) ) return rc;
+    if ( int rc = masked_plan_check ( d_mask, p ) ) return rc;
+    return aov_device_tail ( s, p, RaySource(), d_aov, 0, 0, fb_w, stream, ( const uint32_t* ) d_mask );
+}
+// the host form: the frame goes up whole and comes back whole (an inactive block's pixels are the caller's own), the mask beside it
+extern "C" int terra_amd_render_masked ( const TerraCamera* cam, HTerraScene h, const TerraFramebuffer* fb, size_t x, size_t y, size_t w, size_t hgt, const uint32_t* mask ) {
+    Scene* s = S ( h );
+    if ( !fb || !fb->pixels || !fb->results ) return fail ( kTerraAmdErrBadArgument, "null framebuffer" );
+    DevRenderParams p;
+    if ( int rc = fill_params ( s, primary ( s ), cam, fb->width, fb->height, x, y, w, hgt, 64, 0, 1, p ) ) return rc;          // (the checks alone, before anything is uploaded)
+    if ( int rc = mask_check ( mask, "terra_amd_render_masked" ) ) return rc;
+    HIP_TRY ( hipSetDevice ( primary ( s ).device ), kTerraAmdErrNoDevice );
+    const size_t n = fb->width * fb->height, words = ( ( w + 15 ) / 16 ) * ( ( hgt + 15 ) / 16 );
+    FrameCopy c;
+    hipError_t e = c.up ( 0, fb->pixels, n * 12 );
+    if ( e == hipSuccess ) e = c.up ( 1, fb->results, n * 16 );
+    if ( e == hipSuccess ) e = c.up ( 2, mask, words * sizeof ( uint32_t ) );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "masked render upload: %s", hipGetErrorString ( e ) );
+    if ( int rc = terra_amd_render_masked_device ( cam, h, c.d[0], c.d[1], fb->width, fb->height, x, y, w, hgt, c.d[2], nullptr, nullptr ) ) return rc;
+    e = c.down ( 0, fb->pixels, n * 12 );
+    if ( e == hipSuccess ) e = c.down ( 1, fb->results, n * 16 );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "masked render download: %s", hipGetErrorString ( e ) );
+    return 0;
+}
+// the mask of the adaptive rule: errors as terra_amd_tile_error_device leaves them for the same width, height and tile_size
+extern "C" int terra_amd_error_mask_device ( const void* d_errors, size_t w, size_t hgt, size_t tile, float target_error, int all, void* d_mask, void* stream ) {
+    if ( w == 0 || hgt == 0 || w > 0xffffffffull || hgt > 0xffffffffull ) return fail ( kTerraAmdErrBadArgument, "bad error mask rectangle %zux%zu", w, hgt );
+    if ( !d_errors ) return fail ( kTerraAmdErrBadArgument, "terra_amd_error_mask_device: null errors" );
+    if ( int rc = mask_check ( d_mask, "terra_amd_error_mask_device" ) ) return rc;
+    if ( int rc = tile_size_check ( tile ) ) return rc;
+    const hipError_t e = terra_launch_error_mask ( ( const float* ) d_errors, ( uint32_t ) w, ( uint32_t ) hgt, ( uint32_t ) tile, target_error, all, ( uint32_t* ) d_mask, ( hipStream_t ) stream );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "error mask launch: %s", hipGetErrorString ( e ) );
+    return 0;
+}
+// terra_amd_render_adaptive_device with each round's tile calls as one masked launch (and one masked AOV launch): the rounds, the moments, the tile error and the
+// read-back are that driver's; the report counts the active tiles and their samples from the errors the host holds, as that driver does
+extern "C" int terra_amd_render_adaptive_masked_device ( const TerraCamera* cam, HTerraScene h, void* d_pixels, void* d_results, void* d_moments, void* d_aov, size_t fb_w, size_t fb_h,
+                                                         size_t x, size_t y, size_t w, size_t hgt, const TerraAmdAdaptiveOptions* options, TerraAmdAdaptiveReport* report, void* stream ) {
+    Scene* s = S ( h );
+    if ( int rc = frame_check ( s, "adaptive", fb_w, fb_h, x, y, w, hgt ) ) return rc;
+    if ( !cam || !d_pixels || !d_results || !d_moments ) return fail ( kTerraAmdErrBadArgument, "null camera, framebuffer or moments buffer" );
+    size_t tile = options ? options->tile_size : 0;
+    if ( int rc = tile_size_check ( tile ) ) return rc;
+    const int min_b = options && options->min_batches ? options->min_batches : 4, max_b = options && options->max_batches ? options->max_batches : 64;
+    const float target = options && options->target_error != 0.f ? options->target_error : 0.05f;
+    if ( min_b < 2 || max_b < min_b || ! ( target > 0.f ) ) return fail ( kTerraAmdErrBadArgument, "adaptive options: min_batches %d (>= 2), max_batches %d (>= min_batches), target_error %g (> 0)", min_b, max_b, ( double ) target );
+    HIP_TRY ( hipSetDevice ( primary ( s ).device ), kTerraAmdErrNoDevice );
+    const size_t tiles_x = ( w + tile - 1 ) / tile, tiles_y = ( hgt + tile - 1 ) / tile, tiles = tiles_x * tiles_y;
+    const size_t spp = s->opts.samples_per_pixel, words = ( ( w + 15 ) / 16 ) * ( ( hgt + 15 ) / 16 );
+    std::vector<float> err ( tiles, INFINITY );
+    FrameCopy c;          // [0] the tile errors, [1] the mask: freed when the call returns
+    hipError_t ea = c.up ( 0, nullptr, tiles * sizeof ( float ) );
+    if ( ea == hipSuccess ) ea = c.up ( 1, nullptr, words * sizeof ( uint32_t ) );
+    if ( ea != hipSuccess ) { ( void ) hipGetLastError(); return fail ( kTerraAmdErrNoDevice, "adaptive scratch: %s", hipGetErrorString ( ea ) ); }
+    float* const d_err = ( float* ) c.d[0];
+    TerraAmdAdaptiveReport rep = {};
+    rep.tiles = ( int ) tiles;
+    int rc = 0;
+    for ( int r = 0; r < max_b && !rc; ++r ) {
+        size_t active = 0;
+        for ( size_t t = 0; t < tiles; ++t ) {
+            if ( r >= min_b && ! ( err[t] > target ) ) continue;
+            const size_t x0 = ( t % tiles_x ) * tile, y0 = ( t / tiles_x ) * tile, tw = std::min ( tile, w - x0 ), th = std::min ( tile, hgt - y0 );
+            ++active; ++rep.tile_calls; rep.samples += ( uint64_t ) tw * th * spp;
+        }
+        if ( active == 0 ) break;
+        // (round 0's errors on the device are the zeros of the allocation: rounds below min_batches pass all = 1 and do not look at them)
+        rc = terra_amd_error_mask_device ( d_err, w, hgt, tile, target, r < min_b ? 1 : 0, c.d[1], stream );
+        if ( !rc ) rc = terra_amd_render_masked_device ( cam, h, d_pixels, d_results, fb_w, fb_h, x, y, w, hgt, c.d[1], nullptr, stream );
+        if ( !rc && d_aov ) rc = terra_amd_render_aov_masked_device ( cam, h, d_aov, fb_w, fb_h, x, y, w, hgt, c.d[1], stream );
+        if ( rc ) break;
+        ++rep.rounds;
+        rc = terra_amd_accumulate_moments_device ( h, d_results, d_moments, fb_w, fb_h, x, y, w, hgt, stream );
+        if ( !rc ) rc = terra_amd_tile_error_device ( d_results, d_moments, fb_w, fb_h, x, y, w, hgt, tile, d_err, stream );
+        if ( !rc ) {
+            hipError_t e = hipMemcpyAsync ( err.data(), d_err, tiles * sizeof ( float ), hipMemcpyDeviceToHost, ( hipStream_t ) stream );
+            if ( e == hipSuccess ) e = hipStreamSynchronize ( ( hipStream_t ) stream );
+            if ( e != hipSuccess ) rc = fail ( kTerraAmdErrLaunch, "adaptive error readback: %s", hipGetErrorString ( e ) );
+        }
+    }
+    if ( rc ) { ( void ) hipStreamSynchronize ( ( hipStream_t ) stream ); return rc; }          // (the scratch is freed on return: nothing may still read it)
+    for ( size_t t = 0; t < tiles; ++t ) {
+        if ( err[t] <= target ) ++rep.tiles_converged;
+        if ( std::isfinite ( err[t] ) && err[t] > rep.max_error ) rep.max_error = err[t];
+    }
+    rep.hit_max_batches = rep.tiles_converged < rep.tiles ? 1 : 0;
+    if ( report ) *report = rep;
+    return 0;
+}
+extern "C" int terra_amd_render_adaptive_masked ( const TerraCamera* cam, HTerraScene h, TerraFramebuffer* fb, TerraAmdMoments* moments, TerraAmdAovResult* aov, size_t x, size_t y, size_t w, size_t hgt,
+                                                  const TerraAmdAdaptiveOptions* options, TerraAmdAdaptiveReport* report ) {
+    Scene* s = S ( h );
+    if ( !fb || !fb->results || !fb->pixels || !moments ) return fail ( kTerraAmdErrBadArgument, "null framebuffer or moments buffer" );
+    if ( int rc = frame_check ( s, "adaptive", fb->width, fb->height, x, y, w, hgt ) ) return rc;
+    HIP_TRY ( hipSetDevice ( primary ( s ).device ), kTerraAmdErrNoDevice );
+    const size_t n = fb->width * fb->height;
+    FrameCopy c;
+    hipError_t e = c.up ( 0, fb->pixels, n * 12 );
+    if ( e == hipSuccess ) e = c.up ( 1, fb->results, n * 16 );
+    if ( e == hipSuccess ) e = c.up ( 2, moments, n * 32 );
+    if ( e == hipSuccess && aov ) e = c.up ( 3, aov, n * 48 );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "adaptive upload: %s", hipGetErrorString ( e ) );
+    if ( int rc = terra_amd_render_adaptive_masked_device ( cam, h, c.d[0], c.d[1], c.d[2], aov ? c.d[3] : nullptr, fb->width, fb->height, x, y, w, hgt, options, report, nullptr ) ) return rc;
     e = c.down ( 0, fb->pixels, n * 12 );
     if ( e == hipSuccess ) e = c.down ( 1, fb->results, n * 16 );
     if ( e == hipSuccess ) e = c.down ( 2, moments, n * 32 );

@@ -90,3 +90,22 @@ hipError_t terra_launch_tile_error ( const void* moments, uint32_t fb_w, uint32_
     hipLaunchKernelGGL ( terra_tile_error, dim3 ( tiles_x * tiles_y ), dim3 ( 256 ), 0, stream, reinterpret_cast<const float4*> ( moments ), fb_w, x, y, w, h, tile, tiles_x, errors );
     return hipGetLastError();
 }
+
+// ---- mask from tile errors (include/terra_amd.h "Masked rendering") ----------------------------------------------------------------
+// One thread per 16x16 block of the w x h rectangle, row-major: the block belongs to tile (16 bx / tile, 16 by / tile), tiles numbered as terra_tile_error numbers
+// them, and is active if `all` or its tile's error exceeds the target -- the adaptive driver's own comparison, so +INFINITY is active, a NaN and equality are not.
+__global__ __launch_bounds__ ( 256 ) void terra_error_mask ( const float* errors, uint32_t blocks_x, uint32_t blocks_y, uint32_t tile, uint32_t tiles_x, float target, uint32_t all, uint32_t* mask ) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if ( i >= blocks_x * blocks_y ) return;
+    const uint32_t by = i / blocks_x, bx = i - by * blocks_x;
+    const float e = errors[ ( size_t ) ( ( by * 16u ) / tile ) * tiles_x + ( bx * 16u ) / tile];
+    mask[i] = ( all || e > target ) ? 1u : 0u;
+}
+hipError_t terra_launch_error_mask ( const float* errors, uint32_t w, uint32_t h, uint32_t tile, float target, int all, uint32_t* mask, hipStream_t stream ) {
+    if ( w == 0 || h == 0 ) return hipSuccess;
+    if ( tile == 0 || !errors || !mask ) return hipErrorInvalidValue;
+    const uint32_t blocks_x = ( w + 15u ) / 16u, blocks_y = ( h + 15u ) / 16u, tiles_x = ( w + tile - 1 ) / tile;
+    if ( ( uint64_t ) blocks_x * blocks_y >= ( 1ull << 32 ) ) return hipErrorInvalidValue;
+    hipLaunchKernelGGL ( terra_error_mask, dim3 ( ( blocks_x * blocks_y + 255u ) / 256u ), dim3 ( 256 ), 0, stream, errors, blocks_x, blocks_y, tile, tiles_x, target, all ? 1u : 0u, mask );
+    return hipGetLastError();
+}

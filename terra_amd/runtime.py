@@ -145,6 +145,7 @@ _EXTRA = {
     "terra_amd_reproject": (C.c_int, [C.c_void_p, _CAM, _CAM, C.POINTER(api.TerraFramebuffer)] + [C.c_void_p] * 5 + [_SZ] * 4 + [C.POINTER(api.TerraAmdTemporalOptions)]),
     **api.RAY_QUERY_SIGNATURES,
     **api.RAY_SOURCE_SIGNATURES,
+    **api.MASKED_SIGNATURES,
     **api.LENS_SIGNATURES,
     **api.POINT_SIGNATURES,
     **api.BAKE_SIGNATURES,
@@ -377,14 +378,50 @@ def denoise_variance_device(lib, scene, fb: DeviceFramebuffer, aov: DeviceAov, m
 
 
 def render_adaptive_device(lib, cam, scene, fb: DeviceFramebuffer, moments: DeviceMoments, aov: Optional[DeviceAov] = None, rect: Optional[Tuple[int, int, int, int]] = None,
-                           tile: int = 0, min_batches: int = 0, max_batches: int = 0, target_error: float = 0.0, stream=None) -> dict:
-    """terra_amd_render_adaptive_device (synchronous); returns the report as a dict"""
+                           tile: int = 0, min_batches: int = 0, max_batches: int = 0, target_error: float = 0.0, stream=None, masked: bool = False) -> dict:
+    """terra_amd_render_adaptive_device (synchronous); returns the report as a dict. masked: terra_amd_render_adaptive_masked_device -- one masked launch per round
+    in place of one call per active tile"""
     x, y, w, h = rect if rect else (0, 0, fb.width, fb.height)
     opt = api.TerraAmdAdaptiveOptions(tile, min_batches, max_batches, target_error, 0)
     rep = api.TerraAmdAdaptiveReport()
-    check(lib.render_adaptive_device(C.byref(cam), scene, fb.pixels.data_ptr(), fb.results.data_ptr(), moments.data.data_ptr(), aov.data.data_ptr() if aov is not None else None,
-                                     fb.width, fb.height, x, y, w, h, C.byref(opt), C.byref(rep), stream), "terra_amd_render_adaptive_device")
+    fn, what = (lib.render_adaptive_masked_device, "terra_amd_render_adaptive_masked_device") if masked else (lib.render_adaptive_device, "terra_amd_render_adaptive_device")
+    check(fn(C.byref(cam), scene, fb.pixels.data_ptr(), fb.results.data_ptr(), moments.data.data_ptr(), aov.data.data_ptr() if aov is not None else None,
+             fb.width, fb.height, x, y, w, h, C.byref(opt), C.byref(rep), stream), what)
     return rep.as_dict()
+
+
+def mask_shape(w: int, h: int) -> Tuple[int, int]:
+    """(rows, columns) of the mask of a w x h rectangle: one word per 16 x 16 block (include/terra_amd.h "Masked rendering")"""
+    return -(-h // 16), -(-w // 16)
+
+
+def render_masked_device(lib, cam, scene, fb: DeviceFramebuffer, mask, rect: Optional[Tuple[int, int, int, int]] = None, rand_calls=None, stream=None):
+    """terra_amd_render_masked_device; mask: an int32 / uint32 tensor of mask_shape(w, h) words on the framebuffer's device, non-zero = the block is rendered"""
+    x, y, w, h = rect if rect else (0, 0, fb.width, fb.height)
+    rows, cols = mask_shape(w, h)
+    if mask.numel() != rows * cols or mask.element_size() != 4:
+        raise TerraAmdError(f"mask of {mask.numel()} x {mask.element_size()}-byte words for a {w} x {h} rectangle: {rows * cols} 4-byte words")
+    check(lib.render_masked_device(C.byref(cam), scene, fb.pixels.data_ptr(), fb.results.data_ptr(), fb.width, fb.height, x, y, w, h, mask.data_ptr(),
+                                   rand_calls.data_ptr() if rand_calls is not None else None, stream), "terra_amd_render_masked_device")
+
+
+def render_aov_masked_device(lib, cam, scene, aov: DeviceAov, mask, rect: Optional[Tuple[int, int, int, int]] = None, stream=None):
+    """terra_amd_render_aov_masked_device; mask as render_masked_device takes it"""
+    x, y, w, h = rect if rect else (0, 0, aov.width, aov.height)
+    rows, cols = mask_shape(w, h)
+    if mask.numel() != rows * cols or mask.element_size() != 4:
+        raise TerraAmdError(f"mask of {mask.numel()} x {mask.element_size()}-byte words for a {w} x {h} rectangle: {rows * cols} 4-byte words")
+    check(lib.render_aov_masked_device(C.byref(cam), scene, aov.data.data_ptr(), aov.width, aov.height, x, y, w, h, mask.data_ptr(), stream), "terra_amd_render_aov_masked_device")
+
+
+def error_mask_device(lib, errors, w: int, h: int, tile: int = 0, target_error: float = 0.05, all: bool = False, stream=None):
+    """terra_amd_error_mask_device: the int32 mask tensor, mask_shape(w, h), of the blocks whose tile's error (errors: tile_error_device's tensor for the same w, h,
+    tile) exceeds target_error -- every block where all"""
+    import torch
+    rows, cols = mask_shape(w, h)
+    out = torch.zeros((rows, cols), dtype=torch.int32, device=errors.device)
+    check(lib.error_mask_device(errors.data_ptr(), w, h, tile, target_error, 1 if all else 0, out.data_ptr(), stream), "terra_amd_error_mask_device")
+    return out
 
 
 class DeviceHistory:

@@ -6,9 +6,9 @@ hipError_t terra_launch_render_rays ( const DevRenderParams&, const void*, hipSt
 hipError_t terra_launch_render_lens ( const DevRenderParams&, const DevLens&, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_launch_render_points ( const DevRenderParams&, const void*, const DevPointSampling&, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_launch_job_streams ( const DevRenderParams&, hipStream_t ) { return hipErrorNoDevice; }
-hipError_t terra_launch_block_order ( const DevRenderParams&, uint32_t*, hipStream_t ) { return hipErrorNoDevice; }
+hipError_t terra_launch_block_order ( const DevRenderParams&, uint32_t*, hipStream_t, const DevLaunchMask*, bool, bool ) { return hipErrorNoDevice; }
 hipError_t terra_fill_sincos24 ( float2*, hipStream_t ) { return hipErrorNoDevice; }
-hipError_t terra_launch_resolve ( const DevRenderParams&, hipStream_t ) { return hipErrorNoDevice; }
+hipError_t terra_launch_resolve ( const DevRenderParams&, hipStream_t, const uint32_t* ) { return hipErrorNoDevice; }
 hipError_t terra_launch_tiles ( bool, float*, void*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, float*, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_unit_pcg ( const uint32_t*, int, int, float* ) { return hipErrorNoDevice; }
 hipError_t terra_unit_stream_keys ( uint64_t, const uint64_t*, const uint64_t*, int, uint64_t* ) { return hipErrorNoDevice; }
@@ -32,7 +32,7 @@ hipError_t terra_unit_distribution_1d ( const float*, uint32_t, float*, float*, 
 hipError_t terra_unit_distribution_2d ( const float*, uint32_t, uint32_t, float*, float*, float*, uint32_t*, const float*, int, float*, float* ) { return hipErrorNoDevice; }
 hipError_t terra_unit_distribution_2d_pdf ( const float*, uint32_t, uint32_t, float*, float*, float*, uint32_t*, const float*, int, float* ) { return hipErrorNoDevice; }
 hipError_t terra_build_fast_tree_device ( const DevTri*, const uint32_t*, uint32_t, float, DevNode*, DevTri*, uint32_t*, int*, hipStream_t ) { return hipErrorNoDevice; }
-hipError_t terra_launch_aov ( DevRenderParams, void*, hipStream_t ) { return hipErrorNoDevice; }
+hipError_t terra_launch_aov ( DevRenderParams, void*, hipStream_t, const uint32_t* ) { return hipErrorNoDevice; }
 hipError_t terra_launch_aov_rays ( DevRenderParams, const void*, void*, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_launch_aov_lens ( DevRenderParams, const DevLens&, void*, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_unit_lens_rays ( const DevRenderParams&, const DevLens&, int, const uint32_t*, const float*, float* ) { return hipErrorNoDevice; }
@@ -41,6 +41,7 @@ hipError_t terra_unit_point_rays ( const DevPointSampling&, int, const float*, c
 hipError_t terra_launch_denoise ( const void*, const void*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, int, float, int, float, float*, float*, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_launch_moments_accumulate ( const void*, void*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_launch_tile_error ( const void*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, float*, hipStream_t ) { return hipErrorNoDevice; }
+hipError_t terra_launch_error_mask ( const float*, uint32_t, uint32_t, uint32_t, float, int, uint32_t*, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_launch_denoise_variance ( const void*, const void*, const void*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, int, float, int, float, float*, float*, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_launch_temporal_reproject ( const DevTemporalParams&, const void*, const void*, const void*, void*, void*, void*, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_launch_query ( DevQueryParams, const void*, size_t, void*, bool, hipStream_t ) { return hipErrorNoDevice; }
