@@ -51,10 +51,17 @@ int  terra_amd_init ( void );
 /* Process-wide switches of the commit path (all optional):
    terra_amd_set_commit_timing(1)  prints the phases of terra_scene_commit() on stderr;
    terra_amd_set_build_threads(n)  host threads of the fast tree's builder (0 = as many as the process may use, at most 16; the tree does not depend on it);
-   terra_amd_set_azimuth_table(0)  scenes committed from now on compute the samplers' sin / cos instead of reading the 128 MB per-device table (same bits). */
+   terra_amd_set_azimuth_table(1)  scenes committed from now on read the samplers' azimuth sin / cos from a table of all 2^24 stream variates instead of computing
+                                   it (same bits; LDS-resident launches only). Off by default: computing is faster on every measured workload
+                                   (profiles/azimuth/ab.md). The table costs 128 MB per device and a ~1 ms fill; it is allocated by the first commit on a
+                                   device made while the switch is on, and kept for the life of the process. (0) switches back. */
 void terra_amd_set_commit_timing ( int on );
 int  terra_amd_set_build_threads ( int threads );
 void terra_amd_set_azimuth_table ( int on );
+int  terra_amd_get_azimuth_table ( void );          /* the switch as it stands: 1 = scenes committed now read the table */
+/* 1 if the most recent render call of this scene handed its kernel the azimuth table, 0 if that kernel computed: the scene was committed with the switch off,
+   the launch is not LDS-resident, or the table could not be allocated (the commit then falls back to computing without an error). */
+int  terra_amd_azimuth_table_info ( HTerraScene scene );
 
 /* Device selection for subsequent commits/renders issued by this thread's
    scenes: one device (one process per GPU is bench.py's layout, DESIGN.md "Multi-GPU"), or a set of devices driven from this process (below). */
@@ -1140,6 +1147,10 @@ int terra_amd_unit_distribution_2d ( const float* f, size_t nx, size_t ny, const
    probability the same distribution assigns to the bucket each point lies in ((row, column) = truncated (v ny, u nx); 0 for an empty row) -- bit for bit
    the pdf that sampling reports for that bucket */
 int terra_amd_unit_distribution_2d_pdf ( const float* f, size_t nx, size_t ny, const float* xy2, int m, float* pdf );
+/* The samplers' computed azimuth against the azimuth table on the device, for all 2^24 stream variates: fills a table as a commit would, writes the computed
+   entries into a second buffer of the same size (128 MB each, freed before the call returns) and sets *mismatches to the number of entries that differ in
+   any bit -- 0 in a correct build */
+int terra_amd_unit_azimuth24 ( uint32_t* mismatches );
 /* terra_texture_sample (src/Terra.c:410-466) on the device at uv2[n][2], in texel units: out3[n][3]. The texture is uploaded the way terra_scene_commit
    uploads a scene's textures. Where the reference is undefined (components below 3 at the end of the data, 4 components, mirror addressing at a tile's
    first column or row, coordinates outside (-1, 2^32)) the result is this library's rule, which terra_texture_sample on the host follows too */

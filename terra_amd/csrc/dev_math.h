@@ -86,6 +86,47 @@ TDM_FN void tdm_sincosf_pair ( float y, float& s, float& c ) {
 TDM_FN float tdm_sinf ( float y ) { return tdm_sincosf ( y, 0 ); }
 TDM_FN float tdm_cosf ( float y ) { return tdm_sincosf ( y, 1 ); }
 
+// The samplers' azimuth of a stream-B variate (rng.h: e = k * 2^-24, k < 2^24): bit-identical to
+// tdm_sincosf_pair ( TDM_AZIMUTH_SCALE * trng_b_from_bits ( k ), sn, cs ) for every k, in ONE arm (tests/azimuth24_check.cpp holds both outputs and the quadrant
+// against that function for all 2^24 arguments). Each step is exact by argument:
+// * y is made by the same two float operations.
+// * The quadrant n of the reduction is monotone in y, hence in k: it is the number of the four thresholds below -- the first k at which the reference's
+//   ( ( int32_t ) ( y * 2^24 * 2/pi ) + 2^23 ) >> 24 steps -- that k has reached. (They are not ( 2 j - 1 ) * 2^21: the scale is twice the reference's terra_PI,
+//   which is not pi.) A lane of the unreduced arm (y < 0.75) has n = 0, and x - 0.0 * C = x, so that arm IS the reduced arm with n = 0.
+// * One sine and one cosine polynomial of the same (x, x^2), operation for operation those of tdm_sincos_poly; n's parity says which is sn and which is cs.
+// * The signs are flipped on the results: every operation of the sine polynomial is a product or a sum all of whose terms change sign with x, and every
+//   coefficient of the cosine polynomial is multiplied by -1.0 where the two-arm form flips; round-to-nearest is symmetric in sign, so either negates the
+//   double result, and its conversion to float, exactly.
+// * Only y < 2^-12 (k < 652) keeps its early result.
+#define TDM_AZIMUTH_SCALE ( 2 * 3.1416926535f )          // 2 * terra_PI (shading_device.h TERRA_PI_F)
+TDM_FN uint32_t tdm_azimuth24_quadrant ( uint32_t k ) {
+    return ( uint32_t ) ( k >= 0x1fffbeu ) + ( uint32_t ) ( k >= 0x5fff38u ) + ( uint32_t ) ( k >= 0x9ffeb3u ) + ( uint32_t ) ( k >= 0xdffe2eu );
+}
+TDM_FN void tdm_azimuth24 ( uint32_t k, float& sn, float& cs ) {
+    const float y = TDM_AZIMUTH_SCALE * ( ( float ) k * 0x1p-24f );
+    const uint32_t n = tdm_azimuth24_quadrant ( k );
+    const double x = ( double ) y - ( double ) ( int32_t ) n * 0x1.921FB54442D18p0;
+    const double x2 = x * x;
+    const double S1 = -0x1.555545995a603p-3, S2 = 0x1.1107605230bc4p-7, S3 = -0x1.994eb3774cf24p-13;
+    const double x3 = x * x2;
+    const double t = S2 + x2 * S3;
+    const double x7 = x3 * x2;
+    const double s = x + x3 * S1;
+    const float sine = ( float ) ( s + x7 * t );
+    const double C0 = 0x1p0, C1 = -0x1.ffffffd0c621cp-2, C2 = 0x1.55553e1068f19p-5, C3 = -0x1.6c087e89a359dp-10, C4 = 0x1.99343027bf8c3p-16;
+    const double x4 = x2 * x2;
+    const double t2 = C3 + x2 * C4;
+    const double t1 = C0 + x2 * C1;
+    const double x6 = x4 * x2;
+    const double c = t1 + x4 * C2;
+    const float cosine = ( float ) ( c + x6 * t2 );
+    const bool odd = ( n & 1u ) != 0;
+    // n mod 4 = 0: (S, C), 1: (C, -S), 2: (-S, -C), 3: (-C, S)
+    sn = tdm_float ( tdm_bits ( odd ? cosine : sine ) ^ ( ( n & 2u ) << 30 ) );
+    cs = tdm_float ( tdm_bits ( odd ? sine : cosine ) ^ ( ( ( n + 1u ) & 2u ) << 30 ) );
+    if ( k < 652u ) { sn = y; cs = 1.0f; }
+}
+
 TDM_FN uint64_t tdm_bits64 ( double f ) { return __builtin_bit_cast ( uint64_t, f ); }
 TDM_FN double   tdm_double ( uint64_t u ) { return __builtin_bit_cast ( double, u ); }
 

@@ -190,8 +190,8 @@ TD MisPending mis_prepare ( const Tracer& T, Surface& sf, V3 p, V3 wo, V3 throug
     const DevScene& sc = T.sc;
     V3 Lo = v3 ( 0, 0, 0 );
     if ( bounce == 0 && dot ( wo, sf.normal ) > 0 ) Lo = Lo + sf.emissive;
-    float e1 = randf ( rb, c, COUNT ), e2 = randf ( rb, c, COUNT ), e3 = randf ( rb, c, COUNT );
-    V3 bsdf_dir = bsdf_sample<KINDS> ( sf, e1, e2, e3, wo, azimuth_fetch ( sc.sincos24, e2 ) );
+    const float e1 = randf ( rb, c, COUNT ); const uint32_t k2 = randf_bits ( rb, c, COUNT ); const float e2 = trng_b_from_bits ( k2 ), e3 = randf ( rb, c, COUNT );
+    V3 bsdf_dir = bsdf_sample<KINDS> ( sf, e1, e2, e3, wo, azimuth_fetch_index ( azimuth_table<MODE> ( sc ), k2 ) );
     LightSample ls = draw_light_sample<COUNT, MODE> ( sc, rb, c, &T );
     MisPending m;
     m.a_hid = Lo; m.a_vis = Lo; m.expected = ls.tri; m.p = p; m.light_object = ls.light_object; m.t_before = throughput;
@@ -247,8 +247,8 @@ TD V3 integrate_mis ( const Tracer& T, Surface& sf, V3 p, V3 wo, V3 throughput, 
     V3 Lo = v3 ( 0, 0, 0 );
     if ( DEBUG_WEIGHTS ) { if ( bounce != 0 ) return Lo; }
     else if ( bounce == 0 && dot ( wo, sf.normal ) > 0 ) Lo = Lo + sf.emissive;
-    float e1 = randf ( rb, c, COUNT ), e2 = randf ( rb, c, COUNT ), e3 = randf ( rb, c, COUNT );
-    V3 bsdf_dir = bsdf_sample<KINDS> ( sf, e1, e2, e3, wo, azimuth_fetch ( sc.sincos24, e2 ) );
+    const float e1 = randf ( rb, c, COUNT ); const uint32_t k2 = randf_bits ( rb, c, COUNT ); const float e2 = trng_b_from_bits ( k2 ), e3 = randf ( rb, c, COUNT );
+    V3 bsdf_dir = bsdf_sample<KINDS> ( sf, e1, e2, e3, wo, azimuth_fetch_index ( azimuth_table<MODE> ( sc ), k2 ) );
     LightSample ls = draw_light_sample<COUNT, MODE> ( sc, rb, c, &T );
     {
         V3 p_to_light = ls.pos - p;
@@ -366,24 +366,16 @@ TD V3 integrate ( const Tracer& T, const Ray& ray, Surface& sf, V3 p, V3 wo, V3 
 // The four variates are consecutive draws of stream B whatever the surface is, so they can be drawn -- and the azimuth table entry requested -- BEFORE the
 // surface is set up (path_draw), which hides the load behind terra_surface_init's work; integrators that draw from the stream themselves (Direct, MIS) call
 // path_draw after their own draws, as the reference's order demands.
-// INDEX (the launches of ray_start_masks_for): the table is fetched by the variate's 24 bits
-template <int COUNT, bool INDEX>
+// The azimuth is the second variate's: e1 = k * 2^-24 exactly (k < 2^24 is a float, and so is the product), and the integer is still here, so the azimuth takes it
+template <int COUNT>
 TD PathDraws path_draw ( const float2* sincos24, Pcg32& rb, Counters& c ) {
     PathDraws d;
-    if constexpr ( INDEX ) {
-        // e1 = k * 2^-24 exactly (k < 2^24 is a float, and so is the product): the float form of azimuth_fetch would multiply it back to k, find it in range and
-        // whole, and read entry k -- the integer is still here, so the fetch takes it
-        d.e0 = randf ( rb, c, COUNT );
-        const uint32_t k1 = randf_bits ( rb, c, COUNT );
-        d.e1 = trng_b_from_bits ( k1 );
-        d.e2 = randf ( rb, c, COUNT );
-        d.az = azimuth_fetch_index ( sincos24, k1 );
-        d.e3 = randf ( rb, c, COUNT );
-    } else {
-        d.e0 = randf ( rb, c, COUNT ); d.e1 = randf ( rb, c, COUNT ); d.e2 = randf ( rb, c, COUNT );
-        d.az = azimuth_fetch ( sincos24, d.e1 );
-        d.e3 = randf ( rb, c, COUNT );
-    }
+    d.e0 = randf ( rb, c, COUNT );
+    const uint32_t k1 = randf_bits ( rb, c, COUNT );
+    d.e1 = trng_b_from_bits ( k1 );
+    d.e2 = randf ( rb, c, COUNT );
+    d.az = azimuth_fetch_index ( sincos24, k1 );
+    d.e3 = randf ( rb, c, COUNT );
     return d;
 }
 template <int KINDS>

@@ -116,6 +116,8 @@ hipError_t terra_launch_sh_project ( const void* results, const void* rays, uint
 hipError_t terra_launch_sh_irradiance ( const void* sh, uint32_t probes, const DevProbeGrid& grid, const void* points, const int* index, uint32_t n, void* out, hipStream_t stream );
 
 hipError_t terra_fill_sincos24 ( float2* table, hipStream_t stream );    // DevScene::sincos24: 2^24 entries (128 MB), device pointer
+// table, computed: 2^24 entries each; *mismatches (zeroed by the caller) += the entries of table that tdm_azimuth24 does not reproduce bit for bit
+hipError_t terra_unit_azimuth24 ( const float2* table, float2* computed, uint32_t* mismatches );
 
 // unit-level launchers: all pointers are DEVICE pointers, n items, synchronous semantics left to the caller
 hipError_t terra_unit_pcg ( const uint32_t* seeds, int nseeds, int n, float* out );

@@ -741,7 +741,7 @@ __global__ __launch_bounds__ ( 256, terra_waves ( INTEGRATOR, KINDS, MODE ) ) vo
                 if ( have_ray ) {
                     if ( lt.best.tri != 0xffffffffu ) {
                         Surface sf;
-                        PathDraws pd = path_draw<COUNT> ( T.sc.sincos24, rs.b, c );       // (these integrators draw nothing themselves: the variates, and the table load, come first)
+                        PathDraws pd = path_draw<COUNT> ( azimuth_table<MODE> ( T.sc ), rs.b, c );       // (these integrators draw nothing themselves: the variates, and the table load, come first)
                         if constexpr ( ( KINDS & TERRA_KIND_SAMPLER ) != 0 ) path_apply_sampler ( pd, sp, bounce );
                         V3 point = shade_surface<COUNT, MODE, KINDS> ( T, ray, lt.best, sf, c );
                         V3 wo = neg ( ray.d ), wi;
@@ -822,7 +822,7 @@ __global__ __launch_bounds__ ( 256, terra_waves ( INTEGRATOR, KINDS, MODE ) ) vo
                 if constexpr ( SPLIT_DIRECT ) {
                     Ray shadow_ray;
                     const DirectPending pend = direct_prepare<COUNT, KINDS, MODE> ( T, sf, h.point, wo, throughput, bounce, rs.b, c, shadow_ray );
-                    pd = path_draw<COUNT, ray_start_masks_for ( COUNT, MODE, KINDS )> ( T.sc.sincos24, rs.b, c );
+                    pd = path_draw<COUNT> ( azimuth_table<MODE> ( T.sc ), rs.b, c );
                     end = !path_continue<KINDS> ( sf, wo, throughput, bounce, p.bounces, pd, wi );
                     if ( !end ) { ro = surface_origin ( sf, h.point ); rd = wi; }
                     const uint32_t tri = scene_raycast_triangle<COUNT, MODE, ray_start_masks_for ( COUNT, MODE, KINDS )> ( T, shadow_ray, c, pend.expected );
@@ -842,7 +842,7 @@ __global__ __launch_bounds__ ( 256, terra_waves ( INTEGRATOR, KINDS, MODE ) ) vo
                     lo_add ( mis_finish_b<MODE> ( T, pend, lo_a, hb.hit, hb.object, hb.tri, hb.point, lsf, b_d ) );
                 } else {
                 lo_add ( integrate<INTEGRATOR, COUNT, MODE, KINDS> ( T, ray, sf, h.point, wo, throughput, bounce, rs.b, c ) );
-                if ( !pre_draw ) pd = path_draw<COUNT, ray_start_masks_for ( COUNT, MODE, KINDS )> ( T.sc.sincos24, rs.b, c );
+                if ( !pre_draw ) pd = path_draw<COUNT> ( azimuth_table<MODE> ( T.sc ), rs.b, c );
                 if constexpr ( ( KINDS & TERRA_KIND_SAMPLER ) != 0 ) path_apply_sampler ( pd, sp, bounce );
                 end = !path_continue<KINDS> ( sf, wo, throughput, bounce, p.bounces, pd, wi );
                 if ( !end ) { ro = surface_origin ( sf, h.point ); rd = wi; }      // surface_ray ( sf, h.point, wi ): its make_ray is the one at the top of this block

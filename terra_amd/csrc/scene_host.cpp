@@ -365,6 +365,7 @@ struct Scene {
     int tree_builder = 0;               // terra_amd_set_tree_builder: 0 = host (binned SAH), 1 = device (LBVH, tree_build_device.hip)
     TreeChoice tree;                    // what the last commit decided
     std::atomic<int> last_call { 0 };   // TerraAmdTraversalInfo::last_call: the traversal the most recent render call actually ran
+    std::atomic<int> last_azimuth_table { 0 };   // terra_amd_azimuth_table_info: whether that call's kernel was handed the azimuth table
     uint32_t sample_split = 1;          // terra_amd_set_sample_split: chunks a call's samples are cut into (lanes per pixel)
     bool env_lighting = false;          // terra_amd_set_environment_lighting: escaping rays add throughput * environment
     bool work_counters = false;         // terra_amd_set_work_counters: the render kernels count rays / nodes / tests / hits / draws (instrumentation, off by default)
@@ -815,10 +816,13 @@ static void build_reach_tables ( const std::vector<DevNode>& nodes, const std::v
     }
 }
 
-// DevScene::sincos24, one table per device for the life of the process (128 MB of its 288 GB; filled by tdm_sincosf_pair itself, ~1 ms). nullptr when it cannot
-// be had (or terra_amd_set_azimuth_table turned it off) -- the kernels then compute.
-static std::atomic<bool> g_azimuth_table { true };
+// DevScene::sincos24: off by default -- the kernels compute the azimuth from the variate's 24 bits (dev_math.h tdm_azimuth24), which beats the table on every
+// workload (profiles/azimuth/ab.md). With terra_amd_set_azimuth_table ( 1 ) the first commit on a device allocates that device's table, for the life of the
+// process (128 MB of its 288 GB; filled by tdm_sincosf_pair itself, ~1 ms); nullptr when it cannot be had -- the kernels then compute, same bits.
+static std::atomic<bool> g_azimuth_table { false };
 extern "C" void terra_amd_set_azimuth_table ( int on ) { g_azimuth_table.store ( on != 0, std::memory_order_relaxed ); }      // (takes effect at the next commit)
+extern "C" int terra_amd_get_azimuth_table ( void ) { return g_azimuth_table.load ( std::memory_order_relaxed ) ? 1 : 0; }
+extern "C" int terra_amd_azimuth_table_info ( HTerraScene h ) { return S ( h )->last_azimuth_table.load ( std::memory_order_relaxed ); }
 static const float2* sincos_table_of ( int device ) {
     static std::mutex lock; static const float2* tables[64]; static bool tried[64];
     if ( device < 0 || device >= 64 || !g_azimuth_table.load ( std::memory_order_relaxed ) ) return nullptr;
@@ -1611,10 +1615,11 @@ static int fill_params ( Scene* s, const Scene::Replica& r, const TerraCamera* c
     if ( s->leaf_pair_form && r.d_blob && !s->leaf_pairs.empty() && p.lds_mode == 1 && p.leaf_rank ) p.leaf_pairs = ( uint32_t ) ( s->blob.sec[kSecLeafPairs].offset - s->blob.sec[kSecTris].offset );      // (both in the blob; scenes of at most 32 triangles: a few KB apart)
     // nearest first: a pair launch that also runs the flat test, of a table in which box k holds entry k; the switch rides in the distance's lowest bit (sections are 16-byte aligned)
     if ( p.leaf_pairs && ! ( p.leaf_pairs & 3u ) && p.n_leaf_boxes && s->leaf_nearest_first && s->pair_per_box ) p.leaf_pairs |= TERRA_LEAF_PAIRS_NEAREST;
-    // the azimuth table pays where VALU issue binds (LDS-resident scenes: Cornell Simple 65.8 -> 64.2 ms, Direct 145.2 -> 142.5); the kernels that wait on memory anyway
-    // lose by one more dependent load per shaded hit (sphere scene 395 -> 419 ms, hall 282 -> 284; profiles/r03_measurements/ab_sincos_table.log;
-    // fast-tree launches alone: hall 218.9 -> 219.6 ms, sphere scene 318.6 -> 321.1, profiles/r04_measurements/ab_fast_node_formats.log)
+    // the azimuth table, where a client asked for it, is read by LDS-resident launches only: the kernels that wait on memory anyway lose by one more dependent load per
+    // shaded hit (sphere scene 395 -> 419 ms, hall 282 -> 284; profiles/r03_measurements/ab_sincos_table.log; fast-tree launches alone: hall 218.9 -> 219.6 ms, sphere
+    // scene 318.6 -> 321.1, profiles/r04_measurements/ab_fast_node_formats.log). Against the single-arm computation it loses there too (profiles/azimuth/ab.md).
     if ( p.lds_mode != 1 ) p.scene.sincos24 = nullptr;
+    s->last_azimuth_table.store ( p.scene.sincos24 ? 1 : 0, std::memory_order_relaxed );
     // what this call runs (TerraAmdTraversalInfo::last_call): the commit-time decision can be overridden per call by the camera position
     s->last_call.store ( p.lds_mode == 2 ? ( r.dev.reach ? kTerraAmdCallFastTreeReach : kTerraAmdCallFastTree ) : ( p.leaf_cull ? kTerraAmdCallLeafCull : kTerraAmdCallReplica ), std::memory_order_relaxed );
     p.bsdf_kinds = s->bsdf_kinds;
@@ -3286,6 +3291,25 @@ extern "C" int terra_amd_unit_distribution_2d_pdf ( const float* f, size_t nx, s
     auto dc = u.out ( cdf.data(), nx * ny ); auto di = u.out ( integrals.data(), ny + 1 ); auto dmc = u.out ( mcdf.data(), ny ); auto dm = u.out ( mono.data(), ny + 1 );
     auto dp = u.out ( pdf, ( size_t ) m );
     return u.finish ( u.ok ? terra_unit_distribution_2d_pdf ( df, ( uint32_t ) nx, ( uint32_t ) ny, dc, di, dmc, dm, dxy, m, dp ) : hipSuccess );
+}
+
+// ---- the computed azimuth (dev_math.h tdm_azimuth24) against the table (terra_fill_sincos24: tdm_sincosf_pair itself), all 2^24 arguments, on the device:
+// a table of its own and a second buffer of the same size for the computed entries; only the count comes back
+extern "C" int terra_amd_unit_azimuth24 ( uint32_t* mismatches ) {
+    if ( need_device() ) return kTerraAmdErrNoDevice;
+    if ( !mismatches ) return fail ( kTerraAmdErrBadArgument, "unit azimuth: null count" );
+    float2* table = nullptr; float2* computed = nullptr; uint32_t* count = nullptr;
+    hipError_t e = hipMalloc ( ( void** ) &table, sizeof ( float2 ) << 24 );
+    if ( e == hipSuccess ) e = hipMalloc ( ( void** ) &computed, sizeof ( float2 ) << 24 );
+    if ( e == hipSuccess ) e = hipMalloc ( ( void** ) &count, sizeof ( uint32_t ) );
+    if ( e == hipSuccess ) e = hipMemset ( count, 0, sizeof ( uint32_t ) );
+    if ( e == hipSuccess ) e = terra_fill_sincos24 ( table, nullptr );
+    if ( e == hipSuccess ) e = terra_unit_azimuth24 ( table, computed, count );
+    if ( e == hipSuccess ) e = hipDeviceSynchronize();
+    if ( e == hipSuccess ) e = hipMemcpy ( mismatches, count, sizeof ( uint32_t ), hipMemcpyDeviceToHost );
+    ( void ) hipFree ( table ); ( void ) hipFree ( computed ); ( void ) hipFree ( count );
+    if ( e != hipSuccess ) { ( void ) hipGetLastError(); return fail ( kTerraAmdErrLaunch, "unit azimuth: %s", hipGetErrorString ( e ) ); }
+    return 0;
 }
 
 // ---- the texture lookups (shading_device.h texture_sample, environment_eval's lat-long lookup) on one texture, which reaches the device the way a scene's

@@ -131,9 +131,12 @@ TD void surface_init ( const Tracer& T, uint32_t ti, V3 point, Surface& sf, uint
 
 struct RaycastResult { bool hit; uint32_t object, tri_in_object, tri; V3 point; };
 
-struct Azimuth { float sn, cs; bool have; };
+struct Azimuth { float sn, cs; uint32_t k; int kind; };
 struct PathDraws { float e0, e1, e2, e3; Azimuth az; };
-template <int COUNT, bool INDEX = false> TD PathDraws path_draw ( const float2* sincos24, Pcg32& rb, Counters& c );
+// the azimuth table a kernel of tree mode MODE may read: only LDS-resident launches are ever handed one (scene_host.cpp fill_params), so every other instance
+// is compiled without the load and its branch
+template <int MODE> TD const float2* azimuth_table ( const DevScene& sc ) { return MODE == 1 ? sc.sincos24 : nullptr; }
+template <int COUNT> TD PathDraws path_draw ( const float2* sincos24, Pcg32& rb, Counters& c );
 
 // guarded (the kernels of ray_start_masks_for): what make_ray_guarded found for this lane's ray
 // pre / rb (optional): a hit draws the path's four continuation variates (path_draw) BEFORE the surface is set up, so that the azimuth table load they issue
@@ -142,7 +145,7 @@ template <int COUNT, int MODE, int KINDS>
 TD RaycastResult scene_raycast ( const Tracer& T, const Ray& in, Surface& sf, Counters& c, PathDraws* pre = nullptr, Pcg32* rb = nullptr, bool guarded = false ) {
     Ray r = in;
     r.o = r.o + r.d * 0.001f;
-    constexpr bool MASKS = ray_start_masks_for ( COUNT, MODE, KINDS );          // (trace_geometry.h: the ray start by lane predicates, one range test, the azimuth by its integer)
+    constexpr bool MASKS = ray_start_masks_for ( COUNT, MODE, KINDS );          // (trace_geometry.h: the ray start by lane predicates, one range test)
     if ( COUNT ) ++c.rays;
     Closest best;
     if constexpr ( MASKS ) { V3 o_perm; const RayStateMasks st = ray_start_masks ( r, o_perm ); best = bvh_traverse_from<COUNT, MODE> ( T, r, st, o_perm, c, __all ( guarded ) != 0 ); }
@@ -155,7 +158,7 @@ TD RaycastResult scene_raycast ( const Tracer& T, const Ray& in, Surface& sf, Co
     res.point = res.hit ? r.o + r.d * best.depth : v3 ( FLT_MAX, FLT_MAX, FLT_MAX );
     if ( res.hit ) {
         uint32_t nattr;
-        if ( pre ) *pre = path_draw<COUNT, MASKS> ( T.sc.sincos24, *rb, c );
+        if ( pre ) *pre = path_draw<COUNT> ( azimuth_table<MODE> ( T.sc ), *rb, c );
         surface_init<MODE, KINDS> ( T, best.tri, res.point, sf, res.object, res.tri_in_object, nattr );
         if ( MODE >= 2 ) res.tri = T.sc.mats[res.object].first_tri + res.tri_in_object;      // back to the soup index (lights, areas)
         if ( COUNT ) ++c.hits;
@@ -229,28 +232,33 @@ TD Ray surface_ray ( const Surface& sf, V3 p, V3 d ) { return make_ray ( surface
 // -----------------------------------------------------------------------------
 
 // sin / cos of the azimuth 2 * terra_PI * e that the samplers make of one variate (src/TerraPresets.c:39-40). A stream-B variate is u24 * 2^-24
-// (rng.h), so over the render path this is a pure function of 24 bits: DevScene::sincos24 tabulates it -- every entry computed by tdm_sincosf_pair itself, at
-// library start-up (unit_kernels.hip terra_fill_sincos24) -- and one 8-byte load replaces ~100 double-precision instructions (the glibc algorithm restated in
-// dev_math.h). Any other argument (unit-level calls with arbitrary variates, a sampler-driven first bounce) takes the computation.
-TD Azimuth azimuth_none() { Azimuth a; a.sn = 0.f; a.cs = 1.f; a.have = false; return a; }
-// the table entry of variate e, if e is one of the 2^24 stream-B values (the load is issued here; the caller uses it as late as it can)
-TD Azimuth azimuth_fetch ( const float2* tab, float e ) {
-    Azimuth a = azimuth_none();
-    const float x = e * 16777216.f;
-    if ( tab && e >= 0.f && x < 16777216.f ) {
-        const uint32_t k = ( uint32_t ) x;
-        if ( ( float ) k == x ) { const float2 v = tab[k]; a.cs = v.x; a.sn = v.y; a.have = true; }
-    }
-    return a;
-}
-// the same for a variate whose 24 bits the caller still holds (path_draw): e = k * 2^-24 passes every test above and lands on entry k
+// (rng.h), so over the render path this is a pure function of 24 bits, and it is had in one of two ways, same bits either way:
+// * computed from the 24 bits by tdm_azimuth24 (dev_math.h: the glibc algorithm in one arm, the quadrant from the integer; ~45 instructions) -- the default;
+// * read from DevScene::sincos24, which tabulates it -- every entry computed by tdm_sincosf_pair itself, when the first scene that asks for the table is
+//   committed (unit_kernels.hip terra_fill_sincos24; terra_amd_set_azimuth_table) -- one 8-byte load of a uniformly random entry of 128 MB.
+// Any other argument (unit-level calls with arbitrary variates, a sampler-driven first bounce) takes tdm_sincosf_pair.
+// kind 0: nothing held (the sampler computes from its float); 1: (sn, cs) are the table's entry; 2: k holds the variate's 24 bits
+static_assert ( TDM_AZIMUTH_SCALE == 2 * TERRA_PI_F, "tdm_azimuth24's scale is the samplers' 2 * terra_PI" );
+TD Azimuth azimuth_none() { Azimuth a; a.sn = 0.f; a.cs = 1.f; a.k = 0u; a.kind = 0; return a; }
+// the variate whose 24 bits the caller holds (path_draw, the integrators' own draws): the table's load is issued here and the caller uses it as late as it can
 TD Azimuth azimuth_fetch_index ( const float2* tab, uint32_t k ) {
     Azimuth a = azimuth_none();
-    if ( tab ) { const float2 v = tab[k]; a.cs = v.x; a.sn = v.y; a.have = true; }
+    if ( tab ) { const float2 v = tab[k]; a.cs = v.x; a.sn = v.y; a.kind = 1; }
+    else { a.k = k; a.kind = 2; }
     return a;
 }
+// the same for a float: e is one of the 2^24 stream-B values exactly when e * 2^24 is a whole number below 2^24
+TD Azimuth azimuth_fetch ( const float2* tab, float e ) {
+    const float x = e * 16777216.f;
+    if ( e >= 0.f && x < 16777216.f ) {
+        const uint32_t k = ( uint32_t ) x;
+        if ( ( float ) k == x ) return azimuth_fetch_index ( tab, k );
+    }
+    return azimuth_none();
+}
 TD void azimuth_sincos ( const Azimuth& az, float e, float& sn, float& cs ) {
-    if ( az.have ) { sn = az.sn; cs = az.cs; }
+    if ( az.kind == 1 ) { sn = az.sn; cs = az.cs; }
+    else if ( az.kind == 2 ) tdm_azimuth24 ( az.k, sn, cs );
     else tdm_sincosf_pair ( 2 * TERRA_PI_F * e, sn, cs );
 }
 
@@ -390,7 +398,7 @@ TD V3 glass_eval ( const Surface& sf, V3 wi ) {
 // (bit k = DevBsdfKind k): a diffuse-only scene compiles to straight-line diffuse code, which is
 // what keeps the Simple kernel inside 96 VGPRs (5 waves/SIMD) without scratch.
 #define TERRA_KINDS_ALL 127
-// az: the azimuth of the SECOND variate (e2), if its table entry was fetched (azimuth_fetch) -- what the diffuse and GGX samplers and Phong's diffuse branch use
+// az: the azimuth of the SECOND variate (e2), as azimuth_fetch / azimuth_fetch_index hold it -- what the diffuse and GGX samplers and Phong's diffuse branch use
 template <int KINDS>
 TD V3 bsdf_sample ( Surface& sf, float e1, float e2, float e3, V3 wo, const Azimuth& az ) {
     if ( ( KINDS & 2 ) && ( KINDS == 2 || sf.bsdf == kDevBsdfPhong ) ) return phong_sample ( sf, e1, e2, e3, wo, az );

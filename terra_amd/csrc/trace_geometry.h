@@ -245,9 +245,8 @@ TD RayStateMasks ray_start_masks ( const Ray& r, V3& o_perm ) {
     at_xy ( r.o, o_perm.x, o_perm.y ); o_perm.z = at_z ( r.o );
     return s;
 }
-// Which launches start their rays that way, make one range test per ray (make_ray_guarded) and fetch the azimuth by its integer (shading_device.h
-// azimuth_fetch_index): the LDS-resident kernels of the plain presets without work counters, camera rays made in the kernel -- the headline's and Direct's kernels.
-// Every other instance keeps the integer form and compiles to the code it had: with the three changes some of them took a few bytes more scratch
+// Which launches start their rays that way and make one range test per ray (make_ray_guarded): the LDS-resident kernels of the plain presets without work counters, camera rays made in the kernel -- the headline's and Direct's kernels.
+// Every other instance starts its rays with ray_state_init's integer selection of the axes and keeps both range tests: with the predicate form some of them took a few bytes more scratch
 // (work-counter instances, MODE 0 light integrators, MODE 3), and the hall (MODE 2, a ray's state kept across the calls of a resumable loop) lost 1 %.
 #if TERRA_RAY_SOURCE
 #define TERRA_RAY_START_CAMERA 0

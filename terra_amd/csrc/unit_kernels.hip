@@ -223,7 +223,7 @@ __global__ void k_bsdf ( int kind, int n, float* surfaces47, const float* e3, co
     for ( int a = 0; a < 4; ++a ) sf.attr[a] = v3p ( q + 23 + 3 * a );
     sf.bsdf = kind; sf.ior = q[22];
     V3 wo = v3p ( wo3 + 3 * i );
-    V3 wi = bsdf_sample<TERRA_KINDS_ALL> ( sf, e3[3 * i], e3[3 * i + 1], e3[3 * i + 2], wo, azimuth_none() );
+    V3 wi = bsdf_sample<TERRA_KINDS_ALL> ( sf, e3[3 * i], e3[3 * i + 1], e3[3 * i + 2], wo, azimuth_fetch ( nullptr, e3[3 * i + 1] ) );          // (a stream-B value computes from its 24 bits, as a render does; any other float by tdm_sincosf_pair)
     float p = bsdf_pdf<TERRA_KINDS_ALL> ( sf, wi, wo );
     V3 f = bsdf_eval<TERRA_KINDS_ALL> ( sf, wi, wo );
     wi3[3 * i] = wi.x; wi3[3 * i + 1] = wi.y; wi3[3 * i + 2] = wi.z;
@@ -534,7 +534,7 @@ hipError_t terra_unit_distribution_2d_pdf ( const float* f, uint32_t nx, uint32_
     return hipGetLastError();
 }
 
-// ---- DevScene::sincos24: (cos, sin) of 2 * terra_PI * (k * 2^-24) for every 24-bit k, each entry by tdm_sincosf_pair itself (shading_device.h azimuth_fetch) ----
+// ---- DevScene::sincos24: (cos, sin) of 2 * terra_PI * (k * 2^-24) for every 24-bit k, each entry by tdm_sincosf_pair itself (shading_device.h azimuth_fetch_index) ----
 __global__ __launch_bounds__ ( 256 ) void terra_sincos24_kernel ( float2* table ) {
     const uint32_t k = blockIdx.x * 256u + threadIdx.x;          // grid = 2^24 / 256 blocks
     float sn, cs;
@@ -543,5 +543,19 @@ __global__ __launch_bounds__ ( 256 ) void terra_sincos24_kernel ( float2* table 
 }
 hipError_t terra_fill_sincos24 ( float2* table, hipStream_t stream ) {
     hipLaunchKernelGGL ( terra_sincos24_kernel, dim3 ( ( 1u << 24 ) / 256u ), dim3 ( 256 ), 0, stream, table );
+    return hipGetLastError();
+}
+// tdm_azimuth24 against the table, which stays its independent witness: computed[k] = what the single-arm form gives for k, in the table's layout, and
+// *mismatches counts the entries whose bits differ from table[k] (either word)
+__global__ __launch_bounds__ ( 256 ) void k_azimuth24 ( const float2* table, float2* computed, uint32_t* mismatches ) {
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;          // grid = 2^24 / 256 blocks
+    float sn, cs;
+    tdm_azimuth24 ( k, sn, cs );
+    computed[k] = make_float2 ( cs, sn );
+    const float2 t = table[k];
+    if ( __float_as_uint ( t.x ) != __float_as_uint ( cs ) || __float_as_uint ( t.y ) != __float_as_uint ( sn ) ) atomicAdd ( mismatches, 1u );
+}
+hipError_t terra_unit_azimuth24 ( const float2* table, float2* computed, uint32_t* mismatches ) {
+    hipLaunchKernelGGL ( k_azimuth24, dim3 ( ( 1u << 24 ) / 256u ), dim3 ( 256 ), 0, 0, table, computed, mismatches );
     return hipGetLastError();
 }

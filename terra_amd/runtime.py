@@ -70,6 +70,8 @@ _EXTRA = {
     "terra_amd_set_commit_timing": (None, [C.c_int]),
     "terra_amd_set_build_threads": (C.c_int, [C.c_int]),
     "terra_amd_set_azimuth_table": (None, [C.c_int]),
+    "terra_amd_get_azimuth_table": (C.c_int, []),
+    "terra_amd_azimuth_table_info": (C.c_int, [C.c_void_p]),
     "terra_amd_set_devices": (C.c_int, [C.POINTER(C.c_int), C.c_int]),
     "terra_amd_get_devices": (C.c_int, [C.POINTER(C.c_int), C.c_int]),
     "terra_amd_shard_owner": (C.c_int, [C.c_size_t, C.c_int]),
@@ -85,6 +87,7 @@ _EXTRA = {
     "terra_amd_set_environment_mis": (C.c_int, [C.c_void_p, C.c_int]),
     "terra_amd_get_environment_mis": (C.c_int, [C.c_void_p]),
     "terra_amd_unit_distribution_2d_pdf": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p]),
+    "terra_amd_unit_azimuth24": (C.c_int, [C.POINTER(C.c_uint32)]),
     "terra_amd_get_frame_seed": (C.c_uint64, [C.c_void_p]),
     "terra_amd_set_tree_mode": (C.c_int, [C.c_void_p, C.c_int]),
     "terra_amd_get_tree_mode": (C.c_int, [C.c_void_p]),

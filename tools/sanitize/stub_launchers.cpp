@@ -8,6 +8,7 @@ hipError_t terra_launch_render_points ( const DevRenderParams&, const void*, con
 hipError_t terra_launch_job_streams ( const DevRenderParams&, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_launch_block_order ( const DevRenderParams&, uint32_t*, hipStream_t, const DevLaunchMask*, bool, bool ) { return hipErrorNoDevice; }
 hipError_t terra_fill_sincos24 ( float2*, hipStream_t ) { return hipErrorNoDevice; }
+hipError_t terra_unit_azimuth24 ( const float2*, float2*, uint32_t* ) { return hipErrorNoDevice; }
 hipError_t terra_launch_resolve ( const DevRenderParams&, hipStream_t, const uint32_t* ) { return hipErrorNoDevice; }
 hipError_t terra_launch_tiles ( bool, float*, void*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, float*, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_unit_pcg ( const uint32_t*, int, int, float* ) { return hipErrorNoDevice; }
