@@ -36,7 +36,7 @@
  *       [--frames N] [--camera-to px py pz dx dy dz] [--temporal ALPHA]
  *       [--camera-model pinhole|thinlens|ortho|equirect|fisheye] [--aperture R] [--focus D] [--ortho-height H] [--fisheye-fov DEG]
  *       [--bake-lightmap [--atlas WxH] [--bake-margin M] [--bake-dilate N]]
- *       [--bake-probes NXxNYxNZ [--probe-cells N]]
+ *       [--bake-probes NXxNYxNZ [--probe-cells N] [--probe-visibility maps.pfm [--probe-texels M]]]
  *
  * Environment: the scene's environment attribute is a constant (--environment-color, default 0.4 0.52 1) or a lat-long map (--environment: Radiance .hdr with flat
  * or new-style run-length-encoded scanlines, orientation -Y H +X W, texel = m 2^(e - 136); or .pfm, either byte order, bottom row first), bound as a 3-component
@@ -104,6 +104,12 @@ int         terra_amd_probe_grid_points ( const void*, void*, int ) __attribute_
 int         terra_amd_probe_rays ( const void*, size_t, int, const float*, void* ) __attribute__ ( ( weak ) );
 int         terra_amd_render_rays ( HTerraScene, const void*, const TerraFramebuffer*, size_t, size_t, size_t, size_t ) __attribute__ ( ( weak ) );
 int         terra_amd_sh_project ( const TerraFramebuffer*, const void*, size_t, int, int, void* ) __attribute__ ( ( weak ) );
+/* probe visibility (TerraAmdHit, TerraAmdProbeVisibility, TerraAmdVisibilityTexel and the calls of terra_amd.h "Ray queries" / "Probe visibility", restated likewise) */
+typedef struct { float t; int object; int triangle; int reserved; float point[3]; float reserved2; } ProbeHit;
+typedef struct { int texels; int sharpness; float max_distance; float bias; int flags; int reserved[3]; } ProbeVisibility;
+typedef struct { float weight; float distance; float distance2; int cells; } VisibilityTexel;
+int         terra_amd_intersect ( HTerraScene, const void*, size_t, void* ) __attribute__ ( ( weak ) );
+int         terra_amd_probe_visibility ( const void*, const void*, size_t, int, const void*, int, void* ) __attribute__ ( ( weak ) );
 /* --camera-model: non-NULL = every render call and its AOV call go through the lens door */
 static const Lens* g_lens = NULL;
 static void render_rect ( const TerraCamera* cam, HTerraScene scene, const TerraFramebuffer* fb, size_t x, size_t y, size_t w, size_t h ) {
@@ -643,6 +649,10 @@ static const char* kHelp =
     "           index (iz * NY + iy) * NX + ix), as a float RGB image (.pfm / .hdr) 9 wide and NX * NY * NZ high: pixel (k, p) is coefficient k of probe p.\n"
     "           terra_amd_probe_rays lays N x N (1 .. 64, default 16) equal-area directions about every probe, terra_amd_render_rays gathers --spp samples per\n"
     "           --passes pass along each into one frame, terra_amd_sh_project reduces it. The camera flags, --aov, --denoise*, --adaptive, --frames and --gpus are ignored.\n"
+    "  --probe-visibility PATH [--probe-texels M] (with --bake-probes): also writes the probes' visibility maps as a float RGB image (.pfm / .hdr) M * M wide (M 1 .. 16,\n"
+    "           default 8) and NX * NY * NZ high: pixel (t, p) is texel t = j * M + i of probe p as (sum of w, sum of w * d, sum of w * d * d), d the distance\n"
+    "           terra_amd_intersect finds along the same cell-centre rays, w = cos^64 about the texel's octahedral direction (terra_amd_probe_visibility,\n"
+    "           sharpness 6), a miss and the cap being the diagonal of the scene's bounding box.\n"
     "OBJ/MTL import (--normals apollo, the default): the policy of the reference client's importer (satellite/include/Apollo.h under the\n"
     "options of satellite/src/Scene.cpp:83-93) RESTATED in this tool and pinned by hand-derived fixtures -- restated, not executed: Apollo.h\n"
     "does not compile with this image's toolchains. Everything after the TerraObject fill (commit, render, export) is the pinned path.\n";
@@ -660,6 +670,7 @@ int main ( int argc, char** argv ) {
     int camera_model = 0; float aperture = 0.f, focus = 1.f, ortho_height = 2.f, fisheye_fov = 180.f;      /* camera_model: 0 pinhole, 1 thinlens, 2 ortho, 3 equirect, 4 fisheye */
     int bake = 0, atlas_w = 256, atlas_h = 256, bake_dilate = 2; float bake_margin = 0.5f;      /* --bake-lightmap */
     int probes_on = 0, probe_n[3] = { 1, 1, 1 }, probe_cells = 16;      /* --bake-probes */
+    const char* visibility_path = NULL; int probe_texels = 8;      /* --probe-visibility */
     float fov = 45.f, exposure = 1.f, gamma = 2.2f, jitter = 0.f;
     unsigned long long seed = 0;
     const char* env_path = NULL; float env_rgb[3] = { 0.4f, 0.52f, 1.f }; int env_light = 0, env_sampling = 0;      /* env_sampling: 0 off, 1 table, 2 mis */
@@ -715,6 +726,8 @@ int main ( int argc, char** argv ) {
             probes_on = 1;
             if ( sscanf ( NEXT(), "%dx%dx%d", &probe_n[0], &probe_n[1], &probe_n[2] ) != 3 || probe_n[0] < 1 || probe_n[1] < 1 || probe_n[2] < 1 || ( double ) probe_n[0] * probe_n[1] * probe_n[2] > 1048576. ) { fprintf ( stderr, "terra_headless: --bake-probes NXxNYxNZ, each at least 1, at most 1048576 probes\n" ); return 64; }
         }
+        else if ( !strcmp ( a, "--probe-visibility" ) ) visibility_path = NEXT();
+        else if ( !strcmp ( a, "--probe-texels" ) ) { probe_texels = atoi ( NEXT() ); if ( probe_texels < 1 || probe_texels > 16 ) { fprintf ( stderr, "terra_headless: --probe-texels 1 .. 16\n" ); return 64; } }
         else if ( !strcmp ( a, "--probe-cells" ) ) { probe_cells = atoi ( NEXT() ); if ( probe_cells < 1 || probe_cells > 64 ) { fprintf ( stderr, "terra_headless: --probe-cells 1 .. 64\n" ); return 64; } }
         else if ( !strcmp ( a, "--camera-to" ) && i + 6 < argc ) {
             cam_to.position = terra_f3_set ( ( float ) atof ( argv[i + 1] ), ( float ) atof ( argv[i + 2] ), ( float ) atof ( argv[i + 3] ) );
@@ -807,6 +820,8 @@ int main ( int argc, char** argv ) {
     if ( probes_on && ( !terra_amd_scene_vertex_points || !terra_amd_probe_grid_points || !terra_amd_probe_rays || !terra_amd_render_rays || !terra_amd_sh_project ) ) {
         fprintf ( stderr, "terra_headless: --bake-probes needs libterra_amd.so; ignored, the camera's image is written\n" ); probes_on = 0;
     }
+    if ( visibility_path && !probes_on ) { fprintf ( stderr, "terra_headless: --probe-visibility goes with --bake-probes; ignored\n" ); visibility_path = NULL; }
+    if ( visibility_path && ( !terra_amd_intersect || !terra_amd_probe_visibility ) ) { fprintf ( stderr, "terra_headless: --probe-visibility needs libterra_amd.so; ignored\n" ); visibility_path = NULL; }
     if ( probes_on ) {          /* the probe frame: cell c of probe p at pixel (c, p); one projection of everything the passes gathered */
         const size_t P = ( size_t ) probe_n[0] * ( size_t ) probe_n[1] * ( size_t ) probe_n[2], K = ( size_t ) probe_cells * ( size_t ) probe_cells;
         terra_scene_commit ( scene );
@@ -818,9 +833,11 @@ int main ( int argc, char** argv ) {
         int rc = terra_amd_scene_vertex_points ( scene, verts, nv ) < 0;
         ProbeGrid grid; memset ( &grid, 0, sizeof grid );
         grid.nx = probe_n[0]; grid.ny = probe_n[1]; grid.nz = probe_n[2];
+        double diagonal2 = 0.;          /* of the bounding box, for --probe-visibility */
         for ( int a = 0; a < 3; ++a ) {          /* cell-centred over the bounding box; an axis the scene has no extent on gets the spacing 1 */
             float lo = verts[0].position[a], hi = lo;
             for ( int k = 1; k < nv; ++k ) { const float v = verts[k].position[a]; if ( v < lo ) lo = v; if ( v > hi ) hi = v; }
+            diagonal2 += ( double ) ( hi - lo ) * ( double ) ( hi - lo );
             float sp = ( hi - lo ) / ( float ) probe_n[a];
             if ( !( sp > 0.f ) ) sp = 1.f;
             grid.spacing[a] = sp; grid.origin[a] = lo + 0.5f * sp;
@@ -832,6 +849,21 @@ int main ( int argc, char** argv ) {
         if ( rc ) { fprintf ( stderr, "terra_headless: %s\n", terra_amd_last_error && *terra_amd_last_error() ? terra_amd_last_error() : "the probe bake failed" ); return 70; }
         for ( size_t p = 0; p < P; ++p ) for ( int k = 0; k < 9; ++k ) image.pixels[9 * p + ( size_t ) k] = terra_f3_set ( sh[p].c[k][0], sh[p].c[k][1], sh[p].c[k][2] );
         if ( !write_image ( argv[2], &image ) ) { fprintf ( stderr, "terra_headless: cannot write %s\n", argv[2] ); return 73; }
+        if ( visibility_path ) {          /* the distances along the same cell-centre rays, filtered into one map per probe */
+            const size_t MM = ( size_t ) probe_texels * ( size_t ) probe_texels;
+            ProbeHit* hits = aligned_alloc ( 16, P * K * sizeof ( ProbeHit ) ); VisibilityTexel* texels = aligned_alloc ( 16, P * MM * sizeof ( VisibilityTexel ) );
+            TerraFramebuffer maps;
+            if ( !hits || !texels || !terra_framebuffer_create ( &maps, MM, P ) ) { fprintf ( stderr, "terra_headless: out of memory\n" ); return 71; }
+            ProbeVisibility vis; memset ( &vis, 0, sizeof vis );
+            vis.texels = probe_texels; vis.sharpness = 6; vis.max_distance = ( float ) sqrt ( diagonal2 );
+            rc = terra_amd_intersect ( scene, rays, P * K, hits );
+            if ( !rc ) rc = terra_amd_probe_visibility ( hits, rays, P, probe_cells, &vis, 0, texels );
+            if ( rc ) { fprintf ( stderr, "terra_headless: %s\n", terra_amd_last_error && *terra_amd_last_error() ? terra_amd_last_error() : "the probe visibility bake failed" ); return 70; }
+            for ( size_t t = 0; t < P * MM; ++t ) maps.pixels[t] = terra_f3_set ( texels[t].weight, texels[t].distance, texels[t].distance2 );
+            if ( !write_image ( visibility_path, &maps ) ) { fprintf ( stderr, "terra_headless: cannot write %s\n", visibility_path ); return 73; }
+            printf ( "%s: probe visibility %s (%d x %d texels, max distance %g)\n", argv[1], visibility_path, probe_texels, probe_texels, ( double ) vis.max_distance );
+            free ( hits ); free ( texels ); terra_framebuffer_destroy ( &maps );
+        }
         printf ( "%s: %zu triangles, %zu materials -> probes %s (%dx%dx%d probes, %d x %d cells, %zu spp x %d)\n", argv[1], m.faces.n, m.mtls.n, argv[2], probe_n[0], probe_n[1], probe_n[2], probe_cells, probe_cells, spp, passes );
         free ( verts ); free ( probes ); free ( rays ); free ( sh );
         terra_framebuffer_destroy ( &frame ); terra_framebuffer_destroy ( &image );

@@ -1033,6 +1033,93 @@ int terra_amd_sh_irradiance ( const TerraAmdProbeSH* sh, size_t probes, const Te
    (double) spacing_a), the normal (0, 0, 1). Returns nx * ny * nz whatever the capacity, or a negative status, and writes the first min(capacity, probes) records. */
 int terra_amd_probe_grid_points ( const TerraAmdProbeGrid* grid, TerraAmdPoint* out, int capacity );
 
+/* ---- Probe visibility: per-probe distance maps, and a probe-grid lookup that does not leak through walls -------------------------------------------------------
+   The grid lookup of "Probe harmonics" knows nothing about geometry: a query beside a wall takes up to half of its irradiance from the probes behind that wall.
+   A visibility map records, per probe and per direction, the mean distance and the mean squared distance to the nearest surface (terra_amd_probe_visibility*, from
+   the hit records terra_amd_intersect* returns for the probe rays); terra_amd_sh_irradiance_visible* weights each of the eight probes of a cell by a Chebyshev test
+   of the query's distance against that map and by a back-face term. The reference has no such calls: this is the library's own definition, off unless called.
+   Neither call takes a scene; both run on the calling thread's current device.
+   Arithmetic.  binary64 throughout, in exactly the order written, no fused multiply-add, IEEE division, the correctly rounded square root; (double) of a binary32
+     is exact; sgn(x) is x >= 0 ? 1 : -1 (so sgn(-0.0) is 1); |x| clears the sign bit.
+   The map.  m = options->texels, 1 .. 16: m * m texels per probe, one TerraAmdVisibilityTexel each; texel t = j * m + i of probe p is record p * m * m + t.
+     The fields are SUMS, not means (weight = sum of w, distance = sum of w * d, distance2 = sum of w * d * d), so that batches of different jitter add into one map.
+   Texel direction.  The octahedral decode of the texel centre, in world space (not about the probe's pole: the lookup needs no probe frame):
+       qx = (2.0 * (((double) i + 0.5) / (double) m)) - 1.0,  qy likewise from j;   z = (1.0 - |qx|) - |qy|;
+       z < 0:  x = (1.0 - |qy|) * sgn(qx),  y = (1.0 - |qx|) * sgn(qy);   otherwise x = qx, y = qy;
+       len = sqrt(((x * x) + (y * y)) + (z * z));   T = (x / len, y / len, z / len).
+   Cell distance.  The inputs are the probe rays (K = cells * cells TerraAmdRay per probe, as terra_amd_probe_rays* lays them) and the TerraAmdHit records
+     terra_amd_intersect* returned for exactly those rays. A cell takes part unless its ray is inactive by the ray door's rule (a direction of exactly (0, 0, 0), or
+     an origin or direction component that is not finite) -- the predicate of the projection above. D = (double) max_distance.
+       object < 0:  d = D;   otherwise d = (double) t, and d = D where !(t <= max_distance) (compared in binary32; so a NaN t gives D too).
+     The direction (rx, ry, rz) is the stored binary32 direction widened, used as given and not normalised.
+   Sum.  For each texel, over the cells c = 0, 1, .. K - 1 in ascending order, W = Wd = Wd2 = +0.0 and cells = 0 at the start; a cell that does not take part is passed over;
+       cosv = ((Tx * rx) + (Ty * ry)) + (Tz * rz);   !(cosv > 0): the cell is passed over;
+       w = cosv;  then  w = w * w,  s = options->sharpness times  (the weight cos^(2^s); pow cannot be restated bit for bit);
+       W = W + w;   Wd = Wd + (w * d);   Wd2 = Wd2 + (w * (d * d));   cells = cells + 1.
+     Every texel's three sums are one sequential chain: nothing is combined across lanes, there are no atomics, the same inputs give the same bits.
+     accumulate == 0: weight = (float) W, distance = (float) Wd, distance2 = (float) Wd2, cells = cells.
+     accumulate != 0: field = (float) ((double) old_field + new) for the three sums, cells = old cells + cells (two's complement).
+   The lookup.  Grid mode only. A query is a TerraAmdPoint; the output is four floats per query, (E_r, E_g, E_b, 0).
+     1. The normal test, N, the per-axis lower / upper probe and t, the corner order (dz, dy, dx) = 000 .. 111 and the trilinear weight wt = (wz * wy) * wx are
+        those of terra_amd_sh_irradiance() in grid mode, word for word (a bad normal or a NaN f gives (0, 0, 0, 0)).
+     2. A corner's probe position on axis a is G_a = (double) (float) ((double) origin_a + (double) i_a * (double) spacing_a): what terra_amd_probe_grid_points() gives.
+     3. b = (double) options->bias.  X_a = (double) position_a + (b * N_a);  V_a = X_a - G_a;  dist = sqrt(((Vx * Vx) + (Vy * Vy)) + (Vz * Vz)).
+     4. Back-face term. Flag bit 0 clear: wb = 1. Set and dist > 0:  bf = ((((-((Vx * Nx) + (Vy * Ny))) - (Vz * Nz)) / dist) + 1.0) * 0.5,  wb = (bf * bf) + 0.2.
+        Set and !(dist > 0): wb = 1.2.
+     5. Visibility term. a = (|Vx| + |Vy|) + |Vz|. dist == 0, or a not finite (an infinite position): wv = 1. Otherwise
+          px = Vx / a, py = Vy / a;   Vz < 0:  (px, py) = ((1.0 - |py|) * sgn(px), (1.0 - |px|) * sgn(py)), both from the old values;
+          u = (px * 0.5) + 0.5,  v = (py * 0.5) + 0.5;   fx = (u * (double) m) - 0.5,  i0 = floor(fx),  tx = fx - i0,  i1 = i0 + 1;  the same for (v, fy, j0, ty, j1);
+        the four taps in the order (j0, i0), (j0, i1), (j1, i0), (j1, i1) with the weights (1.0 - ty) * (1.0 - tx), (1.0 - ty) * tx, ty * (1.0 - tx), ty * tx.
+        Octahedral wrap of a tap (i, j): first, i < 0: i = 0, j = m - 1 - j;  i >= m: i = m - 1, j = m - 1 - j;  then, j < 0: j = 0, i = m - 1 - i;  j >= m:
+        j = m - 1, i = m - 1 - i  (so (-1, -1) lands on (m - 1, m - 1)).
+        The three SUMS are blended, not the means: W = sum of tapweight * (double) weight, Wd, Wd2 likewise, in tap order starting from the first tap's term.
+          !(W > 0): wv = 1. Otherwise mean = Wd / W, mean2 = Wd2 / W, var = |(mean * mean) - mean2|.
+          dist <= mean: wv = 1. Otherwise e = dist - mean, q = var + (e * e);  !(q > 0): wv = 0;  otherwise ch = var / q, wv = (ch * ch) * ch.
+     6. w = (wt * wb) * wv.  S = sum of w and, per coefficient, sum of w * (double) c, in corner order starting from the first corner's term; the plain sums with
+        w = wt are kept beside them.
+     7. S > 0: coefficient = sum / S. Otherwise (every probe hidden, or S not a positive number): coefficient = the plain sum -- the result then has
+        terra_amd_sh_irradiance()'s bits. E_ch from the coefficients and N exactly as in terra_amd_sh_irradiance().
+   Calls.  Every refusal is kTerraAmdErrBadArgument, decided before a device is asked for and with nothing written: a NULL required buffer or options pointer; a
+     device or host record buffer (hits, rays, map, sh, queries, the device form's output) that is not 16-byte aligned; cells outside 1 .. 64; K * P above 2^31 - 1;
+     texels outside 1 .. 16; sharpness outside 0 .. 8; max_distance not finite or <= 0; bias not finite or negative; a flag bit other than bit 0; non-zero reserved;
+     probes * m * m above 2^31 - 1; more than 2^31 - 1 queries; a NULL grid and the grid refusals of "Probe harmonics", probes != nx * ny * nz among them.
+     probes == 0 (projection) and n == 0 (lookup) succeed and launch nothing. */
+#define kTerraAmdProbeVisibilityBackface 1      /* TerraAmdProbeVisibility::flags bit 0: the lookup's back-face term */
+typedef struct {              /* 32 bytes */
+    int   texels;             /* +0  m, 1 .. 16: the map is m x m texels per probe */
+    int   sharpness;          /* +4  s, 0 .. 8: the filter weight is cos^(2^s), made by s squarings */
+    float max_distance;       /* +8  finite, > 0: the distance recorded for a miss and the cap on every distance */
+    float bias;               /* +12 finite, >= 0: the lookup moves the query this far along its normal; the projection does not look at it */
+    int   flags;              /* +16 bit 0: the lookup's back-face term; the other bits zero */
+    int   reserved[3];        /* +20 zero */
+} TerraAmdProbeVisibility;
+typedef struct {              /* 16 bytes, 16-byte aligned in a buffer */
+    float weight;             /* +0  sum of w */
+    float distance;           /* +4  sum of w * d */
+    float distance2;          /* +8  sum of w * d * d */
+    int   cells;              /* +12 cells that were added */
+} TerraAmdVisibilityTexel;
+TERRA_ABI_ASSERT ( sizeof ( TerraAmdProbeVisibility ) == 32 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdProbeVisibility, sharpness ) == 4 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdProbeVisibility, max_distance ) == 8 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdProbeVisibility, bias ) == 12 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdProbeVisibility, flags ) == 16 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdProbeVisibility, reserved ) == 20 );
+TERRA_ABI_ASSERT ( sizeof ( TerraAmdVisibilityTexel ) == 16 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdVisibilityTexel, distance ) == 4 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdVisibilityTexel, distance2 ) == 8 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdVisibilityTexel, cells ) == 12 );
+/* d_hits: probes * cells * cells TerraAmdHit, d_rays: the TerraAmdRay records they answer; options: host memory; d_map: probes * texels * texels
+   TerraAmdVisibilityTexel, read as well where accumulate != 0. Asynchronous on `stream`. */
+int terra_amd_probe_visibility_device ( const void* d_hits, const void* d_rays, size_t probes, int cells, const TerraAmdProbeVisibility* options, int accumulate, void* d_map, void* stream );
+/* The same on host memory; synchronous. */
+int terra_amd_probe_visibility ( const TerraAmdHit* hits, const TerraAmdRay* rays, size_t probes_n, int cells, const TerraAmdProbeVisibility* options, int accumulate, TerraAmdVisibilityTexel* map );
+/* d_sh: `probes` TerraAmdProbeSH; d_map: probes * texels * texels TerraAmdVisibilityTexel; grid, options: host memory, both required; d_points: n TerraAmdPoint;
+   d_out: n * 4 floats. Asynchronous on `stream`. */
+int terra_amd_sh_irradiance_visible_device ( const void* d_sh, const void* d_map, size_t probes, const TerraAmdProbeGrid* grid, const TerraAmdProbeVisibility* options, const void* d_points, size_t n, void* d_out, void* stream );
+/* The same on host memory; synchronous. */
+int terra_amd_sh_irradiance_visible ( const TerraAmdProbeSH* sh, const TerraAmdVisibilityTexel* map, size_t probes, const TerraAmdProbeGrid* grid, const TerraAmdProbeVisibility* options, const TerraAmdPoint* points, size_t n, float* out4 );
+
 /* Tile-sharded form for one-process-per-GPU rendering (the reference shards
    the same way over CPU threads: satellite/src/Renderer.cpp:316-350): the
    rectangle is cut into tile_size x tile_size tiles numbered row-major and this

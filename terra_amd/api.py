@@ -323,6 +323,32 @@ PROBE_SIGNATURES = {
     "terra_amd_probe_grid_points": (c_int, [POINTER(ProbeGrid), c_void_p, c_int]),
 }
 
+
+class ProbeVisibility(Structure):
+    """TerraAmdProbeVisibility (include/terra_amd.h "Probe visibility"): texels m (1 .. 16) per side of a probe's map, sharpness s (0 .. 8: the weight cos^(2^s)),
+    max_distance (a miss, and the cap), bias (the lookup's offset along the normal), flags (bit 0: the lookup's back-face term); 32 bytes"""
+    _fields_ = [("texels", c_int), ("sharpness", c_int), ("max_distance", c_float), ("bias", c_float), ("flags", c_int), ("reserved", c_int * 3)]
+
+
+class VisibilityTexel(Structure):
+    """TerraAmdVisibilityTexel: the sums of w, w * d and w * d * d over the cells a texel added, and their number; 16 bytes"""
+    _fields_ = [("weight", c_float), ("distance", c_float), ("distance2", c_float), ("cells", c_int)]
+
+
+PROBE_VISIBILITY_BACKFACE = 1
+ABI_SIZES.update({ProbeVisibility: 32, VisibilityTexel: 16})
+assert C.sizeof(ProbeVisibility) == 32 and C.sizeof(VisibilityTexel) == 16
+VISIBILITY_TEXEL_DTYPE = np.dtype([("weight", np.float32), ("distance", np.float32), ("distance2", np.float32), ("cells", np.int32)])
+assert VISIBILITY_TEXEL_DTYPE.itemsize == 16
+
+# ... and of probe visibility (include/terra_amd.h "Probe visibility")
+PROBE_VISIBILITY_SIGNATURES = {
+    "terra_amd_probe_visibility_device": (c_int, [c_void_p, c_void_p, c_size_t, c_int, POINTER(ProbeVisibility), c_int, c_void_p, c_void_p]),
+    "terra_amd_probe_visibility": (c_int, [c_void_p, c_void_p, c_size_t, c_int, POINTER(ProbeVisibility), c_int, c_void_p]),
+    "terra_amd_sh_irradiance_visible_device": (c_int, [c_void_p, c_void_p, c_size_t, POINTER(ProbeGrid), POINTER(ProbeVisibility), c_void_p, c_size_t, c_void_p, c_void_p]),
+    "terra_amd_sh_irradiance_visible": (c_int, [c_void_p, c_void_p, c_size_t, POINTER(ProbeGrid), POINTER(ProbeVisibility), c_void_p, c_size_t, c_void_p]),
+}
+
 # entry points of include/Terra.h + include/TerraPresets.h, name -> (restype, argtypes)
 API_SIGNATURES = {
     "scene_create": (c_void_p, []),

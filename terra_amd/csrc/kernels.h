@@ -114,6 +114,17 @@ hipError_t terra_launch_probe_rays ( const void* probes, uint32_t count, uint32_
 hipError_t terra_launch_sh_project ( const void* results, const void* rays, uint32_t count, uint32_t cells, int batch, void* sh, hipStream_t stream );
 // sh: probes TerraAmdProbeSH; points: n TerraAmdPoint; index: n ints (index mode only); out: n float4
 hipError_t terra_launch_sh_irradiance ( const void* sh, uint32_t probes, const DevProbeGrid& grid, const void* points, const int* index, uint32_t n, void* out, hipStream_t stream );
+// probe visibility (probe_kernels.hip; include/terra_amd.h "Probe visibility"): the options of a call, checked by the host layer (texels 1 .. 16, sharpness 0 .. 8,
+// count * texels * texels <= 2^31 - 1)
+struct DevProbeVisibility {
+    int32_t texels, sharpness;
+    float   max_distance, bias;
+    int32_t backface;           // flag bit 0
+};
+// hits: count * cells * cells TerraAmdHit, rays: the TerraAmdRay records they answer; map: count * texels * texels TerraAmdVisibilityTexel, read as well where accumulate != 0
+hipError_t terra_launch_probe_visibility ( const void* hits, const void* rays, uint32_t count, uint32_t cells, const DevProbeVisibility& options, int accumulate, void* map, hipStream_t stream );
+// sh: TerraAmdProbeSH and map: texels * texels TerraAmdVisibilityTexel for each probe of the grid (grid.on set); points: n TerraAmdPoint; out: n float4
+hipError_t terra_launch_sh_irradiance_visible ( const void* sh, const void* map, const DevProbeGrid& grid, const DevProbeVisibility& options, const void* points, uint32_t n, void* out, hipStream_t stream );
 
 hipError_t terra_fill_sincos24 ( float2* table, hipStream_t stream );    // DevScene::sincos24: 2^24 entries (128 MB), device pointer
 // table, computed: 2^24 entries each; *mismatches (zeroed by the caller) += the entries of table that tdm_azimuth24 does not reproduce bit for bit

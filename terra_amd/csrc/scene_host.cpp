@@ -2951,6 +2951,88 @@ extern "C" int terra_amd_sh_irradiance ( const TerraAmdProbeSH* sh, size_t probe
     if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "SH irradiance download: %s", hipGetErrorString ( e ) );
     return 0;
 }
+// ---- probe visibility: distance maps and the visible grid lookup (probe_kernels.hip; include/terra_amd.h "Probe visibility") -------------------------------------
+static_assert ( sizeof ( TerraAmdProbeVisibility ) == 32 && sizeof ( TerraAmdVisibilityTexel ) == 16, "TerraAmdProbeVisibility must be 32 bytes, TerraAmdVisibilityTexel 16" );
+// the options of either call, and that `probes` maps of them stay within 2^31 - 1 texels
+static int visibility_options_check ( const TerraAmdProbeVisibility* o, size_t probes, const char* what, DevProbeVisibility& V ) {
+    V = DevProbeVisibility{};
+    if ( !o ) return fail ( kTerraAmdErrBadArgument, "%s: null options", what );
+    if ( o->texels < 1 || o->texels > 16 ) return fail ( kTerraAmdErrBadArgument, "%s: texels %d: 1 .. 16", what, o->texels );
+    if ( o->sharpness < 0 || o->sharpness > 8 ) return fail ( kTerraAmdErrBadArgument, "%s: sharpness %d: 0 .. 8", what, o->sharpness );
+    if ( !std::isfinite ( o->max_distance ) || ! ( o->max_distance > 0.f ) ) return fail ( kTerraAmdErrBadArgument, "%s: max_distance must be finite and above 0", what );
+    if ( !std::isfinite ( o->bias ) || o->bias < 0.f ) return fail ( kTerraAmdErrBadArgument, "%s: bias must be finite and not negative", what );
+    if ( o->flags & ~kTerraAmdProbeVisibilityBackface ) return fail ( kTerraAmdErrBadArgument, "%s: unknown flag bits 0x%x", what, ( unsigned ) o->flags );
+    for ( int r : o->reserved ) if ( r ) return fail ( kTerraAmdErrBadArgument, "%s: TerraAmdProbeVisibility::reserved must be zero", what );
+    if ( probes > ( size_t ) 0x7fffffff / ( ( size_t ) o->texels * ( size_t ) o->texels ) ) return fail ( kTerraAmdErrBadArgument, "%s: %zu probes of %d x %d texels: more than 2^31 - 1 texels", what, probes, o->texels, o->texels );
+    V.texels = o->texels; V.sharpness = o->sharpness; V.max_distance = o->max_distance; V.bias = o->bias; V.backface = o->flags & kTerraAmdProbeVisibilityBackface;
+    return 0;
+}
+// the one check of each call pair, made before the call asks for a device
+static int probe_visibility_check ( const void* hits, const void* rays, size_t probes, int cells, const TerraAmdProbeVisibility* options, const void* map, const char* what, DevProbeVisibility& V ) {
+    if ( int rc = probe_frame_check ( probes, cells, what ) ) return rc;
+    if ( int rc = visibility_options_check ( options, probes, what, V ) ) return rc;
+    if ( int rc = probe_buffer ( hits, "hit", what ) ) return rc;
+    if ( int rc = probe_buffer ( rays, "ray", what ) ) return rc;
+    return probe_buffer ( map, "map", what );
+}
+static int sh_irradiance_visible_check ( const void* sh, const void* map, size_t probes, const TerraAmdProbeGrid* grid, const TerraAmdProbeVisibility* options, const void* points, size_t n, const void* out,
+                                         bool out_aligned, const char* what, DevProbeGrid& G, DevProbeVisibility& V ) {
+    if ( !grid ) return fail ( kTerraAmdErrBadArgument, "%s: null grid (the visible lookup is a grid lookup)", what );
+    if ( int rc = sh_irradiance_check ( sh, probes, grid, points, nullptr, n, out, out_aligned, what, G ) ) return rc;
+    if ( int rc = visibility_options_check ( options, probes, what, V ) ) return rc;
+    return probe_buffer ( map, "map", what );
+}
+extern "C" int terra_amd_probe_visibility_device ( const void* d_hits, const void* d_rays, size_t probes, int cells, const TerraAmdProbeVisibility* options, int accumulate, void* d_map, void* stream ) {
+    DevProbeVisibility V;
+    if ( int rc = probe_visibility_check ( d_hits, d_rays, probes, cells, options, d_map, "terra_amd_probe_visibility_device", V ) ) return rc;
+    if ( probes == 0 ) return 0;
+    const hipError_t e = terra_launch_probe_visibility ( d_hits, d_rays, ( uint32_t ) probes, ( uint32_t ) cells, V, accumulate, d_map, ( hipStream_t ) stream );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "probe visibility launch: %s", hipGetErrorString ( e ) );
+    return 0;
+}
+extern "C" int terra_amd_probe_visibility ( const TerraAmdHit* hits, const TerraAmdRay* rays, size_t probes_n, int cells, const TerraAmdProbeVisibility* options, int accumulate, TerraAmdVisibilityTexel* map ) {
+    DevProbeVisibility V;
+    if ( int rc = probe_visibility_check ( hits, rays, probes_n, cells, options, map, "terra_amd_probe_visibility", V ) ) return rc;
+    if ( probes_n == 0 ) return 0;
+    if ( terra_amd_device_count() <= 0 ) return fail ( kTerraAmdErrNoDevice, "no HIP device visible" );
+    const size_t cells_n = probes_n * ( size_t ) cells * ( size_t ) cells, map_bytes = probes_n * ( size_t ) V.texels * ( size_t ) V.texels * sizeof ( TerraAmdVisibilityTexel );
+    FrameCopy c;
+    hipError_t e = c.up ( 0, hits, cells_n * sizeof ( TerraAmdHit ) );
+    if ( e == hipSuccess ) e = c.up ( 1, rays, cells_n * sizeof ( TerraAmdRay ) );
+    if ( e == hipSuccess ) e = c.up ( 2, accumulate ? map : nullptr, map_bytes );          // (accumulate reads the records)
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "probe visibility upload: %s", hipGetErrorString ( e ) );
+    if ( int rc = terra_amd_probe_visibility_device ( c.d[0], c.d[1], probes_n, cells, options, accumulate, c.d[2], nullptr ) ) return rc;
+    e = c.down ( 2, map, map_bytes );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "probe visibility download: %s", hipGetErrorString ( e ) );
+    return 0;
+}
+extern "C" int terra_amd_sh_irradiance_visible_device ( const void* d_sh, const void* d_map, size_t probes, const TerraAmdProbeGrid* grid, const TerraAmdProbeVisibility* options, const void* d_points, size_t n,
+                                                        void* d_out, void* stream ) {
+    DevProbeGrid G; DevProbeVisibility V;
+    if ( int rc = sh_irradiance_visible_check ( d_sh, d_map, probes, grid, options, d_points, n, d_out, true, "terra_amd_sh_irradiance_visible_device", G, V ) ) return rc;
+    if ( n == 0 ) return 0;
+    const hipError_t e = terra_launch_sh_irradiance_visible ( d_sh, d_map, G, V, d_points, ( uint32_t ) n, d_out, ( hipStream_t ) stream );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "visible SH irradiance launch: %s", hipGetErrorString ( e ) );
+    return 0;
+}
+extern "C" int terra_amd_sh_irradiance_visible ( const TerraAmdProbeSH* sh, const TerraAmdVisibilityTexel* map, size_t probes, const TerraAmdProbeGrid* grid, const TerraAmdProbeVisibility* options,
+                                                 const TerraAmdPoint* points, size_t n, float* out4 ) {
+    DevProbeGrid G; DevProbeVisibility V;
+    if ( int rc = sh_irradiance_visible_check ( sh, map, probes, grid, options, points, n, out4, false, "terra_amd_sh_irradiance_visible", G, V ) ) return rc;
+    if ( n == 0 ) return 0;
+    if ( terra_amd_device_count() <= 0 ) return fail ( kTerraAmdErrNoDevice, "no HIP device visible" );
+    FrameCopy c;
+    hipError_t e = c.up ( 0, sh, probes * sizeof ( TerraAmdProbeSH ) );
+    if ( e == hipSuccess ) e = c.up ( 1, points, n * sizeof ( TerraAmdPoint ) );
+    if ( e == hipSuccess ) e = c.up ( 2, map, probes * ( size_t ) V.texels * ( size_t ) V.texels * sizeof ( TerraAmdVisibilityTexel ) );
+    if ( e == hipSuccess ) e = c.up ( 3, nullptr, n * 4 * sizeof ( float ) );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "visible SH irradiance upload: %s", hipGetErrorString ( e ) );
+    if ( int rc = terra_amd_sh_irradiance_visible_device ( c.d[0], c.d[2], probes, grid, options, c.d[1], n, c.d[3], nullptr ) ) return rc;
+    e = c.down ( 3, out4, n * 4 * sizeof ( float ) );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "visible SH irradiance download: %s", hipGetErrorString ( e ) );
+    return 0;
+}
+
 // the grid's probes as points, in index order. Host only. Returns the number of probes whatever the capacity; writes the first min(capacity, probes) of them
 extern "C" int terra_amd_probe_grid_points ( const TerraAmdProbeGrid* grid, TerraAmdPoint* out, int capacity ) {
     if ( !grid ) return fail ( kTerraAmdErrBadArgument, "terra_amd_probe_grid_points: null grid" );

@@ -153,6 +153,7 @@ _EXTRA = {
     **api.POINT_SIGNATURES,
     **api.BAKE_SIGNATURES,
     **api.PROBE_SIGNATURES,
+    **api.PROBE_VISIBILITY_SIGNATURES,
     **api.EXACT_SQRT_SIGNATURES,
 }
 
@@ -862,6 +863,82 @@ def bake_probes(lib, scene, probes, cells: int = 16, batches: int = 1, jitter=No
         render_rays_device(lib, scene, rays, fb, stream=stream)
         sh = sh_project(lib, fb, rays, cells, batch=b, sh=sh)
     return sh
+
+
+# ---------------------------------------------------------------------------
+# probe visibility (include/terra_amd.h "Probe visibility")
+# ---------------------------------------------------------------------------
+
+def probe_visibility_options(texels: int = 8, sharpness: int = 6, max_distance: float = 1.0, bias: float = 0.0, backface: bool = False) -> api.ProbeVisibility:
+    """api.ProbeVisibility: maps of texels x texels (1 .. 16), the weight cos^(2^sharpness) (0 .. 8), max_distance for a miss and as the cap, and for the lookup the
+    bias along the query's normal and the back-face term"""
+    o = api.ProbeVisibility()
+    o.texels, o.sharpness, o.max_distance, o.bias = int(texels), int(sharpness), float(max_distance), float(bias)
+    o.flags = api.PROBE_VISIBILITY_BACKFACE if backface else 0
+    return o
+
+
+def probe_visibility(lib, hits, rays, cells: int, options: api.ProbeVisibility, map=None):
+    """terra_amd_probe_visibility_device on the current torch stream: hits as intersect returns them for `rays` (float32 [P * K, 8] or [P, K, 8] in HBM), rays as
+    probe_rays returns them -> map float32 [P, texels * texels, 4] in HBM: api.VISIBILITY_TEXEL_DTYPE records (the sums of w, w d, w d d, then the bits of cells;
+    visibility_map_host gives the records). map = the tensor an earlier call returned: the sums are added to it."""
+    import torch
+    n = _records(rays, 8, "probe_visibility rays")
+    if _records(hits, 8, "probe_visibility hits") != n or n % (cells * cells):
+        raise TerraAmdError("probe_visibility: one hit and one ray per cell of every probe")
+    probes, mm = n // (cells * cells), options.texels * options.texels
+    accumulate = map is not None
+    if map is None:
+        map = torch.zeros((probes, mm, 4), dtype=torch.float32, device=rays.device)
+    elif _records(map, 4, "probe_visibility map") != probes * mm:
+        raise TerraAmdError("probe_visibility: texels * texels records per probe")
+    check(lib.probe_visibility_device(hits.data_ptr(), rays.data_ptr(), probes, cells, C.byref(options), int(accumulate), map.data_ptr(), _current_stream()), "terra_amd_probe_visibility_device")
+    return map
+
+
+def visibility_map_host(vis_map) -> np.ndarray:
+    """the texels of a tensor [P, m * m, 4] as [P, m * m] api.VISIBILITY_TEXEL_DTYPE records on the host"""
+    return vis_map.cpu().numpy().view(api.VISIBILITY_TEXEL_DTYPE).reshape(vis_map.shape[0], -1)
+
+
+def sh_irradiance_visible(lib, sh, vis_map, points, grid: api.ProbeGrid, options: api.ProbeVisibility):
+    """terra_amd_sh_irradiance_visible_device on the current torch stream: sh [P, 28] as sh_project returns it, vis_map [P, texels * texels, 4] as probe_visibility
+    returns it, points float32 [n, 8] in HBM (api.POINT_DTYPE records), the grid of the P probes -> float32 [n, 4]: (E_r, E_g, E_b, 0), every probe weighted by its
+    visibility from the query"""
+    import torch
+    probes = _records(sh, 28, "sh_irradiance_visible sh")
+    n = _records(points, 8, "sh_irradiance_visible points")
+    if _records(vis_map, 4, "sh_irradiance_visible map") != probes * options.texels * options.texels:
+        raise TerraAmdError("sh_irradiance_visible: texels * texels map records per probe")
+    if grid is None:
+        raise TerraAmdError("sh_irradiance_visible is a grid lookup: pass the grid")
+    out = torch.empty((n, 4), dtype=torch.float32, device=points.device)
+    check(lib.sh_irradiance_visible_device(sh.data_ptr(), vis_map.data_ptr(), probes, C.byref(grid), C.byref(options), points.data_ptr(), n, out.data_ptr(), _current_stream()),
+          "terra_amd_sh_irradiance_visible_device")
+    return out
+
+
+def bake_probe_visibility(lib, scene, probes, cells: int, options: api.ProbeVisibility, batches: int = 1, jitter=None):
+    """The visibility maps of P probes (float32 [P, 8] in HBM: api.POINT_DTYPE records) -> map float32 [P, texels * texels, 4] in HBM: probe_rays -> intersect ->
+    probe_visibility, all on the current torch stream. jitter None: the cell-centre rays, once (the distances are exact: further batches would add the same sums
+    again, so `batches` must be 1). jitter = an int seed: every batch draws a fresh jitter array the way bake_probes does (torch.rand of [cells * cells, 2] from a
+    device generator with that seed) and adds its sums to the map."""
+    import torch
+    if batches < 1:
+        raise TerraAmdError("bake_probe_visibility: batches must be at least 1")
+    n = _records(probes, 8, "bake_probe_visibility probes")
+    if jitter is None:
+        if batches != 1:
+            raise TerraAmdError("bake_probe_visibility: batches > 1 needs a jitter seed (the cell-centre rays give the same distances every time)")
+        rays = probe_rays(lib, probes, cells)
+        return probe_visibility(lib, intersect(lib, scene, rays.view(-1, 8)), rays, cells, options)
+    gen = torch.Generator(device=probes.device)
+    gen.manual_seed(int(jitter))
+    vis_map = None
+    for _ in range(batches):
+        rays = probe_rays(lib, probes, cells, torch.rand((cells * cells, 2), generator=gen, dtype=torch.float32, device=probes.device))
+        vis_map = probe_visibility(lib, intersect(lib, scene, rays.view(-1, 8)), rays, cells, options, map=vis_map)
+    return vis_map
 
 
 def render_device_sharded(lib, cam, scene, fb: DeviceFramebuffer, tile: int, rank: int, world: int, stream=None):

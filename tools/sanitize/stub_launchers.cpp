@@ -53,3 +53,5 @@ hipError_t terra_launch_dilate ( float*, int, int*, uint32_t, uint32_t, int, hip
 hipError_t terra_launch_probe_rays ( const void*, uint32_t, uint32_t, const float*, void*, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_launch_sh_project ( const void*, const void*, uint32_t, uint32_t, int, void*, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_launch_sh_irradiance ( const void*, uint32_t, const DevProbeGrid&, const void*, const int*, uint32_t, void*, hipStream_t ) { return hipErrorNoDevice; }
+hipError_t terra_launch_probe_visibility ( const void*, const void*, uint32_t, uint32_t, const DevProbeVisibility&, int, void*, hipStream_t ) { return hipErrorNoDevice; }
+hipError_t terra_launch_sh_irradiance_visible ( const void*, const void*, const DevProbeGrid&, const DevProbeVisibility&, const void*, uint32_t, void*, hipStream_t ) { return hipErrorNoDevice; }
