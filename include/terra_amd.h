@@ -1185,6 +1185,9 @@ int terra_amd_unit_trace ( HTerraScene scene, int n, const float* origins3, cons
 /* BSDF presets (src/TerraPresets.c:34-146). kind: 0 diffuse, 1 phong, 2 GGX, 3 glass (the last two are
    this library's own definitions, TerraPresets.h). surfaces47 in/out (Phong and glass write scratch slots). Per item: e[3], wo[3] -> wi[3], pdf, f[3] (pdf/eval at the sampled wi) */
 int terra_amd_unit_bsdf ( int kind, int n, float* surfaces47, const float* e3, const float* wo3, float* wi3, float* pdf, float* f3 );
+/* The same presets' pdf and eval at a GIVEN pair of directions, no sample first: what the Direct and Direct + MIS integrators ask at a light's direction.
+   surfaces47 is read only: Phong reads slot 3 and glass slots 2, 3 (the scratch a sample left) as handed in. Per item: wi[3], wo[3] -> pdf, f[3]. n > 0. */
+int terra_amd_unit_bsdf_at ( int kind, int n, const float* surfaces47, const float* wi3, const float* wo3, float* pdf, float* f3 );
 /* camera (src/Terra.c:1770-1799): dirs3 in world space for pixel (x,y), jitter, r1, r2 */
 int terra_amd_unit_camera ( const TerraCamera* camera, size_t fb_width, size_t fb_height, int n, const uint32_t* xy2, float jitter, const float* r2, float* dirs3 );
 /* tonemap (src/Terra.c:578-627): colors3 in place */

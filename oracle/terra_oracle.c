@@ -818,7 +818,7 @@ static TerraFloat3 phong_eval ( const TerraShadingSurface* sf, const TerraFloat3
 void orc_bsdf_phong_init ( TerraBSDF* b ) { b->sample = phong_sample; b->pdf = phong_pdf; b->eval = phong_eval; }
 
 /* ------------------------------------------------------------------------- */
-/* A14: GGX conductor and dielectric glass -- NO LIVE REFERENCE ("parity unpinned").     */
+/* A14: GGX conductor and dielectric glass -- NO LIVE REFERENCE; tests/presets_ref.py.   */
 /* Defined by this repo (include/TerraPresets.h) from the building blocks of the         */
 /* reference's dead code (src/TerraPresets.c:303-320 D and G1, :333-343 half-vector       */
 /* sampling, :399-449 Snell / TIR / Schlick). Only + - * / sqrt and the pinned sinf/cosf. */
@@ -844,7 +844,7 @@ static TerraFloat3 ggx_sample ( const TerraShadingSurface* sf, float e1, float e
     float alpha = sf->attributes[TERRA_GGX_ROUGHNESS].x;
     float t2 = alpha * alpha * e1 / ( 1.f - e1 );                /* tan^2(theta_h), :337 without the atan */
     float cos_t = 1.f / sqrtf ( 1.f + t2 );
-    float sin_t = sqrtf ( sel_max ( 0.f, 1.f - cos_t * cos_t ) );
+    float sin_t = sqrtf ( t2 ) * cos_t;                          /* tan * cos: sqrt ( 1 - cos_t^2 ) cancels (absolute error ~2^-11.5 whatever alpha) */
     float phi = 2 * terra_PI * e2;
     v3 h = v3_set ( sin_t * orc_math_cosf ( phi ), cos_t, sin_t * orc_math_sinf ( phi ) );
     h = v3_norm ( m3_apply ( &sf->transform, h ) );
@@ -855,7 +855,7 @@ static float ggx_pdf ( const TerraShadingSurface* sf, const TerraFloat3* wi, con
     float alpha = sf->attributes[TERRA_GGX_ROUGHNESS].x;
     v3 h = v3_norm ( v3_add ( *wi, *wo ) );
     float NoH = v3_dot ( sf->normal, h ), HoV = v3_dot ( h, *wo );
-    if ( HoV <= 0.f ) return 0.f;
+    if ( ! ( HoV > 0.f ) ) return 0.f;                           /* wi = -wo (the sampler's clamp) makes h = norm ( 0 ) = NaN: NaN takes this branch */
     return ggx_D ( NoH, alpha * alpha ) * NoH / ( 4.f * HoV );
 }
 static TerraFloat3 ggx_eval ( const TerraShadingSurface* sf, const TerraFloat3* wi, const TerraFloat3* wo ) {
@@ -864,7 +864,7 @@ static TerraFloat3 ggx_eval ( const TerraShadingSurface* sf, const TerraFloat3* 
     if ( NoL <= 0.f || NoV <= 0.f ) return v3_set ( 0, 0, 0 );
     v3 h = v3_norm ( v3_add ( *wi, *wo ) );
     float NoH = v3_dot ( sf->normal, h ), HoV = sel_max ( 0.f, v3_dot ( h, *wo ) );
-    float m = 1.f - HoV, m2 = m * m, w5 = m2 * m2 * m;          /* Schlick weight */
+    float m = sel_max ( 0.f, 1.f - HoV ), m2 = m * m, w5 = m2 * m2 * m;          /* Schlick weight; h.wo can round above 1 (wo = n = wi): never negative */
     v3 F0 = sf->attributes[TERRA_GGX_F0];
     v3 F = v3_set ( F0.x + ( 1.f - F0.x ) * w5, F0.y + ( 1.f - F0.y ) * w5, F0.z + ( 1.f - F0.z ) * w5 );
     float G = ggx_G1 ( *wo, sf->normal, h, alpha2 ) * ggx_G1 ( *wi, sf->normal, h, alpha2 );
@@ -883,7 +883,8 @@ static TerraFloat3 glass_sample ( const TerraShadingSurface* sf, float e1, float
     else { n1 = terra_ior_air; n2 = sf->ior; cos_i = -cos_i; }
     v3 refl = v3_sub ( incident, v3_scale ( normal, 2 * v3_dot ( normal, incident ) ) );
     float nni = n1 / n2;
-    float cos_t2 = 1.f - nni * nni * ( 1.f - cos_i * cos_i );
+    float nni2 = nni * nni;
+    float cos_t2 = ( 1.f - nni2 ) + nni2 * ( cos_i * cos_i );    /* = 1 - nni^2 ( 1 - cos_i^2 ) without rounding 1 - cos_i^2 to 1 at grazing incidence (ior 1: exactly cos_i^2) */
     v3 dir; float prob;
     if ( cos_t2 < 0.f ) { dir = refl; prob = 1.f; }                                      /* total internal reflection, :424-427 */
     else {
@@ -912,7 +913,9 @@ static TerraFloat3 glass_eval ( const TerraShadingSurface* sf, const TerraFloat3
     ( void ) wo;
     if ( !glass_is_sampled ( sf, wi ) ) return v3_set ( 0, 0, 0 );
     /* terra_trace multiplies eval/pdf by the SIGNED dot(n, wi): divide it out so the path weight is the tint */
-    float k = sf->attributes[TERRA_GLASS_SAMPLE_PROB].x / v3_dot ( sf->normal, *wi );
+    float c = v3_dot ( sf->normal, *wi );
+    if ( c == 0.f ) return v3_set ( 0, 0, 0 );     /* a direction in the surface's plane (wo tangent; refraction at exactly the critical angle): the path dies, no inf * 0 */
+    float k = sf->attributes[TERRA_GLASS_SAMPLE_PROB].x / c;
     return v3_scale ( sf->attributes[TERRA_GLASS_TINT], k );
 }
 void orc_bsdf_glass_init ( TerraBSDF* b ) { b->sample = glass_sample; b->pdf = glass_pdf; b->eval = glass_eval; }

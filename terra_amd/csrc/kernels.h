@@ -143,6 +143,7 @@ hipError_t terra_unit_raycast ( const DevScene& sc, int n, const float* o, const
 hipError_t terra_unit_trace ( const DevScene& sc, int integrator, uint32_t bounces, int n, const float* o, const float* d,
                               const uint64_t* stateB, const uint64_t* incB, float* radiance, uint32_t* rand_calls );
 hipError_t terra_unit_bsdf ( int kind, int n, float* surfaces47, const float* e3, const float* wo3, float* wi3, float* pdf, float* f3 );
+hipError_t terra_unit_bsdf_at ( int kind, int n, const float* surfaces47, const float* wi3, const float* wo3, float* pdf, float* f3 );
 hipError_t terra_unit_camera ( const DevRenderParams& p, int n, const uint32_t* xy2, const float* r2, float* dirs3 );
 // lens_sample on arrays: r4[n][4] = (r1, r2, l1, l2); rays8[n][8] = TerraAmdRay records (tmax FLT_MAX, reserved 0). p: the camera fields, jitter and frame size
 hipError_t terra_unit_lens_rays ( const DevRenderParams& p, const DevLens& lens, int n, const uint32_t* xy2, const float* r4, float* rays8 );

@@ -3258,6 +3258,14 @@ extern "C" int terra_amd_unit_bsdf ( int kind, int n, float* surfaces47, const f
     auto wi = u.out ( wi3, 3 * ( size_t ) n ); auto pd = u.out ( pdf, n ); auto f = u.out ( f3, 3 * ( size_t ) n );
     return u.finish ( u.ok ? terra_unit_bsdf ( kind, n, sf, e, wo, wi, pd, f ) : hipSuccess );
 }
+extern "C" int terra_amd_unit_bsdf_at ( int kind, int n, const float* surfaces47, const float* wi3, const float* wo3, float* pdf, float* f3 ) {
+    if ( need_device() ) return kTerraAmdErrNoDevice;
+    if ( kind < kDevBsdfDiffuse || kind > kDevBsdfGlass ) return fail ( kTerraAmdErrBadArgument, "unknown bsdf kind %d", kind );
+    if ( n <= 0 || !surfaces47 || !wi3 || !wo3 || !pdf || !f3 ) return fail ( kTerraAmdErrBadArgument, "terra_amd_unit_bsdf_at: null array or no items" );
+    Unit u; auto sf = u.in ( surfaces47, 47 * ( size_t ) n ); auto wi = u.in ( wi3, 3 * ( size_t ) n ); auto wo = u.in ( wo3, 3 * ( size_t ) n );
+    auto pd = u.out ( pdf, n ); auto f = u.out ( f3, 3 * ( size_t ) n );
+    return u.finish ( u.ok ? terra_unit_bsdf_at ( kind, n, sf, wi, wo, pd, f ) : hipSuccess );
+}
 extern "C" int terra_amd_unit_camera ( const TerraCamera* cam, size_t fb_w, size_t fb_h, int n, const uint32_t* xy2, float jitter, const float* r2, float* dirs3 ) {
     if ( need_device() ) return kTerraAmdErrNoDevice;
     DevRenderParams p; memset ( &p, 0, sizeof p );

@@ -332,7 +332,7 @@ TD V3 ggx_sample ( const Surface& sf, float e1, float e2, V3 wo, const Azimuth& 
     float alpha = sf.attr[1].x;
     float t2 = alpha * alpha * e1 / ( 1.f - e1 );
     float cos_t = 1.f / sqrt_exact ( 1.f + t2 );
-    float sin_t = sqrt_exact ( sel_max ( 0.f, 1.f - cos_t * cos_t ) );
+    float sin_t = sqrt_exact ( t2 ) * cos_t;            // tan * cos: sqrt ( 1 - cos_t^2 ) cancels (absolute error ~2^-11.5 whatever alpha)
     float sn, cs;
     azimuth_sincos ( az, e2, sn, cs );
     V3 h = v3 ( sin_t * cs, cos_t, sin_t * sn );
@@ -344,7 +344,7 @@ TD float ggx_pdf ( const Surface& sf, V3 wi, V3 wo ) {
     float alpha = sf.attr[1].x;
     V3 h = normalize ( wi + wo );
     float NoH = dot ( sf.normal, h ), HoV = dot ( h, wo );
-    if ( HoV <= 0.f ) return 0.f;
+    if ( ! ( HoV > 0.f ) ) return 0.f;                  // wi = -wo (the sampler's clamp) makes h = normalize ( 0 ) = NaN: NaN takes this branch
     return ggx_D ( NoH, alpha * alpha ) * NoH / ( 4.f * HoV );
 }
 TD V3 ggx_eval ( const Surface& sf, V3 wi, V3 wo ) {
@@ -353,7 +353,7 @@ TD V3 ggx_eval ( const Surface& sf, V3 wi, V3 wo ) {
     if ( NoL <= 0.f || NoV <= 0.f ) return v3 ( 0, 0, 0 );
     V3 h = normalize ( wi + wo );
     float NoH = dot ( sf.normal, h ), HoV = sel_max ( 0.f, dot ( h, wo ) );
-    float m = 1.f - HoV, m2 = m * m, w5 = m2 * m2 * m;
+    float m = sel_max ( 0.f, 1.f - HoV ), m2 = m * m, w5 = m2 * m2 * m;            // h.wo can round above 1 (wo = n = wi): no negative Schlick weight
     V3 F0 = sf.attr[0];
     V3 F = v3 ( F0.x + ( 1.f - F0.x ) * w5, F0.y + ( 1.f - F0.y ) * w5, F0.z + ( 1.f - F0.z ) * w5 );
     float G = ggx_G1 ( wo, sf.normal, h, alpha2 ) * ggx_G1 ( wi, sf.normal, h, alpha2 );
@@ -367,7 +367,8 @@ TD V3 glass_sample ( Surface& sf, float e3, V3 wo ) {
     else { n1 = 1.f; n2 = sf.ior; cos_i = -cos_i; }
     V3 refl = incident - normal * ( 2 * dot ( normal, incident ) );
     float nni = n1 / n2;
-    float cos_t2 = 1.f - nni * nni * ( 1.f - cos_i * cos_i );
+    float nni2 = nni * nni;
+    float cos_t2 = ( 1.f - nni2 ) + nni2 * ( cos_i * cos_i );      // = 1 - nni^2 ( 1 - cos_i^2 ) without rounding 1 - cos_i^2 to 1 at grazing incidence (ior 1: exactly cos_i^2)
     V3 dir; float prob;
     if ( cos_t2 < 0.f ) { dir = refl; prob = 1.f; }
     else {
@@ -390,7 +391,9 @@ TD bool glass_is_sampled ( const Surface& sf, V3 wi ) {
 TD float glass_pdf ( const Surface& sf, V3 wi ) { return glass_is_sampled ( sf, wi ) ? sf.attr[3].x : 0.f; }
 TD V3 glass_eval ( const Surface& sf, V3 wi ) {
     if ( !glass_is_sampled ( sf, wi ) ) return v3 ( 0, 0, 0 );
-    float k = sf.attr[3].x / dot ( sf.normal, wi );
+    float c = dot ( sf.normal, wi );
+    if ( c == 0.f ) return v3 ( 0, 0, 0 );         // a direction in the surface's plane (wo tangent; refraction at exactly the critical angle): the path dies, no inf * 0
+    float k = sf.attr[3].x / c;
     return sf.attr[0] * k;
 }
 

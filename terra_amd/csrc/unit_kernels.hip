@@ -236,6 +236,27 @@ hipError_t terra_unit_bsdf ( int kind, int n, float* surfaces47, const float* e3
     return hipGetLastError();
 }
 
+// pdf and eval at a GIVEN pair of directions, no sample first (what Direct and Direct + MIS do at a light's direction). The surfaces are read only:
+// Phong reads its slot 3 and glass its slots 2, 3 (the scratch a sample left) as handed in
+__global__ void k_bsdf_at ( int kind, int n, const float* surfaces47, const float* wi3, const float* wo3, float* pdf, float* f3 ) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if ( i >= n ) return;
+    const float* q = surfaces47 + 47 * ( size_t ) i;
+    Surface sf;
+    sf.normal = v3p ( q + 16 ); sf.emissive = v3p ( q + 19 );
+    for ( int a = 0; a < 4; ++a ) sf.attr[a] = v3p ( q + 23 + 3 * a );
+    sf.bsdf = kind; sf.ior = q[22];
+    V3 wi = v3p ( wi3 + 3 * i ), wo = v3p ( wo3 + 3 * i );
+    float p = bsdf_pdf<TERRA_KINDS_ALL> ( sf, wi, wo );
+    V3 f = bsdf_eval<TERRA_KINDS_ALL> ( sf, wi, wo );
+    pdf[i] = p;
+    f3[3 * i] = f.x; f3[3 * i + 1] = f.y; f3[3 * i + 2] = f.z;
+}
+hipError_t terra_unit_bsdf_at ( int kind, int n, const float* surfaces47, const float* wi3, const float* wo3, float* pdf, float* f3 ) {
+    hipLaunchKernelGGL ( k_bsdf_at, UNIT_GRID ( n ), 0, 0, kind, n, surfaces47, wi3, wo3, pdf, f3 );
+    return hipGetLastError();
+}
+
 __global__ void k_camera ( DevRenderParams p, int n, const uint32_t* xy2, const float* r2, float* dirs3 ) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if ( i >= n ) return;

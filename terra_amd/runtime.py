@@ -88,6 +88,7 @@ _EXTRA = {
     "terra_amd_get_environment_mis": (C.c_int, [C.c_void_p]),
     "terra_amd_unit_distribution_2d_pdf": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p]),
     "terra_amd_unit_azimuth24": (C.c_int, [C.POINTER(C.c_uint32)]),
+    "terra_amd_unit_bsdf_at": (C.c_int, [C.c_int, C.c_int] + [C.c_void_p] * 5),
     "terra_amd_get_frame_seed": (C.c_uint64, [C.c_void_p]),
     "terra_amd_set_tree_mode": (C.c_int, [C.c_void_p, C.c_int]),
     "terra_amd_get_tree_mode": (C.c_int, [C.c_void_p]),

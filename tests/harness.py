@@ -320,6 +320,30 @@ class Unit:
             surf[i] = np.frombuffer(bytes(s), dtype=np.float32)
         return wi, pdf, f, surf
 
+    def bsdf_at(self, kind_id, surfaces47, wi, wo):
+        """pdf and eval at a GIVEN (wi, wo), no sample first; the surfaces are read as handed in (glass and Phong: with the scratch a sample left). Returns pdf, f."""
+        n = len(wi)
+        surf = np.ascontiguousarray(surfaces47, np.float32); wi = np.ascontiguousarray(wi, np.float32); wo = np.ascontiguousarray(wo, np.float32)
+        assert surf.shape == (n, 47) and wi.shape == (n, 3) and wo.shape == (n, 3)
+        pdf = np.zeros(n, np.float32); f = np.zeros((n, 3), np.float32)
+        if self.kind == "amd":
+            before = surf.copy()
+            rc = self._f("bsdf_at", C.c_int, [C.c_int, C.c_int] + [C.c_void_p] * 5)(kind_id, n, surf.ctypes.data, wi.ctypes.data, wo.ctypes.data, pdf.ctypes.data, f.ctypes.data)
+            assert rc == 0, last_error()
+            assert same_bits(before, surf)
+            return pdf, f
+        b = api.TerraBSDF()
+        [self.L.bsdf_diffuse_init, self.L.bsdf_phong_init, getattr(self.L, "bsdf_ggx_init", None), getattr(self.L, "bsdf_glass_init", None)][kind_id](C.byref(b))
+        SP = C.POINTER(api.TerraShadingSurface)
+        fp = C.CFUNCTYPE(c_f, SP, F3P, F3P)(b.pdf)
+        fe = C.CFUNCTYPE(api.TerraFloat3, SP, F3P, F3P)(b.eval)
+        for i in range(n):
+            s = api.TerraShadingSurface.from_buffer_copy(surf[i].tobytes())
+            a, w = self._v(wi, i), self._v(wo, i)
+            pdf[i] = fp(C.byref(s), C.byref(a), C.byref(w))
+            f[i] = fe(C.byref(s), C.byref(a), C.byref(w)).tuple()
+        return pdf, f
+
     def camera_dirs(self, cam: api.TerraCamera, W, H, xy, jitter, r):
         """world-space primary directions (camera sample rotated by the camera frame)."""
         n = len(xy)
@@ -540,6 +564,160 @@ def bsdf_cases(seed, n, kind_id):
         flip[n // 2:] = ~flip[n // 2:]          # glass: half of the cases arrive from inside the medium
     wo[flip] = -wo[flip]
     return np.ascontiguousarray(surf), np.ascontiguousarray(e), np.ascontiguousarray(wo)
+
+
+AXIS_NORMALS = np.array([[0, 1, 0], [0, -1, 0], [1, 0, 0], [-1, 0, 0], [0, 0, 1], [0, 0, -1]], np.float32)
+U24_MAX = np.float32(1.0 - 2.0 ** -24)          # the largest stream-B variate
+
+
+def _u24(r, n):
+    return (r.randint(0, 2 ** 24, size=n).astype(np.float32) * np.float32(2.0 ** -24)).astype(np.float32)
+
+
+def _surfaces_of(nrm):
+    surf = np.zeros((len(nrm), 47), np.float32)
+    for i in range(len(nrm)):
+        surf[i, 0:16] = _basis(nrm[i])
+    surf[:, 16:19] = nrm
+    surf[:, 22] = 1.5
+    return surf
+
+
+def _normals(r, kinds):
+    """kinds < 6: that axis normal, exactly; otherwise a random unit vector"""
+    nrm = unit_dirs(r, len(kinds))
+    ax = kinds < 6
+    nrm[ax] = AXIS_NORMALS[kinds[ax]]
+    return nrm
+
+
+def _tangents(r, nrm):
+    """a random unit vector perpendicular to each normal, binary64"""
+    n = nrm.astype(np.float64)
+    v = r.normal(size=n.shape)
+    v -= np.einsum("nc,nc->n", v, n)[:, None] * n / np.einsum("nc,nc->n", n, n)[:, None]
+    return v / np.linalg.norm(v, axis=1, keepdims=True)
+
+
+def _at_cosine(nrm, tan, cos):
+    """the direction with n.d = cos in the plane of n and tan, rounded to binary32 once"""
+    cos = np.broadcast_to(np.asarray(cos, np.float64), (len(nrm),))
+    return (nrm.astype(np.float64) * cos[:, None] + tan * np.sqrt(1.0 - cos * cos)[:, None]).astype(np.float32)
+
+
+def _upper(r, nrm):
+    d = unit_dirs(r, len(nrm))
+    flip = np.einsum("nc,nc->n", d, nrm) < 0
+    d[flip] = -d[flip]
+    return d
+
+
+def _f0_of(r, n):
+    f0 = r.uniform(0, 1, size=(n, 3)).astype(np.float32)
+    k = r.randint(0, 3, size=n)
+    f0[k == 0] = 0; f0[k == 1] = 1
+    return f0
+
+
+GGX_EDGE_ALPHAS = (0.001, 0.005, 0.02, 0.1, 0.3, 1.0)
+GLASS_EDGE_IORS = (1.0, 1.0 + 2.0 ** -23, 0.75, 1.5, 2.4)
+
+
+def preset_edge_cases(kind_id):
+    """Edge inputs of the GGX (2) and glass (3) presets for Unit.bsdf: surfaces, variates, wo and a dict of per-row labels.
+
+    GGX, 5184 rows = alpha {0.001 .. 1} x e1 {0, 2^-24, k 2^-16 (k = 1 .. 50), 0.5, 1 - 2^-24} x e2 {0, 0.25, 1 - 2^-24, random u24}
+      x wo {exactly n, NoV ~ 1e-3, NoV ~ 0.2, random}; the normal is one of the six axes or random, F0 is 0, 1 or random. A drawn wo that lands within 1e-3 of
+      perpendicular to the half vector its row samples is drawn again (the clamp decision is ill-conditioned there).
+    Glass = ior {1, 1 + 2^-23, 0.75, 1.5, 2.4} x {outside, inside} x wo {+-n exactly, cos_i ~ 1e-3, ~ 1e-6, random} x twelve normals x e3 {0, 1 - 2^-24, 6 random u24};
+      then rows at cos_t2 = +-1e-3 about the critical angle (from inside; ior 0.75 from outside), then wo exactly tangent (labels["tangent"]).
+      Eight consecutive rows share everything but e3: labels["group"]."""
+    import presets_ref
+    r = rng(4100 + kind_id)
+    if kind_id == 2:
+        e1s = np.array([0.0, 2.0 ** -24] + [k * 2.0 ** -16 for k in range(1, 51)] + [0.5, float(U24_MAX)], np.float32)
+        A, E1, E2K, WOK = [x.reshape(-1) for x in np.meshgrid(np.array(GGX_EDGE_ALPHAS, np.float32), e1s, np.arange(4), np.arange(4), indexing="ij")]
+        n = len(A)
+        nrm = _normals(r, r.randint(0, 12, size=n))
+        surf = _surfaces_of(nrm)
+        surf[:, 23:26] = _f0_of(r, n)
+        surf[:, 26:29] = A[:, None]
+        e = np.stack([E1, np.select([E2K == 0, E2K == 1, E2K == 2], [np.float32(0), np.float32(0.25), U24_MAX], _u24(r, n)), _u24(r, n)], axis=1).astype(np.float32)
+        basis = presets_ref.basis_of(surf)
+
+        def draw(idx):
+            m = len(idx)
+            cand = [nrm[idx], _at_cosine(nrm[idx], _tangents(r, nrm[idx]), 1e-3), _at_cosine(nrm[idx], _tangents(r, nrm[idx]), 0.2), _upper(r, nrm[idx])]
+            return np.select([(WOK[idx] == k)[:, None] for k in range(3)], cand[:3], cand[3]).astype(np.float32)
+        wo = draw(np.arange(n))
+        for _ in range(8):
+            hv = presets_ref.ggx_sample(basis, A, e[:, 0], e[:, 1], wo)["HoV"]
+            again = np.flatnonzero((np.abs(hv) < 1e-3) & (WOK != 0))
+            if not len(again):
+                break
+            wo[again] = draw(again)
+        return np.ascontiguousarray(surf), np.ascontiguousarray(e), np.ascontiguousarray(wo), dict(alpha=A, wo_kind=WOK)
+    assert kind_id == 3
+    IOR, SIDE, WOK, NK = [x.reshape(-1) for x in np.meshgrid(np.array(GLASS_EDGE_IORS, np.float32), np.arange(2), np.arange(4), np.arange(12), indexing="ij")]
+    g = len(IOR)
+    nrm = _normals(r, NK)
+    cand = [nrm.copy(), _at_cosine(nrm, _tangents(r, nrm), 1e-3), _at_cosine(nrm, _tangents(r, nrm), 1e-6), _upper(r, nrm)]
+    wo = np.select([(WOK == k)[:, None] for k in range(3)], cand[:3], cand[3]).astype(np.float32)
+    wo[SIDE == 1] = -wo[SIDE == 1]
+    # about the critical angle: cos_t2 = 1 - nni^2 (1 - cos_i^2) = s * 1e-3  <=>  cos_i^2 = 1 - (1 - s * 1e-3) / nni^2
+    crit = [(ior, side, s, nk) for ior, side in ((GLASS_EDGE_IORS[1], 1), (1.5, 1), (2.4, 1), (0.75, 0)) for s in (1.0, -1.0) for nk in range(12)]
+    ior_c = np.array([c[0] for c in crit], np.float32); side_c = np.array([c[1] for c in crit]); s_c = np.array([c[2] for c in crit])
+    nni = np.where(side_c == 1, ior_c.astype(np.float64), 1.0 / ior_c.astype(np.float64))
+    c2 = 1.0 - (1.0 - s_c * 1e-3) / (nni * nni)
+    ok = (c2 > 0) & (c2 < 1)
+    ior_c, side_c, c2 = ior_c[ok], side_c[ok], c2[ok]
+    nrm_c = _normals(r, np.array([c[3] for c in crit])[ok])
+    wo_c = _at_cosine(nrm_c, _tangents(r, nrm_c), np.sqrt(c2))
+    wo_c[side_c == 1] = -wo_c[side_c == 1]
+    # wo exactly tangent: the next axis of each axis normal
+    nrm_t = np.repeat(AXIS_NORMALS, len(GLASS_EDGE_IORS), axis=0); wo_t = np.repeat(np.roll(AXIS_NORMALS, -2, axis=0), len(GLASS_EDGE_IORS), axis=0)
+    ior_t = np.tile(np.array(GLASS_EDGE_IORS, np.float32), 6)
+    nrm = np.concatenate([nrm, nrm_c, nrm_t]); wo = np.concatenate([wo, wo_c, wo_t]); ior = np.concatenate([IOR, ior_c, ior_t])
+    groups = len(nrm)
+    tint = r.uniform(0.5, 1, size=(groups, 3)).astype(np.float32)
+    e3 = np.concatenate([np.zeros((groups, 1), np.float32), np.full((groups, 1), U24_MAX, np.float32), _u24(r, groups * 6).reshape(groups, 6)], axis=1)
+    rep = lambda a: np.repeat(a, 8, axis=0)
+    surf = _surfaces_of(rep(nrm)); surf[:, 22] = rep(ior); surf[:, 23:26] = rep(tint)
+    e = np.stack([_u24(r, groups * 8), _u24(r, groups * 8), e3.reshape(-1)], axis=1).astype(np.float32)
+    labels = dict(wo_kind=rep(np.concatenate([WOK, np.full(groups - g, -1)])), group=np.repeat(np.arange(groups), 8), tangent=rep(np.arange(groups) >= groups - len(nrm_t)), critical=rep((np.arange(groups) >= g) & (np.arange(groups) < g + len(nrm_c))))
+    return np.ascontiguousarray(surf), np.ascontiguousarray(e), np.ascontiguousarray(rep(wo)), labels
+
+
+def ggx_at_cases(alpha, n=2048, extra=32):
+    """GGX surfaces and (wi, wo) pairs for Unit.bsdf_at where wi is NOT what the sampler produced: n / 2 rows with wi within ~3 alpha of the mirror direction, n / 2
+    with wi anywhere in the upper hemisphere, then `extra` rows with wi = -wo exactly and `extra` rows with wi below the horizon. One row in eight has wo = n exactly."""
+    r = rng(4200 + int(round(alpha * 1000)))
+    m = n + 2 * extra
+    nrm = _normals(r, r.randint(0, 12, size=m))
+    surf = _surfaces_of(nrm)
+    surf[:, 23:26] = _f0_of(r, m)
+    surf[:, 26:29] = np.float32(alpha)
+    wo = _upper(r, nrm)
+    wo[::8] = nrm[::8]
+    n64, wo64 = nrm.astype(np.float64), wo.astype(np.float64)
+    mirror = 2.0 * np.einsum("nc,nc->n", n64, wo64)[:, None] * n64 - wo64
+    near = mirror + 3.0 * float(alpha) * r.uniform(0, 1, size=(m, 1)) * unit_dirs(r, m).astype(np.float64)
+    wi = (near / np.linalg.norm(near, axis=1, keepdims=True)).astype(np.float32)
+    wi[n // 2:n] = _upper(r, nrm[n // 2:n])
+    wi[n:n + extra] = -wo[n:n + extra]
+    wi[n + extra:] = -_upper(r, nrm[n + extra:])
+    return np.ascontiguousarray(surf), np.ascontiguousarray(wi), np.ascontiguousarray(wo), dict(back=np.arange(m) >= n, opposite=(np.arange(m) >= n) & (np.arange(m) < n + extra))
+
+
+def ggx_plate_scene(roughness, integrator):
+    """Cornell-32 with one GGX plate (F0 0.9) under the light, seen from below: Direct + MIS evaluates the lobe's pdf at light directions and at the sampler's
+    clamped wi = -wo. 32 x 32, 8 spp."""
+    d = scenes.cornell_box(32, 32, 8, integrator=integrator)
+    plate = scenes._merge([scenes._quad((-0.6, 1.5, -0.8), (0.6, 1.5, -0.8), (0.6, 1.5, 0.3), (-0.6, 1.5, 0.3), (0, -1, 0))])
+    d.objects.append(scenes.ObjectDesc(*plate, scenes.Material(kind="ggx", specular_color=(0.9, 0.9, 0.9), roughness=roughness), "ggx_plate"))
+    d.camera_position = (0.0, 0.2, -1.0); d.camera_direction = (0.0, 1.79, 1.0)
+    d.name = "ggx_plate"
+    return d
 
 
 def _basis(n):

@@ -1,7 +1,7 @@
 """GGX conductor and dielectric glass (BASELINE.json config 4). The reference has no runnable
-form of either (dead code), so there is nothing to pin them to: "parity
-unpinned". These tests check the oracle's definitions for physical sanity on the CPU and
-(gpu) that the device reproduces the oracle bit for bit."""
+form of either (dead code): no reference behaviour; they are pinned to a binary64
+statement of this library's rule in tests/test_presets_ref.py. These tests check the oracle's
+definitions for physical sanity on the CPU and (gpu) that the device reproduces the oracle bit for bit."""
 import numpy as np
 import pytest
 
@@ -31,9 +31,17 @@ def test_glass_obeys_snell_and_weights_paths_by_the_tint(H, orc_lib):
     # total internal reflection never transmits
     tir = (cos_o < 0) & (ior * s_o > 1.0)
     assert tir.any() and refl[tir].all() and np.allclose(pdf[tir], 1.0)
-    # a delta lobe: any other direction has zero pdf and zero value
-    other = H.Unit("orc").bsdf(3, after, np.ones_like(e) * 0.5, wo)      # re-sample with e3 = 0.5 ...
-    assert (other[1] > 0).all()
+    # a delta lobe, evaluated (not re-sampled) on the surfaces the sample left: at the sampled direction pdf and f are the ones bsdf gave; at that direction with one
+    # component moved by 1 ulp, and at another direction, both are exactly 0
+    U = H.Unit("orc")
+    at = U.bsdf_at(3, after, wi, wo)
+    assert H.same_bits(at[0], pdf) and H.same_bits(at[1], f)
+    beside = wi.copy(); k = np.argmax(np.abs(wi), axis=1); rows = np.arange(len(wi))
+    beside[rows, k] = np.nextafter(wi[rows, k], np.float32(0))
+    for d in (beside, np.roll(wi, 1, axis=0)):
+        assert (d != wi).any(axis=1).all()
+        other = U.bsdf_at(3, after, d, wo)
+        assert not other[0].any() and not other[1].any()
 
 
 def test_ggx_is_a_reflection_lobe_with_bounded_energy(H, orc_lib):

@@ -21,6 +21,7 @@ hipError_t terra_unit_bvh_traverse ( const DevScene&, int, const float*, const f
 hipError_t terra_unit_raycast ( const DevScene&, int, const float*, const float*, int*, int*, float*, float* ) { return hipErrorNoDevice; }
 hipError_t terra_unit_trace ( const DevScene&, int, uint32_t, int, const float*, const float*, const uint64_t*, const uint64_t*, float*, uint32_t* ) { return hipErrorNoDevice; }
 hipError_t terra_unit_bsdf ( int, int, float*, const float*, const float*, float*, float*, float* ) { return hipErrorNoDevice; }
+hipError_t terra_unit_bsdf_at ( int, int, const float*, const float*, const float*, float*, float* ) { return hipErrorNoDevice; }
 hipError_t terra_unit_camera ( const DevRenderParams&, int, const uint32_t*, const float*, float* ) { return hipErrorNoDevice; }
 hipError_t terra_unit_tonemap ( int, float, int, float* ) { return hipErrorNoDevice; }
 hipError_t terra_unit_math ( int, int, const float*, const float*, float* ) { return hipErrorNoDevice; }
