@@ -1241,6 +1241,25 @@ int terra_amd_unit_distribution_2d_pdf ( const float* f, size_t nx, size_t ny, c
    entries into a second buffer of the same size (128 MB each, freed before the call returns) and sets *mismatches to the number of entries that differ in
    any bit -- 0 in a correct build */
 int terra_amd_unit_azimuth24 ( uint32_t* mismatches );
+/* The shading stages of the LDS-resident kernels without work counters (diffuse scenes, camera rays made in the kernel) against the guarded code they stand in
+   for. Such a kernel runs the short exact quotients and roots of a stage unguarded, ANDs the sites' range tests into one lane mask, takes one vote per wave and
+   computes the stage again with the guarded helpers where any lane failed. stage 1: the next ray's reciprocals; 2: a hit's barycentrics and normal; 3: the
+   continuation (BSDF sample, density, throughput, roulette). rows[count][16]: a stage's operands (stage 1: d[3]; 2: nu, nv, div, na[3], nb[3], nc[3]; 3: n[3],
+   albedo[3], throughput[3], the 24 bits of the first two variates as words, e3); 64 consecutive rows share a wave and its vote. staged[count][8] /
+   guarded[count][8]: the result words of the staged form and of the guarded code alone (stage 1: inv[3]; 2: u, v, normal[3]; 3: wi[3], throughput[3], 1.f where
+   the roulette lets the path live) -- equal bit for bit in a correct build. The guarded code of stage 3 is path_continue itself, and word 7 of its row holds
+   its nine sites' own range tests, a bit each (unit_kernels.hip lists them). mask[count]: 0 where the row failed a range test; full_mask[count]: the same
+   with the range tests made that `drops` != 0 (stages 1 and 3) leaves out because the render loop's data cannot fail them (stage 1 then takes no component of
+   8 or more in magnitude). stage 5: rows = fx, fy: the film vector ( fx, fy, 1 ) normalised without a range test, as a launch inside the camera limits
+   (terra_amd_shade_stage_info) normalises it, against the plain root and divisions: words = d[3].
+   stage 4: both roots of the diffuse sample on all 2^24 stream variates without their range tests against the guarded root; *mismatches = the offenders, 0 in a
+   correct build; the other pointers are not looked at. At most 2^24 rows. */
+/* Which ray start a render of this camera into a frame of this size takes in the kernels that shade in stages: *s1_guarded = 0 when
+   aspect * tan ( fov / 2 ) and tan ( fov / 2 ) lie in [2^-30, 2^20] and every entry of the camera's frame has a magnitude of at most 2 -- the camera sample is then
+   normalised, and the ray's reciprocals are taken, without the range tests such a launch cannot fail -- and 1 otherwise: the launch keeps every test. The frame
+   is the same either way. Host arithmetic only: no scene, no device. Fails on a null pointer or an empty frame. */
+int terra_amd_shade_stage_info ( const TerraCamera* cam, size_t fb_w, size_t fb_h, int* s1_guarded );
+int terra_amd_unit_shade_stages ( int stage, int drops, const float* rows, uint64_t count, uint32_t* staged, uint32_t* guarded, uint32_t* mask, uint32_t* full_mask, uint32_t* mismatches );
 /* terra_texture_sample (src/Terra.c:410-466) on the device at uv2[n][2], in texel units: out3[n][3]. The texture is uploaded the way terra_scene_commit
    uploads a scene's textures. Where the reference is undefined (components below 3 at the end of the data, 4 components, mirror addressing at a tile's
    first column or row, coordinates outside (-1, 2^32)) the result is this library's rule, which terra_texture_sample on the host follows too */

@@ -313,6 +313,10 @@ struct DevRenderParams {
     // sampler integration (terra_amd_set_sampler_integration; compiled into the KINDS & TERRA_KIND_SAMPLER variants only): 0 off, 1 Halton, 2 stratified
     // (`sampler_strata` strata per dimension, 16 samples per stratum: the sampler the reference constructs at src/Terra.c:542)
     uint32_t sampler_mode, sampler_strata;
+    // shading stages (exact_div.h "Shading stages"; the kernels of trace_geometry.h ray_start_masks_for): 1 = the launch's camera lies outside the limits for which
+    // the first stage may leave out range tests (terra_camera_stage_limits below), and it takes the guarded ray start, every site with its own test. fill_camera
+    // decides once per launch. (A 32-bit word in what was padding before job_live: the structure keeps its size and every field its offset.)
+    uint32_t shade_s1_guarded;
     // empty skip (render_kernels.hip "proved empty"): the job order ends with the blocks that empty_proof.h proved empty; *job_live = the jobs before them
     // (live blocks x split x 256, written by terra_block_order_kernel). Those blocks are never keyed, queued or traced: the resolve kernel adds their +0 sums.
     // nullptr: every block is live. (Last, so that the kernels that never read it keep their argument offsets.)
@@ -334,6 +338,17 @@ struct DevRenderParams {
     // stays where it was; a ray-sourced launch's ray pointer (DevRayRenderParams) moves 8 bytes up.
     float    inv_fb_w, inv_fb_h;
 };
+static_assert ( sizeof ( DevRenderParams ) == 576 && offsetof ( DevRenderParams, job_live ) == 544, "shade_s1_guarded sits in padding: no field of the launch parameters moved" );
+// The limits of DevRenderParams::shade_s1_guarded, checked once per launch where the camera is filled in (host code; plain C++): aspect * tan_half_fov and
+// tan_half_fov in [2^-30, 2^20] and every entry of the rotation of magnitude <= 2 (a NaN fails). Inside them, in trace_geometry.h camera_sample_staged: the film
+// vector ( fx, fy, 1 ) has a squared length in [1, 2^41] and a length in [1, 2^21]; fx and fy are 0 or no smaller than 2^-24 * 2^-30 * ( 1 - 2^-22 ) > 2^-60 (a
+// film coordinate 2 ndc - 1 is 0 or a multiple of 2^-24 near 0); and a rotated unit direction has components below 6 ( 1 + 2^-20 ).
+inline bool terra_camera_stage_limits ( float aspect, float tan_half_fov, const float* rot9 ) {
+    const float at = aspect * tan_half_fov;
+    bool ok = at >= 0x1p-30f && at <= 0x1p20f && tan_half_fov >= 0x1p-30f && tan_half_fov <= 0x1p20f;
+    for ( int i = 0; i < 9; ++i ) ok = ok && ( rot9[i] >= -2.f && rot9[i] <= 2.f );
+    return ok;
+}
 // masked launches (include/terra_amd.h "Masked rendering"; render_kernels.hip "masked launches"): which 16x16 pixel blocks of the rectangle a launch renders. A property
 // of the launch, beside its ray source, not a field of DevRenderParams: the small kernels around the render grid take its two pointers as arguments of their own, the
 // render kernels that key their streams ahead read DevRenderParams::job_live and the job table as they stand, and so no kernel-argument offset of any kernel moves

@@ -94,6 +94,16 @@ XD void xd_normalize3 ( float x, float y, float z, float l, float& qx, float& qy
 // denominator lies in [1e-4, 2^60 + 1e-4]: both v_div_scale pass their operand through, the numerator 1.0 makes q = y exactly, v_div_fmas applies no scale and
 // v_div_fixup meets no special operand -- what is left is the reciprocal, two Newton steps and the last correction e = 1 - d y, y + e y (Markstein's step), the same
 // operations on the same operands: 7 instructions. Any other pr (negative, huge, NaN) takes the plain expression. All 2^32 patterns: tests/test_exact_sqrt_gpu.py.
+// (its guard and its short arm on their own, for the shading stages below)
+XD int roulette_scale_ok ( float pr ) { return ( int ) ( pr >= 0.f ) & ( int ) ( pr <= 0x1p60f ); }
+XD float roulette_scale_short ( float pr ) {
+    const double d = ( double ) pr + 1e-4;
+    double y = __builtin_amdgcn_rcp ( d );
+    double e = __builtin_fma ( -d, y, 1.0 ); y = __builtin_fma ( y, e, y );
+    e = __builtin_fma ( -d, y, 1.0 ); y = __builtin_fma ( y, e, y );
+    e = __builtin_fma ( -d, y, 1.0 ); y = __builtin_fma ( e, y, y );
+    return ( float ) y;
+}
 XD float roulette_scale ( float pr ) {
     const double d = ( double ) pr + 1e-4;
     if ( ( int ) ( pr >= 0.f ) & ( int ) ( pr <= 0x1p60f ) ) {
@@ -105,3 +115,54 @@ XD float roulette_scale ( float pr ) {
     }
     return ( float ) ( 1.0 / d );
 }
+
+// ---- Shading stages (DESIGN.md 3.1 "Shading"): the kernels of trace_geometry.h ray_start_masks_for. A guarded helper above spends a branch per call site -- an exec
+// save, a conditional branch and a join around every short sequence. A STAGE (trace_math.h ray_stage, shading_device.h surface_stage, integrators_device.h
+// continue_stage) runs the short sequences of several sites unconditionally, ANDs the sites' guards -- the *_ok predicates of this file and of exact_sqrt.h -- into
+// one lane mask and takes ONE wave vote: where any lane of the wave failed any site, the whole stage is computed again, for the whole wave, by the guarded helpers,
+// before anything of it is used. A lane that passed every guard got from the short sequences the bits the guarded helpers return (they would have run those very
+// sequences); a lane that failed gets the guarded helpers' bits from the second run; a lane that passed in a wave that runs again gets the same bits twice. So the
+// second run needs no per-lane select. A short sequence on an operand outside its range returns some number or a NaN, traps nothing, and is never used.
+// A stage function is written once, over these site forms: SHORT = the short sequence, the guard ANDed into ok; otherwise "guard ? short : plain", the helper above.
+template <bool SHORT> XD float xd_site_rcp ( float d, int guard, int& ok ) {
+    if constexpr ( SHORT ) { ok &= guard; return xd_rcp_short ( d ); }
+    else { if ( guard ) return xd_rcp_short ( d ); return 1.f / d; }
+}
+template <bool SHORT> XD float xd_site_div_rk ( float x, float d, float r, int& ok ) {
+    if constexpr ( SHORT ) { ok &= xd_in_range ( x ); return xd_div_short ( x, d, r ); }
+    else return div_exact_rk ( x, d, r );
+}
+// The length of a vector that is nearly a unit vector -- an interpolated shading normal, a direction sampled about a wall's normal (where the reference's
+// unnormalised tangent frame happens to be orthonormal) -- is one of the few floats around 1, and 1 - 2^-24, whose
+// significand is all ones, is among them: three lengths in ten of random unit vectors, one in fifteen of a wall's interpolated normals (profiles/shade_stages/ab.md). Behind xd_normalize3's guard that is the plain
+// division's arm in some lane of nearly every wave. A stage takes the reciprocal of such a length by its closed form instead, and its guard leaves the significand
+// test out. For d = 2^k ( 2 - 2^-23 ): 1 / d = 2^-(k+1) ( 1 + 2^-24 + 2^-48 + .. ), a hair above the midpoint of 2^-(k+1) and its upper neighbour, so
+// RN ( 1 / d ) = 2^-(k+1) ( 1 + 2^-23 ): biased exponent 253 - E for d's E, significand 1 (normal whenever d is inside the guarded range). The quotients' theorem
+// (xd_div_short) asks for a correctly rounded reciprocal and excludes no significand. All 242 such d inside the range against 1.f / d: exhaustive. The quotients by them rest on
+// the theorem; the unit entry's stage 4 also holds 2^24 hashed numerators, no more than 2^20 below their denominator, to "/" -- a sample, not a proof.
+XD float xd_rcp_all_ones ( float d ) { return __uint_as_float ( ( 0x7e800000u - ( __float_as_uint ( d ) & 0x7f800000u ) ) | 1u | ( __float_as_uint ( d ) & 0x80000000u ) ); }
+XD float xd_rcp_short_any ( float d ) { return ( __float_as_uint ( d ) & 0x7fffffu ) == 0x7fffffu ? xd_rcp_all_ones ( d ) : xd_rcp_short ( d ); }
+XD int xd_normalize3_any_ok ( float x, float y, float z, float l ) {
+    return ( int ) ( l >= 0x1p-60f ) & ( int ) ( l <= 0x1p60f ) & xd_component_ok ( x ) & xd_component_ok ( y ) & xd_component_ok ( z );
+}
+template <bool SHORT> XD void xd_site_normalize3 ( float x, float y, float z, float l, float& qx, float& qy, float& qz, int& ok ) {
+    if constexpr ( SHORT ) {
+        ok &= xd_normalize3_any_ok ( x, y, z, l );
+        const float r = xd_rcp_short_any ( l );
+        qx = xd_div_short_pos ( x, l, r ); qy = xd_div_short_pos ( y, l, r ); qz = xd_div_short_pos ( z, l, r );
+    } else xd_normalize3 ( x, y, z, l, qx, qy, qz );
+}
+// Range tests that a stage's data cannot fail are not made there (DROPS in the stage functions; -DTERRA_SHADE_DROPS=0 keeps them all). The arguments:
+//  * the reciprocal of a clamped density, rcp_exact ( sel_max ( pdf, 1e-4f ) ): sel_max is "pdf > 1e-4f ? pdf : 1e-4f", so the operand is >= 1e-4f > 2^-60 and never a
+//    NaN (a NaN loses the comparison and the clamp returns 1e-4f). Only the upper bound and the significand test of xd_rcp_ok remain: xd_rcp_clamped_ok.
+//  * a component of the next ray's direction (trace_math.h ray_stage): xd_rcp_unit_ok, the lower bound (which a NaN fails) and the significand test, no upper
+//    bound. A camera direction is a normalised film vector rotated by a frame whose entries the host has checked to be at most 2 in magnitude (dev_types.h
+//    terra_camera_stage_limits): below 8. A continuation direction is a quotient c / l of a component by its vector's length, at most 1 + 2^-21 in magnitude
+//    whenever l > 0 (a denormal squared length has fewer bits, its root is still within a factor 1.5; l = inf gives 0 or a NaN). What is left is an infinity,
+//    from l = 0 beside a non-zero component: a vector shorter than 2^-75. The continuation's vector is the tangent frame applied to
+//    ( r cos, sqrt ( 1 - e ), r sin ) with sqrt ( 1 - e ) >= 2^-12, so along a normal n of roughly unit length it is at least 2^-13 long; and a normal that is
+//    NOT of roughly unit length came from a length of 0 or infinity, has zeros, infinities or NaNs for components, and puts a product 0 * inf or a difference
+//    inf - inf into every row of the frame: the vector is all NaN, or exactly zero (then 0 / 0), never tiny. tests/test_shade_stages_gpu.py holds that on
+//    degenerate normals: no direction the guarded continuation returns has an infinite component.
+XD int xd_rcp_unit_ok ( float d ) { return ( int ) ( __builtin_fabsf ( d ) >= 0x1p-60f ) & ( int ) ( ( __float_as_uint ( d ) & 0x7fffffu ) != 0x7fffffu ); }
+XD int xd_rcp_clamped_ok ( float d ) { return ( int ) ( d <= 0x1p60f ) & ( int ) ( ( __float_as_uint ( d ) & 0x7fffffu ) != 0x7fffffu ); }

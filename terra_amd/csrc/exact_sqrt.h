@@ -31,3 +31,13 @@ XD float sqrt_exact ( float x ) {
     if ( xs_in_range ( x ) ) return xs_sqrt_short ( x );
     return sqrtf ( x );
 }
+// the root as a site of a shading stage (exact_div.h "Shading stages"): SHORT = the short sequence, the guard ANDed into ok; otherwise sqrt_exact with that guard
+template <bool SHORT> XD float xs_site_sqrt ( float x, int guard, int& ok ) {
+    if constexpr ( SHORT ) { ok &= guard; return xs_sqrt_short ( x ); }
+    else { if ( guard ) return xs_sqrt_short ( x ); return sqrtf ( x ); }
+}
+// Roots of a stream-B variate e = k 2^-24, k < 2^24 (rng.h trng_b_from_bits), whose range tests the data cannot fail (the stages' DROPS):
+//  * sqrt ( e ): e is 0 or lies in [2^-24, 1 - 2^-24], far inside the guarded range: the guard is k != 0, one comparison (xs_variate_ok);
+//  * sqrt ( sel_max ( 0, 1 - e ) ): 1 - e is exact and lies in [2^-24, 1]: no test at all.
+// Both roots on all 2^24 variates against sqrt_exact: tests/test_shade_stages_gpu.py.
+XD int xs_variate_ok ( float e ) { return ( int ) ( e != 0.f ); }

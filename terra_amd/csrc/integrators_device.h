@@ -378,6 +378,7 @@ TD PathDraws path_draw ( const float2* sincos24, Pcg32& rb, Counters& c ) {
     d.e3 = randf ( rb, c, COUNT );
     return d;
 }
+// (restated for a diffuse surface in continue_stage below: a change here goes into both)
 template <int KINDS>
 TD bool path_continue ( Surface& sf, V3 wo, V3& throughput, uint32_t& bounce, uint32_t max_bounces, const PathDraws& d, V3& wi ) {
     wi = bsdf_sample<KINDS> ( sf, d.e0, d.e1, d.e2, wo, d.az );
@@ -388,6 +389,47 @@ TD bool path_continue ( Surface& sf, V3 wo, V3& throughput, uint32_t& bounce, ui
     float pr = sel_max ( throughput.x, sel_max ( throughput.y, throughput.z ) );
     if ( d.e3 > pr ) return false;
         throughput = throughput * roulette_scale ( pr );          // ( float ) ( 1.0 / ( ( double ) pr + 1e-4 ) ), bit for bit (exact_div.h)
+    ++bounce;
+    return bounce <= max_bounces;
+}
+// Stage S3 of the shading stages (exact_div.h "Shading stages"): path_continue<1> of a diffuse surface from the BSDF sample to the roulette's rescale, nine sites --
+// diffuse_sample's two roots, make_basis's root, the normalisation of wi (a root and the quotients), diffuse_pdf's quotient, rcp_exact ( pdf ), roulette_scale.
+// Same operations in the same order as path_continue<1>; the draws were made before (path_draw), so no stream moves when the stage runs twice. Nothing is committed
+// here: the outputs are wi, the new throughput t and go = "the roulette let the path live"; the caller writes them after its vote. Returns the lane's mask.
+// SHORT = false, DROPS = false: path_continue<1>'s own helpers, guard for guard. DROPS: d.e0 is a stream-B variate (exact_sqrt.h xs_variate_ok) and the
+// density is clamped (exact_div.h xd_rcp_clamped_ok); the direction wi keeps every test when it becomes the next ray (trace_math.h ray_stage). Kept: the tests of the tangent frame's and wi's roots and components, of diffuse_pdf's numerator
+// (a grazing wi makes it 0) and roulette_scale's bounds.
+template <bool SHORT, bool DROPS>
+TD int continue_stage ( V3 n, V3 albedo, V3 throughput, const PathDraws& d, V3& wi, V3& t, bool& go ) {
+    int ok = 1;
+    const float r = xs_site_sqrt<SHORT> ( d.e0, DROPS ? xs_variate_ok ( d.e0 ) : xs_in_range ( d.e0 ), ok );
+    float sn, cs;
+    azimuth_sincos ( d.az, d.e1, sn, cs );
+    const float x = r * cs, z = r * sn;
+    const float om = sel_max ( 0.f, 1 - d.e0 );
+    const float y = xs_site_sqrt<SHORT> ( om, DROPS ? 1 : xs_in_range ( om ), ok );
+    wi = normalize_site<SHORT> ( basis_apply ( make_basis_site<SHORT> ( n, ok ), v3 ( x, y, z ) ), ok );
+    const float pdf = sel_max ( xd_site_div_rk<SHORT> ( sel_max ( 0.f, dot ( n, wi ) ), TERRA_PI_F, TERRA_INV_PI_F, ok ), ( float ) 1e-4 );
+    const V3 f = ( albedo * ( float ) ( 1. / ( double ) TERRA_PI_F ) ) * xd_site_rcp<SHORT> ( pdf, DROPS ? xd_rcp_clamped_ok ( pdf ) : xd_rcp_ok ( pdf ), ok );
+    t = had ( throughput, f );
+    t = t * dot ( n, wi );
+    const float pr = sel_max ( t.x, sel_max ( t.y, t.z ) );
+    go = ! ( d.e3 > pr );
+    if constexpr ( SHORT ) {          // (a path the roulette ends keeps its throughput unscaled, as path_continue leaves it: t * 1.f is t)
+        ok &= roulette_scale_ok ( pr ) | ( int ) !go;
+        t = t * ( go ? roulette_scale_short ( pr ) : 1.f );
+    } else if ( go ) t = t * roulette_scale ( pr );
+    return ok;
+}
+// path_continue<1> for the kernels of ray_start_masks_for: the stage, one vote, the guarded helpers for a wave that holds a lane some guard turned away; then the commit
+TD bool path_continue_staged ( const Surface& sf, V3& throughput, uint32_t& bounce, uint32_t max_bounces, const PathDraws& d, V3& wi ) {
+    V3 t; bool go;
+    if constexpr ( TERRA_SHADE_STAGES != 0 ) {
+        if ( __any ( !continue_stage<true, TERRA_SHADE_DROPS != 0> ( sf.normal, sf.attr[0], throughput, d, wi, t, go ) ) )
+            continue_stage<false, false> ( sf.normal, sf.attr[0], throughput, d, wi, t, go );
+    } else continue_stage<false, TERRA_SHADE_DROPS != 0> ( sf.normal, sf.attr[0], throughput, d, wi, t, go );
+    throughput = t;
+    if ( !go ) return false;
     ++bounce;
     return bounce <= max_bounces;
 }

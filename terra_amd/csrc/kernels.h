@@ -129,6 +129,9 @@ hipError_t terra_launch_sh_irradiance_visible ( const void* sh, const void* map,
 hipError_t terra_fill_sincos24 ( float2* table, hipStream_t stream );    // DevScene::sincos24: 2^24 entries (128 MB), device pointer
 // table, computed: 2^24 entries each; *mismatches (zeroed by the caller) += the entries of table that tdm_azimuth24 does not reproduce bit for bit
 hipError_t terra_unit_azimuth24 ( const float2* table, float2* computed, uint32_t* mismatches );
+// the shading stages against the guarded code (unit_kernels.hip "the shading stages"): stage 1 - 3: n rows of 16 floats; staged, guarded: 8 words per row; mask, full_mask:
+// a word per row. stage 4: the variate roots, all 2^24; *mismatches (zeroed by the caller) += the offenders; the other pointers are not looked at
+hipError_t terra_unit_shade_stages ( int stage, int drops, const float* rows, uint64_t n, uint32_t* staged, uint32_t* guarded, uint32_t* mask, uint32_t* full_mask, uint32_t* mismatches );
 
 // unit-level launchers: all pointers are DEVICE pointers, n items, synchronous semantics left to the caller
 hipError_t terra_unit_pcg ( const uint32_t* seeds, int nseeds, int n, float* out );

@@ -557,7 +557,7 @@ TD bool ray_record_inactive ( const PrimaryRay& r ) {
 #define TERRA_JOB_NEXT() job_take<COUNT, MODE == 1> ( p, acc_lds, jb, rs, c, job_total, held )
 #else
 #define TERRA_LENS_RAY( ro, rd, r1, r2 )
-#define TERRA_PRIMARY_RAY( ro, rd, r1, r2 ) ro = cam_pos; rd = camera_sample ( p, jb.px, jb.py, r1, r2 )
+#define TERRA_PRIMARY_RAY( ro, rd, r1, r2 ) ro = cam_pos; rd = camera_direction<ray_start_masks_for ( COUNT, MODE, KINDS )> ( p, jb.px, jb.py, r1, r2 )
 #define TERRA_JOB_NEXT() job_next<COUNT, MODE == 1> ( p, acc_lds, jb, rs, c, job_total )
 #endif
 // job_next for the kernel's loops. Ray-sourced launches look at the new job's ray here, once per job: an inactive one ends the job where it starts -- its sum stays
@@ -804,7 +804,7 @@ __global__ __launch_bounds__ ( 256, terra_waves ( INTEGRATOR, KINDS, MODE ) ) vo
         }
         if ( alive ) {
             bool guarded = false;          // (make_ray's guard, for the kernels that make one range test per ray: trace_geometry.h)
-            if constexpr ( ray_start_masks_for ( COUNT, MODE, KINDS ) ) ray = make_ray_guarded ( ro, rd, guarded ); else
+            if constexpr ( ray_start_masks_for ( COUNT, MODE, KINDS ) ) ray = make_ray_staged ( ro, rd, guarded, p.shade_s1_guarded ); else
             ray = make_ray ( ro, rd );
             Surface sf;
             PS_WAVE ( c, kPsRayIter ); PS_LANE ( c, kPsRayLanes );
@@ -818,11 +818,13 @@ __global__ __launch_bounds__ ( 256, terra_waves ( INTEGRATOR, KINDS, MODE ) ) vo
                 // Direct on scenes whose emissive attributes are constants: the integrator is split at its shadow ray. Everything that does not depend on the ray's outcome --
                 // the light sample, both possible values of the integrator, then the continuation's draws, in the reference's order (src/Terra.c:1068-1079 after :1349-1426) --
                 // comes BEFORE the shadow traversal, so that the traversal runs with a pending pair and a continuation ray in registers instead of the whole shaded surface
+                constexpr bool STAGED = ray_start_masks_for ( COUNT, MODE, KINDS );          // the continuation as one stage with one fallback vote (integrators_device.h continue_stage); KINDS is 1 there: a diffuse surface, no sampler pair
                 constexpr bool SPLIT_DIRECT = INTEGRATOR == 1 && ( KINDS & ( TERRA_KIND_TEX | TERRA_KIND_SAMPLER ) ) == 0;
                 if constexpr ( SPLIT_DIRECT ) {
                     Ray shadow_ray;
                     const DirectPending pend = direct_prepare<COUNT, KINDS, MODE> ( T, sf, h.point, wo, throughput, bounce, rs.b, c, shadow_ray );
                     pd = path_draw<COUNT> ( azimuth_table<MODE> ( T.sc ), rs.b, c );
+                    if constexpr ( STAGED ) end = !path_continue_staged ( sf, throughput, bounce, p.bounces, pd, wi ); else
                     end = !path_continue<KINDS> ( sf, wo, throughput, bounce, p.bounces, pd, wi );
                     if ( !end ) { ro = surface_origin ( sf, h.point ); rd = wi; }
                     const uint32_t tri = scene_raycast_triangle<COUNT, MODE, ray_start_masks_for ( COUNT, MODE, KINDS )> ( T, shadow_ray, c, pend.expected );
@@ -833,6 +835,7 @@ __global__ __launch_bounds__ ( 256, terra_waves ( INTEGRATOR, KINDS, MODE ) ) vo
                     Ray ray_a; V3 b_d;
                     const MisPending pend = mis_prepare<COUNT, KINDS, MODE> ( T, sf, h.point, wo, throughput, bounce, rs.b, c, ray_a, b_d );
                     const V3 next_o = surface_origin ( sf, h.point );          // surface_ray ( sf, h.point, direction ) for B and for the continuation alike
+                    if constexpr ( STAGED ) { pd = path_draw<COUNT> ( azimuth_table<MODE> ( T.sc ), rs.b, c ); end = !path_continue_staged ( sf, throughput, bounce, p.bounces, pd, wi ); } else
                     end = !path_continue<COUNT, KINDS> ( T.sc, sf, wo, throughput, bounce, p.bounces, rs.b, c, wi, sp );
                     if ( !end ) { ro = next_o; rd = wi; }
                     const uint32_t tri_a = scene_raycast_triangle<COUNT, MODE, ray_start_masks_for ( COUNT, MODE, KINDS )> ( T, ray_a, c, pend.expected );
@@ -844,6 +847,7 @@ __global__ __launch_bounds__ ( 256, terra_waves ( INTEGRATOR, KINDS, MODE ) ) vo
                 lo_add ( integrate<INTEGRATOR, COUNT, MODE, KINDS> ( T, ray, sf, h.point, wo, throughput, bounce, rs.b, c ) );
                 if ( !pre_draw ) pd = path_draw<COUNT> ( azimuth_table<MODE> ( T.sc ), rs.b, c );
                 if constexpr ( ( KINDS & TERRA_KIND_SAMPLER ) != 0 ) path_apply_sampler ( pd, sp, bounce );
+                if constexpr ( STAGED ) end = !path_continue_staged ( sf, throughput, bounce, p.bounces, pd, wi ); else
                 end = !path_continue<KINDS> ( sf, wo, throughput, bounce, p.bounces, pd, wi );
                 if ( !end ) { ro = surface_origin ( sf, h.point ); rd = wi; }      // surface_ray ( sf, h.point, wi ): its make_ray is the one at the top of this block
                 }

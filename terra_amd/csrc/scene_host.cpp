@@ -1545,6 +1545,15 @@ static void fill_camera ( const TerraCamera* cam, size_t fb_w, size_t fb_h, DevR
     p.tan_half_fov = ( float ) tan ( ( double ) ( ( cam->fov * 0.0174533f ) / 2 ) );     // double tan of a float argument, src/Terra.c:1794
     p.aspect = ( float ) fb_w / ( float ) fb_h;
     p.inv_fb_w = 1.f / ( float ) fb_w; p.inv_fb_h = 1.f / ( float ) fb_h;          // correctly rounded (IEEE division): what camera_sample's div_exact_rk takes
+    p.shade_s1_guarded = terra_camera_stage_limits ( p.aspect, p.tan_half_fov, p.cam_rot ) ? 0u : 1u;      // (dev_types.h: the one check of the launch constants the first shading stage rests on)
+}
+// what fill_camera decides for a camera and a frame size, without a scene or a device
+extern "C" int terra_amd_shade_stage_info ( const TerraCamera* cam, size_t fb_w, size_t fb_h, int* s1_guarded ) {
+    if ( !cam || !s1_guarded || fb_w == 0 || fb_h == 0 ) return fail ( kTerraAmdErrBadArgument, "terra_amd_shade_stage_info: null camera or result, or an empty frame" );
+    DevRenderParams p; memset ( &p, 0, sizeof p );
+    fill_camera ( cam, fb_w, fb_h, p );
+    *s1_guarded = ( int ) p.shade_s1_guarded;
+    return 0;
 }
 
 // the scene can answer a call: committed since it last changed, and with a device replica
@@ -3332,6 +3341,23 @@ extern "C" int terra_amd_unit_exact_sqrt ( int op, const float* a, const float* 
     *mismatches = 0;
     unsigned long long* dm = reinterpret_cast<unsigned long long*> ( u.inout ( mismatches, 1 ) ); uint32_t* dr = u.out ( first_bad, 21 * 16 );
     return u.finish ( u.ok ? terra_unit_exact_sqrt ( op, da, db, dc, first, count, seed, dh, dp, dm, dr ) : hipSuccess );
+}
+
+// the shading stages of the LDS-resident kernels against the guarded code they stand in for (unit_kernels.hip "the shading stages")
+extern "C" int terra_amd_unit_shade_stages ( int stage, int drops, const float* rows, uint64_t count, uint32_t* staged, uint32_t* guarded, uint32_t* mask, uint32_t* full_mask, uint32_t* mismatches ) {
+    if ( need_device() ) return kTerraAmdErrNoDevice;
+    if ( stage < 1 || stage > 5 ) return fail ( kTerraAmdErrBadArgument, "shade_stages unit: stage %d is not one of 1 - 5", stage );
+    if ( stage == 4 ) {
+        if ( !mismatches ) return fail ( kTerraAmdErrBadArgument, "shade_stages unit: stage 4 needs a place for the mismatch count" );
+        *mismatches = 0;
+        Unit u; uint32_t* dm = u.inout ( mismatches, 1 );
+        return u.finish ( u.ok ? terra_unit_shade_stages ( 4, 0, nullptr, 0, nullptr, nullptr, nullptr, nullptr, dm ) : hipSuccess );
+    }
+    if ( count > ( 1ull << 24 ) || ( count && ( !rows || !staged || !guarded || !mask || !full_mask ) ) )
+        return fail ( kTerraAmdErrBadArgument, "shade_stages unit: stage %d needs its rows and four output arrays, at most 2^24 rows", stage );
+    const size_t n = ( size_t ) count;
+    Unit u; const float* dr = u.in ( rows, 16 * n ); uint32_t* ds = u.out ( staged, 8 * n ); uint32_t* dg = u.out ( guarded, 8 * n ); uint32_t* dk = u.out ( mask, n ); uint32_t* df = u.out ( full_mask, n );
+    return u.finish ( u.ok ? terra_unit_shade_stages ( stage, drops, dr, count, ds, dg, dk, df, nullptr ) : hipSuccess );
 }
 
 // binary16 planes of the fast tree's nodes (tree_build.cpp fastbvh::half_outward): host arithmetic, no device needed

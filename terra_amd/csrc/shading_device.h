@@ -72,7 +72,21 @@ struct Surface {
     int   bsdf;
 };
 
-template <int MODE, int KINDS>
+// Stage S2 of the shading stages (exact_div.h "Shading stages"): the hit's barycentrics from the triangle's staged constants (div2_exact with the denominator's
+// part done ahead: flag stands for xd_rcp_ok ( div ), rdiv for xd_rcp_short ( div )) and the interpolated normal's normalisation -- three sites. Returns the lane's
+// mask. SHORT = false: surface_init's own lines. No range test is left out here: a hit on an edge has nu == 0, a cancelled normal component can be arbitrarily small.
+template <bool SHORT> TD int surface_stage ( float nu, float nv, float div, float rdiv, int flag, V3 na, V3 nb, V3 nc, float& u, float& v, V3& normal ) {
+    int ok = 1;
+    const int g = flag & xd_in_range ( nu ) & xd_in_range ( nv );
+    if constexpr ( SHORT ) ok &= g;
+    if ( SHORT || g ) { u = xd_div_short ( nu, div, rdiv ); v = xd_div_short ( nv, div, rdiv ); }
+    else { u = nu / div; v = nv / div; }
+    const float w = 1 - u - v;
+    normal = normalize_site<SHORT> ( ( nc * v + nb * u ) + na * w, ok );
+    return ok;
+}
+// STAGED (the kernels of ray_start_masks_for, pair-form launches): u, v and the normal by surface_stage, one vote
+template <int MODE, int KINDS, bool STAGED = false>
 TD void surface_init ( const Tracer& T, uint32_t ti, V3 point, Surface& sf, uint32_t& object_out, uint32_t& tri_in_object_out, uint32_t& nattr_out ) {
     float4 t0, t1, t2, p0, p1, p2, p3x;
     if ( MODE == 1 ) {
@@ -97,6 +111,11 @@ TD void surface_init ( const Tracer& T, uint32_t ti, V3 point, Surface& sf, uint
         const float dp0 = dot ( p, e0 ), dp1 = dot ( p, e1 );
         const float nu = d11 * dp0 - d01 * dp1, nv = d00 * dp1 - d01 * dp0;
         // the flag word stands for xd_rcp_ok ( div ), c2.z for xd_rcp_short ( div ): div2_exact with its denominator's part done ahead
+        if constexpr ( STAGED ) {
+            const V3 na = v3 ( p0.x, p0.y, p0.z ), nb = v3 ( p0.w, p1.x, p1.y ), nc = v3 ( p1.z, p1.w, p2.x );
+            if ( __any ( !surface_stage<true> ( nu, nv, div, c2.z, ( int ) __float_as_uint ( c2.w ), na, nb, nc, u, v, sf.normal ) ) )
+                surface_stage<false> ( nu, nv, div, c2.z, ( int ) __float_as_uint ( c2.w ), na, nb, nc, u, v, sf.normal );
+        } else
         if ( ( int ) __float_as_uint ( c2.w ) & xd_in_range ( nu ) & xd_in_range ( nv ) ) { u = xd_div_short ( nu, div, c2.z ); v = xd_div_short ( nv, div, c2.z ); }
         else { u = nu / div; v = nv / div; }
     } else {
@@ -109,7 +128,7 @@ TD void surface_init ( const Tracer& T, uint32_t ti, V3 point, Surface& sf, uint
     }
     float w = 1 - u - v;
     V3 na = v3 ( p0.x, p0.y, p0.z ), nb = v3 ( p0.w, p1.x, p1.y ), nc = v3 ( p1.z, p1.w, p2.x );
-    sf.normal = normalize ( ( nc * v + nb * u ) + na * w );
+    if ( !STAGED || ! ( MODE == 1 && T.l_consts ) ) sf.normal = normalize ( ( nc * v + nb * u ) + na * w );          // (STAGED: the pair-form branch above has made it)
     const DevMaterial& m = T.l_mats[object];
     sf.emissive = v3p ( m.emissive );
     #pragma unroll
@@ -159,7 +178,7 @@ TD RaycastResult scene_raycast ( const Tracer& T, const Ray& in, Surface& sf, Co
     if ( res.hit ) {
         uint32_t nattr;
         if ( pre ) *pre = path_draw<COUNT> ( azimuth_table<MODE> ( T.sc ), *rb, c );
-        surface_init<MODE, KINDS> ( T, best.tri, res.point, sf, res.object, res.tri_in_object, nattr );
+        surface_init<MODE, KINDS, MASKS && TERRA_SHADE_STAGES != 0> ( T, best.tri, res.point, sf, res.object, res.tri_in_object, nattr );
         if ( MODE >= 2 ) res.tri = T.sc.mats[res.object].first_tri + res.tri_in_object;      // back to the soup index (lights, areas)
         if ( COUNT ) ++c.hits;
         if ( COUNT == 2 ) c.attr_fetches += nattr + 1;
@@ -262,6 +281,8 @@ TD void azimuth_sincos ( const Azimuth& az, float e, float& sn, float& cs ) {
     else tdm_sincosf_pair ( 2 * TERRA_PI_F * e, sn, cs );
 }
 
+// (diffuse_sample, diffuse_pdf, diffuse_eval and path_continue<1> are restated, operation for operation, in integrators_device.h continue_stage for the kernels that
+// shade in stages: a change of any of them goes into both. terra_amd_unit_shade_stages holds continue_stage to path_continue<1> itself, bit for bit.)
 TD V3 diffuse_sample ( const Surface& sf, float e1, float e2, const Azimuth& az ) {
     float r = sqrt_exact ( e1 );
     float sn, cs;

@@ -30,6 +30,21 @@ TD V3 camera_sample ( const DevRenderParams& p, uint32_t px, uint32_t py, float 
     return camera_rotate ( p, d );
 }
 
+// camera_sample for the kernels that shade in stages, in a launch whose constants passed terra_camera_stage_limits (dev_types.h: the bounds used here): the film
+// vector's normalisation without a range test. Its squared length is in [1, 2^41], inside the short root's range; its length in [1, 2^21] and its components 0
+// or above 2^-60, inside xd_normalize3's; a length whose significand is all ones takes the closed-form reciprocal (exact_div.h xd_rcp_all_ones). The film
+// quotients keep their test (with jitter 0.5 the numerator at px = 0 can be exactly 0). Same bits as camera_sample: the unit entry's stage 5 holds
+// camera_film_normalize to normalize_plain.
+TD V3 camera_film_normalize ( float fx, float fy ) {
+    const float l = xs_sqrt_short ( fx * fx + fy * fy + 1.f * 1.f ), r = xd_rcp_short_any ( l );
+    return v3 ( xd_div_short_pos ( fx, l, r ), xd_div_short_pos ( fy, l, r ), xd_div_short_pos ( 1.f, l, r ) );
+}
+TD V3 camera_sample_staged ( const DevRenderParams& p, uint32_t px, uint32_t py, float r1, float r2 ) {
+    if ( p.shade_s1_guarded || TERRA_SHADE_DROPS == 0 ) return camera_sample ( p, px, py, r1, r2 );          // (a launch constant: the branch is uniform)
+    float sx, sy; camera_film ( p, px, py, r1, r2, sx, sy );
+    return camera_rotate ( p, camera_film_normalize ( sx * p.aspect * p.tan_half_fov, sy * p.tan_half_fov ) );
+}
+
 // concentric map of a pair of draws to the unit disk (include/terra_amd.h "Lens rendering" spells it out): the thin lens's aperture sample and the point door's
 // cosine-weighted direction both take it
 TD void concentric_disk ( float l1, float l2, float& u, float& v ) {
@@ -254,6 +269,10 @@ TD RayStateMasks ray_start_masks ( const Ray& r, V3& o_perm ) {
 #define TERRA_RAY_START_CAMERA 1
 #endif
 TD constexpr bool ray_start_masks_for ( int COUNT, int MODE, int KINDS ) { return TERRA_RAY_START_CAMERA && MODE == 1 && COUNT == 0 && KINDS == 1; }
+// the camera sample of a render kernel: those kernels take the staged form (camera_sample_staged), every other one camera_sample
+template <bool STAGED> TD V3 camera_direction ( const DevRenderParams& p, uint32_t px, uint32_t py, float r1, float r2 ) {
+    if constexpr ( STAGED ) return camera_sample_staged ( p, px, py, r1, r2 ); else return camera_sample ( p, px, py, r1, r2 );
+}
 
 // the three vertices of a triangle record (three float4; the w components carry object, triangle in object, pad / rank)
 TD void tri_vertices ( float4 t0, float4 t1, float4 t2, V3& a, V3& b, V3& c ) { a = v3 ( t0.x, t0.y, t0.z ); b = v3 ( t1.x, t1.y, t1.z ); c = v3 ( t2.x, t2.y, t2.z ); }

@@ -28,7 +28,13 @@ TD float length ( V3 a ) { return sqrtf ( length2 ( a ) ); }          // (the pl
 // a / |a|: the short root of the squared length (exact_sqrt.h), then three quotients that share one refined reciprocal of the length (exact_div.h), each behind its
 // own guard; normalize_plain is the same function written with sqrtf and "/" (the unit entries compare them)
 TD V3 normalize_plain ( V3 a ) { float l = sqrtf ( length2 ( a ) ); return v3 ( a.x / l, a.y / l, a.z / l ); }
+// (normalize_site below restates normalize for the shading stages, make_basis_site restates make_basis: a change of either goes into both)
 TD V3 normalize ( V3 a ) { float l = sqrt_exact ( length2 ( a ) ); V3 r; xd_normalize3 ( a.x, a.y, a.z, l, r.x, r.y, r.z ); return r; }
+// normalize as two sites of a shading stage (exact_div.h "Shading stages"): SHORT = false is normalize itself
+template <bool SHORT> TD V3 normalize_site ( V3 a, int& ok ) {
+    const float l2 = length2 ( a ), l = xs_site_sqrt<SHORT> ( l2, xs_in_range ( l2 ), ok );
+    V3 r; xd_site_normalize3<SHORT> ( a.x, a.y, a.z, l, r.x, r.y, r.z, ok ); return r;
+}
 // compare-selects: exactly "a < b ? a : b" / "a > b ? a : b" (NaN-order sensitive)
 TD float sel_min ( float a, float b ) { return a < b ? a : b; }
 TD float sel_max ( float a, float b ) { return a > b ? a : b; }
@@ -70,6 +76,13 @@ TD Basis make_basis ( V3 n ) {
     const float k = sqrt_exact ( a * a + n.z * n.z );
     return basis_of ( v3 ( ( c ? n.z : 0.f ) * k, ( c ? 0.f : -n.z ) * k, ( c ? -n.x : n.y ) * k ), n );
 }
+// ... as a site of a shading stage: SHORT = false is make_basis itself
+template <bool SHORT> TD Basis make_basis_site ( V3 n, int& ok ) {
+    const bool c = fabsf ( n.x ) > fabsf ( n.y );
+    const float a = c ? n.x : n.y;
+    const float kk = a * a + n.z * n.z, k = xs_site_sqrt<SHORT> ( kk, xs_in_range ( kk ), ok );
+    return basis_of ( v3 ( ( c ? n.z : 0.f ) * k, ( c ? 0.f : -n.z ) * k, ( c ? -n.x : n.y ) * k ), n );
+}
 
 struct Ray { V3 o, d, inv; };
 TD Ray make_ray ( V3 o, V3 d ) { Ray r; r.o = o; r.d = d; rcp3_exact ( d.x, d.y, d.z, r.inv.x, r.inv.y, r.inv.z ); return r; }      // 1.f / d, bit for bit -- 1 / -0 = -inf included: a zero takes the plain division
@@ -82,6 +95,35 @@ TD Ray make_ray_guarded ( V3 o, V3 d, bool& guarded ) {
     guarded = ( xd_rcp_ok ( d.x ) & xd_rcp_ok ( d.y ) & xd_rcp_ok ( d.z ) ) != 0;
     if ( guarded ) { r.inv.x = xd_rcp_short ( d.x ); r.inv.y = xd_rcp_short ( d.y ); r.inv.z = xd_rcp_short ( d.z ); }
     else { r.inv.x = 1.f / d.x; r.inv.y = 1.f / d.y; r.inv.z = 1.f / d.z; }
+    return r;
+}
+// Stage S1 of the shading stages (exact_div.h "Shading stages"), the next ray's three reciprocals. Returns the lane's mask: every component passed its guard --
+// make_ray_guarded's `guarded`. SHORT: the short sequences run unguarded and the caller votes; otherwise make_ray_guarded's own lines. DROPS: d is a camera or
+// continuation direction of a launch whose constants passed terra_camera_stage_limits (dev_types.h), and its components need no upper bound (xd_rcp_unit_ok;
+// the argument stands beside it). `guarded` then still implies what the traversal entry derives from it (trace_geometry.h "One range test per ray"): the
+// component is normal with 2^-60 <= |d| < 8, its reciprocal lies in ( 2^-3, 2^60 ].
+#ifndef TERRA_SHADE_STAGES         // (A/B) 1: the kernels of ray_start_masks_for shade in stages, one fallback vote per stage; 0: every site keeps its own branch
+#define TERRA_SHADE_STAGES 1
+#endif
+#ifndef TERRA_SHADE_DROPS          // (A/B) 1: those kernels leave out the range tests their data cannot fail; 0: every site keeps its whole guard
+#define TERRA_SHADE_DROPS 1
+#endif
+template <bool SHORT, bool DROPS> TD int ray_stage ( V3 o, V3 d, Ray& r ) {
+    r.o = o; r.d = d;
+    const int ok = DROPS ? xd_rcp_unit_ok ( d.x ) & xd_rcp_unit_ok ( d.y ) & xd_rcp_unit_ok ( d.z ) : xd_rcp_ok ( d.x ) & xd_rcp_ok ( d.y ) & xd_rcp_ok ( d.z );
+    if ( SHORT || ok ) { r.inv.x = xd_rcp_short ( d.x ); r.inv.y = xd_rcp_short ( d.y ); r.inv.z = xd_rcp_short ( d.z ); }
+    else { r.inv.x = 1.f / d.x; r.inv.y = 1.f / d.y; r.inv.z = 1.f / d.z; }
+    return ok;
+}
+// the stage as the render loop runs it: one vote; a wave that holds a lane the guard turned away takes make_ray_guarded, all of it
+// s1_guarded: DevRenderParams::shade_s1_guarded, a launch constant -- a launch outside the camera limits keeps make_ray_guarded, every test with its own branch
+TD Ray make_ray_staged ( V3 o, V3 d, bool& guarded, uint32_t s1_guarded ) {
+    Ray r;
+    if ( s1_guarded ) return make_ray_guarded ( o, d, guarded );
+    if constexpr ( TERRA_SHADE_STAGES != 0 ) {
+        guarded = ray_stage<true, TERRA_SHADE_DROPS != 0> ( o, d, r ) != 0;
+        if ( __any ( !guarded ) ) r = make_ray_guarded ( o, d, guarded );
+    } else guarded = ray_stage<false, TERRA_SHADE_DROPS != 0> ( o, d, r ) != 0;
     return r;
 }
 

@@ -580,3 +580,114 @@ hipError_t terra_unit_azimuth24 ( const float2* table, float2* computed, uint32_
     hipLaunchKernelGGL ( k_azimuth24, dim3 ( ( 1u << 24 ) / 256u ), dim3 ( 256 ), 0, 0, table, computed, mismatches );
     return hipGetLastError();
 }
+
+// ---- the shading stages (exact_div.h "Shading stages") against the guarded code they stand in for (tests/test_shade_stages_gpu.py). One row of 16 floats per thread;
+// per row the stage as the render loop runs it -- the short sequences unguarded, one vote over the wave, the guarded code for the whole wave where a lane failed --
+// then the guarded code alone, and the stage's lane mask. 64 consecutive rows share a wave and a vote. Eight result words per row and form (unused ones 0):
+//   stage 1  ray_stage:       row = d[3]                                                    words = inv[3]                 guarded = make_ray_guarded
+//   stage 2  surface_stage:   row = nu, nv, div, na[3], nb[3], nc[3]                       words = u, v, normal[3]        guarded = surface_stage<false> (surface_init's lines)
+//   stage 3  continue_stage:  row = n[3], albedo[3], throughput[3], k0, k1 (words), e3     words = wi[3], t[3], go        guarded = path_continue<1> itself; its word 7: the sites' own guards, a bit each
+//            (k0, k1: the 24 bits of the first two variates; the azimuth is computed from k1 as a launch without a table does)
+//   stage 5  camera_film_normalize: row = fx, fy (a film vector ( fx, fy, 1 ) of a launch inside the camera limits)   words = d[3]   guarded = normalize_plain
+// DROPS (stages 1 and 3): the stage without the range tests its data cannot fail (stage 1: no component of 8 or more in magnitude). full_mask: the same
+// stage's mask with every range test made.
+template <int STAGE, bool DROPS>
+__global__ __launch_bounds__ ( 256 ) void k_shade_stages ( const float* rows, unsigned long long n, uint32_t* staged, uint32_t* guarded, uint32_t* mask, uint32_t* full_mask ) {
+    const unsigned long long i = blockIdx.x * 256ull + threadIdx.x;
+    if ( i >= n ) return;
+    const float* q = rows + 16 * i;
+    float s[8] = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f }, g[8] = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f };
+    int ok = 0, full = 0;
+    if constexpr ( STAGE == 1 ) {
+        const V3 o = v3 ( 0, 0, 0 ), d = v3p ( q );
+        Ray a, b, f; bool gd;
+        ok = ray_stage<true, DROPS> ( o, d, a ); full = ray_stage<true, false> ( o, d, f );
+        if ( __any ( !ok ) ) a = make_ray_guarded ( o, d, gd );
+        b = make_ray_guarded ( o, d, gd );
+        s[0] = a.inv.x; s[1] = a.inv.y; s[2] = a.inv.z; g[0] = b.inv.x; g[1] = b.inv.y; g[2] = b.inv.z;
+    } else if constexpr ( STAGE == 5 ) {          // the film vector's normalisation without a range test (trace_geometry.h camera_film_normalize): row = fx, fy
+        const V3 a = camera_film_normalize ( q[0], q[1] ), b = normalize_plain ( v3 ( q[0], q[1], 1.f ) );
+        ok = 1; full = 1;
+        s[0] = a.x; s[1] = a.y; s[2] = a.z; g[0] = b.x; g[1] = b.y; g[2] = b.z;
+    } else if constexpr ( STAGE == 2 ) {
+        const float nu = q[0], nv = q[1], div = q[2], rdiv = rcp_exact ( div ); const int flag = xd_rcp_ok ( div );          // (the constants as make_tracer stages them)
+        const V3 na = v3p ( q + 3 ), nb = v3p ( q + 6 ), nc = v3p ( q + 9 );
+        V3 ns, ng;
+        ok = surface_stage<true> ( nu, nv, div, rdiv, flag, na, nb, nc, s[0], s[1], ns ); full = ok;
+        if ( __any ( !ok ) ) surface_stage<false> ( nu, nv, div, rdiv, flag, na, nb, nc, s[0], s[1], ns );
+        surface_stage<false> ( nu, nv, div, rdiv, flag, na, nb, nc, g[0], g[1], ng );
+        s[2] = ns.x; s[3] = ns.y; s[4] = ns.z; g[2] = ng.x; g[3] = ng.y; g[4] = ng.z;
+    } else {
+        const V3 nrm = v3p ( q ), albedo = v3p ( q + 3 ), tp = v3p ( q + 6 );
+        const uint32_t k0 = __float_as_uint ( q[9] ) & 0xffffffu, k1 = __float_as_uint ( q[10] ) & 0xffffffu;
+        PathDraws d; d.e0 = trng_b_from_bits ( k0 ); d.e1 = trng_b_from_bits ( k1 ); d.e2 = 0.f; d.e3 = q[11]; d.az = azimuth_fetch_index ( nullptr, k1 );
+        V3 ws, ts, wg, tg, wf, tf; bool gs, gg, gf;
+        ok = continue_stage<true, DROPS> ( nrm, albedo, tp, d, ws, ts, gs ); full = continue_stage<true, false> ( nrm, albedo, tp, d, wf, tf, gf );
+        if ( __any ( !ok ) ) continue_stage<false, false> ( nrm, albedo, tp, d, ws, ts, gs );
+        // the guarded code: path_continue<1> itself, on a diffuse surface with this normal and albedo (it returns "the path lives" while the bounce limit is far)
+        Surface sf; sf.normal = nrm; sf.emissive = v3 ( 0, 0, 0 ); sf.attr[0] = albedo; sf.attr[1] = sf.attr[2] = sf.attr[3] = v3 ( 0, 0, 0 ); sf.ior = 1.f; sf.bsdf = kDevBsdfDiffuse;
+        uint32_t bounce = 0; tg = tp;
+        gg = path_continue<1> ( sf, v3 ( 0, 0, 1 ), tg, bounce, 1000u, d, wg );
+        // ... and its sites' own guards, one bit each, on the operands the plain helpers hand from site to site (diffuse_sample, make_basis, normalize, diffuse_pdf,
+        // rcp_exact, roulette_scale as shading_device.h / trace_math.h / exact_div.h write them): bit 0 the root of e0, 1 the root of 1 - e0, 2 make_basis's root,
+        // 3 the root of wi's squared length, 4 xd_normalize3's range tests of the length and the components, 5 its all-ones test of the length (which a stage does
+        // not make: exact_div.h xd_rcp_all_ones), 6 diffuse_pdf's numerator, 7 rcp_exact ( pdf ), 8 roulette_scale's bounds where the roulette lets the path live
+        {
+            uint32_t bits = 0;
+            const float r = sqrt_exact ( d.e0 ); float sn, cs; azimuth_sincos ( d.az, d.e1, sn, cs );
+            const float om = sel_max ( 0.f, 1 - d.e0 );
+            const V3 local = v3 ( r * cs, sqrt_exact ( om ), r * sn );
+            const float ba = fabsf ( nrm.x ) > fabsf ( nrm.y ) ? nrm.x : nrm.y;
+            const V3 v = basis_apply ( make_basis ( nrm ), local );
+            const float l2 = length2 ( v ), l = sqrt_exact ( l2 );
+            const V3 w = normalize ( v );
+            const float num = sel_max ( 0.f, dot ( nrm, w ) ), pdf = sel_max ( diffuse_pdf ( sf, w ), ( float ) 1e-4 );
+            V3 t = had ( tp, diffuse_eval ( sf ) * rcp_exact ( pdf ) ); t = t * dot ( nrm, w );
+            const float pr = sel_max ( t.x, sel_max ( t.y, t.z ) );
+            bits |= xs_in_range ( d.e0 ) ? 1u : 0u; bits |= xs_in_range ( om ) ? 2u : 0u; bits |= xs_in_range ( ba * ba + nrm.z * nrm.z ) ? 4u : 0u; bits |= xs_in_range ( l2 ) ? 8u : 0u;
+            bits |= ( ( int ) ( l >= 0x1p-60f ) & ( int ) ( l <= 0x1p60f ) & xd_component_ok ( v.x ) & xd_component_ok ( v.y ) & xd_component_ok ( v.z ) ) ? 16u : 0u;
+            bits |= ( __float_as_uint ( l ) & 0x7fffffu ) != 0x7fffffu ? 32u : 0u;
+            bits |= xd_in_range ( num ) ? 64u : 0u; bits |= xd_rcp_ok ( pdf ) ? 128u : 0u;
+            bits |= ( ( ( int ) ( pr >= 0.f ) & ( int ) ( pr <= 0x1p60f ) ) | ( int ) ( d.e3 > pr ) ) ? 256u : 0u;
+            g[7] = __uint_as_float ( bits );
+        }
+        s[0] = ws.x; s[1] = ws.y; s[2] = ws.z; s[3] = ts.x; s[4] = ts.y; s[5] = ts.z; s[6] = gs ? 1.f : 0.f;
+        g[0] = wg.x; g[1] = wg.y; g[2] = wg.z; g[3] = tg.x; g[4] = tg.y; g[5] = tg.z; g[6] = gg ? 1.f : 0.f;
+    }
+    for ( int j = 0; j < 8; ++j ) { staged[8 * i + j] = __float_as_uint ( s[j] ); guarded[8 * i + j] = __float_as_uint ( g[j] ); }
+    mask[i] = ( uint32_t ) ok; full_mask[i] = ( uint32_t ) full;
+}
+// stage 4: the two roots of diffuse_sample on every stream-B variate e = k 2^-24 without their range tests (exact_sqrt.h xs_variate_ok) against sqrt_exact:
+// *mismatches += the k whose short root of e differs from sqrt_exact ( e ) although the guard admits e, the k != 0 the guard refuses, and the k whose short root of
+// sel_max ( 0, 1 - e ) differs from sqrt_exact's; and the reciprocal of a length whose significand is all ones, below
+__global__ __launch_bounds__ ( 256 ) void k_variate_roots ( uint32_t* mismatches ) {
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;          // grid = 2^24 / 256 blocks
+    const float e = trng_b_from_bits ( k ), om = sel_max ( 0.f, 1 - e );
+    const bool admitted = xs_variate_ok ( e ) != 0;
+    uint32_t bad = 0;
+    if ( admitted && __float_as_uint ( xs_sqrt_short ( e ) ) != __float_as_uint ( sqrt_exact ( e ) ) ) ++bad;
+    if ( !admitted && k != 0u ) ++bad;
+    if ( __float_as_uint ( xs_sqrt_short ( om ) ) != __float_as_uint ( sqrt_exact ( om ) ) ) ++bad;
+    // the closed-form reciprocal of an all-ones significand (exact_div.h xd_rcp_all_ones): every such d inside the guarded range, both signs, against 1.f / d; and a
+    // numerator hashed from k over the positive ones -- at the denominator's size and up to 2^-20 of it, as a component is to its vector's length -- against "/"
+    const float d = __uint_as_float ( ( ( 67u + k % 121u ) << 23 ) | 0x7fffffu | ( ( k / 121u ) & 1u ) << 31 );
+    if ( k < 242u && __float_as_uint ( xd_rcp_all_ones ( d ) ) != __float_as_uint ( 1.f / d ) ) ++bad;
+    const float l = __builtin_fabsf ( d );
+    const uint32_t h = ( uint32_t ) xd_hash ( k );
+    const float x = __uint_as_float ( ( __float_as_uint ( l ) & 0x7f800000u ) - ( ( ( h >> 23 ) % 21u ) << 23 ) | ( h & 0x807fffffu ) );
+    if ( xd_in_range ( x ) && __float_as_uint ( xd_div_short_pos ( x, l, xd_rcp_short_any ( l ) ) ) != __float_as_uint ( x / l ) ) ++bad;
+    if ( bad ) atomicAdd ( mismatches, bad );
+}
+hipError_t terra_unit_shade_stages ( int stage, int drops, const float* rows, uint64_t n, uint32_t* staged, uint32_t* guarded, uint32_t* mask, uint32_t* full_mask, uint32_t* mismatches ) {
+    const dim3 grid ( ( unsigned ) ( ( n + 255 ) / 256 ) ), block ( 256 );
+#define SS_CASE(S, D) hipLaunchKernelGGL ( ( k_shade_stages<S, D> ), grid, block, 0, 0, rows, ( unsigned long long ) n, staged, guarded, mask, full_mask )
+    if ( stage == 4 ) hipLaunchKernelGGL ( k_variate_roots, dim3 ( ( 1u << 24 ) / 256u ), dim3 ( 256 ), 0, 0, mismatches );
+    else if ( n == 0 ) return hipSuccess;
+    else if ( stage == 1 ) { if ( drops ) SS_CASE ( 1, true ); else SS_CASE ( 1, false ); }
+    else if ( stage == 5 ) SS_CASE ( 5, false );
+    else if ( stage == 2 ) SS_CASE ( 2, false );
+    else if ( stage == 3 ) { if ( drops ) SS_CASE ( 3, true ); else SS_CASE ( 3, false ); }
+    else return hipErrorInvalidValue;
+#undef SS_CASE
+    return hipGetLastError();
+}

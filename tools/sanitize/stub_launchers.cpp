@@ -9,6 +9,7 @@ hipError_t terra_launch_job_streams ( const DevRenderParams&, hipStream_t ) { re
 hipError_t terra_launch_block_order ( const DevRenderParams&, uint32_t*, hipStream_t, const DevLaunchMask*, bool, bool ) { return hipErrorNoDevice; }
 hipError_t terra_fill_sincos24 ( float2*, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_unit_azimuth24 ( const float2*, float2*, uint32_t* ) { return hipErrorNoDevice; }
+hipError_t terra_unit_shade_stages ( int, int, const float*, uint64_t, uint32_t*, uint32_t*, uint32_t*, uint32_t*, uint32_t* ) { return hipErrorNoDevice; }
 hipError_t terra_launch_resolve ( const DevRenderParams&, hipStream_t, const uint32_t* ) { return hipErrorNoDevice; }
 hipError_t terra_launch_tiles ( bool, float*, void*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, float*, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_unit_pcg ( const uint32_t*, int, int, float* ) { return hipErrorNoDevice; }
