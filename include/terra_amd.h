@@ -1221,6 +1221,21 @@ int terra_amd_unit_exact_sqrt ( int op, const float* a, const float* b, const fl
 /* The plane values of the fast tree's nodes: x[i] rounded to binary16 towards -inf (up = 0) or +inf (up != 0), as bits -- so that a box of such planes
    contains the box it was made from (host arithmetic; no device needed) */
 int terra_amd_unit_half_outward ( const double* x, int n, int up, uint16_t* out );
+/* TESTS ONLY. The fast tree of a soup of n triangles (tris9[n][9]: a, b, c; taken as object 0, triangle i), from the builder itself: 0 = the host's binned SAH,
+   1 = the device LBVH (kTerraAmdErrNoDevice without a device; n <= 2 or n >= 2^27 is the builder's own invalid-argument error). rank[n] is what a commit would
+   put into the soup's `pad` words; every triangle box is grown by extra_margin (>= 0) on top of its 1e-4.
+   Out: bin_nodes = the binary tree as built, NOT verified and not repaired (64 bytes per node: min0[3] max0[3] min1[3] max1[3] child[2] prim[2]; *n_bin nodes),
+   order[k] / pad[k] = the soup index and the pad word of the triangle in leaf slot k, *bin_max_stack = the builder's own stack bound; wide_nodes = that tree as
+   the kernels read it, 4-wide with binary16 planes times `scale` (a power of two; 128 bytes per node, *n_wide nodes) and *wide_max_stack = the bound every
+   fast-tree launch is planned with. Capacities are in nodes; n + 1 of each always suffices. A failed call writes nothing. */
+int terra_amd_unit_fast_tree ( const float* tris9, const uint32_t* rank, uint32_t n, int builder, float extra_margin, float scale,
+                               void* bin_nodes, uint32_t bin_capacity, uint32_t* n_bin, uint32_t* order, uint32_t* pad, int* bin_max_stack,
+                               void* wide_nodes, uint32_t wide_capacity, uint32_t* n_wide, int* wide_max_stack );
+/* TESTS ONLY. The check a commit runs on a fast tree before anything traverses it, on a caller's binary tree (layout as above) and soup in LEAF order: *accepted = 1,
+   or 0 with the reason copied into `reason` (may be NULL). Refused: a child index out of range; a node reached twice (so also a child index that points back at
+   an ancestor: the check ends on any input); a leaf of more than 4 triangles; a leaf range past the soup; a triangle in more than one leaf or in none; a child
+   box that does not contain the triangle boxes below it. Host arithmetic, no device needed. */
+int terra_amd_unit_verify_fast_tree ( const void* bin_nodes, uint32_t n_nodes, const float* tris9_in_leaf_order, uint32_t n, float extra_margin, int* accepted, char* reason, size_t reason_capacity );
 /* SURVEY.md 8f N4, unit level. The reference constructs these samplers and never draws from them on the render path
    (src/Terra.c:535-548) and nothing calls its distributions; they are provided and pinned as stand-alone device functions.
    terra_sampler_stratified_next_pair (src/Terra.c:714-723) for one sampler per seed: out2[nseeds][n][2]; n <= strata^2 * samples_per_stratum */

@@ -622,12 +622,39 @@ static bool verify_reference_leaf_boxes ( const Scene* s, std::string& why ) {
     }
     return true;
 }
-// every child box of the fast tree contains the boxes of all triangles below it (what its culling relies on)
+// What a fast tree must be before anything traverses it. Structure: every node index in range and reached at most once (a visited bitmap, so a child index that
+// points back at an ancestor, at the root or at a node another parent already has is refused and the walk ends on any input), every leaf holds at most 4 triangles
+// (the leaf loop of traverse_fast.h is written for 4) and lies inside the soup, every slot of the soup lies in exactly one leaf. Boxes: every child box contains
+// the boxes of all triangles below it (what the culling relies on). O(nodes + triangles); each refusal has its own reason.
 static bool verify_fast_tree ( const std::vector<DevNode>& nodes, const std::vector<TerraAABB>& boxes_in_leaf_order, std::string& why ) {
     if ( nodes.empty() ) return true;
-    // iterative post-order: compute the union of triangle boxes below each child and compare with the stored box
+    // pass 1, structure: the nodes in the order a walk from the root meets them (a parent before its children), the leaves' ranges marked in `covered`
+    std::vector<uint8_t> visited ( nodes.size(), 0 ), covered ( boxes_in_leaf_order.size(), 0 );
+    std::vector<uint32_t> met, st; met.reserve ( nodes.size() ); st.push_back ( 0u ); visited[0] = 1;
+    while ( !st.empty() ) {
+        const uint32_t ni = st.back(); st.pop_back(); met.push_back ( ni );
+        const DevNode& n = nodes[ni];
+        for ( int c = 0; c < 2; ++c ) {
+            if ( n.child[c] == DEV_CHILD_EMPTY ) continue;
+            if ( n.child[c] & DEV_CHILD_LEAF ) {
+                const uint32_t first = n.child[c] & 0x07ffffffu, cnt = ( ( n.child[c] >> 27 ) & 0xfu ) + 1;
+                if ( cnt > 4 ) { why = "fast tree: a leaf holds more than 4 triangles"; return false; }
+                if ( ( size_t ) first + cnt > boxes_in_leaf_order.size() ) { why = "fast tree: leaf range out of range"; return false; }
+                for ( uint32_t j = 0; j < cnt; ++j ) {
+                    if ( covered[first + j] ) { why = "fast tree: a triangle lies in more than one leaf"; return false; }
+                    covered[first + j] = 1;
+                }
+                continue;
+            }
+            if ( n.child[c] >= nodes.size() ) { why = "fast tree: child index out of range"; return false; }
+            if ( visited[n.child[c]] ) { why = "fast tree: a node is reached twice (a child index points at an ancestor or at another parent's child)"; return false; }
+            visited[n.child[c]] = 1;
+            st.push_back ( n.child[c] );
+        }
+    }
+    for ( uint8_t c : covered ) if ( !c ) { why = "fast tree: a triangle lies in no leaf"; return false; }
+    // pass 2, boxes: backwards through that order (children before their parent) the union of the triangle boxes below each child, compared with the stored box
     std::vector<TerraAABB> below ( nodes.size() * 2 );
-    std::vector<std::pair<uint32_t, int>> st; st.push_back ( { 0u, 0 } );
     auto contains = [] ( const float* lo, const float* hi, const TerraAABB & b ) {
         return lo[0] <= b.min.x && lo[1] <= b.min.y && lo[2] <= b.min.z && hi[0] >= b.max.x && hi[1] >= b.max.y && hi[2] >= b.max.z;
     };
@@ -635,23 +662,14 @@ static bool verify_fast_tree ( const std::vector<DevNode>& nodes, const std::vec
         a.min.x = std::min ( a.min.x, b.min.x ); a.min.y = std::min ( a.min.y, b.min.y ); a.min.z = std::min ( a.min.z, b.min.z );
         a.max.x = std::max ( a.max.x, b.max.x ); a.max.y = std::max ( a.max.y, b.max.y ); a.max.z = std::max ( a.max.z, b.max.z );
     };
-    while ( !st.empty() ) {
-        auto [ni, stage] = st.back(); st.pop_back();
+    for ( size_t k = met.size(); k-- > 0; ) {
+        const uint32_t ni = met[k];
         const DevNode& n = nodes[ni];
-        if ( stage == 0 ) {
-            st.push_back ( { ni, 1 } );
-            for ( int c = 0; c < 2; ++c ) if ( n.child[c] != DEV_CHILD_EMPTY && ! ( n.child[c] & DEV_CHILD_LEAF ) ) {
-                if ( n.child[c] >= nodes.size() ) { why = "fast tree: child index out of range"; return false; }
-                st.push_back ( { n.child[c], 0 } );
-            }
-            continue;
-        }
         for ( int c = 0; c < 2; ++c ) {
             TerraAABB u = bvh::empty_box();
             if ( n.child[c] == DEV_CHILD_EMPTY ) { below[2 * ni + c] = u; continue; }
             if ( n.child[c] & DEV_CHILD_LEAF ) {
                 const uint32_t first = n.child[c] & 0x07ffffffu, cnt = ( ( n.child[c] >> 27 ) & 0xfu ) + 1;
-                if ( ( size_t ) first + cnt > boxes_in_leaf_order.size() ) { why = "fast tree: leaf range out of range"; return false; }
                 for ( uint32_t j = 0; j < cnt; ++j ) unite ( u, boxes_in_leaf_order[first + j] );
             } else {
                 const uint32_t ch = n.child[c];
@@ -1077,8 +1095,11 @@ static int finish_fast_tree ( const Scene* s, TreeChoice& c, const Flat& f, cons
     phase ( "  4-wide binary16 nodes", t_phase );
     c.fast_nodes = ( uint32_t ) ft.wide.nodes.size(); c.fast_max_stack = ft.wide.max_stack;
     // the stack of a fast-tree launch keeps its first entries in LDS and the rest in HBM (terra_plan_fast_tree: 4 bytes per entry and resident lane), so depth is no longer
-    // a reason to give the fast tree up -- short of a degenerate tree whose worst case would ask for gigabytes of spill space (a Morton-ordered tree over coincident
-    // geometry can be thousands of levels deep)
+    // a reason to give the fast tree up -- short of a degenerate tree whose worst case would ask for gigabytes of spill space. Which builder can make one: NOT the
+    // device LBVH -- a level below a node adds at least one bit to the common prefix of its 62-bit keys, so it is at most 62 levels deep (max_stack <= 63), and
+    // coincident geometry, whose keys differ in the index alone, gives a balanced tree (1,000 copies of one triangle: 9 levels; tests/test_fast_tree_gpu.py holds
+    // every case to <= 64). The host's SAH sweep has no such bound: among equal centroids every split costs the same and the first, one triangle off the end, wins,
+    // so the same 1,000 copies come out 176 levels deep (a wide stack of 187 entries; tests/test_fast_tree.py). The limit is for that builder
     if ( c.fast_max_stack > TERRA_FAST_STACK_MAX ) {
         fall_back ( c, format ( "%s needs a traversal stack of %d entries (limit %d): %s", c.fast_on_device ? "device-built fast tree" : "fast tree", c.fast_max_stack, TERRA_FAST_STACK_MAX,
                                 c.cull_ok ? "reference tree with the leaf-box cull (global memory)" : "reference tree, replica traversal" ) );
@@ -1087,14 +1108,19 @@ static int finish_fast_tree ( const Scene* s, TreeChoice& c, const Flat& f, cons
     if ( c.fast_nodes >= ( 1u << 25 ) ) return fail ( kTerraAmdErrUnsupported, "fast tree of %u nodes: the kernels address the 128-byte nodes by a 32-bit byte offset (at most 2^25 nodes)", c.fast_nodes );
     return 0;
 }
-static int build_fast_tree_host ( const Scene* s, TreeChoice& c, const Flat& f, FastTree& ft ) {
-    std::vector<fastbvh::Prim> prims ( f.ntri );
-    for ( size_t k = 0; k < f.ntri; ++k ) {
+// what the host builder is given: per soup triangle its box, the box's centre and its place in the soup
+static std::vector<fastbvh::Prim> fast_prims ( const DevTri* tris, size_t ntri, float extra ) {
+    std::vector<fastbvh::Prim> prims ( ntri );
+    for ( size_t k = 0; k < ntri; ++k ) {
         fastbvh::Prim& q = prims[k];
-        q.box = fast_leaf_box ( f.tris[k], c.fast_extra );
+        q.box = fast_leaf_box ( tris[k], extra );
         q.c[0] = 0.5f * ( q.box.min.x + q.box.max.x ); q.c[1] = 0.5f * ( q.box.min.y + q.box.max.y ); q.c[2] = 0.5f * ( q.box.min.z + q.box.max.z );
         q.soup = ( uint32_t ) k;
     }
+    return prims;
+}
+static int build_fast_tree_host ( const Scene* s, TreeChoice& c, const Flat& f, FastTree& ft ) {
+    std::vector<fastbvh::Prim> prims = fast_prims ( f.tris.data(), f.ntri, c.fast_extra );
     double t_phase = now_s();
     fastbvh::Built built = fastbvh::build ( prims );        // (reorders prims into leaf order)
     phase ( "fast tree (host)", t_phase );
@@ -3364,6 +3390,69 @@ extern "C" int terra_amd_unit_shade_stages ( int stage, int drops, const float* 
 extern "C" int terra_amd_unit_half_outward ( const double* x, int n, int up, uint16_t* out ) {
     if ( n < 0 || ( n && ( !x || !out ) ) ) return fail ( kTerraAmdErrBadArgument, "null array" );
     for ( int i = 0; i < n; ++i ) out[i] = fastbvh::half_outward ( x[i], up != 0 );
+    return 0;
+}
+
+// ---- the fast tree's builders, widening and commit check on a caller's soup (TESTS ONLY: tests/test_fast_tree.py, tests/test_fast_tree_gpu.py) ---------------
+// The soup as a commit would hold it: object 0, triangle i. The host builder's input carries the rank in `pad` as flatten leaves it; the device builder's carries
+// all ones there, so that k_soup has to take the rank from the rank array.
+static std::vector<DevTri> unit_soup ( const float* tris9, const uint32_t* rank, uint32_t n, bool pad_from_rank ) {
+    std::vector<DevTri> t ( n );
+    for ( uint32_t i = 0; i < n; ++i ) {
+        memcpy ( t[i].a, tris9 + 9 * ( size_t ) i, 12 ); memcpy ( t[i].b, tris9 + 9 * ( size_t ) i + 3, 12 ); memcpy ( t[i].c, tris9 + 9 * ( size_t ) i + 6, 12 );
+        t[i].object = 0; t[i].tri_in_object = i; t[i].pad = pad_from_rank ? rank[i] : 0xffffffffu;
+    }
+    return t;
+}
+// The binary tree as the builder made it -- neither verified nor repaired --, the soup's order and ranks in leaf order, the builder's stack bound, and that tree
+// widened. Nothing is written unless the build succeeds and everything fits the capacities given.
+extern "C" int terra_amd_unit_fast_tree ( const float* tris9, const uint32_t* rank, uint32_t n, int builder, float extra_margin, float scale,
+                                          void* bin_nodes, uint32_t bin_capacity, uint32_t* n_bin, uint32_t* order, uint32_t* pad, int* bin_max_stack,
+                                          void* wide_nodes, uint32_t wide_capacity, uint32_t* n_wide, int* wide_max_stack ) {
+    if ( builder < 0 || builder > 1 || ( n && ( !tris9 || !rank || !order || !pad ) ) || !bin_nodes || !n_bin || !bin_max_stack || !wide_nodes || !n_wide || !wide_max_stack )
+        return fail ( kTerraAmdErrBadArgument, "unit fast tree: builder outside 0..1 or null array" );
+    if ( ! ( scale > 0.f ) || !std::isfinite ( scale ) || !std::isfinite ( extra_margin ) || extra_margin < 0.f ) return fail ( kTerraAmdErrBadArgument, "unit fast tree: scale or margin out of range" );
+    std::vector<DevNode> bin; std::vector<DevTri> leaf_tris ( n ); int max_stack = 1;
+    if ( builder == 0 ) {
+        const std::vector<DevTri> tris = unit_soup ( tris9, rank, n, true );
+        std::vector<fastbvh::Prim> prims = fast_prims ( tris.data(), n, extra_margin );
+        fastbvh::Built built = fastbvh::build ( prims );
+        for ( size_t k = 0; k < built.order.size(); ++k ) leaf_tris[k] = tris[built.order[k]];
+        bin.swap ( built.nodes ); max_stack = built.max_stack;
+    } else {
+        if ( need_device() ) return kTerraAmdErrNoDevice;
+        const std::vector<DevTri> tris = unit_soup ( tris9, rank, n, false );
+        Unit u;
+        const DevTri* d_tris = u.in ( tris.data(), n ); const uint32_t* d_rank = u.in ( rank, n );
+        DevNode* d_nodes = ( DevNode* ) u.make ( nullptr, ( size_t ) n * sizeof ( DevNode ), false, false ); DevTri* d_out = ( DevTri* ) u.make ( nullptr, ( size_t ) n * sizeof ( DevTri ), false, false );
+        if ( !u.ok ) return fail ( kTerraAmdErrNoDevice, "unit fast tree: device allocation/copy failed" );
+        uint32_t built_nodes = 0;
+        const hipError_t e = terra_build_fast_tree_device ( d_tris, d_rank, n, extra_margin, d_nodes, d_out, &built_nodes, &max_stack, nullptr );
+        if ( e != hipSuccess ) { ( void ) hipGetLastError(); return fail ( kTerraAmdErrLaunch, "device tree build: %s", hipGetErrorString ( e ) ); }
+        if ( built_nodes > n ) return fail ( kTerraAmdErrLaunch, "device tree build: %u nodes for %u triangles", built_nodes, n );
+        bin.resize ( built_nodes );
+        HIP_TRY ( hipMemcpy ( bin.data(), d_nodes, bin.size() * sizeof ( DevNode ), hipMemcpyDeviceToHost ), kTerraAmdErrNoDevice );
+        HIP_TRY ( hipMemcpy ( leaf_tris.data(), d_out, leaf_tris.size() * sizeof ( DevTri ), hipMemcpyDeviceToHost ), kTerraAmdErrNoDevice );
+    }
+    const fastbvh::Wide wide = fastbvh::widen ( bin, scale );
+    if ( bin.size() > bin_capacity || wide.nodes.size() > wide_capacity ) return fail ( kTerraAmdErrBadArgument, "unit fast tree: %zu binary and %zu wide nodes do not fit the capacities given", bin.size(), wide.nodes.size() );
+    memcpy ( bin_nodes, bin.data(), bin.size() * sizeof ( DevNode ) ); *n_bin = ( uint32_t ) bin.size(); *bin_max_stack = max_stack;
+    for ( uint32_t k = 0; k < n; ++k ) { order[k] = leaf_tris[k].tri_in_object; pad[k] = leaf_tris[k].pad; }
+    memcpy ( wide_nodes, wide.nodes.data(), wide.nodes.size() * sizeof ( DevFastNode ) ); *n_wide = ( uint32_t ) wide.nodes.size(); *wide_max_stack = wide.max_stack;
+    return 0;
+}
+// The commit's check of a fast tree (verify_fast_tree) on a caller's binary tree and soup in leaf order: *accepted = 1 or 0, the refusal's reason in `reason`
+extern "C" int terra_amd_unit_verify_fast_tree ( const void* bin_nodes, uint32_t n_nodes, const float* tris9_in_leaf_order, uint32_t n, float extra_margin, int* accepted, char* reason, size_t reason_capacity ) {
+    if ( ( n_nodes && !bin_nodes ) || ( n && !tris9_in_leaf_order ) || !accepted ) return fail ( kTerraAmdErrBadArgument, "unit verify fast tree: null array" );
+    std::vector<DevNode> nodes ( n_nodes );
+    if ( n_nodes ) memcpy ( nodes.data(), bin_nodes, ( size_t ) n_nodes * sizeof ( DevNode ) );
+    const std::vector<uint32_t> no_rank ( n, 0 );
+    const std::vector<DevTri> tris = unit_soup ( tris9_in_leaf_order, no_rank.data(), n, true );
+    std::vector<TerraAABB> boxes ( n );
+    for ( uint32_t k = 0; k < n; ++k ) boxes[k] = fast_leaf_box ( tris[k], extra_margin );
+    std::string why;
+    *accepted = verify_fast_tree ( nodes, boxes, why ) ? 1 : 0;
+    if ( reason && reason_capacity ) snprintf ( reason, reason_capacity, "%s", why.c_str() );
     return 0;
 }
 

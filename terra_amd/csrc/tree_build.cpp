@@ -262,7 +262,7 @@ Built build ( std::vector<Prim>& prims ) {
     if ( !split ( 0, n, mid, false ) ) {
         set_child ( out.nodes[0], 0, bounds ( 0, n ), make_leaf ( 0, n ) );
         out.nodes[0].child[1] = DEV_CHILD_EMPTY;
-        out.max_stack = 1;
+        out.max_stack = max_depth + 1;          // the rule of the split case below on a tree of one level
     } else {
         // pass 1: ranges of more than TERRA_FAST_LEAF_MAX triangles are split, smaller ones become leaves; pass 2 splits those leaves
         // further where the surface-area estimate pays -- but never below the depth pass 1 reached, because the traversal stack

@@ -89,6 +89,8 @@ _EXTRA = {
     "terra_amd_unit_distribution_2d_pdf": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p]),
     "terra_amd_unit_azimuth24": (C.c_int, [C.POINTER(C.c_uint32)]),
     "terra_amd_unit_bsdf_at": (C.c_int, [C.c_int, C.c_int] + [C.c_void_p] * 5),
+    "terra_amd_unit_fast_tree": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_uint32] + [C.c_void_p] * 5 + [C.c_uint32, C.c_void_p, C.c_void_p]),
+    "terra_amd_unit_verify_fast_tree": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t]),
     "terra_amd_get_frame_seed": (C.c_uint64, [C.c_void_p]),
     "terra_amd_set_tree_mode": (C.c_int, [C.c_void_p, C.c_int]),
     "terra_amd_get_tree_mode": (C.c_int, [C.c_void_p]),

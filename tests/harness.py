@@ -191,6 +191,38 @@ class Unit:
         assert rc == 0, last_error()
         return found, prim, point, nodes
 
+    def fast_tree(self, tris, rank, builder, extra=0.0, scale=1.0):
+        """terra_amd_unit_fast_tree (tests only): the builder's binary tree as built (0 host SAH, 1 device LBVH), the soup's order and pad words in leaf order, the
+        builder's stack bound, and the tree widened at `scale`. Returns (status, dict or None); the node arrays use lbvh_ref's NODE / WIDE layouts. A refused call
+        leaves every output as it was handed in (filled with 0xa5 bytes), which the dict's absence stands for after that is asserted here."""
+        import lbvh_ref as R
+        assert self.kind == "amd"
+        tris = np.ascontiguousarray(tris, np.float32).reshape(-1, 9); rank = np.ascontiguousarray(rank, np.uint32)
+        n = len(tris); cap = n + 1
+        fill = lambda count, dt: np.frombuffer(b"\xa5" * (count * np.dtype(dt).itemsize), dt).copy()
+        nodes = fill(cap, R.NODE); wide = fill(cap, R.WIDE); order = fill(n, np.uint32); pad = fill(n, np.uint32)
+        counts = fill(2, np.uint32); stacks = fill(2, np.int32)
+        untouched = [a.copy() for a in (nodes, wide, order, pad, counts, stacks)]
+        f = self._f("fast_tree", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_uint32] + [C.c_void_p] * 5 + [C.c_uint32, C.c_void_p, C.c_void_p])
+        rc = f(tris.ctypes.data, rank.ctypes.data, n, builder, extra, scale, nodes.ctypes.data, cap, counts.ctypes.data, order.ctypes.data, pad.ctypes.data, stacks.ctypes.data,
+               wide.ctypes.data, cap, counts[1:].ctypes.data, stacks[1:].ctypes.data)
+        if rc != 0:
+            assert all(a.tobytes() == b.tobytes() for a, b in zip((nodes, wide, order, pad, counts, stacks), untouched)), "a refused call wrote into its outputs"
+            return rc, None
+        return 0, dict(nodes=nodes[:counts[0]].copy(), n_nodes=int(counts[0]), order=order, pad=pad, max_stack=int(stacks[0]),
+                       wide=wide[:counts[1]].copy(), n_wide=int(counts[1]), wide_max_stack=int(stacks[1]))
+
+    def verify_fast_tree(self, nodes, tris_in_leaf_order, extra=0.0):
+        """terra_amd_unit_verify_fast_tree (tests only): the commit's check of a fast tree -> (accepted, reason)"""
+        assert self.kind == "amd"
+        nodes = np.ascontiguousarray(nodes); tris = np.ascontiguousarray(tris_in_leaf_order, np.float32).reshape(-1, 9)
+        assert nodes.dtype.itemsize == 64
+        ok = C.c_int(-1); why = C.create_string_buffer(256)
+        rc = self._f("verify_fast_tree", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t])(
+            nodes.ctypes.data, len(nodes), tris.ctypes.data, len(tris), extra, C.byref(ok), why, 256)
+        assert rc == 0 and ok.value in (0, 1), last_error()
+        return bool(ok.value), why.value.decode()
+
     def raycast(self, scene, o, d):
         n = len(o)
         obj = np.zeros(n, np.int32); tri = np.zeros(n, np.int32); point = np.zeros((n, 3), np.float32); surf = np.zeros((n, 47), np.float32)

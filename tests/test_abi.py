@@ -33,7 +33,8 @@ def declared_functions(H):
 def test_every_declared_symbol_is_exported(H, amd_lib):
     names = declared_functions(H)
     assert len(names) >= 27 + 25, names        # Terra.h's 25 + 2 preset inits + the terra_amd_* extension
-    for required in ("terra_render", "terra_scene_commit", "terra_bsdf_phong_init", "terra_amd_render_device", "terra_amd_unit_watertight", "terra_amd_unit_texture_sample", "terra_amd_unit_texture_latlong", "terra_amd_pack_tiles"):
+    for required in ("terra_render", "terra_scene_commit", "terra_bsdf_phong_init", "terra_amd_render_device", "terra_amd_unit_watertight", "terra_amd_unit_texture_sample", "terra_amd_unit_texture_latlong", "terra_amd_pack_tiles",
+                     "terra_amd_unit_fast_tree", "terra_amd_unit_verify_fast_tree"):
         assert required in names
     missing = [n for n in names if not amd_lib.has(n)]
     assert not missing, missing
