@@ -37,6 +37,7 @@
  *       [--camera-model pinhole|thinlens|ortho|equirect|fisheye] [--aperture R] [--focus D] [--ortho-height H] [--fisheye-fov DEG]
  *       [--bake-lightmap [--atlas WxH] [--bake-margin M] [--bake-dilate N]]
  *       [--bake-probes NXxNYxNZ [--probe-cells N] [--probe-visibility maps.pfm [--probe-texels M]]]
+ *       [--distance-field NXxNYxNZ field.pfm]
  *
  * Environment: the scene's environment attribute is a constant (--environment-color, default 0.4 0.52 1) or a lat-long map (--environment: Radiance .hdr with flat
  * or new-style run-length-encoded scanlines, orientation -Y H +X W, texel = m 2^(e - 136); or .pfm, either byte order, bottom row first), bound as a 3-component
@@ -110,6 +111,10 @@ typedef struct { int texels; int sharpness; float max_distance; float bias; int 
 typedef struct { float weight; float distance; float distance2; int cells; } VisibilityTexel;
 int         terra_amd_intersect ( HTerraScene, const void*, size_t, void* ) __attribute__ ( ( weak ) );
 int         terra_amd_probe_visibility ( const void*, const void*, size_t, int, const void*, int, void* ) __attribute__ ( ( weak ) );
+/* --distance-field: the records of include/terra_amd.h "Nearest-surface queries" */
+typedef struct { float position[3]; float max_distance; } NearestQuery;
+typedef struct { float distance; int object; unsigned triangle; unsigned feature; float point[3]; float side; } NearestAnswer;
+int         terra_amd_nearest ( HTerraScene, const void*, size_t, void* ) __attribute__ ( ( weak ) );
 /* --camera-model: non-NULL = every render call and its AOV call go through the lens door */
 static const Lens* g_lens = NULL;
 static void render_rect ( const TerraCamera* cam, HTerraScene scene, const TerraFramebuffer* fb, size_t x, size_t y, size_t w, size_t h ) {
@@ -521,6 +526,19 @@ static int write_png ( const char* path, const TerraFramebuffer* fb ) {
     free ( raw ); free ( z );
     return fclose ( f ) == 0;
 }
+/* A grid of counts[a] cells per axis over the bounding box of nv > 0 vertices (--bake-probes, --distance-field): lo = the box's lower corner, sp = the cell size -- 1 on
+   an axis the scene has no extent on --; returns the squared diagonal of the box */
+static double cell_grid_over ( const BakePoint* verts, int nv, const int counts[3], float lo[3], float sp[3] ) {
+    double diagonal2 = 0.;
+    for ( int a = 0; a < 3; ++a ) {
+        float hi = lo[a] = verts[0].position[a];
+        for ( int k = 1; k < nv; ++k ) { const float v = verts[k].position[a]; if ( v < lo[a] ) lo[a] = v; if ( v > hi ) hi = v; }
+        diagonal2 += ( double ) ( hi - lo[a] ) * ( double ) ( hi - lo[a] );
+        sp[a] = ( hi - lo[a] ) / ( float ) counts[a];
+        if ( !( sp[a] > 0.f ) ) sp[a] = 1.f;
+    }
+    return diagonal2;
+}
 static int write_image ( const char* path, const TerraFramebuffer* fb ) {
     const char* ext = strrchr ( path, '.' );
     if ( ext && strcmp ( ext, ".ppm" ) == 0 ) return write_ppm ( path, fb );
@@ -649,6 +667,8 @@ static const char* kHelp =
     "           index (iz * NY + iy) * NX + ix), as a float RGB image (.pfm / .hdr) 9 wide and NX * NY * NZ high: pixel (k, p) is coefficient k of probe p.\n"
     "           terra_amd_probe_rays lays N x N (1 .. 64, default 16) equal-area directions about every probe, terra_amd_render_rays gathers --spp samples per\n"
     "           --passes pass along each into one frame, terra_amd_sh_project reduces it. The camera flags, --aov, --denoise*, --adaptive, --frames and --gpus are ignored.\n"
+    "  --distance-field NXxNYxNZ PATH (libterra_amd.so only): also writes the scene's distance field as a grey float image (.pfm), NX wide and NY * NZ high: the distance\n"
+    "           from the centre of each of NX x NY x NZ cells over the scene's bounding box to the nearest surface (terra_amd_nearest), slice iz in rows iz * NY ..\n"
     "  --probe-visibility PATH [--probe-texels M] (with --bake-probes): also writes the probes' visibility maps as a float RGB image (.pfm / .hdr) M * M wide (M 1 .. 16,\n"
     "           default 8) and NX * NY * NZ high: pixel (t, p) is texel t = j * M + i of probe p as (sum of w, sum of w * d, sum of w * d * d), d the distance\n"
     "           terra_amd_intersect finds along the same cell-centre rays, w = cos^64 about the texel's octahedral direction (terra_amd_probe_visibility,\n"
@@ -670,6 +690,7 @@ int main ( int argc, char** argv ) {
     int camera_model = 0; float aperture = 0.f, focus = 1.f, ortho_height = 2.f, fisheye_fov = 180.f;      /* camera_model: 0 pinhole, 1 thinlens, 2 ortho, 3 equirect, 4 fisheye */
     int bake = 0, atlas_w = 256, atlas_h = 256, bake_dilate = 2; float bake_margin = 0.5f;      /* --bake-lightmap */
     int probes_on = 0, probe_n[3] = { 1, 1, 1 }, probe_cells = 16;      /* --bake-probes */
+    int field_n[3] = { 0, 0, 0 }; const char* field_path = NULL;        /* --distance-field */
     const char* visibility_path = NULL; int probe_texels = 8;      /* --probe-visibility */
     float fov = 45.f, exposure = 1.f, gamma = 2.2f, jitter = 0.f;
     unsigned long long seed = 0;
@@ -725,6 +746,11 @@ int main ( int argc, char** argv ) {
         else if ( !strcmp ( a, "--bake-probes" ) ) {
             probes_on = 1;
             if ( sscanf ( NEXT(), "%dx%dx%d", &probe_n[0], &probe_n[1], &probe_n[2] ) != 3 || probe_n[0] < 1 || probe_n[1] < 1 || probe_n[2] < 1 || ( double ) probe_n[0] * probe_n[1] * probe_n[2] > 1048576. ) { fprintf ( stderr, "terra_headless: --bake-probes NXxNYxNZ, each at least 1, at most 1048576 probes\n" ); return 64; }
+        }
+        else if ( !strcmp ( a, "--distance-field" ) ) {
+            if ( sscanf ( NEXT(), "%dx%dx%d", &field_n[0], &field_n[1], &field_n[2] ) != 3 || field_n[0] < 1 || field_n[1] < 1 || field_n[2] < 1 || ( double ) field_n[0] * field_n[1] * field_n[2] > 16777216. ) { fprintf ( stderr, "terra_headless: --distance-field NXxNYxNZ PATH, each at least 1, at most 16777216 cells\n" ); return 64; }
+            field_path = NEXT();
+            if ( !*field_path || !strncmp ( field_path, "--", 2 ) ) { fprintf ( stderr, "terra_headless: --distance-field NXxNYxNZ PATH: no path\n" ); return 64; }
         }
         else if ( !strcmp ( a, "--probe-visibility" ) ) visibility_path = NEXT();
         else if ( !strcmp ( a, "--probe-texels" ) ) { probe_texels = atoi ( NEXT() ); if ( probe_texels < 1 || probe_texels > 16 ) { fprintf ( stderr, "terra_headless: --probe-texels 1 .. 16\n" ); return 64; } }
@@ -788,6 +814,32 @@ int main ( int argc, char** argv ) {
         for ( int k = 0; k < gpus; ++k ) devs[k] = k;
         if ( terra_amd_set_devices ( devs, gpus ) != 0 ) { fprintf ( stderr, "terra_headless: %s\n", terra_amd_last_error ? terra_amd_last_error() : "terra_amd_set_devices failed" ); return 69; }
     }
+    if ( field_path && ( !terra_amd_scene_vertex_points || !terra_amd_nearest ) ) { fprintf ( stderr, "terra_headless: --distance-field needs libterra_amd.so; ignored\n" ); field_path = NULL; }
+    if ( field_path ) {          /* beside whatever else the run writes: the distance to the nearest surface at the centres of NX x NY x NZ cells over the bounding box */
+        const size_t nx = ( size_t ) field_n[0], ny = ( size_t ) field_n[1], nz = ( size_t ) field_n[2], n = nx * ny * nz;
+        terra_scene_commit ( scene );
+        const int nv = terra_amd_scene_vertex_points ( scene, NULL, 0 );
+        if ( nv <= 0 ) { fprintf ( stderr, "terra_headless: --distance-field: the scene has no triangles\n" ); return 66; }
+        BakePoint* verts = aligned_alloc ( 16, ( size_t ) nv * sizeof ( BakePoint ) );
+        NearestQuery* queries = aligned_alloc ( 16, n * sizeof ( NearestQuery ) ); NearestAnswer* answers = aligned_alloc ( 16, n * sizeof ( NearestAnswer ) );
+        TerraFramebuffer field;
+        if ( !verts || !queries || !answers || !terra_framebuffer_create ( &field, nx, ny * nz ) ) { fprintf ( stderr, "terra_headless: out of memory\n" ); return 71; }
+        int rc = terra_amd_scene_vertex_points ( scene, verts, nv ) < 0;
+        float lo[3], sp[3];
+        ( void ) cell_grid_over ( verts, nv, field_n, lo, sp );
+        for ( size_t iz = 0; iz < nz; ++iz ) for ( size_t iy = 0; iy < ny; ++iy ) for ( size_t ix = 0; ix < nx; ++ix ) {
+            NearestQuery* q = &queries[ ( iz * ny + iy ) * nx + ix];
+            const size_t i[3] = { ix, iy, iz };
+            for ( int a = 0; a < 3; ++a ) { volatile float t = ( ( float ) i[a] + 0.5f ) * sp[a]; q->position[a] = t + lo[a]; }          /* (volatile: multiply, then add -- no fused form) */
+            q->max_distance = INFINITY;
+        }
+        if ( !rc ) rc = terra_amd_nearest ( scene, queries, n, answers );
+        if ( rc ) { fprintf ( stderr, "terra_headless: %s\n", terra_amd_last_error && *terra_amd_last_error() ? terra_amd_last_error() : "the distance field failed" ); return 70; }
+        for ( size_t k = 0; k < n; ++k ) field.pixels[k] = terra_f3_set ( answers[k].distance, answers[k].distance, answers[k].distance );          /* slice iz = rows iz * NY .. of the image */
+        if ( !write_pfm ( field_path, &field ) ) { fprintf ( stderr, "terra_headless: cannot write %s\n", field_path ); return 73; }
+        printf ( "%s: distance field %s (%dx%dx%d cells from %g %g %g, spacing %g %g %g)\n", argv[1], field_path, field_n[0], field_n[1], field_n[2], ( double ) lo[0], ( double ) lo[1], ( double ) lo[2], ( double ) sp[0], ( double ) sp[1], ( double ) sp[2] );
+        free ( verts ); free ( queries ); free ( answers ); terra_framebuffer_destroy ( &field );
+    }
     if ( bake && ( !terra_amd_atlas_points || !terra_amd_render_points || !terra_amd_dilate ) ) { fprintf ( stderr, "terra_headless: --bake-lightmap needs libterra_amd.so; ignored, the camera's image is written\n" ); bake = 0; }
     if ( bake ) {          /* the atlas is the frame: points under the texels, irradiance at the points, the lit texels grown into the gutters */
         const size_t aw = ( size_t ) atlas_w, ah = ( size_t ) atlas_h, n = aw * ah;
@@ -833,15 +885,9 @@ int main ( int argc, char** argv ) {
         int rc = terra_amd_scene_vertex_points ( scene, verts, nv ) < 0;
         ProbeGrid grid; memset ( &grid, 0, sizeof grid );
         grid.nx = probe_n[0]; grid.ny = probe_n[1]; grid.nz = probe_n[2];
-        double diagonal2 = 0.;          /* of the bounding box, for --probe-visibility */
-        for ( int a = 0; a < 3; ++a ) {          /* cell-centred over the bounding box; an axis the scene has no extent on gets the spacing 1 */
-            float lo = verts[0].position[a], hi = lo;
-            for ( int k = 1; k < nv; ++k ) { const float v = verts[k].position[a]; if ( v < lo ) lo = v; if ( v > hi ) hi = v; }
-            diagonal2 += ( double ) ( hi - lo ) * ( double ) ( hi - lo );
-            float sp = ( hi - lo ) / ( float ) probe_n[a];
-            if ( !( sp > 0.f ) ) sp = 1.f;
-            grid.spacing[a] = sp; grid.origin[a] = lo + 0.5f * sp;
-        }
+        float lo[3], sp[3];
+        const double diagonal2 = cell_grid_over ( verts, nv, probe_n, lo, sp );          /* of the bounding box, for --probe-visibility */
+        for ( int a = 0; a < 3; ++a ) { grid.spacing[a] = sp[a]; grid.origin[a] = lo[a] + 0.5f * sp[a]; }          /* cell-centred over the bounding box */
         if ( !rc ) rc = terra_amd_probe_grid_points ( &grid, probes, ( int ) P ) < 0;
         if ( !rc ) rc = terra_amd_probe_rays ( probes, P, probe_cells, NULL, rays );
         for ( int pass = 0; pass < passes && !rc; ++pass ) rc = terra_amd_render_rays ( scene, rays, &frame, 0, 0, K, P );

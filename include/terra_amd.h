@@ -1120,6 +1120,67 @@ int terra_amd_sh_irradiance_visible_device ( const void* d_sh, const void* d_map
 /* The same on host memory; synchronous. */
 int terra_amd_sh_irradiance_visible ( const TerraAmdProbeSH* sh, const TerraAmdVisibilityTexel* map, size_t probes, const TerraAmdProbeGrid* grid, const TerraAmdProbeVisibility* options, const TerraAmdPoint* points, size_t n, float* out4 );
 
+/* ---- Nearest-surface queries: the closest point of a committed scene to a client's points, and its distance ---------------------------------------------------
+   The point door: "which point of the scene is closest to P, and how far is it" -- distance fields, proximity tests, the clearance of a probe or a sample point
+   from the walls. Per query, independently of every other query, and independently of which accelerator answers (there is ONE rule):
+   Arithmetic.  Binary64 throughout, every operation in the order written, no fused multiply-add, IEEE division, correctly rounded square root. Every binary32
+     input (the query's position and limit, the vertices) is widened first. dot(u, v) = (ux*vx + uy*vy) + uz*vz. A quotient whose divisor is exactly 0 is taken as 0.
+   Closest point of one triangle.  Vertices (A, B, C) in the order the scene stores them, P the query's position. The regions are those of Ericson, Real-Time
+     Collision Detection, 5.1.5, tested in this order; the first that holds decides.
+       ab = B - A, ac = C - A;  ap = P - A, d1 = dot(ab, ap), d2 = dot(ac, ap);  bp = P - B, d3 = dot(ab, bp), d4 = dot(ac, bp);  cp = P - C, d5 = dot(ab, cp),
+       d6 = dot(ac, cp);  vc = d1*d4 - d3*d2, vb = d5*d2 - d1*d6, va = d3*d6 - d5*d4
+       1. d1 <= 0 && d2 <= 0                          Q = A                                                        feature 1
+       2. d3 >= 0 && d4 <= d3                         Q = B                                                        feature 2
+       3. vc <= 0 && d1 >= 0 && d3 <= 0               v = d1 / (d1 - d3),  Q = A + v*ab                            feature 4 (edge AB)
+       4. d6 >= 0 && d5 <= d6                         Q = C                                                        feature 3
+       5. vb <= 0 && d2 >= 0 && d6 <= 0               w = d2 / (d2 - d6),  Q = A + w*ac                            feature 6 (edge CA)
+       6. va <= 0 && (d4 - d3) >= 0 && (d5 - d6) >= 0 w = (d4 - d3) / ((d4 - d3) + (d5 - d6)),  Q = B + w*(C - B)  feature 5 (edge BC)
+       7. otherwise                                   den = (va + vb) + vc,  Q = (A + ab*(vb / den)) + ac*(vc / den)  feature 0 (the face)
+     (component by component; a comparison with a NaN is false, so a triangle with a NaN vertex falls through to 7.) Then e = P - Q and D2 = dot(e, e).
+   Which triangles count.  R = max_distance. R NaN, +inf or >= FLT_MAX: no limit. R < 0: nothing counts. A triangle counts if its D2 is not NaN and, with a limit,
+     D2 <= (double) R * (double) R. A query whose position has a non-finite component counts nothing, whatever the limit.
+   Answer.  The counting triangle with the smallest D2; equal D2 is resolved by the smaller (object, triangle in its object) pair, compared lexicographically --
+     shared edges and vertices make such ties the normal case (a third of uniformly placed queries and more), not a corner. distance = (float) sqrt(D2),
+     point = (float) Q, object / triangle / feature as above, side = +1, -1 or 0: the sign of dot(n, e) with
+       n = cross(ab, ac) = (ab.y*ac.z - ab.z*ac.y,  ab.z*ac.x - ab.x*ac.z,  ab.x*ac.y - ab.y*ac.x)
+     (NaN gives 0). side tells the front of the winning triangle from its back; it tells inside from outside of a closed surface only where feature == 0 -- at an
+     edge or a vertex the winning triangle's plane need not separate the two (that needs angle-weighted pseudonormals, which are not built).
+     Nothing counts: distance = FLT_MAX, object = -1, triangle = 0, feature = 0, point = (FLT_MAX, FLT_MAX, FLT_MAX), side = 0.
+   No camera_limit contract: the answer follows the rule for every finite position, however far from the scene.
+   Traversal.  A scene whose commit built a fast tree (TerraAmdTraversalInfo::fast_tree) is answered by a distance-ordered walk of that tree; every other scene
+     (LDS-resident ones, fewer than two triangles, the fall-backs) by a brute force over all triangles, O(n * triangles): a large scene held in tree mode 0 wants
+     terra_amd_set_tree_mode(scene, 1) before such calls. Both give the same bits.
+   Calls.  As the ray queries: n == 0 succeeds and launches nothing; n > 2^31 - 1 or a NULL buffer with n > 0 is kTerraAmdErrBadArgument, an uncommitted scene
+     kTerraAmdErrNotCommitted; nothing is recorded in terra_amd_get_stats(), no framebuffer is touched, a scene committed for several devices answers on its
+     primary device, no atomics: the same inputs give the same bits. */
+typedef struct {            /* 16 bytes = one 16-byte word */
+    float position[3];      /* +0 */
+    float max_distance;     /* +12  triangles farther than this do not count (see "Which triangles count") */
+} TerraAmdNearestQuery;
+typedef struct {            /* 32 bytes = two 16-byte words */
+    float    distance;      /* +0   (float) sqrt(D2); FLT_MAX where nothing counts */
+    int32_t  object;        /* +4   index of the object in the scene, -1 where nothing counts */
+    uint32_t triangle;      /* +8   index of the triangle in that object */
+    uint32_t feature;       /* +12  0 face, 1 2 3 vertex A B C, 4 5 6 edge AB BC CA */
+    float    point[3];      /* +16  (float) Q */
+    float    side;          /* +28  +1 / -1 / 0 */
+} TerraAmdNearest;
+TERRA_ABI_ASSERT ( sizeof ( TerraAmdNearestQuery ) == 16 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdNearestQuery, max_distance ) == 12 );
+TERRA_ABI_ASSERT ( sizeof ( TerraAmdNearest ) == 32 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdNearest, object ) == 4 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdNearest, triangle ) == 8 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdNearest, feature ) == 12 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdNearest, point ) == 16 );
+TERRA_ABI_ASSERT ( offsetof ( TerraAmdNearest, side ) == 28 );
+/* d_queries: n TerraAmdNearestQuery, d_out: n TerraAmdNearest, both in HBM and 16-byte aligned; asynchronous on `stream`: any scratch the call needs is
+   allocated and freed in stream order, nothing synchronises. */
+int terra_amd_nearest_device ( HTerraScene scene, const void* d_queries, size_t n, void* d_out, void* stream );
+/* The same on host buffers: the queries are uploaded, the kernel runs, the answers are downloaded; synchronous. */
+int terra_amd_nearest ( HTerraScene scene, const TerraAmdNearestQuery* queries, size_t n, TerraAmdNearest* out );
+/* Test plumbing: terra_amd_nearest through the brute-force kernel, whatever tree the scene has. */
+int terra_amd_unit_nearest_brute ( HTerraScene scene, const TerraAmdNearestQuery* queries, size_t n, TerraAmdNearest* out );
+
 /* Tile-sharded form for one-process-per-GPU rendering (the reference shards
    the same way over CPU threads: satellite/src/Renderer.cpp:316-350): the
    rectangle is cut into tile_size x tile_size tiles numbered row-major and this

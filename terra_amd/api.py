@@ -349,6 +349,30 @@ PROBE_VISIBILITY_SIGNATURES = {
     "terra_amd_sh_irradiance_visible": (c_int, [c_void_p, c_void_p, c_size_t, POINTER(ProbeGrid), POINTER(ProbeVisibility), c_void_p, c_size_t, c_void_p]),
 }
 
+# TerraAmdNearestQuery / TerraAmdNearest (include/terra_amd.h "Nearest-surface queries"): 16 and 32 bytes
+NEAREST_QUERY_DTYPE = np.dtype([("position", np.float32, (3,)), ("max_distance", np.float32)])
+NEAREST_DTYPE = np.dtype([("distance", np.float32), ("object", np.int32), ("triangle", np.uint32), ("feature", np.uint32), ("point", np.float32, (3,)), ("side", np.float32)])
+assert NEAREST_QUERY_DTYPE.itemsize == 16 and NEAREST_DTYPE.itemsize == 32
+
+
+class TerraAmdNearestQuery(Structure):
+    _fields_ = [("position", c_float * 3), ("max_distance", c_float)]
+
+
+class TerraAmdNearest(Structure):
+    _fields_ = [("distance", c_float), ("object", c_int), ("triangle", c_uint32), ("feature", c_uint32), ("point", c_float * 3), ("side", c_float)]
+
+
+ABI_SIZES.update({TerraAmdNearestQuery: 16, TerraAmdNearest: 32})
+assert C.sizeof(TerraAmdNearestQuery) == 16 and C.sizeof(TerraAmdNearest) == 32
+
+# ... and of the nearest-surface queries (include/terra_amd.h "Nearest-surface queries")
+NEAREST_SIGNATURES = {
+    "terra_amd_nearest_device": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "terra_amd_nearest": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
+    "terra_amd_unit_nearest_brute": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
+}
+
 # entry points of include/Terra.h + include/TerraPresets.h, name -> (restype, argtypes)
 API_SIGNATURES = {
     "scene_create": (c_void_p, []),

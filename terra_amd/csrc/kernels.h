@@ -91,6 +91,15 @@ struct DevQueryParams {
 };
 hipError_t terra_launch_query ( DevQueryParams p, const void* rays, size_t n, void* out, bool anyhit, hipStream_t stream );
 
+// nearest-surface queries (nearest_kernels.hip; include/terra_amd.h "Nearest-surface queries"): queries = n TerraAmdNearestQuery, out = n TerraAmdNearest, both in HBM.
+// fast: the distance-ordered walk of the fast tree (stack_depth / spill_cap as launch_plan.h terra_plan_fast_tree made them; scene.fast_nodes_h and at least two
+// triangles), otherwise the brute force over scene.tris
+struct DevNearestParams {
+    DevScene scene;
+    uint32_t fast, stack_depth, spill_cap;
+};
+hipError_t terra_launch_nearest ( DevNearestParams p, const void* queries, size_t n, void* out, hipStream_t stream );
+
 // lightmap baking (bake_kernels.hip; include/terra_amd.h "Lightmap baking"): all pointers are device pointers; the launchers take their scratch (the coverage
 // keys; the dilation's second copy) from the stream's pool and give it back on the stream
 struct DevAtlas {

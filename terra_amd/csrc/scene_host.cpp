@@ -2109,6 +2109,57 @@ extern "C" int terra_amd_occluded_device ( HTerraScene h, const void* d_rays, si
 extern "C" int terra_amd_intersect ( HTerraScene h, const TerraAmdRay* rays, size_t n, TerraAmdHit* hits ) { return query_host ( h, rays, n, hits, sizeof ( TerraAmdHit ), false, "terra_amd_intersect" ); }
 extern "C" int terra_amd_occluded ( HTerraScene h, const TerraAmdRay* rays, size_t n, uint32_t* occluded ) { return query_host ( h, rays, n, occluded, sizeof ( uint32_t ), true, "terra_amd_occluded" ); }
 
+// ---- nearest-surface queries (nearest_kernels.hip) ------------------------------------
+static_assert ( sizeof ( TerraAmdNearestQuery ) == 16 && sizeof ( TerraAmdNearest ) == 32, "TerraAmdNearestQuery must be 16 bytes and TerraAmdNearest 32" );
+// the one check of the three entry points, in the order of the ray queries' query_check: the scene can answer, n fits the kernel's 32-bit index, the buffers are there
+static int nearest_check ( Scene* s, const void* queries, size_t n, const void* out, const char* what ) {
+    if ( int rc = scene_check ( s ) ) return rc;
+    if ( n > ( size_t ) 0x7fffffff ) return fail ( kTerraAmdErrBadArgument, "%s: %zu queries in one call, at most 2^31 - 1", what, n );
+    if ( n > 0 && ( !queries || !out ) ) return fail ( kTerraAmdErrBadArgument, "%s: null query or result buffer", what );
+    return 0;
+}
+// The fast tree wherever the commit built one -- there is no range contract to give it up for: the box distance is a lower bound for every finite point, and a point
+// has no reference traversal to replay, so MODE 2 and 3 scenes are walked alike --, otherwise (or brute = true: test plumbing) the brute force over the soup.
+static int launch_nearest ( Scene* s, const void* d_queries, size_t n, void* d_out, bool brute, hipStream_t stream ) {
+    const Scene::Replica& r = primary ( s );
+    DevRenderParams rp;
+    memset ( &rp, 0, sizeof rp );
+    rp.scene = r.dev;
+    DevNearestParams p;
+    memset ( &p, 0, sizeof p );
+    p.scene = r.dev;
+    if ( !brute && s->tree.use_fast && r.dev.fast_nodes_h && r.dev.fast_tris && r.dev.n_tris >= 2 ) { terra_plan_fast_tree ( rp ); apply_stack_hooks ( s, rp ); p.fast = 1; }
+    p.stack_depth = rp.stack_depth; p.spill_cap = rp.spill_cap;
+    p.scene.sincos24 = nullptr;
+    const hipError_t e = terra_launch_nearest ( p, d_queries, n, d_out, stream );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "nearest-surface query launch: %s", hipGetErrorString ( e ) );
+    return 0;
+}
+// host buffers through the staging path of the ray queries: upload, query, download; synchronous
+static int nearest_host ( HTerraScene h, const TerraAmdNearestQuery* queries, size_t n, TerraAmdNearest* out, bool brute, const char* what ) {
+    Scene* s = S ( h );
+    if ( int rc = nearest_check ( s, queries, n, out, what ) ) return rc;
+    if ( n == 0 ) return 0;
+    HIP_TRY ( hipSetDevice ( primary ( s ).device ), kTerraAmdErrNoDevice );
+    FrameCopy c;
+    hipError_t e = c.up ( 0, queries, n * sizeof ( TerraAmdNearestQuery ) );
+    if ( e == hipSuccess ) e = c.up ( 1, nullptr, n * sizeof ( TerraAmdNearest ) );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "%s upload: %s", what, hipGetErrorString ( e ) );
+    if ( int rc = launch_nearest ( s, c.d[0], n, c.d[1], brute, nullptr ) ) return rc;
+    e = c.down ( 1, out, n * sizeof ( TerraAmdNearest ) );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "%s download: %s", what, hipGetErrorString ( e ) );
+    return 0;
+}
+extern "C" int terra_amd_nearest_device ( HTerraScene h, const void* d_queries, size_t n, void* d_out, void* stream ) {
+    Scene* s = S ( h );
+    if ( int rc = nearest_check ( s, d_queries, n, d_out, "terra_amd_nearest_device" ) ) return rc;
+    if ( n == 0 ) return 0;
+    HIP_TRY ( hipSetDevice ( primary ( s ).device ), kTerraAmdErrNoDevice );
+    return launch_nearest ( s, d_queries, n, d_out, false, ( hipStream_t ) stream );
+}
+extern "C" int terra_amd_nearest ( HTerraScene h, const TerraAmdNearestQuery* queries, size_t n, TerraAmdNearest* out ) { return nearest_host ( h, queries, n, out, false, "terra_amd_nearest" ); }
+extern "C" int terra_amd_unit_nearest_brute ( HTerraScene h, const TerraAmdNearestQuery* queries, size_t n, TerraAmdNearest* out ) { return nearest_host ( h, queries, n, out, true, "terra_amd_unit_nearest_brute" ); }
+
 // ---- denoiser (denoise_kernels.hip) ----------------------------------------------------
 extern "C" int terra_amd_denoise_device ( HTerraScene h, const void* d_results, const void* d_aov, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t hgt, int iterations,
                                           void* d_radiance, void* d_pixels, void* stream ) {

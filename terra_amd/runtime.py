@@ -158,6 +158,7 @@ _EXTRA = {
     **api.PROBE_SIGNATURES,
     **api.PROBE_VISIBILITY_SIGNATURES,
     **api.EXACT_SQRT_SIGNATURES,
+    **api.NEAREST_SIGNATURES,
 }
 
 
@@ -483,6 +484,70 @@ def occluded(lib, scene, rays):
     out = torch.empty(rays.shape[0], dtype=torch.int32, device=rays.device)
     check(lib.occluded_device(scene, rays.data_ptr(), rays.shape[0], out.data_ptr(), stream), "terra_amd_occluded_device")
     return out
+
+
+# ---------------------------------------------------------------------------
+# nearest-surface queries (include/terra_amd.h "Nearest-surface queries")
+# ---------------------------------------------------------------------------
+
+def nearest(lib, scene, queries):
+    """terra_amd_nearest_device on queries (float32 [n, 4] in HBM: TerraAmdNearestQuery records, position and max_distance) -> float32 [n, 8], TerraAmdNearest
+    records (.cpu().numpy().view(api.NEAREST_DTYPE)). Queued on the current torch stream; nothing is copied to the host."""
+    import torch
+    if not (isinstance(queries, torch.Tensor) and queries.is_cuda and queries.dtype == torch.float32 and queries.dim() == 2 and queries.shape[1] == 4 and queries.is_contiguous()):
+        raise TerraAmdError("nearest-surface queries take a contiguous float32 tensor [n, 4] on the scene's device: position, max_distance (api.NEAREST_QUERY_DTYPE)")
+    if queries.data_ptr() % 16:
+        raise TerraAmdError("the query buffer must be 16-byte aligned")
+    stream = torch.cuda.current_stream(queries.device).cuda_stream or None
+    out = torch.empty((queries.shape[0], 8), dtype=torch.float32, device=queries.device)
+    check(lib.nearest_device(scene, queries.data_ptr(), queries.shape[0], out.data_ptr(), stream), "terra_amd_nearest_device")
+    return out
+
+
+def distance_field_points(origin, spacing, dims, max_distance=float("inf")) -> np.ndarray:
+    """the queries of distance_field, api.NEAREST_QUERY_DTYPE records [nz, ny, nx]: cell (ix, iy, iz) has its centre at origin + (i + 0.5) * spacing, in float32:
+    (float32(i) + 0.5) * spacing, then + origin"""
+    nx, ny, nz = (int(v) for v in dims)
+    if nx < 1 or ny < 1 or nz < 1:
+        raise TerraAmdError(f"distance_field: dims {dims} must be positive")
+    o = np.asarray(origin, np.float32).reshape(3)
+    s = np.broadcast_to(np.asarray(spacing, np.float32), (3,))
+    q = np.zeros((nz, ny, nx), api.NEAREST_QUERY_DTYPE)
+    axes = [(np.arange(n, dtype=np.float32) + np.float32(0.5)) * s[a] + o[a] for a, n in enumerate((nx, ny, nz))]
+    q["position"][..., 0] = axes[0][None, None, :]
+    q["position"][..., 1] = axes[1][None, :, None]
+    q["position"][..., 2] = axes[2][:, None, None]
+    q["max_distance"] = np.float32(max_distance)
+    return q
+
+
+def distance_field(lib, scene, origin, spacing, dims, max_distance=float("inf"), signed=False):
+    """The scene's distance field on a regular grid -> float32 [nz, ny, nx] in HBM: the `distance` of nearest() at the cell centres of distance_field_points
+    (FLT_MAX where nothing lies within max_distance). signed: the distance times `side` where the closest feature is a face (feature == 0), left positive at edges
+    and vertices -- a CRUDE sign: it follows the winning triangle's winding, says nothing true next to an edge or a vertex, and is no inside / outside test of an
+    open or inconsistently wound scene (angle-weighted pseudonormals are not built)."""
+    import torch
+    q = distance_field_points(origin, spacing, dims, max_distance)
+    out = nearest(lib, scene, torch.from_numpy(q.view(np.float32).reshape(-1, 4)).cuda())
+    dist = out[:, 0]
+    if signed:
+        feature = out[:, 3].view(torch.int32)
+        side = out[:, 7]
+        dist = torch.where((feature == 0) & (side != 0), dist * side, dist)
+    return dist.reshape(q.shape).contiguous()
+
+
+def probe_clearance(lib, scene, probes):
+    """How far each probe is from the scene's surfaces: probes (float32 [n, 8] in HBM, api.POINT_DTYPE records; only the position is read) -> (distance float32 [n],
+    closest point float32 [n, 3]) in HBM -- what a client needs to drop or move the probes of a grid that landed inside or next to a wall."""
+    import torch
+    if not (isinstance(probes, torch.Tensor) and probes.is_cuda and probes.dtype == torch.float32 and probes.dim() == 2 and probes.shape[1] == 8):
+        raise TerraAmdError("probe_clearance takes a float32 tensor [n, 8] on the scene's device: api.POINT_DTYPE records")
+    q = torch.empty((probes.shape[0], 4), dtype=torch.float32, device=probes.device)
+    q[:, :3] = probes[:, :3]
+    q[:, 3] = float("inf")
+    out = nearest(lib, scene, q)
+    return out[:, 0].contiguous(), out[:, 4:7].contiguous()
 
 
 # ---------------------------------------------------------------------------

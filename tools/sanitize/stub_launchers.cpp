@@ -48,6 +48,7 @@ hipError_t terra_launch_error_mask ( const float*, uint32_t, uint32_t, uint32_t,
 hipError_t terra_launch_denoise_variance ( const void*, const void*, const void*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, int, float, int, float, float*, float*, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_launch_temporal_reproject ( const DevTemporalParams&, const void*, const void*, const void*, void*, void*, void*, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_launch_query ( DevQueryParams, const void*, size_t, void*, bool, hipStream_t ) { return hipErrorNoDevice; }
+hipError_t terra_launch_nearest ( DevNearestParams, const void*, size_t, void*, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_unit_texture_sample ( const DevTexture*, int, const float*, float* ) { return hipErrorNoDevice; }
 hipError_t terra_unit_texture_latlong ( const DevTexture*, int, const float*, float* ) { return hipErrorNoDevice; }
 hipError_t terra_launch_atlas_points ( const DevScene&, const DevAtlas&, const float*, void*, void*, hipStream_t ) { return hipErrorNoDevice; }
