@@ -37,7 +37,7 @@
  *       [--camera-model pinhole|thinlens|ortho|equirect|fisheye] [--aperture R] [--focus D] [--ortho-height H] [--fisheye-fov DEG]
  *       [--bake-lightmap [--atlas WxH] [--bake-margin M] [--bake-dilate N]]
  *       [--bake-probes NXxNYxNZ [--probe-cells N] [--probe-visibility maps.pfm [--probe-texels M]]]
- *       [--distance-field NXxNYxNZ field.pfm]
+ *       [--distance-field NXxNYxNZ field.pfm [--signed]]
  *
  * Environment: the scene's environment attribute is a constant (--environment-color, default 0.4 0.52 1) or a lat-long map (--environment: Radiance .hdr with flat
  * or new-style run-length-encoded scanlines, orientation -Y H +X W, texel = m 2^(e - 136); or .pfm, either byte order, bottom row first), bound as a 3-component
@@ -115,6 +115,9 @@ int         terra_amd_probe_visibility ( const void*, const void*, size_t, int, 
 typedef struct { float position[3]; float max_distance; } NearestQuery;
 typedef struct { float distance; int object; unsigned triangle; unsigned feature; float point[3]; float side; } NearestAnswer;
 int         terra_amd_nearest ( HTerraScene, const void*, size_t, void* ) __attribute__ ( ( weak ) );
+/* --signed: the crossing counts of include/terra_amd.h "Multi-hit ray queries"; a ray is a TerraAmdRay */
+typedef struct { float origin[3]; float tmax; float direction[3]; float reserved; } QueryRay;
+int         terra_amd_count_hits ( HTerraScene, const void*, size_t, uint32_t* ) __attribute__ ( ( weak ) );
 /* --camera-model: non-NULL = every render call and its AOV call go through the lens door */
 static const Lens* g_lens = NULL;
 static void render_rect ( const TerraCamera* cam, HTerraScene scene, const TerraFramebuffer* fb, size_t x, size_t y, size_t w, size_t h ) {
@@ -669,6 +672,8 @@ static const char* kHelp =
     "           --passes pass along each into one frame, terra_amd_sh_project reduces it. The camera flags, --aov, --denoise*, --adaptive, --frames and --gpus are ignored.\n"
     "  --distance-field NXxNYxNZ PATH (libterra_amd.so only): also writes the scene's distance field as a grey float image (.pfm), NX wide and NY * NZ high: the distance\n"
     "           from the centre of each of NX x NY x NZ cells over the scene's bounding box to the nearest surface (terra_amd_nearest), slice iz in rows iz * NY ..\n"
+    "           --signed: the distance is negated in the cells that lie inside the scene's closed surfaces -- three rays to infinity per cell along (0.48, 0.64, 0.60),\n"
+    "           (-0.60, 0.48, 0.64) and (0.64, -0.60, 0.48), terra_amd_count_hits on each, inside where at least two of the three counts are odd.\n"
     "  --probe-visibility PATH [--probe-texels M] (with --bake-probes): also writes the probes' visibility maps as a float RGB image (.pfm / .hdr) M * M wide (M 1 .. 16,\n"
     "           default 8) and NX * NY * NZ high: pixel (t, p) is texel t = j * M + i of probe p as (sum of w, sum of w * d, sum of w * d * d), d the distance\n"
     "           terra_amd_intersect finds along the same cell-centre rays, w = cos^64 about the texel's octahedral direction (terra_amd_probe_visibility,\n"
@@ -691,6 +696,7 @@ int main ( int argc, char** argv ) {
     int bake = 0, atlas_w = 256, atlas_h = 256, bake_dilate = 2; float bake_margin = 0.5f;      /* --bake-lightmap */
     int probes_on = 0, probe_n[3] = { 1, 1, 1 }, probe_cells = 16;      /* --bake-probes */
     int field_n[3] = { 0, 0, 0 }; const char* field_path = NULL;        /* --distance-field */
+    int field_signed = 0;                                               /* --signed */
     const char* visibility_path = NULL; int probe_texels = 8;      /* --probe-visibility */
     float fov = 45.f, exposure = 1.f, gamma = 2.2f, jitter = 0.f;
     unsigned long long seed = 0;
@@ -752,6 +758,7 @@ int main ( int argc, char** argv ) {
             field_path = NEXT();
             if ( !*field_path || !strncmp ( field_path, "--", 2 ) ) { fprintf ( stderr, "terra_headless: --distance-field NXxNYxNZ PATH: no path\n" ); return 64; }
         }
+        else if ( !strcmp ( a, "--signed" ) ) field_signed = 1;
         else if ( !strcmp ( a, "--probe-visibility" ) ) visibility_path = NEXT();
         else if ( !strcmp ( a, "--probe-texels" ) ) { probe_texels = atoi ( NEXT() ); if ( probe_texels < 1 || probe_texels > 16 ) { fprintf ( stderr, "terra_headless: --probe-texels 1 .. 16\n" ); return 64; } }
         else if ( !strcmp ( a, "--probe-cells" ) ) { probe_cells = atoi ( NEXT() ); if ( probe_cells < 1 || probe_cells > 64 ) { fprintf ( stderr, "terra_headless: --probe-cells 1 .. 64\n" ); return 64; } }
@@ -781,6 +788,8 @@ int main ( int argc, char** argv ) {
         if ( !env_tex.pixels ) { fprintf ( stderr, "terra_headless: %s: cannot make a texture of it\n", env_path ); return 65; }
         env_tex.filter = kTerraFilterPoint; env_tex.address_mode = kTerraTextureAddressWrap;
     }
+    if ( field_signed && !field_path ) { fprintf ( stderr, "terra_headless: --signed goes with --distance-field NXxNYxNZ PATH\n" ); return 64; }
+    if ( field_signed && !terra_amd_count_hits ) { fprintf ( stderr, "terra_headless: --signed needs a libterra_amd.so with terra_amd_count_hits\n" ); return 64; }
     Model m; memset ( &m, 0, sizeof m );
     if ( !load_obj ( &m, argv[1] ) ) { fprintf ( stderr, "terra_headless: no faces in %s\n", argv[1] ); return 66; }
     FILE* dump = dump_path ? fopen ( dump_path, "w" ) : NULL;
@@ -835,6 +844,21 @@ int main ( int argc, char** argv ) {
         }
         if ( !rc ) rc = terra_amd_nearest ( scene, queries, n, answers );
         if ( rc ) { fprintf ( stderr, "terra_headless: %s\n", terra_amd_last_error && *terra_amd_last_error() ? terra_amd_last_error() : "the distance field failed" ); return 70; }
+        if ( field_signed ) {          /* the crossing sign: three rays to infinity per cell, inside where at least two of the three counts are odd */
+            static const float dirs[3][3] = { { 0.48f, 0.64f, 0.60f }, { -0.60f, 0.48f, 0.64f }, { 0.64f, -0.60f, 0.48f } };
+            QueryRay* rays = aligned_alloc ( 16, 3 * n * sizeof ( QueryRay ) ); uint32_t* counts = malloc ( 3 * n * sizeof ( uint32_t ) );
+            if ( !rays || !counts ) { fprintf ( stderr, "terra_headless: out of memory\n" ); return 71; }
+            for ( int v = 0; v < 3; ++v ) for ( size_t k = 0; k < n; ++k ) {
+                QueryRay* r = &rays[ ( size_t ) v * n + k];
+                for ( int a = 0; a < 3; ++a ) { r->origin[a] = queries[k].position[a]; r->direction[a] = dirs[v][a]; }
+                r->tmax = INFINITY; r->reserved = 0.f;
+            }
+            if ( terra_amd_count_hits ( scene, rays, 3 * n, counts ) ) { fprintf ( stderr, "terra_headless: %s\n", terra_amd_last_error && *terra_amd_last_error() ? terra_amd_last_error() : "the crossing counts failed" ); return 70; }
+            size_t inside = 0;
+            for ( size_t k = 0; k < n; ++k ) if ( ( counts[k] & 1u ) + ( counts[n + k] & 1u ) + ( counts[2 * n + k] & 1u ) >= 2u ) { answers[k].distance = -answers[k].distance; ++inside; }
+            printf ( "%s: signed by crossings: %zu of %zu cells inside\n", argv[1], inside, n );
+            free ( rays ); free ( counts );
+        }
         for ( size_t k = 0; k < n; ++k ) field.pixels[k] = terra_f3_set ( answers[k].distance, answers[k].distance, answers[k].distance );          /* slice iz = rows iz * NY .. of the image */
         if ( !write_pfm ( field_path, &field ) ) { fprintf ( stderr, "terra_headless: cannot write %s\n", field_path ); return 73; }
         printf ( "%s: distance field %s (%dx%dx%d cells from %g %g %g, spacing %g %g %g)\n", argv[1], field_path, field_n[0], field_n[1], field_n[2], ( double ) lo[0], ( double ) lo[1], ( double ) lo[2], ( double ) sp[0], ( double ) sp[1], ( double ) sp[2] );

@@ -1181,6 +1181,53 @@ int terra_amd_nearest ( HTerraScene scene, const TerraAmdNearestQuery* queries, 
 /* Test plumbing: terra_amd_nearest through the brute-force kernel, whatever tree the scene has. */
 int terra_amd_unit_nearest_brute ( HTerraScene scene, const TerraAmdNearestQuery* queries, size_t n, TerraAmdNearest* out );
 
+/* ---- Multi-hit ray queries: the first K triangles along a client's rays, and the number of triangles a ray crosses ---------------------------------------------
+   The ray queries answer "the closest triangle" and "is anything in the way". These answer what lies behind the first surface: picking through glass or foliage,
+   thickness and x-ray measurements, layered transparency, entry / exit pairs of a solid, and the crossing count that tells inside from outside of a closed surface --
+   in ONE launch, with the library's tie rule, instead of re-shooting from point + epsilon once per layer. Per ray (TerraAmdRay, unchanged), independently of every
+   other ray and of which accelerator answers:
+   The ray is traced as given.  No origin offset; direction need not be normalised, depths are in units of its length. The effective limit L is the ray queries':
+     L = tmax if tmax < FLT_MAX, else FLT_MAX: +inf, FLT_MAX and NaN all mean "no limit". tmax < 0: nothing counts.
+   Inactive rays.  A ray whose direction is exactly (0, 0, 0), or whose origin or direction has a component that is not finite, is inactive: nothing counts, and
+     that is decided before any traversal, in every kernel.
+   Which triangles count.  ANY triangle of the scene that the watertight test (its own rule and arithmetic, unchanged) accepts at a depth <= L (a NaN depth is not
+     <= L). This is NOT restricted to what the reference traversal reaches, as the closest hit of the ray queries is: inside the containment range the two sets are
+     the same (every triangle the test accepts lies in boxes the reference's slab tests pass), outside it -- reachability mode -- they can differ by the rare
+     triangle the reference's own slab test misses.
+   Order.  By (depth, rank), lexicographically. Depth is compared as floats, so -0 equals +0; rank is the triangle's reference leaf-visit rank
+     (terra_amd_scene_leaf_ranks), a permutation of the triangles. Exactly duplicated triangles, and coplanar triangles at one depth, are separate hits.
+   terra_amd_intersect_all*.  K = 1 .. TERRA_AMD_MAX_HITS. hits[i * K + j], j = 0 .. K - 1, are the first K counting triangles of ray i in that order, as TerraAmdHit
+     records with the layout and rules of terra_amd_intersect: t = the depth as the watertight test reports it, point = origin + direction * t in float32, multiply
+     then add, no fused multiply-add, object / triangle as there, reserved and reserved2 0. Records past the last hit are the ray queries' miss record (t = FLT_MAX,
+     object = -1, triangle = 0, point = (FLT_MAX, FLT_MAX, FLT_MAX)). counts[i] (optional: counts may be NULL) = the hit records written, min(K, total). A ray with
+     more than K counting triangles loses the far ones -- a tie that straddles position K included: rank alone decides which of the equal depths stay.
+   terra_amd_count_hits*.  counts[i] = the total number of counting triangles, uncapped. Along a ray to infinity its parity tells inside (odd) from outside (even) of
+     a closed surface. Limits: the watertight test guarantees that no ray leaks between two triangles that share an edge, NOT that exactly one of them accepts it --
+     a ray through a shared edge or vertex may be counted by both neighbours (vote over several directions, as terra_headless --signed does); an open mesh has no
+     inside; coincident duplicated surfaces count twice.
+   Property.  For active rays on a scene inside the containment range (TerraAmdTraversalInfo: not reachability mode), origins within camera_limit:
+     terra_amd_intersect_all with K = 1 writes terra_amd_intersect's records bit for bit, and count_hits > 0 exactly where terra_amd_occluded is 1.
+   Traversal.  A scene whose commit built a fast tree (TerraAmdTraversalInfo::fast_tree, reachability scenes included) is answered by a walk of that tree, with no
+     replay of the reference's reachability; every other scene by a brute force over all triangles, O(n * triangles): a large scene held in tree mode 0 wants
+     terra_amd_set_tree_mode(scene, 1) before such calls. Both give the same bits. The fast tree's boxes are conservative for origins within
+     TerraAmdTraversalInfo::camera_limit on every axis: the host forms give the tree up for a batch with an active origin further out (the brute force answers,
+     same rule); the device forms cannot look at rays in HBM without a synchronise and walk the tree whatever the origins: keep them within camera_limit.
+   Calls.  As the ray queries: n == 0 succeeds and launches nothing; n > 2^31 - 1, a NULL ray or result buffer with n > 0 (hits for intersect_all, counts for
+     count_hits), or K outside 1 .. TERRA_AMD_MAX_HITS is kTerraAmdErrBadArgument, an uncommitted scene kTerraAmdErrNotCommitted (terra_amd_last_error() has the
+     message); nothing is launched or written then. Nothing is recorded in terra_amd_get_stats(), no framebuffer is touched, a scene committed for several devices
+     answers on its primary device, no atomics: the same inputs give the same bits. */
+#define TERRA_AMD_MAX_HITS 8
+/* d_rays: n TerraAmdRay, d_hits: n * k TerraAmdHit, d_counts: n uint32_t (NULL allowed in intersect_all), all in HBM, 16-byte aligned (4-byte for d_counts);
+   asynchronous on `stream`: any scratch the call needs is allocated and freed in stream order, nothing synchronises. */
+int terra_amd_intersect_all_device ( HTerraScene scene, const void* d_rays, size_t n, size_t k, void* d_hits, void* d_counts, void* stream );
+int terra_amd_count_hits_device    ( HTerraScene scene, const void* d_rays, size_t n, void* d_counts, void* stream );
+/* The same on host buffers: the rays are uploaded, the kernel runs, the answers are downloaded; synchronous. */
+int terra_amd_intersect_all ( HTerraScene scene, const TerraAmdRay* rays, size_t n, size_t k, TerraAmdHit* hits, uint32_t* counts );
+int terra_amd_count_hits    ( HTerraScene scene, const TerraAmdRay* rays, size_t n, uint32_t* counts );
+/* Test plumbing: the two host forms through the brute-force kernel, whatever tree the scene has. */
+int terra_amd_unit_intersect_all_brute ( HTerraScene scene, const TerraAmdRay* rays, size_t n, size_t k, TerraAmdHit* hits, uint32_t* counts );
+int terra_amd_unit_count_hits_brute    ( HTerraScene scene, const TerraAmdRay* rays, size_t n, uint32_t* counts );
+
 /* Tile-sharded form for one-process-per-GPU rendering (the reference shards
    the same way over CPU threads: satellite/src/Renderer.cpp:316-350): the
    rectangle is cut into tile_size x tile_size tiles numbered row-major and this

@@ -373,6 +373,17 @@ NEAREST_SIGNATURES = {
     "terra_amd_unit_nearest_brute": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
+# ... and of the multi-hit ray queries (include/terra_amd.h "Multi-hit ray queries"): rays and hits are RAY_DTYPE / HIT_DTYPE records, counts uint32
+MAX_HITS = 8
+MULTI_HIT_SIGNATURES = {
+    "terra_amd_intersect_all_device": (c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p]),
+    "terra_amd_intersect_all": (c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p]),
+    "terra_amd_count_hits_device": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "terra_amd_count_hits": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
+    "terra_amd_unit_intersect_all_brute": (c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p]),
+    "terra_amd_unit_count_hits_brute": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
+}
+
 # entry points of include/Terra.h + include/TerraPresets.h, name -> (restype, argtypes)
 API_SIGNATURES = {
     "scene_create": (c_void_p, []),

@@ -19,7 +19,7 @@ OUT = HERE / "libterra_amd.so"
 # (source, object name, extra flags): render_kernels.hip is compiled once per TERRA_TU value -- its kernel instances per template MODE (0 - 3), and the ray-sourced
 # instances of each MODE (4 - 7: primary rays read from a client's buffer), the lens instances (8 - 11: primary rays made from a camera model) and the point instances
 # (12 - 15: primary rays drawn about a client's points) -- so that the units build in parallel; aov_kernels.hip has a ray-sourced unit, a lens unit and a point unit too; bake_kernels.hip (lightmap baking) and
-# probe_kernels.hip (probe harmonics) are one unit each, and so is nearest_kernels.hip (nearest-surface queries)
+# probe_kernels.hip (probe harmonics) are one unit each, and so are nearest_kernels.hip (nearest-surface queries) and multi_hit_kernels.hip (multi-hit ray queries)
 SOURCES = [("scene_host.cpp", "scene_host.cpp", []), ("tree_build.cpp", "tree_build.cpp", []), ("multi_gpu.cpp", "multi_gpu.cpp", []),
            ("render_kernels.hip", "render_kernels.tu0.hip", ["-DTERRA_TU=0"]), ("render_kernels.hip", "render_kernels.tu1.hip", ["-DTERRA_TU=1"]),
            ("render_kernels.hip", "render_kernels.tu2.hip", ["-DTERRA_TU=2"]), ("render_kernels.hip", "render_kernels.tu3.hip", ["-DTERRA_TU=3"]),
@@ -34,7 +34,8 @@ SOURCES = [("scene_host.cpp", "scene_host.cpp", []), ("tree_build.cpp", "tree_bu
            ("aov_kernels.hip", "aov_kernels.tu8.hip", ["-DTERRA_TU=8"]), ("aov_kernels.hip", "aov_kernels.tu12.hip", ["-DTERRA_TU=12"]),
            ("denoise_kernels.hip", "denoise_kernels.hip", []),
            ("variance_kernels.hip", "variance_kernels.hip", []), ("temporal_kernels.hip", "temporal_kernels.hip", []), ("query_kernels.hip", "query_kernels.hip", []),
-           ("bake_kernels.hip", "bake_kernels.hip", []), ("probe_kernels.hip", "probe_kernels.hip", []), ("nearest_kernels.hip", "nearest_kernels.hip", [])]
+           ("bake_kernels.hip", "bake_kernels.hip", []), ("probe_kernels.hip", "probe_kernels.hip", []), ("nearest_kernels.hip", "nearest_kernels.hip", []),
+           ("multi_hit_kernels.hip", "multi_hit_kernels.hip", [])]
 HEADERS = ["dev_types.h", "dev_math.h", "rng.h", "trace_device.h", "trace_math.h", "exact_div.h", "exact_sqrt.h", "trace_geometry.h", "traverse_ref.h", "traverse_fast.h", "shading_device.h",
            "integrators_device.h", "sampling_device.h", "denoise_device.h", "kernels.h", "launch_plan.h", "empty_proof.h", "tree_build.h", "multi_gpu.h"]
 ARCH = os.environ.get("TERRA_AMD_ARCH", "gfx950")

@@ -100,6 +100,15 @@ struct DevNearestParams {
 };
 hipError_t terra_launch_nearest ( DevNearestParams p, const void* queries, size_t n, void* out, hipStream_t stream );
 
+// multi-hit ray queries (multi_hit_kernels.hip; include/terra_amd.h "Multi-hit ray queries"): rays = n TerraAmdRay; k = 1 .. 8: hits = n * k TerraAmdHit, counts = n
+// uint32 or nullptr; k = 0: the crossing count, counts = n uint32 and hits is not looked at. All in HBM. fast: the walk of the fast tree (stack_depth / spill_cap as
+// launch_plan.h terra_plan_fast_tree made them; MODE 2 and 3 scenes alike), otherwise the brute force over scene.tris
+struct DevMultiHitParams {
+    DevScene scene;
+    uint32_t fast, stack_depth, spill_cap;
+};
+hipError_t terra_launch_multi_hit ( DevMultiHitParams p, const void* rays, size_t n, uint32_t k, void* hits, void* counts, hipStream_t stream );
+
 // lightmap baking (bake_kernels.hip; include/terra_amd.h "Lightmap baking"): all pointers are device pointers; the launchers take their scratch (the coverage
 // keys; the dilation's second copy) from the stream's pool and give it back on the stream
 struct DevAtlas {

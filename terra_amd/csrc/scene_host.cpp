@@ -2160,6 +2160,80 @@ extern "C" int terra_amd_nearest_device ( HTerraScene h, const void* d_queries, 
 extern "C" int terra_amd_nearest ( HTerraScene h, const TerraAmdNearestQuery* queries, size_t n, TerraAmdNearest* out ) { return nearest_host ( h, queries, n, out, false, "terra_amd_nearest" ); }
 extern "C" int terra_amd_unit_nearest_brute ( HTerraScene h, const TerraAmdNearestQuery* queries, size_t n, TerraAmdNearest* out ) { return nearest_host ( h, queries, n, out, true, "terra_amd_unit_nearest_brute" ); }
 
+// ---- multi-hit ray queries (multi_hit_kernels.hip) -------------------------------------
+// the one check of the six entry points: the scene is committed, then the arguments -- n fits the kernel's 32-bit index, K is a list length the kernels have (the
+// counting forms have no K; their one result buffer is `counts`), the buffers are there. The arguments are judged before the device is looked for (scene_check, by
+// the callers, once n > 0): a bad call is refused the same way on a machine without one.
+static int multi_hit_check ( Scene* s, const void* rays, size_t n, size_t k, bool counting, const void* out, const char* what ) {
+    if ( !s->committed ) return scene_check ( s );
+    if ( n > ( size_t ) 0x7fffffff ) return fail ( kTerraAmdErrBadArgument, "%s: %zu rays in one call, at most 2^31 - 1", what, n );
+    if ( !counting && ( k < 1 || k > TERRA_AMD_MAX_HITS ) ) return fail ( kTerraAmdErrBadArgument, "%s: %zu hits per ray, 1 to %d", what, k, TERRA_AMD_MAX_HITS );
+    if ( n > 0 && ( !rays || !out ) ) return fail ( kTerraAmdErrBadArgument, "%s: null ray or result buffer", what );
+    return 0;
+}
+// The fast tree wherever the commit built one, reachability scenes included and without their replay -- the rule counts every triangle the watertight test accepts,
+// which is what the fast tree finds --, unless the caller gives it up (walk = false: a host batch with an origin beyond camera_limit, or the test plumbing);
+// otherwise the brute force over the soup, whose DevTri::pad is the rank in every scene (flatten). The plan is the ray queries': the walk's weaker cull pushes more
+// entries, but fast_max_stack bounds the stack whatever is culled (tree_build.cpp fastbvh::widen).
+static int launch_multi_hit ( Scene* s, const void* d_rays, size_t n, uint32_t k, void* d_hits, void* d_counts, bool walk, hipStream_t stream ) {
+    const Scene::Replica& r = primary ( s );
+    DevRenderParams rp;
+    memset ( &rp, 0, sizeof rp );
+    rp.scene = r.dev;
+    DevMultiHitParams p;
+    memset ( &p, 0, sizeof p );
+    p.scene = r.dev;
+    if ( walk && s->tree.use_fast && r.dev.fast_nodes_h && r.dev.fast_tris && r.dev.n_tris >= 2 ) { terra_plan_fast_tree ( rp ); apply_stack_hooks ( s, rp ); p.fast = 1; }
+    p.stack_depth = rp.stack_depth; p.spill_cap = rp.spill_cap;
+    p.scene.sincos24 = nullptr;
+    const hipError_t e = terra_launch_multi_hit ( p, d_rays, n, k, d_hits, d_counts, stream );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "multi-hit ray query launch: %s", hipGetErrorString ( e ) );
+    return 0;
+}
+static int multi_hit_device ( HTerraScene h, const void* d_rays, size_t n, size_t k, bool counting, void* d_hits, void* d_counts, void* stream, const char* what ) {
+    Scene* s = S ( h );
+    if ( int rc = multi_hit_check ( s, d_rays, n, k, counting, counting ? d_counts : d_hits, what ) ) return rc;
+    if ( n == 0 ) return 0;
+    if ( int rc = scene_check ( s ) ) return rc;
+    HIP_TRY ( hipSetDevice ( primary ( s ).device ), kTerraAmdErrNoDevice );
+    return launch_multi_hit ( s, d_rays, n, counting ? 0u : ( uint32_t ) k, d_hits, d_counts, true, ( hipStream_t ) stream );
+}
+// host buffers through the staging path of the ray queries: upload, query, download; synchronous. An ACTIVE ray (the rule's: a finite origin and direction, not the
+// zero direction) that starts beyond camera_limit sends the batch to the brute force, which answers by the same rule without the tree's range contract.
+static int multi_hit_host ( HTerraScene h, const TerraAmdRay* rays, size_t n, size_t k, bool counting, TerraAmdHit* hits, uint32_t* counts, bool brute, const char* what ) {
+    Scene* s = S ( h );
+    if ( int rc = multi_hit_check ( s, rays, n, k, counting, counting ? ( const void* ) counts : ( const void* ) hits, what ) ) return rc;
+    if ( n == 0 ) return 0;
+    if ( int rc = scene_check ( s ) ) return rc;
+    HIP_TRY ( hipSetDevice ( primary ( s ).device ), kTerraAmdErrNoDevice );
+    const float limit = shortcut_limit ( s->tree );
+    bool walk = !brute;
+    for ( size_t i = 0; i < n && walk; ++i ) {
+        const float* o = rays[i].origin; const float* d = rays[i].direction;
+        const bool active = std::isfinite ( o[0] ) && std::isfinite ( o[1] ) && std::isfinite ( o[2] ) && std::isfinite ( d[0] ) && std::isfinite ( d[1] ) && std::isfinite ( d[2] ) && ! ( d[0] == 0.f && d[1] == 0.f && d[2] == 0.f );
+        walk = !active || ( fabsf ( o[0] ) <= limit && fabsf ( o[1] ) <= limit && fabsf ( o[2] ) <= limit );
+    }
+    const size_t hit_bytes = counting ? 0 : n * k * sizeof ( TerraAmdHit ), count_bytes = ( counting || counts ) ? n * sizeof ( uint32_t ) : 0;
+    FrameCopy c;
+    hipError_t e = c.up ( 0, rays, n * sizeof ( TerraAmdRay ) );
+    if ( e == hipSuccess && hit_bytes ) e = c.up ( 1, nullptr, hit_bytes );
+    if ( e == hipSuccess && count_bytes ) e = c.up ( 2, nullptr, count_bytes );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "%s upload: %s", what, hipGetErrorString ( e ) );
+    if ( int rc = launch_multi_hit ( s, c.d[0], n, counting ? 0u : ( uint32_t ) k, hit_bytes ? c.d[1] : nullptr, count_bytes ? c.d[2] : nullptr, walk, nullptr ) ) return rc;
+    if ( hit_bytes ) e = c.down ( 1, hits, hit_bytes );
+    if ( e == hipSuccess && count_bytes ) e = c.down ( 2, counts, count_bytes );
+    if ( e != hipSuccess ) return fail ( kTerraAmdErrLaunch, "%s download: %s", what, hipGetErrorString ( e ) );
+    return 0;
+}
+extern "C" int terra_amd_intersect_all_device ( HTerraScene h, const void* d_rays, size_t n, size_t k, void* d_hits, void* d_counts, void* stream ) {
+    return multi_hit_device ( h, d_rays, n, k, false, d_hits, d_counts, stream, "terra_amd_intersect_all_device" );
+}
+extern "C" int terra_amd_count_hits_device ( HTerraScene h, const void* d_rays, size_t n, void* d_counts, void* stream ) { return multi_hit_device ( h, d_rays, n, 0, true, nullptr, d_counts, stream, "terra_amd_count_hits_device" ); }
+extern "C" int terra_amd_intersect_all ( HTerraScene h, const TerraAmdRay* rays, size_t n, size_t k, TerraAmdHit* hits, uint32_t* counts ) { return multi_hit_host ( h, rays, n, k, false, hits, counts, false, "terra_amd_intersect_all" ); }
+extern "C" int terra_amd_count_hits ( HTerraScene h, const TerraAmdRay* rays, size_t n, uint32_t* counts ) { return multi_hit_host ( h, rays, n, 0, true, nullptr, counts, false, "terra_amd_count_hits" ); }
+extern "C" int terra_amd_unit_intersect_all_brute ( HTerraScene h, const TerraAmdRay* rays, size_t n, size_t k, TerraAmdHit* hits, uint32_t* counts ) { return multi_hit_host ( h, rays, n, k, false, hits, counts, true, "terra_amd_unit_intersect_all_brute" ); }
+extern "C" int terra_amd_unit_count_hits_brute ( HTerraScene h, const TerraAmdRay* rays, size_t n, uint32_t* counts ) { return multi_hit_host ( h, rays, n, 0, true, nullptr, counts, true, "terra_amd_unit_count_hits_brute" ); }
+
 // ---- denoiser (denoise_kernels.hip) ----------------------------------------------------
 extern "C" int terra_amd_denoise_device ( HTerraScene h, const void* d_results, const void* d_aov, size_t fb_w, size_t fb_h, size_t x, size_t y, size_t w, size_t hgt, int iterations,
                                           void* d_radiance, void* d_pixels, void* stream ) {

@@ -159,6 +159,7 @@ _EXTRA = {
     **api.PROBE_VISIBILITY_SIGNATURES,
     **api.EXACT_SQRT_SIGNATURES,
     **api.NEAREST_SIGNATURES,
+    **api.MULTI_HIT_SIGNATURES,
 }
 
 
@@ -523,18 +524,72 @@ def distance_field_points(origin, spacing, dims, max_distance=float("inf")) -> n
 
 def distance_field(lib, scene, origin, spacing, dims, max_distance=float("inf"), signed=False):
     """The scene's distance field on a regular grid -> float32 [nz, ny, nx] in HBM: the `distance` of nearest() at the cell centres of distance_field_points
-    (FLT_MAX where nothing lies within max_distance). signed: the distance times `side` where the closest feature is a face (feature == 0), left positive at edges
-    and vertices -- a CRUDE sign: it follows the winning triangle's winding, says nothing true next to an edge or a vertex, and is no inside / outside test of an
-    open or inconsistently wound scene (angle-weighted pseudonormals are not built)."""
+    (FLT_MAX where nothing lies within max_distance). signed=True: the distance times `side` where the closest feature is a face (feature == 0), left positive at
+    edges and vertices -- a CRUDE sign: it follows the winning triangle's winding, says nothing true next to an edge or a vertex, and is no inside / outside test of
+    an open or inconsistently wound scene (angle-weighted pseudonormals are not built). signed="crossings": the distance negated where inside() says 1 -- the
+    crossing-count sign, which needs a closed surface and no winding."""
     import torch
     q = distance_field_points(origin, spacing, dims, max_distance)
-    out = nearest(lib, scene, torch.from_numpy(q.view(np.float32).reshape(-1, 4)).cuda())
+    queries = torch.from_numpy(q.view(np.float32).reshape(-1, 4)).cuda()
+    out = nearest(lib, scene, queries)
     dist = out[:, 0]
-    if signed:
+    if isinstance(signed, str):
+        if signed != "crossings":
+            raise TerraAmdError(f"distance_field: signed={signed!r}; False, True or \"crossings\"")
+        dist = torch.where(inside(lib, scene, queries[:, :3].contiguous()) == 1, -dist, dist)
+    elif signed:
         feature = out[:, 3].view(torch.int32)
         side = out[:, 7]
         dist = torch.where((feature == 0) & (side != 0), dist * side, dist)
     return dist.reshape(q.shape).contiguous()
+
+
+# ---------------------------------------------------------------------------
+# multi-hit ray queries (include/terra_amd.h "Multi-hit ray queries")
+# ---------------------------------------------------------------------------
+
+def intersect_all(lib, scene, rays, k):
+    """terra_amd_intersect_all_device on rays (float32 [n, 8] in HBM: TerraAmdRay records) -> (hits float32 [n, k, 8]: per ray its first k hits by (depth, rank) as
+    TerraAmdHit records, miss records after the last; counts int32 [n]: the hit records written). 1 <= k <= api.MAX_HITS. Queued on the current torch stream;
+    nothing is copied to the host."""
+    torch, stream = _query_rays(rays)
+    k = int(k)
+    if not 1 <= k <= api.MAX_HITS:
+        raise TerraAmdError(f"intersect_all: k = {k}, 1 to {api.MAX_HITS}")
+    n = rays.shape[0]
+    hits = torch.empty((n, k, 8), dtype=torch.float32, device=rays.device)
+    counts = torch.empty(n, dtype=torch.int32, device=rays.device)
+    check(lib.intersect_all_device(scene, rays.data_ptr(), n, k, hits.data_ptr(), counts.data_ptr(), stream), "terra_amd_intersect_all_device")
+    return hits, counts
+
+
+def count_hits(lib, scene, rays):
+    """terra_amd_count_hits_device on rays (as intersect) -> int32 [n]: how many triangles each ray crosses within its tmax. Queued on the current torch stream."""
+    torch, stream = _query_rays(rays)
+    out = torch.empty(rays.shape[0], dtype=torch.int32, device=rays.device)
+    check(lib.count_hits_device(scene, rays.data_ptr(), rays.shape[0], out.data_ptr(), stream), "terra_amd_count_hits_device")
+    return out
+
+
+# the three directions of inside(), used as float32: cyclic shifts of (0.48, 0.64, 0.60) with one sign turned, of unit length (48^2 + 64^2 + 60^2 = 100^2), none
+# along an axis or a diagonal of the usual modelling grids
+INSIDE_DIRECTIONS = ((0.48, 0.64, 0.60), (-0.60, 0.48, 0.64), (0.64, -0.60, 0.48))
+
+
+def inside(lib, scene, points):
+    """Which points (float32 [n, 3] in HBM) lie inside the scene's closed surfaces -> int32 [n], 1 = inside: three rays to infinity per point along
+    INSIDE_DIRECTIONS, count_hits on each, 1 where at least two of the three counts are odd (one ray through a shared edge or vertex may count both neighbours;
+    two of three doing so is what the vote leaves). Needs a closed surface; an open mesh has no inside. Queued on the current torch stream."""
+    import torch
+    if not (isinstance(points, torch.Tensor) and points.is_cuda and points.dtype == torch.float32 and points.dim() == 2 and points.shape[1] == 3):
+        raise TerraAmdError("inside takes a float32 tensor [n, 3] on the scene's device")
+    n = points.shape[0]
+    rays = torch.zeros((3, n, 8), dtype=torch.float32, device=points.device)
+    rays[:, :, 0:3] = points[None, :, :]
+    rays[:, :, 3] = float("inf")
+    rays[:, :, 4:7] = torch.tensor(INSIDE_DIRECTIONS, dtype=torch.float32, device=points.device)[:, None, :]
+    odd = count_hits(lib, scene, rays.reshape(3 * n, 8)).reshape(3, n) & 1
+    return (odd.sum(dim=0) >= 2).to(torch.int32)
 
 
 def probe_clearance(lib, scene, probes):

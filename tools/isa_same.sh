@@ -1,7 +1,7 @@
 #!/bin/bash
 # Do two source trees compile to the same device code? (dev tool, no GPU needed)
 # Compiles, device-only to assembly, every .hip unit of both trees -- the sixteen TERRA_TU units of render_kernels.hip (0 - 3 camera, 4 - 7 ray-sourced, 8 - 11 lens, 12 - 15 point), unit_kernels.hip,
-# tree_build_device.hip, aov_kernels.hip with its ray-sourced, lens and point units (TERRA_TU 4, 8, 12), denoise_kernels.hip, variance_kernels.hip, temporal_kernels.hip, query_kernels.hip, bake_kernels.hip, probe_kernels.hip and nearest_kernels.hip -- with exactly the FLAGS of this tree's
+# tree_build_device.hip, aov_kernels.hip with its ray-sourced, lens and point units (TERRA_TU 4, 8, 12), denoise_kernels.hip, variance_kernels.hip, temporal_kernels.hip, query_kernels.hip, bake_kernels.hip, probe_kernels.hip, nearest_kernels.hip and multi_hit_kernels.hip -- with exactly the FLAGS of this tree's
 # terra_amd/build.py (plus any extra -D given), strips what is not code -- comment lines, .file/.ident, and the lines naming the per-compilation
 # __hip_cuid_<hash> symbol, trailing comments and the number a function's labels carry for its place in the unit (.LBB<n>_, .Lfunc_end<n>: a function keeps
 # its body when another one leaves the unit) -- and reports per unit "identical" or the symbols whose bodies differ. A unit that only one tree has is reported as such and
@@ -20,7 +20,7 @@ HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS=$(python3 -c "import runpy, sys; print(' '.join(runpy.run_path(sys.argv[1])['FLAGS']))" "$HERE/terra_amd/build.py") || exit 2
 key() { printf '%s\n' "$1" "$HIPCC" "$($HIPCC --version 2>/dev/null | head -n 1)" "$FLAGS" "$2" | md5sum | cut -c1-16; }
 DA=$S/$(key "$A" "$*"); DB=$S/$(key "$B" "$*")
-UNITS="render_kernels.tu0 render_kernels.tu1 render_kernels.tu2 render_kernels.tu3 render_kernels.tu4 render_kernels.tu5 render_kernels.tu6 render_kernels.tu7 render_kernels.tu8 render_kernels.tu9 render_kernels.tu10 render_kernels.tu11 render_kernels.tu12 render_kernels.tu13 render_kernels.tu14 render_kernels.tu15 unit_kernels tree_build_device aov_kernels aov_kernels.tu4 aov_kernels.tu8 aov_kernels.tu12 denoise_kernels variance_kernels temporal_kernels query_kernels bake_kernels probe_kernels nearest_kernels"
+UNITS="render_kernels.tu0 render_kernels.tu1 render_kernels.tu2 render_kernels.tu3 render_kernels.tu4 render_kernels.tu5 render_kernels.tu6 render_kernels.tu7 render_kernels.tu8 render_kernels.tu9 render_kernels.tu10 render_kernels.tu11 render_kernels.tu12 render_kernels.tu13 render_kernels.tu14 render_kernels.tu15 unit_kernels tree_build_device aov_kernels aov_kernels.tu4 aov_kernels.tu8 aov_kernels.tu12 denoise_kernels variance_kernels temporal_kernels query_kernels bake_kernels probe_kernels nearest_kernels multi_hit_kernels"
 JOBS=$(nproc); [ "$JOBS" -gt 16 ] && JOBS=16
 mkdir -p "$DA" "$DB"
 

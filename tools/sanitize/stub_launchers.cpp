@@ -49,6 +49,7 @@ hipError_t terra_launch_denoise_variance ( const void*, const void*, const void*
 hipError_t terra_launch_temporal_reproject ( const DevTemporalParams&, const void*, const void*, const void*, void*, void*, void*, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_launch_query ( DevQueryParams, const void*, size_t, void*, bool, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_launch_nearest ( DevNearestParams, const void*, size_t, void*, hipStream_t ) { return hipErrorNoDevice; }
+hipError_t terra_launch_multi_hit ( DevMultiHitParams, const void*, size_t, uint32_t, void*, void*, hipStream_t ) { return hipErrorNoDevice; }
 hipError_t terra_unit_texture_sample ( const DevTexture*, int, const float*, float* ) { return hipErrorNoDevice; }
 hipError_t terra_unit_texture_latlong ( const DevTexture*, int, const float*, float* ) { return hipErrorNoDevice; }
 hipError_t terra_launch_atlas_points ( const DevScene&, const DevAtlas&, const float*, void*, void*, hipStream_t ) { return hipErrorNoDevice; }
